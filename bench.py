@@ -17,9 +17,18 @@ for N > 1 one RCCL all-gather of the final theta [256,85] per rank over xGMI.  I
 reprojection losses of every stage (one library call) and, for N > 1, ONE all-reduce of the [3,4] block of
 (kp numerator, kp count, -, mesh sum).
 
-Rank 0 prints ONE JSON line.  The top level is the HEADLINE (fp32, batch 256 / GPU).  At N == 1 the default run then
-measures the other single-GPU configurations of BASELINE.json in short legs (10 steps, no sustain loop) and reports them as
-sub-blocks of the same line -- `configs.fp32_b64` (configs[1] as written), `configs.bf16_b256` (configs[3]),
+Rank 0 prints ONE JSON line.  The top level is the HEADLINE (fp32, batch 256 / GPU).  A plain run does only what the headline
+needs: set-up, W warm-up steps, the K timed steps, `--dump-outputs DIR` if given, the line.  Everything described below beyond
+`metric` / `value` / `ms_per_step` (roofline, sustained, cpu_baseline, parity, dist_check, the other configurations) is measured
+only with `--full`.
+
+    python bench.py --gpus 1 --steps K --warmup W --full
+
+`--dump-outputs DIR` writes the arrays the last timed step handed its caller (dump_outputs); inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+With --full at N == 1 the run then measures the other single-GPU configurations of BASELINE.json in short legs (10 steps, no sustain
+loop) and reports them as sub-blocks of the same line -- `configs.fp32_b64` (configs[1] as written), `configs.bf16_b256` (configs[3]),
 `configs.config5_b256` (configs[4], on the well-conditioned "bounded" synthetic regressor so that all three stages project
 the mesh over the silhouette) -- plus `graph` (the step captured into hipGraphs: host microseconds per step before / after)
 and `from_host` (uint8 frames in pinned host memory -> H2D on a copy stream -> batched preprocess kernel -> the path).
@@ -78,7 +87,14 @@ def parse_args():
                                                                  "what the per-configuration child runs of the default line use")
     ap.add_argument("--no-legs", action="store_true", help="headline only: skip the configs / graph / from_host sub-blocks of the default N == 1 run")
     ap.add_argument("--leg-steps", type=int, default=10)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: roofline, sustained loop, "
+                                                        "CPU baseline and oracle parity, dist_check, the other configurations (the options above "
+                                                        "that select or skip those act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------- synthetic assets, once per node
@@ -721,6 +737,38 @@ def loss_parity_block(lg, O, ref5, n5):
             "worst_rel_err": float(max(errs)), "bar": LOSS_BAR, "pass": bool(max(errs) <= LOSS_BAR)}
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(leg, out_dir):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files in out_dir: stage<s>_<name> for the outputs of
+    the three IEF stages (s = 1..3), `losses` (config 5: the [3,4] loss block) and `theta_gathered` (N > 1: the all-gathered theta).
+    Written on rank 0 after the timed region.  If the files would exceed DUMP_MAX_BYTES (batch 256 does, narrowly: the vertices are
+    21 MB per stage), every stage array keeps the same fixed, seeded sample of images, in batch order."""
+    import numpy as np
+
+    extra = {}
+    if leg.config5:
+        extra["losses"] = leg.last_losses().cpu().numpy()
+    if leg.use_dist:
+        extra["theta_gathered"] = leg.theta_all[leg._last_index()].cpu().numpy()
+    arrays = {}
+    for s, st in enumerate(leg.last_outputs()):
+        for name, t in st.items():
+            arrays["stage%d_%s" % (s + 1, name)] = t.cpu().numpy()
+    budget = DUMP_MAX_BYTES - sum(a.nbytes for a in extra.values())
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        n = leg.B * budget // total
+        rows = np.sort(np.random.default_rng(0).choice(leg.B, n, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    arrays.update(extra)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32))
+    return sorted(arrays)
+
+
 # ------------------------------------------------------------------------------------------------- the benchmark (one rank)
 def main():
     args = parse_args()
@@ -788,12 +836,14 @@ def main():
     if made_assets and os.path.exists(made_assets):
         os.remove(made_assets)  # every rank has loaded it (barrier above)
 
-    dt = leg.run_timed(args.steps, args.warmup, timing=not args.no_roofline)
+    dt = leg.run_timed(args.steps, args.warmup, timing=args.full and not args.no_roofline)
     ms_per_step = dt / args.steps * 1e3
     host_us = leg.host_s / args.steps * 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(leg, args.dump_outputs)
 
     roofline = loss_roofline = phase = None
-    if not args.no_roofline and mode != "graph":
+    if args.full and not args.no_roofline and mode != "graph":
         roofline, phase, per_conv = encoder_roofline(leg, ms_per_step)
         if args.config5:
             loss_roofline = loss_roofline_block(leg)
@@ -814,7 +864,7 @@ def main():
 
     # ---- steady state: the same step, untimed by the driver, for >= args.sustain seconds with power / clock sampled
     sustained = None
-    if args.sustain > 0:
+    if args.full and args.sustain > 0:
         sampler = PowerSampler() if rank == 0 else None
         leg.fence()
         if sampler:
@@ -847,7 +897,7 @@ def main():
 
     # ---- N > 1 (and the HPE_FORCE_DIST rehearsal): every rank verifies itself, the flags are reduced into the one line
     dist_check = None
-    if use_dist:
+    if args.full and use_dist:
         from oracle import hmr_oracle as O  # the checker
 
         last = leg._last_index()
@@ -865,7 +915,7 @@ def main():
     cpu_baseline = None
     parity = None
     ref = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         from oracle import hmr_oracle as O  # the checker, timed as the CPU baseline
 
         n = min(args.cpu_sample, B)
@@ -904,7 +954,7 @@ def main():
         parity = parity_block(leg.last_outputs()[-1], ref, n, dtype=args.encoder_dtype, gate_kp2d_rms=(reg_variant == "bounded"), kp2d_cond=cond)
 
     loss_parity = None
-    if rank == 0 and world == 1 and args.cpu_sample == 0 and args.parity_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample == 0 and args.parity_sample > 0:
         from oracle import hmr_oracle as O  # the checker
 
         n = min(args.parity_sample, B)
@@ -922,7 +972,7 @@ def main():
     configs = None
     extras = {}
     default_headline = (args.encoder_dtype == "fp32" and not args.config5 and mode == "pipelined" and not args.from_host and B == 256)
-    if rank == 0 and world == 1 and not use_dist and not args.no_legs and default_headline and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and not use_dist and not args.no_legs and default_headline and not args.no_roofline:
         from oracle import hmr_oracle as O  # the checker
 
         K, W = args.leg_steps, 3
@@ -976,7 +1026,7 @@ def main():
             env_c = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "HPE_FORCE_DIST", "HPE_POWER_TRACE")}
             env_c["HPE_BENCH_ASSETS"] = assets_path
             cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--batch", str(B), "--cpu-sample", "0",
-                   "--parity-sample", str(parity_n), "--sustain", "0", "--no-legs"] + extra
+                   "--parity-sample", str(parity_n), "--sustain", "0", "--no-legs", "--full"] + extra
             r = subprocess.run(cmd, env=env_c, capture_output=True, text=True, timeout=900)
             lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             if not lines:

@@ -68,3 +68,52 @@ def test_assets_roundtrip_and_cpulist(tmp_path):
     # the bounded variant is the survey draw with a smaller last-layer step, nothing else
     assert np.array_equal(a["reg"]["dense_0/kernel"], a["reg_bounded"]["dense_0/kernel"])
     assert np.allclose(a["reg_bounded"]["dense_2/kernel"], 0.25 * a["reg"]["dense_2/kernel"])
+
+
+def test_steps_must_be_positive():
+    """`--steps` is the number of timed steps and `ms_per_step` divides by it: zero steps is refused before any device work."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_sample_and_budget(tmp_path):
+    """--dump-outputs at batch 256: the three stages' outputs exceed 64 MB, so every stage array keeps the same seeded sample of
+    images (in batch order), the files stay within the budget, and the sample is the same from run to run."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    B = 256
+    shapes = {"verts": (6890, 3), "joints": (19, 3), "cams": (3,), "theta": (85,), "J_transformed": (24, 3), "kp2d": (19, 2)}
+
+    class FakeLeg(object):
+        config5 = use_dist = False
+
+        def __init__(self):
+            self.B = B
+            # row i of every array holds the value i: a sampled file tells which images it kept
+            self.sets = [{k: torch.arange(B, dtype=torch.float32).reshape(B, *[1] * len(s)).expand(B, *s).contiguous() + 1000 * st
+                          for k, s in shapes.items()} for st in range(3)]
+
+        def last_outputs(self):
+            return self.sets
+
+    names = bench.dump_outputs(FakeLeg(), str(tmp_path / "a"))
+    bench.dump_outputs(FakeLeg(), str(tmp_path / "b"))
+    assert names == sorted("stage%d_%s" % (s, k) for s in (1, 2, 3) for k in shapes)
+    total = 0
+    rows = None
+    for n in names:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        total += os.path.getsize(tmp_path / "a" / (n + ".npy"))
+        r = a.reshape(a.shape[0], -1)[:, 0] % 1000
+        rows = r if rows is None else rows
+        assert np.array_equal(r, rows)
+    assert total <= 64 * 10 ** 6
+    assert 200 < len(rows) < B and np.all(np.diff(rows) > 0)

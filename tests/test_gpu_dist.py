@@ -40,11 +40,11 @@ def test_sharded_predictor_and_loss_reduce_over_rccl_world1():
 
 @pytest.mark.parametrize("extra", [[], ["--config5"]])
 def test_bench_launches_its_own_ranks(extra):
-    """`HPE_FORCE_DIST=1 python bench.py --gpus 1`: the plain command starts its rank process itself (the parent never
+    """`HPE_FORCE_DIST=1 python bench.py --gpus 1 --full`: the command starts its rank process itself (the parent never
     touches HIP), the rank builds an RCCL group, runs the all-gather (and with --config5 the one all-reduce) and exactly one
     JSON line comes back on stdout."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16",
-           "--cpu-sample", "0", "--sustain", "0"] + extra
+           "--cpu-sample", "0", "--sustain", "0", "--full"] + extra
     r = subprocess.run(cmd, env=_env(HPE_FORCE_DIST="1"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

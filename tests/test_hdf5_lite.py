@@ -1,8 +1,9 @@
 """hdf5_lite against files written by the real HDF5 library.
 
 Fixtures under tests/golden/hdf5/ were written with h5py 3.3 / libhdf5 1.10 by tests/golden/make_hdf5_golden.py and read
-back through h5py into expected.npz; PyTables-written files (what deepdish produces, src/predictor.py:93-105) are
-checked in place when this container's /opt/conda copy of the PyTables test-suite data is present.
+back through h5py into expected.npz; PyTables-written files (what deepdish produces, src/predictor.py:93-105) are files of
+the PyTables 3.6.1 test suite, stored under tests/golden/hdf5/pytables/ (BSD licence, LICENSE.txt there) with their h5py
+reading in expected_pytables.npz.
 """
 import os
 
@@ -12,7 +13,7 @@ import pytest
 from hpe_amd import hdf5_lite as H
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hdf5")
-PYTABLES = "/opt/conda/lib/python3.9/site-packages/tables"
+PYTABLES = os.path.join(GOLD, "pytables")
 
 
 def _walk(node, prefix=""):
@@ -52,7 +53,6 @@ def test_mean_params_layout_feeds_predictor_loader(tmp_path):
     assert np.array_equal(mv["shape"], exp["mean_params.h5:/shape"]) and mv["shape"].shape == (10,)
 
 
-@pytest.mark.skipif(not os.path.isdir(PYTABLES), reason="PyTables test data not present on this machine")
 def test_pytables_written_files():
     exp = np.load(os.path.join(GOLD, "expected_pytables.npz"), allow_pickle=False)
     by_file = {}

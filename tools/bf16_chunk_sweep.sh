@@ -3,7 +3,7 @@
 # Infinity Cache?).  Usage: tools/bf16_chunk_sweep.sh OUTDIR
 OUT=${1:-gpurun_out/chunks}; mkdir -p $OUT
 run() {
-  env "$@" python bench.py --encoder-dtype bf16 --steps 30 --warmup 5 --cpu-sample 0 --sustain 0 --no-legs 2>/dev/null | \
+  env "$@" python bench.py --full --encoder-dtype bf16 --steps 30 --warmup 5 --cpu-sample 0 --sustain 0 --no-legs 2>/dev/null | \
     python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-44s %9.1f img/s  %.4f ms/step  span %.4f' % ('$*', d['value'], d['ms_per_step'], d['roofline']['launch_ms']))"
 }
 run HPE_STREAMS=2

@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/p8}; shift
 MASKS=${@:-0 1 3 7}
 mkdir -p $OUT
 for m in $MASKS; do
-  HPE_BF16_P8=$m HPE_BENCH_LAYERS=1 python bench.py --encoder-dtype bf16 --steps 20 --warmup 5 --cpu-sample 0 --sustain 0 --no-legs \
+  HPE_BF16_P8=$m HPE_BENCH_LAYERS=1 python bench.py --full --encoder-dtype bf16 --steps 20 --warmup 5 --cpu-sample 0 --sustain 0 --no-legs \
       > $OUT/bench_bf16_p8_$m.json 2> $OUT/layers_bf16_p8_$m.txt || exit 1
   python - <<PY
 import json

@@ -7,7 +7,7 @@ mkdir -p $OUT
 i=0
 for m in $MASKS; do
   i=$((i+1))
-  HPE_WINO_F4=$m python bench.py --steps 20 --warmup 5 --cpu-sample 16 --sustain 0 --no-legs > $OUT/bench_f4_${m}_$i.json 2> $OUT/bench_f4_${m}_$i.err || { tail -5 $OUT/bench_f4_${m}_$i.err; exit 1; }
+  HPE_WINO_F4=$m python bench.py --full --steps 20 --warmup 5 --cpu-sample 16 --sustain 0 --no-legs > $OUT/bench_f4_${m}_$i.json 2> $OUT/bench_f4_${m}_$i.err || { tail -5 $OUT/bench_f4_${m}_$i.err; exit 1; }
   python - <<PY
 import json
 d = json.load(open("$OUT/bench_f4_${m}_$i.json"))

@@ -7,7 +7,7 @@ mkdir -p $OUT
 python tools/layer_times.py 256 5 --all -- off=dtype:bf16,halo3:0 on=dtype:bf16,halo3:15 > $OUT/layers_halo3.txt 2>&1 || exit 1
 grep -E "branch2b|3x3|all conv|layer" $OUT/layers_halo3.txt
 for m in $MASKS; do
-  HPE_HALO3=$m python bench.py --encoder-dtype bf16 --steps 20 --warmup 5 --cpu-sample 0 --sustain 0 --no-legs \
+  HPE_HALO3=$m python bench.py --full --encoder-dtype bf16 --steps 20 --warmup 5 --cpu-sample 0 --sustain 0 --no-legs \
       > $OUT/bench_bf16_halo3_$m.json 2> $OUT/bench_bf16_halo3_$m.err || exit 1
   python - <<PY
 import json
