@@ -22,4 +22,5 @@ from .image import get_original, preprocess_batch, preprocess_image  # noqa: F40
 from .ops import kp_reprojection_loss, mesh_reprojection_loss  # noqa: F401
 from .predictor import Predictor  # noqa: F401
 from .projection import batch_orth_proj_idrot, reproject_vertices  # noqa: F401
+from .render import SMPLRenderer  # noqa: F401
 from .smpl import SMPL  # noqa: F401

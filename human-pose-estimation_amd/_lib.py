@@ -65,6 +65,18 @@ class HpeSmplModel(C.Structure):
     ]
 
 
+class HpeRenderParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int),  # sizeof(HpeRenderParams); hpe_render_params_init writes it, every render call checks it
+        ("color_id", C.c_int),
+        ("do_alpha", C.c_int),
+        ("rot_axis", C.c_int),
+        ("rot_deg", C.c_float),
+        ("near", C.c_float),
+        ("far", C.c_float),
+    ]
+
+
 OUTPUT_FIELDS = ("verts", "joints", "cams", "theta", "J_transformed", "kp2d", "verts2d", "Rs")
 
 
@@ -119,6 +131,15 @@ _PROTOS = {
     "hpe_get_loss_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "hpe_debug_set_loss_counter": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hpe_get_conv_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "hpe_render_params_init": (None, [C.POINTER(HpeRenderParams)]),
+    "hpe_renderer_create": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "hpe_renderer_destroy": (C.c_int, [C.c_void_p]),
+    "hpe_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(HpeRenderParams), C.c_void_p,
+                             C.c_void_p]),
+    "hpe_debug_render_ids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(HpeRenderParams), C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "hpe_debug_render_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(HpeRenderParams),
+                                            C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

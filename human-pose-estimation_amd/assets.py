@@ -177,3 +177,35 @@ def load_mean_params(smpl_model_path):
     if pose.shape != (72,) or shape.shape != (10,):
         raise AssetError("%s: pose %s / shape %s, expected (72,) / (10,)" % (base, pose.shape, shape.shape))
     return {"pose": pose, "shape": shape}
+
+
+def load_smpl_faces(path, num_verts=6890):
+    """The SMPL triangle list -> int32 [F,3]: ``smpl_faces.npy`` (what the reference's SMPLRenderer loads, src/util/renderer.py:27),
+    or the ``f`` field of an SMPL model ``.pkl`` (allow-list unpickler, as ``load_smpl_model``) / ``.npz``.  Every index must lie
+    in [0, num_verts)."""
+    path = str(path)
+    if path.endswith(".npy"):
+        f = np.load(path, allow_pickle=False)
+    elif path.endswith(".npz"):
+        with np.load(path, allow_pickle=False) as z:
+            if "f" not in z.files:
+                raise AssetError("%s has no field 'f' (the SMPL faces)" % path)
+            f = z["f"]
+    else:
+        with open(path, "rb") as fh:
+            raw = fh.read()
+        try:
+            dd = _AllowListUnpickler(io.BytesIO(raw), encoding="latin1").load()
+        except pickle.UnpicklingError:
+            raise
+        except Exception as e:
+            raise AssetError("%s is not a readable SMPL pickle: %s: %s" % (path, type(e).__name__, e)) from e
+        if not isinstance(dd, dict) or "f" not in dd:
+            raise AssetError("%s has no field 'f' (the SMPL faces)" % path)
+        f = _dense(dd["f"], "f")
+    f = np.asarray(f)
+    if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1 or not np.issubdtype(f.dtype, np.integer):
+        raise AssetError("%s: faces must be an integer [F,3] array, got %s %s" % (path, f.dtype, f.shape))
+    if f.min() < 0 or f.max() >= num_verts:
+        raise AssetError("%s: face indices span [%d, %d], outside [0, %d)" % (path, f.min(), f.max(), num_verts))
+    return np.ascontiguousarray(f, dtype=np.int32)

@@ -211,3 +211,35 @@ hipError_t hpe_launch_preprocess_u8_batch(const unsigned char* img, const Prepro
                                           float* out, int S, hipStream_t st);
 hipError_t hpe_launch_shift_verts(const float* verts, const float* cam, int B, int P, float flength, float img_size, float* out,
                                   hipStream_t st);
+
+// render.hip: batched mesh rasteriser (SMPLRenderer, DESIGN.md "Renderer").  One record per (image, vertex):
+struct RenderVert {
+    int U, V;      // projected position in 1/256 px (rint(256 u), rint(256 v))
+    int valid;     // 0: non-finite, outside [near, far] or outside the +-16384 px guard band (its faces are dropped)
+    int pad;
+    float iz;      // 1 / z
+    float r, g, b; // lit vertex colour (albedo * sum of the three Lambertian point lights), not clamped
+};
+struct RenderArgs {
+    const float* verts;        // [B,P,3] camera-space vertices
+    const float* cam;          // [B,3] (f, px, py); nullptr: (500, W/2, H/2)
+    const int* faces;          // [Fn,3]
+    const int* adj_off;        // [P+1] vertex -> face CSR
+    const int* adj_face;       // [3 Fn]
+    RenderVert* rec;           // [B,P]
+    uint2* box;                // [B,Fn]
+    float* center;             // [B,4] (rotation only)
+    const unsigned char* bg;   // [B,H,W,3] or nullptr (white)
+    unsigned char* out;        // [B,H,W,C]
+    int* out_face;             // test hook: [B,H,W] winning face (-1 uncovered) instead of the image
+    float* out_z;              // test hook: [B,H,W] its depth
+    int B, P, Fn, H, W, C;
+    int rotate;
+    float R[9];                // row-major, V' = (V - c) R + c
+    float znear, zfar;
+    float albedo[3];
+    float light[9];            // three light positions (already rotated by Ry(120 deg))
+    float light_color[3];
+};
+// stage 0: vertex records only; 1: the whole render (image, or face / depth buffers when out_face is set)
+hipError_t hpe_launch_render(const RenderArgs& a, int stage, hipStream_t st);

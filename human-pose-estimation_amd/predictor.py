@@ -11,7 +11,8 @@ Differences, all deliberate:
   * ``load_path`` / ``pretrained_model_path`` are optional (no reference flag defines them, F9);
   * any batch size <= ``config.batch_size`` works (the reference requires equality, F10); larger inputs are
     processed in chunks of ``config.batch_size``;
-  * the renderer, optimizers and critic the reference instantiates as import/ctor side effects are dropped;
+  * the optimizers and critic the reference instantiates as import/ctor side effects are dropped; the renderer is built on first
+    access of ``Predictor.renderer`` (``render.SMPLRenderer``);
   * assets come from ``config.smpl_model_path`` (the SMPL pickle, read by an allow-list unpickler, or .npz) /
     ``neutral_smpl_mean_params.{npz,h5}`` next to it / ``<checkpoint_dir>``: ``weights.npz`` (Keras-layout names) or the
     reference's own ``tf.train.Checkpoint`` files (``tf_checkpoint.py``, no TensorFlow needed),
@@ -53,6 +54,8 @@ class Predictor(object):
         self.num_stage = getattr(config, "num_stage", 3)
         self.batch_size = getattr(config, "batch_size", 8)
         self.checkpoint_dir = getattr(config, "checkpoint_dir", None)
+        self.smpl_face_path = getattr(config, "smpl_face_path", None)
+        self._renderer = None
         if self.img_size != 224:
             raise ValueError("img_size must be 224 (the encoder plan is built for 224x224 inputs)")
         self.num_joints = 14
@@ -106,6 +109,20 @@ class Predictor(object):
         self.theta_prev = self.mean_var
         if w is not None and "inital_theta" in w:
             self.theta_prev = torch.from_numpy(np.asarray(w["inital_theta"], np.float32)).to(self.engine.tdev)
+
+    @property
+    def renderer(self):
+        """SMPLRenderer(img_size=self.img_size, face_path=config.smpl_face_path) (reference: src/predictor.py:57-59), built on first
+        use so that a predictor that never draws needs no face file."""
+        if self._renderer is None:
+            if not self.smpl_face_path:
+                raise FileNotFoundError("Predictor.renderer needs the SMPL faces: set config.smpl_face_path (smpl_faces.npy, or an SMPL "
+                                        ".pkl / .npz with an 'f' field)")
+            from .render import SMPLRenderer
+
+            self._renderer = SMPLRenderer(img_size=self.img_size, face_path=self.smpl_face_path, max_batch=self.batch_size,
+                                          device=self.engine.device)
+        return self._renderer
 
     def load_mean_param(self):
         """reference: src/predictor.py:88-110 -- zeros(1,85); [0,0]=0.9; pose[:3]=0 then pose[0]=pi; shape."""

@@ -129,6 +129,24 @@ def make_smpl_model(seed=3):
     }
 
 
+def make_faces(seed=0, num_faces=13776, smpl_seed=3):
+    """Deterministic triangle list [num_faces,3] int32 over the vertices of ``make_smpl_model(smpl_seed)`` (stands in for
+    ``smpl_faces.npy``, SMPL's 13776 faces): face i joins vertex i % 6890 to two of its six nearest rest-pose neighbours."""
+    v = make_smpl_model(smpl_seed)["v_template"].astype(np.float64)
+    V = v.shape[0]
+    nbr = np.empty((V, 6), np.int64)
+    for lo in range(0, V, 1024):
+        d = ((v[lo : lo + 1024, None, :] - v[None, :, :]) ** 2).sum(-1)
+        d[np.arange(d.shape[0]), np.arange(lo, lo + d.shape[0])] = np.inf
+        part = np.argpartition(d, 6, axis=1)[:, :6]
+        nbr[lo : lo + 1024] = np.take_along_axis(part, np.argsort(np.take_along_axis(d, part, 1), axis=1, kind="stable"), 1)
+    g = _rng(seed)
+    a = np.arange(num_faces) % V
+    pick = np.argsort(g.random((num_faces, 6)), axis=1, kind="stable")[:, :2]
+    faces = np.stack([a, nbr[a, pick[:, 0]], nbr[a, pick[:, 1]]], 1)
+    return faces.astype(np.int32)
+
+
 def make_mean_params(seed=5, zero=False):
     """Stand-in for neutral_smpl_mean_params.h5: {'pose': [72], 'shape': [10]} (predictor.py:93-105)."""
     g = _rng(seed)

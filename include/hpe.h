@@ -229,7 +229,48 @@ int hpe_get_original(const float* verts_dev, const float* cam_dev, int B, int P,
                      int img_size, float* vert_shifted_dev, float cam_for_render[3], float* kp_original_host,
                      const float* joints2d_host, void* stream);
 
+/* -- mesh renderer: the reference's SMPLRenderer (src/util/renderer.py:23-112) without OpenDR ---------------------------------
+ * A renderer is its own handle (the reference builds SMPLRenderer without a predictor, preview.py:50).  What it computes is
+ * defined in DESIGN.md "Renderer": pinhole projection snapped to 1/256 px, rasterisation with int64 edge functions and a
+ * top-left tie rule (no MSAA), nearest depth wins (ties to the lower face index), Lambertian shading with the reference's three
+ * point lights interpolated perspective-correctly, composited over an optional uint8 background.  No near-plane clipping: a face
+ * with a vertex outside [near, far] is dropped.  A renderer is not re-entrant: its workspace serves one call at a time, so calls
+ * on different streams must be ordered by the caller. */
+typedef struct hpe_renderer hpe_renderer;
+
+typedef struct HpeRenderParams {
+    int struct_size; /* sizeof(HpeRenderParams); written by hpe_render_params_init, checked by every render call */
+    int color_id;    /* albedo: even = light_blue (the reference's default), odd = light_pink (renderer.py:239-243) */
+    int do_alpha;    /* 1: a fourth channel: 255 everywhere with a background, else 255 where a face covers the pixel and 0 elsewhere */
+    int rot_axis;    /* 0 none; 1 x, 2 y, 3 z: the view rotation of SMPLRenderer.rotated (renderer.py:84-112) about the mesh mean */
+    float rot_deg;   /* rotation angle in degrees */
+    float near;      /* < 0: the reference's default max(min z - 25, 0.1) (renderer.py:65-66) */
+    float far;       /* < 0: the reference's default max(max z + 25, 25) (renderer.py:67-68) */
+} HpeRenderParams;
+
+/* defaults: struct_size = sizeof(HpeRenderParams), color_id 0, do_alpha 0, no rotation, near = far = -1 */
+void hpe_render_params_init(HpeRenderParams* p);
+/* faces_host [Fn,3] int32, every index in [0, P); the vertex -> face adjacency is built here.  Workspace for max_batch images
+ * (1..1024) per hpe_render call.  Synchronises. */
+int hpe_renderer_create(int device, const int* faces_host, int Fn, int P, int max_batch, hpe_renderer** out);
+int hpe_renderer_destroy(hpe_renderer* r);
+/* verts_dev [B,P,3] float camera-space vertices (e.g. vert_shifted of hpe_get_original); cam_dev [B,3] (f, px, py) per image
+ * (e.g. cam_for_render) or NULL = (500, W/2, H/2) (renderer.py:53-54); 1 <= B <= max_batch; 1 <= H, W <= 4096; bg_dev
+ * [B,H,W,3] uint8 or NULL (white); p NULL = defaults.  out_dev [B,H,W,3] uint8, or [B,H,W,4] with do_alpha.  Vertex colours go
+ * to channels 0, 1, 2 in that order, as the reference writes its RGB triples onto a BGR frame. */
+int hpe_render(hpe_renderer* r, const float* verts_dev, const float* cam_dev, int B, int H, int W, const unsigned char* bg_dev,
+               const HpeRenderParams* p, unsigned char* out_dev, void* stream);
+
 /* -- test / measurement hooks -------------------------------------------------------------------- */
+/* Renderer internals: face_dev [B,H,W] int32 winning face per pixel (-1 where uncovered) and z_dev [B,H,W] float its depth
+ * z_pix (0 where uncovered); arguments as hpe_render. */
+int hpe_debug_render_ids(hpe_renderer* r, const float* verts_dev, const float* cam_dev, int B, int H, int W, const HpeRenderParams* p,
+                         int* face_dev, float* z_dev, void* stream);
+/* the vertex records of hpe_render: rec_dev [B,P] of 8 x 4 bytes {int U, int V, int valid, int 0, float 1/z, float r, g, b}
+ * with U = rint(256 u), V = rint(256 v) (projected pixel coordinates in 1/256 px); H and W only serve the default camera. */
+int hpe_debug_render_vertices(hpe_renderer* r, const float* verts_dev, const float* cam_dev, int B, int H, int W, const HpeRenderParams* p,
+                              void* rec_dev, void* stream);
+
 /* Run loaded conv layer `idx` (+BN, optional residual, optional ReLU) on x_dev [B,Hin,Hin,Cin] ->
  * y_dev [B,Hout,Hout,Cout]; for idx 0 the input is the raw [B,224,224,3] image and y is the
  * post-ReLU conv1 output [B,112,112,64].  On a bf16 context (idx > 0 only) x / residual are rounded to bf16 on the way in, the
