@@ -33,105 +33,12 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "conv_gemm_common.h"
 #include "hpe_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define BK 32
 #define LDS_PITCH 36  // floats; 144 B row pitch -> conflict-free ds_read_b128 (see header comment)
 
 namespace {
-
-// Per-thread description of one staged A row: element offset of its first k element (+ this thread's
-// 16-B chunk) and, for the 3x3 conv, a 9-bit mask of the taps that fall inside the image.
-struct RowAddr {
-    int base;
-    unsigned mask;
-};
-
-template <int MODE>
-__device__ __forceinline__ RowAddr make_row(const GemmArgs& p, int m, int kc4) {
-    RowAddr r;
-    r.mask = 0x1ffu;
-    if (m >= p.M) m = p.M - 1;  // tail rows: read a valid row, the store guard drops the result
-    if (MODE == GEMM_DENSE || MODE == GEMM_DUAL) {
-        r.base = m * p.lda + kc4;
-    } else {
-        const int hw = p.Ho * p.Wo;
-        const int b = m / hw;
-        const int rem = m - b * hw;
-        const int ho = rem / p.Wo;
-        const int wo = rem - ho * p.Wo;
-        if (MODE == GEMM_STRIDED) {
-            r.base = ((b * p.Hi + ho * p.stride) * p.Wi + wo * p.stride) * p.Cin + kc4;
-        } else if (MODE == GEMM_CONV3) {
-            r.base = ((b * p.Hi + ho) * p.Wi + wo) * p.Cin + kc4;
-            unsigned mk = 0;
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int dh = tap / 3 - 1, dw = tap % 3 - 1;
-                if ((unsigned)(ho + dh) < (unsigned)p.Hi && (unsigned)(wo + dw) < (unsigned)p.Wi) mk |= 1u << tap;
-            }
-            r.mask = mk;
-        } else {  // GEMM_STEM: padded input [B,Hi,Wi,4], 8 pixels x 4 ch = one 32-float slab per kh
-            r.base = ((b * p.Hi + 2 * ho) * p.Wi + 2 * wo) * 4 + kc4;
-        }
-    }
-    return r;
-}
-
-// Wave-uniform position of a k-slab inside the (kh, kw, cin) axis; advanced once per slab with scalar ops.
-struct SlabPos {
-    int off;   // element offset added to every row base
-    int tap;   // CONV3: kh*3+kw
-    int cs;    // CONV3: cin slab inside the tap
-};
-
-template <int MODE>
-__device__ __forceinline__ void slab_advance(const GemmArgs& p, SlabPos& sp) {
-    if (MODE == GEMM_DENSE || MODE == GEMM_STRIDED || MODE == GEMM_DUAL) {
-        sp.off += BK;
-    } else if (MODE == GEMM_CONV3) {
-        sp.cs += 1;
-        sp.off += BK;
-        if (sp.cs == p.cin_slabs) {
-            sp.cs = 0;
-            sp.tap += 1;
-            const int kh = sp.tap / 3;
-            sp.off = ((kh - 1) * p.Wi + (sp.tap - kh * 3 - 1)) * p.Cin;
-        }
-    } else {
-        sp.off += p.Wi * 4;
-    }
-}
-
-template <int MODE>
-__device__ __forceinline__ SlabPos slab_first(const GemmArgs& p) {
-    SlabPos sp;
-    sp.tap = 0;
-    sp.cs = 0;
-    sp.off = (MODE == GEMM_CONV3) ? (-p.Wi - 1) * p.Cin : 0;
-    return sp;
-}
-
-template <int MODE>
-__device__ __forceinline__ SlabPos slab_seek(const GemmArgs& p, int slab) {
-    SlabPos sp;
-    sp.tap = 0;
-    sp.cs = 0;
-    if (MODE == GEMM_DENSE || MODE == GEMM_STRIDED || MODE == GEMM_DUAL) {
-        sp.off = slab * BK;
-    } else if (MODE == GEMM_CONV3) {
-        sp.tap = slab / p.cin_slabs;
-        sp.cs = slab - sp.tap * p.cin_slabs;
-        const int kh = sp.tap / 3;
-        sp.off = ((kh - 1) * p.Wi + (sp.tap - kh * 3 - 1)) * p.Cin + sp.cs * BK;
-    } else {
-        sp.off = slab * p.Wi * 4;
-    }
-    return sp;
-}
 
 template <int MODE>
 __device__ __forceinline__ f32x4 load_a(const GemmArgs& p, const RowAddr& r, const SlabPos& sp) {
@@ -484,84 +391,6 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(GemmArgs p) {
 // register-staged kernel comes from an XOR swizzle applied on the per-lane SOURCE address instead:
 // LDS chunk c of row r holds logical chunk c ^ ((r >> 1) & 7), and the fragment read applies the same XOR, which
 // makes every 16-lane ds_read_b128 group hit 16 distinct 16-B slots of the 256-B bank row.
-// Epilogue shared by the DMA kernel and the split-K fix-up kernel: BN scale/shift in registers, transpose through LDS,
-// rows leave as 16 B per lane with the residual read the same way.
-// The residual of an identity block is read here for the LAST time (the block input is dead after the add): -DHPE_F32_RES_NT reads it with
-// the non-temporal policy (A/B knob of round 4; the bf16 chain kernel gained 1-2 % from the same idea).
-#ifdef HPE_F32_RES_NT
-#define HPE_RES_LOAD(ptr) __builtin_nontemporal_load(ptr)
-#else
-#define HPE_RES_LOAD(ptr) (*(ptr))
-#endif
-// rpre (use_pre): the residual vectors of this thread's rows, loaded by the caller before its main loop (else they are read here)
-template <int BM, int BN, int WM, int WN, int NP>
-__device__ __forceinline__ void conv_epilogue(const GemmArgs& p, float* lds, f32x16 (&acc)[BM / WM / 32][BN / WN / 32], int m0, int n0, int t,
-                                              int lane, int wm, int wn, const f32x4 (&rpre)[NP], bool use_pre) {
-    constexpr int MT = BM / WM / 32;
-    constexpr int NT = BN / WN / 32;
-    constexpr int NTHR = 64 * WM * WN;
-    constexpr int EP = BN + 4;
-    {
-        const int col_l = lane & 31;
-        const int row_l = 4 * (lane >> 5);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int cl = (wn * NT + j) * 32 + col_l;
-            const int n = n0 + cl;
-            const bool n_ok = n < p.N;
-            const float sc = n_ok ? p.scale[n] : 0.f;
-            const float sh = n_ok ? p.shift[n] : 0.f;
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const int rl = (wm * MT + i) * 32 + row_l;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) lds[(rl + (e & 3) + 8 * (e >> 2)) * EP + cl] = acc[i][j][e] * sc + sh;
-            }
-        }
-    }
-    __syncthreads();
-    {
-        constexpr int TPR = BN / 4;
-        constexpr int RPP = NTHR / TPR;
-        const int r = t / TPR;
-        const int c4 = (t - r * TPR) * 4;
-        const int n = n0 + c4;
-        const bool full = (n + 3) < p.N;
-#pragma unroll
-        for (int pass = 0; pass < BM / RPP; ++pass) {
-            const int row = pass * RPP + r;
-            const int m = m0 + row;
-            if (m >= p.M || n >= p.N) continue;
-            f32x4 v = *reinterpret_cast<const f32x4*>(&lds[row * EP + c4]);
-            if (full) {
-                if (use_pre) v += rpre[pass < NP ? pass : 0];
-                else if (p.res) v += HPE_RES_LOAD(reinterpret_cast<const f32x4*>(p.res + (size_t)m * p.ldres + n));
-                if (p.relu) {
-                    v.x = fmaxf(v.x, 0.f);
-                    v.y = fmaxf(v.y, 0.f);
-                    v.z = fmaxf(v.z, 0.f);
-                    v.w = fmaxf(v.w, 0.f);
-                }
-                if (p.y_slab8)
-                    *reinterpret_cast<f32x4*>(p.y + ((size_t)(n >> 3) * p.M + m) * 8 + (n & 7)) = v;
-                else
-                    *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.ldy + n) = v;
-            } else {
-                const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (n + u < p.N) {
-                        float o = vv[u];
-                        if (p.res) o += p.res[(size_t)m * p.ldres + n + u];
-                        if (p.relu) o = fmaxf(o, 0.f);
-                        p.y[(size_t)m * p.ldy + n + u] = o;
-                    }
-                }
-            }
-        }
-    }
-}
-
 template <int MODE, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 2) void conv_gemm_f32_dma_kernel(GemmArgs p) {
     constexpr int MT = BM / WM / 32;

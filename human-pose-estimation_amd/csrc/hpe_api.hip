@@ -92,6 +92,9 @@ struct ConvLayer {
     float* w_dual = nullptr;
     float* shift_dual = nullptr;
     int k_dual = 0, k1_dual = 0;
+    // plan option f32_split: the fp32 weights of the 1x1 layers split exactly into three bf16 pieces, [n_pad][3][k] (conv_gemm_f32s.hip)
+    void* w_split = nullptr;
+    void* w_dual_split = nullptr;
     void* stem_w = nullptr;   // conv1 only: weights in the k enumeration of stem_fused.hip (fp32 [64][160] / bf16 [64][7][32])
     float* wino_u = nullptr;  // device, G g G^T in the blocked layout of conv_wino.hip (3x3 layers on the Winograd path only)
     float* wino4_u = nullptr;  // device, the F(4x4,3x3) G g G^T in the blocked layout of conv_wino4.hip (layers selected by wino_f4)
@@ -134,6 +137,10 @@ struct TileKnobs {
     int bf16_p8 = 0;         // HPE_BF16_P8: layer kinds that take the 256 x 256 phase-interleaved kernel (bit mask, see pick_bf16)
     int bf16_p8_min_n = 256; // HPE_BF16_P8_MINN
     int bf16_p8_min_k = 512; // HPE_BF16_P8_MINK
+    int f32s_tile = TILE_128x128;  // HPE_F32S_TILE: tile of the split-bf16 fp32 kernel (TILE_128x128 = 4 waves, TILE_128x128_W8, TILE_256x128_W8)
+    int f32s_expand_tile = TILE_128x128_W8;  // HPE_F32S_EXPAND_TILE: ... of the identity-block expand layers (+ residual)
+    int f32s_expand_min_k = 256;   // HPE_F32S_EXPAND_MINK: expand layers with a shorter k axis keep the fp32 kernel (stage 3: all epilogue)
+    int f32s_min_tiles = 128;      // HPE_F32S_MIN_TILES: launches with fewer tiles than this keep the fp32 kernel (and its split-K)
 };
 
 struct hpe_ctx {
@@ -205,6 +212,8 @@ struct hpe_ctx {
     int halo3 = 0;         // bf16 only: map sizes (1 = 7x7, 2 = 14x14, 4 = 28x28, 8 = 56x56) whose 3x3 layers run on conv3_halo_bf16.hip; plan option halo3 / HPE_HALO3
     int chain_fuse = 0;    // bf16 only: stages (bit 0: stage 2, bit 1: stage 3) whose identity blocks run branch2c + the next block's branch2a as
                            // one launch (conv_chain_bf16.hip); plan option chain_fuse / HPE_CHAIN
+    int f32_split = 0;     // fp32 only: stages (1 = stage 2 ... 8 = stage 5) whose 1x1 / strided / dual layers run on conv_gemm_f32s.hip; plan option
+                           // f32_split / HPE_F32_SPLIT
     int co_running = 1;    // chunk streams of the encoder call being enqueued (launch-size rules of the F(4x4) kernels)
     float* w4_split = nullptr;  // F(4x4) C-axis split workspaces + counters (4 x hpe_wino4_split_ws_floats: one per chunk-stream slot)
     float* partial_tail = nullptr;
@@ -250,6 +259,50 @@ int upload(hpe_ctx* c, float** p, const std::vector<float>& h) {
     if (rc) return rc;
     HIP_TRY(hipMemcpy(*p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     return HPE_OK;
+}
+
+// fp32 Wt[rows][K] -> bf16 [rows][3][K]: w = w0 + w1 + w2 exactly (finite weights), each piece rounded to nearest even (conv_gemm_f32s.hip)
+int upload_split(hpe_ctx* c, void** p, const std::vector<float>& wt, int rows, int K) {
+    std::vector<unsigned short> ws((size_t)rows * 3 * K);
+    auto bf2f = [](unsigned short h) {
+        const unsigned u = (unsigned)h << 16;
+        float f;
+        memcpy(&f, &u, 4);
+        return f;
+    };
+    for (int n = 0; n < rows; ++n)
+        for (int k = 0; k < K; ++k) {
+            const float x = wt[(size_t)n * K + k];
+            const unsigned short h0 = f2bf(x);
+            const float r1 = x - bf2f(h0);
+            const unsigned short h1 = f2bf(r1);
+            const float r2 = r1 - bf2f(h1);
+            unsigned short* d = &ws[(size_t)n * 3 * K + k];
+            d[0] = h0;
+            d[K] = h1;
+            d[2 * K] = f2bf(r2);
+        }
+    void* q = nullptr;
+    HIP_TRY(hipMalloc(&q, ws.size() * 2));
+    c->allocs.push_back(q);
+    HIP_TRY(hipMemcpy(q, ws.data(), ws.size() * 2, hipMemcpyHostToDevice));
+    *p = q;
+    return HPE_OK;
+}
+
+// bit of a layer's ResNet stage in the f32_split mask, by its output map: 56x56 stage 2 (1), 28x28 stage 3 (2), 14x14 stage 4 (4), 7x7 stage 5 (8)
+inline int stage_bit(int hout) { return hout >= 56 ? 1 : (hout >= 28 ? 2 : (hout >= 14 ? 4 : 8)); }
+
+// tile of conv_gemm_f32s.hip for this launch, -1 = the launch keeps the fp32 kernel.  Split weights exist (fp32 encoder, stage in f32_split),
+// N > 64, the grid is whole tiles of a useful size.  Measured at B = 256 (profiles/r05): the 4-wave 128 x 128 tile (each A element
+// split by one wave) everywhere but on the identity-block expand layers, which are mostly epilogue: there 8 waves (128 x 128, 4 x 2), and on
+// stage 3 (K = 128) the fp32 kernel's 128 x 64 8-wave tile stays ahead.
+int pick_f32s(const hpe_ctx* c, const void* w_split, int M, int N, int K, bool residual_expand) {
+    if (!w_split || N <= 64) return -1;
+    if (residual_expand && K < c->knobs.f32s_expand_min_k) return -1;
+    const int tile = residual_expand ? c->knobs.f32s_expand_tile : c->knobs.f32s_tile;
+    const int bm = tile == TILE_256x128_W8 ? 256 : 128;
+    return (long)((M + bm - 1) / bm) * ((N + 127) / 128) >= c->knobs.f32s_min_tiles ? tile : -1;
 }
 
 int pick_tile(const TileKnobs& kn, int M, int N, int K, bool residual_expand = false, bool concurrent = false) {
@@ -442,7 +495,15 @@ hipError_t run_conv(hpe_ctx* c, int idx, const float* x, int B, const float* res
         const Bf16Plan pl = pick_bf16(c->knobs, p.M, p.N, p.K, mode == GEMM_DENSE && res != nullptr && s.cout == 4 * s.cin, (flags & CONV_CONCURRENT) != 0, mode);
         return hpe_launch_gemm_bf16(p, mode, pl.tile, pl.ns, st);
     }
-    return hpe_launch_gemm(p, mode, pick_tile(c->knobs, p.M, p.N, p.K, mode == GEMM_DENSE && res != nullptr && s.cout == 4 * s.cin, (flags & CONV_CONCURRENT) != 0), st);
+    const bool expand = mode == GEMM_DENSE && res != nullptr && s.cout == 4 * s.cin;
+    const int f32s = (mode == GEMM_DENSE || mode == GEMM_STRIDED) ? pick_f32s(c, L.w_split, p.M, p.N, p.K, expand) : -1;
+    if (f32s >= 0) {
+        p.w = static_cast<const float*>(L.w_split);
+        p.ldw = 3 * L.k_pad;
+        p.w_piece = L.k_pad;
+        return hpe_launch_gemm_f32s(p, mode, f32s, st);
+    }
+    return hpe_launch_gemm(p, mode, pick_tile(c->knobs, p.M, p.N, p.K, expand, (flags & CONV_CONCURRENT) != 0), st);
 }
 
 // branch2c (+BN) + branch1 (+BN) + add + ReLU of a conv_block as one dual-source GEMM: t2 [M, K1] dense, x NHWC strided
@@ -479,6 +540,13 @@ hipError_t run_dual(hpe_ctx* c, int i2c, int i1, const float* t2, const float* x
     if (c->bf16) {
         const Bf16Plan pl = pick_bf16(c->knobs, p.M, p.N, p.K, false, (flags & CONV_CONCURRENT) != 0, GEMM_DUAL);
         return hpe_launch_gemm_bf16(p, GEMM_DUAL, pl.tile, pl.ns, st);
+    }
+    const int f32s = pick_f32s(c, L.w_dual_split, p.M, p.N, p.K, false);
+    if (f32s >= 0) {
+        p.w = static_cast<const float*>(L.w_dual_split);
+        p.ldw = 3 * L.k_dual;
+        p.w_piece = L.k_dual;
+        return hpe_launch_gemm_f32s(p, GEMM_DUAL, f32s, st);
     }
     return hpe_launch_gemm(p, GEMM_DUAL, pick_tile(c->knobs, p.M, p.N, p.K, false, (flags & CONV_CONCURRENT) != 0), st);
 }
@@ -803,7 +871,7 @@ void hpe_config_init(HpeConfig* cfg) {
     cfg->bn_eps = 1e-3f;
     cfg->encoder_dtype = 0;
     cfg->n_streams = cfg->dual_gemm = cfg->stem_fused = cfg->wino_min_c = cfg->wino_min_items = cfg->wino_fused = -1;
-    cfg->wino_fused_min_hw = cfg->mesh_a2b = cfg->wino_f4 = cfg->wino4_fused = cfg->bf16_p8 = cfg->wino4_ksplit = cfg->chain_fuse = cfg->halo3 = -1;
+    cfg->wino_fused_min_hw = cfg->mesh_a2b = cfg->wino_f4 = cfg->wino4_fused = cfg->bf16_p8 = cfg->wino4_ksplit = cfg->chain_fuse = cfg->halo3 = cfg->f32_split = -1;
 }
 
 int hpe_create(const HpeConfig* cfg, hpe_ctx** out) {
@@ -994,6 +1062,11 @@ static int finalize_impl(hpe_ctx* c) {
         c->chain_fuse = c->bf16 ? (opt(c->cfg.chain_fuse, "HPE_CHAIN", 7) & 23) : (opt(c->cfg.chain_fuse, "HPE_CHAIN", 8) & 8);
         c->halo3 = c->bf16 ? (opt(c->cfg.halo3, "HPE_HALO3", 15) & 15) : 0;
         c->halo3_two = opt(-1, "HPE_HALO3_TWO", 4) & 7;
+        c->f32_split = c->bf16 ? 0 : (opt(c->cfg.f32_split, "HPE_F32_SPLIT", 14) & 15);
+        c->knobs.f32s_tile = opt(-1, "HPE_F32S_TILE", c->knobs.f32s_tile);
+        c->knobs.f32s_min_tiles = opt(-1, "HPE_F32S_MIN_TILES", c->knobs.f32s_min_tiles);
+        c->knobs.f32s_expand_tile = opt(-1, "HPE_F32S_EXPAND_TILE", c->knobs.f32s_expand_tile);
+        c->knobs.f32s_expand_min_k = opt(-1, "HPE_F32S_EXPAND_MINK", c->knobs.f32s_expand_min_k);
         c->wino4_fused = c->wino_min_c > 0 ? (opt(c->cfg.wino4_fused, "HPE_WINO4_FUSED", 0) & 12) : 0;
         const char* e;
         e = getenv("HPE_CONCURRENT_TILES");
@@ -1068,6 +1141,8 @@ static int finalize_impl(hpe_ctx* c) {
                     L2.w_dual = static_cast<float*>(qd);
                 } else {
                     if ((rc = upload(c, &L2.w_dual, wt))) return rc;
+                    // f32_split: the folded weight is split (the BN scales are inside the pieces)
+                    if ((c->f32_split & stage_bit(s2.hout)) && (rc = upload_split(c, &L2.w_dual_split, wt, n_pad, K))) return rc;
                 }
                 if ((rc = upload(c, &L2.shift_dual, sh))) return rc;
                 L2.k_dual = K;
@@ -1108,6 +1183,7 @@ static int finalize_impl(hpe_ctx* c) {
                     for (int n = 0; n < s.cout; ++n) wt[(size_t)n * L.k_pad + k] = src[n];
                 }
         if ((rc = upload(c, &L.w, wt))) return rc;
+        if (i != 0 && s.kh == 1 && (c->f32_split & stage_bit(s.hout)) && (rc = upload_split(c, &L.w_split, wt, L.n_pad, L.k_pad))) return rc;
         if (c->wino_min_c > 0 && s.kh == 3 && s.stride == 1 && s.cin % 32 == 0 && s.cout % 64 == 0 &&
             (s.cin >= c->wino_min_c || (c->wino_fused && s.hin >= c->wino_fused_min_hw))) {
             // U = G g G^T, G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1], in double; layout [cout/64][cin/8][16][2][64][4]

@@ -32,9 +32,15 @@ struct GemmArgs {
     int k1_slabs;     // GEMM_DUAL: k-slabs taken from x
     int res_prefetch;  // filled by the launcher: 8-wave tiles read their residual rows before the main loop (HPE_RES_PREFETCH=0: in the epilogue)
     int y_slab8;  // 1: y is written channel-slab major, y[(n / 8) * M + m][n % 8] (the layout the fused Winograd kernel reads); needs N % 8 == 0
+    int w_piece;  // hpe_launch_gemm_f32s: element offset of bf16 piece j = 1, 2 inside a weight row (piece j of Wt[n][k] at w + n * ldw + j * w_piece + k)
 };
 
 hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, hipStream_t st);
+// conv_gemm_f32s.hip: the same fp32 GEMM (GEMM_DENSE / GEMM_STRIDED / GEMM_DUAL, whole tiles, no split-K) on the bf16 matrix cores: p.w points to
+// bf16 weights split exactly into three pieces on the host (w = w0 + w1 + w2, offsets in bf16 elements, ldw and w_piece multiples of 8), A is
+// split the same way in registers; the six products with i + j <= 2 are summed in fp32.  Tiles TILE_128x128 (4 waves), TILE_128x128_W8,
+// TILE_256x128_W8
+hipError_t hpe_launch_gemm_f32s(GemmArgs p, int mode, int tile, hipStream_t st);
 
 // conv_wino.hip: 3x3/s1 SAME convolution as Winograd F(2x2,3x3); U = G g G^T blocked [N/64][C/8][16][2][64][4], V workspace of
 // hpe_wino_v_floats(B, H, W, C) floats; C % 32 == 0, N % 64 == 0

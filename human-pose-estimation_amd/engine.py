@@ -36,7 +36,7 @@ def _require_cuda_tensor(t, name, shape_tail=None):
 class HpeEngine(object):
     def __init__(self, device=0, max_batch=8, num_stage=3, bn_eps=1e-3, encoder_dtype="fp32", **plan_options):
         """plan_options: the HpeConfig plan fields of include/hpe.h (n_streams, dual_gemm, stem_fused, wino_min_c, wino_min_items,
-        wino_fused, wino_fused_min_hw, mesh_a2b, wino_f4, wino4_fused, bf16_p8, wino4_ksplit, chain_fuse, halo3); unset = -1 = the library default (environment variable, else built-in).
+        wino_fused, wino_fused_min_hw, mesh_a2b, wino_f4, wino4_fused, bf16_p8, wino4_ksplit, chain_fuse, halo3, f32_split); unset = -1 = the library default (environment variable, else built-in).
         They select WHICH kernels run, per context -- two engines with different options can coexist in one process."""
         self.lib = _lib.load()
         torch = _torch()
@@ -482,7 +482,8 @@ class HpeEngine(object):
     def encoder_kernel_description(self):
         """The kernel family bench.py's `roofline` block prices (one string per encoder dtype, kept next to the dispatch)."""
         if self.encoder_dtype == "fp32":
-            return ("conv_gemm_f32_dma_kernel (the 1x1 / strided / dual-source layers) + w4_input_kernel + w4_gemm_kernel / w4_gemm32_kernel "
+            return ("conv_gemm_f32s_dma_kernel (the 1x1 / strided / dual-source layers of stages 3-5 on the bf16 matrix cores, operands split "
+                    "exactly into three bf16 pieces) + conv_gemm_f32_dma_kernel (the other 1x1 layers) + w4_input_kernel + w4_gemm_kernel / w4_gemm32_kernel "
                     "(the 13 3x3 layers on the 28x28 / 14x14 / 7x7 maps as fp32 Winograd F(4x4,3x3); F(2x2,3x3) / direct below 64 work "
                     "items) + wino_fused_kernel (the three 56x56 3x3 layers, F(2x2,3x3)) + stem_fused_f32_kernel -- the 53 conv layers of one "
                     "step, priced at their direct-convolution FLOPs")

@@ -91,6 +91,10 @@ typedef struct HpeConfig {
                             *                      the activation tile + halo staged in LDS once per 64 input channels, the 9 taps read it at 9
                             *                      row shifts) instead of the implicit GEMM: bit mask as wino_f4 (1 = 7x7 ... 8 = 56x56) (15); same
                             *                      operands and rounding points, fp32 summation order differs */
+    int f32_split;         /* HPE_F32_SPLIT        fp32 encoder: stages (1 = stage 2, 2 = stage 3, 4 = stage 4, 8 = stage 5) whose 1x1 / strided /
+                            *                      dual-source layers run on the bf16 matrix cores with both operands split exactly into three bf16
+                            *                      pieces (conv_gemm_f32s.hip: fp32-exact products, fp32 accumulation; whole-tile launches only, small
+                            *                      grids keep the fp32 kernel) (14); 0 = the fp32 MFMA everywhere */
 } HpeConfig;
 
 /* defaults: struct_size = sizeof(HpeConfig), device 0, max_batch 8, num_stage 3, bn_eps 1e-3, fp32, every plan option -1.
