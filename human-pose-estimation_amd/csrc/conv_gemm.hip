@@ -9,11 +9,10 @@
 // the bottleneck fused in the epilogue, and the three Dense layers of RegressionNetwork
 // (reference: src/models.py:60-74; y = x @ kernel + bias is the scale == 1 case).
 //
-// Two kernels share the tiling and the epilogue:
-//   conv_gemm_f32_dma_kernel  (default)  LDS-DMA staged: global_load_lds_dwordx4 writes the k-slabs straight into LDS,
-//                                        bank spread by an XOR swizzle on the per-lane source address.
-//   conv_gemm_f32_kernel      (HPE_STAGE=reg, kept for A/B and for the schedule ablations of DESIGN.md §4)
-//                                        register staged: global_load_dwordx4 -> VGPR -> ds_write_b128, padded LDS pitch.
+// conv_gemm_f32_dma_kernel is LDS-DMA staged: global_load_lds_dwordx4 writes the k-slabs straight into LDS, bank spread by an XOR
+// swizzle on the per-lane source address.  (Rounds 1-4 also carried a register-staged kernel -- global_load_dwordx4 -> VGPR ->
+// ds_write_b128, padded LDS pitch -- for A/B runs and the schedule ablations of DESIGN.md §4; no configuration selected it and it was
+// removed.)
 //
 // CDNA4 mapping
 //   * v_mfma_f32_32x32x2_f32: exact-fp32 matrix FMA (64 FLOP/clk/SIMD = the fp32 roofline, 157.3 TF).
@@ -21,8 +20,7 @@
 //   * A (activations) and W (weights, pre-packed [n][k] on the host at load time) are both staged in LDS
 //     as [row][32 k] slabs (one 128-B line per row): one ds_read_b128 per lane then feeds FOUR MFMAs
 //     (lanes 0-31 hold k = 8g..8g+3, lanes 32-63 hold k = 8g+4..8g+7 -- k is only a summation label,
-//     A and B use the same labelling); the 16-lane b128 groups are bank-conflict-free (36-float pitch in the
-//     register-staged kernel, source-side XOR swizzle in the DMA kernel).
+//     A and B use the same labelling); the 16-lane b128 groups are bank-conflict-free (source-side XOR swizzle).
 //   * double buffered: the loads of slab s+1 are in flight while slab s is multiplied; one barrier per slab.
 //   * 64-wide waves in a WM x WN grid, each wave owns an (MT*32) x (NT*32) accumulator block; 4 or 8 waves.
 //   * epilogue: BN scale/shift in registers, transpose through the (free) staging LDS, 16 B/lane row stores with the
@@ -31,364 +29,16 @@
 //     on ONE XCD (blocks b, b+8, ... share an L2), so the panel is fetched from HBM once.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "conv_gemm_common.h"
 #include "hpe_internal.h"
 
-#define LDS_PITCH 36  // floats; 144 B row pitch -> conflict-free ds_read_b128 (see header comment)
-
 namespace {
-
-template <int MODE>
-__device__ __forceinline__ f32x4 load_a(const GemmArgs& p, const RowAddr& r, const SlabPos& sp) {
-    if (MODE == GEMM_CONV3) {
-        // branch-free: out-of-image taps read the (always valid) centre pixel and are zeroed by a select
-        const bool ok = (r.mask >> sp.tap) & 1u;
-        f32x4 v = *reinterpret_cast<const f32x4*>(p.x + (r.base + (ok ? sp.off : sp.cs * BK)));
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        return ok ? v : z;
-    }
-    return *reinterpret_cast<const f32x4*>(p.x + (r.base + sp.off));
-}
-
-template <int MODE, int BM, int BN, int WM, int WN, int SCHED>
-__global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(GemmArgs p) {
-    constexpr int MT = BM / WM / 32;
-    constexpr int NT = BN / WN / 32;
-    constexpr int AP = BM / 32;  // A rows staged per thread
-    constexpr int BP = BN / 32;  // W rows staged per thread
-    constexpr int EP = BN + 4;   // epilogue LDS pitch (floats)
-    static_assert(WM * WN == 4, "4 waves per workgroup");
-    static_assert(MT >= 1 && NT >= 1, "tile too small");
-    static_assert(BM * EP <= 2 * (BM + BN) * LDS_PITCH, "epilogue tile must fit the staging LDS");
-
-    __shared__ __attribute__((aligned(16))) float lds[2 * (BM + BN) * LDS_PITCH];
-    constexpr int BUF = (BM + BN) * LDS_PITCH;
-
-    // XCD-aware bijective remap: blocks b, b+8, ... (one XCD) walk consecutive tiles.
-    const int total = p.n_mtiles * p.n_ntiles;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7;
-    const int q = total >> 3, rr = total & 7;
-    const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
-    const int mtile = swz / p.n_ntiles;
-    const int ntile = swz - mtile * p.n_ntiles;
-    const int m0 = mtile * BM;
-    const int n0 = ntile * BN;
-
-    const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int wm = wave / WN;
-    const int wn = wave - wm * WN;
-
-    // ---- staging addresses: thread t stages 16 B (k chunk t&7) of rows (t>>3) + 32*i
-    const int kc4 = (t & 7) * 4;
-    const int srow = t >> 3;
-    RowAddr arow[AP];
-#pragma unroll
-    for (int i = 0; i < AP; ++i) arow[i] = make_row<MODE>(p, m0 + srow + 32 * i, kc4);
-    const float* wptr = p.w + (size_t)(n0 + srow) * p.ldw + kc4;
-    const int lds_st = srow * LDS_PITCH + kc4;
-
-    // ---- fragment read offsets (floats) inside a buffer
-    const int frag = (lane & 31) * LDS_PITCH + 4 * (lane >> 5);
-    const int a_off = (wm * MT * 32) * LDS_PITCH + frag;
-    const int b_off = (BM + wn * NT * 32) * LDS_PITCH + frag;
-
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    f32x4 ra[AP], rb[BP];
-    const int S = p.K / BK;
-    SlabPos sp = slab_first<MODE>(p);
-
-    auto load_slab = [&](int slab) {
-#pragma unroll
-        for (int i = 0; i < AP; ++i) ra[i] = load_a<MODE>(p, arow[i], sp);
-#pragma unroll
-        for (int i = 0; i < BP; ++i) rb[i] = *reinterpret_cast<const f32x4*>(wptr + (size_t)(32 * i) * p.ldw + slab * BK);
-    };
-    auto store_slab = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < AP; ++i) *reinterpret_cast<f32x4*>(&lds[buf + lds_st + 32 * i * LDS_PITCH]) = ra[i];
-#pragma unroll
-        for (int i = 0; i < BP; ++i) *reinterpret_cast<f32x4*>(&lds[buf + lds_st + (BM + 32 * i) * LDS_PITCH]) = rb[i];
-    };
-    auto mma_groups = [&](int buf, int g0, int g1) {
-        const float* A = &lds[buf + a_off];
-        const float* B = &lds[buf + b_off];
-#pragma unroll
-        for (int g = g0; g < g1; ++g) {
-            f32x4 fa[MT], fb[NT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) fa[i] = *reinterpret_cast<const f32x4*>(A + i * 32 * LDS_PITCH + g * 8);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) fb[j] = *reinterpret_cast<const f32x4*>(B + j * 32 * LDS_PITCH + g * 8);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][ks], fb[j][ks], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    // Software pipeline (register staged, LDS double buffered, one barrier per slab):
-    //   iteration s multiplies LDS[s&1]; in the MIDDLE of its MFMA stream it retires the registers that hold
-    //   slab s+1 into LDS[(s+1)&1] (free since the barrier that ended iteration s-1) and immediately re-issues
-    //   the global loads of slab s+2 into the same registers, so every global load has a full iteration to land
-    //   and the LDS writes issue in the shadow of the 64-cycle MFMAs.
-#ifdef HPE_ABLATION
-    unsigned long long t_clk0 = 0, t_rt0 = 0;
-    if (p.dbg) {
-        t_clk0 = __builtin_amdgcn_s_memtime();
-        t_rt0 = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
-    load_slab(0);
-    store_slab(0);
-    if (S > 1) {
-        slab_advance<MODE>(p, sp);
-        load_slab(1);
-    }
-    __syncthreads();
-
-    if (SCHED == 8 || SCHED == 9) {
-        // Fully interleaved steady state, one basic block per slab.  LDS operations keep their source order
-        // (the compiler must assume the staging writes alias the fragment reads), so the source is written in
-        // the order we want them issued: per k-group g (16*MT*NT/4 MFMAs) -> prefetch the fragments of g+1,
-        // multiply g, retire 1/4 of the staged registers into the other LDS buffer and re-issue their global
-        // loads.  sched_group_barrier then pins the MFMAs between those memory instructions so that each
-        // VMEM / DS issue sits in the shadow of a 64-cycle MFMA.
-        constexpr int QA = AP / 4 > 0 ? AP / 4 : 1;  // staged A rows retired per k-group
-        constexpr int QB = BP / 4 > 0 ? BP / 4 : 1;
-        constexpr int GA = AP / QA, GB = BP / QB;    // groups that retire A / B rows (4, or 2 for 64-row tiles)
-        constexpr int MPG = 4 * MT * NT;             // MFMAs per k-group
-        int s = 0;
-        for (; s + 2 < S; ++s) {
-            const int cur = (s & 1) * BUF;
-            const int nxt = BUF - cur;
-            const float* A = &lds[cur + a_off];
-            const float* B = &lds[cur + b_off];
-            slab_advance<MODE>(p, sp);
-            f32x4 fa[2][MT], fb[2][NT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) fa[0][i] = *reinterpret_cast<const f32x4*>(A + i * 32 * LDS_PITCH);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) fb[0][j] = *reinterpret_cast<const f32x4*>(B + j * 32 * LDS_PITCH);
-#define HPE_KGROUP(G)                                                                                                  \
-    {                                                                                                                  \
-        if (G < 3) {                                                                                                   \
-            _Pragma("unroll") for (int i = 0; i < MT; ++i) fa[(G + 1) & 1][i] =                                        \
-                *reinterpret_cast<const f32x4*>(A + i * 32 * LDS_PITCH + (G + 1) * 8);                                 \
-            _Pragma("unroll") for (int j = 0; j < NT; ++j) fb[(G + 1) & 1][j] =                                        \
-                *reinterpret_cast<const f32x4*>(B + j * 32 * LDS_PITCH + (G + 1) * 8);                                 \
-        }                                                                                                              \
-        _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) _Pragma("unroll") for (int i = 0; i < MT; ++i)                \
-            _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[i][j] =                                                 \
-                __builtin_amdgcn_mfma_f32_32x32x2f32(fa[G & 1][i][ks], fb[G & 1][j][ks], acc[i][j], 0, 0, 0);          \
-        if (G < GA) {                                                                                                  \
-            _Pragma("unroll") for (int q = 0; q < QA; ++q) {                                                           \
-                const int i = G * QA + q;                                                                              \
-                *reinterpret_cast<f32x4*>(&lds[nxt + lds_st + 32 * i * LDS_PITCH]) = ra[i];                            \
-                ra[i] = load_a<MODE>(p, arow[i], sp);                                                                  \
-            }                                                                                                          \
-        }                                                                                                              \
-        if (G < GB) {                                                                                                  \
-            _Pragma("unroll") for (int q = 0; q < QB; ++q) {                                                           \
-                const int i = G * QB + q;                                                                              \
-                *reinterpret_cast<f32x4*>(&lds[nxt + lds_st + (BM + 32 * i) * LDS_PITCH]) = rb[i];                     \
-                rb[i] = *reinterpret_cast<const f32x4*>(wptr + (size_t)(32 * i) * p.ldw + (s + 2) * BK);               \
-            }                                                                                                          \
-        }                                                                                                              \
-        if (SCHED == 9) {                                                                                              \
-            constexpr int NST = (G < GA ? QA : 0) + (G < GB ? QB : 0);                                                 \
-            if (G < 3) __builtin_amdgcn_sched_group_barrier(0x100, MT + NT, 0);                                        \
-            if constexpr (NST == 0) {                                                                                  \
-                __builtin_amdgcn_sched_group_barrier(0x008, MPG, 0);                                                   \
-            } else {                                                                                                   \
-                _Pragma("unroll") for (int q = 0; q < NST; ++q) {                                                      \
-                    __builtin_amdgcn_sched_group_barrier(0x008, MPG / NST, 0);                                         \
-                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                                                 \
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                                 \
-                }                                                                                                      \
-            }                                                                                                          \
-        }                                                                                                              \
-    }
-            HPE_KGROUP(0)
-            HPE_KGROUP(1)
-            HPE_KGROUP(2)
-            HPE_KGROUP(3)
-#undef HPE_KGROUP
-            __syncthreads();
-        }
-        for (; s < S; ++s) {
-            const int cur = (s & 1) * BUF;
-            mma_groups(cur, 0, 2);
-            if (s + 1 < S) store_slab(BUF - cur);
-            mma_groups(cur, 2, 4);
-            __syncthreads();
-        }
-    } else
-    for (int s = 0; s < S; ++s) {
-        const int cur = (s & 1) * BUF;
-        if (SCHED == 0) {
-            mma_groups(cur, 0, 2);
-            if (s + 1 < S) {
-                store_slab(BUF - cur);
-                if (s + 2 < S) {
-                    slab_advance<MODE>(p, sp);
-                    load_slab(s + 2);
-                }
-            }
-            mma_groups(cur, 2, 4);
-        } else if (SCHED == 1) {
-            mma_groups(cur, 0, 2);
-            __builtin_amdgcn_sched_barrier(0);
-            if (s + 1 < S) {
-                store_slab(BUF - cur);
-                __builtin_amdgcn_sched_barrier(0);
-                if (s + 2 < S) {
-                    slab_advance<MODE>(p, sp);
-                    load_slab(s + 2);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            mma_groups(cur, 2, 4);
-        } else if (SCHED == 6) {  // ablation: global loads, no LDS writes
-            if (s + 2 < S) {
-                slab_advance<MODE>(p, sp);
-                load_slab(s + 2);
-            }
-            mma_groups(cur, 0, 4);
-#pragma unroll
-            for (int i = 0; i < AP; ++i) asm volatile("" ::"v"(ra[i]));
-#pragma unroll
-            for (int i = 0; i < BP; ++i) asm volatile("" ::"v"(rb[i]));
-        } else if (SCHED == 7) {  // ablation: LDS writes, no global loads
-            mma_groups(cur, 0, 2);
-            if (s + 1 < S) store_slab(BUF - cur);
-            mma_groups(cur, 2, 4);
-        } else if (SCHED == 3) {  // ablation: no global loads / LDS writes in the loop (wrong results)
-            mma_groups(cur, 0, 4);
-        } else if (SCHED == 4) {  // ablation: 3 + no barrier
-            mma_groups(0, 0, 4);
-            continue;
-        } else if (SCHED == 5) {  // ablation: MFMA only, operands fixed in registers
-            f32x4 fa[MT], fb[NT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) fa[i] = ra[i % AP];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) fb[j] = rb[j % BP];
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-                    for (int i = 0; i < MT; ++i)
-#pragma unroll
-                        for (int j = 0; j < NT; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][ks], fb[j][ks], acc[i][j], 0, 0, 0);
-            continue;
-        } else {
-            mma_groups(cur, 0, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            if (s + 1 < S) store_slab(BUF - cur);
-            mma_groups(cur, 1, 2);
-            __builtin_amdgcn_sched_barrier(0);
-            if (s + 2 < S) {
-                slab_advance<MODE>(p, sp);
-                load_slab(s + 2);
-            }
-            mma_groups(cur, 2, 3);
-            __builtin_amdgcn_sched_barrier(0);
-            mma_groups(cur, 3, 4);
-        }
-        __syncthreads();
-    }
-
-#ifdef HPE_ABLATION
-    if (p.dbg && t == 0) {
-        p.dbg[2 * bid] = __builtin_amdgcn_s_memtime() - t_clk0;
-        p.dbg[2 * bid + 1] = __builtin_amdgcn_s_memrealtime() - t_rt0;
-    }
-#endif
-    // ---- epilogue.  C/D layout of the 32x32 MFMA: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5).
-    // BN-scale/shift is applied in registers, the tile is transposed through LDS (the staging buffers are
-    // free after the last barrier) and leaves as full rows: 16 B per lane, BN*4 contiguous bytes per row,
-    // with the residual read the same way.
-    {
-        const int col_l = lane & 31;
-        const int row_l = 4 * (lane >> 5);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int cl = (wn * NT + j) * 32 + col_l;
-            const int n = n0 + cl;
-            const bool n_ok = n < p.N;
-            const float sc = n_ok ? p.scale[n] : 0.f;
-            const float sh = n_ok ? p.shift[n] : 0.f;
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const int rl = (wm * MT + i) * 32 + row_l;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) lds[(rl + (e & 3) + 8 * (e >> 2)) * EP + cl] = acc[i][j][e] * sc + sh;
-            }
-        }
-    }
-    __syncthreads();
-    {
-        constexpr int TPR = BN / 4;     // threads per output row
-        constexpr int RPP = 256 / TPR;  // rows per pass
-        const int r = t / TPR;
-        const int c4 = (t - r * TPR) * 4;
-        const int n = n0 + c4;
-        const bool full = (n + 3) < p.N;
-#pragma unroll 4
-        for (int pass = 0; pass < BM / RPP; ++pass) {
-            const int row = pass * RPP + r;
-            const int m = m0 + row;
-            if (m >= p.M || n >= p.N) continue;
-            f32x4 v = *reinterpret_cast<const f32x4*>(&lds[row * EP + c4]);
-            if (full) {
-                if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + (size_t)m * p.ldres + n);
-                if (p.relu) {
-                    v.x = fmaxf(v.x, 0.f);
-                    v.y = fmaxf(v.y, 0.f);
-                    v.z = fmaxf(v.z, 0.f);
-                    v.w = fmaxf(v.w, 0.f);
-                }
-                if (p.y_slab8)
-                    *reinterpret_cast<f32x4*>(p.y + ((size_t)(n >> 3) * p.M + m) * 8 + (n & 7)) = v;
-                else
-                    *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.ldy + n) = v;
-            } else {
-                const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (n + u < p.N) {
-                        float o = vv[u];
-                        if (p.res) o += p.res[(size_t)m * p.ldres + n + u];
-                        if (p.relu) o = fmaxf(o, 0.f);
-                        p.y[(size_t)m * p.ldy + n + u] = o;
-                    }
-                }
-            }
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // LDS-DMA staged variant: `global_load_lds_dwordx4` writes each 16-B chunk straight into LDS (no VGPR round trip,
-// no ds_write).  A wave-instruction fills 1 KiB = 8 unpadded 128-B rows; the bank spread the padded pitch gave the
-// register-staged kernel comes from an XOR swizzle applied on the per-lane SOURCE address instead:
+// no ds_write).  A wave-instruction fills 1 KiB = 8 unpadded 128-B rows; the bank spread that a padded pitch would give
+// comes from an XOR swizzle applied on the per-lane SOURCE address instead:
 // LDS chunk c of row r holds logical chunk c ^ ((r >> 1) & 7), and the fragment read applies the same XOR, which
 // makes every 16-lane ds_read_b128 group hit 16 distinct 16-B slots of the 256-B bank row.
 template <int MODE, int BM, int BN, int WM, int WN>
@@ -615,60 +265,22 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_fixup_kernel(GemmArgs 
     conv_epilogue<BM, BN, WM, WN>(p, lds, acc, mtile * BM, ntile * BN, t, lane, wm, wn, no_pre, false);
 }
 
-// environment knobs of the launcher: read once, in a thread-safe function-local static initialiser
-int stage_variant() {
-    static const int v = [] {
-        const char* e = getenv("HPE_STAGE");
-        return (e && e[0] == 'r') ? 0 : 1;  // "reg" = register staged, default = LDS-DMA
-    }();
-    return v;
-}
-
-int sched_variant() {
-    static const int v = [] {
-        const char* e = getenv("HPE_SCHED");
-        const int x = e ? atoi(e) : 0;
-        return (x < 0 || x > 9) ? 0 : x;
-    }();
-    return v;
-}
-
-int splitk_enabled() {
-    static const int v = [] {
-        const char* e = getenv("HPE_SPLITK");
-        return e ? atoi(e) : 1;
-    }();
-    return v;
-}
-
 template <int MODE, int BM, int BN, int WM, int WN>
-hipError_t launch_cfg(GemmArgs& p, hipStream_t st) {
+hipError_t launch_cfg(GemmArgs& p, int splitk_min_slabs, hipStream_t st) {
     p.n_mtiles = (p.M + BM - 1) / BM;
     p.n_ntiles = (p.N + BN - 1) / BN;
     const int grid = p.n_mtiles * p.n_ntiles;
     p.split_k = 1;
     if constexpr (WM * WN == 8) {
-        static const int res_prefetch = [] {
-            const char* e = getenv("HPE_RES_PREFETCH");
-            return e ? atoi(e) : 1;
-        }();
-        p.res_prefetch = res_prefetch;
+        p.res_prefetch = 1;
         hipLaunchKernelGGL((conv_gemm_f32_dma_kernel<MODE, BM, BN, WM, WN>), dim3(grid), dim3(512), 0, st, p);
         return hipGetLastError();
     } else {
-    if ((stage_variant() == 1 && p.zero) || MODE == GEMM_DUAL) {
-        // latency-bound small grids: cut K so that about one workgroup per CU runs (>= 4 slabs per slice)
+        // latency-bound small grids: cut K so that about one workgroup per CU runs, splitk_min_slabs (>= 2, plan option) slabs per slice
         const int S = p.K / BK;
-        // slabs per slice: >= 4 (HPE_SPLITK_SLABS; a slice shorter than that is all launch ramp).  Every split layer pays a second,
-        // dependent launch (the fix-up), which costs a single frame about what 6-8 more slabs in the main loop cost.
-        static const int min_slabs = [] {
-            const char* e = getenv("HPE_SPLITK_SLABS");
-            const int v = e ? atoi(e) : 4;
-            return v < 2 ? 2 : v;
-        }();
-        if (p.partial && splitk_enabled() && grid < 128 && S >= 2 * min_slabs) {
+        if (p.partial && grid < 128 && S >= 2 * splitk_min_slabs) {
             int sk = 256 / grid;
-            if (sk > S / min_slabs) sk = S / min_slabs;
+            if (sk > S / splitk_min_slabs) sk = S / splitk_min_slabs;
             if (sk > 16) sk = 16;
             while (sk > 1 && (size_t)grid * sk * BM * BN > p.partial_floats) --sk;
             if (sk > 1) p.split_k = sk;
@@ -679,36 +291,18 @@ hipError_t launch_cfg(GemmArgs& p, hipStream_t st) {
         hipLaunchKernelGGL((conv_gemm_fixup_kernel<BM, BN, WM, WN>), dim3(grid), dim3(256), 0, st, p);
         return hipGetLastError();
     }
-    if constexpr (MODE == GEMM_DUAL) return hipErrorInvalidValue;  // (not reached: the dual-source mode is LDS-DMA only)
-    else
-    switch (sched_variant()) {
-        case 1: hipLaunchKernelGGL((conv_gemm_f32_kernel<MODE, BM, BN, WM, WN, 1>), dim3(grid), dim3(256), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((conv_gemm_f32_kernel<MODE, BM, BN, WM, WN, 2>), dim3(grid), dim3(256), 0, st, p); break;
-#ifdef HPE_ABLATION
-        case 3: hipLaunchKernelGGL((conv_gemm_f32_kernel<MODE, BM, BN, WM, WN, 3>), dim3(grid), dim3(256), 0, st, p); break;
-        case 4: hipLaunchKernelGGL((conv_gemm_f32_kernel<MODE, BM, BN, WM, WN, 4>), dim3(grid), dim3(256), 0, st, p); break;
-        case 5: hipLaunchKernelGGL((conv_gemm_f32_kernel<MODE, BM, BN, WM, WN, 5>), dim3(grid), dim3(256), 0, st, p); break;
-        case 6: hipLaunchKernelGGL((conv_gemm_f32_kernel<MODE, BM, BN, WM, WN, 6>), dim3(grid), dim3(256), 0, st, p); break;
-        case 7: hipLaunchKernelGGL((conv_gemm_f32_kernel<MODE, BM, BN, WM, WN, 7>), dim3(grid), dim3(256), 0, st, p); break;
-        case 8: hipLaunchKernelGGL((conv_gemm_f32_kernel<MODE, BM, BN, WM, WN, 8>), dim3(grid), dim3(256), 0, st, p); break;
-        case 9: hipLaunchKernelGGL((conv_gemm_f32_kernel<MODE, BM, BN, WM, WN, 9>), dim3(grid), dim3(256), 0, st, p); break;
-#endif
-        default: hipLaunchKernelGGL((conv_gemm_f32_kernel<MODE, BM, BN, WM, WN, 0>), dim3(grid), dim3(256), 0, st, p); break;
-    }
-    return hipGetLastError();
-    }
 }
 
 template <int MODE>
-hipError_t launch_mode(GemmArgs& p, int tile, hipStream_t st) {
+hipError_t launch_mode(GemmArgs& p, int tile, int splitk_min_slabs, hipStream_t st) {
     switch (tile) {
-        case TILE_128x128: return launch_cfg<MODE, 128, 128, 2, 2>(p, st);
-        case TILE_128x64: return launch_cfg<MODE, 128, 64, 2, 2>(p, st);
-        case TILE_64x64: return launch_cfg<MODE, 64, 64, 2, 2>(p, st);
-        case TILE_64x128: return launch_cfg<MODE, 64, 128, 2, 2>(p, st);
-        case TILE_128x128_W8: return launch_cfg<MODE, 128, 128, 2, 4>(p, st);
-        case TILE_128x64_W8: return launch_cfg<MODE, 128, 64, 4, 2>(p, st);
-        case TILE_256x128_W8: return launch_cfg<MODE, 256, 128, 4, 2>(p, st);
+        case TILE_128x128: return launch_cfg<MODE, 128, 128, 2, 2>(p, splitk_min_slabs, st);
+        case TILE_128x64: return launch_cfg<MODE, 128, 64, 2, 2>(p, splitk_min_slabs, st);
+        case TILE_64x64: return launch_cfg<MODE, 64, 64, 2, 2>(p, splitk_min_slabs, st);
+        case TILE_64x128: return launch_cfg<MODE, 64, 128, 2, 2>(p, splitk_min_slabs, st);
+        case TILE_128x128_W8: return launch_cfg<MODE, 128, 128, 2, 4>(p, splitk_min_slabs, st);
+        case TILE_128x64_W8: return launch_cfg<MODE, 128, 64, 4, 2>(p, splitk_min_slabs, st);
+        case TILE_256x128_W8: return launch_cfg<MODE, 256, 128, 4, 2>(p, splitk_min_slabs, st);
         default: return hipErrorInvalidValue;
     }
 }
@@ -716,9 +310,10 @@ hipError_t launch_mode(GemmArgs& p, int tile, hipStream_t st) {
 }  // namespace
 
 // Host-side shape contract (checked here so a bad plan cannot fault on the device).
-hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, hipStream_t st) {
+hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, int splitk_min_slabs, hipStream_t st) {
+    if (splitk_min_slabs < 2) return hipErrorInvalidValue;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.K % BK) != 0 || (p.ldw % 4) != 0 || p.ldw < p.K) return hipErrorInvalidValue;
-    if (!p.x || !p.w || !p.y || !p.scale || !p.shift) return hipErrorInvalidValue;
+    if (!p.x || !p.w || !p.y || !p.scale || !p.shift || !p.zero) return hipErrorInvalidValue;
     // vector epilogue: 16-B aligned rows of y / residual
     if ((p.ldy % 4) != 0 || ((uintptr_t)p.y & 15) != 0) return hipErrorInvalidValue;
     if (p.y_slab8 && (p.N % 8) != 0) return hipErrorInvalidValue;
@@ -730,24 +325,24 @@ hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, hipStream_t st) {
     switch (mode) {
         case GEMM_DENSE:
             if (p.lda < p.K || (p.lda % 4) != 0) return hipErrorInvalidValue;
-            return launch_mode<GEMM_DENSE>(p, tile, st);
+            return launch_mode<GEMM_DENSE>(p, tile, splitk_min_slabs, st);
         case GEMM_STRIDED:
             if (p.Cin != p.K || (p.Cin % 4) != 0) return hipErrorInvalidValue;
             if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_mode<GEMM_STRIDED>(p, tile, st);
+            return launch_mode<GEMM_STRIDED>(p, tile, splitk_min_slabs, st);
         case GEMM_CONV3:
             if ((p.Cin % BK) != 0 || p.K != 9 * p.Cin || p.cin_slabs != p.Cin / BK || p.Ho != p.Hi || p.Wo != p.Wi)
                 return hipErrorInvalidValue;
-            return launch_mode<GEMM_CONV3>(p, tile, st);
+            return launch_mode<GEMM_CONV3>(p, tile, splitk_min_slabs, st);
         case GEMM_STEM:
             if (p.K != 7 * BK || p.Hi < 2 * (p.Ho - 1) + 7 || p.Wi < 2 * (p.Wo - 1) + 8) return hipErrorInvalidValue;
-            return launch_mode<GEMM_STEM>(p, tile, st);
+            return launch_mode<GEMM_STEM>(p, tile, splitk_min_slabs, st);
         case GEMM_DUAL:
             if (!p.x2 || ((uintptr_t)p.x2 & 15) != 0 || p.k1_slabs < 1 || p.k1_slabs * BK >= p.K || p.lda < p.k1_slabs * BK || (p.lda % 4) != 0)
                 return hipErrorInvalidValue;
             if (p.Cin != p.K - p.k1_slabs * BK || (p.Cin % 4) != 0 || p.M != (p.M / (p.Ho * p.Wo)) * p.Ho * p.Wo) return hipErrorInvalidValue;
             if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_mode<GEMM_DUAL>(p, tile, st);
+            return launch_mode<GEMM_DUAL>(p, tile, splitk_min_slabs, st);
         default: return hipErrorInvalidValue;
     }
 }

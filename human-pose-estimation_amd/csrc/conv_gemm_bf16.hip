@@ -41,7 +41,7 @@ __device__ __forceinline__ void slab_advance_b(const GemmArgs& p, SlabB& sp) {
 }
 
 // NS = LDS ring depth: NS - 1 slabs in flight behind counted vmcnt waits and a raw s_barrier (one barrier per slab).  NS = 2 is
-// the shipped configuration.  NS = 3 (HPE_NS_BF16=3, kept for the 128x128 and 256x128 tiles) was the experiment "is the slab DMA
+// the shipped configuration.  NS = 3 (instantiated for the 128x128 and 256x128 tiles at the time, removed since) was the experiment "is the slab DMA
 // latency exposed at the bf16 matrix rate?" -- it is not: the deeper ring halves the workgroups per CU (96 KB of LDS) and LOSES
 // 30-45 % on the 3x3 layers (res4*_branch2b 0.080 -> 0.117 ms; profiles/r02/bf16_ring_depth.txt): block-level overlap of two
 // workgroups per CU already hides the DMA, the kernel sits at the ceiling of the one-barrier-per-slab structure.
@@ -291,32 +291,22 @@ template <int MODE, int BM, int BN, int WM, int WN, int NS>
 hipError_t launch_cfg_b(GemmArgs& p, hipStream_t st) {
     p.n_mtiles = (p.M + BM - 1) / BM;
     p.n_ntiles = (p.N + BN - 1) / BN;
-    static const int res_prefetch = [] {
-        const char* e = getenv("HPE_RES_PREFETCH");
-        return e ? atoi(e) : 1;
-    }();
-    p.res_prefetch = res_prefetch;
+    p.res_prefetch = 1;
     hipLaunchKernelGGL((conv_gemm_bf16_dma_kernel<MODE, BM, BN, WM, WN, NS>), dim3(p.n_mtiles * p.n_ntiles), dim3(64 * WM * WN), 0, st, p);
     return hipGetLastError();
 }
 
-// ring depth: 2 everywhere; 3 only on request (HPE_NS_BF16=3) for the two tiles it was measured on
-template <int MODE, int BM, int BN, int WM, int WN>
-hipError_t launch_ns(GemmArgs& p, int ns, hipStream_t st) {
-    if (ns >= 3) return launch_cfg_b<MODE, BM, BN, WM, WN, 3>(p, st);
-    return launch_cfg_b<MODE, BM, BN, WM, WN, 2>(p, st);
-}
-
+// ring depth 2 everywhere: a 3-deep ring lost on the two tiles it was measured on
 template <int MODE>
-hipError_t launch_mode_b(GemmArgs& p, int tile, int ns, hipStream_t st) {
+hipError_t launch_mode_b(GemmArgs& p, int tile, hipStream_t st) {
     switch (tile) {
-        case TILE_128x128: return launch_ns<MODE, 128, 128, 2, 2>(p, ns, st);
+        case TILE_128x128: return launch_cfg_b<MODE, 128, 128, 2, 2, 2>(p, st);
         case TILE_128x64: return launch_cfg_b<MODE, 128, 64, 2, 2, 2>(p, st);
         case TILE_64x64: return launch_cfg_b<MODE, 64, 64, 2, 2, 2>(p, st);
         case TILE_64x128: return launch_cfg_b<MODE, 64, 128, 2, 2, 2>(p, st);
         case TILE_128x128_W8: return launch_cfg_b<MODE, 128, 128, 2, 4, 2>(p, st);
         case TILE_128x64_W8: return launch_cfg_b<MODE, 128, 64, 4, 2, 2>(p, st);
-        case TILE_256x128_W8: return launch_ns<MODE, 256, 128, 4, 2>(p, ns, st);
+        case TILE_256x128_W8: return launch_cfg_b<MODE, 256, 128, 4, 2, 2>(p, st);
         default: return hipErrorInvalidValue;
     }
 }
@@ -413,7 +403,7 @@ inline int grid_for(long total, int block, int cap = 2048) {
 
 }  // namespace
 
-hipError_t hpe_launch_gemm_bf16(GemmArgs p, int mode, int tile, int ns, hipStream_t st) {
+hipError_t hpe_launch_gemm_bf16(GemmArgs p, int mode, int tile, hipStream_t st) {
     if (tile == TILE_P8_256x256) return hpe_launch_gemm_bf16_p8(p, mode, st);
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.K % BKE) != 0 || (p.ldw % 8) != 0 || p.ldw < p.K) return hipErrorInvalidValue;
     if (!p.x || !p.w || !p.y || !p.scale || !p.shift || !p.zero) return hipErrorInvalidValue;
@@ -425,24 +415,24 @@ hipError_t hpe_launch_gemm_bf16(GemmArgs p, int mode, int tile, int ns, hipStrea
     switch (mode) {
         case GEMM_DENSE:
             if (p.lda < p.K || (p.lda % 8) != 0) return hipErrorInvalidValue;
-            return launch_mode_b<GEMM_DENSE>(p, tile, ns, st);
+            return launch_mode_b<GEMM_DENSE>(p, tile, st);
         case GEMM_STRIDED:
             if (p.Cin != p.K || (p.Cin % 8) != 0) return hipErrorInvalidValue;
             if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_mode_b<GEMM_STRIDED>(p, tile, ns, st);
+            return launch_mode_b<GEMM_STRIDED>(p, tile, st);
         case GEMM_CONV3:
             if ((p.Cin % BKE) != 0 || p.K != 9 * p.Cin || p.cin_slabs != p.Cin / BKE || p.Ho != p.Hi || p.Wo != p.Wi)
                 return hipErrorInvalidValue;
-            return launch_mode_b<GEMM_CONV3>(p, tile, ns, st);
+            return launch_mode_b<GEMM_CONV3>(p, tile, st);
         case GEMM_STEM:
             if (p.K != 4 * BKE || p.Hi < 2 * (p.Ho - 1) + 8 || p.Wi < 2 * (p.Wo - 1) + 8) return hipErrorInvalidValue;
-            return launch_mode_b<GEMM_STEM>(p, tile, ns, st);
+            return launch_mode_b<GEMM_STEM>(p, tile, st);
         case GEMM_DUAL:
             if (!p.x2 || ((uintptr_t)p.x2 & 15) != 0 || p.k1_slabs < 1 || p.k1_slabs * BKE >= p.K || p.lda < p.k1_slabs * BKE || (p.lda % 8) != 0)
                 return hipErrorInvalidValue;
             if (p.Cin != p.K - p.k1_slabs * BKE || (p.Cin % 8) != 0 || p.M != (p.M / (p.Ho * p.Wo)) * p.Ho * p.Wo) return hipErrorInvalidValue;
             if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_mode_b<GEMM_DUAL>(p, tile, ns, st);
+            return launch_mode_b<GEMM_DUAL>(p, tile, st);
         default: return hipErrorInvalidValue;
     }
 }

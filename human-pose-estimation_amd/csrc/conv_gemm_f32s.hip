@@ -224,11 +224,7 @@ hipError_t launch_cfg(GemmArgs& p, hipStream_t st) {
     p.n_mtiles = (p.M + BM - 1) / BM;
     p.n_ntiles = (p.N + BN - 1) / BN;
     p.split_k = 1;
-    static const int res_prefetch = [] {
-        const char* e = getenv("HPE_RES_PREFETCH");
-        return e ? atoi(e) : 1;
-    }();
-    p.res_prefetch = res_prefetch;
+    p.res_prefetch = 1;
     hipLaunchKernelGGL((conv_gemm_f32s_dma_kernel<MODE, BM, BN, WM, WN>), dim3(p.n_mtiles * p.n_ntiles), dim3(64 * WM * WN), 0, st, p);
     return hipGetLastError();
 }

@@ -878,7 +878,7 @@ int hpe_wino4_items(int B, int H, int W, int N) {
 }
 
 hipError_t hpe_launch_wino4_conv3(const float* x, int lda, const float* U, const float* scale, const float* shift, float* y, int ldy, int B,
-                                  int H, int W, int C, int N, int relu, float* V, hipStream_t st, int co_running, float* split_ws) {
+                                  int H, int W, int C, int N, int relu, float* V, hipStream_t st, int co_running, float* split_ws, int n32_below, int abl) {
     if (C % 32 != 0 || N % 64 != 0 || lda % 4 != 0 || ldy % 4 != 0 || B < 1 || H < 1 || W < 1 || !x || !U || !V || !y) return hipErrorInvalidValue;
     const int TH = (H + 3) / 4, TW = (W + 3) / 4, TT = TH * TW;
     const long Tl = (long)B * TT;
@@ -909,11 +909,8 @@ hipError_t hpe_launch_wino4_conv3(const float* x, int lda, const float* U, const
     p.n_nt = N / W4_N;
     p.ldy = ldy;
     p.relu = relu;
+    (void)abl;
 #ifdef HPE_ABLATION
-    static const int abl = [] {
-        const char* e = getenv("HPE_W4_ABL");
-        return e ? atoi(e) : 0;
-    }();
     const dim3 g(p.n_tb * p.n_nt), b(W4_THREADS);
     switch (abl) {
         case 1: hipLaunchKernelGGL(w4_gemm_kernel<1>, g, b, W4_LDS_BYTES, st, p); return hipGetLastError();
@@ -927,20 +924,13 @@ hipError_t hpe_launch_wino4_conv3(const float* x, int lda, const float* U, const
 #endif
     // Fewer 64-cout workgroups on the device than CUs -- this launch's, times the batch chunks running beside it on other streams -- :
     // the 32-cout variant (twice the workgroups, two per CU).  From 256 = one per CU on the 64-cout kernel is the faster one
-    // (profiles/r03/w4_n32_ab.txt).  HPE_WINO4_N32: workgroup count below which the variant is used (0 = never)
-    static const int n32_below = [] {
-        const char* e = getenv("HPE_WINO4_N32");
-        return e ? atoi(e) : 256;
-    }();
+    // (profiles/r03/w4_n32_ab.txt).  n32_below: workgroup count below which the variant is used (0 = never)
     p.ksplit = 1;
     if (p.n_tb * p.n_nt * (co_running > 1 ? co_running : 1) < n32_below) {
         // Still fewer workgroups than half the CUs, and a long C axis (the 7x7 layers up to ~64 images: 128 slabs = a 0.14 ms chain of
         // barriers whatever the batch): cut C into 2-4 parts of >= 16 slabs.  Needs a workspace that no concurrent launch uses (the caller
-        // passes one per chunk stream; nullptr = plan option wino4_ksplit off).  HPE_WINO4_KSPLIT_WGS: workgroups on the device to aim for.
-        static const int ksplit_wgs = [] {
-            const char* e = getenv("HPE_WINO4_KSPLIT_WGS");
-            return e ? atoi(e) : 512;  // two 6-wave workgroups per CU
-        }();
+        // passes one per chunk stream; nullptr = plan option wino4_ksplit off).  ksplit_wgs: workgroups on the device to aim for.
+        constexpr int ksplit_wgs = 512;  // two 6-wave workgroups per CU
         const int wgs = p.n_tb * p.n_nt * 2 * (co_running > 1 ? co_running : 1);  // on the device, with the co-running chunks' launches
         if (split_ws && 2 * wgs <= ksplit_wgs) {
             int ks = ksplit_wgs / wgs;

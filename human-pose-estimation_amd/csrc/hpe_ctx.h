@@ -1,0 +1,186 @@
+// hpe_ctx.h -- the context behind the C ABI of include/hpe.h and what its translation units share: the layer table, the per-layer
+// weights, error reporting, device selection and allocation helpers.  hpe_plan.hip resolves the plan, hpe_finalize.hip packs the weights and
+// sizes the workspaces, hpe_encoder.hip holds the launch sequences, hpe_api.hip the extern "C" entry points.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/hpe.h"
+#include "hpe_internal.h"
+#include "hpe_plan.h"
+
+// sets the thread-local message of hpe_last_error() and returns code
+int fail(int code, const std::string& msg);
+
+#define HIP_TRY(expr)                                                                                             \
+    do {                                                                                                          \
+        hipError_t _e = (expr);                                                                                   \
+        if (_e != hipSuccess)                                                                                     \
+            return fail(HPE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" +      \
+                                         std::to_string(__LINE__) + ")");                                         \
+    } while (0)
+
+struct ConvSpec {
+    char name[24];
+    char bn[24];
+    int kh, kw, cin, cout, stride, hin, hout;
+};
+
+// ResNet-50 v1 layer table, Keras names / order [2a, 2b, 2c, (1)] per block.
+const std::vector<ConvSpec>& specs();
+
+inline int round_up(int x, int m) { return ((x + m - 1) / m) * m; }
+
+struct ConvLayer {
+    std::vector<float> kernel, bias, gamma, beta, mean, var;  // host staging (Keras layouts)
+    bool loaded = false;
+    float* w = nullptr;  // device, packed [n_pad][k_pad] (fp32) or bf16 [n_pad][k_pad16] in bf16 mode
+    float* scale = nullptr;
+    float* shift = nullptr;
+    // *_branch2c of a conv_block only: [scale2c * W2c | scale1 * W1] concatenated along k and the summed shifts -- the expand
+    // convolution and the projection shortcut as one dual-source GEMM (GEMM_DUAL)
+    float* w_dual = nullptr;
+    float* shift_dual = nullptr;
+    int k_dual = 0, k1_dual = 0;
+    // plan option f32_split: the fp32 weights of the 1x1 layers split exactly into three bf16 pieces, [n_pad][3][k] (conv_gemm_f32s.hip)
+    void* w_split = nullptr;
+    void* w_dual_split = nullptr;
+    void* stem_w = nullptr;   // conv1 only: weights in the k enumeration of stem_fused.hip (fp32 [64][160] / bf16 [64][7][32])
+    float* wino_u = nullptr;  // device, G g G^T in the blocked layout of conv_wino.hip (3x3 layers on the Winograd path only)
+    float* wino4_u = nullptr;  // device, the F(4x4,3x3) G g G^T in the blocked layout of conv_wino4.hip (layers selected by wino_f4)
+    int n_pad = 0, k_pad = 0;
+};
+
+inline unsigned short f2bf(float f) {  // round-to-nearest-even fp32 -> bf16 (finite inputs)
+    unsigned u;
+    memcpy(&u, &f, 4);
+    return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+struct DenseLayer {
+    std::vector<float> kernel, bias;
+    bool loaded = false;
+};
+
+constexpr int STEM_HP = 230;  // 224 + 2*3
+constexpr int STEM_WP = 232;  // 224 + 2*3 + 2 (8th tap column of the last window, zero weights)
+constexpr int THETA_LD = 96;  // theta rows padded to 3 k-slabs of 32
+// Winograd V workspace: image-major with this per-image pitch; a chunk of >= 32 images starting at image i0 owns
+// [i0 * pitch, (i0 + n) * pitch): n * 802816 floats of transformed tiles (16 * tiles * C <= 802816 per image for every
+// 3x3 layer) + up to 63 padding tiles * 16 * 512 = 516096 floats <= n * 16384
+constexpr size_t WINO_V_PITCH = 802816 + 16384;
+constexpr size_t WINO_V_SLACK = 524288;
+
+
+struct hpe_ctx {
+    HpeConfig cfg{};
+    bool finalized = false;
+    bool dead = false;  // hpe_finalize failed part-way: everything it had allocated was released, the ctx can only be destroyed
+    HpePlan plan;       // every option that chooses a kernel or a launch shape: resolved once, in hpe_finalize (hpe_plan.h)
+    bool bf16 = false;  // encoder_dtype == 1
+    bool have_encoder = false, have_regressor = false, have_smpl = false;
+    ConvLayer conv[HPE_NUM_CONV];
+    DenseLayer dense[HPE_NUM_DENSE];
+    // SMPL host staging
+    bool smpl_loaded = false, mean_loaded = false;
+    std::vector<float> h_vt, h_sd, h_pd, h_jreg, h_w, h_kreg;
+    std::vector<int> h_par;
+    int num_kp = 19;
+    float h_mean[HPE_THETA_DIM];
+    // device: regressor
+    float *w1f = nullptr, *w1t = nullptr, *w2 = nullptr, *w3 = nullptr, *b1 = nullptr, *b2 = nullptr, *b3 = nullptr;
+    float *ones = nullptr, *zeros = nullptr, *mean_dev = nullptr;
+    // device: SMPL
+    SmplDev smpl{};
+    SmplWork work{};
+    float* smpl_basis_src = nullptr;  // [11][V*3]: v_template | shapedirs^T
+    // device: activations
+    float *padded = nullptr, *X0 = nullptr, *X1 = nullptr, *T1 = nullptr, *T2 = nullptr, *SC = nullptr;
+    float *feat = nullptr, *P1 = nullptr, *H1 = nullptr, *H2 = nullptr, *thA = nullptr, *thB = nullptr;
+    float* loss_ws = nullptr;
+    size_t loss_ws_floats = 0;
+    std::vector<void*> allocs;
+    // batch-chunk streams
+    float* partial = nullptr;  // split-K workspace (small grids only run unchunked on the caller's stream)
+    size_t partial_floats = 0;
+    float* wino_v = nullptr;  // Winograd input-transform workspace (nullptr: direct convolution everywhere)
+    float* wino_ws = nullptr;       // stream-K parking space, one slot of n_cu workgroups per chunk stream (nullptr: plain grid)
+    unsigned* wino_flags = nullptr;
+    unsigned* dev_err = nullptr;  // device error word (bit 0: a stream-K wait timed out -> wrong output), see hpe_device_status
+    unsigned wino_epoch = 0;
+    int n_cu = 0;
+    bool loss_attr_done = false;  // per-device kernel attributes of the loss kernels set (hpe_finalize, or the first loss call of a loss-only ctx)
+    unsigned long long* loss_counter = nullptr;  // hpe_debug_set_loss_counter
+    hipStream_t aux[3]{};
+    hipEvent_t ev_fork{}, ev_join[3]{};
+    // software pipeline across calls (hpe_forward_pipelined): the regressor + SMPL tail of batch k runs on `tail_st` while the
+    // caller's stream already runs the encoder of batch k+1; features alternate between two buffers, the Dense layers of the tail
+    // have their own split-K workspace
+    hipStream_t tail_st{};
+    hipEvent_t ev_enc{}, ev_tail{}, ev_feat_free[2]{};
+    bool feat_free_valid[2] = {false, false};
+    bool tail_pending = false;
+    unsigned pipe_idx = 0;
+    float* feat_alt = nullptr;
+    int co_running = 1;    // chunk streams of the encoder call being enqueued (launch-size rules of the F(4x4) kernels)
+    float* w4_split = nullptr;  // F(4x4) C-axis split workspaces + counters (4 x hpe_wino4_split_ws_floats: one per chunk-stream slot)
+    float* partial_tail = nullptr;
+    size_t partial_tail_floats = 0;
+    bool dense_on_tail = false;  // set while a pipelined tail is being enqueued: run_dense then uses partial_tail
+    // timing
+    int timing = 0;
+    hipEvent_t ev[8]{};
+    // encoder span of every timed call since hpe_enable_timing (ring of the last SPAN_RING calls): hpe_get_span_stats
+    static constexpr int SPAN_RING = 64;
+    hipEvent_t span0[SPAN_RING]{}, span1[SPAN_RING]{};
+    unsigned span_n = 0;
+    hipEvent_t cev0[HPE_NUM_CONV]{}, cev1[HPE_NUM_CONV]{};
+    hipEvent_t lev0[16]{}, lev1[16]{}, lev_all[2]{};  // hpe_val_losses: around each stage's pixel -> vertex search / the whole call
+    int loss_timed_stages = 0;
+    bool ev_ok = false, timed_valid = false, conv_timed_valid = false;
+};
+
+struct DeviceGuard {
+    int prev = -1;
+    bool changed = false;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard() {
+        if (changed) (void)hipSetDevice(prev);
+    }
+};
+
+int dev_alloc(hpe_ctx* c, float** p, size_t n_floats, bool zero);
+int upload(hpe_ctx* c, float** p, const std::vector<float>& h);
+// fp32 Wt[rows][K] -> bf16 [rows][3][K]: w = w0 + w1 + w2 exactly (finite weights), each piece rounded to nearest even (conv_gemm_f32s.hip)
+int upload_split(hpe_ctx* c, void** p, const std::vector<float>& wt, int rows, int K);
+
+#define HIPE(expr)                               \
+    do {                                         \
+        hipError_t _e = (expr);                  \
+        if (_e != hipSuccess) return _e;         \
+    } while (0)
+
+enum { NEED_ENC = 1, NEED_REG = 2, NEED_SMPL = 4 };
+int check_ready(hpe_ctx* c, int B, int need);
+
+// hpe_finalize.hip
+int finalize_impl(hpe_ctx* c);
+void release_device_state(hpe_ctx* c);  // release everything a (possibly partial) hpe_finalize created
+
+// hpe_encoder.hip
+enum { CONV_OUT_SLAB8 = 1, CONV_IN_SLAB8 = 2, CONV_CONCURRENT = 4 };
+hipError_t run_conv(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
+                    float* wino_v = nullptr, int slot = 0, int flags = 0);
+hipError_t run_chain(hpe_ctx* c, int i2c, bool first, const float* t2, const float* res, int B, float* t3, float* u1, hipStream_t st,
+                     bool u1_slab8 = false);
+hipError_t encoder_impl(hpe_ctx* c, const float* images, int B, float* features, int ldfeat, hipStream_t st);
+hipError_t regress_impl(hpe_ctx* c, const float* th_prev, float* th_next, int B, hipStream_t st);
+hipError_t features_proj(hpe_ctx* c, const float* features, int B, hipStream_t st);
+hipError_t tail_impl(hpe_ctx* c, const float* feat, int B, const HpeOutputs* stage_outs, int n_outs, hipStream_t ts, hipEvent_t feat_free);
+int forward_impl(hpe_ctx* c, const float* images, int B, const HpeOutputs* stage_outs, int n_outs, hipStream_t st, bool pipelined);

@@ -1,0 +1,488 @@
+// hpe_encoder.hip -- the launch sequences: one conv layer / dual-source block / chained pair through the kernel the plan picks, the
+// encoder over batch chunks, the regressor steps and the forward tail.  Host logic only.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "hpe_ctx.h"
+
+// one conv layer (+BN fold, +residual, +ReLU) through the implicit-GEMM kernel
+
+hipError_t run_conv(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
+                    float* wino_v, int slot, int flags) {
+    const ConvSpec& s = specs()[idx];
+    const ConvLayer& L = c->conv[idx];
+    if ((flags & CONV_IN_SLAB8) && use_wino4_fused(c, idx, B))
+        return hpe_launch_wino4_fused_conv3(x, L.wino4_u, L.scale, L.shift, c->zeros, y, s.cout, B, s.hin, s.hin, s.cin, s.cout, relu, st);
+    if (flags & CONV_IN_SLAB8)
+        return hpe_launch_wino_fused_conv3(x, L.wino_u, L.scale, L.shift, c->zeros, y, s.cout, B, s.hin, s.hin, s.cin, s.cout, relu, st);
+    if (wino_v && !res && use_wino4(c, idx, B))
+        return hpe_launch_wino4_conv3(x, s.cin, L.wino4_u, L.scale, L.shift, y, s.cout, B, s.hin, s.hin, s.cin, s.cout, relu, wino_v, st,
+                                      (flags & CONV_CONCURRENT) ? c->co_running : 1,
+                                      c->w4_split && slot >= 0 && slot < 4 ? c->w4_split + (size_t)slot * hpe_wino4_split_ws_floats() : nullptr, c->plan.wino4_n32,
+                                      c->plan.w4_abl);
+    // Winograd needs enough (64-tile x 64-cout) work items to occupy the 256 CUs (one 8-wave workgroup each); below that
+    // the direct kernel with split-K is faster (measured crossover: batch ~32, profiles/r01/g_wino_small_batch.txt)
+    if (L.wino_u && wino_v && !res && s.cin >= c->plan.wino_min_c &&
+        (long)((B * ((s.hin + 1) / 2) * ((s.hin + 1) / 2) + 63) / 64) * (s.cout / 64) >= c->plan.wino_min_items)
+    {
+        WinoStreamK sk{};
+        if (c->wino_ws && slot >= 0 && slot < 4) {
+            sk.ws = c->wino_ws + (size_t)slot * c->n_cu * HPE_WINO_WS_FLOATS;
+            sk.flags = c->wino_flags + (size_t)slot * c->n_cu;
+            sk.epoch = ++c->wino_epoch;
+            if (sk.epoch == 0) sk.epoch = ++c->wino_epoch;
+            sk.n_wg = c->n_cu;
+            sk.err = c->dev_err;
+        }
+        return hpe_launch_wino_conv3(x, s.cin, L.wino_u, L.scale, L.shift, y, s.cout, B, s.hin, s.hin, s.cin, s.cout, relu, wino_v,
+                                     c->wino_ws ? &sk : nullptr, st);
+    }
+    GemmArgs p{};
+    p.x = x;
+    p.w = L.w;
+    p.scale = L.scale;
+    p.shift = L.shift;
+    p.res = res;
+    p.y = y;
+    p.M = B * s.hout * s.hout;
+    p.N = s.cout;
+    p.K = L.k_pad;
+    p.ldw = L.k_pad;
+    p.w_rows = L.n_pad;
+    p.ldy = s.cout;
+    p.ldres = s.cout;
+    p.relu = relu;
+    p.Hi = p.Wi = s.hin;
+    p.Cin = s.cin;
+    p.Ho = p.Wo = s.hout;
+    p.stride = s.stride;
+    p.cin_slabs = s.cin / 32;
+    p.lda = s.cin;
+    p.zero = c->zeros;
+    p.y_slab8 = (flags & CONV_OUT_SLAB8) ? 1 : 0;
+    // The ctx has ONE split-K workspace: only a launch that is alone on the device may use it.  Batch chunks running on
+    // concurrent streams (CONV_CONCURRENT) never split K, whatever their size (their grids overlap each other instead).
+    if (!(flags & CONV_CONCURRENT)) {
+        p.partial = c->partial;
+        p.partial_floats = c->partial_floats;
+    }
+    int mode;
+    if (idx == 0) {
+        mode = GEMM_STEM;
+        p.Hi = STEM_HP;
+        p.Wi = STEM_WP;
+        p.Cin = 4;
+    } else if (s.kh == 3) {
+        mode = GEMM_CONV3;
+    } else if (s.stride == 1) {
+        mode = GEMM_DENSE;
+    } else {
+        mode = GEMM_STRIDED;
+    }
+    if (c->bf16 && mode == GEMM_CONV3 && !res && s.stride == 1 && (c->plan.halo3 & f4_bit(s.hin) ? true : false) &&
+        hpe_halo3_bf16_supported(s.hin, s.cin, s.cout) && L.k_pad >= 9 * s.cin)
+    {
+        Halo3Args h{};
+        h.x = reinterpret_cast<const __bf16*>(x);
+        h.w = reinterpret_cast<const __bf16*>(L.w);
+        h.scale = L.scale;
+        h.shift = L.shift;
+        h.y = reinterpret_cast<__bf16*>(y);
+        h.M = p.M;
+        h.N = s.cout;
+        h.ldw = L.k_pad;
+        h.relu = relu;
+        h.two = c->plan.halo3_two;
+        return hpe_launch_halo3_bf16(h, s.hin, s.cin, st);
+    }
+    if (c->bf16) {
+        p.cin_slabs = s.cin / 64;
+        return hpe_launch_gemm_bf16(p, mode, pick_bf16(c->plan, p.M, p.N, p.K, mode == GEMM_DENSE && res != nullptr && s.cout == 4 * s.cin, (flags & CONV_CONCURRENT) != 0, mode), st);
+    }
+    const bool expand = mode == GEMM_DENSE && res != nullptr && s.cout == 4 * s.cin;
+    const int f32s = (mode == GEMM_DENSE || mode == GEMM_STRIDED) ? pick_f32s(c->plan, L.w_split, p.M, p.N, p.K, expand) : -1;
+    if (f32s >= 0) {
+        p.w = static_cast<const float*>(L.w_split);
+        p.ldw = 3 * L.k_pad;
+        p.w_piece = L.k_pad;
+        return hpe_launch_gemm_f32s(p, mode, f32s, st);
+    }
+    return hpe_launch_gemm(p, mode, pick_tile(c->plan, p.M, p.N, p.K, expand, (flags & CONV_CONCURRENT) != 0), c->plan.splitk_min_slabs, st);
+}
+
+// branch2c (+BN) + branch1 (+BN) + add + ReLU of a conv_block as one dual-source GEMM: t2 [M, K1] dense, x NHWC strided
+static hipError_t run_dual(hpe_ctx* c, int i2c, int i1, const float* t2, const float* x, int B, float* y, hipStream_t st, int flags) {
+    const ConvSpec& s2 = specs()[i2c];
+    const ConvSpec& s1 = specs()[i1];
+    const ConvLayer& L = c->conv[i2c];
+    const int slab = c->bf16 ? 64 : 32;
+    GemmArgs p{};
+    p.x = t2;
+    p.x2 = x;
+    p.w = L.w_dual;
+    p.scale = c->ones;
+    p.shift = L.shift_dual;
+    p.y = y;
+    p.M = B * s2.hout * s2.hout;
+    p.N = s2.cout;
+    p.K = L.k_dual;
+    p.k1_slabs = L.k1_dual / slab;
+    p.lda = s2.cin;
+    p.ldw = L.k_dual;
+    p.w_rows = round_up(s2.cout, 128);
+    p.ldy = s2.cout;
+    p.relu = 1;
+    p.Hi = p.Wi = s1.hin;
+    p.Cin = s1.cin;
+    p.Ho = p.Wo = s1.hout;
+    p.stride = s1.stride;
+    p.zero = c->zeros;
+    if (!(flags & CONV_CONCURRENT)) {
+        p.partial = c->partial;
+        p.partial_floats = c->partial_floats;
+    }
+    if (c->bf16) {
+        return hpe_launch_gemm_bf16(p, GEMM_DUAL, pick_bf16(c->plan, p.M, p.N, p.K, false, (flags & CONV_CONCURRENT) != 0, GEMM_DUAL), st);
+    }
+    const int f32s = pick_f32s(c->plan, L.w_dual_split, p.M, p.N, p.K, false);
+    if (f32s >= 0) {
+        p.w = static_cast<const float*>(L.w_dual_split);
+        p.ldw = 3 * L.k_dual;
+        p.w_piece = L.k_dual;
+        return hpe_launch_gemm_f32s(p, GEMM_DUAL, f32s, st);
+    }
+    return hpe_launch_gemm(p, GEMM_DUAL, pick_tile(c->plan, p.M, p.N, p.K, false, (flags & CONV_CONCURRENT) != 0), c->plan.splitk_min_slabs, st);
+}
+
+// res: the block input -- the residual of an identity block, the second A source of a conv_block
+hipError_t run_chain(hpe_ctx* c, int i2c, bool first, const float* t2, const float* res, int B, float* t3, float* u1, hipStream_t st,
+                     bool u1_slab8) {
+    const ConvSpec& s2 = specs()[i2c];
+    const int inext = i2c + (first ? 2 : 1);
+    const ConvSpec& sn = specs()[inext];
+    const ConvLayer& L2 = c->conv[i2c];
+    const ConvLayer& Ln = c->conv[inext];
+    if (!c->bf16) {
+        ChainArgsF32 q{};
+        q.t2 = t2;
+        q.res = res;
+        q.w2c = L2.w;
+        q.w2a = Ln.w;
+        q.scaleA = L2.scale;
+        q.shiftA = L2.shift;
+        q.scaleB = Ln.scale;
+        q.shiftB = Ln.shift;
+        q.t3 = t3;
+        q.u1 = u1;
+        q.M = B * s2.hout * s2.hout;
+        q.ldw2c = L2.k_pad;
+        q.ldw2a = Ln.k_pad;
+        q.u1_slab8 = u1_slab8 ? 1 : 0;
+        return hpe_launch_chain_f32(q, s2.cin, s2.cout, sn.cout, st);
+    }
+    ChainArgs p{};
+    p.t2 = reinterpret_cast<const __bf16*>(t2);
+    if (first) {
+        p.x2 = reinterpret_cast<const __bf16*>(res);
+        p.w2c = reinterpret_cast<const __bf16*>(L2.w_dual);
+        p.scaleA = c->ones;
+        p.shiftA = L2.shift_dual;
+        p.ldw2c = L2.k_dual;
+    } else {
+        p.res = reinterpret_cast<const __bf16*>(res);
+        p.w2c = reinterpret_cast<const __bf16*>(L2.w);
+        p.scaleA = L2.scale;
+        p.shiftA = L2.shift;
+        p.ldw2c = L2.k_pad;
+    }
+    p.w2a = reinterpret_cast<const __bf16*>(Ln.w);
+    p.scaleB = Ln.scale;
+    p.shiftB = Ln.shift;
+    p.t3 = reinterpret_cast<__bf16*>(t3);
+    p.u1 = reinterpret_cast<__bf16*>(u1);
+    p.M = B * s2.hout * s2.hout;
+    p.ldw2a = Ln.k_pad;
+    return hpe_launch_chain_bf16(p, s2.cin, s2.cout, sn.cout, first ? specs()[i2c + 1].cin : 0, st);
+}
+
+static hipError_t run_dense(hpe_ctx* c, const float* x, int lda, int M, int K, const float* w, int w_rows, int N, const float* scale,
+                     const float* shift, const float* res, int ldres, int relu, float* y, int ldy, hipStream_t st) {
+    // single frames and very small batches: one launch per layer (the implicit-GEMM kernel would need split-K + a fix-up launch)
+    if (M <= 4) return hpe_launch_dense_gemv(x, lda, M, K, w, N, scale, shift, res, ldres, relu, y, ldy, st);
+    GemmArgs p{};
+    p.zero = shift;  // any readable 16 B: dense mode never takes the zero-page path
+    // the Dense layers run after the chunk streams have joined; in the pipelined forward they overlap the NEXT batch's encoder,
+    // whose unchunked launches may split K too -> separate workspace
+    p.partial = c->dense_on_tail ? c->partial_tail : c->partial;
+    p.partial_floats = c->dense_on_tail ? c->partial_tail_floats : c->partial_floats;
+    p.x = x;
+    p.w = w;
+    p.scale = scale;
+    p.shift = shift;
+    p.res = res;
+    p.y = y;
+    p.M = M;
+    p.N = N;
+    p.K = K;
+    p.lda = lda;
+    p.ldw = K;
+    p.w_rows = w_rows;
+    p.ldy = ldy;
+    p.ldres = ldres;
+    p.relu = relu;
+    return hpe_launch_gemm(p, GEMM_DENSE, TILE_64x64, c->plan.splitk_min_slabs, st);
+}
+
+static hipError_t timed_conv(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
+                      float* wino_v = nullptr, int slot = 0, int flags = 0) {
+    const bool t2 = c->timing >= 2;
+    if (t2) HIPE(hipEventRecord(c->cev0[idx], st));
+    HIPE(run_conv(c, idx, x, B, res, relu, y, st, wino_v, slot, flags));
+    if (t2) HIPE(hipEventRecord(c->cev1[idx], st));
+    return hipSuccess;
+}
+
+// the encoder on images [i0, i0+B) of the batch (all workspace buffers are image-major)
+static hipError_t encoder_chunk(hpe_ctx* c, const float* images, int i0, int B, float* features, int ldfeat, hipStream_t st, int slot = 0,
+                         bool concurrent = false) {
+    const int cf = concurrent ? CONV_CONCURRENT : 0;
+    // all workspace buffers are image-major; in bf16 mode the same allocations hold bf16 elements (half the bytes)
+    const int esz = c->bf16 ? 2 : 4;
+    auto at = [&](float* base, size_t elems) { return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + elems * esz); };
+    const size_t o_img = (size_t)i0 * HPE_IMG_SIZE * HPE_IMG_SIZE * 3;
+    const size_t o_pad = (size_t)i0 * STEM_HP * STEM_WP * 4;
+    const size_t o_big = (size_t)i0 * 802816;
+    const size_t o_mid = (size_t)i0 * 200704;
+    float* padded = at(c->padded, o_pad);
+    float* SC = at(c->SC, o_big);
+    float* T1 = at(c->T1, o_mid);
+    float* T2 = at(c->T2, o_mid);
+    float* cur = at(c->X0, o_big);
+    float* nxt = at(c->X1, o_big);
+    // the chunk's slice of the Winograd workspace (chunks of < 32 images only occur unchunked, i0 == 0: the slack at the end covers them)
+    float* wv = (c->wino_v && (i0 == 0 || B >= 32)) ? c->wino_v + (size_t)i0 * WINO_V_PITCH : nullptr;
+    // the fused stem stages whole 16-byte chunks of the caller's rows; an images pointer that is only float-aligned (e.g. a
+    // tensor view at an odd offset) takes the pad / im2col / pool path, which reads the images with scalar loads
+    if (c->plan.stem_fused && (reinterpret_cast<uintptr_t>(images + o_img) & 15) == 0) {
+        // conv1_pad .. pool1 in one kernel straight from the caller's images (stem_fused.hip); timed as conv layer 0
+        const bool t2 = c->timing >= 2;
+        if (t2) HIPE(hipEventRecord(c->cev0[0], st));
+        HIPE(hpe_launch_stem_fused(images + o_img, c->conv[0].stem_w, c->conv[0].scale, c->conv[0].shift, cur, B, hpe_stem_fused_pick_rows(B),
+                                   c->bf16 ? 1 : 0, st));
+        if (t2) HIPE(hipEventRecord(c->cev1[0], st));
+    } else if (c->bf16) {
+        HIPE(hpe_launch_pad_input_bf16(images + o_img, padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
+        HIPE(timed_conv(c, 0, padded, B, nullptr, 1, SC, st, nullptr, 0, cf));
+        HIPE(hpe_launch_maxpool_bf16(SC, cur, B, 112, 64, st));
+    } else {
+        HIPE(hpe_launch_pad_input(images + o_img, padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
+        HIPE(timed_conv(c, 0, padded, B, nullptr, 1, SC, st, nullptr, 0, cf));
+        HIPE(hpe_launch_maxpool(SC, cur, B, 112, 64, st));
+    }
+    int ci = 1;
+    const int nblk[4] = {3, 4, 6, 3};
+    bool have_2a = false;  // the previous block's chained launch has already written this block's branch2a output to T1
+    for (int stg = 0; stg < 4; ++stg) {
+        for (int b = 0; b < nblk[stg]; ++b) {
+            const bool first = b == 0;
+            const int i2a = ci, i2b = ci + 1, i2c = ci + 2, i1 = ci + 3;
+            const bool fz = use_wino_fused(c, i2b, B) || use_wino4_fused(c, i2b, B);  // then T1 is channel-slab major and never leaves this pair of launches
+            if (have_2a) {
+                if (c->timing >= 2) {
+                    HIPE(hipEventRecord(c->cev0[i2a], st));
+                    HIPE(hipEventRecord(c->cev1[i2a], st));
+                }
+            } else {
+                HIPE(timed_conv(c, i2a, cur, B, nullptr, 1, T1, st, nullptr, 0, cf | (fz ? CONV_OUT_SLAB8 : 0)));
+            }
+            have_2a = false;
+            HIPE(timed_conv(c, i2b, T1, B, nullptr, 1, T2, st, wv, slot, cf | (fz ? CONV_IN_SLAB8 : 0)));
+            const float* res = cur;
+            if (use_chain(c, stg, i2c, first, b + 1 < nblk[stg])) {
+                // identity block followed by an identity block (bf16): relu(bn(W2c t2) + x) and the next block's relu(bn(W2a' .)) in one
+                // launch; the 4C-wide sum is written once and not read back (timed as layer i2c; the next branch2a then shows 0)
+                const bool t2 = c->timing >= 2;
+                if (t2) HIPE(hipEventRecord(c->cev0[i2c], st));
+                // (fp32: the next block's 3x3 layer may be the fused Winograd kernel, which reads its input channel-slab major)
+                const int i2b_next = i2c + (first ? 3 : 2);
+                const bool slab8_next = !c->bf16 && (use_wino_fused(c, i2b_next, B) || use_wino4_fused(c, i2b_next, B));
+                HIPE(run_chain(c, i2c, first, T2, cur, B, nxt, T1, st, slab8_next));
+                if (t2) {
+                    HIPE(hipEventRecord(c->cev1[i2c], st));
+                    if (first) {  // the projection shortcut is inside the launch
+                        HIPE(hipEventRecord(c->cev0[i1], st));
+                        HIPE(hipEventRecord(c->cev1[i1], st));
+                    }
+                }
+                have_2a = true;
+            } else if (first && c->conv[i2c].w_dual) {
+                // conv_block: expand convolution + projection shortcut + add + ReLU as one dual-source GEMM (timed as layer i2c)
+                const bool t2 = c->timing >= 2;
+                if (t2) HIPE(hipEventRecord(c->cev0[i2c], st));
+                HIPE(run_dual(c, i2c, i1, T2, cur, B, nxt, st, cf));
+                if (t2) {
+                    HIPE(hipEventRecord(c->cev1[i2c], st));
+                    HIPE(hipEventRecord(c->cev0[i1], st));
+                    HIPE(hipEventRecord(c->cev1[i1], st));
+                }
+            } else {
+                if (first) {
+                    // projection shortcut (conv_block), no ReLU before the add
+                    HIPE(timed_conv(c, i1, cur, B, nullptr, 0, SC, st, nullptr, 0, cf));
+                    res = SC;
+                }
+                HIPE(timed_conv(c, i2c, T2, B, res, 1, nxt, st, nullptr, 0, cf));
+            }
+            ci += first ? 4 : 3;
+            float* t = cur;
+            cur = nxt;
+            nxt = t;
+        }
+    }
+    if (c->bf16) return hpe_launch_avgpool_bf16(cur, features + (size_t)i0 * ldfeat, B, 49, HPE_FEATURE_DIM, ldfeat, st);
+    return hpe_launch_avgpool(cur, features + (size_t)i0 * ldfeat, B, 49, HPE_FEATURE_DIM, ldfeat, st);
+}
+
+// Batch chunks run on separate HIP streams (fork/join with events around the caller's stream): images are
+// independent, so while one chunk's launch drains its last partial round of workgroups (49*2^k tiles never fill
+// 256 CUs x 2 evenly) the other chunk's kernels fill the idle CUs.  Per-conv event timing (level 2) needs
+// back-to-back launches on one stream and therefore runs unchunked.
+hipError_t encoder_impl(hpe_ctx* c, const float* images, int B, float* features, int ldfeat, hipStream_t st) {
+    int nstream = c->plan.n_streams;
+    // a chunk needs >= 32 images to keep its own launches efficient.  Rounds 1-2 had 44 (B = 64 was 7 % faster unchunked,
+    // profiles/r01/g_wino_chunk_rule.txt); with the 32-cout / C-split F(4x4) launches of round 3 two chunks of 32-40 win: B = 64 / 72 / 80
+    // 15.0 / 15.1 / 15.8 k img/s in two chunks against 14.1 / 13.4 / 14.1 k unchunked, B = 56 13.3 against 13.6 k, B = 40 12.5 against
+    // 12.8 k (profiles/r03/chunk_rule.txt); B = 128 best with 2 chunks, B = 256 equal for 2-3, 4 chunks of 64 lose 5 %
+    if (nstream > B / c->plan.min_chunk) nstream = B / c->plan.min_chunk;
+    if (c->timing >= 2 || nstream < 2) nstream = 1;
+    if (nstream == 1) return encoder_chunk(c, images, 0, B, features, ldfeat, st);
+    // chunk size: about HPE_CHUNK images (default: one chunk per stream), never below min_chunk -- smaller chunks are launch bound
+    //  -- and all chunks of equal size +-1; chunks go round-robin over the streams
+    int nchunk = nstream;
+    if (c->plan.chunk_images > 0) {
+        const int want = c->plan.chunk_images < c->plan.min_chunk ? c->plan.min_chunk : c->plan.chunk_images;
+        nchunk = B / want;
+        if (nchunk < nstream) nchunk = nstream;
+    }
+    const int per = (B + nchunk - 1) / nchunk;
+    nchunk = (B + per - 1) / per;
+    HIPE(hipEventRecord(c->ev_fork, st));
+    for (int k = 1; k < nstream; ++k) HIPE(hipStreamWaitEvent(c->aux[k - 1], c->ev_fork, 0));
+    c->co_running = nstream;
+    for (int k = 0; k < nchunk; ++k) {
+        const int i0 = k * per;
+        const int n = (i0 + per <= B) ? per : (B - i0);
+        const int sid = k % nstream;
+        hipStream_t s = (sid == 0) ? st : c->aux[sid - 1];
+        const hipError_t ec = encoder_chunk(c, images, i0, n, features, ldfeat, s, sid, true);
+        if (ec != hipSuccess) {
+            c->co_running = 1;
+            return ec;
+        }
+    }
+    c->co_running = 1;
+    for (int k = 1; k < nstream; ++k) {
+        HIPE(hipEventRecord(c->ev_join[k - 1], c->aux[k - 1]));
+        HIPE(hipStreamWaitEvent(st, c->ev_join[k - 1], 0));
+    }
+    return hipSuccess;
+}
+
+// one IEF step on padded theta rows [B, THETA_LD]; P1 = features . W1[:2048] must be current
+hipError_t regress_impl(hpe_ctx* c, const float* th_prev, float* th_next, int B, hipStream_t st) {
+    HIPE(run_dense(c, th_prev, THETA_LD, B, THETA_LD, c->w1t, 1024, 1024, c->ones, c->b1, c->P1, 1024, 1, c->H1, 1024, st));
+    HIPE(run_dense(c, c->H1, 1024, B, 1024, c->w2, 1024, 1024, c->ones, c->b2, nullptr, 0, 1, c->H2, 1024, st));
+    return run_dense(c, c->H2, 1024, B, 1024, c->w3, 128, HPE_THETA_DIM, c->ones, c->b3, th_prev, THETA_LD, 0, th_next, THETA_LD, st);
+}
+
+hipError_t features_proj(hpe_ctx* c, const float* features, int B, hipStream_t st) {
+    return run_dense(c, features, HPE_FEATURE_DIM, B, HPE_FEATURE_DIM, c->w1f, 1024, 1024, c->ones, c->zeros, nullptr, 0, 0, c->P1,
+                     1024, st);
+}
+
+// features [B,2048] -> feature projection (hoisted W1 block), then num_stage x (regressor step, SMPL of the stages that are returned);
+// feat_free (optional) is recorded once the features have been consumed
+hipError_t tail_impl(hpe_ctx* c, const float* feat, int B, const HpeOutputs* stage_outs, int n_outs, hipStream_t ts, hipEvent_t feat_free) {
+    hipError_t e = features_proj(c, feat, B, ts);
+    if (e == hipSuccess && feat_free) e = hipEventRecord(feat_free, ts);
+    if (e == hipSuccess) e = hpe_launch_tile_theta(c->mean_dev, c->thA, B, THETA_LD, ts);
+    float* prev = c->thA;
+    float* next = c->thB;
+    const int first_out = c->cfg.num_stage - n_outs;
+    for (int s = 0; e == hipSuccess && s < c->cfg.num_stage; ++s) {
+        e = regress_impl(c, prev, next, B, ts);
+        if (e == hipSuccess && s >= first_out) e = hpe_launch_smpl(c->smpl, c->work, next, THETA_LD, B, &stage_outs[s - first_out], ts);
+        float* t = prev;
+        prev = next;
+        next = t;
+    }
+    return e;
+}
+
+// encoder on `st`; regressor + SMPL stages on `st` (pipelined == false) or on the ctx's tail stream behind an event (true)
+int forward_impl(hpe_ctx* c, const float* images, int B, const HpeOutputs* stage_outs, int n_outs, hipStream_t st, bool pipelined) {
+    int rc = check_ready(c, B, NEED_ENC | NEED_REG | NEED_SMPL);
+    if (rc) return rc;
+    if (!images || !stage_outs) return fail(HPE_ERR_INVALID, "null pointer");
+    if (n_outs < 1 || n_outs > c->cfg.num_stage) return fail(HPE_ERR_INVALID, "n_outs must be in [1, num_stage]");
+    DeviceGuard g(c->cfg.device);
+    const bool tm = c->timing != 0;
+    if (c->timing >= 2) pipelined = false;  // per-launch event timing wants one serial stream
+    float* feat = c->feat;
+    hipStream_t ts = st;
+    if (pipelined) {
+        // features alternate between two buffers: the tail of batch k reads one while the encoder of batch k+1 fills the other;
+        // the buffer used now was last read by the feature projection of two calls ago (long finished: the wait is a formality)
+        const unsigned slot = c->pipe_idx & 1u;
+        feat = slot ? c->feat_alt : c->feat;
+        if (c->feat_free_valid[slot]) HIP_TRY(hipStreamWaitEvent(st, c->ev_feat_free[slot], 0));
+        ts = c->tail_st;
+    } else if (c->tail_pending) {
+        // a serial call after pipelined ones: its tail shares buffers with the pending tail -> order them
+        HIP_TRY(hipStreamWaitEvent(st, c->ev_tail, 0));
+        c->tail_pending = false;
+    }
+    if (tm) {
+        HIP_TRY(hipEventRecord(c->ev[0], st));
+        HIP_TRY(hipEventRecord(c->span0[c->span_n % hpe_ctx::SPAN_RING], st));
+    }
+    HIP_TRY(encoder_impl(c, images, B, feat, HPE_FEATURE_DIM, st));
+    if (tm) {
+        HIP_TRY(hipEventRecord(c->ev[1], st));
+        HIP_TRY(hipEventRecord(c->span1[c->span_n % hpe_ctx::SPAN_RING], st));
+        ++c->span_n;
+    }
+    if (pipelined) {
+        HIP_TRY(hipEventRecord(c->ev_enc, st));
+        HIP_TRY(hipStreamWaitEvent(ts, c->ev_enc, 0));
+        c->dense_on_tail = true;
+    }
+    hipEvent_t feat_free = nullptr;
+    if (pipelined) {
+        const unsigned slot = c->pipe_idx & 1u;
+        feat_free = c->ev_feat_free[slot];
+        c->feat_free_valid[slot] = true;
+    }
+    hipError_t e = tail_impl(c, feat, B, stage_outs, n_outs, ts, feat_free);
+    c->dense_on_tail = false;
+    if (e != hipSuccess) return fail(HPE_ERR_HIP, std::string("forward tail: ") + hipGetErrorString(e));
+    if (pipelined) {
+        HIP_TRY(hipEventRecord(c->ev_tail, ts));
+        c->tail_pending = true;
+        ++c->pipe_idx;
+    }
+    if (tm) {
+        HIP_TRY(hipEventRecord(c->ev[4], ts));
+        c->timed_valid = true;
+        c->conv_timed_valid = c->timing >= 2;
+    }
+    return HPE_OK;
+}
+

@@ -1,0 +1,552 @@
+// hpe_finalize.hip -- weight ingestion (Keras layouts) and hpe_finalize: BN folding, weight packing for every kernel family the plan
+// selects, workspace sizing, streams and events.  Host logic only.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "hpe_ctx.h"
+
+int dev_alloc(hpe_ctx* c, float** p, size_t n_floats, bool zero) {
+    void* q = nullptr;
+    HIP_TRY(hipMalloc(&q, n_floats * sizeof(float)));
+    c->allocs.push_back(q);
+    if (zero) HIP_TRY(hipMemset(q, 0, n_floats * sizeof(float)));
+    *p = static_cast<float*>(q);
+    return HPE_OK;
+}
+
+int upload(hpe_ctx* c, float** p, const std::vector<float>& h) {
+    int rc = dev_alloc(c, p, h.size(), false);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(*p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return HPE_OK;
+}
+
+// fp32 Wt[rows][K] -> bf16 [rows][3][K]: w = w0 + w1 + w2 exactly (finite weights), each piece rounded to nearest even (conv_gemm_f32s.hip)
+int upload_split(hpe_ctx* c, void** p, const std::vector<float>& wt, int rows, int K) {
+    std::vector<unsigned short> ws((size_t)rows * 3 * K);
+    auto bf2f = [](unsigned short h) {
+        const unsigned u = (unsigned)h << 16;
+        float f;
+        memcpy(&f, &u, 4);
+        return f;
+    };
+    for (int n = 0; n < rows; ++n)
+        for (int k = 0; k < K; ++k) {
+            const float x = wt[(size_t)n * K + k];
+            const unsigned short h0 = f2bf(x);
+            const float r1 = x - bf2f(h0);
+            const unsigned short h1 = f2bf(r1);
+            const float r2 = r1 - bf2f(h1);
+            unsigned short* d = &ws[(size_t)n * 3 * K + k];
+            d[0] = h0;
+            d[K] = h1;
+            d[2 * K] = f2bf(r2);
+        }
+    void* q = nullptr;
+    HIP_TRY(hipMalloc(&q, ws.size() * 2));
+    c->allocs.push_back(q);
+    HIP_TRY(hipMemcpy(q, ws.data(), ws.size() * 2, hipMemcpyHostToDevice));
+    *p = q;
+    return HPE_OK;
+}
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int hpe_load_smpl(hpe_ctx* c, const HpeSmplModel* m) {
+    if (!c || !m) return fail(HPE_ERR_INVALID, "null argument");
+    if (c->finalized) return fail(HPE_ERR_STATE, "already finalized");
+    if (!m->v_template || !m->shapedirs || !m->posedirs || !m->J_regressor || !m->weights || !m->kp_regressor || !m->parents)
+        return fail(HPE_ERR_INVALID, "null SMPL array");
+    if (m->num_kp < 1 || m->num_kp > HPE_MAX_KP) return fail(HPE_ERR_INVALID, "num_kp must be in [1,24]");
+    if (m->parents[0] >= 0) return fail(HPE_ERR_INVALID, "parents[0] must be negative (root)");
+    for (int i = 1; i < 24; ++i)
+        if (m->parents[i] < 0 || m->parents[i] >= i) return fail(HPE_ERR_INVALID, "parents[i] must satisfy 0 <= parents[i] < i");
+    const int V = HPE_NUM_VERTS;
+    c->h_vt.assign(m->v_template, m->v_template + V * 3);
+    c->h_sd.assign(m->shapedirs, m->shapedirs + (size_t)V * 3 * 10);
+    c->h_pd.assign(m->posedirs, m->posedirs + (size_t)V * 3 * 207);
+    c->h_jreg.assign(m->J_regressor, m->J_regressor + (size_t)24 * V);
+    c->h_w.assign(m->weights, m->weights + (size_t)V * 24);
+    c->h_kreg.assign(m->kp_regressor, m->kp_regressor + (size_t)m->num_kp * V);
+    c->h_par.assign(m->parents, m->parents + 24);
+    c->num_kp = m->num_kp;
+    c->smpl_loaded = true;
+    return HPE_OK;
+}
+
+int hpe_load_conv(hpe_ctx* c, int idx, const float* kernel, const float* bias, const float* gamma, const float* beta,
+                  const float* mean, const float* var) {
+    if (!c || idx < 0 || idx >= HPE_NUM_CONV) return fail(HPE_ERR_INVALID, "bad conv index");
+    if (c->finalized) return fail(HPE_ERR_STATE, "already finalized");
+    if (!kernel || !bias || !gamma || !beta || !mean || !var) return fail(HPE_ERR_INVALID, "null conv array");
+    const ConvSpec& s = specs()[idx];
+    ConvLayer& L = c->conv[idx];
+    L.kernel.assign(kernel, kernel + (size_t)s.kh * s.kw * s.cin * s.cout);
+    L.bias.assign(bias, bias + s.cout);
+    L.gamma.assign(gamma, gamma + s.cout);
+    L.beta.assign(beta, beta + s.cout);
+    L.mean.assign(mean, mean + s.cout);
+    L.var.assign(var, var + s.cout);
+    L.loaded = true;
+    return HPE_OK;
+}
+
+int hpe_load_dense(hpe_ctx* c, int idx, const float* kernel, const float* bias) {
+    if (!c || idx < 0 || idx >= HPE_NUM_DENSE) return fail(HPE_ERR_INVALID, "bad dense index");
+    if (c->finalized) return fail(HPE_ERR_STATE, "already finalized");
+    if (!kernel || !bias) return fail(HPE_ERR_INVALID, "null dense array");
+    const int din[3] = {2133, 1024, 1024}, dout[3] = {1024, 1024, 85};
+    c->dense[idx].kernel.assign(kernel, kernel + (size_t)din[idx] * dout[idx]);
+    c->dense[idx].bias.assign(bias, bias + dout[idx]);
+    c->dense[idx].loaded = true;
+    return HPE_OK;
+}
+
+int hpe_load_mean_theta(hpe_ctx* c, const float* mean85) {
+    if (!c || !mean85) return fail(HPE_ERR_INVALID, "null argument");
+    if (c->finalized) return fail(HPE_ERR_STATE, "already finalized");
+    memcpy(c->h_mean, mean85, sizeof(float) * HPE_THETA_DIM);
+    c->mean_loaded = true;
+    return HPE_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop
+
+// release everything a (possibly partial) hpe_finalize created
+void release_device_state(hpe_ctx* c) {
+    for (void* p : c->allocs) (void)hipFree(p);
+    c->allocs.clear();
+    for (auto& a : c->aux)
+        if (a) {
+            (void)hipStreamDestroy(a);
+            a = nullptr;
+        }
+    auto kill = [](hipEvent_t& e) {
+        if (e) {
+            (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    };
+    kill(c->ev_fork);
+    kill(c->ev_enc);
+    kill(c->ev_tail);
+    for (auto& e : c->ev_feat_free) kill(e);
+    if (c->tail_st) {
+        (void)hipStreamDestroy(c->tail_st);
+        c->tail_st = nullptr;
+    }
+    for (auto& e : c->ev_join) kill(e);
+    for (auto& e : c->ev) kill(e);
+    for (auto& e : c->span0) kill(e);
+    for (auto& e : c->span1) kill(e);
+    for (auto& e : c->cev0) kill(e);
+    for (auto& e : c->cev1) kill(e);
+    for (auto& e : c->lev0) kill(e);
+    for (auto& e : c->lev1) kill(e);
+    for (auto& e : c->lev_all) kill(e);
+    c->ev_ok = false;
+}
+
+// every part is either loaded completely or not at all
+static int check_loaded(hpe_ctx* c) {
+    int nconv = 0, ndense = 0;
+    for (int i = 0; i < HPE_NUM_CONV; ++i) nconv += c->conv[i].loaded ? 1 : 0;
+    for (int i = 0; i < HPE_NUM_DENSE; ++i) ndense += c->dense[i].loaded ? 1 : 0;
+    if (nconv != 0 && nconv != HPE_NUM_CONV) {
+        for (int i = 0; i < HPE_NUM_CONV; ++i)
+            if (!c->conv[i].loaded) return fail(HPE_ERR_STATE, std::string("conv layer not loaded: ") + specs()[i].name);
+    }
+    if (ndense != 0 && (ndense != HPE_NUM_DENSE || !c->mean_loaded))
+        return fail(HPE_ERR_STATE, "regressor needs all 3 dense layers and the mean theta");
+    c->have_encoder = nconv == HPE_NUM_CONV;
+    c->have_regressor = ndense == HPE_NUM_DENSE && c->mean_loaded;
+    c->have_smpl = c->smpl_loaded;
+    if (!c->have_encoder && !c->have_regressor && !c->have_smpl) return fail(HPE_ERR_STATE, "nothing was loaded");
+    return HPE_OK;
+}
+
+// ---- conv_block (first block of a stage): out = relu(bn2c(W2c . t2) + bn1(W1 . x_strided)).  Both convolutions are 1x1,
+//      so they are ONE GEMM over the concatenated k axis once each BN scale is folded into its weights:
+//      out = relu([s2c W2c | s1 W1] . [t2 ; x] + (shift2c + shift1))   -- no shortcut tensor in HBM, one launch instead of two
+static int pack_dual_weights(hpe_ctx* c) {
+    int rc;
+    int ci = 1;
+    const int nblk[4] = {3, 4, 6, 3};
+    for (int stg = 0; stg < 4; ++stg) {
+        const int i2c = ci + 2, i1 = ci + 3;
+        const ConvSpec& s2 = specs()[i2c];
+        const ConvSpec& s1 = specs()[i1];
+        ConvLayer& L2 = c->conv[i2c];
+        const ConvLayer& L1 = c->conv[i1];
+        const int K1 = s2.cin, K2 = s1.cin, N = s2.cout;
+        const int slab = c->bf16 ? 64 : 32;
+        if (K1 % slab == 0 && K2 % slab == 0) {
+            const int n_pad = round_up(N, 128), K = K1 + K2;
+            std::vector<float> wt((size_t)n_pad * K, 0.f), sh(N);
+            for (int n = 0; n < N; ++n) {
+                const double inv2 = (double)L2.gamma[n] / std::sqrt((double)L2.var[n] + (double)c->cfg.bn_eps);
+                const double inv1 = (double)L1.gamma[n] / std::sqrt((double)L1.var[n] + (double)c->cfg.bn_eps);
+                for (int k = 0; k < K1; ++k) wt[(size_t)n * K + k] = (float)(inv2 * (double)L2.kernel[(size_t)k * N + n]);
+                for (int k = 0; k < K2; ++k) wt[(size_t)n * K + K1 + k] = (float)(inv1 * (double)L1.kernel[(size_t)k * N + n]);
+                sh[n] = (float)((((double)L2.bias[n] - (double)L2.mean[n]) * inv2 + (double)L2.beta[n]) +
+                                (((double)L1.bias[n] - (double)L1.mean[n]) * inv1 + (double)L1.beta[n]));
+            }
+            if (c->bf16) {
+                std::vector<unsigned short> wb(wt.size());
+                for (size_t q = 0; q < wt.size(); ++q) wb[q] = f2bf(wt[q]);
+                void* qd = nullptr;
+                HIP_TRY(hipMalloc(&qd, wb.size() * 2));
+                c->allocs.push_back(qd);
+                HIP_TRY(hipMemcpy(qd, wb.data(), wb.size() * 2, hipMemcpyHostToDevice));
+                L2.w_dual = static_cast<float*>(qd);
+            } else {
+                if ((rc = upload(c, &L2.w_dual, wt))) return rc;
+                // f32_split: the folded weight is split (the BN scales are inside the pieces)
+                if ((c->plan.f32_split & stage_bit(s2.hout)) && (rc = upload_split(c, &L2.w_dual_split, wt, n_pad, K))) return rc;
+            }
+            if ((rc = upload(c, &L2.shift_dual, sh))) return rc;
+            L2.k_dual = K;
+            L2.k1_dual = K1;
+        }
+        ci += 4 + 3 * (nblk[stg] - 1);
+    }
+    return HPE_OK;
+}
+
+// the F(2x2,3x3) Winograd weights of one 3x3 layer (conv_wino.hip)
+static int pack_wino_weights(hpe_ctx* c, const ConvSpec& s, ConvLayer& L) {
+    int rc;
+    // U = G g G^T, G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1], in double; layout [cout/64][cin/8][16][2][64][4]
+    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    const int S = s.cin / 8;
+    std::vector<float> U((size_t)16 * s.cin * s.cout);
+    for (int ci = 0; ci < s.cin; ++ci)
+        for (int n = 0; n < s.cout; ++n) {
+            double g[3][3];
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) g[a][b] = L.kernel[(((size_t)a * 3 + b) * s.cin + ci) * s.cout + n];
+            const size_t base = ((((size_t)(n >> 6) * S + (ci >> 3)) * 16) * 2 + ((ci >> 2) & 1)) * 256 + (size_t)(n & 63) * 4 + (ci & 3);
+            for (int xi = 0; xi < 4; ++xi)
+                for (int nu = 0; nu < 4; ++nu) {
+                    double u = 0.0;
+                    for (int a = 0; a < 3; ++a)
+                        for (int b = 0; b < 3; ++b) u += G[xi][a] * G[nu][b] * g[a][b];
+                    U[base + (size_t)(xi * 4 + nu) * 512] = (float)u;
+                }
+        }
+    if ((rc = upload(c, &L.wino_u, U))) return rc;
+    return HPE_OK;
+}
+
+// the F(4x4,3x3) Winograd weights of one 3x3 layer (conv_wino4.hip)
+static int pack_wino4_weights(hpe_ctx* c, const ConvSpec& s, ConvLayer& L) {
+    int rc;
+    // F(4x4,3x3): U = G g G^T with G = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1], in double;
+    // layout [cout/64][cin/4][36][64][4]
+    static const double G4[6][3] = {{0.25, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                                    {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
+    const int S4 = s.cin / 4;
+    std::vector<float> U((size_t)36 * s.cin * s.cout);
+    for (int ci = 0; ci < s.cin; ++ci)
+        for (int n = 0; n < s.cout; ++n) {
+            double g[3][3];
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) g[a][b] = L.kernel[(((size_t)a * 3 + b) * s.cin + ci) * s.cout + n];
+            const size_t base = (((size_t)(n >> 6) * S4 + (ci >> 2)) * 36) * 256 + (size_t)(n & 63) * 4 + (ci & 3);
+            for (int xi = 0; xi < 6; ++xi)
+                for (int nu = 0; nu < 6; ++nu) {
+                    double u = 0.0;
+                    for (int a = 0; a < 3; ++a)
+                        for (int b = 0; b < 3; ++b) u += G4[xi][a] * G4[nu][b] * g[a][b];
+                    U[base + (size_t)(xi * 6 + nu) * 256] = (float)u;
+                }
+        }
+    if ((rc = upload(c, &L.wino4_u, U))) return rc;
+    return HPE_OK;
+}
+
+// fused stem: the conv1 weights in the k enumeration of stem_fused.hip
+static int pack_stem_weights(hpe_ctx* c, ConvLayer& L) {
+    void* q = nullptr;
+    if (c->bf16) {
+        std::vector<unsigned short> wp((size_t)64 * 7 * 32, 0);
+        for (int kh = 0; kh < 7; ++kh)
+            for (int kw = 0; kw < 7; ++kw)
+                for (int ci = 0; ci < 3; ++ci)
+                    for (int n = 0; n < 64; ++n)
+                        wp[((size_t)n * 7 + kh) * 32 + kw * 4 + ci] = f2bf(L.kernel[(((size_t)kh * 7 + kw) * 3 + ci) * 64 + n]);
+        HIP_TRY(hipMalloc(&q, wp.size() * 2));
+        c->allocs.push_back(q);
+        HIP_TRY(hipMemcpy(q, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
+    } else {
+        std::vector<float> wp((size_t)64 * 160, 0.f);
+        for (int kh = 0; kh < 7; ++kh)
+            for (int kw = 0; kw < 7; ++kw)
+                for (int ci = 0; ci < 3; ++ci)
+                    for (int n = 0; n < 64; ++n)
+                        wp[(size_t)n * 160 + kh * 22 + 1 + kw * 3 + ci] = L.kernel[(((size_t)kh * 7 + kw) * 3 + ci) * 64 + n];
+        HIP_TRY(hipMalloc(&q, wp.size() * 4));
+        c->allocs.push_back(q);
+        HIP_TRY(hipMemcpy(q, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
+    }
+    L.stem_w = q;
+    return HPE_OK;
+}
+
+// ---- encoder weights: HWIO -> Wt[n][k] (k = (kh,kw,cin), cin fastest), zero padded; BN -> scale/shift
+static int pack_conv_weights(hpe_ctx* c) {
+    int rc;
+    for (int i = 0; i < HPE_NUM_CONV; ++i) {
+        const ConvSpec& s = specs()[i];
+        ConvLayer& L = c->conv[i];
+        L.n_pad = round_up(s.cout, 128);
+        if (c->bf16) {
+            // bf16: 64-element slabs; stem slab s = kernel rows (2s, 2s+1), each 8 px x 4 ch
+            L.k_pad = (i == 0) ? 4 * 64 : round_up(s.kh * s.kw * s.cin, 64);
+            std::vector<unsigned short> wt((size_t)L.n_pad * L.k_pad, 0);
+            for (int kh = 0; kh < s.kh; ++kh)
+                for (int kw = 0; kw < s.kw; ++kw)
+                    for (int ci = 0; ci < s.cin; ++ci) {
+                        const int k = (i == 0) ? (kh * 32 + kw * 4 + ci) : ((kh * s.kw + kw) * s.cin + ci);
+                        const float* src = &L.kernel[(((size_t)kh * s.kw + kw) * s.cin + ci) * s.cout];
+                        for (int n = 0; n < s.cout; ++n) wt[(size_t)n * L.k_pad + k] = f2bf(src[n]);
+                    }
+            void* q = nullptr;
+            HIP_TRY(hipMalloc(&q, wt.size() * 2));
+            c->allocs.push_back(q);
+            HIP_TRY(hipMemcpy(q, wt.data(), wt.size() * 2, hipMemcpyHostToDevice));
+            L.w = static_cast<float*>(q);
+        } else {
+        L.k_pad = (i == 0) ? 7 * 32 : round_up(s.kh * s.kw * s.cin, 32);
+        std::vector<float> wt((size_t)L.n_pad * L.k_pad, 0.f);
+        for (int kh = 0; kh < s.kh; ++kh)
+            for (int kw = 0; kw < s.kw; ++kw)
+                for (int ci = 0; ci < s.cin; ++ci) {
+                    const int k = (i == 0) ? (kh * 32 + kw * 4 + ci) : ((kh * s.kw + kw) * s.cin + ci);
+                    const float* src = &L.kernel[(((size_t)kh * s.kw + kw) * s.cin + ci) * s.cout];
+                    for (int n = 0; n < s.cout; ++n) wt[(size_t)n * L.k_pad + k] = src[n];
+                }
+        if ((rc = upload(c, &L.w, wt))) return rc;
+        if (i != 0 && s.kh == 1 && (c->plan.f32_split & stage_bit(s.hout)) && (rc = upload_split(c, &L.w_split, wt, L.n_pad, L.k_pad))) return rc;
+        if (c->plan.wino_min_c > 0 && s.kh == 3 && s.stride == 1 && s.cin % 32 == 0 && s.cout % 64 == 0 &&
+            (s.cin >= c->plan.wino_min_c || (c->plan.wino_fused && s.hin >= c->plan.wino_fused_min_hw)) && (rc = pack_wino_weights(c, s, L)))
+            return rc;
+        if (s.kh == 3 && s.stride == 1 && s.cin % 32 == 0 && s.cout % 64 == 0 && ((c->plan.wino_f4 | c->plan.wino4_fused) & f4_bit(s.hin)) &&
+            (rc = pack_wino4_weights(c, s, L)))
+            return rc;
+        }
+        if (i == 0 && (rc = pack_stem_weights(c, L))) return rc;
+        std::vector<float> sc(s.cout), sh(s.cout);
+        for (int n = 0; n < s.cout; ++n) {
+            const double inv = (double)L.gamma[n] / std::sqrt((double)L.var[n] + (double)c->cfg.bn_eps);
+            sc[n] = (float)inv;
+            sh[n] = (float)(((double)L.bias[n] - (double)L.mean[n]) * inv + (double)L.beta[n]);
+        }
+        if ((rc = upload(c, &L.scale, sc))) return rc;
+        if ((rc = upload(c, &L.shift, sh))) return rc;
+        std::vector<float>().swap(L.kernel);
+    }
+    return HPE_OK;
+}
+
+// ---- regressor: Dense kernels [in,out] -> [out_pad][in_pad]; W1 split into features / theta parts
+static int pack_regressor(hpe_ctx* c) {
+    int rc;
+    const std::vector<float>& k1 = c->dense[0].kernel;  // [2133][1024]
+    std::vector<float> w1f((size_t)1024 * 2048), w1t((size_t)1024 * THETA_LD, 0.f);
+    for (int n = 0; n < 1024; ++n) {
+        for (int k = 0; k < 2048; ++k) w1f[(size_t)n * 2048 + k] = k1[(size_t)k * 1024 + n];
+        for (int k = 0; k < HPE_THETA_DIM; ++k) w1t[(size_t)n * THETA_LD + k] = k1[(size_t)(2048 + k) * 1024 + n];
+    }
+    const std::vector<float>& k2 = c->dense[1].kernel;
+    std::vector<float> w2((size_t)1024 * 1024);
+    for (int n = 0; n < 1024; ++n)
+        for (int k = 0; k < 1024; ++k) w2[(size_t)n * 1024 + k] = k2[(size_t)k * 1024 + n];
+    const std::vector<float>& k3 = c->dense[2].kernel;  // [1024][85]
+    std::vector<float> w3((size_t)128 * 1024, 0.f);
+    for (int n = 0; n < HPE_THETA_DIM; ++n)
+        for (int k = 0; k < 1024; ++k) w3[(size_t)n * 1024 + k] = k3[(size_t)k * HPE_THETA_DIM + n];
+    if ((rc = upload(c, &c->w1f, w1f))) return rc;
+    if ((rc = upload(c, &c->w1t, w1t))) return rc;
+    if ((rc = upload(c, &c->w2, w2))) return rc;
+    if ((rc = upload(c, &c->w3, w3))) return rc;
+    if ((rc = upload(c, &c->b1, c->dense[0].bias))) return rc;
+    if ((rc = upload(c, &c->b2, c->dense[1].bias))) return rc;
+    std::vector<float> b3(128, 0.f);
+    for (int n = 0; n < HPE_THETA_DIM; ++n) b3[n] = c->dense[2].bias[n];
+    if ((rc = upload(c, &c->b3, b3))) return rc;
+    if ((rc = upload(c, &c->mean_dev, std::vector<float>(c->h_mean, c->h_mean + HPE_THETA_DIM)))) return rc;
+    return HPE_OK;
+}
+
+// ---- SMPL constants in kernel layouts
+static int pack_smpl(hpe_ctx* c) {
+    int rc;
+    const int V = HPE_NUM_VERTS, V3 = V * 3;
+    // basis source [11][V*3]: row 0 v_template, rows 1..10 shapedirs^T  (shapedirs [V,3,10] -> [10][V*3])
+    std::vector<float> src((size_t)11 * V3);
+    memcpy(src.data(), c->h_vt.data(), sizeof(float) * V3);
+    for (int i = 0; i < V3; ++i)
+        for (int k = 0; k < 10; ++k) src[(size_t)(1 + k) * V3 + i] = c->h_sd[(size_t)i * 10 + k];
+    if ((rc = upload(c, &c->smpl_basis_src, src))) return rc;
+    c->smpl.v_template = c->smpl_basis_src;
+    c->smpl.shapedirs = c->smpl_basis_src + V3;
+    // posedirs [V,3,207] -> [207][V*3]
+    std::vector<float> pd((size_t)207 * V3);
+    for (int i = 0; i < V3; ++i)
+        for (int k = 0; k < 207; ++k) pd[(size_t)k * V3 + i] = c->h_pd[(size_t)i * 207 + k];
+    float* p = nullptr;
+    if ((rc = upload(c, &p, pd))) return rc;
+    c->smpl.posedirs = p;
+    if ((rc = upload(c, &p, c->h_w))) return rc;
+    c->smpl.weights = p;
+    // regressors [K,V] -> [V][24] zero padded
+    std::vector<float> jr((size_t)V * SMPL_KP_PITCH, 0.f), kr((size_t)V * SMPL_KP_PITCH, 0.f);
+    for (int j = 0; j < 24; ++j)
+        for (int v = 0; v < V; ++v) jr[(size_t)v * SMPL_KP_PITCH + j] = c->h_jreg[(size_t)j * V + v];
+    for (int j = 0; j < c->num_kp; ++j)
+        for (int v = 0; v < V; ++v) kr[(size_t)v * SMPL_KP_PITCH + j] = c->h_kreg[(size_t)j * V + v];
+    if ((rc = upload(c, &p, jr))) return rc;
+    c->smpl.j_reg = p;
+    if ((rc = upload(c, &p, kr))) return rc;
+    c->smpl.kp_reg = p;
+    int depth[24], maxd = 0;
+    for (int j = 0; j < 24; ++j) {
+        depth[j] = c->h_par[j] < 0 ? 0 : depth[c->h_par[j]] + 1;
+        if (depth[j] > maxd) maxd = depth[j];
+    }
+    void* ip = nullptr;
+    HIP_TRY(hipMalloc(&ip, sizeof(int) * 48));
+    c->allocs.push_back(ip);
+    HIP_TRY(hipMemcpy(ip, c->h_par.data(), sizeof(int) * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(static_cast<int*>(ip) + 24, depth, sizeof(int) * 24, hipMemcpyHostToDevice));
+    c->smpl.parents = static_cast<int*>(ip);
+    c->smpl.depth = static_cast<int*>(ip) + 24;
+    c->smpl.max_depth = maxd;
+    c->smpl.num_kp = c->num_kp;
+    // 24-joint basis through the 6890 -> 24 joint-regressor kernel
+    float* jb = nullptr;
+    if ((rc = dev_alloc(c, &jb, 11 * 24 * 3, true))) return rc;
+    HIP_TRY(hpe_launch_joint_regress(c->smpl_basis_src, c->smpl.j_reg, 11, 24, jb, nullptr, nullptr, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    c->smpl.j_basis = jb;
+    return HPE_OK;
+}
+
+// ---- workspaces for max_batch images
+static int size_workspaces(hpe_ctx* c) {
+    int rc;
+    const size_t B = (size_t)c->cfg.max_batch;
+    const size_t Bpad = (size_t)round_up(c->cfg.max_batch, SMPL_IMG_TILE);
+    if (c->have_encoder) {
+        if ((rc = dev_alloc(c, &c->padded, B * STEM_HP * STEM_WP * 4 + 64, true))) return rc;
+        if ((rc = dev_alloc(c, &c->X0, B * 802816, false))) return rc;
+        if ((rc = dev_alloc(c, &c->X1, B * 802816, false))) return rc;
+        if ((rc = dev_alloc(c, &c->SC, B * 802816, false))) return rc;
+        if ((rc = dev_alloc(c, &c->T1, B * 200704, false))) return rc;
+        if ((rc = dev_alloc(c, &c->T2, B * 200704, false))) return rc;
+        if ((rc = dev_alloc(c, &c->feat, B * HPE_FEATURE_DIM, true))) return rc;
+        if ((rc = dev_alloc(c, &c->feat_alt, B * HPE_FEATURE_DIM, true))) return rc;
+    }
+    if (c->have_encoder && !c->bf16 && c->plan.wino_min_c > 0) {
+        if ((rc = dev_alloc(c, &c->wino_v, B * WINO_V_PITCH + WINO_V_SLACK, false))) return rc;
+        if (c->plan.wino_f4 && c->plan.wino4_ksplit) {
+            // one workspace per chunk-stream slot (16 MB each), block counters zeroed
+            const size_t nws = hpe_wino4_split_ws_floats();
+            if ((rc = dev_alloc(c, &c->w4_split, 4 * nws, false))) return rc;
+            for (int k = 0; k < 4; ++k) HIP_TRY(hipMemset(c->w4_split + (k + 1) * nws - 256, 0, 256 * sizeof(unsigned)));
+        }
+        // persistent stream-K scheduling of the Winograd GEMM (opt-in): parking space and flags, one slot per chunk stream
+        if (c->plan.wino_streamk) {
+            hipDeviceProp_t prop;
+            HIP_TRY(hipGetDeviceProperties(&prop, c->cfg.device));
+            c->n_cu = prop.multiProcessorCount;
+            if ((rc = dev_alloc(c, &c->wino_ws, (size_t)4 * c->n_cu * HPE_WINO_WS_FLOATS, false))) return rc;
+            float* fl = nullptr;
+            if ((rc = dev_alloc(c, &fl, (size_t)4 * c->n_cu + 4, true))) return rc;
+            c->wino_flags = reinterpret_cast<unsigned*>(fl);
+            c->dev_err = c->wino_flags + (size_t)4 * c->n_cu;
+        }
+    }
+    {
+        c->partial_floats = (size_t)512 * 128 * 128;  // 512 slices of the largest tile (32 MB)
+        if ((rc = dev_alloc(c, &c->partial, c->partial_floats, false))) return rc;
+        c->partial_tail_floats = (size_t)64 * 128 * 128;  // Dense layers: <= 16 slices of <= 64 tiles of 64 x 64 (4 MB)
+        if ((rc = dev_alloc(c, &c->partial_tail, c->partial_tail_floats, false))) return rc;
+    }
+    if (c->have_regressor) {
+        if ((rc = dev_alloc(c, &c->P1, B * 1024, true))) return rc;
+        if ((rc = dev_alloc(c, &c->H1, B * 1024, true))) return rc;
+        if ((rc = dev_alloc(c, &c->H2, B * 1024, true))) return rc;
+        if ((rc = dev_alloc(c, &c->thA, B * THETA_LD, true))) return rc;
+        if ((rc = dev_alloc(c, &c->thB, B * THETA_LD, true))) return rc;
+    }
+    if (c->have_smpl) {
+        if ((rc = dev_alloc(c, &c->work.pfT, 207 * Bpad, true))) return rc;
+        if ((rc = dev_alloc(c, &c->work.betaT, 10 * Bpad, true))) return rc;
+        if ((rc = dev_alloc(c, &c->work.A, Bpad * 288, true))) return rc;
+        if ((rc = dev_alloc(c, &c->work.cams, Bpad * 4, true))) return rc;
+        if ((rc = dev_alloc(c, &c->work.verts_tmp, B * HPE_NUM_VERTS * 3, false))) return rc;
+        if ((rc = dev_alloc(c, &c->work.kp_part, (size_t)SMPL_SMALL_B * ((HPE_NUM_VERTS + 63) / 64) * 72, true))) return rc;
+        // reprojection-loss workspace for the geometry the path itself produces (config 5); other sizes grow it on demand
+        c->loss_ws_floats = hpe_mesh_loss_ws_floats(c->cfg.max_batch, HPE_IMG_SIZE, HPE_IMG_SIZE, HPE_NUM_VERTS);
+        if ((rc = dev_alloc(c, &c->loss_ws, c->loss_ws_floats, true))) return rc;
+    }
+    c->work.Bpad = (int)Bpad;
+    return HPE_OK;
+}
+
+// ---- chunk streams, the tail stream and the events of the fork / join, the software pipeline and the timing hooks
+static int create_streams_and_events(hpe_ctx* c) {
+    for (int i = 0; i < c->plan.n_streams - 1; ++i) HIP_TRY(hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    HIP_TRY(hipStreamCreateWithFlags(&c->tail_st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&c->ev_enc, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming));
+    for (auto& ev : c->ev_feat_free) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    for (auto& ev : c->ev_join) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    for (auto& e : c->ev) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : c->span0) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : c->span1) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : c->cev0) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : c->cev1) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : c->lev0) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : c->lev1) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : c->lev_all) HIP_TRY(hipEventCreate(&e));
+    c->ev_ok = true;
+    return HPE_OK;
+}
+
+int finalize_impl(hpe_ctx* c) {
+    int rc = check_loaded(c);
+    if (rc) return rc;
+    DeviceGuard g(c->cfg.device);
+    c->plan = hpe_resolve_plan(c->cfg);
+    // per-device function attributes (dynamic LDS above 64 KB) of the Winograd, stem and loss kernels
+    HIP_TRY(hpe_wino_init_device());
+    HIP_TRY(hpe_wino4_init_device());
+    HIP_TRY(hpe_stem_fused_init_device());
+    HIP_TRY(hpe_losses_init_device());
+    c->loss_attr_done = true;
+    if (c->have_encoder && c->plan.dual_gemm && (rc = pack_dual_weights(c))) return rc;
+    if (c->have_encoder && (rc = pack_conv_weights(c))) return rc;
+    // constants every part uses: the zero page is the LDS-DMA source of out-of-image taps / halo pixels
+    if ((rc = upload(c, &c->ones, std::vector<float>(2048, 1.f)))) return rc;
+    if ((rc = upload(c, &c->zeros, std::vector<float>(1024, 0.f)))) return rc;
+    if (c->have_regressor && (rc = pack_regressor(c))) return rc;
+    if (c->have_smpl && (rc = pack_smpl(c))) return rc;
+    if ((rc = size_workspaces(c))) return rc;
+    if ((rc = create_streams_and_events(c))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    c->finalized = true;
+    return HPE_OK;
+}

@@ -27,15 +27,17 @@ struct GemmArgs {
     float* partial;          // split-K workspace of the launching stream, partial_floats floats; nullptr disables splitting
     size_t partial_floats;
     const float* zero;       // >= 16 B of zeros in global memory (source of out-of-image taps for the LDS-DMA path)
-    unsigned long long* dbg;  // diagnostics only (HPE_ABLATION builds): per-workgroup {shader clocks, 100 MHz ticks}
+    void* reserved;   // unused (was the diagnostics buffer of the removed register-staged kernel): keeps the kernel-argument offsets, and so the
+                      // device code of every GEMM kernel, as they were
     const float* x2;  // GEMM_DUAL: second A source (strided NHWC)
     int k1_slabs;     // GEMM_DUAL: k-slabs taken from x
-    int res_prefetch;  // filled by the launcher: 8-wave tiles read their residual rows before the main loop (HPE_RES_PREFETCH=0: in the epilogue)
+    int res_prefetch;  // filled by the launcher: 8-wave tiles read their residual rows before the main loop (0: in the epilogue)
     int y_slab8;  // 1: y is written channel-slab major, y[(n / 8) * M + m][n % 8] (the layout the fused Winograd kernel reads); needs N % 8 == 0
     int w_piece;  // hpe_launch_gemm_f32s: element offset of bf16 piece j = 1, 2 inside a weight row (piece j of Wt[n][k] at w + n * ldw + j * w_piece + k)
 };
 
-hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, hipStream_t st);
+// splitk_min_slabs (>= 2): k-slabs per slice when a small grid is cut along K
+hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, int splitk_min_slabs, hipStream_t st);
 // conv_gemm_f32s.hip: the same fp32 GEMM (GEMM_DENSE / GEMM_STRIDED / GEMM_DUAL, whole tiles, no split-K) on the bf16 matrix cores: p.w points to
 // bf16 weights split exactly into three pieces on the host (w = w0 + w1 + w2, offsets in bf16 elements, ldw and w_piece multiples of 8), A is
 // split the same way in registers; the six products with i + j <= 2 are summed in fp32.  Tiles TILE_128x128 (4 waves), TILE_128x128_W8,
@@ -67,12 +69,13 @@ hipError_t hpe_launch_nhwc_to_slab8(const float* x, float* xs, long M, int C, hi
 
 // conv_wino4.hip: the same convolution as Winograd F(4x4,3x3); U = G g G^T blocked [N/64][C/4][36][64][4], V workspace of
 // hpe_wino4_v_floats(B, H, W, C) floats (blocked [tiles/32][C/4][36][32][4]); C % 32 == 0, N % 64 == 0; co_running = batch chunks
-// launching the same layer on other streams at the same time (picks between the 64- and the 32-cout GEMM)
+// launching the same layer on other streams at the same time (picks between the 64- and the 32-cout GEMM: the 32-cout one below n32_below
+// workgroups on the device); abl: ablation mask of diagnostics builds (-DHPE_ABLATION), 0 otherwise
 size_t hpe_wino4_v_floats(int B, int H, int W, int C);
 int hpe_wino4_items(int B, int H, int W, int N);  // workgroups of the GEMM launch
 hipError_t hpe_wino4_init_device();
 hipError_t hpe_launch_wino4_conv3(const float* x, int lda, const float* U, const float* scale, const float* shift, float* y, int ldy, int B,
-                                  int H, int W, int C, int N, int relu, float* V, hipStream_t st, int co_running = 1, float* split_ws = nullptr);
+                                  int H, int W, int C, int N, int relu, float* V, hipStream_t st, int co_running, float* split_ws, int n32_below, int abl);
 // split_ws: hpe_wino4_split_ws_floats() floats whose LAST 256 (unsigned counters) are zero, owned by launches that are alone on the device
 // (nullptr: the C axis is never cut)
 size_t hpe_wino4_split_ws_floats();
@@ -83,7 +86,7 @@ hipError_t hpe_launch_wino4_fused_conv3(const float* xs, const float* U, const f
 int hpe_wino4_fused_items(int B, int H, int W, int N);  // workgroups of that launch, 0 if the geometry is not supported
 
 // conv_gemm_bf16.hip (x / w / res / y of GemmArgs point to bf16 data; offsets are in bf16 elements; K % 64 == 0)
-hipError_t hpe_launch_gemm_bf16(GemmArgs p, int mode, int tile, int ring_depth, hipStream_t st);  // ring_depth 2..4 LDS slab buffers
+hipError_t hpe_launch_gemm_bf16(GemmArgs p, int mode, int tile, hipStream_t st);
 // conv_gemm_bf16_p8.hip: 256 x 256 x 64 tile, 8 waves, phase-interleaved main loop, split-K through p.partial (DENSE / STRIDED / CONV3 / DUAL)
 hipError_t hpe_launch_gemm_bf16_p8(GemmArgs p, int mode, hipStream_t st);
 // conv_chain_bf16.hip: t3 = relu(bn(W2c . t2) + res) and u1 = relu(bn'(W2a' . t3)) in one launch (the last 1x1 of identity block i and the
@@ -195,7 +198,6 @@ hipError_t hpe_losses_init_device();  // per-device kernel attributes of the los
 size_t hpe_mesh_loss_ws_floats(int B, int H, int W, int P);
 // a2b_mode: 0 cell-grid search (default), 1 VALU full search, 2 matrix-core full search; counter: optional 2 x u64 (MFMAs issued
 // by the grid / full search)
-int hpe_mesh_a2b_mode_from_env();
 hipError_t hpe_launch_mesh_loss(const float* seg, const float* v2d, int B, int H, int W, int P, float* ws, float* out,
                                 hipStream_t st, int a2b_mode, unsigned long long* counter);
 // the same in two halves: silhouette compaction + bitmap (once per step), then the searches of one vertex set (once per IEF stage)

@@ -1,0 +1,250 @@
+// hpe_plan.hip -- the layer table, the option table and its resolver (the one place of the library that reads the environment), and the
+// rules that choose a tile / kernel per launch.  Host logic only.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "hpe_ctx.h"
+
+namespace {
+
+// ResNet-50 v1 layer table, Keras names / order [2a, 2b, 2c, (1)] per block.
+std::vector<ConvSpec> build_specs() {
+    std::vector<ConvSpec> v;
+    auto add = [&](const std::string& n, const std::string& b, int kh, int cin, int cout, int s, int hin, int hout) {
+        ConvSpec c;
+        snprintf(c.name, sizeof c.name, "%s", n.c_str());
+        snprintf(c.bn, sizeof c.bn, "%s", b.c_str());
+        c.kh = c.kw = kh;
+        c.cin = cin;
+        c.cout = cout;
+        c.stride = s;
+        c.hin = hin;
+        c.hout = hout;
+        v.push_back(c);
+    };
+    add("conv1", "bn_conv1", 7, 3, 64, 2, 224, 112);
+    const int nblk[4] = {3, 4, 6, 3};
+    const int filt[4][3] = {{64, 64, 256}, {128, 128, 512}, {256, 256, 1024}, {512, 512, 2048}};
+    int cin = 64, h = 56;
+    for (int st = 0; st < 4; ++st) {
+        for (int b = 0; b < nblk[st]; ++b) {
+            const bool first = b == 0;
+            const int s = (first && st > 0) ? 2 : 1;
+            const int hout = h / s;
+            char base[24], bn[24];
+            snprintf(base, sizeof base, "res%d%c_branch", st + 2, 'a' + b);
+            snprintf(bn, sizeof bn, "bn%d%c_branch", st + 2, 'a' + b);
+            add(std::string(base) + "2a", std::string(bn) + "2a", 1, cin, filt[st][0], s, h, hout);
+            add(std::string(base) + "2b", std::string(bn) + "2b", 3, filt[st][0], filt[st][1], 1, hout, hout);
+            add(std::string(base) + "2c", std::string(bn) + "2c", 1, filt[st][1], filt[st][2], 1, hout, hout);
+            if (first) add(std::string(base) + "1", std::string(bn) + "1", 1, cin, filt[st][2], s, h, hout);
+            cin = filt[st][2];
+            h = hout;
+        }
+    }
+    return v;
+}
+
+}  // namespace
+
+const std::vector<ConvSpec>& specs() {
+    static const std::vector<ConvSpec> s = build_specs();
+    return s;
+}
+
+// ---- the option table.  One row per HpePlan member that can be set from outside; precedence as documented in include/hpe.h: the HpeConfig
+// field if it is >= 0, else the environment variable, else the built-in default.  dflt / mask are {fp32 encoder, bf16 encoder}; the resolved
+// value is ANDed with the mask (-1 keeps every bit, 0 switches the option off for that dtype), then clamped to [lo, hi].
+struct PlanOption {
+    int HpePlan::*member;
+    int HpeConfig::*cfg;  // nullptr: no HpeConfig field
+    const char* env;
+    int dflt[2];
+    int mask[2];
+    int lo, hi;
+};
+
+constexpr int ANY = -1, NO_LO = INT_MIN, NO_HI = INT_MAX;
+
+const PlanOption kPlanOptions[] = {
+    // Two chunk streams by default: with the tail stream of the pipelined forward that makes 3 busy queues per process, and a 4th for RCCL.
+    // A 5th concurrently busy queue is expensive on this part whatever GPU_MAX_HW_QUEUES says -- with a process group alive 3 chunk streams
+    // cost 6 % in fp32 and 24 % in bf16 (profiles/r02/streams_vs_rccl.txt) -- while 2 and 3 chunk streams are equal without one.
+    {&HpePlan::n_streams, &HpeConfig::n_streams, "HPE_STREAMS", {2, 2}, {ANY, ANY}, 1, 4},
+    {&HpePlan::dual_gemm, &HpeConfig::dual_gemm, "HPE_DUAL", {1, 1}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::stem_fused, &HpeConfig::stem_fused, "HPE_STEM_FUSED", {1, 1}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::wino_min_c, &HpeConfig::wino_min_c, "HPE_WINO_MINC", {128, 128}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::wino_min_items, &HpeConfig::wino_min_items, "HPE_WINO_MIN_ITEMS", {128, 128}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::wino_fused, &HpeConfig::wino_fused, "HPE_WINO_FUSED", {1, 1}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::wino_fused_min_hw, &HpeConfig::wino_fused_min_hw, "HPE_WINO_FUSED_MINHW", {28, 28}, {ANY, ANY}, NO_LO, NO_HI},
+    // HPE_MESH_A2B is a word: "grid" (default), "valu", "mfma" (the full searches, for A/B comparisons)
+    {&HpePlan::mesh_a2b, &HpeConfig::mesh_a2b, "HPE_MESH_A2B", {0, 0}, {ANY, ANY}, NO_LO, NO_HI},
+    // F(4x4,3x3) on the 28x28 / 14x14 / 7x7 maps by default (A/B on one box: 17,720 -> 18,790 img/s; with the 7x7 and 14x14 maps only
+    // 18,540; the 56x56 maps lose: their V round trip costs more than the direct kernel's extra multiplies)
+    {&HpePlan::wino_f4, &HpeConfig::wino_f4, "HPE_WINO_F4", {7, 7}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::wino4_fused, &HpeConfig::wino4_fused, "HPE_WINO4_FUSED", {0, 0}, {12, 12}, NO_LO, NO_HI},
+    {&HpePlan::bf16_p8, &HpeConfig::bf16_p8, "HPE_BF16_P8", {0, 0}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::wino4_ksplit, &HpeConfig::wino4_ksplit, "HPE_WINO4_KSPLIT", {1, 1}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::chain_fuse, &HpeConfig::chain_fuse, "HPE_CHAIN", {8, 7}, {8, 23}, NO_LO, NO_HI},
+    {&HpePlan::halo3, &HpeConfig::halo3, "HPE_HALO3", {15, 15}, {0, 15}, NO_LO, NO_HI},
+    {&HpePlan::f32_split, &HpeConfig::f32_split, "HPE_F32_SPLIT", {14, 14}, {15, 0}, NO_LO, NO_HI},
+    {&HpePlan::chunk_images, nullptr, "HPE_CHUNK", {0, 0}, {ANY, ANY}, NO_LO, NO_HI},
+    // bf16 launches are short enough to leave CUs idle at small batches: two chunks pay from 2 x 24 images on (B = 48 / 64 / 80:
+    // 38.5 / 44.8 / 48.9 k img/s against 34.7 / 39.2 / 44.5 k as one chunk); fp32 from 2 x 32 (see encoder_impl).  Values below 8 are ignored.
+    {&HpePlan::min_chunk, nullptr, "HPE_MIN_CHUNK", {32, 24}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::halo3_two, nullptr, "HPE_HALO3_TWO", {4, 4}, {7, 7}, NO_LO, NO_HI},
+    {&HpePlan::f32s_min_tiles, nullptr, "HPE_F32S_MIN_TILES", {128, 128}, {ANY, ANY}, NO_LO, NO_HI},
+    // persistent stream-K scheduling of the Winograd GEMM: opt-in.  It removes the partial last round of workgroups (-7 % on a res4 layer,
+    // -2 % on the step with HPE_STREAMS=1) but with the default batch-chunk streams, whose kernels already fill those idle CUs, the step
+    // time is unchanged within noise (profiles/r01/g_wino_streamk.txt)
+    {&HpePlan::wino_streamk, nullptr, "HPE_WINO_STREAMK", {0, 0}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::concurrent_tiles, nullptr, "HPE_CONCURRENT_TILES", {0, 0}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::bf16_w8_min_tiles, nullptr, "HPE_BF16_W8_MIN_TILES", {128, 128}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::wide128_min_tiles, nullptr, "HPE_WIDE128_MIN_TILES", {384, 384}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::force_wide, nullptr, "HPE_TILE_WIDE", {-1, -1}, {ANY, ANY}, NO_LO, NO_HI},
+    // slabs per split-K slice: a slice shorter than 4 is all launch ramp.  Every split layer pays a second, dependent launch (the fix-up),
+    // which costs a single frame about what 6-8 more slabs in the main loop cost.
+    {&HpePlan::splitk_min_slabs, nullptr, "HPE_SPLITK_SLABS", {4, 4}, {ANY, ANY}, 2, NO_HI},
+    {&HpePlan::wino4_min_items, nullptr, "HPE_WINO4_MIN_ITEMS", {64, 64}, {ANY, ANY}, NO_LO, NO_HI},
+    // from 256 workgroups = one per CU on, the 64-cout F(4x4) GEMM is the faster one (profiles/r03/w4_n32_ab.txt)
+    {&HpePlan::wino4_n32, nullptr, "HPE_WINO4_N32", {256, 256}, {ANY, ANY}, NO_LO, NO_HI},
+    {&HpePlan::w4_abl, nullptr, "HPE_W4_ABL", {0, 0}, {ANY, ANY}, NO_LO, NO_HI},
+};
+
+HpePlan hpe_resolve_plan(const HpeConfig& cfg) {
+    const int dt = cfg.encoder_dtype == 1 ? 1 : 0;
+    HpePlan pl;
+    for (const PlanOption& o : kPlanOptions) {
+        int v = o.dflt[dt];
+        const char* e = getenv(o.env);
+        if (o.cfg && cfg.*o.cfg >= 0) v = cfg.*o.cfg;
+        else if (e && o.member == &HpePlan::mesh_a2b) v = e[0] == 'v' ? 1 : (e[0] == 'm' ? 2 : 0);
+        else if (e) v = atoi(e);
+        v &= o.mask[dt];
+        pl.*o.member = v < o.lo ? o.lo : (v > o.hi ? o.hi : v);
+    }
+    if (pl.min_chunk < 8) pl.min_chunk = dt ? 24 : 32;
+    // wino_min_c == 0 disables every Winograd path
+    pl.wino_fused = pl.wino_fused && pl.wino_min_c > 0;
+    if (pl.wino_min_c <= 0) pl.wino_f4 = pl.wino4_fused = 0;
+    return pl;
+}
+
+// tile of conv_gemm_f32s.hip for this launch, -1 = the launch keeps the fp32 kernel.  Split weights exist (fp32 encoder, stage in f32_split),
+// N > 64, the grid is whole tiles of a useful size.  Measured at B = 256 (profiles/r05): the 4-wave 128 x 128 tile (each A element
+// split by one wave) everywhere but on the identity-block expand layers, which are mostly epilogue: there 8 waves (128 x 128, 4 x 2), and on
+// stage 3 (K = 128) the fp32 kernel's 128 x 64 8-wave tile stays ahead.
+int pick_f32s(const HpePlan& pl, const void* w_split, int M, int N, int K, bool residual_expand) {
+    if (!w_split || N <= 64) return -1;
+    if (residual_expand && K < PLAN_F32S_EXPAND_MIN_K) return -1;
+    const int tile = residual_expand ? PLAN_F32S_EXPAND_TILE : PLAN_F32S_TILE;
+    const int bm = tile == TILE_256x128_W8 ? 256 : 128;
+    return (long)((M + bm - 1) / bm) * ((N + 127) / 128) >= pl.f32s_min_tiles ? tile : -1;
+}
+
+int pick_tile(const HpePlan& pl, int M, int N, int K, bool residual_expand, bool concurrent) {
+    // prefer the largest tile that still gives >= 2 workgroups per CU; N == 64 layers use 64-wide tiles
+    const bool wide = N > 64;
+    // identity-block expand layers: 8 waves (see below) -- unless the grid is so small that the launch is DMA latency: then the 4-wave
+    // 64x64 tile, which the launcher cuts along K (single frames: res5*_branch2c 21 -> 9 us)
+    if (wide && residual_expand) return (long)((M + 127) / 128) * ((N + 63) / 64) < PLAN_EXPAND_SMALL_GRID ? TILE_64x64 : TILE_128x64_W8;
+    if (wide && pl.force_wide >= 0) return pl.force_wide;
+    // Measured on MI355X (profiles/r01/d_tile_sweep.txt): with LDS-DMA staging the small tiles with 3-5 workgroups
+    // per CU beat 128x128 at 2 per CU except on the huge-M layers of stages 2-3.
+    if (!wide) return TILE_128x64;
+    // Identity-block expand layers (above) and K <= 128 on the huge-M maps (the C -> 4C expand / projection layers of stages 2 and
+    // 3): the launch is mostly epilogue -> 8 waves to issue the row stores and residual loads win; 128x64 beats 128x128
+    // (profiles/r01/h_tile_128x64w8.txt: res2*_branch2c 0.41-0.43 -> 0.37-0.38 ms, res3*_branch2c 0.31 -> 0.28 ms; stages 4-5:
+    // equal to the 64x64 tile within 1 %, profiles/r02/fp32_expand_tile.txt)
+    if (K <= 128 && M >= 150000) return PLAN_SHORTK_TILE;
+    // Launches of concurrent batch chunks: 128x128 wherever it still leaves >= 1.5 tiles per CU (round 2, pipelined steps + two chunk
+    // streams at B = 256: 17,440 -> 17,830 img/s, B = 128: +0.7 %, although most of these layers are 5-10 % SLOWER with it when they
+    // run alone -- fewer, longer workgroups leave the co-running chunk's kernels more room).  A single-chunk batch keeps the
+    // round-1 rule (B = 64: -0.6 ... -1.2 % with 128x128).  Thresholds 300 / 390 / 700 tiles: 17,805 / 17,843 / 17,806 img/s.
+    if ((concurrent || pl.concurrent_tiles) && pl.wide128_min_tiles > 0 && (long)((M + 127) / 128) * ((N + 127) / 128) >= pl.wide128_min_tiles) return TILE_128x128;
+    if (M >= 150000) return TILE_64x128;
+    return TILE_64x64;
+}
+
+// bf16 tile per layer kind, from the per-layer sweeps in profiles/r02 (B = 256):
+//  * identity-block expand layers (1x1, K = C, N = 4C, + residual): all epilogue -> 128x64 with 8 waves issuing the row stores
+//    and residual loads (res2b_branch2c 0.273 -> 0.182 ms = 5.1 TB/s, res3* 0.157 -> 0.108, res4* 0.079 -> 0.062, res5* 0.061 -> 0.048)
+//  * everything with a long k axis on the small maps (stage 5: M = 49 B): 256x128, 8 waves (res5*_branch2b 0.112 -> 0.083 ms)
+//  * otherwise 128x128 while that still gives >= 512 workgroups, else 64x128
+// (the LDS ring is two slabs deep everywhere: a 3-deep ring lost on every layer it was measured on)
+int pick_bf16(const HpePlan& pl, int M, int N, int K, bool residual_expand, bool concurrent, int mode) {
+    // 256 x 256 phase-interleaved kernel (conv_gemm_bf16_p8.hip), per layer kind -- bits of bf16_p8:
+    //   1: 3x3 layers with N == 256 (stage 4), 2: 3x3 layers with N >= 512 (stage 5), 4: 1x1 / strided layers,
+    //   8: dual-source launches with N >= 2048 (res5a), 16: the other dual-source launches
+    if (pl.bf16_p8 && N >= PLAN_BF16_P8_MIN_N && N % 256 == 0 && K >= PLAN_BF16_P8_MIN_K && !residual_expand) {
+        const int bit = mode == GEMM_CONV3 ? (N == 256 ? 1 : 2) : (mode == GEMM_DUAL ? (N >= 2048 ? 8 : 16) : 4);
+        if (pl.bf16_p8 & bit) return TILE_P8_256x256;
+    }
+    if (N <= 64) return TILE_128x64;
+    const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
+    int tile = t128 >= ((concurrent || pl.concurrent_tiles) ? PLAN_BF16_128_MIN_TILES : 512) ? TILE_128x128 : TILE_64x128;
+    if (residual_expand) tile = TILE_128x64_W8;
+    else if (M <= 16384 && M >= 8192 && K >= 1024 && N >= 256) tile = TILE_256x128_W8;
+    // Round 4: these launches are paced by the ISSUE of their LDS-DMA instructions (60-180 cycles each for the issuing wave),
+    // not by the matrix pipe (without any multiplies the 1x1 layers take 0.96-0.99 of their time; a deeper ring is slower):
+    // the 128 x 128 tile with EIGHT waves halves the DMA instructions per wave and slab.  Every N > 64 layer of the B = 256
+    // step is equal or faster with it (serial pass 3.59 -> 3.50 ms, step 75.1 -> 76.7 k img/s); small grids keep the old rules.
+    if (pl.bf16_w8_min_tiles > 0 && t128 >= pl.bf16_w8_min_tiles) tile = TILE_128x128_W8;
+    return tile;
+}
+
+// the 3x3 layer idx runs as Winograd F(4x4,3x3) for this batch (blocked V through the workspace)
+bool use_wino4(const hpe_ctx* c, int idx, int B) {
+    const ConvSpec& s = specs()[idx];
+    return !c->bf16 && c->conv[idx].wino4_u && s.kh == 3 && s.stride == 1 && (c->plan.wino_f4 & f4_bit(s.hin)) &&
+           hpe_wino4_items(B, s.hin, s.hin, s.cout) >= (c->plan.wino_min_items < c->plan.wino4_min_items ? c->plan.wino_min_items : c->plan.wino4_min_items);
+}
+
+// ... with the input transform inside the GEMM kernel (its 1x1 producer then writes channel-slab major); takes precedence over use_wino4
+bool use_wino4_fused(const hpe_ctx* c, int idx, int B) {
+    const ConvSpec& s = specs()[idx];
+    return !c->bf16 && c->conv[idx].wino4_u && s.kh == 3 && s.stride == 1 && (c->plan.wino4_fused & f4_bit(s.hin)) &&
+           hpe_wino4_fused_items(B, s.hin, s.hin, s.cout) >= (c->plan.wino_min_items < c->plan.wino4_min_items ? c->plan.wino_min_items : c->plan.wino4_min_items);
+}
+
+// the 3x3 layer idx runs as the fused F(2x2) Winograd kernel for this batch (its 1x1 producer then writes channel-slab major)
+bool use_wino_fused(const hpe_ctx* c, int idx, int B) {
+    const ConvSpec& s = specs()[idx];
+    if (use_wino4_fused(c, idx, B) || use_wino4(c, idx, B)) return false;
+    return c->plan.wino_fused && !c->bf16 && c->conv[idx].wino_u && s.kh == 3 && s.stride == 1 && s.hin >= c->plan.wino_fused_min_hw &&
+           hpe_wino_fused_items(B, s.hin, s.hin, s.cout) >= c->plan.wino_min_items;
+}
+
+// the bf16 identity-block pair branch2c (idx i2c, + residual + ReLU) -> next block's branch2a (idx i2c + 1) as one launch
+// `first`: the conv_block form -- branch2c + the projection shortcut branch1 (idx i2c + 1, stride 1: stage 2 only) as the dual-source GEMM,
+// chained with the next block's branch2a (idx i2c + 2); bit 2 of chain_fuse
+bool use_chain(const hpe_ctx* c, int stg, int i2c, bool first, bool has_next) {
+    if (!has_next) return false;
+    const ConvSpec& s2 = specs()[i2c];
+    if (!c->bf16) {
+        // fp32: identity blocks of stage 2 only (conv_chain_f32.hip; bit 3 of chain_fuse, on by default: A/B on two boxes +0.3 ... +1.4 % at
+        // B = 256, +1.6 % at B = 64)
+        if (first || stg != 0 || !(c->plan.chain_fuse & 8)) return false;
+        const ConvSpec& sn = specs()[i2c + 1];
+        return sn.kh == 1 && sn.stride == 1 && sn.cin == s2.cout && hpe_chain_f32_supported(s2.cin, s2.cout, sn.cout);
+    }
+    if (first) {
+        const ConvSpec& s1 = specs()[i2c + 1];
+        const ConvSpec& sn = specs()[i2c + 2];
+        return stg == 0 && (c->plan.chain_fuse & 4) && c->conv[i2c].w_dual && s1.stride == 1 && s1.hin == s2.hin && sn.kh == 1 && sn.stride == 1 &&
+               sn.cin == s2.cout && c->conv[i2c].k_dual == s2.cin + s1.cin && hpe_chain_bf16_supported(s2.cin, s2.cout, sn.cout, s1.cin);
+    }
+    // identity blocks: bit 0 = stage 2, bit 1 = stage 3, bit 4 (value 16) = stage 4 (128-pixel workgroups, one per CU)
+    const int bit = stg == 0 ? 1 : stg == 1 ? 2 : stg == 2 ? 16 : 0;
+    if (!(c->plan.chain_fuse & bit)) return false;
+    const ConvSpec& sn = specs()[i2c + 1];
+    return sn.kh == 1 && sn.stride == 1 && sn.cin == s2.cout && hpe_chain_bf16_supported(s2.cin, s2.cout, sn.cout, 0);
+}

@@ -981,20 +981,14 @@ static size_t a2b_grid_lds_bytes(int H, int W, int WW, int P, int Gx, int Gy) {
     return (size_t)((P + 31) & ~31) * 16 + (size_t)(2 * Gx * Gy + 2) * 4 + (size_t)H * WW * 8 + (size_t)((W + 7) / 8) * ((H + 7) / 8) * 4;
 }
 
-typedef void (*A2bGridKernel)(const unsigned long long*, const int*, const float*, int, int, int, int, int, int, float*, int, int, int*, int,
-                              unsigned long long*);
-// (cell edge, 32-pixel groups per tile) variants; [0] is the default
-static const struct {
-    int cell, npg;
-    A2bGridKernel fn;
-} a2b_grid_variants[] = {{8, 2, nn_a2b_grid_kernel<8, 2>}, {4, 2, nn_a2b_grid_kernel<4, 2>}};
+// cell edge 8 pixels, two 32-pixel groups per tile.  Measured on the config-5 inputs (tools/mesh_loss_bench.py, ms per loss call, B = 256):
+// 8 px cells 0.83 / 0.66 / 0.41, 4 px cells 0.99 / 0.76 / 0.39, 8 x 16-pixel tiles (4 groups per wave) 0.90 / 0.70 / 0.43
+constexpr int A2B_CELL = 8;
+constexpr int A2B_MIN_CELLS = 40;  // images whose vertices occupy fewer cells than this go to the full search
 
 hipError_t hpe_losses_init_device() {
-    for (const auto& v : a2b_grid_variants) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(v.fn), hipFuncAttributeMaxDynamicSharedMemorySize, A2B_GRID_MAX_LDS);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(nn_a2b_grid_kernel<A2B_CELL, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               A2B_GRID_MAX_LDS);
 }
 
 hipError_t hpe_launch_kp_loss(const float* gt, const float* pred, int n, float* out, hipStream_t st) {
@@ -1057,44 +1051,18 @@ hipError_t hpe_launch_mesh_loss_prepare(const float* seg, int B, int H, int W, i
 }
 
 // Per-stage half: both nearest-neighbour searches against the prepared silhouette + the reduction.
-int hpe_mesh_a2b_mode_from_env() {
-    // HPE_MESH_A2B: "grid" (default: cell-grid search), "mfma" / "valu" (the full searches, for A/B comparisons)
-    const char* e = getenv("HPE_MESH_A2B");
-    return !e ? 0 : (e[0] == 'v' ? 1 : (e[0] == 'm' ? 2 : 0));
-}
-
 hipError_t hpe_launch_mesh_loss_search(const float* v2d, int B, int H, int W, int P, float* ws, float* out, hipStream_t st,
                                        hipEvent_t ev_a2b0, hipEvent_t ev_a2b1, int a2b_mode, unsigned long long* counter) {
     const MeshWs m = mesh_ws_layout(ws, B, H, W, P);
     const int HW = H * W;
-    // images whose vertices occupy fewer cells than this go to the full search (0: never)
-    static const int a2b_min_cells = [] {
-        const char* e = getenv("HPE_MESH_A2B_MINCELLS");
-        return e ? atoi(e) : 40;
-    }();
-    static const int a2b_slices = [] {
-        const char* e = getenv("HPE_MESH_A2B_SLICES");  // workgroups per image of the grid search (0: about 512 / B)
-        return e ? atoi(e) : 0;
-    }();
     if (ev_a2b0) (void)hipEventRecord(ev_a2b0, st);
-    static const int a2b_variant = [] {
-        // cell edge 8 (default) / 4 pixels.  Measured on the config-5 inputs (tools/mesh_loss_bench.py, ms per loss call, B = 256):
-        // 8 px cells 0.83 / 0.66 / 0.41, 4 px cells 0.99 / 0.76 / 0.39, 8 x 16-pixel tiles (4 groups per wave) 0.90 / 0.70 / 0.43
-        const char* c = getenv("HPE_MESH_A2B_CELL");
-        const int cell = c ? atoi(c) : 8;
-        for (int i = 0; i < 2; ++i)
-            if (a2b_grid_variants[i].cell == cell) return i;
-        return 0;
-    }();
-    const int cell = a2b_grid_variants[a2b_variant].cell;
+    constexpr int cell = A2B_CELL;
     const int Gx = (W + cell - 1) / cell, Gy = (H + cell - 1) / cell;
     const size_t grid_lds = a2b_grid_lds_bytes(H, W, m.WW, P, Gx, Gy);
     if (a2b_mode == 0 && m.grid_path && grid_lds <= A2B_GRID_MAX_LDS) {
-        int nslice = a2b_slices > 0 ? a2b_slices : (512 + B - 1) / B;
-        nslice = std::max(1, std::min(nslice, m.nA));
-        const int min_cells = a2b_min_cells * (64 / (cell * cell));  // the knob is in 8 x 8-pixel cells
-        hipLaunchKernelGGL(a2b_grid_variants[a2b_variant].fn, dim3(nslice, B), dim3(1024), grid_lds, st, m.bits, m.counts, v2d, H, W, m.WW, P,
-                           Gx, Gy, m.partial, m.nblk, m.nA, m.full_search, min_cells, counter);
+        const int nslice = std::max(1, std::min((512 + B - 1) / B, m.nA));  // workgroups per image: about 512 on the device
+        hipLaunchKernelGGL((nn_a2b_grid_kernel<A2B_CELL, 2>), dim3(nslice, B), dim3(1024), grid_lds, st, m.bits, m.counts, v2d, H, W, m.WW, P,
+                           Gx, Gy, m.partial, m.nblk, m.nA, m.full_search, A2B_MIN_CELLS, counter);
         hipError_t eg = hipGetLastError();
         if (eg != hipSuccess) return eg;
         hipLaunchKernelGGL(nn_a2b_mfma_kernel, dim3(m.nA, B), dim3(256), 0, st, m.pts, m.counts, v2d, HW, P, m.partial, m.nblk,

@@ -61,7 +61,9 @@ typedef struct HpeConfig {
     int encoder_dtype; /* 0 = fp32 MFMA (default), 1 = bf16 MFMA with fp32 accumulate (config 4) */
     /* Plan options that change WHICH kernels run (and therefore the rounding of the result, never its meaning).  -1 = the
      * default: the environment variable named on the right if it is set, else the built-in value.  Fill the struct with
-     * hpe_config_init() first; two contexts with different options can live in one process. */
+     * hpe_config_init() first; two contexts with different options can live in one process.  Every option, the environment-only
+     * ones of INTEGRATION.md section 4 included, is resolved once per context in hpe_finalize (a context used for the loss operators
+     * only: at its first loss call); the environment is not read after that. */
     int n_streams;         /* HPE_STREAMS          concurrent batch-chunk streams of the encoder, 1..4 (2) */
     int dual_gemm;         /* HPE_DUAL             conv_block expand + projection shortcut as one dual-source GEMM (1) */
     int stem_fused;        /* HPE_STEM_FUSED       conv1 + BN + ReLU + max-pool as one kernel (1); 0 = pad / im2col GEMM / pool */
@@ -77,7 +79,8 @@ typedef struct HpeConfig {
                             *                      (no V round trip; takes precedence over wino_f4 for those maps) */
     int bf16_p8;           /* HPE_BF16_P8          bf16 layer kinds on the 256 x 256 phase-interleaved GEMM kernel (N % 256 == 0, K >= 512 only):
                             *                      1 the 3x3 layers of stage 4, 2 those of stage 5, 4 1x1 / strided layers, 8 the dual-source
-                            *                      launch of res5a, 16 the other dual-source launches */
+                            *                      launch of res5a, 16 the other dual-source launches.  A 3x3 layer whose map size is in halo3
+                            *                      runs on the halo-resident kernel whatever bits 1-2 say: clear halo3 to use them */
     int wino4_ksplit;      /* HPE_WINO4_KSPLIT     small F(4x4) launches cut their channel axis into 2-4 parts that are added in part order
                             *                      (1); 0 = never (one summation order per output whatever the batch) */
     int chain_fuse;        /* HPE_CHAIN            bf16 encoder: stages (1 = stage 2, 2 = stage 3) whose identity blocks run res*_branch2c + add +
@@ -90,7 +93,8 @@ typedef struct HpeConfig {
     int halo3;             /* HPE_HALO3            bf16 encoder: map sizes whose 3x3 layers run on the halo-resident kernel (conv3_halo_bf16.hip:
                             *                      the activation tile + halo staged in LDS once per 64 input channels, the 9 taps read it at 9
                             *                      row shifts) instead of the implicit GEMM: bit mask as wino_f4 (1 = 7x7 ... 8 = 56x56) (15); same
-                            *                      operands and rounding points, fp32 summation order differs */
+                            *                      operands and rounding points, fp32 summation order differs.  Takes precedence over bf16_p8
+                            *                      bits 1-2 on the 3x3 layers of the selected maps */
     int f32_split;         /* HPE_F32_SPLIT        fp32 encoder: stages (1 = stage 2, 2 = stage 3, 4 = stage 4, 8 = stage 5) whose 1x1 / strided /
                             *                      dual-source layers run on the bf16 matrix cores with both operands split exactly into three bf16
                             *                      pieces (conv_gemm_f32s.hip: fp32-exact products, fp32 accumulation; whole-tile launches only, small
@@ -297,9 +301,6 @@ int hpe_debug_stem(hpe_ctx* ctx, const float* images_dev, int B, int rows_per_st
  * rounded up to the tile width rows of K floats; K % 32 == 0; tile: 0 = 128x128, 1 = 128x64, 2 = 64x64, 3 = 64x128. */
 int hpe_debug_gemm(hpe_ctx* ctx, const float* x_dev, const float* wt_dev, int M, int N, int K, int w_rows, int tile,
                    const float* residual_dev, int relu, float* y_dev, void* stream);
-/* Diagnostics builds only (-DHPE_ABLATION): device buffer of 2 x u64 per workgroup that hpe_debug_gemm fills with
- * {shader-clock cycles, 100 MHz ticks} of the main loop; NULL disables. */
-int hpe_debug_set_dbg(hpe_ctx* ctx, void* dbg_dev);
 /* ZeroPad(1)+MaxPool3x3/2: x [B,H,H,C] -> y [B,H/2,H/2,C];  global average pool x [B,HW,C] -> y [B,C] */
 int hpe_debug_maxpool(const float* x_dev, int B, int H, int C, float* y_dev, void* stream);
 int hpe_debug_avgpool(const float* x_dev, int B, int HW, int C, float* y_dev, void* stream);

@@ -33,5 +33,5 @@ while time.time() - t0 < secs:
 e1.record(); torch.cuda.synchronize()
 stop = True; th.join()
 ms = e0.elapsed_time(e1) / n
-print("SCHED=%s STAGE=%s M=%d N=%d K=%d tile=%d: %.3f ms %.1f TF; power/clock samples (after 2 s): %s" % (
-    os.environ.get("HPE_SCHED", "-"), os.environ.get("HPE_STAGE", "dma"), M, N, K, tile, ms, 2.0 * M * N * K / ms / 1e9, samples[3:]))
+print("M=%d N=%d K=%d tile=%d: %.3f ms %.1f TF; power/clock samples (after 2 s): %s" % (
+    M, N, K, tile, ms, 2.0 * M * N * K / ms / 1e9, samples[3:]))
