@@ -1,0 +1,47 @@
+"""torch.autograd glue of the HIP backward (include/hpe.h: hpe_smpl_backward, hpe_kp_loss_backward).  Used only when an input
+requires grad: ``HpeEngine.smpl`` / ``SMPL.__call__`` / ``kp_reprojection_loss`` keep their plain forward-only path otherwise.
+Nothing numerical happens here -- forward and backward are one library call each."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from . import engine as _engine
+
+
+class SmplFunction(torch.autograd.Function):
+    """outputs = hpe_smpl(theta); every output is differentiable (cams and theta are pass-through copies of theta's columns)."""
+
+    @staticmethod
+    def forward(ctx, theta, engine, want):
+        th = _engine._require_cuda_tensor(theta.detach(), "theta", (85,))
+        B = th.shape[0]
+        tensors, o = engine._alloc_outputs(B, want)
+        _lib.check(engine.lib.hpe_smpl(engine._h, th.data_ptr(), B, C.byref(o), engine._stream()))
+        ctx.engine, ctx.want = engine, want
+        ctx.save_for_backward(th)
+        return tuple(tensors[k] for k in want)
+
+    @staticmethod
+    def backward(ctx, *grad_outs):
+        (th,) = ctx.saved_tensors
+        grads = {k: g for k, g in zip(ctx.want, grad_outs) if g is not None}
+        return ctx.engine.smpl_backward(th, grads), None, None
+
+
+def smpl_with_grad(engine, theta, want):
+    return dict(zip(want, SmplFunction.apply(theta, engine, want)))
+
+
+class KpLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, kp_gt, kp_pred):
+        ctx.save_for_backward(kp_gt.detach(), kp_pred.detach())
+        return _engine.kp_loss_parts(kp_gt.detach(), kp_pred.detach())[2].clone()
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        kp_gt, kp_pred = ctx.saved_tensors
+        return None, _engine.kp_loss_backward(kp_gt, kp_pred, grad_loss.to(torch.float32))

@@ -176,6 +176,15 @@ int hpe_smpl(hpe_ctx* c, const float* theta, int B, const HpeOutputs* outs, void
     return HPE_OK;
 }
 
+int hpe_smpl_backward(hpe_ctx* c, const float* theta, int B, const HpeOutputs* grad_outs, float* grad_theta, void* stream) {
+    int rc = check_ready(c, B, NEED_SMPL);
+    if (rc) return rc;
+    if (!theta || !grad_outs || !grad_theta) return fail(HPE_ERR_INVALID, "null pointer");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(hpe_launch_smpl_backward(c->smpl, c->bwd, theta, B, grad_outs, grad_theta, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
 int hpe_forward(hpe_ctx* c, const float* images, int B, const HpeOutputs* stage_outs, int n_outs, void* stream) {
     return forward_impl(c, images, B, stage_outs, n_outs, static_cast<hipStream_t>(stream), false);
 }
@@ -318,6 +327,12 @@ int hpe_get_original(const float* verts, const float* cam, int B, int P, int K, 
 int hpe_kp_loss(const float* kp_gt, const float* kp_pred, int B, int K, float* out, void* stream) {
     if (!kp_gt || !kp_pred || !out || B < 1 || K < 1) return fail(HPE_ERR_INVALID, "bad argument");
     HIP_TRY(hpe_launch_kp_loss(kp_gt, kp_pred, B * K, out, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+int hpe_kp_loss_backward(const float* kp_gt, const float* kp_pred, int B, int K, const float* grad_loss, float* grad_kp_pred, void* stream) {
+    if (!kp_gt || !kp_pred || !grad_kp_pred || B < 1 || K < 1) return fail(HPE_ERR_INVALID, "bad argument");
+    HIP_TRY(hpe_launch_kp_loss_backward(kp_gt, kp_pred, B * K, grad_loss, grad_kp_pred, static_cast<hipStream_t>(stream)));
     return HPE_OK;
 }
 

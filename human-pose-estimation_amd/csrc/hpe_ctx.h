@@ -97,6 +97,7 @@ struct hpe_ctx {
     // device: SMPL
     SmplDev smpl{};
     SmplWork work{};
+    SmplBwdWork bwd{};  // hpe_smpl_backward
     float* smpl_basis_src = nullptr;  // [11][V*3]: v_template | shapedirs^T
     // device: activations
     float *padded = nullptr, *X0 = nullptr, *X1 = nullptr, *T1 = nullptr, *T2 = nullptr, *SC = nullptr;

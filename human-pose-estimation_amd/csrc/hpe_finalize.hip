@@ -497,11 +497,20 @@ static int size_workspaces(hpe_ctx* c) {
         if ((rc = dev_alloc(c, &c->work.cams, Bpad * 4, true))) return rc;
         if ((rc = dev_alloc(c, &c->work.verts_tmp, B * HPE_NUM_VERTS * 3, false))) return rc;
         if ((rc = dev_alloc(c, &c->work.kp_part, (size_t)SMPL_SMALL_B * ((HPE_NUM_VERTS + 63) / 64) * 72, true))) return rc;
+        // hpe_smpl_backward recomputes the forward's per-image operands into buffers of its own
+        if ((rc = dev_alloc(c, &c->bwd.pfT, 207 * Bpad, true))) return rc;
+        if ((rc = dev_alloc(c, &c->bwd.betaT, 10 * Bpad, true))) return rc;
+        if ((rc = dev_alloc(c, &c->bwd.A, Bpad * 288, true))) return rc;
+        if ((rc = dev_alloc(c, &c->bwd.cams, Bpad * 4, true))) return rc;
+        if ((rc = dev_alloc(c, &c->bwd.rjg, Bpad * 576, true))) return rc;
+        if ((rc = dev_alloc(c, &c->bwd.gj, Bpad * 120, true))) return rc;
+        if ((rc = dev_alloc(c, &c->bwd.part, hpe_smpl_bwd_part_floats((int)Bpad), true))) return rc;
         // reprojection-loss workspace for the geometry the path itself produces (config 5); other sizes grow it on demand
         c->loss_ws_floats = hpe_mesh_loss_ws_floats(c->cfg.max_batch, HPE_IMG_SIZE, HPE_IMG_SIZE, HPE_NUM_VERTS);
         if ((rc = dev_alloc(c, &c->loss_ws, c->loss_ws_floats, true))) return rc;
     }
     c->work.Bpad = (int)Bpad;
+    c->bwd.Bpad = (int)Bpad;
     return HPE_OK;
 }
 

@@ -192,8 +192,28 @@ hipError_t hpe_launch_joint_regress(const float* X, const float* reg, int n, int
 hipError_t hpe_launch_orth_proj(const float* X, const float* cam, int B, int P, float sx, float sy, int pixels, float* out,
                                 hipStream_t st);
 
+// smpl_bwd.hip: the gradient of hpe_launch_smpl with respect to theta.  Its workspace is its own (a backward call reads nothing a
+// forward call left behind): the forward's per-image operands recomputed from theta, and the per-(vertex tile, image) partial sums
+#define SMPL_BWD_PART 512  // floats per partial: dA 288 | d pose_feature 207 | d beta 10 | camera sums 3 | 4 unused
+struct SmplBwdWork {
+    float* pfT;    // [207][Bpad]
+    float* betaT;  // [10][Bpad]
+    float* A;      // [Bpad][24][12]
+    float* cams;   // [Bpad][4]
+    float* rjg;    // [Bpad][24][24]  R (9) | J (3) | G (12) per joint
+    float* gj;     // [Bpad][24][5]   cotangent reaching joints (3) | g_kp2d (2) per keypoint
+    float* part;   // hpe_smpl_bwd_part_floats(Bpad)
+    int Bpad;
+};
+size_t hpe_smpl_bwd_part_floats(int Bpad);
+// g: cotangents of the forward outputs (nullptr = zero); grad_theta [B][85] is written
+hipError_t hpe_launch_smpl_backward(const SmplDev& d, const SmplBwdWork& w, const float* theta, int B, const HpeOutputs* g,
+                                    float* grad_theta, hipStream_t st);
+
 // losses.hip
 hipError_t hpe_launch_kp_loss(const float* gt, const float* pred, int n, float* out, hipStream_t st);
+// d loss / d pred [n][2] = grad_loss * vis * sign(pred - gt) / (2 * #visible); grad_loss: one device float or nullptr (= 1)
+hipError_t hpe_launch_kp_loss_backward(const float* gt, const float* pred, int n, const float* grad_loss, float* grad_pred, hipStream_t st);
 hipError_t hpe_losses_init_device();  // per-device kernel attributes of the loss kernels
 size_t hpe_mesh_loss_ws_floats(int B, int H, int W, int P);
 // a2b_mode: 0 cell-grid search (default), 1 VALU full search, 2 matrix-core full search; counter: optional 2 x u64 (MFMAs issued

@@ -46,6 +46,26 @@ __global__ __launch_bounds__(256) void kp_loss_kernel(const float* __restrict__ 
     }
 }
 
+// d loss / d pred: the loss is sum(vis * |pred - gt|) / cnt with cnt = 2 * #visible (0 if cnt == 0), so each element gets
+// vis * sign(pred - gt) / cnt (sign(0) = 0); the count is reduced here, on the device
+__global__ __launch_bounds__(256) void kp_loss_bwd_kernel(const float* __restrict__ gt, const float* __restrict__ pred, int n,
+                                                          const float* __restrict__ grad_loss, float* __restrict__ grad_pred) {
+    __shared__ float red[4];
+    float cnt = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) cnt += (gt[i * 3 + 2] != 0.f) ? 2.f : 0.f;
+    const float tc = block_sum_256(cnt, red);
+    const float gl = grad_loss ? grad_loss[0] : 1.0f;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float vis = gt[i * 3 + 2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const float dlt = pred[i * 2 + c] - gt[i * 3 + c];
+            const float sg = dlt > 0.f ? 1.0f : (dlt < 0.f ? -1.0f : 0.f);
+            grad_pred[i * 2 + c] = tc > 0.f ? gl * ((vis * sg) / tc) : 0.f;
+        }
+    }
+}
+
 // ordered compaction of the silhouette pixels of image b: pts[b][i] = (x = col, y = row), row-major order
 // (tf.where order; src/trainer.py:291, src/ops.py:123-125).  Each of the 4 waves owns a contiguous quarter of the image:
 // pass 1 counts (ballot + popcount), the 4 totals give each wave its output offset, pass 2 writes -- coalesced reads, no
@@ -993,6 +1013,11 @@ hipError_t hpe_losses_init_device() {
 
 hipError_t hpe_launch_kp_loss(const float* gt, const float* pred, int n, float* out, hipStream_t st) {
     hipLaunchKernelGGL(kp_loss_kernel, dim3(1), dim3(256), 0, st, gt, pred, n, out);
+    return hipGetLastError();
+}
+
+hipError_t hpe_launch_kp_loss_backward(const float* gt, const float* pred, int n, const float* grad_loss, float* grad_pred, hipStream_t st) {
+    hipLaunchKernelGGL(kp_loss_bwd_kernel, dim3(1), dim3(256), 0, st, gt, pred, n, grad_loss, grad_pred);
     return hipGetLastError();
 }
 

@@ -395,12 +395,55 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_regress_stage(self._h, features.data_ptr(), tp, B, out.data_ptr(), self._stream()))
         return out
 
+    def _output_shapes(self, B):
+        return {
+            "verts": (B, NUM_VERTS, 3),
+            "joints": (B, self.num_kp, 3),
+            "cams": (B, 3),
+            "theta": (B, 85),
+            "J_transformed": (B, 24, 3),
+            "kp2d": (B, self.num_kp, 2),
+            "verts2d": (B, NUM_VERTS, 2),
+            "Rs": (B, 24, 3, 3),
+        }
+
     def smpl(self, theta, want=("verts", "joints", "J_transformed", "kp2d", "Rs")):
+        """hpe_smpl on theta rows [B,85].  A theta that requires grad goes through ``autograd.SmplFunction`` (the outputs then
+        backpropagate through hpe_smpl_backward); any other theta takes the plain call below."""
+        if _torch().is_grad_enabled() and isinstance(theta, _torch().Tensor) and theta.requires_grad:
+            from .autograd import smpl_with_grad
+
+            return smpl_with_grad(self, theta, tuple(want))
         theta = _require_cuda_tensor(theta, "theta", (85,))
         B = theta.shape[0]
         t, o = self._alloc_outputs(B, want)
         _lib.check(self.lib.hpe_smpl(self._h, theta.data_ptr(), B, C.byref(o), self._stream()))
         return t
+
+    def smpl_backward(self, theta, grads):
+        """Gradient of ``smpl`` (hpe_smpl_backward): theta [B,85], grads {output name: cotangent tensor of that output's shape}
+        (a missing name or None = zero) -> grad_theta [B,85].  Any B: chunks of max_batch images, as SMPL.__call__ does."""
+        torch = _torch()
+        theta = _require_cuda_tensor(theta.detach(), "theta", (85,))
+        B = theta.shape[0]
+        shapes = self._output_shapes(B)
+        g = {}
+        for k, v in grads.items():
+            if k not in shapes:
+                raise KeyError("unknown output %r (known: %s)" % (k, ", ".join(_lib.OUTPUT_FIELDS)))
+            if v is None:
+                continue
+            v = _require_cuda_tensor(v.detach(), "grads[%r]" % k)
+            if tuple(v.shape) != shapes[k]:
+                raise ValueError("grads[%r] must have shape %s, got %s" % (k, shapes[k], tuple(v.shape)))
+            g[k] = v
+        out = self._new(B, 85)
+        mb = self.max_batch
+        for lo in range(0, B, mb):
+            n = min(mb, B - lo)
+            o = _lib.HpeOutputs(*[g[k][lo : lo + n].data_ptr() if k in g else None for k in _lib.OUTPUT_FIELDS])
+            _lib.check(self.lib.hpe_smpl_backward(self._h, theta[lo : lo + n].data_ptr(), n, C.byref(o), out[lo : lo + n].data_ptr(), self._stream()))
+        return out
 
     def mesh_loss(self, seg, verts2d):
         torch = _torch()
@@ -547,6 +590,21 @@ def reproject(verts, cam, im_w, im_h):
         _lib.check(
             _lib.load().hpe_reproject_vertices(verts.data_ptr(), cam.data_ptr(), B, P, float(im_w), float(im_h), out.data_ptr(), _cur_stream(verts))
         )
+    return out
+
+
+def kp_loss_backward(kp_gt, kp_pred, grad_loss=None):
+    """d kp_reprojection_loss / d kp_pred (hpe_kp_loss_backward): grad_loss = one-element CUDA float tensor or None (= 1)"""
+    kp_gt = _require_cuda_tensor(kp_gt, "kp_gt")
+    kp_pred = _require_cuda_tensor(kp_pred, "kp_pred")
+    B, K = kp_gt.shape[0], kp_gt.shape[1]
+    gl = None
+    if grad_loss is not None:
+        grad_loss = _require_cuda_tensor(grad_loss.reshape(1), "grad_loss")
+        gl = grad_loss.data_ptr()
+    out = _torch().empty((B, K, 2), dtype=_torch().float32, device=kp_gt.device)
+    with _torch().cuda.device(kp_gt.device):
+        _lib.check(_lib.load().hpe_kp_loss_backward(kp_gt.data_ptr(), kp_pred.data_ptr(), B, K, gl, out.data_ptr(), _cur_stream(kp_gt)))
     return out
 
 

@@ -1,4 +1,4 @@
-"""Loss forwards on the path's outputs (reference: src/ops.py:35-137), HIP-backed (BASELINE config 5)."""
+"""Losses on the path's outputs (reference: src/ops.py:35-137), HIP-backed (BASELINE config 5)."""
 from __future__ import annotations
 
 from . import engine as _engine
@@ -7,7 +7,14 @@ from . import engine as _engine
 def kp_reprojection_loss(kp_gt, kp_pred, scale=1.0, name="kp_reprojection_loss", return_parts=False):
     """kp_gt [N,K,3] (x, y, vis), kp_pred [N,K,2] -> sum(vis*|d|) / (2*#visible), 0 if none visible
     (tf.compat.v1.losses.absolute_difference, SUM_BY_NONZERO_WEIGHTS; src/ops.py:35-47).
-    return_parts=True returns the tensor [numerator, count, loss] so ranks can all-reduce before dividing."""
+    return_parts=True returns the tensor [numerator, count, loss] so ranks can all-reduce before dividing (forward only).
+    A kp_pred that requires grad makes the loss differentiable with respect to it (hpe_kp_loss_backward)."""
+    import torch
+
+    if not return_parts and torch.is_grad_enabled() and isinstance(kp_pred, torch.Tensor) and kp_pred.requires_grad:
+        from .autograd import KpLossFunction
+
+        return KpLossFunction.apply(kp_gt, kp_pred)
     parts = _engine.kp_loss_parts(kp_gt, kp_pred)
     return parts if return_parts else parts[2]
 

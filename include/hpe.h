@@ -191,6 +191,12 @@ int hpe_regress_stage(hpe_ctx* ctx, const float* features_dev, const float* thet
                       void* stream);
 /* self.smpl(shapes, poses, get_skin=True) + proj_fn on theta rows [B,85] (src/predictor.py:136-141). */
 int hpe_smpl(hpe_ctx* ctx, const float* theta_dev, int B, const HpeOutputs* outs, void* stream);
+/* gradient of hpe_smpl: grad_outs holds the cotangent of each forward output (NULL = zero); grad_theta_dev [B,85] is written.
+ * It is what Trainer.train_step backpropagates through SMPL.__call__ and batch_orth_proj_idrot (src/trainer.py:383-505): the exact
+ * derivative of hpe_smpl's arithmetic with respect to [ s, tx, ty | 72 axis-angle | 10 betas ]; the cams / theta cotangents pass
+ * through.  Stateless (theta in, everything else recomputed into a workspace of its own, sized by hpe_finalize: no preceding hpe_smpl
+ * is needed), no synchronisation, no allocation, capturable; fixed summation order: the same inputs give the same bits. */
+int hpe_smpl_backward(hpe_ctx* ctx, const float* theta_dev, int B, const HpeOutputs* grad_outs, float* grad_theta_dev, void* stream);
 /* batch_orth_proj_idrot (src/tf_smpl/projection.py:23-33): X [B,P,3], cam [B,3] -> out [B,P,2] */
 int hpe_orth_proj(const float* X_dev, const float* cam_dev, int B, int P, float* out_dev, void* stream);
 /* reproject_vertices (src/tf_smpl/projection.py:45-56): out = (proj + 1) * 0.5 * im_size */
@@ -200,6 +206,10 @@ int hpe_reproject_vertices(const float* verts_dev, const float* cam_dev, int B, 
  * out_dev[1] = 2*#visible (the SUM_BY_NONZERO_WEIGHTS denominator), out_dev[2] = loss (0 if nothing visible).
  * Numerator and count are returned separately so that ranks can all-reduce them before dividing. */
 int hpe_kp_loss(const float* kp_gt_dev, const float* kp_pred_dev, int B, int K, float* out_dev, void* stream);
+/* gradient of hpe_kp_loss w.r.t. kp_pred: grad_loss_dev is one device float (NULL = 1); grad_kp_pred_dev [B,K,2] =
+ * grad_loss * vis * sign(pred - gt) / (2 * #visible), zero where pred == gt and everywhere when nothing is visible */
+int hpe_kp_loss_backward(const float* kp_gt_dev, const float* kp_pred_dev, int B, int K, const float* grad_loss_dev,
+                         float* grad_kp_pred_dev, void* stream);
 /* mesh_reprojection_loss (src/ops.py:117-137) forward: seg_dev [B,H,W] (>0 = silhouette), verts2d_dev
  * [B,P,2] pixels -> out_dev[0] = sum_i bidirectional_dist_i / (3 + P).  workspace from the ctx.
  * Nearest neighbours (find_nearest_neighbors, src/ops.py:60-71) are exact: the argmin of the expanded squared distance
