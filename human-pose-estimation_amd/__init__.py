@@ -18,7 +18,7 @@ except ValueError:
 from . import resnet_spec, synthetic  # noqa: F401,E402
 from ._lib import HpeError  # noqa: F401
 from .engine import HpeEngine  # noqa: F401
-from .fit import fit_keypoints  # noqa: F401
+from .fit import fit_keypoints, fit_reprojection  # noqa: F401
 from .image import get_original, preprocess_batch, preprocess_image  # noqa: F401
 from .ops import kp_reprojection_loss, mesh_reprojection_loss  # noqa: F401
 from .predictor import Predictor  # noqa: F401

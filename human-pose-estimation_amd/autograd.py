@@ -1,5 +1,6 @@
-"""torch.autograd glue of the HIP backward (include/hpe.h: hpe_smpl_backward, hpe_kp_loss_backward).  Used only when an input
-requires grad: ``HpeEngine.smpl`` / ``SMPL.__call__`` / ``kp_reprojection_loss`` keep their plain forward-only path otherwise.
+"""torch.autograd glue of the HIP backward (include/hpe.h: hpe_smpl_backward, hpe_kp_loss_backward, hpe_mesh_loss_grad).  Used only
+when an input requires grad: ``HpeEngine.smpl`` / ``SMPL.__call__`` / ``kp_reprojection_loss`` / ``mesh_reprojection_loss`` keep their
+plain forward-only path otherwise.
 Nothing numerical happens here -- forward and backward are one library call each."""
 from __future__ import annotations
 
@@ -45,3 +46,19 @@ class KpLossFunction(torch.autograd.Function):
     def backward(ctx, grad_loss):
         kp_gt, kp_pred = ctx.saved_tensors
         return None, _engine.kp_loss_backward(kp_gt, kp_pred, grad_loss.to(torch.float32))
+
+
+class MeshLossFunction(torch.autograd.Function):
+    """loss = mesh_reprojection_loss(seg, verts2d), differentiable in verts2d: the forward is ONE hpe_mesh_loss_grad call, which
+    returns the loss and d loss / d verts2d from the same pair of searches; the backward scales the saved gradient."""
+
+    @staticmethod
+    def forward(ctx, engine, seg, verts2d):
+        loss, grad = engine.mesh_loss_grad(seg.detach(), verts2d.detach())
+        ctx.save_for_backward(grad)
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        (grad,) = ctx.saved_tensors
+        return None, None, grad_loss.to(torch.float32) * grad

@@ -376,6 +376,19 @@ int hpe_mesh_loss(hpe_ctx* c, const float* seg, const float* verts2d, int B, int
     return HPE_OK;
 }
 
+int hpe_mesh_loss_grad(hpe_ctx* c, const float* seg, const float* verts2d, int B, int H, int W, int P, float* out, float* grad_verts2d,
+                       int* nn_pix, int* nn_vert, void* stream) {
+    if (!c) return fail(HPE_ERR_INVALID, "null ctx");
+    if (!seg || !verts2d || !out || B < 1 || H < 1 || W < 1 || P < 1) return fail(HPE_ERR_INVALID, "bad argument");
+    if (!grad_verts2d) return fail(HPE_ERR_INVALID, "hpe_mesh_loss_grad needs grad_verts2d_dev (hpe_mesh_loss is the loss-only call)");
+    DeviceGuard g(c->cfg.device);
+    int rc = ensure_loss_ws(c, B, H, W, P);
+    if (rc) return rc;
+    HIP_TRY(hpe_launch_mesh_loss_grad(seg, verts2d, B, H, W, P, c->loss_ws, out, grad_verts2d, nn_pix, nn_vert, static_cast<hipStream_t>(stream),
+                                      c->plan.mesh_a2b, c->loss_counter));
+    return HPE_OK;
+}
+
 int hpe_val_losses(hpe_ctx* c, const float* seg, const float* kp_gt, const float* const* kp2d, const float* const* verts2d, int n_stage,
                    int B, int K, int H, int W, int P, float* out, void* stream) {
     if (!c) return fail(HPE_ERR_INVALID, "null ctx");

@@ -226,6 +226,11 @@ hipError_t hpe_launch_mesh_loss_prepare(const float* seg, int B, int H, int W, i
 hipError_t hpe_launch_mesh_loss_search(const float* v2d, int B, int H, int W, int P, float* ws, float* out, hipStream_t st,
                                        hipEvent_t ev_a2b0, hipEvent_t ev_a2b1, int a2b_mode, unsigned long long* counter);
 
+// the loss and d loss / d v2d [B][P][2] (for a cotangent of 1) from one pair of searches; nn_pix [B][H*W] / nn_vert [B][P] (optional)
+// receive the neighbours used.  Same workspace (its tail holds the integer sign counters).
+hipError_t hpe_launch_mesh_loss_grad(const float* seg, const float* v2d, int B, int H, int W, int P, float* ws, float* out, float* grad,
+                                     int* nn_pix, int* nn_vert, hipStream_t st, int a2b_mode, unsigned long long* counter);
+
 // prepost.hip
 hipError_t hpe_launch_preprocess_u8(const unsigned char* img, int H, int W, int C, int newH, int newW, int start_x, int start_y,
                                     int margin, float* out, int S, hipStream_t st);

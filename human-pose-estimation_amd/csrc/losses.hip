@@ -26,6 +26,40 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// Extra outputs of the gradient-emitting instantiations of the search bodies (hpe_mesh_loss_grad).  The forward kernels
+// instantiate the same bodies with GRAD = false, where nothing below is read: one body per search, so the neighbour a
+// gradient is taken at is the neighbour the loss was summed over.
+// (A gradient-emitting kernel is the forward kernel's template with GRAD = true and ONE extra trailing argument, the MeshGradOut, passed
+// as the parameter pack GO; with GRAD = false the pack is empty and the kernel has the signature and the code it had before.)
+struct MeshGradOut {
+    int* nn_pix = nullptr;    // [B][H*W] nearest vertex of every silhouette pixel (filled with -1 beforehand); may be null
+    int* sign_cnt = nullptr;  // [B][P][2] sum over the pixels a with nn(a) = v of sign(a - b_v), per axis (zeroed beforehand)
+    int* nn_vert = nullptr;   // [B][P] linear index y * W + x of every vertex' nearest silhouette pixel, -1 if there is none; may be null
+    float* grad = nullptr;    // [B][P][2] receives (b_v - a_nn(v)) / |b_v - a_nn(v)|_2 (0 at distance 0); the finish kernel completes it
+    int W = 0;
+};
+
+// pixel (ax, ay) of image b chose vertex vi = (vx, vy): record it and add sign(a - b) to the vertex' integer counters.  Integer
+// atomics commute exactly, so the counts do not depend on the order the pixels arrive in.
+__device__ __forceinline__ void grad_emit_pixel(int b, int HW, int P, float ax, float ay, int vi, float vx, float vy, const MeshGradOut& g) {
+    if ((unsigned)vi >= (unsigned)P) return;  // no vertex compared below +inf (NaN coordinates): nothing to attribute
+    if (g.nn_pix) g.nn_pix[(size_t)b * HW + (int)ay * g.W + (int)ax] = vi;
+    const int sx = (ax > vx) - (ax < vx), sy = (ay > vy) - (ay < vy);
+    int* c = g.sign_cnt + ((size_t)b * P + vi) * 2;
+    if (sx) atomicAdd(c, sx);
+    if (sy) atomicAdd(c + 1, sy);
+}
+
+// vertex p of image b lies at (dx, dy) from its nearest pixel (cx, cy) (has = false: there is none), d = the distance as the search
+// kernel computed it for the loss (handed in, not recomputed: the gradient instantiation adds the very same value to the loss):
+// neighbour index and unit vector
+__device__ __forceinline__ void grad_emit_vertex(int b, int P, int p, float dx, float dy, float d, bool has, int cx, int cy, const MeshGradOut& g) {
+    // a vertex exactly on its pixel: the term is defined as 0 (tf.norm's gradient is NaN there)
+    const bool ok = has && d > 0.f;
+    if (g.nn_vert) g.nn_vert[(size_t)b * P + p] = has ? cy * g.W + cx : -1;
+    *reinterpret_cast<float2*>(&g.grad[((size_t)b * P + p) * 2]) = make_float2(ok ? dx / d : 0.f, ok ? dy / d : 0.f);
+}
+
 // out[0] = sum vis*|gt-pred|, out[1] = #nonzero broadcast weights (2 per visible kp), out[2] = safe ratio
 __global__ __launch_bounds__(256) void kp_loss_kernel(const float* __restrict__ gt, const float* __restrict__ pred, int n,
                                                       float* __restrict__ out) {
@@ -108,9 +142,10 @@ __global__ __launch_bounds__(256) void sil_compact_kernel(const float* __restric
 // so one broadcast ds_read_b128 serves 4 pair evaluations.
 #define NN_PT 4
 #define NN_BT 1024  // mesh vertices staged per LDS tile (16 KB) -- small enough for 8 waves/SIMD
+template <bool GRAD, class... GO>
 __global__ __launch_bounds__(256) void nn_a2b_kernel(const float* __restrict__ pts, const int* __restrict__ counts,
                                                      const float* __restrict__ v2d, int HW, int P, float* __restrict__ partial,
-                                                     int nblk) {
+                                                     int nblk, GO... go) {
     __shared__ __attribute__((aligned(16))) float sB[NN_BT * 4];  // (x, y, |b|^2, 0)
     __shared__ float red[4];
     const int b = blockIdx.y;
@@ -122,6 +157,7 @@ __global__ __launch_bounds__(256) void nn_a2b_kernel(const float* __restrict__ p
     }
     const float* Bp = v2d + (size_t)b * P * 2;
     float ax[NN_PT], ay[NN_PT], aa[NN_PT], best[NN_PT], cx[NN_PT], cy[NN_PT];
+    int bi[NN_PT];  // GRAD: index of the winner
 #pragma unroll
     for (int u = 0; u < NN_PT; ++u) {
         const int idx = min(base + u * 256 + (int)threadIdx.x, cnt - 1);
@@ -130,6 +166,7 @@ __global__ __launch_bounds__(256) void nn_a2b_kernel(const float* __restrict__ p
         aa[u] = ax[u] * ax[u] + ay[u] * ay[u];
         best[u] = 3.4e38f;
         cx[u] = cy[u] = 0.f;
+        bi[u] = -1;
     }
     for (int p0 = 0; p0 < P; p0 += NN_BT) {
         const int n = min(NN_BT, P - p0);
@@ -149,6 +186,7 @@ __global__ __launch_bounds__(256) void nn_a2b_kernel(const float* __restrict__ p
                 best[u] = lt ? d : best[u];
                 cx[u] = lt ? q.x : cx[u];
                 cy[u] = lt ? q.y : cy[u];
+                if constexpr (GRAD) bi[u] = lt ? p0 + p : bi[u];
             }
         }
     }
@@ -156,7 +194,10 @@ __global__ __launch_bounds__(256) void nn_a2b_kernel(const float* __restrict__ p
 #pragma unroll
     for (int u = 0; u < NN_PT; ++u) {
         const int idx = base + u * 256 + (int)threadIdx.x;
-        if (idx < cnt) contrib += fabsf(ax[u] - cx[u]) + fabsf(ay[u] - cy[u]);
+        if (idx < cnt) {
+            contrib += fabsf(ax[u] - cx[u]) + fabsf(ay[u] - cy[u]);
+            if constexpr (GRAD) grad_emit_pixel(b, HW, P, ax[u], ay[u], bi[u], cx[u], cy[u], go...);
+        }
     }
     const float s = block_sum_256(contrib, red);
     if (threadIdx.x == 0) partial[(size_t)b * nblk + blockIdx.x] = s;
@@ -191,10 +232,11 @@ __device__ __forceinline__ float mfma_k2_value(float a0, float b0, float a1, flo
 #define NN_PG 8  // point groups of 32 per wave -> 1024 points per 256-thread block
 // (the explicit waves-per-SIMD bound makes hipcc keep the MFMA results in VGPRs; without it they land in AGPRs and every value
 // costs an extra v_accvgpr_read before the VALU can touch it)
+template <bool GRAD, class... GO>
 __global__ __launch_bounds__(256, 3) void nn_a2b_mfma_kernel(const float* __restrict__ pts, const int* __restrict__ counts,
                                                           const float* __restrict__ v2d, int HW, int P, float* __restrict__ partial,
                                                           int nblk, const int* __restrict__ only_flagged,
-                                                          unsigned long long* __restrict__ mfma_count) {
+                                                          unsigned long long* __restrict__ mfma_count, GO... go) {
     if (only_flagged && only_flagged[blockIdx.y] == 0) return;  // image already done by the cell-grid search
     __shared__ __attribute__((aligned(16))) float sX[NN_BT];  // -2 bx
     __shared__ __attribute__((aligned(16))) float sY[NN_BT];  // -2 by
@@ -304,7 +346,10 @@ __global__ __launch_bounds__(256, 3) void nn_a2b_mfma_kernel(const float* __rest
         const int oi = __shfl_xor(bi, 32, 64);
         const float ox = __shfl_xor(vx, 32, 64), oy = __shfl_xor(vy, 32, 64);
         const bool take = (ob < best[g]) || (ob == best[g] && oi < bi);
-        if (hi == 0 && idx < cnt) contrib += fabsf(px[g] - (take ? ox : vx)) + fabsf(py[g] - (take ? oy : vy));
+        if (hi == 0 && idx < cnt) {
+            contrib += fabsf(px[g] - (take ? ox : vx)) + fabsf(py[g] - (take ? oy : vy));
+            if constexpr (GRAD) grad_emit_pixel(b, HW, P, px[g], py[g], take ? oi : bi, take ? ox : vx, take ? oy : vy, go...);
+        }
     }
     const float s = block_sum_256(contrib, red);
     if (threadIdx.x == 0) partial[(size_t)b * nblk + blockIdx.x] = s;
@@ -329,11 +374,11 @@ __global__ __launch_bounds__(256, 3) void nn_a2b_mfma_kernel(const float* __rest
 // with an explicit (distance, index) order on the VALU (integer vertex coordinates, duplicated vertices).
 // Typical meshes: 10-30 chunks per tile instead of all 216; a mesh collapsed into a few cells degenerates to the full search.
 // NPG: 32-pixel groups (8 x 4 pixels) per tile, stacked vertically; the tile is 8 x 4 NPG pixels
-template <int CELL, int NPG>
+template <int CELL, int NPG, bool GRAD, class... GO>
 __global__ __launch_bounds__(1024) void nn_a2b_grid_kernel(const unsigned long long* __restrict__ bits, const int* __restrict__ counts,
                                                            const float* __restrict__ v2d, int H, int W, int WW, int P, int Gx, int Gy,
                                                            float* __restrict__ partial, int nblk, int nslots, int* __restrict__ full_search,
-                                                           int min_cells, unsigned long long* __restrict__ mfma_count) {
+                                                           int min_cells, unsigned long long* __restrict__ mfma_count, GO... go) {
     extern __shared__ __attribute__((aligned(16))) unsigned char grid_smem[];
     const int NC = Gx * Gy;
     const int Ppad = (P + 31) & ~31;
@@ -574,6 +619,7 @@ __global__ __launch_bounds__(1024) void nn_a2b_grid_kernel(const unsigned long l
         // winner inside the winning 16-vertex groups of each lane half (the best chunk and the chunks tied with it), then the
         // better half; order (distance, vertex index)
         float wx[NPG], wy[NPG];
+        int wi[NPG];  // GRAD: index of the winner
 #pragma unroll
         for (int g = 0; g < NPG; ++g) {
             float vx = 0.f, vy = 0.f;
@@ -611,6 +657,7 @@ __global__ __launch_bounds__(1024) void nn_a2b_grid_kernel(const unsigned long l
             const bool take = (ob < best[g]) || (ob == best[g] && oi < bi);
             wx[g] = take ? ox : vx;
             wy[g] = take ? oy : vy;
+            wi[g] = take ? oi : bi;
         }
         if (__any(overflow)) {
             // more tied chunks than the lane keeps: the same block again with an explicit (distance, vertex index) order
@@ -640,12 +687,17 @@ __global__ __launch_bounds__(1024) void nn_a2b_grid_kernel(const unsigned long l
                     }
                 }
             }
+#pragma unroll
+            for (int g = 0; g < NPG; ++g) wi[g] = bi[g];
         }
         float contrib = 0.f;
         if (hi == 0) {
 #pragma unroll
             for (int g = 0; g < NPG; ++g)
-                if (active[g]) contrib += fabsf(px[g] - wx[g]) + fabsf(py[g] - wy[g]);
+                if (active[g]) {
+                    contrib += fabsf(px[g] - wx[g]) + fabsf(py[g] - wy[g]);
+                    if constexpr (GRAD) grad_emit_pixel(b, H * W, P, px[g], py[g], wi[g], wx[g], wy[g], go...);
+                }
         }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) contrib += __shfl_xor(contrib, off, 64);
@@ -679,9 +731,10 @@ __global__ __launch_bounds__(1024) void nn_a2b_grid_kernel(const unsigned long l
 // direction B -> A: every mesh vertex finds its nearest silhouette point, contributes ||b - a*||_2.
 // grid (ceil(P/1024), B); 4 vertices per lane; A streamed through LDS in tiles of 2048 points (x, y interleaved,
 // one broadcast ds_read_b128 = 2 points = 8 pair evaluations).
+template <bool GRAD, class... GO>
 __global__ __launch_bounds__(256) void nn_b2a_kernel(const float* __restrict__ pts, const int* __restrict__ counts,
                                                      const float* __restrict__ v2d, int HW, int P, float* __restrict__ partial,
-                                                     int nblk, int blk_off) {
+                                                     int nblk, int blk_off, GO... go) {
     __shared__ __attribute__((aligned(16))) float sA[2048 * 2 + 4];
     __shared__ float red[4];
     const int b = blockIdx.y;
@@ -733,7 +786,14 @@ __global__ __launch_bounds__(256) void nn_b2a_kernel(const float* __restrict__ p
     for (int u = 0; u < NN_PT; ++u) {
         if (live[u] && cnt > 0) {
             const float dx = bx[u] - cx[u], dy = by[u] - cy[u];
-            contrib += sqrtf(dx * dx + dy * dy);
+            const float d = sqrtf(dx * dx + dy * dy);
+            contrib += d;
+            // the winner's coordinates are a pixel's: small integers held in floats
+            if constexpr (GRAD)
+                grad_emit_vertex(b, P, blockIdx.x * 256 * NN_PT + u * 256 + threadIdx.x, dx, dy, d, best[u] < 3.4e38f, (int)cx[u], (int)cy[u], go...);
+        } else {
+            if constexpr (GRAD)
+                if (live[u]) grad_emit_vertex(b, P, blockIdx.x * 256 * NN_PT + u * 256 + threadIdx.x, 0.f, 0.f, 0.f, false, 0, 0, go...);  // empty silhouette
         }
     }
     const float s = block_sum_256(contrib, red);
@@ -811,9 +871,10 @@ __global__ __launch_bounds__(256) void sil_compact_bits_kernel(const unsigned lo
 //    used to scan every row within its horizontal distance; the rows above and below where the shape has narrowed away from it now
 //    cost one rectangle test per 8.  (The rectangle bound is not monotone along the walk -- a farther block may be wider -- so only
 //    the vertical distance ends a direction.)
+template <bool GRAD, class... GO>
 __global__ __launch_bounds__(256) void nn_b2a_rows_kernel(const unsigned long long* __restrict__ bits, const int* __restrict__ counts,
                                                           const float* __restrict__ v2d, int H, int W, int WW, int P,
-                                                          float* __restrict__ partial, int nblk, int blk_off) {
+                                                          float* __restrict__ partial, int nblk, int blk_off, GO... go) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long sbits[];  // [H][WW], then rowinfo[H]
     __shared__ float red[4];
     __shared__ int s_ymin, s_ymax;
@@ -967,6 +1028,10 @@ __global__ __launch_bounds__(256) void nn_b2a_rows_kernel(const unsigned long lo
         }
         const float dx = bx - (float)cx, dy = by - (float)cy;
         contrib = sqrtf(dx * dx + dy * dy);
+        if constexpr (GRAD) grad_emit_vertex(b, P, p, dx, dy, contrib, best < 3.4e38f, cx, cy, go...);
+    } else {
+        if constexpr (GRAD)
+            if (p < P) grad_emit_vertex(b, P, p, 0.f, 0.f, 0.f, false, 0, 0, go...);  // empty silhouette
     }
     const float s = block_sum_256(contrib, red);
     if (threadIdx.x == 0) partial[(size_t)b * nblk + blk_off + blockIdx.x] = s;
@@ -994,6 +1059,20 @@ __global__ __launch_bounds__(1024) void mesh_loss_finish_kernel(const float* __r
     }
 }
 
+// before the gradient-emitting searches: zero sign counters, nn_pix = -1 everywhere (the searches then write the silhouette pixels)
+__global__ __launch_bounds__(256) void mesh_grad_init_kernel(int* __restrict__ sign_cnt, long n_cnt, int* __restrict__ nn_pix, long n_pix) {
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_cnt; i += stride) sign_cnt[i] = 0;
+    if (nn_pix)
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_pix; i += stride) nn_pix[i] = -1;
+}
+
+// grad[b][v][c] = (unit vector term left there by the vertex -> pixel search  -  integer sign count of the pixel -> vertex search) / (3 + P)
+__global__ __launch_bounds__(256) void mesh_grad_finish_kernel(const int* __restrict__ sign_cnt, long n, int P, float* __restrict__ grad) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) grad[i] = (grad[i] - (float)sign_cnt[i]) / (float)(3 + P);
+}
+
 }  // namespace
 
 #define A2B_GRID_MAX_LDS (156 * 1024)
@@ -1007,7 +1086,10 @@ constexpr int A2B_CELL = 8;
 constexpr int A2B_MIN_CELLS = 40;  // images whose vertices occupy fewer cells than this go to the full search
 
 hipError_t hpe_losses_init_device() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(nn_a2b_grid_kernel<A2B_CELL, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nn_a2b_grid_kernel<A2B_CELL, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       A2B_GRID_MAX_LDS);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(nn_a2b_grid_kernel<A2B_CELL, 2, true, MeshGradOut>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                A2B_GRID_MAX_LDS);
 }
 
@@ -1021,12 +1103,16 @@ hipError_t hpe_launch_kp_loss_backward(const float* gt, const float* pred, int n
     return hipGetLastError();
 }
 
-size_t hpe_mesh_loss_ws_floats(int B, int H, int W, int P) {
+// the forward's part of the workspace (layout: mesh_ws_layout)
+static size_t mesh_ws_base_floats(int B, int H, int W, int P) {
     const int HW = H * W;
     const int nblk = (HW + 1023) / 1024 + (P + 255) / 256;
     const size_t bitmap_floats = (size_t)B * H * ((W + 63) / 64) * 2;
     return (size_t)B * HW * 2 + (size_t)B * nblk + (size_t)B + 64 + bitmap_floats + 16 + (size_t)B;
 }
+
+// + the [B][P][2] integer sign counters of hpe_mesh_loss_grad behind it
+size_t hpe_mesh_loss_ws_floats(int B, int H, int W, int P) { return mesh_ws_base_floats(B, H, W, P) + (size_t)B * P * 2; }
 
 // Workspace layout shared by the two halves of the mesh loss
 struct MeshWs {
@@ -1075,36 +1161,61 @@ hipError_t hpe_launch_mesh_loss_prepare(const float* seg, int B, int H, int W, i
     return hipGetLastError();
 }
 
-// Per-stage half: both nearest-neighbour searches against the prepared silhouette + the reduction.
-hipError_t hpe_launch_mesh_loss_search(const float* v2d, int B, int H, int W, int P, float* ws, float* out, hipStream_t st,
-                                       hipEvent_t ev_a2b0, hipEvent_t ev_a2b1, int a2b_mode, unsigned long long* counter) {
+// Per-stage half: both nearest-neighbour searches against the prepared silhouette + the reduction.  GRAD = true launches the
+// gradient-emitting instantiation of every search instead (same dispatch, same geometry) and hands it `go`.
+template <bool GRAD>
+static hipError_t mesh_loss_search(const float* v2d, int B, int H, int W, int P, float* ws, float* out, hipStream_t st, hipEvent_t ev_a2b0,
+                                   hipEvent_t ev_a2b1, int a2b_mode, unsigned long long* counter, const MeshGradOut& go) {
     const MeshWs m = mesh_ws_layout(ws, B, H, W, P);
     const int HW = H * W;
     if (ev_a2b0) (void)hipEventRecord(ev_a2b0, st);
     constexpr int cell = A2B_CELL;
     const int Gx = (W + cell - 1) / cell, Gy = (H + cell - 1) / cell;
     const size_t grid_lds = a2b_grid_lds_bytes(H, W, m.WW, P, Gx, Gy);
+    unsigned long long* const counter1 = counter ? counter + 1 : nullptr;
+    auto full_mfma = [&](const int* only_flagged) {
+        if constexpr (GRAD)
+            hipLaunchKernelGGL((nn_a2b_mfma_kernel<true, MeshGradOut>), dim3(m.nA, B), dim3(256), 0, st, m.pts, m.counts, v2d, HW, P, m.partial, m.nblk,
+                               only_flagged, counter1, go);
+        else
+            hipLaunchKernelGGL((nn_a2b_mfma_kernel<false>), dim3(m.nA, B), dim3(256), 0, st, m.pts, m.counts, v2d, HW, P, m.partial, m.nblk,
+                               only_flagged, counter1);
+    };
     if (a2b_mode == 0 && m.grid_path && grid_lds <= A2B_GRID_MAX_LDS) {
         const int nslice = std::max(1, std::min((512 + B - 1) / B, m.nA));  // workgroups per image: about 512 on the device
-        hipLaunchKernelGGL((nn_a2b_grid_kernel<A2B_CELL, 2>), dim3(nslice, B), dim3(1024), grid_lds, st, m.bits, m.counts, v2d, H, W, m.WW, P,
-                           Gx, Gy, m.partial, m.nblk, m.nA, m.full_search, A2B_MIN_CELLS, counter);
+        if constexpr (GRAD)
+            hipLaunchKernelGGL((nn_a2b_grid_kernel<A2B_CELL, 2, true, MeshGradOut>), dim3(nslice, B), dim3(1024), grid_lds, st, m.bits, m.counts, v2d, H, W,
+                               m.WW, P, Gx, Gy, m.partial, m.nblk, m.nA, m.full_search, A2B_MIN_CELLS, counter, go);
+        else
+            hipLaunchKernelGGL((nn_a2b_grid_kernel<A2B_CELL, 2, false>), dim3(nslice, B), dim3(1024), grid_lds, st, m.bits, m.counts, v2d, H, W, m.WW, P,
+                               Gx, Gy, m.partial, m.nblk, m.nA, m.full_search, A2B_MIN_CELLS, counter);
         hipError_t eg = hipGetLastError();
         if (eg != hipSuccess) return eg;
-        hipLaunchKernelGGL(nn_a2b_mfma_kernel, dim3(m.nA, B), dim3(256), 0, st, m.pts, m.counts, v2d, HW, P, m.partial, m.nblk,
-                               (const int*)m.full_search, counter ? counter + 1 : nullptr);
-    } else if (a2b_mode == 1)
-        hipLaunchKernelGGL(nn_a2b_kernel, dim3(m.nA, B), dim3(256), 0, st, m.pts, m.counts, v2d, HW, P, m.partial, m.nblk);
-    else
-        hipLaunchKernelGGL(nn_a2b_mfma_kernel, dim3(m.nA, B), dim3(256), 0, st, m.pts, m.counts, v2d, HW, P, m.partial, m.nblk,
-                           (const int*)nullptr, counter ? counter + 1 : nullptr);
+        full_mfma((const int*)m.full_search);
+    } else if (a2b_mode == 1) {
+        if constexpr (GRAD)
+            hipLaunchKernelGGL((nn_a2b_kernel<true, MeshGradOut>), dim3(m.nA, B), dim3(256), 0, st, m.pts, m.counts, v2d, HW, P, m.partial, m.nblk, go);
+        else
+            hipLaunchKernelGGL((nn_a2b_kernel<false>), dim3(m.nA, B), dim3(256), 0, st, m.pts, m.counts, v2d, HW, P, m.partial, m.nblk);
+    } else {
+        full_mfma(nullptr);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (ev_a2b1) (void)hipEventRecord(ev_a2b1, st);
     if (m.grid_path) {
-        hipLaunchKernelGGL(nn_b2a_rows_kernel, dim3(m.nB, B), dim3(256), (size_t)H * m.WW * 8 + (size_t)(H + (H + 7) / 8) * 4, st, m.bits, m.counts, v2d, H, W, m.WW, P,
-                           m.partial, m.nblk, m.nA);
+        const size_t rows_lds = (size_t)H * m.WW * 8 + (size_t)(H + (H + 7) / 8) * 4;
+        if constexpr (GRAD)
+            hipLaunchKernelGGL((nn_b2a_rows_kernel<true, MeshGradOut>), dim3(m.nB, B), dim3(256), rows_lds, st, m.bits, m.counts, v2d, H, W, m.WW, P, m.partial,
+                               m.nblk, m.nA, go);
+        else
+            hipLaunchKernelGGL((nn_b2a_rows_kernel<false>), dim3(m.nB, B), dim3(256), rows_lds, st, m.bits, m.counts, v2d, H, W, m.WW, P, m.partial,
+                               m.nblk, m.nA);
     } else {
-        hipLaunchKernelGGL(nn_b2a_kernel, dim3(m.nB, B), dim3(256), 0, st, m.pts, m.counts, v2d, HW, P, m.partial, m.nblk, m.nA);
+        if constexpr (GRAD)
+            hipLaunchKernelGGL((nn_b2a_kernel<true, MeshGradOut>), dim3(m.nB, B), dim3(256), 0, st, m.pts, m.counts, v2d, HW, P, m.partial, m.nblk, m.nA, go);
+        else
+            hipLaunchKernelGGL((nn_b2a_kernel<false>), dim3(m.nB, B), dim3(256), 0, st, m.pts, m.counts, v2d, HW, P, m.partial, m.nblk, m.nA);
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -1113,9 +1224,37 @@ hipError_t hpe_launch_mesh_loss_search(const float* v2d, int B, int H, int W, in
     return hipGetLastError();
 }
 
+hipError_t hpe_launch_mesh_loss_search(const float* v2d, int B, int H, int W, int P, float* ws, float* out, hipStream_t st,
+                                       hipEvent_t ev_a2b0, hipEvent_t ev_a2b1, int a2b_mode, unsigned long long* counter) {
+    return mesh_loss_search<false>(v2d, B, H, W, P, ws, out, st, ev_a2b0, ev_a2b1, a2b_mode, counter, MeshGradOut{});
+}
+
 hipError_t hpe_launch_mesh_loss(const float* seg, const float* v2d, int B, int H, int W, int P, float* ws, float* out,
                                 hipStream_t st, int a2b_mode, unsigned long long* counter) {
     hipError_t e = hpe_launch_mesh_loss_prepare(seg, B, H, W, P, ws, st);
     if (e != hipSuccess) return e;
     return hpe_launch_mesh_loss_search(v2d, B, H, W, P, ws, out, st, nullptr, nullptr, a2b_mode, counter);
+}
+
+// The loss and d loss / d verts2d from one pair of searches: prepare as the forward, clear the integer sign counters (and fill nn_pix
+// with -1), the gradient-emitting searches + the forward's own reduction, then counts and unit vectors are combined in place.
+hipError_t hpe_launch_mesh_loss_grad(const float* seg, const float* v2d, int B, int H, int W, int P, float* ws, float* out, float* grad,
+                                     int* nn_pix, int* nn_vert, hipStream_t st, int a2b_mode, unsigned long long* counter) {
+    hipError_t e = hpe_launch_mesh_loss_prepare(seg, B, H, W, P, ws, st);
+    if (e != hipSuccess) return e;
+    MeshGradOut go;
+    go.nn_pix = nn_pix;
+    go.sign_cnt = reinterpret_cast<int*>(ws + mesh_ws_base_floats(B, H, W, P));
+    go.nn_vert = nn_vert;
+    go.grad = grad;
+    go.W = W;
+    const long n_cnt = (long)B * P * 2, n_pix = (long)B * H * W;
+    const long n_init = nn_pix ? std::max(n_cnt, n_pix) : n_cnt;
+    hipLaunchKernelGGL(mesh_grad_init_kernel, dim3((unsigned)std::min<long>((n_init + 255) / 256, 4096)), dim3(256), 0, st, go.sign_cnt, n_cnt,
+                       nn_pix, n_pix);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    e = mesh_loss_search<true>(v2d, B, H, W, P, ws, out, st, nullptr, nullptr, a2b_mode, counter, go);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(mesh_grad_finish_kernel, dim3((unsigned)((n_cnt + 255) / 256)), dim3(256), 0, st, (const int*)go.sign_cnt, n_cnt, P, grad);
+    return hipGetLastError();
 }

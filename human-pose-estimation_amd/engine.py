@@ -455,6 +455,28 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_mesh_loss(self._h, seg.data_ptr(), verts2d.data_ptr(), B, H, W, P, out.data_ptr(), self._stream()))
         return out[0]
 
+    def mesh_loss_grad(self, seg, verts2d, want_neighbours=False):
+        """hpe_mesh_loss_grad: seg [B,H,W] (> 0 = silhouette), verts2d [B,P,2] -> (loss, grad [B,P,2] = d loss / d verts2d) from one
+        pair of nearest-neighbour searches; want_neighbours=True appends (nn_pix [B,H,W] int32: nearest vertex of every silhouette
+        pixel, -1 elsewhere; nn_vert [B,P] int32: y * W + x of every vertex' nearest silhouette pixel, -1 if there is none)."""
+        torch = _torch()
+        seg = _require_cuda_tensor(seg, "seg")
+        verts2d = _require_cuda_tensor(verts2d, "verts2d")
+        if seg.dim() != 3 or verts2d.dim() != 3 or verts2d.shape[2] != 2 or verts2d.shape[0] != seg.shape[0]:
+            raise ValueError("seg must be [B,H,W] and verts2d [B,P,2], got %s and %s" % (tuple(seg.shape), tuple(verts2d.shape)))
+        B, H, W = seg.shape[0], seg.shape[1], seg.shape[2]
+        P = verts2d.shape[1]
+        out = torch.zeros(4, dtype=torch.float32, device=self.tdev)
+        grad = torch.empty((B, P, 2), dtype=torch.float32, device=self.tdev)
+        nn_pix = nn_vert = None
+        if want_neighbours:
+            nn_pix = torch.empty((B, H, W), dtype=torch.int32, device=self.tdev)
+            nn_vert = torch.empty((B, P), dtype=torch.int32, device=self.tdev)
+        _lib.check(self.lib.hpe_mesh_loss_grad(self._h, seg.data_ptr(), verts2d.data_ptr(), B, H, W, P, out.data_ptr(), grad.data_ptr(),
+                                               nn_pix.data_ptr() if want_neighbours else None,
+                                               nn_vert.data_ptr() if want_neighbours else None, self._stream()))
+        return (out[0], grad, nn_pix, nn_vert) if want_neighbours else (out[0], grad)
+
     def val_losses(self, kp_gt, kp2d_stages, seg=None, verts2d_stages=None, out=None):
         """Both reprojection losses of every IEF stage in one call (hpe_val_losses): -> tensor [n_stage, 4] =
         (kp numerator, kp count, kp loss, mesh loss sum) per stage.  The silhouette-only work is done once per call."""

@@ -22,7 +22,15 @@ def kp_reprojection_loss(kp_gt, kp_pred, scale=1.0, name="kp_reprojection_loss",
 def mesh_reprojection_loss(engine, seg_gts, silhouette_pred, name="mesh_reprojection_loss"):
     """seg_gts [N,H,W(,1)] (> 0 = silhouette), silhouette_pred [N,6890,2] pixels -> scalar
     sum_i bidirectional_dist_i / (3 + 6890)   (src/ops.py:117-137 with src/trainer.py:291 folded in:
-    the reference first builds tf.where(seg > 0); here the compaction is a kernel of the same call)."""
+    the reference first builds tf.where(seg > 0); here the compaction is a kernel of the same call).
+    A silhouette_pred that requires grad makes the loss differentiable with respect to it (hpe_mesh_loss_grad; the silhouette is a
+    constant)."""
     if seg_gts.dim() == 4:
         seg_gts = seg_gts[..., 0]
+    import torch
+
+    if torch.is_grad_enabled() and isinstance(silhouette_pred, torch.Tensor) and silhouette_pred.requires_grad:
+        from .autograd import MeshLossFunction
+
+        return MeshLossFunction.apply(engine, seg_gts.contiguous(), silhouette_pred)
     return engine.mesh_loss(seg_gts.contiguous(), silhouette_pred)

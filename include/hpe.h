@@ -15,7 +15,7 @@
  *     pointers owned by the caller (e.g. torch tensors' data_ptr()).  All tensors are dense float32.
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  No call synchronises the
  *     device except hpe_create / hpe_load_* / hpe_finalize / hpe_destroy / hpe_get_timings / hpe_device_status,
- *     and hpe_mesh_loss / hpe_val_losses ONCE when they meet a problem larger than the loss workspace
+ *     and hpe_mesh_loss / hpe_mesh_loss_grad / hpe_val_losses ONCE when they meet a problem larger than the loss workspace
  *     hpe_finalize sized (max_batch images of 224 x 224, 6890 vertices): that call synchronises, frees the
  *     old workspace and allocates the larger one (such a call cannot be captured into a hipGraph).
  *   - a hpe_finalize that fails on the device (e.g. out of memory) releases everything it had allocated
@@ -218,6 +218,23 @@ int hpe_kp_loss_backward(const float* kp_gt_dev, const float* kp_pred_dev, int B
  * it evaluates every pair; the two give the same neighbours). */
 int hpe_mesh_loss(hpe_ctx* ctx, const float* seg_dev, const float* verts2d_dev, int B, int H, int W, int P, float* out_dev,
                   void* stream);
+/* mesh_reprojection_loss and its gradient with respect to verts2d in one call (one pair of searches serves both).
+ * out_dev[0] = the loss as hpe_mesh_loss; grad_verts2d_dev [B,P,2] = dL/dverts2d (for an upstream cotangent of 1);
+ * nn_pix_dev [B,H,W] int32 and nn_vert_dev [B,P] int32 receive the neighbours used (either may be NULL).
+ * The nearest neighbours are argmins and carry no gradient (tf.gather on tf.argmin), so with A the silhouette pixels and B the vertices
+ *   (3 + P) dL/dB_v = (B_v - A_nn(v)) / |B_v - A_nn(v)|_2  -  sum over the pixels a whose nearest vertex is v of sign(A_a - B_v)
+ * (componentwise sign, sign(0) = 0).  nn_pix[b][y][x] = the nearest vertex of a silhouette pixel, -1 off the silhouette;
+ * nn_vert[b][v] = y * W + x of vertex v's nearest silhouette pixel, -1 when the silhouette is empty.
+ * Deliberate deviations from TensorFlow's gradient: a vertex lying exactly on its nearest pixel gets 0 from the first term
+ * (tf.norm's gradient is NaN there), as hpe_kp_loss_backward defines sign(0) = 0; an image with an empty silhouette contributes
+ * nothing to the loss and gets an all-zero gradient.
+ * The second term is accumulated as integers, so the gradient does not depend on execution order: the same inputs give the same bits.
+ * Same rules as hpe_mesh_loss: any H, W, P, a ctx that was never finalized will do, the searches follow the ctx's plan (mesh_a2b),
+ * arguments are checked before any launch, the workspace is the loss workspace (which grows -- and synchronises -- only for a
+ * geometry larger than the one hpe_finalize sized); no allocation or synchronisation otherwise, capturable.
+ * grad_verts2d_dev == NULL is refused (HPE_ERR_INVALID): hpe_mesh_loss is the loss-only call. */
+int hpe_mesh_loss_grad(hpe_ctx* ctx, const float* seg_dev, const float* verts2d_dev, int B, int H, int W, int P,
+                       float* out_dev, float* grad_verts2d_dev, int* nn_pix_dev, int* nn_vert_dev, void* stream);
 
 /* Both reprojection losses of all n_stage IEF stages in ONE call -- what Trainer.val_step evaluates per step
  * (src/trainer.py:274-296): the work that depends only on seg_gts (tf.where compaction, src/trainer.py:291;
