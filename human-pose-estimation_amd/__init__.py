@@ -2,7 +2,8 @@
 
 Host side mirrors the reference's interface for this path: ``Predictor`` (src/predictor.py), ``SMPL``
 (src/tf_smpl/batch_smpl.py), ``batch_orth_proj_idrot`` / ``reproject_vertices`` (src/tf_smpl/projection.py),
-``kp_reprojection_loss`` / ``mesh_reprojection_loss`` (src/ops.py).  All arithmetic runs in the C-ABI
+``kp_reprojection_loss`` / ``mesh_reprojection_loss`` (src/ops.py), ``critic_scores`` /
+``generator_critic_loss`` (CriticNetwork + get_kcs, src/models.py:97-202).  All arithmetic runs in the C-ABI
 library ``lib/libhpe_hip.so`` (include/hpe.h); there is no CPU fallback.
 """
 import os as _os
@@ -20,7 +21,7 @@ from ._lib import HpeError  # noqa: F401
 from .engine import HpeEngine  # noqa: F401
 from .fit import fit_keypoints, fit_reprojection  # noqa: F401
 from .image import get_original, preprocess_batch, preprocess_image  # noqa: F401
-from .ops import kp_reprojection_loss, mesh_reprojection_loss  # noqa: F401
+from .ops import critic_scores, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss  # noqa: F401
 from .predictor import Predictor  # noqa: F401
 from .projection import batch_orth_proj_idrot, reproject_vertices  # noqa: F401
 from .render import SMPLRenderer  # noqa: F401

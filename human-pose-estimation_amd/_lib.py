@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libhpe_hip.so")
 
 NUM_CONV = 53
 NUM_DENSE = 3
+NUM_CRITIC_DENSE = 9
 NUM_VERTS = 6890
 THETA_DIM = 85
 FEATURE_DIM = 2048
@@ -64,6 +65,10 @@ class HpeSmplModel(C.Structure):
         ("parents", C.c_void_p),
         ("num_kp", C.c_int),
     ]
+
+
+class HpeCriticModel(C.Structure):
+    _fields_ = [("kernel", C.c_void_p * NUM_CRITIC_DENSE), ("bias", C.c_void_p * NUM_CRITIC_DENSE)]
 
 
 class HpeRenderParams(C.Structure):
@@ -121,6 +126,12 @@ _PROTOS = {
                                      C.c_void_p, C.c_void_p]),
     "hpe_val_losses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_critic_layer_name": (C.c_char_p, [C.c_int]),
+    "hpe_critic_layer_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
+    "hpe_load_critic": (C.c_int, [C.c_void_p, C.POINTER(HpeCriticModel)]),
+    "hpe_critic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_critic_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_device_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hpe_debug_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

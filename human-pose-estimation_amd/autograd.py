@@ -1,6 +1,6 @@
-"""torch.autograd glue of the HIP backward (include/hpe.h: hpe_smpl_backward, hpe_kp_loss_backward, hpe_mesh_loss_grad).  Used only
-when an input requires grad: ``HpeEngine.smpl`` / ``SMPL.__call__`` / ``kp_reprojection_loss`` / ``mesh_reprojection_loss`` keep their
-plain forward-only path otherwise.
+"""torch.autograd glue of the HIP backward (include/hpe.h: hpe_smpl_backward, hpe_kp_loss_backward, hpe_mesh_loss_grad,
+hpe_critic_backward).  Used only when an input requires grad: ``HpeEngine.smpl`` / ``SMPL.__call__`` / ``kp_reprojection_loss`` /
+``mesh_reprojection_loss`` / ``critic_scores`` keep their plain forward-only path otherwise.
 Nothing numerical happens here -- forward and backward are one library call each."""
 from __future__ import annotations
 
@@ -62,3 +62,22 @@ class MeshLossFunction(torch.autograd.Function):
     def backward(ctx, grad_loss):
         (grad,) = ctx.saved_tensors
         return None, None, grad_loss.to(torch.float32) * grad
+
+
+class CriticFunction(torch.autograd.Function):
+    """scores = hpe_critic(joints, betas, Rs), differentiable in all three (hpe_critic_backward; stateless, so only the inputs are
+    saved)."""
+
+    @staticmethod
+    def forward(ctx, engine, joints, betas, Rs):
+        ctx.engine = engine
+        ctx.save_for_backward(joints.detach(), betas.detach(), Rs.detach())
+        return engine.critic(joints, betas, Rs)
+
+    @staticmethod
+    def backward(ctx, grad_scores):
+        joints, betas, Rs = ctx.saved_tensors
+        names = ("joints", "betas", "Rs")
+        want = tuple(k for k, need in zip(names, ctx.needs_input_grad[1:]) if need)
+        g = ctx.engine.critic_backward(joints, betas, Rs, grad_scores.to(torch.float32).contiguous(), want=want)
+        return (None,) + tuple(g.get(k) for k in names)

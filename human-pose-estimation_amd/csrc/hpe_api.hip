@@ -422,6 +422,87 @@ int hpe_val_losses(hpe_ctx* c, const float* seg, const float* kp_gt, const float
     return HPE_OK;
 }
 
+const char* hpe_critic_layer_name(int idx) { return (idx >= 0 && idx < HPE_NUM_CRITIC_DENSE) ? hpe_critic_layers()[idx].name : nullptr; }
+
+int hpe_critic_layer_shape(int idx, int out[2]) {
+    if (idx < 0 || idx >= HPE_NUM_CRITIC_DENSE || !out) return fail(HPE_ERR_INVALID, "bad critic layer index");
+    out[0] = hpe_critic_layers()[idx].in;
+    out[1] = hpe_critic_layers()[idx].out;
+    return HPE_OK;
+}
+
+int hpe_load_critic(hpe_ctx* c, const HpeCriticModel* m) {
+    if (!c || !m) return fail(HPE_ERR_INVALID, "null argument");
+    if (c->dead) return fail(HPE_ERR_STATE, "hpe_finalize failed on this ctx: destroy it and create a new one");
+    const CriticLayerSpec* L = hpe_critic_layers();
+    size_t off_w[HPE_NUM_CRITIC_DENSE], off_t[HPE_NUM_CRITIC_DENSE], off_b[HPE_NUM_CRITIC_DENSE], total = 0;
+    for (int i = 0; i < HPE_NUM_CRITIC_DENSE; ++i) {
+        if (!m->kernel[i] || !m->bias[i]) return fail(HPE_ERR_INVALID, std::string("critic layer ") + L[i].name + ": null kernel or bias");
+        // every block starts on a 16-byte boundary
+        off_w[i] = total;
+        total += (size_t)round_up(L[i].in * L[i].out, 4);
+        off_t[i] = total;
+        total += (size_t)round_up(L[i].in * L[i].out, 4);
+        off_b[i] = total;
+        total += (size_t)round_up(L[i].out, 4);
+    }
+    std::vector<float> h(total, 0.f);
+    for (int i = 0; i < HPE_NUM_CRITIC_DENSE; ++i) {
+        const int in = L[i].in, out = L[i].out;
+        memcpy(&h[off_w[i]], m->kernel[i], sizeof(float) * in * out);
+        for (int k = 0; k < in; ++k)
+            for (int o = 0; o < out; ++o) h[off_t[i] + (size_t)o * in + k] = m->kernel[i][(size_t)k * out + o];
+        memcpy(&h[off_b[i]], m->bias[i], sizeof(float) * out);
+    }
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(hipDeviceSynchronize());  // a call still running may read the weights that are about to be replaced
+    if (!c->critic_buf) {
+        void* q = nullptr;
+        HIP_TRY(hipMalloc(&q, total * sizeof(float)));
+        c->critic_buf = static_cast<float*>(q);
+    }
+    HIP_TRY(hipMemcpy(c->critic_buf, h.data(), total * sizeof(float), hipMemcpyHostToDevice));
+    for (int i = 0; i < HPE_NUM_CRITIC_DENSE; ++i) {
+        c->critic.w[i] = c->critic_buf + off_w[i];
+        c->critic.wt[i] = c->critic_buf + off_t[i];
+        c->critic.b[i] = c->critic_buf + off_b[i];
+    }
+    c->have_critic = true;
+    return HPE_OK;
+}
+
+static int check_critic(hpe_ctx* c, const float* joints, int K, const float* betas, int betas_stride, const float* Rs, int N) {
+    if (!c) return fail(HPE_ERR_INVALID, "null ctx");
+    if (c->dead) return fail(HPE_ERR_STATE, "hpe_finalize failed on this ctx: destroy it and create a new one");
+    if (!c->have_critic) return fail(HPE_ERR_STATE, "no critic loaded (hpe_load_critic)");
+    if (!joints || !betas || !Rs) return fail(HPE_ERR_INVALID, "null pointer");
+    if (K < 14 || K > HPE_MAX_KP) return fail(HPE_ERR_INVALID, "joints must be [N,K,3] with 14 <= K <= " + std::to_string(HPE_MAX_KP));
+    if (betas_stride < HPE_NUM_BETAS) return fail(HPE_ERR_INVALID, "betas_stride must be >= 10");
+    if (N < 1) return fail(HPE_ERR_INVALID, "N must be >= 1");
+    return HPE_OK;
+}
+
+int hpe_critic(hpe_ctx* c, const float* joints, int K, const float* betas, int betas_stride, const float* Rs, int N, float* scores,
+               float* kcs, void* stream) {
+    int rc = check_critic(c, joints, K, betas, betas_stride, Rs, N);
+    if (rc) return rc;
+    if (!scores) return fail(HPE_ERR_INVALID, "null scores_dev");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(hpe_launch_critic(c->critic, joints, K, betas, betas_stride, Rs, N, scores, kcs, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+int hpe_critic_backward(hpe_ctx* c, const float* joints, int K, const float* betas, int betas_stride, const float* Rs, int N,
+                        const float* grad_scores, float* grad_joints, float* grad_betas, float* grad_Rs, float* grad_kcs, void* stream) {
+    int rc = check_critic(c, joints, K, betas, betas_stride, Rs, N);
+    if (rc) return rc;
+    if (!grad_joints && !grad_betas && !grad_Rs && !grad_kcs) return fail(HPE_ERR_INVALID, "hpe_critic_backward: every output is NULL");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(hpe_launch_critic_backward(c->critic, joints, K, betas, betas_stride, Rs, N, grad_scores, grad_joints, grad_betas, grad_Rs,
+                                       grad_kcs, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
 int hpe_debug_conv(hpe_ctx* c, int idx, const float* x, int B, const float* residual, int relu, float* y, void* stream) {
     int rc = check_ready(c, B, NEED_ENC);
     if (rc) return rc;

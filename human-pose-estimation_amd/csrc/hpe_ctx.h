@@ -102,6 +102,10 @@ struct hpe_ctx {
     // device: activations
     float *padded = nullptr, *X0 = nullptr, *X1 = nullptr, *T1 = nullptr, *T2 = nullptr, *SC = nullptr;
     float *feat = nullptr, *P1 = nullptr, *H1 = nullptr, *H2 = nullptr, *thA = nullptr, *thB = nullptr;
+    // device: critic (hpe_load_critic; valid before and after hpe_finalize, released with the rest of the device state)
+    float* critic_buf = nullptr;  // kernels | transposed kernels | biases of the nine Dense layers
+    CriticW critic{};
+    bool have_critic = false;
     float* loss_ws = nullptr;
     size_t loss_ws_floats = 0;
     std::vector<void*> allocs;

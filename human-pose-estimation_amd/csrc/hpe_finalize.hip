@@ -125,6 +125,12 @@ int hpe_load_mean_theta(hpe_ctx* c, const float* mean85) {
 void release_device_state(hpe_ctx* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     c->allocs.clear();
+    if (c->critic_buf) {
+        (void)hipFree(c->critic_buf);
+        c->critic_buf = nullptr;
+        c->critic = CriticW{};
+        c->have_critic = false;
+    }
     for (auto& a : c->aux)
         if (a) {
             (void)hipStreamDestroy(a);

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "../../include/hpe.h"
+
 // GEMM_DUAL: two A sources summed into one accumulator (K concatenated): k-slabs [0, k1_slabs) come from the dense matrix x
 // (row pitch lda), the rest from the strided NHWC tensor x2 (geometry in Hi / Wi / Cin / Ho / Wo / stride) -- the last 1x1
 // convolution of a ResNet conv_block and its projection shortcut as ONE launch (weights concatenated along k, BN scales folded in)
@@ -209,6 +211,28 @@ size_t hpe_smpl_bwd_part_floats(int Bpad);
 // g: cotangents of the forward outputs (nullptr = zero); grad_theta [B][85] is written
 hipError_t hpe_launch_smpl_backward(const SmplDev& d, const SmplBwdWork& w, const float* theta, int B, const HpeOutputs* g,
                                     float* grad_theta, hipStream_t st);
+
+// critic.hip: CriticNetwork + get_kcs (src/models.py:97-202), forward and the gradient of the scores with respect to the inputs
+#define CRITIC_ROWS 4  // rows per workgroup
+struct CriticLayerSpec {
+    const char* name;  // Keras layer name
+    int in, out;       // kernel [in][out]
+};
+const CriticLayerSpec* hpe_critic_layers();  // HPE_NUM_CRITIC_DENSE entries, the order of hpe_critic_layer_name()
+struct CriticW {  // device pointers into the ctx's one critic buffer
+    const float* w[HPE_NUM_CRITIC_DENSE];   // kernel [in][out] (the Keras layout)
+    const float* wt[HPE_NUM_CRITIC_DENSE];  // its transpose [out][in], read by the backward
+    const float* b[HPE_NUM_CRITIC_DENSE];   // bias [out]
+};
+// joints [N][K][3] (the first 14 are read), betas: 10 floats per row, betas_stride floats apart, Rs [N][24][3][3] (the root is skipped);
+// scores [N][3], kcs [N][169] or nullptr.  One launch, no workspace.
+hipError_t hpe_launch_critic(const CriticW& w, const float* joints, int K, const float* betas, int betas_stride, const float* Rs, long N,
+                             float* scores, float* kcs, hipStream_t st);
+// grad_scores [N][3] or nullptr (= ones); any output may be nullptr.  grad_joints [N][K][3] is the total derivative (the KCS path folded
+// in), grad_kcs [N][169] the partial one with KCS held as an independent input.  One launch, stateless: the hidden layers are recomputed.
+hipError_t hpe_launch_critic_backward(const CriticW& w, const float* joints, int K, const float* betas, int betas_stride, const float* Rs,
+                                      long N, const float* grad_scores, float* grad_joints, float* grad_betas, float* grad_Rs,
+                                      float* grad_kcs, hipStream_t st);
 
 // losses.hip
 hipError_t hpe_launch_kp_loss(const float* gt, const float* pred, int n, float* out, hipStream_t st);

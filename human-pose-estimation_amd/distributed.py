@@ -93,7 +93,8 @@ def reduce_losses(packed_local):
     [n_stage, 4] holds (kp numerator, kp count, kp loss, mesh loss sum) of the local shard for every IEF stage; the whole
     block is summed over the ranks in a single all-reduce (12 floats at 3 stages).  kp_reprojection_loss normalises by the
     GLOBAL visible count, so column 2 is recomputed from the reduced numerator / count (0 if nothing is visible anywhere);
-    the mesh loss is a plain sum over images."""
+    the mesh loss is a plain sum over images.  Columns past the fourth (val_step(critic_loss_weight=...) appends the critic's three
+    score sums and N) are plain sums too and ride in the same all-reduce: only column 2 is recomputed."""
     import torch
 
     dist = _dist()

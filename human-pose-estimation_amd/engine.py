@@ -64,6 +64,7 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_create(C.byref(cfg), C.byref(h)))
         self._h = h
         self._finalized = False
+        self._has_critic = False
         self.tdev = torch.device("cuda", self.device)
 
     # ------------------------------------------------------------------ ingestion
@@ -126,14 +127,44 @@ class HpeEngine(object):
             raise ValueError("mean theta must have 85 entries")
         _lib.check(self.lib.hpe_load_mean_theta(self._h, m[1]))
 
+    def load_critic(self, params):
+        """params: {'critic/<layer name>/kernel' [in,out], 'critic/<layer name>/bias' [out]} for the nine Dense layers of
+        CriticNetwork (hpe_critic_layer_name); valid before or after ``finalize``, loading again replaces the weights."""
+        m = _lib.HpeCriticModel()
+        keep = []
+        shape = (C.c_int * 2)()
+        for i in range(_lib.NUM_CRITIC_DENSE):
+            name = self.lib.hpe_critic_layer_name(i).decode()
+            _lib.check(self.lib.hpe_critic_layer_shape(i, shape))
+            try:
+                k = _lib.f32(params["critic/%s/kernel" % name])
+                b = _lib.f32(params["critic/%s/bias" % name])
+            except KeyError as e:
+                raise KeyError("critic weights lack %s" % e) from None
+            if k[0].shape != (shape[0], shape[1]) or b[0].shape != (shape[1],):
+                raise ValueError("critic/%s: kernel must be %s and bias (%d,), got %s and %s" % (name, (shape[0], shape[1]), shape[1], k[0].shape, b[0].shape))
+            keep += [k, b]
+            m.kernel[i], m.bias[i] = k[1].value, b[1].value
+        _lib.check(self.lib.hpe_load_critic(self._h, C.byref(m)))
+        self._has_critic = True
+
+    @property
+    def has_critic(self):
+        """a critic is loaded in the live ctx (a failed ``finalize`` releases it with the rest of the device state; ``close`` ends it)"""
+        return self._has_critic
+
     def finalize(self):
-        _lib.check(self.lib.hpe_finalize(self._h))
+        rc = self.lib.hpe_finalize(self._h)
+        if rc not in (0, 3):  # a device-side failure leaves the ctx dead, the critic's device copy released (3 = call order: nothing touched)
+            self._has_critic = False
+        _lib.check(rc)
         self._finalized = True
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self.lib.hpe_destroy(self._h)
             self._h = C.c_void_p()
+            self._has_critic = False
 
     def __del__(self):
         try:
@@ -443,6 +474,55 @@ class HpeEngine(object):
             n = min(mb, B - lo)
             o = _lib.HpeOutputs(*[g[k][lo : lo + n].data_ptr() if k in g else None for k in _lib.OUTPUT_FIELDS])
             _lib.check(self.lib.hpe_smpl_backward(self._h, theta[lo : lo + n].data_ptr(), n, C.byref(o), out[lo : lo + n].data_ptr(), self._stream()))
+        return out
+
+    def _critic_inputs(self, joints, betas, Rs):
+        """-> (joints, betas, Rs, N, K, betas_stride): joints [N,K,3] and Rs [N,24,3,3] contiguous; betas [N,10] with unit column
+        stride is used in place whatever its row stride (theta[:, 75:] is not copied)."""
+        joints = _require_cuda_tensor(joints.detach(), "joints")
+        Rs = _require_cuda_tensor(Rs.detach(), "Rs", (24, 3, 3))
+        betas = betas.detach()
+        if not betas.is_cuda or betas.dtype != _torch().float32 or betas.dim() != 2 or betas.shape[1] != 10:
+            raise ValueError("betas must be a float32 CUDA tensor [N,10]")
+        N = joints.shape[0]
+        if joints.dim() != 3 or joints.shape[2] != 3 or not 14 <= joints.shape[1] <= 24:
+            raise ValueError("joints must be [N,K,3] with 14 <= K <= 24, got %s" % (tuple(joints.shape),))
+        if betas.shape[0] != N or Rs.shape[0] != N or N < 1:
+            raise ValueError("joints, betas and Rs must have the same number (>= 1) of rows")
+        if betas.stride(1) != 1 or (N > 1 and betas.stride(0) < 10):
+            betas = betas.contiguous()
+        stride = betas.stride(0) if N > 1 else 10
+        return joints, betas, Rs, N, joints.shape[1], stride
+
+    def critic(self, joints, betas, Rs, want_kcs=False):
+        """hpe_critic: joints [N,K,3] (the first 14 are read), betas [N,10], Rs [N,24,3,3] (the root is skipped) -> scores [N,3]
+        = (joints + KCS, shapes, rotations); want_kcs=True returns (scores, kcs [N,13,13]).  Any N."""
+        joints, betas, Rs, N, K, stride = self._critic_inputs(joints, betas, Rs)
+        scores = self._new(N, 3)
+        kcs = self._new(N, 13, 13) if want_kcs else None
+        _lib.check(self.lib.hpe_critic(self._h, joints.data_ptr(), K, betas.data_ptr(), stride, Rs.data_ptr(), N, scores.data_ptr(),
+                                       kcs.data_ptr() if want_kcs else None, self._stream()))
+        return (scores, kcs) if want_kcs else scores
+
+    def critic_backward(self, joints, betas, Rs, grad_scores=None, want=("joints", "betas", "Rs")):
+        """hpe_critic_backward: the gradient of sum(grad_scores * scores) (grad_scores [N,3]; None = ones) with respect to the inputs
+        named in ``want`` (among joints [N,K,3], betas [N,10], Rs [N,24,3,3], kcs [N,13,13]) -> dict.  'joints' is the total
+        derivative, 'kcs' the partial one with KCS held as an independent input."""
+        shapes_of = {"joints": None, "betas": (10,), "Rs": (24, 3, 3), "kcs": (13, 13)}
+        unknown = [k for k in want if k not in shapes_of]
+        if unknown or not want:
+            raise ValueError("want must name some of %s, got %r" % (sorted(shapes_of), tuple(want)))
+        joints, betas, Rs, N, K, stride = self._critic_inputs(joints, betas, Rs)
+        shapes_of["joints"] = (K, 3)
+        gs = None
+        if grad_scores is not None:
+            gs = _require_cuda_tensor(grad_scores.detach(), "grad_scores", (3,))
+            if gs.shape[0] != N:
+                raise ValueError("grad_scores must be [N,3]")
+        out = {k: self._new(N, *shapes_of[k]) for k in want}
+        ptr = [out[k].data_ptr() if k in out else None for k in ("joints", "betas", "Rs", "kcs")]
+        _lib.check(self.lib.hpe_critic_backward(self._h, joints.data_ptr(), K, betas.data_ptr(), stride, Rs.data_ptr(), N,
+                                                gs.data_ptr() if gs is not None else None, *ptr, self._stream()))
         return out
 
     def mesh_loss(self, seg, verts2d):

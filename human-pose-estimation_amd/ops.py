@@ -1,4 +1,5 @@
-"""Losses on the path's outputs (reference: src/ops.py:35-137), HIP-backed (BASELINE config 5)."""
+"""Losses on the path's outputs (reference: src/ops.py:35-137; the critic term of the generator loss, src/trainer.py:300-313),
+HIP-backed (BASELINE config 5)."""
 from __future__ import annotations
 
 from . import engine as _engine
@@ -34,3 +35,27 @@ def mesh_reprojection_loss(engine, seg_gts, silhouette_pred, name="mesh_reprojec
 
         return MeshLossFunction.apply(engine, seg_gts.contiguous(), silhouette_pred)
     return engine.mesh_loss(seg_gts.contiguous(), silhouette_pred)
+
+
+def critic_scores(engine, joints, shapes, Rs):
+    """critic_network([get_kcs(joints), joints[:, :14], shapes, Rs[:, 1:]]) (src/trainer.py:300-308; CriticNetwork and get_kcs,
+    src/models.py:97-202) as one hpe_critic call: joints [N,K,3], shapes [N,10] (a theta[:, 75:] view is read in place), Rs [N,24,3,3]
+    -> scores [N,3].  An input that requires grad makes the scores differentiable in joints, shapes and Rs (hpe_critic_backward)."""
+    import torch
+
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (joints, shapes, Rs)):
+        from .autograd import CriticFunction
+
+        return CriticFunction.apply(engine, joints, shapes, Rs)
+    return engine.critic(joints, shapes, Rs)
+
+
+def generator_critic_loss(engine, joints, shapes, Rs, return_parts=False):
+    """-reduce_sum(reduce_mean(critic scores, 0)) (src/trainer.py:309-313, before critic_loss_weight).  return_parts=True returns the
+    tensor [4] = (the three column sums, N) so that ranks can all-reduce before dividing (forward only), as kp_reprojection_loss does."""
+    scores = critic_scores(engine, joints, shapes, Rs)
+    if return_parts:
+        import torch
+
+        return torch.cat([scores.detach().sum(0), scores.new_full((1,), float(scores.shape[0]))])
+    return -scores.mean(0).sum()

@@ -11,8 +11,10 @@ Differences, all deliberate:
   * ``load_path`` / ``pretrained_model_path`` are optional (no reference flag defines them, F9);
   * any batch size <= ``config.batch_size`` works (the reference requires equality, F10); larger inputs are
     processed in chunks of ``config.batch_size``;
-  * the optimizers and critic the reference instantiates as import/ctor side effects are dropped; the renderer is built on first
-    access of ``Predictor.renderer`` (``render.SMPLRenderer``);
+  * the optimizers the reference instantiates as import/ctor side effects are dropped; the critic is loaded when its weights are
+    given (``critic_params=``, ``config.critic_params``, ``critic/...`` keys of ``weights.npz``, the checkpoint's ``discriminator``)
+    and serves ``val_step(critic_loss_weight=...)``; the renderer is built on first access of ``Predictor.renderer``
+    (``render.SMPLRenderer``);
   * assets come from ``config.smpl_model_path`` (the SMPL pickle, read by an allow-list unpickler, or .npz) /
     ``neutral_smpl_mean_params.{npz,h5}`` next to it / ``<checkpoint_dir>``: ``weights.npz`` (Keras-layout names) or the
     reference's own ``tf.train.Checkpoint`` files (``tf_checkpoint.py``, no TensorFlow needed),
@@ -40,8 +42,31 @@ def _load_mean_file(smpl_model_path):
     return assets.load_mean_params(smpl_model_path)  # .npz or the deepdish .h5 (predictor.py:93-95)
 
 
+def resolve_critic_params(config, critic_params=None, weights=None, checkpoint_info=None):
+    """Where a Predictor takes its critic from, first match wins: the ``critic_params`` argument, ``config.critic_params``,
+    ``critic/<layer>/kernel|bias`` keys among ``weights`` (config.weights / weights.npz), the ``discriminator`` of the TensorFlow
+    checkpoint the networks were restored from (``checkpoint_info["prefix"]``).  None when there is none -- only a checkpoint with no
+    discriminator at all is passed over; one that is present but incomplete or misshapen raises ``tf_checkpoint.CheckpointError``."""
+    if critic_params is not None:
+        return critic_params
+    critic_params = getattr(config, "critic_params", None)
+    if critic_params is not None:
+        return critic_params
+    if weights is not None and any(k.startswith("critic/") for k in weights):
+        return weights
+    if checkpoint_info is not None:
+        from . import tf_checkpoint
+
+        try:
+            return tf_checkpoint.load_critic_weights(checkpoint_info["prefix"])[0]
+        except tf_checkpoint.NoCriticError:
+            return None
+    return None
+
+
 class Predictor(object):
-    def __init__(self, config, smpl_model=None, mean_params=None, encoder_params=None, regressor_params=None, device=None):
+    def __init__(self, config, smpl_model=None, mean_params=None, encoder_params=None, regressor_params=None, device=None,
+                 critic_params=None):
         import torch
 
         # ---- config information (reference :31-41; load_path / pretrained_model_path optional, F9)
@@ -103,6 +128,11 @@ class Predictor(object):
         self.engine.load_encoder(encoder_params)
         self.engine.load_regressor(regressor_params)
         self.engine.finalize()
+        # ---- critic (reference src/trainer.py:120,193-198: the checkpoint's `discriminator`); optional: a predictor without one
+        # behaves as it always did, and only val_step(critic_loss_weight=...) asks for it
+        critic_params = resolve_critic_params(config, critic_params, w, self.checkpoint_info)
+        if critic_params is not None:
+            self.engine.load_critic(critic_params)
         self.smpl = SMPL(None, engine=self.engine)
         self.mean_var = torch.from_numpy(self.mean_np).to(self.engine.tdev)
         # the reference tracks `theta_prev` in its checkpoint as "inital_theta" (:84) but predicts from `mean_var` (:126)
@@ -182,16 +212,27 @@ class Predictor(object):
         return result
 
     def val_step(self, images, seg_gts, kp2d_gts, use_mesh_repro_loss=True, kpr_loss_weight=60.0, mr_loss_weight=0.001,
-                 reduce_fn=None):
-        """Forward + reprojection losses of every IEF stage, i.e. the critic-free part of the reference's
+                 reduce_fn=None, critic_loss_weight=None):
+        """Forward + losses of every IEF stage, i.e. the generator side of the reference's
         ``Trainer.val_step`` (src/trainer.py:226-348; BASELINE config 5): per stage
         ``kpr = 60 * kp_reprojection_loss(kp2d_gts, proj_fn(joints, cams))`` (:274-281) and
         ``mr = 0.001 * mesh_reprojection_loss(where(seg > 0), reproject_vertices(verts, cams, [224, 224]), B)``
         (:285-296).  All stages' (kp numerator, kp count, kp loss, mesh sum) come back from ONE library call
         (``hpe_val_losses``: the silhouette-only work is done once per step) as a ``[n_stage, 4]`` tensor;
         ``reduce_fn(packed) -> packed`` (``distributed.reduce_losses``) lets ranks sum that block in a single all-reduce
-        before the kp division; default is single-process."""
+        before the kp division; default is single-process.
+        ``critic_loss_weight`` (the reference's 0.01, src/config.py:69; None = no critic term, the result of earlier versions) adds
+        the third term of the reference's ``encoder_only=False`` path (src/trainer.py:300-313), per stage
+        ``generator_critic_losses[i] = critic_loss_weight * -reduce_sum(reduce_mean(critic([kcs, joints[:, :14], shapes, Rs[:, 1:]]), 0))``
+        from one ``hpe_critic`` call, and ``critic_parts`` ``[n_stage, 4]`` = (the three column sums of the scores, N).  These are
+        plain sums over images: they are appended to the loss block, so ``reduce_fn`` then receives ONE ``[n_stage, 8]`` block
+        (columns 0-3 as above, 4-7 the critic's) and a step still costs one all-reduce; ``reduce_fn`` must sum the columns past the
+        third over the ranks, as ``distributed.reduce_losses`` does.  It needs a loaded critic."""
         import torch
+
+        if critic_loss_weight is not None and not self.engine.has_critic:
+            raise RuntimeError("val_step(critic_loss_weight=...) needs critic weights: pass critic_params / config.critic_params, put "
+                               "critic/<layer>/kernel|bias into weights.npz, or use a checkpoint that holds its discriminator")
 
         images = self._to_device(images)
         seg = self._to_device(seg_gts)
@@ -203,17 +244,32 @@ class Predictor(object):
         if B > self.batch_size:
             raise ValueError("val_step needs B <= config.batch_size")
         want = ("verts", "joints", "cams", "theta", "kp2d") + (("verts2d",) if use_mesh_repro_loss else ())
+        if critic_loss_weight is not None:
+            want += ("Rs",)
         stages = self.engine.forward(images, all_stages=True, want=want)
         packed = self.engine.val_losses(kp_gt, [st["kp2d"] for st in stages], seg if use_mesh_repro_loss else None,
                                         [st["verts2d"] for st in stages] if use_mesh_repro_loss else None)
+        if critic_loss_weight is not None:
+            # columns 4..7 = the three column sums of the scores and N: plain sums over images, so they ride in the same block
+            # (and the same single collective) as the reprojection losses; reduce_fn recomputes column 2 only
+            from .ops import generator_critic_loss
+
+            parts = torch.stack([generator_critic_loss(self.engine, st["joints"], st["theta"][:, 75:], st["Rs"], return_parts=True)
+                                 for st in stages])
+            packed = torch.cat([packed, parts], 1)
         if reduce_fn is not None:
             packed = reduce_fn(packed)
+        if critic_loss_weight is not None:
+            packed, parts = packed[:, :4].contiguous(), packed[:, 4:].contiguous()
         kpr = [packed[i, 2] * kpr_loss_weight for i in range(len(stages))]
         result = {"kpr_losses": kpr, "pred_keypoints": torch.stack([s["kp2d"] for s in stages], 1),
                   "generated_verts": torch.stack([s["verts"] for s in stages], 1),
                   "generated_cams": torch.stack([s["cams"] for s in stages], 1), "loss_parts": packed}
         if use_mesh_repro_loss:
             result["mr_losses"] = [packed[i, 3] * mr_loss_weight for i in range(len(stages))]
+        if critic_loss_weight is not None:
+            result["critic_parts"] = parts
+            result["generator_critic_losses"] = [-(parts[i, :3] / parts[i, 3]).sum() * critic_loss_weight for i in range(len(stages))]
         return result
 
     def predict_single_image(self, image):

@@ -5,6 +5,7 @@ loads but does not ship:
 * mean theta                  -- stands in for ``neutral_smpl_mean_params.h5`` (reference: src/predictor.py:88-110)
 * ResNet-50 v1 encoder params -- Keras layouts (conv HWIO + bias, BN gamma/beta/moving_mean/moving_variance)
 * regressor params            -- Keras Dense layouts ([in, out] kernel + bias) (reference: src/models.py:60-74)
+* critic params               -- the nine Dense layers of CriticNetwork (reference: src/models.py:158-202)
 * 224x224x3 images in [-1, 1) -- reference input contract (src/util/data_utils.py:72-80)
 
 Everything is generated from counter-based Philox streams, so the build container and the GPU box
@@ -18,6 +19,7 @@ import math
 
 import numpy as np
 
+from .critic_spec import CRITIC_LAYERS
 from .resnet_spec import CONV_SPECS
 
 NUM_VERTS = 6890
@@ -214,6 +216,18 @@ def make_regressor_params(seed=2, variant="survey"):
         p["dense_%d/bias" % i] = g.normal(0, 0.01, fo).astype(np.float32)
     if variant == "bounded":
         p["dense_2/kernel"] = (p["dense_2/kernel"] * np.float32(0.25)).astype(np.float32)
+    return p
+
+
+def make_critic_params(seed=6):
+    """Keras Dense layouts of the critic: ``critic/<layer name>/kernel`` [in,out], ``critic/<layer name>/bias`` [out]; glorot-uniform
+    kernels as Keras initialises them, small non-zero biases (Keras starts them at zero; non-zero ones exercise the bias path)."""
+    g = _rng(seed)
+    p = {}
+    for name, fi, fo in CRITIC_LAYERS:
+        lim = math.sqrt(6.0 / (fi + fo))
+        p["critic/%s/kernel" % name] = g.uniform(-lim, lim, (fi, fo)).astype(np.float32)
+        p["critic/%s/bias" % name] = g.normal(0, 0.05, fo).astype(np.float32)
     return p
 
 

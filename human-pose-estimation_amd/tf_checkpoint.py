@@ -20,7 +20,7 @@ On disk that is ``<dir>/checkpoint`` (a text file naming the newest prefix) plus
     Python attribute names (``feature_extractor`` -> ``layer_with_weights-3`` -> ``kernel``) with, per variable, its
     ``full_name`` (the Keras variable name, e.g. ``res2a_branch2a/kernel``) and its ``checkpoint_key``.
 
-``load_hmr_weights`` walks that graph, so Keras layer names -- not positional guesses -- decide which tensor feeds
+``load_hmr_weights`` (encoder, regressor) and ``load_critic_weights`` (the ``discriminator``) walk that graph, so Keras layer names -- not positional guesses -- decide which tensor feeds
 which ``hpe_load_conv`` / ``hpe_load_dense`` slot; when a checkpoint has no graph entry the positional order of
 keras_applications 1.0.8 / tf.keras >= 2.2 is used and cross-checked against every kernel shape.
 
@@ -36,6 +36,7 @@ import re
 
 import numpy as np
 
+from .critic_spec import CRITIC_LAYERS
 from .resnet_spec import CONV_SPECS
 
 TABLE_MAGIC = 0xDB4775248B80FB57
@@ -592,4 +593,80 @@ def load_hmr_weights(prefix_or_dir, verify=True):
     ckey = "inital_theta" + VAR_SUFFIX
     if ckey in rd:
         out["inital_theta"] = rd.get(ckey)
+    return out, info
+
+
+# ----------------------------------------------------------------------------------------------- the checkpoint's critic
+# CriticNetwork's Dense layers (src/models.py:158-202): Keras layer name -> kernel shape [in, out]; all nine shapes differ
+CRITIC_SHAPES = {name: (fi, fo) for name, fi, fo in CRITIC_LAYERS}
+
+
+class NoCriticError(CheckpointError):
+    """the checkpoint holds no discriminator at all (one that is present but incomplete or misshapen is a plain CheckpointError)"""
+
+
+def load_critic_weights(prefix_or_dir, verify=True):
+    """-> (weights, info): the checkpoint's ``discriminator`` (the CriticNetwork, src/trainer.py:193-198) as the dict
+    ``HpeEngine.load_critic`` takes: ``critic/<Keras layer name>/kernel`` [in,out] and ``critic/<Keras layer name>/bias`` [out].
+    Layers are found by their Keras names through the object graph; failing that (no graph, or names that say nothing) each
+    ``discriminator/layer_with_weights-N`` is assigned by its kernel shape, which is unambiguous because all nine differ.  Every
+    shape is verified either way.  A checkpoint without any discriminator raises NoCriticError (with an object graph: no
+    ``discriminator`` child of the root -- what a restore would see; without one: no ``discriminator/layer_with_weights-N`` key); one
+    that is there but incomplete or misshapen raises CheckpointError."""
+    prefix = str(prefix_or_dir)
+    if os.path.isdir(prefix):
+        p = latest_checkpoint(prefix)
+        if p is None:
+            raise FileNotFoundError("no TensorFlow checkpoint state in %s" % prefix)
+        prefix = p
+    rd = BundleReader(prefix, verify=verify)
+    info = {"prefix": prefix, "resolved_by": None}
+    keys = {}  # Keras layer name -> {"kernel": checkpoint key, "bias": checkpoint key}
+    slots = {}  # N of layer_with_weights-N -> {"kernel": checkpoint key, "bias": checkpoint key}
+    graph = ObjectGraph(rd.get(OBJECT_GRAPH_KEY)) if OBJECT_GRAPH_KEY in rd else None
+    disc = graph.child(0, "discriminator") if graph is not None else None
+    if disc is not None:
+        for lname, nid in graph.nodes[disc]["children"].items():
+            m = re.fullmatch(r"layer_with_weights-(\d+)", lname)
+            if not m:
+                continue
+            for var, vid in graph.nodes[nid]["children"].items():
+                v = graph.variable(vid)
+                if v is None or var not in ("kernel", "bias") or v[1] not in rd:
+                    continue
+                full, ckey = v
+                slots.setdefault(int(m.group(1)), {})[var] = ckey
+                layer = full.split("/")[-2] if "/" in full else ""
+                if layer in CRITIC_SHAPES:
+                    keys.setdefault(layer, {})[var] = ckey
+    elif graph is not None:
+        raise NoCriticError("%s has no discriminator (critic): its object graph has no such child" % prefix)
+    else:
+        for k in rd.keys():
+            m = re.fullmatch(r"discriminator/layer_with_weights-(\d+)/(kernel|bias)" + re.escape(VAR_SUFFIX), k)
+            if m:
+                slots.setdefault(int(m.group(1)), {})[m.group(2)] = k
+    complete = lambda d: len(d) == len(CRITIC_SHAPES) and all(len(v) == 2 for v in d.values())  # noqa: E731
+    if complete(keys):
+        info["resolved_by"] = "object graph (Keras variable names)"
+    else:
+        by_shape = {shape: name for name, shape in CRITIC_SHAPES.items()}
+        keys = {}
+        for n in sorted(slots):
+            ck = slots[n]
+            name = by_shape.get(tuple(rd.shape(ck["kernel"]))) if "kernel" in ck else None
+            if name is not None and name not in keys and "bias" in ck:
+                keys[name] = ck
+        if not complete(keys):
+            if not slots:
+                raise NoCriticError("%s has no discriminator (critic): no discriminator/layer_with_weights-N variables" % prefix)
+            missing = sorted(set(CRITIC_SHAPES) - set(keys))
+            raise CheckpointError("%s: the discriminator (critic) is incomplete: missing %s" % (prefix, ", ".join(missing)))
+        info["resolved_by"] = "kernel shape"
+    out = {}
+    for name, (fi, fo) in CRITIC_SHAPES.items():
+        k, b = rd.get(keys[name]["kernel"]), rd.get(keys[name]["bias"])
+        if k.shape != (fi, fo) or b.shape != (fo,):
+            raise CheckpointError("critic layer %s has kernel %s and bias %s, expected %s and %s" % (name, k.shape, b.shape, (fi, fo), (fo,)))
+        out["critic/%s/kernel" % name], out["critic/%s/bias" % name] = k, b
     return out, info

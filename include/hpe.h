@@ -40,6 +40,7 @@ extern "C" {
 
 #define HPE_NUM_CONV 53      /* ResNet-50 v1 conv layers, order of hpe_conv_layer_name() */
 #define HPE_NUM_DENSE 3      /* RegressionNetwork: 2133->1024->1024->85 */
+#define HPE_NUM_CRITIC_DENSE 9 /* CriticNetwork (src/models.py:158-202), order of hpe_critic_layer_name() */
 #define HPE_NUM_VERTS 6890
 #define HPE_NUM_JOINTS 24
 #define HPE_NUM_BETAS 10
@@ -235,6 +236,45 @@ int hpe_mesh_loss(hpe_ctx* ctx, const float* seg_dev, const float* verts2d_dev, 
  * grad_verts2d_dev == NULL is refused (HPE_ERR_INVALID): hpe_mesh_loss is the loss-only call. */
 int hpe_mesh_loss_grad(hpe_ctx* ctx, const float* seg_dev, const float* verts2d_dev, int B, int H, int W, int P,
                        float* out_dev, float* grad_verts2d_dev, int* nn_pix_dev, int* nn_vert_dev, void* stream);
+
+/* -- the critic: CriticNetwork + get_kcs (src/models.py:97-202), the learned prior of the generator loss (src/trainer.py:300-313) ------
+ * Nine fp32 Dense layers, Keras layer names and kernel shapes [in, out]:
+ *   0 kcs_dense 169x100 (leaky ReLU 0.2)   1 joints_dense 42x100 (leaky)      2 combined_dense 200x1 on [kcs_dense | joints_dense]
+ *   3 shapes_dense_1 10x10 (ReLU)          4 shapes_dense_2 10x5 (ReLU)       5 shapes_dense_3 5x1
+ *   6 rotation_dense_1 207x300 (leaky)     7 rotation_dense_2 300x100 (leaky) 8 rotation_dense_3 100x1
+ * scores = [combined_dense, shapes_dense_3, rotation_dense_3] per row.  KCS = B^T B [13,13] with B = J^T C [3,13], J the first 14
+ * joints and C the bone matrix of precompute_C_matrix (src/models.py:97-112); the reference's N x 13 x 13 x N tensordot + diag_part
+ * (src/models.py:123-139) is this Gram matrix per row.  The rotation input is Rs[1:], the joints input J, both flattened row-major. */
+/* Keras layer name of critic Dense `idx`; its kernel shape out[0..1] = in, out */
+const char* hpe_critic_layer_name(int idx);
+int hpe_critic_layer_shape(int idx, int out[2]);
+/* Keras layouts, host pointers: kernel[i] [in,out], bias[i] [out] (the checkpoint's `discriminator`, src/trainer.py:193-198) */
+typedef struct HpeCriticModel {
+    const float* kernel[HPE_NUM_CRITIC_DENSE];
+    const float* bias[HPE_NUM_CRITIC_DENSE];
+} HpeCriticModel;
+/* self.critic_network = CriticNetwork() + its restore (src/trainer.py:120,193-198).  Valid before or after hpe_finalize (the critic needs
+ * nothing of the encoder, like the loss operators); synchronises; the ctx owns a device copy, released by hpe_destroy and by a failed
+ * hpe_finalize; loading again replaces the weights. */
+int hpe_load_critic(hpe_ctx* ctx, const HpeCriticModel* host_model);
+/* critic_network([get_kcs(joints), joints[:, :14], shapes, Rs[:, 1:]]) (src/trainer.py:300-308): joints_dev [N,K,3] with
+ * 14 <= K <= HPE_MAX_KP (the first 14 joints are read), betas_dev 10 floats per row, betas_stride (>= 10) floats apart (theta + 75 with
+ * stride 85 works in place), Rs_dev [N,24,3,3] as HpeOutputs.Rs (the root is skipped) -> scores_dev [N,3]; kcs_dev [N,13,13] or NULL.
+ * Any N >= 1.  One launch; no allocation, no synchronisation, capturable; arguments are checked before the launch.  Fixed summation
+ * order: the same inputs give the same bits, and a row's result depends neither on N nor on the row's position.
+ * HPE_ERR_STATE without a loaded critic, HPE_ERR_INVALID for a NULL ctx or a bad shape. */
+int hpe_critic(hpe_ctx* ctx, const float* joints_dev, int K, const float* betas_dev, int betas_stride, const float* Rs_dev, int N,
+               float* scores_dev, float* kcs_dev, void* stream);
+/* Gradient of hpe_critic's scores with respect to its inputs -- what the generator loss backpropagates (src/trainer.py:383-505) and what
+ * the gradient penalty differentiates (tf.gradients(out_interpolated, [kcs, joints, shapes, Rs]), src/trainer.py:566-570).
+ * grad_scores_dev [N,3] or NULL (all ones).  Outputs, any of which may be NULL (all four NULL: HPE_ERR_INVALID): grad_joints_dev [N,K,3]
+ * (joints 14..K-1 get zeros), grad_betas_dev [N,10] dense, grad_Rs_dev [N,24,3,3] (the root gets zeros), grad_kcs_dev [N,13,13].
+ * grad_kcs is the partial derivative with KCS held as an independent input; grad_joints is always the total one, the KCS path folded in:
+ * dL/dB = B (G + G^T), dL/dJ = (dL/dB C^T)^T with G = dL/dKCS.  Stateless (the hidden layers are recomputed); launch rules, summation
+ * order and error codes as hpe_critic. */
+int hpe_critic_backward(hpe_ctx* ctx, const float* joints_dev, int K, const float* betas_dev, int betas_stride, const float* Rs_dev, int N,
+                        const float* grad_scores_dev, float* grad_joints_dev, float* grad_betas_dev, float* grad_Rs_dev,
+                        float* grad_kcs_dev, void* stream);
 
 /* Both reprojection losses of all n_stage IEF stages in ONE call -- what Trainer.val_step evaluates per step
  * (src/trainer.py:274-296): the work that depends only on seg_gts (tf.where compaction, src/trainer.py:291;
