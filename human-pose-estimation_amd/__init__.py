@@ -3,7 +3,8 @@
 Host side mirrors the reference's interface for this path: ``Predictor`` (src/predictor.py), ``SMPL``
 (src/tf_smpl/batch_smpl.py), ``batch_orth_proj_idrot`` / ``reproject_vertices`` (src/tf_smpl/projection.py),
 ``kp_reprojection_loss`` / ``mesh_reprojection_loss`` (src/ops.py), ``critic_scores`` /
-``generator_critic_loss`` (CriticNetwork + get_kcs, src/models.py:97-202).  All arithmetic runs in the C-ABI
+``generator_critic_loss`` (CriticNetwork + get_kcs, src/models.py:97-202), ``critic_wgan_loss`` / ``CriticTrainer`` (the critic
+update, src/trainer.py:508-583).  All arithmetic runs in the C-ABI
 library ``lib/libhpe_hip.so`` (include/hpe.h); there is no CPU fallback.
 """
 import os as _os
@@ -18,10 +19,11 @@ except ValueError:
 
 from . import resnet_spec, synthetic  # noqa: F401,E402
 from ._lib import HpeError  # noqa: F401
+from .critic_train import CriticTrainer  # noqa: F401
 from .engine import HpeEngine  # noqa: F401
 from .fit import fit_keypoints, fit_reprojection  # noqa: F401
 from .image import get_original, preprocess_batch, preprocess_image  # noqa: F401
-from .ops import critic_scores, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss  # noqa: F401
+from .ops import critic_gradient_penalty, critic_scores, critic_wgan_loss, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss  # noqa: F401
 from .predictor import Predictor  # noqa: F401
 from .projection import batch_orth_proj_idrot, reproject_vertices  # noqa: F401
 from .render import SMPLRenderer  # noqa: F401

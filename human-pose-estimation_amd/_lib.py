@@ -132,6 +132,14 @@ _PROTOS = {
     "hpe_critic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_critic_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_critic_param_floats": (C.c_int, []),
+    "hpe_critic_param_offset": (C.c_int, [C.c_int, C.c_int]),
+    "hpe_critic_weight_grad_ws_floats": (C.c_longlong, [C.c_int]),
+    "hpe_critic_reserve": (C.c_int, [C.c_void_p, C.c_int]),
+    "hpe_critic_weight_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_critic_get_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_critic_set_params_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_device_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hpe_debug_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

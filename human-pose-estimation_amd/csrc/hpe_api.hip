@@ -503,6 +503,81 @@ int hpe_critic_backward(hpe_ctx* c, const float* joints, int K, const float* bet
     return HPE_OK;
 }
 
+int hpe_critic_param_floats(void) { return CRITIC_PARAM_FLOATS; }
+
+int hpe_critic_param_offset(int idx, int is_bias) {
+    if (idx < 0 || idx >= HPE_NUM_CRITIC_DENSE) return -1;
+    return hpe_critic_flat_offset(idx, is_bias != 0);
+}
+
+long long hpe_critic_weight_grad_ws_floats(int N) { return N < 1 ? 0 : (long long)hpe_critic_wg_ws_floats(N); }
+
+// Workspace of hpe_critic_weight_grad: grown here, with a device synchronisation, when a call needs more than the ctx holds
+static int ensure_critic_ws(hpe_ctx* c, int N) {
+    const size_t need = hpe_critic_wg_ws_floats(N);
+    if (need <= c->critic_ws_floats) return HPE_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    if (c->critic_ws) {
+        (void)hipFree(c->critic_ws);
+        c->critic_ws = nullptr;
+        c->critic_ws_floats = 0;
+    }
+    void* q = nullptr;
+    HIP_TRY(hipMalloc(&q, need * sizeof(float)));
+    c->critic_ws = static_cast<float*>(q);
+    c->critic_ws_floats = need;
+    return HPE_OK;
+}
+
+int hpe_critic_reserve(hpe_ctx* c, int N) {
+    if (!c) return fail(HPE_ERR_INVALID, "null ctx");
+    if (c->dead) return fail(HPE_ERR_STATE, "hpe_finalize failed on this ctx: destroy it and create a new one");
+    if (N < 1) return fail(HPE_ERR_INVALID, "N must be >= 1");
+    DeviceGuard g(c->cfg.device);
+    return ensure_critic_ws(c, N);
+}
+
+int hpe_critic_weight_grad(hpe_ctx* c, const float* joints, int K, const float* betas, int betas_stride, const float* Rs, int N,
+                           const float* grad_scores, const float* tangent_kcs, const float* tangent_joints, const float* tangent_betas,
+                           const float* tangent_Rs, int tangent_per_row, float* grad_params, void* stream) {
+    int rc = check_critic(c, joints, K, betas, betas_stride, Rs, N);
+    if (rc) return rc;
+    if (!grad_params) return fail(HPE_ERR_INVALID, "null grad_params_dev");
+    if (!grad_scores && !tangent_kcs && !tangent_joints && !tangent_betas && !tangent_Rs)
+        return fail(HPE_ERR_INVALID, "hpe_critic_weight_grad: grad_scores and every tangent are NULL");
+    DeviceGuard g(c->cfg.device);
+    rc = ensure_critic_ws(c, N);
+    if (rc) return rc;
+    HIP_TRY(hpe_launch_critic_weight_grad(c->critic, joints, K, betas, betas_stride, Rs, N, grad_scores, tangent_kcs, tangent_joints,
+                                          tangent_betas, tangent_Rs, tangent_per_row, c->critic_ws, grad_params,
+                                          static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+static int check_critic_params(hpe_ctx* c, const void* flat) {
+    if (!c) return fail(HPE_ERR_INVALID, "null ctx");
+    if (c->dead) return fail(HPE_ERR_STATE, "hpe_finalize failed on this ctx: destroy it and create a new one");
+    if (!c->have_critic) return fail(HPE_ERR_STATE, "no critic loaded (hpe_load_critic)");
+    if (!flat) return fail(HPE_ERR_INVALID, "null flat_dev");
+    return HPE_OK;
+}
+
+int hpe_critic_get_params(hpe_ctx* c, float* flat, void* stream) {
+    int rc = check_critic_params(c, flat);
+    if (rc) return rc;
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(hpe_launch_critic_params(c->critic, flat, false, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+int hpe_critic_set_params_dev(hpe_ctx* c, const float* flat, void* stream) {
+    int rc = check_critic_params(c, flat);
+    if (rc) return rc;
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(hpe_launch_critic_params(c->critic, const_cast<float*>(flat), true, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
 int hpe_debug_conv(hpe_ctx* c, int idx, const float* x, int B, const float* residual, int relu, float* y, void* stream) {
     int rc = check_ready(c, B, NEED_ENC);
     if (rc) return rc;

@@ -106,6 +106,8 @@ struct hpe_ctx {
     float* critic_buf = nullptr;  // kernels | transposed kernels | biases of the nine Dense layers
     CriticW critic{};
     bool have_critic = false;
+    float* critic_ws = nullptr;  // hpe_critic_weight_grad's workspace (hpe_critic_wg_ws_floats), grown outside capture
+    size_t critic_ws_floats = 0;
     float* loss_ws = nullptr;
     size_t loss_ws_floats = 0;
     std::vector<void*> allocs;

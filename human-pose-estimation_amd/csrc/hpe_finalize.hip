@@ -131,6 +131,11 @@ void release_device_state(hpe_ctx* c) {
         c->critic = CriticW{};
         c->have_critic = false;
     }
+    if (c->critic_ws) {
+        (void)hipFree(c->critic_ws);
+        c->critic_ws = nullptr;
+        c->critic_ws_floats = 0;
+    }
     for (auto& a : c->aux)
         if (a) {
             (void)hipStreamDestroy(a);

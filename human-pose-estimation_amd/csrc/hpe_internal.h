@@ -234,6 +234,23 @@ hipError_t hpe_launch_critic_backward(const CriticW& w, const float* joints, int
                                       long N, const float* grad_scores, float* grad_joints, float* grad_betas, float* grad_Rs,
                                       float* grad_kcs, hipStream_t st);
 
+// critic_train.hip: d F / d (critic weights) for F = sum_n [ sum_c grad_scores[n,c] scores[n,c] + <t_n, d(sum_c scores[n,c]) / dx_n> ],
+// as one flat buffer (kernel 0 [in][out], bias 0, kernel 1, ...), and the flat <-> live weights copies
+#define CRITIC_PARAM_FLOATS 114273  // sum over the nine layers of in * out + out
+#define CRITIC_WG_ROW_FLOATS 1664   // workspace floats per row: left operands of the nine layers 1043 | signals 618 | grad_scores 3
+#define CRITIC_WG_CHUNK 64          // rows per partial sum
+int hpe_critic_wg_chunks(long N);
+size_t hpe_critic_wg_ws_floats(long N);  // N rows + one flat partial per chunk (none for a single chunk)
+int hpe_critic_flat_offset(int idx, bool bias);  // idx == HPE_NUM_CRITIC_DENSE (bias false): the total
+// grad_scores [N][3] or nullptr (no first-order term); tangents t_kcs [.][169], t_joints [.][42], t_betas [.][10], t_Rs [.][207] or
+// nullptr, one row shared by all rows (tangent_per_row 0) or one per row; ws: hpe_critic_wg_ws_floats(N); grad_params is overwritten.
+// Three launches (two when N <= CRITIC_WG_CHUNK); fixed summation order, no atomics.
+hipError_t hpe_launch_critic_weight_grad(const CriticW& w, const float* joints, int K, const float* betas, int betas_stride, const float* Rs,
+                                         long N, const float* grad_scores, const float* t_kcs, const float* t_joints, const float* t_betas,
+                                         const float* t_Rs, int tangent_per_row, float* ws, float* grad_params, hipStream_t st);
+// set: flat -> the ctx's kernels, their transposed copies and biases; else the live weights -> flat.  One launch.
+hipError_t hpe_launch_critic_params(const CriticW& w, float* flat, bool set, hipStream_t st);
+
 // losses.hip
 hipError_t hpe_launch_kp_loss(const float* gt, const float* pred, int n, float* out, hipStream_t st);
 // d loss / d pred [n][2] = grad_loss * vis * sign(pred - gt) / (2 * #visible); grad_loss: one device float or nullptr (= 1)

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .critic_spec import PARAM_FLOATS
 from .resnet_spec import CONV_SPECS
 
 NUM_VERTS = _lib.NUM_VERTS
@@ -524,6 +525,69 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_critic_backward(self._h, joints.data_ptr(), K, betas.data_ptr(), stride, Rs.data_ptr(), N,
                                                 gs.data_ptr() if gs is not None else None, *ptr, self._stream()))
         return out
+
+    _TANGENT_SHAPES = {"kcs": (13, 13), "joints": (14, 3), "betas": (10,), "Rs": (23, 3, 3)}
+
+    def critic_weight_grad(self, joints, betas, Rs, grad_scores=None, tangents=None):
+        """hpe_critic_weight_grad: the gradient with respect to the critic's weights of
+
+            F = sum_n [ sum_c grad_scores[n,c] * scores[n,c] + < t_n , d(sum_c scores[n,c]) / d x_n > ]
+
+        as one flat tensor [critic_spec.PARAM_FLOATS] (kernel 0, bias 0, kernel 1, ...).  grad_scores [N,3] or None (no first-order
+        term); tangents: {name: tensor} for some of kcs (13,13), joints (14,3), betas (10,), Rs (23,3,3) -- the root is left out --
+        either all of exactly that shape (one tangent shared by all rows: the reference's gradient penalty) or all with a leading N
+        (one per row).  The result is a sum over the rows in a fixed order: same inputs, same bits."""
+        joints, betas, Rs, N, K, stride = self._critic_inputs(joints, betas, Rs)
+        gs = None
+        if grad_scores is not None:
+            gs = _require_cuda_tensor(grad_scores.detach(), "grad_scores", (3,))
+            if gs.shape[0] != N:
+                raise ValueError("grad_scores must be [N,3]")
+        tangents = {k: v for k, v in (tangents or {}).items() if v is not None}
+        unknown = [k for k in tangents if k not in self._TANGENT_SHAPES]
+        if unknown:
+            raise ValueError("tangents must name some of %s, got %r" % (sorted(self._TANGENT_SHAPES), unknown))
+        if gs is None and not tangents:
+            raise ValueError("critic_weight_grad needs grad_scores or a tangent")
+        per_row, keep = None, {}
+        for k, v in tangents.items():
+            base = self._TANGENT_SHAPES[k]
+            v = _require_cuda_tensor(v.detach(), "tangents[%r]" % k)
+            if tuple(v.shape) == base:
+                row = False
+            elif tuple(v.shape) == (N,) + base:
+                row = True
+            else:
+                raise ValueError("tangents[%r] must be %s or %s, got %s" % (k, base, (N,) + base, tuple(v.shape)))
+            if per_row is not None and row != per_row:
+                raise ValueError("tangents must be all shared or all per row")
+            per_row = row
+            keep[k] = v
+        out = self._new(PARAM_FLOATS)
+        ptr = [keep[k].data_ptr() if k in keep else None for k in ("kcs", "joints", "betas", "Rs")]
+        _lib.check(self.lib.hpe_critic_weight_grad(self._h, joints.data_ptr(), K, betas.data_ptr(), stride, Rs.data_ptr(), N,
+                                                   gs.data_ptr() if gs is not None else None, *ptr, 1 if per_row else 0, out.data_ptr(),
+                                                   self._stream()))
+        return out
+
+    def critic_reserve(self, N):
+        """size the workspace of ``critic_weight_grad`` for N rows ahead of time (a call that needs more grows it itself, which
+        synchronises and cannot happen inside a graph capture)"""
+        _lib.check(self.lib.hpe_critic_reserve(self._h, int(N)))
+
+    def critic_params(self):
+        """hpe_critic_get_params: the live critic weights as one flat CUDA tensor [critic_spec.PARAM_FLOATS] (a copy)"""
+        out = self._new(PARAM_FLOATS)
+        _lib.check(self.lib.hpe_critic_get_params(self._h, out.data_ptr(), self._stream()))
+        return out
+
+    def set_critic_params(self, flat):
+        """hpe_critic_set_params_dev: replace the live critic weights by ``flat`` on the device, in stream order, without a host round
+        trip (``load_critic`` comes first, once; ``critic_spec.flat_to_params`` turns a flat tensor back into its dict)"""
+        flat = _require_cuda_tensor(flat.detach(), "flat")
+        if tuple(flat.shape) != (PARAM_FLOATS,):
+            raise ValueError("flat must be [%d], got %s" % (PARAM_FLOATS, tuple(flat.shape)))
+        _lib.check(self.lib.hpe_critic_set_params_dev(self._h, flat.data_ptr(), self._stream()))
 
     def mesh_loss(self, seg, verts2d):
         torch = _torch()

@@ -276,6 +276,43 @@ int hpe_critic_backward(hpe_ctx* ctx, const float* joints_dev, int K, const floa
                         const float* grad_scores_dev, float* grad_joints_dev, float* grad_betas_dev, float* grad_Rs_dev,
                         float* grad_kcs_dev, void* stream);
 
+/* -- critic training: gradients with respect to the critic's weights (the critic update, src/trainer.py:511-583) -------------
+ * All nine layers' parameters as ONE flat fp32 buffer of hpe_critic_param_floats() floats: kernel 0 [in,out], bias 0, kernel 1, ...
+ * in hpe_critic_layer_name order.  hpe_critic_param_offset(idx, is_bias): the first float of layer idx's kernel (is_bias 0) or bias;
+ * -1 for a bad index. */
+int hpe_critic_param_floats(void);
+int hpe_critic_param_offset(int idx, int is_bias);
+/* Weight gradient of
+ *     F = sum_n [ sum_c grad_scores[n,c] * scores[n,c] + < t_n , d(sum_c scores[n,c]) / dx_n > ]
+ * where x = [kcs, joints[:, :14], shapes, Rs[:, 1:]] and d(...)/dx is exactly hpe_critic_backward's output for grad_scores = ones
+ * (grad_kcs the partial, grad_joints the total derivative): the list tf.gradients(out_interpolated, [kcs, joints, shapes, Rs])
+ * penalises (src/trainer.py:566-572, src/ops.py:153-172).  The first term serves critic_tape.gradient of the WGAN term
+ * (src/trainer.py:546,578), the second the gradient penalty: with the tangent t = d penalty / d (mean gradient) / N shared by all
+ * rows it is the penalty's weight gradient in the reference's form (the norm of the batch mean); one tangent per row gives the
+ * per-row form of the WGAN-GP paper.  The critic is piecewise linear, so no second derivative of an activation is involved, and the
+ * tangent term contributes exactly zero to every bias.
+ * Inputs as hpe_critic.  grad_scores_dev [N,3] or NULL (no first-order term).  Tangents, each may be NULL (zero): tangent_kcs_dev
+ * [.,13,13], tangent_joints_dev [.,14,3] (14 joints whatever K), tangent_betas_dev [.,10] dense, tangent_Rs_dev [.,23,3,3] (without the
+ * root).  tangent_per_row 0: each tangent is ONE row shared by all N rows; otherwise each has N rows.  grad_scores and all four
+ * tangents NULL: HPE_ERR_INVALID.  grad_params_dev [hpe_critic_param_floats()] is overwritten.
+ * Stateless (the hidden layers are recomputed).  Three launches; no synchronisation, capturable, and no allocation while the ctx's
+ * workspace holds hpe_critic_weight_grad_ws_floats(N) floats: a call that needs more grows it after a device synchronisation (not
+ * inside a capture; hpe_critic_reserve(ctx, N) does that ahead of time).  No floating-point atomics; rows are summed in a fixed order
+ * (chunks of 64 rows in row order, chunks in chunk order): the same inputs give the same bits.  The result is a sum over rows, so
+ * unlike hpe_critic's it depends on N and on the order of the rows.  Error codes as hpe_critic. */
+long long hpe_critic_weight_grad_ws_floats(int N);
+int hpe_critic_reserve(hpe_ctx* ctx, int N);
+int hpe_critic_weight_grad(hpe_ctx* ctx, const float* joints_dev, int K, const float* betas_dev, int betas_stride, const float* Rs_dev,
+                           int N, const float* grad_scores_dev, const float* tangent_kcs_dev, const float* tangent_joints_dev,
+                           const float* tangent_betas_dev, const float* tangent_Rs_dev, int tangent_per_row, float* grad_params_dev,
+                           void* stream);
+/* The live weights <-> the flat layout, on the device (critic_optimizer.apply_gradients, src/trainer.py:582-583, then lives in the
+ * caller's one flat tensor).  hpe_critic_set_params_dev also rebuilds the transposed copies hpe_critic_backward reads; one launch each,
+ * no host round trip, no synchronisation, capturable: calls on `stream` see the new weights in stream order (calls on other streams
+ * must be ordered by the caller).  HPE_ERR_STATE without a loaded critic: hpe_load_critic comes first, once. */
+int hpe_critic_get_params(hpe_ctx* ctx, float* flat_dev, void* stream);
+int hpe_critic_set_params_dev(hpe_ctx* ctx, const float* flat_dev, void* stream);
+
 /* Both reprojection losses of all n_stage IEF stages in ONE call -- what Trainer.val_step evaluates per step
  * (src/trainer.py:274-296): the work that depends only on seg_gts (tf.where compaction, src/trainer.py:291;
  * the silhouette bitmap) is done once per call instead of once per stage.
