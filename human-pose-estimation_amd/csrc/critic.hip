@@ -7,28 +7,16 @@
 // Summation order: ONE thread owns one output of one layer for all rows of the tile and adds its k terms in ascending k with fmaf, starting
 // from the bias.  No k axis is split, nothing is reduced across threads, no atomics: a row's bits do not depend on N, on the tile it lands
 // in, or on its slot in that tile (the slots run the same instruction sequence).  The backward recomputes the hidden pre-activations with
-// the forward's own loops and walks the transposed weight copies [out][in] (made once by hpe_load_critic) the same way.
+// the forward's own loops and walks the transposed weight copies [out][in] (made once by hpe_critic_pack_live) the same way.
 #include <hip/hip_runtime.h>
 
-#include "hpe_internal.h"
+#include <string.h>
+
+#include "critic_common.h"
 
 namespace {
 
-constexpr int R = CRITIC_ROWS;
-static_assert(R == 4, "the tile is read as one float4 per k");
-constexpr int NJ = 14, NB = 13, NJF = 42, NKCS = 169, NROT = 207, NBETA = 10;
 constexpr int FWD_THREADS = 384, BWD_THREADS = 512;
-
-// precompute_C_matrix (src/models.py:97-112): bone b = joint b - joint BONE_MINUS[b]
-__constant__ int BONE_MINUS[NB] = {1, 2, 8, 9, 3, 4, 7, 8, 12, 12, 9, 10, 13};
-
-// the activations (leaky ReLU 0.2 after kcs_dense, joints_dense, rotation_dense_1/2; ReLU after shapes_dense_1/2) are in the kernels
-const CriticLayerSpec LAYERS[HPE_NUM_CRITIC_DENSE] = {
-    {"kcs_dense", 169, 100},      {"joints_dense", 42, 100},      {"combined_dense", 200, 1},
-    {"shapes_dense_1", 10, 10},   {"shapes_dense_2", 10, 5},      {"shapes_dense_3", 5, 1},
-    {"rotation_dense_1", 207, 300}, {"rotation_dense_2", 300, 100}, {"rotation_dense_3", 100, 1},
-};
-enum { L_KCS = 0, L_JOINTS = 1, L_COMB = 2, L_S1 = 3, L_S2 = 4, L_S3 = 5, L_R1 = 6, L_R2 = 7, L_R3 = 8 };
 
 struct Tile {  // LDS image of one tile; every [k][R] array is read as float4 per k
     float J[NJF * R];
@@ -43,28 +31,6 @@ struct Tile {  // LDS image of one tile; every [k][R] array is read as float4 pe
     float gk[NKCS * R];    // backward: d L / d KCS
     float dB[R][3][NB];    // backward: d L / d B
 };
-
-__device__ __forceinline__ float slope(float z) { return z > 0.f ? 1.f : 0.2f; }  // tf.nn.leaky_relu, alpha 0.2
-
-// acc[r] = init + sum over k (ascending) of W[k * ld + o] * xs[k][r]
-__device__ __forceinline__ void dense_col(const float* __restrict__ W, int ld, int K, int o, float init, const float* xs, float acc[R]) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = init;
-    const float* w = W + o;
-#pragma unroll 8
-    for (int k = 0; k < K; ++k) {
-        const float wk = w[(size_t)k * ld];
-        const float4 x = *reinterpret_cast<const float4*>(xs + k * R);
-        acc[0] = fmaf(wk, x.x, acc[0]);
-        acc[1] = fmaf(wk, x.y, acc[1]);
-        acc[2] = fmaf(wk, x.z, acc[2]);
-        acc[3] = fmaf(wk, x.w, acc[3]);
-    }
-}
-
-__device__ __forceinline__ void put(float* xs, int o, const float v[R]) {
-    *reinterpret_cast<float4*>(xs + o * R) = make_float4(v[0], v[1], v[2], v[3]);
-}
 
 // inputs of the tile's rows -> LDS (rows past N read as zeros), then KCS = B^T B with B = J^T C, its three terms added in coordinate order
 __device__ void load_tile(Tile& s, const float* joints, int K, const float* betas, int betas_stride, const float* Rs, long row0, long N,
@@ -325,9 +291,51 @@ __global__ __launch_bounds__(BWD_THREADS) void critic_bwd_kernel(CriticW w, cons
     }
 }
 
+// The live weights, one buffer: per layer kernel [in][out] | its transpose [out][in] | bias, every block on a 16-byte boundary
+struct Live {
+    size_t w[NL], wt[NL], b[NL], total;
+};
+constexpr Live make_live() {
+    Live v{};
+    size_t off = 0;
+    for (int l = 0; l < NL; ++l) {
+        const size_t kernel = (size_t)(LAYOUT.in[l] * LAYOUT.out[l] + 3) / 4 * 4, bias = (size_t)(LAYOUT.out[l] + 3) / 4 * 4;
+        v.w[l] = off;
+        v.wt[l] = off + kernel;
+        v.b[l] = off + 2 * kernel;
+        off += 2 * kernel + bias;
+    }
+    v.total = off;
+    return v;
+}
+constexpr Live LIVE = make_live();
+
 }  // namespace
 
 const CriticLayerSpec* hpe_critic_layers() { return LAYERS; }
+
+size_t hpe_critic_live_floats() { return LIVE.total; }
+
+void hpe_critic_pack_live(const HpeCriticModel& m, float* host) {
+    memset(host, 0, LIVE.total * sizeof(float));
+    for (int l = 0; l < NL; ++l) {
+        const int in = LAYOUT.in[l], out = LAYOUT.out[l];
+        memcpy(host + LIVE.w[l], m.kernel[l], sizeof(float) * in * out);
+        for (int k = 0; k < in; ++k)
+            for (int o = 0; o < out; ++o) host[LIVE.wt[l] + (size_t)o * in + k] = m.kernel[l][(size_t)k * out + o];
+        memcpy(host + LIVE.b[l], m.bias[l], sizeof(float) * out);
+    }
+}
+
+CriticW hpe_critic_live_view(const float* buf) {
+    CriticW w{};
+    for (int l = 0; l < NL; ++l) {
+        w.w[l] = buf + LIVE.w[l];
+        w.wt[l] = buf + LIVE.wt[l];
+        w.b[l] = buf + LIVE.b[l];
+    }
+    return w;
+}
 
 hipError_t hpe_launch_critic(const CriticW& w, const float* joints, int K, const float* betas, int betas_stride, const float* Rs, long N,
                              float* scores, float* kcs, hipStream_t st) {

@@ -19,57 +19,22 @@
 // ascending order by one thread per weight.  No atomics, nothing reduced across threads: the same inputs give the same bits.  The result
 // is a sum over rows, so it depends on N and on the order of the rows.
 //
-// The small helpers (dense loops, tile load) repeat critic.hip's: that file's device code is pinned bit for bit and stays untouched.
+// The layer table, the layouts derived from it and the dense loops are critic_common.h's.  Still repeated: the prologue of
+// critic_wg_rows_kernel restates critic.hip's load_tile (three staging loops, KCS = B^T B) with a tangent read beside every input and the
+// tangent products inside the KCS sum.  One loader with a functor for those six points was tried: the compiler then schedules the prologue
+// of all three kernels differently, and their device code is pinned to what it was.
 #include <hip/hip_runtime.h>
 
-#include "hpe_internal.h"
+#include "critic_common.h"
 
 namespace {
 
-constexpr int R = CRITIC_ROWS;
-static_assert(R == 4, "the tile is read as one float4 per k");
-constexpr int NB = 13, NJF = 42, NKCS = 169, NROT = 207, NBETA = 10;
 constexpr int ROW_THREADS = 512, GEMM_THREADS = 256;
-constexpr int NL = HPE_NUM_CRITIC_DENSE;
-enum { L_KCS = 0, L_JOINTS = 1, L_COMB = 2, L_S1 = 3, L_S2 = 4, L_S3 = 5, L_R1 = 6, L_R2 = 7, L_R3 = 8 };
+constexpr int TILE = WG_TILE, KB = 16;  // output tile of the row-reduction GEMM; rows staged in LDS per step
 
-// workspace row: left operands of the nine layers | signals of the nine layers | grad_scores
-constexpr int X_KCS = 0, X_JOINTS = 169, X_COMB = 211, X_S1 = 411, X_S2 = 421, X_S3 = 431, X_R1 = 436, X_R2 = 643, X_R3 = 943, NX = 1043;
-constexpr int S_KCS = NX, S_JOINTS = NX + 100, S_COMB = NX + 200, S_S1 = NX + 201, S_S2 = NX + 211, S_S3 = NX + 216, S_R1 = NX + 217,
-              S_R2 = NX + 517, S_R3 = NX + 617, G_OFF = NX + 618;
-constexpr int ROW_LD = CRITIC_WG_ROW_FLOATS;
-static_assert(G_OFF + 3 == ROW_LD, "workspace row layout");
-
-constexpr int TILE = 64, KB = 16;  // output tile of the row-reduction GEMM; rows staged in LDS per step
-constexpr int N_TILES = 47;
-
-__constant__ int BONE_MINUS[NB] = {1, 2, 8, 9, 3, 4, 7, 8, 12, 12, 9, 10, 13};  // precompute_C_matrix (src/models.py:97-112)
-__constant__ int L_IN[NL] = {169, 42, 200, 10, 10, 5, 207, 300, 100};
-__constant__ int L_OUT[NL] = {100, 100, 1, 10, 5, 1, 300, 100, 1};
-__constant__ int L_X[NL] = {X_KCS, X_JOINTS, X_COMB, X_S1, X_S2, X_S3, X_R1, X_R2, X_R3};
-__constant__ int L_S[NL] = {S_KCS, S_JOINTS, S_COMB, S_S1, S_S2, S_S3, S_R1, S_R2, S_R3};
-__constant__ int L_COL[NL] = {0, 0, 0, 1, 1, 1, 2, 2, 2};                     // the score column a layer feeds
-__constant__ int L_TILE0[NL + 1] = {0, 6, 8, 12, 13, 14, 15, 35, 45, N_TILES};  // first 64 x 64 tile of a layer
-// flat layout: kernel l at L_W[l], bias l right behind it
-__constant__ int L_W[NL + 1] = {0, 17000, 21300, 21501, 21611, 21666, 21672, 84072, 114172, CRITIC_PARAM_FLOATS};
-
-__device__ __forceinline__ float slope(float z) { return z > 0.f ? 1.f : 0.2f; }  // tf.nn.leaky_relu, alpha 0.2
-
-// acc[r] = init + sum over k (ascending) of W[k * ld + o] * xs[k][r]
-__device__ __forceinline__ void dense_col(const float* __restrict__ W, int ld, int K, int o, float init, const float* xs, float acc[R]) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = init;
-    const float* w = W + o;
-#pragma unroll 8
-    for (int k = 0; k < K; ++k) {
-        const float wk = w[(size_t)k * ld];
-        const float4 x = *reinterpret_cast<const float4*>(xs + k * R);
-        acc[0] = fmaf(wk, x.x, acc[0]);
-        acc[1] = fmaf(wk, x.y, acc[1]);
-        acc[2] = fmaf(wk, x.z, acc[2]);
-        acc[3] = fmaf(wk, x.w, acc[3]);
-    }
-}
+// the tables the gemm and params kernels index at run time (aligned as the plain int arrays they were: the object code is unchanged)
+__constant__ __align__(16) Table<NL> L_IN = LAYOUT.in, L_OUT = LAYOUT.out, L_X = LAYOUT.x, L_S = LAYOUT.s, L_COL = LAYOUT.col;
+__constant__ __align__(16) Table<NL + 1> L_TILE0 = LAYOUT.tile0, L_W = LAYOUT.w;
 
 // the same, and beside it the tangent tan[r] = sum over k of W[k * ld + o] * us[k][r]: one weight read serves both
 __device__ __forceinline__ void dense_col2(const float* __restrict__ W, int ld, int K, int o, float init, const float* xs, const float* us,
@@ -94,10 +59,6 @@ __device__ __forceinline__ void dense_col2(const float* __restrict__ W, int ld, 
         tan[2] = fmaf(wk, u.z, tan[2]);
         tan[3] = fmaf(wk, u.w, tan[3]);
     }
-}
-
-__device__ __forceinline__ void put(float* xs, int o, const float v[R]) {
-    *reinterpret_cast<float4*>(xs + o * R) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
 struct Tangents {
@@ -168,15 +129,15 @@ __global__ __launch_bounds__(ROW_THREADS) void critic_wg_rows_kernel(CriticW w, 
         }
         s.kcs[m * R + r] = v;
         s.tk[m * R + r] = tv;
-        if (row < N) ws[(size_t)row * ROW_LD + X_KCS + m] = fmaf(s.g[r][0], v, tv);
+        if (row < N) ws[(size_t)row * ROW_LD + X_OF<L_KCS> + m] = fmaf(s.g[r][0], v, tv);
     }
     for (int i = t; i < NJF * R; i += ROW_THREADS) {
         const int r = i / NJF, k = i - r * NJF;
-        if (row0 + r < N) ws[(size_t)(row0 + r) * ROW_LD + X_JOINTS + k] = fmaf(s.g[r][0], s.J[k * R + r], s.tJ[k * R + r]);
+        if (row0 + r < N) ws[(size_t)(row0 + r) * ROW_LD + X_OF<L_JOINTS> + k] = fmaf(s.g[r][0], s.J[k * R + r], s.tJ[k * R + r]);
     }
     for (int i = t; i < NROT * R; i += ROW_THREADS) {
         const int r = i / NROT, k = i - r * NROT;
-        if (row0 + r < N) ws[(size_t)(row0 + r) * ROW_LD + X_R1 + k] = fmaf(s.g[r][2], s.rot[k * R + r], s.trot[k * R + r]);
+        if (row0 + r < N) ws[(size_t)(row0 + r) * ROW_LD + X_OF<L_R1> + k] = fmaf(s.g[r][2], s.rot[k * R + r], s.trot[k * R + r]);
     }
     if (t < R * 4) {  // grad_scores; the signal of the three one-output layers is 1
         const int r = t >> 2, k = t & 3;
@@ -185,7 +146,7 @@ __global__ __launch_bounds__(ROW_THREADS) void critic_wg_rows_kernel(CriticW w, 
             if (k < 3)
                 o[G_OFF + k] = s.g[r][k];
             else
-                o[S_COMB] = o[S_S3] = o[S_R3] = 1.f;
+                o[S_OF<L_COMB>] = o[S_OF<L_S3>] = o[S_OF<L_R3>] = 1.f;
         }
     }
     __syncthreads();
@@ -198,7 +159,7 @@ __global__ __launch_bounds__(ROW_THREADS) void critic_wg_rows_kernel(CriticW w, 
             sl1[r] = slope(acc[r]);
             acc[r] *= sl1[r];
             tan[r] *= sl1[r];
-            if (row0 + r < N) ws[(size_t)(row0 + r) * ROW_LD + X_R2 + t] = fmaf(s.g[r][2], acc[r], tan[r]);
+            if (row0 + r < N) ws[(size_t)(row0 + r) * ROW_LD + X_OF<L_R2> + t] = fmaf(s.g[r][2], acc[r], tan[r]);
         }
         put(s.r1, t, acc);
         put(s.u1, t, tan);
@@ -237,14 +198,14 @@ __global__ __launch_bounds__(ROW_THREADS) void critic_wg_rows_kernel(CriticW w, 
                 float v = 0.f;
 #pragma unroll
                 for (int j = 0; j < 5; ++j) v = fmaf(W2[k * 5 + j], b2[j], v);
-                o[X_S1 + k] = fmaf(g, s.beta[r][k], s.tbeta[r][k]);
-                o[X_S2 + k] = fmaf(g, z1[k] > 0.f ? z1[k] : 0.f, v1[k]);
-                o[S_S1 + k] = z1[k] > 0.f ? v : 0.f;
+                o[X_OF<L_S1> + k] = fmaf(g, s.beta[r][k], s.tbeta[r][k]);
+                o[X_OF<L_S2> + k] = fmaf(g, z1[k] > 0.f ? z1[k] : 0.f, v1[k]);
+                o[S_OF<L_S1> + k] = z1[k] > 0.f ? v : 0.f;
             }
 #pragma unroll
             for (int k = 0; k < 5; ++k) {
-                o[X_S3 + k] = fmaf(g, z2[k] > 0.f ? z2[k] : 0.f, v2[k]);
-                o[S_S2 + k] = b2[k];
+                o[X_OF<L_S3> + k] = fmaf(g, z2[k] > 0.f ? z2[k] : 0.f, v2[k]);
+                o[S_OF<L_S2> + k] = b2[k];
             }
         }
     }
@@ -259,15 +220,15 @@ __global__ __launch_bounds__(ROW_THREADS) void critic_wg_rows_kernel(CriticW w, 
             if (role == 0) {
                 dense_col2(w.w[L_R2], 100, 300, o, w.b[L_R2][o], s.r1, s.u1, acc, tan);
                 wn = w.w[L_R3][o];
-                col = 2, xo = X_R3 + o, so = S_R2 + o;
+                col = 2, xo = X_OF<L_R3> + o, so = S_OF<L_R2> + o;
             } else if (role == 1) {
                 dense_col2(w.w[L_KCS], 100, NKCS, o, w.b[L_KCS][o], s.kcs, s.tk, acc, tan);
                 wn = w.w[L_COMB][o];
-                col = 0, xo = X_COMB + o, so = S_KCS + o;
+                col = 0, xo = X_OF<L_COMB> + o, so = S_OF<L_KCS> + o;
             } else {
                 dense_col2(w.w[L_JOINTS], 100, NJF, o, w.b[L_JOINTS][o], s.J, s.tJ, acc, tan);
                 wn = w.w[L_COMB][100 + o];
-                col = 0, xo = X_COMB + 100 + o, so = S_JOINTS + o;
+                col = 0, xo = X_OF<L_COMB> + 100 + o, so = S_OF<L_JOINTS> + o;
             }
             float sig[R];
 #pragma unroll
@@ -289,7 +250,7 @@ __global__ __launch_bounds__(ROW_THREADS) void critic_wg_rows_kernel(CriticW w, 
         dense_col(w.wt[L_R2], 300, 100, t, 0.f, s.s2, acc);
 #pragma unroll
         for (int r = 0; r < R; ++r)
-            if (row0 + r < N) ws[(size_t)(row0 + r) * ROW_LD + S_R1 + t] = acc[r] * sl1[r];
+            if (row0 + r < N) ws[(size_t)(row0 + r) * ROW_LD + S_OF<L_R1> + t] = acc[r] * sl1[r];
     }
 }
 
@@ -426,9 +387,6 @@ hipError_t hpe_launch_critic_params(const CriticW& w, float* flat, bool set, hip
     return hipGetLastError();
 }
 
-int hpe_critic_flat_offset(int idx, bool bias) {
-    const CriticLayerSpec* s = hpe_critic_layers();
-    int off = 0;
-    for (int i = 0; i < idx; ++i) off += s[i].in * s[i].out + s[i].out;
-    return off + (bias ? s[idx].in * s[idx].out : 0);  // idx == HPE_NUM_CRITIC_DENSE, bias false: the total, CRITIC_PARAM_FLOATS
+int hpe_critic_flat_offset(int idx, bool bias) {  // idx == HPE_NUM_CRITIC_DENSE, bias false: the total, CRITIC_PARAM_FLOATS
+    return LAYOUT.w[idx] + (bias ? LAYOUT.in[idx] * LAYOUT.out[idx] : 0);
 }

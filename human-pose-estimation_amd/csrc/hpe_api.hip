@@ -434,26 +434,12 @@ int hpe_critic_layer_shape(int idx, int out[2]) {
 int hpe_load_critic(hpe_ctx* c, const HpeCriticModel* m) {
     if (!c || !m) return fail(HPE_ERR_INVALID, "null argument");
     if (c->dead) return fail(HPE_ERR_STATE, "hpe_finalize failed on this ctx: destroy it and create a new one");
-    const CriticLayerSpec* L = hpe_critic_layers();
-    size_t off_w[HPE_NUM_CRITIC_DENSE], off_t[HPE_NUM_CRITIC_DENSE], off_b[HPE_NUM_CRITIC_DENSE], total = 0;
-    for (int i = 0; i < HPE_NUM_CRITIC_DENSE; ++i) {
-        if (!m->kernel[i] || !m->bias[i]) return fail(HPE_ERR_INVALID, std::string("critic layer ") + L[i].name + ": null kernel or bias");
-        // every block starts on a 16-byte boundary
-        off_w[i] = total;
-        total += (size_t)round_up(L[i].in * L[i].out, 4);
-        off_t[i] = total;
-        total += (size_t)round_up(L[i].in * L[i].out, 4);
-        off_b[i] = total;
-        total += (size_t)round_up(L[i].out, 4);
-    }
-    std::vector<float> h(total, 0.f);
-    for (int i = 0; i < HPE_NUM_CRITIC_DENSE; ++i) {
-        const int in = L[i].in, out = L[i].out;
-        memcpy(&h[off_w[i]], m->kernel[i], sizeof(float) * in * out);
-        for (int k = 0; k < in; ++k)
-            for (int o = 0; o < out; ++o) h[off_t[i] + (size_t)o * in + k] = m->kernel[i][(size_t)k * out + o];
-        memcpy(&h[off_b[i]], m->bias[i], sizeof(float) * out);
-    }
+    for (int i = 0; i < HPE_NUM_CRITIC_DENSE; ++i)
+        if (!m->kernel[i] || !m->bias[i])
+            return fail(HPE_ERR_INVALID, std::string("critic layer ") + hpe_critic_layers()[i].name + ": null kernel or bias");
+    const size_t total = hpe_critic_live_floats();
+    std::vector<float> h(total);
+    hpe_critic_pack_live(*m, h.data());
     DeviceGuard g(c->cfg.device);
     HIP_TRY(hipDeviceSynchronize());  // a call still running may read the weights that are about to be replaced
     if (!c->critic_buf) {
@@ -462,19 +448,22 @@ int hpe_load_critic(hpe_ctx* c, const HpeCriticModel* m) {
         c->critic_buf = static_cast<float*>(q);
     }
     HIP_TRY(hipMemcpy(c->critic_buf, h.data(), total * sizeof(float), hipMemcpyHostToDevice));
-    for (int i = 0; i < HPE_NUM_CRITIC_DENSE; ++i) {
-        c->critic.w[i] = c->critic_buf + off_w[i];
-        c->critic.wt[i] = c->critic_buf + off_t[i];
-        c->critic.b[i] = c->critic_buf + off_b[i];
-    }
+    c->critic = hpe_critic_live_view(c->critic_buf);
     c->have_critic = true;
     return HPE_OK;
 }
 
-static int check_critic(hpe_ctx* c, const float* joints, int K, const float* betas, int betas_stride, const float* Rs, int N) {
+// what every critic entry point checks first; loaded: the call needs the weights
+static int check_critic_ctx(hpe_ctx* c, bool loaded) {
     if (!c) return fail(HPE_ERR_INVALID, "null ctx");
     if (c->dead) return fail(HPE_ERR_STATE, "hpe_finalize failed on this ctx: destroy it and create a new one");
-    if (!c->have_critic) return fail(HPE_ERR_STATE, "no critic loaded (hpe_load_critic)");
+    if (loaded && !c->have_critic) return fail(HPE_ERR_STATE, "no critic loaded (hpe_load_critic)");
+    return HPE_OK;
+}
+
+static int check_critic(hpe_ctx* c, const float* joints, int K, const float* betas, int betas_stride, const float* Rs, int N) {
+    int rc = check_critic_ctx(c, true);
+    if (rc) return rc;
     if (!joints || !betas || !Rs) return fail(HPE_ERR_INVALID, "null pointer");
     if (K < 14 || K > HPE_MAX_KP) return fail(HPE_ERR_INVALID, "joints must be [N,K,3] with 14 <= K <= " + std::to_string(HPE_MAX_KP));
     if (betas_stride < HPE_NUM_BETAS) return fail(HPE_ERR_INVALID, "betas_stride must be >= 10");
@@ -530,8 +519,8 @@ static int ensure_critic_ws(hpe_ctx* c, int N) {
 }
 
 int hpe_critic_reserve(hpe_ctx* c, int N) {
-    if (!c) return fail(HPE_ERR_INVALID, "null ctx");
-    if (c->dead) return fail(HPE_ERR_STATE, "hpe_finalize failed on this ctx: destroy it and create a new one");
+    int rc = check_critic_ctx(c, false);
+    if (rc) return rc;
     if (N < 1) return fail(HPE_ERR_INVALID, "N must be >= 1");
     DeviceGuard g(c->cfg.device);
     return ensure_critic_ws(c, N);
@@ -555,9 +544,8 @@ int hpe_critic_weight_grad(hpe_ctx* c, const float* joints, int K, const float* 
 }
 
 static int check_critic_params(hpe_ctx* c, const void* flat) {
-    if (!c) return fail(HPE_ERR_INVALID, "null ctx");
-    if (c->dead) return fail(HPE_ERR_STATE, "hpe_finalize failed on this ctx: destroy it and create a new one");
-    if (!c->have_critic) return fail(HPE_ERR_STATE, "no critic loaded (hpe_load_critic)");
+    int rc = check_critic_ctx(c, true);
+    if (rc) return rc;
     if (!flat) return fail(HPE_ERR_INVALID, "null flat_dev");
     return HPE_OK;
 }

@@ -103,7 +103,7 @@ struct hpe_ctx {
     float *padded = nullptr, *X0 = nullptr, *X1 = nullptr, *T1 = nullptr, *T2 = nullptr, *SC = nullptr;
     float *feat = nullptr, *P1 = nullptr, *H1 = nullptr, *H2 = nullptr, *thA = nullptr, *thB = nullptr;
     // device: critic (hpe_load_critic; valid before and after hpe_finalize, released with the rest of the device state)
-    float* critic_buf = nullptr;  // kernels | transposed kernels | biases of the nine Dense layers
+    float* critic_buf = nullptr;  // hpe_critic_live_floats() floats in the layout of hpe_critic_pack_live (critic.hip)
     CriticW critic{};
     bool have_critic = false;
     float* critic_ws = nullptr;  // hpe_critic_weight_grad's workspace (hpe_critic_wg_ws_floats), grown outside capture

@@ -224,6 +224,11 @@ struct CriticW {  // device pointers into the ctx's one critic buffer
     const float* wt[HPE_NUM_CRITIC_DENSE];  // its transpose [out][in], read by the backward
     const float* b[HPE_NUM_CRITIC_DENSE];   // bias [out]
 };
+// the ctx's one critic buffer (per layer kernel | transposed kernel | bias, 16-byte aligned blocks): its size, its host image built from
+// a model in the Keras layouts (host: hpe_critic_live_floats() floats, all written), and the pointers into a buffer of that layout
+size_t hpe_critic_live_floats();
+void hpe_critic_pack_live(const HpeCriticModel& m, float* host);
+CriticW hpe_critic_live_view(const float* buf);
 // joints [N][K][3] (the first 14 are read), betas: 10 floats per row, betas_stride floats apart, Rs [N][24][3][3] (the root is skipped);
 // scores [N][3], kcs [N][169] or nullptr.  One launch, no workspace.
 hipError_t hpe_launch_critic(const CriticW& w, const float* joints, int K, const float* betas, int betas_stride, const float* Rs, long N,
@@ -236,7 +241,7 @@ hipError_t hpe_launch_critic_backward(const CriticW& w, const float* joints, int
 
 // critic_train.hip: d F / d (critic weights) for F = sum_n [ sum_c grad_scores[n,c] scores[n,c] + <t_n, d(sum_c scores[n,c]) / dx_n> ],
 // as one flat buffer (kernel 0 [in][out], bias 0, kernel 1, ...), and the flat <-> live weights copies
-#define CRITIC_PARAM_FLOATS 114273  // sum over the nine layers of in * out + out
+#define CRITIC_PARAM_FLOATS 114273  // sum over the nine layers of in * out + out; these three are checked against the table in critic_common.h
 #define CRITIC_WG_ROW_FLOATS 1664   // workspace floats per row: left operands of the nine layers 1043 | signals 618 | grad_scores 3
 #define CRITIC_WG_CHUNK 64          // rows per partial sum
 int hpe_critic_wg_chunks(long N);

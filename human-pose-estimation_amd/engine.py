@@ -495,6 +495,16 @@ class HpeEngine(object):
         stride = betas.stride(0) if N > 1 else 10
         return joints, betas, Rs, N, joints.shape[1], stride
 
+    @staticmethod
+    def _grad_scores(grad_scores, N):
+        """-> grad_scores as a float32 CUDA tensor [N,3], or None"""
+        if grad_scores is None:
+            return None
+        gs = _require_cuda_tensor(grad_scores.detach(), "grad_scores", (3,))
+        if gs.shape[0] != N:
+            raise ValueError("grad_scores must be [N,3]")
+        return gs
+
     def critic(self, joints, betas, Rs, want_kcs=False):
         """hpe_critic: joints [N,K,3] (the first 14 are read), betas [N,10], Rs [N,24,3,3] (the root is skipped) -> scores [N,3]
         = (joints + KCS, shapes, rotations); want_kcs=True returns (scores, kcs [N,13,13]).  Any N."""
@@ -515,11 +525,7 @@ class HpeEngine(object):
             raise ValueError("want must name some of %s, got %r" % (sorted(shapes_of), tuple(want)))
         joints, betas, Rs, N, K, stride = self._critic_inputs(joints, betas, Rs)
         shapes_of["joints"] = (K, 3)
-        gs = None
-        if grad_scores is not None:
-            gs = _require_cuda_tensor(grad_scores.detach(), "grad_scores", (3,))
-            if gs.shape[0] != N:
-                raise ValueError("grad_scores must be [N,3]")
+        gs = self._grad_scores(grad_scores, N)
         out = {k: self._new(N, *shapes_of[k]) for k in want}
         ptr = [out[k].data_ptr() if k in out else None for k in ("joints", "betas", "Rs", "kcs")]
         _lib.check(self.lib.hpe_critic_backward(self._h, joints.data_ptr(), K, betas.data_ptr(), stride, Rs.data_ptr(), N,
@@ -538,11 +544,7 @@ class HpeEngine(object):
         either all of exactly that shape (one tangent shared by all rows: the reference's gradient penalty) or all with a leading N
         (one per row).  The result is a sum over the rows in a fixed order: same inputs, same bits."""
         joints, betas, Rs, N, K, stride = self._critic_inputs(joints, betas, Rs)
-        gs = None
-        if grad_scores is not None:
-            gs = _require_cuda_tensor(grad_scores.detach(), "grad_scores", (3,))
-            if gs.shape[0] != N:
-                raise ValueError("grad_scores must be [N,3]")
+        gs = self._grad_scores(grad_scores, N)
         tangents = {k: v for k, v in (tangents or {}).items() if v is not None}
         unknown = [k for k in tangents if k not in self._TANGENT_SHAPES]
         if unknown:
