@@ -4,7 +4,8 @@ Host side mirrors the reference's interface for this path: ``Predictor`` (src/pr
 (src/tf_smpl/batch_smpl.py), ``batch_orth_proj_idrot`` / ``reproject_vertices`` (src/tf_smpl/projection.py),
 ``kp_reprojection_loss`` / ``mesh_reprojection_loss`` (src/ops.py), ``critic_scores`` /
 ``generator_critic_loss`` (CriticNetwork + get_kcs, src/models.py:97-202), ``critic_wgan_loss`` / ``CriticTrainer`` (the critic
-update, src/trainer.py:508-583).  All arithmetic runs in the C-ABI
+update, src/trainer.py:508-583), ``regressor_thetas`` / ``GeneratorTrainer`` (the generator update after the encoder,
+src/trainer.py:383-505).  All arithmetic runs in the C-ABI
 library ``lib/libhpe_hip.so`` (include/hpe.h); there is no CPU fallback.
 """
 import os as _os
@@ -17,13 +18,14 @@ try:
 except ValueError:
     _os.environ["GPU_MAX_HW_QUEUES"] = "8"
 
-from . import resnet_spec, synthetic  # noqa: F401,E402
+from . import critic_spec, regressor_spec, resnet_spec, synthetic  # noqa: F401,E402
 from ._lib import HpeError  # noqa: F401
 from .critic_train import CriticTrainer  # noqa: F401
 from .engine import HpeEngine  # noqa: F401
+from .generator_train import GeneratorTrainer  # noqa: F401
 from .fit import fit_keypoints, fit_reprojection  # noqa: F401
 from .image import get_original, preprocess_batch, preprocess_image  # noqa: F401
-from .ops import critic_gradient_penalty, critic_scores, critic_wgan_loss, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss  # noqa: F401
+from .ops import critic_gradient_penalty, critic_scores, critic_wgan_loss, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas  # noqa: F401
 from .predictor import Predictor  # noqa: F401
 from .projection import batch_orth_proj_idrot, reproject_vertices  # noqa: F401
 from .render import SMPLRenderer  # noqa: F401

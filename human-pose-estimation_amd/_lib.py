@@ -140,6 +140,12 @@ _PROTOS = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_critic_get_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_critic_set_params_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_regressor_param_floats": (C.c_int, []),
+    "hpe_regressor_param_offset": (C.c_int, [C.c_int, C.c_int]),
+    "hpe_regressor_get_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_regressor_set_params_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_regressor_forward_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_regressor_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_device_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hpe_debug_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

@@ -1,5 +1,5 @@
 """torch.autograd glue of the HIP backward (include/hpe.h: hpe_smpl_backward, hpe_kp_loss_backward, hpe_mesh_loss_grad,
-hpe_critic_backward).  Used only when an input requires grad: ``HpeEngine.smpl`` / ``SMPL.__call__`` / ``kp_reprojection_loss`` /
+hpe_critic_backward, hpe_regressor_backward).  Used only when an input requires grad: ``HpeEngine.smpl`` / ``SMPL.__call__`` / ``kp_reprojection_loss`` /
 ``mesh_reprojection_loss`` / ``critic_scores`` keep their plain forward-only path otherwise.
 Nothing numerical happens here -- forward and backward are one library call each."""
 from __future__ import annotations
@@ -81,3 +81,22 @@ class CriticFunction(torch.autograd.Function):
         want = tuple(k for k, need in zip(names, ctx.needs_input_grad[1:]) if need)
         g = ctx.engine.critic_backward(joints, betas, Rs, grad_scores.to(torch.float32).contiguous(), want=want)
         return (None,) + tuple(g.get(k) for k in names)
+
+
+class RegressorFunction(torch.autograd.Function):
+    """thetas [S,B,85] = hpe_regressor_forward_train(features; the engine's live regressor), differentiable in ``params`` -- the flat
+    tensor the optimiser owns, which must EQUAL what the engine holds: it carries ``.grad``, the arithmetic reads the engine's weights
+    -- and in ``features`` (hpe_regressor_backward; stateless, so only the inputs are saved)."""
+
+    @staticmethod
+    def forward(ctx, engine, features, params, drop):
+        ctx.engine = engine
+        ctx.save_for_backward(features.detach(), drop.detach() if drop is not None else None)
+        return engine.regressor_forward_train(features, drop)
+
+    @staticmethod
+    def backward(ctx, grad_thetas):
+        features, drop = ctx.saved_tensors
+        gflat, gfeat = ctx.engine.regressor_backward(features, grad_thetas.to(torch.float32).contiguous(), drop,
+                                                     want_grad_features=ctx.needs_input_grad[1])
+        return None, gfeat, gflat if ctx.needs_input_grad[2] else None, None

@@ -566,6 +566,60 @@ int hpe_critic_set_params_dev(hpe_ctx* c, const float* flat, void* stream) {
     return HPE_OK;
 }
 
+int hpe_regressor_param_floats(void) { return regressor_param_offset(4, false); }
+
+int hpe_regressor_param_offset(int idx, int is_bias) {
+    if (idx < 0 || idx > 3 || (idx == 3 && is_bias)) return -1;
+    return regressor_param_offset(idx, is_bias != 0);
+}
+
+static int check_regressor_params(hpe_ctx* c, const void* flat) {
+    if (!c) return fail(HPE_ERR_INVALID, "null ctx");
+    if (c->dead) return fail(HPE_ERR_STATE, "hpe_finalize failed on this ctx: destroy it and create a new one");
+    if (!c->finalized) return fail(HPE_ERR_STATE, "hpe_finalize() has not been called");
+    if (!c->have_regressor) return fail(HPE_ERR_STATE, "regressor weights / mean theta were not loaded");
+    if (!flat) return fail(HPE_ERR_INVALID, "null flat_dev");
+    return HPE_OK;
+}
+
+int hpe_regressor_get_params(hpe_ctx* c, float* flat, void* stream) {
+    int rc = check_regressor_params(c, flat);
+    if (rc) return rc;
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(regressor_params_copy(c, flat, false, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+int hpe_regressor_set_params_dev(hpe_ctx* c, const float* flat, void* stream) {
+    int rc = check_regressor_params(c, flat);
+    if (rc) return rc;
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(regressor_params_copy(c, const_cast<float*>(flat), true, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+int hpe_regressor_forward_train(hpe_ctx* c, const float* features, int B, const float* drop, float* thetas, void* stream) {
+    int rc = check_ready(c, B, NEED_REG);
+    if (rc) return rc;
+    if (!features || !thetas) return fail(HPE_ERR_INVALID, "null pointer");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(regressor_train_forward(c, features, B, drop, st));
+    // rows [S * B] of pitch THETA_LD, stage-major, behind the tiled mean
+    HIP_TRY(hpe_launch_copy_theta(c->rt.th + (size_t)B * THETA_LD, THETA_LD, thetas, HPE_THETA_DIM, c->cfg.num_stage * B, HPE_THETA_DIM, st));
+    return HPE_OK;
+}
+
+int hpe_regressor_backward(hpe_ctx* c, const float* features, int B, const float* drop, const float* grad_thetas, float* grad_flat,
+                           float* grad_features, void* stream) {
+    int rc = check_ready(c, B, NEED_REG);
+    if (rc) return rc;
+    if (!features || !grad_flat) return fail(HPE_ERR_INVALID, "null pointer");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(regressor_train_backward(c, features, B, drop, grad_thetas, grad_flat, grad_features, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
 int hpe_debug_conv(hpe_ctx* c, int idx, const float* x, int B, const float* residual, int relu, float* y, void* stream) {
     int rc = check_ready(c, B, NEED_ENC);
     if (rc) return rc;

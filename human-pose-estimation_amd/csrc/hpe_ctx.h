@@ -76,6 +76,27 @@ constexpr size_t WINO_V_PITCH = 802816 + 16384;
 constexpr size_t WINO_V_SLACK = 524288;
 
 
+// Regressor training (regressor_train.hip).  The backward multiplies by the transposed kernels, and for the dense GEMM's Wt[n][k] operand
+// the transpose of a packed weight is the Keras [in][out] matrix itself: w1k / w2k / w3k hold it (pack_regressor and
+// hpe_regressor_set_params_dev write them beside the packed copies).  Everything else is workspace for max_batch rows and num_stage stages
+// that no other entry point touches.
+struct RegTrainWork {
+    float *w1k = nullptr;  // [2048 + 128][1024]: dense_0/kernel, rows 2133.. zero (the theta block is an 85-row operand padded to two 64-row tiles)
+    float *w2k = nullptr;  // [1024][1024]
+    float *w3k = nullptr;  // [1024][THETA_LD]: dense_2/kernel, columns 85.. zero
+    float *p1 = nullptr;   // [B][1024] features . W1[:2048]
+    float *a1 = nullptr, *a2 = nullptr;    // [S][B][1024] hidden activations (after dropout)
+    float *th = nullptr;   // [S + 1][B][THETA_LD]: tiled mean, then theta of every stage
+    float *g = nullptr;    // [S + 1][B][THETA_LD]: cotangent reaching theta_{i-1} at index i (index 0: the tiled mean's)
+    float *r = nullptr;    // [B][THETA_LD] residual operand of the theta GEMM
+    float *da = nullptr;   // [B][1024] ungated data gradient
+    float *dz1 = nullptr, *dz2 = nullptr;  // [S][B][1024]
+    float *sum1 = nullptr; // [B][1024] sum over the stages of dz1
+    float *zeros = nullptr;    // 2048 zeros (shift of the bias-free GEMMs)
+    float *partial = nullptr;  // split-K workspace of its Dense launches
+    size_t partial_floats = 0;
+};
+
 struct hpe_ctx {
     HpeConfig cfg{};
     bool finalized = false;
@@ -94,6 +115,7 @@ struct hpe_ctx {
     // device: regressor
     float *w1f = nullptr, *w1t = nullptr, *w2 = nullptr, *w3 = nullptr, *b1 = nullptr, *b2 = nullptr, *b3 = nullptr;
     float *ones = nullptr, *zeros = nullptr, *mean_dev = nullptr;
+    RegTrainWork rt{};  // regressor training (regressor_train.hip): Keras-major weight copies and a workspace of its own
     // device: SMPL
     SmplDev smpl{};
     SmplWork work{};
@@ -187,7 +209,17 @@ hipError_t run_conv(hpe_ctx* c, int idx, const float* x, int B, const float* res
 hipError_t run_chain(hpe_ctx* c, int i2c, bool first, const float* t2, const float* res, int B, float* t3, float* u1, hipStream_t st,
                      bool u1_slab8 = false);
 hipError_t encoder_impl(hpe_ctx* c, const float* images, int B, float* features, int ldfeat, hipStream_t st);
+// partial == nullptr: the ctx's split-K workspace (the tail's own while a tail is being enqueued)
+hipError_t run_dense(hpe_ctx* c, const float* x, int lda, int M, int K, const float* w, int w_rows, int N, const float* scale, const float* shift,
+                     const float* res, int ldres, int relu, float* y, int ldy, hipStream_t st, float* partial = nullptr, size_t partial_floats = 0);
 hipError_t regress_impl(hpe_ctx* c, const float* th_prev, float* th_next, int B, hipStream_t st);
 hipError_t features_proj(hpe_ctx* c, const float* features, int B, hipStream_t st);
 hipError_t tail_impl(hpe_ctx* c, const float* feat, int B, const HpeOutputs* stage_outs, int n_outs, hipStream_t ts, hipEvent_t feat_free);
 int forward_impl(hpe_ctx* c, const float* images, int B, const HpeOutputs* stage_outs, int n_outs, hipStream_t st, bool pipelined);
+
+// regressor_train.hip
+int regressor_param_offset(int idx, bool bias);  // idx 3: mean theta; idx 4 (bias false): the total
+hipError_t regressor_train_forward(hpe_ctx* c, const float* features, int B, const float* drop, hipStream_t st);  // fills rt.a1 / a2 / th
+hipError_t regressor_train_backward(hpe_ctx* c, const float* features, int B, const float* drop, const float* grad_thetas, float* grad_flat,
+                                    float* grad_features, hipStream_t st);
+hipError_t regressor_params_copy(hpe_ctx* c, float* flat, bool set, hipStream_t st);

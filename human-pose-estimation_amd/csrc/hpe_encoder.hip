@@ -212,16 +212,17 @@ hipError_t run_chain(hpe_ctx* c, int i2c, bool first, const float* t2, const flo
     return hpe_launch_chain_bf16(p, s2.cin, s2.cout, sn.cout, first ? specs()[i2c + 1].cin : 0, st);
 }
 
-static hipError_t run_dense(hpe_ctx* c, const float* x, int lda, int M, int K, const float* w, int w_rows, int N, const float* scale,
-                     const float* shift, const float* res, int ldres, int relu, float* y, int ldy, hipStream_t st) {
+hipError_t run_dense(hpe_ctx* c, const float* x, int lda, int M, int K, const float* w, int w_rows, int N, const float* scale,
+                     const float* shift, const float* res, int ldres, int relu, float* y, int ldy, hipStream_t st, float* partial,
+                     size_t partial_floats) {
     // single frames and very small batches: one launch per layer (the implicit-GEMM kernel would need split-K + a fix-up launch)
     if (M <= 4) return hpe_launch_dense_gemv(x, lda, M, K, w, N, scale, shift, res, ldres, relu, y, ldy, st);
     GemmArgs p{};
     p.zero = shift;  // any readable 16 B: dense mode never takes the zero-page path
     // the Dense layers run after the chunk streams have joined; in the pipelined forward they overlap the NEXT batch's encoder,
     // whose unchunked launches may split K too -> separate workspace
-    p.partial = c->dense_on_tail ? c->partial_tail : c->partial;
-    p.partial_floats = c->dense_on_tail ? c->partial_tail_floats : c->partial_floats;
+    p.partial = partial ? partial : c->dense_on_tail ? c->partial_tail : c->partial;
+    p.partial_floats = partial ? partial_floats : c->dense_on_tail ? c->partial_tail_floats : c->partial_floats;
     p.x = x;
     p.w = w;
     p.scale = scale;

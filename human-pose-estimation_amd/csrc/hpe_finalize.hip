@@ -2,6 +2,7 @@
 // selects, workspace sizing, streams and events.  Host logic only.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -125,6 +126,7 @@ int hpe_load_mean_theta(hpe_ctx* c, const float* mean85) {
 void release_device_state(hpe_ctx* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     c->allocs.clear();
+    c->rt = RegTrainWork{};
     if (c->critic_buf) {
         (void)hipFree(c->critic_buf);
         c->critic_buf = nullptr;
@@ -396,6 +398,14 @@ static int pack_regressor(hpe_ctx* c) {
     for (int n = 0; n < HPE_THETA_DIM; ++n) b3[n] = c->dense[2].bias[n];
     if ((rc = upload(c, &c->b3, b3))) return rc;
     if ((rc = upload(c, &c->mean_dev, std::vector<float>(c->h_mean, c->h_mean + HPE_THETA_DIM)))) return rc;
+    // the Keras [in][out] matrices as the backward's Wt[n][k] operands (hpe_ctx.h: RegTrainWork), zero padded
+    std::vector<float> w1k((size_t)(2048 + 128) * 1024, 0.f), w3k((size_t)1024 * THETA_LD, 0.f);
+    std::copy(k1.begin(), k1.end(), w1k.begin());
+    for (int k = 0; k < 1024; ++k)
+        for (int n = 0; n < HPE_THETA_DIM; ++n) w3k[(size_t)k * THETA_LD + n] = k3[(size_t)k * HPE_THETA_DIM + n];
+    if ((rc = upload(c, &c->rt.w1k, w1k))) return rc;
+    if ((rc = upload(c, &c->rt.w2k, k2))) return rc;
+    if ((rc = upload(c, &c->rt.w3k, w3k))) return rc;
     return HPE_OK;
 }
 
@@ -500,6 +510,22 @@ static int size_workspaces(hpe_ctx* c) {
         if ((rc = dev_alloc(c, &c->H2, B * 1024, true))) return rc;
         if ((rc = dev_alloc(c, &c->thA, B * THETA_LD, true))) return rc;
         if ((rc = dev_alloc(c, &c->thB, B * THETA_LD, true))) return rc;
+        // hpe_regressor_forward_train / hpe_regressor_backward: their own workspace, split-K slices included
+        const size_t S = (size_t)c->cfg.num_stage;
+        RegTrainWork& t = c->rt;
+        if ((rc = dev_alloc(c, &t.p1, B * 1024, true))) return rc;
+        if ((rc = dev_alloc(c, &t.a1, S * B * 1024, true))) return rc;
+        if ((rc = dev_alloc(c, &t.a2, S * B * 1024, true))) return rc;
+        if ((rc = dev_alloc(c, &t.th, (S + 1) * B * THETA_LD, true))) return rc;
+        if ((rc = dev_alloc(c, &t.g, (S + 1) * B * THETA_LD, true))) return rc;
+        if ((rc = dev_alloc(c, &t.r, B * THETA_LD, true))) return rc;
+        if ((rc = dev_alloc(c, &t.da, B * 1024, true))) return rc;
+        if ((rc = dev_alloc(c, &t.dz1, S * B * 1024, true))) return rc;
+        if ((rc = dev_alloc(c, &t.dz2, S * B * 1024, true))) return rc;
+        if ((rc = dev_alloc(c, &t.sum1, B * 1024, true))) return rc;
+        if ((rc = dev_alloc(c, &t.zeros, 2048, true))) return rc;
+        t.partial_floats = c->partial_tail_floats;
+        if ((rc = dev_alloc(c, &t.partial, t.partial_floats, false))) return rc;
     }
     if (c->have_smpl) {
         if ((rc = dev_alloc(c, &c->work.pfT, 207 * Bpad, true))) return rc;

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _lib
 from .critic_spec import PARAM_FLOATS
+from .regressor_spec import PARAM_FLOATS as REGRESSOR_PARAM_FLOATS
 from .resnet_spec import CONV_SPECS
 
 NUM_VERTS = _lib.NUM_VERTS
@@ -590,6 +591,59 @@ class HpeEngine(object):
         if tuple(flat.shape) != (PARAM_FLOATS,):
             raise ValueError("flat must be [%d], got %s" % (PARAM_FLOATS, tuple(flat.shape)))
         _lib.check(self.lib.hpe_critic_set_params_dev(self._h, flat.data_ptr(), self._stream()))
+
+    # ------------------------------------------------------------------ regressor training
+    def regressor_params(self):
+        """hpe_regressor_get_params: the live regressor (three Dense layers + mean theta) as one flat CUDA tensor
+        [regressor_spec.PARAM_FLOATS] (a copy)"""
+        out = self._new(REGRESSOR_PARAM_FLOATS)
+        _lib.check(self.lib.hpe_regressor_get_params(self._h, out.data_ptr(), self._stream()))
+        return out
+
+    def set_regressor_params(self, flat):
+        """hpe_regressor_set_params_dev: replace the live regressor and mean theta by ``flat`` on the device, in stream order, without
+        a host round trip (``regressor_spec.flat_to_params`` turns a flat tensor back into its dict)"""
+        flat = _require_cuda_tensor(flat.detach(), "flat")
+        if tuple(flat.shape) != (REGRESSOR_PARAM_FLOATS,):
+            raise ValueError("flat must be [%d], got %s" % (REGRESSOR_PARAM_FLOATS, tuple(flat.shape)))
+        _lib.check(self.lib.hpe_regressor_set_params_dev(self._h, flat.data_ptr(), self._stream()))
+
+    def _drop(self, drop, B):
+        if drop is None:
+            return None
+        drop = _require_cuda_tensor(drop.detach(), "drop")
+        if tuple(drop.shape) != (2, B, 1024):
+            raise ValueError("drop must be [2,%d,1024] (the multipliers of the two hidden layers at the last stage), got %s" % (B, tuple(drop.shape)))
+        return drop
+
+    def regressor_forward_train(self, features, drop=None):
+        """hpe_regressor_forward_train: features [B,2048] -> thetas [num_stage,B,85], the IEF loop with the dropout multipliers
+        ``drop`` [2,B,1024] (0 or 1 / keep) on the two hidden layers of the LAST stage; None: no dropout, the bits of ``tail``."""
+        features = _require_cuda_tensor(features.detach(), "features", (2048,))
+        B = features.shape[0]
+        drop = self._drop(drop, B)
+        out = self._new(self.num_stage, B, 85)
+        _lib.check(self.lib.hpe_regressor_forward_train(self._h, features.data_ptr(), B, drop.data_ptr() if drop is not None else None,
+                                                        out.data_ptr(), self._stream()))
+        return out
+
+    def regressor_backward(self, features, grad_thetas, drop=None, want_grad_features=True):
+        """hpe_regressor_backward: the gradient of sum(grad_thetas * thetas) (grad_thetas [num_stage,B,85]; None = zeros) with respect
+        to the flat parameters -> (grad_flat [regressor_spec.PARAM_FLOATS], grad_features [B,2048] or None).  Stateless: the forward
+        is recomputed, pass the same ``drop``.  Same inputs, same bits."""
+        features = _require_cuda_tensor(features.detach(), "features", (2048,))
+        B = features.shape[0]
+        drop = self._drop(drop, B)
+        if grad_thetas is not None:
+            grad_thetas = _require_cuda_tensor(grad_thetas.detach(), "grad_thetas")
+            if tuple(grad_thetas.shape) != (self.num_stage, B, 85):
+                raise ValueError("grad_thetas must be [%d,%d,85], got %s" % (self.num_stage, B, tuple(grad_thetas.shape)))
+        gflat = self._new(REGRESSOR_PARAM_FLOATS)
+        gfeat = self._new(B, 2048) if want_grad_features else None
+        _lib.check(self.lib.hpe_regressor_backward(self._h, features.data_ptr(), B, drop.data_ptr() if drop is not None else None,
+                                                   grad_thetas.data_ptr() if grad_thetas is not None else None, gflat.data_ptr(),
+                                                   gfeat.data_ptr() if want_grad_features else None, self._stream()))
+        return gflat, gfeat
 
     def mesh_loss(self, seg, verts2d):
         torch = _torch()

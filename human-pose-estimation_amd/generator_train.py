@@ -1,0 +1,98 @@
+"""GeneratorTrainer: the generator half of the reference's Trainer.train_step (src/trainer.py:383-505) after the encoder -- the IEF loop
+with dropout at the last stage, SMPL, the keypoint / mesh reprojection losses and the critic term on the last stage, their gradient with
+respect to the RegressionNetwork and mean theta (hpe_smpl_backward, hpe_kp_loss_backward, hpe_mesh_loss_grad, hpe_critic_backward,
+hpe_regressor_backward), an Adam step and the new weights back into the engine on the device (hpe_regressor_set_params_dev).  Adam is
+torch.optim.Adam on ONE flat tensor; everything else runs in libhpe_hip.so.  The encoder is not trained here: ``grad_features`` is
+returned for a caller who carries on into it."""
+from __future__ import annotations
+
+from .ops import generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas
+
+GENERATOR_LR = 0.0001  # the reference's generator_lr (src/config.py:64-69)
+ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon
+
+
+class GeneratorTrainer(object):
+    def __init__(self, engine, lr=GENERATOR_LR, betas=(0.9, 0.999), eps=ADAM_EPS, kpr_loss_weight=60.0, mr_loss_weight=0.001,
+                 critic_loss_weight=0.01, dropout=0.5, generator=None):
+        """engine: a finalized HpeEngine with a regressor, mean theta and SMPL (and a critic, for the critic term).  ``params`` is the
+        flat parameter tensor (regressor_spec.flat_layout) the optimiser owns; ``regressor_spec.flat_to_params(params)`` gives the
+        dict ``load_regressor`` / ``load_mean_theta`` take.  generator: the torch.Generator of the dropout draws."""
+        import torch
+
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("dropout must be in [0, 1)")
+        self.engine = engine
+        self.kpr_loss_weight, self.mr_loss_weight, self.critic_loss_weight = float(kpr_loss_weight), float(mr_loss_weight), float(critic_loss_weight)
+        self.dropout = float(dropout)
+        self.generator = generator
+        self.params = engine.regressor_params().requires_grad_(True)
+        self.optimizer = torch.optim.Adam([self.params], lr=lr, betas=betas, eps=eps)
+
+    def draw_masks(self, B):
+        """the dropout multipliers [2,B,1024] of one step: 0 with probability ``dropout``, else 1 / (1 - dropout); None without dropout"""
+        import torch
+
+        if self.dropout == 0.0:
+            return None
+        u = torch.rand((2, B, 1024), generator=self.generator, device=self.engine.tdev, dtype=torch.float32)
+        return (u >= self.dropout).to(torch.float32) * (1.0 / (1.0 - self.dropout))
+
+    def _smpl(self, theta, want):
+        """engine.smpl in chunks of max_batch rows (with gradient where theta carries one)"""
+        import torch
+
+        mb = self.engine.max_batch
+        if theta.shape[0] <= mb:
+            return self.engine.smpl(theta, want=want)
+        parts = [self.engine.smpl(theta[lo : lo + mb], want=want) for lo in range(0, theta.shape[0], mb)]
+        return {k: torch.cat([p[k] for p in parts]) for k in want}
+
+    def step(self, images_or_features, kp_gt, seg_gts=None, use_critic=None, drop="draw"):
+        """One generator update.  images_or_features: images [B,224,224,3] (the encoder runs without gradient) or features [B,2048];
+        kp_gt [B,K,3] (x, y, visibility); seg_gts [B,H,W(,1)] adds the mesh reprojection loss; use_critic (default: the engine has a
+        critic) adds the critic term.  drop: the multipliers [2,B,1024] of this step, None for none, "draw" to draw them.
+        -> the reference's result keys: kpr_losses, mr_losses, generator_critic_losses (lists over the stages, already weighted, 0-dim
+        device tensors; the LAST stage's terms are what is minimised, src/trainer.py:487-496), pred_keypoints, generated_cams (last
+        stage), thetas (list over the stages: what CriticTrainer.step_from_thetas takes), and grad_features [B,2048].  Nothing reads
+        the device."""
+        import torch
+
+        eng = self.engine
+        x = images_or_features
+        if use_critic is None:
+            use_critic = eng.has_critic
+        with torch.no_grad():
+            features = x if x.dim() == 2 else torch.cat([eng.encoder(x[lo : lo + eng.max_batch]) for lo in range(0, x.shape[0], eng.max_batch)])
+        B = features.shape[0]
+        if isinstance(drop, str):
+            drop = self.draw_masks(B)
+        features = features.detach().clone().requires_grad_(True)
+        thetas = regressor_thetas(eng, features, self.params, drop)
+        S = thetas.shape[0]
+        kpr, mr, gc = [], [], []
+        # kp2d / verts2d: batch_orth_proj_idrot / reproject_vertices of the stage, as outputs of the one hpe_smpl call (and of its backward)
+        want = ("kp2d", "joints", "Rs") + (("verts2d",) if seg_gts is not None else ())
+        loss = pred_kp = None
+        for i in range(S):
+            last = i == S - 1
+            with torch.set_grad_enabled(last):
+                th = thetas[i] if last else thetas[i].detach()
+                o = self._smpl(th, want)
+                kp = o["kp2d"]
+                kpr.append(self.kpr_loss_weight * kp_reprojection_loss(kp_gt, kp))
+                if seg_gts is not None:
+                    mr.append(self.mr_loss_weight * mesh_reprojection_loss(eng, seg_gts, o["verts2d"]))
+                if use_critic:
+                    gc.append(self.critic_loss_weight * generator_critic_loss(eng, o["joints"], th[:, 75:], o["Rs"]))
+                if last:
+                    pred_kp = kp.detach()
+                    loss = kpr[-1] + (mr[-1] if mr else 0.0) + (gc[-1] if gc else 0.0)
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        self.optimizer.step()
+        eng.set_regressor_params(self.params)
+        det = lambda ts: [t.detach() for t in ts]  # noqa: E731
+        return {"kpr_losses": det(kpr), "mr_losses": det(mr), "generator_critic_losses": det(gc), "pred_keypoints": pred_kp,
+                "generated_cams": thetas[S - 1, :, :3].detach(), "thetas": [thetas[i].detach() for i in range(S)],
+                "grad_features": features.grad}

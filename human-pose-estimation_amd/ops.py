@@ -61,6 +61,20 @@ def generator_critic_loss(engine, joints, shapes, Rs, return_parts=False):
     return -scores.mean(0).sum()
 
 
+def regressor_thetas(engine, features, params, drop=None):
+    """The IEF loop of the generator step (src/trainer.py:389-401) on the engine's live regressor: features [B,2048] -> thetas
+    [num_stage,B,85], with ``drop`` [2,B,1024] the dropout multipliers of the last stage (None: none).  ``params`` is the flat
+    parameter tensor the optimiser owns (``engine.regressor_params()`` layout); it must equal what the engine holds -- it is the
+    carrier of ``.grad``, not a second copy of the arithmetic.  The result has a ``grad_fn``: its backward is ONE
+    hpe_regressor_backward call that fills ``params.grad`` and, if ``features`` requires grad, ``features.grad``."""
+    from .autograd import RegressorFunction
+    from .regressor_spec import PARAM_FLOATS
+
+    if tuple(params.shape) != (PARAM_FLOATS,):
+        raise ValueError("params must be the flat tensor [%d], got %s" % (PARAM_FLOATS, tuple(params.shape)))
+    return RegressorFunction.apply(engine, features, params, drop)
+
+
 _PENALTY_ORDER = ("kcs", "joints", "betas", "Rs")  # tf.gradients(out_interpolated, [kcs, joints, shapes, Rs]) (src/trainer.py:566-570)
 
 

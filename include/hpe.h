@@ -313,6 +313,41 @@ int hpe_critic_weight_grad(hpe_ctx* ctx, const float* joints_dev, int K, const f
 int hpe_critic_get_params(hpe_ctx* ctx, float* flat_dev, void* stream);
 int hpe_critic_set_params_dev(hpe_ctx* ctx, const float* flat_dev, void* stream);
 
+/* -- regressor training: the generator update's missing leg (src/trainer.py:383-505) -------------------------------------------
+ * The RegressionNetwork (three Dense layers, src/models.py:60-74) and mean theta as ONE flat fp32 buffer of
+ * hpe_regressor_param_floats() = 3,322,026 floats: dense_0/kernel [2133,1024], dense_0/bias, dense_1/kernel [1024,1024], dense_1/bias,
+ * dense_2/kernel [1024,85], dense_2/bias, then the 85 floats of mean theta.  hpe_regressor_param_offset(idx, is_bias): the first float
+ * of layer idx's kernel (is_bias 0) or bias; idx 3, is_bias 0: mean theta; -1 otherwise.  Host code: no device is needed. */
+int hpe_regressor_param_floats(void);
+int hpe_regressor_param_offset(int idx, int is_bias);
+/* The live regressor <-> the flat layout, on the device.  hpe_regressor_set_params_dev rewrites every buffer hpe_finalize packed from
+ * hpe_load_dense / hpe_load_mean_theta (the transposed kernels with their padding, biases, mean theta) and the [in][out] copies the
+ * backward reads: afterwards hpe_tail / hpe_regress_stage give the bits of a ctx that loaded the same values.  Four launches (get: one),
+ * no host round trip, no synchronisation, capturable; calls on `stream` see the new weights in stream order, calls on other streams
+ * (a pipelined tail, too) must be ordered by the caller.  HPE_ERR_STATE before hpe_finalize or without a loaded regressor. */
+int hpe_regressor_get_params(hpe_ctx* ctx, float* flat_dev, void* stream);
+int hpe_regressor_set_params_dev(hpe_ctx* ctx, const float* flat_dev, void* stream);
+/* The IEF loop of the generator step: for i = 0 .. num_stage - 1, x = [features | theta_{i-1}] (theta_{-1} = the tiled mean),
+ * a1 = drop1 * relu(x W1 + b1), a2 = drop2 * relu(a1 W2 + b2), theta_i = theta_{i-1} + a2 W3 + b3; thetas_dev [num_stage][B][85].
+ * drop_dev: float [2][B][1024] multipliers (>= 0; Keras dropout at rate 0.5: 0 or 2) applied at the LAST stage only, as the reference
+ * passes training=True there only (src/trainer.py:395-398); NULL: no dropout, and then every theta row has the bits hpe_regress_stage /
+ * hpe_tail compute (the same launches).  1 <= B <= max_batch.  The masks are an input: nothing here draws random numbers. */
+int hpe_regressor_forward_train(hpe_ctx* ctx, const float* features_dev, int B, const float* drop_dev, float* thetas_dev, void* stream);
+/* Gradient of  sum_i < grad_thetas[i], theta_i >  of that loop with respect to the flat parameters (grad_flat_dev
+ * [hpe_regressor_param_floats()], overwritten) and, if grad_features_dev is not NULL, to the features ([B,2048], overwritten).  The
+ * cotangent of stage i reaches every earlier stage through theta_{i-1}; every stage adds to the same six tensors and to mean theta.
+ * grad_thetas_dev [num_stage][B][85]; NULL = all zero (a stage without a loss term is passed as zeros).  drop_dev as in the forward:
+ * pass the same masks.  ReLU's gradient is taken as 0 at 0 (TensorFlow's).
+ * Stateless: the forward is recomputed into a workspace of the ctx's own (sized by hpe_finalize for max_batch), so no forward call has
+ * to precede it.  About 30 launches on `stream`; no allocation, no synchronisation, capturable; no atomics and a fixed summation order:
+ * the same inputs give the same bits.  The result is a sum over rows, so it depends on B and on the order of the rows.
+ * Concurrency: the two training calls share that one workspace, so they must not overlap each other or hpe_regressor_set_params_dev
+ * on the same ctx; they read the weights only and share no buffer (no split-K slices either) with hpe_encoder, hpe_forward*, hpe_tail,
+ * hpe_regress_stage, hpe_smpl* or the loss and critic calls, so they may run next to any of those on another stream.
+ * HPE_ERR_INVALID for B outside [1, max_batch] or NULL features / grad_flat; HPE_ERR_STATE before hpe_finalize. */
+int hpe_regressor_backward(hpe_ctx* ctx, const float* features_dev, int B, const float* drop_dev, const float* grad_thetas_dev,
+                           float* grad_flat_dev, float* grad_features_dev, void* stream);
+
 /* Both reprojection losses of all n_stage IEF stages in ONE call -- what Trainer.val_step evaluates per step
  * (src/trainer.py:274-296): the work that depends only on seg_gts (tf.where compaction, src/trainer.py:291;
  * the silhouette bitmap) is done once per call instead of once per stage.
