@@ -20,6 +20,7 @@ except ValueError:
 
 from . import critic_spec, regressor_spec, resnet_spec, synthetic  # noqa: F401,E402
 from ._lib import HpeError  # noqa: F401
+from .augment import augment_batch, draw_augmentation, mocap_real, plan_augmentation  # noqa: F401
 from .critic_train import CriticTrainer  # noqa: F401
 from .engine import HpeEngine  # noqa: F401
 from .generator_train import GeneratorTrainer  # noqa: F401

@@ -83,6 +83,13 @@ class HpeRenderParams(C.Structure):
     ]
 
 
+class HpeAugmentFrame(C.Structure):
+    """one table entry of hpe_augment_plan / hpe_augment_batch (include/hpe.h), 64 bytes"""
+    _fields_ = [("frame_offset", C.c_longlong), ("seg_offset", C.c_longlong), ("H", C.c_int), ("W", C.c_int), ("newH", C.c_int),
+                ("newW", C.c_int), ("cx", C.c_int), ("cy", C.c_int), ("fx", C.c_float), ("fy", C.c_float), ("flip", C.c_int),
+                ("inside", C.c_int), ("rx", C.c_float), ("ry", C.c_float)]
+
+
 OUTPUT_FIELDS = ("verts", "joints", "cams", "theta", "J_transformed", "kp2d", "verts2d", "Rs")
 
 
@@ -118,6 +125,8 @@ _PROTOS = {
     "hpe_preprocess_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "hpe_preprocess_u8_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int),
                                           C.c_void_p, C.c_void_p]),
+    "hpe_augment_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_augment_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_get_original": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_kp_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_kp_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

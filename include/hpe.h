@@ -376,6 +376,37 @@ int hpe_get_original(const float* verts_dev, const float* cam_dev, int B, int P,
                      int img_size, float* vert_shifted_dev, float cam_for_render[3], float* kp_original_host,
                      const float* joints2d_host, void* stream);
 
+/* -- training-batch augmentation: DataLoader.image_preprocessing (src/data_loader.py:160-213) with jitter_center, jitter_scale,
+ * pad_image_edge and random_flip (src/util/data_utils.py:144-238), the random draws as inputs.  What is computed is defined in
+ * DESIGN.md "Training-batch augmentation": all float32, in the reference's operation order, casts truncate toward zero. */
+typedef struct HpeAugmentFrame {
+    long long frame_offset; /* byte offset of the uint8 [H,W,3] image in frames_dev */
+    long long seg_offset;   /* byte offset of the uint8 [H,W] mask in segs_dev */
+    int H, W;               /* source size */
+    int newH, newW;         /* int(float(H) * scale), int(float(W) * scale) */
+    int cx, cy;             /* jittered centre in the resized image: int(float(center + trans) * fx), ... * fy) */
+    float fx, fy;           /* actual_factor: float(newW) / float(W), float(newH) / float(H) */
+    int flip;               /* 0 / 1 */
+    int inside;             /* 1: the 224 x 224 window lies inside the resized image padded by 112 + trans_max + 50 (where the reference's
+                             * tf.slice succeeds); 0: it leaves it, and the kernel clamps to the edge as if the pad were wider */
+    float rx, ry;           /* resize scale of tf.image.resize: float(W) / float(newW), float(H) / float(newH) */
+} HpeAugmentFrame;
+
+/* Pure host code, no device needed: fills table_out[B] from sizes_hw [B][2] (H, W), centers_xy [B][2], trans_xy [B][2], scales [B],
+ * flips [B] (0 / 1) and the byte offsets of the packed frames and masks.  HPE_ERR_INVALID for a NULL pointer, B < 1, trans_max < 0, a
+ * negative offset, H or W outside [1, 2^20], a scale that is not finite and positive, or a frame whose newH or newW is < 1 or > 2^20. */
+int hpe_augment_plan(int B, const int* sizes_hw, const int* centers_xy, const int* trans_xy, const float* scales,
+                     const unsigned char* flips, int trans_max, const long long* frame_offsets, const long long* seg_offsets,
+                     HpeAugmentFrame* table_out);
+/* ONE launch: images_out [B,224,224,3] in [-1,1], seg_out [B,224,224] in [0,1] and kp_out [B,19,3] from the packed uint8 frames and
+ * masks, the table of hpe_augment_plan and kp_dev [B,19,3] (x, y, visibility in source pixels).  The kernel reads table_dev, the
+ * caller's device copy of table_host (in flight on `stream` is enough); table_host is what this call checks.  No allocation, no
+ * synchronisation, capturable, no atomics: the same inputs give the same bits.  HPE_ERR_INVALID for a NULL pointer, B outside
+ * [1, 65535] and a table entry with H, W, newH or newW < 1 or a negative offset. */
+int hpe_augment_batch(const unsigned char* frames_dev, const unsigned char* segs_dev, const HpeAugmentFrame* table_host,
+                      const HpeAugmentFrame* table_dev, const float* kp_dev, int B, float* images_out, float* seg_out, float* kp_out,
+                      void* stream);
+
 /* -- mesh renderer: the reference's SMPLRenderer (src/util/renderer.py:23-112) without OpenDR ---------------------------------
  * A renderer is its own handle (the reference builds SMPLRenderer without a predictor, preview.py:50).  What it computes is
  * defined in DESIGN.md "Renderer": pinhole projection snapped to 1/256 px, rasterisation with int64 edge functions and a
