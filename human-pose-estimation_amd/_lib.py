@@ -90,6 +90,20 @@ class HpeAugmentFrame(C.Structure):
                 ("inside", C.c_int), ("rx", C.c_float), ("ry", C.c_float)]
 
 
+GEMM_DENSE, GEMM_STRIDED, GEMM_CONV3, GEMM_DUAL = 0, 1, 2, 4  # HpeDebugGemm.mode
+GEMM_TILES = ((128, 128), (128, 64), (64, 64), (64, 128), (128, 128), (128, 64), (256, 128))  # (BM, BN) of tile 0..6; 4..6 run 8 waves
+
+
+class HpeDebugGemm(C.Structure):
+    """arguments of hpe_debug_gemm_ex (include/hpe.h)"""
+    _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("tile", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+                ("lda", C.c_int), ("ldw", C.c_int), ("ldy", C.c_int), ("ldres", C.c_int), ("w_rows", C.c_int), ("relu", C.c_int),
+                ("Hi", C.c_int), ("Wi", C.c_int), ("Cin", C.c_int), ("Ho", C.c_int), ("Wo", C.c_int), ("stride", C.c_int),
+                ("k1_slabs", C.c_int), ("y_slab8", C.c_int), ("use_splitk", C.c_int), ("reserved", C.c_int),
+                ("x", C.c_void_p), ("x2", C.c_void_p), ("wt", C.c_void_p), ("residual", C.c_void_p), ("scale", C.c_void_p),
+                ("shift", C.c_void_p), ("y", C.c_void_p), ("split_k", C.POINTER(C.c_int))]
+
+
 OUTPUT_FIELDS = ("verts", "joints", "cams", "theta", "J_transformed", "kp2d", "verts2d", "Rs")
 
 
@@ -160,6 +174,7 @@ _PROTOS = {
     "hpe_debug_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "hpe_debug_stem": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_debug_gemm_ex": (C.c_int, [C.c_void_p, C.POINTER(HpeDebugGemm), C.c_void_p]),
     "hpe_debug_maxpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_avgpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_joint_regress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

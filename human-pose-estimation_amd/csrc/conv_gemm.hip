@@ -307,10 +307,8 @@ hipError_t launch_mode(GemmArgs& p, int tile, int splitk_min_slabs, hipStream_t 
     }
 }
 
-}  // namespace
-
 // Host-side shape contract (checked here so a bad plan cannot fault on the device).
-hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, int splitk_min_slabs, hipStream_t st) {
+hipError_t check_and_launch(GemmArgs& p, int mode, int tile, int splitk_min_slabs, hipStream_t st) {
     if (splitk_min_slabs < 2) return hipErrorInvalidValue;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.K % BK) != 0 || (p.ldw % 4) != 0 || p.ldw < p.K) return hipErrorInvalidValue;
     if (!p.x || !p.w || !p.y || !p.scale || !p.shift || !p.zero) return hipErrorInvalidValue;
@@ -328,11 +326,13 @@ hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, int splitk_min_slabs,
             return launch_mode<GEMM_DENSE>(p, tile, splitk_min_slabs, st);
         case GEMM_STRIDED:
             if (p.Cin != p.K || (p.Cin % 4) != 0) return hipErrorInvalidValue;
+            if (p.Ho < 1 || p.Wo < 1 || p.stride < 1) return hipErrorInvalidValue;  // the kernel divides by Ho * Wo and by Wo
             if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
             return launch_mode<GEMM_STRIDED>(p, tile, splitk_min_slabs, st);
         case GEMM_CONV3:
             if ((p.Cin % BK) != 0 || p.K != 9 * p.Cin || p.cin_slabs != p.Cin / BK || p.Ho != p.Hi || p.Wo != p.Wi)
                 return hipErrorInvalidValue;
+            if (p.Hi < 1 || p.Wi < 1) return hipErrorInvalidValue;
             return launch_mode<GEMM_CONV3>(p, tile, splitk_min_slabs, st);
         case GEMM_STEM:
             if (p.K != 7 * BK || p.Hi < 2 * (p.Ho - 1) + 7 || p.Wi < 2 * (p.Wo - 1) + 8) return hipErrorInvalidValue;
@@ -340,9 +340,19 @@ hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, int splitk_min_slabs,
         case GEMM_DUAL:
             if (!p.x2 || ((uintptr_t)p.x2 & 15) != 0 || p.k1_slabs < 1 || p.k1_slabs * BK >= p.K || p.lda < p.k1_slabs * BK || (p.lda % 4) != 0)
                 return hipErrorInvalidValue;
+            if (p.Ho < 1 || p.Wo < 1 || p.stride < 1) return hipErrorInvalidValue;  // before the host's own division by Ho * Wo
             if (p.Cin != p.K - p.k1_slabs * BK || (p.Cin % 4) != 0 || p.M != (p.M / (p.Ho * p.Wo)) * p.Ho * p.Wo) return hipErrorInvalidValue;
             if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
             return launch_mode<GEMM_DUAL>(p, tile, splitk_min_slabs, st);
         default: return hipErrorInvalidValue;
     }
+}
+
+}  // namespace
+
+hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, int splitk_min_slabs, hipStream_t st, int* split_k_out) {
+    p.split_k = 0;
+    const hipError_t e = check_and_launch(p, mode, tile, splitk_min_slabs, st);
+    if (split_k_out) *split_k_out = p.split_k;  // 0: rejected before a launcher ran
+    return e;
 }

@@ -700,30 +700,84 @@ int hpe_debug_stem(hpe_ctx* c, const float* images, int B, int rows_per_strip, f
     return HPE_OK;
 }
 
+int hpe_debug_gemm_ex(hpe_ctx* c, const HpeDebugGemm* g, void* stream) {
+    if (g && g->split_k) *g->split_k = 0;
+    if (!c || !c->finalized) return fail(HPE_ERR_STATE, "needs a finalized ctx");
+    if (!g) return fail(HPE_ERR_INVALID, "null HpeDebugGemm");
+    if (g->struct_size != (int)sizeof(HpeDebugGemm))
+        return fail(HPE_ERR_INVALID, "HpeDebugGemm.struct_size is " + std::to_string(g->struct_size) + ", this library's is " +
+                                         std::to_string(sizeof(HpeDebugGemm)) + " (other revision of include/hpe.h?)");
+    if (g->mode != HPE_GEMM_DENSE && g->mode != HPE_GEMM_STRIDED && g->mode != HPE_GEMM_CONV3 && g->mode != HPE_GEMM_DUAL)
+        return fail(HPE_ERR_INVALID, "hpe_debug_gemm_ex: mode must be dense, strided, conv3 or dual");
+    if ((!g->scale || !g->shift) && g->N > 1024) return fail(HPE_ERR_INVALID, "hpe_debug_gemm_ex: N <= 1024 without scale / shift");
+    static_assert(HPE_GEMM_DENSE == GEMM_DENSE && HPE_GEMM_STRIDED == GEMM_STRIDED && HPE_GEMM_CONV3 == GEMM_CONV3 && HPE_GEMM_DUAL == GEMM_DUAL,
+                  "include/hpe.h numbers the modes as GemmMode does");
+    DeviceGuard guard(c->cfg.device);
+    GemmArgs p{};
+    p.x = g->x;
+    p.x2 = g->x2;
+    p.w = g->wt;
+    p.scale = g->scale ? g->scale : c->ones;
+    p.shift = g->shift ? g->shift : c->zeros;
+    p.res = g->residual;
+    p.y = g->y;
+    p.M = g->M;
+    p.N = g->N;
+    p.K = g->K;
+    p.lda = g->lda;
+    p.ldw = g->ldw;
+    p.ldy = g->ldy;
+    p.ldres = g->ldres;
+    p.w_rows = g->w_rows;
+    p.relu = g->relu;
+    p.Hi = g->Hi;
+    p.Wi = g->Wi;
+    p.Cin = g->Cin;
+    p.Ho = g->Ho;
+    p.Wo = g->Wo;
+    p.stride = g->stride;
+    p.cin_slabs = g->Cin / 32;
+    p.k1_slabs = g->k1_slabs;
+    p.y_slab8 = g->y_slab8;
+    p.zero = c->zeros;
+    if (g->use_splitk) {
+        p.partial = c->partial;
+        p.partial_floats = c->partial_floats;
+    }
+    int split_k = 0;
+    const hipError_t e = hpe_launch_gemm(p, g->mode, g->tile, c->plan.splitk_min_slabs, static_cast<hipStream_t>(stream), &split_k);
+    if (g->split_k) *g->split_k = split_k;
+    if (e == hipErrorInvalidValue && split_k == 0)
+        return fail(HPE_ERR_INVALID, "hpe_launch_gemm rejected mode " + std::to_string(g->mode) + " tile " + std::to_string(g->tile) + " M " +
+                                         std::to_string(g->M) + " N " + std::to_string(g->N) + " K " + std::to_string(g->K) +
+                                         ": outside the launcher's contract (conv_gemm.hip), nothing was launched");
+    HIP_TRY(e);
+    return HPE_OK;
+}
+
 int hpe_debug_gemm(hpe_ctx* c, const float* x, const float* wt, int M, int N, int K, int w_rows, int tile, const float* residual,
                    int relu, float* y, void* stream) {
     if (!c || !c->finalized || !c->have_regressor) return fail(HPE_ERR_STATE, "needs a finalized ctx with the regressor loaded");
     if (!x || !wt || !y || N > 1024) return fail(HPE_ERR_INVALID, "bad argument (N <= 1024)");
-    DeviceGuard g(c->cfg.device);
-    GemmArgs p{};
-    p.x = x;
-    p.w = wt;
-    p.scale = c->ones;
-    p.shift = c->zeros;
-    p.res = residual;
-    p.y = y;
-    p.M = M;
-    p.N = N;
-    p.K = K;
-    p.lda = K;
-    p.ldw = K;
-    p.w_rows = w_rows;
-    p.ldy = N;
-    p.ldres = N;
-    p.relu = relu;
-    p.zero = c->zeros;
-    HIP_TRY(hpe_launch_gemm(p, GEMM_DENSE, tile, c->plan.splitk_min_slabs, static_cast<hipStream_t>(stream)));
-    return HPE_OK;
+    HpeDebugGemm g{};
+    g.struct_size = (int)sizeof(HpeDebugGemm);
+    g.mode = HPE_GEMM_DENSE;
+    g.tile = tile;
+    g.x = x;
+    g.wt = wt;
+    g.residual = residual;
+    g.y = y;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.lda = K;
+    g.ldw = K;
+    g.w_rows = w_rows;
+    g.ldy = N;
+    g.ldres = N;
+    g.relu = relu;
+    g.use_splitk = 0;
+    return hpe_debug_gemm_ex(c, &g, stream);
 }
 
 int hpe_debug_maxpool(const float* x, int B, int H, int C, float* y, void* stream) {

@@ -38,8 +38,9 @@ struct GemmArgs {
     int w_piece;  // hpe_launch_gemm_f32s: element offset of bf16 piece j = 1, 2 inside a weight row (piece j of Wt[n][k] at w + n * ldw + j * w_piece + k)
 };
 
-// splitk_min_slabs (>= 2): k-slabs per slice when a small grid is cut along K
-hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, int splitk_min_slabs, hipStream_t st);
+// splitk_min_slabs (>= 2): k-slabs per slice when a small grid is cut along K; split_k_out (host, optional) receives the split_k the
+// launcher chose (1 = whole tiles, 0 = the contract rejected the arguments and nothing was launched)
+hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, int splitk_min_slabs, hipStream_t st, int* split_k_out = nullptr);
 // conv_gemm_f32s.hip: the same fp32 GEMM (GEMM_DENSE / GEMM_STRIDED / GEMM_DUAL, whole tiles, no split-K) on the bf16 matrix cores: p.w points to
 // bf16 weights split exactly into three pieces on the host (w = w0 + w1 + w2, offsets in bf16 elements, ldw and w_piece multiples of 8), A is
 // split the same way in registers; the six products with i + j <= 2 are summed in fp32.  Tiles TILE_128x128 (4 waves), TILE_128x128_W8,

@@ -716,6 +716,25 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_debug_conv(self._h, idx, x.data_ptr(), B, r, int(relu), y.data_ptr(), self._stream()))
         return y
 
+    def debug_gemm_ex(self, mode, tile, x, wt, y, M, N, K, **kw):
+        """hpe_debug_gemm_ex: the fp32 implicit-GEMM kernel with every launch argument given (HpeDebugGemm of include/hpe.h).  x, wt, y
+        and the optional x2 / residual / scale / shift are CUDA tensors or device addresses, y is written in place; the other
+        HpeDebugGemm fields are keywords (default 0, pitches default to the dense ones).  Returns the split_k the launcher chose."""
+        g = _lib.HpeDebugGemm()
+        g.struct_size = C.sizeof(_lib.HpeDebugGemm)
+        fields = dict(lda=K, ldw=K, ldy=N, ldres=N, mode=mode, tile=tile, x=x, wt=wt, y=y, M=M, N=N, K=K)
+        fields.update(kw)
+        for k, v in fields.items():
+            if k in ("x", "x2", "wt", "residual", "scale", "shift", "y"):
+                v = v.data_ptr() if hasattr(v, "data_ptr") else v
+            elif k in ("struct_size", "split_k") or not hasattr(g, k):
+                raise TypeError("debug_gemm_ex: unknown argument %r" % k)
+            setattr(g, k, v)
+        sk = C.c_int(-1)
+        g.split_k = C.pointer(sk)
+        _lib.check(self.lib.hpe_debug_gemm_ex(self._h, C.byref(g), self._stream()))
+        return sk.value
+
     def debug_chain(self, idx2c, t2, residual):
         """bf16 contexts: res*_branch2c (+ residual + ReLU) and the next block's res*_branch2a (+ ReLU) as the one launch of
         conv_chain_bf16.hip.  Returns (t3 [B,H,H,4C], u1 [B,H,H,C], resident workgroups per CU of the two instantiations)."""

@@ -467,8 +467,47 @@ int hpe_debug_chain(hpe_ctx* ctx, int idx2c, const float* t2_dev, const float* r
  * src/models.py:39): images_dev [B,224,224,3] -> y_dev [B,56,56,64].  rows_per_strip: pooled rows per workgroup
  * (1, 2, 4, 7 or 8; 0 = the default for this batch).  fp32 contexts only. */
 int hpe_debug_stem(hpe_ctx* ctx, const float* images_dev, int B, int rows_per_strip, float* y_dev, void* stream);
-/* Raw GEMM through the conv kernel (dense mode): y[M,N] = act(x[M,K] . wt[n][k]^T (+ residual)), wt has w_rows >= N
- * rounded up to the tile width rows of K floats; K % 32 == 0; tile: 0 = 128x128, 1 = 128x64, 2 = 64x64, 3 = 64x128. */
+/* The fp32 implicit-GEMM kernel (conv_gemm.hip) with every launch argument in the caller's hands:
+ *   y[m][n] = act((sum_k A[m][k] * wt[n][k]) * scale[n] + shift[n] (+ residual[m][n]))
+ * mode picks how row m of A is gathered:
+ *   HPE_GEMM_DENSE    x [M][lda];
+ *   HPE_GEMM_STRIDED  x NHWC [B][Hi][Wi][Cin], row m = pixel (b, ho * stride, wo * stride) of the Ho x Wo output map, K = Cin;
+ *   HPE_GEMM_CONV3    x NHWC [B][Hi][Wi][Cin], 3x3 / stride 1 / SAME (Ho = Hi, Wo = Wi), K = 9 * Cin, k = (kh * 3 + kw) * Cin + ci;
+ *   HPE_GEMM_DUAL     k-slabs (of 32) [0, k1_slabs) from the dense x [M][lda], the rest from the strided x2 (Cin = K - 32 * k1_slabs).
+ * tile: 0 = 128x128, 1 = 128x64, 2 = 64x64, 3 = 64x128 (4 waves; these may split K), 4 = 128x128, 5 = 128x64, 6 = 256x128 (8 waves).
+ * wt: w_rows rows of pitch ldw, w_rows >= N rounded up to the tile width, zero padded.  scale / shift NULL: ones / zeros (N <= 1024).
+ * y_slab8: y is written channel-slab major, y[(n / 8) * M + m][n % 8].  use_splitk: the launcher is handed the context's split-K
+ * workspace (it then cuts K on small grids of the 4-wave tiles), else none.  split_k (host, optional) receives the number of K slices the
+ * launcher chose (1 = not split).  Every argument goes through the launcher's host-side contract: a rejected one returns
+ * HPE_ERR_INVALID, launches nothing and sets *split_k to 0.  All device pointers 16-byte aligned; all pitches multiples of 4 floats. */
+#define HPE_GEMM_DENSE 0
+#define HPE_GEMM_STRIDED 1
+#define HPE_GEMM_CONV3 2
+#define HPE_GEMM_DUAL 4
+typedef struct HpeDebugGemm {
+    int struct_size; /* sizeof(HpeDebugGemm), written by the caller and checked by the call */
+    int mode;
+    int tile;
+    int M, N, K;
+    int lda, ldw, ldy, ldres, w_rows;
+    int relu;
+    int Hi, Wi, Cin, Ho, Wo, stride;
+    int k1_slabs;
+    int y_slab8;
+    int use_splitk;
+    int reserved; /* 0 */
+    const float* x;
+    const float* x2;
+    const float* wt;
+    const float* residual;
+    const float* scale;
+    const float* shift;
+    float* y;
+    int* split_k;
+} HpeDebugGemm;
+int hpe_debug_gemm_ex(hpe_ctx* ctx, const HpeDebugGemm* g, void* stream);
+/* The dense mode of hpe_debug_gemm_ex with scale = ones, shift = zeros, lda = ldw = K, ldy = ldres = N and no split-K
+ * workspace: y[M,N] = act(x[M,K] . wt[n][k]^T (+ residual)); K % 32 == 0; N <= 1024; tile 0..6 as above.  Needs the regressor loaded. */
 int hpe_debug_gemm(hpe_ctx* ctx, const float* x_dev, const float* wt_dev, int M, int N, int K, int w_rows, int tile,
                    const float* residual_dev, int relu, float* y_dev, void* stream);
 /* ZeroPad(1)+MaxPool3x3/2: x [B,H,H,C] -> y [B,H/2,H/2,C];  global average pool x [B,HW,C] -> y [B,C] */

@@ -1,0 +1,509 @@
+"""float64 references of the fp32 implicit-GEMM kernel (conv_gemm.hip), written from the definition
+
+    y[m][n] = act((sum_k A[m][k] * Wt[n][k]) * scale[n] + shift[n] (+ res[m][n]))
+
+for its four product modes, the weight packing the kernel reads, seeded inputs, the shape lists of tests/test_gpu_gemm_edges.py and
+a restatement of the launcher's host-side contract (hpe_launch_gemm).  Plain NumPy, no GPU, nothing taken from the library:
+tests/test_gemm_ref_cpu.py pins the references to oracle.hmr_oracle.conv2d_nhwc, the inputs to the bar and the lists to the contract.
+
+Packed weights Wt[n][k], w_rows x ldw, zero padded:  1x1 layers k = ci;  3x3 layers k = (kh * 3 + kw) * Cin + ci;  dual: the k
+range of the dense source followed by the k range of the strided source.
+"""
+import functools
+
+import numpy as np
+
+DENSE, STRIDED, CONV3, STEM, DUAL = 0, 1, 2, 3, 4
+TILES = ((128, 128), (128, 64), (64, 64), (64, 128), (128, 128), (128, 64), (256, 128))  # (BM, BN) of tile 0..6
+TILE_NAMES = ("128x128", "128x64", "64x64", "64x128", "128x128_W8", "128x64_W8", "256x128_W8")
+SPLIT_TILES = (0, 1, 2, 3)  # the 4-wave tiles: the only ones the launcher cuts along K
+W8_TILES = (4, 5, 6)
+BK = 32
+SPLITK_MIN_SLABS = 4  # the plan's default (HPE_SPLITK_SLABS)
+BAR = 5e-6  # the project's single-conv bar (test_conv_layer_matches_oracle): max|got - ref| / max|ref|
+THETA_LD = 96  # pitch of the regressor's theta rows: run_dense writes its N = 85 layer at this pitch
+
+
+def pad_to(n, b):
+    return (n + b - 1) // b * b
+
+
+# ------------------------------------------------------------------------------------------- references
+def epilogue(acc, scale, shift, res, relu):
+    """acc [M,N] float64 -> act(acc * scale + shift (+ res))"""
+    N = acc.shape[1]
+    y = acc * np.asarray(scale, np.float64)[:N] + np.asarray(shift, np.float64)[:N]
+    if res is not None:
+        y = y + np.asarray(res, np.float64)[: acc.shape[0], :N]
+    return np.maximum(y, 0.0) if relu else y
+
+
+def acc_dense(A, W):
+    """A [M,K], W [N,K] -> [M,N] in float64"""
+    return np.asarray(A, np.float64) @ np.asarray(W, np.float64).T
+
+
+def gather_strided(x, Ho, Wo, stride):
+    """x [B,Hi,Wi,C] -> rows [B*Ho*Wo, C]: pixel (ho * stride, wo * stride) of every image, (b, ho, wo) flattened"""
+    B, _, _, C = x.shape
+    rows = np.empty((B, Ho, Wo, C), x.dtype)
+    for ho in range(Ho):
+        for wo in range(Wo):
+            rows[:, ho, wo, :] = x[:, ho * stride, wo * stride, :]
+    return rows.reshape(B * Ho * Wo, C)
+
+
+def acc_strided(x, W, Ho, Wo, stride):
+    """1x1 convolution with a stride, no padding: x [B,Hi,Wi,Cin], W [N,Cin] -> [B*Ho*Wo, N]"""
+    return acc_dense(gather_strided(x, Ho, Wo, stride), W)
+
+
+def acc_conv3(x, hwio):
+    """3x3 / stride 1 / SAME with zero padding around EACH image: x [B,H,W,Cin], hwio [3,3,Cin,N] -> [B*H*W, N]"""
+    B, H, W, C = x.shape
+    xp = np.zeros((B, H + 2, W + 2, C), np.float64)
+    xp[:, 1 : H + 1, 1 : W + 1, :] = x
+    k = np.asarray(hwio, np.float64)
+    acc = np.zeros((B, H, W, k.shape[3]), np.float64)
+    for kh in range(3):
+        for kw in range(3):
+            acc += xp[:, kh : kh + H, kw : kw + W, :] @ k[kh, kw]
+    return acc.reshape(B * H * W, -1)
+
+
+def acc_dual(a, W1, x2, W2, Ho, Wo, stride):
+    """dense source a [M,K1] . W1 [N,K1] plus strided source x2 [B,Hi,Wi,Cin] . W2 [N,Cin], M = B*Ho*Wo"""
+    return acc_dense(a, W1) + acc_strided(x2, W2, Ho, Wo, stride)
+
+
+def to_slab8(y):
+    """row-major [M,N] (N % 8 == 0) -> channel-slab major [(n / 8) * M + m][n % 8], as GemmArgs::y_slab8 writes it"""
+    M, N = y.shape
+    return np.ascontiguousarray(y.reshape(M, N // 8, 8).transpose(1, 0, 2)).reshape(N // 8 * M, 8)
+
+
+# ------------------------------------------------------------------------------------------- packing
+def pack_rows(W, w_rows, ldw):
+    """W [N,K] -> float32 [w_rows, ldw], zero padded"""
+    N, K = W.shape
+    out = np.zeros((w_rows, ldw), np.float32)
+    out[:N, :K] = W
+    return out
+
+
+def pack_3x3(hwio, w_rows, ldw):
+    """hwio [3,3,Cin,N] -> Wt[n][(kh * 3 + kw) * Cin + ci]"""
+    _, _, C, N = hwio.shape
+    W = np.empty((N, 9 * C), np.float32)
+    for kh in range(3):
+        for kw in range(3):
+            for ci in range(C):
+                W[:, (kh * 3 + kw) * C + ci] = hwio[kh, kw, ci, :]
+    return pack_rows(W, w_rows, ldw)
+
+
+def pack_dual(W1, W2, w_rows, ldw):
+    return pack_rows(np.concatenate([W1, W2], axis=1), w_rows, ldw)
+
+
+# ------------------------------------------------------------------------------------------- inputs
+def rng(*key):
+    return np.random.Generator(np.random.Philox(key=[int(sum((k + 1) * 1000003 ** i for i, k in enumerate(key))) % (1 << 63), 17]))
+
+
+def normal(g, shape, sigma=1.0):
+    """signed normal data: ReLU cuts about half of the outputs and a leaked halo tap is never hidden by a zero"""
+    return (g.normal(0, 1, shape) * sigma).astype(np.float32)
+
+
+def weights(g, N, K):
+    """N(0, 1/K): the accumulators come out N(0, 1), the size of shift and of the residual, so no term of the epilogue is hidden"""
+    return normal(g, (N, K), 1.0 / np.sqrt(K))
+
+
+def scale_shift(g, N):
+    """scale in +-[0.5, 2], shift normal: a different pair in every column"""
+    sc = (g.uniform(0.5, 2.0, N) * np.where(g.integers(0, 2, N) == 0, -1.0, 1.0)).astype(np.float32)
+    return sc, normal(g, (N,))
+
+
+# ------------------------------------------------------------------------------------------- metric
+def rel(got, ref):
+    got = np.asarray(got, np.float64)
+    ref = np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    return float(np.abs(got - ref).max() / (np.abs(ref).max() + 1e-30))
+
+
+def edge_errors(got, ref, BM, BN):
+    """(whole matrix, rows of the last partial M-tile, columns of the last partial N-tile): each block over its OWN largest
+    reference entry, so that an edge error is not diluted by the rest of the matrix.  A block that does not exist gives 0."""
+    M, N = ref.shape
+    e = [rel(got, ref), 0.0, 0.0]
+    if M % BM:
+        e[1] = rel(got[M // BM * BM :], ref[M // BM * BM :])
+    if N % BN:
+        e[2] = rel(got[:, N // BN * BN :], ref[:, N // BN * BN :])
+    return tuple(e)
+
+
+# ------------------------------------------------------------------------------------------- the shape lists of the GPU file
+DENSE_K = (32, 64, 96, 512)
+
+
+def _mix(i, n_widths):
+    """case number -> a counter whose bits change along the width loop (the innermost, n_widths long) AND along the loops around it,
+    so that residual, ReLU and the pitches are not tied to one width"""
+    return i // n_widths + i % n_widths
+
+
+def dense_m(BM):
+    return (1, BM - 1, BM, BM + 1, 2 * BM + 37)
+
+
+def dense_n(BN):
+    return (4, BN - 4, BN, BN + 4, 2 * BN + 20, 85)
+
+
+DENSE_M_MAX = 2 * 256 + 37
+DENSE_N_MAX = 2 * 128 + 20
+DENSE_W_ROWS = pad_to(DENSE_N_MAX, 128)
+
+
+def dense_cases(tile):
+    """every (M, N, K) of the dense block on one tile; the pitches, residual and ReLU cycle with the case number so that each tile
+    sees lda > K with ldy > N and ldres != ldy, and all four (residual, ReLU) pairs, many times over.  N = 85 always runs at
+    run_dense's pitch: ldy = ldres = THETA_LD, w_rows = 128."""
+    BM, BN = TILES[tile]
+    out = []
+    i = 0
+    for K in DENSE_K:
+        for M in dense_m(BM):
+            for N in dense_n(BN):
+                c = dict(mode=DENSE, tile=tile, M=M, N=N, K=K, ldw=K, w_rows=pad_to(N, BN), relu=(_mix(i, 6) >> 1) & 1, use_res=_mix(i, 6) & 1,
+                         lda=K + 8 * ((_mix(i, 6) >> 2) % 3 == 1), ldy=pad_to(N, 4) + 4 + 4 * ((_mix(i, 6) >> 3) & 1), ldres=pad_to(N, 4) + 12)
+                if N == 85:
+                    c.update(ldy=THETA_LD, ldres=THETA_LD, w_rows=128)
+                out.append(c)
+                i += 1
+    return out
+
+
+SLAB8_TILES = (1, 4)
+
+
+def slab8_cases(tile):
+    BM, BN = TILES[tile]
+    return [dict(mode=DENSE, tile=tile, M=M, N=N, K=64, lda=64, ldw=64, ldy=N, ldres=N + 4, w_rows=pad_to(N, BN), relu=_mix(i, 3) & 1, use_res=(_mix(i, 3) >> 1) & 1,
+                 y_slab8=1, master=(257, 136))
+            for i, (M, N) in enumerate((M, N) for M in (BM + 1, 37) for N in (8, 72, BN + 8))]
+
+
+SPLITK_M, SPLITK_N, SPLITK_K = (1, 5, 65), (64, 85, 200), (256, 288, 2048)
+
+
+def splitk_cases(tile):
+    BN = TILES[tile][1]
+    out = []
+    for i, (K, M, N) in enumerate((K, M, N) for K in SPLITK_K for M in SPLITK_M for N in SPLITK_N):
+        out.append(dict(mode=DENSE, tile=tile, M=M, N=N, K=K, lda=K, ldw=K, ldy=pad_to(N, 4) + 4, ldres=pad_to(N, 4) + 8, w_rows=pad_to(N, BN),
+                        relu=(_mix(i, 3) >> 1) & 1, use_res=_mix(i, 3) & 1, use_splitk=1, master=(65, 200)))
+    return out
+
+
+def w8_splitk_cases():
+    """an 8-wave tile handed the workspace must not split: one shape per tile that a 4-wave tile would cut in 16"""
+    return [dict(mode=DENSE, tile=t, M=65, N=200, K=2048, lda=2048, ldw=2048, ldy=204, ldres=208, w_rows=256, relu=1, use_res=1, use_splitk=1,
+                 master=(65, 200)) for t in W8_TILES]
+
+
+def expected_split_k(c, partial_floats=512 * 128 * 128):
+    """the launcher's choice as written in launch_cfg (conv_gemm.hip), for the CPU check that every split-K case really splits"""
+    BM, BN = TILES[c["tile"]]
+    if c["tile"] not in SPLIT_TILES or not c.get("use_splitk"):
+        return 1
+    grid = pad_to(c["M"], BM) // BM * (pad_to(c["N"], BN) // BN)
+    S = c["K"] // BK
+    if grid >= 128 or S < 2 * SPLITK_MIN_SLABS:
+        return 1
+    sk = min(256 // grid, S // SPLITK_MIN_SLABS, 16)
+    while sk > 1 and grid * sk * BM * BN > partial_floats:
+        sk -= 1
+    return max(sk, 1)
+
+
+BATCH = 3
+STRIDED_GEO = ((6, 3, 2), (14, 7, 2), (7, 7, 1))  # (Hi, Ho, stride); (14, 7, 2): M = 147 crosses a 128-row tile inside an image
+
+
+def strided_cases(tile):
+    BN = TILES[tile][1]
+    out = []
+    for i, (geo, Cin, N) in enumerate((g, c, n) for g in STRIDED_GEO for c in (32, 96) for n in (64, 132)):
+        Hi, Ho, s = geo
+        out.append(dict(mode=STRIDED, tile=tile, M=BATCH * Ho * Ho, N=N, K=Cin, Cin=Cin, Hi=Hi, Wi=Hi, Ho=Ho, Wo=Ho, stride=s, lda=Cin, ldw=Cin,
+                        ldy=N + 4, ldres=N + 8, w_rows=pad_to(N, BN), relu=(_mix(i, 2) >> 1) & 1, use_res=_mix(i, 2) & 1))
+    return out
+
+
+CONV3_MAPS = ((1, 1), (3, 3), (7, 7), (14, 14), (5, 7))  # (H, W); (5, 7): inside the launcher's contract, outside the product's use
+
+
+def conv3_cases(tile, use_splitk=0):
+    BN = TILES[tile][1]
+    out = []
+    for i, (hw, Cin, N) in enumerate((m, c, n) for m in CONV3_MAPS for c in (32, 64) for n in (64, 192)):
+        H, W = hw
+        out.append(dict(mode=CONV3, tile=tile, M=BATCH * H * W, N=N, K=9 * Cin, Cin=Cin, Hi=H, Wi=W, Ho=H, Wo=W, stride=1, lda=Cin, ldw=9 * Cin,
+                        ldy=N + 4, ldres=N + 8, w_rows=pad_to(N, BN), relu=(_mix(i, 2) >> 1) & 1, use_res=_mix(i, 2) & 1, use_splitk=use_splitk))
+    return out
+
+
+DUAL_GEO = ((7, 7, 1), (14, 7, 2))
+
+
+def dual_cases(tile):
+    BN = TILES[tile][1]
+    out = []
+    for i, (geo, k1, Cin, N) in enumerate((g, k, c, n) for g in DUAL_GEO for k in (1, 3) for c in (32, 64) for n in (128, 260)):
+        Hi, Ho, s = geo
+        K = k1 * BK + Cin
+        out.append(dict(mode=DUAL, tile=tile, M=BATCH * Ho * Ho, N=N, K=K, Cin=Cin, Hi=Hi, Wi=Hi, Ho=Ho, Wo=Ho, stride=s, k1_slabs=k1,
+                        lda=k1 * BK + 8 * (_mix(i, 2) & 1), ldw=K, ldy=N + 4, ldres=N + 4, w_rows=pad_to(N, BN), relu=(_mix(i, 2) >> 1) & 1, use_res=0))
+    return out
+
+
+def all_valid_cases():
+    out = []
+    for t in range(7):
+        out += dense_cases(t) + strided_cases(t) + conv3_cases(t) + dual_cases(t)
+    for t in SLAB8_TILES:
+        out += slab8_cases(t)
+    for t in SPLIT_TILES:
+        out += splitk_cases(t)
+    out += conv3_cases(2, use_splitk=1)
+    out += w8_splitk_cases()
+    return out
+
+
+# ------------------------------------------------------------------------------------------- the launcher's contract
+POINTERS = ("x", "x2", "wt", "residual", "y")
+
+
+def contract_violations(c, null=(), misaligned=()):
+    """The clauses of hpe_launch_gemm's host-side contract (conv_gemm.hip) that the launch c breaks, by name.  Pointers are
+    described, not held: a case has x, wt and y, residual with use_res and x2 in dual mode, minus `null`; the ones in `misaligned`
+    are not multiples of 16 bytes.  scale, shift and the zero page come from the hook and are never NULL."""
+    g = dict(lda=0, ldw=0, ldy=0, ldres=0, w_rows=0, Hi=0, Wi=0, Cin=0, Ho=0, Wo=0, stride=0, k1_slabs=0, y_slab8=0)
+    g.update(c)
+    has = {"x": True, "wt": True, "y": True, "residual": bool(g.get("use_res")), "x2": g["mode"] == DUAL}
+    for n in null:
+        has[n] = False
+    bad = []
+
+    def clause(name, broken):
+        if broken:
+            bad.append(name)
+
+    M, N, K = g["M"], g["N"], g["K"]
+    clause("M > 0", M <= 0)
+    clause("N > 0", N <= 0)
+    clause("K > 0", K <= 0)
+    clause("K % 32 == 0", K > 0 and K % BK != 0)
+    clause("ldw % 4 == 0", g["ldw"] % 4 != 0)
+    clause("ldw >= K", g["ldw"] < K)
+    for n in ("x", "wt", "y"):
+        clause(n + " != NULL", not has[n])
+    clause("ldy % 4 == 0", g["ldy"] % 4 != 0)
+    clause("y aligned", "y" in misaligned)
+    clause("y_slab8 needs N % 8 == 0", bool(g["y_slab8"]) and N % 8 != 0)
+    if has["residual"]:
+        clause("ldres % 4 == 0", g["ldres"] % 4 != 0)
+        clause("residual aligned", "residual" in misaligned)
+    clause("x aligned", "x" in misaligned)
+    clause("wt aligned", "wt" in misaligned)
+    tile = g["tile"]
+    clause("tile in 0..6", not 0 <= tile <= 6)
+    if 0 <= tile <= 6 and N > 0:
+        clause("w_rows covers the padded N", pad_to(N, TILES[tile][1]) > g["w_rows"])
+    mode = g["mode"]
+    clause("mode", mode not in (DENSE, STRIDED, CONV3, DUAL))  # the hook refuses the stem mode, the launcher unknown ones
+    stride_ok = g["Ho"] >= 1 and g["Wo"] >= 1 and g["stride"] >= 1
+    if mode == DENSE:
+        clause("lda >= K", g["lda"] < K)
+        clause("lda % 4 == 0", g["lda"] % 4 != 0)
+    elif mode == STRIDED:
+        clause("Cin == K", g["Cin"] != K)
+        clause("Cin % 4 == 0", g["Cin"] % 4 != 0)
+        clause("Ho, Wo, stride >= 1", not stride_ok)
+        clause("(Ho - 1) * stride < Hi", stride_ok and (g["Ho"] - 1) * g["stride"] >= g["Hi"])
+        clause("(Wo - 1) * stride < Wi", stride_ok and (g["Wo"] - 1) * g["stride"] >= g["Wi"])
+    elif mode == CONV3:
+        clause("Cin % 32 == 0", g["Cin"] % BK != 0)
+        clause("K == 9 * Cin", K != 9 * g["Cin"])
+        clause("Ho == Hi", g["Ho"] != g["Hi"])
+        clause("Wo == Wi", g["Wo"] != g["Wi"])
+        clause("Hi, Wi >= 1", g["Hi"] < 1 or g["Wi"] < 1)
+    elif mode == DUAL:
+        k1 = g["k1_slabs"]
+        clause("x2 != NULL", not has["x2"])
+        clause("x2 aligned", "x2" in misaligned)
+        clause("k1_slabs >= 1", k1 < 1)
+        clause("k1_slabs * 32 < K", k1 * BK >= K)
+        clause("lda >= k1_slabs * 32", g["lda"] < k1 * BK)
+        clause("lda % 4 == 0", g["lda"] % 4 != 0)
+        clause("Cin == K - k1_slabs * 32", g["Cin"] != K - k1 * BK)
+        clause("Cin % 4 == 0", g["Cin"] % 4 != 0)
+        clause("Ho, Wo, stride >= 1", not stride_ok)
+        clause("M % (Ho * Wo) == 0", stride_ok and M % (g["Ho"] * g["Wo"]) != 0)
+        clause("(Ho - 1) * stride < Hi", stride_ok and (g["Ho"] - 1) * g["stride"] >= g["Hi"])
+        clause("(Wo - 1) * stride < Wi", stride_ok and (g["Wo"] - 1) * g["stride"] >= g["Wi"])
+    return bad
+
+
+def error_bases():
+    """one valid launch per mode (64x64 tile, no residual unless the case needs one): the error cases are these with ONE change"""
+    return {
+        "dense": dict(mode=DENSE, tile=2, M=5, N=64, K=64, lda=64, ldw=64, ldy=68, ldres=72, w_rows=64, relu=0, use_res=1),
+        "strided": dict(mode=STRIDED, tile=2, M=27, N=64, K=32, Cin=32, Hi=6, Wi=6, Ho=3, Wo=3, stride=2, lda=32, ldw=32, ldy=68, ldres=72, w_rows=64,
+                        relu=0, use_res=0),
+        "conv3": dict(mode=CONV3, tile=2, M=27, N=64, K=288, Cin=32, Hi=3, Wi=3, Ho=3, Wo=3, stride=1, lda=32, ldw=288, ldy=68, ldres=72, w_rows=64,
+                      relu=0, use_res=0),
+        "dual": dict(mode=DUAL, tile=2, M=27, N=64, K=64, Cin=32, Hi=6, Wi=6, Ho=3, Wo=3, stride=2, k1_slabs=1, lda=32, ldw=64, ldy=68, ldres=72,
+                     w_rows=64, relu=0, use_res=0),
+    }
+
+
+# (base, the one change, null pointers, misaligned pointers): each breaks exactly one clause of the contract.  Not reachable alone and
+# so not listed: Cin % 4 (strided: Cin == K and K % 32 == 0 imply it; dual: K and k1_slabs * 32 are multiples of 32), Cin % 32 of
+# conv3 (K == 9 * Cin and K % 32 == 0 imply it) and cin_slabs (the hook derives it from Cin).
+ERROR_CASES = [
+    ("dense", dict(M=0), (), ()),
+    ("dense", dict(N=0), (), ()),
+    ("dense", dict(K=0, lda=0, ldw=0), (), ()),
+    ("dense", dict(K=48), (), ()),
+    ("dense", dict(ldw=66), (), ()),
+    ("dense", dict(ldw=60), (), ()),
+    ("dense", {}, ("x",), ()),
+    ("dense", {}, ("wt",), ()),
+    ("dense", {}, ("y",), ()),
+    ("dense", dict(ldy=70), (), ()),
+    ("dense", {}, (), ("y",)),
+    ("dense", dict(y_slab8=1, N=60), (), ()),
+    ("dense", dict(ldres=70), (), ()),
+    ("dense", {}, (), ("residual",)),
+    ("dense", {}, (), ("x",)),
+    ("dense", {}, (), ("wt",)),
+    ("dense", dict(w_rows=60), (), ()),
+    ("dense", dict(N=68), (), ()),  # 68 columns need two 64-wide tiles = 128 weight rows
+    ("dense", dict(tile=7), (), ()),
+    ("dense", dict(tile=-1), (), ()),
+    ("dense", dict(mode=STEM), (), ()),
+    ("dense", dict(lda=60), (), ()),
+    ("dense", dict(lda=66), (), ()),
+    ("strided", dict(Cin=64), (), ()),
+    ("strided", dict(Ho=0), (), ()),
+    ("strided", dict(stride=0), (), ()),
+    ("strided", dict(stride=-2), (), ()),
+    ("strided", dict(Hi=4), (), ()),  # (Ho - 1) * stride = 4 >= Hi
+    ("strided", dict(Wi=4), (), ()),
+    ("conv3", dict(K=256, ldw=288), (), ()),
+    ("conv3", dict(Ho=2), (), ()),
+    ("conv3", dict(Wo=4), (), ()),
+    ("conv3", dict(Hi=0, Ho=0), (), ()),
+    ("dual", {}, ("x2",), ()),
+    ("dual", {}, (), ("x2",)),
+    ("dual", dict(k1_slabs=0, Cin=64), (), ()),
+    ("dual", dict(k1_slabs=2, Cin=0, lda=64), (), ()),  # k1_slabs * 32 == K: nothing left for the strided source
+    ("dual", dict(lda=28), (), ()),
+    ("dual", dict(lda=34), (), ()),
+    ("dual", dict(Cin=64), (), ()),
+    ("dual", dict(Wo=0), (), ()),
+    ("dual", dict(M=26), (), ()),
+    ("dual", dict(Hi=4), (), ()),
+    ("dual", dict(Wi=4), (), ()),
+]
+
+
+def error_case(i):
+    base, change, null, mis = ERROR_CASES[i]
+    return dict(error_bases()[base], **change), null, mis
+
+
+# ------------------------------------------------------------------------------------------- the inputs and references of a case
+@functools.lru_cache(maxsize=None)
+def _dense_master(K, Mmax, Nmax):
+    """one draw per (K, block): every dense case of the block is its top-left corner, the float64 product is formed once"""
+    g = rng(DENSE, K, Mmax, Nmax)
+    A, W = normal(g, (Mmax, K)), weights(g, Nmax, K)
+    sc, sh = scale_shift(g, Nmax)
+    return dict(A=A, W=W, R=normal(g, (Mmax, Nmax)), pad=normal(g, (Mmax, 8)), scale=sc, shift=sh, acc=acc_dense(A, W))
+
+
+@functools.lru_cache(maxsize=None)
+def _conv_master(mode, Hi, Wi, Ho, Wo, stride, Cin, N, k1):
+    g = rng(mode, Hi, Wi, Ho, stride, Cin, N, k1)
+    M = BATCH * Ho * Wo
+    d = dict(x2=None, x=normal(g, (BATCH, Hi, Wi, Cin)), R=normal(g, (M, N)))
+    d["scale"], d["shift"] = scale_shift(g, N)
+    if mode == STRIDED:
+        d["W"] = weights(g, N, Cin)
+        d["acc"] = acc_strided(d["x"], d["W"], Ho, Wo, stride)
+    elif mode == CONV3:
+        d["hwio"] = normal(g, (3, 3, Cin, N), 1.0 / np.sqrt(9 * Cin))
+        d["W"] = pack_3x3(d["hwio"], N, 9 * Cin)
+        d["acc"] = acc_conv3(d["x"], d["hwio"])
+    else:  # DUAL: x is the strided source here, a the dense one
+        K = k1 * BK + Cin
+        d["a"], d["pad"] = normal(g, (M, k1 * BK)), normal(g, (M, 8))
+        d["W1"], d["W2"] = weights(g, N, K)[:, : k1 * BK].copy(), weights(g, N, K)[:, :Cin].copy()
+        d["W"] = np.concatenate([d["W1"], d["W2"]], axis=1)
+        d["acc"] = acc_dual(d["a"], d["W1"], d["x"], d["W2"], Ho, Wo, stride)
+    return d
+
+
+def inputs(c):
+    """host arrays of case c in the layouts the kernel reads -- x [M, lda] (dense; the columns past K hold noise, not zeros) or NHWC,
+    x2, wt [w_rows, ldw], res [M + 1, ldres], scale, shift -- and acc, the float64 accumulators A . Wt^T"""
+    M, N, K = c["M"], c["N"], c["K"]
+    if c["mode"] == DENSE:
+        m = _dense_master(K, *c.get("master", (DENSE_M_MAX, DENSE_N_MAX)))
+        x = np.concatenate([m["A"][:M], m["pad"][:M]], axis=1)[:, : c["lda"]]
+        x2, W, R, acc = None, m["W"][:N], m["R"][:M, :N], m["acc"][:M, :N]
+    else:
+        m = _conv_master(c["mode"], c["Hi"], c["Wi"], c["Ho"], c["Wo"], c["stride"], c["Cin"], N, c.get("k1_slabs", 0))
+        x, x2, W, R, acc = m["x"], None, m["W"], m["R"], m["acc"]
+        if c["mode"] == DUAL:
+            x, x2 = np.concatenate([m["a"], m["pad"]], axis=1)[:, : c["lda"]], m["x"]
+    res = None
+    if c.get("use_res"):
+        res = np.full((M + 1, c["ldres"]), 1e3, np.float32)  # a residual read at the wrong pitch, column or row lands on 1000
+        res[:M, :N] = R
+    return dict(x=np.ascontiguousarray(x), x2=x2, wt=pack_rows(W, c["w_rows"], c["ldw"]), res=res, scale=m["scale"][:N], shift=m["shift"][:N], acc=acc)
+
+
+def reference(c, inp):
+    """row-major float64 [M, N]"""
+    return epilogue(inp["acc"], inp["scale"], inp["shift"], None if inp["res"] is None else inp["res"][: c["M"], : c["N"]], c["relu"])
+
+
+def float32_restatement(c, inp):
+    """the same computation carried out in float32 NumPy on the packed operands: what an fp32 kernel can be asked to reach"""
+    M, N, K = c["M"], c["N"], c["K"]
+    Wt = inp["wt"][:N, :K]
+    if c["mode"] == DENSE:
+        A = inp["x"][:, :K]
+    elif c["mode"] == STRIDED:
+        A = gather_strided(inp["x"], c["Ho"], c["Wo"], c["stride"])
+    elif c["mode"] == CONV3:
+        B, H, W, C = inp["x"].shape
+        xp = np.zeros((B, H + 2, W + 2, C), np.float32)
+        xp[:, 1 : H + 1, 1 : W + 1] = inp["x"]
+        A = np.concatenate([xp[:, kh : kh + H, kw : kw + W].reshape(M, C) for kh in range(3) for kw in range(3)], axis=1)
+    else:
+        A = np.concatenate([inp["x"][:, : c["k1_slabs"] * BK], gather_strided(inp["x2"], c["Ho"], c["Wo"], c["stride"])], axis=1)
+    y = (A.astype(np.float32) @ Wt.T.astype(np.float32)) * inp["scale"] + inp["shift"]
+    if inp["res"] is not None:
+        y = y + inp["res"][:M, :N]
+    assert y.dtype == np.float32
+    return np.maximum(y, 0) if c["relu"] else y

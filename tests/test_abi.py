@@ -49,6 +49,33 @@ def test_config_struct_matches_header(lib):
     assert all(getattr(cfg, k) == -1 for k in _lib.PLAN_OPTIONS)
 
 
+def test_debug_gemm_struct_matches_header(lib):
+    """HpeDebugGemm (hpe_debug_gemm_ex): the ctypes mirror has the header's fields in the header's order and types, 22 ints then 8
+    pointers with no padding between them; the call checks struct_size before it reads anything else and needs no GPU to refuse."""
+    import ctypes as C
+
+    txt = open(os.path.join(ROOT, "include", "hpe.h")).read()
+    body = txt[txt.index("typedef struct HpeDebugGemm {") + len("typedef struct HpeDebugGemm {"):txt.index("} HpeDebugGemm;")]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = []
+    for decl in body.split(";"):
+        m = re.match(r"\s*(const float\*|float\*|int\*|int)\s+(.+)$", decl.strip(), flags=re.S)
+        if m:
+            fields += [(n.strip(), m.group(1)) for n in m.group(2).split(",")]
+    assert [n for n, _ in fields] == [f[0] for f in _lib.HpeDebugGemm._fields_]
+    for (n, ctype), (_, py) in zip(fields, _lib.HpeDebugGemm._fields_):
+        assert (py is C.c_int) == (ctype == "int"), n
+        assert C.sizeof(py) == (4 if ctype == "int" else 8), n
+    n_int = sum(1 for _, t in fields if t == "int")
+    assert fields[0][0] == "struct_size" and n_int % 2 == 0 and C.sizeof(_lib.HpeDebugGemm) == 4 * n_int + 8 * (len(fields) - n_int)
+    for mode, name in ((_lib.GEMM_DENSE, "DENSE"), (_lib.GEMM_STRIDED, "STRIDED"), (_lib.GEMM_CONV3, "CONV3"), (_lib.GEMM_DUAL, "DUAL")):
+        assert re.search(r"#define HPE_GEMM_%s %d\b" % (name, mode), txt)
+    assert "hpe_debug_gemm_ex" in _lib.declared_symbols() and hasattr(lib, "hpe_debug_gemm_ex")
+    sk = C.c_int(7)
+    g = _lib.HpeDebugGemm(struct_size=C.sizeof(_lib.HpeDebugGemm), split_k=C.pointer(sk))
+    assert lib.hpe_debug_gemm_ex(None, C.byref(g), None) == 3 and sk.value == 0  # HPE_ERR_STATE: no context; the output is still defined
+
+
 def test_create_refuses_foreign_config_struct(lib):
     """hpe_create checks HpeConfig.struct_size before it reads anything else: a zero-initialised struct (hpe_config_init not called: every
     plan option would read 0 = the slowest plan) and a struct of another header revision (shorter: the library would read plan options
