@@ -26,7 +26,7 @@ from .engine import HpeEngine  # noqa: F401
 from .generator_train import GeneratorTrainer  # noqa: F401
 from .fit import fit_keypoints, fit_reprojection  # noqa: F401
 from .image import get_original, preprocess_batch, preprocess_image  # noqa: F401
-from .ops import critic_gradient_penalty, critic_scores, critic_wgan_loss, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas  # noqa: F401
+from .ops import critic_gradient_penalty, critic_scores, critic_wgan_loss, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas, encoder_features  # noqa: F401
 from .predictor import Predictor  # noqa: F401
 from .projection import batch_orth_proj_idrot, reproject_vertices  # noqa: F401
 from .render import SMPLRenderer  # noqa: F401

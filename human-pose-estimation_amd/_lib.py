@@ -169,6 +169,20 @@ _PROTOS = {
     "hpe_regressor_set_params_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_regressor_forward_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_regressor_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_encoder_param_floats": (C.c_int, []),
+    "hpe_encoder_param_offset": (C.c_int, [C.c_int, C.c_int]),
+    "hpe_encoder_train_reserve": (C.c_int, [C.c_void_p, C.c_int]),
+    "hpe_encoder_train_ws_floats": (C.c_longlong, [C.c_int]),
+    "hpe_encoder_wg_slices": (C.c_int, [C.c_int, C.c_int]),
+    "hpe_encoder_forward_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_encoder_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_encoder_get_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_encoder_set_params": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hpe_debug_conv_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_debug_maxpool_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_debug_avgpool_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_debug_encoder_stash": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_debug_encoder_stash_batch": (C.c_int, [C.c_void_p]),
     "hpe_device_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hpe_debug_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

@@ -100,3 +100,22 @@ class RegressorFunction(torch.autograd.Function):
         gflat, gfeat = ctx.engine.regressor_backward(features, grad_thetas.to(torch.float32).contiguous(), drop,
                                                      want_grad_features=ctx.needs_input_grad[1])
         return None, gfeat, gflat if ctx.needs_input_grad[2] else None, None
+
+
+class EncoderFunction(torch.autograd.Function):
+    """features [B,2048] = hpe_encoder_forward_train(images; the engine's live encoder, BatchNorm statistics fixed), differentiable in
+    ``params`` -- the flat tensor the optimiser owns, which must EQUAL what the engine holds (``set_encoder_params`` after every step):
+    it carries ``.grad``, the arithmetic reads the engine's weights.  Images get no gradient.  hpe_encoder_backward is stateless, so only
+    the images are saved."""
+
+    @staticmethod
+    def forward(ctx, engine, images, params):
+        ctx.engine = engine
+        ctx.save_for_backward(images.detach())
+        return engine.encoder_forward_train(images)
+
+    @staticmethod
+    def backward(ctx, grad_features):
+        (images,) = ctx.saved_tensors
+        g = ctx.engine.encoder_backward(images, grad_features.to(torch.float32).contiguous()) if ctx.needs_input_grad[2] else None
+        return None, None, g

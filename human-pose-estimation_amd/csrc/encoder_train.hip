@@ -1,0 +1,722 @@
+// encoder_train.hip -- fine-tuning the ResNet-50 encoder with the BatchNorm statistics held fixed (Keras' frozen-BN mode; the generator
+// update of src/trainer.py:481 puts image_feature_extractor.trainable_variables into the Adam step): the layer-by-layer training forward
+// that keeps every activation, the backward to the flat parameters, and the flat <-> live parameter copies.
+//
+// Per conv layer, with s = gamma / sqrt(var + eps):   y = act(s * (conv(x, W) + b - mean) + beta (+ residual))
+//
+//   dz = dy * [y > 0]          (enc_gate_kernel; TensorFlow's ReLU gradient, zero at 0; also writes dz * s, the data-gradient operand)
+//   G  = A^T dz                (conv_wg_gemm_kernel + conv_wg_fixup_kernel; A = the gathered im2col of x)
+//   dW = s * G    dshift = sum_m dz    dbeta = dshift    db = s * dshift    dgamma = (<W[:,n], G[:,n]> + (b - mean) * dshift) / sqrt(var + eps)
+//   dx = (dz * s) . W^T        (the implicit-GEMM launcher of the forward: dense for 1x1, CONV3 with the flipped, channel-transposed kernel for
+//                               3x3; a 1x1 / stride 2 layer runs the dense GEMM on the low-resolution map, enc_scatter2_kernel spreads it)
+//
+// sum_m dz * conv_raw = sum_k W[k][n] G[k][n] exactly, so the BatchNorm gradient needs neither the pre-BN tensor nor a division by s.
+//
+// conv_wg_gemm_kernel: G[k][n] = sum_m A[m][k] dz[m][n] on v_mfma_f32_32x32x2_f32.  For a fixed pixel m both A[m][.] (channels of one tap,
+// NHWC) and dz[m][.] are contiguous, so every lane reads its operand straight from global memory in one coalesced dword load per pixel --
+// no LDS, no transposed copy.  One wave per workgroup owns a 64 x 64 tile of G (four accumulators: two A and two B loads feed four MFMAs)
+// over one slice of the pixel axis; the grid is (tile, slice), so a 64 x 64 output over B * 56 * 56 pixels still fills the device.  Each
+// slice writes its partial tile; conv_wg_fixup_kernel adds the slices in ascending order, writes dW and the per-64-row partial sums of
+// <W, G>; conv_wg_finish_kernel adds those and the per-slice column sums of dz in ascending order.  No atomics anywhere: the same inputs
+// give the same bits.  Rows past M, taps outside the map and columns past K / N are masked to zero and never read.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "hpe_ctx.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int POOL_FLOATS = 56 * 56 * 64;  // the max-pooled map, per image
+constexpr int MAX_SLICES = 128;            // pixel slices of one weight gradient (what the fix-up adds per element)
+constexpr int WGP_FLOATS = 1152 * 512;     // <W, G> per 4-row chunk: K / 4 x N of the largest kernel (3x3, 512 -> 512)
+constexpr int BIG = 802816, MID = 200704;  // the largest layer output / the largest bottleneck (and low-resolution) map, per image
+
+struct WgArgs {
+    const float* x;   // the layer's input, NHWC [B][Hi][Wi][Cin]
+    const float* dz;  // [M][N]
+    float* part;      // [slices][K][N]
+    float* dsh;       // [slices][N] column sums of dz
+    int M, K, N;
+    int Hi, Wi, Cin, Ho, Wo, kw, stride, pad;
+    int P;     // pixels per slice, a multiple of 8
+    int n_nt;  // tiles along N
+};
+
+__global__ __launch_bounds__(64) void conv_wg_gemm_kernel(WgArgs a) {
+    const int lane = threadIdx.x, hi = lane >> 5, l31 = lane & 31;
+    const int kt = blockIdx.x / a.n_nt, nt = blockIdx.x - kt * a.n_nt, slice = blockIdx.y;
+    const int k0 = kt * 64, n0 = nt * 64;
+    // lane l feeds A[row = l & 31][k = l >> 5] and B[k = l >> 5][col = l & 31]: pixel m + hi of x and of dz
+    int kh[2], kwi[2];
+    long koff[2];
+    bool kok[2], nok[2];
+    int col[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int k = k0 + 32 * i + l31;
+        kok[i] = k < a.K;
+        const int tap = k / a.Cin, c = k - tap * a.Cin;
+        kh[i] = tap / a.kw;
+        kwi[i] = tap - kh[i] * a.kw;
+        koff[i] = ((long)kh[i] * a.Wi + kwi[i]) * a.Cin + c;
+        col[i] = n0 + 32 * i + l31;
+        nok[i] = col[i] < a.N;
+    }
+    const int m_end = min(a.M, (slice + 1) * a.P);
+    int m = slice * a.P + hi;
+    int b = m / (a.Ho * a.Wo);
+    int r = m - b * (a.Ho * a.Wo);
+    int ho = r / a.Wo, wo = r - ho * a.Wo;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    float bs[2] = {0.f, 0.f};
+    for (int it = 0; it < a.P; it += 8) {  // four steps of two pixels, all 16 loads issued before the first MFMA
+        float av[4][2], bv[4][2];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool live = m < m_end;
+            const int h0 = ho * a.stride - a.pad, w0 = wo * a.stride - a.pad;
+            const long base = (((long)b * a.Hi + h0) * a.Wi + w0) * a.Cin;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const bool in = live && kok[i] && (unsigned)(h0 + kh[i]) < (unsigned)a.Hi && (unsigned)(w0 + kwi[i]) < (unsigned)a.Wi;
+                av[u][i] = in ? a.x[base + koff[i]] : 0.f;
+                bv[u][i] = (live && nok[i]) ? a.dz[(long)m * a.N + col[i]] : 0.f;
+            }
+            m += 2;
+            wo += 2;
+            if (wo >= a.Wo) {  // Wo >= 2 (weight_grad refuses anything else): one wrap per step
+                wo -= a.Wo;
+                if (++ho >= a.Ho) {
+                    ho = 0;
+                    ++b;
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][i], bv[u][j], acc[i][j], 0, 0, 0);
+            bs[0] += bv[u][0];
+            bs[1] += bv[u][1];
+        }
+    }
+    // accumulator element e of lane l: row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31
+    float* part = a.part + (size_t)slice * a.K * a.N;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (!nok[j]) continue;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = k0 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * hi;
+                if (row < a.K) part[(size_t)row * a.N + col[j]] = acc[i][j][e];
+            }
+        }
+    if (kt == 0) {  // workgroup-uniform: the first tile row also owns the column sums of dz (even + odd pixels)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float other = __shfl_xor(bs[j], 32, 64);
+            if (hi == 0 && nok[j]) a.dsh[(size_t)slice * a.N + col[j]] = bs[j] + other;
+        }
+    }
+}
+
+// G = sum over the slices (ascending, four loads in flight); dW = s * G; wgp[kc][n] = sum over the 4 rows of chunk kc of W * G (row
+// 0 + 1 + 2 + 3).  One thread per element of G: grid (N / 64, K / 4) rounded up, 256 threads = 64 columns x 4 rows
+__global__ __launch_bounds__(256) void conv_wg_fixup_kernel(const float* __restrict__ part, int slices, int K, int N, const float* __restrict__ W,
+                                                            const float* __restrict__ s, float* __restrict__ dW, float* __restrict__ wgp) {
+    __shared__ float red[4][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int n = blockIdx.x * 64 + tx, k = blockIdx.y * 4 + ty;
+    float acc = 0.f;
+    if (n < N && k < K) {
+        const size_t o = (size_t)k * N + n, kn = (size_t)K * N;
+        float g = 0.f;
+        int sl = 0;
+        for (; sl + 4 <= slices; sl += 4) {
+            const float p0 = part[(size_t)sl * kn + o], p1 = part[(size_t)(sl + 1) * kn + o], p2 = part[(size_t)(sl + 2) * kn + o],
+                        p3 = part[(size_t)(sl + 3) * kn + o];
+            g = (((g + p0) + p1) + p2) + p3;
+        }
+        for (; sl < slices; ++sl) g += part[(size_t)sl * kn + o];
+        dW[o] = s[n] * g;
+        acc = W[o] * g;
+    }
+    red[ty][tx] = acc;
+    __syncthreads();
+    if (ty == 0 && n < N) wgp[(size_t)blockIdx.y * N + n] = ((red[0][tx] + red[1][tx]) + red[2][tx]) + red[3][tx];
+}
+
+// <W, G> = sum over the kc chunks, dshift = sum over the slices: four interleaved partial sums per column, each ascending, then
+// 0 + 1 + 2 + 3.  grid N / 64 rounded up, 256 threads = 64 columns x 4 groups
+__global__ __launch_bounds__(256) void conv_wg_finish_kernel(const float* __restrict__ wgp, int kc, const float* __restrict__ dsh, int slices, int N,
+                                                             const float* __restrict__ bias, const float* __restrict__ mean,
+                                                             const float* __restrict__ istd, const float* __restrict__ s, float* __restrict__ db,
+                                                             float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    __shared__ float rw[4][64], rd[4][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int n = blockIdx.x * 64 + tx;
+    float wg = 0.f, d = 0.f;
+    if (n < N) {
+        for (int i = ty; i < kc; i += 4) wg += wgp[(size_t)i * N + n];
+        for (int i = ty; i < slices; i += 4) d += dsh[(size_t)i * N + n];
+    }
+    rw[ty][tx] = wg;
+    rd[ty][tx] = d;
+    __syncthreads();
+    if (ty != 0 || n >= N) return;
+    wg = ((rw[0][tx] + rw[1][tx]) + rw[2][tx]) + rw[3][tx];
+    d = ((rd[0][tx] + rd[1][tx]) + rd[2][tx]) + rd[3][tx];
+    dbeta[n] = d;
+    db[n] = s[n] * d;
+    dgamma[n] = (wg + (bias[n] - mean[n]) * d) * istd[n];
+}
+
+// dz = dy * [y > 0] (y == nullptr: no activation, dz = dy); dzs = dz * s[n].  dz / dzs may be nullptr; dz may alias dy.  n4 quads, N % 4 == 0
+__global__ __launch_bounds__(256) void enc_gate_kernel(const f32x4* dy, const f32x4* __restrict__ y, const float* __restrict__ s, f32x4* dz,
+                                                       f32x4* __restrict__ dzs, long n4, int N4) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    f32x4 v = dy[i];
+    if (y) {
+        const f32x4 a = y[i];
+        v.x = a.x > 0.f ? v.x : 0.f;
+        v.y = a.y > 0.f ? v.y : 0.f;
+        v.z = a.z > 0.f ? v.z : 0.f;
+        v.w = a.w > 0.f ? v.w : 0.f;
+    }
+    if (dz) dz[i] = v;
+    if (dzs) dzs[i] = v * reinterpret_cast<const f32x4*>(s)[i % N4];
+}
+
+// lo [B][H][H][C] -> hi [B][2H][2H][C]: the even pixels, zero elsewhere (the data gradient of a 1x1 / stride 2 convolution)
+__global__ __launch_bounds__(256) void enc_scatter2_kernel(const f32x4* __restrict__ lo, f32x4* __restrict__ hi, int B, int H, int C4) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * 4 * H * H * C4) return;
+    const int c = (int)(i % C4);
+    long r = i / C4;
+    const int w = (int)(r % (2 * H));
+    r /= 2 * H;
+    const int h = (int)(r % (2 * H)), b = (int)(r / (2 * H));
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (!(h & 1) && !(w & 1)) v = lo[(((long)b * H + (h >> 1)) * H + (w >> 1)) * C4 + c];
+    hi[i] = v;
+}
+
+// dx [B][HW][C] = dy [B][C] / HW
+__global__ __launch_bounds__(256) void enc_avgpool_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int B, int HW, int C) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * HW * C) return;
+    const int c = (int)(i % C), b = (int)(i / ((long)HW * C));
+    dx[i] = dy[(long)b * C + c] / (float)HW;
+}
+
+// MaxPooling2D(3, 2) over the zero-padded map: every cotangent goes to the first maximum of its window in row-major order, the pad
+// (value 0) taking part.  Gather form, no atomics: each input pixel looks at the (up to four) windows that hold it, in row-major order.
+__global__ __launch_bounds__(256) void enc_maxpool_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx, int B,
+                                                              int H, int C) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * H * H * C) return;
+    const int Ho = H / 2;
+    const int c = (int)(i % C);
+    long r = i / C;
+    const int w = (int)(r % H);
+    r /= H;
+    const int h = (int)(r % H), b = (int)(r / H);
+    float g = 0.f;
+    for (int ho = h / 2; ho <= (h + 1) / 2; ++ho) {
+        if (ho >= Ho) continue;
+        for (int wo = w / 2; wo <= (w + 1) / 2; ++wo) {
+            if (wo >= Ho) continue;
+            float best = 0.f;
+            int by = -2, bx = -2;
+            for (int dy_ = 0; dy_ < 3; ++dy_)
+                for (int dx_ = 0; dx_ < 3; ++dx_) {
+                    const int yy = 2 * ho - 1 + dy_, xx = 2 * wo - 1 + dx_;
+                    const bool in = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)H;
+                    const float v = in ? x[(((long)b * H + yy) * H + xx) * C + c] : 0.f;
+                    if ((dy_ == 0 && dx_ == 0) || v > best) {
+                        best = v;
+                        by = in ? yy : -2;
+                        bx = xx;
+                    }
+                }
+            if (by == h && bx == w) g += dy[(((long)b * Ho + ho) * Ho + wo) * C + c];
+        }
+    }
+    dx[i] = g;
+}
+
+inline dim3 grid1(long n) { return dim3((unsigned)((n + 255) / 256)); }
+
+struct Layout {
+    int off[HPE_NUM_CONV][4];
+    int stat[HPE_NUM_CONV];      // offset into the per-channel statistics arrays
+    size_t stash[HPE_NUM_CONV];  // per-image offset of the layer's output in the stash
+    size_t stash_pool, stash_per_image;
+    int total, channels;
+};
+
+const Layout& layout() {
+    static const Layout L = [] {
+        Layout l{};
+        int o = 0, ch = 0;
+        size_t so = 0;
+        for (int i = 0; i < HPE_NUM_CONV; ++i) {
+            const ConvSpec& s = specs()[i];
+            l.off[i][0] = o;
+            o += s.kh * s.kw * s.cin * s.cout;
+            for (int w = 1; w < 4; ++w) {
+                l.off[i][w] = o;
+                o += s.cout;
+            }
+            l.stat[i] = ch;
+            ch += s.cout;
+            l.stash[i] = so;
+            so += (size_t)s.hout * s.hout * s.cout;
+        }
+        l.stash_pool = so;
+        l.stash_per_image = so + POOL_FLOATS;
+        l.total = o;
+        l.channels = ch;
+        return l;
+    }();
+    return L;
+}
+
+// pixels per slice and the slice count of layer idx at batch B: about 2048 single-wave workgroups on the device, at least 256 pixels a slice
+void wg_slicing(int idx, int B, int* P, int* slices) {
+    const ConvSpec& s = specs()[idx];
+    const int K = s.kh * s.kw * s.cin, M = B * s.hout * s.hout;
+    const int tiles = ((K + 63) / 64) * ((s.cout + 63) / 64);
+    int sl = std::min((M + 255) / 256, std::max(1, 2048 / tiles));
+    sl = std::min(sl, MAX_SLICES);
+    *P = round_up((M + sl - 1) / sl, 8);
+    *slices = (M + *P - 1) / *P;
+}
+
+// the partial buffer for every batch up to B: sized from the slice count before P is rounded to a multiple of 8, which is monotone in the
+// batch and never below the count wg_slicing ends with (the rounded count is not monotone in the batch: a larger P can leave fewer slices)
+size_t partial_floats(int B) {
+    size_t need = 0;
+    for (int i = 0; i < HPE_NUM_CONV; ++i) {
+        const ConvSpec& s = specs()[i];
+        const int K = s.kh * s.kw * s.cin, M = B * s.hout * s.hout;
+        const int tiles = ((K + 63) / 64) * ((s.cout + 63) / 64);
+        const int sl = std::min(std::min((M + 255) / 256, std::max(1, 2048 / tiles)), MAX_SLICES);
+        need = std::max(need, (size_t)sl * K * s.cout);
+    }
+    return need;
+}
+
+size_t dxw_floats(int idx) {
+    const ConvSpec& s = specs()[idx];
+    return idx == 0 ? 0 : (size_t)round_up(s.cin, 128) * s.kh * s.kw * s.cout;
+}
+
+size_t ws_floats(int B) {
+    size_t n = (size_t)B * layout().stash_per_image + (size_t)B * (3 * (size_t)BIG + 3 * (size_t)MID) + partial_floats(B);
+    n += (size_t)MAX_SLICES * 2048 + (size_t)WGP_FLOATS;  // column sums of dz per slice, <W, G> per 64-row chunk
+    for (int i = 0; i < HPE_NUM_CONV; ++i) n += dxw_floats(i);
+    return n + layout().total + 2 * layout().channels + 2048 + (size_t)B * HPE_FEATURE_DIM;
+}
+
+// the data-gradient operand of layer idx in the forward GEMM's Wt[n][k] form: rows = input channels (zero padded to 128), k = output channels
+// (1x1: the HWIO matrix itself) or (tap', output channel) with the taps flipped (3x3)
+void pack_dx_weights(int idx, const float* kernel, std::vector<float>& out) {
+    const ConvSpec& s = specs()[idx];
+    const int taps = s.kh * s.kw, K = taps * s.cout;
+    out.assign(dxw_floats(idx), 0.f);
+    for (int t = 0; t < taps; ++t)
+        for (int ci = 0; ci < s.cin; ++ci) {
+            const float* src = kernel + ((size_t)t * s.cin + ci) * s.cout;
+            std::copy(src, src + s.cout, out.begin() + (size_t)ci * K + (size_t)(taps - 1 - t) * s.cout);
+        }
+}
+
+// one forward layer as hpe_debug_conv launches it
+hipError_t train_conv(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st) {
+    if (!res && (use_wino_fused(c, idx, B) || use_wino4_fused(c, idx, B))) {
+        const ConvSpec& s = specs()[idx];
+        HIPE(hpe_launch_nhwc_to_slab8(x, c->T1, (long)B * s.hin * s.hin, s.cin, st));
+        return run_conv(c, idx, c->T1, B, nullptr, relu, y, st, nullptr, 0, CONV_IN_SLAB8);
+    }
+    return run_conv(c, idx, x, B, res, relu, y, st, c->wino_v);
+}
+
+void gate(const float* dy, const float* y, const float* s, float* dz, float* dzs, long n, int N, hipStream_t st) {
+    hipLaunchKernelGGL(enc_gate_kernel, grid1(n / 4), dim3(256), 0, st, reinterpret_cast<const f32x4*>(dy), reinterpret_cast<const f32x4*>(y), s,
+                       reinterpret_cast<f32x4*>(dz), reinterpret_cast<f32x4*>(dzs), n / 4, N / 4);
+}
+
+// the weight gradient of layer idx and what hangs on it, into grad_layer = [kernel | bias | gamma | beta]: three launches
+hipError_t weight_grad(hpe_ctx* c, int idx, const float* x, const float* dz, int B, float* grad_layer, hipStream_t st) {
+    const ConvSpec& s = specs()[idx];
+    EncTrainWork& w = c->et;
+    const Layout& l = layout();
+    WgArgs a{};
+    a.x = x;
+    a.dz = dz;
+    a.part = w.partial;
+    a.dsh = w.dsh;
+    a.M = B * s.hout * s.hout;
+    a.K = s.kh * s.kw * s.cin;
+    a.N = s.cout;
+    a.Hi = a.Wi = s.hin;
+    a.Cin = s.cin;
+    a.Ho = a.Wo = s.hout;
+    a.kw = s.kw;
+    a.stride = s.stride;
+    a.pad = (s.kh - 1) / 2;
+    int slices;
+    wg_slicing(idx, B, &a.P, &slices);
+    a.n_nt = (a.N + 63) / 64;
+    const int n_kt = (a.K + 63) / 64, n_kc = (a.K + 3) / 4;
+    if ((size_t)slices * a.K * a.N > w.partial_floats || slices > MAX_SLICES || (size_t)n_kc * a.N > WGP_FLOATS) return hipErrorInvalidValue;
+    // the kernel's pixel walk steps two pixels with at most one row wrap, and a slice is whole groups of eight pixels
+    if (a.Wo < 2 || a.P < 8 || a.P % 8 != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(conv_wg_gemm_kernel, dim3(n_kt * a.n_nt, slices), dim3(64), 0, st, a);
+    const float* flat = w.flat;
+    const int kn = a.K * a.N;
+    hipLaunchKernelGGL(conv_wg_fixup_kernel, dim3(a.n_nt, n_kc), dim3(256), 0, st, w.partial, slices, a.K, a.N, flat + l.off[idx][0],
+                       c->conv[idx].scale, grad_layer, w.wgp);
+    hipLaunchKernelGGL(conv_wg_finish_kernel, dim3(a.n_nt), dim3(256), 0, st, w.wgp, n_kc, w.dsh, slices, a.N, flat + l.off[idx][1],
+                       w.mean + l.stat[idx], w.istd + l.stat[idx], c->conv[idx].scale, grad_layer + kn, grad_layer + kn + a.N,
+                       grad_layer + kn + 2 * a.N);
+    return hipGetLastError();
+}
+
+// out [M][cin] = dzs [M][cout] . W^T (+ res) on the map of the layer's OUTPUT (a stride-2 layer: the low-resolution map)
+hipError_t data_grad(hpe_ctx* c, int idx, const float* dzs, int B, const float* res, float* out, hipStream_t st) {
+    const ConvSpec& s = specs()[idx];
+    GemmArgs p{};
+    p.x = dzs;
+    p.w = c->et.dxw[idx];
+    p.scale = c->ones;
+    p.shift = c->et.zeros;
+    p.res = res;
+    p.y = out;
+    p.M = B * s.hout * s.hout;
+    p.N = s.cin;
+    p.K = s.kh * s.kw * s.cout;
+    p.lda = s.cout;
+    p.ldw = p.K;
+    p.w_rows = round_up(s.cin, 128);
+    p.ldy = p.ldres = s.cin;
+    p.Hi = p.Wi = p.Ho = p.Wo = s.hout;
+    p.Cin = s.cout;
+    p.stride = 1;
+    p.cin_slabs = s.cout / 32;
+    p.zero = c->zeros;
+    p.partial = c->partial;
+    p.partial_floats = c->partial_floats;
+    return hpe_launch_gemm(p, s.kh == 3 ? GEMM_CONV3 : GEMM_DENSE, pick_tile(c->plan, p.M, p.N, p.K), c->plan.splitk_min_slabs, st);
+}
+
+void scatter2(const float* lo, float* hi, int B, int H, int C, hipStream_t st) {
+    hipLaunchKernelGGL(enc_scatter2_kernel, grid1((long)B * 4 * H * H * (C / 4)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(lo),
+                       reinterpret_cast<f32x4*>(hi), B, H, C / 4);
+}
+
+float* stash_of(hpe_ctx* c, int idx, int B) {
+    const Layout& l = layout();
+    return c->et.stash + (size_t)B * (idx < 0 ? l.stash_pool : l.stash[idx]);
+}
+
+hipError_t forward_train(hpe_ctx* c, const float* images, int B, float* features, hipStream_t st) {
+    HIPE(hpe_launch_pad_input(images, c->padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
+    HIPE(run_conv(c, 0, c->padded, B, nullptr, 1, stash_of(c, 0, B), st));
+    HIPE(hpe_launch_maxpool(stash_of(c, 0, B), stash_of(c, -1, B), B, 112, 64, st));
+    const float* cur = stash_of(c, -1, B);
+    const int nblk[4] = {3, 4, 6, 3};
+    int ci = 1;
+    for (int stg = 0; stg < 4; ++stg)
+        for (int b = 0; b < nblk[stg]; ++b) {
+            const bool first = b == 0;
+            const int i2a = ci, i2b = ci + 1, i2c = ci + 2, i1 = ci + 3;
+            HIPE(train_conv(c, i2a, cur, B, nullptr, 1, stash_of(c, i2a, B), st));
+            HIPE(train_conv(c, i2b, stash_of(c, i2a, B), B, nullptr, 1, stash_of(c, i2b, B), st));
+            const float* res = cur;
+            if (first) {
+                HIPE(train_conv(c, i1, cur, B, nullptr, 0, stash_of(c, i1, B), st));
+                res = stash_of(c, i1, B);
+            }
+            HIPE(train_conv(c, i2c, stash_of(c, i2b, B), B, res, 1, stash_of(c, i2c, B), st));
+            cur = stash_of(c, i2c, B);
+            ci += first ? 4 : 3;
+        }
+    return hpe_launch_avgpool(cur, features, B, 49, HPE_FEATURE_DIM, HPE_FEATURE_DIM, st);
+}
+
+hipError_t backward(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, hipStream_t st) {
+    EncTrainWork& w = c->et;
+    const Layout& l = layout();
+    HIPE(forward_train(c, images, B, w.feat, st));
+    float *g = w.g0, *go = w.g1;
+    hipLaunchKernelGGL(enc_avgpool_bwd_kernel, grid1((long)B * 49 * HPE_FEATURE_DIM), dim3(256), 0, st, grad_features, g, B, 49, HPE_FEATURE_DIM);
+    const int nblk[4] = {3, 4, 6, 3};
+    int first_idx[16], n_blocks = 0, ci = 1;
+    bool is_first[16];
+    for (int stg = 0; stg < 4; ++stg)
+        for (int b = 0; b < nblk[stg]; ++b) {
+            is_first[n_blocks] = b == 0;
+            first_idx[n_blocks++] = ci;
+            ci += b == 0 ? 4 : 3;
+        }
+    for (int k = n_blocks - 1; k >= 0; --k) {
+        const int i2a = first_idx[k], i2b = i2a + 1, i2c = i2a + 2, i1 = i2a + 3;
+        const bool first = is_first[k];
+        const ConvSpec &sa = specs()[i2a], &sb = specs()[i2b], &sc = specs()[i2c];
+        const float* xin = stash_of(c, k == 0 ? -1 : first_idx[k - 1] + 2, B);  // the block's input: the previous block's branch2c output
+        const long Mo = (long)B * sc.hout * sc.hout;
+        // branch2c: g becomes dz (the cotangent of the shortcut too)
+        gate(g, stash_of(c, i2c, B), c->conv[i2c].scale, g, w.sbig, Mo * sc.cout, sc.cout, st);
+        HIPE(weight_grad(c, i2c, stash_of(c, i2b, B), g, B, grad_flat + l.off[i2c][0], st));
+        HIPE(data_grad(c, i2c, w.sbig, B, nullptr, w.t0, st));
+        gate(w.t0, stash_of(c, i2b, B), c->conv[i2b].scale, w.t0, w.ssmall, Mo * sb.cout, sb.cout, st);
+        HIPE(weight_grad(c, i2b, stash_of(c, i2a, B), w.t0, B, grad_flat + l.off[i2b][0], st));
+        HIPE(data_grad(c, i2b, w.ssmall, B, nullptr, w.t1, st));
+        gate(w.t1, stash_of(c, i2a, B), c->conv[i2a].scale, w.t1, w.ssmall, Mo * sa.cout, sa.cout, st);
+        HIPE(weight_grad(c, i2a, xin, w.t1, B, grad_flat + l.off[i2a][0], st));
+        if (!first) {
+            HIPE(data_grad(c, i2a, w.ssmall, B, g, go, st));
+            std::swap(g, go);
+            continue;
+        }
+        // projection shortcut: no activation of its own, its dz is the block's
+        gate(g, nullptr, c->conv[i1].scale, nullptr, w.sbig, Mo * sc.cout, sc.cout, st);
+        HIPE(weight_grad(c, i1, xin, g, B, grad_flat + l.off[i1][0], st));
+        if (sa.stride == 1) {
+            HIPE(data_grad(c, i2a, w.ssmall, B, nullptr, go, st));
+            HIPE(data_grad(c, i1, w.sbig, B, go, g, st));
+        } else {
+            HIPE(data_grad(c, i2a, w.ssmall, B, nullptr, w.t0, st));
+            HIPE(data_grad(c, i1, w.sbig, B, w.t0, w.t1, st));
+            scatter2(w.t1, go, B, sa.hout, sa.cin, st);
+            std::swap(g, go);
+        }
+    }
+    hipLaunchKernelGGL(enc_maxpool_bwd_kernel, grid1((long)B * 112 * 112 * 64), dim3(256), 0, st, stash_of(c, 0, B), g, go, B, 112, 64);
+    gate(go, stash_of(c, 0, B), nullptr, go, nullptr, (long)B * BIG, 64, st);
+    return weight_grad(c, 0, images, go, B, grad_flat + l.off[0][0], st);
+}
+
+int check_train(hpe_ctx* c, int B, bool need_reserve = true) {
+    if (!c) return fail(HPE_ERR_INVALID, "null ctx");
+    if (c->dead) return fail(HPE_ERR_STATE, "hpe_finalize failed on this ctx: destroy it and create a new one");
+    if (!c->finalized) return fail(HPE_ERR_STATE, "hpe_finalize() has not been called");
+    if (!c->have_encoder) return fail(HPE_ERR_STATE, "encoder weights were not loaded before hpe_finalize");
+    if (c->bf16) return fail(HPE_ERR_STATE, "encoder training needs an fp32 context");
+    if (need_reserve && c->et.B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve() has not been called");
+    if (B < 1 || B > (need_reserve ? c->et.B : c->cfg.max_batch))
+        return fail(HPE_ERR_INVALID, "batch " + std::to_string(B) + (need_reserve ? " outside [1, reserved batch]" : " outside [1, max_batch]"));
+    return HPE_OK;
+}
+
+// host flat -> the data-gradient packings and the flat device copy (buffers exist)
+int upload_train_params(hpe_ctx* c, const float* flat) {
+    const Layout& l = layout();
+    std::vector<float> dx;
+    for (int i = 1; i < HPE_NUM_CONV; ++i) {
+        pack_dx_weights(i, flat + l.off[i][0], dx);
+        HIP_TRY(hipMemcpy(c->et.dxw[i], dx.data(), dx.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(c->et.flat, flat, (size_t)l.total * sizeof(float), hipMemcpyHostToDevice));
+    return HPE_OK;
+}
+
+}  // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int hpe_encoder_param_floats(void) { return layout().total; }
+
+int hpe_encoder_param_offset(int idx, int which) {
+    if (idx < 0 || idx >= HPE_NUM_CONV || which < 0 || which > 3) return -1;
+    return layout().off[idx][which];
+}
+
+long long hpe_encoder_train_ws_floats(int B) { return B < 1 ? 0 : (long long)ws_floats(B); }
+
+int hpe_encoder_wg_slices(int idx, int B) {
+    if (idx < 0 || idx >= HPE_NUM_CONV || B < 1) return -1;
+    int P, sl;
+    wg_slicing(idx, B, &P, &sl);
+    return sl;
+}
+
+int hpe_encoder_train_reserve(hpe_ctx* c, int B) {
+    int rc = check_train(c, B, false);
+    if (rc) return rc;
+    EncTrainWork& w = c->et;
+    if (w.B != 0) return B <= w.B ? HPE_OK : fail(HPE_ERR_STATE, "hpe_encoder_train_reserve: already reserved for a smaller batch");
+    DeviceGuard g(c->cfg.device);
+    const Layout& l = layout();
+    const size_t nb = (size_t)B;
+    if ((rc = dev_alloc(c, &w.stash, nb * l.stash_per_image, false))) return rc;
+    if ((rc = dev_alloc(c, &w.g0, nb * BIG, false))) return rc;
+    if ((rc = dev_alloc(c, &w.g1, nb * BIG, false))) return rc;
+    if ((rc = dev_alloc(c, &w.sbig, nb * BIG, false))) return rc;
+    if ((rc = dev_alloc(c, &w.t0, nb * MID, false))) return rc;
+    if ((rc = dev_alloc(c, &w.t1, nb * MID, false))) return rc;
+    if ((rc = dev_alloc(c, &w.ssmall, nb * MID, false))) return rc;
+    w.partial_floats = partial_floats(B);
+    if ((rc = dev_alloc(c, &w.partial, w.partial_floats, false))) return rc;
+    if ((rc = dev_alloc(c, &w.dsh, (size_t)MAX_SLICES * 2048, false))) return rc;
+    if ((rc = dev_alloc(c, &w.wgp, (size_t)WGP_FLOATS, false))) return rc;
+    if ((rc = dev_alloc(c, &w.zeros, 2048, true))) return rc;
+    if ((rc = dev_alloc(c, &w.feat, nb * HPE_FEATURE_DIM, false))) return rc;
+    if ((rc = dev_alloc(c, &w.flat, l.total, false))) return rc;
+    if ((rc = dev_alloc(c, &w.mean, l.channels, false))) return rc;
+    if ((rc = dev_alloc(c, &w.istd, l.channels, false))) return rc;
+    for (int i = 1; i < HPE_NUM_CONV; ++i)
+        if ((rc = dev_alloc(c, &w.dxw[i], dxw_floats(i), false))) return rc;
+    // the flat parameters: hpe_finalize released the host kernels, so they come back from the packed device weights Wt[n][k] (fp32: exact)
+    std::vector<float> flat(l.total), mean(l.channels), istd(l.channels), wt;
+    HIP_TRY(hipDeviceSynchronize());
+    for (int i = 0; i < HPE_NUM_CONV; ++i) {
+        const ConvSpec& s = specs()[i];
+        const ConvLayer& L = c->conv[i];
+        wt.resize((size_t)L.n_pad * L.k_pad);
+        HIP_TRY(hipMemcpy(wt.data(), L.w, wt.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (int kh = 0; kh < s.kh; ++kh)
+            for (int kw = 0; kw < s.kw; ++kw)
+                for (int ci = 0; ci < s.cin; ++ci) {
+                    const int k = (i == 0) ? (kh * 32 + kw * 4 + ci) : ((kh * s.kw + kw) * s.cin + ci);
+                    float* dst = &flat[l.off[i][0] + (((size_t)kh * s.kw + kw) * s.cin + ci) * s.cout];
+                    for (int n = 0; n < s.cout; ++n) dst[n] = wt[(size_t)n * L.k_pad + k];
+                }
+        for (int n = 0; n < s.cout; ++n) {
+            flat[l.off[i][1] + n] = L.bias[n];
+            flat[l.off[i][2] + n] = L.gamma[n];
+            flat[l.off[i][3] + n] = L.beta[n];
+            mean[l.stat[i] + n] = L.mean[n];
+            istd[l.stat[i] + n] = (float)(1.0 / std::sqrt((double)L.var[n] + (double)c->cfg.bn_eps));
+        }
+    }
+    HIP_TRY(hipMemcpy(w.mean, mean.data(), mean.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.istd, istd.data(), istd.size() * sizeof(float), hipMemcpyHostToDevice));
+    if ((rc = upload_train_params(c, flat.data()))) return rc;
+    w.B = B;
+    return HPE_OK;
+}
+
+int hpe_encoder_forward_train(hpe_ctx* c, const float* images, int B, float* features, void* stream) {
+    int rc = check_train(c, B);
+    if (rc) return rc;
+    if (!images || !features) return fail(HPE_ERR_INVALID, "null pointer");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(forward_train(c, images, B, features, static_cast<hipStream_t>(stream)));
+    c->et.stash_B = B;
+    return HPE_OK;
+}
+
+int hpe_encoder_backward(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
+    int rc = check_train(c, B);
+    if (rc) return rc;
+    if (!images || !grad_features || !grad_flat) return fail(HPE_ERR_INVALID, "null pointer");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(backward(c, images, B, grad_features, grad_flat, static_cast<hipStream_t>(stream)));
+    c->et.stash_B = B;
+    return HPE_OK;
+}
+
+int hpe_encoder_get_params(hpe_ctx* c, float* flat, void* stream) {
+    int rc = check_train(c, 1);
+    if (rc) return rc;
+    if (!flat) return fail(HPE_ERR_INVALID, "null flat_dev");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(hipMemcpyAsync(flat, c->et.flat, (size_t)layout().total * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+int hpe_encoder_set_params(hpe_ctx* c, const float* flat) {
+    int rc = check_train(c, 1);
+    if (rc) return rc;
+    if (!flat) return fail(HPE_ERR_INVALID, "null flat_host");
+    DeviceGuard g(c->cfg.device);
+    const Layout& l = layout();
+    HIP_TRY(hipDeviceSynchronize());  // launches still reading the weights
+    for (int i = 0; i < HPE_NUM_CONV; ++i) {
+        const ConvSpec& s = specs()[i];
+        ConvLayer& L = c->conv[i];
+        L.kernel.assign(flat + l.off[i][0], flat + l.off[i][1]);
+        L.bias.assign(flat + l.off[i][1], flat + l.off[i][1] + s.cout);
+        L.gamma.assign(flat + l.off[i][2], flat + l.off[i][2] + s.cout);
+        L.beta.assign(flat + l.off[i][3], flat + l.off[i][3] + s.cout);
+    }
+    if ((rc = repack_encoder(c))) return rc;
+    if ((rc = upload_train_params(c, flat))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return HPE_OK;
+}
+
+int hpe_debug_conv_backward(hpe_ctx* c, int idx, const float* x, const float* y, const float* dy, int B, float* dx, float* grad_layer,
+                            void* stream) {
+    int rc = check_train(c, B);
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !dy || !grad_layer) return fail(HPE_ERR_INVALID, "bad argument");
+    if (idx == 0 && dx) return fail(HPE_ERR_INVALID, "hpe_debug_conv_backward: conv1 has no data gradient, dx_dev must be NULL");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ConvSpec& s = specs()[idx];
+    EncTrainWork& w = c->et;
+    const long n = (long)B * s.hout * s.hout * s.cout;
+    gate(dy, y, c->conv[idx].scale, w.g0, dx ? w.sbig : nullptr, n, s.cout, st);
+    HIP_TRY(weight_grad(c, idx, x, w.g0, B, grad_layer, st));
+    if (!dx) return HPE_OK;
+    if (s.stride == 1) {
+        HIP_TRY(data_grad(c, idx, w.sbig, B, nullptr, dx, st));
+    } else {
+        HIP_TRY(data_grad(c, idx, w.sbig, B, nullptr, w.t0, st));
+        scatter2(w.t0, dx, B, s.hout, s.cin, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return HPE_OK;
+}
+
+int hpe_debug_maxpool_backward(const float* x, const float* dy, int B, int H, int C, float* dx, void* stream) {
+    if (!x || !dy || !dx || B < 1 || H < 2 || (H & 1) || C < 1) return fail(HPE_ERR_INVALID, "bad argument");
+    hipLaunchKernelGGL(enc_maxpool_bwd_kernel, grid1((long)B * H * H * C), dim3(256), 0, static_cast<hipStream_t>(stream), x, dy, dx, B, H, C);
+    HIP_TRY(hipGetLastError());
+    return HPE_OK;
+}
+
+int hpe_debug_avgpool_backward(const float* dy, int B, int HW, int C, float* dx, void* stream) {
+    if (!dy || !dx || B < 1 || HW < 1 || C < 1) return fail(HPE_ERR_INVALID, "bad argument");
+    hipLaunchKernelGGL(enc_avgpool_bwd_kernel, grid1((long)B * HW * C), dim3(256), 0, static_cast<hipStream_t>(stream), dy, dx, B, HW, C);
+    HIP_TRY(hipGetLastError());
+    return HPE_OK;
+}
+
+int hpe_debug_encoder_stash_batch(hpe_ctx* c) { return (c && c->finalized && !c->dead) ? c->et.stash_B : 0; }
+
+int hpe_debug_encoder_stash(hpe_ctx* c, int idx, float* out, void* stream) {
+    int rc = check_train(c, 1);
+    if (rc) return rc;
+    if (idx < -1 || idx >= HPE_NUM_CONV || !out) return fail(HPE_ERR_INVALID, "bad argument");
+    const int B = c->et.stash_B;
+    if (B == 0) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash: no training forward has run");
+    DeviceGuard g(c->cfg.device);
+    const size_t n = idx < 0 ? (size_t)POOL_FLOATS : (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
+    HIP_TRY(hipMemcpyAsync(out, stash_of(c, idx, B), (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

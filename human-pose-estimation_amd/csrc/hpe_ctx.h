@@ -97,6 +97,25 @@ struct RegTrainWork {
     size_t partial_floats = 0;
 };
 
+// Encoder training (encoder_train.hip), allocated by hpe_encoder_train_reserve for B images: nothing of it exists in an inference context
+struct EncTrainWork {
+    int B = 0;        // reserved batch (0: not reserved)
+    int stash_B = 0;  // batch of the training forward that last filled the stash
+    float *flat = nullptr;   // the live parameters in the flat layout (kernel HWIO | bias | gamma | beta per layer)
+    float *mean = nullptr, *istd = nullptr;  // moving_mean and 1 / sqrt(moving_variance + eps) of every layer's channels, layer after layer
+    float *stash = nullptr;  // every layer's post-activation output, then the max-pooled map; layer-major, B images each
+    float *g0 = nullptr, *g1 = nullptr;  // [B][802816] block cotangents (ping-pong)
+    float *sbig = nullptr;   // [B][802816] dz * s of the wide layers (branch2c, branch1)
+    float *t0 = nullptr, *t1 = nullptr, *ssmall = nullptr;  // [B][200704] bottleneck cotangents / low-resolution data gradients / dz * s
+    float *partial = nullptr;  // [slices][K][N] of the weight gradient in flight
+    size_t partial_floats = 0;
+    float *dsh = nullptr;    // [128][2048] column sums of dz per slice
+    float *wgp = nullptr;    // <W, G> per 4-row chunk, [K / 4][N] of the layer in flight
+    float *zeros = nullptr;  // 2048 zeros (shift of the data-gradient GEMMs)
+    float *feat = nullptr;   // [B][2048] features of the backward's own forward
+    float *dxw[HPE_NUM_CONV] = {};  // data-gradient operands Wt[cin][k], beside the forward's packings
+};
+
 struct hpe_ctx {
     HpeConfig cfg{};
     bool finalized = false;
@@ -115,6 +134,7 @@ struct hpe_ctx {
     // device: regressor
     float *w1f = nullptr, *w1t = nullptr, *w2 = nullptr, *w3 = nullptr, *b1 = nullptr, *b2 = nullptr, *b3 = nullptr;
     float *ones = nullptr, *zeros = nullptr, *mean_dev = nullptr;
+    EncTrainWork et{};  // encoder training (encoder_train.hip)
     RegTrainWork rt{};  // regressor training (regressor_train.hip): Keras-major weight copies and a workspace of its own
     // device: SMPL
     SmplDev smpl{};
@@ -201,6 +221,9 @@ int check_ready(hpe_ctx* c, int B, int need);
 // hpe_finalize.hip
 int finalize_impl(hpe_ctx* c);
 void release_device_state(hpe_ctx* c);  // release everything a (possibly partial) hpe_finalize created
+// pack the conv layers again from their host staging (kernel / bias / gamma / beta refilled by the caller) into the device buffers
+// hpe_finalize allocated: no pointer changes.  Synchronous.
+int repack_encoder(hpe_ctx* c);
 
 // hpe_encoder.hip
 enum { CONV_OUT_SLAB8 = 1, CONV_IN_SLAB8 = 2, CONV_CONCURRENT = 4 };

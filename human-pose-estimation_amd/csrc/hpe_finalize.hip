@@ -29,6 +29,13 @@ int upload(hpe_ctx* c, float** p, const std::vector<float>& h) {
     return HPE_OK;
 }
 
+// upload(), or a copy into the buffer *p already names (repack_encoder: the pointers of a finalized context never change)
+static int upload_to(hpe_ctx* c, float** p, const std::vector<float>& h) {
+    if (!*p) return upload(c, p, h);
+    HIP_TRY(hipMemcpy(*p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return HPE_OK;
+}
+
 // fp32 Wt[rows][K] -> bf16 [rows][3][K]: w = w0 + w1 + w2 exactly (finite weights), each piece rounded to nearest even (conv_gemm_f32s.hip)
 int upload_split(hpe_ctx* c, void** p, const std::vector<float>& wt, int rows, int K) {
     std::vector<unsigned short> ws((size_t)rows * 3 * K);
@@ -50,9 +57,11 @@ int upload_split(hpe_ctx* c, void** p, const std::vector<float>& wt, int rows, i
             d[K] = h1;
             d[2 * K] = f2bf(r2);
         }
-    void* q = nullptr;
-    HIP_TRY(hipMalloc(&q, ws.size() * 2));
-    c->allocs.push_back(q);
+    void* q = *p;  // a buffer of an earlier call is written again (repack_encoder)
+    if (!q) {
+        HIP_TRY(hipMalloc(&q, ws.size() * 2));
+        c->allocs.push_back(q);
+    }
     HIP_TRY(hipMemcpy(q, ws.data(), ws.size() * 2, hipMemcpyHostToDevice));
     *p = q;
     return HPE_OK;
@@ -127,6 +136,7 @@ void release_device_state(hpe_ctx* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     c->allocs.clear();
     c->rt = RegTrainWork{};
+    c->et = EncTrainWork{};
     if (c->critic_buf) {
         (void)hipFree(c->critic_buf);
         c->critic_buf = nullptr;
@@ -222,11 +232,11 @@ static int pack_dual_weights(hpe_ctx* c) {
                 HIP_TRY(hipMemcpy(qd, wb.data(), wb.size() * 2, hipMemcpyHostToDevice));
                 L2.w_dual = static_cast<float*>(qd);
             } else {
-                if ((rc = upload(c, &L2.w_dual, wt))) return rc;
+                if ((rc = upload_to(c, &L2.w_dual, wt))) return rc;
                 // f32_split: the folded weight is split (the BN scales are inside the pieces)
                 if ((c->plan.f32_split & stage_bit(s2.hout)) && (rc = upload_split(c, &L2.w_dual_split, wt, n_pad, K))) return rc;
             }
-            if ((rc = upload(c, &L2.shift_dual, sh))) return rc;
+            if ((rc = upload_to(c, &L2.shift_dual, sh))) return rc;
             L2.k_dual = K;
             L2.k1_dual = K1;
         }
@@ -256,7 +266,7 @@ static int pack_wino_weights(hpe_ctx* c, const ConvSpec& s, ConvLayer& L) {
                     U[base + (size_t)(xi * 4 + nu) * 512] = (float)u;
                 }
         }
-    if ((rc = upload(c, &L.wino_u, U))) return rc;
+    if ((rc = upload_to(c, &L.wino_u, U))) return rc;
     return HPE_OK;
 }
 
@@ -283,7 +293,7 @@ static int pack_wino4_weights(hpe_ctx* c, const ConvSpec& s, ConvLayer& L) {
                     U[base + (size_t)(xi * 6 + nu) * 256] = (float)u;
                 }
         }
-    if ((rc = upload(c, &L.wino4_u, U))) return rc;
+    if ((rc = upload_to(c, &L.wino4_u, U))) return rc;
     return HPE_OK;
 }
 
@@ -307,8 +317,11 @@ static int pack_stem_weights(hpe_ctx* c, ConvLayer& L) {
                 for (int ci = 0; ci < 3; ++ci)
                     for (int n = 0; n < 64; ++n)
                         wp[(size_t)n * 160 + kh * 22 + 1 + kw * 3 + ci] = L.kernel[(((size_t)kh * 7 + kw) * 3 + ci) * 64 + n];
-        HIP_TRY(hipMalloc(&q, wp.size() * 4));
-        c->allocs.push_back(q);
+        q = L.stem_w;  // written again by repack_encoder
+        if (!q) {
+            HIP_TRY(hipMalloc(&q, wp.size() * 4));
+            c->allocs.push_back(q);
+        }
         HIP_TRY(hipMemcpy(q, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
     }
     L.stem_w = q;
@@ -348,7 +361,7 @@ static int pack_conv_weights(hpe_ctx* c) {
                     const float* src = &L.kernel[(((size_t)kh * s.kw + kw) * s.cin + ci) * s.cout];
                     for (int n = 0; n < s.cout; ++n) wt[(size_t)n * L.k_pad + k] = src[n];
                 }
-        if ((rc = upload(c, &L.w, wt))) return rc;
+        if ((rc = upload_to(c, &L.w, wt))) return rc;
         if (i != 0 && s.kh == 1 && (c->plan.f32_split & stage_bit(s.hout)) && (rc = upload_split(c, &L.w_split, wt, L.n_pad, L.k_pad))) return rc;
         if (c->plan.wino_min_c > 0 && s.kh == 3 && s.stride == 1 && s.cin % 32 == 0 && s.cout % 64 == 0 &&
             (s.cin >= c->plan.wino_min_c || (c->plan.wino_fused && s.hin >= c->plan.wino_fused_min_hw)) && (rc = pack_wino_weights(c, s, L)))
@@ -364,8 +377,8 @@ static int pack_conv_weights(hpe_ctx* c) {
             sc[n] = (float)inv;
             sh[n] = (float)(((double)L.bias[n] - (double)L.mean[n]) * inv + (double)L.beta[n]);
         }
-        if ((rc = upload(c, &L.scale, sc))) return rc;
-        if ((rc = upload(c, &L.shift, sh))) return rc;
+        if ((rc = upload_to(c, &L.scale, sc))) return rc;
+        if ((rc = upload_to(c, &L.shift, sh))) return rc;
         std::vector<float>().swap(L.kernel);
     }
     return HPE_OK;
@@ -570,6 +583,12 @@ static int create_streams_and_events(hpe_ctx* c) {
     for (auto& e : c->lev_all) HIP_TRY(hipEventCreate(&e));
     c->ev_ok = true;
     return HPE_OK;
+}
+
+int repack_encoder(hpe_ctx* c) {
+    int rc;
+    if (c->plan.dual_gemm && (rc = pack_dual_weights(c))) return rc;
+    return pack_conv_weights(c);
 }
 
 int finalize_impl(hpe_ctx* c) {

@@ -11,7 +11,7 @@ import numpy as np
 from . import _lib
 from .critic_spec import PARAM_FLOATS
 from .regressor_spec import PARAM_FLOATS as REGRESSOR_PARAM_FLOATS
-from .resnet_spec import CONV_SPECS
+from .resnet_spec import CONV_SPECS, ENCODER_PARAM_FLOATS
 
 NUM_VERTS = _lib.NUM_VERTS
 
@@ -644,6 +644,84 @@ class HpeEngine(object):
                                                    grad_thetas.data_ptr() if grad_thetas is not None else None, gflat.data_ptr(),
                                                    gfeat.data_ptr() if want_grad_features else None, self._stream()))
         return gflat, gfeat
+
+    # ------------------------------------------------------------------ encoder training (fp32 contexts, frozen BatchNorm statistics)
+    def reserve_encoder_train(self, B):
+        """hpe_encoder_train_reserve: allocate the stash, cotangent buffers, partial sums and data-gradient packings for batches up to B"""
+        _lib.check(self.lib.hpe_encoder_train_reserve(self._h, int(B)))
+
+    def encoder_params(self):
+        """hpe_encoder_get_params: the live kernels, biases, gammas and betas as one flat CUDA tensor [resnet_spec.ENCODER_PARAM_FLOATS]"""
+        out = self._new(ENCODER_PARAM_FLOATS)
+        _lib.check(self.lib.hpe_encoder_get_params(self._h, out.data_ptr(), self._stream()))
+        return out
+
+    def set_encoder_params(self, flat):
+        """hpe_encoder_set_params: replace the encoder's trainable parameters by ``flat`` (a tensor on any device or an array).  The host
+        packing runs again and is copied into the existing device buffers; synchronous, not capturable."""
+        torch = _torch()
+        if isinstance(flat, torch.Tensor):
+            flat = flat.detach().to("cpu", torch.float32).numpy()
+        arr, ptr = _lib.f32(np.asarray(flat).reshape(-1))
+        if arr.shape != (ENCODER_PARAM_FLOATS,):
+            raise ValueError("flat must be [%d], got %s" % (ENCODER_PARAM_FLOATS, arr.shape))
+        _lib.check(self.lib.hpe_encoder_set_params(self._h, ptr))
+
+    def encoder_forward_train(self, images):
+        """hpe_encoder_forward_train: images [B,224,224,3] -> features [B,2048], layer by layer, every activation kept in the stash"""
+        images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))
+        B = images.shape[0]
+        out = self._new(B, 2048)
+        _lib.check(self.lib.hpe_encoder_forward_train(self._h, images.data_ptr(), B, out.data_ptr(), self._stream()))
+        return out
+
+    def encoder_backward(self, images, grad_features):
+        """hpe_encoder_backward: the gradient of sum(grad_features * features) with respect to the flat encoder parameters.  Stateless
+        (the training forward runs again); same inputs, same bits."""
+        images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))
+        B = images.shape[0]
+        grad_features = _require_cuda_tensor(grad_features.detach(), "grad_features")
+        if tuple(grad_features.shape) != (B, 2048):
+            raise ValueError("grad_features must be [%d,2048], got %s" % (B, tuple(grad_features.shape)))
+        g = self._new(ENCODER_PARAM_FLOATS)
+        _lib.check(self.lib.hpe_encoder_backward(self._h, images.data_ptr(), B, grad_features.data_ptr(), g.data_ptr(), self._stream()))
+        return g
+
+    def debug_conv_backward(self, idx, x, y, dy, want_dx=True):
+        """hpe_debug_conv_backward: one layer's gate, weight gradient and data gradient -> (dx or None, grad_layer = [kernel | bias |
+        gamma | beta] flat)"""
+        s = CONV_SPECS[idx]
+        x, dy = _require_cuda_tensor(x, "x"), _require_cuda_tensor(dy, "dy")
+        y = _require_cuda_tensor(y, "y") if y is not None else None  # None: a layer without activation (dz = dy)
+        B = x.shape[0]
+        want_dx = want_dx and idx != 0
+        dx = self._new(B, s.hin, s.hin, s.cin) if want_dx else None
+        gl = self._new(s.kh * s.kw * s.cin * s.cout + 3 * s.cout)
+        _lib.check(self.lib.hpe_debug_conv_backward(self._h, idx, x.data_ptr(), y.data_ptr() if y is not None else None, dy.data_ptr(), B,
+                                                    dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
+        return dx, gl
+
+    def debug_maxpool_backward(self, x, dy):
+        x, dy = _require_cuda_tensor(x, "x"), _require_cuda_tensor(dy, "dy")
+        dx = self._new(*x.shape)
+        _lib.check(self.lib.hpe_debug_maxpool_backward(x.data_ptr(), dy.data_ptr(), x.shape[0], x.shape[1], x.shape[3], dx.data_ptr(), self._stream()))
+        return dx
+
+    def debug_avgpool_backward(self, dy, HW):
+        dy = _require_cuda_tensor(dy, "dy")
+        dx = self._new(dy.shape[0], HW, dy.shape[1])
+        _lib.check(self.lib.hpe_debug_avgpool_backward(dy.data_ptr(), dy.shape[0], HW, dy.shape[1], dx.data_ptr(), self._stream()))
+        return dx
+
+    def encoder_stash(self, idx):
+        """hpe_debug_encoder_stash: layer idx's output of the last training forward, over that call's batch (idx -1: the max-pooled map)"""
+        B = self.lib.hpe_debug_encoder_stash_batch(self._h)
+        if B < 1:
+            raise _lib.HpeError("encoder_stash: no training forward has run")
+        s = CONV_SPECS[idx] if idx >= 0 else None
+        out = self._new(B, s.hout, s.hout, s.cout) if s else self._new(B, 56, 56, 64)
+        _lib.check(self.lib.hpe_debug_encoder_stash(self._h, idx, out.data_ptr(), self._stream()))
+        return out
 
     def mesh_loss(self, seg, verts2d):
         torch = _torch()

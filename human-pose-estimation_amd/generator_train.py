@@ -2,11 +2,13 @@
 with dropout at the last stage, SMPL, the keypoint / mesh reprojection losses and the critic term on the last stage, their gradient with
 respect to the RegressionNetwork and mean theta (hpe_smpl_backward, hpe_kp_loss_backward, hpe_mesh_loss_grad, hpe_critic_backward,
 hpe_regressor_backward), an Adam step and the new weights back into the engine on the device (hpe_regressor_set_params_dev).  Adam is
-torch.optim.Adam on ONE flat tensor; everything else runs in libhpe_hip.so.  The encoder is not trained here: ``grad_features`` is
-returned for a caller who carries on into it."""
+torch.optim.Adam on ONE flat tensor; everything else runs in libhpe_hip.so.  With ``train_encoder=True`` the encoder (BatchNorm statistics
+fixed, fp32) is in the same step, as in the reference (src/trainer.py:481): features come from ``encoder_features``, the one
+``.backward()`` fills both flat gradients, a second Adam steps the encoder's flat tensor and ``set_encoder_params`` installs it.
+``grad_features`` is returned either way."""
 from __future__ import annotations
 
-from .ops import generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas
+from .ops import encoder_features, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas
 
 GENERATOR_LR = 0.0001  # the reference's generator_lr (src/config.py:64-69)
 ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon
@@ -14,10 +16,12 @@ ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon
 
 class GeneratorTrainer(object):
     def __init__(self, engine, lr=GENERATOR_LR, betas=(0.9, 0.999), eps=ADAM_EPS, kpr_loss_weight=60.0, mr_loss_weight=0.001,
-                 critic_loss_weight=0.01, dropout=0.5, generator=None):
+                 critic_loss_weight=0.01, dropout=0.5, generator=None, train_encoder=False, encoder_lr=None):
         """engine: a finalized HpeEngine with a regressor, mean theta and SMPL (and a critic, for the critic term).  ``params`` is the
         flat parameter tensor (regressor_spec.flat_layout) the optimiser owns; ``regressor_spec.flat_to_params(params)`` gives the
-        dict ``load_regressor`` / ``load_mean_theta`` take.  generator: the torch.Generator of the dropout draws."""
+        dict ``load_regressor`` / ``load_mean_theta`` take.  generator: the torch.Generator of the dropout draws.  train_encoder: also
+        step the encoder's flat tensor ``encoder_params`` (needs ``engine.reserve_encoder_train(B)``; Adam with the same
+        hyper-parameters, lr ``encoder_lr``, default the generator's) whenever ``step`` is given images."""
         import torch
 
         if not 0.0 <= dropout < 1.0:
@@ -28,6 +32,11 @@ class GeneratorTrainer(object):
         self.generator = generator
         self.params = engine.regressor_params().requires_grad_(True)
         self.optimizer = torch.optim.Adam([self.params], lr=lr, betas=betas, eps=eps)
+        self.train_encoder = bool(train_encoder)
+        self.encoder_params = self.encoder_optimizer = None
+        if self.train_encoder:
+            self.encoder_params = engine.encoder_params().requires_grad_(True)
+            self.encoder_optimizer = torch.optim.Adam([self.encoder_params], lr=lr if encoder_lr is None else encoder_lr, betas=betas, eps=eps)
 
     def draw_masks(self, B):
         """the dropout multipliers [2,B,1024] of one step: 0 with probability ``dropout``, else 1 / (1 - dropout); None without dropout"""
@@ -62,12 +71,18 @@ class GeneratorTrainer(object):
         x = images_or_features
         if use_critic is None:
             use_critic = eng.has_critic
-        with torch.no_grad():
-            features = x if x.dim() == 2 else torch.cat([eng.encoder(x[lo : lo + eng.max_batch]) for lo in range(0, x.shape[0], eng.max_batch)])
+        enc = self.train_encoder and x.dim() == 4
+        if enc:
+            features = encoder_features(eng, x, self.encoder_params)
+            features.retain_grad()
+        else:
+            with torch.no_grad():
+                features = x if x.dim() == 2 else torch.cat([eng.encoder(x[lo : lo + eng.max_batch]) for lo in range(0, x.shape[0], eng.max_batch)])
         B = features.shape[0]
         if isinstance(drop, str):
             drop = self.draw_masks(B)
-        features = features.detach().clone().requires_grad_(True)
+        if not enc:
+            features = features.detach().clone().requires_grad_(True)
         thetas = regressor_thetas(eng, features, self.params, drop)
         S = thetas.shape[0]
         kpr, mr, gc = [], [], []
@@ -89,9 +104,14 @@ class GeneratorTrainer(object):
                     pred_kp = kp.detach()
                     loss = kpr[-1] + (mr[-1] if mr else 0.0) + (gc[-1] if gc else 0.0)
         self.optimizer.zero_grad(set_to_none=True)
+        if enc:
+            self.encoder_optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.optimizer.step()
         eng.set_regressor_params(self.params)
+        if enc:
+            self.encoder_optimizer.step()
+            eng.set_encoder_params(self.encoder_params)
         det = lambda ts: [t.detach() for t in ts]  # noqa: E731
         return {"kpr_losses": det(kpr), "mr_losses": det(mr), "generator_critic_losses": det(gc), "pred_keypoints": pred_kp,
                 "generated_cams": thetas[S - 1, :, :3].detach(), "thetas": [thetas[i].detach() for i in range(S)],

@@ -61,6 +61,14 @@ def generator_critic_loss(engine, joints, shapes, Rs, return_parts=False):
     return -scores.mean(0).sum()
 
 
+def encoder_features(engine, images, params):
+    """features [B,2048] of the engine's encoder (layer by layer, BatchNorm statistics fixed), differentiable in ``params``, the flat
+    tensor [resnet_spec.ENCODER_PARAM_FLOATS] that must equal ``engine.encoder_params()``; needs ``engine.reserve_encoder_train(B)``"""
+    from .autograd import EncoderFunction
+
+    return EncoderFunction.apply(engine, images, params)
+
+
 def regressor_thetas(engine, features, params, drop=None):
     """The IEF loop of the generator step (src/trainer.py:389-401) on the engine's live regressor: features [B,2048] -> thetas
     [num_stage,B,85], with ``drop`` [2,B,1024] the dropout multipliers of the last stage (None: none).  ``params`` is the flat

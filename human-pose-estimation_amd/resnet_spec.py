@@ -51,6 +51,59 @@ def encoder_param_count():
     return n
 
 
+# ---- the flat layout of the trainable encoder parameters (include/hpe.h: hpe_encoder_param_offset): per layer kernel HWIO, bias, gamma, beta
+PARAM_PARTS = ("kernel", "bias", "gamma", "beta")
+
+
+def encoder_param_offsets():
+    """[(kernel, bias, gamma, beta offsets)] per layer and the total float count"""
+    offs, o = [], 0
+    for s in CONV_SPECS:
+        kn = s.kh * s.kw * s.cin * s.cout
+        offs.append((o, o + kn, o + kn + s.cout, o + kn + 2 * s.cout))
+        o += kn + 3 * s.cout
+    return offs, o
+
+
+ENCODER_PARAM_OFFSETS, ENCODER_PARAM_FLOATS = encoder_param_offsets()
+
+
+def _flat_keys(s):
+    return (s.name + "/kernel", s.name + "/bias", s.bn_name + "/gamma", s.bn_name + "/beta")
+
+
+def params_to_flat(params):
+    """the dict ``load_encoder`` takes -> the flat float32 array (the statistics are not in it)"""
+    import numpy as np
+
+    out = np.empty(ENCODER_PARAM_FLOATS, np.float32)
+    for s, off in zip(CONV_SPECS, ENCODER_PARAM_OFFSETS):
+        for key, o in zip(_flat_keys(s), off):
+            v = np.asarray(params[key], np.float32).reshape(-1)
+            out[o:o + v.size] = v
+    return out
+
+
+def flat_to_params(flat, stats):
+    """flat array (or CPU/CUDA tensor) -> the dict ``load_encoder`` takes; moving_mean / moving_variance are passed through from ``stats``
+    (any dict that holds them, e.g. the parameters the flat array came from)"""
+    import numpy as np
+
+    if hasattr(flat, "detach"):
+        flat = flat.detach().cpu().numpy()
+    flat = np.asarray(flat, np.float32).reshape(-1)
+    if flat.size != ENCODER_PARAM_FLOATS:
+        raise ValueError("flat must hold %d floats, got %d" % (ENCODER_PARAM_FLOATS, flat.size))
+    out = {}
+    for s, off in zip(CONV_SPECS, ENCODER_PARAM_OFFSETS):
+        shapes = ((s.kh, s.kw, s.cin, s.cout), (s.cout,), (s.cout,), (s.cout,))
+        for key, o, shp in zip(_flat_keys(s), off, shapes):
+            out[key] = flat[o:o + int(np.prod(shp))].reshape(shp).copy()
+        for k in ("/moving_mean", "/moving_variance"):
+            out[s.bn_name + k] = np.asarray(stats[s.bn_name + k], np.float32)
+    return out
+
+
 def encoder_macs_per_image():
     return sum(s.kh * s.kw * s.cin * s.cout * s.hout * s.hout for s in CONV_SPECS)
 

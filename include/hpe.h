@@ -348,6 +348,55 @@ int hpe_regressor_forward_train(hpe_ctx* ctx, const float* features_dev, int B, 
 int hpe_regressor_backward(hpe_ctx* ctx, const float* features_dev, int B, const float* drop_dev, const float* grad_thetas_dev,
                            float* grad_flat_dev, float* grad_features_dev, void* stream);
 
+/* -- encoder training: fine-tuning ResNet-50 with the BatchNorm statistics held fixed ---------------------------------------------
+ * (src/trainer.py:481 steps image_feature_extractor.trainable_variables with the regressor; here moving_mean / moving_variance stay as
+ * loaded, Keras' frozen-BN mode.)  fp32 contexts only: every call that takes a ctx returns HPE_ERR_STATE on a bf16 context.
+ * Per layer of the table (hpe_conv_layer_name), s = gamma / sqrt(var + eps):  y = act(s * (conv(x, W) + b - mean) + beta (+ residual)).
+ * The trainable parameters as ONE flat fp32 buffer of hpe_encoder_param_floats() floats, layer after layer in table order: kernel HWIO,
+ * bias, gamma, beta.  hpe_encoder_param_offset(idx, which): the first float of layer idx's kernel (which 0), bias (1), gamma (2) or
+ * beta (3); -1 otherwise.  The statistics are not in it.  Host code: no device is needed. */
+int hpe_encoder_param_floats(void);
+int hpe_encoder_param_offset(int idx, int which);
+/* hpe_encoder_train_reserve allocates, once and outside any capture, what the calls below need for batches up to B (1 <= B <= max_batch):
+ * the activation stash (every layer's output and the pooled map, about 11 M floats per image), the cotangent buffers, the partial sums of
+ * the weight gradient and the data-gradient packings of the weights (about 94 MB, kept beside the forward's packings); it also rebuilds
+ * the flat parameters from the packed weights.  hpe_encoder_train_ws_floats(B): the floats it allocates.  An inference context that never
+ * calls it does not grow.  A second call with a B not above the first is a no-op; a larger one is refused (HPE_ERR_STATE).
+ * hpe_encoder_wg_slices(idx, B): the number of pixel slices the weight gradient of layer idx is cut into at batch B (host code). */
+int hpe_encoder_train_reserve(hpe_ctx* ctx, int B);
+long long hpe_encoder_train_ws_floats(int B);
+int hpe_encoder_wg_slices(int idx, int B);
+/* The encoder layer by layer (the launches of hpe_debug_conv, the max-pool and the average pool; no fused stem, dual or chained launch),
+ * every output kept in the stash; images_dev [B,224,224,3], features_dev [B,2048]. */
+int hpe_encoder_forward_train(hpe_ctx* ctx, const float* images_dev, int B, float* features_dev, void* stream);
+/* Gradient of < grad_features, features > with respect to the flat parameters (grad_flat_dev [hpe_encoder_param_floats()], overwritten).
+ * ReLU's gradient is 0 at 0 (TensorFlow's); the max-pool sends each cotangent to the first maximum of its zero-padded window in row-major
+ * order.  Stateless: the training forward is run again into the stash first.  No allocation, no synchronisation, capturable on one
+ * stream; no atomics and a fixed summation order: the same inputs give the same bits.  It shares the split-K slices and the padded-image
+ * buffer of hpe_encoder / hpe_forward*, so it must not overlap them on another stream.
+ * HPE_ERR_INVALID for NULL pointers or B outside [1, reserved B]; HPE_ERR_STATE before hpe_finalize or hpe_encoder_train_reserve. */
+int hpe_encoder_backward(hpe_ctx* ctx, const float* images_dev, int B, const float* grad_features_dev, float* grad_flat_dev, void* stream);
+/* The live encoder parameters in the flat layout (one device copy on `stream`).  Needs hpe_encoder_train_reserve. */
+int hpe_encoder_get_params(hpe_ctx* ctx, float* flat_dev, void* stream);
+/* Replace the encoder's kernels, biases, gammas and betas by flat_host (HOST memory): the host packing of hpe_finalize runs again for
+ * every kernel family the plan uses, and for the data-gradient packings, and is copied into the buffers that already exist -- no pointer
+ * changes, captured graphs stay valid.  SYNCHRONOUS (it waits for the device before and after) and NOT capturable.  Afterwards
+ * hpe_encoder gives the bits of a fresh context that loaded the same values.  Needs hpe_encoder_train_reserve. */
+int hpe_encoder_set_params(hpe_ctx* ctx, const float* flat_host);
+/* One layer's gate, weight gradient and data gradient: x_dev the layer's input (idx 0: the images), y_dev its output (after ReLU; the
+ * gate is [y > 0]) or NULL for a layer without activation (the projection shortcuts in the network: dz = dy), dy_dev the cotangent of y.  grad_layer_dev receives [kernel | bias | gamma | beta] of that layer, dx_dev
+ * [B,hin,hin,cin] the data gradient (NULL: not computed; must be NULL for idx 0). */
+int hpe_debug_conv_backward(hpe_ctx* ctx, int idx, const float* x_dev, const float* y_dev, const float* dy_dev, int B, float* dx_dev,
+                            float* grad_layer_dev, void* stream);
+/* x_dev [B,H,H,C] (the max-pool's input), dy_dev [B,H/2,H/2,C] -> dx_dev [B,H,H,C]; dy_dev [B,C] -> dx_dev [B,HW,C] */
+int hpe_debug_maxpool_backward(const float* x_dev, const float* dy_dev, int B, int H, int C, float* dx_dev, void* stream);
+int hpe_debug_avgpool_backward(const float* dy_dev, int B, int HW, int C, float* dx_dev, void* stream);
+/* Copies layer idx's output of the last training forward (hpe_encoder_forward_train / hpe_encoder_backward), B images of it, to out_dev;
+ * idx -1: the max-pooled map [B,56,56,64]. */
+int hpe_debug_encoder_stash(hpe_ctx* ctx, int idx, float* out_dev, void* stream);
+/* The batch of the last training forward, i.e. the images hpe_debug_encoder_stash copies (0: none has run). */
+int hpe_debug_encoder_stash_batch(hpe_ctx* ctx);
+
 /* Both reprojection losses of all n_stage IEF stages in ONE call -- what Trainer.val_step evaluates per step
  * (src/trainer.py:274-296): the work that depends only on seg_gts (tf.where compaction, src/trainer.py:291;
  * the silhouette bitmap) is done once per call instead of once per stage.

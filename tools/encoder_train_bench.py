@@ -1,0 +1,116 @@
+"""ms per hpe_encoder_backward and per hpe_encoder_set_params at B in {8, 32, 64}, against the same ResNet-50 (frozen BatchNorm statistics)
+in torch fp32 with autograd in the same process.  Prints one JSON line and writes profiles/encoder_train_bench.json.
+
+    python tools/encoder_train_bench.py [--batches 8,32,64] [--iters 10] [--out profiles/encoder_train_bench.json]
+
+Timing: device events around `iters` back-to-back calls after 3 warm-up calls, median of 5 such groups; torch's TF32 paths are off."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+import hpe_amd  # noqa: E402
+from hpe_amd import synthetic  # noqa: E402
+from hpe_amd.resnet_spec import CONV_SPECS, STAGE_BLOCKS  # noqa: E402
+
+
+def timed(fn, iters):
+    for _ in range(3):
+        fn()
+    groups = []
+    for _ in range(5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        b.synchronize()
+        groups.append(a.elapsed_time(b) / iters)
+    return statistics.median(groups)
+
+
+class TorchResNet(object):
+    """the same function in torch: NCHW conv2d + the folded affine of the fixed statistics + ReLU; gradients to W, b, gamma, beta"""
+
+    def __init__(self, params, eps=1e-3):
+        self.layers = []
+        for s in CONV_SPECS:
+            t = lambda k: torch.from_numpy(np.asarray(params[k], np.float32)).cuda()  # noqa: E731
+            W = t(s.name + "/kernel").permute(3, 2, 0, 1).contiguous().requires_grad_(True)
+            b, gamma, beta = (t(k).requires_grad_(True) for k in (s.name + "/bias", s.bn_name + "/gamma", s.bn_name + "/beta"))
+            mean, istd = t(s.bn_name + "/moving_mean"), 1.0 / torch.sqrt(t(s.bn_name + "/moving_variance") + eps)
+            self.layers.append((s, W, b, gamma, beta, mean, istd))
+        self.leaves = [p for l in self.layers for p in l[1:5]]
+
+    def conv(self, i, x, res=None, relu=True):
+        s, W, b, gamma, beta, mean, istd = self.layers[i]
+        z = F.conv2d(x, W, stride=s.stride, padding=(s.kh - 1) // 2)
+        y = (gamma * istd).view(1, -1, 1, 1) * (z + (b - mean).view(1, -1, 1, 1)) + beta.view(1, -1, 1, 1)
+        if res is not None:
+            y = y + res
+        return torch.relu(y) if relu else y
+
+    def features(self, img):
+        x = self.conv(0, img.permute(0, 3, 1, 2))
+        x = F.max_pool2d(F.pad(x, (1, 1, 1, 1)), 3, 2)
+        ci = 1
+        for stage in (2, 3, 4, 5):
+            for b in range(STAGE_BLOCKS[stage]):
+                t = self.conv(ci + 1, self.conv(ci, x))
+                res = self.conv(ci + 3, x, relu=False) if b == 0 else x
+                x = self.conv(ci + 2, t, res)
+                ci += 4 if b == 0 else 3
+        return x.mean((2, 3))
+
+    def backward(self, img, gf):
+        for p in self.leaves:
+            p.grad = None
+        (self.features(img) * gf).sum().backward()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="8,32,64")
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "encoder_train_bench.json"))
+    a = ap.parse_args()
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    batches = [int(b) for b in a.batches.split(",")]
+    params = synthetic.make_encoder_params()
+    eng = hpe_amd.HpeEngine(device=0, max_batch=max(batches))
+    eng.load_encoder(params)
+    eng.finalize()
+    eng.reserve_encoder_train(max(batches))
+    ref = TorchResNet(params)
+    flat = eng.encoder_params().cpu()
+    res = {"device": torch.cuda.get_device_name(0), "iters": a.iters, "rows": []}
+    for B in batches:
+        img = torch.from_numpy(synthetic.make_images(B, seed=1)).cuda()
+        gf = torch.randn(B, 2048, device="cuda")
+        hip = timed(lambda: eng.encoder_backward(img, gf), a.iters)
+        tch = timed(lambda: ref.backward(img, gf), a.iters)
+        t0 = time.perf_counter()
+        for _ in range(3):
+            eng.set_encoder_params(flat)
+        setp = (time.perf_counter() - t0) / 3 * 1e3
+        res["rows"].append({"B": B, "hpe_encoder_backward_ms": round(hip, 3), "torch_autograd_fwd_bwd_ms": round(tch, 3),
+                            "hpe_encoder_set_params_ms": round(setp, 1)})
+    eng.close()
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
