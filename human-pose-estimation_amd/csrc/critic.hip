@@ -7,10 +7,9 @@
 // Summation order: ONE thread owns one output of one layer for all rows of the tile and adds its k terms in ascending k with fmaf, starting
 // from the bias.  No k axis is split, nothing is reduced across threads, no atomics: a row's bits do not depend on N, on the tile it lands
 // in, or on its slot in that tile (the slots run the same instruction sequence).  The backward recomputes the hidden pre-activations with
-// the forward's own loops and walks the transposed weight copies [out][in] (made once by hpe_critic_pack_live) the same way.
+// the forward's own loops and walks the transposed weight copies [out][in] (critic_params_kernel<true> of critic_train.hip writes them
+// beside the kernels) the same way.
 #include <hip/hip_runtime.h>
-
-#include <string.h>
 
 #include "critic_common.h"
 
@@ -315,17 +314,6 @@ constexpr Live LIVE = make_live();
 const CriticLayerSpec* hpe_critic_layers() { return LAYERS; }
 
 size_t hpe_critic_live_floats() { return LIVE.total; }
-
-void hpe_critic_pack_live(const HpeCriticModel& m, float* host) {
-    memset(host, 0, LIVE.total * sizeof(float));
-    for (int l = 0; l < NL; ++l) {
-        const int in = LAYOUT.in[l], out = LAYOUT.out[l];
-        memcpy(host + LIVE.w[l], m.kernel[l], sizeof(float) * in * out);
-        for (int k = 0; k < in; ++k)
-            for (int o = 0; o < out; ++o) host[LIVE.wt[l] + (size_t)o * in + k] = m.kernel[l][(size_t)k * out + o];
-        memcpy(host + LIVE.b[l], m.bias[l], sizeof(float) * out);
-    }
-}
 
 CriticW hpe_critic_live_view(const float* buf) {
     CriticW w{};

@@ -28,9 +28,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int POOL_FLOATS = 56 * 56 * 64;  // the max-pooled map, per image
 constexpr int MAX_SLICES = 128;            // pixel slices of one weight gradient (what the fix-up adds per element)
 constexpr int WGP_FLOATS = 1152 * 512;     // <W, G> per 4-row chunk: K / 4 x N of the largest kernel (3x3, 512 -> 512)
@@ -261,8 +258,6 @@ __global__ __launch_bounds__(256) void enc_maxpool_bwd_kernel(const float* __res
     dx[i] = g;
 }
 
-inline dim3 grid1(long n) { return dim3((unsigned)((n + 255) / 256)); }
-
 struct Layout {
     int off[HPE_NUM_CONV][4];
     int stat[HPE_NUM_CONV];      // offset into the per-channel statistics arrays
@@ -441,25 +436,18 @@ hipError_t forward_train(hpe_ctx* c, const float* images, int B, float* features
     HIPE(hpe_launch_pad_input(images, c->padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
     HIPE(run_conv(c, 0, c->padded, B, nullptr, 1, stash_of(c, 0, B), st));
     HIPE(hpe_launch_maxpool(stash_of(c, 0, B), stash_of(c, -1, B), B, 112, 64, st));
-    const float* cur = stash_of(c, -1, B);
-    const int nblk[4] = {3, 4, 6, 3};
-    int ci = 1;
-    for (int stg = 0; stg < 4; ++stg)
-        for (int b = 0; b < nblk[stg]; ++b) {
-            const bool first = b == 0;
-            const int i2a = ci, i2b = ci + 1, i2c = ci + 2, i1 = ci + 3;
-            HIPE(train_conv(c, i2a, cur, B, nullptr, 1, stash_of(c, i2a, B), st));
-            HIPE(train_conv(c, i2b, stash_of(c, i2a, B), B, nullptr, 1, stash_of(c, i2b, B), st));
-            const float* res = cur;
-            if (first) {
-                HIPE(train_conv(c, i1, cur, B, nullptr, 0, stash_of(c, i1, B), st));
-                res = stash_of(c, i1, B);
-            }
-            HIPE(train_conv(c, i2c, stash_of(c, i2b, B), B, res, 1, stash_of(c, i2c, B), st));
-            cur = stash_of(c, i2c, B);
-            ci += first ? 4 : 3;
+    for (const ResBlock& blk : blocks()) {
+        const float* cur = stash_of(c, blk.in, B);
+        HIPE(train_conv(c, blk.i2a, cur, B, nullptr, 1, stash_of(c, blk.i2a, B), st));
+        HIPE(train_conv(c, blk.i2b, stash_of(c, blk.i2a, B), B, nullptr, 1, stash_of(c, blk.i2b, B), st));
+        const float* res = cur;
+        if (blk.first) {
+            HIPE(train_conv(c, blk.i1, cur, B, nullptr, 0, stash_of(c, blk.i1, B), st));
+            res = stash_of(c, blk.i1, B);
         }
-    return hpe_launch_avgpool(cur, features, B, 49, HPE_FEATURE_DIM, HPE_FEATURE_DIM, st);
+        HIPE(train_conv(c, blk.i2c, stash_of(c, blk.i2b, B), B, res, 1, stash_of(c, blk.i2c, B), st));
+    }
+    return hpe_launch_avgpool(stash_of(c, blocks().back().i2c, B), features, B, 49, HPE_FEATURE_DIM, HPE_FEATURE_DIM, st);
 }
 
 hipError_t backward(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, hipStream_t st) {
@@ -468,20 +456,11 @@ hipError_t backward(hpe_ctx* c, const float* images, int B, const float* grad_fe
     HIPE(forward_train(c, images, B, w.feat, st));
     float *g = w.g0, *go = w.g1;
     hipLaunchKernelGGL(enc_avgpool_bwd_kernel, grid1((long)B * 49 * HPE_FEATURE_DIM), dim3(256), 0, st, grad_features, g, B, 49, HPE_FEATURE_DIM);
-    const int nblk[4] = {3, 4, 6, 3};
-    int first_idx[16], n_blocks = 0, ci = 1;
-    bool is_first[16];
-    for (int stg = 0; stg < 4; ++stg)
-        for (int b = 0; b < nblk[stg]; ++b) {
-            is_first[n_blocks] = b == 0;
-            first_idx[n_blocks++] = ci;
-            ci += b == 0 ? 4 : 3;
-        }
-    for (int k = n_blocks - 1; k >= 0; --k) {
-        const int i2a = first_idx[k], i2b = i2a + 1, i2c = i2a + 2, i1 = i2a + 3;
-        const bool first = is_first[k];
+    for (auto it = blocks().rbegin(); it != blocks().rend(); ++it) {
+        const int i2a = it->i2a, i2b = it->i2b, i2c = it->i2c, i1 = it->i1;
+        const bool first = it->first;
         const ConvSpec &sa = specs()[i2a], &sb = specs()[i2b], &sc = specs()[i2c];
-        const float* xin = stash_of(c, k == 0 ? -1 : first_idx[k - 1] + 2, B);  // the block's input: the previous block's branch2c output
+        const float* xin = stash_of(c, it->in, B);  // the block's input: the previous block's branch2c output
         const long Mo = (long)B * sc.hout * sc.hout;
         // branch2c: g becomes dz (the cotangent of the shortcut too)
         gate(g, stash_of(c, i2c, B), c->conv[i2c].scale, g, w.sbig, Mo * sc.cout, sc.cout, st);
@@ -597,7 +576,7 @@ int hpe_encoder_train_reserve(hpe_ctx* c, int B) {
         for (int kh = 0; kh < s.kh; ++kh)
             for (int kw = 0; kw < s.kw; ++kw)
                 for (int ci = 0; ci < s.cin; ++ci) {
-                    const int k = (i == 0) ? (kh * 32 + kw * 4 + ci) : ((kh * s.kw + kw) * s.cin + ci);
+                    const int k = conv_wt_k(i, kh, kw, ci);
                     float* dst = &flat[l.off[i][0] + (((size_t)kh * s.kw + kw) * s.cin + ci) * s.cout];
                     for (int n = 0; n < s.cout; ++n) dst[n] = wt[(size_t)n * L.k_pad + k];
                 }
@@ -606,7 +585,7 @@ int hpe_encoder_train_reserve(hpe_ctx* c, int B) {
             flat[l.off[i][2] + n] = L.gamma[n];
             flat[l.off[i][3] + n] = L.beta[n];
             mean[l.stat[i] + n] = L.mean[n];
-            istd[l.stat[i] + n] = (float)(1.0 / std::sqrt((double)L.var[n] + (double)c->cfg.bn_eps));
+            istd[l.stat[i] + n] = bn_istd(L, n, c->cfg.bn_eps);
         }
     }
     HIP_TRY(hipMemcpy(w.mean, mean.data(), mean.size() * sizeof(float), hipMemcpyHostToDevice));

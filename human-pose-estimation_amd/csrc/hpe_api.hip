@@ -2,6 +2,7 @@
 // launchers; debug and timing hooks.  The renderer's entry points are in hpe_render_api.hip.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -149,10 +150,7 @@ int hpe_regress_stage(hpe_ctx* c, const float* features, const float* theta_prev
     if (!features || !theta_out) return fail(HPE_ERR_INVALID, "null pointer");
     DeviceGuard g(c->cfg.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (c->tail_pending) {  // shares the regressor buffers with a pipelined call's tail
-        HIP_TRY(hipStreamWaitEvent(st, c->ev_tail, 0));
-        c->tail_pending = false;
-    }
+    HIP_TRY(join_tail(c, st));  // shares the regressor buffers with a pipelined call's tail
     HIP_TRY(features_proj(c, features, B, st));
     if (theta_prev)
         HIP_TRY(hpe_launch_copy_theta(theta_prev, HPE_THETA_DIM, c->thA, THETA_LD, B, HPE_THETA_DIM, st));
@@ -168,10 +166,7 @@ int hpe_smpl(hpe_ctx* c, const float* theta, int B, const HpeOutputs* outs, void
     if (rc) return rc;
     if (!theta || !outs) return fail(HPE_ERR_INVALID, "null pointer");
     DeviceGuard g(c->cfg.device);
-    if (c->tail_pending) {  // shares the SMPL work buffers with a pipelined call's tail
-        HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(stream), c->ev_tail, 0));
-        c->tail_pending = false;
-    }
+    HIP_TRY(join_tail(c, static_cast<hipStream_t>(stream)));  // shares the SMPL work buffers with a pipelined call's tail
     HIP_TRY(hpe_launch_smpl(c->smpl, c->work, theta, HPE_THETA_DIM, B, outs, static_cast<hipStream_t>(stream)));
     return HPE_OK;
 }
@@ -200,10 +195,7 @@ int hpe_tail(hpe_ctx* c, const float* features, int B, const HpeOutputs* stage_o
     if (n_outs < 1 || n_outs > c->cfg.num_stage) return fail(HPE_ERR_INVALID, "n_outs must be in [1, num_stage]");
     DeviceGuard g(c->cfg.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (c->tail_pending) {  // shares the regressor / SMPL buffers with a pipelined call's tail
-        HIP_TRY(hipStreamWaitEvent(st, c->ev_tail, 0));
-        c->tail_pending = false;
-    }
+    HIP_TRY(join_tail(c, st));  // shares the regressor / SMPL buffers with a pipelined call's tail
     c->dense_on_tail = true;  // its own split-K workspace: may overlap hpe_encoder of the next batch
     const hipError_t e = tail_impl(c, features, B, stage_outs, n_outs, st, nullptr);
     c->dense_on_tail = false;
@@ -437,18 +429,30 @@ int hpe_load_critic(hpe_ctx* c, const HpeCriticModel* m) {
     for (int i = 0; i < HPE_NUM_CRITIC_DENSE; ++i)
         if (!m->kernel[i] || !m->bias[i])
             return fail(HPE_ERR_INVALID, std::string("critic layer ") + hpe_critic_layers()[i].name + ": null kernel or bias");
-    const size_t total = hpe_critic_live_floats();
-    std::vector<float> h(total);
-    hpe_critic_pack_live(*m, h.data());
+    // the flat layout (kernel 0 | bias 0 | kernel 1 | ...); the live layout is written from it by the one kernel that states it
+    std::vector<float> flat((size_t)CRITIC_PARAM_FLOATS);
+    for (int l = 0; l < HPE_NUM_CRITIC_DENSE; ++l) {
+        const int kn = hpe_critic_layers()[l].in * hpe_critic_layers()[l].out;
+        std::copy(m->kernel[l], m->kernel[l] + kn, flat.begin() + hpe_critic_flat_offset(l, false));
+        std::copy(m->bias[l], m->bias[l] + hpe_critic_layers()[l].out, flat.begin() + hpe_critic_flat_offset(l, true));
+    }
     DeviceGuard g(c->cfg.device);
     HIP_TRY(hipDeviceSynchronize());  // a call still running may read the weights that are about to be replaced
     if (!c->critic_buf) {
         void* q = nullptr;
-        HIP_TRY(hipMalloc(&q, total * sizeof(float)));
+        HIP_TRY(hipMalloc(&q, hpe_critic_live_floats() * sizeof(float)));
         c->critic_buf = static_cast<float*>(q);
+        c->critic = hpe_critic_live_view(c->critic_buf);
     }
-    HIP_TRY(hipMemcpy(c->critic_buf, h.data(), total * sizeof(float), hipMemcpyHostToDevice));
-    c->critic = hpe_critic_live_view(c->critic_buf);
+    // the set kernel writes the live elements only: the padding between the 16-byte aligned blocks is zero from here
+    HIP_TRY(hipMemset(c->critic_buf, 0, hpe_critic_live_floats() * sizeof(float)));
+    void* tmp = nullptr;
+    HIP_TRY(hipMalloc(&tmp, flat.size() * sizeof(float)));
+    hipError_t e = hipMemcpy(tmp, flat.data(), flat.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hpe_launch_critic_params(c->critic, static_cast<float*>(tmp), true, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(tmp);
+    HIP_TRY(e);
     c->have_critic = true;
     return HPE_OK;
 }
@@ -594,6 +598,7 @@ int hpe_regressor_set_params_dev(hpe_ctx* c, const float* flat, void* stream) {
     int rc = check_regressor_params(c, flat);
     if (rc) return rc;
     DeviceGuard g(c->cfg.device);
+    HIP_TRY(join_tail(c, static_cast<hipStream_t>(stream)));  // a pipelined call's tail may still read the weights this rewrites
     HIP_TRY(regressor_params_copy(c, const_cast<float*>(flat), true, static_cast<hipStream_t>(stream)));
     return HPE_OK;
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -33,6 +34,16 @@ struct ConvSpec {
 // ResNet-50 v1 layer table, Keras names / order [2a, 2b, 2c, (1)] per block.
 const std::vector<ConvSpec>& specs();
 
+// One bottleneck block of that table: the indices of its layers.  first: a conv_block (projection shortcut i1, else i1 = -1), last: the
+// last block of its stage; in: the layer whose output is the block's input (the previous block's i2c), -1 = the max-pooled map
+struct ResBlock {
+    int stage;
+    bool first, last;
+    int i2a, i2b, i2c, i1;
+    int in;
+};
+const std::vector<ResBlock>& blocks();  // 16 entries, built by the loop that builds specs()
+
 inline int round_up(int x, int m) { return ((x + m - 1) / m) * m; }
 
 struct ConvLayer {
@@ -54,6 +65,21 @@ struct ConvLayer {
     float* wino4_u = nullptr;  // device, the F(4x4,3x3) G g G^T in the blocked layout of conv_wino4.hip (layers selected by wino_f4)
     int n_pad = 0, k_pad = 0;
 };
+
+// The k index of tap (kh, kw, ci) of layer idx in its packed weights Wt[n][k]: (kh, kw, cin) with cin fastest; conv1 has one 32-wide
+// group per kernel row, 8 px x 4 ch (the 8th pixel and the 4th channel are zero weights)
+inline int conv_wt_k(int idx, int kh, int kw, int ci) {
+    const ConvSpec& s = specs()[idx];
+    return idx == 0 ? kh * 32 + kw * 4 + ci : (kh * s.kw + kw) * s.cin + ci;
+}
+
+// BatchNorm with the moving statistics folded into the layer: y = scale * conv(x, W) + shift, the conv bias inside shift.  In double.
+inline void bn_fold(const ConvLayer& L, int n, float eps, double* scale, double* shift) {
+    *scale = (double)L.gamma[n] / std::sqrt((double)L.var[n] + (double)eps);
+    *shift = ((double)L.bias[n] - (double)L.mean[n]) * *scale + (double)L.beta[n];
+}
+// ... and what the gamma gradient of the encoder's backward divides by
+inline float bn_istd(const ConvLayer& L, int n, float eps) { return (float)(1.0 / std::sqrt((double)L.var[n] + (double)eps)); }
 
 inline unsigned short f2bf(float f) {  // round-to-nearest-even fp32 -> bf16 (finite inputs)
     unsigned u;
@@ -77,8 +103,8 @@ constexpr size_t WINO_V_SLACK = 524288;
 
 
 // Regressor training (regressor_train.hip).  The backward multiplies by the transposed kernels, and for the dense GEMM's Wt[n][k] operand
-// the transpose of a packed weight is the Keras [in][out] matrix itself: w1k / w2k / w3k hold it (pack_regressor and
-// hpe_regressor_set_params_dev write them beside the packed copies).  Everything else is workspace for max_batch rows and num_stage stages
+// the transpose of a packed weight is the Keras [in][out] matrix itself: w1k / w2k / w3k hold it
+// (regressor_params_copy writes them beside the packed copies, for hpe_finalize as for hpe_regressor_set_params_dev).  Everything else is workspace for max_batch rows and num_stage stages
 // that no other entry point touches.
 struct RegTrainWork {
     float *w1k = nullptr;  // [2048 + 128][1024]: dense_0/kernel, rows 2133.. zero (the theta block is an 85-row operand padded to two 64-row tiles)
@@ -145,7 +171,7 @@ struct hpe_ctx {
     float *padded = nullptr, *X0 = nullptr, *X1 = nullptr, *T1 = nullptr, *T2 = nullptr, *SC = nullptr;
     float *feat = nullptr, *P1 = nullptr, *H1 = nullptr, *H2 = nullptr, *thA = nullptr, *thB = nullptr;
     // device: critic (hpe_load_critic; valid before and after hpe_finalize, released with the rest of the device state)
-    float* critic_buf = nullptr;  // hpe_critic_live_floats() floats in the layout of hpe_critic_pack_live (critic.hip)
+    float* critic_buf = nullptr;  // hpe_critic_live_floats() floats: the live layout of critic.hip
     CriticW critic{};
     bool have_critic = false;
     float* critic_ws = nullptr;  // hpe_critic_weight_grad's workspace (hpe_critic_wg_ws_floats), grown outside capture
@@ -238,6 +264,7 @@ hipError_t run_dense(hpe_ctx* c, const float* x, int lda, int M, int K, const fl
 hipError_t regress_impl(hpe_ctx* c, const float* th_prev, float* th_next, int B, hipStream_t st);
 hipError_t features_proj(hpe_ctx* c, const float* features, int B, hipStream_t st);
 hipError_t tail_impl(hpe_ctx* c, const float* feat, int B, const HpeOutputs* stage_outs, int n_outs, hipStream_t ts, hipEvent_t feat_free);
+hipError_t join_tail(hpe_ctx* c, hipStream_t st);  // wait on `st` for a pipelined call's tail, if one is pending
 int forward_impl(hpe_ctx* c, const float* images, int B, const HpeOutputs* stage_outs, int n_outs, hipStream_t st, bool pipelined);
 
 // regressor_train.hip

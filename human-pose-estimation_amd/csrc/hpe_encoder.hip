@@ -287,65 +287,60 @@ static hipError_t encoder_chunk(hpe_ctx* c, const float* images, int i0, int B, 
         HIPE(timed_conv(c, 0, padded, B, nullptr, 1, SC, st, nullptr, 0, cf));
         HIPE(hpe_launch_maxpool(SC, cur, B, 112, 64, st));
     }
-    int ci = 1;
-    const int nblk[4] = {3, 4, 6, 3};
     bool have_2a = false;  // the previous block's chained launch has already written this block's branch2a output to T1
-    for (int stg = 0; stg < 4; ++stg) {
-        for (int b = 0; b < nblk[stg]; ++b) {
-            const bool first = b == 0;
-            const int i2a = ci, i2b = ci + 1, i2c = ci + 2, i1 = ci + 3;
-            const bool fz = use_wino_fused(c, i2b, B) || use_wino4_fused(c, i2b, B);  // then T1 is channel-slab major and never leaves this pair of launches
-            if (have_2a) {
-                if (c->timing >= 2) {
-                    HIPE(hipEventRecord(c->cev0[i2a], st));
-                    HIPE(hipEventRecord(c->cev1[i2a], st));
-                }
-            } else {
-                HIPE(timed_conv(c, i2a, cur, B, nullptr, 1, T1, st, nullptr, 0, cf | (fz ? CONV_OUT_SLAB8 : 0)));
+    for (const ResBlock& blk : blocks()) {
+        const bool first = blk.first;
+        const int i2a = blk.i2a, i2b = blk.i2b, i2c = blk.i2c, i1 = blk.i1;
+        const bool fz = use_wino_fused(c, i2b, B) || use_wino4_fused(c, i2b, B);  // then T1 is channel-slab major and never leaves this pair of launches
+        if (have_2a) {
+            if (c->timing >= 2) {
+                HIPE(hipEventRecord(c->cev0[i2a], st));
+                HIPE(hipEventRecord(c->cev1[i2a], st));
             }
-            have_2a = false;
-            HIPE(timed_conv(c, i2b, T1, B, nullptr, 1, T2, st, wv, slot, cf | (fz ? CONV_IN_SLAB8 : 0)));
-            const float* res = cur;
-            if (use_chain(c, stg, i2c, first, b + 1 < nblk[stg])) {
-                // identity block followed by an identity block (bf16): relu(bn(W2c t2) + x) and the next block's relu(bn(W2a' .)) in one
-                // launch; the 4C-wide sum is written once and not read back (timed as layer i2c; the next branch2a then shows 0)
-                const bool t2 = c->timing >= 2;
-                if (t2) HIPE(hipEventRecord(c->cev0[i2c], st));
-                // (fp32: the next block's 3x3 layer may be the fused Winograd kernel, which reads its input channel-slab major)
-                const int i2b_next = i2c + (first ? 3 : 2);
-                const bool slab8_next = !c->bf16 && (use_wino_fused(c, i2b_next, B) || use_wino4_fused(c, i2b_next, B));
-                HIPE(run_chain(c, i2c, first, T2, cur, B, nxt, T1, st, slab8_next));
-                if (t2) {
-                    HIPE(hipEventRecord(c->cev1[i2c], st));
-                    if (first) {  // the projection shortcut is inside the launch
-                        HIPE(hipEventRecord(c->cev0[i1], st));
-                        HIPE(hipEventRecord(c->cev1[i1], st));
-                    }
-                }
-                have_2a = true;
-            } else if (first && c->conv[i2c].w_dual) {
-                // conv_block: expand convolution + projection shortcut + add + ReLU as one dual-source GEMM (timed as layer i2c)
-                const bool t2 = c->timing >= 2;
-                if (t2) HIPE(hipEventRecord(c->cev0[i2c], st));
-                HIPE(run_dual(c, i2c, i1, T2, cur, B, nxt, st, cf));
-                if (t2) {
-                    HIPE(hipEventRecord(c->cev1[i2c], st));
+        } else {
+            HIPE(timed_conv(c, i2a, cur, B, nullptr, 1, T1, st, nullptr, 0, cf | (fz ? CONV_OUT_SLAB8 : 0)));
+        }
+        have_2a = false;
+        HIPE(timed_conv(c, i2b, T1, B, nullptr, 1, T2, st, wv, slot, cf | (fz ? CONV_IN_SLAB8 : 0)));
+        const float* res = cur;
+        if (use_chain(c, blk)) {
+            // identity block followed by an identity block (bf16): relu(bn(W2c t2) + x) and the next block's relu(bn(W2a' .)) in one
+            // launch; the 4C-wide sum is written once and not read back (timed as layer i2c; the next branch2a then shows 0)
+            const bool t2 = c->timing >= 2;
+            if (t2) HIPE(hipEventRecord(c->cev0[i2c], st));
+            // (fp32: the next block's 3x3 layer may be the fused Winograd kernel, which reads its input channel-slab major)
+            const int i2b_next = i2c + (first ? 3 : 2);
+            const bool slab8_next = !c->bf16 && (use_wino_fused(c, i2b_next, B) || use_wino4_fused(c, i2b_next, B));
+            HIPE(run_chain(c, i2c, first, T2, cur, B, nxt, T1, st, slab8_next));
+            if (t2) {
+                HIPE(hipEventRecord(c->cev1[i2c], st));
+                if (first) {  // the projection shortcut is inside the launch
                     HIPE(hipEventRecord(c->cev0[i1], st));
                     HIPE(hipEventRecord(c->cev1[i1], st));
                 }
-            } else {
-                if (first) {
-                    // projection shortcut (conv_block), no ReLU before the add
-                    HIPE(timed_conv(c, i1, cur, B, nullptr, 0, SC, st, nullptr, 0, cf));
-                    res = SC;
-                }
-                HIPE(timed_conv(c, i2c, T2, B, res, 1, nxt, st, nullptr, 0, cf));
             }
-            ci += first ? 4 : 3;
-            float* t = cur;
-            cur = nxt;
-            nxt = t;
+            have_2a = true;
+        } else if (first && c->conv[i2c].w_dual) {
+            // conv_block: expand convolution + projection shortcut + add + ReLU as one dual-source GEMM (timed as layer i2c)
+            const bool t2 = c->timing >= 2;
+            if (t2) HIPE(hipEventRecord(c->cev0[i2c], st));
+            HIPE(run_dual(c, i2c, i1, T2, cur, B, nxt, st, cf));
+            if (t2) {
+                HIPE(hipEventRecord(c->cev1[i2c], st));
+                HIPE(hipEventRecord(c->cev0[i1], st));
+                HIPE(hipEventRecord(c->cev1[i1], st));
+            }
+        } else {
+            if (first) {
+                // projection shortcut (conv_block), no ReLU before the add
+                HIPE(timed_conv(c, i1, cur, B, nullptr, 0, SC, st, nullptr, 0, cf));
+                res = SC;
+            }
+            HIPE(timed_conv(c, i2c, T2, B, res, 1, nxt, st, nullptr, 0, cf));
         }
+        float* t = cur;
+        cur = nxt;
+        nxt = t;
     }
     if (c->bf16) return hpe_launch_avgpool_bf16(cur, features + (size_t)i0 * ldfeat, B, 49, HPE_FEATURE_DIM, ldfeat, st);
     return hpe_launch_avgpool(cur, features + (size_t)i0 * ldfeat, B, 49, HPE_FEATURE_DIM, ldfeat, st);
@@ -427,6 +422,15 @@ hipError_t tail_impl(hpe_ctx* c, const float* feat, int B, const HpeOutputs* sta
     return e;
 }
 
+// What runs on `st` from here on reads or writes buffers the tail of a pipelined call uses (regressor weights and activations, SMPL
+// work buffers): order it behind a tail that may still be running
+hipError_t join_tail(hpe_ctx* c, hipStream_t st) {
+    if (!c->tail_pending) return hipSuccess;
+    HIPE(hipStreamWaitEvent(st, c->ev_tail, 0));
+    c->tail_pending = false;
+    return hipSuccess;
+}
+
 // encoder on `st`; regressor + SMPL stages on `st` (pipelined == false) or on the ctx's tail stream behind an event (true)
 int forward_impl(hpe_ctx* c, const float* images, int B, const HpeOutputs* stage_outs, int n_outs, hipStream_t st, bool pipelined) {
     int rc = check_ready(c, B, NEED_ENC | NEED_REG | NEED_SMPL);
@@ -445,10 +449,8 @@ int forward_impl(hpe_ctx* c, const float* images, int B, const HpeOutputs* stage
         feat = slot ? c->feat_alt : c->feat;
         if (c->feat_free_valid[slot]) HIP_TRY(hipStreamWaitEvent(st, c->ev_feat_free[slot], 0));
         ts = c->tail_st;
-    } else if (c->tail_pending) {
-        // a serial call after pipelined ones: its tail shares buffers with the pending tail -> order them
-        HIP_TRY(hipStreamWaitEvent(st, c->ev_tail, 0));
-        c->tail_pending = false;
+    } else {
+        HIP_TRY(join_tail(c, st));  // a serial call after pipelined ones
     }
     if (tm) {
         HIP_TRY(hipEventRecord(c->ev[0], st));

@@ -36,6 +36,30 @@ static int upload_to(hpe_ctx* c, float** p, const std::vector<float>& h) {
     return HPE_OK;
 }
 
+// bf16 elements into a new buffer, or into the buffer *p already names (as upload_to)
+static int upload_bf16(hpe_ctx* c, void** p, const std::vector<unsigned short>& h) {
+    if (!*p) {
+        HIP_TRY(hipMalloc(p, h.size() * 2));
+        c->allocs.push_back(*p);
+    }
+    HIP_TRY(hipMemcpy(*p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+    return HPE_OK;
+}
+
+// (bf16 contexts keep bf16 elements behind the float* members of ConvLayer)
+static int upload_bf16(hpe_ctx* c, float** p, const std::vector<unsigned short>& h) {
+    void* q = *p;
+    const int rc = upload_bf16(c, &q, h);
+    *p = static_cast<float*>(q);
+    return rc;
+}
+
+static std::vector<unsigned short> to_bf16(const std::vector<float>& v) {
+    std::vector<unsigned short> h(v.size());
+    for (size_t q = 0; q < v.size(); ++q) h[q] = f2bf(v[q]);
+    return h;
+}
+
 // fp32 Wt[rows][K] -> bf16 [rows][3][K]: w = w0 + w1 + w2 exactly (finite weights), each piece rounded to nearest even (conv_gemm_f32s.hip)
 int upload_split(hpe_ctx* c, void** p, const std::vector<float>& wt, int rows, int K) {
     std::vector<unsigned short> ws((size_t)rows * 3 * K);
@@ -57,14 +81,7 @@ int upload_split(hpe_ctx* c, void** p, const std::vector<float>& wt, int rows, i
             d[K] = h1;
             d[2 * K] = f2bf(r2);
         }
-    void* q = *p;  // a buffer of an earlier call is written again (repack_encoder)
-    if (!q) {
-        HIP_TRY(hipMalloc(&q, ws.size() * 2));
-        c->allocs.push_back(q);
-    }
-    HIP_TRY(hipMemcpy(q, ws.data(), ws.size() * 2, hipMemcpyHostToDevice));
-    *p = q;
-    return HPE_OK;
+    return upload_bf16(c, p, ws);
 }
 
 #pragma GCC visibility push(default)
@@ -202,45 +219,35 @@ static int check_loaded(hpe_ctx* c) {
 //      out = relu([s2c W2c | s1 W1] . [t2 ; x] + (shift2c + shift1))   -- no shortcut tensor in HBM, one launch instead of two
 static int pack_dual_weights(hpe_ctx* c) {
     int rc;
-    int ci = 1;
-    const int nblk[4] = {3, 4, 6, 3};
-    for (int stg = 0; stg < 4; ++stg) {
-        const int i2c = ci + 2, i1 = ci + 3;
-        const ConvSpec& s2 = specs()[i2c];
-        const ConvSpec& s1 = specs()[i1];
-        ConvLayer& L2 = c->conv[i2c];
-        const ConvLayer& L1 = c->conv[i1];
+    const int slab = c->bf16 ? 64 : 32;
+    for (const ResBlock& blk : blocks()) {
+        if (!blk.first) continue;
+        const ConvSpec& s2 = specs()[blk.i2c];
+        const ConvSpec& s1 = specs()[blk.i1];
+        ConvLayer& L2 = c->conv[blk.i2c];
+        const ConvLayer& L1 = c->conv[blk.i1];
         const int K1 = s2.cin, K2 = s1.cin, N = s2.cout;
-        const int slab = c->bf16 ? 64 : 32;
-        if (K1 % slab == 0 && K2 % slab == 0) {
-            const int n_pad = round_up(N, 128), K = K1 + K2;
-            std::vector<float> wt((size_t)n_pad * K, 0.f), sh(N);
-            for (int n = 0; n < N; ++n) {
-                const double inv2 = (double)L2.gamma[n] / std::sqrt((double)L2.var[n] + (double)c->cfg.bn_eps);
-                const double inv1 = (double)L1.gamma[n] / std::sqrt((double)L1.var[n] + (double)c->cfg.bn_eps);
-                for (int k = 0; k < K1; ++k) wt[(size_t)n * K + k] = (float)(inv2 * (double)L2.kernel[(size_t)k * N + n]);
-                for (int k = 0; k < K2; ++k) wt[(size_t)n * K + K1 + k] = (float)(inv1 * (double)L1.kernel[(size_t)k * N + n]);
-                sh[n] = (float)((((double)L2.bias[n] - (double)L2.mean[n]) * inv2 + (double)L2.beta[n]) +
-                                (((double)L1.bias[n] - (double)L1.mean[n]) * inv1 + (double)L1.beta[n]));
-            }
-            if (c->bf16) {
-                std::vector<unsigned short> wb(wt.size());
-                for (size_t q = 0; q < wt.size(); ++q) wb[q] = f2bf(wt[q]);
-                void* qd = nullptr;
-                HIP_TRY(hipMalloc(&qd, wb.size() * 2));
-                c->allocs.push_back(qd);
-                HIP_TRY(hipMemcpy(qd, wb.data(), wb.size() * 2, hipMemcpyHostToDevice));
-                L2.w_dual = static_cast<float*>(qd);
-            } else {
-                if ((rc = upload_to(c, &L2.w_dual, wt))) return rc;
-                // f32_split: the folded weight is split (the BN scales are inside the pieces)
-                if ((c->plan.f32_split & stage_bit(s2.hout)) && (rc = upload_split(c, &L2.w_dual_split, wt, n_pad, K))) return rc;
-            }
-            if ((rc = upload_to(c, &L2.shift_dual, sh))) return rc;
-            L2.k_dual = K;
-            L2.k1_dual = K1;
+        if (K1 % slab != 0 || K2 % slab != 0) continue;
+        const int n_pad = round_up(N, 128), K = K1 + K2;
+        std::vector<float> wt((size_t)n_pad * K, 0.f), sh(N);
+        for (int n = 0; n < N; ++n) {
+            double inv2, inv1, shift2, shift1;
+            bn_fold(L2, n, c->cfg.bn_eps, &inv2, &shift2);
+            bn_fold(L1, n, c->cfg.bn_eps, &inv1, &shift1);
+            for (int k = 0; k < K1; ++k) wt[(size_t)n * K + k] = (float)(inv2 * (double)L2.kernel[(size_t)k * N + n]);
+            for (int k = 0; k < K2; ++k) wt[(size_t)n * K + K1 + k] = (float)(inv1 * (double)L1.kernel[(size_t)k * N + n]);
+            sh[n] = (float)(shift2 + shift1);
         }
-        ci += 4 + 3 * (nblk[stg] - 1);
+        if (c->bf16) {
+            if ((rc = upload_bf16(c, &L2.w_dual, to_bf16(wt)))) return rc;
+        } else {
+            if ((rc = upload_to(c, &L2.w_dual, wt))) return rc;
+            // f32_split: the folded weight is split (the BN scales are inside the pieces)
+            if ((c->plan.f32_split & stage_bit(s2.hout)) && (rc = upload_split(c, &L2.w_dual_split, wt, n_pad, K))) return rc;
+        }
+        if ((rc = upload_to(c, &L2.shift_dual, sh))) return rc;
+        L2.k_dual = K;
+        L2.k1_dual = K1;
     }
     return HPE_OK;
 }
@@ -299,83 +306,59 @@ static int pack_wino4_weights(hpe_ctx* c, const ConvSpec& s, ConvLayer& L) {
 
 // fused stem: the conv1 weights in the k enumeration of stem_fused.hip
 static int pack_stem_weights(hpe_ctx* c, ConvLayer& L) {
-    void* q = nullptr;
-    if (c->bf16) {
-        std::vector<unsigned short> wp((size_t)64 * 7 * 32, 0);
-        for (int kh = 0; kh < 7; ++kh)
-            for (int kw = 0; kw < 7; ++kw)
-                for (int ci = 0; ci < 3; ++ci)
-                    for (int n = 0; n < 64; ++n)
-                        wp[((size_t)n * 7 + kh) * 32 + kw * 4 + ci] = f2bf(L.kernel[(((size_t)kh * 7 + kw) * 3 + ci) * 64 + n]);
-        HIP_TRY(hipMalloc(&q, wp.size() * 2));
-        c->allocs.push_back(q);
-        HIP_TRY(hipMemcpy(q, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> wp((size_t)64 * 160, 0.f);
-        for (int kh = 0; kh < 7; ++kh)
-            for (int kw = 0; kw < 7; ++kw)
-                for (int ci = 0; ci < 3; ++ci)
-                    for (int n = 0; n < 64; ++n)
-                        wp[(size_t)n * 160 + kh * 22 + 1 + kw * 3 + ci] = L.kernel[(((size_t)kh * 7 + kw) * 3 + ci) * 64 + n];
-        q = L.stem_w;  // written again by repack_encoder
-        if (!q) {
-            HIP_TRY(hipMalloc(&q, wp.size() * 4));
-            c->allocs.push_back(q);
-        }
-        HIP_TRY(hipMemcpy(q, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
-    }
+    // bf16 [64][7][32], k as in Wt[n][k]; fp32 [64][160], k = kh * 22 + 1 + kw * 3 + ci
+    const size_t ld = c->bf16 ? 7 * 32 : 160;
+    std::vector<float> wp(64 * ld, 0.f);
+    for (int kh = 0; kh < 7; ++kh)
+        for (int kw = 0; kw < 7; ++kw)
+            for (int ci = 0; ci < 3; ++ci) {
+                const int k = c->bf16 ? conv_wt_k(0, kh, kw, ci) : kh * 22 + 1 + kw * 3 + ci;
+                for (int n = 0; n < 64; ++n) wp[n * ld + k] = L.kernel[(((size_t)kh * 7 + kw) * 3 + ci) * 64 + n];
+            }
+    if (c->bf16) return upload_bf16(c, &L.stem_w, to_bf16(wp));
+    float* q = static_cast<float*>(L.stem_w);
+    const int rc = upload_to(c, &q, wp);
     L.stem_w = q;
-    return HPE_OK;
+    return rc;
 }
 
 // ---- encoder weights: HWIO -> Wt[n][k] (k = (kh,kw,cin), cin fastest), zero padded; BN -> scale/shift
 static int pack_conv_weights(hpe_ctx* c) {
     int rc;
+    // k-slab of the GEMM kernels: 32 floats or 64 bf16; the bf16 stem slab s holds kernel rows (2s, 2s + 1), each 8 px x 4 ch
+    const int slab = c->bf16 ? 64 : 32;
     for (int i = 0; i < HPE_NUM_CONV; ++i) {
         const ConvSpec& s = specs()[i];
         ConvLayer& L = c->conv[i];
         L.n_pad = round_up(s.cout, 128);
-        if (c->bf16) {
-            // bf16: 64-element slabs; stem slab s = kernel rows (2s, 2s+1), each 8 px x 4 ch
-            L.k_pad = (i == 0) ? 4 * 64 : round_up(s.kh * s.kw * s.cin, 64);
-            std::vector<unsigned short> wt((size_t)L.n_pad * L.k_pad, 0);
-            for (int kh = 0; kh < s.kh; ++kh)
-                for (int kw = 0; kw < s.kw; ++kw)
-                    for (int ci = 0; ci < s.cin; ++ci) {
-                        const int k = (i == 0) ? (kh * 32 + kw * 4 + ci) : ((kh * s.kw + kw) * s.cin + ci);
-                        const float* src = &L.kernel[(((size_t)kh * s.kw + kw) * s.cin + ci) * s.cout];
-                        for (int n = 0; n < s.cout; ++n) wt[(size_t)n * L.k_pad + k] = f2bf(src[n]);
-                    }
-            void* q = nullptr;
-            HIP_TRY(hipMalloc(&q, wt.size() * 2));
-            c->allocs.push_back(q);
-            HIP_TRY(hipMemcpy(q, wt.data(), wt.size() * 2, hipMemcpyHostToDevice));
-            L.w = static_cast<float*>(q);
-        } else {
-        L.k_pad = (i == 0) ? 7 * 32 : round_up(s.kh * s.kw * s.cin, 32);
+        L.k_pad = (i == 0) ? round_up(7 * 32, slab) : round_up(s.kh * s.kw * s.cin, slab);
         std::vector<float> wt((size_t)L.n_pad * L.k_pad, 0.f);
         for (int kh = 0; kh < s.kh; ++kh)
             for (int kw = 0; kw < s.kw; ++kw)
                 for (int ci = 0; ci < s.cin; ++ci) {
-                    const int k = (i == 0) ? (kh * 32 + kw * 4 + ci) : ((kh * s.kw + kw) * s.cin + ci);
+                    const int k = conv_wt_k(i, kh, kw, ci);
                     const float* src = &L.kernel[(((size_t)kh * s.kw + kw) * s.cin + ci) * s.cout];
                     for (int n = 0; n < s.cout; ++n) wt[(size_t)n * L.k_pad + k] = src[n];
                 }
-        if ((rc = upload_to(c, &L.w, wt))) return rc;
-        if (i != 0 && s.kh == 1 && (c->plan.f32_split & stage_bit(s.hout)) && (rc = upload_split(c, &L.w_split, wt, L.n_pad, L.k_pad))) return rc;
-        if (c->plan.wino_min_c > 0 && s.kh == 3 && s.stride == 1 && s.cin % 32 == 0 && s.cout % 64 == 0 &&
-            (s.cin >= c->plan.wino_min_c || (c->plan.wino_fused && s.hin >= c->plan.wino_fused_min_hw)) && (rc = pack_wino_weights(c, s, L)))
-            return rc;
-        if (s.kh == 3 && s.stride == 1 && s.cin % 32 == 0 && s.cout % 64 == 0 && ((c->plan.wino_f4 | c->plan.wino4_fused) & f4_bit(s.hin)) &&
-            (rc = pack_wino4_weights(c, s, L)))
-            return rc;
+        if (c->bf16) {
+            if ((rc = upload_bf16(c, &L.w, to_bf16(wt)))) return rc;
+        } else {
+            if ((rc = upload_to(c, &L.w, wt))) return rc;
+            if (i != 0 && s.kh == 1 && (c->plan.f32_split & stage_bit(s.hout)) && (rc = upload_split(c, &L.w_split, wt, L.n_pad, L.k_pad))) return rc;
+            if (c->plan.wino_min_c > 0 && s.kh == 3 && s.stride == 1 && s.cin % 32 == 0 && s.cout % 64 == 0 &&
+                (s.cin >= c->plan.wino_min_c || (c->plan.wino_fused && s.hin >= c->plan.wino_fused_min_hw)) && (rc = pack_wino_weights(c, s, L)))
+                return rc;
+            if (s.kh == 3 && s.stride == 1 && s.cin % 32 == 0 && s.cout % 64 == 0 && ((c->plan.wino_f4 | c->plan.wino4_fused) & f4_bit(s.hin)) &&
+                (rc = pack_wino4_weights(c, s, L)))
+                return rc;
         }
         if (i == 0 && (rc = pack_stem_weights(c, L))) return rc;
         std::vector<float> sc(s.cout), sh(s.cout);
         for (int n = 0; n < s.cout; ++n) {
-            const double inv = (double)L.gamma[n] / std::sqrt((double)L.var[n] + (double)c->cfg.bn_eps);
-            sc[n] = (float)inv;
-            sh[n] = (float)(((double)L.bias[n] - (double)L.mean[n]) * inv + (double)L.beta[n]);
+            double scale, shift;
+            bn_fold(L, n, c->cfg.bn_eps, &scale, &shift);
+            sc[n] = (float)scale;
+            sh[n] = (float)shift;
         }
         if ((rc = upload_to(c, &L.scale, sc))) return rc;
         if ((rc = upload_to(c, &L.shift, sh))) return rc;
@@ -384,41 +367,43 @@ static int pack_conv_weights(hpe_ctx* c) {
     return HPE_OK;
 }
 
-// ---- regressor: Dense kernels [in,out] -> [out_pad][in_pad]; W1 split into features / theta parts
+// ---- regressor: Dense kernels [in,out] -> [out_pad][in_pad], W1 split into features / theta parts, and the Keras-major operands of the
+//      backward.  The layouts are stated once, by the set kernels of regressor_train.hip: finalize runs them on the loaded parameters.
 static int pack_regressor(hpe_ctx* c) {
     int rc;
-    const std::vector<float>& k1 = c->dense[0].kernel;  // [2133][1024]
-    std::vector<float> w1f((size_t)1024 * 2048), w1t((size_t)1024 * THETA_LD, 0.f);
-    for (int n = 0; n < 1024; ++n) {
-        for (int k = 0; k < 2048; ++k) w1f[(size_t)n * 2048 + k] = k1[(size_t)k * 1024 + n];
-        for (int k = 0; k < HPE_THETA_DIM; ++k) w1t[(size_t)n * THETA_LD + k] = k1[(size_t)(2048 + k) * 1024 + n];
+    // Zero-filled: the set kernels write the live elements only, so this fill is what keeps the padding rows and columns zero.  They are
+    // read: the theta GEMM feeds columns 85..95 of a theta row back as a K = 96 operand, and garbage there would reach the output.
+    const struct {
+        float** p;
+        size_t n;
+    } live[] = {
+        {&c->w1f, (size_t)1024 * 2048},
+        {&c->w1t, (size_t)1024 * THETA_LD},
+        {&c->w2, (size_t)1024 * 1024},
+        {&c->w3, (size_t)128 * 1024},
+        {&c->b1, 1024},
+        {&c->b2, 1024},
+        {&c->b3, 128},
+        {&c->mean_dev, HPE_THETA_DIM},
+        {&c->rt.w1k, (size_t)(2048 + 128) * 1024},
+        {&c->rt.w2k, (size_t)1024 * 1024},
+        {&c->rt.w3k, (size_t)1024 * THETA_LD},
+    };
+    for (const auto& b : live)
+        if ((rc = dev_alloc(c, b.p, b.n, true))) return rc;
+    // the flat layout (regressor_spec.flat_layout): kernel and bias of the three layers as loaded, then mean theta
+    std::vector<float> flat((size_t)regressor_param_offset(4, false));
+    for (int i = 0; i < HPE_NUM_DENSE; ++i) {
+        std::copy(c->dense[i].kernel.begin(), c->dense[i].kernel.end(), flat.begin() + regressor_param_offset(i, false));
+        std::copy(c->dense[i].bias.begin(), c->dense[i].bias.end(), flat.begin() + regressor_param_offset(i, true));
     }
-    const std::vector<float>& k2 = c->dense[1].kernel;
-    std::vector<float> w2((size_t)1024 * 1024);
-    for (int n = 0; n < 1024; ++n)
-        for (int k = 0; k < 1024; ++k) w2[(size_t)n * 1024 + k] = k2[(size_t)k * 1024 + n];
-    const std::vector<float>& k3 = c->dense[2].kernel;  // [1024][85]
-    std::vector<float> w3((size_t)128 * 1024, 0.f);
-    for (int n = 0; n < HPE_THETA_DIM; ++n)
-        for (int k = 0; k < 1024; ++k) w3[(size_t)n * 1024 + k] = k3[(size_t)k * HPE_THETA_DIM + n];
-    if ((rc = upload(c, &c->w1f, w1f))) return rc;
-    if ((rc = upload(c, &c->w1t, w1t))) return rc;
-    if ((rc = upload(c, &c->w2, w2))) return rc;
-    if ((rc = upload(c, &c->w3, w3))) return rc;
-    if ((rc = upload(c, &c->b1, c->dense[0].bias))) return rc;
-    if ((rc = upload(c, &c->b2, c->dense[1].bias))) return rc;
-    std::vector<float> b3(128, 0.f);
-    for (int n = 0; n < HPE_THETA_DIM; ++n) b3[n] = c->dense[2].bias[n];
-    if ((rc = upload(c, &c->b3, b3))) return rc;
-    if ((rc = upload(c, &c->mean_dev, std::vector<float>(c->h_mean, c->h_mean + HPE_THETA_DIM)))) return rc;
-    // the Keras [in][out] matrices as the backward's Wt[n][k] operands (hpe_ctx.h: RegTrainWork), zero padded
-    std::vector<float> w1k((size_t)(2048 + 128) * 1024, 0.f), w3k((size_t)1024 * THETA_LD, 0.f);
-    std::copy(k1.begin(), k1.end(), w1k.begin());
-    for (int k = 0; k < 1024; ++k)
-        for (int n = 0; n < HPE_THETA_DIM; ++n) w3k[(size_t)k * THETA_LD + n] = k3[(size_t)k * HPE_THETA_DIM + n];
-    if ((rc = upload(c, &c->rt.w1k, w1k))) return rc;
-    if ((rc = upload(c, &c->rt.w2k, k2))) return rc;
-    if ((rc = upload(c, &c->rt.w3k, w3k))) return rc;
+    std::copy(c->h_mean, c->h_mean + HPE_THETA_DIM, flat.begin() + regressor_param_offset(3, false));
+    float* tmp = nullptr;  // in c->allocs while it lives: a failure below leaves it to release_device_state
+    if ((rc = upload(c, &tmp, flat))) return rc;
+    HIP_TRY(regressor_params_copy(c, tmp, true, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    c->allocs.pop_back();
+    HIP_TRY(hipFree(tmp));
     return HPE_OK;
 }
 

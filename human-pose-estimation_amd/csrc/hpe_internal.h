@@ -5,6 +5,11 @@
 
 #include "../../include/hpe.h"
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));  // accumulator of v_mfma_f32_32x32x2_f32
+
+inline dim3 grid1(long n) { return dim3((unsigned)((n + 255) / 256)); }  // one thread per element, 256 a block
+
 // GEMM_DUAL: two A sources summed into one accumulator (K concatenated): k-slabs [0, k1_slabs) come from the dense matrix x
 // (row pitch lda), the rest from the strided NHWC tensor x2 (geometry in Hi / Wi / Cin / Ho / Wo / stride) -- the last 1x1
 // convolution of a ResNet conv_block and its projection shortcut as ONE launch (weights concatenated along k, BN scales folded in)
@@ -225,10 +230,9 @@ struct CriticW {  // device pointers into the ctx's one critic buffer
     const float* wt[HPE_NUM_CRITIC_DENSE];  // its transpose [out][in], read by the backward
     const float* b[HPE_NUM_CRITIC_DENSE];   // bias [out]
 };
-// the ctx's one critic buffer (per layer kernel | transposed kernel | bias, 16-byte aligned blocks): its size, its host image built from
-// a model in the Keras layouts (host: hpe_critic_live_floats() floats, all written), and the pointers into a buffer of that layout
+// the ctx's one critic buffer (per layer kernel | transposed kernel | bias, 16-byte aligned blocks, the padding zero): its size and the
+// pointers into a buffer of that layout.  hpe_launch_critic_params(set) is the one writer of its contents.
 size_t hpe_critic_live_floats();
-void hpe_critic_pack_live(const HpeCriticModel& m, float* host);
 CriticW hpe_critic_live_view(const float* buf);
 // joints [N][K][3] (the first 14 are read), betas: 10 floats per row, betas_stride floats apart, Rs [N][24][3][3] (the root is skipped);
 // scores [N][3], kcs [N][169] or nullptr.  One launch, no workspace.

@@ -63,7 +63,8 @@ int pick_bf16(const HpePlan& pl, int M, int N, int K, bool residual_expand, bool
 
 // which kernel a layer of a finalized context takes (the plan and the weights that were packed for it)
 struct hpe_ctx;
+struct ResBlock;
 bool use_wino4(const hpe_ctx* c, int idx, int B);
 bool use_wino4_fused(const hpe_ctx* c, int idx, int B);
 bool use_wino_fused(const hpe_ctx* c, int idx, int B);
-bool use_chain(const hpe_ctx* c, int stg, int i2c, bool first, bool has_next);
+bool use_chain(const hpe_ctx* c, const ResBlock& blk);

@@ -15,9 +15,16 @@
 
 namespace {
 
-// ResNet-50 v1 layer table, Keras names / order [2a, 2b, 2c, (1)] per block.
-std::vector<ConvSpec> build_specs() {
-    std::vector<ConvSpec> v;
+struct Network {
+    std::vector<ConvSpec> specs;
+    std::vector<ResBlock> blocks;
+};
+
+// ResNet-50 v1 layer table, Keras names / order [2a, 2b, 2c, (1)] per block, and the block table over it: the
+// one loop that numbers the layers also says which of them form a block
+Network build_network() {
+    Network net;
+    std::vector<ConvSpec>& v = net.specs;
     auto add = [&](const std::string& n, const std::string& b, int kh, int cin, int cout, int s, int hin, int hout) {
         ConvSpec c;
         snprintf(c.name, sizeof c.name, "%s", n.c_str());
@@ -34,11 +41,15 @@ std::vector<ConvSpec> build_specs() {
     const int nblk[4] = {3, 4, 6, 3};
     const int filt[4][3] = {{64, 64, 256}, {128, 128, 512}, {256, 256, 1024}, {512, 512, 2048}};
     int cin = 64, h = 56;
+    int in = -1;  // the layer that feeds the next block: the previous block's branch2c; the max-pooled map for the first
     for (int st = 0; st < 4; ++st) {
         for (int b = 0; b < nblk[st]; ++b) {
             const bool first = b == 0;
             const int s = (first && st > 0) ? 2 : 1;
             const int hout = h / s;
+            const int i2a = (int)v.size();
+            net.blocks.push_back(ResBlock{st, first, b == nblk[st] - 1, i2a, i2a + 1, i2a + 2, first ? i2a + 3 : -1, in});
+            in = i2a + 2;
             char base[24], bn[24];
             snprintf(base, sizeof base, "res%d%c_branch", st + 2, 'a' + b);
             snprintf(bn, sizeof bn, "bn%d%c_branch", st + 2, 'a' + b);
@@ -50,15 +61,18 @@ std::vector<ConvSpec> build_specs() {
             h = hout;
         }
     }
-    return v;
+    return net;
+}
+
+const Network& network() {
+    static const Network n = build_network();
+    return n;
 }
 
 }  // namespace
 
-const std::vector<ConvSpec>& specs() {
-    static const std::vector<ConvSpec> s = build_specs();
-    return s;
-}
+const std::vector<ConvSpec>& specs() { return network().specs; }
+const std::vector<ResBlock>& blocks() { return network().blocks; }
 
 // ---- the option table.  One row per HpePlan member that can be set from outside; precedence as documented in include/hpe.h: the HpeConfig
 // field if it is >= 0, else the environment variable, else the built-in default.  dflt / mask are {fp32 encoder, bf16 encoder}; the resolved
@@ -224,10 +238,12 @@ bool use_wino_fused(const hpe_ctx* c, int idx, int B) {
 }
 
 // the bf16 identity-block pair branch2c (idx i2c, + residual + ReLU) -> next block's branch2a (idx i2c + 1) as one launch
-// `first`: the conv_block form -- branch2c + the projection shortcut branch1 (idx i2c + 1, stride 1: stage 2 only) as the dual-source GEMM,
-// chained with the next block's branch2a (idx i2c + 2); bit 2 of chain_fuse
-bool use_chain(const hpe_ctx* c, int stg, int i2c, bool first, bool has_next) {
-    if (!has_next) return false;
+// blk.first: the conv_block form -- branch2c + the projection shortcut branch1 (idx i2c + 1, stride 1: stage 2 only) as the dual-source GEMM,
+// chained with the next block's branch2a (idx i2c + 2); bit 2 of chain_fuse.  The last block of a stage has no partner.
+bool use_chain(const hpe_ctx* c, const ResBlock& blk) {
+    if (blk.last) return false;
+    const int stg = blk.stage, i2c = blk.i2c;
+    const bool first = blk.first;
     const ConvSpec& s2 = specs()[i2c];
     if (!c->bf16) {
         // fp32: identity blocks of stage 2 only (conv_chain_f32.hip; bit 3 of chain_fuse, on by default: A/B on two boxes +0.3 ... +1.4 % at

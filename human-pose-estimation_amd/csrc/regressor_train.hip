@@ -26,8 +26,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int F = HPE_FEATURE_DIM, H = 1024, T = HPE_THETA_DIM, LD = THETA_LD;
 constexpr int IN1 = F + T;
 // the flat layout: dense_0/kernel [2133][1024], dense_0/bias, dense_1/kernel, dense_1/bias, dense_2/kernel [1024][85], dense_2/bias, mean theta
@@ -213,8 +211,6 @@ __global__ __launch_bounds__(256) void reg_wg_gemm_kernel(WgArgs a) {
         if (hi == 0 && b_ok) g.bias[col_b] = bs + other;
     }
 }
-
-inline dim3 grid1(long n) { return dim3((unsigned)((n + 255) / 256)); }
 
 RegW live(hpe_ctx* c) { return RegW{c->w1f, c->w1t, c->w2, c->w3, c->b1, c->b2, c->b3, c->mean_dev, c->rt.w1k, c->rt.w2k, c->rt.w3k}; }
 

@@ -193,6 +193,30 @@ def test_errors(engine):
     assert b"every output is NULL" in lib.hpe_last_error()
 
 
+def test_load_twice_replaces(engine, params):
+    """load_critic(Q) then load_critic(P) on one context leaves what load_critic(P) alone leaves, bit for bit: the scores, the input
+    gradients (the only readers of the transposed kernels) and critic_params().  N = 5 is two row tiles, the second partial."""
+    N, K = 5, 14
+    joints, betas, Rs = make_inputs(engine, params, N, K, seed=95)
+    names = ("joints", "betas", "Rs", "kcs")
+    twice, once = hpe_amd.HpeEngine(device=0, max_batch=8), hpe_amd.HpeEngine(device=0, max_batch=8)
+    try:
+        twice.load_critic(synthetic.make_critic_params(seed=2))
+        s_q = twice.critic(joints, betas, Rs).clone()
+        twice.load_critic(params)
+        once.load_critic(params)
+        s2, s1 = twice.critic(joints, betas, Rs), once.critic(joints, betas, Rs)
+        assert not torch.equal(s_q, s2)  # Q is another critic
+        assert torch.equal(s2.view(torch.int32), s1.view(torch.int32))
+        g2, g1 = twice.critic_backward(joints, betas, Rs, want=names), once.critic_backward(joints, betas, Rs, want=names)
+        for k in names:
+            assert torch.equal(g2[k].view(torch.int32), g1[k].view(torch.int32)), k
+        assert torch.equal(twice.critic_params().view(torch.int32), once.critic_params().view(torch.int32))
+    finally:
+        twice.close()
+        once.close()
+
+
 def test_bitwise_repeatable(engine, params):
     N = 300
     joints, betas, Rs = make_inputs(engine, params, N, 19, seed=31)
