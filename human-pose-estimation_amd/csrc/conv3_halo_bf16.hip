@@ -120,9 +120,7 @@ __global__ __launch_bounds__(BM * 2, A1 ? 4 : (BM == 256 ? 2 : 1)) void conv3_ha
     // consecutive workgroup ids share an XCD's L2 every 8th: give each XCD a contiguous run of tiles (neighbouring pixel tiles share
     // halo rows, the channel tiles of one pixel tile share the whole image)
     const int total = gridDim.x;
-    const int xcd = blockIdx.x & 7;
-    const int q = total >> 3, rr = total & 7;
-    const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (blockIdx.x >> 3);
+    const int swz = xcd_remap(blockIdx.x, total);
     const int mtile = __builtin_amdgcn_readfirstlane(swz / p.n_ntiles);  // (the division runs on the VALU)
     const int n0 = (swz - mtile * p.n_ntiles) * BN;
     const int m0 = mtile * BM;

@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "conv_gemm_common.h"
+#include "gemm_contract.h"
 #include "hpe_internal.h"
 
 namespace {
@@ -70,9 +71,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 2) void conv_gemm_f32_dma
         ks0 = (int)((long)part * S / p.split_k);
         ks1 = (int)((long)(part + 1) * S / p.split_k);
     } else {
-        const int xcd = bid & 7;
-        const int q = total >> 3, rr = total & 7;
-        tile = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+        tile = xcd_remap(bid, total);
     }
     const int mtile = tile / p.n_ntiles;
     const int ntile = tile - mtile * p.n_ntiles;
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 2) void conv_gemm_f32_dma
 #pragma unroll
     for (int i = 0; i < AP; ++i) {
         const int r = (NW * i + wave) * 8 + drow;
-        const int lc = (lane & 7) ^ ((r >> 1) & 7);
+        const int lc = (lane & 7) ^ ((r >> 1) & 7);  // 0..7: make_row's stem branch needs lc * 4 < 32
         arow[i] = make_row<MODE>(p, m0 + r, lc * 4);
         if (MODE == GEMM_DUAL) arow2[i] = make_row<GEMM_STRIDED>(p, m0 + r, lc * 4).base;
     }
@@ -265,8 +264,10 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm_fixup_kernel(GemmArgs 
     conv_epilogue<BM, BN, WM, WN>(p, lds, acc, mtile * BM, ntile * BN, t, lane, wm, wn, no_pre, false);
 }
 
-template <int MODE, int BM, int BN, int WM, int WN>
+template <int MODE, int TILE>
 hipError_t launch_cfg(GemmArgs& p, int splitk_min_slabs, hipStream_t st) {
+    constexpr TileShape T = tile_shape(GEMM_K_F32, TILE);
+    constexpr int BM = T.bm, BN = T.bn, WM = T.wm, WN = T.wn;
     p.n_mtiles = (p.M + BM - 1) / BM;
     p.n_ntiles = (p.N + BN - 1) / BN;
     const int grid = p.n_mtiles * p.n_ntiles;
@@ -293,57 +294,17 @@ hipError_t launch_cfg(GemmArgs& p, int splitk_min_slabs, hipStream_t st) {
     }
 }
 
+// the one place that instantiates the kernels: a tile id is a shape only through tile_shape (gemm_contract.h)
 template <int MODE>
 hipError_t launch_mode(GemmArgs& p, int tile, int splitk_min_slabs, hipStream_t st) {
     switch (tile) {
-        case TILE_128x128: return launch_cfg<MODE, 128, 128, 2, 2>(p, splitk_min_slabs, st);
-        case TILE_128x64: return launch_cfg<MODE, 128, 64, 2, 2>(p, splitk_min_slabs, st);
-        case TILE_64x64: return launch_cfg<MODE, 64, 64, 2, 2>(p, splitk_min_slabs, st);
-        case TILE_64x128: return launch_cfg<MODE, 64, 128, 2, 2>(p, splitk_min_slabs, st);
-        case TILE_128x128_W8: return launch_cfg<MODE, 128, 128, 2, 4>(p, splitk_min_slabs, st);
-        case TILE_128x64_W8: return launch_cfg<MODE, 128, 64, 4, 2>(p, splitk_min_slabs, st);
-        case TILE_256x128_W8: return launch_cfg<MODE, 256, 128, 4, 2>(p, splitk_min_slabs, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-// Host-side shape contract (checked here so a bad plan cannot fault on the device).
-hipError_t check_and_launch(GemmArgs& p, int mode, int tile, int splitk_min_slabs, hipStream_t st) {
-    if (splitk_min_slabs < 2) return hipErrorInvalidValue;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.K % BK) != 0 || (p.ldw % 4) != 0 || p.ldw < p.K) return hipErrorInvalidValue;
-    if (!p.x || !p.w || !p.y || !p.scale || !p.shift || !p.zero) return hipErrorInvalidValue;
-    // vector epilogue: 16-B aligned rows of y / residual
-    if ((p.ldy % 4) != 0 || ((uintptr_t)p.y & 15) != 0) return hipErrorInvalidValue;
-    if (p.y_slab8 && (p.N % 8) != 0) return hipErrorInvalidValue;
-    if (p.res && ((p.ldres % 4) != 0 || ((uintptr_t)p.res & 15) != 0)) return hipErrorInvalidValue;
-    if (((uintptr_t)p.x & 15) != 0 || ((uintptr_t)p.w & 15) != 0) return hipErrorInvalidValue;
-    const int bn = (tile == TILE_128x128 || tile == TILE_64x128 || tile == TILE_128x128_W8 || tile == TILE_256x128_W8) ? 128 : 64;
-    const int n_pad = ((p.N + bn - 1) / bn) * bn;
-    if (n_pad > p.w_rows) return hipErrorInvalidValue;  // packed weights must cover the padded N tiles
-    switch (mode) {
-        case GEMM_DENSE:
-            if (p.lda < p.K || (p.lda % 4) != 0) return hipErrorInvalidValue;
-            return launch_mode<GEMM_DENSE>(p, tile, splitk_min_slabs, st);
-        case GEMM_STRIDED:
-            if (p.Cin != p.K || (p.Cin % 4) != 0) return hipErrorInvalidValue;
-            if (p.Ho < 1 || p.Wo < 1 || p.stride < 1) return hipErrorInvalidValue;  // the kernel divides by Ho * Wo and by Wo
-            if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_mode<GEMM_STRIDED>(p, tile, splitk_min_slabs, st);
-        case GEMM_CONV3:
-            if ((p.Cin % BK) != 0 || p.K != 9 * p.Cin || p.cin_slabs != p.Cin / BK || p.Ho != p.Hi || p.Wo != p.Wi)
-                return hipErrorInvalidValue;
-            if (p.Hi < 1 || p.Wi < 1) return hipErrorInvalidValue;
-            return launch_mode<GEMM_CONV3>(p, tile, splitk_min_slabs, st);
-        case GEMM_STEM:
-            if (p.K != 7 * BK || p.Hi < 2 * (p.Ho - 1) + 7 || p.Wi < 2 * (p.Wo - 1) + 8) return hipErrorInvalidValue;
-            return launch_mode<GEMM_STEM>(p, tile, splitk_min_slabs, st);
-        case GEMM_DUAL:
-            if (!p.x2 || ((uintptr_t)p.x2 & 15) != 0 || p.k1_slabs < 1 || p.k1_slabs * BK >= p.K || p.lda < p.k1_slabs * BK || (p.lda % 4) != 0)
-                return hipErrorInvalidValue;
-            if (p.Ho < 1 || p.Wo < 1 || p.stride < 1) return hipErrorInvalidValue;  // before the host's own division by Ho * Wo
-            if (p.Cin != p.K - p.k1_slabs * BK || (p.Cin % 4) != 0 || p.M != (p.M / (p.Ho * p.Wo)) * p.Ho * p.Wo) return hipErrorInvalidValue;
-            if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_mode<GEMM_DUAL>(p, tile, splitk_min_slabs, st);
+        case TILE_128x128: return launch_cfg<MODE, TILE_128x128>(p, splitk_min_slabs, st);
+        case TILE_128x64: return launch_cfg<MODE, TILE_128x64>(p, splitk_min_slabs, st);
+        case TILE_64x64: return launch_cfg<MODE, TILE_64x64>(p, splitk_min_slabs, st);
+        case TILE_64x128: return launch_cfg<MODE, TILE_64x128>(p, splitk_min_slabs, st);
+        case TILE_128x128_W8: return launch_cfg<MODE, TILE_128x128_W8>(p, splitk_min_slabs, st);
+        case TILE_128x64_W8: return launch_cfg<MODE, TILE_128x64_W8>(p, splitk_min_slabs, st);
+        case TILE_256x128_W8: return launch_cfg<MODE, TILE_256x128_W8>(p, splitk_min_slabs, st);
         default: return hipErrorInvalidValue;
     }
 }
@@ -352,7 +313,16 @@ hipError_t check_and_launch(GemmArgs& p, int mode, int tile, int splitk_min_slab
 
 hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, int splitk_min_slabs, hipStream_t st, int* split_k_out) {
     p.split_k = 0;
-    const hipError_t e = check_and_launch(p, mode, tile, splitk_min_slabs, st);
+    hipError_t e = hipErrorInvalidValue;
+    if (splitk_min_slabs >= 2 && !gemm_contract(p, mode, tile, GEMM_K_F32)) {
+        switch (mode) {
+            case GEMM_DENSE: e = launch_mode<GEMM_DENSE>(p, tile, splitk_min_slabs, st); break;
+            case GEMM_STRIDED: e = launch_mode<GEMM_STRIDED>(p, tile, splitk_min_slabs, st); break;
+            case GEMM_CONV3: e = launch_mode<GEMM_CONV3>(p, tile, splitk_min_slabs, st); break;
+            case GEMM_STEM: e = launch_mode<GEMM_STEM>(p, tile, splitk_min_slabs, st); break;
+            case GEMM_DUAL: e = launch_mode<GEMM_DUAL>(p, tile, splitk_min_slabs, st); break;
+        }
+    }
     if (split_k_out) *split_k_out = p.split_k;  // 0: rejected before a launcher ran
     return e;
 }

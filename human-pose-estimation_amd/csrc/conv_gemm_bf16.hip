@@ -8,37 +8,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bf16_rows.h"
+#include "conv_gemm_common.h"
+#include "gemm_contract.h"
 #include "hpe_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-#include "bf16_rows.h"
-
 namespace {
-
-struct SlabB {
-    int off, tap, cs;
-};
-
-template <int MODE>
-__device__ __forceinline__ void slab_advance_b(const GemmArgs& p, SlabB& sp) {
-    if (MODE == GEMM_DENSE || MODE == GEMM_STRIDED || MODE == GEMM_DUAL) {
-        sp.off += BKE;
-    } else if (MODE == GEMM_CONV3) {
-        sp.cs += 1;
-        sp.off += BKE;
-        if (sp.cs == p.cin_slabs) {
-            sp.cs = 0;
-            sp.tap += 1;
-            const int kh = sp.tap / 3;
-            sp.off = ((kh - 1) * p.Wi + (sp.tap - kh * 3 - 1)) * p.Cin;
-        }
-    } else {
-        sp.off += 2 * p.Wi * 4;
-    }
-}
 
 // NS = LDS ring depth: NS - 1 slabs in flight behind counted vmcnt waits and a raw s_barrier (one barrier per slab).  NS = 2 is
 // the shipped configuration.  NS = 3 (instantiated for the 128x128 and 256x128 tiles at the time, removed since) was the experiment "is the slab DMA
@@ -71,9 +48,7 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 || BM * BN >= 256 * 128) ? (W
 
     const int total = p.n_mtiles * p.n_ntiles;
     const int bid = blockIdx.x;
-    const int xcd = bid & 7;
-    const int q = total >> 3, rr = total & 7;
-    const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int swz = xcd_remap(bid, total);
     const int mtile = swz / p.n_ntiles;
     const int ntile = swz - mtile * p.n_ntiles;
     const int m0 = mtile * BM;
@@ -86,7 +61,7 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 || BM * BN >= 256 * 128) ? (W
     const int wn = wave - wm * WN;
 
     const int drow = lane >> 3;
-    RowB arow[AP];
+    RowAddr arow[AP];
     int arow2[MODE == GEMM_DUAL ? AP : 1];  // GEMM_DUAL: the same rows in the second (strided) source
     const __bf16* X2 = reinterpret_cast<const __bf16*>(p.x2);
     const __bf16* wsrc[BP];
@@ -94,8 +69,8 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 || BM * BN >= 256 * 128) ? (W
     for (int i = 0; i < AP; ++i) {
         const int r = (NW * i + wave) * 8 + drow;
         const int lc = (lane & 7) ^ ((r >> 1) & 7);
-        arow[i] = make_row_b<MODE>(p, m0 + r, lc);
-        if (MODE == GEMM_DUAL) arow2[i] = make_row_b<GEMM_STRIDED>(p, m0 + r, lc).base;
+        arow[i] = make_row<MODE, 8>(p, m0 + r, lc);
+        if (MODE == GEMM_DUAL) arow2[i] = make_row<GEMM_STRIDED, 8>(p, m0 + r, lc).base;
     }
 #pragma unroll
     for (int i = 0; i < BP; ++i) {
@@ -147,10 +122,7 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 || BM * BN >= 256 * 128) ? (W
     }
 
     const int S = p.K / BKE;
-    SlabB sp;
-    sp.tap = 0;
-    sp.cs = 0;
-    sp.off = (MODE == GEMM_CONV3) ? (-p.Wi - 1) * p.Cin : 0;
+    SlabPos sp = slab_first<MODE>(p);
 
     auto issue_dma = [&](int slab, int buf) {
 #pragma unroll
@@ -179,7 +151,7 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 || BM * BN >= 256 * 128) ? (W
     {
         const int npre = (NS - 1 < S) ? NS - 1 : S;
         for (int i = 0; i < npre; ++i) {
-            if (i > 0) slab_advance_b<MODE>(p, sp);
+            if (i > 0) slab_advance<MODE, BKE, 2>(p, sp);
             issue_dma(i, i * BUF);
         }
     }
@@ -203,7 +175,7 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 || BM * BN >= 256 * 128) ? (W
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             if (s + NS - 1 < S) {
-                slab_advance_b<MODE>(p, sp);
+                slab_advance<MODE, BKE, 2>(p, sp);
                 issue_dma(s + NS - 1, nxt);
             }
 #pragma unroll
@@ -287,26 +259,28 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 || BM * BN >= 256 * 128) ? (W
     }
 }
 
-template <int MODE, int BM, int BN, int WM, int WN, int NS>
-hipError_t launch_cfg_b(GemmArgs& p, hipStream_t st) {
+// ring depth 2 everywhere: a 3-deep ring lost on the two tiles it was measured on
+template <int MODE, int TILE>
+hipError_t launch_cfg(GemmArgs& p, hipStream_t st) {
+    constexpr TileShape T = tile_shape(GEMM_K_BF16, TILE);
+    constexpr int BM = T.bm, BN = T.bn, WM = T.wm, WN = T.wn;
     p.n_mtiles = (p.M + BM - 1) / BM;
     p.n_ntiles = (p.N + BN - 1) / BN;
     p.res_prefetch = 1;
-    hipLaunchKernelGGL((conv_gemm_bf16_dma_kernel<MODE, BM, BN, WM, WN, NS>), dim3(p.n_mtiles * p.n_ntiles), dim3(64 * WM * WN), 0, st, p);
+    hipLaunchKernelGGL((conv_gemm_bf16_dma_kernel<MODE, BM, BN, WM, WN, 2>), dim3(p.n_mtiles * p.n_ntiles), dim3(64 * WM * WN), 0, st, p);
     return hipGetLastError();
 }
 
-// ring depth 2 everywhere: a 3-deep ring lost on the two tiles it was measured on
 template <int MODE>
-hipError_t launch_mode_b(GemmArgs& p, int tile, hipStream_t st) {
+hipError_t launch_mode(GemmArgs& p, int tile, hipStream_t st) {
     switch (tile) {
-        case TILE_128x128: return launch_cfg_b<MODE, 128, 128, 2, 2, 2>(p, st);
-        case TILE_128x64: return launch_cfg_b<MODE, 128, 64, 2, 2, 2>(p, st);
-        case TILE_64x64: return launch_cfg_b<MODE, 64, 64, 2, 2, 2>(p, st);
-        case TILE_64x128: return launch_cfg_b<MODE, 64, 128, 2, 2, 2>(p, st);
-        case TILE_128x128_W8: return launch_cfg_b<MODE, 128, 128, 2, 4, 2>(p, st);
-        case TILE_128x64_W8: return launch_cfg_b<MODE, 128, 64, 4, 2, 2>(p, st);
-        case TILE_256x128_W8: return launch_cfg_b<MODE, 256, 128, 4, 2, 2>(p, st);
+        case TILE_128x128: return launch_cfg<MODE, TILE_128x128>(p, st);
+        case TILE_128x64: return launch_cfg<MODE, TILE_128x64>(p, st);
+        case TILE_64x64: return launch_cfg<MODE, TILE_64x64>(p, st);
+        case TILE_64x128: return launch_cfg<MODE, TILE_64x128>(p, st);
+        case TILE_128x128_W8: return launch_cfg<MODE, TILE_128x128_W8>(p, st);
+        case TILE_128x64_W8: return launch_cfg<MODE, TILE_128x64_W8>(p, st);
+        case TILE_256x128_W8: return launch_cfg<MODE, TILE_256x128_W8>(p, st);
         default: return hipErrorInvalidValue;
     }
 }
@@ -405,34 +379,13 @@ inline int grid_for(long total, int block, int cap = 2048) {
 
 hipError_t hpe_launch_gemm_bf16(GemmArgs p, int mode, int tile, hipStream_t st) {
     if (tile == TILE_P8_256x256) return hpe_launch_gemm_bf16_p8(p, mode, st);
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.K % BKE) != 0 || (p.ldw % 8) != 0 || p.ldw < p.K) return hipErrorInvalidValue;
-    if (!p.x || !p.w || !p.y || !p.scale || !p.shift || !p.zero) return hipErrorInvalidValue;
-    if ((p.ldy % 8) != 0 || ((uintptr_t)p.y & 15) != 0) return hipErrorInvalidValue;
-    if (p.res && ((p.ldres % 8) != 0 || ((uintptr_t)p.res & 15) != 0)) return hipErrorInvalidValue;
-    if (((uintptr_t)p.x & 15) != 0 || ((uintptr_t)p.w & 15) != 0) return hipErrorInvalidValue;
-    const int bn = (tile == TILE_128x128 || tile == TILE_64x128 || tile == TILE_128x128_W8 || tile == TILE_256x128_W8) ? 128 : 64;
-    if (((p.N + bn - 1) / bn) * bn > p.w_rows) return hipErrorInvalidValue;
+    if (gemm_contract(p, mode, tile, GEMM_K_BF16)) return hipErrorInvalidValue;
     switch (mode) {
-        case GEMM_DENSE:
-            if (p.lda < p.K || (p.lda % 8) != 0) return hipErrorInvalidValue;
-            return launch_mode_b<GEMM_DENSE>(p, tile, st);
-        case GEMM_STRIDED:
-            if (p.Cin != p.K || (p.Cin % 8) != 0) return hipErrorInvalidValue;
-            if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_mode_b<GEMM_STRIDED>(p, tile, st);
-        case GEMM_CONV3:
-            if ((p.Cin % BKE) != 0 || p.K != 9 * p.Cin || p.cin_slabs != p.Cin / BKE || p.Ho != p.Hi || p.Wo != p.Wi)
-                return hipErrorInvalidValue;
-            return launch_mode_b<GEMM_CONV3>(p, tile, st);
-        case GEMM_STEM:
-            if (p.K != 4 * BKE || p.Hi < 2 * (p.Ho - 1) + 8 || p.Wi < 2 * (p.Wo - 1) + 8) return hipErrorInvalidValue;
-            return launch_mode_b<GEMM_STEM>(p, tile, st);
-        case GEMM_DUAL:
-            if (!p.x2 || ((uintptr_t)p.x2 & 15) != 0 || p.k1_slabs < 1 || p.k1_slabs * BKE >= p.K || p.lda < p.k1_slabs * BKE || (p.lda % 8) != 0)
-                return hipErrorInvalidValue;
-            if (p.Cin != p.K - p.k1_slabs * BKE || (p.Cin % 8) != 0 || p.M != (p.M / (p.Ho * p.Wo)) * p.Ho * p.Wo) return hipErrorInvalidValue;
-            if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_mode_b<GEMM_DUAL>(p, tile, st);
+        case GEMM_DENSE: return launch_mode<GEMM_DENSE>(p, tile, st);
+        case GEMM_STRIDED: return launch_mode<GEMM_STRIDED>(p, tile, st);
+        case GEMM_CONV3: return launch_mode<GEMM_CONV3>(p, tile, st);
+        case GEMM_STEM: return launch_mode<GEMM_STEM>(p, tile, st);
+        case GEMM_DUAL: return launch_mode<GEMM_DUAL>(p, tile, st);
         default: return hipErrorInvalidValue;
     }
 }

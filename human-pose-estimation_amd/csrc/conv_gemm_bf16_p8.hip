@@ -32,17 +32,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bf16_rows.h"
+#include "conv_gemm_common.h"
+#include "gemm_contract.h"
 #include "hpe_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-#include "bf16_rows.h"
 
 namespace {
 
-constexpr int P8_BM = 256, P8_BN = 256, P8_THREADS = 512;
+constexpr TileShape P8 = tile_shape(GEMM_K_BF16_P8, TILE_P8_256x256);
+constexpr int P8_BM = P8.bm, P8_BN = P8.bn, P8_THREADS = 64 * P8.wm * P8.wn;
 constexpr int P8_BUF = (P8_BM + P8_BN) * RF;  // floats per k-tile buffer (64 KB)
 constexpr int P8_EP = P8_BN + 4;              // epilogue staging pitch (floats)
 
@@ -122,9 +122,7 @@ __global__ __launch_bounds__(P8_THREADS, 1) void conv_gemm_bf16_p8_kernel(GemmAr
     const int tiles = p.n_mtiles * p.n_ntiles;
     const int total = tiles * p.split_k;
     const int bid = blockIdx.x;
-    const int xcd = bid & 7;
-    const int q = total >> 3, rr = total & 7;
-    const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int swz = xcd_remap(bid, total);
     const int part = swz % p.split_k;
     const int tile = swz / p.split_k;
     const int mtile = tile / p.n_ntiles;
@@ -146,12 +144,12 @@ __global__ __launch_bounds__(P8_THREADS, 1) void conv_gemm_bf16_p8_kernel(GemmAr
     //      depend on d, so one chunk index serves all rounds
     const int drow = wave * 8 + (lane >> 3);
     const int lc = (lane & 7) ^ ((drow >> 1) & 7);
-    RowB arow[4];
+    RowAddr arow[4];
     int arow2[MODE == GEMM_DUAL ? 4 : 1];
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
-        arow[d] = make_row_b<MODE>(p, m0 + 64 * d + drow, lc);
-        if (MODE == GEMM_DUAL) arow2[d] = make_row_b<GEMM_STRIDED>(p, m0 + 64 * d + drow, lc).base;
+        arow[d] = make_row<MODE, 8>(p, m0 + 64 * d + drow, lc);
+        if (MODE == GEMM_DUAL) arow2[d] = make_row<GEMM_STRIDED, 8>(p, m0 + 64 * d + drow, lc).base;
     }
     const __bf16* wsrc[4];
 #pragma unroll
@@ -382,32 +380,13 @@ hipError_t launch_p8(GemmArgs& p, hipStream_t st) {
 
 }  // namespace
 
-// Host-side contract as hpe_launch_gemm_bf16 (conv_gemm_bf16.hip), plus: N % 8 == 0 rows of 16 B, cin_slabs a power of two.
 hipError_t hpe_launch_gemm_bf16_p8(GemmArgs p, int mode, hipStream_t st) {
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.K % BKE) != 0 || (p.ldw % 8) != 0 || p.ldw < p.K || p.w_rows < 1) return hipErrorInvalidValue;
-    if (!p.x || !p.w || !p.y || !p.scale || !p.shift || !p.zero) return hipErrorInvalidValue;
-    if ((p.ldy % 8) != 0 || ((uintptr_t)p.y & 15) != 0) return hipErrorInvalidValue;
-    if (p.res && ((p.ldres % 8) != 0 || ((uintptr_t)p.res & 15) != 0)) return hipErrorInvalidValue;
-    if (((uintptr_t)p.x & 15) != 0 || ((uintptr_t)p.w & 15) != 0 || ((uintptr_t)p.zero & 15) != 0) return hipErrorInvalidValue;
-    if (p.partial && ((uintptr_t)p.partial & 15) != 0) return hipErrorInvalidValue;
+    if (gemm_contract(p, mode, TILE_P8_256x256, GEMM_K_BF16_P8)) return hipErrorInvalidValue;
     switch (mode) {
-        case GEMM_DENSE:
-            if (p.lda < p.K || (p.lda % 8) != 0) return hipErrorInvalidValue;
-            return launch_p8<GEMM_DENSE>(p, st);
-        case GEMM_STRIDED:
-            if (p.Cin != p.K || (p.Cin % 8) != 0) return hipErrorInvalidValue;
-            if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_p8<GEMM_STRIDED>(p, st);
-        case GEMM_CONV3:
-            if ((p.Cin % BKE) != 0 || p.K != 9 * p.Cin || p.cin_slabs != p.Cin / BKE || p.Ho != p.Hi || p.Wo != p.Wi) return hipErrorInvalidValue;
-            if ((p.cin_slabs & (p.cin_slabs - 1)) != 0) return hipErrorInvalidValue;
-            return launch_p8<GEMM_CONV3>(p, st);
-        case GEMM_DUAL:
-            if (!p.x2 || ((uintptr_t)p.x2 & 15) != 0 || p.k1_slabs < 1 || p.k1_slabs * BKE >= p.K || p.lda < p.k1_slabs * BKE || (p.lda % 8) != 0)
-                return hipErrorInvalidValue;
-            if (p.Cin != p.K - p.k1_slabs * BKE || (p.Cin % 8) != 0 || p.M != (p.M / (p.Ho * p.Wo)) * p.Ho * p.Wo) return hipErrorInvalidValue;
-            if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_p8<GEMM_DUAL>(p, st);
+        case GEMM_DENSE: return launch_p8<GEMM_DENSE>(p, st);
+        case GEMM_STRIDED: return launch_p8<GEMM_STRIDED>(p, st);
+        case GEMM_CONV3: return launch_p8<GEMM_CONV3>(p, st);
+        case GEMM_DUAL: return launch_p8<GEMM_DUAL>(p, st);
         default: return hipErrorInvalidValue;
     }
 }

@@ -1,31 +1,33 @@
-// conv_gemm_common.h -- pieces shared by the fp32 implicit-GEMM kernels (conv_gemm.hip, conv_gemm_f32s.hip): the A-row addressing of
-// the implicit GEMM and the epilogue (BN scale/shift, residual, ReLU, row stores).  Included inside an anonymous namespace.
+// conv_gemm_common.h -- pieces shared by the implicit-GEMM kernels: the A-row addressing and the k-slab walk of the implicit GEMM (all four:
+// conv_gemm.hip, conv_gemm_f32s.hip, conv_gemm_bf16.hip, conv_gemm_bf16_p8.hip) and the fp32 epilogue (BN scale/shift, residual, ReLU, row
+// stores; conv_gemm.hip, conv_gemm_f32s.hip).  Everything here is in an anonymous namespace.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "hpe_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define BK 32
 
 namespace {
 
 // Per-thread description of one staged A row: element offset of its first k element (+ this thread's
-// 16-B chunk) and, for the 3x3 conv, a 9-bit mask of the taps that fall inside the image.
+// 16-B chunk) and, for the 3x3 conv, a 9-bit mask of the taps that fall inside the image.  Offsets are in elements of the kernel's
+// type (fp32 or bf16).  c * CHUNK is the element offset of the thread's 16-B chunk inside the 128-B slab row, chunk = 0..7 (the callers form
+// it as (lane & 7) ^ swizzle).  Two conventions, because where the multiply is written decides the instruction order hipcc emits and the
+// device code of every kernel is kept as it was: the fp32 kernels pass chunk * 4 (c = 0, 4, .., 28) with CHUNK = 1, the bf16 kernels the
+// chunk itself with CHUNK = 8.  PRECONDITION of the stem branch: c * CHUNK < 32 in fp32 (one kernel row per slab), < 64 in bf16 (two).
 struct RowAddr {
     int base;
     unsigned mask;
 };
 
-template <int MODE>
-__device__ __forceinline__ RowAddr make_row(const GemmArgs& p, int m, int kc4) {
+template <int MODE, int CHUNK = 1>
+__device__ __forceinline__ RowAddr make_row(const GemmArgs& p, int m, int c) {
     RowAddr r;
     r.mask = 0x1ffu;
     if (m >= p.M) m = p.M - 1;  // tail rows: read a valid row, the store guard drops the result
     if (MODE == GEMM_DENSE || MODE == GEMM_DUAL) {
-        r.base = m * p.lda + kc4;
+        r.base = m * p.lda + c * CHUNK;
     } else {
         const int hw = p.Ho * p.Wo;
         const int b = m / hw;
@@ -33,9 +35,9 @@ __device__ __forceinline__ RowAddr make_row(const GemmArgs& p, int m, int kc4) {
         const int ho = rem / p.Wo;
         const int wo = rem - ho * p.Wo;
         if (MODE == GEMM_STRIDED) {
-            r.base = ((b * p.Hi + ho * p.stride) * p.Wi + wo * p.stride) * p.Cin + kc4;
+            r.base = ((b * p.Hi + ho * p.stride) * p.Wi + wo * p.stride) * p.Cin + c * CHUNK;
         } else if (MODE == GEMM_CONV3) {
-            r.base = ((b * p.Hi + ho) * p.Wi + wo) * p.Cin + kc4;
+            r.base = ((b * p.Hi + ho) * p.Wi + wo) * p.Cin + c * CHUNK;
             unsigned mk = 0;
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
@@ -43,27 +45,29 @@ __device__ __forceinline__ RowAddr make_row(const GemmArgs& p, int m, int kc4) {
                 if ((unsigned)(ho + dh) < (unsigned)p.Hi && (unsigned)(wo + dw) < (unsigned)p.Wi) mk |= 1u << tap;
             }
             r.mask = mk;
-        } else {  // GEMM_STEM: padded input [B,Hi,Wi,4], 8 pixels x 4 ch = one 32-float slab per kh
-            r.base = ((b * p.Hi + 2 * ho) * p.Wi + 2 * wo) * 4 + kc4;
+        } else {  // GEMM_STEM: padded input [B,Hi,Wi,4], 8 pixels x 4 ch = 32 elements per kernel row: a 32-float slab is one row (c < 32, so
+                  // c >> 5 is 0: see the precondition above), a 64-bf16 slab two
+            r.base = ((b * p.Hi + 2 * ho + (c * CHUNK >> 5)) * p.Wi + 2 * wo) * 4 + (c * CHUNK & 31);
         }
     }
     return r;
 }
 
-// Wave-uniform position of a k-slab inside the (kh, kw, cin) axis; advanced once per slab with scalar ops.
+// Wave-uniform position of a k-slab inside the (kh, kw, cin) axis; advanced once per slab with scalar ops.  slab_advance -- SLAB: elements
+// per k-slab (BK floats, or 64 bf16); STEM_ROWS: kernel rows of the stem's padded input per slab.  slab_seek (split-K) is fp32's alone.
 struct SlabPos {
     int off;   // element offset added to every row base
     int tap;   // CONV3: kh*3+kw
     int cs;    // CONV3: cin slab inside the tap
 };
 
-template <int MODE>
+template <int MODE, int SLAB = BK, int STEM_ROWS = 1>
 __device__ __forceinline__ void slab_advance(const GemmArgs& p, SlabPos& sp) {
     if (MODE == GEMM_DENSE || MODE == GEMM_STRIDED || MODE == GEMM_DUAL) {
-        sp.off += BK;
+        sp.off += SLAB;
     } else if (MODE == GEMM_CONV3) {
         sp.cs += 1;
-        sp.off += BK;
+        sp.off += SLAB;
         if (sp.cs == p.cin_slabs) {
             sp.cs = 0;
             sp.tap += 1;
@@ -71,7 +75,7 @@ __device__ __forceinline__ void slab_advance(const GemmArgs& p, SlabPos& sp) {
             sp.off = ((kh - 1) * p.Wi + (sp.tap - kh * 3 - 1)) * p.Cin;
         }
     } else {
-        sp.off += p.Wi * 4;
+        sp.off += STEM_ROWS * p.Wi * 4;
     }
 }
 

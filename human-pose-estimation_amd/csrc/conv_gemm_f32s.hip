@@ -29,6 +29,7 @@
 #include <stdlib.h>
 
 #include "conv_gemm_common.h"
+#include "gemm_contract.h"
 #include "hpe_internal.h"
 
 namespace {
@@ -73,9 +74,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_gemm_f32s_dma_kernel(Gem
     // XCD-aware bijective remap: blocks b, b+8, ... (one XCD) walk consecutive tiles
     const int total = p.n_mtiles * p.n_ntiles;
     const int bid = blockIdx.x;
-    const int xcd = bid & 7;
-    const int q8 = total >> 3, rr = total & 7;
-    const int tile = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (bid >> 3);
+    const int tile = xcd_remap(bid, total);
     const int mtile = tile / p.n_ntiles;
     const int ntile = tile - mtile * p.n_ntiles;
     const int m0 = mtile * BM;
@@ -94,7 +93,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_gemm_f32s_dma_kernel(Gem
 #pragma unroll
     for (int i = 0; i < AP; ++i) {
         const int r = (NW * i + wave) * 8 + (lane >> 3);
-        const int lc = (lane & 7) ^ ((r >> 1) & 7);
+        const int lc = (lane & 7) ^ ((r >> 1) & 7);  // 0..7: make_row's stem branch needs lc * 4 < 32
         arow[i] = make_row<MODE>(p, m0 + r, lc * 4);
         if (MODE == GEMM_DUAL) arow2[i] = make_row<GEMM_STRIDED>(p, m0 + r, lc * 4).base;
     }
@@ -219,8 +218,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_gemm_f32s_dma_kernel(Gem
     conv_epilogue<BM, BN, WM, WN>(p, lds, acc, m0, n0, t, lane, wm, wn, rpre, R_PRE && r_pre);
 }
 
-template <int MODE, int BM, int BN, int WM, int WN>
+template <int MODE, int TILE>
 hipError_t launch_cfg(GemmArgs& p, hipStream_t st) {
+    constexpr TileShape T = tile_shape(GEMM_K_F32S, TILE);
+    constexpr int BM = T.bm, BN = T.bn, WM = T.wm, WN = T.wn;
     p.n_mtiles = (p.M + BM - 1) / BM;
     p.n_ntiles = (p.N + BN - 1) / BN;
     p.split_k = 1;
@@ -232,40 +233,21 @@ hipError_t launch_cfg(GemmArgs& p, hipStream_t st) {
 template <int MODE>
 hipError_t launch_mode(GemmArgs& p, int tile, hipStream_t st) {
     switch (tile) {
-        case TILE_128x128: return launch_cfg<MODE, 128, 128, 4, 1>(p, st);
-        case TILE_128x128_W8: return launch_cfg<MODE, 128, 128, 4, 2>(p, st);
-        case TILE_256x128_W8: return launch_cfg<MODE, 256, 128, 8, 1>(p, st);
+        case TILE_128x128: return launch_cfg<MODE, TILE_128x128>(p, st);
+        case TILE_128x128_W8: return launch_cfg<MODE, TILE_128x128_W8>(p, st);
+        case TILE_256x128_W8: return launch_cfg<MODE, TILE_256x128_W8>(p, st);
         default: return hipErrorInvalidValue;
     }
 }
 
 }  // namespace
 
-// Host-side shape contract (checked here so a bad plan cannot fault on the device).
 hipError_t hpe_launch_gemm_f32s(GemmArgs p, int mode, int tile, hipStream_t st) {
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.K % BK) != 0 || (p.ldw % 8) != 0 || (p.w_piece % 8) != 0 || p.w_piece < p.K ||
-        p.ldw < p.K + 2 * p.w_piece)
-        return hipErrorInvalidValue;
-    if (!p.x || !p.w || !p.y || !p.scale || !p.shift) return hipErrorInvalidValue;
-    if ((p.ldy % 4) != 0 || ((uintptr_t)p.y & 15) != 0) return hipErrorInvalidValue;
-    if (p.y_slab8 && (p.N % 8) != 0) return hipErrorInvalidValue;
-    if (p.res && ((p.ldres % 4) != 0 || ((uintptr_t)p.res & 15) != 0)) return hipErrorInvalidValue;
-    if (((uintptr_t)p.x & 15) != 0 || ((uintptr_t)p.w & 15) != 0) return hipErrorInvalidValue;
-    if (((p.N + 127) / 128) * 128 > p.w_rows) return hipErrorInvalidValue;  // every tile is 128 columns wide
+    if (gemm_contract(p, mode, tile, GEMM_K_F32S)) return hipErrorInvalidValue;
     switch (mode) {
-        case GEMM_DENSE:
-            if (p.lda < p.K || (p.lda % 4) != 0) return hipErrorInvalidValue;
-            return launch_mode<GEMM_DENSE>(p, tile, st);
-        case GEMM_STRIDED:
-            if (p.Cin != p.K || (p.Cin % 4) != 0) return hipErrorInvalidValue;
-            if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_mode<GEMM_STRIDED>(p, tile, st);
-        case GEMM_DUAL:
-            if (!p.x2 || ((uintptr_t)p.x2 & 15) != 0 || p.k1_slabs < 1 || p.k1_slabs * BK >= p.K || p.lda < p.k1_slabs * BK || (p.lda % 4) != 0)
-                return hipErrorInvalidValue;
-            if (p.Cin != p.K - p.k1_slabs * BK || (p.Cin % 4) != 0 || p.M != (p.M / (p.Ho * p.Wo)) * p.Ho * p.Wo) return hipErrorInvalidValue;
-            if ((p.Ho - 1) * p.stride >= p.Hi || (p.Wo - 1) * p.stride >= p.Wi) return hipErrorInvalidValue;
-            return launch_mode<GEMM_DUAL>(p, tile, st);
+        case GEMM_DENSE: return launch_mode<GEMM_DENSE>(p, tile, st);
+        case GEMM_STRIDED: return launch_mode<GEMM_STRIDED>(p, tile, st);
+        case GEMM_DUAL: return launch_mode<GEMM_DUAL>(p, tile, st);
         default: return hipErrorInvalidValue;
     }
 }

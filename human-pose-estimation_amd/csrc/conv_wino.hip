@@ -271,9 +271,7 @@ __global__ __launch_bounds__(512, 2) void wino_gemm_kernel(WinoArgs p) {
     const int total = p.n_tb * p.n_nt;
     const int bid = blockIdx.x;
     // XCD-aware bijective remap: consecutive logical ids (the cout blocks of one tile block) share an XCD and its L2
-    const int xcd = bid & 7;
-    const int q = total >> 3, rr = total & 7;
-    const int lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int lid = xcd_remap(bid, total);
     const int tb = lid / p.n_nt;
     const int nt = lid - tb * p.n_nt;
 
@@ -433,9 +431,7 @@ __global__ __launch_bounds__(512, 2) void wino_fused_kernel(WinoFusedArgs p) {
 
     const int total = p.n_blk * p.n_nt;
     const int bid = blockIdx.x;
-    const int xcd = bid & 7;
-    const int q = total >> 3, rr = total & 7;
-    const int lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int lid = xcd_remap(bid, total);
     const int blk = lid / p.n_nt;
     const int nt = lid - blk * p.n_nt;
 

@@ -209,9 +209,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void w4_gemm_kernel(W4Args p) {
     const int total = p.n_tb * p.n_nt;
     const int bid = blockIdx.x;
     // XCD-aware bijective remap: consecutive logical ids (the cout blocks of one tile block) share an XCD and its L2
-    const int xcd = bid & 7;
-    const int q = total >> 3, rr = total & 7;
-    const int lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int lid = xcd_remap(bid, total);
     const int tb = lid / p.n_nt;
     const int nt = lid - tb * p.n_nt;
 
@@ -324,9 +322,7 @@ __global__ __launch_bounds__(W4_THREADS32, 2) void w4_gemm32_kernel(W4Args p) {
     const int KS = p.ksplit;
     const int bid = KS > 1 ? (int)blockIdx.x / KS : (int)blockIdx.x;
     const int part = KS > 1 ? (int)blockIdx.x - bid * KS : 0;
-    const int xcd = bid & 7;
-    const int q = total >> 3, rr = total & 7;
-    const int lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int lid = xcd_remap(bid, total);
     const int tb = lid / n_nt;
     const int nt = lid - tb * n_nt;
 
@@ -569,9 +565,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void w4_fused_kernel(W4FusedArgs p) 
 
     const int total = p.n_blk * p.n_nt;
     const int bid = blockIdx.x;
-    const int xcd = bid & 7;
-    const int q = total >> 3, rr = total & 7;
-    const int lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int lid = xcd_remap(bid, total);
     const int blk = lid / p.n_nt;
     const int nt = lid - blk * p.n_nt;
 

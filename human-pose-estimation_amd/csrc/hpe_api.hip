@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "gemm_contract.h"
 #include "hpe_ctx.h"
 
 namespace {
@@ -705,58 +706,72 @@ int hpe_debug_stem(hpe_ctx* c, const float* images, int B, int rows_per_strip, f
     return HPE_OK;
 }
 
+// HpeDebugGemm -> the launcher's arguments (slab: elements per k-slab of the kernel asked for); scale, shift and the zero page stay with the caller
+static GemmArgs debug_gemm_args(const HpeDebugGemm* g, int slab) {
+    static_assert(HPE_GEMM_DENSE == GEMM_DENSE && HPE_GEMM_STRIDED == GEMM_STRIDED && HPE_GEMM_CONV3 == GEMM_CONV3 && HPE_GEMM_DUAL == GEMM_DUAL,
+                  "include/hpe.h numbers the modes as GemmMode does");
+    GemmArgs p{};
+    p.x = g->x, p.x2 = g->x2, p.w = g->wt, p.res = g->residual, p.y = g->y;
+    p.M = g->M, p.N = g->N, p.K = g->K;
+    p.lda = g->lda, p.ldw = g->ldw, p.ldy = g->ldy, p.ldres = g->ldres, p.w_rows = g->w_rows;
+    p.Hi = g->Hi, p.Wi = g->Wi, p.Cin = g->Cin, p.Ho = g->Ho, p.Wo = g->Wo, p.stride = g->stride;
+    p.cin_slabs = g->Cin / slab;
+    p.k1_slabs = g->k1_slabs;
+    p.relu = g->relu;
+    p.y_slab8 = g->y_slab8;
+    return p;
+}
+
+// the guards both hooks share; empty: g can be read and its mode is one the hooks take
+static std::string debug_gemm_refusal(const HpeDebugGemm* g) {
+    if (!g) return "null HpeDebugGemm";
+    if (g->struct_size != (int)sizeof(HpeDebugGemm))
+        return "HpeDebugGemm.struct_size is " + std::to_string(g->struct_size) + ", this library's is " + std::to_string(sizeof(HpeDebugGemm)) +
+               " (other revision of include/hpe.h?)";
+    if (g->mode != HPE_GEMM_DENSE && g->mode != HPE_GEMM_STRIDED && g->mode != HPE_GEMM_CONV3 && g->mode != HPE_GEMM_DUAL)
+        return "HpeDebugGemm.mode must be dense, strided, conv3 or dual";
+    return "";
+}
+
+static std::string debug_gemm_rejected(const HpeDebugGemm* g, const char* clause) {
+    return "mode " + std::to_string(g->mode) + " tile " + std::to_string(g->tile) + " M " + std::to_string(g->M) + " N " + std::to_string(g->N) + " K " +
+           std::to_string(g->K) + " is outside the launcher's contract (gemm_contract.h), clause \"" + clause + "\": nothing was launched";
+}
+
 int hpe_debug_gemm_ex(hpe_ctx* c, const HpeDebugGemm* g, void* stream) {
     if (g && g->split_k) *g->split_k = 0;
     if (!c || !c->finalized) return fail(HPE_ERR_STATE, "needs a finalized ctx");
-    if (!g) return fail(HPE_ERR_INVALID, "null HpeDebugGemm");
-    if (g->struct_size != (int)sizeof(HpeDebugGemm))
-        return fail(HPE_ERR_INVALID, "HpeDebugGemm.struct_size is " + std::to_string(g->struct_size) + ", this library's is " +
-                                         std::to_string(sizeof(HpeDebugGemm)) + " (other revision of include/hpe.h?)");
-    if (g->mode != HPE_GEMM_DENSE && g->mode != HPE_GEMM_STRIDED && g->mode != HPE_GEMM_CONV3 && g->mode != HPE_GEMM_DUAL)
-        return fail(HPE_ERR_INVALID, "hpe_debug_gemm_ex: mode must be dense, strided, conv3 or dual");
+    const std::string why = debug_gemm_refusal(g);
+    if (!why.empty()) return fail(HPE_ERR_INVALID, why);
     if ((!g->scale || !g->shift) && g->N > 1024) return fail(HPE_ERR_INVALID, "hpe_debug_gemm_ex: N <= 1024 without scale / shift");
-    static_assert(HPE_GEMM_DENSE == GEMM_DENSE && HPE_GEMM_STRIDED == GEMM_STRIDED && HPE_GEMM_CONV3 == GEMM_CONV3 && HPE_GEMM_DUAL == GEMM_DUAL,
-                  "include/hpe.h numbers the modes as GemmMode does");
     DeviceGuard guard(c->cfg.device);
-    GemmArgs p{};
-    p.x = g->x;
-    p.x2 = g->x2;
-    p.w = g->wt;
+    GemmArgs p = debug_gemm_args(g, 32);
     p.scale = g->scale ? g->scale : c->ones;
     p.shift = g->shift ? g->shift : c->zeros;
-    p.res = g->residual;
-    p.y = g->y;
-    p.M = g->M;
-    p.N = g->N;
-    p.K = g->K;
-    p.lda = g->lda;
-    p.ldw = g->ldw;
-    p.ldy = g->ldy;
-    p.ldres = g->ldres;
-    p.w_rows = g->w_rows;
-    p.relu = g->relu;
-    p.Hi = g->Hi;
-    p.Wi = g->Wi;
-    p.Cin = g->Cin;
-    p.Ho = g->Ho;
-    p.Wo = g->Wo;
-    p.stride = g->stride;
-    p.cin_slabs = g->Cin / 32;
-    p.k1_slabs = g->k1_slabs;
-    p.y_slab8 = g->y_slab8;
     p.zero = c->zeros;
     if (g->use_splitk) {
         p.partial = c->partial;
         p.partial_floats = c->partial_floats;
     }
+    if (const char* clause = gemm_contract(p, g->mode, g->tile, GEMM_K_F32)) return fail(HPE_ERR_INVALID, "hpe_debug_gemm_ex: " + debug_gemm_rejected(g, clause));
     int split_k = 0;
     const hipError_t e = hpe_launch_gemm(p, g->mode, g->tile, c->plan.splitk_min_slabs, static_cast<hipStream_t>(stream), &split_k);
     if (g->split_k) *g->split_k = split_k;
-    if (e == hipErrorInvalidValue && split_k == 0)
-        return fail(HPE_ERR_INVALID, "hpe_launch_gemm rejected mode " + std::to_string(g->mode) + " tile " + std::to_string(g->tile) + " M " +
-                                         std::to_string(g->M) + " N " + std::to_string(g->N) + " K " + std::to_string(g->K) +
-                                         ": outside the launcher's contract (conv_gemm.hip), nothing was launched");
+    if (e == hipErrorInvalidValue && split_k == 0) return fail(HPE_ERR_INVALID, "hpe_debug_gemm_ex: the launcher refused the plan's splitk_min_slabs, nothing was launched");
     HIP_TRY(e);
+    return HPE_OK;
+}
+
+int hpe_debug_gemm_check(const HpeDebugGemm* g, int kernel, int w_piece) {
+    const std::string why = debug_gemm_refusal(g);
+    if (!why.empty()) return fail(HPE_ERR_INVALID, why);
+    if (kernel < GEMM_K_F32 || kernel > GEMM_K_BF16_P8) return fail(HPE_ERR_INVALID, "hpe_debug_gemm_check: kernel must be 0 (fp32), 1 (f32s), 2 (bf16) or 3 (bf16_p8)");
+    const GemmKernel k = static_cast<GemmKernel>(kernel);
+    GemmArgs p = debug_gemm_args(g, gemm_rules(k).slab);
+    alignas(16) static const float present[4] = {};  // scale, shift and the zero page count as present (never read)
+    p.scale = p.shift = p.zero = present;
+    if (k == GEMM_K_F32S) p.w_piece = w_piece;
+    if (const char* clause = gemm_contract(p, g->mode, g->tile, k)) return fail(HPE_ERR_INVALID, "hpe_debug_gemm_check: " + debug_gemm_rejected(g, clause));
     return HPE_OK;
 }
 

@@ -8,6 +8,16 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));  // accumulator of v_mfma_f32_32x32x2_f32
 
+// XCD-aware bijective remap of a workgroup id onto `total` logical ids: the workgroups of one XCD (bid, bid + 8, ...: they share an L2) walk
+// consecutive logical ids, so that neighbouring tiles (the N tiles of one A row panel, ...) fetch their shared operand from HBM once
+// (Id: int, or blockIdx.x's unsigned -- the type decides the shift the kernel was compiled with)
+template <typename Id>
+__device__ __forceinline__ int xcd_remap(Id bid, int total) {
+    const int xcd = bid & 7;
+    const int q = total >> 3, rr = total & 7;
+    return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+}
+
 inline dim3 grid1(long n) { return dim3((unsigned)((n + 255) / 256)); }  // one thread per element, 256 a block
 
 // GEMM_DUAL: two A sources summed into one accumulator (K concatenated): k-slabs [0, k1_slabs) come from the dense matrix x

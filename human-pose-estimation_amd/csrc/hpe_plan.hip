@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "gemm_contract.h"
 #include "hpe_ctx.h"
 
 namespace {
@@ -160,8 +161,8 @@ int pick_f32s(const HpePlan& pl, const void* w_split, int M, int N, int K, bool 
     if (!w_split || N <= 64) return -1;
     if (residual_expand && K < PLAN_F32S_EXPAND_MIN_K) return -1;
     const int tile = residual_expand ? PLAN_F32S_EXPAND_TILE : PLAN_F32S_TILE;
-    const int bm = tile == TILE_256x128_W8 ? 256 : 128;
-    return (long)((M + bm - 1) / bm) * ((N + 127) / 128) >= pl.f32s_min_tiles ? tile : -1;
+    const TileShape ts = tile_shape(GEMM_K_F32S, tile);
+    return (long)((M + ts.bm - 1) / ts.bm) * ((N + ts.bn - 1) / ts.bn) >= pl.f32s_min_tiles ? tile : -1;
 }
 
 int pick_tile(const HpePlan& pl, int M, int N, int K, bool residual_expand, bool concurrent) {

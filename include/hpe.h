@@ -528,7 +528,8 @@ int hpe_debug_stem(hpe_ctx* ctx, const float* images_dev, int B, int rows_per_st
  * y_slab8: y is written channel-slab major, y[(n / 8) * M + m][n % 8].  use_splitk: the launcher is handed the context's split-K
  * workspace (it then cuts K on small grids of the 4-wave tiles), else none.  split_k (host, optional) receives the number of K slices the
  * launcher chose (1 = not split).  Every argument goes through the launcher's host-side contract: a rejected one returns
- * HPE_ERR_INVALID, launches nothing and sets *split_k to 0.  All device pointers 16-byte aligned; all pitches multiples of 4 floats. */
+ * HPE_ERR_INVALID with the name of the broken clause in hpe_last_error(), launches nothing and sets *split_k to 0.  All device
+ * pointers 16-byte aligned; all pitches multiples of 4 floats. */
 #define HPE_GEMM_DENSE 0
 #define HPE_GEMM_STRIDED 1
 #define HPE_GEMM_CONV3 2
@@ -555,6 +556,13 @@ typedef struct HpeDebugGemm {
     int* split_k;
 } HpeDebugGemm;
 int hpe_debug_gemm_ex(hpe_ctx* ctx, const HpeDebugGemm* g, void* stream);
+/* The host-side contract alone, of any of the four implicit-GEMM launchers: kernel 0 = fp32 (the one hpe_debug_gemm_ex launches),
+ * 1 = fp32 on the bf16 matrix cores (split weights; tiles 0, 4, 6; w_piece = element offset between the three pieces of a weight row,
+ * read for this kernel only), 2 = bf16 (tiles 0..6; K and Cin in slabs of 64, pitches multiples of 8 elements), 3 = bf16 256x256
+ * (tile 7).  No context, no HIP call, nothing is launched: the pointers of g are taken as numbers (NULL or not, aligned or not) and
+ * never dereferenced; scale, shift and the library's zero page count as present; use_splitk is ignored.  HPE_OK if the launch is
+ * inside the contract, else HPE_ERR_INVALID with the name of the first broken clause in hpe_last_error(). */
+int hpe_debug_gemm_check(const HpeDebugGemm* g, int kernel, int w_piece);
 /* The dense mode of hpe_debug_gemm_ex with scale = ones, shift = zeros, lda = ldw = K, ldy = ldres = N and no split-K
  * workspace: y[M,N] = act(x[M,K] . wt[n][k]^T (+ residual)); K % 32 == 0; N <= 1024; tile 0..6 as above.  Needs the regressor loaded. */
 int hpe_debug_gemm(hpe_ctx* ctx, const float* x_dev, const float* wt_dev, int M, int N, int K, int w_rows, int tile,

@@ -3,7 +3,7 @@
     y[m][n] = act((sum_k A[m][k] * Wt[n][k]) * scale[n] + shift[n] (+ res[m][n]))
 
 for its four product modes, the weight packing the kernel reads, seeded inputs, the shape lists of tests/test_gpu_gemm_edges.py and
-a restatement of the launcher's host-side contract (hpe_launch_gemm).  Plain NumPy, no GPU, nothing taken from the library:
+a restatement of the host-side contract of the four GEMM launchers (csrc/gemm_contract.h).  Plain NumPy, no GPU, nothing taken from the library:
 tests/test_gemm_ref_cpu.py pins the references to oracle.hmr_oracle.conv2d_nhwc, the inputs to the bar and the lists to the contract.
 
 Packed weights Wt[n][k], w_rows x ldw, zero padded:  1x1 layers k = ci;  3x3 layers k = (kh * 3 + kw) * Cin + ci;  dual: the k
@@ -286,15 +286,41 @@ def all_valid_cases():
     return out
 
 
-# ------------------------------------------------------------------------------------------- the launcher's contract
+# ------------------------------------------------------------------------------------------- the launchers' contract
 POINTERS = ("x", "x2", "wt", "residual", "y")
+P8_TILE = (256, 256)
+# The four launchers (csrc/gemm_contract.h), by the number hpe_debug_gemm_check takes: elements per 16-byte vector of the activations
+# (gran) and of the weights (wgran), elements per k-slab, the modes the debug hooks can ask of the kernel and its tiles {id: (BM, BN)}.
+KERNELS = {
+    "f32": dict(id=0, gran=4, wgran=4, slab=32, modes=(DENSE, STRIDED, CONV3, DUAL), tiles=dict(enumerate(TILES))),
+    "f32s": dict(id=1, gran=4, wgran=8, slab=32, modes=(DENSE, STRIDED, DUAL), tiles={t: TILES[t] for t in (0, 4, 6)}),
+    "bf16": dict(id=2, gran=8, wgran=8, slab=64, modes=(DENSE, STRIDED, CONV3, DUAL), tiles=dict(enumerate(TILES))),
+    "bf16_p8": dict(id=3, gran=8, wgran=8, slab=64, modes=(DENSE, STRIDED, CONV3, DUAL), tiles={7: P8_TILE}),
+}
+TILE_CLAUSE = {"f32": "tile in 0..6", "f32s": "tile in {0, 4, 6}", "bf16": "tile in 0..6", "bf16_p8": "tile == 7"}
+# contract_violations writes every clause under the fp32 launcher's name; these tables give the names of the clauses whose number is
+# the kernel's slab (64), its activation vector (8) or its weight vector (8) instead
+SLAB64_NAMES = {"K % 32 == 0": "K % 64 == 0", "Cin % 32 == 0": "Cin % 64 == 0", "k1_slabs * 32 < K": "k1_slabs * 64 < K",
+                "lda >= k1_slabs * 32": "lda >= k1_slabs * 64", "Cin == K - k1_slabs * 32": "Cin == K - k1_slabs * 64"}
+VEC8_NAMES = {"ldy % 4 == 0": "ldy % 8 == 0", "ldres % 4 == 0": "ldres % 8 == 0", "lda % 4 == 0": "lda % 8 == 0", "Cin % 4 == 0": "Cin % 8 == 0"}
+WVEC8_NAMES = {"ldw % 4 == 0": "ldw % 8 == 0"}
+CLAUSE_NAMES = {"f32": {}, "f32s": dict(WVEC8_NAMES), "bf16": {**SLAB64_NAMES, **VEC8_NAMES, **WVEC8_NAMES}}
+CLAUSE_NAMES["bf16_p8"] = CLAUSE_NAMES["bf16"]
 
 
-def contract_violations(c, null=(), misaligned=()):
-    """The clauses of hpe_launch_gemm's host-side contract (conv_gemm.hip) that the launch c breaks, by name.  Pointers are
-    described, not held: a case has x, wt and y, residual with use_res and x2 in dual mode, minus `null`; the ones in `misaligned`
-    are not multiples of 16 bytes.  scale, shift and the zero page come from the hook and are never NULL."""
-    g = dict(lda=0, ldw=0, ldy=0, ldres=0, w_rows=0, Hi=0, Wi=0, Cin=0, Ho=0, Wo=0, stride=0, k1_slabs=0, y_slab8=0)
+def clause_name(name, kernel):
+    """the fp32 launcher's name of a clause -> the name of the same clause of `kernel`"""
+    return TILE_CLAUSE[kernel] if name == "tile in 0..6" else CLAUSE_NAMES[kernel].get(name, name)
+
+
+def contract_violations(c, null=(), misaligned=(), kernel="f32"):
+    """The clauses of a launcher's host-side contract (gemm_contract.h; default: hpe_launch_gemm, the fp32 kernel) that the launch c
+    breaks, by name.  Pointers are described, not held: a case has x, wt and y, residual with use_res and x2 in dual mode, minus `null`;
+    the ones in `misaligned` are not multiples of 16 bytes.  scale, shift and the zero page come from the hook and are never NULL.
+    The clauses are written with the fp32 kernel's numbers in their names; clause_name() turns them into the other kernels'."""
+    k = KERNELS[kernel]
+    G, WG, SLAB = k["gran"], k["wgran"], k["slab"]
+    g = dict(lda=0, ldw=0, ldy=0, ldres=0, w_rows=0, Hi=0, Wi=0, Cin=0, Ho=0, Wo=0, stride=0, k1_slabs=0, y_slab8=0, w_piece=0)
     g.update(c)
     has = {"x": True, "wt": True, "y": True, "residual": bool(g.get("use_res")), "x2": g["mode"] == DUAL}
     for n in null:
@@ -303,44 +329,60 @@ def contract_violations(c, null=(), misaligned=()):
 
     def clause(name, broken):
         if broken:
+            bad.append(clause_name(name, kernel))
+
+    def only(which, name, broken):  # a clause that only the kernel `which` has
+        if kernel == which and broken:
             bad.append(name)
 
     M, N, K = g["M"], g["N"], g["K"]
     clause("M > 0", M <= 0)
     clause("N > 0", N <= 0)
     clause("K > 0", K <= 0)
-    clause("K % 32 == 0", K > 0 and K % BK != 0)
-    clause("ldw % 4 == 0", g["ldw"] % 4 != 0)
-    clause("ldw >= K", g["ldw"] < K)
+    clause("K % 32 == 0", K > 0 and K % SLAB != 0)
+    clause("ldw % 4 == 0", g["ldw"] % WG != 0)
+    if kernel == "f32s":  # three bf16 pieces per weight row
+        only("f32s", "w_piece % 8 == 0", g["w_piece"] % 8 != 0)
+        only("f32s", "w_piece >= K", g["w_piece"] < K)
+        only("f32s", "ldw >= K + 2 * w_piece", g["ldw"] < K + 2 * g["w_piece"])
+    else:
+        clause("ldw >= K", g["ldw"] < K)
     for n in ("x", "wt", "y"):
         clause(n + " != NULL", not has[n])
-    clause("ldy % 4 == 0", g["ldy"] % 4 != 0)
+    clause("ldy % 4 == 0", g["ldy"] % G != 0)
     clause("y aligned", "y" in misaligned)
-    clause("y_slab8 needs N % 8 == 0", bool(g["y_slab8"]) and N % 8 != 0)
+    if G == 4:  # the bf16 kernels have no slab-major output
+        clause("y_slab8 needs N % 8 == 0", bool(g["y_slab8"]) and N % 8 != 0)
     if has["residual"]:
-        clause("ldres % 4 == 0", g["ldres"] % 4 != 0)
+        clause("ldres % 4 == 0", g["ldres"] % G != 0)
         clause("residual aligned", "residual" in misaligned)
     clause("x aligned", "x" in misaligned)
     clause("wt aligned", "wt" in misaligned)
     tile = g["tile"]
-    clause("tile in 0..6", not 0 <= tile <= 6)
-    if 0 <= tile <= 6 and N > 0:
-        clause("w_rows covers the padded N", pad_to(N, TILES[tile][1]) > g["w_rows"])
+    clause("tile in 0..6", tile not in k["tiles"])
+    if kernel == "bf16_p8":  # it clamps the weight rows it reads instead
+        only("bf16_p8", "w_rows >= 1", g["w_rows"] < 1)
+    elif tile in k["tiles"] and N > 0:
+        clause("w_rows covers the padded N", pad_to(N, k["tiles"][tile][1]) > g["w_rows"])
     mode = g["mode"]
-    clause("mode", mode not in (DENSE, STRIDED, CONV3, DUAL))  # the hook refuses the stem mode, the launcher unknown ones
+    clause("mode", mode not in k["modes"])  # the hooks refuse the stem mode, the launchers the modes their kernel lacks
     stride_ok = g["Ho"] >= 1 and g["Wo"] >= 1 and g["stride"] >= 1
-    if mode == DENSE:
+    if mode not in k["modes"]:
+        pass
+    elif mode == DENSE:
         clause("lda >= K", g["lda"] < K)
-        clause("lda % 4 == 0", g["lda"] % 4 != 0)
+        clause("lda % 4 == 0", g["lda"] % G != 0)
     elif mode == STRIDED:
         clause("Cin == K", g["Cin"] != K)
-        clause("Cin % 4 == 0", g["Cin"] % 4 != 0)
+        clause("Cin % 4 == 0", g["Cin"] % G != 0)
         clause("Ho, Wo, stride >= 1", not stride_ok)
         clause("(Ho - 1) * stride < Hi", stride_ok and (g["Ho"] - 1) * g["stride"] >= g["Hi"])
         clause("(Wo - 1) * stride < Wi", stride_ok and (g["Wo"] - 1) * g["stride"] >= g["Wi"])
     elif mode == CONV3:
-        clause("Cin % 32 == 0", g["Cin"] % BK != 0)
+        clause("Cin % 32 == 0", g["Cin"] % SLAB != 0)
         clause("K == 9 * Cin", K != 9 * g["Cin"])
+        cs = g["Cin"] // SLAB  # the hooks derive cin_slabs from Cin
+        only("bf16_p8", "cin_slabs a power of two", g["Cin"] % SLAB == 0 and cs & (cs - 1) != 0)
         clause("Ho == Hi", g["Ho"] != g["Hi"])
         clause("Wo == Wi", g["Wo"] != g["Wi"])
         clause("Hi, Wi >= 1", g["Hi"] < 1 or g["Wi"] < 1)
@@ -349,11 +391,11 @@ def contract_violations(c, null=(), misaligned=()):
         clause("x2 != NULL", not has["x2"])
         clause("x2 aligned", "x2" in misaligned)
         clause("k1_slabs >= 1", k1 < 1)
-        clause("k1_slabs * 32 < K", k1 * BK >= K)
-        clause("lda >= k1_slabs * 32", g["lda"] < k1 * BK)
-        clause("lda % 4 == 0", g["lda"] % 4 != 0)
-        clause("Cin == K - k1_slabs * 32", g["Cin"] != K - k1 * BK)
-        clause("Cin % 4 == 0", g["Cin"] % 4 != 0)
+        clause("k1_slabs * 32 < K", k1 * SLAB >= K)
+        clause("lda >= k1_slabs * 32", g["lda"] < k1 * SLAB)
+        clause("lda % 4 == 0", g["lda"] % G != 0)
+        clause("Cin == K - k1_slabs * 32", g["Cin"] != K - k1 * SLAB)
+        clause("Cin % 4 == 0", g["Cin"] % G != 0)
         clause("Ho, Wo, stride >= 1", not stride_ok)
         clause("M % (Ho * Wo) == 0", stride_ok and M % (g["Ho"] * g["Wo"]) != 0)
         clause("(Ho - 1) * stride < Hi", stride_ok and (g["Ho"] - 1) * g["stride"] >= g["Hi"])
@@ -361,17 +403,72 @@ def contract_violations(c, null=(), misaligned=()):
     return bad
 
 
-def error_bases():
-    """one valid launch per mode (64x64 tile, no residual unless the case needs one): the error cases are these with ONE change"""
-    return {
-        "dense": dict(mode=DENSE, tile=2, M=5, N=64, K=64, lda=64, ldw=64, ldy=68, ldres=72, w_rows=64, relu=0, use_res=1),
-        "strided": dict(mode=STRIDED, tile=2, M=27, N=64, K=32, Cin=32, Hi=6, Wi=6, Ho=3, Wo=3, stride=2, lda=32, ldw=32, ldy=68, ldres=72, w_rows=64,
-                        relu=0, use_res=0),
-        "conv3": dict(mode=CONV3, tile=2, M=27, N=64, K=288, Cin=32, Hi=3, Wi=3, Ho=3, Wo=3, stride=1, lda=32, ldw=288, ldy=68, ldres=72, w_rows=64,
-                      relu=0, use_res=0),
-        "dual": dict(mode=DUAL, tile=2, M=27, N=64, K=64, Cin=32, Hi=6, Wi=6, Ho=3, Wo=3, stride=2, k1_slabs=1, lda=32, ldw=64, ldy=68, ldres=72,
-                     w_rows=64, relu=0, use_res=0),
+def error_bases(kernel="f32"):
+    """one valid launch per mode of the kernel (no residual unless the case needs one): the error cases are these with ONE change.
+    fp32: the 64x64 tile.  The others: the kernel's first tile, K and Cin in its slabs, pitches in its vectors, w_rows one tile wide;
+    f32s: the three weight pieces w_piece = K apart, ldw = 3 K."""
+    if kernel == "f32":
+        return {
+            "dense": dict(mode=DENSE, tile=2, M=5, N=64, K=64, lda=64, ldw=64, ldy=68, ldres=72, w_rows=64, relu=0, use_res=1),
+            "strided": dict(mode=STRIDED, tile=2, M=27, N=64, K=32, Cin=32, Hi=6, Wi=6, Ho=3, Wo=3, stride=2, lda=32, ldw=32, ldy=68, ldres=72, w_rows=64,
+                            relu=0, use_res=0),
+            "conv3": dict(mode=CONV3, tile=2, M=27, N=64, K=288, Cin=32, Hi=3, Wi=3, Ho=3, Wo=3, stride=1, lda=32, ldw=288, ldy=68, ldres=72, w_rows=64,
+                          relu=0, use_res=0),
+            "dual": dict(mode=DUAL, tile=2, M=27, N=64, K=64, Cin=32, Hi=6, Wi=6, Ho=3, Wo=3, stride=2, k1_slabs=1, lda=32, ldw=64, ldy=68, ldres=72,
+                         w_rows=64, relu=0, use_res=0),
+        }
+    k = KERNELS[kernel]
+    S, tile = k["slab"], min(k["tiles"])
+    common = dict(tile=tile, N=64, ldy=72, ldres=80, w_rows=k["tiles"][tile][1], relu=0, use_res=0)
+    geo = dict(M=27, Hi=6, Wi=6, Ho=3, Wo=3, stride=2)
+    out = {
+        "dense": dict(common, mode=DENSE, M=5, K=2 * S, lda=2 * S, use_res=1),
+        "strided": dict(common, mode=STRIDED, K=S, Cin=S, lda=S, **geo),
+        "conv3": dict(common, mode=CONV3, M=27, K=9 * S, Cin=S, Hi=3, Wi=3, Ho=3, Wo=3, stride=1, lda=S),
+        "dual": dict(common, mode=DUAL, K=2 * S, Cin=S, k1_slabs=1, lda=S, **geo),
     }
+    for c in out.values():
+        c.update(ldw=3 * c["K"], w_piece=c["K"]) if kernel == "f32s" else c.update(ldw=c["K"])
+    return out
+
+
+def error_cases(kernel):
+    """(base, the one change, null pointers, misaligned pointers) for a kernel other than fp32: every clause of its contract that a
+    debug hook can reach, broken once and alone.  Out of reach, for every kernel: the clauses of the stem mode (both geometries: the
+    hooks refuse the mode), cin_slabs == Cin / slab (the hooks derive it) and, as in ERROR_CASES, Cin % vector and Cin % slab (other
+    clauses imply them); for the 256x256 kernel also the alignment of the zero page and of the split-K workspace, which the library owns.  A conv3 case handed to f32s
+    breaks "mode": the kernel has no such mode."""
+    k = KERNELS[kernel]
+    G, WG, S = k["gran"], k["wgran"], k["slab"]
+    b = error_bases(kernel)
+    d, K = b["dense"], b["dense"]["K"]
+    out = [("dense", dict(M=0), (), ()), ("dense", dict(N=0), (), ()), ("dense", dict(K=0, lda=0, ldw=0, w_piece=0), (), ()),
+           ("dense", dict(K=S // 2), (), ()), ("dense", dict(ldw=d["ldw"] + WG // 2), (), ())]
+    if kernel == "f32s":
+        out += [("dense", dict(w_piece=K + 4, ldw=3 * K + 16), (), ()), ("dense", dict(w_piece=K - 8), (), ()), ("dense", dict(ldw=3 * K - 8), (), ())]
+    else:
+        out += [("dense", dict(ldw=K - WG), (), ())]
+    out += [("dense", {}, (n,), ()) for n in ("x", "wt", "y")]
+    out += [("dense", dict(ldy=d["ldy"] + G // 2), (), ()), ("dense", dict(ldres=d["ldres"] + G // 2), (), ())]
+    out += [("dense", {}, (), (n,)) for n in ("y", "residual", "x", "wt")]
+    if G == 4:
+        out += [("dense", dict(y_slab8=1, N=60), (), ())]
+    out += [("dense", dict(tile=t), (), ()) for t in (-1, 8) + tuple(t for t in range(8) if t not in k["tiles"])]
+    out += [("dense", dict(w_rows=0), (), ())]  # one tile short: the coverage clause, or w_rows >= 1 of the 256x256 kernel
+    if kernel != "bf16_p8":
+        out += [("dense", dict(w_rows=d["w_rows"] - 4), (), ()), ("dense", dict(N=d["w_rows"] + 4, ldy=d["w_rows"] + 8, ldres=d["w_rows"] + 8), (), ())]
+    out += [("dense", dict(mode=STEM), (), ()), ("dense", dict(lda=K - G), (), ()), ("dense", dict(lda=K + G // 2), (), ())]
+    out += [("strided", ch, (), ()) for ch in (dict(Cin=2 * S), dict(Ho=0), dict(Wo=0), dict(stride=0), dict(stride=-2), dict(Hi=4), dict(Wi=4))]
+    if CONV3 in k["modes"]:
+        out += [("conv3", ch, (), ()) for ch in (dict(K=8 * S), dict(Ho=2), dict(Wo=4), dict(Hi=0, Ho=0), dict(Wi=0, Wo=0))]
+        if kernel == "bf16_p8":
+            out += [("conv3", dict(Cin=3 * S, K=27 * S, ldw=27 * S), (), ())]
+    else:
+        out += [("conv3", {}, (), ())]
+    out += [("dual", {}, ("x2",), ()), ("dual", {}, (), ("x2",))]
+    out += [("dual", ch, (), ()) for ch in (dict(k1_slabs=0, Cin=2 * S), dict(k1_slabs=2, Cin=0, lda=2 * S), dict(lda=S - G), dict(lda=S + G // 2),
+                                            dict(Cin=2 * S), dict(Ho=0), dict(Wo=0), dict(stride=0), dict(M=26), dict(Hi=4), dict(Wi=4))]
+    return out
 
 
 # (base, the one change, null pointers, misaligned pointers): each breaks exactly one clause of the contract.  Not reachable alone and
@@ -425,9 +522,9 @@ ERROR_CASES = [
 ]
 
 
-def error_case(i):
-    base, change, null, mis = ERROR_CASES[i]
-    return dict(error_bases()[base], **change), null, mis
+def error_case(i, kernel="f32"):
+    base, change, null, mis = (ERROR_CASES if kernel == "f32" else error_cases(kernel))[i]
+    return dict(error_bases(kernel)[base], **change), null, mis
 
 
 # ------------------------------------------------------------------------------------------- the inputs and references of a case

@@ -214,8 +214,8 @@ def test_old_entry_point(eng):
 
 
 def test_rejected_launches(eng):
-    """each clause of the launcher's contract broken once (gemm_ref.ERROR_CASES): HPE_ERR_INVALID, a message, split_k = 0 and an
-    untouched output.  Nothing is launched, so nothing here can reach the device with a bad shape."""
+    """each clause of the launcher's contract broken once (gemm_ref.ERROR_CASES): HPE_ERR_INVALID, a message that names the clause,
+    split_k = 0 and an untouched output.  Nothing is launched, so nothing here can reach the device with a bad shape."""
     import torch
 
     lib = eng.lib
@@ -223,7 +223,8 @@ def test_rejected_launches(eng):
     for i in range(len(R.ERROR_CASES)):
         c, null, mis = R.error_case(i)
         base = R.error_bases()[R.ERROR_CASES[i][0]]
-        assert len(R.contract_violations(c, null, mis)) == 1
+        want = R.contract_violations(c, null, mis)
+        assert len(want) == 1
         inp = R.inputs(base)
         if inp["res"] is None:
             inp["res"] = np.zeros((base["M"], base["ldres"]), np.float32)
@@ -244,7 +245,7 @@ def test_rejected_launches(eng):
         rc = lib.hpe_debug_gemm_ex(eng._h, C.byref(g), None)
         msg = lib.hpe_last_error().decode()
         torch.cuda.synchronize()
-        ok = rc == 1 and sk.value == 0 and len(msg) > 20 and ("contract" in msg or "mode" in msg) and bool((y.view(torch.int32) == SENTINEL).all())
+        ok = rc == 1 and sk.value == 0 and len(msg) > 20 and ("contract" in msg or "mode" in msg) and want[0] in msg and bool((y.view(torch.int32) == SENTINEL).all())
         if not ok:
             missed.append((i, R.ERROR_CASES[i], rc, sk.value, msg))
     assert not missed, missed
