@@ -104,6 +104,9 @@ class HpeDebugGemm(C.Structure):
                 ("shift", C.c_void_p), ("y", C.c_void_p), ("split_k", C.POINTER(C.c_int))]
 
 
+# `which` of hpe_debug_encoder_packing (include/hpe.h: HPE_PACK_*)
+ENCODER_PACKINGS = ("w", "w_split", "wino_u", "wino4_u", "stem_w", "scale", "shift", "w_dual", "w_dual_split", "shift_dual", "dxw", "flat")
+
 OUTPUT_FIELDS = ("verts", "joints", "cams", "theta", "J_transformed", "kp2d", "verts2d", "Rs")
 
 
@@ -178,6 +181,9 @@ _PROTOS = {
     "hpe_encoder_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_encoder_get_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_encoder_set_params": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hpe_encoder_set_params_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_debug_encoder_packing_bytes": (C.c_longlong, [C.c_void_p, C.c_int, C.c_int]),
+    "hpe_debug_encoder_packing": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_conv_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_debug_maxpool_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_avgpool_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -104,7 +104,7 @@ class RegressorFunction(torch.autograd.Function):
 
 class EncoderFunction(torch.autograd.Function):
     """features [B,2048] = hpe_encoder_forward_train(images; the engine's live encoder, BatchNorm statistics fixed), differentiable in
-    ``params`` -- the flat tensor the optimiser owns, which must EQUAL what the engine holds (``set_encoder_params`` after every step):
+    ``params`` -- the flat tensor the optimiser owns, which must EQUAL what the engine holds (``set_encoder_params_dev`` after every step):
     it carries ``.grad``, the arithmetic reads the engine's weights.  Images get no gradient.  hpe_encoder_backward is stateless, so only
     the images are saved."""
 

@@ -318,15 +318,13 @@ size_t partial_floats(int B) {
     return need;
 }
 
-size_t dxw_floats(int idx) {
-    const ConvSpec& s = specs()[idx];
-    return idx == 0 ? 0 : (size_t)round_up(s.cin, 128) * s.kh * s.kw * s.cout;
-}
+size_t dxw_floats(int idx) { return conv_dxw_floats(idx); }
 
 size_t ws_floats(int B) {
     size_t n = (size_t)B * layout().stash_per_image + (size_t)B * (3 * (size_t)BIG + 3 * (size_t)MID) + partial_floats(B);
     n += (size_t)MAX_SLICES * 2048 + (size_t)WGP_FLOATS;  // column sums of dz per slice, <W, G> per 64-row chunk
     for (int i = 0; i < HPE_NUM_CONV; ++i) n += dxw_floats(i);
+    n += 2 * (size_t)layout().channels + encoder_repack_reserve_floats();  // hpe_encoder_set_params_dev: sqrt(var + eps) in double, the layer table
     return n + layout().total + 2 * layout().channels + 2048 + (size_t)B * HPE_FEATURE_DIM;
 }
 
@@ -563,10 +561,14 @@ int hpe_encoder_train_reserve(hpe_ctx* c, int B) {
     if ((rc = dev_alloc(c, &w.flat, l.total, false))) return rc;
     if ((rc = dev_alloc(c, &w.mean, l.channels, false))) return rc;
     if ((rc = dev_alloc(c, &w.istd, l.channels, false))) return rc;
+    float* sdp = nullptr;
+    if ((rc = dev_alloc(c, &sdp, 2 * (size_t)l.channels, false))) return rc;
+    w.sd = reinterpret_cast<double*>(sdp);
     for (int i = 1; i < HPE_NUM_CONV; ++i)
         if ((rc = dev_alloc(c, &w.dxw[i], dxw_floats(i), false))) return rc;
     // the flat parameters: hpe_finalize released the host kernels, so they come back from the packed device weights Wt[n][k] (fp32: exact)
     std::vector<float> flat(l.total), mean(l.channels), istd(l.channels), wt;
+    std::vector<double> sd(l.channels);
     HIP_TRY(hipDeviceSynchronize());
     for (int i = 0; i < HPE_NUM_CONV; ++i) {
         const ConvSpec& s = specs()[i];
@@ -586,11 +588,14 @@ int hpe_encoder_train_reserve(hpe_ctx* c, int B) {
             flat[l.off[i][3] + n] = L.beta[n];
             mean[l.stat[i] + n] = L.mean[n];
             istd[l.stat[i] + n] = bn_istd(L, n, c->cfg.bn_eps);
+            sd[l.stat[i] + n] = bn_sd(L, n, c->cfg.bn_eps);
         }
     }
     HIP_TRY(hipMemcpy(w.mean, mean.data(), mean.size() * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(w.istd, istd.data(), istd.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.sd, sd.data(), sd.size() * sizeof(double), hipMemcpyHostToDevice));
     if ((rc = upload_train_params(c, flat.data()))) return rc;
+    if ((rc = encoder_repack_reserve(c))) return rc;
     w.B = B;
     return HPE_OK;
 }
@@ -642,6 +647,17 @@ int hpe_encoder_set_params(hpe_ctx* c, const float* flat) {
     if ((rc = repack_encoder(c))) return rc;
     if ((rc = upload_train_params(c, flat))) return rc;
     HIP_TRY(hipDeviceSynchronize());
+    return HPE_OK;
+}
+
+int hpe_encoder_set_params_dev(hpe_ctx* c, const float* flat, void* stream) {
+    int rc = check_train(c, 1);
+    if (rc) return rc;
+    if (!flat) return fail(HPE_ERR_INVALID, "null flat_dev");
+    DeviceGuard g(c->cfg.device);
+    // Nothing to wait for here: encoder_impl has made the caller's stream wait for every chunk stream before it returned (the ev_join
+    // loop at its end), so launches of earlier calls on `stream` are ordered before these; a pipelined tail reads no encoder weight.
+    HIP_TRY(encoder_repack_launch(c, flat, static_cast<hipStream_t>(stream)));
     return HPE_OK;
 }
 

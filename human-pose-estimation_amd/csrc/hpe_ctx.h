@@ -47,7 +47,10 @@ const std::vector<ResBlock>& blocks();  // 16 entries, built by the loop that bu
 inline int round_up(int x, int m) { return ((x + m - 1) / m) * m; }
 
 struct ConvLayer {
-    std::vector<float> kernel, bias, gamma, beta, mean, var;  // host staging (Keras layouts)
+    // Host staging (Keras layouts).  kernel is released by hpe_finalize.  bias / gamma / beta go STALE after hpe_encoder_set_params_dev:
+    // after hpe_finalize nothing reads them but hpe_encoder_train_reserve (once, before any device update can run) and
+    // hpe_encoder_set_params, which overwrites all of them first.  mean / var never change.
+    std::vector<float> kernel, bias, gamma, beta, mean, var;
     bool loaded = false;
     float* w = nullptr;  // device, packed [n_pad][k_pad] (fp32) or bf16 [n_pad][k_pad16] in bf16 mode
     float* scale = nullptr;
@@ -73,18 +76,71 @@ inline int conv_wt_k(int idx, int kh, int kw, int ci) {
     return idx == 0 ? kh * 32 + kw * 4 + ci : (kh * s.kw + kw) * s.cin + ci;
 }
 
-// BatchNorm with the moving statistics folded into the layer: y = scale * conv(x, W) + shift, the conv bias inside shift.  In double.
+// The packing rules the host packers (hpe_finalize.hip, encoder_train.hip) and the repack kernels (encoder_repack.hip) share.  Every
+// floating-point helper fixes its operation order and turns contraction off, so that both sides round alike.
+
+// conv1's row of the fp32 fused-stem weights [64][160] (stem_fused.hip)
+__host__ __device__ inline int stem_w_k(int kh, int kw, int ci) { return kh * 22 + 1 + kw * 3 + ci; }
+
+// first element of (cout n, cin ci) in the F(2x2,3x3) weights [cout/64][cin/8][16][2][64][4]; element (xi, nu) is (xi * 4 + nu) * 512 further
+__host__ __device__ inline size_t wino_u_base(int n, int ci, int cin) {
+    return ((((size_t)(n >> 6) * (cin / 8) + (ci >> 3)) * 16) * 2 + ((ci >> 2) & 1)) * 256 + (size_t)(n & 63) * 4 + (ci & 3);
+}
+// ... and in the F(4x4,3x3) weights [cout/64][cin/4][36][64][4]; element (xi, nu) is (xi * 6 + nu) * 256 further
+__host__ __device__ inline size_t wino4_u_base(int n, int ci, int cin) {
+    return (((size_t)(n >> 6) * (cin / 4) + (ci >> 2)) * 36) * 256 + (size_t)(n & 63) * 4 + (ci & 3);
+}
+// rows of G: F(2x2,3x3) [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1], F(4x4,3x3) [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1]
+__host__ __device__ inline double wino_g(int xi, int a) {
+    constexpr double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    return G[xi][a];
+}
+__host__ __device__ inline double wino4_g(int xi, int a) {
+    constexpr double G4[6][3] = {{0.25, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                                 {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
+    return G4[xi][a];
+}
+// element (xi, nu) of U = G g G^T from rows gx = G[xi], gn = G[nu]: in double, a and b ascending, one rounding to float
+__host__ __device__ inline float wino_elem(const double gx[3], const double gn[3], const double g[3][3]) {
+#pragma clang fp contract(off)
+    double u = 0.0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) u += gx[a] * gn[b] * g[a][b];
+    return (float)u;
+}
+
+// BatchNorm with the moving statistics folded into the layer: y = scale * conv(x, W) + shift, the conv bias inside shift.  In double;
+// sd = sqrt((double)var + (double)eps), taken on the host (the statistics are fixed: hpe_encoder_train_reserve keeps sd on the device)
+__host__ __device__ inline void bn_fold_sd(float gamma, float bias, float mean, float beta, double sd, double* scale, double* shift) {
+#pragma clang fp contract(off)
+    *scale = (double)gamma / sd;
+    *shift = ((double)bias - (double)mean) * *scale + (double)beta;
+}
+inline double bn_sd(const ConvLayer& L, int n, float eps) { return std::sqrt((double)L.var[n] + (double)eps); }
 inline void bn_fold(const ConvLayer& L, int n, float eps, double* scale, double* shift) {
-    *scale = (double)L.gamma[n] / std::sqrt((double)L.var[n] + (double)eps);
-    *shift = ((double)L.bias[n] - (double)L.mean[n]) * *scale + (double)L.beta[n];
+    bn_fold_sd(L.gamma[n], L.bias[n], L.mean[n], L.beta[n], bn_sd(L, n, eps), scale, shift);
 }
 // ... and what the gamma gradient of the encoder's backward divides by
 inline float bn_istd(const ConvLayer& L, int n, float eps) { return (float)(1.0 / std::sqrt((double)L.var[n] + (double)eps)); }
 
-inline unsigned short f2bf(float f) {  // round-to-nearest-even fp32 -> bf16 (finite inputs)
+__host__ __device__ inline unsigned short f2bf(float f) {  // round-to-nearest-even fp32 -> bf16 (finite inputs)
     unsigned u;
     memcpy(&u, &f, 4);
     return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+__host__ __device__ inline float bf2f(unsigned short h) {
+    const unsigned u = (unsigned)h << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+// x = h[0] + h[1] + h[2] exactly (finite x): each piece the bf16 nearest to what the pieces before it left (conv_gemm_f32s.hip)
+__host__ __device__ inline void bf16_split3(float x, unsigned short h[3]) {
+    h[0] = f2bf(x);
+    const float r1 = x - bf2f(h[0]);
+    h[1] = f2bf(r1);
+    const float r2 = r1 - bf2f(h[1]);
+    h[2] = f2bf(r2);
 }
 
 struct DenseLayer {
@@ -123,12 +179,17 @@ struct RegTrainWork {
     size_t partial_floats = 0;
 };
 
-// Encoder training (encoder_train.hip), allocated by hpe_encoder_train_reserve for B images: nothing of it exists in an inference context
+// Encoder training (encoder_train.hip), allocated by hpe_encoder_train_reserve for B images: nothing of it exists in an inference context.
+// flat and dxw follow the live parameters: hpe_encoder_set_params uploads them from the host, hpe_encoder_set_params_dev rewrites them on
+// the device with every packing of ConvLayer (encoder_repack.hip); mean / istd / sd and the repack table are written once, by the reserve
 struct EncTrainWork {
     int B = 0;        // reserved batch (0: not reserved)
     int stash_B = 0;  // batch of the training forward that last filled the stash
     float *flat = nullptr;   // the live parameters in the flat layout (kernel HWIO | bias | gamma | beta per layer)
     float *mean = nullptr, *istd = nullptr;  // moving_mean and 1 / sqrt(moving_variance + eps) of every layer's channels, layer after layer
+    double *sd = nullptr;    // sqrt((double)moving_variance + (double)eps) of the same channels: what bn_fold divides by (encoder_repack.hip)
+    void *repack = nullptr;  // the device-side layer table of hpe_encoder_set_params_dev (encoder_repack.hip), built once by the reserve
+    unsigned repack_grid[8] = {};  // workgroups of each of its launches (0: the context holds nothing of that form)
     float *stash = nullptr;  // every layer's post-activation output, then the max-pooled map; layer-major, B images each
     float *g0 = nullptr, *g1 = nullptr;  // [B][802816] block cotangents (ping-pong)
     float *sbig = nullptr;   // [B][802816] dz * s of the wide layers (branch2c, branch1)
@@ -141,6 +202,11 @@ struct EncTrainWork {
     float *feat = nullptr;   // [B][2048] features of the backward's own forward
     float *dxw[HPE_NUM_CONV] = {};  // data-gradient operands Wt[cin][k], beside the forward's packings
 };
+// floats of layer idx's data-gradient operand: rows = input channels padded to 128, k = (flipped tap, output channel); conv1 has none
+inline size_t conv_dxw_floats(int idx) {
+    const ConvSpec& s = specs()[idx];
+    return idx == 0 ? 0 : (size_t)round_up(s.cin, 128) * s.kh * s.kw * s.cout;
+}
 
 struct hpe_ctx {
     HpeConfig cfg{};
@@ -266,6 +332,11 @@ hipError_t features_proj(hpe_ctx* c, const float* features, int B, hipStream_t s
 hipError_t tail_impl(hpe_ctx* c, const float* feat, int B, const HpeOutputs* stage_outs, int n_outs, hipStream_t ts, hipEvent_t feat_free);
 hipError_t join_tail(hpe_ctx* c, hipStream_t st);  // wait on `st` for a pipelined call's tail, if one is pending
 int forward_impl(hpe_ctx* c, const float* images, int B, const HpeOutputs* stage_outs, int n_outs, hipStream_t st, bool pipelined);
+
+// encoder_repack.hip: the flat device parameters into every packing the ctx holds, in stream order
+size_t encoder_repack_reserve_floats();            // what encoder_repack_reserve allocates beyond the statistics (the layer table)
+int encoder_repack_reserve(hpe_ctx* c);            // builds the device-side layer table from the ctx's pointers; et.sd / et.mean / et.dxw exist
+hipError_t encoder_repack_launch(hpe_ctx* c, const float* flat_dev, hipStream_t st);
 
 // regressor_train.hip
 int regressor_param_offset(int idx, bool bias);  // idx 3: mean theta; idx 4 (bias false): the total

@@ -384,6 +384,9 @@ hipError_t encoder_impl(hpe_ctx* c, const float* images, int B, float* features,
         }
     }
     c->co_running = 1;
+    // The join: an event behind the last launch of every chunk stream, waited for on the caller's stream.  Whatever is enqueued on `st`
+    // after this call therefore runs after every launch of it; hpe_encoder_set_params_dev relies on that to rewrite the weights in
+    // stream order without a wait of its own.
     for (int k = 1; k < nstream; ++k) {
         HIPE(hipEventRecord(c->ev_join[k - 1], c->aux[k - 1]));
         HIPE(hipStreamWaitEvent(st, c->ev_join[k - 1], 0));

@@ -63,23 +63,14 @@ static std::vector<unsigned short> to_bf16(const std::vector<float>& v) {
 // fp32 Wt[rows][K] -> bf16 [rows][3][K]: w = w0 + w1 + w2 exactly (finite weights), each piece rounded to nearest even (conv_gemm_f32s.hip)
 int upload_split(hpe_ctx* c, void** p, const std::vector<float>& wt, int rows, int K) {
     std::vector<unsigned short> ws((size_t)rows * 3 * K);
-    auto bf2f = [](unsigned short h) {
-        const unsigned u = (unsigned)h << 16;
-        float f;
-        memcpy(&f, &u, 4);
-        return f;
-    };
     for (int n = 0; n < rows; ++n)
         for (int k = 0; k < K; ++k) {
-            const float x = wt[(size_t)n * K + k];
-            const unsigned short h0 = f2bf(x);
-            const float r1 = x - bf2f(h0);
-            const unsigned short h1 = f2bf(r1);
-            const float r2 = r1 - bf2f(h1);
+            unsigned short h[3];
+            bf16_split3(wt[(size_t)n * K + k], h);
             unsigned short* d = &ws[(size_t)n * 3 * K + k];
-            d[0] = h0;
-            d[K] = h1;
-            d[2 * K] = f2bf(r2);
+            d[0] = h[0];
+            d[K] = h[1];
+            d[2 * K] = h[2];
         }
     return upload_bf16(c, p, ws);
 }
@@ -255,22 +246,18 @@ static int pack_dual_weights(hpe_ctx* c) {
 // the F(2x2,3x3) Winograd weights of one 3x3 layer (conv_wino.hip)
 static int pack_wino_weights(hpe_ctx* c, const ConvSpec& s, ConvLayer& L) {
     int rc;
-    // U = G g G^T, G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1], in double; layout [cout/64][cin/8][16][2][64][4]
-    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    const int S = s.cin / 8;
+    // U = G g G^T in double (wino_elem); layout [cout/64][cin/8][16][2][64][4] (wino_u_base)
     std::vector<float> U((size_t)16 * s.cin * s.cout);
     for (int ci = 0; ci < s.cin; ++ci)
         for (int n = 0; n < s.cout; ++n) {
             double g[3][3];
             for (int a = 0; a < 3; ++a)
                 for (int b = 0; b < 3; ++b) g[a][b] = L.kernel[(((size_t)a * 3 + b) * s.cin + ci) * s.cout + n];
-            const size_t base = ((((size_t)(n >> 6) * S + (ci >> 3)) * 16) * 2 + ((ci >> 2) & 1)) * 256 + (size_t)(n & 63) * 4 + (ci & 3);
+            const size_t base = wino_u_base(n, ci, s.cin);
             for (int xi = 0; xi < 4; ++xi)
                 for (int nu = 0; nu < 4; ++nu) {
-                    double u = 0.0;
-                    for (int a = 0; a < 3; ++a)
-                        for (int b = 0; b < 3; ++b) u += G[xi][a] * G[nu][b] * g[a][b];
-                    U[base + (size_t)(xi * 4 + nu) * 512] = (float)u;
+                    const double gx[3] = {wino_g(xi, 0), wino_g(xi, 1), wino_g(xi, 2)}, gn[3] = {wino_g(nu, 0), wino_g(nu, 1), wino_g(nu, 2)};
+                    U[base + (size_t)(xi * 4 + nu) * 512] = wino_elem(gx, gn, g);
                 }
         }
     if ((rc = upload_to(c, &L.wino_u, U))) return rc;
@@ -280,24 +267,18 @@ static int pack_wino_weights(hpe_ctx* c, const ConvSpec& s, ConvLayer& L) {
 // the F(4x4,3x3) Winograd weights of one 3x3 layer (conv_wino4.hip)
 static int pack_wino4_weights(hpe_ctx* c, const ConvSpec& s, ConvLayer& L) {
     int rc;
-    // F(4x4,3x3): U = G g G^T with G = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1], in double;
-    // layout [cout/64][cin/4][36][64][4]
-    static const double G4[6][3] = {{0.25, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                    {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-    const int S4 = s.cin / 4;
+    // F(4x4,3x3): U = G g G^T in double (wino_elem, rows of wino4_g); layout [cout/64][cin/4][36][64][4] (wino4_u_base)
     std::vector<float> U((size_t)36 * s.cin * s.cout);
     for (int ci = 0; ci < s.cin; ++ci)
         for (int n = 0; n < s.cout; ++n) {
             double g[3][3];
             for (int a = 0; a < 3; ++a)
                 for (int b = 0; b < 3; ++b) g[a][b] = L.kernel[(((size_t)a * 3 + b) * s.cin + ci) * s.cout + n];
-            const size_t base = (((size_t)(n >> 6) * S4 + (ci >> 2)) * 36) * 256 + (size_t)(n & 63) * 4 + (ci & 3);
+            const size_t base = wino4_u_base(n, ci, s.cin);
             for (int xi = 0; xi < 6; ++xi)
                 for (int nu = 0; nu < 6; ++nu) {
-                    double u = 0.0;
-                    for (int a = 0; a < 3; ++a)
-                        for (int b = 0; b < 3; ++b) u += G4[xi][a] * G4[nu][b] * g[a][b];
-                    U[base + (size_t)(xi * 6 + nu) * 256] = (float)u;
+                    const double gx[3] = {wino4_g(xi, 0), wino4_g(xi, 1), wino4_g(xi, 2)}, gn[3] = {wino4_g(nu, 0), wino4_g(nu, 1), wino4_g(nu, 2)};
+                    U[base + (size_t)(xi * 6 + nu) * 256] = wino_elem(gx, gn, g);
                 }
         }
     if ((rc = upload_to(c, &L.wino4_u, U))) return rc;
@@ -306,13 +287,13 @@ static int pack_wino4_weights(hpe_ctx* c, const ConvSpec& s, ConvLayer& L) {
 
 // fused stem: the conv1 weights in the k enumeration of stem_fused.hip
 static int pack_stem_weights(hpe_ctx* c, ConvLayer& L) {
-    // bf16 [64][7][32], k as in Wt[n][k]; fp32 [64][160], k = kh * 22 + 1 + kw * 3 + ci
+    // bf16 [64][7][32], k as in Wt[n][k]; fp32 [64][160], k = stem_w_k
     const size_t ld = c->bf16 ? 7 * 32 : 160;
     std::vector<float> wp(64 * ld, 0.f);
     for (int kh = 0; kh < 7; ++kh)
         for (int kw = 0; kw < 7; ++kw)
             for (int ci = 0; ci < 3; ++ci) {
-                const int k = c->bf16 ? conv_wt_k(0, kh, kw, ci) : kh * 22 + 1 + kw * 3 + ci;
+                const int k = c->bf16 ? conv_wt_k(0, kh, kw, ci) : stem_w_k(kh, kw, ci);
                 for (int n = 0; n < 64; ++n) wp[n * ld + k] = L.kernel[(((size_t)kh * 7 + kw) * 3 + ci) * 64 + n];
             }
     if (c->bf16) return upload_bf16(c, &L.stem_w, to_bf16(wp));

@@ -667,6 +667,28 @@ class HpeEngine(object):
             raise ValueError("flat must be [%d], got %s" % (ENCODER_PARAM_FLOATS, arr.shape))
         _lib.check(self.lib.hpe_encoder_set_params(self._h, ptr))
 
+    def set_encoder_params_dev(self, flat):
+        """hpe_encoder_set_params_dev: replace the encoder's trainable parameters by the CUDA tensor ``flat`` on the device, in stream
+        order: every packing the context holds is rewritten by gather kernels, bit for bit what a fresh context would hold.  No host
+        round trip, no synchronisation, capturable."""
+        flat = _require_cuda_tensor(flat.detach(), "flat")
+        if tuple(flat.shape) != (ENCODER_PARAM_FLOATS,):
+            raise ValueError("flat must be [%d], got %s" % (ENCODER_PARAM_FLOATS, tuple(flat.shape)))
+        _lib.check(self.lib.hpe_encoder_set_params_dev(self._h, flat.data_ptr(), self._stream()))
+
+    def encoder_packing(self, idx, which):
+        """hpe_debug_encoder_packing: the bytes of one packing of layer idx (``which``: a name of _lib.ENCODER_PACKINGS or its index)
+        as a CUDA uint8 tensor; None if this context does not hold that form of that layer"""
+        torch = _torch()
+        if isinstance(which, str):
+            which = _lib.ENCODER_PACKINGS.index(which)
+        n = self.lib.hpe_debug_encoder_packing_bytes(self._h, int(idx), int(which))
+        if n == 0:
+            return None
+        out = torch.empty(n, dtype=torch.uint8, device=self.tdev)
+        _lib.check(self.lib.hpe_debug_encoder_packing(self._h, int(idx), int(which), out.data_ptr(), self._stream()))
+        return out
+
     def encoder_forward_train(self, images):
         """hpe_encoder_forward_train: images [B,224,224,3] -> features [B,2048], layer by layer, every activation kept in the stash"""
         images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))

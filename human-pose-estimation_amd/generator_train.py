@@ -4,7 +4,8 @@ respect to the RegressionNetwork and mean theta (hpe_smpl_backward, hpe_kp_loss_
 hpe_regressor_backward), an Adam step and the new weights back into the engine on the device (hpe_regressor_set_params_dev).  Adam is
 torch.optim.Adam on ONE flat tensor; everything else runs in libhpe_hip.so.  With ``train_encoder=True`` the encoder (BatchNorm statistics
 fixed, fp32) is in the same step, as in the reference (src/trainer.py:481): features come from ``encoder_features``, the one
-``.backward()`` fills both flat gradients, a second Adam steps the encoder's flat tensor and ``set_encoder_params`` installs it.
+``.backward()`` fills both flat gradients, a second Adam steps the encoder's flat tensor and ``set_encoder_params_dev`` installs it on the device, in stream order
+(hpe_encoder_set_params_dev).
 ``grad_features`` is returned either way."""
 from __future__ import annotations
 
@@ -111,7 +112,7 @@ class GeneratorTrainer(object):
         eng.set_regressor_params(self.params)
         if enc:
             self.encoder_optimizer.step()
-            eng.set_encoder_params(self.encoder_params)
+            eng.set_encoder_params_dev(self.encoder_params)
         det = lambda ts: [t.detach() for t in ts]  # noqa: E731
         return {"kpr_losses": det(kpr), "mr_losses": det(mr), "generator_critic_losses": det(gc), "pred_keypoints": pred_kp,
                 "generated_cams": thetas[S - 1, :, :3].detach(), "thetas": [thetas[i].detach() for i in range(S)],

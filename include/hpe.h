@@ -360,7 +360,8 @@ int hpe_encoder_param_offset(int idx, int which);
 /* hpe_encoder_train_reserve allocates, once and outside any capture, what the calls below need for batches up to B (1 <= B <= max_batch):
  * the activation stash (every layer's output and the pooled map, about 11 M floats per image), the cotangent buffers, the partial sums of
  * the weight gradient and the data-gradient packings of the weights (about 94 MB, kept beside the forward's packings); it also rebuilds
- * the flat parameters from the packed weights.  hpe_encoder_train_ws_floats(B): the floats it allocates.  An inference context that never
+ * the flat parameters from the packed weights, and stores what hpe_encoder_set_params_dev needs (sqrt(var + eps) per channel in double, a
+ * small layer table).  hpe_encoder_train_ws_floats(B): the floats it allocates.  An inference context that never
  * calls it does not grow.  A second call with a B not above the first is a no-op; a larger one is refused (HPE_ERR_STATE).
  * hpe_encoder_wg_slices(idx, B): the number of pixel slices the weight gradient of layer idx is cut into at batch B (host code). */
 int hpe_encoder_train_reserve(hpe_ctx* ctx, int B);
@@ -383,6 +384,43 @@ int hpe_encoder_get_params(hpe_ctx* ctx, float* flat_dev, void* stream);
  * changes, captured graphs stay valid.  SYNCHRONOUS (it waits for the device before and after) and NOT capturable.  Afterwards
  * hpe_encoder gives the bits of a fresh context that loaded the same values.  Needs hpe_encoder_train_reserve. */
 int hpe_encoder_set_params(hpe_ctx* ctx, const float* flat_host);
+/* The same replacement from DEVICE memory, in stream order: flat_dev [hpe_encoder_param_floats()] is read by a few gather kernels on
+ * `stream` (one per packing form, every layer in one launch; seven launches and one copy) that rewrite, in the buffers that already
+ * exist, every packing the context holds -- the GEMM weights Wt[n_pad][k_pad], their bf16 split, both Winograd forms, the fused-stem
+ * weights, the folded BatchNorm scale / shift, the dual-source weights with their split and shift, the data-gradient packings and the
+ * flat copy.  No host copy, no synchronisation, no allocation: capturable.  Moving mean and variance stay as loaded.  Afterwards
+ * hpe_encoder, hpe_forward*, hpe_debug_conv, hpe_encoder_forward_train, hpe_encoder_backward and hpe_encoder_get_params give, bit for
+ * bit, what a fresh context that loaded the same values gives (the folded values are computed in double in the host packers' operation
+ * order; sqrt(var + eps) is taken once, on the host, by hpe_encoder_train_reserve).
+ * Ordering: the caller orders the call after everything that still reads the weights.  Launches issued through the same `stream` are
+ * ordered by the library: every encoder call makes `stream` wait for its batch-chunk streams before it returns (an event per chunk
+ * stream, recorded behind its last launch), so nothing of an earlier call on `stream` can still run when these kernels start; the tail
+ * of hpe_forward_pipelined reads no encoder weight.  Calls on other streams, and flat_dev itself until the launches have run, are the
+ * caller's to order.  HPE_ERR_INVALID for a NULL ctx or pointer; HPE_ERR_STATE before hpe_finalize or hpe_encoder_train_reserve, on a
+ * dead context and on a bf16 context. */
+int hpe_encoder_set_params_dev(hpe_ctx* ctx, const float* flat_dev, void* stream);
+/* Read-back of one packing of layer idx for tests: `which` names the buffer.  hpe_debug_encoder_packing_bytes: its size in bytes, 0 if
+ * this context does not hold that form of that layer (a plan option off, a layer the form does not apply to, HPE_PACK_DXW / HPE_PACK_FLAT
+ * before hpe_encoder_train_reserve, a bf16 or unfinalized context, an index out of range).  hpe_debug_encoder_packing copies that many
+ * bytes to dst_dev on `stream` (device to device): HPE_ERR_INVALID for idx or which out of range or a NULL pointer, HPE_ERR_STATE where
+ * the size is 0.  HPE_PACK_FLAT is layer idx's [kernel | bias | gamma | beta] slice of the flat copy. */
+enum {
+    HPE_PACK_W = 0,        /* Wt[n_pad][k_pad] fp32 */
+    HPE_PACK_W_SPLIT,      /* bf16 [n_pad][3][k_pad] (f32_split) */
+    HPE_PACK_WINO_U,       /* F(2x2,3x3) [cout/64][cin/8][16][2][64][4] */
+    HPE_PACK_WINO4_U,      /* F(4x4,3x3) [cout/64][cin/4][36][64][4] */
+    HPE_PACK_STEM_W,       /* conv1: fp32 [64][160] */
+    HPE_PACK_SCALE,        /* [cout] */
+    HPE_PACK_SHIFT,        /* [cout] */
+    HPE_PACK_W_DUAL,       /* *_branch2c of a conv_block: [n_pad][K1 + K2] fp32, scales folded in */
+    HPE_PACK_W_DUAL_SPLIT, /* bf16 [n_pad][3][K1 + K2] */
+    HPE_PACK_SHIFT_DUAL,   /* [cout] */
+    HPE_PACK_DXW,          /* data-gradient operand Wt[cin padded to 128][taps * cout], taps flipped */
+    HPE_PACK_FLAT,         /* the layer's slice of the flat parameters */
+    HPE_PACK_COUNT
+};
+long long hpe_debug_encoder_packing_bytes(hpe_ctx* ctx, int idx, int which);
+int hpe_debug_encoder_packing(hpe_ctx* ctx, int idx, int which, void* dst_dev, void* stream);
 /* One layer's gate, weight gradient and data gradient: x_dev the layer's input (idx 0: the images), y_dev its output (after ReLU; the
  * gate is [y > 0]) or NULL for a layer without activation (the projection shortcuts in the network: dz = dy), dy_dev the cotangent of y.  grad_layer_dev receives [kernel | bias | gamma | beta] of that layer, dx_dev
  * [B,hin,hin,cin] the data gradient (NULL: not computed; must be NULL for idx 0). */

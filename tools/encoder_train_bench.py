@@ -1,9 +1,12 @@
-"""ms per hpe_encoder_backward and per hpe_encoder_set_params at B in {8, 32, 64}, against the same ResNet-50 (frozen BatchNorm statistics)
+"""ms per hpe_encoder_backward, per hpe_encoder_set_params (host) and per hpe_encoder_set_params_dev (device) at B in {8, 32, 64}, against the same ResNet-50 (frozen BatchNorm statistics)
 in torch fp32 with autograd in the same process.  Prints one JSON line and writes profiles/encoder_train_bench.json.
 
     python tools/encoder_train_bench.py [--batches 8,32,64] [--iters 10] [--out profiles/encoder_train_bench.json]
 
-Timing: device events around `iters` back-to-back calls after 3 warm-up calls, median of 5 such groups; torch's TF32 paths are off."""
+Timing: device events around `iters` back-to-back calls after 3 warm-up calls, median of 5 such groups (the backward, torch and the device
+update alike; the host update is wall time over 3 calls); torch's TF32 paths are off.  `set_params_dev_bytes_written` is what one device
+update writes at the default plan (every packing the context holds, from hpe_debug_encoder_packing_bytes), `set_params_dev_write_GBps`
+those bytes over the measured time."""
 import argparse
 import json
 import os
@@ -19,7 +22,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 import hpe_amd  # noqa: E402
-from hpe_amd import synthetic  # noqa: E402
+from hpe_amd import _lib, synthetic  # noqa: E402
 from hpe_amd.resnet_spec import CONV_SPECS, STAGE_BLOCKS  # noqa: E402
 
 
@@ -92,8 +95,10 @@ def main():
     eng.finalize()
     eng.reserve_encoder_train(max(batches))
     ref = TorchResNet(params)
-    flat = eng.encoder_params().cpu()
-    res = {"device": torch.cuda.get_device_name(0), "iters": a.iters, "rows": []}
+    flat_dev = eng.encoder_params()
+    flat = flat_dev.cpu()
+    written = sum(eng.lib.hpe_debug_encoder_packing_bytes(eng._h, i, w) for i in range(len(CONV_SPECS)) for w in range(len(_lib.ENCODER_PACKINGS)))
+    res = {"device": torch.cuda.get_device_name(0), "iters": a.iters, "set_params_dev_bytes_written": written, "rows": []}
     for B in batches:
         img = torch.from_numpy(synthetic.make_images(B, seed=1)).cuda()
         gf = torch.randn(B, 2048, device="cuda")
@@ -103,8 +108,10 @@ def main():
         for _ in range(3):
             eng.set_encoder_params(flat)
         setp = (time.perf_counter() - t0) / 3 * 1e3
+        setd = timed(lambda: eng.set_encoder_params_dev(flat_dev), a.iters)
         res["rows"].append({"B": B, "hpe_encoder_backward_ms": round(hip, 3), "torch_autograd_fwd_bwd_ms": round(tch, 3),
-                            "hpe_encoder_set_params_ms": round(setp, 1)})
+                            "hpe_encoder_set_params_ms": round(setp, 1), "hpe_encoder_set_params_dev_ms": round(setd, 3),
+                            "set_params_dev_write_GBps": round(written / setd / 1e6, 1)})
     eng.close()
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
