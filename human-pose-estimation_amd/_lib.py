@@ -104,6 +104,24 @@ class HpeDebugGemm(C.Structure):
                 ("shift", C.c_void_p), ("y", C.c_void_p), ("split_k", C.POINTER(C.c_int))]
 
 
+# HpeConvRoute.kernel (include/hpe.h: HPE_CONV_K_*) and .join
+CONV_KERNELS = ("f32", "f32s", "bf16", "bf16_p8", "halo3", "wino", "wino_fused", "wino4", "wino4_fused")
+BLOCK_JOINS = ("separate", "dual", "chain")
+
+
+class HpeConvRoute(C.Structure):
+    """what hpe_debug_conv_route fills (include/hpe.h)"""
+    _fields_ = [("struct_size", C.c_int), ("kernel", C.c_int), ("mode", C.c_int), ("tile", C.c_int), ("in_slab8", C.c_int), ("out_slab8", C.c_int),
+                ("join", C.c_int), ("join_kernel", C.c_int), ("join_tile", C.c_int), ("next_slab8", C.c_int), ("packs", C.c_uint), ("reserved", C.c_int)]
+
+
+def conv_route(lib, cfg, idx, B, concurrent=False, residual=False, workspace=True):
+    """hpe_debug_conv_route on an HpeConfig: no context, no GPU"""
+    r = HpeConvRoute(struct_size=C.sizeof(HpeConvRoute))
+    check(lib.hpe_debug_conv_route(C.byref(cfg), int(idx), int(B), int(concurrent), int(residual), int(workspace), C.byref(r)))
+    return r
+
+
 # `which` of hpe_debug_encoder_packing (include/hpe.h: HPE_PACK_*)
 ENCODER_PACKINGS = ("w", "w_split", "wino_u", "wino4_u", "stem_w", "scale", "shift", "w_dual", "w_dual_split", "shift_dual", "dxw", "flat")
 
@@ -196,6 +214,7 @@ _PROTOS = {
     "hpe_debug_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_gemm_ex": (C.c_int, [C.c_void_p, C.POINTER(HpeDebugGemm), C.c_void_p]),
     "hpe_debug_gemm_check": (C.c_int, [C.POINTER(HpeDebugGemm), C.c_int, C.c_int]),
+    "hpe_debug_conv_route": (C.c_int, [C.POINTER(HpeConfig), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(HpeConvRoute)]),
     "hpe_debug_maxpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_avgpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_joint_regress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -341,16 +341,6 @@ void pack_dx_weights(int idx, const float* kernel, std::vector<float>& out) {
         }
 }
 
-// one forward layer as hpe_debug_conv launches it
-hipError_t train_conv(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st) {
-    if (!res && (use_wino_fused(c, idx, B) || use_wino4_fused(c, idx, B))) {
-        const ConvSpec& s = specs()[idx];
-        HIPE(hpe_launch_nhwc_to_slab8(x, c->T1, (long)B * s.hin * s.hin, s.cin, st));
-        return run_conv(c, idx, c->T1, B, nullptr, relu, y, st, nullptr, 0, CONV_IN_SLAB8);
-    }
-    return run_conv(c, idx, x, B, res, relu, y, st, c->wino_v);
-}
-
 void gate(const float* dy, const float* y, const float* s, float* dz, float* dzs, long n, int N, hipStream_t st) {
     hipLaunchKernelGGL(enc_gate_kernel, grid1(n / 4), dim3(256), 0, st, reinterpret_cast<const f32x4*>(dy), reinterpret_cast<const f32x4*>(y), s,
                        reinterpret_cast<f32x4*>(dz), reinterpret_cast<f32x4*>(dzs), n / 4, N / 4);
@@ -432,18 +422,18 @@ float* stash_of(hpe_ctx* c, int idx, int B) {
 
 hipError_t forward_train(hpe_ctx* c, const float* images, int B, float* features, hipStream_t st) {
     HIPE(hpe_launch_pad_input(images, c->padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
-    HIPE(run_conv(c, 0, c->padded, B, nullptr, 1, stash_of(c, 0, B), st));
+    HIPE(run_conv_nhwc(c, 0, c->padded, B, nullptr, 1, stash_of(c, 0, B), st));
     HIPE(hpe_launch_maxpool(stash_of(c, 0, B), stash_of(c, -1, B), B, 112, 64, st));
     for (const ResBlock& blk : blocks()) {
         const float* cur = stash_of(c, blk.in, B);
-        HIPE(train_conv(c, blk.i2a, cur, B, nullptr, 1, stash_of(c, blk.i2a, B), st));
-        HIPE(train_conv(c, blk.i2b, stash_of(c, blk.i2a, B), B, nullptr, 1, stash_of(c, blk.i2b, B), st));
+        HIPE(run_conv_nhwc(c, blk.i2a, cur, B, nullptr, 1, stash_of(c, blk.i2a, B), st));
+        HIPE(run_conv_nhwc(c, blk.i2b, stash_of(c, blk.i2a, B), B, nullptr, 1, stash_of(c, blk.i2b, B), st));
         const float* res = cur;
         if (blk.first) {
-            HIPE(train_conv(c, blk.i1, cur, B, nullptr, 0, stash_of(c, blk.i1, B), st));
+            HIPE(run_conv_nhwc(c, blk.i1, cur, B, nullptr, 0, stash_of(c, blk.i1, B), st));
             res = stash_of(c, blk.i1, B);
         }
-        HIPE(train_conv(c, blk.i2c, stash_of(c, blk.i2b, B), B, res, 1, stash_of(c, blk.i2c, B), st));
+        HIPE(run_conv_nhwc(c, blk.i2c, stash_of(c, blk.i2b, B), B, res, 1, stash_of(c, blk.i2c, B), st));
     }
     return hpe_launch_avgpool(stash_of(c, blocks().back().i2c, B), features, B, 49, HPE_FEATURE_DIM, HPE_FEATURE_DIM, st);
 }

@@ -638,7 +638,7 @@ int hpe_debug_conv(hpe_ctx* c, int idx, const float* x, int B, const float* resi
         const long nin = (long)B * s.hin * s.hin * s.cin, nout = (long)B * s.hout * s.hout * s.cout;
         HIP_TRY(hpe_launch_f32_to_bf16(x, c->X0, nin, st));
         if (residual) HIP_TRY(hpe_launch_f32_to_bf16(residual, c->SC, nout, st));
-        HIP_TRY(run_conv(c, idx, c->X0, B, residual ? c->SC : nullptr, relu, c->X1, st));
+        HIP_TRY(run_conv_nhwc(c, idx, c->X0, B, residual ? c->SC : nullptr, relu, c->X1, st));
         HIP_TRY(hpe_launch_bf16_to_f32(c->X1, y, nout, st));
         return HPE_OK;
     }
@@ -647,14 +647,7 @@ int hpe_debug_conv(hpe_ctx* c, int idx, const float* x, int B, const float* resi
         HIP_TRY(hpe_launch_pad_input(x, c->padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
         in = c->padded;
     }
-    if (!residual && (use_wino_fused(c, idx, B) || use_wino4_fused(c, idx, B))) {
-        // the fused Winograd kernel reads channel-slab major input; in the network its 1x1 producer writes that directly
-        const ConvSpec& s = specs()[idx];
-        HIP_TRY(hpe_launch_nhwc_to_slab8(in, c->T1, (long)B * s.hin * s.hin, s.cin, st));
-        HIP_TRY(run_conv(c, idx, c->T1, B, nullptr, relu, y, st, nullptr, 0, CONV_IN_SLAB8));
-        return HPE_OK;
-    }
-    HIP_TRY(run_conv(c, idx, in, B, residual, relu, y, st, c->wino_v));
+    HIP_TRY(run_conv_nhwc(c, idx, in, B, residual, relu, y, st));
     return HPE_OK;
 }
 
@@ -772,6 +765,29 @@ int hpe_debug_gemm_check(const HpeDebugGemm* g, int kernel, int w_piece) {
     p.scale = p.shift = p.zero = present;
     if (k == GEMM_K_F32S) p.w_piece = w_piece;
     if (const char* clause = gemm_contract(p, g->mode, g->tile, k)) return fail(HPE_ERR_INVALID, "hpe_debug_gemm_check: " + debug_gemm_rejected(g, clause));
+    return HPE_OK;
+}
+
+int hpe_debug_conv_route(const HpeConfig* cfg, int idx, int B, int concurrent, int residual, int workspace, HpeConvRoute* out) {
+    static_assert(HPE_CONV_K_F32 == CONV_K_F32 && HPE_CONV_K_HALO3 == CONV_K_HALO3 && HPE_CONV_K_WINO4_FUSED == CONV_K_WINO4_FUSED && HPE_CONV_K_COUNT == CONV_K_WINO4_FUSED + 1,
+                  "include/hpe.h numbers the kernels as ConvKernel does");
+    if (!cfg || !out) return fail(HPE_ERR_INVALID, "null argument");
+    if (cfg->struct_size != (int)sizeof(HpeConfig) || out->struct_size != (int)sizeof(HpeConvRoute))
+        return fail(HPE_ERR_INVALID, "hpe_debug_conv_route: HpeConfig.struct_size / HpeConvRoute.struct_size are " + std::to_string(cfg->struct_size) + " / " +
+                                         std::to_string(out->struct_size) + ", this library's are " + std::to_string(sizeof(HpeConfig)) + " / " + std::to_string(sizeof(HpeConvRoute)));
+    if (idx < 0 || idx >= HPE_NUM_CONV || B < 1) return fail(HPE_ERR_INVALID, "hpe_debug_conv_route: idx must be in [0, HPE_NUM_CONV) and B >= 1");
+    const HpePlan pl = hpe_resolve_plan(*cfg);
+    const bool bf16 = cfg->encoder_dtype == 1;
+    const ConvQuery q{B, concurrent != 0, residual != 0, workspace != 0};
+    const ConvRoute r = route_conv(pl, bf16, idx, q);
+    *out = HpeConvRoute{(int)sizeof(HpeConvRoute), r.kernel, r.mode, r.tile, r.in_slab8, 0, 0, -1, -1, 0, layer_packs(pl, bf16, idx), 0};
+    for (const ResBlock& blk : blocks()) {
+        if (idx != blk.i2a && idx != blk.i2c) continue;
+        const BlockRoute b = route_block(pl, bf16, blk, q);
+        if (idx == blk.i2a) out->out_slab8 = b.r2a.out_slab8;
+        if (idx == blk.i2c) out->join = b.join, out->next_slab8 = b.u1_slab8;
+        if (idx == blk.i2c && b.join == JOIN_DUAL) out->join_kernel = b.r2c.kernel, out->join_tile = b.r2c.tile;
+    }
     return HPE_OK;
 }
 

@@ -1,6 +1,6 @@
 // hpe_ctx.h -- the context behind the C ABI of include/hpe.h and what its translation units share: the layer table, the per-layer
-// weights, error reporting, device selection and allocation helpers.  hpe_plan.hip resolves the plan, hpe_finalize.hip packs the weights and
-// sizes the workspaces, hpe_encoder.hip holds the launch sequences, hpe_api.hip the extern "C" entry points.
+// weights, error reporting, device selection and allocation helpers.  hpe_plan.hip resolves the plan and routes every conv launch,
+// hpe_finalize.hip packs the weights and sizes the workspaces, hpe_encoder.hip holds the launch sequences, hpe_api.hip the extern "C" entry points.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,6 +75,9 @@ inline int conv_wt_k(int idx, int kh, int kw, int ci) {
     const ConvSpec& s = specs()[idx];
     return idx == 0 ? kh * 32 + kw * 4 + ci : (kh * s.kw + kw) * s.cin + ci;
 }
+
+// ... and the length of that k axis: whole k-slabs of the GEMM kernels, 32 floats or 64 bf16 (the bf16 stem slab s holds kernel rows (2s, 2s + 1))
+inline int conv_k_pad(int idx, bool bf16) { return round_up(idx == 0 ? 7 * 32 : specs()[idx].kh * specs()[idx].kw * specs()[idx].cin, bf16 ? 64 : 32); }
 
 // The packing rules the host packers (hpe_finalize.hip, encoder_train.hip) and the repack kernels (encoder_repack.hip) share.  Every
 // floating-point helper fixes its operation order and turns contraction off, so that both sides round alike.
@@ -317,10 +320,12 @@ void release_device_state(hpe_ctx* c);  // release everything a (possibly partia
 // hpe_finalize allocated: no pointer changes.  Synchronous.
 int repack_encoder(hpe_ctx* c);
 
-// hpe_encoder.hip
-enum { CONV_OUT_SLAB8 = 1, CONV_IN_SLAB8 = 2, CONV_CONCURRENT = 4 };
-hipError_t run_conv(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
-                    float* wino_v = nullptr, int slot = 0, int flags = 0);
+// hpe_encoder.hip: launch what the route says.  wino_v: the launch's slice of the Winograd V workspace, slot: its chunk stream
+hipError_t run_conv(hpe_ctx* c, int idx, const ConvRoute& r, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
+                    float* wino_v = nullptr, int slot = 0);
+// one layer on NHWC input, alone on the device, as hpe_debug_conv and the training forward launch it: asks the route and converts the
+// input to channel-slab major (through T1) when the route reads that
+hipError_t run_conv_nhwc(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st);
 hipError_t run_chain(hpe_ctx* c, int i2c, bool first, const float* t2, const float* res, int B, float* t3, float* u1, hipStream_t st,
                      bool u1_slab8 = false);
 hipError_t encoder_impl(hpe_ctx* c, const float* images, int B, float* features, int ldfeat, hipStream_t st);

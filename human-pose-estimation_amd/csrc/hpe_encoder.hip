@@ -1,4 +1,4 @@
-// hpe_encoder.hip -- the launch sequences: one conv layer / dual-source block / chained pair through the kernel the plan picks, the
+// hpe_encoder.hip -- the launch sequences: one conv layer / dual-source block / chained pair through the kernel its route names, the
 // encoder over batch chunks, the regressor steps and the forward tail.  Host logic only.
 #include <hip/hip_runtime.h>
 
@@ -12,153 +12,91 @@
 
 #include "hpe_ctx.h"
 
-// one conv layer (+BN fold, +residual, +ReLU) through the implicit-GEMM kernel
+// the implicit GEMM a route names, p filled but for the workspace; w_split: the three-bf16-piece form of p.w (rows of p.ldw elements)
+static hipError_t launch_gemm(hpe_ctx* c, GemmArgs& p, const ConvRoute& r, const void* w_split, hipStream_t st) {
+    // The ctx has ONE split-K workspace: only a launch that is alone on the device may use it.  Batch chunks running on
+    // concurrent streams never split K, whatever their size (their grids overlap each other instead).
+    if (!r.concurrent) p.partial = c->partial, p.partial_floats = c->partial_floats;
+    if (r.kernel == CONV_K_BF16 || r.kernel == CONV_K_BF16_P8) return hpe_launch_gemm_bf16(p, r.mode, r.tile, st);
+    if (r.kernel != CONV_K_F32S) return hpe_launch_gemm(p, r.mode, r.tile, c->plan.splitk_min_slabs, st);
+    if (!w_split) return hipErrorInvalidValue;
+    p.w = static_cast<const float*>(w_split);
+    p.w_piece = p.ldw;
+    p.ldw *= 3;
+    return hpe_launch_gemm_f32s(p, r.mode, r.tile, st);
+}
 
-hipError_t run_conv(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
-                    float* wino_v, int slot, int flags) {
+// one conv layer (+BN fold, +residual, +ReLU) through the kernel of its route (hpe_plan.hip).  A route whose packing or workspace this
+// context does not hold, or a residual on a kernel that takes none, is refused: nothing is launched
+hipError_t run_conv(hpe_ctx* c, int idx, const ConvRoute& r, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
+                    float* wino_v, int slot) {
     const ConvSpec& s = specs()[idx];
     const ConvLayer& L = c->conv[idx];
-    if ((flags & CONV_IN_SLAB8) && use_wino4_fused(c, idx, B))
-        return hpe_launch_wino4_fused_conv3(x, L.wino4_u, L.scale, L.shift, c->zeros, y, s.cout, B, s.hin, s.hin, s.cin, s.cout, relu, st);
-    if (flags & CONV_IN_SLAB8)
-        return hpe_launch_wino_fused_conv3(x, L.wino_u, L.scale, L.shift, c->zeros, y, s.cout, B, s.hin, s.hin, s.cin, s.cout, relu, st);
-    if (wino_v && !res && use_wino4(c, idx, B))
-        return hpe_launch_wino4_conv3(x, s.cin, L.wino4_u, L.scale, L.shift, y, s.cout, B, s.hin, s.hin, s.cin, s.cout, relu, wino_v, st,
-                                      (flags & CONV_CONCURRENT) ? c->co_running : 1,
-                                      c->w4_split && slot >= 0 && slot < 4 ? c->w4_split + (size_t)slot * hpe_wino4_split_ws_floats() : nullptr, c->plan.wino4_n32,
-                                      c->plan.w4_abl);
-    // Winograd needs enough (64-tile x 64-cout) work items to occupy the 256 CUs (one 8-wave workgroup each); below that
-    // the direct kernel with split-K is faster (measured crossover: batch ~32, profiles/r01/g_wino_small_batch.txt)
-    if (L.wino_u && wino_v && !res && s.cin >= c->plan.wino_min_c &&
-        (long)((B * ((s.hin + 1) / 2) * ((s.hin + 1) / 2) + 63) / 64) * (s.cout / 64) >= c->plan.wino_min_items)
-    {
-        WinoStreamK sk{};
-        if (c->wino_ws && slot >= 0 && slot < 4) {
-            sk.ws = c->wino_ws + (size_t)slot * c->n_cu * HPE_WINO_WS_FLOATS;
-            sk.flags = c->wino_flags + (size_t)slot * c->n_cu;
-            sk.epoch = ++c->wino_epoch;
-            if (sk.epoch == 0) sk.epoch = ++c->wino_epoch;
-            sk.n_wg = c->n_cu;
-            sk.err = c->dev_err;
+    const int H = s.hin;
+    const bool f2 = r.kernel == CONV_K_WINO || r.kernel == CONV_K_WINO_FUSED, f4 = r.kernel == CONV_K_WINO4 || r.kernel == CONV_K_WINO4_FUSED;
+    if ((r.kernel >= CONV_K_HALO3 && res) || (f2 && !L.wino_u) || (f4 && !L.wino4_u) || ((f2 || f4) && !r.in_slab8 && !wino_v)) return hipErrorInvalidValue;
+    switch (r.kernel) {
+        case CONV_K_WINO4_FUSED: return hpe_launch_wino4_fused_conv3(x, L.wino4_u, L.scale, L.shift, c->zeros, y, s.cout, B, H, H, s.cin, s.cout, relu, st);
+        case CONV_K_WINO_FUSED: return hpe_launch_wino_fused_conv3(x, L.wino_u, L.scale, L.shift, c->zeros, y, s.cout, B, H, H, s.cin, s.cout, relu, st);
+        case CONV_K_WINO4:
+            return hpe_launch_wino4_conv3(x, s.cin, L.wino4_u, L.scale, L.shift, y, s.cout, B, H, H, s.cin, s.cout, relu, wino_v, st, r.concurrent ? c->co_running : 1,
+                                          c->w4_split && slot >= 0 && slot < 4 ? c->w4_split + (size_t)slot * hpe_wino4_split_ws_floats() : nullptr, c->plan.wino4_n32,
+                                          c->plan.w4_abl);
+        case CONV_K_WINO: {
+            WinoStreamK sk{};
+            if (c->wino_ws && slot >= 0 && slot < 4) {
+                sk.ws = c->wino_ws + (size_t)slot * c->n_cu * HPE_WINO_WS_FLOATS;
+                sk.flags = c->wino_flags + (size_t)slot * c->n_cu;
+                sk.epoch = ++c->wino_epoch;
+                if (sk.epoch == 0) sk.epoch = ++c->wino_epoch;
+                sk.n_wg = c->n_cu;
+                sk.err = c->dev_err;
+            }
+            return hpe_launch_wino_conv3(x, s.cin, L.wino_u, L.scale, L.shift, y, s.cout, B, H, H, s.cin, s.cout, relu, wino_v, c->wino_ws ? &sk : nullptr, st);
         }
-        return hpe_launch_wino_conv3(x, s.cin, L.wino_u, L.scale, L.shift, y, s.cout, B, s.hin, s.hin, s.cin, s.cout, relu, wino_v,
-                                     c->wino_ws ? &sk : nullptr, st);
+        case CONV_K_HALO3: {
+            Halo3Args h{};
+            h.x = reinterpret_cast<const __bf16*>(x), h.w = reinterpret_cast<const __bf16*>(L.w), h.y = reinterpret_cast<__bf16*>(y);
+            h.scale = L.scale, h.shift = L.shift;
+            h.M = B * s.hout * s.hout, h.N = s.cout, h.ldw = L.k_pad;
+            h.relu = relu, h.two = c->plan.halo3_two;
+            return hpe_launch_halo3_bf16(h, H, s.cin, st);
+        }
     }
     GemmArgs p{};
-    p.x = x;
-    p.w = L.w;
-    p.scale = L.scale;
-    p.shift = L.shift;
-    p.res = res;
-    p.y = y;
-    p.M = B * s.hout * s.hout;
-    p.N = s.cout;
-    p.K = L.k_pad;
-    p.ldw = L.k_pad;
-    p.w_rows = L.n_pad;
-    p.ldy = s.cout;
-    p.ldres = s.cout;
-    p.relu = relu;
-    p.Hi = p.Wi = s.hin;
-    p.Cin = s.cin;
-    p.Ho = p.Wo = s.hout;
-    p.stride = s.stride;
-    p.cin_slabs = s.cin / 32;
-    p.lda = s.cin;
-    p.zero = c->zeros;
-    p.y_slab8 = (flags & CONV_OUT_SLAB8) ? 1 : 0;
-    // The ctx has ONE split-K workspace: only a launch that is alone on the device may use it.  Batch chunks running on
-    // concurrent streams (CONV_CONCURRENT) never split K, whatever their size (their grids overlap each other instead).
-    if (!(flags & CONV_CONCURRENT)) {
-        p.partial = c->partial;
-        p.partial_floats = c->partial_floats;
+    p.x = x, p.w = L.w, p.scale = L.scale, p.shift = L.shift, p.res = res, p.y = y, p.zero = c->zeros;
+    p.M = B * s.hout * s.hout, p.N = s.cout, p.K = L.k_pad;
+    p.lda = s.cin, p.ldw = L.k_pad, p.w_rows = L.n_pad, p.ldy = p.ldres = s.cout;
+    p.Hi = p.Wi = H, p.Cin = s.cin, p.Ho = p.Wo = s.hout, p.stride = s.stride;
+    p.cin_slabs = s.cin / (c->bf16 ? 64 : 32);
+    p.relu = relu, p.y_slab8 = r.out_slab8 ? 1 : 0;
+    if (r.mode == GEMM_STEM) p.Hi = STEM_HP, p.Wi = STEM_WP, p.Cin = 4;
+    return launch_gemm(c, p, r, L.w_split, st);
+}
+
+hipError_t run_conv_nhwc(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st) {
+    const ConvRoute r = route_conv(c->plan, c->bf16, idx, ConvQuery{B, false, res != nullptr, c->wino_v != nullptr});
+    if (r.in_slab8) {
+        // the fused Winograd kernels read channel-slab major input; in the network their 1x1 producer writes that directly
+        const ConvSpec& s = specs()[idx];
+        HIPE(hpe_launch_nhwc_to_slab8(x, c->T1, (long)B * s.hin * s.hin, s.cin, st));
+        x = c->T1;
     }
-    int mode;
-    if (idx == 0) {
-        mode = GEMM_STEM;
-        p.Hi = STEM_HP;
-        p.Wi = STEM_WP;
-        p.Cin = 4;
-    } else if (s.kh == 3) {
-        mode = GEMM_CONV3;
-    } else if (s.stride == 1) {
-        mode = GEMM_DENSE;
-    } else {
-        mode = GEMM_STRIDED;
-    }
-    if (c->bf16 && mode == GEMM_CONV3 && !res && s.stride == 1 && (c->plan.halo3 & f4_bit(s.hin) ? true : false) &&
-        hpe_halo3_bf16_supported(s.hin, s.cin, s.cout) && L.k_pad >= 9 * s.cin)
-    {
-        Halo3Args h{};
-        h.x = reinterpret_cast<const __bf16*>(x);
-        h.w = reinterpret_cast<const __bf16*>(L.w);
-        h.scale = L.scale;
-        h.shift = L.shift;
-        h.y = reinterpret_cast<__bf16*>(y);
-        h.M = p.M;
-        h.N = s.cout;
-        h.ldw = L.k_pad;
-        h.relu = relu;
-        h.two = c->plan.halo3_two;
-        return hpe_launch_halo3_bf16(h, s.hin, s.cin, st);
-    }
-    if (c->bf16) {
-        p.cin_slabs = s.cin / 64;
-        return hpe_launch_gemm_bf16(p, mode, pick_bf16(c->plan, p.M, p.N, p.K, mode == GEMM_DENSE && res != nullptr && s.cout == 4 * s.cin, (flags & CONV_CONCURRENT) != 0, mode), st);
-    }
-    const bool expand = mode == GEMM_DENSE && res != nullptr && s.cout == 4 * s.cin;
-    const int f32s = (mode == GEMM_DENSE || mode == GEMM_STRIDED) ? pick_f32s(c->plan, L.w_split, p.M, p.N, p.K, expand) : -1;
-    if (f32s >= 0) {
-        p.w = static_cast<const float*>(L.w_split);
-        p.ldw = 3 * L.k_pad;
-        p.w_piece = L.k_pad;
-        return hpe_launch_gemm_f32s(p, mode, f32s, st);
-    }
-    return hpe_launch_gemm(p, mode, pick_tile(c->plan, p.M, p.N, p.K, expand, (flags & CONV_CONCURRENT) != 0), c->plan.splitk_min_slabs, st);
+    return run_conv(c, idx, r, x, B, res, relu, y, st, c->wino_v);
 }
 
 // branch2c (+BN) + branch1 (+BN) + add + ReLU of a conv_block as one dual-source GEMM: t2 [M, K1] dense, x NHWC strided
-static hipError_t run_dual(hpe_ctx* c, int i2c, int i1, const float* t2, const float* x, int B, float* y, hipStream_t st, int flags) {
+static hipError_t run_dual(hpe_ctx* c, int i2c, int i1, const ConvRoute& r, const float* t2, const float* x, int B, float* y, hipStream_t st) {
     const ConvSpec& s2 = specs()[i2c];
     const ConvSpec& s1 = specs()[i1];
     const ConvLayer& L = c->conv[i2c];
-    const int slab = c->bf16 ? 64 : 32;
     GemmArgs p{};
-    p.x = t2;
-    p.x2 = x;
-    p.w = L.w_dual;
-    p.scale = c->ones;
-    p.shift = L.shift_dual;
-    p.y = y;
-    p.M = B * s2.hout * s2.hout;
-    p.N = s2.cout;
-    p.K = L.k_dual;
-    p.k1_slabs = L.k1_dual / slab;
-    p.lda = s2.cin;
-    p.ldw = L.k_dual;
-    p.w_rows = round_up(s2.cout, 128);
-    p.ldy = s2.cout;
-    p.relu = 1;
-    p.Hi = p.Wi = s1.hin;
-    p.Cin = s1.cin;
-    p.Ho = p.Wo = s1.hout;
-    p.stride = s1.stride;
-    p.zero = c->zeros;
-    if (!(flags & CONV_CONCURRENT)) {
-        p.partial = c->partial;
-        p.partial_floats = c->partial_floats;
-    }
-    if (c->bf16) {
-        return hpe_launch_gemm_bf16(p, GEMM_DUAL, pick_bf16(c->plan, p.M, p.N, p.K, false, (flags & CONV_CONCURRENT) != 0, GEMM_DUAL), st);
-    }
-    const int f32s = pick_f32s(c->plan, L.w_dual_split, p.M, p.N, p.K, false);
-    if (f32s >= 0) {
-        p.w = static_cast<const float*>(L.w_dual_split);
-        p.ldw = 3 * L.k_dual;
-        p.w_piece = L.k_dual;
-        return hpe_launch_gemm_f32s(p, GEMM_DUAL, f32s, st);
-    }
-    return hpe_launch_gemm(p, GEMM_DUAL, pick_tile(c->plan, p.M, p.N, p.K, false, (flags & CONV_CONCURRENT) != 0), c->plan.splitk_min_slabs, st);
+    p.x = t2, p.x2 = x, p.w = L.w_dual, p.scale = c->ones, p.shift = L.shift_dual, p.y = y, p.zero = c->zeros;
+    p.M = B * s2.hout * s2.hout, p.N = s2.cout, p.K = L.k_dual;
+    p.k1_slabs = L.k1_dual / (c->bf16 ? 64 : 32), p.relu = 1;
+    p.lda = s2.cin, p.ldw = L.k_dual, p.w_rows = round_up(s2.cout, 128), p.ldy = s2.cout;
+    p.Hi = p.Wi = s1.hin, p.Cin = s1.cin, p.Ho = p.Wo = s1.hout, p.stride = s1.stride;
+    return launch_gemm(c, p, r, L.w_dual_split, st);
 }
 
 // res: the block input -- the residual of an identity block, the second A source of a conv_block
@@ -241,11 +179,11 @@ hipError_t run_dense(hpe_ctx* c, const float* x, int lda, int M, int K, const fl
     return hpe_launch_gemm(p, GEMM_DENSE, TILE_64x64, c->plan.splitk_min_slabs, st);
 }
 
-static hipError_t timed_conv(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
-                      float* wino_v = nullptr, int slot = 0, int flags = 0) {
+static hipError_t timed_conv(hpe_ctx* c, int idx, const ConvRoute& r, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
+                             float* wino_v = nullptr, int slot = 0) {
     const bool t2 = c->timing >= 2;
     if (t2) HIPE(hipEventRecord(c->cev0[idx], st));
-    HIPE(run_conv(c, idx, x, B, res, relu, y, st, wino_v, slot, flags));
+    HIPE(run_conv(c, idx, r, x, B, res, relu, y, st, wino_v, slot));
     if (t2) HIPE(hipEventRecord(c->cev1[idx], st));
     return hipSuccess;
 }
@@ -253,7 +191,6 @@ static hipError_t timed_conv(hpe_ctx* c, int idx, const float* x, int B, const f
 // the encoder on images [i0, i0+B) of the batch (all workspace buffers are image-major)
 static hipError_t encoder_chunk(hpe_ctx* c, const float* images, int i0, int B, float* features, int ldfeat, hipStream_t st, int slot = 0,
                          bool concurrent = false) {
-    const int cf = concurrent ? CONV_CONCURRENT : 0;
     // all workspace buffers are image-major; in bf16 mode the same allocations hold bf16 elements (half the bytes)
     const int esz = c->bf16 ? 2 : 4;
     auto at = [&](float* base, size_t elems) { return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + elems * esz); };
@@ -269,6 +206,7 @@ static hipError_t encoder_chunk(hpe_ctx* c, const float* images, int i0, int B, 
     float* nxt = at(c->X1, o_big);
     // the chunk's slice of the Winograd workspace (chunks of < 32 images only occur unchunked, i0 == 0: the slack at the end covers them)
     float* wv = (c->wino_v && (i0 == 0 || B >= 32)) ? c->wino_v + (size_t)i0 * WINO_V_PITCH : nullptr;
+    const ConvQuery q{B, concurrent, false, wv != nullptr};
     // the fused stem stages whole 16-byte chunks of the caller's rows; an images pointer that is only float-aligned (e.g. a
     // tensor view at an odd offset) takes the pad / im2col / pool path, which reads the images with scalar loads
     if (c->plan.stem_fused && (reinterpret_cast<uintptr_t>(images + o_img) & 15) == 0) {
@@ -280,38 +218,35 @@ static hipError_t encoder_chunk(hpe_ctx* c, const float* images, int i0, int B, 
         if (t2) HIPE(hipEventRecord(c->cev1[0], st));
     } else if (c->bf16) {
         HIPE(hpe_launch_pad_input_bf16(images + o_img, padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
-        HIPE(timed_conv(c, 0, padded, B, nullptr, 1, SC, st, nullptr, 0, cf));
+        HIPE(timed_conv(c, 0, route_conv(c->plan, true, 0, q), padded, B, nullptr, 1, SC, st));
         HIPE(hpe_launch_maxpool_bf16(SC, cur, B, 112, 64, st));
     } else {
         HIPE(hpe_launch_pad_input(images + o_img, padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
-        HIPE(timed_conv(c, 0, padded, B, nullptr, 1, SC, st, nullptr, 0, cf));
+        HIPE(timed_conv(c, 0, route_conv(c->plan, false, 0, q), padded, B, nullptr, 1, SC, st));
         HIPE(hpe_launch_maxpool(SC, cur, B, 112, 64, st));
     }
     bool have_2a = false;  // the previous block's chained launch has already written this block's branch2a output to T1
     for (const ResBlock& blk : blocks()) {
         const bool first = blk.first;
         const int i2a = blk.i2a, i2b = blk.i2b, i2c = blk.i2c, i1 = blk.i1;
-        const bool fz = use_wino_fused(c, i2b, B) || use_wino4_fused(c, i2b, B);  // then T1 is channel-slab major and never leaves this pair of launches
+        const BlockRoute br = route_block(c->plan, c->bf16, blk, q);  // (r2a.out_slab8: T1 is channel-slab major between branch2a and branch2b)
         if (have_2a) {
             if (c->timing >= 2) {
                 HIPE(hipEventRecord(c->cev0[i2a], st));
                 HIPE(hipEventRecord(c->cev1[i2a], st));
             }
         } else {
-            HIPE(timed_conv(c, i2a, cur, B, nullptr, 1, T1, st, nullptr, 0, cf | (fz ? CONV_OUT_SLAB8 : 0)));
+            HIPE(timed_conv(c, i2a, br.r2a, cur, B, nullptr, 1, T1, st));
         }
         have_2a = false;
-        HIPE(timed_conv(c, i2b, T1, B, nullptr, 1, T2, st, wv, slot, cf | (fz ? CONV_IN_SLAB8 : 0)));
+        HIPE(timed_conv(c, i2b, br.r2b, T1, B, nullptr, 1, T2, st, wv, slot));
         const float* res = cur;
-        if (use_chain(c, blk)) {
+        if (br.join == JOIN_CHAIN) {
             // identity block followed by an identity block (bf16): relu(bn(W2c t2) + x) and the next block's relu(bn(W2a' .)) in one
             // launch; the 4C-wide sum is written once and not read back (timed as layer i2c; the next branch2a then shows 0)
             const bool t2 = c->timing >= 2;
             if (t2) HIPE(hipEventRecord(c->cev0[i2c], st));
-            // (fp32: the next block's 3x3 layer may be the fused Winograd kernel, which reads its input channel-slab major)
-            const int i2b_next = i2c + (first ? 3 : 2);
-            const bool slab8_next = !c->bf16 && (use_wino_fused(c, i2b_next, B) || use_wino4_fused(c, i2b_next, B));
-            HIPE(run_chain(c, i2c, first, T2, cur, B, nxt, T1, st, slab8_next));
+            HIPE(run_chain(c, i2c, first, T2, cur, B, nxt, T1, st, br.u1_slab8));
             if (t2) {
                 HIPE(hipEventRecord(c->cev1[i2c], st));
                 if (first) {  // the projection shortcut is inside the launch
@@ -320,11 +255,11 @@ static hipError_t encoder_chunk(hpe_ctx* c, const float* images, int i0, int B, 
                 }
             }
             have_2a = true;
-        } else if (first && c->conv[i2c].w_dual) {
+        } else if (br.join == JOIN_DUAL) {
             // conv_block: expand convolution + projection shortcut + add + ReLU as one dual-source GEMM (timed as layer i2c)
             const bool t2 = c->timing >= 2;
             if (t2) HIPE(hipEventRecord(c->cev0[i2c], st));
-            HIPE(run_dual(c, i2c, i1, T2, cur, B, nxt, st, cf));
+            HIPE(run_dual(c, i2c, i1, br.r2c, T2, cur, B, nxt, st));
             if (t2) {
                 HIPE(hipEventRecord(c->cev1[i2c], st));
                 HIPE(hipEventRecord(c->cev0[i1], st));
@@ -333,10 +268,10 @@ static hipError_t encoder_chunk(hpe_ctx* c, const float* images, int i0, int B, 
         } else {
             if (first) {
                 // projection shortcut (conv_block), no ReLU before the add
-                HIPE(timed_conv(c, i1, cur, B, nullptr, 0, SC, st, nullptr, 0, cf));
+                HIPE(timed_conv(c, i1, br.r1, cur, B, nullptr, 0, SC, st));
                 res = SC;
             }
-            HIPE(timed_conv(c, i2c, T2, B, res, 1, nxt, st, nullptr, 0, cf));
+            HIPE(timed_conv(c, i2c, br.r2c, T2, B, res, 1, nxt, st));
         }
         float* t = cur;
         cur = nxt;

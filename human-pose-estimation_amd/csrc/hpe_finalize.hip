@@ -210,15 +210,14 @@ static int check_loaded(hpe_ctx* c) {
 //      out = relu([s2c W2c | s1 W1] . [t2 ; x] + (shift2c + shift1))   -- no shortcut tensor in HBM, one launch instead of two
 static int pack_dual_weights(hpe_ctx* c) {
     int rc;
-    const int slab = c->bf16 ? 64 : 32;
     for (const ResBlock& blk : blocks()) {
-        if (!blk.first) continue;
+        const unsigned packs = layer_packs(c->plan, c->bf16, blk.i2c);
+        if (!(packs & PACK_W_DUAL)) continue;
         const ConvSpec& s2 = specs()[blk.i2c];
         const ConvSpec& s1 = specs()[blk.i1];
         ConvLayer& L2 = c->conv[blk.i2c];
         const ConvLayer& L1 = c->conv[blk.i1];
         const int K1 = s2.cin, K2 = s1.cin, N = s2.cout;
-        if (K1 % slab != 0 || K2 % slab != 0) continue;
         const int n_pad = round_up(N, 128), K = K1 + K2;
         std::vector<float> wt((size_t)n_pad * K, 0.f), sh(N);
         for (int n = 0; n < N; ++n) {
@@ -233,8 +232,7 @@ static int pack_dual_weights(hpe_ctx* c) {
             if ((rc = upload_bf16(c, &L2.w_dual, to_bf16(wt)))) return rc;
         } else {
             if ((rc = upload_to(c, &L2.w_dual, wt))) return rc;
-            // f32_split: the folded weight is split (the BN scales are inside the pieces)
-            if ((c->plan.f32_split & stage_bit(s2.hout)) && (rc = upload_split(c, &L2.w_dual_split, wt, n_pad, K))) return rc;
+            if ((packs & PACK_W_DUAL_SPLIT) && (rc = upload_split(c, &L2.w_dual_split, wt, n_pad, K))) return rc;
         }
         if ((rc = upload_to(c, &L2.shift_dual, sh))) return rc;
         L2.k_dual = K;
@@ -303,16 +301,15 @@ static int pack_stem_weights(hpe_ctx* c, ConvLayer& L) {
     return rc;
 }
 
-// ---- encoder weights: HWIO -> Wt[n][k] (k = (kh,kw,cin), cin fastest), zero padded; BN -> scale/shift
+// ---- encoder weights: HWIO -> Wt[n][k] (k = (kh,kw,cin), cin fastest), zero padded; BN -> scale/shift; and the packings layer_packs names
 static int pack_conv_weights(hpe_ctx* c) {
     int rc;
-    // k-slab of the GEMM kernels: 32 floats or 64 bf16; the bf16 stem slab s holds kernel rows (2s, 2s + 1), each 8 px x 4 ch
-    const int slab = c->bf16 ? 64 : 32;
     for (int i = 0; i < HPE_NUM_CONV; ++i) {
         const ConvSpec& s = specs()[i];
         ConvLayer& L = c->conv[i];
+        const unsigned packs = layer_packs(c->plan, c->bf16, i);
         L.n_pad = round_up(s.cout, 128);
-        L.k_pad = (i == 0) ? round_up(7 * 32, slab) : round_up(s.kh * s.kw * s.cin, slab);
+        L.k_pad = conv_k_pad(i, c->bf16);
         std::vector<float> wt((size_t)L.n_pad * L.k_pad, 0.f);
         for (int kh = 0; kh < s.kh; ++kh)
             for (int kw = 0; kw < s.kw; ++kw)
@@ -325,15 +322,11 @@ static int pack_conv_weights(hpe_ctx* c) {
             if ((rc = upload_bf16(c, &L.w, to_bf16(wt)))) return rc;
         } else {
             if ((rc = upload_to(c, &L.w, wt))) return rc;
-            if (i != 0 && s.kh == 1 && (c->plan.f32_split & stage_bit(s.hout)) && (rc = upload_split(c, &L.w_split, wt, L.n_pad, L.k_pad))) return rc;
-            if (c->plan.wino_min_c > 0 && s.kh == 3 && s.stride == 1 && s.cin % 32 == 0 && s.cout % 64 == 0 &&
-                (s.cin >= c->plan.wino_min_c || (c->plan.wino_fused && s.hin >= c->plan.wino_fused_min_hw)) && (rc = pack_wino_weights(c, s, L)))
-                return rc;
-            if (s.kh == 3 && s.stride == 1 && s.cin % 32 == 0 && s.cout % 64 == 0 && ((c->plan.wino_f4 | c->plan.wino4_fused) & f4_bit(s.hin)) &&
-                (rc = pack_wino4_weights(c, s, L)))
-                return rc;
+            if ((packs & PACK_W_SPLIT) && (rc = upload_split(c, &L.w_split, wt, L.n_pad, L.k_pad))) return rc;
+            if ((packs & PACK_WINO_U) && (rc = pack_wino_weights(c, s, L))) return rc;
+            if ((packs & PACK_WINO4_U) && (rc = pack_wino4_weights(c, s, L))) return rc;
         }
-        if (i == 0 && (rc = pack_stem_weights(c, L))) return rc;
+        if ((packs & PACK_STEM_W) && (rc = pack_stem_weights(c, L))) return rc;
         std::vector<float> sc(s.cout), sh(s.cout);
         for (int n = 0; n < s.cout; ++n) {
             double scale, shift;
@@ -553,7 +546,7 @@ static int create_streams_and_events(hpe_ctx* c) {
 
 int repack_encoder(hpe_ctx* c) {
     int rc;
-    if (c->plan.dual_gemm && (rc = pack_dual_weights(c))) return rc;
+    if ((rc = pack_dual_weights(c))) return rc;
     return pack_conv_weights(c);
 }
 
@@ -568,7 +561,7 @@ int finalize_impl(hpe_ctx* c) {
     HIP_TRY(hpe_stem_fused_init_device());
     HIP_TRY(hpe_losses_init_device());
     c->loss_attr_done = true;
-    if (c->have_encoder && c->plan.dual_gemm && (rc = pack_dual_weights(c))) return rc;
+    if (c->have_encoder && (rc = pack_dual_weights(c))) return rc;
     if (c->have_encoder && (rc = pack_conv_weights(c))) return rc;
     // constants every part uses: the zero page is the LDS-DMA source of out-of-image taps / halo pixels
     if ((rc = upload(c, &c->ones, std::vector<float>(2048, 1.f)))) return rc;

@@ -1,6 +1,8 @@
 // hpe_plan.h -- the launch plan of one context: every option that decides which kernel runs and how it is launched, resolved ONCE
-// (hpe_finalize, or the first loss call of a loss-only context) by hpe_resolve_plan() from the table in hpe_plan.hip.  That file is the only
-// one of the library that reads the environment; the launchers are pure functions of their arguments.
+// (hpe_finalize, or the first loss call of a loss-only context) by hpe_resolve_plan() from the table in hpe_plan.hip, and the dispatch over
+// it: layer_packs() says which packings a layer holds, route_conv() / route_block() which kernel, tile and layouts a launch takes.  All of
+// it is pure host logic of (plan, dtype, layer, query): no pointer, no HIP call.  hpe_plan.hip is the only file of the library that reads the
+// environment; the launchers are pure functions of their arguments.
 #pragma once
 #include "../../include/hpe.h"
 #include "hpe_internal.h"
@@ -57,14 +59,30 @@ inline int stage_bit(int hout) { return hout >= 56 ? 1 : (hout >= 28 ? 2 : (hout
 // bit of a 3x3 layer's map size in wino_f4 / wino4_fused / halo3
 inline int f4_bit(int hin) { return hin <= 7 ? 1 : (hin <= 14 ? 2 : (hin <= 28 ? 4 : 8)); }
 
-int pick_f32s(const HpePlan& pl, const void* w_split, int M, int N, int K, bool residual_expand);
-int pick_tile(const HpePlan& pl, int M, int N, int K, bool residual_expand = false, bool concurrent = false);
-int pick_bf16(const HpePlan& pl, int M, int N, int K, bool residual_expand, bool concurrent = false, int mode = GEMM_DENSE);
+// ---- the dispatch ("The conv dispatch").  Packings of a layer: bit 1 << HPE_PACK_* of include/hpe.h
+constexpr unsigned PACK_W_SPLIT = 1u << HPE_PACK_W_SPLIT, PACK_WINO_U = 1u << HPE_PACK_WINO_U, PACK_WINO4_U = 1u << HPE_PACK_WINO4_U,
+                   PACK_STEM_W = 1u << HPE_PACK_STEM_W, PACK_W_DUAL = 1u << HPE_PACK_W_DUAL, PACK_W_DUAL_SPLIT = 1u << HPE_PACK_W_DUAL_SPLIT;
+// which of them hpe_finalize packs for layer idx: the rule, not its side effect
+unsigned layer_packs(const HpePlan& pl, bool bf16, int idx);
 
-// which kernel a layer of a finalized context takes (the plan and the weights that were packed for it)
-struct hpe_ctx;
+// one launcher each; the first four are GemmKernel's (gemm_contract.h)
+enum ConvKernel { CONV_K_F32 = 0, CONV_K_F32S, CONV_K_BF16, CONV_K_BF16_P8, CONV_K_HALO3, CONV_K_WINO, CONV_K_WINO_FUSED, CONV_K_WINO4, CONV_K_WINO4_FUSED };
+// what a launch is asked with: images, a batch chunk running beside others, a residual operand, a slice of the Winograd V workspace
+struct ConvQuery { int B; bool concurrent, residual, workspace; };
+struct ConvRoute {
+    int kernel, mode, tile;  // ConvKernel, GemmMode, GemmTile (-1: the kernel has none)
+    bool in_slab8;           // the kernel reads its input channel-slab major (the fused Winograd kernels)
+    bool out_slab8;          // ... and so must its producer write it (route_block sets it on branch2a)
+    bool concurrent;         // of the query: such a launch never takes the context's one split-K workspace
+};
+enum BlockJoin { JOIN_SEPARATE = 0, JOIN_DUAL, JOIN_CHAIN };  // branch2c (+ branch1) as launches of their own / the dual-source GEMM / chained with the next branch2a
+struct BlockRoute {
+    ConvRoute r2a, r2b, r2c, r1;  // r2c: the dual-source launch when join == JOIN_DUAL; r1 only when a conv_block joins separately
+    int join;
+    bool u1_slab8;  // JOIN_CHAIN: the next block's branch2a output is written channel-slab major
+};
 struct ResBlock;
-bool use_wino4(const hpe_ctx* c, int idx, int B);
-bool use_wino4_fused(const hpe_ctx* c, int idx, int B);
-bool use_wino_fused(const hpe_ctx* c, int idx, int B);
-bool use_chain(const hpe_ctx* c, const ResBlock& blk);
+ConvRoute route_conv(const HpePlan& pl, bool bf16, int idx, const ConvQuery& q);
+BlockRoute route_block(const HpePlan& pl, bool bf16, const ResBlock& blk, ConvQuery q);  // q.residual is ignored: the block says which layer has one
+// fp32 tile of a launch outside the table (the data-gradient GEMMs of encoder_train.hip)
+int pick_tile(const HpePlan& pl, int M, int N, int K, bool residual_expand = false, bool concurrent = false);

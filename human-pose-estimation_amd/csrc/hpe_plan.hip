@@ -1,5 +1,6 @@
 // hpe_plan.hip -- the layer table, the option table and its resolver (the one place of the library that reads the environment), and the
-// rules that choose a tile / kernel per launch.  Host logic only.
+// dispatch: which packings a layer holds (layer_packs) and which kernel, tile and layouts a launch takes (route_conv, route_block).  Host
+// logic only: no pointer, no HIP call.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -153,12 +154,12 @@ HpePlan hpe_resolve_plan(const HpeConfig& cfg) {
     return pl;
 }
 
-// tile of conv_gemm_f32s.hip for this launch, -1 = the launch keeps the fp32 kernel.  Split weights exist (fp32 encoder, stage in f32_split),
+// tile of conv_gemm_f32s.hip for this launch, -1 = the launch keeps the fp32 kernel.  Split weights are packed (fp32 encoder, stage in f32_split),
 // N > 64, the grid is whole tiles of a useful size.  Measured at B = 256 (profiles/r05): the 4-wave 128 x 128 tile (each A element
 // split by one wave) everywhere but on the identity-block expand layers, which are mostly epilogue: there 8 waves (128 x 128, 4 x 2), and on
 // stage 3 (K = 128) the fp32 kernel's 128 x 64 8-wave tile stays ahead.
-int pick_f32s(const HpePlan& pl, const void* w_split, int M, int N, int K, bool residual_expand) {
-    if (!w_split || N <= 64) return -1;
+static int pick_f32s(const HpePlan& pl, bool split_packed, int M, int N, int K, bool residual_expand) {
+    if (!split_packed || N <= 64) return -1;
     if (residual_expand && K < PLAN_F32S_EXPAND_MIN_K) return -1;
     const int tile = residual_expand ? PLAN_F32S_EXPAND_TILE : PLAN_F32S_TILE;
     const TileShape ts = tile_shape(GEMM_K_F32S, tile);
@@ -195,7 +196,7 @@ int pick_tile(const HpePlan& pl, int M, int N, int K, bool residual_expand, bool
 //  * everything with a long k axis on the small maps (stage 5: M = 49 B): 256x128, 8 waves (res5*_branch2b 0.112 -> 0.083 ms)
 //  * otherwise 128x128 while that still gives >= 512 workgroups, else 64x128
 // (the LDS ring is two slabs deep everywhere: a 3-deep ring lost on every layer it was measured on)
-int pick_bf16(const HpePlan& pl, int M, int N, int K, bool residual_expand, bool concurrent, int mode) {
+static int pick_bf16(const HpePlan& pl, int M, int N, int K, bool residual_expand, bool concurrent, int mode) {
     // 256 x 256 phase-interleaved kernel (conv_gemm_bf16_p8.hip), per layer kind -- bits of bf16_p8:
     //   1: 3x3 layers with N == 256 (stage 4), 2: 3x3 layers with N >= 512 (stage 5), 4: 1x1 / strided layers,
     //   8: dual-source launches with N >= 2048 (res5a), 16: the other dual-source launches
@@ -216,52 +217,116 @@ int pick_bf16(const HpePlan& pl, int M, int N, int K, bool residual_expand, bool
     return tile;
 }
 
-// the 3x3 layer idx runs as Winograd F(4x4,3x3) for this batch (blocked V through the workspace)
-bool use_wino4(const hpe_ctx* c, int idx, int B) {
+// ---- the dispatch.  layer_packs() is the rule hpe_finalize packs by and the routes ask; the order of the tests in route_conv() is the
+// precedence of the kernels.
+unsigned layer_packs(const HpePlan& pl, bool bf16, int idx) {
     const ConvSpec& s = specs()[idx];
-    return !c->bf16 && c->conv[idx].wino4_u && s.kh == 3 && s.stride == 1 && (c->plan.wino_f4 & f4_bit(s.hin)) &&
-           hpe_wino4_items(B, s.hin, s.hin, s.cout) >= (c->plan.wino_min_items < c->plan.wino4_min_items ? c->plan.wino_min_items : c->plan.wino4_min_items);
+    // fused stem: the conv1 weights in the k enumeration of stem_fused.hip
+    unsigned m = idx == 0 ? PACK_STEM_W : 0;
+    // conv_block: branch2c + branch1 as one GEMM over the concatenated k axis, both k axes whole slabs (32 floats / 64 bf16)
+    const int slab = bf16 ? 64 : 32;
+    const ResBlock* blk = nullptr;
+    for (const ResBlock& b : blocks())
+        if (b.first && b.i2c == idx) blk = &b;
+    if (pl.dual_gemm && blk && s.cin % slab == 0 && specs()[blk->i1].cin % slab == 0) {
+        m |= PACK_W_DUAL;
+        // f32_split: the folded weight is split (the BN scales are inside the pieces)
+        if (!bf16 && (pl.f32_split & stage_bit(s.hout))) m |= PACK_W_DUAL_SPLIT;
+    }
+    if (bf16) return m;
+    if (idx != 0 && s.kh == 1 && (pl.f32_split & stage_bit(s.hout))) m |= PACK_W_SPLIT;
+    const bool wino = s.kh == 3 && s.stride == 1 && s.cin % 32 == 0 && s.cout % 64 == 0;
+    if (wino && pl.wino_min_c > 0 && (s.cin >= pl.wino_min_c || (pl.wino_fused && s.hin >= pl.wino_fused_min_hw))) m |= PACK_WINO_U;
+    if (wino && ((pl.wino_f4 | pl.wino4_fused) & f4_bit(s.hin))) m |= PACK_WINO4_U;
+    return m;
 }
 
-// ... with the input transform inside the GEMM kernel (its 1x1 producer then writes channel-slab major); takes precedence over use_wino4
-bool use_wino4_fused(const hpe_ctx* c, int idx, int B) {
-    const ConvSpec& s = specs()[idx];
-    return !c->bf16 && c->conv[idx].wino4_u && s.kh == 3 && s.stride == 1 && (c->plan.wino4_fused & f4_bit(s.hin)) &&
-           hpe_wino4_fused_items(B, s.hin, s.hin, s.cout) >= (c->plan.wino_min_items < c->plan.wino4_min_items ? c->plan.wino_min_items : c->plan.wino4_min_items);
+// steps 6-8 of route_conv, and the dual-source launch: the implicit-GEMM kernel and tile of an M x N x K launch
+static ConvRoute route_gemm(const HpePlan& pl, bool bf16, int mode, int M, int N, int K, bool expand, bool split_packed, bool concurrent) {
+    ConvRoute r{CONV_K_F32, mode, -1, false, false, concurrent};
+    if (bf16) {  // 6. bf16 / bf16_p8
+        r.tile = pick_bf16(pl, M, N, K, expand, concurrent, mode);
+        r.kernel = r.tile == TILE_P8_256x256 ? CONV_K_BF16_P8 : CONV_K_BF16;
+    } else if ((r.tile = pick_f32s(pl, split_packed, M, N, K, expand)) >= 0) {  // 7. f32s
+        r.kernel = CONV_K_F32S;
+    } else {  // 8. fp32
+        r.tile = pick_tile(pl, M, N, K, expand, concurrent);
+    }
+    return r;
 }
 
-// the 3x3 layer idx runs as the fused F(2x2) Winograd kernel for this batch (its 1x1 producer then writes channel-slab major)
-bool use_wino_fused(const hpe_ctx* c, int idx, int B) {
+ConvRoute route_conv(const HpePlan& pl, bool bf16, int idx, const ConvQuery& q) {
     const ConvSpec& s = specs()[idx];
-    if (use_wino4_fused(c, idx, B) || use_wino4(c, idx, B)) return false;
-    return c->plan.wino_fused && !c->bf16 && c->conv[idx].wino_u && s.kh == 3 && s.stride == 1 && s.hin >= c->plan.wino_fused_min_hw &&
-           hpe_wino_fused_items(B, s.hin, s.hin, s.cout) >= c->plan.wino_min_items;
+    const unsigned packs = layer_packs(pl, bf16, idx);
+    const int B = q.B, H = s.hin;
+    const int mode = idx == 0 ? GEMM_STEM : s.kh == 3 ? GEMM_CONV3 : s.stride == 1 ? GEMM_DENSE : GEMM_STRIDED;
+    // every kernel but the implicit GEMMs is a plain 3x3 / stride 1 convolution: no residual operand
+    const bool plain3 = mode == GEMM_CONV3 && s.stride == 1 && !q.residual;
+    auto special = [&](int kernel) { return ConvRoute{kernel, mode, -1, kernel == CONV_K_WINO_FUSED || kernel == CONV_K_WINO4_FUSED, false, q.concurrent}; };
+    const int min4 = pl.wino_min_items < pl.wino4_min_items ? pl.wino_min_items : pl.wino4_min_items;
+    // 1. F(4x4) with the input transform inside the GEMM kernel (its 1x1 producer then writes channel-slab major); before F(4x4)
+    if (plain3 && (packs & PACK_WINO4_U) && (pl.wino4_fused & f4_bit(H)) && hpe_wino4_fused_items(B, H, H, s.cout) >= min4) return special(CONV_K_WINO4_FUSED);
+    // the layer runs as F(4x4,3x3) for this batch (blocked V through the workspace) -- where it would, F(2x2) fused stands back even in a
+    // chunk that has no workspace slice
+    const bool f4 = plain3 && (packs & PACK_WINO4_U) && (pl.wino_f4 & f4_bit(H)) && hpe_wino4_items(B, H, H, s.cout) >= min4;
+    // 2. the fused F(2x2) kernel (its 1x1 producer then writes channel-slab major)
+    if (plain3 && !f4 && pl.wino_fused && (packs & PACK_WINO_U) && H >= pl.wino_fused_min_hw && hpe_wino_fused_items(B, H, H, s.cout) >= pl.wino_min_items)
+        return special(CONV_K_WINO_FUSED);
+    // 3. F(4x4)
+    if (f4 && q.workspace) return special(CONV_K_WINO4);
+    // 4. F(2x2).  Winograd needs enough (64-tile x 64-cout) work items to occupy the 256 CUs (one 8-wave workgroup each); below that
+    // the direct kernel with split-K is faster (measured crossover: batch ~32, profiles/r01/g_wino_small_batch.txt)
+    if (plain3 && (packs & PACK_WINO_U) && q.workspace && s.cin >= pl.wino_min_c &&
+        (long)((B * ((H + 1) / 2) * ((H + 1) / 2) + 63) / 64) * (s.cout / 64) >= pl.wino_min_items)
+        return special(CONV_K_WINO);
+    // 5. halo3 (bf16): before bf16_p8, whose bits 1-2 name the same 3x3 layers -- clear halo3 to reach them
+    if (bf16 && plain3 && (pl.halo3 & f4_bit(H)) && hpe_halo3_bf16_supported(H, s.cin, s.cout)) return special(CONV_K_HALO3);
+    // 6.-8. the implicit GEMMs; expand: an identity block's C -> 4C layer with its residual
+    return route_gemm(pl, bf16, mode, B * s.hout * s.hout, s.cout, conv_k_pad(idx, bf16), mode == GEMM_DENSE && q.residual && s.cout == 4 * s.cin,
+                      (packs & PACK_W_SPLIT) != 0, q.concurrent);
 }
 
-// the bf16 identity-block pair branch2c (idx i2c, + residual + ReLU) -> next block's branch2a (idx i2c + 1) as one launch
-// blk.first: the conv_block form -- branch2c + the projection shortcut branch1 (idx i2c + 1, stride 1: stage 2 only) as the dual-source GEMM,
-// chained with the next block's branch2a (idx i2c + 2); bit 2 of chain_fuse.  The last block of a stage has no partner.
-bool use_chain(const hpe_ctx* c, const ResBlock& blk) {
+// the pair branch2c (+ residual + ReLU) -> next block's branch2a as one launch.  The last block of a stage has no partner.
+static bool use_chain(const HpePlan& pl, bool bf16, const ResBlock& blk) {
     if (blk.last) return false;
     const int stg = blk.stage, i2c = blk.i2c;
-    const bool first = blk.first;
     const ConvSpec& s2 = specs()[i2c];
-    if (!c->bf16) {
-        // fp32: identity blocks of stage 2 only (conv_chain_f32.hip; bit 3 of chain_fuse, on by default: A/B on two boxes +0.3 ... +1.4 % at
-        // B = 256, +1.6 % at B = 64)
-        if (first || stg != 0 || !(c->plan.chain_fuse & 8)) return false;
-        const ConvSpec& sn = specs()[i2c + 1];
-        return sn.kh == 1 && sn.stride == 1 && sn.cin == s2.cout && hpe_chain_f32_supported(s2.cin, s2.cout, sn.cout);
-    }
-    if (first) {
-        const ConvSpec& s1 = specs()[i2c + 1];
-        const ConvSpec& sn = specs()[i2c + 2];
-        return stg == 0 && (c->plan.chain_fuse & 4) && c->conv[i2c].w_dual && s1.stride == 1 && s1.hin == s2.hin && sn.kh == 1 && sn.stride == 1 &&
-               sn.cin == s2.cout && c->conv[i2c].k_dual == s2.cin + s1.cin && hpe_chain_bf16_supported(s2.cin, s2.cout, sn.cout, s1.cin);
+    const ConvSpec& sn = specs()[i2c + (blk.first ? 2 : 1)];  // the next block's branch2a
+    if (sn.kh != 1 || sn.stride != 1 || sn.cin != s2.cout) return false;
+    // fp32: identity blocks of stage 2 only (conv_chain_f32.hip; bit 3 of chain_fuse, on by default: A/B on two boxes +0.3 ... +1.4 % at
+    // B = 256, +1.6 % at B = 64)
+    if (!bf16) return !blk.first && stg == 0 && (pl.chain_fuse & 8) && hpe_chain_f32_supported(s2.cin, s2.cout, sn.cout);
+    // blk.first: the conv_block form -- branch2c + the projection shortcut branch1 (stride 1: stage 2 only) as the dual-source GEMM, chained
+    // with the next block's branch2a; bit 2 of chain_fuse
+    if (blk.first) {
+        const ConvSpec& s1 = specs()[blk.i1];
+        return stg == 0 && (pl.chain_fuse & 4) && (layer_packs(pl, bf16, i2c) & PACK_W_DUAL) && s1.stride == 1 && s1.hin == s2.hin &&
+               hpe_chain_bf16_supported(s2.cin, s2.cout, sn.cout, s1.cin);
     }
     // identity blocks: bit 0 = stage 2, bit 1 = stage 3, bit 4 (value 16) = stage 4 (128-pixel workgroups, one per CU)
     const int bit = stg == 0 ? 1 : stg == 1 ? 2 : stg == 2 ? 16 : 0;
-    if (!(c->plan.chain_fuse & bit)) return false;
-    const ConvSpec& sn = specs()[i2c + 1];
-    return sn.kh == 1 && sn.stride == 1 && sn.cin == s2.cout && hpe_chain_bf16_supported(s2.cin, s2.cout, sn.cout, 0);
+    return (pl.chain_fuse & bit) && hpe_chain_bf16_supported(s2.cin, s2.cout, sn.cout, 0);
+}
+
+BlockRoute route_block(const HpePlan& pl, bool bf16, const ResBlock& blk, ConvQuery q) {
+    BlockRoute b{};
+    q.residual = false;
+    b.r2a = route_conv(pl, bf16, blk.i2a, q);
+    b.r2b = route_conv(pl, bf16, blk.i2b, q);
+    b.r2a.out_slab8 = b.r2b.in_slab8;  // then branch2a's output never leaves this pair of launches
+    const ConvSpec& s2 = specs()[blk.i2c];
+    if (use_chain(pl, bf16, blk)) {
+        b.join = JOIN_CHAIN;
+        // (fp32: the next block's 3x3 layer may be a fused Winograd kernel, which reads its input channel-slab major)
+        b.u1_slab8 = route_conv(pl, bf16, blk.i2c + (blk.first ? 3 : 2), q).in_slab8;
+    } else if (blk.first && (layer_packs(pl, bf16, blk.i2c) & PACK_W_DUAL)) {
+        b.join = JOIN_DUAL;
+        b.r2c = route_gemm(pl, bf16, GEMM_DUAL, q.B * s2.hout * s2.hout, s2.cout, s2.cin + specs()[blk.i1].cin, false,
+                           (layer_packs(pl, bf16, blk.i2c) & PACK_W_DUAL_SPLIT) != 0, q.concurrent);
+    } else {
+        if (blk.first) b.r1 = route_conv(pl, bf16, blk.i1, q);
+        q.residual = true;
+        b.r2c = route_conv(pl, bf16, blk.i2c, q);
+    }
+    return b;
 }

@@ -62,6 +62,7 @@ class HpeEngine(object):
                 v = {"grid": 0, "valu": 1, "mfma": 2}[v]
             setattr(cfg, k, int(v))
         self.plan_options = dict(plan_options)
+        self._cfg = cfg
         h = C.c_void_p()
         _lib.check(self.lib.hpe_create(C.byref(cfg), C.byref(h)))
         self._h = h
@@ -815,6 +816,10 @@ class HpeEngine(object):
             r = _require_cuda_tensor(residual, "residual").data_ptr()
         _lib.check(self.lib.hpe_debug_conv(self._h, idx, x.data_ptr(), B, r, int(relu), y.data_ptr(), self._stream()))
         return y
+
+    def conv_route(self, idx, B, concurrent=False, residual=False, workspace=True):
+        """hpe_debug_conv_route with this engine's own config: which kernel layer idx takes at batch B (_lib.HpeConvRoute)"""
+        return _lib.conv_route(self.lib, self._cfg, idx, B, concurrent, residual, workspace)
 
     def debug_gemm_ex(self, mode, tile, x, wt, y, M, N, K, **kw):
         """hpe_debug_gemm_ex: the fp32 implicit-GEMM kernel with every launch argument given (HpeDebugGemm of include/hpe.h).  x, wt, y

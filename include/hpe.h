@@ -601,6 +601,40 @@ int hpe_debug_gemm_ex(hpe_ctx* ctx, const HpeDebugGemm* g, void* stream);
  * never dereferenced; scale, shift and the library's zero page count as present; use_splitk is ignored.  HPE_OK if the launch is
  * inside the contract, else HPE_ERR_INVALID with the name of the first broken clause in hpe_last_error(). */
 int hpe_debug_gemm_check(const HpeDebugGemm* g, int kernel, int w_piece);
+/* Which kernel conv layer idx takes, asked of the plan alone: cfg is resolved as hpe_create / hpe_finalize resolve it (fields >= 0, else the
+ * environment, else the defaults of cfg->encoder_dtype), then the library's one routing function is asked.  No context, no GPU, no HIP
+ * call.  B images; concurrent: the launch is a batch chunk running beside others (no split-K, the concurrent tile rules); residual: the
+ * launch has a residual operand; workspace: it has a slice of the Winograd V workspace (false for a chunk that starts past image 0 with
+ * fewer than 32 images).  out->kernel / mode / tile / in_slab8 are what hpe_debug_conv launches under that query (in_slab8: the kernel
+ * reads channel-slab major input, hpe_debug_conv converts); out_slab8: idx is a branch2a whose block's 3x3 layer makes it write
+ * channel-slab major in the network.  For a branch2c, join says how its block ends in the network: 0 = launches of their own (branch1 of
+ * a conv_block first, then the layer as out->kernel says when asked with residual = 1), 1 = the dual-source GEMM, whose kernel and tile are
+ * join_kernel / join_tile, 2 = chained with the next block's branch2a (hpe_debug_chain), whose output is channel-slab major if
+ * next_slab8.  packs: bit (1 << HPE_PACK_*) for each of W_SPLIT, WINO_U, WINO4_U, STEM_W, W_DUAL, W_DUAL_SPLIT that hpe_finalize packs for
+ * the layer.  HPE_ERR_INVALID on a wrong struct_size (of cfg or out), idx outside [0, HPE_NUM_CONV) or B < 1. */
+enum {
+    HPE_CONV_K_F32 = 0,      /* conv_gemm.hip */
+    HPE_CONV_K_F32S,         /* conv_gemm_f32s.hip (f32_split) */
+    HPE_CONV_K_BF16,         /* conv_gemm_bf16.hip */
+    HPE_CONV_K_BF16_P8,      /* conv_gemm_bf16_p8.hip (bf16_p8) */
+    HPE_CONV_K_HALO3,        /* conv3_halo_bf16.hip */
+    HPE_CONV_K_WINO,         /* F(2x2,3x3) through the V workspace */
+    HPE_CONV_K_WINO_FUSED,   /* F(2x2,3x3), input transform inside the GEMM */
+    HPE_CONV_K_WINO4,        /* F(4x4,3x3) through the V workspace */
+    HPE_CONV_K_WINO4_FUSED,  /* F(4x4,3x3), input transform inside the GEMM (wino4_fused) */
+    HPE_CONV_K_COUNT
+};
+typedef struct HpeConvRoute {
+    int struct_size; /* sizeof(HpeConvRoute), written by the caller and checked by the call */
+    int kernel;      /* HPE_CONV_K_* */
+    int mode;        /* HPE_GEMM_*; 3 = conv1 as the im2col stem GEMM */
+    int tile;        /* as HpeDebugGemm.tile, 7 = 256x256 (bf16_p8); -1: the kernel has no tile table */
+    int in_slab8, out_slab8;
+    int join, join_kernel, join_tile, next_slab8; /* branch2c only; else 0, -1, -1, 0 */
+    unsigned packs;
+    int reserved; /* 0 */
+} HpeConvRoute;
+int hpe_debug_conv_route(const HpeConfig* cfg, int idx, int B, int concurrent, int residual, int workspace, HpeConvRoute* out);
 /* The dense mode of hpe_debug_gemm_ex with scale = ones, shift = zeros, lda = ldw = K, ldy = ldres = N and no split-K
  * workspace: y[M,N] = act(x[M,K] . wt[n][k]^T (+ residual)); K % 32 == 0; N <= 1024; tile 0..6 as above.  Needs the regressor loaded. */
 int hpe_debug_gemm(hpe_ctx* ctx, const float* x_dev, const float* wt_dev, int M, int N, int K, int w_rows, int tile,

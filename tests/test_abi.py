@@ -76,6 +76,33 @@ def test_debug_gemm_struct_matches_header(lib):
     assert lib.hpe_debug_gemm_ex(None, C.byref(g), None) == 3 and sk.value == 0  # HPE_ERR_STATE: no context; the output is still defined
 
 
+def test_conv_route_struct_matches_header(lib):
+    """HpeConvRoute (hpe_debug_conv_route): the ctypes mirror has the header's fields in the header's order, all 4-byte scalars; the kernel
+    and pack numbering of the binding is the header's; the call checks struct_size first and needs neither a context nor a GPU."""
+    import ctypes as C
+
+    txt = open(os.path.join(ROOT, "include", "hpe.h")).read()
+    body = txt[txt.index("typedef struct HpeConvRoute {") + len("typedef struct HpeConvRoute {"):txt.index("} HpeConvRoute;")]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = []
+    for decl in body.split(";"):
+        m = re.match(r"\s*(unsigned|int)\s+(.+)$", decl.strip(), flags=re.S)
+        if m:
+            fields += [(n.strip(), m.group(1)) for n in m.group(2).split(",")]
+    assert [n for n, _ in fields] == [f[0] for f in _lib.HpeConvRoute._fields_]
+    assert all((py is C.c_uint) == (t == "unsigned") for (_, t), (_, py) in zip(fields, _lib.HpeConvRoute._fields_))
+    assert fields[0][0] == "struct_size" and C.sizeof(_lib.HpeConvRoute) == 4 * len(fields)
+    enum = re.findall(r"\bHPE_CONV_K_([A-Z0-9_]+)\b", txt[txt.index("enum {\n    HPE_CONV_K_F32"):txt.index("typedef struct HpeConvRoute")])
+    assert tuple(e.lower() for e in enum) == _lib.CONV_KERNELS + ("count",)
+    assert "hpe_debug_conv_route" in _lib.declared_symbols() and hasattr(lib, "hpe_debug_conv_route")
+    cfg = _lib.HpeConfig()
+    lib.hpe_config_init(C.byref(cfg))
+    r = _lib.HpeConvRoute()  # struct_size 0
+    assert lib.hpe_debug_conv_route(C.byref(cfg), 1, 8, 0, 0, 1, C.byref(r)) == 1 and b"struct_size" in lib.hpe_last_error()
+    r = _lib.conv_route(lib, cfg, 0, 8)
+    assert _lib.CONV_KERNELS[r.kernel] == "f32" and r.mode == 3 and r.packs == 1 << _lib.ENCODER_PACKINGS.index("stem_w")
+
+
 def test_create_refuses_foreign_config_struct(lib):
     """hpe_create checks HpeConfig.struct_size before it reads anything else: a zero-initialised struct (hpe_config_init not called: every
     plan option would read 0 = the slowest plan) and a struct of another header revision (shorter: the library would read plan options
