@@ -207,6 +207,21 @@ _PROTOS = {
     "hpe_debug_avgpool_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_encoder_stash": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_encoder_stash_batch": (C.c_int, [C.c_void_p]),
+    "hpe_encoder_stat_floats": (C.c_int, []),
+    "hpe_encoder_stat_offset": (C.c_int, [C.c_int, C.c_int]),
+    "hpe_encoder_train_reserve_batchnorm": (C.c_int, [C.c_void_p, C.c_int]),
+    "hpe_encoder_train_ws_floats_batchnorm": (C.c_longlong, [C.c_int]),
+    "hpe_debug_encoder_bn_slices": (C.c_int, [C.c_int, C.c_int]),
+    "hpe_encoder_forward_batchnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_encoder_backward_batchnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_encoder_get_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_encoder_update_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
+    "hpe_encoder_set_stats_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_debug_conv_batchnorm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_debug_conv_backward_batchnorm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
+    "hpe_debug_encoder_stash_raw": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_debug_encoder_batch_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_device_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hpe_debug_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

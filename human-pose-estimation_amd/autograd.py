@@ -106,16 +106,16 @@ class EncoderFunction(torch.autograd.Function):
     """features [B,2048] = hpe_encoder_forward_train(images; the engine's live encoder, BatchNorm statistics fixed), differentiable in
     ``params`` -- the flat tensor the optimiser owns, which must EQUAL what the engine holds (``set_encoder_params_dev`` after every step):
     it carries ``.grad``, the arithmetic reads the engine's weights.  Images get no gradient.  hpe_encoder_backward is stateless, so only
-    the images are saved."""
+    the images are saved.  ``bn``: "frozen" or "batch" (hpe_encoder_forward_batchnorm / hpe_encoder_backward_batchnorm)."""
 
     @staticmethod
-    def forward(ctx, engine, images, params):
-        ctx.engine = engine
+    def forward(ctx, engine, images, params, bn="frozen"):
+        ctx.engine, ctx.bn = engine, bn
         ctx.save_for_backward(images.detach())
-        return engine.encoder_forward_train(images)
+        return engine.encoder_forward_train(images, bn=bn)
 
     @staticmethod
     def backward(ctx, grad_features):
         (images,) = ctx.saved_tensors
-        g = ctx.engine.encoder_backward(images, grad_features.to(torch.float32).contiguous()) if ctx.needs_input_grad[2] else None
-        return None, None, g
+        g = ctx.engine.encoder_backward(images, grad_features.to(torch.float32).contiguous(), bn=ctx.bn) if ctx.needs_input_grad[2] else None
+        return None, None, g, None

@@ -7,8 +7,9 @@
 // workgroup that transposes reads each line it touches completely).  The permutations and the bf16 split are exact.  The folded values
 // (BatchNorm scale / shift, the dual-source weights, both Winograd forms) are computed in double by the __host__ __device__ helpers of
 // hpe_ctx.h the host packers call too: the same operations in the same order with contraction off, and fp64 + * / are correctly rounded on
-// gfx950.  The one sqrt is not taken here: the statistics are fixed, so hpe_encoder_train_reserve stores sqrt(var + eps) per channel, in
-// double, once (EncTrainWork::sd).
+// gfx950.  The one sqrt is not taken here: hpe_encoder_train_reserve stores sqrt(var + eps) per channel, in double (EncTrainWork::sd),
+// and hpe_encoder_set_stats_dev rewrites it on the device with a correctly rounded sqrt (encoder_bn.hip) before it reruns the two
+// kernels that fold the statistics (encoder_repack_stats_launch).
 //
 // One launch per form, not per layer: a form's grid is the concatenation of its layers' workgroups, and RepackForm says which layer a
 // workgroup belongs to (a scan of at most 53 workgroup-uniform entries).  The table is built once, by hpe_encoder_train_reserve, from the
@@ -337,6 +338,15 @@ hipError_t encoder_repack_launch(hpe_ctx* c, const float* flat, hipStream_t st) 
     if (grid[F_DUAL]) hipLaunchKernelGGL(repack_dual_kernel, dim3(grid[F_DUAL]), dim3(256), 0, st, T, flat, w.mean, w.sd);
     HIPE(hipGetLastError());
     return hipMemcpyAsync(w.flat, flat, (size_t)hpe_encoder_param_floats() * sizeof(float), hipMemcpyDeviceToDevice, st);
+}
+
+hipError_t encoder_repack_stats_launch(hpe_ctx* c, hipStream_t st) {
+    const EncTrainWork& w = c->et;
+    const RepackTable* T = static_cast<const RepackTable*>(w.repack);
+    const unsigned* grid = w.repack_grid;
+    if (grid[F_BN]) hipLaunchKernelGGL(repack_bn_kernel, dim3(grid[F_BN]), dim3(256), 0, st, T, w.flat, w.mean, w.sd);
+    if (grid[F_DUAL]) hipLaunchKernelGGL(repack_dual_kernel, dim3(grid[F_DUAL]), dim3(256), 0, st, T, w.flat, w.mean, w.sd);
+    return hipGetLastError();
 }
 
 #pragma GCC visibility push(default)

@@ -346,8 +346,9 @@ void gate(const float* dy, const float* y, const float* s, float* dz, float* dzs
                        reinterpret_cast<f32x4*>(dz), reinterpret_cast<f32x4*>(dzs), n / 4, N / 4);
 }
 
-// the weight gradient of layer idx and what hangs on it, into grad_layer = [kernel | bias | gamma | beta]: three launches
-hipError_t weight_grad(hpe_ctx* c, int idx, const float* x, const float* dz, int B, float* grad_layer, hipStream_t st) {
+// the weight gradient of layer idx and what hangs on it, into grad_layer = [kernel | bias | gamma | beta]: three launches.  bn (batch
+// statistics): dz is dzraw, dW = G with a unit scale, and the finish is not launched -- bias, gamma and beta come from bn_launch_bwd_reduce
+hipError_t weight_grad(hpe_ctx* c, int idx, const float* x, const float* dz, int B, float* grad_layer, hipStream_t st, bool bn = false) {
     const ConvSpec& s = specs()[idx];
     EncTrainWork& w = c->et;
     const Layout& l = layout();
@@ -376,7 +377,8 @@ hipError_t weight_grad(hpe_ctx* c, int idx, const float* x, const float* dz, int
     const float* flat = w.flat;
     const int kn = a.K * a.N;
     hipLaunchKernelGGL(conv_wg_fixup_kernel, dim3(a.n_nt, n_kc), dim3(256), 0, st, w.partial, slices, a.K, a.N, flat + l.off[idx][0],
-                       c->conv[idx].scale, grad_layer, w.wgp);
+                       bn ? c->ones : c->conv[idx].scale, grad_layer, w.wgp);
+    if (bn) return hipGetLastError();
     hipLaunchKernelGGL(conv_wg_finish_kernel, dim3(a.n_nt), dim3(256), 0, st, w.wgp, n_kc, w.dsh, slices, a.N, flat + l.off[idx][1],
                        w.mean + l.stat[idx], w.istd + l.stat[idx], c->conv[idx].scale, grad_layer + kn, grad_layer + kn + a.N,
                        grad_layer + kn + 2 * a.N);
@@ -482,6 +484,118 @@ hipError_t backward(hpe_ctx* c, const float* images, int B, const float* grad_fe
     return weight_grad(c, 0, images, go, B, grad_flat + l.off[0][0], st);
 }
 
+// ---- BatchNorm with batch statistics (encoder_bn.hip holds the kernels): the same walks with z kept beside y
+
+float* zstash_of(hpe_ctx* c, int idx, int B) { return c->et.zstash + (size_t)B * layout().stash[idx]; }
+
+struct BnSlots {
+    float *mu, *var, *r;
+};
+
+// layer idx's slots of the batch statistics; scratch: the three 2048-float slots behind them, for the one-layer debug calls
+BnSlots bn_slots(hpe_ctx* c, int idx, bool scratch) {
+    const Layout& l = layout();
+    float* b = c->et.bn_batch;
+    if (scratch) return {b + 3 * l.channels, b + 3 * l.channels + 2048, b + 3 * l.channels + 4096};
+    return {b + l.stat[idx], b + l.channels + l.stat[idx], b + 2 * l.channels + l.stat[idx]};
+}
+
+// z = conv(x, W) + b (the layer's own route, unit scale, the bias of the flat copy as shift), its statistics, y = act(BN(z) (+ res))
+hipError_t layer_forward_bn(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* z, float* y, const BnSlots& s, hipStream_t st) {
+    const ConvSpec& sp = specs()[idx];
+    const Layout& l = layout();
+    const float* flat = c->et.flat;
+    const int M = B * sp.hout * sp.hout;
+    HIPE(run_conv_nhwc(c, idx, x, B, nullptr, 0, z, st, c->ones, flat + l.off[idx][1]));
+    HIPE(bn_launch_stats(z, M, sp.cout, c->cfg.bn_eps, c->et.bn_part, s.mu, s.var, s.r, st));
+    return bn_launch_apply(z, s.mu, s.r, flat + l.off[idx][2], flat + l.off[idx][3], res, relu, y, M, sp.cout, st);
+}
+
+// the gate and the BatchNorm backward of layer idx: db (= 0), dgamma, dbeta into grad_layer; dz (may be nullptr, may alias dy) and dzraw
+hipError_t layer_gate_bn(hpe_ctx* c, int idx, const float* dy, const float* y, const float* z, int B, const BnSlots& s, float* grad_layer, float* dz,
+                         float* dzraw, hipStream_t st) {
+    const ConvSpec& sp = specs()[idx];
+    const int M = B * sp.hout * sp.hout, N = sp.cout, kn = sp.kh * sp.kw * sp.cin * N;
+    float *db = grad_layer + kn, *dgamma = db + N, *dbeta = dgamma + N;
+    HIPE(bn_launch_bwd_reduce(dy, y, z, s.mu, s.r, M, N, c->et.bn_part, db, dgamma, dbeta, st));
+    return bn_launch_bwd_apply(dy, y, z, s.mu, s.r, c->et.flat + layout().off[idx][2], dgamma, dbeta, M, N, dz, dzraw, st);
+}
+
+hipError_t forward_bn(hpe_ctx* c, const float* images, int B, float* features, hipStream_t st) {
+    auto layer = [&](int idx, const float* x, const float* res, int relu) {
+        return layer_forward_bn(c, idx, x, B, res, relu, zstash_of(c, idx, B), stash_of(c, idx, B), bn_slots(c, idx, false), st);
+    };
+    HIPE(hpe_launch_pad_input(images, c->padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
+    HIPE(layer(0, c->padded, nullptr, 1));
+    HIPE(hpe_launch_maxpool(stash_of(c, 0, B), stash_of(c, -1, B), B, 112, 64, st));
+    for (const ResBlock& blk : blocks()) {
+        const float* cur = stash_of(c, blk.in, B);
+        HIPE(layer(blk.i2a, cur, nullptr, 1));
+        HIPE(layer(blk.i2b, stash_of(c, blk.i2a, B), nullptr, 1));
+        const float* res = cur;
+        if (blk.first) {
+            HIPE(layer(blk.i1, cur, nullptr, 0));
+            res = stash_of(c, blk.i1, B);
+        }
+        HIPE(layer(blk.i2c, stash_of(c, blk.i2b, B), res, 1));
+    }
+    return hpe_launch_avgpool(stash_of(c, blocks().back().i2c, B), features, B, 49, HPE_FEATURE_DIM, HPE_FEATURE_DIM, st);
+}
+
+hipError_t backward_bn(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, hipStream_t st) {
+    EncTrainWork& w = c->et;
+    const Layout& l = layout();
+    HIPE(forward_bn(c, images, B, w.feat, st));
+    // dy -> layer idx's bias / gamma / beta gradients, dz (nullptr: not kept) and dzraw
+    auto gate_bn = [&](int idx, const float* dy, bool gated, float* dz, float* dzraw) {
+        return layer_gate_bn(c, idx, dy, gated ? stash_of(c, idx, B) : nullptr, zstash_of(c, idx, B), B, bn_slots(c, idx, false),
+                             grad_flat + l.off[idx][0], dz, dzraw, st);
+    };
+    auto wgrad = [&](int idx, const float* x, const float* dzraw) { return weight_grad(c, idx, x, dzraw, B, grad_flat + l.off[idx][0], st, true); };
+    float *g = w.g0, *go = w.g1;
+    hipLaunchKernelGGL(enc_avgpool_bwd_kernel, grid1((long)B * 49 * HPE_FEATURE_DIM), dim3(256), 0, st, grad_features, g, B, 49, HPE_FEATURE_DIM);
+    for (auto it = blocks().rbegin(); it != blocks().rend(); ++it) {
+        const int i2a = it->i2a, i2b = it->i2b, i2c = it->i2c, i1 = it->i1;
+        const ConvSpec& sa = specs()[i2a];
+        const float* xin = stash_of(c, it->in, B);
+        // branch2c: g becomes dz (the cotangent of the shortcut too)
+        HIPE(gate_bn(i2c, g, true, g, w.sbig));
+        HIPE(wgrad(i2c, stash_of(c, i2b, B), w.sbig));
+        HIPE(data_grad(c, i2c, w.sbig, B, nullptr, w.t0, st));
+        HIPE(gate_bn(i2b, w.t0, true, nullptr, w.ssmall));
+        HIPE(wgrad(i2b, stash_of(c, i2a, B), w.ssmall));
+        HIPE(data_grad(c, i2b, w.ssmall, B, nullptr, w.t1, st));
+        HIPE(gate_bn(i2a, w.t1, true, nullptr, w.ssmall));
+        HIPE(wgrad(i2a, xin, w.ssmall));
+        if (!it->first) {
+            HIPE(data_grad(c, i2a, w.ssmall, B, g, go, st));
+            std::swap(g, go);
+            continue;
+        }
+        // projection shortcut: no activation of its own, its dz is the block's
+        HIPE(gate_bn(i1, g, false, nullptr, w.sbig));
+        HIPE(wgrad(i1, xin, w.sbig));
+        if (sa.stride == 1) {
+            HIPE(data_grad(c, i2a, w.ssmall, B, nullptr, go, st));
+            HIPE(data_grad(c, i1, w.sbig, B, go, g, st));
+        } else {
+            HIPE(data_grad(c, i2a, w.ssmall, B, nullptr, w.t0, st));
+            HIPE(data_grad(c, i1, w.sbig, B, w.t0, w.t1, st));
+            scatter2(w.t1, go, B, sa.hout, sa.cin, st);
+            std::swap(g, go);
+        }
+    }
+    hipLaunchKernelGGL(enc_maxpool_bwd_kernel, grid1((long)B * 112 * 112 * 64), dim3(256), 0, st, stash_of(c, 0, B), g, go, B, 112, 64);
+    HIPE(gate_bn(0, go, true, nullptr, w.sbig));
+    return wgrad(0, images, w.sbig);
+}
+
+size_t bn_batch_floats() { return 3 * (size_t)layout().channels + 3 * 2048; }
+
+size_t ws_floats_bn(int B) {
+    return (size_t)B * layout().stash_pool + bn_batch_floats() + 2 * (size_t)layout().channels + 4 * (size_t)BN_PART_COLS + layout().channels;
+}
+
 int check_train(hpe_ctx* c, int B, bool need_reserve = true) {
     if (!c) return fail(HPE_ERR_INVALID, "null ctx");
     if (c->dead) return fail(HPE_ERR_STATE, "hpe_finalize failed on this ctx: destroy it and create a new one");
@@ -491,6 +605,15 @@ int check_train(hpe_ctx* c, int B, bool need_reserve = true) {
     if (need_reserve && c->et.B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve() has not been called");
     if (B < 1 || B > (need_reserve ? c->et.B : c->cfg.max_batch))
         return fail(HPE_ERR_INVALID, "batch " + std::to_string(B) + (need_reserve ? " outside [1, reserved batch]" : " outside [1, max_batch]"));
+    return HPE_OK;
+}
+
+// ... and for the calls that need hpe_encoder_train_reserve_batchnorm
+int check_train_bn(hpe_ctx* c, int B) {
+    int rc = check_train(c, 1);
+    if (rc) return rc;
+    if (c->et.bn_B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_batchnorm() has not been called");
+    if (B < 1 || B > c->et.bn_B) return fail(HPE_ERR_INVALID, "batch " + std::to_string(B) + " outside [1, batch of the batch-norm reserve]");
     return HPE_OK;
 }
 
@@ -626,6 +749,15 @@ int hpe_encoder_set_params(hpe_ctx* c, const float* flat) {
     DeviceGuard g(c->cfg.device);
     const Layout& l = layout();
     HIP_TRY(hipDeviceSynchronize());  // launches still reading the weights
+    if (c->et.bn_B) {  // hpe_encoder_set_stats_dev may have moved the statistics: the host packers fold what is installed
+        std::vector<float> stats(2 * (size_t)l.channels);
+        HIP_TRY(hipMemcpy(stats.data(), c->et.bn_stats, stats.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (int i = 0; i < HPE_NUM_CONV; ++i) {
+            const int n = specs()[i].cout;
+            c->conv[i].mean.assign(stats.begin() + l.stat[i], stats.begin() + l.stat[i] + n);
+            c->conv[i].var.assign(stats.begin() + l.channels + l.stat[i], stats.begin() + l.channels + l.stat[i] + n);
+        }
+    }
     for (int i = 0; i < HPE_NUM_CONV; ++i) {
         const ConvSpec& s = specs()[i];
         ConvLayer& L = c->conv[i];
@@ -700,6 +832,176 @@ int hpe_debug_encoder_stash(hpe_ctx* c, int idx, float* out, void* stream) {
     DeviceGuard g(c->cfg.device);
     const size_t n = idx < 0 ? (size_t)POOL_FLOATS : (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
     HIP_TRY(hipMemcpyAsync(out, stash_of(c, idx, B), (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+// ---- BatchNorm with batch statistics
+
+int hpe_encoder_stat_floats(void) { return 2 * layout().channels; }
+
+int hpe_encoder_stat_offset(int idx, int which) {
+    if (idx < 0 || idx >= HPE_NUM_CONV || which < 0 || which > 1) return -1;
+    return which * layout().channels + layout().stat[idx];
+}
+
+long long hpe_encoder_train_ws_floats_batchnorm(int B) { return B < 1 ? 0 : (long long)(ws_floats(B) + ws_floats_bn(B)); }
+
+int hpe_debug_encoder_bn_slices(int idx, int B) {
+    if (idx < 0 || idx >= HPE_NUM_CONV || B < 1) return -1;
+    return bn_slices(B * specs()[idx].hout * specs()[idx].hout, specs()[idx].cout);
+}
+
+int hpe_encoder_train_reserve_batchnorm(hpe_ctx* c, int B) {
+    int rc = hpe_encoder_train_reserve(c, B);
+    if (rc) return rc;
+    EncTrainWork& w = c->et;
+    if (w.bn_B != 0) return B <= w.bn_B ? HPE_OK : fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_batchnorm: already reserved for a smaller batch");
+    DeviceGuard g(c->cfg.device);
+    const Layout& l = layout();
+    float* p = nullptr;
+    if ((rc = dev_alloc(c, &w.zstash, (size_t)B * l.stash_pool, false))) return rc;
+    if ((rc = dev_alloc(c, &w.bn_batch, bn_batch_floats(), true))) return rc;
+    if ((rc = dev_alloc(c, &w.bn_stats, 2 * (size_t)l.channels, false))) return rc;
+    if ((rc = dev_alloc(c, &p, 4 * (size_t)BN_PART_COLS, false))) return rc;
+    w.bn_part = reinterpret_cast<double*>(p);
+    p = nullptr;
+    if ((rc = dev_alloc(c, &p, l.channels, false))) return rc;
+    w.bn_hw = reinterpret_cast<int*>(p);
+    // the statistics as loaded (nothing can have moved them: hpe_encoder_set_stats_dev needs this reserve) and every channel's map size
+    std::vector<float> stats(2 * (size_t)l.channels);
+    std::vector<int> hw(l.channels);
+    for (int i = 0; i < HPE_NUM_CONV; ++i) {
+        const ConvSpec& s = specs()[i];
+        for (int n = 0; n < s.cout; ++n) {
+            stats[l.stat[i] + n] = c->conv[i].mean[n];
+            stats[l.channels + l.stat[i] + n] = c->conv[i].var[n];
+            hw[l.stat[i] + n] = s.hout * s.hout;
+        }
+    }
+    HIP_TRY(hipMemcpy(w.bn_stats, stats.data(), stats.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.bn_hw, hw.data(), hw.size() * sizeof(int), hipMemcpyHostToDevice));
+    w.bn_B = B;
+    return HPE_OK;
+}
+
+int hpe_encoder_forward_batchnorm(hpe_ctx* c, const float* images, int B, float* features, void* stream) {
+    int rc = check_train_bn(c, B);
+    if (rc) return rc;
+    if (!images || !features) return fail(HPE_ERR_INVALID, "null pointer");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(forward_bn(c, images, B, features, static_cast<hipStream_t>(stream)));
+    c->et.stash_B = c->et.bn_stat_B = B;
+    return HPE_OK;
+}
+
+int hpe_encoder_backward_batchnorm(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
+    int rc = check_train_bn(c, B);
+    if (rc) return rc;
+    if (!images || !grad_features || !grad_flat) return fail(HPE_ERR_INVALID, "null pointer");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(backward_bn(c, images, B, grad_features, grad_flat, static_cast<hipStream_t>(stream)));
+    c->et.stash_B = c->et.bn_stat_B = B;
+    return HPE_OK;
+}
+
+int hpe_encoder_get_stats(hpe_ctx* c, float* stats, void* stream) {
+    int rc = check_train_bn(c, 1);
+    if (rc) return rc;
+    if (!stats) return fail(HPE_ERR_INVALID, "null stats_dev");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(hipMemcpyAsync(stats, c->et.bn_stats, 2 * (size_t)layout().channels * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+int hpe_encoder_update_stats(hpe_ctx* c, float* stats, double momentum, int unbiased, void* stream) {
+    int rc = check_train_bn(c, 1);
+    if (rc) return rc;
+    if (!stats) return fail(HPE_ERR_INVALID, "null stats_dev");
+    if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(HPE_ERR_INVALID, "momentum outside [0, 1]");
+    if (c->et.bn_stat_B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_update_stats: no batch-statistics forward has run");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(bn_launch_momentum(stats, c->et.bn_batch, c->et.bn_hw, c->et.bn_stat_B, layout().channels, momentum, unbiased != 0,
+                               static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+int hpe_encoder_set_stats_dev(hpe_ctx* c, const float* stats, void* stream) {
+    int rc = check_train_bn(c, 1);
+    if (rc) return rc;
+    if (!stats) return fail(HPE_ERR_INVALID, "null stats_dev");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    EncTrainWork& w = c->et;
+    HIP_TRY(bn_launch_install(stats, layout().channels, c->cfg.bn_eps, w.bn_stats, w.mean, w.istd, w.sd, st));
+    HIP_TRY(encoder_repack_stats_launch(c, st));
+    return HPE_OK;
+}
+
+int hpe_debug_conv_batchnorm(hpe_ctx* c, int idx, const float* x, int B, const float* residual, int relu, float* y, float* z_out, float* stats_out,
+                             void* stream) {
+    int rc = check_train_bn(c, B);
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !y || !z_out || !stats_out) return fail(HPE_ERR_INVALID, "bad argument");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const float* in = x;
+    if (idx == 0) {
+        HIP_TRY(hpe_launch_pad_input(x, c->padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
+        in = c->padded;
+    }
+    const BnSlots s = bn_slots(c, idx, true);
+    HIP_TRY(layer_forward_bn(c, idx, in, B, residual, relu, z_out, y, s, st));
+    const size_t n = (size_t)specs()[idx].cout * sizeof(float);
+    HIP_TRY(hipMemcpyAsync(stats_out, s.mu, n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(stats_out + specs()[idx].cout, s.var, n, hipMemcpyDeviceToDevice, st));
+    return HPE_OK;
+}
+
+int hpe_debug_conv_backward_batchnorm(hpe_ctx* c, int idx, const float* x, const float* z, const float* y, const float* dy, int B, float* dx,
+                                      float* grad_layer, void* stream) {
+    int rc = check_train_bn(c, B);
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !z || !dy || !grad_layer) return fail(HPE_ERR_INVALID, "bad argument");
+    if (idx == 0 && dx) return fail(HPE_ERR_INVALID, "hpe_debug_conv_backward_batchnorm: conv1 has no data gradient, dx_dev must be NULL");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ConvSpec& s = specs()[idx];
+    EncTrainWork& w = c->et;
+    const BnSlots sl = bn_slots(c, idx, true);
+    HIP_TRY(bn_launch_stats(z, B * s.hout * s.hout, s.cout, c->cfg.bn_eps, w.bn_part, sl.mu, sl.var, sl.r, st));
+    HIP_TRY(layer_gate_bn(c, idx, dy, y, z, B, sl, grad_layer, nullptr, w.sbig, st));
+    HIP_TRY(weight_grad(c, idx, x, w.sbig, B, grad_layer, st, true));
+    if (!dx) return HPE_OK;
+    if (s.stride == 1) {
+        HIP_TRY(data_grad(c, idx, w.sbig, B, nullptr, dx, st));
+    } else {
+        HIP_TRY(data_grad(c, idx, w.sbig, B, nullptr, w.t0, st));
+        scatter2(w.t0, dx, B, s.hout, s.cin, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return HPE_OK;
+}
+
+int hpe_debug_encoder_stash_raw(hpe_ctx* c, int idx, float* out, void* stream) {
+    int rc = check_train_bn(c, 1);
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV || !out) return fail(HPE_ERR_INVALID, "bad argument");
+    const int B = c->et.bn_stat_B;
+    if (B == 0) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw: no batch-statistics forward has run");
+    if (c->et.stash_B != B) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw: a frozen-statistics forward of another batch has refilled the stash since");
+    DeviceGuard g(c->cfg.device);
+    const size_t n = (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
+    HIP_TRY(hipMemcpyAsync(out, zstash_of(c, idx, B), (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+int hpe_debug_encoder_batch_stats(hpe_ctx* c, float* out, void* stream) {
+    int rc = check_train_bn(c, 1);
+    if (rc) return rc;
+    if (!out) return fail(HPE_ERR_INVALID, "null out_dev");
+    if (c->et.bn_stat_B == 0) return fail(HPE_ERR_STATE, "hpe_debug_encoder_batch_stats: no batch-statistics forward has run");
+    DeviceGuard g(c->cfg.device);
+    HIP_TRY(hipMemcpyAsync(out, c->et.bn_batch, 2 * (size_t)layout().channels * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     return HPE_OK;
 }
 

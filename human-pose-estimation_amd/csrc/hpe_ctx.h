@@ -49,7 +49,8 @@ inline int round_up(int x, int m) { return ((x + m - 1) / m) * m; }
 struct ConvLayer {
     // Host staging (Keras layouts).  kernel is released by hpe_finalize.  bias / gamma / beta go STALE after hpe_encoder_set_params_dev:
     // after hpe_finalize nothing reads them but hpe_encoder_train_reserve (once, before any device update can run) and
-    // hpe_encoder_set_params, which overwrites all of them first.  mean / var never change.
+    // hpe_encoder_set_params, which overwrites all of them first.  mean / var change only through hpe_encoder_set_stats_dev, on the device:
+    // hpe_encoder_set_params copies the installed statistics back here before it folds.
     std::vector<float> kernel, bias, gamma, beta, mean, var;
     bool loaded = false;
     float* w = nullptr;  // device, packed [n_pad][k_pad] (fp32) or bf16 [n_pad][k_pad16] in bf16 mode
@@ -184,7 +185,8 @@ struct RegTrainWork {
 
 // Encoder training (encoder_train.hip), allocated by hpe_encoder_train_reserve for B images: nothing of it exists in an inference context.
 // flat and dxw follow the live parameters: hpe_encoder_set_params uploads them from the host, hpe_encoder_set_params_dev rewrites them on
-// the device with every packing of ConvLayer (encoder_repack.hip); mean / istd / sd and the repack table are written once, by the reserve
+// the device with every packing of ConvLayer (encoder_repack.hip); mean / istd / sd are written by the reserve and rewritten by
+// hpe_encoder_set_stats_dev; the repack table is written once, by the reserve
 struct EncTrainWork {
     int B = 0;        // reserved batch (0: not reserved)
     int stash_B = 0;  // batch of the training forward that last filled the stash
@@ -204,7 +206,17 @@ struct EncTrainWork {
     float *zeros = nullptr;  // 2048 zeros (shift of the data-gradient GEMMs)
     float *feat = nullptr;   // [B][2048] features of the backward's own forward
     float *dxw[HPE_NUM_CONV] = {};  // data-gradient operands Wt[cin][k], beside the forward's packings
+    // BatchNorm with batch statistics (encoder_bn.hip), allocated by hpe_encoder_train_reserve_batchnorm only
+    int bn_B = 0;       // its reserved batch (0: not reserved)
+    int bn_stat_B = 0;  // batch of the batch-statistics forward that last filled zstash / bn_batch (0: none has run)
+    float *zstash = nullptr;    // every layer's raw output conv(x, W) + b, laid out as the stash (without the pooled map)
+    float *bn_batch = nullptr;  // [mu | var | r] of that forward, `channels` floats each, then 3 x 2048 floats for the one-layer debug calls
+    float *bn_stats = nullptr;  // the installed moving statistics [mean of every channel | variance of every channel]
+    double *bn_part = nullptr;  // [slices][2][N] partial column sums of the reduction in flight (2 * BN_PART_COLS doubles)
+    int *bn_hw = nullptr;       // hout * hout of every channel's layer (the M of hpe_encoder_update_stats)
 };
+constexpr int BN_MAX_SLICES = 512;     // pixel slices of one BatchNorm reduction
+constexpr int BN_PART_COLS = 262144;   // slices * channels of one reduction, at most
 // floats of layer idx's data-gradient operand: rows = input channels padded to 128, k = (flipped tap, output channel); conv1 has none
 inline size_t conv_dxw_floats(int idx) {
     const ConvSpec& s = specs()[idx];
@@ -320,12 +332,15 @@ void release_device_state(hpe_ctx* c);  // release everything a (possibly partia
 // hpe_finalize allocated: no pointer changes.  Synchronous.
 int repack_encoder(hpe_ctx* c);
 
-// hpe_encoder.hip: launch what the route says.  wino_v: the launch's slice of the Winograd V workspace, slot: its chunk stream
+// hpe_encoder.hip: launch what the route says.  wino_v: the launch's slice of the Winograd V workspace, slot: its chunk stream.
+// scale / shift: the epilogue's per-channel vectors, nullptr = the layer's folded BatchNorm (the batch-statistics forward passes ones and
+// the conv bias: every packing of the weights is unscaled)
 hipError_t run_conv(hpe_ctx* c, int idx, const ConvRoute& r, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
-                    float* wino_v = nullptr, int slot = 0);
+                    float* wino_v = nullptr, int slot = 0, const float* scale = nullptr, const float* shift = nullptr);
 // one layer on NHWC input, alone on the device, as hpe_debug_conv and the training forward launch it: asks the route and converts the
 // input to channel-slab major (through T1) when the route reads that
-hipError_t run_conv_nhwc(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st);
+hipError_t run_conv_nhwc(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
+                         const float* scale = nullptr, const float* shift = nullptr);
 hipError_t run_chain(hpe_ctx* c, int i2c, bool first, const float* t2, const float* res, int B, float* t3, float* u1, hipStream_t st,
                      bool u1_slab8 = false);
 hipError_t encoder_impl(hpe_ctx* c, const float* images, int B, float* features, int ldfeat, hipStream_t st);
@@ -342,6 +357,22 @@ int forward_impl(hpe_ctx* c, const float* images, int B, const HpeOutputs* stage
 size_t encoder_repack_reserve_floats();            // what encoder_repack_reserve allocates beyond the statistics (the layer table)
 int encoder_repack_reserve(hpe_ctx* c);            // builds the device-side layer table from the ctx's pointers; et.sd / et.mean / et.dxw exist
 hipError_t encoder_repack_launch(hpe_ctx* c, const float* flat_dev, hipStream_t st);
+
+// the two of them that fold the statistics (scale / shift, the dual-source weights), from the ctx's own flat copy: hpe_encoder_set_stats_dev
+hipError_t encoder_repack_stats_launch(hpe_ctx* c, hipStream_t st);
+
+// encoder_bn.hip: BatchNorm with batch statistics around a layer's raw output z [M][N] (N a multiple of 64, at most 2048).  part: 2 *
+// BN_PART_COLS doubles.  mu / var / r / gamma / beta are 16-byte aligned; dgamma / dbeta / db need not be
+int bn_slices(int M, int N);  // pixel slices of the reductions (-1: a shape they do not take)
+hipError_t bn_launch_stats(const float* z, int M, int N, float eps, double* part, float* mu, float* var, float* r, hipStream_t st);
+hipError_t bn_launch_apply(const float* z, const float* mu, const float* r, const float* gamma, const float* beta, const float* res, int relu, float* y,
+                           int M, int N, hipStream_t st);
+hipError_t bn_launch_bwd_reduce(const float* dy, const float* y, const float* z, const float* mu, const float* r, int M, int N, double* part, float* db,
+                                float* dgamma, float* dbeta, hipStream_t st);
+hipError_t bn_launch_bwd_apply(const float* dy, const float* y, const float* z, const float* mu, const float* r, const float* gamma, const float* dgamma,
+                               const float* dbeta, int M, int N, float* dz, float* dzraw, hipStream_t st);
+hipError_t bn_launch_momentum(float* stats, const float* batch, const int* hw, int B, int channels, double momentum, int unbiased, hipStream_t st);
+hipError_t bn_launch_install(const float* stats, int channels, float eps, float* keep, float* mean, float* istd, double* sd, hipStream_t st);
 
 // regressor_train.hip
 int regressor_param_offset(int idx, bool bias);  // idx 3: mean theta; idx 4 (bias false): the total

@@ -29,17 +29,19 @@ static hipError_t launch_gemm(hpe_ctx* c, GemmArgs& p, const ConvRoute& r, const
 // one conv layer (+BN fold, +residual, +ReLU) through the kernel of its route (hpe_plan.hip).  A route whose packing or workspace this
 // context does not hold, or a residual on a kernel that takes none, is refused: nothing is launched
 hipError_t run_conv(hpe_ctx* c, int idx, const ConvRoute& r, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
-                    float* wino_v, int slot) {
+                    float* wino_v, int slot, const float* scale, const float* shift) {
     const ConvSpec& s = specs()[idx];
     const ConvLayer& L = c->conv[idx];
+    if (!scale) scale = L.scale;
+    if (!shift) shift = L.shift;
     const int H = s.hin;
     const bool f2 = r.kernel == CONV_K_WINO || r.kernel == CONV_K_WINO_FUSED, f4 = r.kernel == CONV_K_WINO4 || r.kernel == CONV_K_WINO4_FUSED;
     if ((r.kernel >= CONV_K_HALO3 && res) || (f2 && !L.wino_u) || (f4 && !L.wino4_u) || ((f2 || f4) && !r.in_slab8 && !wino_v)) return hipErrorInvalidValue;
     switch (r.kernel) {
-        case CONV_K_WINO4_FUSED: return hpe_launch_wino4_fused_conv3(x, L.wino4_u, L.scale, L.shift, c->zeros, y, s.cout, B, H, H, s.cin, s.cout, relu, st);
-        case CONV_K_WINO_FUSED: return hpe_launch_wino_fused_conv3(x, L.wino_u, L.scale, L.shift, c->zeros, y, s.cout, B, H, H, s.cin, s.cout, relu, st);
+        case CONV_K_WINO4_FUSED: return hpe_launch_wino4_fused_conv3(x, L.wino4_u, scale, shift, c->zeros, y, s.cout, B, H, H, s.cin, s.cout, relu, st);
+        case CONV_K_WINO_FUSED: return hpe_launch_wino_fused_conv3(x, L.wino_u, scale, shift, c->zeros, y, s.cout, B, H, H, s.cin, s.cout, relu, st);
         case CONV_K_WINO4:
-            return hpe_launch_wino4_conv3(x, s.cin, L.wino4_u, L.scale, L.shift, y, s.cout, B, H, H, s.cin, s.cout, relu, wino_v, st, r.concurrent ? c->co_running : 1,
+            return hpe_launch_wino4_conv3(x, s.cin, L.wino4_u, scale, shift, y, s.cout, B, H, H, s.cin, s.cout, relu, wino_v, st, r.concurrent ? c->co_running : 1,
                                           c->w4_split && slot >= 0 && slot < 4 ? c->w4_split + (size_t)slot * hpe_wino4_split_ws_floats() : nullptr, c->plan.wino4_n32,
                                           c->plan.w4_abl);
         case CONV_K_WINO: {
@@ -52,19 +54,19 @@ hipError_t run_conv(hpe_ctx* c, int idx, const ConvRoute& r, const float* x, int
                 sk.n_wg = c->n_cu;
                 sk.err = c->dev_err;
             }
-            return hpe_launch_wino_conv3(x, s.cin, L.wino_u, L.scale, L.shift, y, s.cout, B, H, H, s.cin, s.cout, relu, wino_v, c->wino_ws ? &sk : nullptr, st);
+            return hpe_launch_wino_conv3(x, s.cin, L.wino_u, scale, shift, y, s.cout, B, H, H, s.cin, s.cout, relu, wino_v, c->wino_ws ? &sk : nullptr, st);
         }
         case CONV_K_HALO3: {
             Halo3Args h{};
             h.x = reinterpret_cast<const __bf16*>(x), h.w = reinterpret_cast<const __bf16*>(L.w), h.y = reinterpret_cast<__bf16*>(y);
-            h.scale = L.scale, h.shift = L.shift;
+            h.scale = scale, h.shift = shift;
             h.M = B * s.hout * s.hout, h.N = s.cout, h.ldw = L.k_pad;
             h.relu = relu, h.two = c->plan.halo3_two;
             return hpe_launch_halo3_bf16(h, H, s.cin, st);
         }
     }
     GemmArgs p{};
-    p.x = x, p.w = L.w, p.scale = L.scale, p.shift = L.shift, p.res = res, p.y = y, p.zero = c->zeros;
+    p.x = x, p.w = L.w, p.scale = scale, p.shift = shift, p.res = res, p.y = y, p.zero = c->zeros;
     p.M = B * s.hout * s.hout, p.N = s.cout, p.K = L.k_pad;
     p.lda = s.cin, p.ldw = L.k_pad, p.w_rows = L.n_pad, p.ldy = p.ldres = s.cout;
     p.Hi = p.Wi = H, p.Cin = s.cin, p.Ho = p.Wo = s.hout, p.stride = s.stride;
@@ -74,7 +76,8 @@ hipError_t run_conv(hpe_ctx* c, int idx, const ConvRoute& r, const float* x, int
     return launch_gemm(c, p, r, L.w_split, st);
 }
 
-hipError_t run_conv_nhwc(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st) {
+hipError_t run_conv_nhwc(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st, const float* scale,
+                         const float* shift) {
     const ConvRoute r = route_conv(c->plan, c->bf16, idx, ConvQuery{B, false, res != nullptr, c->wino_v != nullptr});
     if (r.in_slab8) {
         // the fused Winograd kernels read channel-slab major input; in the network their 1x1 producer writes that directly
@@ -82,7 +85,7 @@ hipError_t run_conv_nhwc(hpe_ctx* c, int idx, const float* x, int B, const float
         HIPE(hpe_launch_nhwc_to_slab8(x, c->T1, (long)B * s.hin * s.hin, s.cin, st));
         x = c->T1;
     }
-    return run_conv(c, idx, r, x, B, res, relu, y, st, c->wino_v);
+    return run_conv(c, idx, r, x, B, res, relu, y, st, c->wino_v, 0, scale, shift);
 }
 
 // branch2c (+BN) + branch1 (+BN) + add + ReLU of a conv_block as one dual-source GEMM: t2 [M, K1] dense, x NHWC strided

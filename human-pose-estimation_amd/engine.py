@@ -11,7 +11,7 @@ import numpy as np
 from . import _lib
 from .critic_spec import PARAM_FLOATS
 from .regressor_spec import PARAM_FLOATS as REGRESSOR_PARAM_FLOATS
-from .resnet_spec import CONV_SPECS, ENCODER_PARAM_FLOATS
+from .resnet_spec import CONV_SPECS, ENCODER_PARAM_FLOATS, ENCODER_STAT_FLOATS
 
 NUM_VERTS = _lib.NUM_VERTS
 
@@ -646,10 +646,88 @@ class HpeEngine(object):
                                                    gfeat.data_ptr() if want_grad_features else None, self._stream()))
         return gflat, gfeat
 
-    # ------------------------------------------------------------------ encoder training (fp32 contexts, frozen BatchNorm statistics)
-    def reserve_encoder_train(self, B):
-        """hpe_encoder_train_reserve: allocate the stash, cotangent buffers, partial sums and data-gradient packings for batches up to B"""
-        _lib.check(self.lib.hpe_encoder_train_reserve(self._h, int(B)))
+    # ------------------------------------------------------------------ encoder training (fp32 contexts; BatchNorm statistics frozen or of the batch)
+    def reserve_encoder_train(self, B, batch_norm=False):
+        """hpe_encoder_train_reserve: allocate the stash, cotangent buffers, partial sums and data-gradient packings for batches up to B.
+        batch_norm=True (hpe_encoder_train_reserve_batchnorm): also the raw-output stash and the statistics buffers that ``bn="batch"``,
+        ``encoder_stats``, ``update_encoder_stats`` and ``set_encoder_stats_dev`` need."""
+        if batch_norm:
+            _lib.check(self.lib.hpe_encoder_train_reserve_batchnorm(self._h, int(B)))
+        else:
+            _lib.check(self.lib.hpe_encoder_train_reserve(self._h, int(B)))
+
+    @staticmethod
+    def _bn_mode(bn):
+        if bn not in ("frozen", "batch"):
+            raise ValueError("bn must be 'frozen' or 'batch', got %r" % (bn,))
+        return bn == "batch"
+
+    def encoder_stats(self):
+        """hpe_encoder_get_stats: the installed moving statistics as one flat CUDA tensor [resnet_spec.ENCODER_STAT_FLOATS] (moving_mean of
+        every layer, then moving_variance of every layer)"""
+        out = self._new(ENCODER_STAT_FLOATS)
+        _lib.check(self.lib.hpe_encoder_get_stats(self._h, out.data_ptr(), self._stream()))
+        return out
+
+    def _stats_arg(self, stats):
+        stats = _require_cuda_tensor(stats.detach(), "stats")
+        if tuple(stats.shape) != (ENCODER_STAT_FLOATS,):
+            raise ValueError("stats must be [%d], got %s" % (ENCODER_STAT_FLOATS, tuple(stats.shape)))
+        return stats
+
+    def update_encoder_stats(self, stats, momentum=0.99, unbiased=True):
+        """hpe_encoder_update_stats: stats <- momentum * stats + (1 - momentum) * (the batch statistics of the last ``bn="batch"`` forward
+        or backward), in place on the CUDA tensor ``stats``; unbiased multiplies each batch variance by M / (M - 1).  Returns ``stats``.
+        It installs nothing: ``set_encoder_stats_dev`` does."""
+        _lib.check(self.lib.hpe_encoder_update_stats(self._h, self._stats_arg(stats).data_ptr(), float(momentum), int(bool(unbiased)), self._stream()))
+        return stats
+
+    def set_encoder_stats_dev(self, stats):
+        """hpe_encoder_set_stats_dev: install the CUDA tensor ``stats`` as the moving statistics, in stream order: the folded BatchNorm
+        scale / shift and the dual-source weights are rewritten from them and the live parameters.  Capturable."""
+        stats = self._stats_arg(stats)
+        _lib.check(self.lib.hpe_encoder_set_stats_dev(self._h, stats.data_ptr(), self._stream()))
+
+    def encoder_batch_stats(self):
+        """hpe_debug_encoder_batch_stats: mu | var of every layer of the last ``bn="batch"`` forward, in the statistics layout"""
+        out = self._new(ENCODER_STAT_FLOATS)
+        _lib.check(self.lib.hpe_debug_encoder_batch_stats(self._h, out.data_ptr(), self._stream()))
+        return out
+
+    def encoder_stash_raw(self, idx):
+        """hpe_debug_encoder_stash_raw: layer idx's raw output conv(x, W) + b of the last ``bn="batch"`` forward, over that call's batch"""
+        B = self.lib.hpe_debug_encoder_stash_batch(self._h)
+        if B < 1:
+            raise _lib.HpeError("encoder_stash_raw: no training forward has run")
+        s = CONV_SPECS[idx]
+        out = self._new(B, s.hout, s.hout, s.cout)
+        _lib.check(self.lib.hpe_debug_encoder_stash_raw(self._h, idx, out.data_ptr(), self._stream()))
+        return out
+
+    def debug_conv_batchnorm(self, idx, x, residual=None, relu=True):
+        """hpe_debug_conv_batchnorm: one layer with batch statistics -> (y, z, stats [2 * cout] = mu | var)"""
+        s = CONV_SPECS[idx]
+        x = _require_cuda_tensor(x, "x")
+        B = x.shape[0]
+        y, z, st = self._new(B, s.hout, s.hout, s.cout), self._new(B, s.hout, s.hout, s.cout), self._new(2 * s.cout)
+        r = _require_cuda_tensor(residual, "residual").data_ptr() if residual is not None else None
+        _lib.check(self.lib.hpe_debug_conv_batchnorm(self._h, idx, x.data_ptr(), B, r, int(relu), y.data_ptr(), z.data_ptr(), st.data_ptr(),
+                                                     self._stream()))
+        return y, z, st
+
+    def debug_conv_backward_batchnorm(self, idx, x, z, y, dy, want_dx=True):
+        """hpe_debug_conv_backward_batchnorm: one layer's gate, BatchNorm backward, weight and data gradient from its raw output z and
+        its activated output y (None: no activation) -> (dx or None, grad_layer = [kernel | bias = 0 | gamma | beta] flat)"""
+        s = CONV_SPECS[idx]
+        x, z, dy = _require_cuda_tensor(x, "x"), _require_cuda_tensor(z, "z"), _require_cuda_tensor(dy, "dy")
+        y = _require_cuda_tensor(y, "y") if y is not None else None
+        B = x.shape[0]
+        want_dx = want_dx and idx != 0
+        dx = self._new(B, s.hin, s.hin, s.cin) if want_dx else None
+        gl = self._new(s.kh * s.kw * s.cin * s.cout + 3 * s.cout)
+        _lib.check(self.lib.hpe_debug_conv_backward_batchnorm(self._h, idx, x.data_ptr(), z.data_ptr(), y.data_ptr() if y is not None else None,
+                                                              dy.data_ptr(), B, dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
+        return dx, gl
 
     def encoder_params(self):
         """hpe_encoder_get_params: the live kernels, biases, gammas and betas as one flat CUDA tensor [resnet_spec.ENCODER_PARAM_FLOATS]"""
@@ -690,24 +768,28 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_debug_encoder_packing(self._h, int(idx), int(which), out.data_ptr(), self._stream()))
         return out
 
-    def encoder_forward_train(self, images):
-        """hpe_encoder_forward_train: images [B,224,224,3] -> features [B,2048], layer by layer, every activation kept in the stash"""
+    def encoder_forward_train(self, images, bn="frozen"):
+        """hpe_encoder_forward_train: images [B,224,224,3] -> features [B,2048], layer by layer, every activation kept in the stash.
+        bn="batch" (hpe_encoder_forward_batchnorm): every BatchNorm normalises with the statistics of this batch."""
+        fn = self.lib.hpe_encoder_forward_batchnorm if self._bn_mode(bn) else self.lib.hpe_encoder_forward_train
         images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))
         B = images.shape[0]
         out = self._new(B, 2048)
-        _lib.check(self.lib.hpe_encoder_forward_train(self._h, images.data_ptr(), B, out.data_ptr(), self._stream()))
+        _lib.check(fn(self._h, images.data_ptr(), B, out.data_ptr(), self._stream()))
         return out
 
-    def encoder_backward(self, images, grad_features):
+    def encoder_backward(self, images, grad_features, bn="frozen"):
         """hpe_encoder_backward: the gradient of sum(grad_features * features) with respect to the flat encoder parameters.  Stateless
-        (the training forward runs again); same inputs, same bits."""
+        (the training forward runs again); same inputs, same bits.  bn="batch" (hpe_encoder_backward_batchnorm): through the batch
+        statistics; the bias slots are 0."""
+        fn = self.lib.hpe_encoder_backward_batchnorm if self._bn_mode(bn) else self.lib.hpe_encoder_backward
         images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))
         B = images.shape[0]
         grad_features = _require_cuda_tensor(grad_features.detach(), "grad_features")
         if tuple(grad_features.shape) != (B, 2048):
             raise ValueError("grad_features must be [%d,2048], got %s" % (B, tuple(grad_features.shape)))
         g = self._new(ENCODER_PARAM_FLOATS)
-        _lib.check(self.lib.hpe_encoder_backward(self._h, images.data_ptr(), B, grad_features.data_ptr(), g.data_ptr(), self._stream()))
+        _lib.check(fn(self._h, images.data_ptr(), B, grad_features.data_ptr(), g.data_ptr(), self._stream()))
         return g
 
     def debug_conv_backward(self, idx, x, y, dy, want_dx=True):

@@ -5,7 +5,9 @@ hpe_regressor_backward), an Adam step and the new weights back into the engine o
 torch.optim.Adam on ONE flat tensor; everything else runs in libhpe_hip.so.  With ``train_encoder=True`` the encoder (BatchNorm statistics
 fixed, fp32) is in the same step, as in the reference (src/trainer.py:481): features come from ``encoder_features``, the one
 ``.backward()`` fills both flat gradients, a second Adam steps the encoder's flat tensor and ``set_encoder_params_dev`` installs it on the device, in stream order
-(hpe_encoder_set_params_dev).
+(hpe_encoder_set_params_dev).  ``encoder_bn="batch"`` is the reference's own mode (src/trainer.py:386, training=True): every BatchNorm
+normalises with the statistics of the batch, the gradient flows through them, and after the Adam steps the moving statistics follow the
+batch (hpe_encoder_update_stats on ``encoder_stats``, installed by hpe_encoder_set_stats_dev).
 ``grad_features`` is returned either way."""
 from __future__ import annotations
 
@@ -17,12 +19,16 @@ ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon
 
 class GeneratorTrainer(object):
     def __init__(self, engine, lr=GENERATOR_LR, betas=(0.9, 0.999), eps=ADAM_EPS, kpr_loss_weight=60.0, mr_loss_weight=0.001,
-                 critic_loss_weight=0.01, dropout=0.5, generator=None, train_encoder=False, encoder_lr=None):
+                 critic_loss_weight=0.01, dropout=0.5, generator=None, train_encoder=False, encoder_lr=None, encoder_bn="frozen",
+                 bn_momentum=0.99, bn_unbiased=True):
         """engine: a finalized HpeEngine with a regressor, mean theta and SMPL (and a critic, for the critic term).  ``params`` is the
         flat parameter tensor (regressor_spec.flat_layout) the optimiser owns; ``regressor_spec.flat_to_params(params)`` gives the
         dict ``load_regressor`` / ``load_mean_theta`` take.  generator: the torch.Generator of the dropout draws.  train_encoder: also
         step the encoder's flat tensor ``encoder_params`` (needs ``engine.reserve_encoder_train(B)``; Adam with the same
-        hyper-parameters, lr ``encoder_lr``, default the generator's) whenever ``step`` is given images."""
+        hyper-parameters, lr ``encoder_lr``, default the generator's) whenever ``step`` is given images.  encoder_bn: "frozen" (the
+        moving statistics stay fixed) or "batch" (needs ``engine.reserve_encoder_train(B, batch_norm=True)``): batch statistics in the
+        forward and the backward, and ``encoder_stats``, the flat statistics tensor (resnet_spec.stats_to_params), moves with momentum
+        ``bn_momentum`` after every step (``bn_unbiased``: the batch variance times M / (M - 1))."""
         import torch
 
         if not 0.0 <= dropout < 1.0:
@@ -34,7 +40,14 @@ class GeneratorTrainer(object):
         self.params = engine.regressor_params().requires_grad_(True)
         self.optimizer = torch.optim.Adam([self.params], lr=lr, betas=betas, eps=eps)
         self.train_encoder = bool(train_encoder)
-        self.encoder_params = self.encoder_optimizer = None
+        if encoder_bn not in ("frozen", "batch"):
+            raise ValueError("encoder_bn must be 'frozen' or 'batch'")
+        if not 0.0 <= bn_momentum <= 1.0:
+            raise ValueError("bn_momentum must be in [0, 1]")
+        self.encoder_bn, self.bn_momentum, self.bn_unbiased = encoder_bn, float(bn_momentum), bool(bn_unbiased)
+        self.encoder_params = self.encoder_optimizer = self.encoder_stats = None
+        if self.train_encoder and encoder_bn == "batch":
+            self.encoder_stats = engine.encoder_stats()
         if self.train_encoder:
             self.encoder_params = engine.encoder_params().requires_grad_(True)
             self.encoder_optimizer = torch.optim.Adam([self.encoder_params], lr=lr if encoder_lr is None else encoder_lr, betas=betas, eps=eps)
@@ -74,7 +87,7 @@ class GeneratorTrainer(object):
             use_critic = eng.has_critic
         enc = self.train_encoder and x.dim() == 4
         if enc:
-            features = encoder_features(eng, x, self.encoder_params)
+            features = encoder_features(eng, x, self.encoder_params, self.encoder_bn)
             features.retain_grad()
         else:
             with torch.no_grad():
@@ -113,6 +126,9 @@ class GeneratorTrainer(object):
         if enc:
             self.encoder_optimizer.step()
             eng.set_encoder_params_dev(self.encoder_params)
+            if self.encoder_bn == "batch":
+                eng.update_encoder_stats(self.encoder_stats, self.bn_momentum, self.bn_unbiased)
+                eng.set_encoder_stats_dev(self.encoder_stats)
         det = lambda ts: [t.detach() for t in ts]  # noqa: E731
         return {"kpr_losses": det(kpr), "mr_losses": det(mr), "generator_critic_losses": det(gc), "pred_keypoints": pred_kp,
                 "generated_cams": thetas[S - 1, :, :3].detach(), "thetas": [thetas[i].detach() for i in range(S)],

@@ -61,12 +61,13 @@ def generator_critic_loss(engine, joints, shapes, Rs, return_parts=False):
     return -scores.mean(0).sum()
 
 
-def encoder_features(engine, images, params):
+def encoder_features(engine, images, params, bn="frozen"):
     """features [B,2048] of the engine's encoder (layer by layer, BatchNorm statistics fixed), differentiable in ``params``, the flat
-    tensor [resnet_spec.ENCODER_PARAM_FLOATS] that must equal ``engine.encoder_params()``; needs ``engine.reserve_encoder_train(B)``"""
+    tensor [resnet_spec.ENCODER_PARAM_FLOATS] that must equal ``engine.encoder_params()``; needs ``engine.reserve_encoder_train(B)``.
+    bn="batch": BatchNorm with the statistics of this batch, the gradient through them (``reserve_encoder_train(B, batch_norm=True)``)"""
     from .autograd import EncoderFunction
 
-    return EncoderFunction.apply(engine, images, params)
+    return EncoderFunction.apply(engine, images, params, bn)
 
 
 def regressor_thetas(engine, features, params, drop=None):

@@ -104,6 +104,52 @@ def flat_to_params(flat, stats):
     return out
 
 
+# ---- the layout of the moving statistics (include/hpe.h: hpe_encoder_stat_offset): moving_mean of every layer, then moving_variance of
+# every layer, both in table order
+ENCODER_STAT_CHANNELS = sum(s.cout for s in CONV_SPECS)
+ENCODER_STAT_FLOATS = 2 * ENCODER_STAT_CHANNELS
+
+
+def encoder_stat_offsets():
+    """[(moving_mean offset, moving_variance offset)] per layer"""
+    offs, o = [], 0
+    for s in CONV_SPECS:
+        offs.append((o, ENCODER_STAT_CHANNELS + o))
+        o += s.cout
+    return offs
+
+
+ENCODER_STAT_OFFSETS = encoder_stat_offsets()
+
+
+def params_to_stats(params):
+    """the dict ``load_encoder`` takes -> its moving statistics as the flat float32 array of ``HpeEngine.encoder_stats``"""
+    import numpy as np
+
+    out = np.empty(ENCODER_STAT_FLOATS, np.float32)
+    for s, (om, ov) in zip(CONV_SPECS, ENCODER_STAT_OFFSETS):
+        out[om:om + s.cout] = np.asarray(params[s.bn_name + "/moving_mean"], np.float32).reshape(-1)
+        out[ov:ov + s.cout] = np.asarray(params[s.bn_name + "/moving_variance"], np.float32).reshape(-1)
+    return out
+
+
+def stats_to_params(stats):
+    """the flat statistics (array or CPU/CUDA tensor) -> {bn_name/moving_mean, bn_name/moving_variance}: what ``flat_to_params`` takes as
+    its ``stats``, so ``flat_to_params(trainer.encoder_params, stats_to_params(trainer.encoder_stats))`` is a trained encoder, whole"""
+    import numpy as np
+
+    if hasattr(stats, "detach"):
+        stats = stats.detach().cpu().numpy()
+    stats = np.asarray(stats, np.float32).reshape(-1)
+    if stats.size != ENCODER_STAT_FLOATS:
+        raise ValueError("stats must hold %d floats, got %d" % (ENCODER_STAT_FLOATS, stats.size))
+    out = {}
+    for s, (om, ov) in zip(CONV_SPECS, ENCODER_STAT_OFFSETS):
+        out[s.bn_name + "/moving_mean"] = stats[om:om + s.cout].copy()
+        out[s.bn_name + "/moving_variance"] = stats[ov:ov + s.cout].copy()
+    return out
+
+
 def encoder_macs_per_image():
     return sum(s.kh * s.kw * s.cin * s.cout * s.hout * s.hout for s in CONV_SPECS)
 

@@ -435,6 +435,60 @@ int hpe_debug_encoder_stash(hpe_ctx* ctx, int idx, float* out_dev, void* stream)
 /* The batch of the last training forward, i.e. the images hpe_debug_encoder_stash copies (0: none has run). */
 int hpe_debug_encoder_stash_batch(hpe_ctx* ctx);
 
+/* -- encoder training with batch statistics: BatchNorm in training mode (src/trainer.py:386, image_feature_extractor(images, training=True)) --
+ * fp32 contexts only.  Per layer, M = B * hout * hout rows:  z = conv(x, W) + b,  mu = mean_m z,  var = mean_m (z - mu)^2 (biased),
+ * r = 1 / sqrt(var + eps),  xhat = (z - mu) * r,  y = act(gamma * xhat + beta (+ residual)).  Backward:  dz = dy * [y > 0] (a projection
+ * shortcut: dz = dy),  dbeta = sum_m dz,  dgamma = sum_m dz * xhat,  dzraw = gamma * r * (dz - dbeta / M - xhat * dgamma / M),
+ * dW = A^T dzraw,  dx = dzraw . W^T;  the bias gradient is written as exactly 0 (the bias cancels in z - mu).  The sums are accumulated in
+ * double in a fixed order, no atomics: the same inputs give the same bits.  The frozen-statistics calls above are untouched by all of this.
+ * The moving statistics as ONE fp32 tensor of hpe_encoder_stat_floats() = 2 * (channels of all layers) floats: moving_mean of every layer in
+ * table order, then moving_variance of every layer in table order.  hpe_encoder_stat_offset(idx, which): the first float of layer idx's
+ * mean (which 0) or variance (1); -1 otherwise.  Host code: no device is needed. */
+int hpe_encoder_stat_floats(void);
+int hpe_encoder_stat_offset(int idx, int which);
+/* hpe_encoder_train_reserve_batchnorm: hpe_encoder_train_reserve(ctx, B) if that has not run, then, once and outside any capture, what the
+ * batch-statistics calls need beyond it: a stash of every layer's raw output z (about 11 M floats per image), the batch statistics, the
+ * installed moving statistics and the reduction partials.  hpe_encoder_train_ws_floats_batchnorm(B): the floats of both reserves together.
+ * A context that only calls hpe_encoder_train_reserve does not grow.  A second call with a B not above the first is a no-op; a larger one
+ * is refused (HPE_ERR_STATE).
+ * Every call below returns HPE_ERR_STATE before this reserve. */
+int hpe_encoder_train_reserve_batchnorm(hpe_ctx* ctx, int B);
+long long hpe_encoder_train_ws_floats_batchnorm(int B);
+/* hpe_encoder_forward_train / hpe_encoder_backward with batch statistics.  Each layer runs the convolution launch of the frozen forward
+ * with a unit scale and the bias as shift, the two statistics launches and one elementwise launch; both calls keep y AND z of every layer
+ * and the batch statistics of every layer (what hpe_encoder_update_stats reads).  The backward runs its own forward again and writes the
+ * flat layout of hpe_encoder_backward (every bias slot 0).  No allocation, no synchronisation, capturable on one stream; the workspace
+ * sharing of hpe_encoder_backward applies.  HPE_ERR_INVALID for NULL pointers or B outside [1, batch of the batch-norm reserve]. */
+int hpe_encoder_forward_batchnorm(hpe_ctx* ctx, const float* images_dev, int B, float* features_dev, void* stream);
+int hpe_encoder_backward_batchnorm(hpe_ctx* ctx, const float* images_dev, int B, const float* grad_features_dev, float* grad_flat_dev, void* stream);
+/* The moving statistics as installed (as loaded, until hpe_encoder_set_stats_dev), one device copy on `stream`. */
+int hpe_encoder_get_stats(hpe_ctx* ctx, float* stats_dev, void* stream);
+/* stats_dev <- momentum * stats_dev + (1 - momentum) * batch, in place on the caller's tensor, from the batch statistics of the last
+ * hpe_encoder_forward_batchnorm / hpe_encoder_backward_batchnorm (HPE_ERR_STATE if there has been none); unbiased != 0 multiplies each
+ * batch variance by M / (M - 1), M = that call's B * hout * hout of the layer.  In double, one rounding.  One launch, capturable.
+ * Keras' momentum is 0.99.  HPE_ERR_INVALID for a momentum outside [0, 1].  It installs nothing: hpe_encoder_set_stats_dev does. */
+int hpe_encoder_update_stats(hpe_ctx* ctx, float* stats_dev, double momentum, int unbiased, void* stream);
+/* Install stats_dev as the moving statistics, in stream order: the per-channel mean, sqrt(var + eps) (double, correctly rounded) and its
+ * reciprocal are rewritten, then the two repack launches that fold them (BatchNorm scale / shift, the dual-source weights where the
+ * context holds them) run again from the live flat parameters.  No host work, no synchronisation, capturable; the ordering rules of
+ * hpe_encoder_set_params_dev apply.  After hpe_encoder_set_params_dev(q) and hpe_encoder_set_stats_dev(t), in either order, every packing
+ * equals, byte for byte, that of a fresh context that loaded (q, t).  hpe_encoder_set_params (the host path) folds the installed statistics. */
+int hpe_encoder_set_stats_dev(hpe_ctx* ctx, const float* stats_dev, void* stream);
+/* One layer in batch-statistics mode for tests: z_out_dev [B,hout,hout,cout] the raw output, y_dev the activated one, stats_out_dev
+ * [2 * cout] = mu | var of this call.  The backward takes z_dev and y_dev (NULL: no activation, dz = dy) as inputs, recomputes the batch
+ * statistics from z_dev, and fills grad_layer_dev = [kernel | bias = 0 | gamma | beta] and dx_dev (NULL: not computed; NULL for idx 0).
+ * Neither touches the statistics of the last whole-network call.  Device pointers are 16-byte aligned. */
+int hpe_debug_conv_batchnorm(hpe_ctx* ctx, int idx, const float* x_dev, int B, const float* residual_dev, int relu, float* y_dev, float* z_out_dev,
+                             float* stats_out_dev, void* stream);
+int hpe_debug_conv_backward_batchnorm(hpe_ctx* ctx, int idx, const float* x_dev, const float* z_dev, const float* y_dev, const float* dy_dev, int B,
+                                      float* dx_dev, float* grad_layer_dev, void* stream);
+/* Layer idx's raw output z of the last batch-statistics forward (B images of it), and mu | var of all layers of that forward in the
+ * statistics layout; HPE_ERR_STATE if none has run. */
+int hpe_debug_encoder_stash_raw(hpe_ctx* ctx, int idx, float* out_dev, void* stream);
+int hpe_debug_encoder_batch_stats(hpe_ctx* ctx, float* out_dev, void* stream);
+/* For tests: the pixel slices the column sums of layer idx are cut into at batch B (host code; -1 for an idx or B out of range). */
+int hpe_debug_encoder_bn_slices(int idx, int B);
+
 /* Both reprojection losses of all n_stage IEF stages in ONE call -- what Trainer.val_step evaluates per step
  * (src/trainer.py:274-296): the work that depends only on seg_gts (tf.where compaction, src/trainer.py:291;
  * the silhouette bitmap) is done once per call instead of once per stage.

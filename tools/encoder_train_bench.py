@@ -6,7 +6,12 @@ in torch fp32 with autograd in the same process.  Prints one JSON line and write
 Timing: device events around `iters` back-to-back calls after 3 warm-up calls, median of 5 such groups (the backward, torch and the device
 update alike; the host update is wall time over 3 calls); torch's TF32 paths are off.  `set_params_dev_bytes_written` is what one device
 update writes at the default plan (every packing the context holds, from hpe_debug_encoder_packing_bytes), `set_params_dev_write_GBps`
-those bytes over the measured time."""
+those bytes over the measured time.
+
+    python tools/encoder_train_bench.py --bn batch [--out profiles/encoder_bn_train_bench.json]
+
+The batch-statistics leg, same method: ms per hpe_encoder_backward_batchnorm, per frozen hpe_encoder_backward in the same run, per
+hpe_encoder_update_stats + hpe_encoder_set_stats_dev, against torch fp32 autograd of the same ResNet-50 with F.batch_norm(training=True)."""
 import argparse
 import json
 import os
@@ -44,8 +49,8 @@ def timed(fn, iters):
 class TorchResNet(object):
     """the same function in torch: NCHW conv2d + the folded affine of the fixed statistics + ReLU; gradients to W, b, gamma, beta"""
 
-    def __init__(self, params, eps=1e-3):
-        self.layers = []
+    def __init__(self, params, eps=1e-3, batch_norm=False):
+        self.layers, self.eps, self.batch_norm = [], eps, batch_norm
         for s in CONV_SPECS:
             t = lambda k: torch.from_numpy(np.asarray(params[k], np.float32)).cuda()  # noqa: E731
             W = t(s.name + "/kernel").permute(3, 2, 0, 1).contiguous().requires_grad_(True)
@@ -56,6 +61,12 @@ class TorchResNet(object):
 
     def conv(self, i, x, res=None, relu=True):
         s, W, b, gamma, beta, mean, istd = self.layers[i]
+        if self.batch_norm:  # BatchNorm in training mode: the statistics of the batch, the gradient through them
+            z = F.conv2d(x, W, bias=b, stride=s.stride, padding=(s.kh - 1) // 2)
+            y = F.batch_norm(z, None, None, gamma, beta, training=True, eps=self.eps)
+            if res is not None:
+                y = y + res
+            return torch.relu(y) if relu else y
         z = F.conv2d(x, W, stride=s.stride, padding=(s.kh - 1) // 2)
         y = (gamma * istd).view(1, -1, 1, 1) * (z + (b - mean).view(1, -1, 1, 1)) + beta.view(1, -1, 1, 1)
         if res is not None:
@@ -84,8 +95,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="8,32,64")
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "encoder_train_bench.json"))
+    ap.add_argument("--bn", choices=("frozen", "batch"), default="frozen")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--trace-calls", type=int, default=0,
+                    help="run only this many backward calls of the chosen mode at the first batch and exit: the workload of a rocprofv3 --kernel-trace --stats run")
     a = ap.parse_args()
+    bn = a.bn == "batch"
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "encoder_bn_train_bench.json" if bn else "encoder_train_bench.json")
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
     batches = [int(b) for b in a.batches.split(",")]
@@ -93,8 +110,16 @@ def main():
     eng = hpe_amd.HpeEngine(device=0, max_batch=max(batches))
     eng.load_encoder(params)
     eng.finalize()
-    eng.reserve_encoder_train(max(batches))
-    ref = TorchResNet(params)
+    eng.reserve_encoder_train(max(batches), batch_norm=bn)
+    if a.trace_calls:
+        img = torch.from_numpy(synthetic.make_images(batches[0], seed=1)).cuda()
+        gf = torch.randn(batches[0], 2048, device="cuda")
+        for _ in range(a.trace_calls):
+            eng.encoder_backward(img, gf, bn=a.bn)
+        torch.cuda.synchronize()
+        eng.close()
+        return
+    ref = TorchResNet(params, batch_norm=bn)
     flat_dev = eng.encoder_params()
     flat = flat_dev.cpu()
     written = sum(eng.lib.hpe_debug_encoder_packing_bytes(eng._h, i, w) for i in range(len(CONV_SPECS)) for w in range(len(_lib.ENCODER_PACKINGS)))
@@ -102,6 +127,15 @@ def main():
     for B in batches:
         img = torch.from_numpy(synthetic.make_images(B, seed=1)).cuda()
         gf = torch.randn(B, 2048, device="cuda")
+        if bn:
+            stats = eng.encoder_stats()
+            hip = timed(lambda: eng.encoder_backward(img, gf, bn="batch"), a.iters)
+            frozen = timed(lambda: eng.encoder_backward(img, gf), a.iters)
+            tch = timed(lambda: ref.backward(img, gf), a.iters)
+            upd = timed(lambda: eng.set_encoder_stats_dev(eng.update_encoder_stats(stats, 1.0)), a.iters)  # momentum 1: the statistics stay
+            res["rows"].append({"B": B, "hpe_encoder_backward_batchnorm_ms": round(hip, 3), "hpe_encoder_backward_ms": round(frozen, 3),
+                                "torch_autograd_batchnorm_fwd_bwd_ms": round(tch, 3), "update_and_set_stats_dev_ms": round(upd, 3)})
+            continue
         hip = timed(lambda: eng.encoder_backward(img, gf), a.iters)
         tch = timed(lambda: ref.backward(img, gf), a.iters)
         t0 = time.perf_counter()
