@@ -90,6 +90,19 @@ class HpeAugmentFrame(C.Structure):
                 ("inside", C.c_int), ("rx", C.c_float), ("ry", C.c_float)]
 
 
+class HpeJpegInfo(C.Structure):
+    """what hpe_jpeg_info fills per stream (include/hpe.h), 72 bytes"""
+    _fields_ = [("status", C.c_int), ("H", C.c_int), ("W", C.c_int), ("ncomp", C.c_int), ("hs", C.c_int * 3), ("vs", C.c_int * 3),
+                ("blocks_w", C.c_int * 3), ("blocks_h", C.c_int * 3), ("coefs", C.c_longlong)]
+
+
+class HpeJpegImage(C.Structure):
+    """one table entry of hpe_jpeg_decode / hpe_jpeg_backend (include/hpe.h), 304 bytes"""
+    _fields_ = [("coef_offset", C.c_longlong * 3), ("plane_offset", C.c_longlong * 3), ("out_offset", C.c_longlong), ("H", C.c_int),
+                ("W", C.c_int), ("ncomp", C.c_int), ("channels", C.c_int), ("hmax", C.c_int), ("vmax", C.c_int), ("blocks_w", C.c_int * 3),
+                ("blocks_h", C.c_int * 3), ("idct_group0", C.c_int), ("store_group0", C.c_int), ("quant", C.c_ubyte * 192)]
+
+
 GEMM_DENSE, GEMM_STRIDED, GEMM_CONV3, GEMM_DUAL = 0, 1, 2, 4  # HpeDebugGemm.mode
 GEMM_TILES = ((128, 128), (128, 64), (64, 64), (64, 128), (128, 128), (128, 64), (256, 128))  # (BM, BN) of tile 0..6; 4..6 run 8 waves
 
@@ -162,6 +175,10 @@ _PROTOS = {
                                           C.c_void_p, C.c_void_p]),
     "hpe_augment_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_augment_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_jpeg_info": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_jpeg_decode": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_jpeg_backend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
+                                   C.c_void_p]),
     "hpe_get_original": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_kp_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_kp_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

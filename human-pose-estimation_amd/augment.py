@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .jpeg import DecodedBatch
 
 IMG_SIZE = 224
 NUM_KP = 19
@@ -99,6 +100,11 @@ def _pack(items, channels, name):
     tail = "[H,W,3]" if channels else "[H,W]"
     as_t = lambda f: torch.as_tensor(np.ascontiguousarray(f) if isinstance(f, np.ndarray) else f)  # noqa: E731
     nd = 3 if channels else 2
+    if isinstance(items, DecodedBatch):  # decode_jpeg_batch's buffer is this packing already
+        if items.channels != (channels or 1):
+            raise ValueError("%s must be decoded with %d channel(s)" % (name, channels or 1))
+        total = int(items.offsets[-1] + (items.sizes[-1, 0] * items.sizes[-1, 1] * items.channels + 15) // 16 * 16)
+        return items.buffer, items.sizes, items.offsets, total
     if isinstance(items, (list, tuple)):
         ts = [as_t(f) for f in items]
         if not ts:
@@ -139,8 +145,9 @@ def augment_batch(frames, segs, kp, centers, draws=None, generator=None, trans_m
     thresholded: the mesh loss takes > 0), kp_gt [B,19,3] (x, y in [-1,1], visibility; invisible rows 0)) as CUDA float32 -- what
     ``GeneratorTrainer.step(images, kp_gt, seg_gts=seg_gts)`` takes.
 
-    frames / segs: lists of uint8 [H_i,W_i,3] / [H_i,W_i] arrays or tensors (host or device; packed into one device buffer each here), or
-    single uint8 tensors [B,H,W,3] / [B,H,W].  kp [B,19,3] (x, y, visibility in source pixels; host or device), centers int [B,2]
+    frames / segs: lists of uint8 [H_i,W_i,3] / [H_i,W_i] arrays or tensors (host or device; packed into one device buffer each here),
+    single uint8 tensors [B,H,W,3] / [B,H,W], or ``decode_jpeg_batch``'s ``DecodedBatch`` (3 / 1 channels), whose buffer and offsets are
+    used as they are.  kp [B,19,3] (x, y, visibility in source pixels; host or device), centers int [B,2]
     (x, y; host).  draws: ``draw_augmentation``'s dict (host), drawn here with ``generator`` when None.  A sample whose window leaves
     the padded frame is a ValueError unless ``clamp`` (``plan_augmentation``).  out: an optional (images, seg_gts, kp_gt) triple of
     preallocated contiguous float32 CUDA tensors.  Nothing reads the device; the table goes up from pinned memory without blocking."""

@@ -1,0 +1,198 @@
+"""The reference's training files without TensorFlow: ``*.tfrecords`` framing, ``tf.train.Example`` protos and the two parsers of
+src/util/data_utils.py (``parse_example_proto`` :11-69, ``parse_mocap_example`` :109-127), plus ``load_training_batch``, the path from
+parsed records to what ``GeneratorTrainer.step`` takes (src/data_loader.py:87-93, 160-213).  Everything but ``load_training_batch`` is
+host code.  CRC-32C, varints and the protobuf wire format are those of tf_checkpoint.py."""
+from __future__ import annotations
+
+import os
+import struct
+
+import numpy as np
+
+from .tf_checkpoint import CheckpointError, _proto_fields, _signed64, _varint, crc32c, mask_crc
+
+NUM_KP = 19
+
+
+class RecordError(ValueError):
+    pass
+
+
+def read_tfrecords(path_or_paths, verify=True):
+    """Yield the payload of every record of one file or of several, in order.  Framing: uint64 length (LE), uint32 masked CRC-32C of
+    the 8 length bytes, payload, uint32 masked CRC-32C of the payload.  A bad CRC, a truncated header or payload, or a length beyond
+    the file raises RecordError with the file name and the record index.  verify=False skips the payload CRC only."""
+    paths = [path_or_paths] if isinstance(path_or_paths, (str, bytes, os.PathLike)) else list(path_or_paths)
+    for path in paths:
+        name = os.fspath(path)
+        with open(path, "rb") as f:
+            size = os.fstat(f.fileno()).st_size
+            idx = 0
+            while True:
+                at = "%s: record %d: " % (name, idx)
+                head = f.read(12)
+                if not head:
+                    break
+                if len(head) < 12:
+                    raise RecordError(at + "truncated header (%d of 12 bytes)" % len(head))
+                length, len_crc = struct.unpack("<QI", head)
+                if mask_crc(crc32c(head[:8])) != len_crc:
+                    raise RecordError(at + "the CRC of the length does not match")
+                if length + 4 > size - f.tell():
+                    raise RecordError(at + "a payload of %d bytes runs past the end of the file (truncated?)" % length)
+                body = f.read(length + 4)
+                payload = body[:length]
+                if verify and mask_crc(crc32c(payload)) != struct.unpack("<I", body[length:])[0]:
+                    raise RecordError(at + "the CRC of the payload does not match")
+                yield payload
+                idx += 1
+
+
+def _feature(buf):
+    """one tf.train.Feature -> list[bytes] | float32 array | int64 array"""
+    kind, out = None, []
+    for fn, wt, v in _proto_fields(buf):
+        if fn not in (1, 2, 3) or wt != 2:
+            continue
+        kind = fn
+        for vfn, vwt, vv in _proto_fields(v):
+            if vfn != 1:
+                continue
+            if fn == 1 and vwt == 2:
+                out.append(vv)
+            elif fn == 2 and vwt == 2:  # packed
+                if len(vv) % 4:
+                    raise RecordError("a packed float list of %d bytes" % len(vv))
+                out.extend(np.frombuffer(vv, "<f4").tolist())
+            elif fn == 2 and vwt == 5:
+                out.append(struct.unpack("<f", struct.pack("<I", vv))[0])
+            elif fn == 3 and vwt == 2:  # packed varints
+                pos = 0
+                while pos < len(vv):
+                    x, pos = _varint(vv, pos)
+                    out.append(_signed64(x & 0xFFFFFFFFFFFFFFFF))
+            elif fn == 3 and vwt == 0:
+                out.append(_signed64(vv & 0xFFFFFFFFFFFFFFFF))
+            else:
+                raise RecordError("a list value with wire type %d" % vwt)
+    if kind == 2:
+        return np.array(out, np.float32)
+    if kind == 3:
+        return np.array(out, np.int64)
+    return out
+
+
+def parse_example(payload):
+    """A serialized tf.train.Example -> {name: float32 array | int64 array | list[bytes]}.  Example.features = 1, Features.feature = 1
+    is the map (entry key 1, value 2); Feature: bytes_list = 1, float_list = 2, int64_list = 3, each list's value = 1, packed or not.
+    Unknown fields are skipped; a key that appears twice takes the last value, as protobuf maps do."""
+    out = {}
+    try:
+        for fn, wt, features in _proto_fields(payload):
+            if fn != 1 or wt != 2:
+                continue
+            for efn, ewt, entry in _proto_fields(features):
+                if efn != 1 or ewt != 2:
+                    continue
+                key, value = None, b""
+                for kfn, kwt, kv in _proto_fields(entry):
+                    if kfn == 1 and kwt == 2:
+                        key = kv
+                    elif kfn == 2 and kwt == 2:
+                        value = kv
+                if key is not None:
+                    out[key.decode("utf-8")] = _feature(value)
+    except RecordError:
+        raise
+    except (CheckpointError, UnicodeError, struct.error, OverflowError) as e:
+        raise RecordError("corrupt Example: %s" % e) from e
+    return out
+
+
+def _need(feats, key, kind, count):
+    if key not in feats:
+        raise RecordError("the record lacks '%s'" % key)
+    v = feats[key]
+    ok = isinstance(v, list) if kind == "bytes" else isinstance(v, np.ndarray) and v.dtype == (np.float32 if kind == "float" else np.int64)
+    if not ok or len(v) != count:
+        raise RecordError("'%s' must hold %d %s value(s), got %d %s" % (key, count, kind, len(v), "bytes" if isinstance(v, list) else v.dtype))
+    return v
+
+
+def parse_image_example(payload):
+    """``parse_example_proto`` without the decode: {'image', 'seg': JPEG bytes, 'height', 'width': int, 'center': int64 [2] (x, y),
+    'filename': bytes, 'kp': float32 [19,3]}.  kp is the 14 image/x, image/y, image/visibility columns followed by image/face_pts
+    reshaped [3,5] (all zeros when the record has none: the reference's default).  A missing key or a wrong length raises RecordError
+    naming the key."""
+    f = parse_example(payload)
+    label = np.zeros((3, NUM_KP), np.float32)
+    label[0, :14] = _need(f, "image/x", "float", 14)
+    label[1, :14] = _need(f, "image/y", "float", 14)
+    label[2, :14] = _need(f, "image/visibility", "int64", 14).astype(np.float32)
+    if "image/face_pts" in f:
+        label[:, 14:] = _need(f, "image/face_pts", "float", 15).reshape(3, 5)
+    return {"image": _need(f, "image/encoded", "bytes", 1)[0], "seg": _need(f, "image/seg_gt", "bytes", 1)[0],
+            "height": int(_need(f, "image/height", "int64", 1)[0]), "width": int(_need(f, "image/width", "int64", 1)[0]),
+            "center": _need(f, "image/center", "int64", 2).copy(), "filename": _need(f, "image/filename", "bytes", 1)[0],
+            "kp": np.ascontiguousarray(label.T)}
+
+
+def parse_mocap_example(payload):
+    """-> (pose float32 [72], shape float32 [10])"""
+    f = parse_example(payload)
+    return _need(f, "pose", "float", 72).copy(), _need(f, "shape", "float", 10).copy()
+
+
+class RecordDataset:
+    """Batches of parsed records from one or several files: iterating yields lists of ``batch_size`` values of ``parse`` (default
+    ``parse_image_example``).  With ``shuffle_seed`` the records are read once and every pass walks a new permutation, drawn from
+    RandomState(shuffle_seed + pass); without it the files are streamed in order.  Host-only: nothing is decoded here."""
+
+    def __init__(self, paths, batch_size, shuffle_seed=None, drop_last=True, parse=parse_image_example, verify=True):
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        self.paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+        self.batch_size, self.shuffle_seed, self.drop_last, self.parse, self.verify = int(batch_size), shuffle_seed, bool(drop_last), parse, verify
+        self._payloads, self._pass = None, 0
+
+    def _ordered(self):
+        if self.shuffle_seed is None:
+            return read_tfrecords(self.paths, self.verify)
+        if self._payloads is None:
+            self._payloads = list(read_tfrecords(self.paths, self.verify))
+        order = np.random.RandomState(int(self.shuffle_seed) + self._pass).permutation(len(self._payloads))
+        self._pass += 1
+        return (self._payloads[i] for i in order)
+
+    def __iter__(self):
+        batch = []
+        for payload in self._ordered():
+            batch.append(self.parse(payload))
+            if len(batch) == self.batch_size:
+                yield batch
+                batch = []
+        if batch and not self.drop_last:
+            yield batch
+
+
+def load_training_batch(records, draws=None, generator=None, threads=None, **augment_args):
+    """Parsed image records (``parse_image_example`` dicts, or serialized payloads) -> the (images [B,224,224,3], seg_gts [B,224,224],
+    kp_gt [B,19,3]) CUDA triple that ``GeneratorTrainer.step`` takes: ``image`` decoded with 3 channels and ``seg`` with 1, one
+    ``decode_jpeg_batch`` each, then ``augment_batch`` on the decoded buffers as they are.  draws / generator / further keyword
+    arguments are ``augment_batch``'s.  A record whose streams do not have its height and width raises RecordError."""
+    from .augment import augment_batch
+    from .jpeg import DEFAULT_THREADS, decode_jpeg_batch
+
+    recs = [parse_image_example(r) if isinstance(r, (bytes, bytearray, memoryview)) else r for r in records]
+    if not recs:
+        raise ValueError("records is empty")
+    threads = DEFAULT_THREADS if threads is None else threads
+    frames = decode_jpeg_batch([r["image"] for r in recs], channels=3, threads=threads)
+    segs = decode_jpeg_batch([r["seg"] for r in recs], channels=1, threads=threads)
+    for i, r in enumerate(recs):
+        for what, d in (("image/encoded", frames), ("image/seg_gt", segs)):
+            if tuple(d.sizes[i]) != (r["height"], r["width"]):
+                raise RecordError("record %d: '%s' decodes to %s, the record says %s" % (i, what, d.sizes[i].tolist(), [r["height"], r["width"]]))
+    kp = np.stack([r["kp"] for r in recs]).astype(np.float32)
+    centers = np.stack([np.asarray(r["center"]) for r in recs]).astype(np.int32)
+    return augment_batch(frames, segs, kp, centers, draws=draws, generator=generator, **augment_args)

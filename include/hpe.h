@@ -548,6 +548,59 @@ int hpe_augment_batch(const unsigned char* frames_dev, const unsigned char* segs
                       const HpeAugmentFrame* table_dev, const float* kp_dev, int B, float* images_out, float* seg_out, float* kp_out,
                       void* stream);
 
+/* -- JPEG decode: tf.image.decode_jpeg(buf, channels) of the training records (src/util/data_utils.py:129-141) ---------------
+ * Baseline sequential DCT streams only (SOF0, 8-bit samples and quantisation tables, 1 or 3 components, luma sampling 1x1, 2x1 or
+ * 2x2 with 1x1 chroma, one interleaved scan, DRI / RST, any DHT).  Everything else is refused with HPE_ERR_INVALID and a message that
+ * names the image index and the clause.  Entropy decoding is host code (hpe_jpeg_info, hpe_jpeg_decode: no device needed);
+ * dequantisation, inverse DCT, chroma upsampling, colour conversion and the store are two launches (hpe_jpeg_backend).  What is
+ * computed is libjpeg's default decode (JDCT_ISLOW, fancy upsampling) in 32-bit integers, bit for bit: DESIGN.md "Training records and
+ * JPEG decode". */
+#define HPE_JPEG_MAX_SIDE 16384 /* larger frames are refused */
+typedef struct HpeJpegInfo {
+    int status;       /* HPE_OK, or HPE_ERR_INVALID: the stream is refused and every other field is 0 */
+    int H, W, ncomp;  /* ncomp 1 (grey) or 3 (YCbCr) */
+    int hs[3], vs[3]; /* sampling factors per component (a grey stream: 1, 1) */
+    int blocks_w[3], blocks_h[3]; /* block grid per component plane, padded to whole MCUs */
+    long long coefs;  /* int16 coefficients of all components: 64 * sum of blocks_w * blocks_h */
+} HpeJpegInfo;
+
+typedef struct HpeJpegImage {
+    long long coef_offset[3];  /* index of component c's first int16 in the coefficient buffer: natural order, 64 per block, blocks
+                                * row-major over [blocks_h, blocks_w] */
+    long long plane_offset[3]; /* byte offset of component c's uint8 sample plane [8 * blocks_h, 8 * blocks_w] in the workspace */
+    long long out_offset;      /* byte offset of the uint8 [H,W,channels] frame in the frame buffer, a multiple of 16 */
+    int H, W;
+    int ncomp;                 /* components stored: 1 (a grey stream, or channels == 1: Y alone) or 3 */
+    int channels;              /* 1 or 3 */
+    int hmax, vmax;            /* the stream's luma sampling: the chroma upsampling factors, and what pads every block grid to whole
+                                * MCUs (so also set when Y alone is stored; a grey stream has 1, 1) */
+    int blocks_w[3], blocks_h[3];
+    int idct_group0;           /* first workgroup of this image in launch one (32 blocks per workgroup) */
+    int store_group0;          /* first workgroup of this image in launch two (1024 output bytes per workgroup) */
+    unsigned char quant[3][64]; /* quantisation table per component, natural order */
+} HpeJpegImage;
+
+/* Info pass over B streams: info_out[b] for every stream.  HPE_OK if all are accepted; HPE_ERR_INVALID if one is refused (its
+ * info_out[b].status says which; hpe_last_error() names the first) or for a NULL pointer, B < 1 or a negative length. */
+int hpe_jpeg_info(int B, const unsigned char* const* streams, const long long* lengths, HpeJpegInfo* info_out);
+/* Decode pass over B streams: channels[b] in {1, 3} (1 on a colour stream stores the Y blocks only; 3 on a grey stream replicates Y in
+ * the back end), threads in [1, 16] std::threads over the images (the bytes written do not depend on it).  Fills table_out[b] (offsets
+ * of images packed in order: coefficients on 8-element, planes and frames on 16-byte boundaries), status_out[b], and totals_out[5] =
+ * {int16 coefficients, workspace bytes, frame-buffer bytes, workgroups of launch one, workgroups of launch two}.  coef_out == NULL: layout
+ * only (headers are parsed, table offsets and totals are filled, quant is not).  Otherwise the coefficients are written, never past
+ * coef_capacity (int16 elements; HPE_ERR_INVALID before anything is written if the total exceeds it).  A refused stream gets
+ * status_out[b] = HPE_ERR_INVALID and an all-zero table entry, and the call returns HPE_ERR_INVALID naming the first one. */
+int hpe_jpeg_decode(int B, const unsigned char* const* streams, const long long* lengths, const int* channels, int threads,
+                    short* coef_out, long long coef_capacity, HpeJpegImage* table_out, int* status_out, long long* totals_out);
+/* Two launches on `stream`: coefficients -> uint8 sample planes in workspace_dev (dequantisation + 8x8 inverse DCT), planes -> packed
+ * frames in frames_dev (upsampling + colour conversion).  The kernels read table_dev, the caller's device copy of table_host (in flight
+ * on `stream` is enough); table_host is what this call checks, entry by entry, against coef_count (int16 elements), workspace_bytes and
+ * frames_bytes before anything is launched.  Bytes of frames_dev outside the frames are not written.  No allocation, no
+ * synchronisation, no atomics, capturable: the same inputs give the same bits. */
+int hpe_jpeg_backend(const HpeJpegImage* table_host, const HpeJpegImage* table_dev, int B, const short* coef_dev, long long coef_count,
+                     unsigned char* workspace_dev, long long workspace_bytes, unsigned char* frames_dev, long long frames_bytes,
+                     void* stream);
+
 /* -- mesh renderer: the reference's SMPLRenderer (src/util/renderer.py:23-112) without OpenDR ---------------------------------
  * A renderer is its own handle (the reference builds SMPLRenderer without a predictor, preview.py:50).  What it computes is
  * defined in DESIGN.md "Renderer": pinhole projection snapped to 1/256 px, rasterisation with int64 edge functions and a
