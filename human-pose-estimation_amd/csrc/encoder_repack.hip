@@ -109,15 +109,15 @@ __global__ __launch_bounds__(256) void repack_bn_kernel(const RepackTable* __res
     L.shift[n] = (float)shift;
 }
 
-// conv1's fused-stem weights, fp32 [64][160]: the inverse of stem_w_k, zero elsewhere
-__global__ __launch_bounds__(256) void repack_stem_kernel(float* __restrict__ stem_w, const float* __restrict__ kernel) {
+// conv1's fused-stem weights, the three bf16 pieces [3][64][7][32] of Wt[n][k = kh * 32 + kw * 4 + ci] (zero for kw = 7 and ci = 3)
+__global__ __launch_bounds__(256) void repack_stem_kernel(unsigned short* __restrict__ stem_w, const float* __restrict__ kernel) {
     const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o >= 64 * 160) return;
-    const int n = o / 160, k = o - n * 160;
-    const int kh = k / 22, r = k - kh * 22 - 1;  // r = kw * 3 + ci
+    if (o >= 64 * 224) return;
+    const int n = o / 224, k = o - n * 224;
+    const int kh = k >> 5, kw = (k & 31) >> 2, ci = k & 3;
     float v = 0.f;
-    if (kh < 7 && r >= 0) v = kernel[((kh * 7 + r / 3) * 3 + r % 3) * 64 + n];
-    stem_w[o] = v;
+    if (kw < 7 && ci < 3) v = kernel[((kh * 7 + kw) * 3 + ci) * 64 + n];
+    store_split(stem_w + o, 64 * 224, v);
 }
 
 // both Winograd forms: one thread per (ci, n), consecutive threads along the [64 n][4 ci] inner block of the layouts, so each of the
@@ -232,7 +232,7 @@ const void* packing_of(hpe_ctx* c, int idx, int which, size_t* bytes) {
         case HPE_PACK_W_SPLIT: p = L.w_split, n = wt * 3 * 2; break;
         case HPE_PACK_WINO_U: p = L.wino_u, n = u * 16 * 4; break;
         case HPE_PACK_WINO4_U: p = L.wino4_u, n = u * 36 * 4; break;
-        case HPE_PACK_STEM_W: p = L.stem_w, n = (size_t)64 * 160 * 4; break;
+        case HPE_PACK_STEM_W: p = L.stem_w, n = (size_t)3 * 64 * 224 * 2; break;
         case HPE_PACK_SCALE: p = L.scale, n = (size_t)s.cout * 4; break;
         case HPE_PACK_SHIFT: p = L.shift, n = (size_t)s.cout * 4; break;
         case HPE_PACK_W_DUAL: p = L.w_dual, n = dual * 4; break;
@@ -330,7 +330,7 @@ hipError_t encoder_repack_launch(hpe_ctx* c, const float* flat, hipStream_t st) 
     if (grid[F_WT]) hipLaunchKernelGGL(repack_wt_kernel, dim3(grid[F_WT]), dim3(256), 0, st, T, flat);
     if (grid[F_BN]) hipLaunchKernelGGL(repack_bn_kernel, dim3(grid[F_BN]), dim3(256), 0, st, T, flat, w.mean, w.sd);
     if (c->conv[0].stem_w)
-        hipLaunchKernelGGL(repack_stem_kernel, grid1(64 * 160), dim3(256), 0, st, static_cast<float*>(c->conv[0].stem_w),
+        hipLaunchKernelGGL(repack_stem_kernel, grid1(64 * 224), dim3(256), 0, st, static_cast<unsigned short*>(c->conv[0].stem_w),
                            flat + hpe_encoder_param_offset(0, 0));
     if (grid[F_WINO]) hipLaunchKernelGGL(repack_wino_kernel<4>, dim3(grid[F_WINO]), dim3(256), 0, st, T, flat);
     if (grid[F_WINO4]) hipLaunchKernelGGL(repack_wino_kernel<6>, dim3(grid[F_WINO4]), dim3(256), 0, st, T, flat);

@@ -64,7 +64,7 @@ struct ConvLayer {
     // plan option f32_split: the fp32 weights of the 1x1 layers split exactly into three bf16 pieces, [n_pad][3][k] (conv_gemm_f32s.hip)
     void* w_split = nullptr;
     void* w_dual_split = nullptr;
-    void* stem_w = nullptr;   // conv1 only: weights in the k enumeration of stem_fused.hip (fp32 [64][160] / bf16 [64][7][32])
+    void* stem_w = nullptr;   // conv1 only: weights in the k enumeration of stem_fused.hip (bf16 [64][7][32]; fp32: its three bf16 pieces [3][64][7][32])
     float* wino_u = nullptr;  // device, G g G^T in the blocked layout of conv_wino.hip (3x3 layers on the Winograd path only)
     float* wino4_u = nullptr;  // device, the F(4x4,3x3) G g G^T in the blocked layout of conv_wino4.hip (layers selected by wino_f4)
     int n_pad = 0, k_pad = 0;
@@ -82,9 +82,6 @@ inline int conv_k_pad(int idx, bool bf16) { return round_up(idx == 0 ? 7 * 32 : 
 
 // The packing rules the host packers (hpe_finalize.hip, encoder_train.hip) and the repack kernels (encoder_repack.hip) share.  Every
 // floating-point helper fixes its operation order and turns contraction off, so that both sides round alike.
-
-// conv1's row of the fp32 fused-stem weights [64][160] (stem_fused.hip)
-__host__ __device__ inline int stem_w_k(int kh, int kw, int ci) { return kh * 22 + 1 + kw * 3 + ci; }
 
 // first element of (cout n, cin ci) in the F(2x2,3x3) weights [cout/64][cin/8][16][2][64][4]; element (xi, nu) is (xi * 4 + nu) * 512 further
 __host__ __device__ inline size_t wino_u_base(int n, int ci, int cin) {

@@ -285,20 +285,23 @@ static int pack_wino4_weights(hpe_ctx* c, const ConvSpec& s, ConvLayer& L) {
 
 // fused stem: the conv1 weights in the k enumeration of stem_fused.hip
 static int pack_stem_weights(hpe_ctx* c, ConvLayer& L) {
-    // bf16 [64][7][32], k as in Wt[n][k]; fp32 [64][160], k = stem_w_k
-    const size_t ld = c->bf16 ? 7 * 32 : 160;
+    // [64][7][32], k as in Wt[n][k]: rounded to bf16 (bf16 contexts), or its three exact bf16 pieces [3][64][7][32] (fp32 contexts)
+    const size_t ld = 7 * 32;
     std::vector<float> wp(64 * ld, 0.f);
     for (int kh = 0; kh < 7; ++kh)
         for (int kw = 0; kw < 7; ++kw)
             for (int ci = 0; ci < 3; ++ci) {
-                const int k = c->bf16 ? conv_wt_k(0, kh, kw, ci) : stem_w_k(kh, kw, ci);
+                const int k = conv_wt_k(0, kh, kw, ci);
                 for (int n = 0; n < 64; ++n) wp[n * ld + k] = L.kernel[(((size_t)kh * 7 + kw) * 3 + ci) * 64 + n];
             }
     if (c->bf16) return upload_bf16(c, &L.stem_w, to_bf16(wp));
-    float* q = static_cast<float*>(L.stem_w);
-    const int rc = upload_to(c, &q, wp);
-    L.stem_w = q;
-    return rc;
+    std::vector<unsigned short> ws(3 * wp.size());
+    for (size_t o = 0; o < wp.size(); ++o) {
+        unsigned short h[3];
+        bf16_split3(wp[o], h);
+        for (int j = 0; j < 3; ++j) ws[j * wp.size() + o] = h[j];
+    }
+    return upload_bf16(c, &L.stem_w, ws);
 }
 
 // ---- encoder weights: HWIO -> Wt[n][k] (k = (kh,kw,cin), cin fastest), zero padded; BN -> scale/shift; and the packings layer_packs names

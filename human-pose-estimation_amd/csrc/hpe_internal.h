@@ -155,8 +155,8 @@ hipError_t hpe_launch_maxpool_bf16(const void* x, void* y, int B, int H, int C, 
 hipError_t hpe_launch_avgpool_bf16(const void* x, float* y, int B, int HW, int C, int ldy, hipStream_t st);
 
 // stem_fused.hip: conv1_pad + conv1 + bn_conv1 + ReLU + pool1_pad + max-pool in one kernel; img [B,224,224,3] fp32 ->
-// y [B,56,56,64] (fp32, or bf16 when bf16 != 0).  w: fp32 [64][160] (k = kh * 22 + 1 + kw * 3 + c, other slots zero) or
-// bf16 [64][7][32] (k = kh * 32 + kw * 4 + c, other slots zero).  R pooled rows per workgroup, 56 % R == 0, R <= 8.
+// y [B,56,56,64] (fp32, or bf16 when bf16 != 0).  w: bf16 [64][7][32] (k = kh * 32 + kw * 4 + c, other slots zero);
+// for fp32 output the three exact bf16 pieces of the fp32 weights in that order, [3][64][7][32].  R pooled rows per workgroup, 56 % R == 0, R <= 8.
 hipError_t hpe_launch_stem_fused(const float* img, const void* w, const float* scale, const float* shift, void* y, int B, int R, int bf16,
                                  hipStream_t st);
 hipError_t hpe_stem_fused_init_device();

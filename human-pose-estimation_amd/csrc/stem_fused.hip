@@ -6,21 +6,21 @@
 // A workgroup (8 waves) owns one strip of an image: R pooled rows = 2R (+1 halo) conv rows.  It stages the 4R+7 padded
 // input rows it needs in LDS once (zero borders written here: that IS conv1_pad) and then runs an implicit GEMM whose A
 // operand is read straight from that LDS image -- no per-slab global traffic at all -- against weights held in registers:
-//   fp32:  v_mfma_f32_16x16x4_f32 (M = 112 = 7 x 16 conv pixels of a row: no padding rows, K packed 3 channels tight).
-//          k enumeration: kh-major, 22 slots per kernel row = {1 lead float (weight 0), 7 px x 3 ch}, so that every lane's
-//          2-float fragment (ds_read_b64) stays inside one input row and is 8-B aligned: 7 x 22 = 154 -> 160 = 20 chunks of 8.
-//          91.9 % of the issued MACs are real ones (the im2col GEMM this replaces: K padded 147 -> 224 = 65.6 %).
-//   bf16:  v_mfma_f32_16x16x32_bf16; the LDS image is bf16 with the channel padded 3 -> 4, so one kernel row of a pixel pair
-//          is one aligned ds_read_b128 and one MFMA k-step is one kernel row (8 px x 4 ch = 32 k); the matrix pipe is idle
-//          most of the time anyway -- this variant is bound by the image read and the LDS traffic.
+//   bf16:  v_mfma_f32_16x16x32_bf16 (M = 112 = 7 x 16 conv pixels of a row: no padding rows); the LDS image is bf16 with the
+//          channel padded 3 -> 4, so one kernel row of a pixel pair is one aligned ds_read_b128 and one MFMA k-step is one
+//          kernel row (8 px x 4 ch = 32 k); the matrix pipe is idle most of the time anyway -- this variant is bound by the
+//          image read and the LDS traffic.
+//   fp32:  the same k enumeration on the same instruction, image and weights each split exactly into three bf16 pieces and six
+//          products per step (see the fp32 section); a strip taller than 4 pooled rows is walked in passes that restage LDS.
 // A workgroup has 8 waves: wave w owns output channels 16 (w & 3) .. + 15 and the conv pixels 0-63 (w < 4: 4 blocks of 16) or
 // 64-111 (w >= 4: 3 blocks) of a conv row pair; the two waves that share a SIMD cover each other's LDS latency (one wave per SIMD
-// ran the fp32 loop at 66 % of the matrix rate).  The conv rows 2py and 2py+1 of pooled row py sit in the same lanes / register slots as row 2py-1 kept from the previous
+// ran the fp32 MFMA loop this file had before the split at 66 % of the matrix rate).  The conv rows 2py and 2py+1 of pooled row py sit in the same lanes / register slots as row 2py-1 kept from the previous
 // iteration, so the vertical 3-max is register-wise; the maximum goes through one LDS buffer for the horizontal 3-max
 // (stride 2) and leaves as full NHWC rows.  ReLU output is >= 0, so pool1_pad's zeros never win and are not materialised.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hpe_ctx.h"
 #include "hpe_internal.h"
 
 namespace {
@@ -34,14 +34,12 @@ constexpr int IMG = 224;        // input side
 constexpr int CONV = 112;       // conv1 output side
 constexpr int POOL = 56;        // pooled output side
 constexpr int NCH = 64;         // conv1 output channels
-constexpr int PITCH_F = 696;    // fp32 image row in LDS: 3 lead floats + 230 px x 3 ch + 3 tail floats (multiple of 4)
 constexpr int PITCH_B = 464;    // bf16 image row in LDS, in floats: 232 px x 4 ch x 2 B = 1856 B
 constexpr int VP = 68;          // V buffer row pitch in floats (64 channels + 4: the 4 lane groups of a store hit 4 bank sets)
-constexpr int KCH = 20;         // fp32: chunks of 8 k slots (160 >= 154)
 
 struct StemArgs {
     const float* img;    // [B,224,224,3] fp32
-    const void* w;       // fp32: [64][160] floats in the k enumeration above;  bf16: [64][7][32] bf16 (kh, then 8 px x 4 ch)
+    const void* w;       // bf16 [64][7][32] (kh, then 8 px x 4 ch);  fp32: its three bf16 pieces, [3][64][7][32]
     const float* scale;  // [64] folded BN
     const float* shift;
     void* y;             // [B,56,56,64] fp32 or bf16
@@ -105,77 +103,188 @@ __device__ __forceinline__ void bn_relu_vmax(f32x4 (&acc)[2][NRB], f32x4 (&prev)
     }
 }
 
-// --------------------------------------------------------------------------------------------------------- fp32
-// main part of a wave: conv pixels 16 RB0 .. 16 (RB0 + NRB) - 1 of every conv row, channels 16 (wave & 3) .. + 15
-template <int RB0, int NRB>
-__device__ __forceinline__ void stem_rows_f32(const StemArgs& p, const float* sIn, float* sV, int b, int r0, int t, int lane, int wave) {
+// The same, one conv row at a time (the split kernel).  STEP 0: the halo row 2 r0 - 1, it just becomes `prev`; STEP 1: row 2 py,
+// `prev` becomes the maximum of the two; STEP 2: row 2 py + 1 completes the vertical 3-max, V -> LDS, and becomes `prev`.
+template <int STEP, int RB0, int NRB>
+__device__ __forceinline__ void bn_relu_row(f32x4 (&acc)[NRB], f32x4 (&prev)[NRB], float sc, float sh, float* sV, int lane, int wave) {
     const int m = lane & 15, g = lane >> 4;
-    const int ch = 16 * (wave & 3) + m;
-    // ---- weights of this wave's 16 channels into registers: lane (col = m, k group g) holds slots 8p + 2g, 8p + 2g + 1
-    f32x2 wb[KCH];
-    {
-        const float* wrow = reinterpret_cast<const float*>(p.w) + (size_t)ch * (8 * KCH) + 2 * g;
 #pragma unroll
-        for (int pc = 0; pc < KCH; ++pc) wb[pc] = *reinterpret_cast<const f32x2*>(wrow + 8 * pc);
-    }
-    const float sc = p.scale[ch], sh = p.shift[ch];
-    // per-lane offset of k chunk pc inside the image: slot k' = 8 pc + 2 g -> (kh = k' / 22, j = k' % 22) -> kh * PITCH + j;
-    // slots >= 154 carry zero weights: they re-read slot 0 (finite data) instead of running past the staged rows
-    int off[KCH];
+    for (int rb = 0; rb < NRB; ++rb) {
 #pragma unroll
-    for (int pc = 0; pc < KCH; ++pc) {
-        const int k = 8 * pc + 2 * g;
-        const int kh = k / 22;
-        off[pc] = (k < 154) ? kh * PITCH_F + (k - 22 * kh) : 0;
-    }
-    // pixel wo = 16 rb + m of a conv row: window slot j is float 2 + 6 wo + j of the staged row (lead = 3, slot 0 = float before)
-    const float* abase = sIn + 2 + 6 * (16 * RB0 + m);
-
-    f32x4 acc[2][NRB], prev[NRB];
-#pragma unroll
-    for (int rb = 0; rb < NRB; ++rb) prev[rb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    // conv row hl (local: conv row 2 r0 - 1 + hl) reads staged rows 2 hl .. 2 hl + 6
-    auto conv_rows = [&](int hl0, bool both) {
-#pragma unroll
-        for (int cr = 0; cr < 2; ++cr)
-#pragma unroll
-            for (int rb = 0; rb < NRB; ++rb) acc[cr][rb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const float* a0 = abase + (2 * (hl0 + 1)) * PITCH_F;  // staged row of conv row hl0 + 1 (cr = 1); cr = 0 is 2 rows up
-#pragma unroll
-        for (int pc = 0; pc < KCH; ++pc) {
-            const float* ap = a0 + off[pc];
-#pragma unroll
-            for (int cr = 0; cr < 2; ++cr) {
-                if (cr == 0 && !both) continue;
-#pragma unroll
-                for (int rb = 0; rb < NRB; ++rb) {
-                    const f32x2 a = *reinterpret_cast<const f32x2*>(ap + (cr - 1) * (2 * PITCH_F) + rb * 96);
-                    acc[cr][rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, wb[pc].x, acc[cr][rb], 0, 0, 0);
-                    acc[cr][rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, wb[pc].y, acc[cr][rb], 0, 0, 0);
-                }
-            }
+        for (int i = 0; i < 4; ++i) {
+            const float v = fmaxf(acc[rb][i] * sc + sh, 0.f);
+            if (STEP == 2) sV[(16 * (RB0 + rb) + 4 * g + i) * VP + 16 * (wave & 3) + m] = fmaxf(prev[rb][i], v);
+            prev[rb][i] = STEP == 1 ? fmaxf(prev[rb][i], v) : v;
         }
-    };
-
-    if (r0 > 0) {  // halo: conv row 2 r0 - 1 (local 0) into acc[1] (for r0 == 0 it is pool1_pad's zero row)
-        conv_rows(-1, false);
-        bn_relu_vmax<false, RB0, NRB>(acc, prev, sc, sh, sV, lane, wave);
-    }
-    for (int pyl = 0; pyl < p.R; ++pyl) {
-        conv_rows(2 * pyl + 1, true);  // local rows 2 pyl + 1, 2 pyl + 2 = conv rows 2 py, 2 py + 1
-        bn_relu_vmax<true, RB0, NRB>(acc, prev, sc, sh, sV, lane, wave);
-        __syncthreads();
-        pool_store<false>(sV, p.y, b, r0 + pyl, t);
-        __syncthreads();
     }
 }
 
-__global__ __launch_bounds__(512, 2) void stem_fused_f32_kernel(StemArgs p) {
+// --------------------------------------------------------------------------------------------------------- fp32 (split)
+// The fp32 stem on the bf16 matrix cores (v_mfma_f32_16x16x4_f32 runs at 1/16 of the bf16 rate): image and weights as three bf16
+// pieces each, x = x0 + x1 + x2 exactly (bf16_split3), the six products a_i w_j with i + j <= 2 in the bf16 kernel's k enumeration
+// (one kernel row of 8 px x 4 ch per MFMA) -- 7 x 6 x 16 = 672 cycles per 16 x 16 block of a conv row against 40 x 32 = 1280.
+//   * the image is split ONCE, while it is staged: three bf16 planes per staged row, each in the bf16 kernel's layout
+//     ([232 px][4 ch], borders and pad channel exactly zero), PITCH_S floats per row; a fragment is one ds_read_b128 per piece.
+//   * the weights arrive split (pack_stem_weights / repack_stem_kernel): bf16 [3][64][7][32], 84 VGPRs per lane.
+//   * a0 w0 goes into one accumulator, the five cross terms (smallest first) into a second one; they are added once per conv row,
+//     before BN (the order conv_gemm_f32s.hip proved).
+//   * three planes of 4 R + 7 rows do not fit in LDS for R > 4, so a workgroup walks its strip in passes of at most PASS pooled
+//     rows: 23 staged rows (128,064 B) + the V buffer = 158,528 B.  `prev` (the last conv row after BN and ReLU) stays in registers
+//     across passes, so no conv row is computed twice inside a strip; a pass restages 4 PASS + 7 rows from the same relative origin
+//     as the first one (the two rows above its first window are not read).  The global loads of the next pass are issued before
+//     the MFMA work of the current one and written to LDS after the barrier that retires it.
+constexpr int PITCH_S = 3 * PITCH_B;                           // floats per staged row: three bf16 planes
+constexpr int PASS = 4;                                        // pooled rows per pass
+constexpr int STAGE_ROWS = 4 * PASS + 7;                       // staged rows of a full pass
+constexpr int STAGE_IT = (STAGE_ROWS * (IMG / 4) + 511) / 512;  // 4-pixel groups per thread
+
+typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+
+struct StageGroup {
+    f32x4 v0, v1, v2;  // 4 raw pixels (12 floats)
+};
+
+// group idx (staged row idx / 56, pixels 4 (idx % 56) ..) of raw rows 4 py0 - 5 .. + rows - 1 of image img4 into registers; rows
+// outside the picture are conv1_pad's zeros
+__device__ __forceinline__ StageGroup stage_load(const f32x4* img4, int py0, int rows, int idx) {
+    const int sr = idx / (IMG / 4);
+    const int u = idx - sr * (IMG / 4);
+    const int raw = 4 * py0 - 5 + sr;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    StageGroup s = {z, z, z};
+    if (sr < rows && (unsigned)raw < (unsigned)IMG) {
+        const f32x4* src = img4 + raw * (IMG * 3 / 4) + 3 * u;
+        s.v0 = src[0];
+        s.v1 = src[1];
+        s.v2 = src[2];
+    }
+    return s;
+}
+
+// ... split and written as three planes: raw pixel 4u + i = padded column 4u + 3 + i, 8 B per pixel and piece
+__device__ __forceinline__ void stage_store(const StageGroup& s, float* sIn, int rows, int idx) {
+    const int sr = idx / (IMG / 4);
+    const int u = idx - sr * (IMG / 4);
+    if (sr >= rows) return;
+    const float px[12] = {s.v0.x, s.v0.y, s.v0.z, s.v0.w, s.v1.x, s.v1.y, s.v1.z, s.v1.w, s.v2.x, s.v2.y, s.v2.z, s.v2.w};
+    unsigned short* dst = reinterpret_cast<unsigned short*>(sIn + (size_t)sr * PITCH_S) + (4 * u + 3) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        unsigned short h0[3], h1[3], h2[3];
+        bf16_split3(px[3 * i], h0);
+        bf16_split3(px[3 * i + 1], h1);
+        bf16_split3(px[3 * i + 2], h2);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const u16x4 o = {h0[j], h1[j], h2[j], 0};
+            *reinterpret_cast<u16x4*>(dst + j * (2 * PITCH_B) + 4 * i) = o;
+        }
+    }
+}
+
+// a wave: conv pixels 16 RB0 .. 16 (RB0 + NRB) - 1 of every conv row, channels 16 (wave & 3) .. + 15
+template <int RB0, int NRB>
+__device__ __forceinline__ void stem_rows_f32s(const StemArgs& p, float* sIn, float* sV, int b, int r0, int t, int lane, int wave) {
+    const int m = lane & 15, g = lane >> 4;
+    const int ch = 16 * (wave & 3) + m;
+    // ---- weights: piece j of lane (col = m, pixel pair g), kernel row kh: the 8 values of pixels 2g, 2g + 1 (4 ch each)
+    bf16x8 wb[3][7];
+    {
+        const bf16x8* wrow = reinterpret_cast<const bf16x8*>(p.w) + (size_t)ch * 28 + g;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int kh = 0; kh < 7; ++kh) wb[j][kh] = wrow[j * (NCH * 28) + 4 * kh];
+    }
+    const float sc = p.scale[ch], sh = p.shift[ch];
+    // pixel wo = 16 rb + m, pixel pair g: 16 B at padded column 2 wo + 2 g of a plane
+    const float* abase = sIn + 4 * (16 * RB0 + m + g);
+
+    f32x4 acc[NRB], acx[NRB], prev[NRB];  // a0 w0 / the cross terms
+#pragma unroll
+    for (int rb = 0; rb < NRB; ++rb) prev[rb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    // conv row hl (local: conv row 2 py0 - 1 + hl of the pass that starts at pooled row py0) reads staged rows 2 hl .. 2 hl + 6.
+    // One conv row at a time: the two rows of a pooled row together would hold 64 accumulator registers, and the staged loads of
+    // the next pass then no longer fit next to the weights.
+    auto conv_row = [&](int hl) {
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb) acc[rb] = acx[rb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        const float* a0 = abase + (2 * hl) * PITCH_S;
+#pragma unroll
+        for (int kh = 0; kh < 7; ++kh) {
+            bf16x8 a[3][NRB];
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+#pragma unroll
+                for (int rb = 0; rb < NRB; ++rb) a[j][rb] = *reinterpret_cast<const bf16x8*>(a0 + kh * PITCH_S + j * PITCH_B + rb * 64);
+            // cross terms smallest first; consecutive MFMAs go to different accumulators
+#pragma unroll
+            for (int rb = 0; rb < NRB; ++rb) acx[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2][rb], wb[0][kh], acx[rb], 0, 0, 0);
+#pragma unroll
+            for (int rb = 0; rb < NRB; ++rb) acx[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][rb], wb[2][kh], acx[rb], 0, 0, 0);
+#pragma unroll
+            for (int rb = 0; rb < NRB; ++rb) acx[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1][rb], wb[1][kh], acx[rb], 0, 0, 0);
+#pragma unroll
+            for (int rb = 0; rb < NRB; ++rb) acx[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1][rb], wb[0][kh], acx[rb], 0, 0, 0);
+#pragma unroll
+            for (int rb = 0; rb < NRB; ++rb) acx[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][rb], wb[1][kh], acx[rb], 0, 0, 0);
+#pragma unroll
+            for (int rb = 0; rb < NRB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][rb], wb[0][kh], acc[rb], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);  // keep the scheduler from hoisting the fragment reads of every kernel row to the top
+        }
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb) acc[rb] += acx[rb];
+    };
+
+    const int rows = 4 * (p.R < PASS ? p.R : PASS) + 7;
+    const f32x4* img4 = reinterpret_cast<const f32x4*>(p.img) + (size_t)b * IMG * (IMG * 3 / 4);
+    static_assert(STAGE_IT == 3, "three groups per thread");
+    StageGroup s0 = stage_load(img4, r0, rows, t), s1 = stage_load(img4, r0, rows, t + 512), s2 = stage_load(img4, r0, rows, t + 1024);
+    {  // zero the planes once: the borders and the pad channel are never written again
+        const int total = rows * (PITCH_S / 4);
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        for (int idx = t; idx < total; idx += 512) reinterpret_cast<f32x4*>(sIn)[idx] = z;
+    }
+    __syncthreads();
+    stage_store(s0, sIn, rows, t), stage_store(s1, sIn, rows, t + 512), stage_store(s2, sIn, rows, t + 1024);
+    __syncthreads();
+
+    for (int q0 = 0; q0 < p.R; q0 += PASS) {
+        const int py0 = r0 + q0;
+        const int n = p.R - q0 < PASS ? p.R - q0 : PASS;
+        const bool more = q0 + PASS < p.R;
+        if (more) {
+            s0 = stage_load(img4, py0 + PASS, rows, t);
+            s1 = stage_load(img4, py0 + PASS, rows, t + 512);
+            s2 = stage_load(img4, py0 + PASS, rows, t + 1024);
+        }
+        if (q0 == 0 && r0 > 0) {  // halo: conv row 2 r0 - 1 (local 0) becomes `prev` (for r0 == 0 it is pool1_pad's zero row)
+            conv_row(0);
+            bn_relu_row<0, RB0, NRB>(acc, prev, sc, sh, sV, lane, wave);
+        }
+        for (int pyl = 0; pyl < n; ++pyl) {
+            conv_row(2 * pyl + 1);  // local rows 2 pyl + 1, 2 pyl + 2 = conv rows 2 py, 2 py + 1
+            bn_relu_row<1, RB0, NRB>(acc, prev, sc, sh, sV, lane, wave);
+            conv_row(2 * pyl + 2);
+            // every wave has read the V buffer of the previous pooled row (its pool_store ran before these MFMAs, so this barrier
+            // finds the others there already) and, once pyl == n - 1, has read the staged rows for the last time
+            __syncthreads();
+            bn_relu_row<2, RB0, NRB>(acc, prev, sc, sh, sV, lane, wave);
+            __syncthreads();
+            pool_store<false>(sV, p.y, b, py0 + pyl, t);  // overlaps the next pooled row's MFMAs of the other waves
+        }
+        if (more) {
+            stage_store(s0, sIn, rows, t), stage_store(s1, sIn, rows, t + 512), stage_store(s2, sIn, rows, t + 1024);
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(512) void stem_fused_f32s_kernel(StemArgs p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int rows = 4 * p.R + 7;
-    float* sIn = lds;
-    float* sV = lds + rows * PITCH_F;
+    float* sIn = lds;  // [rows][3 pieces][232 px][4 ch] bf16
+    float* sV = lds + (4 * (p.R < PASS ? p.R : PASS) + 7) * PITCH_S;
 
     const int b = blockIdx.x / p.strips;
     const int strip = blockIdx.x - b * p.strips;
@@ -183,27 +292,10 @@ __global__ __launch_bounds__(512, 2) void stem_fused_f32_kernel(StemArgs p) {
     const int t = threadIdx.x;
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-
-    // ---- stage the padded input rows: staged row s = padded row 4 r0 - 2 + s = raw row 4 r0 - 5 + s; float4 slot q4 of a row
-    //      holds floats 4 q4 .. 4 q4 + 3, raw float4 q (pixels 4q/3 ...) lands in slot q + 3 (3 lead floats + 3 pad pixels = 12)
-    {
-        const int total = rows * (PITCH_F / 4);
-        const f32x4* img4 = reinterpret_cast<const f32x4*>(p.img) + (size_t)b * IMG * (IMG * 3 / 4);
-#pragma unroll 8
-        for (int idx = t; idx < total; idx += 512) {
-            const int s = idx / (PITCH_F / 4);
-            const int q4 = idx - s * (PITCH_F / 4);
-            const int raw = 4 * r0 - 5 + s;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if ((unsigned)raw < (unsigned)IMG && q4 >= 3 && q4 < 3 + IMG * 3 / 4) v = img4[raw * (IMG * 3 / 4) + (q4 - 3)];
-            *reinterpret_cast<f32x4*>(sIn + s * PITCH_F + 4 * q4) = v;
-        }
-    }
-    __syncthreads();
     if (wave < 4)
-        stem_rows_f32<0, 4>(p, sIn, sV, b, r0, t, lane, wave);
+        stem_rows_f32s<0, 4>(p, sIn, sV, b, r0, t, lane, wave);
     else
-        stem_rows_f32<4, 3>(p, sIn, sV, b, r0, t, lane, wave);
+        stem_rows_f32s<4, 3>(p, sIn, sV, b, r0, t, lane, wave);
 }
 
 // --------------------------------------------------------------------------------------------------------- bf16
@@ -314,11 +406,15 @@ __global__ __launch_bounds__(512, 2) void stem_fused_bf16_kernel(StemArgs p) {
 
 }  // namespace
 
-size_t hpe_stem_fused_lds_bytes(int R, int bf16) { return ((size_t)(4 * R + 7) * (bf16 ? PITCH_B : PITCH_F) + (size_t)CONV * VP) * sizeof(float); }
+// bf16: the whole strip's 4 R + 7 rows; fp32: three planes of the rows of one pass
+size_t hpe_stem_fused_lds_bytes(int R, int bf16) {
+    const size_t image = bf16 ? (size_t)(4 * R + 7) * PITCH_B : (size_t)(4 * (R < PASS ? R : PASS) + 7) * PITCH_S;
+    return (image + (size_t)CONV * VP) * sizeof(float);
+}
 
 // per-device attribute (dynamic LDS above 64 KB); call with the target device current
 hipError_t hpe_stem_fused_init_device() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_fused_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_fused_f32s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)hpe_stem_fused_lds_bytes(8, 0));
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(stem_fused_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -351,6 +447,6 @@ hipError_t hpe_launch_stem_fused(const float* img, const void* w, const float* s
     if (bf16)
         hipLaunchKernelGGL(stem_fused_bf16_kernel, dim3(B * p.strips), dim3(512), ldsb, st, p);
     else
-        hipLaunchKernelGGL(stem_fused_f32_kernel, dim3(B * p.strips), dim3(512), ldsb, st, p);
+        hipLaunchKernelGGL(stem_fused_f32s_kernel, dim3(B * p.strips), dim3(512), ldsb, st, p);
     return hipGetLastError();
 }

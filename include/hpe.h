@@ -409,7 +409,7 @@ enum {
     HPE_PACK_W_SPLIT,      /* bf16 [n_pad][3][k_pad] (f32_split) */
     HPE_PACK_WINO_U,       /* F(2x2,3x3) [cout/64][cin/8][16][2][64][4] */
     HPE_PACK_WINO4_U,      /* F(4x4,3x3) [cout/64][cin/4][36][64][4] */
-    HPE_PACK_STEM_W,       /* conv1: fp32 [64][160] */
+    HPE_PACK_STEM_W,       /* conv1: bf16 [3][64][7][32], the three exact pieces of the fp32 weights */
     HPE_PACK_SCALE,        /* [cout] */
     HPE_PACK_SHIFT,        /* [cout] */
     HPE_PACK_W_DUAL,       /* *_branch2c of a conv_block: [n_pad][K1 + K2] fp32, scales folded in */
