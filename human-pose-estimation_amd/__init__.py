@@ -29,7 +29,9 @@ from .jpeg import DecodedBatch, decode_jpeg_batch, jpeg_info  # noqa: F401
 from .records import RecordDataset, RecordError, load_training_batch, parse_example, parse_image_example, parse_mocap_example, read_tfrecords  # noqa: F401
 from .image import get_original, preprocess_batch, preprocess_image  # noqa: F401
 from .ops import critic_gradient_penalty, critic_scores, critic_wgan_loss, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas, encoder_features  # noqa: F401
+from .optim import KerasAdam  # noqa: F401
 from .predictor import Predictor  # noqa: F401
 from .projection import batch_orth_proj_idrot, reproject_vertices  # noqa: F401
 from .render import SMPLRenderer  # noqa: F401
 from .smpl import SMPL  # noqa: F401
+from .trainer import Trainer  # noqa: F401

@@ -11,10 +11,11 @@ ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon (src/trainer.py:184)
 
 
 class CriticTrainer(object):
-    def __init__(self, engine, lr=CRITIC_LR, betas=(0.9, 0.999), eps=ADAM_EPS, gp_weight=10.0, generator=None):
+    def __init__(self, engine, lr=CRITIC_LR, betas=(0.9, 0.999), eps=ADAM_EPS, gp_weight=10.0, generator=None, optimizer="torch"):
         """engine: an HpeEngine with a loaded critic (the starting point: a checkpoint's discriminator or a fresh initialisation).
         ``params`` is the flat parameter tensor (critic_spec.flat_layout) the optimiser owns; ``critic_spec.flat_to_params(params)``
-        gives the dict ``load_critic`` / ``weights.npz`` take.  generator: the torch.Generator of the interpolation draws."""
+        gives the dict ``load_critic`` / ``weights.npz`` take.  generator: the torch.Generator of the interpolation draws.  optimizer:
+        "torch" (torch.optim.Adam) or "keras" (``KerasAdam``, optim.py: the reference's fused update in HIP)."""
         import torch
 
         if not engine.has_critic:
@@ -23,7 +24,15 @@ class CriticTrainer(object):
         self.gp_weight = float(gp_weight)
         self.generator = generator
         self.params = engine.critic_params()
-        self.optimizer = torch.optim.Adam([self.params], lr=lr, betas=betas, eps=eps)
+        if optimizer not in ("torch", "keras"):
+            raise ValueError("optimizer must be 'torch' or 'keras'")
+        if optimizer == "keras":
+            from .optim import KerasAdam
+
+            self.optimizer = KerasAdam(lr, betas[0], betas[1], eps)
+            self.optimizer.add("critic", self.params)
+        else:
+            self.optimizer = torch.optim.Adam([self.params], lr=lr, betas=betas, eps=eps)
 
     def step(self, real, fake, interp=None):
         """One critic update on (joints, shapes, Rs) triples of equal row count -> {'critic_network_loss', 'critic_penalty'} as in

@@ -20,7 +20,7 @@ ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon
 class GeneratorTrainer(object):
     def __init__(self, engine, lr=GENERATOR_LR, betas=(0.9, 0.999), eps=ADAM_EPS, kpr_loss_weight=60.0, mr_loss_weight=0.001,
                  critic_loss_weight=0.01, dropout=0.5, generator=None, train_encoder=False, encoder_lr=None, encoder_bn="frozen",
-                 bn_momentum=0.99, bn_unbiased=True):
+                 bn_momentum=0.99, bn_unbiased=True, optimizer="torch"):
         """engine: a finalized HpeEngine with a regressor, mean theta and SMPL (and a critic, for the critic term).  ``params`` is the
         flat parameter tensor (regressor_spec.flat_layout) the optimiser owns; ``regressor_spec.flat_to_params(params)`` gives the
         dict ``load_regressor`` / ``load_mean_theta`` take.  generator: the torch.Generator of the dropout draws.  train_encoder: also
@@ -28,7 +28,10 @@ class GeneratorTrainer(object):
         hyper-parameters, lr ``encoder_lr``, default the generator's) whenever ``step`` is given images.  encoder_bn: "frozen" (the
         moving statistics stay fixed) or "batch" (needs ``engine.reserve_encoder_train(B, batch_norm=True)``): batch statistics in the
         forward and the backward, and ``encoder_stats``, the flat statistics tensor (resnet_spec.stats_to_params), moves with momentum
-        ``bn_momentum`` after every step (``bn_unbiased``: the batch variance times M / (M - 1))."""
+        ``bn_momentum`` after every step (``bn_unbiased``: the batch variance times M / (M - 1)).  optimizer: "torch"
+        (torch.optim.Adam, one per flat tensor) or "keras": ONE ``KerasAdam`` (optim.py: the reference's fused update in HIP) that owns
+        the regressor's and, with ``train_encoder``, the encoder's tensor under one step count, as the reference's
+        ``generator_optimizer`` does; it has one rate, so an ``encoder_lr`` other than ``lr`` is refused."""
         import torch
 
         if not 0.0 <= dropout < 1.0:
@@ -38,7 +41,18 @@ class GeneratorTrainer(object):
         self.dropout = float(dropout)
         self.generator = generator
         self.params = engine.regressor_params().requires_grad_(True)
-        self.optimizer = torch.optim.Adam([self.params], lr=lr, betas=betas, eps=eps)
+        if optimizer not in ("torch", "keras"):
+            raise ValueError("optimizer must be 'torch' or 'keras'")
+        self.keras = optimizer == "keras"
+        if self.keras:
+            from .optim import KerasAdam
+
+            if train_encoder and encoder_lr is not None and float(encoder_lr) != float(lr):
+                raise ValueError("optimizer='keras' steps the encoder and the regressor with one optimiser: encoder_lr must equal lr")
+            self.optimizer = KerasAdam(lr, betas[0], betas[1], eps)
+            self.optimizer.add("regressor", self.params)
+        else:
+            self.optimizer = torch.optim.Adam([self.params], lr=lr, betas=betas, eps=eps)
         self.train_encoder = bool(train_encoder)
         if encoder_bn not in ("frozen", "batch"):
             raise ValueError("encoder_bn must be 'frozen' or 'batch'")
@@ -50,7 +64,10 @@ class GeneratorTrainer(object):
             self.encoder_stats = engine.encoder_stats()
         if self.train_encoder:
             self.encoder_params = engine.encoder_params().requires_grad_(True)
-            self.encoder_optimizer = torch.optim.Adam([self.encoder_params], lr=lr if encoder_lr is None else encoder_lr, betas=betas, eps=eps)
+            if self.keras:
+                self.optimizer.add("encoder", self.encoder_params)
+            else:
+                self.encoder_optimizer = torch.optim.Adam([self.encoder_params], lr=lr if encoder_lr is None else encoder_lr, betas=betas, eps=eps)
 
     def draw_masks(self, B):
         """the dropout multipliers [2,B,1024] of one step: 0 with probability ``dropout``, else 1 / (1 - dropout); None without dropout"""
@@ -117,14 +134,20 @@ class GeneratorTrainer(object):
                 if last:
                     pred_kp = kp.detach()
                     loss = kpr[-1] + (mr[-1] if mr else 0.0) + (gc[-1] if gc else 0.0)
-        self.optimizer.zero_grad(set_to_none=True)
-        if enc:
-            self.encoder_optimizer.zero_grad(set_to_none=True)
-        loss.backward()
-        self.optimizer.step()
+        if self.keras:
+            self.optimizer.zero_grad()
+            loss.backward()
+            self.optimizer.step(only=None if enc or not self.train_encoder else ("regressor",))
+        else:
+            self.optimizer.zero_grad(set_to_none=True)
+            if enc:
+                self.encoder_optimizer.zero_grad(set_to_none=True)
+            loss.backward()
+            self.optimizer.step()
         eng.set_regressor_params(self.params)
         if enc:
-            self.encoder_optimizer.step()
+            if not self.keras:
+                self.encoder_optimizer.step()
             eng.set_encoder_params_dev(self.encoder_params)
             if self.encoder_bn == "batch":
                 eng.update_encoder_stats(self.encoder_stats, self.bn_momentum, self.bn_unbiased)

@@ -125,6 +125,11 @@ class Predictor(object):
                 )
             encoder_params = encoder_params or w
             regressor_params = regressor_params or w
+            if self.checkpoint_info is not None and "mean_var" in w:
+                # a checkpoint saved by this package (tf_checkpoint.save_checkpoint) carries the TRAINED mean theta, which the
+                # reference's own checkpoints lose: the restored model predicts from it
+                self.mean_np = np.asarray(w["mean_var"], np.float32).reshape(1, self.total_params)
+                self.engine.load_mean_theta(self.mean_np)
         self.engine.load_encoder(encoder_params)
         self.engine.load_regressor(regressor_params)
         self.engine.finalize()

@@ -1,4 +1,4 @@
-"""Stand-alone reader for the TensorFlow-2 object-graph checkpoints the reference restores its weights from
+"""Stand-alone reader and writer for the TensorFlow-2 object-graph checkpoints the reference restores its weights from
  -- no TensorFlow involved.
 
 What the reference does (src/predictor.py:77-86, same in src/trainer.py:192-198,836):
@@ -28,6 +28,9 @@ PARITY UNPINNED: no TensorFlow-written checkpoint exists in this environment (th
 authors", README.md:76) -- the reader follows the published formats (LevelDB table_format.md; tensor_bundle.proto;
 trackable_object_graph.proto) and is tested against bundles produced by the independent writer in
 tests/tf_bundle_writer.py.
+
+The second half of this file is the writer of the same layout (``save_checkpoint``, ``write_bundle``) and ``load_training_state``, which
+reads the optimisers' step counts and moments back; its parity with TensorFlow is unpinned in the same way (see its header below).
 """
 from __future__ import annotations
 
@@ -120,6 +123,19 @@ def _shift_pow2(k):
     return _SHIFT_POW2[k]
 
 
+_CRC_NP16 = None
+
+
+def _crc_table16():
+    """[x] = the register after the two bytes x & 0xFF, x >> 8 from a register of zero: one lookup advances a lane by two bytes"""
+    global _CRC_NP16
+    if _CRC_NP16 is None:
+        x = np.arange(65536, dtype=np.uint32)
+        r = _CRC_NP[x & np.uint32(0xFF)] ^ (x >> np.uint32(8))
+        _CRC_NP16 = _CRC_NP[r & np.uint32(0xFF)] ^ (r >> np.uint32(8))
+    return _CRC_NP16
+
+
 def crc32c(data, crc=0):
     """CRC-32C (Castagnoli, reflected 0x82F63B78).  Large buffers use the register's linearity over GF(2): the initial
     register value is folded into the first four bytes, the buffer is zero-padded at the FRONT (a zero register stays
@@ -142,11 +158,11 @@ def crc32c(data, crc=0):
     buf[lanes * L - n:] = a
     head = buf[lanes * L - n:lanes * L - n + 4]
     head ^= np.frombuffer(init.to_bytes(4, "little"), dtype=np.uint8)
-    cols = np.ascontiguousarray(buf.reshape(lanes, L).T)
+    cols = np.ascontiguousarray(buf.reshape(lanes, L).view("<u2").T)  # two bytes per step (the table of _crc_table16)
     reg = np.zeros(lanes, dtype=np.uint32)
-    m8, s8 = np.uint32(0xFF), np.uint32(8)
-    for j in range(L):
-        reg = _CRC_NP[(reg ^ cols[j]) & m8] ^ (reg >> s8)
+    t16, m16, s16 = _crc_table16(), np.uint32(0xFFFF), np.uint32(16)
+    for j in range(L // 2):
+        reg = t16[(reg ^ cols[j]) & m16] ^ (reg >> s16)
     k = logL
     while reg.shape[0] > 1:
         reg = _mat_apply(_shift_pow2(k), reg[0::2]) ^ reg[1::2]
@@ -593,6 +609,10 @@ def load_hmr_weights(prefix_or_dir, verify=True):
     ckey = "inital_theta" + VAR_SUFFIX
     if ckey in rd:
         out["inital_theta"] = rd.get(ckey)
+    # the trained mean theta: a root only ``save_checkpoint`` writes (the reference's checkpoints do not hold it, see the writer)
+    ckey = "mean_var" + VAR_SUFFIX
+    if ckey in rd:
+        out["mean_var"] = rd.get(ckey)
     return out, info
 
 
@@ -670,3 +690,453 @@ def load_critic_weights(prefix_or_dir, verify=True):
             raise CheckpointError("critic layer %s has kernel %s and bias %s, expected %s and %s" % (name, k.shape, b.shape, (fi, fo), (fo,)))
         out["critic/%s/kernel" % name], out["critic/%s/bias" % name] = k, b
     return out, info
+
+
+# =============================================================================================== the writer
+# ``save_checkpoint`` writes the layout described at the top of this file: what ``tf.train.Checkpoint.save`` of the reference's Trainer
+# (src/trainer.py:193-198, 836) leaves on disk, so that a model trained here can be restored by ``Predictor(config)``, resumed by
+# ``load_training_state``, and is laid out for the reference's own ``checkpoint.restore``.  Written from the published format
+# descriptions (LevelDB table_format.md; tensor_bundle.proto; trackable_object_graph.proto; checkpoint_state.proto), sharing only the
+# CRC and the constants with the reader above.
+#
+# PARITY UNPINNED, as for the reader: no TensorFlow exists in this environment, so no file written here has been restored by
+# TensorFlow and none written by TensorFlow has been compared with one written here.  Tested: the reader above and the independent
+# test writer (tests/tf_bundle_writer.py) agree with it.
+#
+# One root is this project's own: ``mean_var``.  The reference trains ``mean_var`` (src/trainer.py:482) but tracks only the untrained
+# ``theta_prev`` as ``inital_theta``, so its checkpoints lose the trained mean; here the trained mean theta is saved as ``mean_var``
+# (with its optimiser slots) and ``inital_theta`` keeps the reference's meaning.  A restore that does not know the extra root skips it.
+OPTIMIZER_ROOTS = ("generator_optimizer", "discriminator_optimizer")
+_HYPER = ("learning_rate", "beta_1", "beta_2", "decay")
+_NP_TO_DT = {"float32": 1, "float64": 2, "int32": 3, "int64": 9}
+_BLOCK_BYTES = 4096
+_RESTART_INTERVAL = 16
+
+
+def _enc_varint(n):
+    out = bytearray()
+    while n >= 0x80:
+        out.append((n & 0x7F) | 0x80)
+        n >>= 7
+    out.append(n)
+    return bytes(out)
+
+
+def _pb_varint(fn, v):
+    return _enc_varint(fn << 3) + _enc_varint(v)
+
+
+def _pb_bytes(fn, payload):
+    return _enc_varint((fn << 3) | 2) + _enc_varint(len(payload)) + payload
+
+
+def _pb_str(fn, s):
+    return _pb_bytes(fn, s.encode("utf-8"))
+
+
+def _pb_fixed32(fn, v):
+    return _enc_varint((fn << 3) | 5) + int(v).to_bytes(4, "little")
+
+
+class _BlockWriter:
+    """one table block: entries (shared, non_shared, value_length, key suffix, value) with a restart point every `interval` entries, then
+    the restart offsets and their count as fixed32"""
+
+    def __init__(self, interval):
+        self.interval, self.buf, self.restarts, self.count, self.last = interval, bytearray(), [], 0, b""
+
+    def add(self, key, value):
+        shared = 0
+        if self.count % self.interval == 0:
+            self.restarts.append(len(self.buf))
+        else:
+            limit = min(len(key), len(self.last))
+            while shared < limit and key[shared] == self.last[shared]:
+                shared += 1
+        self.buf += _enc_varint(shared) + _enc_varint(len(key) - shared) + _enc_varint(len(value)) + key[shared:] + value
+        self.last = key
+        self.count += 1
+
+    def finish(self):
+        restarts = self.restarts or [0]
+        return bytes(self.buf) + b"".join(r.to_bytes(4, "little") for r in restarts) + len(restarts).to_bytes(4, "little")
+
+
+def _write_table(path, items):
+    """items: [(key bytes, value bytes)] in ascending key order -> a LevelDB-format table without compression or filter"""
+    out = bytearray()
+
+    def emit(block):
+        handle = _enc_varint(len(out)) + _enc_varint(len(block))
+        out.extend(block)
+        out.append(0)  # kNoCompression
+        out.extend(mask_crc(crc32c(block + b"\0")).to_bytes(4, "little"))
+        return handle
+
+    index = _BlockWriter(1)
+    cur = _BlockWriter(_RESTART_INTERVAL)
+    prev = None
+    for key, value in items:
+        if prev is not None and key <= prev:
+            raise CheckpointError("table keys must be strictly ascending")
+        cur.add(key, value)
+        prev = key
+        if len(cur.buf) >= _BLOCK_BYTES:
+            index.add(key, emit(cur.finish()))  # the block's last key separates it from the next
+            cur = _BlockWriter(_RESTART_INTERVAL)
+    if cur.count:
+        index.add(prev, emit(cur.finish()))
+    meta = emit(_BlockWriter(1).finish())
+    idx = emit(index.finish())
+    footer = meta + idx
+    out.extend(footer + b"\0" * (40 - len(footer)) + TABLE_MAGIC.to_bytes(8, "little"))
+    with open(path, "wb") as f:
+        f.write(out)
+
+
+def _string_tensor_bytes(s):
+    """a scalar DT_STRING tensor in a data shard: the length as a varint, the masked CRC of the lengths (as uint32 each), the bytes; the
+    entry's own checksum runs over the lengths, that checksum and the bytes"""
+    crc = crc32c(len(s).to_bytes(4, "little"))
+    check = mask_crc(crc).to_bytes(4, "little")
+    return _enc_varint(len(s)) + check + s, crc32c(s, crc32c(check, crc))
+
+
+def write_bundle(prefix, tensors):
+    """tensors: {checkpoint key: ndarray (float32 / float64 / int32 / int64) or bytes (a scalar string tensor)} -> ``prefix.index`` and
+    ``prefix.data-00000-of-00001``"""
+    header = _pb_varint(1, 1) + _pb_bytes(3, _pb_varint(1, 1))  # num_shards = 1, little endian (the default), version.producer = 1
+    items = [(b"", header)]
+    offset = 0
+    with open(prefix + ".data-00000-of-00001", "wb") as data:
+        for key in sorted(tensors, key=lambda k: k.encode("utf-8")):
+            t = tensors[key]
+            if isinstance(t, (bytes, bytearray)):
+                payload, crc = _string_tensor_bytes(bytes(t))
+                entry = _pb_varint(1, DT_STRING) + _pb_bytes(2, b"")
+            else:
+                t = np.asarray(t)
+                t = t if t.flags.c_contiguous else np.ascontiguousarray(t)  # (ascontiguousarray alone would make a scalar [1])
+                if t.dtype.name not in _NP_TO_DT:
+                    raise CheckpointError("%s: dtype %s cannot be written" % (key, t.dtype))
+                t = t.astype(t.dtype.newbyteorder("<"), copy=False)
+                payload = t.tobytes()
+                crc = crc32c(t) if t.size else crc32c(b"")
+                shape = b"".join(_pb_bytes(2, _pb_varint(1, d)) for d in t.shape)
+                entry = _pb_varint(1, _NP_TO_DT[t.dtype.name]) + _pb_bytes(2, shape)
+            if offset:
+                entry += _pb_varint(4, offset)
+            entry += _pb_varint(5, len(payload)) + _pb_fixed32(6, mask_crc(crc))
+            data.write(payload)
+            offset += len(payload)
+            items.append((key.encode("utf-8"), entry))
+    _write_table(prefix + ".index", items)
+
+
+class _GraphBuilder:
+    """TrackableObjectGraph: nodes numbered breadth-first from the root, slot variables after them"""
+
+    def __init__(self):
+        self.children = [[]]  # per node [(local name, node id)]
+        self.attrs = [None]  # per node (full_name, checkpoint_key) or None
+        self.slots = [[]]  # per node [(original node id, slot name, slot node id)]
+
+    def _new(self):
+        self.children.append([])
+        self.attrs.append(None)
+        self.slots.append([])
+        return len(self.children) - 1
+
+    def child(self, parent, name):
+        nid = self._new()
+        self.children[parent].append((name, nid))
+        return nid
+
+    def variable(self, parent, name, full_name, key):
+        nid = self.child(parent, name)
+        self.attrs[nid] = (full_name, key)
+        return nid
+
+    def slot(self, optimizer, original, slot_name, full_name, key):
+        nid = self._new()
+        self.attrs[nid] = (full_name, key)
+        self.slots[optimizer].append((original, slot_name, nid))
+        return nid
+
+    def serialize(self):
+        out = b""
+        for ch, at, sl in zip(self.children, self.attrs, self.slots):
+            body = b"".join(_pb_bytes(1, _pb_varint(1, nid) + _pb_str(2, name)) for name, nid in ch)
+            if at is not None:
+                body += _pb_bytes(2, _pb_str(1, "VARIABLE_VALUE") + _pb_str(2, at[0]) + _pb_str(3, at[1]))
+            body += b"".join(_pb_bytes(3, _pb_varint(1, o) + _pb_str(2, n) + _pb_varint(3, s)) for o, n, s in sl)
+            out += _pb_bytes(1, body)
+        return out
+
+
+def _keras_dense_name(i):
+    return "dense" if i == 0 else "dense_%d" % i
+
+
+def _model_variables():
+    """[(root, object path under the root, Keras full_name, project key)] of every variable of the three networks, in the order the
+    object graph lists them"""
+    out = []
+    bn_of = {s.bn_name for s in CONV_SPECS}
+    for i, layer in enumerate(keras_weighted_layer_order(False)):
+        for var in (_BN_VARS if layer in bn_of else ("kernel", "bias")):
+            out.append(("feature_extractor", "layer_with_weights-%d/%s" % (i, var), "%s/%s" % (layer, var), "%s/%s" % (layer, var)))
+    for i in range(3):
+        for var in ("kernel", "bias"):
+            out.append(("generator3d", "layer_with_weights-%d/%s" % (i, var), "%s/%s" % (_keras_dense_name(i), var), "dense_%d/%s" % (i, var)))
+    for i, (name, _fi, _fo) in enumerate(CRITIC_LAYERS):
+        for var in ("kernel", "bias"):
+            out.append(("discriminator", "layer_with_weights-%d/%s" % (i, var), "%s/%s" % (name, var), "critic/%s/%s" % (name, var)))
+    return out
+
+
+def _read_state_paths(checkpoint_dir):
+    path = os.path.join(checkpoint_dir, "checkpoint")
+    if not os.path.exists(path):
+        return []
+    with open(path, "r") as f:
+        return re.findall(r'^\s*all_model_checkpoint_paths:\s*"((?:[^"\\]|\\.)*)"', f.read(), re.M)
+
+
+def write_checkpoint_state(checkpoint_dir, name):
+    """the ``checkpoint`` state file (CheckpointState in text format): ``name`` becomes the newest, earlier ones stay listed"""
+    older = [p for p in _read_state_paths(checkpoint_dir) if p != name]
+    tmp = os.path.join(checkpoint_dir, "checkpoint.tmp%d" % os.getpid())
+    with open(tmp, "w") as f:
+        f.write('model_checkpoint_path: "%s"\n' % name)
+        for p in older + [name]:
+            f.write('all_model_checkpoint_paths: "%s"\n' % p)
+    os.replace(tmp, os.path.join(checkpoint_dir, "checkpoint"))
+
+
+def save_checkpoint(prefix, weights, inital_theta=None, mean_var=None, optimizers=None, save_counter=1, update_state=True):
+    """Write ``prefix.index`` / ``prefix.data-00000-of-00001`` (``prefix`` = ``<dir>/ckpt-N``) and, with ``update_state``, name it in
+    ``<dir>/checkpoint``.
+
+    weights: the Keras-layout dict of ``load_encoder`` + ``load_regressor`` (+ ``load_critic``'s ``critic/...`` keys; without them the
+    checkpoint has no ``discriminator``).  inital_theta [1,85]: the reference's untrained ``theta_prev``; mean_var [85] or [1,85]: the
+    trained mean theta (see above).  optimizers: {"generator_optimizer" | "discriminator_optimizer": {"iterations", "learning_rate",
+    "beta_1", "beta_2", "decay" (default 0), "slots": {project key: {"m": array, "v": array}}}} where a project key is a key of
+    ``weights`` or "mean_var" (``flat_slots`` splits a flat optimiser tensor into them); a variable without slots simply has none.
+    -> prefix"""
+    prefix = str(prefix)
+    g = _GraphBuilder()
+    tensors = {}
+    opt_nodes = {}
+    # breadth-first: the root's children first, in the reference's constructor order
+    roots = {}
+    for name in OPTIMIZER_ROOTS:
+        if optimizers and name in optimizers:
+            roots[name] = opt_nodes[name] = g.child(0, name)
+    has_critic = any(k.startswith("critic/") for k in weights)
+    for name in ("feature_extractor", "generator3d") + (("discriminator",) if has_critic else ()):
+        roots[name] = g.child(0, name)
+    var_nodes = {}  # project key -> (node id, object path)
+
+    def put(parent, local, full, path, value, dtype, key=None):
+        ckey = path + VAR_SUFFIX
+        nid = g.variable(parent, local, full, ckey)
+        tensors[ckey] = np.asarray(value, dtype)
+        if key is not None:
+            var_nodes[key] = (nid, path)
+
+    if inital_theta is not None:
+        put(0, "inital_theta", "mean_param", "inital_theta", np.asarray(inital_theta, np.float32).reshape(1, 85), np.float32)
+    if mean_var is not None:
+        put(0, "mean_var", "mean_param_1", "mean_var", np.asarray(mean_var, np.float32).reshape(1, 85), np.float32, key="mean_var")
+    put(0, "save_counter", "save_counter", "save_counter", int(save_counter), np.int64)
+    for name, node in opt_nodes.items():
+        o = optimizers[name]
+        put(node, "iter", "Adam/iter", name + "/iter", int(o["iterations"]), np.int64)
+        for h in _HYPER:
+            put(node, h, "Adam/" + h, "%s/%s" % (name, h), float(o.get(h, 0.0)), np.float32)
+    layers = {}
+    model_vars = [mv for mv in _model_variables() if mv[0] in roots]
+    for root, path, _full, _key in model_vars:  # the layer objects of each network ...
+        lname = path.split("/")[0]
+        if (root, lname) not in layers:
+            layers[root, lname] = g.child(roots[root], lname)
+    for root, path, full, key in model_vars:  # ... then their variables
+        if key not in weights:
+            raise KeyError("weights has no %s" % key)
+        lname, var = path.split("/")
+        put(layers[root, lname], var, full, "%s/%s" % (root, path), weights[key], np.float32, key=key)
+    for name, node in opt_nodes.items():
+        for key, mv in optimizers[name].get("slots", {}).items():
+            if key not in var_nodes:
+                raise KeyError("optimiser slots for %s, which is not a saved variable" % key)
+            nid, path = var_nodes[key]
+            shape = tensors[path + VAR_SUFFIX].shape
+            for s in ("m", "v"):
+                ckey = "%s/.OPTIMIZER_SLOT/%s/%s%s" % (path, name, s, VAR_SUFFIX)
+                a = np.asarray(mv[s], np.float32)
+                if a.size != int(np.prod(shape, dtype=np.int64)):
+                    raise ValueError("slot %s of %s holds %d values, the variable %s" % (s, key, a.size, shape))
+                tensors[ckey] = a.reshape(shape)
+                g.slot(node, nid, s, "Adam/%s/%s" % (g.attrs[nid][0], s), ckey)
+    tensors[OBJECT_GRAPH_KEY] = g.serialize()
+    os.makedirs(os.path.dirname(prefix) or ".", exist_ok=True)
+    write_bundle(prefix, tensors)
+    if update_state:
+        write_checkpoint_state(os.path.dirname(prefix) or ".", os.path.basename(prefix))
+    return prefix
+
+
+def _flat_tables():
+    """{"encoder" | "regressor" | "critic": ([(project key, offset, size)], total floats)} of the three flat layouts"""
+    from . import critic_spec, regressor_spec, resnet_spec
+
+    enc = []
+    for s, off in zip(CONV_SPECS, resnet_spec.ENCODER_PARAM_OFFSETS):
+        sizes = (s.kh * s.kw * s.cin * s.cout, s.cout, s.cout, s.cout)
+        enc += [(k, o, n) for k, o, n in zip(resnet_spec._flat_keys(s), off, sizes)]
+    reg = [("mean_var" if k == "mean_theta" else k, o, int(np.prod(shp))) for k, o, shp in regressor_spec.flat_layout()]
+    cri = [(k, o, int(np.prod(shp))) for k, o, shp in critic_spec.flat_layout()]
+    return {"encoder": (enc, resnet_spec.ENCODER_PARAM_FLOATS), "regressor": (reg, regressor_spec.PARAM_FLOATS), "critic": (cri, critic_spec.PARAM_FLOATS)}
+
+
+def flat_slots(layout, m, v):
+    """the moments of one flat optimiser tensor (``layout``: "encoder" = resnet_spec, "regressor" = regressor_spec with mean theta as
+    "mean_var", "critic" = critic_spec) -> {project key: {"m", "v"}} as ``save_checkpoint`` takes them"""
+    table, total = _flat_tables()[layout]
+    m, v = (np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, np.float32).reshape(-1) for a in (m, v))
+    if m.size != total or v.size != total:
+        raise ValueError("%s moments must hold %d floats" % (layout, total))
+    return {k: {"m": m[o:o + n], "v": v[o:o + n]} for k, o, n in table}
+
+
+def _graph_slots(blob):
+    """[(optimizer node id, original node id, slot name, slot node id)]: the slot_variables records of every node"""
+    out = []
+    node = 0
+    for fn, _wt, val in _proto_fields(blob):
+        if fn != 1:
+            continue
+        for fn2, _w2, v2 in _proto_fields(val):
+            if fn2 == 3:
+                rec = {1: 0, 2: b"", 3: 0}
+                for fn3, _w3, v3 in _proto_fields(v2):
+                    rec[fn3] = v3
+                out.append((node, rec[1], rec[2].decode("utf-8"), rec[3]))
+        node += 1
+    return out
+
+
+@_guard
+def load_training_state(prefix_or_dir, verify=True):
+    """What a resumed run needs besides the weights: per optimiser of the reference's checkpoint its ``iter``, its hyper-parameters and
+    its moments, mapped back to the flat layouts.  ->
+    {"prefix", "save_counter", "mean_var" ([85] or None),
+     "generator_optimizer": {"iter", "learning_rate", "beta_1", "beta_2", "decay", "slots": {project key: {"m", "v"}},
+                             "encoder": {"m", "v"} (flat, resnet_spec) or None, "regressor": {"m", "v"} (flat, regressor_spec) or None,
+                             "missing": [project keys of those layouts without slots: zeros in the flat tensors]},
+     "discriminator_optimizer": {..., "critic": {"m", "v"} (flat, critic_spec) or None, "missing": [...]}}
+    A checkpoint with weights but no optimiser state (a weights-only export; the reference restores such a file with
+    ``expect_partial()`` and starts fresh moments) raises CheckpointError: the caller decides to start fresh."""
+    prefix = str(prefix_or_dir)
+    if os.path.isdir(prefix):
+        p = latest_checkpoint(prefix)
+        if p is None:
+            raise FileNotFoundError("no TensorFlow checkpoint state in %s" % prefix)
+        prefix = p
+    rd = BundleReader(prefix, verify=verify)
+    if OBJECT_GRAPH_KEY not in rd:
+        raise CheckpointError("%s has no optimiser state (no object graph)" % prefix)
+    blob = rd.get(OBJECT_GRAPH_KEY)
+    graph = ObjectGraph(blob)
+    records = _graph_slots(blob)
+    opt_ids = {name: graph.child(0, name) for name in OPTIMIZER_ROOTS}
+    if all(v is None for v in opt_ids.values()) or not records:
+        raise CheckpointError("%s has weights but no optimiser state (no generator_optimizer / discriminator_optimizer slots): "
+                              "start fresh moments" % prefix)
+    # node id -> project key, through the Keras names as load_hmr_weights / load_critic_weights resolve them
+    key_of = {}
+    known = {s.name for s in CONV_SPECS} | {s.bn_name for s in CONV_SPECS}
+
+    def layer_vars(root):
+        rid = graph.child(0, root)
+        if rid is None:
+            return
+        for lname, nid in graph.nodes[rid]["children"].items():
+            m = re.fullmatch(r"layer_with_weights-(\d+)", lname)
+            if m:
+                for var, vid in graph.nodes[nid]["children"].items():
+                    v = graph.variable(vid)
+                    if v is not None:
+                        yield int(m.group(1)), var, vid, v[0], v[1]
+
+    for _i, var, vid, full, _ck in layer_vars("feature_extractor"):
+        layer = full.split("/")[-2] if "/" in full else ""
+        layer = layer if layer in known else (_modern_to_legacy(layer) or layer)
+        if layer in known:
+            key_of[vid] = "%s/%s" % (layer, var)
+    for i, var, vid, _full, _ck in layer_vars("generator3d"):
+        if i < 3 and var in ("kernel", "bias"):
+            key_of[vid] = "dense_%d/%s" % (i, var)
+    by_shape = {shape: name for name, shape in CRITIC_SHAPES.items()}
+    crit = {}
+    for i, var, vid, full, ck in layer_vars("discriminator"):
+        crit.setdefault(i, {})[var] = (vid, full, ck)
+    for i, d in crit.items():
+        layer = d["kernel"][1].split("/")[-2] if "kernel" in d and "/" in d["kernel"][1] else ""
+        if layer not in CRITIC_SHAPES and "kernel" in d and d["kernel"][2] in rd:
+            layer = by_shape.get(tuple(rd.shape(d["kernel"][2])), "")
+        if layer in CRITIC_SHAPES:
+            for var, (vid, _f, _c) in d.items():
+                key_of[vid] = "critic/%s/%s" % (layer, var)
+    mv = graph.child(0, "mean_var")
+    if mv is not None:
+        key_of[mv] = "mean_var"
+    out = {"prefix": prefix, "save_counter": None, "mean_var": None}
+    sc = graph.child(0, "save_counter")
+    if sc is not None and graph.variable(sc) is not None:
+        out["save_counter"] = int(rd.get(graph.variable(sc)[1]).reshape(-1)[0])
+    if mv is not None and graph.variable(mv) is not None:
+        out["mean_var"] = rd.get(graph.variable(mv)[1]).reshape(-1)
+    tables = _flat_tables()
+    for name, oid in opt_ids.items():
+        if oid is None:
+            continue
+        st = {"slots": {}, "missing": []}
+        for h in ("iter",) + _HYPER:
+            hid = graph.child(oid, h)
+            v = graph.variable(hid) if hid is not None else None
+            val = rd.get(v[1]) if v is not None else None
+            st[h] = None if val is None else (int(val.reshape(-1)[0]) if h == "iter" else float(val.reshape(-1)[0]))
+        if st["iter"] is None:
+            raise CheckpointError("%s: %s has no iter" % (prefix, name))
+        for onode, orig, sname, sid in records:
+            if onode != oid or orig not in key_of or sname not in ("m", "v"):
+                continue
+            v = graph.variable(sid) if 0 <= sid < len(graph.nodes) else None
+            if v is None:
+                raise CheckpointError("%s: slot variable node %d of %s holds no value" % (prefix, sid, name))
+            st["slots"].setdefault(key_of[orig], {})[sname] = rd.get(v[1])
+        for key, mvs in st["slots"].items():
+            if set(mvs) != {"m", "v"}:
+                raise CheckpointError("%s: %s has only one of the slots m and v for %s" % (prefix, name, key))
+        for layout in (("encoder", "regressor") if name == "generator_optimizer" else ("critic",)):
+            table, total = tables[layout]
+            if not any(k in st["slots"] for k, _o, _n in table):
+                st[layout] = None
+                continue
+            flat = {"m": np.zeros(total, np.float32), "v": np.zeros(total, np.float32)}
+            for k, o, n in table:
+                if k not in st["slots"]:
+                    st["missing"].append(k)
+                    continue
+                for s in ("m", "v"):
+                    a = st["slots"][k][s]
+                    if a.size != n:
+                        raise CheckpointError("%s: slot %s of %s holds %d values, expected %d" % (prefix, s, k, a.size, n))
+                    flat[s][o:o + n] = a.reshape(-1)
+            st[layout] = flat
+        out[name] = st
+    if not any(out.get(n, {}).get("slots") for n in OPTIMIZER_ROOTS):
+        raise CheckpointError("%s has weights but no optimiser state (its optimisers hold no slots): start fresh moments" % prefix)
+    return out

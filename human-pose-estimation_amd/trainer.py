@@ -1,0 +1,354 @@
+"""Trainer -- the reference's training driver (src/trainer.py:40-870) without TensorBoard and without drawing: ``train_step`` is
+``GeneratorTrainer.step`` (encoder with batch statistics, IEF loop, losses, gradient, update) followed by
+``CriticTrainer.step_from_thetas``, both with the reference's optimiser (``KerasAdam``: one for the encoder, the regressor and mean theta,
+one for the critic); ``train`` is the reference's loop; ``save`` / ``restore`` write and read the reference's ``tf.train.Checkpoint``
+layout (tf_checkpoint.save_checkpoint / load_training_state), optimiser moments and step counts included, so a run resumes with the bits
+of one that was never interrupted.
+
+Not here: TensorBoard event files, ``draw_results``, the bone-length evaluation, multi-GPU training.  ``generated_verts``
+is not among ``train_step``'s result keys (only drawing read it).  ``use_kpr_loss`` decides, as in the reference, only whether the
+keypoint loss is logged: it is always minimised."""
+from __future__ import annotations
+
+import os
+import time
+
+import numpy as np
+
+from . import critic_spec, regressor_spec, resnet_spec, tf_checkpoint
+from .critic_train import CRITIC_LR, CriticTrainer
+from .generator_train import GENERATOR_LR, GeneratorTrainer
+
+SAVE_EVERY = 5  # epochs (src/trainer.py:835)
+
+
+def run_training_loop(batches, train_step, num_images, batch_size, max_epoch, val_step=None, validation_step_size=0, save=None,
+                      save_every=SAVE_EVERY, summarize=None, log=print):
+    """The bookkeeping of the reference's loop (src/trainer.py:715-868), free of any engine.  batches: an iterable of
+    (generator batch, critic batch, validation batch) that normally never ends; train_step(generator batch, critic batch) -> result;
+    val_step(validation batch) -> result, called after every ``validation_step_size``-th step when given; save(epoch) when the finished
+    epoch count is a multiple of ``save_every``; summarize(epoch, train results, validation results) -> the text of the epoch's line.
+    ``num_itr_per_epoch = max(num_images / batch_size, 1)`` is NOT rounded: the epoch rolls at the first step count that reaches it.
+    Stops after ``max_epoch`` epochs (or when ``batches`` ends).  -> {"steps", "epochs", "saved": [epochs], "validations"}"""
+    num_itr_per_epoch = max(float(num_images) / float(batch_size), 1.0)
+    step = itr = epoch = validations = 0
+    saved, train_results, val_results = [], [], []
+    log("Starting epoch 0")
+    start_time = time.time()
+    if max_epoch <= 0:
+        return {"steps": 0, "epochs": 0, "saved": saved, "validations": 0}
+    for gen_batch, critic_batch, val_batch in batches:
+        if itr == 0:
+            start_time = time.time()
+        train_results.append(train_step(gen_batch, critic_batch))
+        step += 1
+        if val_step is not None and validation_step_size > 0 and step % validation_step_size == 0:
+            val_results.append(val_step(val_batch))
+            validations += 1
+        itr += 1
+        if itr >= num_itr_per_epoch:
+            end_time = time.time()
+            itr = 0
+            epoch += 1
+            if save is not None and epoch % save_every == 0:
+                save(epoch)
+                saved.append(epoch)
+            log(summarize(epoch - 1, train_results, val_results) if summarize is not None else "Finished epoch %d" % (epoch - 1))
+            train_results, val_results = [], []
+            if epoch >= max_epoch:
+                break
+            log("Starting epoch {}, approx finished in {:04.2f} min".format(epoch, (max_epoch - epoch) * (end_time - start_time) / 60.0))
+    return {"steps": step, "epochs": epoch, "saved": saved, "validations": validations}
+
+
+def _repeat(dataset):
+    """batches of an iterable dataset, over and over (the reference's ``.repeat()``)"""
+    while True:
+        empty = True
+        for batch in dataset:
+            empty = False
+            yield batch
+        if empty:
+            raise ValueError("a dataset yields no batch (fewer records than one batch?)")
+
+
+class Trainer(object):
+    def __init__(self, config, dataset, mocap_dataset, val_dataset=None, validation_only=False, log=print, generator=None,
+                 **predictor_args):
+        """config: read by attribute like the reference's -- ``batch_size``, ``epoch``, ``generator_lr``, ``critic_lr``,
+        ``kpr_loss_weight``, ``mr_loss_weight``, ``critic_loss_weight``, ``use_kpr_loss``, ``use_mesh_repro_loss``, ``encoder_only``,
+        ``use_validation``, ``validation_step_size``, ``train_from_checkpoint``, ``checkpoint_dir``, plus what ``Predictor`` reads (the
+        SMPL model, the mean parameters and the starting weights: ``predictor_args`` are passed on).  dataset / val_dataset:
+        ``RecordDataset``s of image records (batch size ``config.batch_size``) or any iterable of what ``load_training_batch`` takes;
+        mocap_dataset: a ``RecordDataset(..., parse=parse_mocap_example)`` of ``batch_size * num_stage`` rows or any iterable of lists
+        of (pose [72], shape [10]).  ``config.num_images`` (default: counted once from the dataset) sets the epoch length.  generator:
+        the torch.Generator (CUDA) of the dropout and interpolation draws; the augmentation draws come from ``config.augment_seed``.
+        validation_only: no trainers are built (``validate_checkpoint`` / ``val_step`` only)."""
+        import torch
+
+        from .predictor import Predictor
+
+        g = lambda name, default: getattr(config, name, default)  # noqa: E731
+        self.config, self.log = config, log
+        self.batch_size, self.max_epoch = int(g("batch_size", 8)), int(g("epoch", 125))
+        self.generator_lr, self.critic_lr = float(g("generator_lr", GENERATOR_LR)), float(g("critic_lr", CRITIC_LR))
+        self.kpr_loss_weight, self.mr_loss_weight = float(g("kpr_loss_weight", 60.0)), float(g("mr_loss_weight", 0.001))
+        self.critic_loss_weight = float(g("critic_loss_weight", 0.01))
+        self.use_kpr_loss, self.use_mesh_repro_loss = bool(g("use_kpr_loss", True)), bool(g("use_mesh_repro_loss", False))
+        self.encoder_only, self.use_validation = bool(g("encoder_only", False)), bool(g("use_validation", True))
+        self.val_step_size = int(g("validation_step_size", 50))
+        self.train_from_checkpoint, self.checkpoint_dir = bool(g("train_from_checkpoint", False)), g("checkpoint_dir", None)
+        self.model_dir = g("model_dir", None)
+        self.dataset, self.mocap_dataset, self.val_dataset = dataset, mocap_dataset, val_dataset
+        self.use_validation = self.use_validation and val_dataset is not None
+        self.predictor = Predictor(config, **predictor_args)
+        self.engine = eng = self.predictor.engine
+        self.num_stage = self.predictor.num_stage
+        self.inital_theta = np.asarray(self.predictor.load_mean_param(), np.float32).reshape(1, 85)  # the reference's untrained theta_prev
+        self.save_counter = 0
+        self._aug = torch.Generator().manual_seed(int(g("augment_seed", 0)))
+        self.generator = self.critic = None
+        if validation_only:
+            return
+        if not self.encoder_only and not eng.has_critic:
+            raise RuntimeError("Trainer needs critic weights to start from (critic_params=, config.critic_params, critic/... keys of the "
+                               "weights, or a checkpoint with a discriminator) unless config.encoder_only is set")
+        eng.reserve_encoder_train(self.batch_size, batch_norm=True)
+        self.generator = GeneratorTrainer(eng, lr=self.generator_lr, kpr_loss_weight=self.kpr_loss_weight, mr_loss_weight=self.mr_loss_weight,
+                                          critic_loss_weight=self.critic_loss_weight, generator=generator, train_encoder=True,
+                                          encoder_bn="batch", optimizer="keras")
+        if not self.encoder_only:
+            self.critic = CriticTrainer(eng, lr=self.critic_lr, generator=generator, optimizer="keras")
+
+    # ------------------------------------------------------------------ steps
+    def train_step(self, images, seg_gts, kp_gt, joints=None, shapes=None, Rs=None, drop="draw", interp=None):
+        """One update of the generator, then one of the critic on the thetas it produced (src/trainer.py:383-583).  images
+        [B,224,224,3], seg_gts [B,224,224(,1)], kp_gt [B,19,3]; joints / shapes / Rs: the real triple of ``mocap_real`` (B * num_stage
+        or B rows), unused with ``encoder_only``.  drop / interp: fixed dropout multipliers and interpolation draws (tests).
+        -> the reference's result keys: kpr_losses, mr_losses (with ``use_mesh_repro_loss``), pred_keypoints, generated_cams and, unless
+        ``encoder_only``, generator_critic_losses, critic_penalty, critic_network_loss; plus ``thetas``.  Nothing reads the device."""
+        if self.generator is None:
+            raise RuntimeError("this Trainer was built with validation_only")
+        r = self.generator.step(images, kp_gt, seg_gts if self.use_mesh_repro_loss else None, use_critic=not self.encoder_only, drop=drop)
+        result = {"kpr_losses": r["kpr_losses"], "pred_keypoints": r["pred_keypoints"], "generated_cams": r["generated_cams"],
+                  "thetas": r["thetas"]}
+        if self.use_mesh_repro_loss:
+            result["mr_losses"] = r["mr_losses"]
+        if not self.encoder_only:
+            c = self.critic.step_from_thetas((joints, shapes, Rs), r["thetas"], interp=interp)
+            result["generator_critic_losses"] = r["generator_critic_losses"]
+            result["critic_penalty"], result["critic_network_loss"] = c["critic_penalty"], c["critic_network_loss"]
+        return result
+
+    def val_step(self, images, seg_gts, kp2d_gts):
+        return self.predictor.val_step(images, seg_gts, kp2d_gts, use_mesh_repro_loss=self.use_mesh_repro_loss,
+                                       kpr_loss_weight=self.kpr_loss_weight, mr_loss_weight=self.mr_loss_weight)
+
+    # ------------------------------------------------------------------ data
+    def _load_images(self, records, augment=True):
+        from .augment import draw_augmentation
+        from .records import load_training_batch
+
+        if isinstance(records, (tuple, list)) and len(records) == 3 and hasattr(records[0], "is_cuda"):
+            return records  # an (images, seg_gts, kp_gt) triple, ready
+        if augment:
+            return load_training_batch(records, generator=self._aug)
+        draws = draw_augmentation(len(records), trans_max=0, scale_range=(1.0, 1.0))  # validation: centre crop, no jitter, no flip
+        draws["flip"][:] = False
+        return load_training_batch(records, draws=draws)
+
+    def _load_mocap(self, rows):
+        import torch
+
+        from .augment import mocap_real
+
+        if isinstance(rows, (tuple, list)) and len(rows) == 3 and hasattr(rows[0], "is_cuda"):
+            return rows
+        poses = torch.from_numpy(np.stack([np.asarray(p, np.float32) for p, _s in rows])).to(self.engine.tdev)
+        shapes = torch.from_numpy(np.stack([np.asarray(s, np.float32) for _p, s in rows])).to(self.engine.tdev)
+        return mocap_real(self.engine, poses, shapes)
+
+    def _num_images(self):
+        n = getattr(self.config, "num_images", None)
+        if n is not None:
+            return int(n)
+        if hasattr(self.dataset, "paths"):
+            from .records import read_tfrecords
+
+            return sum(1 for _ in read_tfrecords(self.dataset.paths, False))
+        return len(self.dataset) * self.batch_size
+
+    def _batches(self):
+        gen = _repeat(self.dataset)
+        moc = _repeat(self.mocap_dataset) if not self.encoder_only else None
+        val = _repeat(self.val_dataset) if self.use_validation else None
+        while True:
+            yield next(gen), (next(moc) if moc is not None else None), (next(val) if val is not None else None)
+
+    # ------------------------------------------------------------------ the loop
+    def _summarize(self, epoch, train_results, val_results):
+        """the reference's line (src/trainer.py:838-852); every device scalar of the epoch is read here, in one transfer"""
+        import torch
+
+        cols = []
+        if self.use_kpr_loss:
+            cols.append(("kpr", "{:04.2f}", [r["kpr_losses"][-1] for r in train_results]))
+        if self.use_mesh_repro_loss:
+            cols.append(("mr", "{:05.2f}", [r["mr_losses"][-1] for r in train_results]))
+        if not self.encoder_only:
+            cols.append(("gc", "{:05.2f}", [r["generator_critic_losses"][-1] for r in train_results]))
+            cols.append(("cn", "{:05.2f}", [r["critic_network_loss"] for r in train_results]))
+        n_train = len(cols)
+        if self.use_validation:
+            if self.use_kpr_loss:
+                cols.append(("kpr", "{:04.2f}", [r["kpr_losses"][-1] for r in val_results]))
+            if self.use_mesh_repro_loss:
+                cols.append(("mr", "{:05.2f}", [r["mr_losses"][-1] for r in val_results]))
+        flat = [t.reshape(()).float() for _n, _f, ts in cols for t in ts]
+        host = torch.stack(flat).cpu().numpy() if flat else np.zeros(0, np.float32)
+        text, pos = "Finished epoch {}, average losses:".format(epoch), 0
+        for i, (name, fmt, ts) in enumerate(cols):
+            if i == n_train:
+                text += " Validation:"
+            mean = float(np.mean(host[pos:pos + len(ts)])) if ts else float("nan")  # no validation step in this epoch: nan, as np.mean([])
+            pos += len(ts)
+            text += (" %s=" % name) + fmt.format(mean)
+        if self.use_validation and n_train == len(cols):
+            text += " Validation:"
+        return text
+
+    def train(self, save_every=SAVE_EVERY):
+        """the reference's ``train()``: restore when ``train_from_checkpoint``, then epochs of ``num_images / batch_size`` steps with a
+        validation step every ``validation_step_size``, a checkpoint every ``save_every`` epochs and one line per epoch -> the loop's
+        counts"""
+        if self.generator is None:
+            raise RuntimeError("this Trainer was built with validation_only")
+        self.log("started training")
+        if self.train_from_checkpoint:
+            self.log("restore checkpoint")
+            self.restore()
+            self.log("checkpoint restored")
+        self.log("Loading Data")
+
+        def step(gen_batch, critic_batch):
+            images, segs, kp = self._load_images(gen_batch)
+            real = self._load_mocap(critic_batch) if not self.encoder_only else (None, None, None)
+            return self.train_step(images, segs, kp, *real)
+
+        def val(val_batch):
+            return self.val_step(*self._load_images(val_batch, augment=False))
+
+        out = run_training_loop(self._batches(), step, self._num_images(), self.batch_size, self.max_epoch,
+                                val_step=val if self.use_validation else None, validation_step_size=self.val_step_size,
+                                save=lambda epoch: self.save(), save_every=save_every, summarize=self._summarize, log=self.log)
+        self.log("Finish training on %s" % self.model_dir)
+        return out
+
+    def validate_checkpoint(self, restore=True):
+        """the mean keypoint and mesh reprojection losses (last stage, weighted) of the newest checkpoint over ONE pass of the
+        validation set (src/trainer.py:882-960 without the drawing) -> {"kpr_loss", "mr_loss" (None without the mesh loss), "batches"}"""
+        import torch
+
+        if self.val_dataset is None:
+            raise RuntimeError("validate_checkpoint needs a validation dataset")
+        if restore:
+            self.restore()
+        kpr, mr = [], []
+        for batch in self.val_dataset:
+            r = self.val_step(*self._load_images(batch, augment=False))
+            kpr.append(r["kpr_losses"][-1])
+            if self.use_mesh_repro_loss:
+                mr.append(r["mr_losses"][-1])
+        if not kpr:
+            raise ValueError("the validation dataset yields no batch")
+        host = torch.stack([t.reshape(()).float() for t in kpr + mr]).cpu().numpy()
+        return {"kpr_loss": float(host[:len(kpr)].mean()), "mr_loss": float(host[len(kpr):].mean()) if mr else None, "batches": len(kpr)}
+
+    # ------------------------------------------------------------------ checkpoints
+    def weights(self):
+        """the live networks as the Keras-layout dict (host arrays): encoder with its moving statistics, regressor, critic, and
+        ``mean_theta``"""
+        gen = self.generator
+        w = resnet_spec.flat_to_params(gen.encoder_params, resnet_spec.stats_to_params(gen.encoder_stats))
+        w.update(regressor_spec.flat_to_params(gen.params))
+        if self.critic is not None:
+            w.update(critic_spec.flat_to_params(self.critic.params))
+        return w
+
+    def save(self):
+        """``checkpoint.save(checkpoint_prefix)``: ``<checkpoint_dir>/ckpt-N`` with N = the save counter -> the prefix"""
+        if self.generator is None:
+            raise RuntimeError("this Trainer was built with validation_only")
+        if not self.checkpoint_dir:
+            raise RuntimeError("config.checkpoint_dir is not set")
+        w = self.weights()
+        mean = w.pop("mean_theta")
+        sd = self.generator.optimizer.state_dict()
+        slots = tf_checkpoint.flat_slots("encoder", sd["slots"]["encoder"]["m"], sd["slots"]["encoder"]["v"])
+        slots.update(tf_checkpoint.flat_slots("regressor", sd["slots"]["regressor"]["m"], sd["slots"]["regressor"]["v"]))
+        opts = {"generator_optimizer": dict(sd, slots=slots)}
+        if self.critic is not None:
+            sd = self.critic.optimizer.state_dict()
+            opts["discriminator_optimizer"] = dict(sd, slots=tf_checkpoint.flat_slots("critic", sd["slots"]["critic"]["m"], sd["slots"]["critic"]["v"]))
+        self.save_counter += 1
+        os.makedirs(self.checkpoint_dir, exist_ok=True)
+        return tf_checkpoint.save_checkpoint(os.path.join(self.checkpoint_dir, "ckpt-%d" % self.save_counter), w, inital_theta=self.inital_theta,
+                                             mean_var=mean, optimizers=opts, save_counter=self.save_counter)
+
+    def restore(self, prefix_or_dir=None, verify=True):
+        """``checkpoint.restore(latest_checkpoint(checkpoint_dir))``: weights, moving statistics, mean theta, optimiser moments and step
+        counts into the live engine and trainers, on the device.  The learning rates stay the configuration's.  A checkpoint without
+        optimiser state restores the weights and keeps fresh moments (the reference's ``expect_partial()``).  -> the prefix"""
+        import torch
+
+        src = prefix_or_dir if prefix_or_dir is not None else self.checkpoint_dir
+        w, info = tf_checkpoint.load_hmr_weights(src, verify=verify)
+        prefix = info["prefix"]
+        eng, dev = self.engine, self.engine.tdev
+        mean = np.asarray(w["mean_var"], np.float32).reshape(-1) if "mean_var" in w else self.inital_theta.reshape(-1)
+        reg_flat = torch.from_numpy(regressor_spec.params_to_flat(w, mean)).to(dev)
+        enc_flat = torch.from_numpy(resnet_spec.params_to_flat(w)).to(dev)
+        stats = torch.from_numpy(resnet_spec.params_to_stats(w)).to(dev)
+        try:
+            cw = tf_checkpoint.load_critic_weights(prefix, verify=verify)[0]
+        except tf_checkpoint.NoCriticError:
+            cw = None
+        if self.generator is None:  # validation only: no trainers to fill, the engine alone
+            eng.set_encoder_params(enc_flat)
+            eng.set_regressor_params(reg_flat)
+            if cw is not None:
+                eng.load_critic(cw)
+            if not torch.equal(stats, eng.encoder_stats()):
+                raise RuntimeError("validation_only: the checkpoint's moving statistics differ from the ones this engine was built with; "
+                                   "build the Trainer with config.checkpoint_dir naming the checkpoint")
+            return prefix
+        gen = self.generator
+        with torch.no_grad():
+            gen.params.copy_(reg_flat)
+            gen.encoder_params.copy_(enc_flat)
+            gen.encoder_stats.copy_(stats)
+        eng.set_regressor_params(gen.params)
+        eng.set_encoder_params_dev(gen.encoder_params)
+        eng.set_encoder_stats_dev(gen.encoder_stats)
+        if self.critic is not None:
+            if cw is None:
+                raise tf_checkpoint.NoCriticError("%s has no discriminator to resume the critic from" % prefix)
+            with torch.no_grad():
+                self.critic.params.copy_(torch.from_numpy(critic_spec.params_to_flat(cw)).to(dev))
+            eng.set_critic_params(self.critic.params)
+        try:
+            st = tf_checkpoint.load_training_state(prefix, verify=verify)
+        except tf_checkpoint.CheckpointError as e:
+            if "no optimiser state" not in str(e):
+                raise
+            self.log("no optimiser state in %s: starting fresh moments" % prefix)
+            return prefix
+        go = st.get("generator_optimizer")
+        if go is not None and go["encoder"] is not None and go["regressor"] is not None:
+            gen.optimizer.load_state_dict({"iterations": go["iter"], "slots": {"encoder": go["encoder"], "regressor": go["regressor"]}}, hyper=False)
+        do = st.get("discriminator_optimizer")
+        if self.critic is not None and do is not None and do["critic"] is not None:
+            self.critic.optimizer.load_state_dict({"iterations": do["iter"], "slots": {"critic": do["critic"]}}, hyper=False)
+        if st["save_counter"] is not None:
+            self.save_counter = int(st["save_counter"])
+        return prefix

@@ -548,6 +548,24 @@ int hpe_augment_batch(const unsigned char* frames_dev, const unsigned char* segs
                       const HpeAugmentFrame* table_dev, const float* kp_dev, int B, float* images_out, float* seg_out, float* kp_out,
                       void* stream);
 
+/* -- the optimiser: tf.keras.optimizers.Adam = TensorFlow's fused ResourceApplyAdam (src/trainer.py:183-184) ------------------
+ *     alpha = lr * sqrt(1 - beta2^t) / (1 - beta1^t)
+ *     m += (g - m) * (1 - beta1);  v += (g * g - v) * (1 - beta2);  p -= (m * alpha) / (sqrt(v) + eps)
+ * No ctx: every call takes a stream, launches, and returns; nothing reads the host, so a step is stream-ordered and capturable.
+ * state_dev: 4 doubles {t, beta1^t, beta2^t, alpha} on the device; a fresh optimiser is {0, 1, 1, 0}.  HPE_ERR_INVALID for a NULL
+ * pointer, a beta outside [0, 1), a lr that is not finite, t < 0 or n < 0. */
+/* One single-thread launch: t += 1, both powers from t by square-and-multiply in double, alpha in double. */
+int hpe_adam_advance(double* state_dev, double lr, double beta1, double beta2, void* stream);
+/* One launch over n elements of p, m, v (updated in place) and g, in float32 in the order above, alpha rounded once to float.  Every
+ * element gets the bits of the same lines in IEEE float32 whatever its position, n, or the alignment of the pointers (16-byte aligned
+ * pointers take 16-byte loads and stores, anything else a scalar kernel).  n == 0 succeeds and launches nothing. */
+int hpe_adam_apply(float* p, float* m, float* v, const float* g, long long n, const double* state_dev, float one_minus_beta1,
+                   float one_minus_beta2, float eps, void* stream);
+/* Resume: t and both powers as hpe_adam_advance would have left them after t steps; alpha is 0 until the next hpe_adam_advance. */
+int hpe_adam_set_step(double* state_dev, long long t, double beta1, double beta2, void* stream);
+/* The host build of the power helper of the two calls above: *out = beta^t (t >= 0), square-and-multiply in double.  No device needed. */
+int hpe_debug_adam_power(double beta, long long t, double* out);
+
 /* -- JPEG decode: tf.image.decode_jpeg(buf, channels) of the training records (src/util/data_utils.py:129-141) ---------------
  * Baseline sequential DCT streams only (SOF0, 8-bit samples and quantisation tables, 1 or 3 components, luma sampling 1x1, 2x1 or
  * 2x2 with 1x1 chroma, one interleaved scan, DRI / RST, any DHT).  Everything else is refused with HPE_ERR_INVALID and a message that
