@@ -240,7 +240,7 @@ const void* packing_of(hpe_ctx* c, int idx, int which, size_t* bytes) {
         case HPE_PACK_SHIFT_DUAL: p = L.shift_dual, n = (size_t)s.cout * 4; break;
         case HPE_PACK_DXW: p = c->et.dxw[idx], n = conv_dxw_floats(idx) * 4; break;
         case HPE_PACK_FLAT:
-            if (c->et.flat) p = c->et.flat + hpe_encoder_param_offset(idx, 0);
+            if (c->et.flat) p = c->et.flat + layout().off[idx][0];
             n = ((size_t)s.kh * s.kw * s.cin * s.cout + 3 * (size_t)s.cout) * 4;
             break;
     }
@@ -254,7 +254,6 @@ size_t encoder_repack_reserve_floats() { return (sizeof(RepackTable) + 3) / 4; }
 
 int encoder_repack_reserve(hpe_ctx* c) {
     RepackTable t{};
-    int stat = 0;
     for (int i = 0; i < HPE_NUM_CONV; ++i) {
         const ConvSpec& s = specs()[i];
         const ConvLayer& L = c->conv[i];
@@ -271,9 +270,8 @@ int encoder_repack_reserve(hpe_ctx* c) {
         r.cout = s.cout;
         r.n_pad = L.n_pad;
         r.k_pad = L.k_pad;
-        for (int w = 0; w < 4; ++w) r.off[w] = hpe_encoder_param_offset(i, w);
-        r.stat = stat;
-        stat += s.cout;
+        for (int w = 0; w < 4; ++w) r.off[w] = layout().off[i][w];
+        r.stat = layout().stat[i];
         // what the kernels take for granted: square kernels, whole [64][4] blocks in the Winograd layouts, whole row tiles
         if (s.kh != s.kw || L.n_pad % TILE_N != 0 || ((L.wino_u || L.wino4_u) && (s.cin % 8 != 0 || s.cout % 64 != 0)))
             return fail(HPE_ERR_STATE, std::string("encoder repack: unexpected geometry of ") + s.name);
@@ -331,13 +329,13 @@ hipError_t encoder_repack_launch(hpe_ctx* c, const float* flat, hipStream_t st) 
     if (grid[F_BN]) hipLaunchKernelGGL(repack_bn_kernel, dim3(grid[F_BN]), dim3(256), 0, st, T, flat, w.mean, w.sd);
     if (c->conv[0].stem_w)
         hipLaunchKernelGGL(repack_stem_kernel, grid1(64 * 224), dim3(256), 0, st, static_cast<unsigned short*>(c->conv[0].stem_w),
-                           flat + hpe_encoder_param_offset(0, 0));
+                           flat + layout().off[0][0]);
     if (grid[F_WINO]) hipLaunchKernelGGL(repack_wino_kernel<4>, dim3(grid[F_WINO]), dim3(256), 0, st, T, flat);
     if (grid[F_WINO4]) hipLaunchKernelGGL(repack_wino_kernel<6>, dim3(grid[F_WINO4]), dim3(256), 0, st, T, flat);
     if (grid[F_DXW]) hipLaunchKernelGGL(repack_dxw_kernel, dim3(grid[F_DXW]), dim3(256), 0, st, T, flat);
     if (grid[F_DUAL]) hipLaunchKernelGGL(repack_dual_kernel, dim3(grid[F_DUAL]), dim3(256), 0, st, T, flat, w.mean, w.sd);
     HIPE(hipGetLastError());
-    return hipMemcpyAsync(w.flat, flat, (size_t)hpe_encoder_param_floats() * sizeof(float), hipMemcpyDeviceToDevice, st);
+    return hipMemcpyAsync(w.flat, flat, (size_t)layout().total * sizeof(float), hipMemcpyDeviceToDevice, st);
 }
 
 hipError_t encoder_repack_stats_launch(hpe_ctx* c, hipStream_t st) {

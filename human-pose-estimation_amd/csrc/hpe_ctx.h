@@ -214,11 +214,22 @@ struct EncTrainWork {
 };
 constexpr int BN_MAX_SLICES = 512;     // pixel slices of one BatchNorm reduction
 constexpr int BN_PART_COLS = 262144;   // slices * channels of one reduction, at most
+constexpr int WG_MAX_SLICES = 128;         // pixel slices of one weight gradient (what the fix-up adds per element)
+constexpr int WG_WGP_FLOATS = 1152 * 512;  // <W, G> per 4-row chunk: K / 4 x N of the largest kernel (3x3, 512 -> 512)
 // floats of layer idx's data-gradient operand: rows = input channels padded to 128, k = (flipped tap, output channel); conv1 has none
 inline size_t conv_dxw_floats(int idx) {
     const ConvSpec& s = specs()[idx];
     return idx == 0 ? 0 : (size_t)round_up(s.cin, 128) * s.kh * s.kw * s.cout;
 }
+// Where each layer sits in the flat parameters, in the per-channel statistics arrays and in the stash (encoder_train.hip)
+struct EncLayout {
+    int off[HPE_NUM_CONV][4];    // kernel, bias, gamma, beta
+    int stat[HPE_NUM_CONV];      // offset into the per-channel statistics arrays
+    size_t stash[HPE_NUM_CONV];  // per-image offset of the layer's output in the stash
+    size_t stash_pool, stash_per_image;
+    int total, channels;
+};
+const EncLayout& layout();
 
 struct hpe_ctx {
     HpeConfig cfg{};
@@ -370,6 +381,21 @@ hipError_t bn_launch_bwd_apply(const float* dy, const float* y, const float* z, 
                                const float* dbeta, int M, int N, float* dz, float* dzraw, hipStream_t st);
 hipError_t bn_launch_momentum(float* stats, const float* batch, const int* hw, int B, int channels, double momentum, int unbiased, hipStream_t st);
 hipError_t bn_launch_install(const float* stats, int channels, float eps, float* keep, float* mean, float* istd, double* sd, hipStream_t st);
+
+// encoder_grad.hip: the launches of the encoder's backward
+// pixels per slice and the slice count of layer idx's weight gradient at batch B; the floats of its partial buffer for every batch up to B
+void wg_slicing(int idx, int B, int* P, int* slices);
+size_t wg_partial_floats(int B);
+// dz = dy * [y > 0] (y == nullptr: no activation), dzs = dz * s.  dz / dzs may be nullptr; dz may alias dy.  n elements, N channels
+void gate(const float* dy, const float* y, const float* s, float* dz, float* dzs, long n, int N, hipStream_t st);
+// the weight gradient of layer idx and what hangs on it, into grad_layer = [kernel | bias | gamma | beta]: three launches.  bn (batch
+// statistics): dz is dzraw, dW = G with a unit scale, and the finish is not launched -- bias, gamma and beta come from bn_launch_bwd_reduce
+hipError_t weight_grad(hpe_ctx* c, int idx, const float* x, const float* dz, int B, float* grad_layer, hipStream_t st, bool bn = false);
+// out [M][cin] = dzs [M][cout] . W^T (+ res) on the map of the layer's OUTPUT (a stride-2 layer: the low-resolution map)
+hipError_t data_grad(hpe_ctx* c, int idx, const float* dzs, int B, const float* res, float* out, hipStream_t st);
+void scatter2(const float* lo, float* hi, int B, int H, int C, hipStream_t st);  // lo [B][H][H][C] -> the even pixels of hi [B][2H][2H][C]
+void avgpool_bwd(const float* dy, float* dx, int B, int HW, int C, hipStream_t st);
+void maxpool_bwd(const float* x, const float* dy, float* dx, int B, int H, int C, hipStream_t st);  // x [B][H][H][C], the pool's input
 
 // regressor_train.hip
 int regressor_param_offset(int idx, bool bias);  // idx 3: mean theta; idx 4 (bias false): the total

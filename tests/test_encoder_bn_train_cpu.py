@@ -75,6 +75,9 @@ def test_stat_layout_matches_library(lib):
     # the raw-output stash is the one thing that grows with the batch: about 11 M floats per image
     grow = lib.hpe_encoder_train_ws_floats_batchnorm(2) - lib.hpe_encoder_train_ws_floats_batchnorm(1)
     assert grow - (lib.hpe_encoder_train_ws_floats(2) - lib.hpe_encoder_train_ws_floats(1)) == sum(s.hout * s.hout * s.cout for s in CONV_SPECS)
+    # both reserves' buffers, added up from the lists they allocate from: the values of commit 03ecb51, which added them up by hand
+    want = {1: 76083504, 2: 100471088, 3: 124858672, 8: 249155888, 64: 1618530608}
+    assert {B: lib.hpe_encoder_train_ws_floats_batchnorm(B) for B in want} == want
     # refusals that need no device
     assert lib.hpe_encoder_train_reserve_batchnorm(None, 1) == 1
     assert lib.hpe_encoder_backward_batchnorm(None, None, 1, None, None, None) == 1

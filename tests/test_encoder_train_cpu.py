@@ -48,6 +48,9 @@ def test_flat_layout_matches_library(lib):
     assert total == resnet_spec.ENCODER_PARAM_FLOATS
     assert lib.hpe_encoder_param_offset(53, 0) == -1 and lib.hpe_encoder_param_offset(0, 4) == -1 and lib.hpe_encoder_param_offset(-1, 0) == -1
     assert lib.hpe_encoder_train_ws_floats(1) > 11_000_000 and lib.hpe_encoder_train_ws_floats(0) == 0
+    # the documented size is added up from the list the reserve allocates from: the values of commit 03ecb51, which added them up by hand
+    want = {1: 64282288, 2: 78082736, 3: 91883184, 8: 163244720, 64: 939739824}
+    assert {B: lib.hpe_encoder_train_ws_floats(B) for B in want} == want
     # conv1 and stage 2 at B = 3 are cut into more than one pixel slice; the 7x7 maps at B = 3 (147 pixels) are not
     assert lib.hpe_encoder_wg_slices(0, 3) > 1 and lib.hpe_encoder_wg_slices(2, 3) > 1 and lib.hpe_encoder_wg_slices(52, 3) == 1
 

@@ -236,6 +236,36 @@ def test_every_batch_below_the_reserve(params):
         e.close()
 
 
+def test_modes_interleave(params):
+    """Both modes run one walk over one set of work buffers: calls of the two modes at different batches, interleaved on one context,
+    give the bits of the same call on a context that has only ever run that mode at that batch"""
+    img = torch.from_numpy(synthetic.make_images(2, seed=5)).cuda()
+    gf = torch.randn(2, 2048, generator=torch.Generator().manual_seed(6)).cuda()
+    calls = [("backward", "batch", 2), ("backward", "frozen", 1), ("backward", "batch", 2), ("backward", "frozen", 2), ("forward", "batch", 1),
+             ("forward", "frozen", 2)]
+
+    def run(e, what, bn, B):
+        if what == "forward":
+            return e.encoder_forward_train(img[:B].contiguous(), bn=bn)
+        return e.encoder_backward(img[:B].contiguous(), gf[:B].contiguous(), bn=bn)
+
+    want = {}
+    for bn, B in sorted({(bn, B) for _, bn, B in calls}):
+        e = make_engine(params, max_batch=2, reserve=B, batch_norm=bn == "batch")
+        try:
+            want.update({c: run(e, *c) for c in calls if c[1:] == (bn, B)})
+        finally:
+            e.close()
+    e = make_engine(params, max_batch=2, reserve=2)
+    try:
+        for c in calls:
+            assert torch.equal(run(e, *c), want[c]), c
+        with pytest.raises(_lib.HpeError, match="refilled the stash"):  # the frozen forward of B = 2, since the batch forward of B = 1
+            e.encoder_stash_raw(1)
+    finally:
+        e.close()
+
+
 def test_refusals(engine, params):
     lib, h = engine.lib, engine._h
     img = torch.zeros(4, 224, 224, 3, device="cuda")
