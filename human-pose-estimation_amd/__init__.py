@@ -26,6 +26,7 @@ from .engine import HpeEngine  # noqa: F401
 from .generator_train import GeneratorTrainer  # noqa: F401
 from .fit import fit_keypoints, fit_reprojection  # noqa: F401
 from .jpeg import DecodedBatch, decode_jpeg_batch, jpeg_info  # noqa: F401
+from .png import decode_image_batch, decode_png_batch, png_info  # noqa: F401
 from .records import RecordDataset, RecordError, load_training_batch, parse_example, parse_image_example, parse_mocap_example, read_tfrecords  # noqa: F401
 from .image import get_original, preprocess_batch, preprocess_image  # noqa: F401
 from .ops import critic_gradient_penalty, critic_scores, critic_wgan_loss, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas, encoder_features  # noqa: F401

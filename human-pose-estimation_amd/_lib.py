@@ -103,6 +103,13 @@ class HpeJpegImage(C.Structure):
                 ("blocks_h", C.c_int * 3), ("idct_group0", C.c_int), ("store_group0", C.c_int), ("quant", C.c_ubyte * 192)]
 
 
+class HpePngImage(C.Structure):
+    """one table entry of hpe_png_backend (include/hpe.h), 64 bytes"""
+    _fields_ = [("raw_offset", C.c_longlong), ("pal_offset", C.c_longlong), ("work_offset", C.c_longlong), ("out_offset", C.c_longlong),
+                ("H", C.c_int), ("W", C.c_int), ("color_type", C.c_int), ("depth", C.c_int), ("channels", C.c_int), ("rowbytes", C.c_int),
+                ("bpp", C.c_int), ("store_group0", C.c_int)]
+
+
 GEMM_DENSE, GEMM_STRIDED, GEMM_CONV3, GEMM_DUAL = 0, 1, 2, 4  # HpeDebugGemm.mode
 GEMM_TILES = ((128, 128), (128, 64), (64, 64), (64, 128), (128, 128), (128, 64), (256, 128))  # (BM, BN) of tile 0..6; 4..6 run 8 waves
 
@@ -183,6 +190,8 @@ _PROTOS = {
     "hpe_jpeg_decode": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_jpeg_backend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
                                    C.c_void_p]),
+    "hpe_png_backend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
+                                  C.c_void_p]),
     "hpe_get_original": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_kp_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_kp_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

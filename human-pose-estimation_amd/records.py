@@ -120,7 +120,7 @@ def _need(feats, key, kind, count):
 
 
 def parse_image_example(payload):
-    """``parse_example_proto`` without the decode: {'image', 'seg': JPEG bytes, 'height', 'width': int, 'center': int64 [2] (x, y),
+    """``parse_example_proto`` without the decode: {'image', 'seg': JPEG or PNG bytes, 'height', 'width': int, 'center': int64 [2] (x, y),
     'filename': bytes, 'kp': float32 [19,3]}.  kp is the 14 image/x, image/y, image/visibility columns followed by image/face_pts
     reshaped [3,5] (all zeros when the record has none: the reference's default).  A missing key or a wrong length raises RecordError
     naming the key."""
@@ -178,17 +178,18 @@ class RecordDataset:
 def load_training_batch(records, draws=None, generator=None, threads=None, **augment_args):
     """Parsed image records (``parse_image_example`` dicts, or serialized payloads) -> the (images [B,224,224,3], seg_gts [B,224,224],
     kp_gt [B,19,3]) CUDA triple that ``GeneratorTrainer.step`` takes: ``image`` decoded with 3 channels and ``seg`` with 1, one
-    ``decode_jpeg_batch`` each, then ``augment_batch`` on the decoded buffers as they are.  draws / generator / further keyword
+    ``decode_image_batch`` each (every stream a JPEG or a PNG, side by side in one batch), then ``augment_batch`` on the decoded buffers as they are.  draws / generator / further keyword
     arguments are ``augment_batch``'s.  A record whose streams do not have its height and width raises RecordError."""
     from .augment import augment_batch
-    from .jpeg import DEFAULT_THREADS, decode_jpeg_batch
+    from .jpeg import DEFAULT_THREADS
+    from .png import decode_image_batch
 
     recs = [parse_image_example(r) if isinstance(r, (bytes, bytearray, memoryview)) else r for r in records]
     if not recs:
         raise ValueError("records is empty")
     threads = DEFAULT_THREADS if threads is None else threads
-    frames = decode_jpeg_batch([r["image"] for r in recs], channels=3, threads=threads)
-    segs = decode_jpeg_batch([r["seg"] for r in recs], channels=1, threads=threads)
+    frames = decode_image_batch([r["image"] for r in recs], channels=3, threads=threads)
+    segs = decode_image_batch([r["seg"] for r in recs], channels=1, threads=threads)
     for i, r in enumerate(recs):
         for what, d in (("image/encoded", frames), ("image/seg_gt", segs)):
             if tuple(d.sizes[i]) != (r["height"], r["width"]):

@@ -79,7 +79,9 @@ class Trainer(object):
         ``kpr_loss_weight``, ``mr_loss_weight``, ``critic_loss_weight``, ``use_kpr_loss``, ``use_mesh_repro_loss``, ``encoder_only``,
         ``use_validation``, ``validation_step_size``, ``train_from_checkpoint``, ``checkpoint_dir``, plus what ``Predictor`` reads (the
         SMPL model, the mean parameters and the starting weights: ``predictor_args`` are passed on).  dataset / val_dataset:
-        ``RecordDataset``s of image records (batch size ``config.batch_size``) or any iterable of what ``load_training_batch`` takes;
+        ``RecordDataset``s of image records (batch size ``config.batch_size``) or any iterable of what ``load_training_batch`` takes: the
+        reference's image records, whose ``image/encoded`` and ``image/seg_gt`` are JPEG or PNG streams (lsp_train / lsp_val masks and
+        mpii frames are PNG, lsp_ext and mpii masks JPEG; one batch may mix them);
         mocap_dataset: a ``RecordDataset(..., parse=parse_mocap_example)`` of ``batch_size * num_stage`` rows or any iterable of lists
         of (pose [72], shape [10]).  ``config.num_images`` (default: counted once from the dataset) sets the epoch length.  generator:
         the torch.Generator (CUDA) of the dropout and interpolation draws; the augmentation draws come from ``config.augment_seed``.

@@ -619,6 +619,39 @@ int hpe_jpeg_backend(const HpeJpegImage* table_host, const HpeJpegImage* table_d
                      unsigned char* workspace_dev, long long workspace_bytes, unsigned char* frames_dev, long long frames_bytes,
                      void* stream);
 
+/* -- PNG decode: the PNG streams tf.image.decode_jpeg also takes (LSP masks, MPII frames) -------------------------------------
+ * The chunk walk, the CRCs and inflate are host code (hpe_amd/png.py: zlib); what reaches this library is, per image, the inflated
+ * scanlines -- H rows of one filter byte and rowbytes filtered bytes -- and a table entry.  Two launches (hpe_png_backend): the PNG
+ * unfilter (None, Sub, Up, Average, Paeth), then unpack / palette / channel conversion and the store.  Lossless, so bit for bit:
+ * DESIGN.md "PNG streams in the records". */
+#define HPE_PNG_MAX_SIDE 16384 /* larger frames are refused */
+#define HPE_PNG_STORE_BYTES_PER_GROUP 1024 /* launch two: 4 output bytes per thread, 256 threads */
+typedef struct HpePngImage {
+    long long raw_offset;  /* byte offset in the raw buffer of the H * (1 + rowbytes) inflated bytes, a multiple of 16 */
+    long long pal_offset;  /* colour type 3: byte offset in the raw buffer of 256 entries of 4 bytes (R, G, B, 0), entries beyond PLTE
+                            * zero, a multiple of 16; every other colour type: -1 */
+    long long work_offset; /* byte offset in the workspace of the H * rowbytes unfiltered bytes, a multiple of 16; -1 for a direct image:
+                            * 8-bit grey asked for 1 channel or 8-bit RGB asked for 3, whose unfiltered rows ARE the frame */
+    long long out_offset;  /* byte offset of the uint8 [H,W,channels] frame in the frame buffer, a multiple of 16 */
+    int H, W;
+    int color_type;        /* 0 grey, 2 RGB, 3 palette, 4 grey + alpha, 6 RGBA */
+    int depth;             /* 8; also 1, 2, 4 for colour types 0 and 3 */
+    int channels;          /* 1 or 3 */
+    int rowbytes;          /* ceil(W * samples * depth / 8) */
+    int bpp;               /* max(1, samples * depth / 8): the filters' distance to the byte on the left */
+    int store_group0;      /* first workgroup of this image in launch two (a direct image has none) */
+} HpePngImage;
+
+/* Two launches on `stream`: raw_dev -> unfiltered rows (one workgroup per image; into workspace_dev, or into frames_dev for a direct
+ * image), rows -> packed frames in frames_dev.  The kernels read table_dev, the caller's device copy of table_host (in flight on
+ * `stream` is enough); table_host is what this call checks, entry by entry, against raw_bytes, workspace_bytes and frames_bytes and
+ * against what H, W, colour type and depth imply, before anything else: with a sound table a NULL device pointer is refused next, so
+ * the check runs without a device.  Bytes of frames_dev outside the frames are not written.  No allocation, no synchronisation, no
+ * atomics, capturable: the same inputs give the same bits. */
+int hpe_png_backend(const HpePngImage* table_host, const HpePngImage* table_dev, int B, const unsigned char* raw_dev, long long raw_bytes,
+                    unsigned char* workspace_dev, long long workspace_bytes, unsigned char* frames_dev, long long frames_bytes,
+                    void* stream);
+
 /* -- mesh renderer: the reference's SMPLRenderer (src/util/renderer.py:23-112) without OpenDR ---------------------------------
  * A renderer is its own handle (the reference builds SMPLRenderer without a predictor, preview.py:50).  What it computes is
  * defined in DESIGN.md "Renderer": pinhole projection snapped to 1/256 px, rasterisation with int64 edge functions and a
