@@ -22,11 +22,13 @@ from . import critic_spec, regressor_spec, resnet_spec, synthetic  # noqa: F401,
 from ._lib import HpeError  # noqa: F401
 from .augment import augment_batch, draw_augmentation, mocap_real, plan_augmentation  # noqa: F401
 from .critic_train import CriticTrainer  # noqa: F401
+from .draw import draw_panels, draw_results, draw_skeleton  # noqa: F401
 from .engine import HpeEngine  # noqa: F401
 from .generator_train import GeneratorTrainer  # noqa: F401
 from .fit import fit_keypoints, fit_reprojection  # noqa: F401
 from .jpeg import DecodedBatch, decode_jpeg_batch, jpeg_info  # noqa: F401
 from .png import decode_image_batch, decode_png_batch, png_info  # noqa: F401
+from .png_encode import encode_png_batch  # noqa: F401
 from .records import RecordDataset, RecordError, load_training_batch, parse_example, parse_image_example, parse_mocap_example, read_tfrecords  # noqa: F401
 from .image import get_original, preprocess_batch, preprocess_image  # noqa: F401
 from .ops import critic_gradient_penalty, critic_scores, critic_wgan_loss, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas, encoder_features  # noqa: F401
@@ -35,4 +37,5 @@ from .predictor import Predictor  # noqa: F401
 from .projection import batch_orth_proj_idrot, reproject_vertices  # noqa: F401
 from .render import SMPLRenderer  # noqa: F401
 from .smpl import SMPL  # noqa: F401
+from .summary import SummaryWriter, read_events  # noqa: F401
 from .trainer import Trainer  # noqa: F401

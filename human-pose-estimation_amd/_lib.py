@@ -110,6 +110,11 @@ class HpePngImage(C.Structure):
                 ("bpp", C.c_int), ("store_group0", C.c_int)]
 
 
+class HpePngFilterImage(C.Structure):
+    """one table entry of hpe_png_filter (include/hpe.h), 32 bytes"""
+    _fields_ = [("frame_offset", C.c_longlong), ("scan_offset", C.c_longlong), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("row0", C.c_int)]
+
+
 GEMM_DENSE, GEMM_STRIDED, GEMM_CONV3, GEMM_DUAL = 0, 1, 2, 4  # HpeDebugGemm.mode
 GEMM_TILES = ((128, 128), (128, 64), (64, 64), (64, 128), (128, 128), (128, 64), (256, 128))  # (BM, BN) of tile 0..6; 4..6 run 8 waves
 
@@ -192,6 +197,9 @@ _PROTOS = {
                                    C.c_void_p]),
     "hpe_png_backend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
                                   C.c_void_p]),
+    "hpe_png_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "hpe_draw_panels": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_draw_skeleton": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hpe_get_original": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_kp_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_kp_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,13 +1,21 @@
-"""Trainer -- the reference's training driver (src/trainer.py:40-870) without TensorBoard and without drawing: ``train_step`` is
+"""Trainer -- the reference's training driver (src/trainer.py:40-870): ``train_step`` is
 ``GeneratorTrainer.step`` (encoder with batch statistics, IEF loop, losses, gradient, update) followed by
 ``CriticTrainer.step_from_thetas``, both with the reference's optimiser (``KerasAdam``: one for the encoder, the regressor and mean theta,
 one for the critic); ``train`` is the reference's loop; ``save`` / ``restore`` write and read the reference's ``tf.train.Checkpoint``
 layout (tf_checkpoint.save_checkpoint / load_training_state), optimiser moments and step counts included, so a run resumes with the bits
 of one that was never interrupted.
 
-Not here: TensorBoard event files, ``draw_results``, the bone-length evaluation, multi-GPU training.  ``generated_verts``
-is not among ``train_step``'s result keys (only drawing read it).  ``use_kpr_loss`` decides, as in the reference, only whether the
-keypoint loss is logged: it is always minimised."""
+Summaries (DESIGN.md "Training summaries"): with ``config.model_dir`` set and ``config.write_summaries`` (default True), ``train`` writes
+the reference's TensorBoard scalars at every step -- a training writer under ``<model_dir>/training``, a validation writer under
+``<model_dir>/validation`` (the reference concatenates ``model_dir + 'training'`` without a separator) -- and, every
+``config.log_img_step`` steps, the ``draw_results`` panels of the rows ``show_these`` as ``vis_images/<i>`` (summary.py, draw.py,
+png_encode.py).  Scalars stay on the device between flushes; a writer is flushed at image steps and when the epoch rolls.  The
+bone-length evaluation runs with ``config.do_bone_evaluation`` (default False here so that the result keys stay as they were; the
+reference's default is True).
+
+Not here: ``draw_text`` on the panels, the best / worst drawings of ``validate_checkpoint``, multi-GPU training.
+``generated_verts`` is not among ``train_step``'s result keys: drawing recomputes the vertices of the rows it shows from ``thetas``.
+``use_kpr_loss`` decides, as in the reference, only whether the keypoint loss is logged: it is always minimised."""
 from __future__ import annotations
 
 import os
@@ -20,15 +28,37 @@ from .critic_train import CRITIC_LR, CriticTrainer
 from .generator_train import GENERATOR_LR, GeneratorTrainer
 
 SAVE_EVERY = 5  # epochs (src/trainer.py:835)
+BONE_ENDS = (1, 2, 8, 9, 3, 4, 7, 8, 12, 12, 9, 10, 13)  # precompute_C_matrix (src/models.py:97-112): bone k = joint k - joint BONE_ENDS[k]
+
+
+def total_bone_length(joints):
+    """``reduce_mean(reduce_sum(diag_part(get_kcs(joints, C)), axis=1))`` (src/trainer.py:610-617): the KCS diagonal is the squared
+    length of each of the 13 bones B = X C of the first 14 joints; summed over the bones, averaged over the rows.  joints [N, >=14, 3]
+    -> a 0-dim float32 tensor.  Plain torch: C has one +1 and one -1 per column, so X C is a difference of two joints; squares and sums
+    run in float64 (a few hundred terms, not a hot path) and the result is rounded to float32 once."""
+    j = joints[:, :14].double()
+    b = j[:, :13] - j[:, list(BONE_ENDS)]
+    return (b * b).sum(dim=2).sum(dim=1).mean().float()
+
+
+def show_rows(batch_size):
+    """``show_these`` (src/trainer.py:116-121): half of min(6, batch) rows from the front and three from the back.  Below a batch of
+    three the reference's list leaves the batch (tf.gather fails there); such rows are dropped here."""
+    num2show = min(6, batch_size)
+    rows = np.hstack([np.arange(num2show / 2), batch_size - np.arange(3) - 1]).astype(np.int64)
+    return [int(r) for r in rows if 0 <= r < batch_size]
 
 
 def run_training_loop(batches, train_step, num_images, batch_size, max_epoch, val_step=None, validation_step_size=0, save=None,
-                      save_every=SAVE_EVERY, summarize=None, log=print):
+                      save_every=SAVE_EVERY, summarize=None, log=print, after_train_step=None, after_val_step=None, after_epoch=None):
     """The bookkeeping of the reference's loop (src/trainer.py:715-868), free of any engine.  batches: an iterable of
     (generator batch, critic batch, validation batch) that normally never ends; train_step(generator batch, critic batch) -> result;
     val_step(validation batch) -> result, called after every ``validation_step_size``-th step when given; save(epoch) when the finished
     epoch count is a multiple of ``save_every``; summarize(epoch, train results, validation results) -> the text of the epoch's line.
     ``num_itr_per_epoch = max(num_images / batch_size, 1)`` is NOT rounded: the epoch rolls at the first step count that reaches it.
+    after_train_step(step, result) is called after every train step with the 1-based step count, after_val_step(step, result) after
+    every validation step (the places the reference writes its summaries, src/trainer.py:745-809), after_epoch(epoch) when an epoch
+    rolls, before its line is logged; all default to None.
     Stops after ``max_epoch`` epochs (or when ``batches`` ends).  -> {"steps", "epochs", "saved": [epochs], "validations"}"""
     num_itr_per_epoch = max(float(num_images) / float(batch_size), 1.0)
     step = itr = epoch = validations = 0
@@ -42,9 +72,13 @@ def run_training_loop(batches, train_step, num_images, batch_size, max_epoch, va
             start_time = time.time()
         train_results.append(train_step(gen_batch, critic_batch))
         step += 1
+        if after_train_step is not None:
+            after_train_step(step, train_results[-1])
         if val_step is not None and validation_step_size > 0 and step % validation_step_size == 0:
             val_results.append(val_step(val_batch))
             validations += 1
+            if after_val_step is not None:
+                after_val_step(step, val_results[-1])
         itr += 1
         if itr >= num_itr_per_epoch:
             end_time = time.time()
@@ -53,6 +87,8 @@ def run_training_loop(batches, train_step, num_images, batch_size, max_epoch, va
             if save is not None and epoch % save_every == 0:
                 save(epoch)
                 saved.append(epoch)
+            if after_epoch is not None:
+                after_epoch(epoch - 1)
             log(summarize(epoch - 1, train_results, val_results) if summarize is not None else "Finished epoch %d" % (epoch - 1))
             train_results, val_results = [], []
             if epoch >= max_epoch:
@@ -101,6 +137,10 @@ class Trainer(object):
         self.val_step_size = int(g("validation_step_size", 50))
         self.train_from_checkpoint, self.checkpoint_dir = bool(g("train_from_checkpoint", False)), g("checkpoint_dir", None)
         self.model_dir = g("model_dir", None)
+        self.write_summaries = self.model_dir is not None and bool(g("write_summaries", True))
+        self.log_img_step, self.do_bone_evaluation = int(g("log_img_step", 1000)), bool(g("do_bone_evaluation", False))
+        self.show_these = show_rows(self.batch_size)
+        self.training_writer = self.val_writer = None
         self.dataset, self.mocap_dataset, self.val_dataset = dataset, mocap_dataset, val_dataset
         self.use_validation = self.use_validation and val_dataset is not None
         self.predictor = Predictor(config, **predictor_args)
@@ -128,7 +168,8 @@ class Trainer(object):
         [B,224,224,3], seg_gts [B,224,224(,1)], kp_gt [B,19,3]; joints / shapes / Rs: the real triple of ``mocap_real`` (B * num_stage
         or B rows), unused with ``encoder_only``.  drop / interp: fixed dropout multipliers and interpolation draws (tests).
         -> the reference's result keys: kpr_losses, mr_losses (with ``use_mesh_repro_loss``), pred_keypoints, generated_cams and, unless
-        ``encoder_only``, generator_critic_losses, critic_penalty, critic_network_loss; plus ``thetas``.  Nothing reads the device."""
+        ``encoder_only``, generator_critic_losses, critic_penalty, critic_network_loss; plus ``thetas``; with ``do_bone_evaluation``
+        also avg_total_bone_length_pred (all stages' joints) and avg_total_bone_length_gt (``joints``).  Nothing reads the device."""
         if self.generator is None:
             raise RuntimeError("this Trainer was built with validation_only")
         r = self.generator.step(images, kp_gt, seg_gts if self.use_mesh_repro_loss else None, use_critic=not self.encoder_only, drop=drop)
@@ -140,6 +181,14 @@ class Trainer(object):
             c = self.critic.step_from_thetas((joints, shapes, Rs), r["thetas"], interp=interp)
             result["generator_critic_losses"] = r["generator_critic_losses"]
             result["critic_penalty"], result["critic_network_loss"] = c["critic_penalty"], c["critic_network_loss"]
+        if self.do_bone_evaluation:
+            import torch
+
+            if joints is None:
+                raise ValueError("do_bone_evaluation needs the mocap joints")
+            fake = torch.cat([self.engine.smpl(t, want=("joints",))["joints"] for t in r["thetas"]])
+            result["avg_total_bone_length_pred"] = total_bone_length(fake)
+            result["avg_total_bone_length_gt"] = total_bone_length(joints)
         return result
 
     def val_step(self, images, seg_gts, kp2d_gts):
@@ -182,7 +231,7 @@ class Trainer(object):
 
     def _batches(self):
         gen = _repeat(self.dataset)
-        moc = _repeat(self.mocap_dataset) if not self.encoder_only else None
+        moc = _repeat(self.mocap_dataset) if not self.encoder_only or self.do_bone_evaluation else None
         val = _repeat(self.val_dataset) if self.use_validation else None
         while True:
             yield next(gen), (next(moc) if moc is not None else None), (next(val) if val is not None else None)
@@ -219,6 +268,78 @@ class Trainer(object):
             text += " Validation:"
         return text
 
+    # ------------------------------------------------------------------ summaries
+    def draw_rows(self, images, segs, kp_gt, rows, thetas=None, val_result=None):
+        """``draw_results`` (src/trainer.py:656-695) for the given rows of a batch -> list of PNG streams, one panel [T*S, 3*S, 3] per
+        row.  thetas: the stages' theta [B,85] of a train step -- vertices and keypoints of the rows come from ``engine.smpl`` --, or
+        val_result: a ``val_step`` result, which carries them.  Waits for the device (the PNG streams are host bytes)."""
+        import torch
+
+        from .draw import draw_results
+        from .png_encode import encode_png_batch
+
+        idx = torch.as_tensor(list(rows), dtype=torch.long, device=images.device)
+        n = int(idx.numel())
+        if thetas is not None:
+            th = torch.stack([t.detach()[idx] for t in thetas], 1)  # [n,T,85]
+            T, flat, mb = int(th.shape[1]), th.reshape(-1, 85).contiguous(), self.engine.max_batch
+            outs = [self.engine.smpl(flat[lo:lo + mb].contiguous(), want=("verts", "kp2d")) for lo in range(0, flat.shape[0], mb)]
+            verts = torch.cat([o["verts"] for o in outs]).reshape(n, T, -1, 3)
+            kps = torch.cat([o["kp2d"] for o in outs]).reshape(n, T, 19, 2)
+            cams = th[:, :, :3]
+        else:
+            verts, kps, cams = val_result["generated_verts"][idx], val_result["pred_keypoints"][idx], val_result["generated_cams"][idx]
+        panels = draw_results(self.predictor.renderer, images[idx], segs[idx], kp_gt[idx], verts, kps, cams)
+        return encode_png_batch(panels)
+
+    def _open_writers(self):
+        from .summary import SummaryWriter
+
+        if self.log_img_step > 0:
+            self.predictor.renderer  # noqa: B018  the panels need the SMPL faces: fail before the first step, not at step log_img_step
+        self.training_writer = SummaryWriter(os.path.join(self.model_dir, "training"))
+        self.val_writer = SummaryWriter(os.path.join(self.model_dir, "validation")) if self.use_validation else None
+
+    def _write_images(self, writer, step, batch, **source):
+        for i, png in enumerate(self.draw_rows(*batch, self.show_these, **source)):
+            writer.image("vis_images/%d" % i, png, step)
+
+    def _summarize_train_step(self, step, result, batch):
+        """the training writer's block of the reference's loop (src/trainer.py:747-783), same tags, same conditions, same order"""
+        w = self.training_writer
+        if self.use_kpr_loss:
+            w.scalar("generator/kpr_loss", result["kpr_losses"][-1], step)
+        if self.use_mesh_repro_loss:
+            w.scalar("generator/mr_loss", result["mr_losses"][-1], step)
+        if self.do_bone_evaluation:
+            w.scalar("bones/avg_total_bone_lenth_pred", result["avg_total_bone_length_pred"], step)  # the reference's spelling
+            w.scalar("bones/avg_total_bone_lenth_gt", result["avg_total_bone_length_gt"], step)
+        image_step = self.log_img_step > 0 and step % self.log_img_step == 0
+        if image_step:
+            self._write_images(w, step, batch, thetas=result["thetas"])
+        if not self.encoder_only:
+            w.scalar("critic/critic_network_loss", result["critic_network_loss"], step)
+            w.scalar("critic/generator_critic_loss", result["generator_critic_losses"][-1], step)
+            w.scalar("critic/penalty", result["critic_penalty"], step)
+        if image_step:
+            w.flush()
+
+    def _summarize_val_step(self, step, result, batch):
+        """the validation writer's block (src/trainer.py:798-812)"""
+        w = self.val_writer
+        if self.use_kpr_loss:
+            w.scalar("generator/kpr_loss", result["kpr_losses"][-1], step)
+        if self.use_mesh_repro_loss:
+            w.scalar("generator/mr_loss", result["mr_losses"][-1], step)
+        if self.log_img_step > 0 and step % self.log_img_step == 0:
+            self._write_images(w, step, batch, val_result=result)
+            w.flush()
+
+    def _flush_writers(self):
+        for w in (self.training_writer, self.val_writer):
+            if w is not None:
+                w.flush()
+
     def train(self, save_every=SAVE_EVERY):
         """the reference's ``train()``: restore when ``train_from_checkpoint``, then epochs of ``num_images / batch_size`` steps with a
         validation step every ``validation_step_size``, a checkpoint every ``save_every`` epochs and one line per epoch -> the loop's
@@ -232,23 +353,40 @@ class Trainer(object):
             self.log("checkpoint restored")
         self.log("Loading Data")
 
+        last = {}  # the loaded batches of the step in flight: what an image step draws over
+
         def step(gen_batch, critic_batch):
-            images, segs, kp = self._load_images(gen_batch)
-            real = self._load_mocap(critic_batch) if not self.encoder_only else (None, None, None)
+            last["train"] = images, segs, kp = self._load_images(gen_batch)
+            real = self._load_mocap(critic_batch) if not self.encoder_only or self.do_bone_evaluation else (None, None, None)
             return self.train_step(images, segs, kp, *real)
 
         def val(val_batch):
-            return self.val_step(*self._load_images(val_batch, augment=False))
+            last["val"] = self._load_images(val_batch, augment=False)
+            return self.val_step(*last["val"])
 
-        out = run_training_loop(self._batches(), step, self._num_images(), self.batch_size, self.max_epoch,
-                                val_step=val if self.use_validation else None, validation_step_size=self.val_step_size,
-                                save=lambda epoch: self.save(), save_every=save_every, summarize=self._summarize, log=self.log)
+        hooks = {}
+        if self.write_summaries:
+            self._open_writers()
+            hooks = {"after_train_step": lambda s, r: self._summarize_train_step(s, r, last["train"]),
+                     "after_val_step": lambda s, r: self._summarize_val_step(s, r, last["val"]),
+                     "after_epoch": lambda epoch: self._flush_writers()}
+        try:
+            out = run_training_loop(self._batches(), step, self._num_images(), self.batch_size, self.max_epoch,
+                                    val_step=val if self.use_validation else None, validation_step_size=self.val_step_size,
+                                    save=lambda epoch: self.save(), save_every=save_every, summarize=self._summarize, log=self.log, **hooks)
+        finally:
+            for w in (self.training_writer, self.val_writer):
+                if w is not None:
+                    w.close()
+            self.training_writer = self.val_writer = None
         self.log("Finish training on %s" % self.model_dir)
         return out
 
-    def validate_checkpoint(self, restore=True):
+    def validate_checkpoint(self, restore=True, draw_every_image=False):
         """the mean keypoint and mesh reprojection losses (last stage, weighted) of the newest checkpoint over ONE pass of the
-        validation set (src/trainer.py:882-960 without the drawing) -> {"kpr_loss", "mr_loss" (None without the mesh loss), "batches"}"""
+        validation set (src/trainer.py:882-960 without the best / worst drawings) -> {"kpr_loss", "mr_loss" (None without the mesh
+        loss), "batches"}.  draw_every_image: every image of every batch is drawn (``draw_results``) into an event file under
+        ``<model_dir or checkpoint_dir>/checkpoint_validation`` as ``vis_images/<i>`` at step = the batch's 1-based number."""
         import torch
 
         if self.val_dataset is None:
@@ -256,11 +394,27 @@ class Trainer(object):
         if restore:
             self.restore()
         kpr, mr = [], []
-        for batch in self.val_dataset:
-            r = self.val_step(*self._load_images(batch, augment=False))
-            kpr.append(r["kpr_losses"][-1])
-            if self.use_mesh_repro_loss:
-                mr.append(r["mr_losses"][-1])
+        writer = None
+        if draw_every_image:
+            from .summary import SummaryWriter
+
+            if not (self.model_dir or self.checkpoint_dir):
+                raise RuntimeError("draw_every_image needs config.model_dir or config.checkpoint_dir for its event file")
+            writer = SummaryWriter(os.path.join(self.model_dir or self.checkpoint_dir, "checkpoint_validation"))
+        try:
+            for batch in self.val_dataset:
+                loaded = self._load_images(batch, augment=False)
+                r = self.val_step(*loaded)
+                kpr.append(r["kpr_losses"][-1])
+                if self.use_mesh_repro_loss:
+                    mr.append(r["mr_losses"][-1])
+                if writer is not None:
+                    for i, png in enumerate(self.draw_rows(*loaded, range(int(loaded[0].shape[0])), val_result=r)):
+                        writer.image("vis_images/%d" % i, png, len(kpr))
+                    writer.flush()
+        finally:
+            if writer is not None:
+                writer.close()
         if not kpr:
             raise ValueError("the validation dataset yields no batch")
         host = torch.stack([t.reshape(()).float() for t in kpr + mr]).cpu().numpy()

@@ -652,6 +652,46 @@ int hpe_png_backend(const HpePngImage* table_host, const HpePngImage* table_dev,
                     unsigned char* workspace_dev, long long workspace_bytes, unsigned char* frames_dev, long long frames_bytes,
                     void* stream);
 
+/* -- PNG encode: the mirror, for the panels of the training summaries -----------------------------------------------------------
+ * Packed uint8 frames [H,W,C] with C in {1, 3, 4} -> PNG scanlines: per row one filter byte and W * C filtered bytes, the filter
+ * chosen per row by libpng's minimum-sum rule (all five candidates from the raw neighbours, scored by the sum of v < 128 ? v :
+ * 256 - v, lowest score, then lowest filter number).  Deflate and the chunks are host code (hpe_amd/png_encode.py).  DESIGN.md
+ * "Training summaries". */
+typedef struct HpePngFilterImage {
+    long long frame_offset; /* byte offset of the uint8 [H,W,C] frame in the frame buffer */
+    long long scan_offset;  /* byte offset in the scanline buffer of the H * (1 + W * C) bytes written */
+    int H, W;               /* 1 .. HPE_PNG_MAX_SIDE */
+    int C;                  /* 1 grey, 3 RGB, 4 RGBA: the filters' bpp */
+    int row0;               /* first row of this image in the launch's grid over all rows: the sum of H of the images before */
+} HpePngFilterImage;
+
+/* One launch on `stream`, one wave per row.  The kernel reads table_dev, the caller's device copy of table_host (in flight on
+ * `stream` is enough); table_host is what this call checks, entry by entry, against frames_bytes and scan_bytes before anything
+ * else: with a sound table a NULL device pointer is refused next, so the check runs without a device.  Bytes of scan_dev outside
+ * the scanlines are not written.  No allocation, no synchronisation, no atomics, capturable: the same inputs give the same bits. */
+int hpe_png_filter(const HpePngFilterImage* table_host, const HpePngFilterImage* table_dev, int B, const unsigned char* frames_dev,
+                   long long frames_bytes, unsigned char* scan_dev, long long scan_bytes, void* stream);
+
+/* -- draw_results panels: the skeleton drawing of the reference's draw_skeleton (src/util/renderer.py:286-447) and the panel of
+ * visualize_img / draw_results (src/trainer.py:622-679) composed on the device.  The raster rules are this project's own, in exact
+ * integer arithmetic (DESIGN.md "Training summaries": PARITY UNPINNED against cv2):  disc d2 <= r*r;  ring of thickness 1
+ * (2r-1)^2 <= 4*d2 < (2r+1)^2;  edge of thickness th: 4 * dist2 <= th*th with dist2 the squared distance to the segment, evaluated
+ * without a division in 64-bit integers.  Joint pixels are rint of the float coordinate (half to even), clamped to +-32768 (a NaN
+ * goes to -32768).  `skeleton` is the device copy of the drawing's tables (hpe_amd/draw.py holds them as data): int32 [19][8], per
+ * joint its parent (-1: none), the joint's R, G, B, its edge's R, G, B, and 0. */
+#define HPE_DRAW_JOINTS 19
+#define HPE_DRAW_MAX_RADIUS 256
+/* out uint8 [n, T*S, 3*S, 3]: row block t of image i is hstack[skeleton over the crop, rend_img[i*T+t], rend_seg[i*T+t]].
+ * images fp32 [n,S,S,3] in [-1,1]; kp_gt fp32 [n,19,3] (x, y in [-1,1], visibility); kp_pred fp32 [n,T,19,2]; rend_img / rend_seg
+ * uint8 [n*T,S,S,3].  The radius is max(4, int(0.01 * S)).  One launch on `stream`, no atomics. */
+int hpe_draw_panels(const float* images, const float* kp_gt, const float* kp_pred, const unsigned char* rend_img,
+                    const unsigned char* rend_seg, const int* skeleton, int n, int T, int S, unsigned char* out, void* stream);
+/* draw_skeleton on n uint8 [H,W,3] images in place: joints fp32 [n,19,2] in PIXELS, vis uint8 [n,19] or NULL (all visible),
+ * draw_edges 1: discs and edges of thickness max(1, radius - 2), 0: rings of radius - 1.  radius in [1, HPE_DRAW_MAX_RADIUS].  One
+ * launch on `stream`. */
+int hpe_draw_skeleton(unsigned char* images, const float* joints, const unsigned char* vis, const int* skeleton, int n, int H, int W,
+                      int draw_edges, int radius, void* stream);
+
 /* -- mesh renderer: the reference's SMPLRenderer (src/util/renderer.py:23-112) without OpenDR ---------------------------------
  * A renderer is its own handle (the reference builds SMPLRenderer without a predictor, preview.py:50).  What it computes is
  * defined in DESIGN.md "Renderer": pinhole projection snapped to 1/256 px, rasterisation with int64 edge functions and a
