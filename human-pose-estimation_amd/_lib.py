@@ -103,6 +103,13 @@ class HpeJpegImage(C.Structure):
                 ("blocks_h", C.c_int * 3), ("idct_group0", C.c_int), ("store_group0", C.c_int), ("quant", C.c_ubyte * 192)]
 
 
+class HpeJpegEncImage(C.Structure):
+    """one table entry of hpe_jpeg_encode_layout / hpe_jpeg_forward / hpe_jpeg_entropy_encode (include/hpe.h), 232 bytes"""
+    _fields_ = [("frame_offset", C.c_longlong), ("coef_offset", C.c_longlong * 3), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int),
+                ("hmax", C.c_int), ("vmax", C.c_int), ("blocks_w", C.c_int * 3), ("blocks_h", C.c_int * 3), ("real_w", C.c_int * 3),
+                ("real_h", C.c_int * 3), ("group0", C.c_int), ("quant", C.c_ubyte * 128)]
+
+
 class HpePngImage(C.Structure):
     """one table entry of hpe_png_backend (include/hpe.h), 64 bytes"""
     _fields_ = [("raw_offset", C.c_longlong), ("pal_offset", C.c_longlong), ("work_offset", C.c_longlong), ("out_offset", C.c_longlong),
@@ -195,6 +202,10 @@ _PROTOS = {
     "hpe_jpeg_decode": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_jpeg_backend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
                                    C.c_void_p]),
+    "hpe_jpeg_encode_layout": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_jpeg_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "hpe_jpeg_entropy_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong,
+                                          C.c_void_p, C.c_void_p]),
     "hpe_png_backend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
                                   C.c_void_p]),
     "hpe_png_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]),

@@ -21,6 +21,21 @@ int info_batch(int B, const unsigned char* const* streams, const long long* leng
 int decode_batch(int B, const unsigned char* const* streams, const long long* lengths, const int* channels, int threads, short* coef_out,
                  long long coef_capacity, HpeJpegImage* table_out, int* status_out, long long* totals_out, std::string* why);
 
+// The host half of the encoder (jpeg_huffman_enc.hip), also plain C++17 (tools/jpeg_enc_host_check.cpp is its sanitizer build): the
+// arguments are those of hpe_jpeg_encode_layout / hpe_jpeg_entropy_encode; HPE_OK, or HPE_ERR_INVALID with the message in *why.
+int encode_layout(int B, const int* shapes, const long long* frame_offsets, int hmax, int vmax, int quality, HpeJpegEncImage* table_out,
+                  long long* totals_out, std::string* why);
+int entropy_encode(const HpeJpegEncImage* table, int B, const short* coef, long long coef_count, int units, int xdensity, int ydensity,
+                   int threads, unsigned char* out, long long out_capacity, long long* offsets_out, long long* lengths_out, std::string* why);
+// What hpe_jpeg_forward and entropy_encode hold a table entry against ("" = fine), but for the buffer sizes and the workgroup base.
+const char* enc_entry_fault(const HpeJpegEncImage& e);
+inline long long enc_blocks(const HpeJpegEncImage& e) {
+    long long n = 0;
+    for (int c = 0; c < e.C; ++c) n += (long long)e.blocks_w[c] * e.blocks_h[c];
+    return n;
+}
+inline long long enc_stream_bound(const HpeJpegEncImage& e) { return HPE_JPEG_ENC_HEADER_BYTES + HPE_JPEG_ENC_BLOCK_BYTES * enc_blocks(e); }
+
 // The block grid the layout gives a frame: what hpe_jpeg_backend holds every table entry against.
 inline int blocks_for(int side, int smax, int s) { return (side + 8 * smax - 1) / (8 * smax) * s; }
 

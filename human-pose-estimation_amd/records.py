@@ -1,7 +1,9 @@
 """The reference's training files without TensorFlow: ``*.tfrecords`` framing, ``tf.train.Example`` protos and the two parsers of
 src/util/data_utils.py (``parse_example_proto`` :11-69, ``parse_mocap_example`` :109-127), plus ``load_training_batch``, the path from
 parsed records to what ``GeneratorTrainer.step`` takes (src/data_loader.py:87-93, 160-213).  Everything but ``load_training_batch`` is
-host code.  CRC-32C, varints and the protobuf wire format are those of tf_checkpoint.py."""
+host code.  CRC-32C, varints and the protobuf wire format are those of tf_checkpoint.py.  The writers (``serialize_example``,
+``image_example``, ``mocap_example``, ``write_tfrecords``, ``TFRecordWriter``) are the inverse: what ``tf.io.TFRecordWriter`` and
+``tf.train.Example.SerializeToString`` produce, with packed lists and the features in the order given."""
 from __future__ import annotations
 
 import os
@@ -9,7 +11,7 @@ import struct
 
 import numpy as np
 
-from .tf_checkpoint import CheckpointError, _proto_fields, _signed64, _varint, crc32c, mask_crc
+from .tf_checkpoint import CheckpointError, _enc_varint, _pb_bytes, _proto_fields, _signed64, _varint, crc32c, mask_crc
 
 NUM_KP = 19
 
@@ -173,6 +175,82 @@ class RecordDataset:
                 batch = []
         if batch and not self.drop_last:
             yield batch
+
+
+def _feature_bytes(value):
+    """one value -> a serialized tf.train.Feature: bytes or a list of bytes -> bytes_list; a float array, a float or a list holding a
+    float -> float_list (float32, packed); integers and bools -> int64_list (packed varints, a negative value as 10 bytes)"""
+    if isinstance(value, (bytes, bytearray, memoryview)):
+        value = [bytes(value)]
+    if isinstance(value, (list, tuple)) and value and all(isinstance(v, (bytes, bytearray, memoryview)) for v in value):
+        return _pb_bytes(1, b"".join(_pb_bytes(1, bytes(v)) for v in value))
+    arr = np.asarray(value)
+    if arr.dtype.kind == "f":
+        return _pb_bytes(2, _pb_bytes(1, arr.astype("<f4").reshape(-1).tobytes()))
+    if arr.dtype.kind in "iub":
+        return _pb_bytes(3, _pb_bytes(1, b"".join(_enc_varint(int(v) & 0xFFFFFFFFFFFFFFFF) for v in arr.reshape(-1).tolist())))
+    raise RecordError("a feature must be bytes, a list of bytes, floats or integers, not %s" % (arr.dtype if arr.dtype != object else type(value).__name__))
+
+
+def serialize_example(features):
+    """A tf.train.Example of ``features`` -- a dict, or a list of (name, value) pairs, kept in order -> bytes.  The value decides the
+    list type (``_feature_bytes``).  ``parse_example`` is the inverse."""
+    items = features.items() if isinstance(features, dict) else features
+    entries = b"".join(_pb_bytes(1, _pb_bytes(1, str(k).encode("utf-8")) + _pb_bytes(2, _feature_bytes(v))) for k, v in items)
+    return _pb_bytes(1, entries)
+
+
+def image_example(image, seg, height, width, center, filename, x, y, vis, face_pts=None):
+    """The record of src/util/create_dataset.py:52-70: image and mask bytes as they are, height, width, the file's base name, format
+    b"JPEG", center int64 [2] (x, y), the 14 visibilities (int64) and coordinates (float), and the 15 face floats if there are any."""
+    name = filename if isinstance(filename, (bytes, bytearray)) else str(filename).encode("utf-8")
+    feats = [("image/encoded", bytes(image)), ("image/seg_gt", bytes(seg)), ("image/height", [int(height)]), ("image/width", [int(width)]),
+             ("image/filename", bytes(name)), ("image/format", b"JPEG"), ("image/center", np.asarray(center, np.int64)),
+             ("image/visibility", np.asarray(vis, np.int64)), ("image/x", np.asarray(x, np.float32)), ("image/y", np.asarray(y, np.float32))]
+    if face_pts is not None:
+        feats.append(("image/face_pts", np.asarray(face_pts, np.float32)))
+    return serialize_example(feats)
+
+
+def mocap_example(pose, shape):
+    return serialize_example([("pose", np.asarray(pose, np.float32)), ("shape", np.asarray(shape, np.float32))])
+
+
+def frame_record(payload):
+    """one record's bytes: uint64 length, its masked CRC-32C, the payload, its masked CRC-32C"""
+    head = struct.pack("<Q", len(payload))
+    return head + struct.pack("<I", mask_crc(crc32c(head))) + bytes(payload) + struct.pack("<I", mask_crc(crc32c(payload)))
+
+
+class TFRecordWriter:
+    """``with TFRecordWriter(path) as w: w.write(payload)`` -- a ``*.tfrecords`` file ``read_tfrecords`` and TensorFlow read"""
+
+    def __init__(self, path):
+        self._f = open(path, "wb")
+        self.count = 0
+
+    def write(self, payload):
+        self._f.write(frame_record(payload))
+        self.count += 1
+
+    def close(self):
+        if not self._f.closed:
+            self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def write_tfrecords(path, payloads):
+    """every payload as one record of ``path`` -> the number written"""
+    with TFRecordWriter(path) as w:
+        for p in payloads:
+            w.write(p)
+        return w.count
 
 
 def load_training_batch(records, draws=None, generator=None, threads=None, **augment_args):

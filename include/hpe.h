@@ -619,6 +619,48 @@ int hpe_jpeg_backend(const HpeJpegImage* table_host, const HpeJpegImage* table_d
                      unsigned char* workspace_dev, long long workspace_bytes, unsigned char* frames_dev, long long frames_bytes,
                      void* stream);
 
+/* -- JPEG encode: tf.image.encode_jpeg of the dataset writers (src/util/create_dataset.py:36-40), the mirror of the decoder --------
+ * libjpeg's default baseline compressor bit for bit (jccolor.c, jcsample.c without smoothing, the edge rules of jcprepct.c and
+ * jccoefct.c, jfdctint.c, the Annex K Huffman tables, no optimisation, no restart markers): DESIGN.md "Dataset writers and JPEG
+ * encode".  Colour conversion, chroma downsampling, forward DCT and quantisation are one launch (hpe_jpeg_forward); the layout and the
+ * entropy coder are host code (hpe_jpeg_encode_layout, hpe_jpeg_entropy_encode: no device needed). */
+#define HPE_JPEG_ENC_HEADER_BYTES 640 /* covers every header and EOI (625 bytes for three components) */
+#define HPE_JPEG_ENC_BLOCK_BYTES 416  /* no block's entropy-coded bytes are more: 63 AC terms of 16 + 10 bits, a DC of 11 + 11, all stuffed */
+typedef struct HpeJpegEncImage {
+    long long frame_offset;   /* byte offset of the packed uint8 [H,W,C] frame in the frame buffer */
+    long long coef_offset[3]; /* as HpeJpegImage.coef_offset: natural order, 64 per block, blocks row-major over [blocks_h, blocks_w] */
+    int H, W;                 /* 1 .. HPE_JPEG_MAX_SIDE */
+    int C;                    /* 1 (grey: one component) or 3 (RGB: Y, Cb, Cr) */
+    int hmax, vmax;           /* luma sampling 1x1, 2x1 or 2x2; chroma is 1x1; a grey frame has 1, 1 */
+    int blocks_w[3], blocks_h[3]; /* block grid per component plane, padded to whole MCUs */
+    int real_w[3], real_h[3]; /* the blocks that hold samples: ceil(ceil(W * h / hmax) / 8) by ceil(ceil(H * v / vmax) / 8); the
+                               * others are dummy blocks (AC 0, DC of the previous block of the MCU) */
+    int group0;               /* first workgroup of this image in the launch (32 blocks per workgroup) */
+    unsigned char quant[2][64]; /* luminance and chrominance quantisation table, natural order, entries 1 .. 255 */
+} HpeJpegEncImage;
+
+/* shapes int [B][3] = H, W, C; frame_offsets [B] (bytes); hmax, vmax: the luma sampling of the colour frames (1,1 / 2,1 / 2,2; a grey
+ * frame takes 1,1); quality in [1, 100] (libjpeg's scaling of the Annex K tables).  Fills table_out[b] (coefficients packed in order,
+ * every plane on an 8-element boundary) and totals_out[3] = {int16 coefficients, workgroups, stream-buffer capacity =
+ * sum of HPE_JPEG_ENC_HEADER_BYTES + HPE_JPEG_ENC_BLOCK_BYTES * blocks}.  HPE_ERR_INVALID names the image and the clause. */
+int hpe_jpeg_encode_layout(int B, const int* shapes, const long long* frame_offsets, int hmax, int vmax, int quality,
+                           HpeJpegEncImage* table_out, long long* totals_out);
+/* One launch on `stream`: 8 threads per 8x8 block, every block of every component of every image, dummy blocks included.  The kernel
+ * reads table_dev, the caller's device copy of table_host (in flight on `stream` is enough); table_host is what this call checks,
+ * entry by entry, against frames_bytes and coef_count (int16 elements) before anything else: with a sound table a NULL device pointer
+ * is refused next, so the check runs without a device.  Elements of coef_dev outside the images' planes are not written.  No
+ * allocation, no synchronisation, no atomics, capturable: the same inputs give the same bits. */
+int hpe_jpeg_forward(const HpeJpegEncImage* table_host, const HpeJpegEncImage* table_dev, int B, const unsigned char* frames_dev,
+                     long long frames_bytes, short* coef_dev, long long coef_count, void* stream);
+/* Host: coefficient planes -> whole streams (SOI, JFIF APP0 with `units` 0 none / 1 inch / 2 cm and the densities, DQT, SOF0, DHT,
+ * SOS, data, EOI).  Image b's stream starts at offsets_out[b] = the sum of the images' bounds before it (see totals_out[2] above) and
+ * is lengths_out[b] bytes long.  out_capacity below the batch's bound is refused before anything is written; every write is checked
+ * against the image's own bound as well.  A coefficient the standard tables cannot code (|AC| > 1023, |DC difference| > 2047) is
+ * refused naming the image.  threads in [1, 16] std::threads over the images; the bytes do not depend on it. */
+int hpe_jpeg_entropy_encode(const HpeJpegEncImage* table, int B, const short* coef, long long coef_count, int units, int xdensity,
+                            int ydensity, int threads, unsigned char* out, long long out_capacity, long long* offsets_out,
+                            long long* lengths_out);
+
 /* -- PNG decode: the PNG streams tf.image.decode_jpeg also takes (LSP masks, MPII frames) -------------------------------------
  * The chunk walk, the CRCs and inflate are host code (hpe_amd/png.py: zlib); what reaches this library is, per image, the inflated
  * scanlines -- H rows of one filter byte and rowbytes filtered bytes -- and a table entry.  Two launches (hpe_png_backend): the PNG
