@@ -100,14 +100,14 @@ class HpeJpegImage(C.Structure):
     """one table entry of hpe_jpeg_decode / hpe_jpeg_backend (include/hpe.h), 304 bytes"""
     _fields_ = [("coef_offset", C.c_longlong * 3), ("plane_offset", C.c_longlong * 3), ("out_offset", C.c_longlong), ("H", C.c_int),
                 ("W", C.c_int), ("ncomp", C.c_int), ("channels", C.c_int), ("hmax", C.c_int), ("vmax", C.c_int), ("blocks_w", C.c_int * 3),
-                ("blocks_h", C.c_int * 3), ("idct_group0", C.c_int), ("store_group0", C.c_int), ("quant", C.c_ubyte * 192)]
+                ("blocks_h", C.c_int * 3), ("idct_group0", C.c_int), ("store_group0", C.c_int), ("quant", (C.c_ubyte * 64) * 3)]
 
 
 class HpeJpegEncImage(C.Structure):
     """one table entry of hpe_jpeg_encode_layout / hpe_jpeg_forward / hpe_jpeg_entropy_encode (include/hpe.h), 232 bytes"""
     _fields_ = [("frame_offset", C.c_longlong), ("coef_offset", C.c_longlong * 3), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int),
                 ("hmax", C.c_int), ("vmax", C.c_int), ("blocks_w", C.c_int * 3), ("blocks_h", C.c_int * 3), ("real_w", C.c_int * 3),
-                ("real_h", C.c_int * 3), ("group0", C.c_int), ("quant", C.c_ubyte * 128)]
+                ("real_h", C.c_int * 3), ("group0", C.c_int), ("quant", (C.c_ubyte * 64) * 2)]
 
 
 class HpePngImage(C.Structure):
@@ -120,6 +120,19 @@ class HpePngImage(C.Structure):
 class HpePngFilterImage(C.Structure):
     """one table entry of hpe_png_filter (include/hpe.h), 32 bytes"""
     _fields_ = [("frame_offset", C.c_longlong), ("scan_offset", C.c_longlong), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("row0", C.c_int)]
+
+
+def record_dtype(struct):
+    """the numpy record dtype of a table entry's ctypes structure: its names, offsets and itemsize; a nested array such as
+    (c_ubyte * 64) * 3 becomes ONE sub-array field of shape (3, 64), where numpy alone nests a (64,) sub-array in a (3,) one"""
+    d = np.dtype(struct)
+    formats = []
+    for name in d.names:
+        t, shape = d.fields[name][0], ()
+        while t.subdtype:
+            t, shape = t.subdtype[0], shape + t.subdtype[1]
+        formats.append((t, shape))
+    return np.dtype({"names": list(d.names), "formats": formats, "offsets": [d.fields[n][1] for n in d.names], "itemsize": d.itemsize})
 
 
 GEMM_DENSE, GEMM_STRIDED, GEMM_CONV3, GEMM_DUAL = 0, 1, 2, 4  # HpeDebugGemm.mode

@@ -5,12 +5,10 @@ The random draws are inputs (``draw_augmentation``), the way ``drop`` is an inpu
 defined in DESIGN.md "Training-batch augmentation".  HIP-backed through include/hpe.h; no CPU fallback."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
-from .jpeg import DecodedBatch
+from .batch_io import DecodedBatch, frame_offsets as packed_offsets, pinned, ptr as _p, stream_ptr, upload
 
 IMG_SIZE = 224
 NUM_KP = 19
@@ -18,10 +16,7 @@ TRANS_MAX = 20  # src/config.py:72
 SCALE_RANGE = (0.8, 1.23)  # src/config.py:73-74
 SWAP_INDS = (5, 4, 3, 2, 1, 0, 11, 10, 9, 8, 7, 6, 12, 13, 14, 16, 15, 18, 17)  # flip_image, src/util/data_utils.py:234-235
 # HpeAugmentFrame (include/hpe.h) as a numpy record
-TABLE_DTYPE = np.dtype([("frame_offset", "<i8"), ("seg_offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("newH", "<i4"), ("newW", "<i4"),
-                        ("cx", "<i4"), ("cy", "<i4"), ("fx", "<f4"), ("fy", "<f4"), ("flip", "<i4"), ("inside", "<i4"), ("rx", "<f4"),
-                        ("ry", "<f4")])
-assert TABLE_DTYPE.itemsize == C.sizeof(_lib.HpeAugmentFrame) == 64
+TABLE_DTYPE = _lib.record_dtype(_lib.HpeAugmentFrame)
 
 
 def draw_augmentation(B, generator=None, trans_max=TRANS_MAX, scale_range=SCALE_RANGE):
@@ -83,8 +78,7 @@ def plan_augmentation(sizes, centers, draws, trans_max=TRANS_MAX, frame_offsets=
         out = np.empty(B, TABLE_DTYPE)
     elif out.dtype != TABLE_DTYPE or out.shape != (B,) or not out.flags.c_contiguous:
         raise ValueError("out must be a contiguous record array [B] of TABLE_DTYPE")
-    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    _lib.check(_lib.load().hpe_augment_plan(B, p(sizes), p(centers), p(trans), p(scale), p(flip), int(trans_max), p(fo), p(so), p(out)))
+    _lib.check(_lib.load().hpe_augment_plan(B, _p(sizes), _p(centers), _p(trans), _p(scale), _p(flip), int(trans_max), _p(fo), _p(so), _p(out)))
     if not clamp and not out["inside"].all():
         bad = np.flatnonzero(out["inside"] == 0)
         raise ValueError("the 224 x 224 window of sample(s) %s leaves the frame padded by %d pixels (pass clamp=True to clamp to the edge)"
@@ -103,8 +97,7 @@ def _pack(items, channels, name):
     if isinstance(items, DecodedBatch):  # decode_jpeg_batch's buffer is this packing already
         if items.channels != (channels or 1):
             raise ValueError("%s must be decoded with %d channel(s)" % (name, channels or 1))
-        total = int(items.offsets[-1] + (items.sizes[-1, 0] * items.sizes[-1, 1] * items.channels + 15) // 16 * 16)
-        return items.buffer, items.sizes, items.offsets, total
+        return items.buffer, items.sizes, items.offsets, items.nbytes
     if isinstance(items, (list, tuple)):
         ts = [as_t(f) for f in items]
         if not ts:
@@ -113,11 +106,7 @@ def _pack(items, channels, name):
             if t.dtype != torch.uint8 or t.dim() != nd or (channels and t.shape[2] != channels) or t.numel() < 1:
                 raise ValueError("%s must be uint8 %s arrays or tensors" % (name, tail))
         sizes = np.array([[int(t.shape[0]), int(t.shape[1])] for t in ts], np.int64)
-        offs, total = [], 0
-        for t in ts:
-            offs.append(total)
-            total += (t.numel() + 15) // 16 * 16
-        return ts, sizes, np.array(offs, np.int64), total
+        return (ts, sizes) + packed_offsets(sizes, channels or 1)
     t = as_t(items)
     if t.dtype != torch.uint8 or t.dim() != nd + 1 or (channels and t.shape[3] != channels) or t.numel() < 1:
         raise ValueError("%s must be a uint8 [B,%s tensor or a list of uint8 %s" % (name, tail[1:], tail))
@@ -176,19 +165,17 @@ def augment_batch(frames, segs, kp, centers, draws=None, generator=None, trans_m
             if not isinstance(t, torch.Tensor) or tuple(t.shape) != s or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
                 raise ValueError("out must hold contiguous float32 CUDA tensors %s on %s" % (list(shapes), dev))
     with torch.cuda.device(dev):
-        pinned = torch.empty(B * TABLE_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
-        table = pinned.numpy().view(TABLE_DTYPE)
-        plan_augmentation(fsizes, centers, draws, trans_max=trans_max, frame_offsets=foffs, seg_offsets=soffs, clamp=clamp, out=table)
+        table_pinned, host = pinned(B * TABLE_DTYPE.itemsize)
+        plan_augmentation(fsizes, centers, draws, trans_max=trans_max, frame_offsets=foffs, seg_offsets=soffs, clamp=clamp,
+                          out=host.view(TABLE_DTYPE))
         fbuf = _to_device(fpk, foffs, ftotal, dev)
         sbuf = _to_device(spk, soffs, stotal, dev)
         kpd = kp.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
-        table_dev = torch.empty(pinned.numel(), dtype=torch.uint8, device=dev)
-        table_dev.copy_(pinned, non_blocking=True)
+        table_dev = upload(table_pinned, dev)
         if out is None:
             out = tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in shapes)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().hpe_augment_batch(fbuf.data_ptr(), sbuf.data_ptr(), pinned.data_ptr(), table_dev.data_ptr(), kpd.data_ptr(), B,
-                                                 out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), st))
+        _lib.check(_lib.load().hpe_augment_batch(fbuf.data_ptr(), sbuf.data_ptr(), table_pinned.data_ptr(), table_dev.data_ptr(), kpd.data_ptr(), B,
+                                                 out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), stream_ptr(dev)))
     return tuple(out)
 
 

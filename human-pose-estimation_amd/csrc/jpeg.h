@@ -3,11 +3,40 @@
 // build.  The C ABI over it (hpe_jpeg_info, hpe_jpeg_decode) and the two launches live in jpeg_decode.hip.
 #pragma once
 
+#include <atomic>
 #include <string>
+#include <thread>
+#include <vector>
 
 #include "../../include/hpe.h"
 
 namespace jpeg {
+
+// zigzag position -> natural order, shared by the entropy decoder and the entropy coder
+inline constexpr unsigned char ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// a refusal: the clause into *why, false back
+inline bool refuse(std::string* why, const std::string& clause) {
+    if (why) *why = clause;
+    return false;
+}
+inline std::string at_image(int b, const std::string& clause) { return "image " + std::to_string(b) + ": " + clause; }
+
+// work(b) for every image of the batch on min(threads, B) threads; an atomic counter hands the images out
+template <class Work>
+void for_each_image(int B, int threads, Work work) {
+    std::atomic<int> next(0);
+    auto run = [&]() {
+        for (int b = next.fetch_add(1); b < B; b = next.fetch_add(1)) work(b);
+    };
+    const int workers = threads < B ? threads : B;
+    if (workers <= 1) return run();
+    std::vector<std::thread> pool;
+    for (int i = 0; i < workers; ++i) pool.emplace_back(run);
+    for (auto& th : pool) th.join();
+}
 
 constexpr int IDCT_BLOCKS_PER_GROUP = 32;  // launch one: 8 threads per 8x8 block, 256 threads
 constexpr int STORE_BYTES_PER_GROUP = 1024;  // launch two: 4 output bytes per thread, 256 threads

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <string>
 
+#include "batch_table.h"
 #include "hpe_ctx.h"
 #include "jpeg.h"
 
@@ -62,25 +63,10 @@ __device__ __forceinline__ void idct8(const int* in, int* out) {
     out[4] = (int)(tmp13 - t0 + r) >> SHIFT;
 }
 
-// the last image whose first workgroup is <= group (the host checked that the bases are the strictly increasing prefix sums)
-template <bool STORE>
-__device__ __forceinline__ int find_image(const HpeJpegImage* __restrict__ table, int B, int group) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        const int g = STORE ? table[mid].store_group0 : table[mid].idct_group0;
-        if (g <= group)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(JPEG_THREADS) void jpeg_idct_kernel(const HpeJpegImage* __restrict__ table, int B, const short* __restrict__ coef,
                                                                  unsigned char* __restrict__ workspace) {
     __shared__ int ws[jpeg::IDCT_BLOCKS_PER_GROUP][8][9];  // [block][row][column], rows padded against bank conflicts in pass 2
-    const int b = find_image<false>(table, B, blockIdx.x);
+    const int b = find_image<&HpeJpegImage::idct_group0>(table, B, (int)blockIdx.x);
     const HpeJpegImage* e = table + b;
     const int slot = threadIdx.x >> 3, j = threadIdx.x & 7;
     int k = (blockIdx.x - e->idct_group0) * jpeg::IDCT_BLOCKS_PER_GROUP + slot;  // block of the image, components back to back
@@ -142,7 +128,7 @@ __device__ __forceinline__ int clamp_u8(int v) { return min(max(v, 0), 255); }
 
 __global__ __launch_bounds__(JPEG_THREADS) void jpeg_store_kernel(const HpeJpegImage* __restrict__ table, int B, const unsigned char* __restrict__ workspace,
                                                                   unsigned char* __restrict__ frames) {
-    const int b = find_image<true>(table, B, blockIdx.x);
+    const int b = find_image<&HpeJpegImage::store_group0>(table, B, (int)blockIdx.x);
     const HpeJpegImage* e = table + b;
     const int H = e->H, W = e->W, ch = e->channels, ncomp = e->ncomp;
     const int total = H * W * ch;  // < 2^31 by HPE_JPEG_MAX_SIDE

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <string>
 
+#include "batch_table.h"
 #include "hpe_ctx.h"
 #include "jpeg.h"
 
@@ -56,19 +57,6 @@ __device__ __forceinline__ void fdct8(const int* d, int* out) {
     out[1] = (m7 + z1 + z4 + R) >> SHIFT;
 }
 
-// the last image whose first workgroup is <= group (the host checked that the bases are the strictly increasing prefix sums)
-__device__ __forceinline__ int find_image(const HpeJpegEncImage* __restrict__ table, int B, int group) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].group0 <= group)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
 // jccolor.c on one RGB pixel: component c of (Y, Cb, Cr)
 __device__ __forceinline__ int ycc(const unsigned char* __restrict__ px, int c) {
     const int r = px[0], g = px[1], b = px[2];
@@ -80,7 +68,7 @@ __device__ __forceinline__ int ycc(const unsigned char* __restrict__ px, int c) 
 __global__ __launch_bounds__(ENC_THREADS) void jpeg_forward_kernel(const HpeJpegEncImage* __restrict__ table, int B,
                                                                    const unsigned char* __restrict__ frames, short* __restrict__ coef) {
     __shared__ int ws[jpeg::IDCT_BLOCKS_PER_GROUP][8][9];  // [block][row][column], rows padded against bank conflicts in the column pass
-    const int b = find_image(table, B, blockIdx.x);
+    const int b = find_image<&HpeJpegEncImage::group0>(table, B, (int)blockIdx.x);
     const HpeJpegEncImage* e = table + b;
     const int slot = threadIdx.x >> 3, j = threadIdx.x & 7;
     int k = (blockIdx.x - e->group0) * jpeg::IDCT_BLOCKS_PER_GROUP + slot;  // block of the image, components back to back

@@ -6,21 +6,19 @@
 // chroma, one interleaved scan, DRI / RST0-7, any DHT.  Everything else is refused with a clause; nothing is decoded "as far as it goes".
 // Every read is checked against the stream length (Reader, Bits), every coefficient index against 63, and every write lands in the
 // image's own region of the coefficient buffer, whose end decode_batch holds against the caller's capacity before anything is written.
-#include <atomic>
 #include <climits>
 #include <cstdint>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "jpeg.h"
 
 namespace {
 
-const unsigned char ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                  41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                  30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+using jpeg::at_image;
+using jpeg::refuse;
+using jpeg::ZIGZAG;
 
 struct Huff {
     bool defined = false;
@@ -40,11 +38,6 @@ struct Header {
     int restart = 0;
     long long scan_pos = 0;  // first byte of the entropy-coded data
 };
-
-bool refuse(std::string* why, const char* clause) {
-    if (why) *why = clause;
-    return false;
-}
 
 // bounds-checked big-endian reads of the marker segments
 struct Reader {
@@ -420,8 +413,6 @@ bool layout_one(const HpeJpegInfo& in, int channels, Totals* t, HpeJpegImage* e)
     return t->idct_groups <= INT_MAX && t->store_groups <= INT_MAX;
 }
 
-std::string at_image(int b, const std::string& clause) { return "image " + std::to_string(b) + ": " + clause; }
-
 }  // namespace
 
 namespace jpeg {
@@ -492,29 +483,18 @@ int decode_batch(int B, const unsigned char* const* streams, const long long* le
     if (coef_out) {
         if (t.coef > coef_capacity)
             return refuse(why, "coef_capacity is below the batch's coefficient count"), HPE_ERR_INVALID;
-        std::atomic<int> next(0);
-        auto work = [&]() {
-            for (int b = next.fetch_add(1); b < B; b = next.fetch_add(1)) {
-                if (status_out[b] != HPE_OK) continue;
-                HpeJpegImage& e = table_out[b];
-                const Header& hd = headers[b];
-                for (int c = 0; c < e.ncomp; ++c) std::memcpy(e.quant[c], hd.quant[hd.tq[c]], 64);
-                if (!decode_scan(streams[b], lengths[b], hd, e, coef_out, &whys[b])) {
-                    for (int c = 0; c < e.ncomp; ++c)  // no partial decode stays behind
-                        std::memset(coef_out + e.coef_offset[c], 0, sizeof(short) * 64 * (size_t)e.blocks_w[c] * (size_t)e.blocks_h[c]);
-                    std::memset(&e, 0, sizeof(e));
-                    status_out[b] = HPE_ERR_INVALID;
-                }
+        for_each_image(B, threads, [&](int b) {
+            if (status_out[b] != HPE_OK) return;
+            HpeJpegImage& e = table_out[b];
+            const Header& hd = headers[b];
+            for (int c = 0; c < e.ncomp; ++c) std::memcpy(e.quant[c], hd.quant[hd.tq[c]], 64);
+            if (!decode_scan(streams[b], lengths[b], hd, e, coef_out, &whys[b])) {
+                for (int c = 0; c < e.ncomp; ++c)  // no partial decode stays behind
+                    std::memset(coef_out + e.coef_offset[c], 0, sizeof(short) * 64 * (size_t)e.blocks_w[c] * (size_t)e.blocks_h[c]);
+                std::memset(&e, 0, sizeof(e));
+                status_out[b] = HPE_ERR_INVALID;
             }
-        };
-        const int workers = threads < B ? threads : B;
-        if (workers <= 1) {
-            work();
-        } else {
-            std::vector<std::thread> pool;
-            for (int i = 0; i < workers; ++i) pool.emplace_back(work);
-            for (auto& th : pool) th.join();
-        }
+        });
     }
     for (int b = 0; b < B; ++b)
         if (status_out[b] != HPE_OK) {

@@ -6,21 +6,19 @@
 // component ids 1, 2, 3, the Annex K.3-K.6 Huffman tables, one interleaved scan, no restart markers.  Every write goes through Out,
 // which holds it against the end of the image's own region; every coefficient read lies in a plane that the entry check held against
 // coef_count.
-#include <atomic>
 #include <climits>
 #include <cstdint>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "jpeg.h"
 
 namespace {
 
-const unsigned char ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                  41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                  30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+using jpeg::at_image;
+using jpeg::refuse;
+using jpeg::ZIGZAG;
 
 // Annex K.1, K.2 in natural order
 const unsigned char BASE_Q[2][64] = {
@@ -83,13 +81,6 @@ const Tables& tables() {
     static const Tables t;
     return t;
 }
-
-bool refuse(std::string* why, const std::string& clause) {
-    if (why) *why = clause;
-    return false;
-}
-
-std::string at_image(int b, const std::string& clause) { return "image " + std::to_string(b) + ": " + clause; }
 
 // the image's own region of the caller's buffer: a write past its end is dropped and remembered
 struct Out {
@@ -342,22 +333,11 @@ int entropy_encode(const HpeJpegEncImage* table, int B, const short* coef, long 
         return refuse(why, "out_capacity " + std::to_string(out_capacity) + " is below the batch's bound " + std::to_string(bound)), HPE_ERR_INVALID;
     std::vector<std::string> whys((size_t)B);
     std::vector<char> bad((size_t)B, 0);
-    std::atomic<int> next(0);
-    auto work = [&]() {
-        for (int b = next.fetch_add(1); b < B; b = next.fetch_add(1)) {
-            Out o{out, offsets_out[b], offsets_out[b] + enc_stream_bound(table[b])};
-            if (!encode_image(table[b], coef, units, xdensity, ydensity, &o, &whys[(size_t)b])) bad[(size_t)b] = 1;
-            lengths_out[b] = bad[(size_t)b] ? 0 : o.pos - offsets_out[b];
-        }
-    };
-    const int workers = threads < B ? threads : B;
-    if (workers <= 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int i = 0; i < workers; ++i) pool.emplace_back(work);
-        for (auto& th : pool) th.join();
-    }
+    for_each_image(B, threads, [&](int b) {
+        Out o{out, offsets_out[b], offsets_out[b] + enc_stream_bound(table[b])};
+        if (!encode_image(table[b], coef, units, xdensity, ydensity, &o, &whys[(size_t)b])) bad[(size_t)b] = 1;
+        lengths_out[b] = bad[(size_t)b] ? 0 : o.pos - offsets_out[b];
+    });
     for (int b = 0; b < B; ++b)
         if (bad[(size_t)b]) return refuse(why, at_image(b, whys[(size_t)b])), HPE_ERR_INVALID;
     return HPE_OK;

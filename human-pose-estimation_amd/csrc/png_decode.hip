@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <string>
 
+#include "batch_table.h"
 #include "hpe_ctx.h"
 #include "png.h"
 
@@ -195,20 +196,6 @@ __global__ __launch_bounds__(PNG_WAVE) void png_unfilter_kernel(const HpePngImag
         unfilter_image<4>(src, dst, png_row, H, rowbytes);
 }
 
-// the last image whose first workgroup is <= group: images without workgroups (direct ones) share their base with the next image and
-// are stepped over
-__device__ __forceinline__ int find_image(const HpePngImage* __restrict__ table, int B, int group) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].store_group0 <= group)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
 // Colour to grey: libpng's png_set_rgb_to_gray without gamma, coefficients 9797 / 19234 / 3737 of 32768 (they sum to 32768, so a grey
 // pixel keeps its value).  TRUNCATING, as libpng 1.6's png_do_rgb_to_gray does without a gamma table ("the historical approach which
 // simply truncates"); the rounding variant would add 16384.  DESIGN.md states what this rests on.
@@ -223,7 +210,7 @@ __device__ __forceinline__ u32 sample_at(const unsigned char* __restrict__ row, 
 
 __global__ __launch_bounds__(PNG_STORE_THREADS) void png_store_kernel(const HpePngImage* __restrict__ table, int B, const unsigned char* __restrict__ raw,
                                                                       const unsigned char* __restrict__ workspace, unsigned char* __restrict__ frames) {
-    const int b = find_image(table, B, blockIdx.x);
+    const int b = find_image<&HpePngImage::store_group0>(table, B, (int)blockIdx.x);
     const HpePngImage* e = table + b;
     if (e->work_offset < 0) return;  // a direct image has no workgroup: not reached with a checked table
     const int H = e->H, W = e->W, ch = e->channels, ct = e->color_type, depth = e->depth, rowbytes = e->rowbytes;

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <string>
 
+#include "batch_table.h"
 #include "hpe_ctx.h"
 
 namespace {
@@ -24,19 +25,6 @@ constexpr int ENC_ROWS_PER_GROUP = 4;  // waves of a workgroup, one row each
 static_assert(sizeof(HpePngFilterImage) == 32, "the table entry of include/hpe.h and png_encode.py");
 
 typedef unsigned int u32;
-
-// the last image whose first row is <= row: every image has at least one row, so row0 is strictly increasing
-__device__ __forceinline__ int find_row_image(const HpePngFilterImage* __restrict__ table, int B, long long row) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].row0 <= row)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ u32 paeth_pred(u32 a, u32 b, u32 c) {  // ties in the order a, b, c
     const int pa = abs((int)b - (int)c), pb = abs((int)a - (int)c), pc = abs((int)a + (int)b - 2 * (int)c);
@@ -63,7 +51,7 @@ __global__ __launch_bounds__(ENC_WAVE* ENC_ROWS_PER_GROUP) void png_filter_kerne
     const int lane = threadIdx.x & (ENC_WAVE - 1);
     const long long row = (long long)blockIdx.x * ENC_ROWS_PER_GROUP + (threadIdx.x / ENC_WAVE);  // wave-uniform
     if (row >= rows) return;
-    const HpePngFilterImage* e = table + find_row_image(table, B, row);
+    const HpePngFilterImage* e = table + find_image<&HpePngFilterImage::row0>(table, B, row);
     const int y = (int)(row - e->row0), bpp = e->C, rb = e->W * e->C;  // rb <= 16384 * 4
     const unsigned char* cur = frames + e->frame_offset + (long long)y * rb;
     const unsigned char* prev = cur - rb;  // read only when y > 0

@@ -6,11 +6,10 @@ mesh columns come from ``SMPLRenderer``, batched.  The raster rules are this pro
 are not drawn.  HIP-backed through include/hpe.h; no CPU fallback."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
+from .batch_io import stream_ptr
 
 NUM_JOINTS = 19
 MAX_RADIUS = 256
@@ -77,9 +76,8 @@ def draw_panels(images, kp_gt, kp_pred, rend_img, rend_seg):
     rend_img, rend_seg = rend_img.contiguous(), rend_seg.contiguous()
     out = torch.empty((n, T * S, 3 * S, 3), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.load().hpe_draw_panels(images.data_ptr(), kp_gt.data_ptr(), kp_pred.data_ptr(), rend_img.data_ptr(), rend_seg.data_ptr(),
-                                               _table_dev(dev).data_ptr(), n, T, S, out.data_ptr(), st))
+                                               _table_dev(dev).data_ptr(), n, T, S, out.data_ptr(), stream_ptr(dev)))
     return out
 
 
@@ -122,9 +120,8 @@ def draw_skeleton(image, joints, draw_edges=True, vis=None, radius=None):
     if not 1 <= radius <= MAX_RADIUS:
         raise ValueError("radius must be in [1, %d]" % MAX_RADIUS)
     with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.load().hpe_draw_skeleton(work.data_ptr(), jd.data_ptr(), None if vd is None else vd.data_ptr(), _table_dev(dev).data_ptr(), 1, H,
-                                                 W, 1 if draw_edges else 0, radius, st))
+                                                 W, 1 if draw_edges else 0, radius, stream_ptr(dev)))
     if max_val is not None:
         # k / 255 through a table divided on the host: correctly rounded whatever the device's division does
         work = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255)).to(dev)[work.long()] if max_val <= 1.0 else work.float()

@@ -10,35 +10,17 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .batch_io import DEFAULT_THREADS, DecodedBatch, check_out, frames_out, pinned, ptr as _p, stream_list, stream_ptr, upload
 
 # HpeJpegInfo / HpeJpegImage (include/hpe.h) as numpy records
-INFO_DTYPE = np.dtype([("status", "<i4"), ("H", "<i4"), ("W", "<i4"), ("ncomp", "<i4"), ("hs", "<i4", 3), ("vs", "<i4", 3),
-                       ("blocks_w", "<i4", 3), ("blocks_h", "<i4", 3), ("coefs", "<i8")])
-TABLE_DTYPE = np.dtype([("coef_offset", "<i8", 3), ("plane_offset", "<i8", 3), ("out_offset", "<i8"), ("H", "<i4"), ("W", "<i4"),
-                        ("ncomp", "<i4"), ("channels", "<i4"), ("hmax", "<i4"), ("vmax", "<i4"), ("blocks_w", "<i4", 3),
-                        ("blocks_h", "<i4", 3), ("idct_group0", "<i4"), ("store_group0", "<i4"), ("quant", "u1", (3, 64))])
-assert INFO_DTYPE.itemsize == C.sizeof(_lib.HpeJpegInfo) == 72
-assert TABLE_DTYPE.itemsize == C.sizeof(_lib.HpeJpegImage) == 304
-DEFAULT_THREADS = 8  # a plain argument everywhere; never derived from the machine's core count
-
-_p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+INFO_DTYPE = _lib.record_dtype(_lib.HpeJpegInfo)
+TABLE_DTYPE = _lib.record_dtype(_lib.HpeJpegImage)
 
 
 def _stream_args(streams):
-    """-> (arrays kept alive, pointer array, lengths int64 [B]) of a list of bytes-like JPEG streams"""
-    if isinstance(streams, (bytes, bytearray, memoryview)) or not hasattr(streams, "__len__"):
-        raise ValueError("streams must be a list of bytes objects")
-    if len(streams) < 1:
-        raise ValueError("streams is empty")
-    keep = []
-    for s in streams:
-        if not isinstance(s, (bytes, bytearray, memoryview, np.ndarray)):
-            raise ValueError("every stream must be bytes-like")
-        keep.append(np.frombuffer(s.tobytes() if isinstance(s, np.ndarray) else bytes(s), dtype=np.uint8))
-    lengths = np.array([a.size for a in keep], np.int64)
-    keep = [a if a.size else np.zeros(1, np.uint8) for a in keep]  # an empty stream still needs an address; its length stays 0
-    ptrs = (C.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
-    return keep, ptrs, lengths
+    """-> (bytes kept alive, pointer array, lengths int64 [B]) of a list of bytes-like JPEG streams"""
+    data, lengths = stream_list(streams)
+    return data, (C.c_char_p * len(data))(*data), lengths
 
 
 def _channels(channels, B):
@@ -82,24 +64,25 @@ def entropy_decode(streams, channels=3, threads=DEFAULT_THREADS, alloc=None):
     return coef, table, totals
 
 
-class DecodedBatch:
-    """Decoded frames in one device buffer, each on a 16-byte boundary (the packing ``augment_batch`` uses): ``buffer`` uint8 CUDA
-    tensor, ``sizes`` int64 [B,2] (H, W), ``offsets`` int64 [B] (bytes), ``channels`` 1 or 3, ``frames`` a list of views [H,W,3] (or
-    [H,W] for one channel)."""
+def _pinned_alloc(keep):
+    """``entropy_decode``'s alloc over ONE pinned buffer, coefficients then table; the buffer is appended to ``keep``"""
+    def alloc(n, B):
+        buf, host = pinned(2 * n + B * TABLE_DTYPE.itemsize)
+        keep.append(buf)
+        return host[:2 * n].view(np.int16), host[2 * n:].view(TABLE_DTYPE)
 
-    def __init__(self, buffer, sizes, offsets, channels):
-        self.buffer, self.sizes, self.offsets, self.channels = buffer, sizes, offsets, int(channels)
+    return alloc
 
-    def __len__(self):
-        return int(self.sizes.shape[0])
 
-    @property
-    def frames(self):
-        out = []
-        for (h, w), o in zip(self.sizes.tolist(), self.offsets.tolist()):
-            v = self.buffer[o:o + h * w * self.channels]
-            out.append(v.view(h, w, 3) if self.channels == 3 else v.view(h, w))
-        return out
+def _launch_jpeg(pinned_buf, table, totals, out, dev):
+    """one non-blocking copy of the staged buffer and the two launches on the current stream"""
+    import torch
+
+    n = int(totals[0])
+    staged = upload(pinned_buf, dev)
+    workspace = torch.empty(int(totals[1]), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().hpe_jpeg_backend(_p(table), staged.data_ptr() + 2 * n, table.shape[0], staged.data_ptr(), n, workspace.data_ptr(),
+                                            workspace.numel(), out.data_ptr(), out.numel(), stream_ptr(dev)))
 
 
 def decode_jpeg_batch(streams, channels=3, threads=DEFAULT_THREADS, out=None):
@@ -112,31 +95,11 @@ def decode_jpeg_batch(streams, channels=3, threads=DEFAULT_THREADS, out=None):
 
     if channels not in (1, 3):
         raise ValueError("channels must be 1 or 3")
-    dev = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
-    if out is not None and (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 1 or
-                            not out.is_contiguous() or out.data_ptr() % 16):
-        raise ValueError("out must be a contiguous 1-D uint8 CUDA tensor on a 16-byte boundary")
-    pinned = []
-
-    def alloc(n, B):
-        buf = torch.empty(2 * n + B * TABLE_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
-        pinned.append(buf)
-        host = buf.numpy()
-        return host[:2 * n].view(np.int16), host[2 * n:].view(TABLE_DTYPE)
-
+    dev = check_out(out)
+    keep = []
     with torch.cuda.device(dev):
-        coef, table, totals = entropy_decode(streams, channels, threads, alloc)
-        n, B = coef.shape[0], table.shape[0]
-        need = int(totals[2])
-        if out is None:
-            out = torch.empty(need, dtype=torch.uint8, device=dev)
-        elif out.numel() < need:
-            raise ValueError("out holds %d bytes, the packed frames need %d" % (out.numel(), need))
-        staged = torch.empty(pinned[0].numel(), dtype=torch.uint8, device=dev)
-        staged.copy_(pinned[0], non_blocking=True)
-        workspace = torch.empty(int(totals[1]), dtype=torch.uint8, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.load().hpe_jpeg_backend(_p(table), staged.data_ptr() + 2 * n, B, staged.data_ptr(), n, workspace.data_ptr(),
-                                                workspace.numel(), out.data_ptr(), out.numel(), st))
+        _, table, totals = entropy_decode(streams, channels, threads, _pinned_alloc(keep))
+        out = frames_out(out, int(totals[2]), dev)
+        _launch_jpeg(keep[0], table, totals, out, dev)
     sizes = np.stack([table["H"], table["W"]], axis=1).astype(np.int64)
     return DecodedBatch(out, sizes, table["out_offset"].astype(np.int64), channels)

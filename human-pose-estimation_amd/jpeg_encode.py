@@ -6,21 +6,15 @@ baseline compressor byte for byte; what is computed is defined in DESIGN.md "Dat
 include/hpe.h; no CPU fallback and no image library."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
 from ._lib import HpeError
-from .jpeg import DEFAULT_THREADS
-from .png import _p
-from .png_encode import _layout
+from .batch_io import DEFAULT_THREADS, download, pack_frames, ptr as _p, stream_ptr, thread_count, upload_table
 
 # HpeJpegEncImage (include/hpe.h) as a numpy record
-ENC_DTYPE = np.dtype([("frame_offset", "<i8"), ("coef_offset", "<i8", 3), ("H", "<i4"), ("W", "<i4"), ("C", "<i4"), ("hmax", "<i4"),
-                      ("vmax", "<i4"), ("blocks_w", "<i4", 3), ("blocks_h", "<i4", 3), ("real_w", "<i4", 3), ("real_h", "<i4", 3),
-                      ("group0", "<i4"), ("quant", "u1", (2, 64))])
-assert ENC_DTYPE.itemsize == C.sizeof(_lib.HpeJpegEncImage) == 232
+ENC_DTYPE = _lib.record_dtype(_lib.HpeJpegEncImage)
+CHANNELS = (1, 3)  # grey, RGB
 SAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}  # luma (h, v); chroma is 1x1
 UNITS = {None: 0, "": 0, "none": 0, "in": 1, "cm": 2}
 DEFAULT_DENSITY = (300, 300, "in")
@@ -48,27 +42,6 @@ def _density(density):
     if not (1 <= x <= 65535 and 1 <= y <= 65535):
         raise HpeError("density: x and y must be in [1, 65535]")
     return x, y, unit
-
-
-def _thread_count(threads):
-    if int(threads) != threads or not 1 <= int(threads) <= 16:
-        raise HpeError("threads must be an integer in [1, 16], got %r" % (threads,))
-    return int(threads)
-
-
-def _channel_fault(frames):
-    """the channel clause of ``frames`` before ``_layout`` packs anything: C = 4 is a PNG encoder's frame, not this one's"""
-    import torch
-
-    if isinstance(frames, torch.Tensor):
-        counts = [int(frames.shape[3])] if frames.dim() == 4 else []
-    elif isinstance(frames, (list, tuple)):
-        counts = [int(t.shape[2]) if isinstance(t, torch.Tensor) and t.dim() == 3 else 1 for t in frames]
-    else:
-        counts = [int(getattr(frames, "channels", 1))]
-    for i, Cn in enumerate(counts):
-        if Cn not in (1, 3):
-            raise HpeError("image %d: %d channels: the channel count must be 1 or 3" % (i, Cn))
 
 
 def encode_layout(shapes, offsets=None, quality=95, subsampling="4:2:0"):
@@ -99,7 +72,7 @@ def entropy_encode(coef, table, density=DEFAULT_DENSITY, threads=DEFAULT_THREADS
     ``out``: an optional uint8 array to write into, at least the bound ``sum(stream_bound(table))`` long (smaller is refused before
     anything is written).  The bytes do not depend on ``threads`` (1 .. 16)."""
     x, y, unit = _density(density)
-    threads = _thread_count(threads)
+    threads = thread_count(threads, HpeError)
     coef = np.ascontiguousarray(coef, dtype=np.int16)
     table = np.ascontiguousarray(table, dtype=ENC_DTYPE)
     B = len(table)
@@ -149,22 +122,17 @@ def forward_dct_batch(frames, quality=95, subsampling="4:2:0", out=None):
     import torch
 
     quality, _ = _quality(quality), _sampling(subsampling)
-    _channel_fault(frames)
-    buf, shapes, offsets = _layout(frames)
+    buf, shapes, offsets = pack_frames(frames, CHANNELS)
     table, totals = encode_layout(shapes, offsets, quality, subsampling)
     n, dev = int(totals[0]), buf.device
     if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.int16 or out.dim() != 1 or
                             not out.is_contiguous() or out.data_ptr() % 16 or out.numel() < n):
         raise ValueError("out must be a contiguous 1-D int16 tensor on the frames' device, on a 16-byte boundary, of at least %d elements" % n)
     with torch.cuda.device(dev):
-        pinned = torch.empty(table.nbytes, dtype=torch.uint8, pin_memory=True)
-        pinned.numpy()[:] = table.view(np.uint8)
-        table_dev = torch.empty(table.nbytes, dtype=torch.uint8, device=dev)
-        table_dev.copy_(pinned, non_blocking=True)
+        table_dev = upload_table(table, dev)
         coef = torch.empty(n, dtype=torch.int16, device=dev) if out is None else out
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.load().hpe_jpeg_forward(_p(table), table_dev.data_ptr(), len(shapes), buf.data_ptr(), buf.numel(), coef.data_ptr(),
-                                                coef.numel(), st))
+                                                coef.numel(), stream_ptr(dev)))
     return coef, table
 
 
@@ -175,13 +143,7 @@ def encode_jpeg_batch(frames, quality=95, subsampling="4:2:0", density=DEFAULT_D
     grey frames.  Anything else raises HpeError naming the image and the clause, before anything is launched.  The table goes up in one
     pinned copy, one launch computes every coefficient, they come down in one copy, and the Huffman coder runs per image on ``threads``
     host threads (1 .. 16).  The bytes do not depend on ``threads``.  This call waits for the device."""
-    import torch
-
     _density(density)
-    threads = _thread_count(threads)
+    threads = thread_count(threads, HpeError)
     coef, table = forward_dct_batch(frames, quality, subsampling)
-    with torch.cuda.device(coef.device):
-        host = torch.empty(coef.numel(), dtype=torch.int16, pin_memory=True)
-        host.copy_(coef, non_blocking=True)
-        torch.cuda.current_stream(coef.device).synchronize()
-    return entropy_encode(host.numpy(), table, density, threads)
+    return entropy_encode(download(coef), table, density, threads)

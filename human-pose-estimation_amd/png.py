@@ -7,7 +7,6 @@ records".  ``decode_image_batch`` takes JPEG and PNG streams side by side.  HIP-
 image library."""
 from __future__ import annotations
 
-import ctypes as C
 import re
 import struct
 import zlib
@@ -17,7 +16,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import HpeError
-from .jpeg import DEFAULT_THREADS, DecodedBatch
+from .batch_io import (DEFAULT_THREADS, DecodedBatch, check_out, frame_offsets, frames_out, pinned, ptr as _p, stream_list, stream_ptr,
+                       thread_count, up16, upload)
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 JPEG_SOI = b"\xff\xd8"
@@ -27,12 +27,7 @@ PALETTE_BYTES = 256 * 4  # on the device: 256 entries (R, G, B, 0), entries beyo
 STORE_BYTES_PER_GROUP = 1024
 
 # HpePngImage (include/hpe.h) as a numpy record
-TABLE_DTYPE = np.dtype([("raw_offset", "<i8"), ("pal_offset", "<i8"), ("work_offset", "<i8"), ("out_offset", "<i8"), ("H", "<i4"), ("W", "<i4"),
-                        ("color_type", "<i4"), ("depth", "<i4"), ("channels", "<i4"), ("rowbytes", "<i4"), ("bpp", "<i4"), ("store_group0", "<i4")])
-assert TABLE_DTYPE.itemsize == C.sizeof(_lib.HpePngImage) == 64
-
-_p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-_up16 = lambda n: (int(n) + 15) // 16 * 16  # noqa: E731
+TABLE_DTYPE = _lib.record_dtype(_lib.HpePngImage)
 
 
 class _Refused(Exception):
@@ -41,26 +36,6 @@ class _Refused(Exception):
 
 def _named(idx, e):
     return HpeError("image %d: %s" % (idx, e))
-
-
-def _bytes_list(streams):
-    if isinstance(streams, (bytes, bytearray, memoryview)) or not hasattr(streams, "__len__"):
-        raise ValueError("streams must be a list of bytes objects")
-    if len(streams) < 1:
-        raise ValueError("streams is empty")
-    out = []
-    for s in streams:
-        if not isinstance(s, (bytes, bytearray, memoryview, np.ndarray)):
-            raise ValueError("every stream must be bytes-like")
-        out.append(s.tobytes() if isinstance(s, np.ndarray) else bytes(s))
-    return out
-
-
-def _threads(threads):
-    t = int(threads)
-    if t != threads or not 1 <= t <= 16:
-        raise ValueError("threads must be an integer in [1, 16]")
-    return t
 
 
 def is_direct(color_type, depth, channels):
@@ -153,7 +128,7 @@ def png_info(data, verify=True):
     The whole chunk walk runs (every length bounds-checked, every CRC-32 verified unless verify=False); nothing is inflated.  A stream
     outside the accepted subset raises HpeError with the clause.  Pure host."""
     try:
-        h = _parse(_bytes_list([data])[0], verify)
+        h = _parse(stream_list([data])[0][0], verify)
     except _Refused as e:
         raise _named(0, e) from None
     return {"height": h["H"], "width": h["W"], "color_type": h["color_type"], "depth": h["depth"], "samples": h["samples"],
@@ -178,21 +153,12 @@ def _run(pool, fn, items, indices):
 
 def parse_batch(streams, threads=DEFAULT_THREADS, verify=True, indices=None, pool=None):
     """The chunk walk of every stream -> a list of header dicts (``_parse``).  indices: the image numbers a refusal names (default 0..B-1)."""
-    data = _bytes_list(streams)
+    data, _ = stream_list(streams)
     indices = range(len(data)) if indices is None else indices
-    if pool is not None or _threads(threads) == 1:
+    if pool is not None or thread_count(threads) == 1:
         return _run(pool, lambda d: _parse(d, verify), data, indices)
     with ThreadPoolExecutor(max_workers=threads) as own:
         return _run(own, lambda d: _parse(d, verify), data, indices)
-
-
-def frame_offsets(sizes, channels):
-    """sizes [B,2] (H, W) -> (byte offsets [B] of frames packed in order, each on a 16-byte boundary; total bytes): DecodedBatch's packing"""
-    offs, pos = [], 0
-    for h, w in np.asarray(sizes).reshape(-1, 2).tolist():
-        offs.append(pos)
-        pos += _up16(h * w * channels)
-    return np.array(offs, np.int64), pos
 
 
 def _inflate(job):
@@ -232,8 +198,8 @@ def inflate_batch(streams, channels=3, threads=DEFAULT_THREADS, alloc=None, veri
     anything is inflated when its chunks are the reason.  The bytes do not depend on ``threads``.  Pure host code: no device is needed."""
     if channels not in (1, 3):
         raise ValueError("channels must be 1 or 3")
-    threads = _threads(threads)
-    data = _bytes_list(streams)
+    threads = thread_count(threads)
+    data, _ = stream_list(streams)
     B = len(data)
     indices = list(range(B)) if indices is None else list(indices)
     pool = ThreadPoolExecutor(max_workers=threads) if threads > 1 else None
@@ -251,12 +217,12 @@ def inflate_batch(streams, channels=3, threads=DEFAULT_THREADS, alloc=None, veri
             for k in ("H", "W", "color_type", "depth", "rowbytes", "bpp"):
                 e[k] = h[k]
             e["channels"], e["out_offset"], e["raw_offset"], e["store_group0"] = channels, packed[b], raw_pos, groups
-            raw_pos += _up16(h["H"] * (h["rowbytes"] + 1))
+            raw_pos += up16(h["H"] * (h["rowbytes"] + 1))
             if is_direct(h["color_type"], h["depth"], channels):
                 e["work_offset"] = -1
             else:
                 e["work_offset"] = work_pos
-                work_pos += _up16(h["H"] * h["rowbytes"])
+                work_pos += up16(h["H"] * h["rowbytes"])
                 groups += (h["H"] * h["W"] * channels + STORE_BYTES_PER_GROUP - 1) // STORE_BYTES_PER_GROUP
         for b, h in enumerate(hs):
             table[b]["pal_offset"] = -1
@@ -270,7 +236,7 @@ def inflate_batch(streams, channels=3, threads=DEFAULT_THREADS, alloc=None, veri
         jobs = []
         for b, h in enumerate(hs):
             o, n = int(table[b]["raw_offset"]), h["H"] * (h["rowbytes"] + 1)
-            staged[o + n:o + _up16(n)] = 0  # the bytes between the regions are defined too
+            staged[o + n:o + up16(n)] = 0  # the bytes between the regions are defined too
             jobs.append((h, staged[o:o + n]))
             if h["color_type"] == 3:
                 pal = staged[int(table[b]["pal_offset"]):int(table[b]["pal_offset"]) + PALETTE_BYTES].reshape(256, 4)
@@ -284,36 +250,24 @@ def inflate_batch(streams, channels=3, threads=DEFAULT_THREADS, alloc=None, veri
     return staged, staged[raw_pos:].view(TABLE_DTYPE), np.array([raw_pos, max(work_pos, 16), frames_total, groups], np.int64)
 
 
-def _check_out(out):
-    import torch
-
-    if out is not None and (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 1 or
-                            not out.is_contiguous() or out.data_ptr() % 16):
-        raise ValueError("out must be a contiguous 1-D uint8 CUDA tensor on a 16-byte boundary")
-    return out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
-
-
 def _pinned_alloc(keep):
-    import torch
-
     def alloc(nbytes):
-        keep.append(torch.empty(nbytes, dtype=torch.uint8, pin_memory=True))
-        return keep[-1].numpy()
+        buf, host = pinned(nbytes)
+        keep.append(buf)
+        return host
 
     return alloc
 
 
-def _launch_png(pinned, table, totals, out, dev):
+def _launch_png(pinned_buf, table, totals, out, dev):
     """one non-blocking copy of the staged buffer and the two launches on the current stream"""
     import torch
 
     raw_bytes = int(totals[0])
-    staged = torch.empty(pinned.numel(), dtype=torch.uint8, device=dev)
-    staged.copy_(pinned, non_blocking=True)
+    staged = upload(pinned_buf, dev)
     workspace = torch.empty(int(totals[1]), dtype=torch.uint8, device=dev)
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(_lib.load().hpe_png_backend(_p(table), staged.data_ptr() + raw_bytes, table.shape[0], staged.data_ptr(), raw_bytes,
-                                           workspace.data_ptr(), workspace.numel(), out.data_ptr(), out.numel(), st))
+                                           workspace.data_ptr(), workspace.numel(), out.data_ptr(), out.numel(), stream_ptr(dev)))
 
 
 def decode_png_batch(streams, channels=3, threads=DEFAULT_THREADS, out=None):
@@ -327,15 +281,11 @@ def decode_png_batch(streams, channels=3, threads=DEFAULT_THREADS, out=None):
 
     if channels not in (1, 3):
         raise ValueError("channels must be 1 or 3")
-    dev = _check_out(out)
+    dev = check_out(out)
     keep = []
     with torch.cuda.device(dev):
         _, table, totals = inflate_batch(streams, channels, threads, _pinned_alloc(keep))
-        need = int(totals[2])
-        if out is None:
-            out = torch.empty(need, dtype=torch.uint8, device=dev)
-        elif out.numel() < need:
-            raise ValueError("out holds %d bytes, the packed frames need %d" % (out.numel(), need))
+        out = frames_out(out, int(totals[2]), dev)
         _launch_png(keep[0], table, totals, out, dev)
     sizes = np.stack([table["H"], table["W"]], axis=1).astype(np.int64)
     return DecodedBatch(out, sizes, table["out_offset"].astype(np.int64), channels)
@@ -359,9 +309,9 @@ def decode_image_batch(streams, channels, threads=DEFAULT_THREADS, out=None):
 
     if channels not in (1, 3):
         raise ValueError("channels must be 1 or 3")
-    data = _bytes_list(streams)
-    threads = _threads(threads)
-    dev = _check_out(out)
+    data, _ = stream_list(streams)
+    threads = thread_count(threads)
+    dev = check_out(out)
     kinds = [sniff(s) for s in data]
     for i, k in enumerate(kinds):
         if k is None:
@@ -372,17 +322,11 @@ def decode_image_batch(streams, channels, threads=DEFAULT_THREADS, out=None):
     sizes = np.zeros((B, 2), np.int64)
     pinned_j, pinned_p = [], []
 
-    def jalloc(n, nb):
-        buf = torch.empty(2 * n + nb * jpeg.TABLE_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
-        pinned_j.append(buf)
-        host = buf.numpy()
-        return host[:2 * n].view(np.int16), host[2 * n:].view(jpeg.TABLE_DTYPE)
-
     with torch.cuda.device(dev):
         headers = parse_batch([data[i] for i in pi], threads, True, pi) if pi else []
         if ji:
             try:
-                coef, jtable, jtotals = jpeg.entropy_decode([data[i] for i in ji], channels, threads, jalloc)
+                _, jtable, jtotals = jpeg.entropy_decode([data[i] for i in ji], channels, threads, jpeg._pinned_alloc(pinned_j))
             except HpeError as e:  # the subset's numbering -> the batch's
                 raise HpeError(re.sub(r"image (\d+)", lambda m: "image %d" % ji[int(m.group(1))], str(e), count=1)) from None
             sizes[ji] = np.stack([jtable["H"], jtable["W"]], axis=1)
@@ -392,19 +336,10 @@ def decode_image_batch(streams, channels, threads=DEFAULT_THREADS, out=None):
         if pi:
             _, ptable, ptotals = inflate_batch([data[i] for i in pi], channels, threads, _pinned_alloc(pinned_p), out_offsets=offsets[pi],
                                                indices=pi, headers=headers)
-        if out is None:
-            out = torch.empty(need, dtype=torch.uint8, device=dev)
-        elif out.numel() < need:
-            raise ValueError("out holds %d bytes, the packed frames need %d" % (out.numel(), need))
+        out = frames_out(out, need, dev)
         if ji:
             jtable["out_offset"] = offsets[ji]  # hpe_jpeg_backend takes any 16-byte aligned offset inside the buffer
-            n = coef.shape[0]
-            staged = torch.empty(pinned_j[0].numel(), dtype=torch.uint8, device=dev)
-            staged.copy_(pinned_j[0], non_blocking=True)
-            workspace = torch.empty(int(jtotals[1]), dtype=torch.uint8, device=dev)
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(_lib.load().hpe_jpeg_backend(_p(jtable), staged.data_ptr() + 2 * n, len(ji), staged.data_ptr(), n, workspace.data_ptr(),
-                                                    workspace.numel(), out.data_ptr(), out.numel(), st))
+            jpeg._launch_jpeg(pinned_j[0], jtable, jtotals, out, dev)
         if pi:
             _launch_png(pinned_p[0], ptable, ptotals, out, dev)
     return DecodedBatch(out, sizes, offsets, channels)

@@ -259,7 +259,7 @@ def load_training_batch(records, draws=None, generator=None, threads=None, **aug
     ``decode_image_batch`` each (every stream a JPEG or a PNG, side by side in one batch), then ``augment_batch`` on the decoded buffers as they are.  draws / generator / further keyword
     arguments are ``augment_batch``'s.  A record whose streams do not have its height and width raises RecordError."""
     from .augment import augment_batch
-    from .jpeg import DEFAULT_THREADS
+    from .batch_io import DEFAULT_THREADS
     from .png import decode_image_batch
 
     recs = [parse_image_example(r) if isinstance(r, (bytes, bytearray, memoryview)) else r for r in records]

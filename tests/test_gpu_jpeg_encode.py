@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import hpe_amd
-from hpe_amd import _lib, jpeg, jpeg_encode
+from hpe_amd import _lib, batch_io, jpeg, jpeg_encode
 
 import jpeg_encode_ref as R
 
@@ -81,7 +81,7 @@ def test_gaps_between_images_keep_their_bytes_and_two_calls_agree(want):
     """a hand-laid table with 192 unused elements between the images' planes: they keep 0x5A5A; a second call gives the same bits"""
     part = ["rgb_17x33", "rgb_8x24", "rgb_3x5"]
     frames = [dev(R.pixels(n)) for n in part]
-    buf, shapes, offsets = jpeg_encode._layout(frames)
+    buf, shapes, offsets = batch_io.pack_frames(frames, jpeg_encode.CHANNELS)
     table, totals = jpeg_encode.encode_layout(shapes, offsets, 95, "4:2:0")
     gap = 192
     for b in range(len(part)):
@@ -106,7 +106,7 @@ def test_gaps_between_images_keep_their_bytes_and_two_calls_agree(want):
 
 def test_launch_replays_from_a_graph(want):
     part = [n for n in NAMES if R.CASES[n][3:] == (95, "4:2:0")]
-    buf, shapes, offsets = jpeg_encode._layout([dev(R.pixels(n)) for n in part])
+    buf, shapes, offsets = batch_io.pack_frames([dev(R.pixels(n)) for n in part], jpeg_encode.CHANNELS)
     table, totals = jpeg_encode.encode_layout(shapes, offsets, 95, "4:2:0")
     table_dev = dev(table.view(np.uint8))
     coef = torch.zeros(int(totals[0]), dtype=torch.int16, device="cuda")

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import hpe_amd
-from hpe_amd import _lib, png, png_encode
+from hpe_amd import _lib, batch_io, jpeg_encode, png, png_encode
 
 import png_encode_ref as E
 import png_ref as R
@@ -148,7 +148,7 @@ def test_filter_refusals_leave_the_output_untouched():
 def test_filter_launch_replays_from_a_graph(want):
     """hpe_png_filter captured on one stream and replayed twice: the restatement's scanlines again, after the output was wiped"""
     frames = [f for _, f in CASES]
-    buf, shapes, offsets = png_encode._layout([dev(f) for f in frames])
+    buf, shapes, offsets = batch_io.pack_frames([dev(f) for f in frames], png_encode.COLOR_TYPE)
     table, scan_bytes = png_encode.filter_table(shapes, offsets)
     table_dev = dev(table.view(np.uint8))
     scan = torch.zeros(scan_bytes, dtype=torch.uint8, device="cuda")
@@ -167,3 +167,38 @@ def test_filter_launch_replays_from_a_graph(want):
         for e, (n, _) in zip(table, CASES):
             w = want[n]
             assert np.array_equal(host[int(e["scan_offset"]):int(e["scan_offset"]) + w.size].reshape(w.shape), w), n
+
+
+def test_pack_frames_in_its_three_input_forms():
+    """batch_io.pack_frames on 1 x 1 x 3 (3 bytes), 4 x 4 x 1 (16 bytes exactly: no padding piece) and 3 x 5 x 3 (45 bytes) as a list, as
+    [B,H,W,C] tensors and as decode_png_batch's DecodedBatch: the offsets, the buffer's bytes at them, and both encoders' channel clause"""
+    frames = [E.content(h, w, c, seed=h + w) for h, w, c in ((1, 1, 3), (4, 4, 1), (3, 5, 3))]
+    buf, shapes, offsets = batch_io.pack_frames([dev(f) for f in frames], png_encode.COLOR_TYPE)
+    assert shapes == [(1, 1, 3), (4, 4, 1), (3, 5, 3)] and offsets == [0, 16, 32] and buf.numel() == 80
+    host = buf.cpu().numpy()
+    for f, o in zip(frames, offsets):
+        assert np.array_equal(host[o:o + f.size], f.reshape(-1))
+    assert not host[3:16].any() and not host[77:].any()  # the padding is zeros
+    assert batch_io.pack_frames([dev(frames[1][:, :, 0])], [1])[1:] == ([(4, 4, 1)], [0])  # [H,W] is one channel
+
+    for f in frames:  # a tensor is used as it lies: back to back, whatever the frame's size
+        x = np.stack([f, f[::-1].copy()])
+        buf, shapes, offsets = batch_io.pack_frames(dev(x), png_encode.COLOR_TYPE)
+        assert shapes == [f.shape] * 2 and offsets == [0, f.size] and np.array_equal(buf.cpu().numpy(), x.reshape(-1))
+
+    batch = hpe_amd.decode_png_batch([E.encode(f) for f in frames], channels=3)  # the grey frame comes back on three channels
+    buf, shapes, offsets = batch_io.pack_frames(batch, png_encode.COLOR_TYPE)
+    assert buf is batch.buffer and shapes == [(1, 1, 3), (4, 4, 3), (3, 5, 3)] and offsets == [0, 16, 64] and batch.nbytes == 112
+    host = buf.cpu().numpy()
+    for f, o in zip(frames, offsets):
+        f3 = np.broadcast_to(f, f.shape[:2] + (3,))
+        assert np.array_equal(host[o:o + f3.size], f3.reshape(-1))
+
+    ok = dev(frames[0])
+    for bad, channels, clause in ((4, jpeg_encode.CHANNELS, "1 or 3"), (2, jpeg_encode.CHANNELS, "1 or 3"), (2, png_encode.COLOR_TYPE, "1, 3 or 4")):
+        with pytest.raises(hpe_amd.HpeError) as e:
+            batch_io.pack_frames([ok, dev(np.zeros((2, 2, bad), np.uint8))], channels)
+        assert str(e.value) == "image 1: %d channels: the channel count must be %s" % (bad, clause)
+    assert batch_io.pack_frames([dev(np.zeros((2, 2, 4), np.uint8))], png_encode.COLOR_TYPE)[1] == [(2, 2, 4)]
+    with pytest.raises(hpe_amd.HpeError, match=r"^image 0: 4 channels: the channel count must be 1 or 3$"):
+        hpe_amd.encode_jpeg_batch(dev(np.zeros((1, 8, 8, 4), np.uint8)))

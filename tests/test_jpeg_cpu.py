@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import jpeg_ref as R
-from hpe_amd import HpeError, _lib, build as hbuild, jpeg
+from hpe_amd import HpeError, _lib, batch_io, build as hbuild, jpeg
 
 
 @pytest.fixture(scope="module")
@@ -168,7 +168,8 @@ def test_single_byte_damage_returns_a_status_and_stays_inside_the_buffer(lib):
 
 def test_capacity_is_checked_before_anything_is_written(lib):
     s = R.stream("s420_37x43")
-    keep, ptrs, lengths = jpeg._stream_args([s])
+    data, lengths = batch_io.stream_list([s])
+    ptrs = (C.c_char_p * 1)(*data)
     ch = np.array([3], np.int32)
     status, totals, table = np.zeros(1, np.int32), np.zeros(5, np.int64), np.zeros(1, jpeg.TABLE_DTYPE)
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731

@@ -27,7 +27,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import hpe_amd  # noqa: E402
-from hpe_amd import _lib, jpeg_encode  # noqa: E402
+from hpe_amd import _lib, batch_io, jpeg_encode  # noqa: E402
 
 B, H, W = 64, 200, 300
 
@@ -77,7 +77,7 @@ def main():
     lib = _lib.load()
     res = {"batch": B, "height": H, "width": W, "subsampling": "4:2:0", "quality": 95, "pixel_bytes": int(host.nbytes)}
 
-    buf, shapes, offsets = jpeg_encode._layout(frames)
+    buf, shapes, offsets = batch_io.pack_frames(frames, jpeg_encode.CHANNELS)
     table, totals = jpeg_encode.encode_layout(shapes, offsets, 95, "4:2:0")
     table_dev = torch.from_numpy(table.view(np.uint8).copy()).cuda()
     coef = torch.empty(int(totals[0]), dtype=torch.int16, device="cuda")

@@ -28,7 +28,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import hpe_amd  # noqa: E402
-from hpe_amd import _lib, png_encode, synthetic  # noqa: E402
+from hpe_amd import _lib, batch_io, png_encode, synthetic  # noqa: E402
 from hpe_amd.draw import draw_panels, draw_results  # noqa: E402
 
 B, STAGES, S = 6, 3, 224
@@ -101,7 +101,7 @@ def main():
     panels = draw_results(renderer, images, segs, kp, verts, kps, cams)
 
     # the encoder on those panels: filter, copy, deflate
-    buf, shapes, offsets = png_encode._layout(panels)
+    buf, shapes, offsets = batch_io.pack_frames(panels, png_encode.COLOR_TYPE)
     table, scan_bytes = png_encode.filter_table(shapes, offsets)
     table_dev = torch.from_numpy(table.view(np.uint8).copy()).cuda()
     scan = torch.empty(scan_bytes, dtype=torch.uint8, device="cuda")
