@@ -353,8 +353,9 @@ __global__ __launch_bounds__(P8_THREADS, 1) void conv_gemm_bf16_p8_fixup_kernel(
     p8_epilogue(p, lds, acc, mtile * P8_BM, ntile * P8_BN, t, lane, wave >> 2, wave & 3);
 }
 
+// split_k_out (optional): the number of K slices chosen, written before anything is launched
 template <int MODE>
-hipError_t launch_p8(GemmArgs& p, hipStream_t st) {
+hipError_t launch_p8(GemmArgs& p, hipStream_t st, int* split_k_out) {
     p.n_mtiles = (p.M + P8_BM - 1) / P8_BM;
     p.n_ntiles = (p.N + P8_BN - 1) / P8_BN;
     const int tiles = p.n_mtiles * p.n_ntiles;
@@ -371,6 +372,7 @@ hipError_t launch_p8(GemmArgs& p, hipStream_t st) {
         if (sk < 1) sk = 1;
     }
     p.split_k = sk;
+    if (split_k_out) *split_k_out = sk;
     hipLaunchKernelGGL((conv_gemm_bf16_p8_kernel<MODE>), dim3(tiles * sk), dim3(P8_THREADS), 0, st, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || sk == 1) return e;
@@ -380,13 +382,13 @@ hipError_t launch_p8(GemmArgs& p, hipStream_t st) {
 
 }  // namespace
 
-hipError_t hpe_launch_gemm_bf16_p8(GemmArgs p, int mode, hipStream_t st) {
+hipError_t hpe_launch_gemm_bf16_p8(GemmArgs p, int mode, hipStream_t st, int* split_k_out) {
     if (gemm_contract(p, mode, TILE_P8_256x256, GEMM_K_BF16_P8)) return hipErrorInvalidValue;
     switch (mode) {
-        case GEMM_DENSE: return launch_p8<GEMM_DENSE>(p, st);
-        case GEMM_STRIDED: return launch_p8<GEMM_STRIDED>(p, st);
-        case GEMM_CONV3: return launch_p8<GEMM_CONV3>(p, st);
-        case GEMM_DUAL: return launch_p8<GEMM_DUAL>(p, st);
+        case GEMM_DENSE: return launch_p8<GEMM_DENSE>(p, st, split_k_out);
+        case GEMM_STRIDED: return launch_p8<GEMM_STRIDED>(p, st, split_k_out);
+        case GEMM_CONV3: return launch_p8<GEMM_CONV3>(p, st, split_k_out);
+        case GEMM_DUAL: return launch_p8<GEMM_DUAL>(p, st, split_k_out);
         default: return hipErrorInvalidValue;
     }
 }

@@ -768,6 +768,48 @@ int hpe_debug_gemm_check(const HpeDebugGemm* g, int kernel, int w_piece) {
     return HPE_OK;
 }
 
+// The launching twin of hpe_debug_gemm_check.  Kernel 0 is hpe_debug_gemm_ex.  Kernels 1..3: the contract is checked FIRST, with what the
+// context owns (scale / shift when NULL, the zero page) counted as present, so a broken clause is named with no context at all; then
+// the context is required, its buffers are filled in and the launcher (which runs the contract again on the real pointers) is called.
+// The zero page: conv_gemm_bf16.hip (3x3 taps outside the image) and conv_gemm_bf16_p8.hip (those, and k-tiles past the end of K)
+// fetch 16 bytes from p.zero -- every lane of a global_load_lds the same 16 -- and f32s never reads it; c->zeros is 1024 floats = 4096
+// zero bytes from hipMalloc (256-byte aligned), which covers both.  The split-K workspace is c->partial (partial_floats floats; the
+// 256x256 launcher shrinks its split until tiles * split_k * 256 * 256 floats fit).
+int hpe_debug_gemm_launch(hpe_ctx* c, const HpeDebugGemm* g, int kernel, int w_piece, void* stream) {
+    if (kernel == GEMM_K_F32) return hpe_debug_gemm_ex(c, g, stream);
+    if (g && g->split_k) *g->split_k = 0;
+    const std::string why = debug_gemm_refusal(g);
+    if (!why.empty()) return fail(HPE_ERR_INVALID, why);
+    if (kernel < GEMM_K_F32 || kernel > GEMM_K_BF16_P8) return fail(HPE_ERR_INVALID, "hpe_debug_gemm_launch: kernel must be 0 (fp32), 1 (f32s), 2 (bf16) or 3 (bf16_p8)");
+    if ((!g->scale || !g->shift) && g->N > 1024) return fail(HPE_ERR_INVALID, "hpe_debug_gemm_launch: N <= 1024 without scale / shift");
+    const GemmKernel k = static_cast<GemmKernel>(kernel);
+    GemmArgs p = debug_gemm_args(g, gemm_rules(k).slab);
+    if (k == GEMM_K_F32S) p.w_piece = w_piece;
+    alignas(16) static const float present[4] = {};
+    p.scale = g->scale ? g->scale : present;
+    p.shift = g->shift ? g->shift : present;
+    p.zero = present;
+    if (const char* clause = gemm_contract(p, g->mode, g->tile, k)) return fail(HPE_ERR_INVALID, "hpe_debug_gemm_launch: " + debug_gemm_rejected(g, clause));
+    if (!c || !c->finalized) return fail(HPE_ERR_STATE, "needs a finalized ctx");
+    DeviceGuard guard(c->cfg.device);
+    p.scale = g->scale ? g->scale : c->ones;
+    p.shift = g->shift ? g->shift : c->zeros;
+    p.zero = c->zeros;
+    if (g->use_splitk) {
+        p.partial = c->partial;
+        p.partial_floats = c->partial_floats;
+    }
+    if (const char* clause = gemm_contract(p, g->mode, g->tile, k)) return fail(HPE_ERR_INVALID, "hpe_debug_gemm_launch: " + debug_gemm_rejected(g, clause));
+    int split_k = 1;  // f32s and the bf16 tiles 0..6 never split
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const hipError_t e = k == GEMM_K_F32S ? hpe_launch_gemm_f32s(p, g->mode, g->tile, st)
+                       : k == GEMM_K_BF16 ? hpe_launch_gemm_bf16(p, g->mode, g->tile, st)
+                                          : hpe_launch_gemm_bf16_p8(p, g->mode, st, &split_k);
+    if (g->split_k) *g->split_k = split_k;
+    HIP_TRY(e);
+    return HPE_OK;
+}
+
 int hpe_debug_conv_route(const HpeConfig* cfg, int idx, int B, int concurrent, int residual, int workspace, HpeConvRoute* out) {
     static_assert(HPE_CONV_K_F32 == CONV_K_F32 && HPE_CONV_K_HALO3 == CONV_K_HALO3 && HPE_CONV_K_WINO4_FUSED == CONV_K_WINO4_FUSED && HPE_CONV_K_COUNT == CONV_K_WINO4_FUSED + 1,
                   "include/hpe.h numbers the kernels as ConvKernel does");

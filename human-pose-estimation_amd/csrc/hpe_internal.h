@@ -106,7 +106,7 @@ int hpe_wino4_fused_items(int B, int H, int W, int N);  // workgroups of that la
 // conv_gemm_bf16.hip (x / w / res / y of GemmArgs point to bf16 data; offsets are in bf16 elements; K % 64 == 0)
 hipError_t hpe_launch_gemm_bf16(GemmArgs p, int mode, int tile, hipStream_t st);
 // conv_gemm_bf16_p8.hip: 256 x 256 x 64 tile, 8 waves, phase-interleaved main loop, split-K through p.partial (DENSE / STRIDED / CONV3 / DUAL)
-hipError_t hpe_launch_gemm_bf16_p8(GemmArgs p, int mode, hipStream_t st);
+hipError_t hpe_launch_gemm_bf16_p8(GemmArgs p, int mode, hipStream_t st, int* split_k_out = nullptr);
 // conv_chain_bf16.hip: t3 = relu(bn(W2c . t2) + res) and u1 = relu(bn'(W2a' . t3)) in one launch (the last 1x1 of identity block i and the
 // first 1x1 of identity block i + 1); all tensors bf16, row-major [M, channels], weights packed [n][k]
 struct ChainArgs {

@@ -903,10 +903,7 @@ class HpeEngine(object):
         """hpe_debug_conv_route with this engine's own config: which kernel layer idx takes at batch B (_lib.HpeConvRoute)"""
         return _lib.conv_route(self.lib, self._cfg, idx, B, concurrent, residual, workspace)
 
-    def debug_gemm_ex(self, mode, tile, x, wt, y, M, N, K, **kw):
-        """hpe_debug_gemm_ex: the fp32 implicit-GEMM kernel with every launch argument given (HpeDebugGemm of include/hpe.h).  x, wt, y
-        and the optional x2 / residual / scale / shift are CUDA tensors or device addresses, y is written in place; the other
-        HpeDebugGemm fields are keywords (default 0, pitches default to the dense ones).  Returns the split_k the launcher chose."""
+    def _debug_gemm(self, call, what, mode, tile, x, wt, y, M, N, K, kw):
         g = _lib.HpeDebugGemm()
         g.struct_size = C.sizeof(_lib.HpeDebugGemm)
         fields = dict(lda=K, ldw=K, ldy=N, ldres=N, mode=mode, tile=tile, x=x, wt=wt, y=y, M=M, N=N, K=K)
@@ -915,12 +912,25 @@ class HpeEngine(object):
             if k in ("x", "x2", "wt", "residual", "scale", "shift", "y"):
                 v = v.data_ptr() if hasattr(v, "data_ptr") else v
             elif k in ("struct_size", "split_k") or not hasattr(g, k):
-                raise TypeError("debug_gemm_ex: unknown argument %r" % k)
+                raise TypeError("%s: unknown argument %r" % (what, k))
             setattr(g, k, v)
         sk = C.c_int(-1)
         g.split_k = C.pointer(sk)
-        _lib.check(self.lib.hpe_debug_gemm_ex(self._h, C.byref(g), self._stream()))
+        _lib.check(call(g))
         return sk.value
+
+    def debug_gemm_ex(self, mode, tile, x, wt, y, M, N, K, **kw):
+        """hpe_debug_gemm_ex: the fp32 implicit-GEMM kernel with every launch argument given (HpeDebugGemm of include/hpe.h).  x, wt, y
+        and the optional x2 / residual / scale / shift are CUDA tensors or device addresses, y is written in place; the other
+        HpeDebugGemm fields are keywords (default 0, pitches default to the dense ones).  Returns the split_k the launcher chose."""
+        return self._debug_gemm(lambda g: self.lib.hpe_debug_gemm_ex(self._h, C.byref(g), self._stream()), "debug_gemm_ex", mode, tile, x, wt, y, M, N, K, kw)
+
+    def debug_gemm_launch(self, kernel, mode, tile, x, wt, y, M, N, K, w_piece=0, **kw):
+        """hpe_debug_gemm_launch: debug_gemm_ex for any of the four implicit-GEMM kernels -- 0 fp32, 1 f32s (wt: three bf16 pieces per
+        row, w_piece elements apart), 2 bf16, 3 bf16 256x256 (x, x2, wt, residual, y in bf16; pitches in bf16 elements).  Returns the
+        split_k the launcher chose."""
+        return self._debug_gemm(lambda g: self.lib.hpe_debug_gemm_launch(self._h, C.byref(g), int(kernel), int(w_piece), self._stream()),
+                                "debug_gemm_launch", mode, tile, x, wt, y, M, N, K, kw)
 
     def debug_chain(self, idx2c, t2, residual):
         """bf16 contexts: res*_branch2c (+ residual + ReLU) and the next block's res*_branch2a (+ ReLU) as the one launch of

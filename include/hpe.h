@@ -841,6 +841,15 @@ int hpe_debug_gemm_ex(hpe_ctx* ctx, const HpeDebugGemm* g, void* stream);
  * never dereferenced; scale, shift and the library's zero page count as present; use_splitk is ignored.  HPE_OK if the launch is
  * inside the contract, else HPE_ERR_INVALID with the name of the first broken clause in hpe_last_error(). */
 int hpe_debug_gemm_check(const HpeDebugGemm* g, int kernel, int w_piece);
+/* The launching twin of hpe_debug_gemm_check: the launch g on kernel 0..3 as numbered there (w_piece read for kernel 1 only).
+ * Kernel 0 is hpe_debug_gemm_ex.  Kernel 1 (f32s): x, x2, residual, y in fp32 as for kernel 0, wt points at bf16 data -- the three
+ * pieces of Wt[n][k] at wt + n * ldw + j * w_piece + k, j = 0..2, ldw and w_piece in bf16 elements.  Kernels 2 and 3: x, x2, wt,
+ * residual and y all point at bf16 data, every pitch and offset is in bf16 elements, k-slabs are 64 wide (HPE_GEMM_DUAL: Cin = K -
+ * 64 * k1_slabs), y_slab8 is ignored; scale and shift stay fp32.  scale / shift NULL (N <= 1024), the zero page and, with
+ * use_splitk, the split-K workspace come from the context.  The contract is checked before the context is looked at: a broken clause
+ * returns HPE_ERR_INVALID with its name in hpe_last_error() whatever ctx is, launches nothing and sets *split_k to 0.  *split_k
+ * receives what the launcher chose: kernel 3 may cut K when handed the workspace, kernels 1 and 2 always report 1. */
+int hpe_debug_gemm_launch(hpe_ctx* ctx, const HpeDebugGemm* g, int kernel, int w_piece, void* stream);
 /* Which kernel conv layer idx takes, asked of the plan alone: cfg is resolved as hpe_create / hpe_finalize resolve it (fields >= 0, else the
  * environment, else the defaults of cfg->encoder_dtype), then the library's one routing function is asked.  No context, no GPU, no HIP
  * call.  B images; concurrent: the launch is a batch chunk running beside others (no split-K, the concurrent tile rules); residual: the
