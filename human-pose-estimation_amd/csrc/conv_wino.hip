@@ -4,7 +4,8 @@
 //     Y = A^T [ (G g G^T) (.) (B^T d B) ] A        per 2x2 output tile, summed over input channels
 //
 // 16 multiplies per tile and channel pair instead of 36: the MFMA work of these 16 layers (48 % of the encoder's
-// FLOPs) shrinks 2.25x (1.72x on the 7x7 maps, whose 4x4 tile grid covers 8x8).  Arithmetic stays fp32 end to end.
+// FLOPs) shrinks 2.25x (1.72x on the 7x7 maps, whose 4x4 tile grid covers 8x8).  Arithmetic stays fp32 end to end (the fused
+// kernel of the large maps multiplies on the bf16 matrix cores through the exact three-piece split, fp32 accumulators).
 //
 // Two variants:
 //  (a) 14x14 and 7x7 maps -- two kernels per layer:
@@ -17,7 +18,7 @@
 //                       the barrier in the middle of a slab's MFMA work), then the output
 //                       transform A^T M A through LDS, BN scale/shift, ReLU and 16 B/lane NHWC stores.
 //                       U = G g G^T is precomputed on the host in the same blocked layout.
-//  (b) 56x56 and 28x28 maps -- wino_fused_kernel: the same GEMM with the input transform done inside, from activations the
+//  (b) 56x56 and 28x28 maps -- wino_fused_split_kernel: the same GEMMs with the input transform done inside, from activations the
 //      producing 1x1 convolution wrote channel-slab major (see the comment at the kernel); no V in memory.
 //
 // Why (a) does not read NHWC activations directly: a slab can only hold 8 channels of 64 tiles x 16 components (LDS), i.e.
@@ -402,13 +403,13 @@ __global__ __launch_bounds__(512, 2) void wino_gemm_streamk_kernel(WinoArgs p) {
 //   * the 4 input rows of each of its tile rows arrive by LDS-DMA as 16-B chunks in the layout
 //     raw[tile row][input row 4][half 2][pixel parity 2][pixel / 2][4 ch]  (zero page for the halo) -- ~15 KB;
 //   * thread (tile = lane, wave = (half, xi)) reads 2 rows x 4 pixels from it (lanes hit consecutive 16-B slots:
-//     conflict-free), forms row xi of B^T d B for its 4 channels and writes the 4 components into the V slab image the
-//     MFMA loop reads -- exactly the bytes wino_input_kernel would have written to HBM;
-//   * the MFMA work on slab s overlaps the transform of slab s + 1 and the DMAs of U(s + 1) and raw(s + 2).
-// LDS: V 2 x 32 KB + U 2 x 32 KB + raw 2 x 15 KB = 158 KB of the 160 KB.
+//     conflict-free), forms row xi of B^T d B for its 4 channels in fp32 and writes the 4 components into the V slab the
+//     MFMA loop reads;
+//   * the MFMA work on slab s overlaps the transform of slab s + 1, the loads of U(s + 1) and the DMA of raw(s + 3).
+// The 16 GEMMs run on the bf16 matrix cores (wino_fused_split_kernel below).
 struct WinoFusedArgs {
-    const float* Xs;     // [S][M][8], M = B * H * W
-    const float* U;
+    const float* Xs;           // [S][M][8], M = B * H * W
+    const unsigned short* Us;  // ConvLayer::wino_u_split
     const float* scale;
     const float* shift;
     const float* zero;   // >= 16 B of zeros
@@ -422,164 +423,12 @@ struct WinoFusedArgs {
     int ldy, relu;
 };
 
-constexpr int RAWF = 960 * 4;  // floats per raw buffer (960 chunks >= 2*4*4*29 = 928 and 4*4*4*15 = 960)
-constexpr int FUSED_LDS_FLOATS = 4 * OPER + 2 * RAWF;
 
-__global__ __launch_bounds__(512, 2) void wino_fused_kernel(WinoFusedArgs p) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* rawb = lds + 4 * OPER;
-
-    const int total = p.n_blk * p.n_nt;
-    const int bid = blockIdx.x;
-    const int lid = xcd_remap(bid, total);
-    const int blk = lid / p.n_nt;
-    const int nt = lid - blk * p.n_nt;
-
-    const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+// epilogue of the fused kernel (as wino_epilogue, with its tile -> pixel mapping).  Entered with all waves past the main loop's
+// last barrier (LDS free): M[comp][tile][cout] of one 32-tile half through LDS (128 KB), output transform, BN, ReLU, NHWC stores.
+__device__ __forceinline__ void wino_fused_epilogue(const WinoFusedArgs& p, float* lds, int blk, int nt, int n_tiles, f32x16 (&acc)[2][2][2], int t,
+                                                    int wave, int lane) {
     const int hi = lane >> 5;
-    const int TW1 = p.TW + 1;
-
-    // ---- raw DMA sources: chunk slot c = (i * 8 + wave) * 64 + lane, i = 0, 1 -> (tile row, input row, half, parity, idx)
-    long rsrc[2];  // float offset inside a slab of Xs, or -1 for the zero page
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int c = (i * 8 + wave) * 64 + lane;
-        long off = -1;
-        if (c < p.NC) {
-            const int idx = c % TW1;
-            int r = c / TW1;
-            const int par = r & 1;
-            r >>= 1;
-            const int h = r & 1;
-            r >>= 1;
-            const int a = r & 3;
-            const int trl = r >> 2;
-            const int g = blk * p.R + trl;
-            if (g < p.NG) {
-                const int b = g / p.TH;
-                const int ty = g - b * p.TH;
-                const int iy = 2 * ty - 1 + a;
-                const int px = 2 * idx + par - 1;
-                if (iy >= 0 && iy < p.H && px >= 0 && px < p.W) off = ((long)(b * p.H + iy) * p.W + px) * 8 + h * 4;
-            }
-        }
-        rsrc[i] = off;
-    }
-    const int n_raw_instr = (p.NC + 63) >> 6;  // wave-instructions per slab (<= 15)
-    const float* usrc = p.U + (size_t)nt * p.S * OPER + wave * 1024 + lane * 4;
-
-    auto issue_raw = [&](int s, int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            if (i * 8 + wave < n_raw_instr) {
-                const float* src = rsrc[i] >= 0 ? p.Xs + (size_t)s * p.M * 8 + rsrc[i] : p.zero;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(rawb + buf * RAWF + (i * 8 + wave) * 256), 16, 0, 0);
-            }
-        }
-    };
-    auto issue_u = [&](int s, int buf) {
-        float* dstu = lds + buf * (2 * OPER) + OPER + wave * 1024;
-        const float* su = usrc + (size_t)s * OPER;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(su + i * 256),
-                                             (__attribute__((address_space(3))) void*)(dstu + i * 256), 16, 0, 0);
-    };
-
-    // ---- transform role: tile = lane, wave = (half, xi)
-    const int th = wave & 1, xi = wave >> 1;
-    const int n_tiles = p.R * p.TW;
-    const bool t_live = lane < n_tiles;
-    const int t_trl = t_live ? lane / p.TW : 0;
-    const int t_tx = t_live ? lane - t_trl * p.TW : 0;
-    // row xi of B^T d uses input rows (ra, rb): xi 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3
-    const int ra = (xi == 0) ? 0 : (xi == 2 ? 2 : 1);
-    const int rb = (xi == 0) ? 2 : (xi == 1 ? 2 : (xi == 2 ? 1 : 3));
-    const float sgn = (xi == 1) ? 1.f : -1.f;
-    // raw chunk (floats) of input row a, pixel 2 tx - 1 + e: parity e & 1, idx tx + (e >> 1)
-    const int raw_a = (((t_trl * 4 + ra) * 2 + th) * 2) * TW1 + t_tx;
-    const int raw_b = (((t_trl * 4 + rb) * 2 + th) * 2) * TW1 + t_tx;
-    auto transform = [&](int rbuf, int vbuf) {
-        if (!t_live) return;
-        const float* rw = rawb + rbuf * RAWF;
-        f32x4 r[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int o = ((e & 1) * TW1 + (e >> 1)) * 4;
-            const f32x4 da = *reinterpret_cast<const f32x4*>(rw + raw_a * 4 + o);
-            const f32x4 db = *reinterpret_cast<const f32x4*>(rw + raw_b * 4 + o);
-            r[e] = da + sgn * db;
-        }
-        float* v = lds + vbuf * (2 * OPER) + (((xi * 4) * 2 + th) * 64 + lane) * 4;
-        *reinterpret_cast<f32x4*>(v + 0 * 512) = r[0] - r[2];
-        *reinterpret_cast<f32x4*>(v + 1 * 512) = r[1] + r[2];
-        *reinterpret_cast<f32x4*>(v + 2 * 512) = r[2] - r[1];
-        *reinterpret_cast<f32x4*>(v + 3 * 512) = r[1] - r[3];
-    };
-
-    f32x16 acc[2][2][2];
-    zero_acc(acc);
-    const int frag = ((2 * wave) * 2 + hi) * 256 + (lane & 31) * 4;
-    const int S = p.S;
-
-    issue_raw(0, 0);
-    if (S > 1) issue_raw(1, 1);
-    issue_u(0, 0);
-    // rows of V that belong to no tile (n_tiles < 64) are never written by the transform: clear them once in both buffers so
-    // that the MFMAs do not chew on stale LDS contents (their outputs are masked anyway)
-    if (n_tiles < 64) {
-        const int dead = 64 - n_tiles;  // rows n_tiles .. 63 of each of the 32 (component, half) planes, 2 buffers
-        for (int i = t; i < 2 * 32 * dead; i += 512) {
-            const int row = n_tiles + i % dead;
-            const int plane = (i / dead) & 31;
-            const int buf = i / (dead * 32);
-            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<f32x4*>(lds + buf * (2 * OPER) + (plane * 64 + row) * 4) = z;
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70 | 4);  // vmcnt(4): everything but the 4 newest DMAs (U(0), issued last) has landed: raw(0), raw(1)
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    transform(0, 0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), written out (see wino_gemm_loop): raw(1), U(0) landed
-    __syncthreads();                     // ... and V(0) written by every wave
-    for (int s = 0; s < S; ++s) {
-        const int cur = s & 1, nxt = cur ^ 1;
-        if (s + 1 < S) issue_u(s + 1, nxt);
-        if (s + 2 < S) issue_raw(s + 2, cur);
-        const int cb = cur * (2 * OPER);
-        f32x4 fa[2][2], fb[2][2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) fa[c][i] = *reinterpret_cast<const f32x4*>(&lds[cb + frag + c * 512 + i * 128]);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) fb[c][j] = *reinterpret_cast<const f32x4*>(&lds[cb + OPER + frag + c * 512 + j * 128]);
-        }
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[0][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[0][i][ks], fb[0][j][ks], acc[0][i][j], 0, 0, 0);
-        if (s + 1 < S) transform(nxt, nxt);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[1][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[1][i][ks], fb[1][j][ks], acc[1][i][j], 0, 0, 0);
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), written out: U(s + 1) and raw(s + 2) of this wave have landed
-        __syncthreads();
-    }
-
-    // ---- epilogue (as wino_epilogue, with this kernel's tile -> pixel mapping)
     const int n0 = nt * WN_;
     const int em = t >> 4;
     const int eq = (t & 15) * 4;
@@ -638,6 +487,247 @@ __global__ __launch_bounds__(512, 2) void wino_fused_kernel(WinoFusedArgs p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ fused kernel on the bf16 matrix cores
+// The 16 GEMMs go through v_mfma_f32_32x32x16_bf16, fp32-exact by the three-piece split of conv_gemm_f32s.hip (x = x0 + x1 + x2,
+// every piece a bf16 rounded to nearest even; the six products a_i w_j with i + j <= 2): 3 x 32 matrix cycles per 32x32 block and
+// slab where the fp32 instruction (v_mfma_f32_32x32x2_f32) takes 4 x 64.
+//   * V: the transform threads split each element once as they write it, into three bf16 planes
+//     Vp[piece 3][comp 16][tile 64][8 ch] (16 B per tile and component: one ds_read_b128 is one MFMA operand), 2 x 48 KB.
+//   * U does not pass through LDS.  A wave owns two components, so its U operands are private: lane (row, half) loads the 8
+//     channels of couts row and row + 32 of both components straight into registers, one slab ahead (8 x 16 B), from
+//     ConvLayer::wino_u_split -- the three bf16 pieces of wino_u, [piece 3][comp 16][cout 64][8 ch] per slab, split once when
+//     the weights are packed.  (Splitting the fp32 wino_u in registers would be 32 values per lane and slab in both half-waves,
+//     about as much VALU time as the matrix instructions save: the two waves of a SIMD run in step between barriers, so their
+//     VALU and MFMA phases add up instead of overlapping.)
+//   * k axis: a slab is 8 channels, the instruction takes 16 k, so the two half-waves carry two different (A piece, W piece)
+//     pairs over the same 8 channels.  Three MFMAs per 32x32 block and slab, smallest terms first, into ONE fp32 accumulator
+//     (k = C <= 128 here; tests/wino_split_ref.py restates the arithmetic):
+//         lanes 0-31   a0 w2   a1 w0   a0 w0
+//         lanes 32-63  a2 w0   a1 w1   a0 w1
+//     so a lane keeps two W operands per block column (lanes 0-31: w2, w0; lanes 32-63: w0, w1).
+//   * with U out of LDS there is room for a third raw buffer: the raw slabs form a ring of three, and a slab's DMA has two slabs
+//     of matrix time to arrive instead of one.
+// LDS: V 2 x 48 KB + raw 3 x 16 KB = 144 KB (the epilogue's transpose tile reuses the first 128 KB).
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int VPL = 16 * 64 * 16;                 // bytes of one piece plane of a V slab
+constexpr int VSB = 3 * VPL;                      // bytes of one V buffer
+constexpr int SRAWF = 1024 * 4;                   // floats per raw buffer: 16 wave-instructions of 64 chunks (the 16th is padding)
+constexpr int NRAW = 3;                           // raw ring: slab s + 3 is in flight while slab s computes
+constexpr int SPLIT_LDS_BYTES = 2 * VSB + NRAW * SRAWF * 4;  // 144 KB
+static_assert(SPLIT_LDS_BYTES >= 16 * 32 * 64 * 4 && SPLIT_LDS_BYTES <= 160 * 1024, "the epilogue's transpose tile needs 128 KB");
+
+// x = h0 + h1 + h2 exactly (finite x), each piece rounded to nearest even (bf16_split3)
+__device__ __forceinline__ void wino_split3(float x, __bf16& h0, __bf16& h1, __bf16& h2) {
+    h0 = (__bf16)x;
+    const float r1 = x - (float)h0;
+    h1 = (__bf16)r1;
+    const float r2 = r1 - (float)h1;
+    h2 = (__bf16)r2;
+}
+
+// the three pieces of 4 channels of one (component, tile) into the three planes
+__device__ __forceinline__ void wino_store_split(char* v, const f32x4& x) {
+    bf16x4 h0, h1, h2;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        __bf16 b0, b1, b2;
+        wino_split3(x[e], b0, b1, b2);
+        h0[e] = b0;
+        h1[e] = b1;
+        h2[e] = b2;
+    }
+    *reinterpret_cast<bf16x4*>(v) = h0;
+    *reinterpret_cast<bf16x4*>(v + VPL) = h1;
+    *reinterpret_cast<bf16x4*>(v + 2 * VPL) = h2;
+}
+
+__global__ __launch_bounds__(512, 2) void wino_fused_split_kernel(WinoFusedArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    char* const ldsb = reinterpret_cast<char*>(lds);
+    float* rawb = reinterpret_cast<float*>(ldsb + 2 * VSB);
+
+    const int total = p.n_blk * p.n_nt;
+    const int bid = blockIdx.x;
+    const int lid = xcd_remap(bid, total);
+    const int blk = lid / p.n_nt;
+    const int nt = lid - blk * p.n_nt;
+
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int hi = lane >> 5;
+    const int row = lane & 31;
+    const int TW1 = p.TW + 1;
+
+    // ---- raw DMA sources: chunk slot c = (i * 8 + wave) * 64 + lane -> (tile row, input row, half, parity, idx)
+    long rsrc[2];  // float offset inside a slab of Xs, or -1 for the zero page
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int c = (i * 8 + wave) * 64 + lane;
+        long off = -1;
+        if (c < p.NC) {
+            const int idx = c % TW1;
+            int r = c / TW1;
+            const int par = r & 1;
+            r >>= 1;
+            const int h = r & 1;
+            r >>= 1;
+            const int a = r & 3;
+            const int trl = r >> 2;
+            const int g = blk * p.R + trl;
+            if (g < p.NG) {
+                const int b = g / p.TH;
+                const int ty = g - b * p.TH;
+                const int iy = 2 * ty - 1 + a;
+                const int px = 2 * idx + par - 1;
+                if (iy >= 0 && iy < p.H && px >= 0 && px < p.W) off = ((long)(b * p.H + iy) * p.W + px) * 8 + h * 4;
+            }
+        }
+        rsrc[i] = off;
+    }
+    // Every wave issues exactly two DMA instructions per slab (chunk slots past NC read the zero page), so that the counted waits
+    // below mean the same thing in every wave.
+    auto issue_raw = [&](int s, int buf) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const float* src = rsrc[i] >= 0 ? p.Xs + (size_t)s * p.M * 8 + rsrc[i] : p.zero;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                             (__attribute__((address_space(3))) void*)(rawb + buf * SRAWF + (i * 8 + wave) * 256), 16, 0, 0);
+        }
+    };
+
+    // ---- W operands of this wave's two components from wino_u_split [piece 3][comp 16][cout 64][8 ch]: fn[c][j][0] goes with the first
+    // MFMA (w2 | w0 by half-wave), fn[c][j][1] with the other two (w0 | w1)
+    const unsigned short* usrc = p.Us + (size_t)nt * p.S * (3 * VPL / 2) + ((2 * wave) * 64 + row) * 8;
+    const int up0 = (hi ? 0 : 2) * (VPL / 2), up1 = (hi ? 1 : 0) * (VPL / 2);
+    bf16x8 fn[2][2][2];
+    auto load_u = [&](int s) {
+        const unsigned short* su = usrc + (size_t)s * (3 * VPL / 2);
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                fn[c][j][0] = *reinterpret_cast<const bf16x8*>(su + up0 + (c * 64 + j * 32) * 8);
+                fn[c][j][1] = *reinterpret_cast<const bf16x8*>(su + up1 + (c * 64 + j * 32) * 8);
+            }
+    };
+
+    // ---- transform role: tile = lane, wave = (half, xi)
+    const int th = wave & 1, xi = wave >> 1;
+    const int n_tiles = p.R * p.TW;
+    const bool t_live = lane < n_tiles;
+    const int t_trl = t_live ? lane / p.TW : 0;
+    const int t_tx = t_live ? lane - t_trl * p.TW : 0;
+    // row xi of B^T d uses input rows (ra, rb): xi 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3
+    const int ra = (xi == 0) ? 0 : (xi == 2 ? 2 : 1);
+    const int rb = (xi == 0) ? 2 : (xi == 1 ? 2 : (xi == 2 ? 1 : 3));
+    const float sgn = (xi == 1) ? 1.f : -1.f;
+    const int raw_a = (((t_trl * 4 + ra) * 2 + th) * 2) * TW1 + t_tx;
+    const int raw_b = (((t_trl * 4 + rb) * 2 + th) * 2) * TW1 + t_tx;
+    auto transform = [&](int rbuf, int vbuf) {
+        if (!t_live) return;
+        const float* rw = rawb + rbuf * SRAWF;
+        f32x4 r[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int o = ((e & 1) * TW1 + (e >> 1)) * 4;
+            const f32x4 da = *reinterpret_cast<const f32x4*>(rw + raw_a * 4 + o);
+            const f32x4 db = *reinterpret_cast<const f32x4*>(rw + raw_b * 4 + o);
+            r[e] = da + sgn * db;
+        }
+        char* v = ldsb + vbuf * VSB + ((xi * 4) * 64 + lane) * 16 + th * 8;
+        wino_store_split(v + 0 * 1024, r[0] - r[2]);
+        wino_store_split(v + 1 * 1024, r[1] + r[2]);
+        wino_store_split(v + 2 * 1024, r[2] - r[1]);
+        wino_store_split(v + 3 * 1024, r[1] - r[3]);
+    };
+
+    f32x16 acc[2][2][2];
+    zero_acc(acc);
+    // A operands of the three MFMAs: plane (half-wave 0: a0, half-wave 1: a2), a1, a0 of component 2 * wave, tile = row
+    const int fr0 = (((hi ? 2 : 0) * 16 + 2 * wave) * 64 + row) * 16;
+    const int fr1 = ((1 * 16 + 2 * wave) * 64 + row) * 16;
+    const int fr2 = ((2 * wave) * 64 + row) * 16;
+    const int S = p.S;
+
+    // the ring's first three slabs (a slab index past the end repeats the last slab: the data is never used)
+    issue_raw(0, 0);
+    issue_raw(S > 1 ? 1 : S - 1, 1);
+    issue_raw(S > 2 ? 2 : S - 1, 2);
+    // rows of V that belong to no tile (n_tiles < 64) are never written by the transform: clear them once in both buffers so
+    // that the MFMAs do not chew on stale LDS contents (their outputs are masked anyway)
+    if (n_tiles < 64) {
+        const int dead = 64 - n_tiles;  // rows n_tiles .. 63 of each of the 48 (piece, component) planes, 2 buffers
+        for (int i = t; i < 2 * 48 * dead; i += 512) {
+            const int r = n_tiles + i % dead;
+            const int plane = (i / dead) % 48;
+            const int buf = i / (dead * 48);
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(ldsb + buf * VSB + (plane * 64 + r) * 16) = z;
+        }
+    }
+    load_u(0);
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), written out: raw(0 .. 2) of this wave have landed
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    transform(0, 0);
+    __syncthreads();  // V(0) written by every wave
+    // Per slab s: take the W operands of U(s) | load U(s + 1) into the registers just freed | DMA raw(s + 3) into the ring slot raw(s) left when slab
+    // s - 1 transformed it | MFMAs of component 0 | transform raw(s + 1) -> V(s + 1) | MFMAs of component 1 | barrier.  The barrier
+    // publishes V(s + 1) and raw(s + 2), so the wait in front of it leaves this slab's two DMA instructions in flight: a raw slab has two
+    // slabs of matrix time to arrive from HBM.  What vmcnt(2) needs to be right: every slab issues at least two vector-memory operations
+    // after raw(s + 2) -- every wave issues its two DMAs in every slab, whatever s and NC -- and the loop holds no global stores (loads
+    // return in order).  The U loads of the last slab are dead and the compiler may drop them; nothing behind them is waited for.
+    int slot = 0;  // s % NRAW
+    for (int s = 0; s < S; ++s) {
+        const int cur = s & 1, nxt = cur ^ 1;
+        const int slot1 = slot + 1 == NRAW ? 0 : slot + 1;
+        bf16x8 fb[2][2][2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                fb[c][j][0] = fn[c][j][0];
+                fb[c][j][1] = fn[c][j][1];
+            }
+        load_u(s + 1 < S ? s + 1 : S - 1);
+        issue_raw(s + 3 < S ? s + 3 : S - 1, slot);
+        const char* vb = ldsb + cur * VSB;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            bf16x8 fa[3][2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                fa[0][i] = *reinterpret_cast<const bf16x8*>(vb + fr0 + c * 1024 + i * 512);
+                fa[1][i] = *reinterpret_cast<const bf16x8*>(vb + fr1 + c * 1024 + i * 512);
+                fa[2][i] = *reinterpret_cast<const bf16x8*>(vb + fr2 + c * 1024 + i * 512);
+            }
+#pragma unroll
+            for (int m = 0; m < 3; ++m)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[c][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[m][i], fb[c][j][m ? 1 : 0], acc[c][i][j], 0, 0, 0);
+            if (c == 0 && s + 1 < S) transform(slot1, nxt);
+        }
+        // vmcnt(2) lgkmcnt(0), written out: all but raw(s + 3) of this wave has landed -- raw(s + 2), U(s + 1) -- and its V(s + 1) is
+        // written.  A bare barrier: __syncthreads() would bring its own vmcnt(0) behind the DMAs and shorten the ring to one slab.
+        __builtin_amdgcn_s_waitcnt(0x0072);
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        slot = slot1;
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): no DMA may land in the LDS the epilogue reuses
+    __syncthreads();
+
+    wino_fused_epilogue(p, lds, blk, nt, n_tiles, acc, t, wave, lane);
+}
+
 // NHWC -> channel-slab major (only the debug entry point needs it: in the network the producing convolution writes Xs itself)
 __global__ __launch_bounds__(256) void nhwc_to_slab8_kernel(const float* __restrict__ x, float* __restrict__ xs, long M, int C) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;  // one float4
@@ -656,8 +746,7 @@ hipError_t hpe_wino_init_device() {
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino_gemm_streamk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WINO_LDS_BYTES);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(wino_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               FUSED_LDS_FLOATS * (int)sizeof(float));
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(wino_fused_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_LDS_BYTES);
 }
 
 size_t hpe_wino_v_floats(int B, int H, int W, int C) {
@@ -711,9 +800,9 @@ hipError_t hpe_launch_wino_conv3(const float* x, int lda, const float* U, const 
 }
 
 // fused variant for even maps with W / 2 <= 64 tiles per row: xs is channel-slab major [C/8][B*H*W][8]
-hipError_t hpe_launch_wino_fused_conv3(const float* xs, const float* U, const float* scale, const float* shift, const float* zero16, float* y,
+hipError_t hpe_launch_wino_fused_conv3(const float* xs, const unsigned short* Us, const float* scale, const float* shift, const float* zero16, float* y,
                                        int ldy, int B, int H, int W, int C, int N, int relu, hipStream_t st) {
-    if (C % 8 != 0 || N % 64 != 0 || ldy % 4 != 0 || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || !zero16) return hipErrorInvalidValue;
+    if (C % 8 != 0 || N % 64 != 0 || ldy % 4 != 0 || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || !zero16 || !Us) return hipErrorInvalidValue;
     const int TW = W / 2, TH = H / 2;
     if (TW > 64) return hipErrorInvalidValue;
     int R = 64 / TW;
@@ -721,10 +810,9 @@ hipError_t hpe_launch_wino_fused_conv3(const float* xs, const float* U, const fl
     if (R > TH * B) R = TH * B;
     const int NC = R * 4 * 2 * 2 * (TW + 1);
     if (R < 1 || NC > 960) return hipErrorInvalidValue;
-    constexpr int LDS_BYTES = FUSED_LDS_FLOATS * (int)sizeof(float);
     WinoFusedArgs p{};
     p.Xs = xs;
-    p.U = U;
+    p.Us = Us;
     p.scale = scale;
     p.shift = shift;
     p.zero = zero16;
@@ -742,7 +830,7 @@ hipError_t hpe_launch_wino_fused_conv3(const float* xs, const float* U, const fl
     p.M = (long)B * H * W;
     p.ldy = ldy;
     p.relu = relu;
-    hipLaunchKernelGGL(wino_fused_kernel, dim3(p.n_blk * p.n_nt), dim3(512), LDS_BYTES, st, p);
+    hipLaunchKernelGGL(wino_fused_split_kernel, dim3(p.n_blk * p.n_nt), dim3(512), SPLIT_LDS_BYTES, st, p);
     return hipGetLastError();
 }
 

@@ -530,7 +530,7 @@ __global__ __launch_bounds__(W4_THREADS32, 2) void w4_gemm32_kernel(W4Args p) {
 
 // ------------------------------------------------------------------------------------------------ fused input transform (56x56 / 28x28 maps)
 // The same GEMM without V in memory: the producing 1x1 convolution writes its output channel-slab major, Xs[slab of 8 ch][pixel][8]
-// (GemmArgs::y_slab8, as for wino_fused_kernel), and a workgroup owns R consecutive tile rows of the batch -- 2 x 14 tiles on the 56x56
+// (GemmArgs::y_slab8, as for wino_fused_split_kernel), and a workgroup owns R consecutive tile rows of the batch -- 2 x 14 tiles on the 56x56
 // maps, 4 x 7 on the 28x28 maps: 28 of its 32 tile slots -- for one 64-cout block.  Per 4-channel slab (half of an 8-channel record: 16 B
 // per pixel) the 6 input rows of every tile row arrive by LDS-DMA as raw[tile row][6][W + 2][4 ch] (zero page for the halo; <= 720 chunks =
 // ONE wave-instruction per wave), and 168 (tile, xi) pairs, 14 lanes of every wave, turn them into the V slab image the MFMA loop reads:

@@ -25,7 +25,11 @@ namespace {
 struct RepackLayer {
     float *w, *scale, *shift, *wino_u, *wino4_u, *dxw;
     unsigned short* w_split;
-    int kh, cin, cout, n_pad, k_pad;
+    // wino_split: wino_u is followed by ConvLayer::wino_u_split in the same allocation (pack_wino_weights; wino_u_split_of in hpe_ctx.h is the
+    // one place that says where).  A flag beside kh, not a pointer: sizeof(RepackTable) sizes the device update's reserve, and
+    // tests/encoder_train_ref.py restates that size.
+    short kh, wino_split;
+    int cin, cout, n_pad, k_pad;
     int off[4];  // kernel, bias, gamma, beta in the flat layout
     int stat;    // first channel in EncTrainWork::mean / sd
 };
@@ -147,7 +151,10 @@ __global__ __launch_bounds__(256) void repack_wino_kernel(const RepackTable* __r
                 gx[a] = TT == 4 ? wino_g(xi, a) : wino4_g(xi, a);
                 gn[a] = TT == 4 ? wino_g(nu, a) : wino4_g(nu, a);
             }
-            out[(size_t)(xi * TT + nu) * step] = wino_elem(gx, gn, g);
+            const float u = wino_elem(gx, gn, g);
+            out[(size_t)(xi * TT + nu) * step] = u;
+            if (TT == 4 && L.wino_split)
+                store_split(wino_u_split_of(L.wino_u, L.cin, L.cout) + wino_us_base(n, ci, L.cin) + (size_t)(xi * 4 + nu) * 512, WINO_US_PIECE, u);
         }
 }
 
@@ -262,6 +269,7 @@ int encoder_repack_reserve(hpe_ctx* c) {
         r.scale = L.scale;
         r.shift = L.shift;
         r.wino_u = L.wino_u;
+        r.wino_split = L.wino_u_split != nullptr;
         r.wino4_u = L.wino4_u;
         r.dxw = c->et.dxw[i];
         r.w_split = static_cast<unsigned short*>(L.w_split);

@@ -66,6 +66,10 @@ struct ConvLayer {
     void* w_dual_split = nullptr;
     void* stem_w = nullptr;   // conv1 only: weights in the k enumeration of stem_fused.hip (bf16 [64][7][32]; fp32: its three bf16 pieces [3][64][7][32])
     float* wino_u = nullptr;  // device, G g G^T in the blocked layout of conv_wino.hip (3x3 layers on the Winograd path only)
+    // derived from wino_u, not a packing of its own: its three bf16 pieces in the operand order of wino_fused_split_kernel (wino_us_base),
+    // behind wino_u in the same allocation; held by the layers of the fused F(2x2,3x3) path (maps from wino_fused_min_hw on), written by
+    // hpe_finalize and by the repack kernel
+    unsigned short* wino_u_split = nullptr;
     float* wino4_u = nullptr;  // device, the F(4x4,3x3) G g G^T in the blocked layout of conv_wino4.hip (layers selected by wino_f4)
     int n_pad = 0, k_pad = 0;
 };
@@ -86,6 +90,16 @@ inline int conv_k_pad(int idx, bool bf16) { return round_up(idx == 0 ? 7 * 32 : 
 // first element of (cout n, cin ci) in the F(2x2,3x3) weights [cout/64][cin/8][16][2][64][4]; element (xi, nu) is (xi * 4 + nu) * 512 further
 __host__ __device__ inline size_t wino_u_base(int n, int ci, int cin) {
     return ((((size_t)(n >> 6) * (cin / 8) + (ci >> 3)) * 16) * 2 + ((ci >> 2) & 1)) * 256 + (size_t)(n & 63) * 4 + (ci & 3);
+}
+// ... in the split F(2x2,3x3) weights, bf16 [cout/64][cin/8][piece 3][16][64][8]: element (xi, nu) is (xi * 4 + nu) * 512 further, piece j is
+// j * WINO_US_PIECE further
+constexpr size_t WINO_US_PIECE = 16 * 64 * 8;
+__host__ __device__ inline size_t wino_us_base(int n, int ci, int cin) {
+    return ((size_t)(n >> 6) * (cin / 8) + (ci >> 3)) * 3 * WINO_US_PIECE + (size_t)(n & 63) * 8 + (ci & 7);
+}
+// where that buffer lives: behind the 16 * cin * cout floats of wino_u, in wino_u's allocation (packer and repack kernel both ask here)
+__host__ __device__ inline unsigned short* wino_u_split_of(float* wino_u, int cin, int cout) {
+    return reinterpret_cast<unsigned short*>(wino_u + (size_t)16 * cin * cout);
 }
 // ... and in the F(4x4,3x3) weights [cout/64][cin/4][36][64][4]; element (xi, nu) is (xi * 6 + nu) * 256 further
 __host__ __device__ inline size_t wino4_u_base(int n, int ci, int cin) {

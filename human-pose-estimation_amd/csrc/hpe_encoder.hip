@@ -39,7 +39,7 @@ hipError_t run_conv(hpe_ctx* c, int idx, const ConvRoute& r, const float* x, int
     if ((r.kernel >= CONV_K_HALO3 && res) || (f2 && !L.wino_u) || (f4 && !L.wino4_u) || ((f2 || f4) && !r.in_slab8 && !wino_v)) return hipErrorInvalidValue;
     switch (r.kernel) {
         case CONV_K_WINO4_FUSED: return hpe_launch_wino4_fused_conv3(x, L.wino4_u, scale, shift, c->zeros, y, s.cout, B, H, H, s.cin, s.cout, relu, st);
-        case CONV_K_WINO_FUSED: return hpe_launch_wino_fused_conv3(x, L.wino_u, scale, shift, c->zeros, y, s.cout, B, H, H, s.cin, s.cout, relu, st);
+        case CONV_K_WINO_FUSED: return hpe_launch_wino_fused_conv3(x, L.wino_u_split, scale, shift, c->zeros, y, s.cout, B, H, H, s.cin, s.cout, relu, st);
         case CONV_K_WINO4:
             return hpe_launch_wino4_conv3(x, s.cin, L.wino4_u, scale, shift, y, s.cout, B, H, H, s.cin, s.cout, relu, wino_v, st, r.concurrent ? c->co_running : 1,
                                           c->w4_split && slot >= 0 && slot < 4 ? c->w4_split + (size_t)slot * hpe_wino4_split_ws_floats() : nullptr, c->plan.wino4_n32,

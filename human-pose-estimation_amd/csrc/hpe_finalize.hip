@@ -258,7 +258,21 @@ static int pack_wino_weights(hpe_ctx* c, const ConvSpec& s, ConvLayer& L) {
                     U[base + (size_t)(xi * 4 + nu) * 512] = wino_elem(gx, gn, g);
                 }
         }
+    if (!(c->plan.wino_fused && s.hin >= c->plan.wino_fused_min_hw)) return upload_to(c, &L.wino_u, U);
+    // the fused kernel of the large maps reads U as three bf16 pieces (wino_us_base): kept behind wino_u in the same allocation
+    const size_t nu = U.size();
+    std::vector<unsigned short> Us((size_t)3 * nu);
+    for (int ci = 0; ci < s.cin; ++ci)
+        for (int n = 0; n < s.cout; ++n)
+            for (int e = 0; e < 16; ++e) {
+                unsigned short h[3];
+                bf16_split3(U[wino_u_base(n, ci, s.cin) + (size_t)e * 512], h);
+                for (int j = 0; j < 3; ++j) Us[wino_us_base(n, ci, s.cin) + j * WINO_US_PIECE + (size_t)e * 512] = h[j];
+            }
+    U.resize(nu + Us.size() / 2);
+    memcpy(U.data() + nu, Us.data(), Us.size() * 2);
     if ((rc = upload_to(c, &L.wino_u, U))) return rc;
+    L.wino_u_split = wino_u_split_of(L.wino_u, s.cin, s.cout);
     return HPE_OK;
 }
 

@@ -80,7 +80,7 @@ hipError_t hpe_launch_wino_conv3(const float* x, int lda, const float* U, const 
                                  int B, int H, int W, int C, int N, int relu, float* V, const WinoStreamK* sk, hipStream_t st);
 
 // fused-transform variant (56x56 / 28x28 maps): xs is channel-slab major [C/8][B*H*W][8] (GemmArgs::y_slab8 of the producer)
-hipError_t hpe_launch_wino_fused_conv3(const float* xs, const float* U, const float* scale, const float* shift, const float* zero16, float* y,
+hipError_t hpe_launch_wino_fused_conv3(const float* xs, const unsigned short* Us, const float* scale, const float* shift, const float* zero16, float* y,
                                        int ldy, int B, int H, int W, int C, int N, int relu, hipStream_t st);
 int hpe_wino_fused_items(int B, int H, int W, int N);  // work items of that launch, 0 if the geometry is not supported
 hipError_t hpe_launch_nhwc_to_slab8(const float* x, float* xs, long M, int C, hipStream_t st);

@@ -966,7 +966,7 @@ class HpeEngine(object):
             return ("conv_gemm_f32s_dma_kernel (the 1x1 / strided / dual-source layers of stages 3-5 on the bf16 matrix cores, operands split "
                     "exactly into three bf16 pieces) + conv_gemm_f32_dma_kernel (the other 1x1 layers) + w4_input_kernel + w4_gemm_kernel / w4_gemm32_kernel "
                     "(the 13 3x3 layers on the 28x28 / 14x14 / 7x7 maps as fp32 Winograd F(4x4,3x3); F(2x2,3x3) / direct below 64 work "
-                    "items) + wino_fused_kernel (the three 56x56 3x3 layers, F(2x2,3x3)) + stem_fused_f32s_kernel (image and weights split like the 1x1 layers) -- the 53 conv layers of one "
+                    "items) + wino_fused_split_kernel (the three 56x56 3x3 layers, F(2x2,3x3) on the bf16 matrix cores through the same exact split) + stem_fused_f32s_kernel (image and weights split like the 1x1 layers) -- the 53 conv layers of one "
                     "step, priced at their direct-convolution FLOPs")
         return ("conv_gemm_bf16_dma_kernel (1x1 / strided / dual-source layers) + chain_expand_reduce_bf16_kernel (branch2c + next branch2a of "
                 "stages 2-3 as one launch) + conv3_halo_bf16_kernel (the sixteen 3x3 layers, tile + halo resident in LDS) + stem_fused_bf16_kernel "
