@@ -22,6 +22,8 @@ from . import critic_spec, regressor_spec, resnet_spec, synthetic  # noqa: F401,
 from ._lib import HpeError  # noqa: F401
 from .augment import augment_batch, draw_augmentation, mocap_real, plan_augmentation  # noqa: F401
 from .critic_train import CriticTrainer  # noqa: F401
+from . import distributed  # noqa: F401
+from .distributed import Reducer, ShardedPredictor  # noqa: F401
 from .draw import draw_panels, draw_results, draw_skeleton  # noqa: F401
 from .engine import HpeEngine  # noqa: F401
 from .generator_train import GeneratorTrainer  # noqa: F401

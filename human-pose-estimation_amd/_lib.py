@@ -177,6 +177,9 @@ class HpeOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in OUTPUT_FIELDS]
 
 
+# hpe_reduce_fn (include/hpe.h): (user, dev_buf, count, stream) -> 0, or nonzero for a failure.  ctypes takes the GIL for the callback
+REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p)
+
 _PROTOS = {
     "hpe_last_error": (C.c_char_p, []),
     "hpe_version": (C.c_char_p, []),
@@ -284,6 +287,14 @@ _PROTOS = {
                                                     C.c_void_p]),
     "hpe_debug_encoder_stash_raw": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_encoder_batch_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_encoder_set_reduce": (C.c_int, [C.c_void_p, REDUCE_FN, C.c_void_p, C.c_int]),
+    "hpe_debug_bn_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_debug_bn_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "hpe_debug_bn_backward_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p,
+                                             C.c_void_p]),
+    "hpe_debug_bn_backward_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_device_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hpe_debug_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

@@ -48,6 +48,27 @@ class KpLossFunction(torch.autograd.Function):
         return None, _engine.kp_loss_backward(kp_gt, kp_pred, grad_loss.to(torch.float32))
 
 
+class KpLossShareFunction(torch.autograd.Function):
+    """One rank's share of kp_reprojection_loss over a batch spread across ranks: (this rank's sum of vis * |d|) / (2 * #visible of ALL
+    ranks).  ``global_count``: that denominator as a one-element CUDA tensor, already summed over the ranks (``kp_visible_count`` and one
+    all-reduce); the ranks' shares add up to the loss of the global batch, 0 where nothing is visible anywhere.  The backward is
+    hpe_kp_loss_backward, which divides by the local count, scaled by local count / global count; nothing reads the device."""
+
+    @staticmethod
+    def forward(ctx, kp_gt, kp_pred, global_count):
+        parts = _engine.kp_loss_parts(kp_gt.detach(), kp_pred.detach())
+        g = global_count.detach().reshape(()).to(torch.float32)
+        zero = torch.zeros_like(g)
+        den = torch.clamp(g, min=1.0)
+        ctx.save_for_backward(kp_gt.detach(), kp_pred.detach(), torch.where(g > 0, parts[1] / den, zero))
+        return torch.where(g > 0, parts[0] / den, zero)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        kp_gt, kp_pred, ratio = ctx.saved_tensors
+        return None, _engine.kp_loss_backward(kp_gt, kp_pred, grad_loss.to(torch.float32) * ratio), None
+
+
 class MeshLossFunction(torch.autograd.Function):
     """loss = mesh_reprojection_loss(seg, verts2d), differentiable in verts2d: the forward is ONE hpe_mesh_loss_grad call, which
     returns the loss and d loss / d verts2d from the same pair of searches; the backward scales the saved gradient."""

@@ -12,6 +12,9 @@
 // nothing a float sees until mu^2 / var nears 2^29).  bn_apply_kernel / bn_bwd_apply_kernel are elementwise, one f32x4 per thread.
 // bn_momentum_kernel moves the whole statistics tensor [mean of every channel | variance of every channel] in one launch;
 // bn_install_kernel rewrites what the frozen path folds (mean, sqrt(var + eps) in double, its reciprocal) from such a tensor.
+// Data-parallel training cuts both reductions where the ranks meet: bn_sums_kernel / bn_bwd_sums_kernel leave the column sums of this
+// rank's rows as [2][N] doubles (added over the slices in the finish kernels' order), the caller adds the other ranks' to them, and
+// bn_stats_from_sums_kernel / bn_bwd_from_sums_kernel finish from the sums over all M rows with the arithmetic of the one-rank finish.
 // N is a multiple of 64 on every layer; rows past M are never read.
 #include <hip/hip_runtime.h>
 
@@ -117,20 +120,43 @@ __device__ inline bool bn_sum_slices(const double* __restrict__ part, int slices
     return true;
 }
 
-// mu, var (biased) and r = 1 / sqrt(var + eps) of every channel from the slices' partials (bn_sum_slices)
-__global__ __launch_bounds__(256) void bn_stats_finish_kernel(const double* __restrict__ part, int slices, int M, int N, float eps, float* __restrict__ mu,
-                                                              float* __restrict__ var, float* __restrict__ r) {
+// mu, var (biased) and r = 1 / sqrt(var + eps) of channel n from its two column sums over M rows
+__device__ inline void bn_finish_channel(double s, double q, double M, float eps, int n, float* __restrict__ mu, float* __restrict__ var,
+                                         float* __restrict__ r) {
 #pragma clang fp contract(off)
-    int n;
-    double s, q;
-    if (!bn_sum_slices(part, slices, N, &n, &s, &q)) return;
-    const double mean = s / (double)M;
-    double v = q / (double)M - mean * mean;
+    const double mean = s / M;
+    double v = q / M - mean * mean;
     if (v < 0.0) v = 0.0;
     const float vf = (float)v;
     mu[n] = (float)mean;
     var[n] = vf;
     r[n] = (float)(1.0 / __dsqrt_rn((double)vf + (double)eps));
+}
+
+// mu, var (biased) and r = 1 / sqrt(var + eps) of every channel from the slices' partials (bn_sum_slices)
+__global__ __launch_bounds__(256) void bn_stats_finish_kernel(const double* __restrict__ part, int slices, int M, int N, float eps, float* __restrict__ mu,
+                                                              float* __restrict__ var, float* __restrict__ r) {
+    int n;
+    double s, q;
+    if (!bn_sum_slices(part, slices, N, &n, &s, &q)) return;
+    bn_finish_channel(s, q, (double)M, eps, n, mu, var, r);
+}
+
+// The same in two launches, for statistics over more rows than this device holds (data-parallel training): the slices' partials into
+// sums [2][N] = (sum z | sum z^2) in the order of bn_sum_slices; the caller adds the other ranks' sums to them in place; then mu, var
+// and r from the sums over all M rows, one thread per channel
+__global__ __launch_bounds__(256) void bn_sums_kernel(const double* __restrict__ part, int slices, int N, double* __restrict__ sums) {
+    int n;
+    double s, q;
+    if (!bn_sum_slices(part, slices, N, &n, &s, &q)) return;
+    sums[n] = s;
+    sums[N + n] = q;
+}
+
+__global__ __launch_bounds__(256) void bn_stats_from_sums_kernel(const double* __restrict__ sums, double M, int N, float eps, float* __restrict__ mu,
+                                                                 float* __restrict__ var, float* __restrict__ r) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n < N) bn_finish_channel(sums[n], sums[N + n], M, eps, n, mu, var, r);
 }
 
 __device__ inline f32x4 relu4(f32x4 v) {
@@ -208,6 +234,28 @@ __global__ __launch_bounds__(256) void bn_bwd_finish_kernel(const double* __rest
     dgamma[n] = (float)q;
 }
 
+// The same in two launches (bn_sums_kernel's split).  The local sums into sums [2][N] = (sum dz | sum dz * xhat) and, rounded, into the
+// caller's gradient: dbeta and dgamma stay this rank's partial, which the all-reduce of the whole flat gradient completes ...
+__global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const double* __restrict__ part, int slices, int N, double* __restrict__ sums,
+                                                          float* __restrict__ db, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    int n;
+    double s, q;
+    if (!bn_sum_slices(part, slices, N, &n, &s, &q)) return;
+    sums[n] = s;
+    sums[N + n] = q;
+    db[n] = 0.f;
+    dbeta[n] = (float)s;
+    dgamma[n] = (float)q;
+}
+
+// ... and the sums over all ranks, rounded as bn_bwd_finish_kernel rounds, into red [2][N] = (dbeta | dgamma): what bn_bwd_apply_kernel reads
+__global__ __launch_bounds__(256) void bn_bwd_from_sums_kernel(const double* __restrict__ sums, int N, float* __restrict__ red) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    red[n] = (float)sums[n];
+    red[N + n] = (float)sums[N + n];
+}
+
 // dz = dy * [y > 0] (y == nullptr: dz = dy) and dzraw = gamma * r * (dz - dbeta / M - xhat * dgamma / M).  dz may be nullptr and may alias dy
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const f32x4* dy, const f32x4* __restrict__ y, const f32x4* __restrict__ z,
                                                            const f32x4* __restrict__ mu, const f32x4* __restrict__ r, const f32x4* __restrict__ gamma,
@@ -275,6 +323,20 @@ hipError_t bn_launch_stats(const float* z, int M, int N, float eps, double* part
     return hipGetLastError();
 }
 
+hipError_t bn_launch_stats_sums(const float* z, int M, int N, double* part, double* sums, hipStream_t st) {
+    if (bad_shape(M, N)) return hipErrorInvalidValue;
+    const BnGeom g = geom(M, N);
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(z), M, N, g.cg, g.rows, g.P, part);
+    hipLaunchKernelGGL(bn_sums_kernel, dim3(N / 16), dim3(256), 0, st, part, g.slices, N, sums);
+    return hipGetLastError();
+}
+
+hipError_t bn_launch_stats_from_sums(const double* sums, double M, int N, float eps, float* mu, float* var, float* r, hipStream_t st) {
+    if (bad_shape(1, N) || !(M >= 1.0)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bn_stats_from_sums_kernel, grid1(N), dim3(256), 0, st, sums, M, N, eps, mu, var, r);
+    return hipGetLastError();
+}
+
 hipError_t bn_launch_apply(const float* z, const float* mu, const float* r, const float* gamma, const float* beta, const float* res, int relu, float* y,
                            int M, int N, hipStream_t st) {
     if (bad_shape(M, N)) return hipErrorInvalidValue;
@@ -292,12 +354,27 @@ hipError_t bn_launch_bwd_reduce(const float* dy, const float* y, const float* z,
     return hipGetLastError();
 }
 
+hipError_t bn_launch_bwd_sums(const float* dy, const float* y, const float* z, const float* mu, const float* r, int M, int N, double* part, double* sums,
+                              float* db, float* dgamma, float* dbeta, hipStream_t st) {
+    if (bad_shape(M, N)) return hipErrorInvalidValue;
+    const BnGeom g = geom(M, N);
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(dy), q4(y), q4(z), q4(mu), q4(r), M, N, g.cg, g.rows, g.P, part);
+    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(N / 16), dim3(256), 0, st, part, g.slices, N, sums, db, dgamma, dbeta);
+    return hipGetLastError();
+}
+
+hipError_t bn_launch_bwd_from_sums(const double* sums, int N, float* red, hipStream_t st) {
+    if (bad_shape(1, N)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bn_bwd_from_sums_kernel, grid1(N), dim3(256), 0, st, sums, N, red);
+    return hipGetLastError();
+}
+
 hipError_t bn_launch_bwd_apply(const float* dy, const float* y, const float* z, const float* mu, const float* r, const float* gamma, const float* dgamma,
-                               const float* dbeta, int M, int N, float* dz, float* dzraw, hipStream_t st) {
+                               const float* dbeta, int M, int N, float* dz, float* dzraw, hipStream_t st, double M_all) {
     if (bad_shape(M, N)) return hipErrorInvalidValue;
     const long n4 = (long)M * (N / 4);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, grid1(n4), dim3(256), 0, st, q4(dy), q4(y), q4(z), q4(mu), q4(r), q4(gamma), dgamma, dbeta, (float)M,
-                       q4(dz), q4(dzraw), n4, N / 4);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, grid1(n4), dim3(256), 0, st, q4(dy), q4(y), q4(z), q4(mu), q4(r), q4(gamma), dgamma, dbeta,
+                       M_all > 0.0 ? (float)M_all : (float)M, q4(dz), q4(dzraw), n4, N / 4);
     return hipGetLastError();
 }
 

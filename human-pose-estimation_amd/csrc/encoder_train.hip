@@ -142,32 +142,65 @@ BnSlots bn_slots(hpe_ctx* c, int idx, bool scratch) {
     return {b + l.stat[idx], b + l.channels + l.stat[idx], b + 2 * l.channels + l.stat[idx]};
 }
 
-// z = conv(x, W) + b (the layer's own route, unit scale, the bias of the flat copy as shift), its statistics, y = act(BN(z) (+ res))
-hipError_t layer_forward_bn(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* z, float* y, const BnSlots& s, hipStream_t st) {
+// the reduce buffers of data-parallel training, in the weight gradient's scratch (hpe_ctx.h): the sums [2][N] doubles that cross the
+// ranks, and behind them the reduced dbeta | dgamma [2][N] floats
+double* reduce_sums(hpe_ctx* c) { return reinterpret_cast<double*>(c->et.wgp); }
+float* reduce_grads(hpe_ctx* c) { return c->et.wgp + 2 * 2 * 2048; }
+
+// the rows of layer idx over the batch of all ranks
+double rows_all(hpe_ctx* c, int idx) { return (double)c->et.reduce_G * specs()[idx].hout * specs()[idx].hout; }
+
+// the hook on `count` doubles of the reduce buffer; a failure is kept for the entry point, which names the layer
+hipError_t reduce_call(hpe_ctx* c, int idx, long long count, hipStream_t st) {
+    if (c->et.reduce(c->et.reduce_user, reduce_sums(c), count, st) == 0) return hipSuccess;
+    c->et.reduce_failed = idx;
+    return hipErrorUnknown;
+}
+
+// z = conv(x, W) + b (the layer's own route, unit scale, the bias of the flat copy as shift), its statistics, y = act(BN(z) (+ res)).
+// reduce: the statistics of all ranks' rows (the hook is set)
+hipError_t layer_forward_bn(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* z, float* y, const BnSlots& s, hipStream_t st,
+                            bool reduce = false) {
     const ConvSpec& sp = specs()[idx];
     const EncLayout& l = layout();
     const float* flat = c->et.flat;
     const int M = B * sp.hout * sp.hout;
     HIPE(run_conv_nhwc(c, idx, x, B, nullptr, 0, z, st, c->ones, flat + l.off[idx][1]));
-    HIPE(bn_launch_stats(z, M, sp.cout, c->cfg.bn_eps, c->et.bn_part, s.mu, s.var, s.r, st));
+    if (reduce) {
+        HIPE(bn_launch_stats_sums(z, M, sp.cout, c->et.bn_part, reduce_sums(c), st));
+        HIPE(reduce_call(c, idx, 2LL * sp.cout, st));
+        HIPE(bn_launch_stats_from_sums(reduce_sums(c), rows_all(c, idx), sp.cout, c->cfg.bn_eps, s.mu, s.var, s.r, st));
+    } else {
+        HIPE(bn_launch_stats(z, M, sp.cout, c->cfg.bn_eps, c->et.bn_part, s.mu, s.var, s.r, st));
+    }
     return bn_launch_apply(z, s.mu, s.r, flat + l.off[idx][2], flat + l.off[idx][3], res, relu, y, M, sp.cout, st);
 }
 
 // the gate and the BatchNorm backward of layer idx: db (= 0), dgamma, dbeta into grad_layer; dz (may be nullptr, may alias dy) and dzraw
+// reduce: grad_layer keeps this rank's partial sums, dzraw is that of the batch of all ranks (the hook is set)
 hipError_t layer_gate_bn(hpe_ctx* c, int idx, const float* dy, const float* y, const float* z, int B, const BnSlots& s, float* grad_layer, float* dz,
-                         float* dzraw, hipStream_t st) {
+                         float* dzraw, hipStream_t st, bool reduce = false) {
     const ConvSpec& sp = specs()[idx];
     const int M = B * sp.hout * sp.hout, N = sp.cout, kn = sp.kh * sp.kw * sp.cin * N;
     float *db = grad_layer + kn, *dgamma = db + N, *dbeta = dgamma + N;
-    HIPE(bn_launch_bwd_reduce(dy, y, z, s.mu, s.r, M, N, c->et.bn_part, db, dgamma, dbeta, st));
-    return bn_launch_bwd_apply(dy, y, z, s.mu, s.r, c->et.flat + layout().off[idx][2], dgamma, dbeta, M, N, dz, dzraw, st);
+    const float* gamma = c->et.flat + layout().off[idx][2];
+    if (!reduce) {
+        HIPE(bn_launch_bwd_reduce(dy, y, z, s.mu, s.r, M, N, c->et.bn_part, db, dgamma, dbeta, st));
+        return bn_launch_bwd_apply(dy, y, z, s.mu, s.r, gamma, dgamma, dbeta, M, N, dz, dzraw, st);
+    }
+    float* red = reduce_grads(c);
+    HIPE(bn_launch_bwd_sums(dy, y, z, s.mu, s.r, M, N, c->et.bn_part, reduce_sums(c), db, dgamma, dbeta, st));
+    HIPE(reduce_call(c, idx, 2LL * N, st));
+    HIPE(bn_launch_bwd_from_sums(reduce_sums(c), N, red, st));
+    return bn_launch_bwd_apply(dy, y, z, s.mu, s.r, gamma, red + N, red, M, N, dz, dzraw, st, rows_all(c, idx));
 }
 
 // The training forward, every activation kept in the stash.  bn (batch statistics): z kept beside y, the statistics in the layers' slots
 hipError_t forward_train(hpe_ctx* c, bool bn, const float* images, int B, float* features, hipStream_t st) {
+    const bool reduce = bn && c->et.reduce != nullptr;
     auto layer = [&](int idx, const float* x, const float* res, int relu) {
         float* y = stash_of(c, idx, B);
-        return bn ? layer_forward_bn(c, idx, x, B, res, relu, zstash_of(c, idx, B), y, bn_slots(c, idx, false), st)
+        return bn ? layer_forward_bn(c, idx, x, B, res, relu, zstash_of(c, idx, B), y, bn_slots(c, idx, false), st, reduce)
                   : run_conv_nhwc(c, idx, x, B, res, relu, y, st);
     };
     HIPE(hpe_launch_pad_input(images, c->padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
@@ -203,7 +236,7 @@ hipError_t layer_gate(hpe_ctx* c, bool bn, int idx, float* dy, bool gated, bool 
     if (bn) {
         *o = {copy, copy};
         return layer_gate_bn(c, idx, dy, y, zstash_of(c, idx, B), B, bn_slots(c, idx, false), grad_flat + layout().off[idx][0], keep ? dy : nullptr,
-                             copy, st);
+                             copy, st, c->et.reduce != nullptr);
     }
     float* dzs = idx == 0 ? nullptr : copy;
     gate(dy, y, dzs ? c->conv[idx].scale : nullptr, gated ? dy : nullptr, dzs, (long)B * s.hout * s.hout * s.cout, s.cout, st);
@@ -287,15 +320,45 @@ int check_train(hpe_ctx* c, int B, Reserve need = RESERVE_FROZEN) {
     return HPE_OK;
 }
 
+// before a walk's first launch: no hook failure on record and, with the reduce hook set, what a batch-statistics walk needs: B within
+// the batch of all ranks, no capture
+int check_reduce(hpe_ctx* c, bool bn, int B, hipStream_t st) {
+    c->et.reduce_failed = -1;
+    if (!bn || !c->et.reduce) return HPE_OK;
+    if (B > c->et.reduce_G)
+        return fail(HPE_ERR_INVALID, "batch " + std::to_string(B) + " above the global batch " + std::to_string(c->et.reduce_G) + " of hpe_encoder_set_reduce");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail(HPE_ERR_STATE, "the stream is being captured and a reduce hook is set: the hook is host code");
+    return HPE_OK;
+}
+
+// the result of a walk: a hook failure (named by its layer) before any HIP error
+int walk_result(hpe_ctx* c, hipError_t e, const char* what) {
+    if (c->et.reduce_failed >= 0)
+        return fail(HPE_ERR_REDUCE, std::string("the reduce hook failed in the ") + what + " at layer " + std::to_string(c->et.reduce_failed) + " (" +
+                                        specs()[c->et.reduce_failed].name + ")");
+    HIP_TRY(e);
+    return HPE_OK;
+}
+
+void walk_done(hpe_ctx* c, bool bn, int B) {
+    c->et.stash_B = B;
+    if (!bn) return;
+    c->et.bn_stat_B = B;
+    c->et.bn_stat_G = c->et.reduce ? c->et.reduce_G : B;
+}
+
 // hpe_encoder_forward_train / _batchnorm and hpe_encoder_backward / _batchnorm
 int forward_entry(hpe_ctx* c, bool bn, const float* images, int B, float* features, void* stream) {
     int rc = check_train(c, B, bn ? RESERVE_BN : RESERVE_FROZEN);
     if (rc) return rc;
     if (!images || !features) return fail(HPE_ERR_INVALID, "null pointer");
     DeviceGuard g(c->cfg.device);
-    HIP_TRY(forward_train(c, bn, images, B, features, static_cast<hipStream_t>(stream)));
-    c->et.stash_B = B;
-    if (bn) c->et.bn_stat_B = B;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if ((rc = check_reduce(c, bn, B, st))) return rc;
+    if ((rc = walk_result(c, forward_train(c, bn, images, B, features, st), "forward"))) return rc;
+    walk_done(c, bn, B);
     return HPE_OK;
 }
 
@@ -304,9 +367,10 @@ int backward_entry(hpe_ctx* c, bool bn, const float* images, int B, const float*
     if (rc) return rc;
     if (!images || !grad_features || !grad_flat) return fail(HPE_ERR_INVALID, "null pointer");
     DeviceGuard g(c->cfg.device);
-    HIP_TRY(backward(c, bn, images, B, grad_features, grad_flat, static_cast<hipStream_t>(stream)));
-    c->et.stash_B = B;
-    if (bn) c->et.bn_stat_B = B;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if ((rc = check_reduce(c, bn, B, st))) return rc;
+    if ((rc = walk_result(c, backward(c, bn, images, B, grad_features, grad_flat, st), "backward"))) return rc;
+    walk_done(c, bn, B);
     return HPE_OK;
 }
 
@@ -319,6 +383,16 @@ int upload_train_params(hpe_ctx* c, const float* flat) {
         HIP_TRY(hipMemcpy(c->et.dxw[i], dx.data(), dx.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMemcpy(c->et.flat, flat, (size_t)l.total * sizeof(float), hipMemcpyHostToDevice));
+    return HPE_OK;
+}
+
+// what the four half-layer debug calls check: M, where they take one, is the rows of all parts
+int debug_bn_check(hpe_ctx* c, int idx, int B, long long M, bool with_m) {
+    int rc = check_train(c, B, RESERVE_BN);
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV) return fail(HPE_ERR_INVALID, "bad argument");
+    const long long local = (long long)B * specs()[idx].hout * specs()[idx].hout;
+    if (with_m && (M < local || M > 0x7fffffffLL / 2)) return fail(HPE_ERR_INVALID, "M below the rows given, or too large");
     return HPE_OK;
 }
 
@@ -557,7 +631,7 @@ int hpe_encoder_update_stats(hpe_ctx* c, float* stats, double momentum, int unbi
     if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(HPE_ERR_INVALID, "momentum outside [0, 1]");
     if (c->et.bn_stat_B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_update_stats: no batch-statistics forward has run");
     DeviceGuard g(c->cfg.device);
-    HIP_TRY(bn_launch_momentum(stats, c->et.bn_batch, c->et.bn_hw, c->et.bn_stat_B, layout().channels, momentum, unbiased != 0,
+    HIP_TRY(bn_launch_momentum(stats, c->et.bn_batch, c->et.bn_hw, c->et.bn_stat_G, layout().channels, momentum, unbiased != 0,
                                static_cast<hipStream_t>(stream)));
     return HPE_OK;
 }
@@ -632,6 +706,81 @@ int hpe_debug_encoder_batch_stats(hpe_ctx* c, float* out, void* stream) {
     DeviceGuard g(c->cfg.device);
     HIP_TRY(hipMemcpyAsync(out, c->et.bn_batch, 2 * (size_t)layout().channels * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     return HPE_OK;
+}
+
+// ---- data-parallel training: the statistics over the batch of all ranks
+
+int hpe_encoder_set_reduce(hpe_ctx* c, hpe_reduce_fn fn, void* user, int global_batch) {
+    int rc = check_train(c, 1, RESERVE_BN);
+    if (rc) return rc;
+    if (fn && (global_batch < 1 || global_batch > 65536)) return fail(HPE_ERR_INVALID, "hpe_encoder_set_reduce: global batch outside [1, 65536]");
+    c->et.reduce = fn;
+    c->et.reduce_user = fn ? user : nullptr;
+    c->et.reduce_G = fn ? global_batch : 0;
+    return HPE_OK;
+}
+
+int hpe_debug_bn_sums(hpe_ctx* c, int idx, const float* z, int B, double* sums_out, void* stream) {
+    int rc = debug_bn_check(c, idx, B, 0, false);
+    if (rc) return rc;
+    if (!z || !sums_out) return fail(HPE_ERR_INVALID, "null pointer");
+    DeviceGuard g(c->cfg.device);
+    const ConvSpec& s = specs()[idx];
+    HIP_TRY(bn_launch_stats_sums(z, B * s.hout * s.hout, s.cout, c->et.bn_part, sums_out, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+int hpe_debug_bn_finish(hpe_ctx* c, int idx, const double* sums, long long M, const float* z, int B, const float* residual, int relu, float* y,
+                        float* stats_out, void* stream) {
+    int rc = debug_bn_check(c, idx, B, M, true);
+    if (rc) return rc;
+    if (!sums || !z || !y || !stats_out) return fail(HPE_ERR_INVALID, "null pointer");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ConvSpec& s = specs()[idx];
+    const EncLayout& l = layout();
+    const BnSlots sl = bn_slots(c, idx, true);
+    HIP_TRY(bn_launch_stats_from_sums(sums, (double)M, s.cout, c->cfg.bn_eps, sl.mu, sl.var, sl.r, st));
+    HIP_TRY(bn_launch_apply(z, sl.mu, sl.r, c->et.flat + l.off[idx][2], c->et.flat + l.off[idx][3], residual, relu, y, B * s.hout * s.hout, s.cout, st));
+    HIP_TRY(hipMemcpyAsync(stats_out, sl.mu, (size_t)s.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(stats_out + s.cout, sl.var, (size_t)s.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return HPE_OK;
+}
+
+int hpe_debug_bn_backward_sums(hpe_ctx* c, int idx, const float* z, const float* y, const float* dy, int B, const double* sums, long long M,
+                               double* sums_out, void* stream) {
+    int rc = debug_bn_check(c, idx, B, M, true);
+    if (rc) return rc;
+    if (!z || !dy || !sums || !sums_out) return fail(HPE_ERR_INVALID, "null pointer");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ConvSpec& s = specs()[idx];
+    const BnSlots sl = bn_slots(c, idx, true);
+    float* local = reduce_grads(c);  // the rounded local sums, which nobody reads here: [db | dgamma | dbeta]
+    HIP_TRY(bn_launch_stats_from_sums(sums, (double)M, s.cout, c->cfg.bn_eps, sl.mu, sl.var, sl.r, st));
+    HIP_TRY(bn_launch_bwd_sums(dy, y, z, sl.mu, sl.r, B * s.hout * s.hout, s.cout, c->et.bn_part, sums_out, local, local + s.cout, local + 2 * s.cout, st));
+    return HPE_OK;
+}
+
+int hpe_debug_bn_backward_finish(hpe_ctx* c, int idx, const float* x, const float* z, const float* y, const float* dy, int B, const double* sums,
+                                 const double* bwd_sums, long long M, float* dx, float* grad_layer, void* stream) {
+    int rc = debug_bn_check(c, idx, B, M, true);
+    if (rc) return rc;
+    if (!x || !z || !dy || !sums || !bwd_sums || !grad_layer) return fail(HPE_ERR_INVALID, "null pointer");
+    if (idx == 0 && dx) return fail(HPE_ERR_INVALID, "hpe_debug_bn_backward_finish: conv1 has no data gradient, dx_dev must be NULL");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ConvSpec& s = specs()[idx];
+    EncTrainWork& w = c->et;
+    const int rows = B * s.hout * s.hout, N = s.cout, kn = s.kh * s.kw * s.cin * N;
+    const BnSlots sl = bn_slots(c, idx, true);
+    float *db = grad_layer + kn, *dgamma = db + N, *dbeta = dgamma + N, *red = reduce_grads(c);
+    HIP_TRY(bn_launch_stats_from_sums(sums, (double)M, N, c->cfg.bn_eps, sl.mu, sl.var, sl.r, st));
+    HIP_TRY(bn_launch_bwd_sums(dy, y, z, sl.mu, sl.r, rows, N, w.bn_part, reduce_sums(c), db, dgamma, dbeta, st));
+    HIP_TRY(bn_launch_bwd_from_sums(bwd_sums, N, red, st));
+    HIP_TRY(bn_launch_bwd_apply(dy, y, z, sl.mu, sl.r, w.flat + layout().off[idx][2], red + N, red, rows, N, nullptr, w.sbig, st, (double)M));
+    HIP_TRY(weight_grad(c, idx, x, w.sbig, B, grad_layer, st, true));
+    return dx ? debug_data_grad(c, idx, w.sbig, B, dx, st) : HPE_OK;
 }
 
 }  // extern "C"

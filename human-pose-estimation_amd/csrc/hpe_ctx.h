@@ -225,11 +225,20 @@ struct EncTrainWork {
     float *bn_stats = nullptr;  // the installed moving statistics [mean of every channel | variance of every channel]
     double *bn_part = nullptr;  // [slices][2][N] partial column sums of the reduction in flight (2 * BN_PART_COLS doubles)
     int *bn_hw = nullptr;       // hout * hout of every channel's layer (the M of hpe_encoder_update_stats)
+    // Data-parallel training (hpe_encoder_set_reduce): the hook that adds the ranks' column sums and the batch of all ranks together.
+    // The sums it reduces ([2][N] doubles, then the reduced dbeta | dgamma as [2][N] floats) live at the front of wgp: the weight
+    // gradient's scratch, which in stream order is idle from a layer's reduction to its elementwise launch
+    hpe_reduce_fn reduce = nullptr;
+    void *reduce_user = nullptr;
+    int reduce_G = 0;
+    int reduce_failed = -1;  // the layer at which the hook reported a failure during the walk in flight (-1: none)
+    int bn_stat_G = 0;       // the batch the statistics in bn_batch were taken over: bn_stat_B, or reduce_G where the hook ran
 };
 constexpr int BN_MAX_SLICES = 512;     // pixel slices of one BatchNorm reduction
 constexpr int BN_PART_COLS = 262144;   // slices * channels of one reduction, at most
 constexpr int WG_MAX_SLICES = 128;         // pixel slices of one weight gradient (what the fix-up adds per element)
 constexpr int WG_WGP_FLOATS = 1152 * 512;  // <W, G> per 4-row chunk: K / 4 x N of the largest kernel (3x3, 512 -> 512)
+static_assert(WG_WGP_FLOATS >= 3 * 2 * 2048, "the reduce buffers of data-parallel training fit the weight gradient's scratch");
 // floats of layer idx's data-gradient operand: rows = input channels padded to 128, k = (flipped tap, output channel); conv1 has none
 inline size_t conv_dxw_floats(int idx) {
     const ConvSpec& s = specs()[idx];
@@ -391,8 +400,17 @@ hipError_t bn_launch_apply(const float* z, const float* mu, const float* r, cons
                            int M, int N, hipStream_t st);
 hipError_t bn_launch_bwd_reduce(const float* dy, const float* y, const float* z, const float* mu, const float* r, int M, int N, double* part, float* db,
                                 float* dgamma, float* dbeta, hipStream_t st);
+// M_all > 0: the rows the statistics were taken over (all ranks'), where that is more than the M rows held here
 hipError_t bn_launch_bwd_apply(const float* dy, const float* y, const float* z, const float* mu, const float* r, const float* gamma, const float* dgamma,
-                               const float* dbeta, int M, int N, float* dz, float* dzraw, hipStream_t st);
+                               const float* dbeta, int M, int N, float* dz, float* dzraw, hipStream_t st, double M_all = 0.0);
+// The two reductions cut where the ranks of data-parallel training meet: the local column sums into sums [2][N] doubles (which the caller
+// adds over the ranks, in place), then the finish from the sums.  The backward's first half also writes the LOCAL db (= 0), dgamma and
+// dbeta; its second half rounds the summed (dbeta | dgamma) into red [2][N] floats for bn_launch_bwd_apply
+hipError_t bn_launch_stats_sums(const float* z, int M, int N, double* part, double* sums, hipStream_t st);
+hipError_t bn_launch_stats_from_sums(const double* sums, double M_all, int N, float eps, float* mu, float* var, float* r, hipStream_t st);
+hipError_t bn_launch_bwd_sums(const float* dy, const float* y, const float* z, const float* mu, const float* r, int M, int N, double* part, double* sums,
+                              float* db, float* dgamma, float* dbeta, hipStream_t st);
+hipError_t bn_launch_bwd_from_sums(const double* sums, int N, float* red, hipStream_t st);
 hipError_t bn_launch_momentum(float* stats, const float* batch, const int* hw, int B, int channels, double momentum, int unbiased, hipStream_t st);
 hipError_t bn_launch_install(const float* stats, int channels, float eps, float* keep, float* mean, float* istd, double* sd, hipStream_t st);
 

@@ -18,9 +18,10 @@ def _dist():
     return dist
 
 
-def init_from_env(backend=None):
+def init_from_env(backend=None, timeout=None):
     """Initialise the default process group from RANK / WORLD_SIZE / LOCAL_RANK / MASTER_* (torchrun contract).
-    Returns (rank, world, local_rank).  world == 1 needs no process group."""
+    Returns (rank, world, local_rank).  world == 1 needs no process group.  timeout: a
+    datetime.timedelta for the group's collectives (None: torch's default)."""
     import torch
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -30,7 +31,7 @@ def init_from_env(backend=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if backend is None:
             backend = "nccl" if torch.cuda.is_available() else "gloo"
-        kw = {}
+        kw = {} if timeout is None else {"timeout": timeout}
         if backend == "nccl":
             torch.cuda.set_device(local_rank)
             kw["device_id"] = torch.device("cuda", local_rank)
@@ -117,6 +118,147 @@ def reduce_sum(x):
     if dist.is_initialized() and dist.get_world_size() > 1:
         dist.all_reduce(x, op=dist.ReduceOp.SUM)
     return x
+
+
+class _DevicePointer(object):
+    """what ``torch.as_tensor`` needs to see device memory it does not own: the CUDA array interface (version 2) of ``count`` float64"""
+
+    def __init__(self, ptr, count):
+        self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": "<f8", "data": (int(ptr), False), "strides": None, "version": 2}
+
+
+def device_doubles(ptr, count, device):
+    """the ``count`` float64 at address ``ptr`` of ``device`` as a 1-D tensor: a view, no copy; valid while the memory is.  A CPU device
+    takes a host address (the gloo rehearsal of the callback on a host without a GPU)."""
+    import torch
+
+    if torch.device(device).type == "cpu":
+        import ctypes
+
+        import numpy as np
+
+        return torch.from_numpy(np.ctypeslib.as_array((ctypes.c_double * int(count)).from_address(int(ptr))))
+    return torch.as_tensor(_DevicePointer(ptr, count), device=device)
+
+
+DEFAULT_TIMEOUT_S = 300.0  # of a process group made here: a rank that never arrives raises on the others instead of hanging them
+
+
+class Reducer(object):
+    """The sums that join the ranks of data-parallel training (DESIGN.md "Data-parallel training"), over one process group.
+
+    ``nccl`` (RCCL): the all-reduce runs on the device tensor, on the current stream.  ``gloo``: the tensor is staged through ONE
+    reused pinned host buffer -- device to host (which waits for the stream), the host all-reduce, host to device on the stream --
+    gloo's own device support is not relied on.  A world of one rank is the identity unless ``HPE_FORCE_DIST`` is set
+    (``active``).  CPU tensors go straight to the group.
+
+    ``callback`` is the ``hpe_reduce_fn`` of ``HpeEngine.set_encoder_reduce``: it wraps the library's device buffer as a tensor
+    without a copy and sums it over the ranks.  An exception inside it is caught and kept, the callback returns nonzero (the library
+    call then fails with the layer's name), and ``reraise()`` -- which the engine calls once the library call has returned -- raises it.
+    ``counts`` tallies the collectives issued, by kind: "hook", "grad", "block", "broadcast"."""
+
+    def __init__(self, group=None, device=None):
+        import torch
+
+        from . import _lib
+
+        dist = _dist()
+        self.group = group
+        self.initialized = dist.is_available() and dist.is_initialized()
+        self.world = dist.get_world_size(group) if self.initialized else 1
+        self.rank = dist.get_rank(group) if self.initialized else 0
+        self.backend = dist.get_backend(group) if self.initialized else None
+        self.active = self.initialized and (self.world > 1 or _force_collectives())
+        self.device = torch.device(device) if device is not None else None
+        self.counts = {"hook": 0, "grad": 0, "block": 0, "broadcast": 0}
+        self._host = None
+        self._exc = None
+        self.callback = _lib.REDUCE_FN(self._hook)
+
+    @classmethod
+    def from_env(cls, backend=None, timeout_s=DEFAULT_TIMEOUT_S, device=None):
+        """``init_from_env`` with a finite timeout on the group it creates -> a Reducer on the default group"""
+        import datetime
+
+        init_from_env(backend, timeout=datetime.timedelta(seconds=float(timeout_s)))
+        return cls(device=device)
+
+    # ------------------------------------------------------------------ transport
+    def _staging(self, nbytes):
+        """the first ``nbytes`` of the pinned host buffer (grown, never shrunk), as uint8"""
+        import torch
+
+        if self._host is None or self._host.numel() < nbytes:
+            self._host = torch.empty(max(int(nbytes), 1 << 16), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        return self._host[:nbytes]
+
+    def _collective(self, t, fn):
+        """fn(tensor) on ``t`` in place: directly (CPU tensors, nccl) or through the staging buffer (a device tensor over gloo)"""
+        if not t.is_contiguous():
+            raise ValueError("Reducer: the tensor must be contiguous")
+        if not t.is_cuda or self.backend == "nccl":
+            fn(t)
+            return t
+        host = self._staging(t.numel() * t.element_size()).view(t.dtype).reshape(t.shape)
+        host.copy_(t)  # a blocking copy: waits for what the stream holds
+        fn(host)
+        t.copy_(host, non_blocking=True)  # stream-ordered; the next staging copy is ordered behind it on the same stream
+        return t
+
+    def _sum(self, t):
+        if self.active:
+            dist = _dist()
+            self._collective(t, lambda x: dist.all_reduce(x, op=dist.ReduceOp.SUM, group=self.group))
+        return t
+
+    # ------------------------------------------------------------------ the four uses
+    def sum_grad(self, flat):
+        """the flat gradient of one network, summed over the ranks in place: ONE all-reduce"""
+        self.counts["grad"] += 1
+        return self._sum(flat)
+
+    def sum_block(self, block):
+        """a small packed block of loss terms or counts, summed over the ranks in place: ONE all-reduce"""
+        self.counts["block"] += 1
+        return self._sum(block)
+
+    def broadcast(self, t, src=0):
+        """rank ``src``'s tensor into every rank's, in place"""
+        self.counts["broadcast"] += 1
+        if self.active:
+            dist = _dist()
+            src_global = dist.get_global_rank(self.group, src) if self.group is not None else src
+            self._collective(t, lambda x: dist.broadcast(x, src=src_global, group=self.group))
+        return t
+
+    def barrier(self):
+        if self.active:
+            _dist().barrier(group=self.group)
+
+    def _hook(self, user, ptr, count, stream):
+        import torch
+
+        try:
+            self.counts["hook"] += 1
+            if not self.active:
+                return 0
+            dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+            t = device_doubles(ptr, count, dev)
+            if not t.is_cuda or (stream or 0) == torch.cuda.current_stream(dev).cuda_stream:
+                self._sum(t)
+            else:
+                with torch.cuda.stream(torch.cuda.ExternalStream(stream or 0, device=dev)):
+                    self._sum(t)
+            return 0
+        except BaseException as e:  # noqa: B902  nothing may unwind through the C frames of the library
+            self._exc = e
+            return 1
+
+    def reraise(self):
+        """raise, once, what the callback caught"""
+        e, self._exc = self._exc, None
+        if e is not None:
+            raise e
 
 
 class ShardedPredictor(object):

@@ -729,6 +729,82 @@ class HpeEngine(object):
                                                               dy.data_ptr(), B, dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
         return dx, gl
 
+    # ------------------------------------------------------------------ data-parallel training: statistics over the batch of all ranks
+    def set_encoder_reduce(self, callback, global_batch=0, owner=None):
+        """hpe_encoder_set_reduce: from now on ``bn="batch"`` takes every layer's statistics over ``global_batch`` images: per layer the
+        local column sums [2, cout] (float64, on the device) go through ``callback(user, dev_ptr, count, stream) -> 0 or nonzero``, which
+        adds the other ranks' to them in place, ordered on the stream (``distributed.Reducer.callback``).  ``encoder_backward`` then
+        returns this rank's PARTIAL gradient in every entry: the sum over the ranks is the gradient of the global batch.  None clears
+        the hook.  owner: an object whose ``reraise()`` runs after every hooked library call, so that an exception the callback caught
+        surfaces once the call has returned.  The callback object is kept alive here."""
+        if callback is None:
+            _lib.check(self.lib.hpe_encoder_set_reduce(self._h, _lib.REDUCE_FN(), None, 0))
+            self._reduce_cb = self._reduce_owner = None
+            return
+        if not isinstance(callback, _lib.REDUCE_FN):
+            callback = _lib.REDUCE_FN(callback)
+        _lib.check(self.lib.hpe_encoder_set_reduce(self._h, callback, None, int(global_batch)))
+        self._reduce_cb, self._reduce_owner = callback, owner
+
+    def _check_hooked(self, rc):
+        """the result of a library call that may have run the reduce hook: the callback's own exception first"""
+        owner = getattr(self, "_reduce_owner", None)
+        if owner is not None:
+            owner.reraise()
+        _lib.check(rc)
+
+    def debug_bn_sums(self, idx, z):
+        """hpe_debug_bn_sums: z [B,hout,hout,cout] -> the column sums [2, cout] float64 = (sum z | sum z^2), in the library's order"""
+        torch = _torch()
+        z = _require_cuda_tensor(z, "z")
+        out = torch.empty((2, CONV_SPECS[idx].cout), dtype=torch.float64, device=self.tdev)
+        _lib.check(self.lib.hpe_debug_bn_sums(self._h, idx, z.data_ptr(), z.shape[0], out.data_ptr(), self._stream()))
+        return out
+
+    @staticmethod
+    def _sums_arg(sums, idx, name):
+        torch = _torch()
+        if not (isinstance(sums, torch.Tensor) and sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous()
+                and tuple(sums.shape) == (2, CONV_SPECS[idx].cout)):
+            raise ValueError("%s must be a contiguous CUDA float64 tensor [2, %d]" % (name, CONV_SPECS[idx].cout))
+        return sums
+
+    def debug_bn_finish(self, idx, sums, M, z, residual=None, relu=True):
+        """hpe_debug_bn_finish: the statistics of ``sums`` over M rows applied to the images of z -> (y, stats [2 * cout] = mu | var)"""
+        s = CONV_SPECS[idx]
+        z, sums = _require_cuda_tensor(z, "z"), self._sums_arg(sums, idx, "sums")
+        y, st = self._new(*z.shape), self._new(2 * s.cout)
+        r = _require_cuda_tensor(residual, "residual").data_ptr() if residual is not None else None
+        _lib.check(self.lib.hpe_debug_bn_finish(self._h, idx, sums.data_ptr(), int(M), z.data_ptr(), z.shape[0], r, int(relu), y.data_ptr(),
+                                                st.data_ptr(), self._stream()))
+        return y, st
+
+    def debug_bn_backward_sums(self, idx, z, y, dy, sums, M):
+        """hpe_debug_bn_backward_sums: -> [2, cout] float64 = (sum dz | sum dz * xhat) over the rows given, xhat from (sums, M)"""
+        torch = _torch()
+        z, dy, sums = _require_cuda_tensor(z, "z"), _require_cuda_tensor(dy, "dy"), self._sums_arg(sums, idx, "sums")
+        y = _require_cuda_tensor(y, "y") if y is not None else None
+        out = torch.empty((2, CONV_SPECS[idx].cout), dtype=torch.float64, device=self.tdev)
+        _lib.check(self.lib.hpe_debug_bn_backward_sums(self._h, idx, z.data_ptr(), y.data_ptr() if y is not None else None, dy.data_ptr(),
+                                                       z.shape[0], sums.data_ptr(), int(M), out.data_ptr(), self._stream()))
+        return out
+
+    def debug_bn_backward_finish(self, idx, x, z, y, dy, sums, bwd_sums, M, want_dx=True):
+        """hpe_debug_bn_backward_finish: the layer's backward on the rows given with the statistics of (sums, M) and the reduced
+        ``bwd_sums`` -> (dx or None, grad_layer = [kernel | bias = 0 | gamma | beta], each the partial of these rows)"""
+        s = CONV_SPECS[idx]
+        x, z, dy = _require_cuda_tensor(x, "x"), _require_cuda_tensor(z, "z"), _require_cuda_tensor(dy, "dy")
+        y = _require_cuda_tensor(y, "y") if y is not None else None
+        sums, bwd_sums = self._sums_arg(sums, idx, "sums"), self._sums_arg(bwd_sums, idx, "bwd_sums")
+        B = x.shape[0]
+        want_dx = want_dx and idx != 0
+        dx = self._new(B, s.hin, s.hin, s.cin) if want_dx else None
+        gl = self._new(s.kh * s.kw * s.cin * s.cout + 3 * s.cout)
+        _lib.check(self.lib.hpe_debug_bn_backward_finish(self._h, idx, x.data_ptr(), z.data_ptr(), y.data_ptr() if y is not None else None,
+                                                         dy.data_ptr(), B, sums.data_ptr(), bwd_sums.data_ptr(), int(M),
+                                                         dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
+        return dx, gl
+
     def encoder_params(self):
         """hpe_encoder_get_params: the live kernels, biases, gammas and betas as one flat CUDA tensor [resnet_spec.ENCODER_PARAM_FLOATS]"""
         out = self._new(ENCODER_PARAM_FLOATS)
@@ -775,7 +851,7 @@ class HpeEngine(object):
         images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))
         B = images.shape[0]
         out = self._new(B, 2048)
-        _lib.check(fn(self._h, images.data_ptr(), B, out.data_ptr(), self._stream()))
+        self._check_hooked(fn(self._h, images.data_ptr(), B, out.data_ptr(), self._stream()))
         return out
 
     def encoder_backward(self, images, grad_features, bn="frozen"):
@@ -789,7 +865,7 @@ class HpeEngine(object):
         if tuple(grad_features.shape) != (B, 2048):
             raise ValueError("grad_features must be [%d,2048], got %s" % (B, tuple(grad_features.shape)))
         g = self._new(ENCODER_PARAM_FLOATS)
-        _lib.check(fn(self._h, images.data_ptr(), B, grad_features.data_ptr(), g.data_ptr(), self._stream()))
+        self._check_hooked(fn(self._h, images.data_ptr(), B, grad_features.data_ptr(), g.data_ptr(), self._stream()))
         return g
 
     def debug_conv_backward(self, idx, x, y, dy, want_dx=True):

@@ -8,10 +8,18 @@ fixed, fp32) is in the same step, as in the reference (src/trainer.py:481): feat
 (hpe_encoder_set_params_dev).  ``encoder_bn="batch"`` is the reference's own mode (src/trainer.py:386, training=True): every BatchNorm
 normalises with the statistics of the batch, the gradient flows through them, and after the Adam steps the moving statistics follow the
 batch (hpe_encoder_update_stats on ``encoder_stats``, installed by hpe_encoder_set_stats_dev).
-``grad_features`` is returned either way."""
+``grad_features`` is returned either way.
+
+Data-parallel (DESIGN.md "Data-parallel training"): with ``reducer=`` (distributed.Reducer) and ``global_batch=`` G, ``step`` takes this
+rank's rows of a batch of G spread across the ranks.  Every loss term is the rank's SHARE of the global loss -- the keypoint numerator over
+the visible count of all ranks (all-reduced on the device before the forward), the mesh sum as it is, the critic's column sums over G --
+so that after ``loss.backward()`` ONE sum per flat gradient over the ranks is the gradient of the global batch, which every rank then
+steps with; BatchNorm takes its statistics over the G images (``HpeEngine.set_encoder_reduce``) and the moving statistics follow
+those.  The reported losses are the global values, from one packed all-reduce per step."""
 from __future__ import annotations
 
-from .ops import encoder_features, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas
+from .ops import (encoder_features, generator_critic_loss, kp_reprojection_loss, kp_reprojection_loss_share, kp_visible_count,
+                  mesh_reprojection_loss, regressor_thetas)
 
 GENERATOR_LR = 0.0001  # the reference's generator_lr (src/config.py:64-69)
 ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon
@@ -20,7 +28,7 @@ ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon
 class GeneratorTrainer(object):
     def __init__(self, engine, lr=GENERATOR_LR, betas=(0.9, 0.999), eps=ADAM_EPS, kpr_loss_weight=60.0, mr_loss_weight=0.001,
                  critic_loss_weight=0.01, dropout=0.5, generator=None, train_encoder=False, encoder_lr=None, encoder_bn="frozen",
-                 bn_momentum=0.99, bn_unbiased=True, optimizer="torch"):
+                 bn_momentum=0.99, bn_unbiased=True, optimizer="torch", reducer=None, global_batch=None):
         """engine: a finalized HpeEngine with a regressor, mean theta and SMPL (and a critic, for the critic term).  ``params`` is the
         flat parameter tensor (regressor_spec.flat_layout) the optimiser owns; ``regressor_spec.flat_to_params(params)`` gives the
         dict ``load_regressor`` / ``load_mean_theta`` take.  generator: the torch.Generator of the dropout draws.  train_encoder: also
@@ -31,12 +39,19 @@ class GeneratorTrainer(object):
         ``bn_momentum`` after every step (``bn_unbiased``: the batch variance times M / (M - 1)).  optimizer: "torch"
         (torch.optim.Adam, one per flat tensor) or "keras": ONE ``KerasAdam`` (optim.py: the reference's fused update in HIP) that owns
         the regressor's and, with ``train_encoder``, the encoder's tensor under one step count, as the reference's
-        ``generator_optimizer`` does; it has one rate, so an ``encoder_lr`` other than ``lr`` is refused."""
+        ``generator_optimizer`` does; it has one rate, so an ``encoder_lr`` other than ``lr`` is refused.  reducer / global_batch:
+        data-parallel training (the module's text); with ``encoder_bn="batch"`` the reducer's callback is installed as the engine's
+        reduce hook.  ``reducer=None`` is the single-process trainer, unchanged."""
         import torch
 
         if not 0.0 <= dropout < 1.0:
             raise ValueError("dropout must be in [0, 1)")
         self.engine = engine
+        self.reducer, self.global_batch = reducer, None
+        if reducer is not None:
+            if global_batch is None or int(global_batch) < 1:
+                raise ValueError("reducer= needs global_batch, the rows of all ranks together")
+            self.global_batch = int(global_batch)
         self.kpr_loss_weight, self.mr_loss_weight, self.critic_loss_weight = float(kpr_loss_weight), float(mr_loss_weight), float(critic_loss_weight)
         self.dropout = float(dropout)
         self.generator = generator
@@ -68,6 +83,8 @@ class GeneratorTrainer(object):
                 self.optimizer.add("encoder", self.encoder_params)
             else:
                 self.encoder_optimizer = torch.optim.Adam([self.encoder_params], lr=lr if encoder_lr is None else encoder_lr, betas=betas, eps=eps)
+        if reducer is not None and self.train_encoder and encoder_bn == "batch":
+            engine.set_encoder_reduce(reducer.callback, self.global_batch, owner=reducer)
 
     def draw_masks(self, B):
         """the dropout multipliers [2,B,1024] of one step: 0 with probability ``dropout``, else 1 / (1 - dropout); None without dropout"""
@@ -87,6 +104,14 @@ class GeneratorTrainer(object):
             return self.engine.smpl(theta, want=want)
         parts = [self.engine.smpl(theta[lo : lo + mb], want=want) for lo in range(0, theta.shape[0], mb)]
         return {k: torch.cat([p[k] for p in parts]) for k in want}
+
+    def _sum_grads(self, enc):
+        """data-parallel: each flat gradient summed over the ranks, one all-reduce per tensor, before the optimiser reads it"""
+        if self.reducer is None:
+            return
+        self.reducer.sum_grad(self.params.grad)
+        if enc:
+            self.reducer.sum_grad(self.encoder_params.grad)
 
     def step(self, images_or_features, kp_gt, seg_gts=None, use_critic=None, drop="draw"):
         """One generator update.  images_or_features: images [B,224,224,3] (the encoder runs without gradient) or features [B,2048];
@@ -116,6 +141,11 @@ class GeneratorTrainer(object):
             features = features.detach().clone().requires_grad_(True)
         thetas = regressor_thetas(eng, features, self.params, drop)
         S = thetas.shape[0]
+        red, G = self.reducer, self.global_batch
+        if red is not None:
+            if B > G:
+                raise ValueError("this rank's %d rows exceed global_batch %d" % (B, G))
+            count = red.sum_block(kp_visible_count(kp_gt))  # 2 * #visible of all ranks, before the forward; stays on the device
         kpr, mr, gc = [], [], []
         # kp2d / verts2d: batch_orth_proj_idrot / reproject_vertices of the stage, as outputs of the one hpe_smpl call (and of its backward)
         want = ("kp2d", "joints", "Rs") + (("verts2d",) if seg_gts is not None else ())
@@ -126,23 +156,25 @@ class GeneratorTrainer(object):
                 th = thetas[i] if last else thetas[i].detach()
                 o = self._smpl(th, want)
                 kp = o["kp2d"]
-                kpr.append(self.kpr_loss_weight * kp_reprojection_loss(kp_gt, kp))
+                kpr.append(self.kpr_loss_weight * (kp_reprojection_loss(kp_gt, kp) if red is None else kp_reprojection_loss_share(kp_gt, kp, count)))
                 if seg_gts is not None:
                     mr.append(self.mr_loss_weight * mesh_reprojection_loss(eng, seg_gts, o["verts2d"]))
                 if use_critic:
-                    gc.append(self.critic_loss_weight * generator_critic_loss(eng, o["joints"], th[:, 75:], o["Rs"]))
+                    gc.append(self.critic_loss_weight * generator_critic_loss(eng, o["joints"], th[:, 75:], o["Rs"], global_rows=G))
                 if last:
                     pred_kp = kp.detach()
                     loss = kpr[-1] + (mr[-1] if mr else 0.0) + (gc[-1] if gc else 0.0)
         if self.keras:
             self.optimizer.zero_grad()
             loss.backward()
+            self._sum_grads(enc)
             self.optimizer.step(only=None if enc or not self.train_encoder else ("regressor",))
         else:
             self.optimizer.zero_grad(set_to_none=True)
             if enc:
                 self.encoder_optimizer.zero_grad(set_to_none=True)
             loss.backward()
+            self._sum_grads(enc)
             self.optimizer.step()
         eng.set_regressor_params(self.params)
         if enc:
@@ -153,6 +185,9 @@ class GeneratorTrainer(object):
                 eng.update_encoder_stats(self.encoder_stats, self.bn_momentum, self.bn_unbiased)
                 eng.set_encoder_stats_dev(self.encoder_stats)
         det = lambda ts: [t.detach() for t in ts]  # noqa: E731
+        if red is not None:  # the ranks' shares into the losses of the global batch: one packed all-reduce for all of them
+            block = red.sum_block(torch.stack([t.detach().reshape(()) for t in kpr + mr + gc]))
+            kpr, mr, gc = list(block[:len(kpr)]), list(block[len(kpr):len(kpr) + len(mr)]), list(block[len(kpr) + len(mr):])
         return {"kpr_losses": det(kpr), "mr_losses": det(mr), "generator_critic_losses": det(gc), "pred_keypoints": pred_kp,
                 "generated_cams": thetas[S - 1, :, :3].detach(), "thetas": [thetas[i].detach() for i in range(S)],
                 "grad_features": features.grad}

@@ -20,6 +20,37 @@ def kp_reprojection_loss(kp_gt, kp_pred, scale=1.0, name="kp_reprojection_loss",
     return parts if return_parts else parts[2]
 
 
+def kp_visible_count(kp_gt):
+    """2 * #visible of kp_gt [N,K,3] as a one-element CUDA tensor (hpe_kp_loss's own count): what a data-parallel caller all-reduces
+    BEFORE the forward, so that every rank divides by the count of the global batch"""
+    return _engine.kp_loss_parts(kp_gt, kp_gt[..., :2].contiguous())[1:2].clone()
+
+
+def kp_loss_share(numerator, global_count):
+    """one rank's share of the keypoint loss: its numerator sum(vis * |d|) over the denominator of ALL ranks, 0 where nothing is visible
+    anywhere; the shares of the ranks add up to the loss of the global batch.  Plain torch, any device."""
+    import torch
+
+    g = global_count.reshape(()).to(numerator.dtype)
+    return torch.where(g > 0, numerator / torch.clamp(g, min=1.0), torch.zeros_like(g))
+
+
+def kp_reprojection_loss_share(kp_gt, kp_pred, global_count):
+    """``kp_loss_share`` of this rank's rows through the library (hpe_kp_loss); differentiable in a kp_pred that requires grad"""
+    import torch
+
+    if torch.is_grad_enabled() and isinstance(kp_pred, torch.Tensor) and kp_pred.requires_grad:
+        from .autograd import KpLossShareFunction
+
+        return KpLossShareFunction.apply(kp_gt, kp_pred, global_count)
+    return kp_loss_share(_engine.kp_loss_parts(kp_gt, kp_pred)[0], global_count)
+
+
+def critic_term_share(scores, global_rows):
+    """one rank's share of -reduce_sum(reduce_mean(scores, 0)): its column sums over the rows of ALL ranks.  Plain torch."""
+    return -(scores.sum(0) / global_rows).sum()
+
+
 def mesh_reprojection_loss(engine, seg_gts, silhouette_pred, name="mesh_reprojection_loss"):
     """seg_gts [N,H,W(,1)] (> 0 = silhouette), silhouette_pred [N,6890,2] pixels -> scalar
     sum_i bidirectional_dist_i / (3 + 6890)   (src/ops.py:117-137 with src/trainer.py:291 folded in:
@@ -50,10 +81,13 @@ def critic_scores(engine, joints, shapes, Rs):
     return engine.critic(joints, shapes, Rs)
 
 
-def generator_critic_loss(engine, joints, shapes, Rs, return_parts=False):
+def generator_critic_loss(engine, joints, shapes, Rs, return_parts=False, global_rows=None):
     """-reduce_sum(reduce_mean(critic scores, 0)) (src/trainer.py:309-313, before critic_loss_weight).  return_parts=True returns the
-    tensor [4] = (the three column sums, N) so that ranks can all-reduce before dividing (forward only), as kp_reprojection_loss does."""
+    tensor [4] = (the three column sums, N) so that ranks can all-reduce before dividing (forward only), as kp_reprojection_loss does.
+    global_rows: this rank's share of the term over a batch of that many rows spread across ranks (``critic_term_share``)."""
     scores = critic_scores(engine, joints, shapes, Rs)
+    if global_rows is not None:
+        return critic_term_share(scores, global_rows)
     if return_parts:
         import torch
 
@@ -97,7 +131,36 @@ def critic_gradient_penalty(grads):
     return sum((1.0 - g.mean(0).norm()) ** 2 for g in grads)
 
 
-def critic_wgan_loss(engine, real, fake, gp_weight=10.0, interp=None, generator=None, return_grad=True, per_row=False):
+def wgan_terms(wgan_sums, grad_sums, N, gp_weight=10.0):
+    """The critic's loss from the plain sums over N rows (``critic_wgan_loss``; a data-parallel caller passes the sums and the N of ALL
+    ranks): wgan = sum(wgan_sums) / N, penalty = sum over the four inputs of (1 - ||grad_sum / N||)^2, loss = wgan + gp_weight * penalty,
+    and tangents = d(gp_weight * penalty) / d(the penalised gradient of any one row), the same vector for every row.  Plain torch.
+    -> dict wgan, penalty, loss, norms, tangents (a list in the order of grad_sums)"""
+    wgan = wgan_sums.sum() / N
+    norms = [(s / N).norm() for s in grad_sums]
+    penalty = sum((1.0 - n) ** 2 for n in norms)
+    tangents = [((-2.0 * gp_weight / N) * (1.0 - n) / n) * (s / N) for n, s in zip(norms, grad_sums)]
+    return dict(wgan=wgan, penalty=penalty, loss=wgan + gp_weight * penalty, norms=norms, tangents=tangents)
+
+
+def pack_critic_sums(wgan_sums, grad_sums, N):
+    """the sums of ``critic_wgan_loss`` and N as ONE flat block, for one all-reduce"""
+    import torch
+
+    return torch.cat([wgan_sums.reshape(-1)] + [s.reshape(-1) for s in grad_sums] + [wgan_sums.new_full((1,), float(N))])
+
+
+def unpack_critic_sums(block, like):
+    """the inverse: ``like`` = the local grad_sums (for the shapes) -> (wgan_sums, grad_sums, rows as a one-element tensor)"""
+    out, pos = [], 3
+    for s in like:
+        out.append(block[pos:pos + s.numel()].reshape(s.shape))
+        pos += s.numel()
+    return block[:3], out, block[pos:pos + 1]
+
+
+def critic_wgan_loss(engine, real, fake, gp_weight=10.0, interp=None, generator=None, return_grad=True, per_row=False, reduce=None,
+                     global_rows=None):
     """The critic's loss of Trainer.train_step and its gradient with respect to the critic's weights (src/trainer.py:511-583):
 
         loss = wgan + gp_weight * penalty
@@ -115,7 +178,9 @@ def critic_wgan_loss(engine, real, fake, gp_weight=10.0, interp=None, generator=
 
     -> dict: loss, wgan, penalty (0-dim tensors), grad (flat [PARAM_FLOATS]; absent with return_grad=False), and the plain sums over
     the rows a data-parallel caller all-reduces before it divides and takes the norms: wgan_sums [3] (column sums of fake - real
-    scores), grad_sums (the four sums over the rows of the penalised gradients, Rs without the root) and N."""
+    scores), grad_sums (the four sums over the rows of the penalised gradients, Rs without the root) and N.
+
+    reduce (``Reducer.sum_block``) with global_rows: the data-parallel form, see ``_critic_wgan_reduced``."""
     import torch
 
     jr, br, Rr = real
@@ -138,6 +203,8 @@ def critic_wgan_loss(engine, real, fake, gp_weight=10.0, interp=None, generator=
     g = engine.critic_backward(ji, bi, Ri, None, want=_PENALTY_ORDER)
     g["Rs"] = g["Rs"][:, 1:]  # the root is no input of the critic: its gradient is zero
     grad_sums = [g[k].sum(0) for k in _PENALTY_ORDER]
+    if reduce is not None:
+        return _critic_wgan_reduced(engine, (j2, b2, R2), (ji, bi, Ri), wgan_sums, grad_sums, N, gp_weight, return_grad, per_row, reduce, global_rows)
     if per_row:
         norms = [g[k].reshape(N, -1).norm(dim=1) for k in _PENALTY_ORDER]
         penalty = sum(((1.0 - n) ** 2).mean() for n in norms)
@@ -153,4 +220,27 @@ def critic_wgan_loss(engine, real, fake, gp_weight=10.0, interp=None, generator=
         else:  # d(gp_weight * (1 - ||m||)^2) / d g_n with m the mean over the rows: the same vector for every row
             tangents = {k: ((-2.0 * gp_weight / N) * (1.0 - n) / n) * (s / N) for k, n, s in zip(_PENALTY_ORDER, norms, grad_sums)}
         out["grad"] = engine.critic_weight_grad(j2, b2, R2, grad_scores=gs) + engine.critic_weight_grad(ji, bi, Ri, tangents=tangents)
+    return out
+
+
+def _critic_wgan_reduced(engine, both, interpolated, wgan_sums, grad_sums, N, gp_weight, return_grad, per_row, reduce, global_rows):
+    """``critic_wgan_loss`` on this rank's N rows of ``global_rows`` spread across ranks: the sums and N go through ``reduce`` (ONE packed
+    all-reduce, in place) before the norms; loss, wgan and penalty are those of the global batch; grad_scores and the tangents divide
+    by the global row count, so ``grad`` is this rank's partial and the sum over the ranks the gradient of the global batch.
+    ``global_rows`` is the caller's host number (nothing reads the device); the reduced N comes back as ``rows`` for whoever checks."""
+    import torch
+
+    if per_row:
+        raise ValueError("per_row is not available with reduce")
+    if global_rows is None or int(global_rows) < N:
+        raise ValueError("reduce needs global_rows, the rows of all ranks (at least this rank's %d)" % N)
+    G = int(global_rows)
+    wgan_sums, grad_sums, rows = unpack_critic_sums(reduce(pack_critic_sums(wgan_sums, grad_sums, N)), grad_sums)
+    t = wgan_terms(wgan_sums, grad_sums, G, gp_weight)
+    out = dict(loss=t["loss"], wgan=t["wgan"], penalty=t["penalty"], wgan_sums=wgan_sums, grad_sums=grad_sums, N=G, rows=rows)
+    if return_grad:
+        j2, b2, R2 = both
+        gs = torch.full((2 * N, 3), 1.0 / G, dtype=torch.float32, device=j2.device)
+        gs[:N] = -1.0 / G
+        out["grad"] = engine.critic_weight_grad(j2, b2, R2, grad_scores=gs) + engine.critic_weight_grad(*interpolated, tangents=dict(zip(_PENALTY_ORDER, t["tangents"])))
     return out

@@ -148,11 +148,24 @@ def parse_mocap_example(payload):
 class RecordDataset:
     """Batches of parsed records from one or several files: iterating yields lists of ``batch_size`` values of ``parse`` (default
     ``parse_image_example``).  With ``shuffle_seed`` the records are read once and every pass walks a new permutation, drawn from
-    RandomState(shuffle_seed + pass); without it the files are streamed in order.  Host-only: nothing is decoded here."""
+    RandomState(shuffle_seed + pass); without it the files are streamed in order.  Host-only: nothing is decoded here.
 
-    def __init__(self, paths, batch_size, shuffle_seed=None, drop_last=True, parse=parse_image_example, verify=True):
+    shard=(rank, world): data-parallel training.  ``batch_size`` stays the GLOBAL batch: every rank walks the same global batches (the
+    same files, the same ``shuffle_seed``) and yields only its ``distributed.shard_bounds`` slice of each, cut before ``parse`` so that
+    only that slice is parsed; the ranks' batches, concatenated in rank order, are the single-process batch.  shard_unit: rows that
+    stay together (the mocap rows of one image: ``num_stage``); the bounds are taken over batch / shard_unit units."""
+
+    def __init__(self, paths, batch_size, shuffle_seed=None, drop_last=True, parse=parse_image_example, verify=True, shard=None, shard_unit=1):
         if int(batch_size) < 1:
             raise ValueError("batch_size must be >= 1")
+        if shard is not None:
+            rank, world = (int(v) for v in shard)
+            if world < 1 or not 0 <= rank < world:
+                raise ValueError("shard must be (rank, world) with 0 <= rank < world")
+            if int(shard_unit) < 1 or int(batch_size) % int(shard_unit):
+                raise ValueError("shard_unit must divide batch_size")
+            shard = (rank, world)
+        self.shard, self.shard_unit = shard, int(shard_unit)
         self.paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
         self.batch_size, self.shuffle_seed, self.drop_last, self.parse, self.verify = int(batch_size), shuffle_seed, bool(drop_last), parse, verify
         self._payloads, self._pass = None, 0
@@ -166,15 +179,33 @@ class RecordDataset:
         self._pass += 1
         return (self._payloads[i] for i in order)
 
+    def _mine(self, payloads):
+        """this rank's slice of one global batch (a short last batch is cut over the units it has)"""
+        from .distributed import shard_bounds
+
+        u = self.shard_unit
+        lo, hi = shard_bounds(len(payloads) // u, *self.shard)
+        return payloads[lo * u:hi * u]
+
     def __iter__(self):
+        if self.shard is None:
+            batch = []
+            for payload in self._ordered():
+                batch.append(self.parse(payload))
+                if len(batch) == self.batch_size:
+                    yield batch
+                    batch = []
+            if batch and not self.drop_last:
+                yield batch
+            return
         batch = []
         for payload in self._ordered():
-            batch.append(self.parse(payload))
+            batch.append(payload)
             if len(batch) == self.batch_size:
-                yield batch
+                yield [self.parse(p) for p in self._mine(batch)]
                 batch = []
         if batch and not self.drop_last:
-            yield batch
+            yield [self.parse(p) for p in self._mine(batch)]
 
 
 def _feature_bytes(value):

@@ -13,11 +13,18 @@ png_encode.py).  Scalars stay on the device between flushes; a writer is flushed
 bone-length evaluation runs with ``config.do_bone_evaluation`` (default False here so that the result keys stay as they were; the
 reference's default is True).
 
-Not here: ``draw_text`` on the panels, the best / worst drawings of ``validate_checkpoint``, multi-GPU training.
+Data-parallel (DESIGN.md "Data-parallel training"): under ``torchrun`` -- a process group is initialised, or ``config.distributed`` asks
+for ``distributed.init_from_env`` -- every rank builds the same Trainer on the device ``LOCAL_RANK``.  ``config.batch_size`` stays the
+GLOBAL batch G; rank r steps on its ``shard_bounds(G, r, world)`` rows (datasets built with ``RecordDataset(..., shard=(rank, world))``),
+BatchNorm statistics and gradients are those of the G rows, the replicas start from rank 0's tensors and stay bit-identical; only
+rank 0 saves, summarises and logs.
+
+Not here: ``draw_text`` on the panels, the best / worst drawings of ``validate_checkpoint``.
 ``generated_verts`` is not among ``train_step``'s result keys: drawing recomputes the vertices of the rows it shows from ``thetas``.
 ``use_kpr_loss`` decides, as in the reference, only whether the keypoint loss is logged: it is always minimised."""
 from __future__ import annotations
 
+import datetime
 import os
 import time
 
@@ -97,6 +104,24 @@ def run_training_loop(batches, train_step, num_images, batch_size, max_epoch, va
     return {"steps": step, "epochs": epoch, "saved": saved, "validations": validations}
 
 
+def rank_zero_only(rank, barrier=None, save=None, log=print, **hooks):
+    """The loop's side effects for rank ``rank`` of a data-parallel run, free of any engine: ``save`` runs on rank 0 only and EVERY rank
+    then waits at ``barrier()`` (nobody runs ahead of a checkpoint that is being written); the summary hooks (after_train_step,
+    after_val_step, after_epoch) and the log exist on rank 0 only.  -> the keyword arguments of ``run_training_loop`` for this rank"""
+    out = {"log": log if rank == 0 else (lambda *a, **k: None)}
+    if save is not None:
+        def save_all(epoch):
+            if rank == 0:
+                save(epoch)
+            if barrier is not None:
+                barrier()
+
+        out["save"] = save_all
+    if rank == 0:
+        out.update({k: v for k, v in hooks.items() if v is not None})
+    return out
+
+
 def _repeat(dataset):
     """batches of an iterable dataset, over and over (the reference's ``.repeat()``)"""
     while True:
@@ -121,13 +146,30 @@ class Trainer(object):
         mocap_dataset: a ``RecordDataset(..., parse=parse_mocap_example)`` of ``batch_size * num_stage`` rows or any iterable of lists
         of (pose [72], shape [10]).  ``config.num_images`` (default: counted once from the dataset) sets the epoch length.  generator:
         the torch.Generator (CUDA) of the dropout and interpolation draws; the augmentation draws come from ``config.augment_seed``.
-        validation_only: no trainers are built (``validate_checkpoint`` / ``val_step`` only)."""
+        validation_only: no trainers are built (``validate_checkpoint`` / ``val_step`` only).
+        Data-parallel: see the module's text; ``config.seed`` (default 0) + rank seeds the dropout and interpolation draws where no
+        generator is given, ``config.augment_seed`` + rank the augmentation; ``config.dist_backend`` / ``config.dist_timeout_s`` go to
+        ``Reducer.from_env``."""
         import torch
 
+        from . import distributed as D
         from .predictor import Predictor
 
         g = lambda name, default: getattr(config, name, default)  # noqa: E731
         self.config, self.log = config, log
+        self.reducer, self.rank, self.world, self.sharded = None, 0, 1, None
+        dist = D._dist()
+        if bool(g("distributed", False)) and not (dist.is_available() and dist.is_initialized()):
+            D.init_from_env(g("dist_backend", None), timeout=datetime.timedelta(seconds=float(g("dist_timeout_s", D.DEFAULT_TIMEOUT_S))))
+        if dist.is_available() and dist.is_initialized():
+            local = int(os.environ.get("LOCAL_RANK", "0"))
+            torch.cuda.set_device(local)
+            predictor_args.setdefault("device", local)
+            red = D.Reducer(device=torch.device("cuda", local))
+            if red.active:
+                self.reducer, self.rank, self.world = red, red.rank, red.world
+                if self.rank != 0:
+                    self.log = lambda *a, **k: None
         self.batch_size, self.max_epoch = int(g("batch_size", 8)), int(g("epoch", 125))
         self.generator_lr, self.critic_lr = float(g("generator_lr", GENERATOR_LR)), float(g("critic_lr", CRITIC_LR))
         self.kpr_loss_weight, self.mr_loss_weight = float(g("kpr_loss_weight", 60.0)), float(g("mr_loss_weight", 0.001))
@@ -137,9 +179,13 @@ class Trainer(object):
         self.val_step_size = int(g("validation_step_size", 50))
         self.train_from_checkpoint, self.checkpoint_dir = bool(g("train_from_checkpoint", False)), g("checkpoint_dir", None)
         self.model_dir = g("model_dir", None)
-        self.write_summaries = self.model_dir is not None and bool(g("write_summaries", True))
+        self.write_summaries = self.model_dir is not None and bool(g("write_summaries", True)) and self.rank == 0
         self.log_img_step, self.do_bone_evaluation = int(g("log_img_step", 1000)), bool(g("do_bone_evaluation", False))
-        self.show_these = show_rows(self.batch_size)
+        lo, hi = D.shard_bounds(self.batch_size, self.rank, self.world)
+        self.local_batch = hi - lo  # this rank's rows of a step; rank 0 has the largest shard
+        if self.local_batch < 1:
+            raise ValueError("batch_size %d leaves rank %d of %d without a row" % (self.batch_size, self.rank, self.world))
+        self.show_these = show_rows(self.local_batch)
         self.training_writer = self.val_writer = None
         self.dataset, self.mocap_dataset, self.val_dataset = dataset, mocap_dataset, val_dataset
         self.use_validation = self.use_validation and val_dataset is not None
@@ -148,19 +194,49 @@ class Trainer(object):
         self.num_stage = self.predictor.num_stage
         self.inital_theta = np.asarray(self.predictor.load_mean_param(), np.float32).reshape(1, 85)  # the reference's untrained theta_prev
         self.save_counter = 0
-        self._aug = torch.Generator().manual_seed(int(g("augment_seed", 0)))
+        self._aug = torch.Generator().manual_seed(int(g("augment_seed", 0)) + self.rank)
         self.generator = self.critic = None
+        if self.reducer is not None:
+            self.sharded = D.ShardedPredictor(self.predictor)
+            if generator is None:  # every rank its own draws
+                generator = torch.Generator(device=eng.tdev).manual_seed(int(g("seed", 0)) + self.rank)
         if validation_only:
             return
         if not self.encoder_only and not eng.has_critic:
             raise RuntimeError("Trainer needs critic weights to start from (critic_params=, config.critic_params, critic/... keys of the "
                                "weights, or a checkpoint with a discriminator) unless config.encoder_only is set")
-        eng.reserve_encoder_train(self.batch_size, batch_norm=True)
+        dp = {} if self.reducer is None else {"reducer": self.reducer}
+        dp_gen = dict(dp, global_batch=self.batch_size) if dp else {}
+        eng.reserve_encoder_train(D.shard_bounds(self.batch_size, 0, self.world)[1], batch_norm=True)  # the largest shard
         self.generator = GeneratorTrainer(eng, lr=self.generator_lr, kpr_loss_weight=self.kpr_loss_weight, mr_loss_weight=self.mr_loss_weight,
                                           critic_loss_weight=self.critic_loss_weight, generator=generator, train_encoder=True,
-                                          encoder_bn="batch", optimizer="keras")
+                                          encoder_bn="batch", optimizer="keras", **dp_gen)
         if not self.encoder_only:
-            self.critic = CriticTrainer(eng, lr=self.critic_lr, generator=generator, optimizer="keras")
+            self.critic = CriticTrainer(eng, lr=self.critic_lr, generator=generator, optimizer="keras", **dp)
+        self._sync_replicas()
+
+    def _sync_replicas(self):
+        """data-parallel: rank 0's flat tensors, moving statistics and optimiser state into every rank, and into the engines"""
+        import torch
+
+        red = self.reducer
+        if red is None or self.generator is None:
+            return
+        gen, eng = self.generator, self.engine
+        opts = [gen.optimizer] + ([self.critic.optimizer] if self.critic is not None else [])
+        with torch.no_grad():
+            for t in (gen.params, gen.encoder_params, gen.encoder_stats) + ((self.critic.params,) if self.critic is not None else ()):
+                red.broadcast(t.detach())
+            for opt in opts:
+                for slot in opt.slots.values():
+                    red.broadcast(slot["m"])
+                    red.broadcast(slot["v"])
+                red.broadcast(opt._ensure_state(gen.params))
+        eng.set_regressor_params(gen.params)
+        eng.set_encoder_params_dev(gen.encoder_params)
+        eng.set_encoder_stats_dev(gen.encoder_stats)
+        if self.critic is not None:
+            eng.set_critic_params(self.critic.params)
 
     # ------------------------------------------------------------------ steps
     def train_step(self, images, seg_gts, kp_gt, joints=None, shapes=None, Rs=None, drop="draw", interp=None):
@@ -178,7 +254,8 @@ class Trainer(object):
         if self.use_mesh_repro_loss:
             result["mr_losses"] = r["mr_losses"]
         if not self.encoder_only:
-            c = self.critic.step_from_thetas((joints, shapes, Rs), r["thetas"], interp=interp)
+            c = self.critic.step_from_thetas((joints, shapes, Rs), r["thetas"], interp=interp,
+                                             global_batch=self.batch_size if self.reducer is not None else None)
             result["generator_critic_losses"] = r["generator_critic_losses"]
             result["critic_penalty"], result["critic_network_loss"] = c["critic_penalty"], c["critic_network_loss"]
         if self.do_bone_evaluation:
@@ -192,8 +269,11 @@ class Trainer(object):
         return result
 
     def val_step(self, images, seg_gts, kp2d_gts):
-        return self.predictor.val_step(images, seg_gts, kp2d_gts, use_mesh_repro_loss=self.use_mesh_repro_loss,
-                                       kpr_loss_weight=self.kpr_loss_weight, mr_loss_weight=self.mr_loss_weight)
+        """data-parallel: this rank's rows (the validation dataset is sharded like the training one), the losses those of all ranks"""
+        kw = dict(use_mesh_repro_loss=self.use_mesh_repro_loss, kpr_loss_weight=self.kpr_loss_weight, mr_loss_weight=self.mr_loss_weight)
+        if self.sharded is not None:
+            return self.sharded.val_step(images, seg_gts, kp2d_gts, presharded=True, **kw)
+        return self.predictor.val_step(images, seg_gts, kp2d_gts, **kw)
 
     # ------------------------------------------------------------------ data
     def _load_images(self, records, augment=True):
@@ -370,10 +450,13 @@ class Trainer(object):
             hooks = {"after_train_step": lambda s, r: self._summarize_train_step(s, r, last["train"]),
                      "after_val_step": lambda s, r: self._summarize_val_step(s, r, last["val"]),
                      "after_epoch": lambda epoch: self._flush_writers()}
+        side = dict(hooks, save=lambda epoch: self.save(), log=self.log)
+        if self.reducer is not None:
+            side = rank_zero_only(self.rank, barrier=self.reducer.barrier, **side)
         try:
             out = run_training_loop(self._batches(), step, self._num_images(), self.batch_size, self.max_epoch,
                                     val_step=val if self.use_validation else None, validation_step_size=self.val_step_size,
-                                    save=lambda epoch: self.save(), save_every=save_every, summarize=self._summarize, log=self.log, **hooks)
+                                    save_every=save_every, summarize=self._summarize, **side)
         finally:
             for w in (self.training_writer, self.val_writer):
                 if w is not None:
@@ -498,6 +581,7 @@ class Trainer(object):
             if "no optimiser state" not in str(e):
                 raise
             self.log("no optimiser state in %s: starting fresh moments" % prefix)
+            self._sync_replicas()
             return prefix
         go = st.get("generator_optimizer")
         if go is not None and go["encoder"] is not None and go["regressor"] is not None:
@@ -507,4 +591,5 @@ class Trainer(object):
             self.critic.optimizer.load_state_dict({"iterations": do["iter"], "slots": {"critic": do["critic"]}}, hyper=False)
         if st["save_counter"] is not None:
             self.save_counter = int(st["save_counter"])
+        self._sync_replicas()
         return prefix

@@ -37,6 +37,7 @@ extern "C" {
 #define HPE_ERR_HIP 2       /* a HIP runtime call failed */
 #define HPE_ERR_STATE 3     /* call order violated (e.g. forward before finalize) */
 #define HPE_ERR_NO_DEVICE 4 /* no gfx950 device visible */
+#define HPE_ERR_REDUCE 5    /* the reduce hook of hpe_encoder_set_reduce reported a failure */
 
 #define HPE_NUM_CONV 53      /* ResNet-50 v1 conv layers, order of hpe_conv_layer_name() */
 #define HPE_NUM_DENSE 3      /* RegressionNetwork: 2133->1024->1024->85 */
@@ -488,6 +489,45 @@ int hpe_debug_encoder_stash_raw(hpe_ctx* ctx, int idx, float* out_dev, void* str
 int hpe_debug_encoder_batch_stats(hpe_ctx* ctx, float* out_dev, void* stream);
 /* For tests: the pixel slices the column sums of layer idx are cut into at batch B (host code; -1 for an idx or B out of range). */
 int hpe_debug_encoder_bn_slices(int idx, int B);
+
+/* -- data-parallel training: the batch statistics over the batch of ALL ranks --
+ * Rank r holds B_r of the G images of a step.  A reduce hook joins the ranks: it adds `count` doubles at dev_buf (device memory) over
+ * the ranks, in place, ordered on `stream`, and returns 0, or nonzero for a failure.  It is called from inside the library call, on
+ * the calling thread, and may run any host code (an all-reduce of a process group, say); it must not synchronise the device unless
+ * its transport needs that. */
+typedef int (*hpe_reduce_fn)(void* user, double* dev_buf, long long count, void* stream);
+/* hpe_encoder_set_reduce(ctx, fn, user, G): from now on hpe_encoder_forward_batchnorm and hpe_encoder_backward_batchnorm take every
+ * layer's statistics over G * hout * hout rows.  Per layer the forward adds its local column sums (sum z | sum z^2, the order of the
+ * one-rank reduction) into [2][cout] doubles, calls fn on them and finishes mu, var and r from the reduced sums with the formulas of the
+ * one-rank path; the backward does the same with (sum dz | sum dz * xhat) and divides by the global M in dzraw: 2 * 53 hook calls per
+ * backward (its own forward included).  grad_flat stays this rank's PARTIAL in every entry -- dgamma and dbeta are written from the
+ * local sums, dW from the local rows, db is 0 -- so that ONE sum over the ranks of the whole flat tensor is the gradient of the
+ * global batch.  hpe_encoder_update_stats then uses M = G * hout * hout for the unbiased factor of statistics such a call left.
+ * With an identity hook and G = B every result has the bits of the path without a hook.  fn == NULL clears the hook (G is ignored):
+ * every call is again, bit for bit, what it was.  The one-layer debug calls never call the hook.
+ * A hook failure ends the walk: HPE_ERR_REDUCE, hpe_last_error() names the layer; the outputs are then undefined.  With a hook set, a
+ * call on a stream that is being captured is refused (HPE_ERR_STATE): the hook is host code.  B > G is refused (HPE_ERR_INVALID).  No
+ * allocation: the reduce buffers are part of the reserve (hpe_encoder_train_ws_floats_batchnorm counts them).
+ * HPE_ERR_INVALID for a NULL ctx or, with fn, G outside [1, 65536]; HPE_ERR_STATE before hpe_encoder_train_reserve_batchnorm. */
+int hpe_encoder_set_reduce(hpe_ctx* ctx, hpe_reduce_fn fn, void* user, int global_batch);
+/* The two halves of one layer's reductions for tests, so that the arithmetic of a layer split over ranks can be checked on one device
+ * (sums of the parts added on the host).  All of them leave the statistics of the last whole-network call alone.
+ * hpe_debug_bn_sums: sums_out_dev [2][cout] doubles = (sum z | sum z^2) over the B * hout * hout rows of z_dev.
+ * hpe_debug_bn_finish: mu, var, r from sums_dev over M rows (the caller's M: the rows of all parts), stats_out_dev [2 * cout] = mu |
+ * var, and y_dev = act(BN(z_dev) (+ residual_dev)) of the B images given.
+ * hpe_debug_bn_backward_sums: with mu and r from (sums_dev, M) as above, sums_out_dev [2][cout] doubles = (sum dz | sum dz * xhat)
+ * over the rows given (y_dev NULL: no activation, dz = dy).
+ * hpe_debug_bn_backward_finish: the layer's backward on the rows given, with the statistics of (sums_dev, M) and the reduced
+ * bwd_sums_dev: grad_layer_dev = [kernel | bias = 0 | gamma | beta], each the PARTIAL of these rows, and dx_dev (NULL: not computed;
+ * NULL for idx 0).  HPE_ERR_INVALID for a bad idx, a NULL pointer, B outside the batch-norm reserve or M < B * hout * hout. */
+int hpe_debug_bn_sums(hpe_ctx* ctx, int idx, const float* z_dev, int B, double* sums_out_dev, void* stream);
+int hpe_debug_bn_finish(hpe_ctx* ctx, int idx, const double* sums_dev, long long M, const float* z_dev, int B, const float* residual_dev, int relu,
+                        float* y_dev, float* stats_out_dev, void* stream);
+int hpe_debug_bn_backward_sums(hpe_ctx* ctx, int idx, const float* z_dev, const float* y_dev, const float* dy_dev, int B, const double* sums_dev,
+                               long long M, double* sums_out_dev, void* stream);
+int hpe_debug_bn_backward_finish(hpe_ctx* ctx, int idx, const float* x_dev, const float* z_dev, const float* y_dev, const float* dy_dev, int B,
+                                 const double* sums_dev, const double* bwd_sums_dev, long long M, float* dx_dev, float* grad_layer_dev,
+                                 void* stream);
 
 /* Both reprojection losses of all n_stage IEF stages in ONE call -- what Trainer.val_step evaluates per step
  * (src/trainer.py:274-296): the work that depends only on seg_gts (tf.where compaction, src/trainer.py:291;
