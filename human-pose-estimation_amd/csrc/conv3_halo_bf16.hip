@@ -33,20 +33,10 @@
 #include <type_traits>
 
 #include "hpe_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(4))) float* cfloat_p;
-typedef const __attribute__((address_space(4))) f32x4* cf32x4_p;
+#include "lds_dma.h"
 
 namespace {
 
-__device__ __forceinline__ void dma16(const void* src, void* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // Fragment reads are inline asm with COUNTED lgkmcnt waits.  hipcc never emits a counted lgkmcnt in a kernel that issues LDS-DMA inside
 // the loop (a global_load_lds is a FLAT-encoded instruction that touches LDS; LLVM's waitcnt pass then treats the counter as unordered
 // and falls back to lgkmcnt(0) -- checked on a six-line kernel).  lgkmcnt(0) in front of the multiplies of a group also waits for the
@@ -66,20 +56,6 @@ __device__ __forceinline__ bf16x8 lds_read16(unsigned addr) {
 #define HPE_LGKM_WAIT3(N, a, b, c) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(a), "+v"(b), "+v"(c))
 #define HPE_LGKM_WAIT12(N, a, b, c, d, e, f, g, h, i, j, k, l) \
     asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h), "+v"(i), "+v"(j), "+v"(k), "+v"(l))
-
-// all but the wave's n youngest vector-memory operations are done; n is a compile-time constant after unrolling
-__device__ __forceinline__ void wait_dma_leaving(int n) {
-    switch (n) {
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;  // 0, and anything unforeseen: over-waiting is safe
-    }
-}
 
 // HW = map height = width, CIN = input channels, BN = output channels per workgroup, BM = pixels per workgroup (BM / 32 waves),
 // NSW = weight ring depth

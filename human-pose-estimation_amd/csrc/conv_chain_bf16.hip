@@ -24,56 +24,37 @@
 //     each and are requested as soon as the previous chunk has released the slot.
 //   * every wave issues a QUARTER of every DMA group and of the t3 stores (one loader wave only reaches ~25 GB/s; a version with
 //     dedicated loader waves was slower), so all four waves hold the same queue, and every barrier is preceded by a COUNTED vmcnt
-//     wait that names exactly what may stay in flight behind the youngest thing the barrier publishes (vmcnt is per wave and counts
-//     LDS-DMA, loads and stores together, in issue order); the issue order is fixed in the prologue comment below.  On the last,
+//     wait that names exactly what may stay in flight behind the youngest thing the barrier publishes (chain_wait_leaving below, lds_barrier
+//     of lds_dma.h: a __syncthreads() after the in-place epilogue would bring a vmcnt(0) and make the waves wait for the residual chunk
+//     and the weight slot they have only just requested); the issue order is fixed in the prologue comment below.  On the last,
 //     partial tile the counts are not exact (skipped stores) and every wait drains the queue.
-//   * every wait in front of a barrier that publishes LDS-DMA data is written out: hipcc's __syncthreads() only waits for lgkmcnt
-//     behind some DMA patterns and for vmcnt(0) behind others (rounds 3-4).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "hpe_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-// per-channel scale / shift are read through the CONSTANT address space: the address is wave-uniform, so the loads become s_load (the
-// kernel also stores to global memory, which makes hipcc fall back to per-lane global_load for plain pointers -- those would queue
-// behind the LDS-DMA in flight, vmcnt counts in issue order)
-typedef const __attribute__((address_space(4))) float* cfloat_p;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(4))) f32x4* cf32x4_p;
-
-#include "bf16_rows.h"
+#include "lds_dma.h"
 
 namespace {
 
-__device__ __forceinline__ void dma16(const void* src, void* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-// The same with the non-temporal cache policy (aux bit 1) for the residual, which is read exactly once; the t3 rows (4C wide, next read a
+// The residual, which is read exactly once, comes in with the non-temporal cache policy (dma16_nt); the t3 rows (4C wide, next read a
 // whole 3x3 layer later) are stored non-temporal too.  What that buys is cache room for the C-wide u1 rows, which the next launch (the
 // 3x3 layer) reads: A/B on one box (tools/chain_nt_ab.sh, -DHPE_CHAIN_NO_NT = plain policy): res2c_branch2b 0.109 -> 0.097 ms, the chained
 // launches themselves 0.200 -> 0.195 / 0.132 -> 0.129 ms, bf16 step 69.4-69.5 k -> 70.1-70.8 k img/s.
-__device__ __forceinline__ void dma16_nt(const void* src, void* lds_dst) {
+// (the switch stays in this file: conv_chain_f32.hip uses dma16_nt too and never read it)
+__device__ __forceinline__ void dma16_res(const void* src, void* lds_dst) {
 #ifndef HPE_CHAIN_NO_NT
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 2);
+    dma16_nt(src, lds_dst);
 #else
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
+    dma16(src, lds_dst);
 #endif
 }
 
-// Barriers are written out: __syncthreads() is a workgroup fence + s_barrier, and behind pending LDS-DMA hipcc puts a vmcnt(0) in
-// front of some of them (here: the one after the in-place epilogue, which would make the waves wait for the residual chunk and the
-// weight slot they have only just requested) and only lgkmcnt(0) in front of others.  lds_barrier: LDS traffic of this wave is done, DMAs stay in flight;
-// the caller adds wait_dma() where the barrier publishes this wave's LDS-DMA data.
-__device__ __forceinline__ void wait_dma() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// counted wait: all but the wave's n youngest vector-memory operations (LDS-DMA, loads and stores count together, in issue order) are
-// done.  n is a compile-time constant after unrolling; inline asm needs an immediate.
-__device__ __forceinline__ void wait_dma_leaving(int n, bool exact_counts) {
+// The counted wait of this kernel keeps its own form (two arguments, its own case list): through wait_dma_leaving of lds_dma.h two of the
+// four instantiations come out with other instructions (profiles/lds_dma_device_code.txt).  exact_counts: full tiles only, elsewhere
+// every wait drains the queue.  A count outside the list would quietly become vmcnt(0): the kernel's static_assert names every count.
+constexpr bool chain_count_provided(int n) { return n == 0 || n == 2 || n == 4 || n == 6 || n == 8 || n == 10; }
+__device__ __forceinline__ void chain_wait_leaving(int n, bool exact_counts) {
     if (!exact_counts) n = 0;
     switch (n) {
         case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
@@ -81,7 +62,7 @@ __device__ __forceinline__ void wait_dma_leaving(int n, bool exact_counts) {
         case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
         case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
         case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;  // 0, and anything unforeseen: over-waiting is safe
+        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;  // 0
     }
 }
 
@@ -111,6 +92,8 @@ __global__ __launch_bounds__(BM * 4, BM == 128 ? 2 : (C2 > 0 ? 3 : 2)) void chai
     static_assert(C % 64 == 0 && C2 % 64 == 0 && C4 % NC == 0 && (NC == 64 || NC == 128) && CP % 64 == 0 && (BM == 64 || BM == 128), "geometry");
     static_assert(NC % (8 * NW) == 0 && CP % (8 * NW) == 0 && (BM * NC / 8) % NTHR == 0 && (BM * CP / 8) % NTHR == 0, "every wave issues an equal share");
     static_assert(QBUFS >= 1 && QBUFS <= NCH && (!HAS_RES || QBUFS * QBYTES == 32768), "residual ring");
+    static_assert(chain_count_provided(WIB + (QBUFS - 1) * RI) && chain_count_provided(ST) && chain_count_provided((QBUFS - 1) * RI) &&
+                  chain_count_provided(RI), "a counted wait of this kernel is not in chain_wait_leaving's list");
     static_assert(KSA * SLAB >= (CP / 64) * SLAB, "the u1 tile reuses the t2 tile's space");
     // identity blocks: two workgroups per CU (72-80 KB each, ~40 KB of HBM requests in flight per workgroup).  The conv_block form has no
     // residual ring to keep in flight (24 KB per workgroup: the [t2 | x] tile and the first weight slots), so it is built for THREE
@@ -167,7 +150,7 @@ __global__ __launch_bounds__(BM * 4, BM == 128 ? 2 : (C2 > 0 ? 3 : 2)) void chai
         for (int s = 0; s < KSB; ++s)
 #pragma unroll
             for (int i = 0; i < 2; ++i)
-                dma16_nt(RESb + (c * NC + s * 64) * 2 + off_res[i], lds + Q_OFF + (c % QBUFS) * QBYTES + s * SLAB + (wave + NW * i) * 1024);
+                dma16_res(RESb + (c * NC + s * 64) * 2 + off_res[i], lds + Q_OFF + (c % QBUFS) * QBYTES + s * SLAB + (wave + NW * i) * 1024);
     };
     auto issue_wa = [&](int c) {  // W2c rows [c * NC, + NC), all KSA k-slabs -> slot A
 #pragma unroll
@@ -230,7 +213,7 @@ __global__ __launch_bounds__(BM * 4, BM == 128 ? 2 : (C2 > 0 ? 3 : 2)) void chai
         const int qb = c % QBUFS;
         // ---- barrier 1: the GEMM-A weights and the residual of this chunk (and the t2 tile when c == 0) have landed -- the youngest of
         //      them is A(c); what was issued after it stays in flight -- and every wave is out of chunk c - 1.
-        wait_dma_leaving(c == 0 ? WIB + (QBUFS - 1) * RI : ST, full_tile);
+        chain_wait_leaving(c == 0 ? WIB + (QBUFS - 1) * RI : ST, full_tile);
         lds_barrier();
         if (c > 0) issue_wb(c);                                      // slot B: GEMM-B of chunk c - 1 is done
         if (HAS_RES && c > 0 && c - 1 + QBUFS < NCH) issue_res(c - 1 + QBUFS);  // Q[(c - 1) % QBUFS]: read and stored
@@ -286,7 +269,7 @@ __global__ __launch_bounds__(BM * 4, BM == 128 ? 2 : (C2 > 0 ? 3 : 2)) void chai
         }
         // ---- barrier 2: Q[qb] is the t3 tile of this chunk; the GEMM-B weights have landed (only residual chunks are younger); GEMM-A
         //      is done everywhere
-        wait_dma_leaving(c == 0 ? (QBUFS - 1) * RI : (c - 1 + QBUFS < NCH ? RI : 0), full_tile);
+        chain_wait_leaving(c == 0 ? (QBUFS - 1) * RI : (c - 1 + QBUFS < NCH ? RI : 0), full_tile);
         lds_barrier();
         if (c + 1 < NCH) issue_wa(c + 1);  // slot A is free
 

@@ -18,29 +18,9 @@
 #include <stdint.h>
 
 #include "hpe_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(4))) float* cfloat_p;
-typedef const __attribute__((address_space(4))) f32x4* cf32x4_p;
+#include "lds_dma.h"
 
 namespace {
-
-__device__ __forceinline__ void dma16(const void* src, void* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-__device__ __forceinline__ void dma16_nt(const void* src, void* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 2);
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void wait_dma_leaving(int n, bool exact_counts) {
-    if (!exact_counts) n = 0;
-    switch (n) {
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
 
 template <int C, int CP>
 __global__ __launch_bounds__(256, 2) void chain_expand_reduce_f32_kernel(ChainArgsF32 p) {
@@ -54,7 +34,6 @@ __global__ __launch_bounds__(256, 2) void chain_expand_reduce_f32_kernel(ChainAr
     constexpr int RI = KSB * 2, WIB = KSB * CP / 32, ST = NC / 16;  // per-wave instruction counts: residual chunk, GEMM-B weights, t3 stores
     static_assert(C == 64 && CP == 64, "stage 2 only: one 32-channel block per wave in both GEMMs");
     static_assert(QBUFS == 2 && NCH == 4 && LDS_BYTES <= 80 * 1024, "geometry");
-    static_assert(RI == 4 && WIB == 4 && ST == 4, "the counted waits below know 0 / 4 / 8 only");
 
     __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
 
@@ -136,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void chain_expand_reduce_f32_kernel(ChainAr
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         const int qb = c % QBUFS;
-        wait_dma_leaving(c == 0 ? WIB + (QBUFS - 1) * RI : ST, full_tile);
+        wait_dma_leaving(!full_tile ? 0 : (c == 0 ? WIB + (QBUFS - 1) * RI : ST));
         lds_barrier();
         if (c > 0) issue_wb(c);
         if (c > 0 && c - 1 + QBUFS < NCH) issue_res(c - 1 + QBUFS);
@@ -177,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void chain_expand_reduce_f32_kernel(ChainAr
                 *reinterpret_cast<f32x4*>(qp) = o;
             }
         }
-        wait_dma_leaving(c == 0 ? (QBUFS - 1) * RI : (c - 1 + QBUFS < NCH ? RI : 0), full_tile);
+        wait_dma_leaving(!full_tile ? 0 : (c == 0 ? (QBUFS - 1) * RI : (c - 1 + QBUFS < NCH ? RI : 0)));
         lds_barrier();
         if (c + 1 < NCH) issue_wa(c + 1);
 

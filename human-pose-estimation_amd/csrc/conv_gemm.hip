@@ -33,6 +33,7 @@
 #include "conv_gemm_common.h"
 #include "gemm_contract.h"
 #include "hpe_internal.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -161,22 +162,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 2) void conv_gemm_f32_dma
             } else {
                 src = p.x + (arow[i].base + sp.off);
             }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(lds + buf + (NW * i + wave) * 8 * BK), 16, 0, 0);
+            dma16(src, lds + buf + (NW * i + wave) * 8 * BK);
         }
 #pragma unroll
-        for (int i = 0; i < BP; ++i) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc[i] + slab * BK),
-                                             (__attribute__((address_space(3))) void*)(lds + buf + (BM + (NW * i + wave) * 8) * BK), 16, 0,
-                                             0);
-        }
+        for (int i = 0; i < BP; ++i) dma16(wsrc[i] + slab * BK, lds + buf + (BM + (NW * i + wave) * 8) * BK);
     };
 
     issue_dma(ks0, 0);
-    // The wait for the LDS-DMA is WRITTEN OUT in front of every barrier that publishes DMA'd data (here and at the end of the loop body):
-    // __syncthreads() alone is a workgroup fence + s_barrier, and whether hipcc adds a vmcnt wait to it depends on the control flow around
-    // the DMA issue (round 3: conv_wino4.hip got lgkmcnt only and raced).  tools/isa_lint.py / tests/test_isa_lint.py check the ISA.
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    wait_counts<0>();  // written out in front of every barrier that publishes DMA'd data (lds_dma.h): slab ks0 has landed
     __syncthreads();
 
     for (int s = ks0; s < ks1; ++s) {
@@ -201,7 +194,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 2) void conv_gemm_f32_dma
                     for (int j = 0; j < NT; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][ks], fb[j][ks], acc[i][j], 0, 0, 0);
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's part of slab s + 1 has landed (see above)
+        wait_counts<0>();  // this wave's part of slab s + 1 has landed
         __syncthreads();
     }
 

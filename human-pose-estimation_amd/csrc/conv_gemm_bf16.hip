@@ -12,8 +12,7 @@
 #include "conv_gemm_common.h"
 #include "gemm_contract.h"
 #include "hpe_internal.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "lds_dma.h"
 
 namespace {
 
@@ -136,15 +135,10 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 || BM * BN >= 256 * 128) ? (W
             } else {
                 src = X + (arow[i].base + sp.off);
             }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(lds + buf + (NW * i + wave) * 8 * RF), 16, 0, 0);
+            dma16(src, lds + buf + (NW * i + wave) * 8 * RF);
         }
 #pragma unroll
-        for (int i = 0; i < BP; ++i) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc[i] + slab * BKE),
-                                             (__attribute__((address_space(3))) void*)(lds + buf + (BM + (NW * i + wave) * 8) * RF), 16, 0,
-                                             0);
-        }
+        for (int i = 0; i < BP; ++i) dma16(wsrc[i] + slab * BKE, lds + buf + (BM + (NW * i + wave) * 8) * RF);
     };
 
     // ---- ring of NS slab buffers: slabs s+1 .. s+NS-1 are in flight while slab s is multiplied
@@ -168,12 +162,10 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 || BM * BN >= 256 * 128) ? (W
             // this wave's part of slab s has landed once at most min(NS-2, S-1-s) younger slabs are outstanding; the barrier
             // extends that to every wave's part, and tells that every wave is done reading the buffer of slab s-1
             const int ahead = (S - 1 - s < NS - 2) ? S - 1 - s : NS - 2;
-            if (ahead <= 0) HPE_WAIT_VMCNT(0);
-            else if (ahead == 1) HPE_WAIT_VMCNT(NDMA);
-            else HPE_WAIT_VMCNT(2 * NDMA);
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            if (ahead <= 0) wait_counts<0>();
+            else if (ahead == 1) wait_counts<NDMA>();
+            else wait_counts<2 * NDMA>();
+            bare_barrier();
             if (s + NS - 1 < S) {
                 slab_advance<MODE, BKE, 2>(p, sp);
                 issue_dma(s + NS - 1, nxt);

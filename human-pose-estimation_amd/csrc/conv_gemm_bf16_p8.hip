@@ -36,8 +36,7 @@
 #include "conv_gemm_common.h"
 #include "gemm_contract.h"
 #include "hpe_internal.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "lds_dma.h"
 
 namespace {
 
@@ -187,8 +186,7 @@ __global__ __launch_bounds__(P8_THREADS, 1) void conv_gemm_bf16_p8_kernel(GemmAr
             } else {
                 src = live ? static_cast<const void*>(X + (arow[d].base + off)) : static_cast<const void*>(p.zero);
             }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(lds + buf * P8_BUF + (64 * d + wave * 8) * RF), 16, 0, 0);
+            dma16(src, lds + buf * P8_BUF + (64 * d + wave * 8) * RF);
         }
     };
     auto issue_b = [&](int h, int kt, int buf) {
@@ -197,8 +195,7 @@ __global__ __launch_bounds__(P8_THREADS, 1) void conv_gemm_bf16_p8_kernel(GemmAr
         for (int u = 0; u < 2; ++u) {
             const int d = 2 * h + u;
             const void* src = live ? static_cast<const void*>(wsrc[d] + kt * BKE) : static_cast<const void*>(p.zero);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(lds + buf * P8_BUF + (P8_BM + 64 * d + wave * 8) * RF), 16, 0, 0);
+            dma16(src, lds + buf * P8_BUF + (P8_BM + 64 * d + wave * 8) * RF);
         }
     };
 
@@ -241,10 +238,10 @@ __global__ __launch_bounds__(P8_THREADS, 1) void conv_gemm_bf16_p8_kernel(GemmAr
     };
     // the two barriers of a phase with the counted wait in front of the first one
     auto sync_loaded = [&]() {
-        HPE_WAIT_VMCNT(8);
+        wait_counts<8>();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
-        HPE_WAIT_LGKM0();
+        wait_counts<WAIT_NONE, 0>();
         __builtin_amdgcn_sched_barrier(0);
     };
     auto sync_done = [&]() {
@@ -260,7 +257,7 @@ __global__ __launch_bounds__(P8_THREADS, 1) void conv_gemm_bf16_p8_kernel(GemmAr
     issue_a(1, ks0, 0);
     issue_a(0, ks0 + 1, 1);
     issue_b(0, ks0 + 1, 1);
-    HPE_WAIT_VMCNT(8);  // A0, B0 of the first k-tile have landed (this wave's part; the barrier extends it to every wave's)
+    wait_counts<8>();  // A0, B0 of the first k-tile have landed (this wave's part; the barrier extends it to every wave's)
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();  // stagger: the second wave group runs one barrier behind the first
@@ -300,7 +297,7 @@ __global__ __launch_bounds__(P8_THREADS, 1) void conv_gemm_bf16_p8_kernel(GemmAr
         }
     }
     if (wr == 0) __builtin_amdgcn_s_barrier();  // pairs with the second group's last barrier
-    HPE_WAIT_VMCNT(0);  // the zero-page DMAs of the tail have landed before the epilogue reuses the LDS
+    wait_counts<0>();  // the zero-page DMAs of the tail have landed before the epilogue reuses the LDS
 
     if (p.split_k > 1) {
         // split-K slice: raw accumulators -> workspace [tile][slice][block 8][register quad 4][thread 512] (16 B per lane, coalesced)

@@ -1,12 +1,7 @@
 // conv_gemm_f32s.hip -- the fp32 1x1 / strided / dual-source implicit GEMM of conv_gemm.hip on the bf16 matrix cores, fp32-exact.
 //
-// gfx950 has no xf32: the fp32 MFMA (v_mfma_f32_32x32x2_f32) runs at 1/16 of the bf16 one.  An fp32 value splits EXACTLY into three
-// bf16 pieces, each rounded to nearest:  x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1)  (8 + 8 + 8 significand bits; both
-// subtractions are exact), and the product of two split values is
-//     a * w = sum_{i + j <= 2} a_i w_j  +  (a1 w2 + a2 w1 + a2 w2),
-// where the dropped terms are below 2^-9 * 2^-18 = 2^-27 of |a w| (the pieces shrink by >= 2^-9 each with round-to-nearest) -- under
-// fp32's own rounding of the product.  The six kept products go through v_mfma_f32_32x32x16_bf16 into fp32 accumulators:
-// 6 x 32 = 192 cycles per 32x32x16 block against 8 x 64 = 512 on the fp32 MFMA.
+// Both operands are split exactly into three bf16 pieces and the six products a_i w_j with i + j <= 2 are summed in fp32 (bf16_split.h:
+// the derivation and the error bound): 6 x 32 = 192 cycles per 32x32x16 block against 8 x 64 = 512 on the fp32 MFMA.
 //
 //   * weights: split once on the host (hpe_finalize), three bf16 planes per weight row: piece j of Wt[n][k] at w + n * ldw + j * w_piece + k
 //   * activations: LDS-DMA'd as fp32 exactly as in conv_gemm_f32_dma_kernel and split per wave in registers after the fragment read.
@@ -15,7 +10,7 @@
 //     expand layers (row stores + residual loads) from twice the waves, which those layers need.
 //   * staging per slab (32 k): A [BM][32] fp32 (128-B rows, chunk swizzle c ^ ((r >> 1) & 7) as in conv_gemm.hip), then the three W pieces,
 //     each [BN][32] bf16 (64-B rows, 4 chunks, swizzle c ^ ((r >> 2) & 3): a 16-lane ds_read_b128 group then covers 16 distinct 16-B slots
-//     of the 256-B bank row).  Double buffered, one barrier per slab, the vmcnt wait written out in front of it (tools/isa_lint.py).
+//     of the 256-B bank row).  Double buffered, one barrier per slab, the vmcnt wait written out in front of it (lds_dma.h).
 //   * k labelling of one 16-deep MFMA step q: lane l supplies row l & 31, k = 16 q + 8 (l >> 5) .. + 7 -- for A the two logical fp32
 //     chunks 4q + 2(l >> 5) + {0, 1}, for W the logical bf16 chunk 2q + (l >> 5); both in natural k order.
 //   * two fp32 accumulators: a0 w0 alone in one, the five cross terms (2^-8 smaller and below) in the other, added once after the k loop.
@@ -28,28 +23,13 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "bf16_split.h"
 #include "conv_gemm_common.h"
 #include "gemm_contract.h"
 #include "hpe_internal.h"
+#include "lds_dma.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// x = h0 + h1 + h2 exactly (finite x), each piece rounded to nearest even
-__device__ __forceinline__ void split3(const f32x4& lo, const f32x4& hi, bf16x8& h0, bf16x8& h1, bf16x8& h2) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float x = e < 4 ? lo[e] : hi[e - 4];
-        const __bf16 b0 = (__bf16)x;
-        const float r1 = x - (float)b0;
-        const __bf16 b1 = (__bf16)r1;
-        const float r2 = r1 - (float)b1;
-        h0[e] = b0;
-        h1[e] = b1;
-        h2[e] = (__bf16)r2;
-    }
-}
 
 template <int MODE, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(64 * WM * WN, 2) void conv_gemm_f32s_dma_kernel(GemmArgs p) {
@@ -156,22 +136,18 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_gemm_f32s_dma_kernel(Gem
                 src = slab < p.k1_slabs ? p.x + (arow[i].base + slab * BK) : p.x2 + (arow2[i] + (slab - p.k1_slabs) * BK);
             else
                 src = p.x + (arow[i].base + slab * BK);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(ldsb + buf + (NW * i + wave) * 1024), 16, 0, 0);
+            dma16(src, ldsb + buf + (NW * i + wave) * 1024);
         }
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc)
 #pragma unroll
             for (int i = 0; i < BP; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc[i] + (size_t)pc * p.w_piece + slab * BK),
-                                                 (__attribute__((address_space(3))) void*)(ldsb + buf + A_BYTES + pc * W_BYTES + (NW * i + wave) * 1024),
-                                                 16, 0, 0);
+                dma16(wsrc[i] + (size_t)pc * p.w_piece + slab * BK, ldsb + buf + A_BYTES + pc * W_BYTES + (NW * i + wave) * 1024);
     };
 
     const int S = p.K / BK;
     issue_dma(0, 0);
-    // the LDS-DMA wait is written out in front of every barrier that publishes DMA'd data (conv_gemm.hip; tools/isa_lint.py checks it)
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    wait_counts<0>();  // slab 0 has landed
     __syncthreads();
 
     for (int s = 0; s < S; ++s) {
@@ -185,7 +161,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_gemm_f32s_dma_kernel(Gem
                 const int lc = 4 * q + 2 * hi;
                 const f32x4 lo = *reinterpret_cast<const f32x4*>(ldsb + cur + a_row[i] + ((lc ^ a_x[i]) << 4));
                 const f32x4 up = *reinterpret_cast<const f32x4*>(ldsb + cur + a_row[i] + (((lc + 1) ^ a_x[i]) << 4));
-                split3(lo, up, a0[i], a1[i], a2[i]);
+                bf16_split3_cast<8>([&](int e) { return e < 4 ? lo[e] : up[e - 4]; }, a0[i], a1[i], a2[i]);
             }
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
@@ -207,7 +183,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_gemm_f32s_dma_kernel(Gem
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[i], w0[j], acc[i][j], 0, 0, 0);
                 }
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's part of slab s + 1 has landed
+        wait_counts<0>();  // this wave's part of slab s + 1 has landed
         __syncthreads();
     }
 

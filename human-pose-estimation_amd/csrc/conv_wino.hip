@@ -26,12 +26,11 @@
 // 32 KB L1 until the next slab -> 4x L2 traffic.  The blocked V removes the problem at the price of one extra HBM round
 // trip that runs concurrently with another batch chunk's MFMA-bound GEMM (chunk streams); the slab-major producer of (b)
 // removes it without that round trip, where whole tile rows of the batch fill a workgroup.
+#include "bf16_split.h"
 #include "hpe_internal.h"
+#include "lds_dma.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WT = 64;             // tiles per workgroup
 constexpr int WN_ = 64;            // output channels per workgroup
@@ -128,13 +127,9 @@ __device__ __forceinline__ void wino_mainloop(const WinoArgs& p, float* lds, int
         const float* sv = vsrc + (size_t)s * OPER;
         const float* su = usrc + (size_t)s * OPER;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sv + i * 256),
-                                             (__attribute__((address_space(3))) void*)(dstv + i * 256), 16, 0, 0);
+        for (int i = 0; i < 4; ++i) dma16(sv + i * 256, dstv + i * 256);
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(su + i * 256),
-                                             (__attribute__((address_space(3))) void*)(dstv + OPER + i * 256), 16, 0, 0);
+        for (int i = 0; i < 4; ++i) dma16(su + i * 256, dstv + OPER + i * 256);
     };
 
     // fragment offsets (floats) inside an operand slab: [comp][half][row][4]
@@ -148,12 +143,10 @@ __device__ __forceinline__ void wino_mainloop(const WinoArgs& p, float* lds, int
     issue(0, 0);
     if (n > 1) issue(1, 1);
     if (n > 1)
-        __builtin_amdgcn_s_waitcnt(0x0F78);  // vmcnt(8): slab 0 landed, slab 1 (the 8 newest DMA instructions) may be in flight
+        wait_counts<8>();  // slab 0 landed, slab 1 (the 8 newest DMA instructions) may be in flight
     else
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    asm volatile("" ::: "memory");  // no LDS access of the loop may be scheduled above this barrier
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+        wait_counts<0>();
+    bare_barrier();  // no LDS access of the loop may be scheduled above it
     for (int s = 0; s < n; ++s) {
         const int cur = (s & 1) * (2 * OPER);
         f32x4 fa[2][2], fb[2][2];
@@ -172,9 +165,7 @@ __device__ __forceinline__ void wino_mainloop(const WinoArgs& p, float* lds, int
                 for (int j = 0; j < 2; ++j)
                     acc[0][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[0][i][ks], fb[0][j][ks], acc[0][i][j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        // my part of slab s+1 has landed: written out, not left to __syncthreads() (which guarantees lgkmcnt(0) -- my fragments of slab s
-        // are in registers -- but adds a vmcnt wait only behind some DMA patterns; tools/isa_lint.py checks the ISA)
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+        wait_counts<0>();  // my part of slab s+1 has landed (written out: lds_dma.h; my fragments of slab s are in registers)
         __syncthreads();
         if (s + 2 < n) issue(s + 2, s & 1);
         __builtin_amdgcn_sched_barrier(0);
@@ -337,7 +328,7 @@ __global__ __launch_bounds__(512, 2) void wino_gemm_streamk_kernel(WinoArgs p) {
                     }
         // every wave's parked stores must be acknowledged before the counter / flag moves: written out, because hipcc emits no
         // vmcnt wait for a workgroup-scope release fence or __syncthreads() here (checked in the ISA)
-        __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0)
+        wait_counts<0, 0>();
         __syncthreads();
         if (t == 0) __hip_atomic_store(p.flags + lid, p.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         u += S - k_first;
@@ -488,7 +479,7 @@ __device__ __forceinline__ void wino_fused_epilogue(const WinoFusedArgs& p, floa
 }
 
 // ------------------------------------------------------------------------------------------------ fused kernel on the bf16 matrix cores
-// The 16 GEMMs go through v_mfma_f32_32x32x16_bf16, fp32-exact by the three-piece split of conv_gemm_f32s.hip (x = x0 + x1 + x2,
+// The 16 GEMMs go through v_mfma_f32_32x32x16_bf16, fp32-exact by the three-piece split of bf16_split.h (x = x0 + x1 + x2,
 // every piece a bf16 rounded to nearest even; the six products a_i w_j with i + j <= 2): 3 x 32 matrix cycles per 32x32 block and
 // slab where the fp32 instruction (v_mfma_f32_32x32x2_f32) takes 4 x 64.
 //   * V: the transform threads split each element once as they write it, into three bf16 planes
@@ -508,9 +499,6 @@ __device__ __forceinline__ void wino_fused_epilogue(const WinoFusedArgs& p, floa
 //   * with U out of LDS there is room for a third raw buffer: the raw slabs form a ring of three, and a slab's DMA has two slabs
 //     of matrix time to arrive instead of one.
 // LDS: V 2 x 48 KB + raw 3 x 16 KB = 144 KB (the epilogue's transpose tile reuses the first 128 KB).
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int VPL = 16 * 64 * 16;                 // bytes of one piece plane of a V slab
 constexpr int VSB = 3 * VPL;                      // bytes of one V buffer
 constexpr int SRAWF = 1024 * 4;                   // floats per raw buffer: 16 wave-instructions of 64 chunks (the 16th is padding)
@@ -518,26 +506,10 @@ constexpr int NRAW = 3;                           // raw ring: slab s + 3 is in 
 constexpr int SPLIT_LDS_BYTES = 2 * VSB + NRAW * SRAWF * 4;  // 144 KB
 static_assert(SPLIT_LDS_BYTES >= 16 * 32 * 64 * 4 && SPLIT_LDS_BYTES <= 160 * 1024, "the epilogue's transpose tile needs 128 KB");
 
-// x = h0 + h1 + h2 exactly (finite x), each piece rounded to nearest even (bf16_split3)
-__device__ __forceinline__ void wino_split3(float x, __bf16& h0, __bf16& h1, __bf16& h2) {
-    h0 = (__bf16)x;
-    const float r1 = x - (float)h0;
-    h1 = (__bf16)r1;
-    const float r2 = r1 - (float)h1;
-    h2 = (__bf16)r2;
-}
-
 // the three pieces of 4 channels of one (component, tile) into the three planes
 __device__ __forceinline__ void wino_store_split(char* v, const f32x4& x) {
     bf16x4 h0, h1, h2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        __bf16 b0, b1, b2;
-        wino_split3(x[e], b0, b1, b2);
-        h0[e] = b0;
-        h1[e] = b1;
-        h2[e] = b2;
-    }
+    bf16_split3_cast<4>([&](int e) { return x[e]; }, h0, h1, h2);
     *reinterpret_cast<bf16x4*>(v) = h0;
     *reinterpret_cast<bf16x4*>(v + VPL) = h1;
     *reinterpret_cast<bf16x4*>(v + 2 * VPL) = h2;
@@ -593,8 +565,7 @@ __global__ __launch_bounds__(512, 2) void wino_fused_split_kernel(WinoFusedArgs 
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const float* src = rsrc[i] >= 0 ? p.Xs + (size_t)s * p.M * 8 + rsrc[i] : p.zero;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(rawb + buf * SRAWF + (i * 8 + wave) * 256), 16, 0, 0);
+            dma16(src, rawb + buf * SRAWF + (i * 8 + wave) * 256);
         }
     };
 
@@ -669,10 +640,8 @@ __global__ __launch_bounds__(512, 2) void wino_fused_split_kernel(WinoFusedArgs 
         }
     }
     load_u(0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), written out: raw(0 .. 2) of this wave have landed
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    wait_counts<0>();  // raw(0 .. 2) of this wave have landed
+    bare_barrier();
     transform(0, 0);
     __syncthreads();  // V(0) written by every wave
     // Per slab s: take the W operands of U(s) | load U(s + 1) into the registers just freed | DMA raw(s + 3) into the ring slot raw(s) left when slab
@@ -714,15 +683,13 @@ __global__ __launch_bounds__(512, 2) void wino_fused_split_kernel(WinoFusedArgs 
                         acc[c][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[m][i], fb[c][j][m ? 1 : 0], acc[c][i][j], 0, 0, 0);
             if (c == 0 && s + 1 < S) transform(slot1, nxt);
         }
-        // vmcnt(2) lgkmcnt(0), written out: all but raw(s + 3) of this wave has landed -- raw(s + 2), U(s + 1) -- and its V(s + 1) is
-        // written.  A bare barrier: __syncthreads() would bring its own vmcnt(0) behind the DMAs and shorten the ring to one slab.
-        __builtin_amdgcn_s_waitcnt(0x0072);
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        // all but raw(s + 3) of this wave has landed -- raw(s + 2), U(s + 1) -- and its V(s + 1) is written.  A bare barrier:
+        // __syncthreads() would bring its own vmcnt(0) behind the DMAs and shorten the ring to one slab.
+        wait_counts<2, 0>();
+        bare_barrier();
         slot = slot1;
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): no DMA may land in the LDS the epilogue reuses
+    wait_counts<0>();  // no DMA may land in the LDS the epilogue reuses
     __syncthreads();
 
     wino_fused_epilogue(p, lds, blk, nt, n_tiles, acc, t, wave, lane);

@@ -25,12 +25,11 @@
 #include <stdlib.h>
 
 #include "hpe_internal.h"
+#include "lds_dma.h"
 
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int W4_T = 32;                      // tiles per workgroup
 constexpr int W4_N = 64;                      // output channels per workgroup
@@ -232,6 +231,8 @@ __global__ __launch_bounds__(W4_THREADS, 1) void w4_gemm_kernel(W4Args p) {
             const int k = wave + 12 * i;
             if (k < W4_DMA && !((ABL & 1) && k < 18) && !((ABL & 2) && k >= 18)) {
                 const float* src = (k < 18) ? sv + k * 256 : su + (k - 18) * 256;
+                // dma16() written out, the one site: through the helper the source cast follows the LDS address and hipcc schedules the
+                // address arithmetic of this kernel differently (profiles/lds_dma_device_code.txt)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                  (__attribute__((address_space(3))) void*)(lds + buf * W4_SLAB + k * 256), 16, 0, 0);
             }
@@ -254,10 +255,8 @@ __global__ __launch_bounds__(W4_THREADS, 1) void w4_gemm_kernel(W4Args p) {
     // so the buffer is free for slab s+2, and that DMA has a whole slab of MFMA time to land before barrier s+1 waits for it.
     issue(0, 0);
     if (S > 1) issue(1, 1);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) (once per workgroup: not worth a per-wave counted wait)
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    wait_counts<0>();  // (once per workgroup: not worth a per-wave counted wait)
+    bare_barrier();
     for (int s = 0; s < S; ++s) {
         const int cur = (s & 1) * W4_SLAB;
         f32x2 fa[6], fb[6];
@@ -281,10 +280,8 @@ __global__ __launch_bounds__(W4_THREADS, 1) void w4_gemm_kernel(W4Args p) {
         // lgkmcnt(0): my fragments of slab s are in registers; vmcnt(0): my part of slab s+1 has landed.  Written out: with the
         // wave-uniform branches of issue() in the loop hipcc's __syncthreads() emitted only the lgkmcnt wait here (found as whole
         // tile blocks that came out wrong, now and then, once >= 200 workgroups stretched the DMA latency)
-        __builtin_amdgcn_s_waitcnt(0x0070);
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        wait_counts<0, 0>();
+        bare_barrier();
         if (s + 2 < S) issue(s + 2, s & 1);
         __builtin_amdgcn_sched_barrier(0);
         if (!(ABL & 4)) {
@@ -297,7 +294,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void w4_gemm_kernel(W4Args p) {
             for (int nu = 0; nu < 6; ++nu) acc[nu][0] += fa[nu][0] * fb[nu][1];
         }
     }
-    __builtin_amdgcn_s_waitcnt(0x0070);
+    wait_counts<0, 0>();
     __syncthreads();  // all waves out of the last slab before the epilogue reuses the LDS
 
     w4_epilogue(p, lds, acc, tb, nt, t, lane, xi, nb);
@@ -344,8 +341,7 @@ __global__ __launch_bounds__(W4_THREADS32, 2) void w4_gemm32_kernel(W4Args p) {
         for (int i = 0; i < 6; ++i) {
             const int k = xi + 6 * i;  // 36 wave-instructions, 6 per wave
             const float* src = (k < 18) ? sv + k * 256 : su + (k - 18) * (2 * W4_N * 4);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(lds + buf * W4_SLAB32 + k * 256), 16, 0, 0);
+            dma16(src, lds + buf * W4_SLAB32 + k * 256);
         }
     };
 
@@ -359,10 +355,8 @@ __global__ __launch_bounds__(W4_THREADS32, 2) void w4_gemm32_kernel(W4Args p) {
 
     issue(s_begin, 0);
     if (s_begin + 1 < s_end) issue(s_begin + 1, 1);
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    wait_counts<0>();
+    bare_barrier();
     for (int s = s_begin; s < s_end; ++s) {
         const int cur = ((s - s_begin) & 1) * W4_SLAB32;
         f32x2 fa[6], fb[6];
@@ -376,10 +370,8 @@ __global__ __launch_bounds__(W4_THREADS32, 2) void w4_gemm32_kernel(W4Args p) {
 #pragma unroll
             for (int nu = 0; nu < 3; ++nu) acc[nu] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[nu][ks], fb[nu][ks], acc[nu], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0), written out (see w4_gemm_kernel)
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        wait_counts<0, 0>();  // (see w4_gemm_kernel)
+        bare_barrier();
         if (s + 2 < s_end) issue(s + 2, (s - s_begin) & 1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -387,7 +379,7 @@ __global__ __launch_bounds__(W4_THREADS32, 2) void w4_gemm32_kernel(W4Args p) {
 #pragma unroll
             for (int nu = 3; nu < 6; ++nu) acc[nu] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[nu][ks], fb[nu][ks], acc[nu], 0, 0, 0);
     }
-    __builtin_amdgcn_s_waitcnt(0x0070);
+    wait_counts<0, 0>();
     __syncthreads();
 
     // ---- output transform as w4_epilogue, 32 couts wide: exchange area [xi 6][jj 2][tile 32][cout 32] = 48 KB
@@ -483,7 +475,7 @@ __global__ __launch_bounds__(W4_THREADS32, 2) void w4_gemm32_kernel(W4Args p) {
         // The parts of one block run on different XCDs; the form above is what makes that safe, not the memory model's fences.
         // every wave's parked stores must be acknowledged before the counter moves (written out: hipcc emits no vmcnt wait for a
         // workgroup-scope fence / __syncthreads() here)
-        __builtin_amdgcn_s_waitcnt(0x0070);
+        wait_counts<0, 0>();
         __syncthreads();
         int* flag = reinterpret_cast<int*>(lds);
         if (t == 0) {
@@ -603,16 +595,14 @@ __global__ __launch_bounds__(W4_THREADS, 1) void w4_fused_kernel(W4FusedArgs p) 
     auto issue_raw = [&](int s, int buf) {
         if (!raw_wave) return;
         const float* src = rsrc >= 0 ? p.Xs + (size_t)(s >> 1) * p.M * 8 + rsrc + (s & 1) * 4 : p.zero;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(lds + buf * W4F_BUF + W4_VS + W4_US + wave * 256), 16, 0, 0);
+        dma16(src, lds + buf * W4F_BUF + W4_VS + W4_US + wave * 256);
     };
     auto issue_u = [&](int s, int buf) {
         const float* su = usrc + (size_t)s * W4_US;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int k = wave + 12 * i;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(su + k * 256),
-                                             (__attribute__((address_space(3))) void*)(lds + buf * W4F_BUF + W4_VS + k * 256), 16, 0, 0);
+            dma16(su + k * 256, lds + buf * W4F_BUF + W4_VS + k * 256);
         }
     };
 
@@ -668,15 +658,11 @@ __global__ __launch_bounds__(W4_THREADS, 1) void w4_fused_kernel(W4FusedArgs p) 
             *reinterpret_cast<f32x4*>(lds + buf * W4F_BUF + (comp * W4_T + row) * 4) = z;
         }
     }
-    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0)
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    wait_counts<0, 0>();
+    bare_barrier();
     transform(0, 0);
-    __builtin_amdgcn_s_waitcnt(0x0070);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    wait_counts<0, 0>();
+    bare_barrier();
     for (int s = 0; s < S; ++s) {
         const int cur = s & 1, nxt = cur ^ 1;
         if (s + 1 < S) issue_u(s + 1, nxt);
@@ -712,10 +698,8 @@ __global__ __launch_bounds__(W4_THREADS, 1) void w4_fused_kernel(W4FusedArgs p) 
                 for (int nu = 0; nu < 3; ++nu) acc[nu + 3] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[nu][ks], fb[nu][ks], acc[nu + 3], 0, 0, 0);
         }
         // U(s+1) and raw(s+2) have landed, V(s+1) is written, every wave is done with V(s) / U(s)
-        __builtin_amdgcn_s_waitcnt(0x0070);
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        wait_counts<0, 0>();
+        bare_barrier();
     }
 
     // ---- output transform (w4_epilogue with this kernel's tile -> pixel mapping)

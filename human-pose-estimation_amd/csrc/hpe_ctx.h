@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/hpe.h"
+#include "bf16_split.h"
 #include "hpe_internal.h"
 #include "hpe_plan.h"
 
@@ -137,26 +138,6 @@ inline void bn_fold(const ConvLayer& L, int n, float eps, double* scale, double*
 }
 // ... and what the gamma gradient of the encoder's backward divides by
 inline float bn_istd(const ConvLayer& L, int n, float eps) { return (float)(1.0 / std::sqrt((double)L.var[n] + (double)eps)); }
-
-__host__ __device__ inline unsigned short f2bf(float f) {  // round-to-nearest-even fp32 -> bf16 (finite inputs)
-    unsigned u;
-    memcpy(&u, &f, 4);
-    return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-__host__ __device__ inline float bf2f(unsigned short h) {
-    const unsigned u = (unsigned)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-// x = h[0] + h[1] + h[2] exactly (finite x): each piece the bf16 nearest to what the pieces before it left (conv_gemm_f32s.hip)
-__host__ __device__ inline void bf16_split3(float x, unsigned short h[3]) {
-    h[0] = f2bf(x);
-    const float r1 = x - bf2f(h[0]);
-    h[1] = f2bf(r1);
-    const float r2 = r1 - bf2f(h[1]);
-    h[2] = f2bf(r2);
-}
 
 struct DenseLayer {
     std::vector<float> kernel, bias;

@@ -121,7 +121,7 @@ __device__ __forceinline__ void bn_relu_row(f32x4 (&acc)[NRB], f32x4 (&prev)[NRB
 
 // --------------------------------------------------------------------------------------------------------- fp32 (split)
 // The fp32 stem on the bf16 matrix cores (v_mfma_f32_16x16x4_f32 runs at 1/16 of the bf16 rate): image and weights as three bf16
-// pieces each, x = x0 + x1 + x2 exactly (bf16_split3), the six products a_i w_j with i + j <= 2 in the bf16 kernel's k enumeration
+// pieces each, x = x0 + x1 + x2 exactly (bf16_split3; bf16_split.h), the six products a_i w_j with i + j <= 2 in the bf16 kernel's k enumeration
 // (one kernel row of 8 px x 4 ch per MFMA) -- 7 x 6 x 16 = 672 cycles per 16 x 16 block of a conv row against 40 x 32 = 1280.
 //   * the image is split ONCE, while it is staged: three bf16 planes per staged row, each in the bf16 kernel's layout
 //     ([232 px][4 ch], borders and pad channel exactly zero), PITCH_S floats per row; a fragment is one ds_read_b128 per piece.

@@ -634,7 +634,7 @@ def reads_bf16(kernel):
 
 
 def split3(W):
-    """The three-step rule of conv_gemm_f32s.hip's header comment: w0 = bf16(w), w1 = bf16(w - w0), w2 = bf16(w - w0 - w1); both
+    """The three-step rule of csrc/bf16_split.h's header comment (conv_gemm_f32s.hip): w0 = bf16(w), w1 = bf16(w - w0), w2 = bf16(w - w0 - w1); both
     subtractions are exact in float32.  Three float32 arrays holding bf16 values.  Written from the comment, not from the host packer."""
     w = np.asarray(W, np.float32)
     w0 = bf16_round(w)

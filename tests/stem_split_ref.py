@@ -16,7 +16,7 @@ BAR = 5e-6  # the project's per-kernel bar against fp64: max|d| / max|ref|
 
 
 def bf16_round(x):
-    """round-to-nearest-even fp32 -> bf16 (finite inputs), returned as uint16 bit patterns: f2bf of csrc/hpe_ctx.h"""
+    """round-to-nearest-even fp32 -> bf16 (finite inputs), returned as uint16 bit patterns: f2bf of csrc/bf16_split.h"""
     u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
     return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
 
