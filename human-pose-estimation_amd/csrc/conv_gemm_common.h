@@ -1,6 +1,6 @@
 // conv_gemm_common.h -- pieces shared by the implicit-GEMM kernels: the A-row addressing and the k-slab walk of the implicit GEMM (all four:
 // conv_gemm.hip, conv_gemm_f32s.hip, conv_gemm_bf16.hip, conv_gemm_bf16_p8.hip) and the fp32 epilogue (BN scale/shift, residual, ReLU, row
-// stores; conv_gemm.hip, conv_gemm_f32s.hip).  Everything here is in an anonymous namespace.
+// stores; conv_gemm.hip, conv_gemm_f32s.hip, conv_stream_f32s.hip).  Everything here is in an anonymous namespace.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -116,9 +116,18 @@ __device__ __forceinline__ SlabPos slab_seek(const GemmArgs& p, int slab) {
 #define HPE_RES_LOAD(ptr) (*(ptr))
 #endif
 // rpre (use_pre): the residual vectors of this thread's rows, loaded by the caller before its main loop (else they are read here)
-template <int BM, int BN, int WM, int WN, int NP>
+// STREAM: the caller is a persistent workgroup with the LDS-DMA of its next tile in flight (conv_stream_f32s.hip), and nothing here may wait
+// for that: scale / shift of the lane's one column come in sc0 / sh0, loaded once (a load issued here would queue behind the DMA), and the
+// barrier between transpose and row stores is an s_barrier behind this wave's LDS traffic alone (__syncthreads() is also a fence, which
+// hipcc turns into vmcnt(0)); the caller has the vmcnt wait of that barrier in front of the call.  false: every one-tile kernel.
+// THE STREAM CALLER COUNTS THIS FUNCTION'S VECTOR-MEMORY OPERATIONS in its s_waitcnt vmcnt(n): with STREAM, use_pre or p.res == nullptr, and a
+// full tile (m0 + BM <= M, n0 + BN <= N) every thread issues exactly BM / RPP row stores and nothing else that vmcnt counts.  A load added
+// to that path, or a store made conditional, makes the caller's count too large and lets it read a tile that has not landed: change
+// NPASS / the wait_counts<> of conv_stream_f32s.hip with it (fewer operations than counted is the unsafe direction, more only waits longer)
+template <int BM, int BN, int WM, int WN, bool STREAM = false, int NP>
 __device__ __forceinline__ void conv_epilogue(const GemmArgs& p, float* lds, f32x16 (&acc)[BM / WM / 32][BN / WN / 32], int m0, int n0, int t,
-                                              int lane, int wm, int wn, const f32x4 (&rpre)[NP], bool use_pre) {
+                                              int lane, int wm, int wn, const f32x4 (&rpre)[NP], bool use_pre, float sc0 = 0.f, float sh0 = 0.f) {
+    static_assert(!STREAM || BN / WN == 32, "STREAM: one column per lane");
     constexpr int MT = BM / WM / 32;
     constexpr int NT = BN / WN / 32;
     constexpr int NTHR = 64 * WM * WN;
@@ -131,8 +140,8 @@ __device__ __forceinline__ void conv_epilogue(const GemmArgs& p, float* lds, f32
             const int cl = (wn * NT + j) * 32 + col_l;
             const int n = n0 + cl;
             const bool n_ok = n < p.N;
-            const float sc = n_ok ? p.scale[n] : 0.f;
-            const float sh = n_ok ? p.shift[n] : 0.f;
+            const float sc = STREAM ? sc0 : n_ok ? p.scale[n] : 0.f;
+            const float sh = STREAM ? sh0 : n_ok ? p.shift[n] : 0.f;
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int rl = (wm * MT + i) * 32 + row_l;
@@ -141,7 +150,8 @@ __device__ __forceinline__ void conv_epilogue(const GemmArgs& p, float* lds, f32
             }
         }
     }
-    __syncthreads();
+    if constexpr (STREAM) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    else __syncthreads();
     {
         constexpr int TPR = BN / 4;
         constexpr int RPP = NTHR / TPR;

@@ -272,7 +272,7 @@ int encoder_repack_reserve(hpe_ctx* c) {
         r.wino_split = L.wino_u_split != nullptr;
         r.wino4_u = L.wino4_u;
         r.dxw = c->et.dxw[i];
-        r.w_split = static_cast<unsigned short*>(L.w_split);
+        r.w_split = L.w_split ? static_cast<unsigned short*>(L.w_split) : L.w_stream;  // (w_stream: w_split itself, or the same image behind w)
         r.kh = s.kh;
         r.cin = s.cin;
         r.cout = s.cout;
@@ -305,7 +305,7 @@ int encoder_repack_reserve(hpe_ctx* c) {
             RepackDual& d = t.D[F.n];
             d.w = L2.w_dual;
             d.shift = L2.shift_dual;
-            d.split = static_cast<unsigned short*>(L2.w_dual_split);
+            d.split = L2.w_dual_split ? static_cast<unsigned short*>(L2.w_dual_split) : L2.w_dual_stream;  // (as RepackLayer::w_split)
             d.i2c = blk.i2c;
             d.i1 = blk.i1;
             d.K1 = L2.k1_dual;

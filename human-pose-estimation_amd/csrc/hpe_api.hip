@@ -833,6 +833,37 @@ int hpe_debug_conv_route(const HpeConfig* cfg, int idx, int B, int concurrent, i
     return HPE_OK;
 }
 
+int hpe_debug_conv_stream1x1(const HpeConfig* cfg, int idx, int B, int concurrent, int residual) {
+    if (!cfg || cfg->struct_size != (int)sizeof(HpeConfig) || idx < 0 || idx >= HPE_NUM_CONV || B < 1) {
+        fail(HPE_ERR_INVALID, "hpe_debug_conv_stream1x1: cfg (struct_size), idx in [0, HPE_NUM_CONV) and B >= 1");
+        return -1;
+    }
+    const HpePlan pl = hpe_resolve_plan(*cfg);
+    const bool bf16 = cfg->encoder_dtype == 1;
+    const ConvQuery q{B, concurrent != 0, residual != 0, true};
+    for (const ResBlock& blk : blocks())  // the branch2c of a conv_block: the block's dual-source launch
+        if (blk.first && blk.i2c == idx) {
+            const BlockRoute b = route_block(pl, bf16, blk, q);
+            return (stream1x1_dual(pl, bf16, blk) ? 2 : 0) | (b.join == JOIN_DUAL && b.r2c.stream ? 1 : 0);
+        }
+    return (stream1x1_layer(pl, bf16, idx) ? 2 : 0) | (route_conv(pl, bf16, idx, q).stream ? 1 : 0);
+}
+
+int hpe_debug_dual(hpe_ctx* c, int idx2c, const float* t2, const float* x, int B, float* y, void* stream) {
+    int rc = check_ready(c, B, NEED_ENC);
+    if (rc) return rc;
+    if (!t2 || !x || !y || c->bf16) return fail(HPE_ERR_INVALID, "hpe_debug_dual: null pointer, or a bf16 context");
+    for (const ResBlock& blk : blocks()) {
+        if (!blk.first || blk.i2c != idx2c) continue;
+        const BlockRoute b = route_block(c->plan, false, blk, ConvQuery{B, false, false, c->wino_v != nullptr});
+        if (b.join != JOIN_DUAL) break;
+        DeviceGuard g(c->cfg.device);
+        HIP_TRY(run_dual(c, blk.i2c, blk.i1, b.r2c, t2, x, B, y, static_cast<hipStream_t>(stream)));
+        return HPE_OK;
+    }
+    return fail(HPE_ERR_INVALID, "hpe_debug_dual: idx2c must be the branch2c of a conv_block that this plan runs as the dual-source launch");
+}
+
 int hpe_debug_gemm(hpe_ctx* c, const float* x, const float* wt, int M, int N, int K, int w_rows, int tile, const float* residual,
                    int relu, float* y, void* stream) {
     if (!c || !c->finalized || !c->have_regressor) return fail(HPE_ERR_STATE, "needs a finalized ctx with the regressor loaded");

@@ -65,6 +65,10 @@ struct ConvLayer {
     // plan option f32_split: the fp32 weights of the 1x1 layers split exactly into three bf16 pieces, [n_pad][3][k] (conv_gemm_f32s.hip)
     void* w_split = nullptr;
     void* w_dual_split = nullptr;
+    // what conv_stream_f32s.hip reads, held by the layers stream1x1_layer() names: w_split where the layer has that packing, else the same
+    // [n_pad][3][k] image derived behind w in w's allocation (w_stream_of) -- not a packing of its own; written by hpe_finalize and the repack kernel
+    unsigned short* w_stream = nullptr;
+    unsigned short* w_dual_stream = nullptr;  // the same for the dual-source launch: w_dual_split, or its image behind w_dual
     void* stem_w = nullptr;   // conv1 only: weights in the k enumeration of stem_fused.hip (bf16 [64][7][32]; fp32: its three bf16 pieces [3][64][7][32])
     float* wino_u = nullptr;  // device, G g G^T in the blocked layout of conv_wino.hip (3x3 layers on the Winograd path only)
     // derived from wino_u, not a packing of its own: its three bf16 pieces in the operand order of wino_fused_split_kernel (wino_us_base),
@@ -98,6 +102,8 @@ constexpr size_t WINO_US_PIECE = 16 * 64 * 8;
 __host__ __device__ inline size_t wino_us_base(int n, int ci, int cin) {
     return ((size_t)(n >> 6) * (cin / 8) + (ci >> 3)) * 3 * WINO_US_PIECE + (size_t)(n & 63) * 8 + (ci & 7);
 }
+// the derived ConvLayer::w_stream: behind the n_pad * k_pad floats of w, in w's allocation
+inline unsigned short* w_stream_of(float* w, int n_pad, int k_pad) { return reinterpret_cast<unsigned short*>(w + (size_t)n_pad * k_pad); }
 // where that buffer lives: behind the 16 * cin * cout floats of wino_u, in wino_u's allocation (packer and repack kernel both ask here)
 __host__ __device__ inline unsigned short* wino_u_split_of(float* wino_u, int cin, int cout) {
     return reinterpret_cast<unsigned short*>(wino_u + (size_t)16 * cin * cout);
@@ -351,6 +357,7 @@ hipError_t run_conv(hpe_ctx* c, int idx, const ConvRoute& r, const float* x, int
                     float* wino_v = nullptr, int slot = 0, const float* scale = nullptr, const float* shift = nullptr);
 // one layer on NHWC input, alone on the device, as hpe_debug_conv and the training forward launch it: asks the route and converts the
 // input to channel-slab major (through T1) when the route reads that
+hipError_t run_dual(hpe_ctx* c, int i2c, int i1, const ConvRoute& r, const float* t2, const float* x, int B, float* y, hipStream_t st);
 hipError_t run_conv_nhwc(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
                          const float* scale = nullptr, const float* shift = nullptr);
 hipError_t run_chain(hpe_ctx* c, int i2c, bool first, const float* t2, const float* res, int B, float* t3, float* u1, hipStream_t st,

@@ -73,6 +73,13 @@ hipError_t run_conv(hpe_ctx* c, int idx, const ConvRoute& r, const float* x, int
     p.cin_slabs = s.cin / (c->bf16 ? 64 : 32);
     p.relu = relu, p.y_slab8 = r.out_slab8 ? 1 : 0;
     if (r.mode == GEMM_STEM) p.Hi = STEM_HP, p.Wi = STEM_WP, p.Cin = 4;
+    if (r.stream) {  // conv_stream_f32s.hip: a missing weight image is an error, not a reason for another kernel
+        if (!L.w_stream || !res) return hipErrorInvalidValue;
+        p.w = reinterpret_cast<const float*>(L.w_stream);
+        p.w_piece = p.ldw;
+        p.ldw *= 3;
+        return hpe_launch_stream_f32s(p, GEMM_DENSE, c->plan.stream1x1_walkers, st);
+    }
     return launch_gemm(c, p, r, L.w_split, st);
 }
 
@@ -89,7 +96,7 @@ hipError_t run_conv_nhwc(hpe_ctx* c, int idx, const float* x, int B, const float
 }
 
 // branch2c (+BN) + branch1 (+BN) + add + ReLU of a conv_block as one dual-source GEMM: t2 [M, K1] dense, x NHWC strided
-static hipError_t run_dual(hpe_ctx* c, int i2c, int i1, const ConvRoute& r, const float* t2, const float* x, int B, float* y, hipStream_t st) {
+hipError_t run_dual(hpe_ctx* c, int i2c, int i1, const ConvRoute& r, const float* t2, const float* x, int B, float* y, hipStream_t st) {
     const ConvSpec& s2 = specs()[i2c];
     const ConvSpec& s1 = specs()[i1];
     const ConvLayer& L = c->conv[i2c];
@@ -99,6 +106,13 @@ static hipError_t run_dual(hpe_ctx* c, int i2c, int i1, const ConvRoute& r, cons
     p.k1_slabs = L.k1_dual / (c->bf16 ? 64 : 32), p.relu = 1;
     p.lda = s2.cin, p.ldw = L.k_dual, p.w_rows = round_up(s2.cout, 128), p.ldy = s2.cout;
     p.Hi = p.Wi = s1.hin, p.Cin = s1.cin, p.Ho = p.Wo = s1.hout, p.stride = s1.stride;
+    if (r.stream) {  // conv_stream_f32s.hip, the dual-source form
+        if (!L.w_dual_stream) return hipErrorInvalidValue;
+        p.w = reinterpret_cast<const float*>(L.w_dual_stream);
+        p.w_piece = p.ldw;
+        p.ldw *= 3;
+        return hpe_launch_stream_f32s(p, GEMM_DUAL, c->plan.stream1x1_walkers, st);
+    }
     return launch_gemm(c, p, r, L.w_dual_split, st);
 }
 

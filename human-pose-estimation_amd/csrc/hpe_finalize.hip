@@ -75,6 +75,21 @@ int upload_split(hpe_ctx* c, void** p, const std::vector<float>& wt, int rows, i
     return upload_bf16(c, p, ws);
 }
 
+// the split image conv_stream_f32s.hip reads, [rows][3][K] bf16, appended behind the rows * K floats of wt (a layer without the split
+// packing keeps it in the allocation of its fp32 weights: w_stream_of)
+static void append_split(std::vector<float>& wt, int rows, int K) {
+    const size_t nw = (size_t)rows * K;
+    std::vector<unsigned short> ws(nw * 3);
+    for (int n = 0; n < rows; ++n)
+        for (int k = 0; k < K; ++k) {
+            unsigned short h[3];
+            bf16_split3(wt[(size_t)n * K + k], h);
+            for (int j = 0; j < 3; ++j) ws[((size_t)n * 3 + j) * K + k] = h[j];
+        }
+    wt.resize(nw + nw * 3 / 2);
+    memcpy(wt.data() + nw, ws.data(), ws.size() * 2);
+}
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -231,8 +246,11 @@ static int pack_dual_weights(hpe_ctx* c) {
         if (c->bf16) {
             if ((rc = upload_bf16(c, &L2.w_dual, to_bf16(wt)))) return rc;
         } else {
+            const bool stream = stream1x1_dual(c->plan, c->bf16, blk), derived = stream && !(packs & PACK_W_DUAL_SPLIT);
+            if (derived) append_split(wt, n_pad, K);
             if ((rc = upload_to(c, &L2.w_dual, wt))) return rc;
             if ((packs & PACK_W_DUAL_SPLIT) && (rc = upload_split(c, &L2.w_dual_split, wt, n_pad, K))) return rc;
+            if (stream) L2.w_dual_stream = derived ? w_stream_of(L2.w_dual, n_pad, K) : static_cast<unsigned short*>(L2.w_dual_split);
         }
         if ((rc = upload_to(c, &L2.shift_dual, sh))) return rc;
         L2.k_dual = K;
@@ -338,8 +356,11 @@ static int pack_conv_weights(hpe_ctx* c) {
         if (c->bf16) {
             if ((rc = upload_bf16(c, &L.w, to_bf16(wt)))) return rc;
         } else {
+            const bool stream = stream1x1_layer(c->plan, c->bf16, i), derived = stream && !(packs & PACK_W_SPLIT);
+            if (derived) append_split(wt, L.n_pad, L.k_pad);
             if ((rc = upload_to(c, &L.w, wt))) return rc;
             if ((packs & PACK_W_SPLIT) && (rc = upload_split(c, &L.w_split, wt, L.n_pad, L.k_pad))) return rc;
+            if (stream) L.w_stream = derived ? w_stream_of(L.w, L.n_pad, L.k_pad) : static_cast<unsigned short*>(L.w_split);
             if ((packs & PACK_WINO_U) && (rc = pack_wino_weights(c, s, L))) return rc;
             if ((packs & PACK_WINO4_U) && (rc = pack_wino4_weights(c, s, L))) return rc;
         }

@@ -61,6 +61,13 @@ hipError_t hpe_launch_gemm(GemmArgs p, int mode, int tile, int splitk_min_slabs,
 // split the same way in registers; the six products with i + j <= 2 are summed in fp32.  Tiles TILE_128x128 (4 waves), TILE_128x128_W8,
 // TILE_256x128_W8
 hipError_t hpe_launch_gemm_f32s(GemmArgs p, int mode, int tile, hipStream_t st);
+// conv_stream_f32s.hip: the dense split-bf16 GEMM with a residual for K = 64 / 128 and N % 128 == 0 as persistent workgroups that hold their
+// weights in registers and stream 32-row A tiles (p.w, p.ldw, p.w_piece as for hpe_launch_gemm_f32s; mode GEMM_DENSE: p.res is required).  max_walkers > 0
+// caps the workgroups per 128-cout slice (the outputs do not depend on it)
+// mode GEMM_DUAL: no residual, k = 0 .. 63 from x, 64 .. 127 from x2 [M][Cin = 64] (stride 1, Ho = Hi): the conv_block of stage 2
+bool hpe_stream_f32s_supported(int M, int N, int K);
+bool hpe_stream_f32s_dual_supported(int M, int N, int K1, int K2, int stride, int Hi, int Ho);
+hipError_t hpe_launch_stream_f32s(GemmArgs p, int mode, int max_walkers, hipStream_t st);
 
 // conv_wino.hip: 3x3/s1 SAME convolution as Winograd F(2x2,3x3); U = G g G^T blocked [N/64][C/8][16][2][64][4], V workspace of
 // hpe_wino_v_floats(B, H, W, C) floats; C % 32 == 0, N % 64 == 0

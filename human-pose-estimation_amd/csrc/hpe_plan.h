@@ -30,6 +30,10 @@ struct HpePlan {
     int min_chunk = 32;         // HPE_MIN_CHUNK: smallest batch chunk that still gets its own stream
     int halo3_two = 4;          // HPE_HALO3_TWO: map sizes of halo3 on the two-workgroups-per-CU form of that kernel (default: 28x28)
     int f32s_min_tiles = 128;   // HPE_F32S_MIN_TILES: launches with fewer tiles than this keep the fp32 kernel (and its split-K)
+    int stream1x1 = 3;          // HPE_STREAM1X1: forms on conv_stream_f32s.hip (1: identity-block expand layers with K <= 128; 2: the dual-source
+                                // launch of res2a); needs f32_split != 0 (f32_split = 0 is the fp32-MFMA plan)
+    int stream1x1_min_m = 25088;  // HPE_STREAM1X1_MIN_M: launches with fewer rows keep the fp32 GEMM (default: 8 images of 56x56, 32 of 28x28)
+    int stream1x1_walkers = 0;  // HPE_STREAM1X1_WALKERS: cap on the workgroups per 128-cout slice of such a launch (0: two workgroups per CU)
     int wino_streamk = 0;       // HPE_WINO_STREAMK: persistent stream-K scheduling of the F(2x2) Winograd GEMM
     int concurrent_tiles = 0;   // HPE_CONCURRENT_TILES=1: the tile rule of concurrent chunk launches on every launch (profiling passes with HPE_STREAMS=1)
     int bf16_w8_min_tiles = 128;  // HPE_BF16_W8_MIN_TILES: N > 64 bf16 launches with >= this many 128 x 128 tiles use the 8-wave tile (0 = never)
@@ -64,6 +68,8 @@ constexpr unsigned PACK_W_SPLIT = 1u << HPE_PACK_W_SPLIT, PACK_WINO_U = 1u << HP
                    PACK_STEM_W = 1u << HPE_PACK_STEM_W, PACK_W_DUAL = 1u << HPE_PACK_W_DUAL, PACK_W_DUAL_SPLIT = 1u << HPE_PACK_W_DUAL_SPLIT;
 // which of them hpe_finalize packs for layer idx: the rule, not its side effect
 unsigned layer_packs(const HpePlan& pl, bool bf16, int idx);
+// layer idx is one conv_stream_f32s.hip takes at some batch: hpe_finalize then keeps its split weights ([n_pad][3][k], ConvLayer::w_stream)
+bool stream1x1_layer(const HpePlan& pl, bool bf16, int idx);
 
 // one launcher each; the first four are GemmKernel's (gemm_contract.h)
 enum ConvKernel { CONV_K_F32 = 0, CONV_K_F32S, CONV_K_BF16, CONV_K_BF16_P8, CONV_K_HALO3, CONV_K_WINO, CONV_K_WINO_FUSED, CONV_K_WINO4, CONV_K_WINO4_FUSED };
@@ -74,6 +80,7 @@ struct ConvRoute {
     bool in_slab8;           // the kernel reads its input channel-slab major (the fused Winograd kernels)
     bool out_slab8;          // ... and so must its producer write it (route_block sets it on branch2a)
     bool concurrent;         // of the query: such a launch never takes the context's one split-K workspace
+    bool stream;             // the launch runs on conv_stream_f32s.hip instead; kernel / tile name the GEMM it takes with HPE_STREAM1X1=0
 };
 enum BlockJoin { JOIN_SEPARATE = 0, JOIN_DUAL, JOIN_CHAIN };  // branch2c (+ branch1) as launches of their own / the dual-source GEMM / chained with the next branch2a
 struct BlockRoute {
@@ -82,6 +89,7 @@ struct BlockRoute {
     bool u1_slab8;  // JOIN_CHAIN: the next block's branch2a output is written channel-slab major
 };
 struct ResBlock;
+bool stream1x1_dual(const HpePlan& pl, bool bf16, const ResBlock& blk);  // the conv_block whose dual-source launch conv_stream_f32s.hip takes (ConvLayer::w_dual_stream of blk.i2c)
 ConvRoute route_conv(const HpePlan& pl, bool bf16, int idx, const ConvQuery& q);
 BlockRoute route_block(const HpePlan& pl, bool bf16, const ResBlock& blk, ConvQuery q);  // q.residual is ignored: the block says which layer has one
 // fp32 tile of a launch outside the table (the data-gradient GEMMs of encoder_train.hip)

@@ -118,6 +118,11 @@ const PlanOption kPlanOptions[] = {
     {&HpePlan::min_chunk, nullptr, "HPE_MIN_CHUNK", {32, 24}, {ANY, ANY}, NO_LO, NO_HI},
     {&HpePlan::halo3_two, nullptr, "HPE_HALO3_TWO", {4, 4}, {7, 7}, NO_LO, NO_HI},
     {&HpePlan::f32s_min_tiles, nullptr, "HPE_F32S_MIN_TILES", {128, 128}, {ANY, ANY}, NO_LO, NO_HI},
+    // conv_stream_f32s.hip: form mask (1: the K <= 128 identity-block expand layers; 2: the dual-source launch of res2a), fp32 only; the
+    // smallest launch it takes; a cap on its grid (the walk tests)
+    {&HpePlan::stream1x1, nullptr, "HPE_STREAM1X1", {3, 0}, {3, 0}, 0, 3},
+    {&HpePlan::stream1x1_min_m, nullptr, "HPE_STREAM1X1_MIN_M", {25088, 25088}, {ANY, ANY}, 1, NO_HI},
+    {&HpePlan::stream1x1_walkers, nullptr, "HPE_STREAM1X1_WALKERS", {0, 0}, {ANY, ANY}, 0, NO_HI},
     // persistent stream-K scheduling of the Winograd GEMM: opt-in.  It removes the partial last round of workgroups (-7 % on a res4 layer,
     // -2 % on the step with HPE_STREAMS=1) but with the default batch-chunk streams, whose kernels already fill those idle CUs, the step
     // time is unchanged within noise (profiles/r01/g_wino_streamk.txt)
@@ -241,9 +246,31 @@ unsigned layer_packs(const HpePlan& pl, bool bf16, int idx) {
     return m;
 }
 
-// steps 6-8 of route_conv, and the dual-source launch: the implicit-GEMM kernel and tile of an M x N x K launch
-static ConvRoute route_gemm(const HpePlan& pl, bool bf16, int mode, int M, int N, int K, bool expand, bool split_packed, bool concurrent) {
-    ConvRoute r{CONV_K_F32, mode, -1, false, false, concurrent};
+// the identity-block expand layers with K <= 128 that run as launches of their own (stage 2: the last block, the others are chained; stage 3:
+// all three): conv_stream_f32s.hip takes them from stream1x1_min_m rows on.  Part of the split-bf16 family: f32_split = 0 keeps the fp32-MFMA plan
+static bool use_chain(const HpePlan& pl, bool bf16, const ResBlock& blk);
+bool stream1x1_layer(const HpePlan& pl, bool bf16, int idx) {
+    if (bf16 || !(pl.stream1x1 & 1) || !pl.f32_split) return false;
+    const ConvSpec& s = specs()[idx];
+    for (const ResBlock& b : blocks())
+        if (b.i2c == idx && !b.first && !use_chain(pl, bf16, b))
+            return s.kh == 1 && s.stride == 1 && s.cout == 4 * s.cin && hpe_stream_f32s_supported(1, s.cout, conv_k_pad(idx, bf16));
+    return false;
+}
+
+// the conv_block whose dual-source launch conv_stream_f32s.hip takes (form 2): two sources of 64 channels on one map -- res2a
+bool stream1x1_dual(const HpePlan& pl, bool bf16, const ResBlock& blk) {
+    if (bf16 || !(pl.stream1x1 & 2) || !pl.f32_split || !blk.first || use_chain(pl, bf16, blk) || !(layer_packs(pl, bf16, blk.i2c) & PACK_W_DUAL)) return false;
+    const ConvSpec& s2 = specs()[blk.i2c];
+    const ConvSpec& s1 = specs()[blk.i1];
+    return hpe_stream_f32s_dual_supported(1, s2.cout, s2.cin, s1.cin, s1.stride, s1.hin, s1.hout);
+}
+
+// steps 6-8 of route_conv, and the dual-source launch: the implicit-GEMM kernel and tile of an M x N x K launch; stream_layer: the launch is
+// one of stream1x1_layer's (then step 5a: conv_stream_f32s.hip from stream1x1_min_m rows on, noted beside the GEMM route)
+static ConvRoute route_gemm(const HpePlan& pl, bool bf16, int mode, int M, int N, int K, bool expand, bool split_packed, bool concurrent,
+                            bool stream_layer = false) {
+    ConvRoute r{CONV_K_F32, mode, -1, false, false, concurrent, stream_layer && expand && M >= pl.stream1x1_min_m};
     if (bf16) {  // 6. bf16 / bf16_p8
         r.tile = pick_bf16(pl, M, N, K, expand, concurrent, mode);
         r.kernel = r.tile == TILE_P8_256x256 ? CONV_K_BF16_P8 : CONV_K_BF16;
@@ -283,7 +310,7 @@ ConvRoute route_conv(const HpePlan& pl, bool bf16, int idx, const ConvQuery& q) 
     if (bf16 && plain3 && (pl.halo3 & f4_bit(H)) && hpe_halo3_bf16_supported(H, s.cin, s.cout)) return special(CONV_K_HALO3);
     // 6.-8. the implicit GEMMs; expand: an identity block's C -> 4C layer with its residual
     return route_gemm(pl, bf16, mode, B * s.hout * s.hout, s.cout, conv_k_pad(idx, bf16), mode == GEMM_DENSE && q.residual && s.cout == 4 * s.cin,
-                      (packs & PACK_W_SPLIT) != 0, q.concurrent);
+                      (packs & PACK_W_SPLIT) != 0, q.concurrent, stream1x1_layer(pl, bf16, idx));
 }
 
 // the pair branch2c (+ residual + ReLU) -> next block's branch2a as one launch.  The last block of a stage has no partner.
@@ -323,6 +350,7 @@ BlockRoute route_block(const HpePlan& pl, bool bf16, const ResBlock& blk, ConvQu
         b.join = JOIN_DUAL;
         b.r2c = route_gemm(pl, bf16, GEMM_DUAL, q.B * s2.hout * s2.hout, s2.cout, s2.cin + specs()[blk.i1].cin, false,
                            (layer_packs(pl, bf16, blk.i2c) & PACK_W_DUAL_SPLIT) != 0, q.concurrent);
+        b.r2c.stream = stream1x1_dual(pl, bf16, blk) && q.B * s2.hout * s2.hout >= pl.stream1x1_min_m;
     } else {
         if (blk.first) b.r1 = route_conv(pl, bf16, blk.i1, q);
         q.residual = true;

@@ -979,6 +979,21 @@ class HpeEngine(object):
         """hpe_debug_conv_route with this engine's own config: which kernel layer idx takes at batch B (_lib.HpeConvRoute)"""
         return _lib.conv_route(self.lib, self._cfg, idx, B, concurrent, residual, workspace)
 
+    def debug_dual(self, idx2c, t2, x):
+        """hpe_debug_dual: the dual-source launch of the conv_block whose branch2c is idx2c, t2 [B,ho,ho,cin2c] and the block input x"""
+        s = CONV_SPECS[idx2c]
+        t2 = _require_cuda_tensor(t2, "t2")
+        x = _require_cuda_tensor(x, "x")
+        B = t2.shape[0]
+        y = self._new(B, s.hout, s.hout, s.cout)
+        _lib.check(self.lib.hpe_debug_dual(self._h, int(idx2c), t2.data_ptr(), x.data_ptr(), B, y.data_ptr(), self._stream()))
+        return y
+
+    def conv_stream1x1(self, idx, B, concurrent=False, residual=True):
+        """hpe_debug_conv_stream1x1 with this engine's own config and the environment as it is now: bit 0 = the launch runs on
+        conv_stream_f32s.hip, bit 1 = the layer is one of that kernel's"""
+        return int(self.lib.hpe_debug_conv_stream1x1(C.byref(self._cfg), int(idx), int(B), int(concurrent), int(residual)))
+
     def _debug_gemm(self, call, what, mode, tile, x, wt, y, M, N, K, kw):
         g = _lib.HpeDebugGemm()
         g.struct_size = C.sizeof(_lib.HpeDebugGemm)

@@ -924,6 +924,17 @@ typedef struct HpeConvRoute {
     int reserved; /* 0 */
 } HpeConvRoute;
 int hpe_debug_conv_route(const HpeConfig* cfg, int idx, int B, int concurrent, int residual, int workspace, HpeConvRoute* out);
+/* The weight-resident streaming kernel (conv_stream_f32s.hip) stands beside the routes above: it takes the identity-block expand layers with
+ * K <= 128 that are launches of their own (res2c_branch2c, res3{b,c,d}_branch2c; fp32 contexts with f32_split != 0, HPE_STREAM1X1) from
+ * HPE_STREAM1X1_MIN_M rows on, and hpe_debug_conv_route then still names the GEMM the launch takes without it.  Asked of the plan alone, as
+ * hpe_debug_conv_route: bit 0 = this launch runs on the streaming kernel, bit 1 = the layer is one of its layers (hpe_finalize keeps the
+ * split weights it reads); -1 with hpe_last_error() set for a bad argument.  For res2a_branch2c the answer is about its block's dual-source
+ * launch (value 2 of HPE_STREAM1X1). */
+int hpe_debug_conv_stream1x1(const HpeConfig* cfg, int idx, int B, int concurrent, int residual);
+/* The dual-source launch of a conv_block alone (fp32 contexts): y [B,ho,ho,cout] = relu(bn2c(W2c . t2) + bn1(W1 . x at the shortcut's stride)),
+ * t2_dev [B,ho,ho,cin of idx2c] the branch2b output, x_dev [B,hi,hi,cin of branch1] the block input, through the kernel the plan routes
+ * that launch to at batch B.  HPE_ERR_INVALID unless idx2c is the branch2c of a conv_block joined as the dual-source GEMM. */
+int hpe_debug_dual(hpe_ctx* ctx, int idx2c, const float* t2_dev, const float* x_dev, int B, float* y_dev, void* stream);
 /* The dense mode of hpe_debug_gemm_ex with scale = ones, shift = zeros, lda = ldw = K, ldy = ldres = N and no split-K
  * workspace: y[M,N] = act(x[M,K] . wt[n][k]^T (+ residual)); K % 32 == 0; N <= 1024; tile 0..6 as above.  Needs the regressor loaded. */
 int hpe_debug_gemm(hpe_ctx* ctx, const float* x_dev, const float* wt_dev, int M, int N, int K, int w_rows, int tile,
