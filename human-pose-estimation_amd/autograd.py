@@ -127,16 +127,18 @@ class EncoderFunction(torch.autograd.Function):
     """features [B,2048] = hpe_encoder_forward_train(images; the engine's live encoder, BatchNorm statistics fixed), differentiable in
     ``params`` -- the flat tensor the optimiser owns, which must EQUAL what the engine holds (``set_encoder_params_dev`` after every step):
     it carries ``.grad``, the arithmetic reads the engine's weights.  Images get no gradient.  hpe_encoder_backward is stateless, so only
-    the images are saved.  ``bn``: "frozen" or "batch" (hpe_encoder_forward_batchnorm / hpe_encoder_backward_batchnorm)."""
+    the images are saved.  ``bn``: "frozen" or "batch" (hpe_encoder_forward_batchnorm / hpe_encoder_backward_batchnorm).  ``precision``:
+    "fp32" or "bf16" (hpe_encoder_forward_train_mixed / hpe_encoder_backward_mixed; frozen statistics only): features and ``.grad`` stay fp32."""
 
     @staticmethod
-    def forward(ctx, engine, images, params, bn="frozen"):
-        ctx.engine, ctx.bn = engine, bn
+    def forward(ctx, engine, images, params, bn="frozen", precision="fp32"):
+        ctx.engine, ctx.bn, ctx.precision = engine, bn, precision
         ctx.save_for_backward(images.detach())
-        return engine.encoder_forward_train(images, bn=bn)
+        return engine.encoder_forward_train(images, bn=bn, precision=precision)
 
     @staticmethod
     def backward(ctx, grad_features):
         (images,) = ctx.saved_tensors
-        g = ctx.engine.encoder_backward(images, grad_features.to(torch.float32).contiguous(), bn=ctx.bn) if ctx.needs_input_grad[2] else None
-        return None, None, g, None
+        g = (ctx.engine.encoder_backward(images, grad_features.to(torch.float32).contiguous(), bn=ctx.bn, precision=ctx.precision)
+             if ctx.needs_input_grad[2] else None)
+        return None, None, g, None, None

@@ -257,6 +257,13 @@ void wg_slicing(int idx, int B, int* P, int* slices) {
     *slices = (M + *P - 1) / *P;
 }
 
+// the same with whole groups of 16 pixels a slice: what conv_wg_gemm_bf16_kernel (encoder_grad_bf16.hip) steps by
+void wg_slicing16(int idx, int B, int* P, int* slices) {
+    const int M = B * specs()[idx].hout * specs()[idx].hout, sl = wg_slices_unrounded(idx, B);
+    *P = round_up((M + sl - 1) / sl, 16);
+    *slices = (M + *P - 1) / *P;
+}
+
 // sized from the slice count before P is rounded to a multiple of 8, which is monotone in the batch and never below the count wg_slicing
 // ends with (the rounded count is not monotone in the batch: a larger P can leave fewer slices)
 size_t wg_partial_floats(int B) {
@@ -304,9 +311,16 @@ hipError_t weight_grad(hpe_ctx* c, int idx, const float* x, const float* dz, int
     hipLaunchKernelGGL(conv_wg_fixup_kernel, dim3(a.n_nt, n_kc), dim3(256), 0, st, w.partial, slices, a.K, a.N, flat + l.off[idx][0],
                        bn ? c->ones : c->conv[idx].scale, grad_layer, w.wgp);
     if (bn) return hipGetLastError();
-    hipLaunchKernelGGL(conv_wg_finish_kernel, dim3(a.n_nt), dim3(256), 0, st, w.wgp, n_kc, w.dsh, slices, a.N, flat + l.off[idx][1],
-                       w.mean + l.stat[idx], w.istd + l.stat[idx], c->conv[idx].scale, grad_layer + kn, grad_layer + kn + a.N,
-                       grad_layer + kn + 2 * a.N);
+    return wg_finish(c, idx, n_kc, slices, grad_layer, st);
+}
+
+hipError_t wg_finish(hpe_ctx* c, int idx, int n_kc, int slices, float* grad_layer, hipStream_t st) {
+    const ConvSpec& s = specs()[idx];
+    EncTrainWork& w = c->et;
+    const EncLayout& l = layout();
+    const int N = s.cout, kn = s.kh * s.kw * s.cin * N;
+    hipLaunchKernelGGL(conv_wg_finish_kernel, dim3((N + 63) / 64), dim3(256), 0, st, w.wgp, n_kc, w.dsh, slices, N, w.flat + l.off[idx][1],
+                       w.mean + l.stat[idx], w.istd + l.stat[idx], c->conv[idx].scale, grad_layer + kn, grad_layer + kn + N, grad_layer + kn + 2 * N);
     return hipGetLastError();
 }
 

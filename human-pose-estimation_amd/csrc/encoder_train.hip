@@ -12,8 +12,9 @@
 //
 // sum_m dz * conv_raw = sum_k W[k][n] G[k][n] exactly, so the BatchNorm gradient needs neither the pre-BN tensor nor a division by s.
 //
-// The kernels and their launchers are in encoder_grad.hip, those of BatchNorm with batch statistics in encoder_bn.hip; this file holds the
-// layout, the reserves, the two walks (one forward, one backward, each taking the BatchNorm mode) and the C ABI.
+// The kernels and their launchers are in encoder_grad.hip, those of BatchNorm with batch statistics in encoder_bn.hip, those of the
+// mixed-precision walk (bf16 activations and cotangents on this fp32 context) in encoder_grad_bf16.hip; this file holds the layout, the
+// reserves, the two walks (one forward, one backward, each taking the BatchNorm mode or the mixed precision as a per-layer choice) and the C ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -89,6 +90,26 @@ void train_buffers_bn(EncTrainWork& w, int B, F&& f) {
     f(w.bn_hw, l.channels, false);
 }
 
+// ... and what hpe_encoder_train_reserve_mixed adds: bf16 elements, two to a float (every count is even).  The weight operands are zeroed:
+// the cast that opens a mixed call never writes their k padding
+constexpr size_t PADDED16 = (size_t)STEM_HP * STEM_WP * 4;  // the padded bf16 input, per image
+template <class F>
+void train_buffers_mixed(EncTrainWork& w, int B, F&& f) {
+    const EncLayout& l = layout();
+    const size_t nb = (size_t)B;
+    f(w.mx_stash, nb * l.stash_per_image / 2, false);
+    f(w.mx_g0, nb * BIG / 2, false);
+    f(w.mx_g1, nb * BIG / 2, false);
+    f(w.mx_sbig, nb * BIG / 2, false);
+    f(w.mx_t0, nb * MID / 2, false);
+    f(w.mx_t1, nb * MID / 2, false);
+    f(w.mx_ssmall, nb * MID / 2, false);
+    f(w.mx_padded, nb * PADDED16 / 2, false);
+    for (int i = 0; i < HPE_NUM_CONV; ++i) f(w.mx_w[i], (size_t)round_up(specs()[i].cout, 128) * conv_k_pad(i, true) / 2, true);
+    for (int i = 1; i < HPE_NUM_CONV; ++i) f(w.mx_dxw[i], conv_dxw_floats(i) / 2, false);
+    f(w.mx_cast, (size_t)MX_CAST_SEGS * sizeof(MxCastSeg) / sizeof(float), false);
+}
+
 struct TrainAlloc {  // rc keeps the first failure, which ends the allocations
     hpe_ctx* c;
     int rc = HPE_OK;
@@ -99,14 +120,22 @@ struct TrainAlloc {  // rc keeps the first failure, which ends the allocations
     }
 };
 
-size_t ws_floats(int B, bool bn) {
+size_t ws_floats(int B, bool bn, bool mixed = false) {
     EncTrainWork w;
     size_t n = encoder_repack_reserve_floats();  // the layer table of hpe_encoder_set_params_dev, allocated by encoder_repack_reserve
     auto add = [&n](auto&, size_t floats, bool) { n += floats; };
     train_buffers(w, B, add);
     if (bn) train_buffers_bn(w, B, add);
+    if (mixed) train_buffers_mixed(w, B, add);
     return n;
 }
+
+// the walks: frozen statistics in fp32, batch statistics in fp32, frozen statistics in mixed precision.  A mixed walk keeps bf16
+// elements behind the float pointers of its activations and cotangents (as a bf16 context does behind ConvLayer::w)
+enum Walk { WALK_FROZEN, WALK_BATCH, WALK_MIXED };
+cmx16 h16(const float* p) { return reinterpret_cast<cmx16>(p); }
+mx16 h16(float* p) { return reinterpret_cast<mx16>(p); }
+float* f16(mx16 p) { return reinterpret_cast<float*>(p); }
 
 // the data-gradient operand of layer idx in the forward GEMM's Wt[n][k] form: rows = input channels (zero padded to 128), k = output channels
 // (1x1: the HWIO matrix itself) or (tap', output channel) with the taps flipped (3x3)
@@ -124,6 +153,13 @@ void pack_dx_weights(int idx, const float* kernel, std::vector<float>& out) {
 float* stash_of(hpe_ctx* c, int idx, int B) {
     const EncLayout& l = layout();
     return c->et.stash + (size_t)B * (idx < 0 ? l.stash_pool : l.stash[idx]);
+}
+
+// ... of the walk's own stash: the mixed one has the same layout in bf16 elements
+float* stash_of(hpe_ctx* c, Walk wk, int idx, int B) {
+    if (wk != WALK_MIXED) return stash_of(c, idx, B);
+    const EncLayout& l = layout();
+    return f16(c->et.mx_stash + (size_t)B * (idx < 0 ? l.stash_pool : l.stash[idx]));
 }
 
 // ---- BatchNorm with batch statistics (encoder_bn.hip holds the kernels): z kept beside y, the layer's statistics in its slots
@@ -196,28 +232,41 @@ hipError_t layer_gate_bn(hpe_ctx* c, int idx, const float* dy, const float* y, c
 }
 
 // The training forward, every activation kept in the stash.  bn (batch statistics): z kept beside y, the statistics in the layers' slots
-hipError_t forward_train(hpe_ctx* c, bool bn, const float* images, int B, float* features, hipStream_t st) {
+//                       mixed: the weight operands are cast from the live fp32 weights first, every layer runs on the bf16 GEMMs
+hipError_t forward_train(hpe_ctx* c, Walk wk, const float* images, int B, float* features, hipStream_t st) {
+    const bool bn = wk == WALK_BATCH, mx = wk == WALK_MIXED;
     const bool reduce = bn && c->et.reduce != nullptr;
+    auto stash = [&](int idx) { return stash_of(c, wk, idx, B); };
     auto layer = [&](int idx, const float* x, const float* res, int relu) {
-        float* y = stash_of(c, idx, B);
+        float* y = stash(idx);
+        if (mx) return mx_conv_forward(c, idx, h16(x), B, h16(res), relu, h16(y), st);
         return bn ? layer_forward_bn(c, idx, x, B, res, relu, zstash_of(c, idx, B), y, bn_slots(c, idx, false), st, reduce)
                   : run_conv_nhwc(c, idx, x, B, res, relu, y, st);
     };
-    HIPE(hpe_launch_pad_input(images, c->padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
-    HIPE(layer(0, c->padded, nullptr, 1));
-    HIPE(hpe_launch_maxpool(stash_of(c, 0, B), stash_of(c, -1, B), B, 112, 64, st));
+    if (mx) {
+        HIPE(mx_cast_launch(c, 0, MX_CAST_SEGS, st));
+        HIPE(hpe_launch_pad_input_bf16(images, c->et.mx_padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
+        HIPE(layer(0, f16(c->et.mx_padded), nullptr, 1));
+        HIPE(hpe_launch_maxpool_bf16(stash(0), stash(-1), B, 112, 64, st));
+    } else {
+        HIPE(hpe_launch_pad_input(images, c->padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
+        HIPE(layer(0, c->padded, nullptr, 1));
+        HIPE(hpe_launch_maxpool(stash(0), stash(-1), B, 112, 64, st));
+    }
     for (const ResBlock& blk : blocks()) {
-        const float* cur = stash_of(c, blk.in, B);
+        const float* cur = stash(blk.in);
         HIPE(layer(blk.i2a, cur, nullptr, 1));
-        HIPE(layer(blk.i2b, stash_of(c, blk.i2a, B), nullptr, 1));
+        HIPE(layer(blk.i2b, stash(blk.i2a), nullptr, 1));
         const float* res = cur;
         if (blk.first) {
             HIPE(layer(blk.i1, cur, nullptr, 0));
-            res = stash_of(c, blk.i1, B);
+            res = stash(blk.i1);
         }
-        HIPE(layer(blk.i2c, stash_of(c, blk.i2b, B), res, 1));
+        HIPE(layer(blk.i2c, stash(blk.i2b), res, 1));
     }
-    return hpe_launch_avgpool(stash_of(c, blocks().back().i2c, B), features, B, 49, HPE_FEATURE_DIM, HPE_FEATURE_DIM, st);
+    const float* last = stash(blocks().back().i2c);
+    if (mx) return hpe_launch_avgpool_bf16(last, features, B, 49, HPE_FEATURE_DIM, HPE_FEATURE_DIM, st);
+    return hpe_launch_avgpool(last, features, B, 49, HPE_FEATURE_DIM, HPE_FEATURE_DIM, st);
 }
 
 struct GateOut {
@@ -229,11 +278,18 @@ struct GateOut {
 //   frozen  dz in place where there is a ReLU (without one dz is dy), copy = dz * s (none for conv1, which has no data gradient); the
 //           weight gradient reads dz
 //   batch   the bias / gamma / beta gradients go into grad_flat, copy = dzraw, which both gradients read; dz is written only if kept
-hipError_t layer_gate(hpe_ctx* c, bool bn, int idx, float* dy, bool gated, bool keep, float* copy, int B, float* grad_flat, hipStream_t st,
+//   mixed   as frozen on bf16 elements; copy = RNE(dz * s)
+hipError_t layer_gate(hpe_ctx* c, Walk wk, int idx, float* dy, bool gated, bool keep, float* copy, int B, float* grad_flat, hipStream_t st,
                       GateOut* o) {
     const ConvSpec& s = specs()[idx];
-    const float* y = gated ? stash_of(c, idx, B) : nullptr;
-    if (bn) {
+    const float* y = gated ? stash_of(c, wk, idx, B) : nullptr;
+    if (wk == WALK_MIXED) {
+        float* dzs = idx == 0 ? nullptr : copy;
+        mx_gate(h16(dy), h16(y), dzs ? c->conv[idx].scale : nullptr, gated ? h16(dy) : nullptr, h16(dzs), (long)B * s.hout * s.hout * s.cout, s.cout, st);
+        *o = {dy, dzs};
+        return hipSuccess;
+    }
+    if (wk == WALK_BATCH) {
         *o = {copy, copy};
         return layer_gate_bn(c, idx, dy, y, zstash_of(c, idx, B), B, bn_slots(c, idx, false), grad_flat + layout().off[idx][0], keep ? dy : nullptr,
                              copy, st, c->et.reduce != nullptr);
@@ -244,50 +300,72 @@ hipError_t layer_gate(hpe_ctx* c, bool bn, int idx, float* dy, bool gated, bool 
     return hipSuccess;
 }
 
-hipError_t backward(hpe_ctx* c, bool bn, const float* images, int B, const float* grad_features, float* grad_flat, hipStream_t st) {
+hipError_t backward(hpe_ctx* c, Walk wk, const float* images, int B, const float* grad_features, float* grad_flat, hipStream_t st) {
     EncTrainWork& w = c->et;
-    HIPE(forward_train(c, bn, images, B, w.feat, st));
+    const bool bn = wk == WALK_BATCH, mx = wk == WALK_MIXED;
+    HIPE(forward_train(c, wk, images, B, w.feat, st));
+    auto stash = [&](int idx) { return stash_of(c, wk, idx, B); };
     auto lgate = [&](int idx, float* dy, bool gated, bool keep, float* copy, GateOut* o) {
-        return layer_gate(c, bn, idx, dy, gated, keep, copy, B, grad_flat, st, o);
+        return layer_gate(c, wk, idx, dy, gated, keep, copy, B, grad_flat, st, o);
     };
-    auto wgrad = [&](int idx, const float* x, const float* dz) { return weight_grad(c, idx, x, dz, B, grad_flat + layout().off[idx][0], st, bn); };
+    auto wgrad = [&](int idx, const float* x, const float* dz) {
+        float* grad_layer = grad_flat + layout().off[idx][0];
+        return mx ? mx_weight_grad(c, idx, h16(x), h16(dz), B, grad_layer, st) : weight_grad(c, idx, x, dz, B, grad_layer, st, bn);
+    };
+    auto dgrad = [&](int idx, const float* dzs, const float* res, float* out) {
+        return mx ? mx_data_grad(c, idx, h16(dzs), B, h16(res), h16(out), st) : data_grad(c, idx, dzs, B, res, out, st);
+    };
     GateOut o2c, o2b, o2a, o1, o0;
-    float *g = w.g0, *go = w.g1;
-    avgpool_bwd(grad_features, g, B, 49, HPE_FEATURE_DIM, st);
+    // the cotangent and operand buffers of the walk's precision
+    float *g = mx ? f16(w.mx_g0) : w.g0, *go = mx ? f16(w.mx_g1) : w.g1, *sbig = mx ? f16(w.mx_sbig) : w.sbig;
+    float *t0 = mx ? f16(w.mx_t0) : w.t0, *t1 = mx ? f16(w.mx_t1) : w.t1, *ssmall = mx ? f16(w.mx_ssmall) : w.ssmall;
+    if (mx) {
+        mx_avgpool_bwd(grad_features, h16(g), B, 49, HPE_FEATURE_DIM, st);
+    } else {
+        avgpool_bwd(grad_features, g, B, 49, HPE_FEATURE_DIM, st);
+    }
     for (auto it = blocks().rbegin(); it != blocks().rend(); ++it) {
         const int i2a = it->i2a, i2b = it->i2b, i2c = it->i2c, i1 = it->i1;
         const ConvSpec& sa = specs()[i2a];
-        const float* xin = stash_of(c, it->in, B);  // the block's input: the previous block's branch2c output
+        const float* xin = stash(it->in);  // the block's input: the previous block's branch2c output
         // branch2c: g becomes dz (the cotangent of the shortcut too)
-        HIPE(lgate(i2c, g, true, true, w.sbig, &o2c));
-        HIPE(wgrad(i2c, stash_of(c, i2b, B), o2c.wg));
-        HIPE(data_grad(c, i2c, o2c.dg, B, nullptr, w.t0, st));
-        HIPE(lgate(i2b, w.t0, true, false, w.ssmall, &o2b));
-        HIPE(wgrad(i2b, stash_of(c, i2a, B), o2b.wg));
-        HIPE(data_grad(c, i2b, o2b.dg, B, nullptr, w.t1, st));
-        HIPE(lgate(i2a, w.t1, true, false, w.ssmall, &o2a));
+        HIPE(lgate(i2c, g, true, true, sbig, &o2c));
+        HIPE(wgrad(i2c, stash(i2b), o2c.wg));
+        HIPE(dgrad(i2c, o2c.dg, nullptr, t0));
+        HIPE(lgate(i2b, t0, true, false, ssmall, &o2b));
+        HIPE(wgrad(i2b, stash(i2a), o2b.wg));
+        HIPE(dgrad(i2b, o2b.dg, nullptr, t1));
+        HIPE(lgate(i2a, t1, true, false, ssmall, &o2a));
         HIPE(wgrad(i2a, xin, o2a.wg));
         if (!it->first) {
-            HIPE(data_grad(c, i2a, o2a.dg, B, g, go, st));
+            HIPE(dgrad(i2a, o2a.dg, g, go));
             std::swap(g, go);
             continue;
         }
         // projection shortcut: no activation of its own, its dz is the block's
-        HIPE(lgate(i1, g, false, false, w.sbig, &o1));
+        HIPE(lgate(i1, g, false, false, sbig, &o1));
         HIPE(wgrad(i1, xin, o1.wg));
         if (sa.stride == 1) {
-            HIPE(data_grad(c, i2a, o2a.dg, B, nullptr, go, st));
-            HIPE(data_grad(c, i1, o1.dg, B, go, g, st));
+            HIPE(dgrad(i2a, o2a.dg, nullptr, go));
+            HIPE(dgrad(i1, o1.dg, go, g));
         } else {
-            HIPE(data_grad(c, i2a, o2a.dg, B, nullptr, w.t0, st));
-            HIPE(data_grad(c, i1, o1.dg, B, w.t0, w.t1, st));
-            scatter2(w.t1, go, B, sa.hout, sa.cin, st);
+            HIPE(dgrad(i2a, o2a.dg, nullptr, t0));
+            HIPE(dgrad(i1, o1.dg, t0, t1));
+            if (mx) {
+                mx_scatter2(h16(t1), h16(go), B, sa.hout, sa.cin, st);
+            } else {
+                scatter2(t1, go, B, sa.hout, sa.cin, st);
+            }
             std::swap(g, go);
         }
     }
-    maxpool_bwd(stash_of(c, 0, B), g, go, B, 112, 64, st);
-    HIPE(lgate(0, go, true, false, w.sbig, &o0));
-    return wgrad(0, images, o0.wg);
+    if (mx) {
+        mx_maxpool_bwd(h16(stash(0)), h16(g), h16(go), B, 112, 64, st);
+    } else {
+        maxpool_bwd(stash(0), g, go, B, 112, 64, st);
+    }
+    HIPE(lgate(0, go, true, false, sbig, &o0));
+    return wgrad(0, mx ? f16(w.mx_padded) : images, o0.wg);  // conv1's weight gradient reads the images; mixed: the padded bf16 input
 }
 
 // dx of layer idx from its data-gradient operand, for the one-layer debug calls: a stride-2 layer's comes on the low-resolution map
@@ -304,7 +382,7 @@ int debug_data_grad(hpe_ctx* c, int idx, const float* dzs, int B, float* dx, hip
 }
 
 // what a call needs: nothing reserved yet, hpe_encoder_train_reserve, or hpe_encoder_train_reserve_batchnorm as well
-enum Reserve { RESERVE_NONE, RESERVE_FROZEN, RESERVE_BN };
+enum Reserve { RESERVE_NONE, RESERVE_FROZEN, RESERVE_BN, RESERVE_MIXED };
 
 int check_train(hpe_ctx* c, int B, Reserve need = RESERVE_FROZEN) {
     if (!c) return fail(HPE_ERR_INVALID, "null ctx");
@@ -314,8 +392,9 @@ int check_train(hpe_ctx* c, int B, Reserve need = RESERVE_FROZEN) {
     if (c->bf16) return fail(HPE_ERR_STATE, "encoder training needs an fp32 context");
     if (need != RESERVE_NONE && c->et.B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve() has not been called");
     if (need == RESERVE_BN && c->et.bn_B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_batchnorm() has not been called");
-    static const char* const range[] = {"max_batch", "reserved batch", "batch of the batch-norm reserve"};
-    const int top = need == RESERVE_NONE ? c->cfg.max_batch : need == RESERVE_FROZEN ? c->et.B : c->et.bn_B;
+    if (need == RESERVE_MIXED && c->et.mx_B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_mixed() has not been called");
+    static const char* const range[] = {"max_batch", "reserved batch", "batch of the batch-norm reserve", "batch of the mixed-precision reserve"};
+    const int top = need == RESERVE_NONE ? c->cfg.max_batch : need == RESERVE_FROZEN ? c->et.B : need == RESERVE_BN ? c->et.bn_B : c->et.mx_B;
     if (B < 1 || B > top) return fail(HPE_ERR_INVALID, "batch " + std::to_string(B) + " outside [1, " + range[need] + "]");
     return HPE_OK;
 }
@@ -342,35 +421,41 @@ int walk_result(hpe_ctx* c, hipError_t e, const char* what) {
     return HPE_OK;
 }
 
-void walk_done(hpe_ctx* c, bool bn, int B) {
+void walk_done(hpe_ctx* c, Walk wk, int B) {
+    if (wk == WALK_MIXED) {  // the mixed stash has its own batch counter: the fp32 stash is as it was
+        c->et.mx_stash_B = B;
+        return;
+    }
     c->et.stash_B = B;
-    if (!bn) return;
+    if (wk != WALK_BATCH) return;
     c->et.bn_stat_B = B;
     c->et.bn_stat_G = c->et.reduce ? c->et.reduce_G : B;
 }
 
-// hpe_encoder_forward_train / _batchnorm and hpe_encoder_backward / _batchnorm
-int forward_entry(hpe_ctx* c, bool bn, const float* images, int B, float* features, void* stream) {
-    int rc = check_train(c, B, bn ? RESERVE_BN : RESERVE_FROZEN);
+Reserve reserve_of(Walk wk) { return wk == WALK_BATCH ? RESERVE_BN : wk == WALK_MIXED ? RESERVE_MIXED : RESERVE_FROZEN; }
+
+// hpe_encoder_forward_train / _batchnorm / _mixed and hpe_encoder_backward / _batchnorm / _mixed
+int forward_entry(hpe_ctx* c, Walk wk, const float* images, int B, float* features, void* stream) {
+    int rc = check_train(c, B, reserve_of(wk));
     if (rc) return rc;
     if (!images || !features) return fail(HPE_ERR_INVALID, "null pointer");
     DeviceGuard g(c->cfg.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((rc = check_reduce(c, bn, B, st))) return rc;
-    if ((rc = walk_result(c, forward_train(c, bn, images, B, features, st), "forward"))) return rc;
-    walk_done(c, bn, B);
+    if ((rc = check_reduce(c, wk == WALK_BATCH, B, st))) return rc;
+    if ((rc = walk_result(c, forward_train(c, wk, images, B, features, st), "forward"))) return rc;
+    walk_done(c, wk, B);
     return HPE_OK;
 }
 
-int backward_entry(hpe_ctx* c, bool bn, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
-    int rc = check_train(c, B, bn ? RESERVE_BN : RESERVE_FROZEN);
+int backward_entry(hpe_ctx* c, Walk wk, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
+    int rc = check_train(c, B, reserve_of(wk));
     if (rc) return rc;
     if (!images || !grad_features || !grad_flat) return fail(HPE_ERR_INVALID, "null pointer");
     DeviceGuard g(c->cfg.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((rc = check_reduce(c, bn, B, st))) return rc;
-    if ((rc = walk_result(c, backward(c, bn, images, B, grad_features, grad_flat, st), "backward"))) return rc;
-    walk_done(c, bn, B);
+    if ((rc = check_reduce(c, wk == WALK_BATCH, B, st))) return rc;
+    if ((rc = walk_result(c, backward(c, wk, images, B, grad_features, grad_flat, st), "backward"))) return rc;
+    walk_done(c, wk, B);
     return HPE_OK;
 }
 
@@ -463,11 +548,11 @@ int hpe_encoder_train_reserve(hpe_ctx* c, int B) {
 }
 
 int hpe_encoder_forward_train(hpe_ctx* c, const float* images, int B, float* features, void* stream) {
-    return forward_entry(c, false, images, B, features, stream);
+    return forward_entry(c, WALK_FROZEN, images, B, features, stream);
 }
 
 int hpe_encoder_backward(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
-    return backward_entry(c, false, images, B, grad_features, grad_flat, stream);
+    return backward_entry(c, WALK_FROZEN, images, B, grad_features, grad_flat, stream);
 }
 
 int hpe_encoder_get_params(hpe_ctx* c, float* flat, void* stream) {
@@ -608,11 +693,11 @@ int hpe_encoder_train_reserve_batchnorm(hpe_ctx* c, int B) {
 }
 
 int hpe_encoder_forward_batchnorm(hpe_ctx* c, const float* images, int B, float* features, void* stream) {
-    return forward_entry(c, true, images, B, features, stream);
+    return forward_entry(c, WALK_BATCH, images, B, features, stream);
 }
 
 int hpe_encoder_backward_batchnorm(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
-    return backward_entry(c, true, images, B, grad_features, grad_flat, stream);
+    return backward_entry(c, WALK_BATCH, images, B, grad_features, grad_flat, stream);
 }
 
 int hpe_encoder_get_stats(hpe_ctx* c, float* stats, void* stream) {
@@ -781,6 +866,101 @@ int hpe_debug_bn_backward_finish(hpe_ctx* c, int idx, const float* x, const floa
     HIP_TRY(bn_launch_bwd_apply(dy, y, z, sl.mu, sl.r, w.flat + layout().off[idx][2], red + N, red, rows, N, nullptr, w.sbig, st, (double)M));
     HIP_TRY(weight_grad(c, idx, x, w.sbig, B, grad_layer, st, true));
     return dx ? debug_data_grad(c, idx, w.sbig, B, dx, st) : HPE_OK;
+}
+
+// ---- mixed precision: bf16 walks on an fp32 context.  The bf16 weight operands are cast from the context's live fp32 weights
+// (ConvLayer::w and dxw, which both setters keep current) by one launch at the start of every mixed call: no setter knows of them
+
+long long hpe_encoder_train_ws_floats_mixed(int B) { return B < 1 ? 0 : (long long)ws_floats(B, false, true); }
+
+int hpe_encoder_train_reserve_mixed(hpe_ctx* c, int B) {
+    int rc = hpe_encoder_train_reserve(c, B);
+    if (rc) return rc;
+    EncTrainWork& w = c->et;
+    if (w.mx_B != 0) return B <= w.mx_B ? HPE_OK : fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_mixed: already reserved for a smaller batch");
+    DeviceGuard g(c->cfg.device);
+    TrainAlloc alloc{c};
+    train_buffers_mixed(w, B, alloc);
+    if (alloc.rc) return alloc.rc;
+    std::vector<MxCastSeg> table(MX_CAST_SEGS);
+    for (int i = 0; i < HPE_NUM_CONV; ++i) {
+        const ConvLayer& L = c->conv[i];
+        table[i] = {L.w, w.mx_w[i], L.k_pad, conv_k_pad(i, true), (long)L.n_pad * L.k_pad / 4};
+        if (i == 0) continue;
+        const int kd = specs()[i].kh * specs()[i].kw * specs()[i].cout;
+        table[HPE_NUM_CONV - 1 + i] = {w.dxw[i], w.mx_dxw[i], kd, kd, (long)(conv_dxw_floats(i) / 4)};
+    }
+    HIP_TRY(hipMemcpy(w.mx_cast, table.data(), table.size() * sizeof(MxCastSeg), hipMemcpyHostToDevice));
+    w.mx_B = B;
+    return HPE_OK;
+}
+
+int hpe_encoder_forward_train_mixed(hpe_ctx* c, const float* images, int B, float* features, void* stream) {
+    return forward_entry(c, WALK_MIXED, images, B, features, stream);
+}
+
+int hpe_encoder_backward_mixed(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
+    return backward_entry(c, WALK_MIXED, images, B, grad_features, grad_flat, stream);
+}
+
+int hpe_debug_conv_backward_mixed(hpe_ctx* c, int idx, const void* x, const void* y, const void* dy, int B, void* dx, float* grad_layer,
+                                  void* stream) {
+    int rc = check_train(c, B, RESERVE_MIXED);
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !dy || !grad_layer) return fail(HPE_ERR_INVALID, "bad argument");
+    if (idx == 0 && dx) return fail(HPE_ERR_INVALID, "hpe_debug_conv_backward_mixed: conv1 has no data gradient, dx_dev must be NULL");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ConvSpec& s = specs()[idx];
+    EncTrainWork& w = c->et;
+    HIP_TRY(mx_cast_launch(c, idx, 1, st));
+    if (idx > 0) HIP_TRY(mx_cast_launch(c, HPE_NUM_CONV - 1 + idx, 1, st));
+    cmx16 in = static_cast<cmx16>(x);
+    if (idx == 0) {  // x is the fp32 image tensor
+        HIP_TRY(hpe_launch_pad_input_bf16(static_cast<const float*>(x), w.mx_padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
+        in = w.mx_padded;
+    }
+    const long n = (long)B * s.hout * s.hout * s.cout;
+    mx_gate(static_cast<cmx16>(dy), static_cast<cmx16>(y), c->conv[idx].scale, w.mx_g0, dx ? w.mx_sbig : nullptr, n, s.cout, st);
+    HIP_TRY(mx_weight_grad(c, idx, in, w.mx_g0, B, grad_layer, st));
+    if (!dx) return HPE_OK;
+    if (s.stride == 1) {
+        HIP_TRY(mx_data_grad(c, idx, w.mx_sbig, B, nullptr, static_cast<mx16>(dx), st));
+    } else {  // a stride-2 layer's data gradient comes on the low-resolution map
+        HIP_TRY(mx_data_grad(c, idx, w.mx_sbig, B, nullptr, w.mx_t0, st));
+        mx_scatter2(w.mx_t0, static_cast<mx16>(dx), B, s.hout, s.cin, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return HPE_OK;
+}
+
+int hpe_debug_maxpool_backward_mixed(const void* x, const void* dy, int B, int H, int C, void* dx, void* stream) {
+    if (!x || !dy || !dx || B < 1 || H < 2 || (H & 1) || C < 8 || (C & 7)) return fail(HPE_ERR_INVALID, "bad argument");
+    mx_maxpool_bwd(static_cast<cmx16>(x), static_cast<cmx16>(dy), static_cast<mx16>(dx), B, H, C, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return HPE_OK;
+}
+
+int hpe_debug_avgpool_backward_mixed(const float* dy, int B, int HW, int C, void* dx, void* stream) {
+    if (!dy || !dx || B < 1 || HW < 1 || C < 8 || (C & 7)) return fail(HPE_ERR_INVALID, "bad argument");
+    mx_avgpool_bwd(dy, static_cast<mx16>(dx), B, HW, C, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return HPE_OK;
+}
+
+int hpe_debug_encoder_stash_batch_mixed(hpe_ctx* c) { return (c && c->finalized && !c->dead) ? c->et.mx_stash_B : 0; }
+
+int hpe_debug_encoder_stash_mixed(hpe_ctx* c, int idx, void* out, void* stream) {
+    int rc = check_train(c, 1, RESERVE_MIXED);
+    if (rc) return rc;
+    if (idx < -1 || idx >= HPE_NUM_CONV || !out) return fail(HPE_ERR_INVALID, "bad argument");
+    const int B = c->et.mx_stash_B;
+    if (B == 0) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_mixed: no mixed-precision forward has run");
+    DeviceGuard g(c->cfg.device);
+    const size_t n = idx < 0 ? (size_t)POOL_FLOATS : (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
+    HIP_TRY(hipMemcpyAsync(out, stash_of(c, WALK_MIXED, idx, B), (size_t)B * n * sizeof(unsigned short), hipMemcpyDeviceToDevice,
+                           static_cast<hipStream_t>(stream)));
+    return HPE_OK;
 }
 
 }  // extern "C"

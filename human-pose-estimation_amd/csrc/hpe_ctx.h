@@ -220,6 +220,23 @@ struct EncTrainWork {
     int reduce_G = 0;
     int reduce_failed = -1;  // the layer at which the hook reported a failure during the walk in flight (-1: none)
     int bn_stat_G = 0;       // the batch the statistics in bn_batch were taken over: bn_stat_B, or reduce_G where the hook ran
+    // Mixed precision (encoder_grad_bf16.hip), allocated by hpe_encoder_train_reserve_mixed only: bf16 elements behind every pointer.
+    // partial / dsh / wgp / flat / mean / istd / feat / zeros above are shared with the fp32 walks
+    int mx_B = 0;        // its reserved batch (0: not reserved)
+    int mx_stash_B = 0;  // batch of the mixed forward that last filled mx_stash
+    unsigned short *mx_stash = nullptr;   // laid out as the stash
+    unsigned short *mx_g0 = nullptr, *mx_g1 = nullptr, *mx_sbig = nullptr, *mx_t0 = nullptr, *mx_t1 = nullptr, *mx_ssmall = nullptr;
+    unsigned short *mx_padded = nullptr;  // [B][STEM_HP][STEM_WP][4] the padded input, the 4th channel zero
+    unsigned short *mx_w[HPE_NUM_CONV] = {};    // RNE of ConvLayer::w, Wt[n_pad][conv_k_pad(idx, true)]; the k padding is zero from the reserve on
+    unsigned short *mx_dxw[HPE_NUM_CONV] = {};  // RNE of dxw
+    void *mx_cast = nullptr;  // the device table of the cast launch that opens every mixed call: MX_CAST_SEGS segments
+};
+constexpr int MX_CAST_SEGS = 2 * HPE_NUM_CONV - 1;  // segment idx: mx_w[idx]; segment HPE_NUM_CONV - 1 + idx (idx >= 1): mx_dxw[idx]
+struct MxCastSeg {
+    const float* src;     // rows of src_pitch floats
+    unsigned short* dst;  // rows of dst_pitch >= src_pitch bf16; columns past src_pitch are not written
+    int src_pitch, dst_pitch;
+    long quads;           // rows * src_pitch / 4
 };
 constexpr int BN_MAX_SLICES = 512;     // pixel slices of one BatchNorm reduction
 constexpr int BN_PART_COLS = 262144;   // slices * channels of one reduction, at most
@@ -416,6 +433,25 @@ hipError_t data_grad(hpe_ctx* c, int idx, const float* dzs, int B, const float* 
 void scatter2(const float* lo, float* hi, int B, int H, int C, hipStream_t st);  // lo [B][H][H][C] -> the even pixels of hi [B][2H][2H][C]
 void avgpool_bwd(const float* dy, float* dx, int B, int HW, int C, hipStream_t st);
 void maxpool_bwd(const float* x, const float* dy, float* dx, int B, int H, int C, hipStream_t st);  // x [B][H][H][C], the pool's input
+
+// ... what the mixed-precision weight gradient shares with them: the slicing with whole groups of 16 pixels, and the finish launch
+void wg_slicing16(int idx, int B, int* P, int* slices);
+hipError_t wg_finish(hpe_ctx* c, int idx, int n_kc, int slices, float* grad_layer, hipStream_t st);
+
+// encoder_grad_bf16.hip: the launches of the mixed-precision walks (bf16 activations and cotangents, fp32 accumulation, fp32 gradients).
+// Every activation pointer names bf16 elements
+typedef unsigned short* mx16;
+typedef const unsigned short* cmx16;
+hipError_t mx_cast_launch(hpe_ctx* c, int first, int segs, hipStream_t st);  // segments [first, first + segs) of the cast table
+// y = RNE(act(s * conv(x, W16) + shift (+ res))) through the bf16 route of the layer; idx 0 reads the padded bf16 input
+hipError_t mx_conv_forward(hpe_ctx* c, int idx, cmx16 x, int B, cmx16 res, int relu, mx16 y, hipStream_t st);
+void mx_gate(cmx16 dy, cmx16 y, const float* s, mx16 dz, mx16 dzs, long n, int N, hipStream_t st);  // dzs = RNE(dz * s)
+// x: the layer's input (idx 0: the padded bf16 input); grad_layer fp32 as weight_grad writes it
+hipError_t mx_weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* grad_layer, hipStream_t st);
+hipError_t mx_data_grad(hpe_ctx* c, int idx, cmx16 dzs, int B, cmx16 res, mx16 out, hipStream_t st);
+void mx_scatter2(cmx16 lo, mx16 hi, int B, int H, int C, hipStream_t st);
+void mx_avgpool_bwd(const float* dy, mx16 dx, int B, int HW, int C, hipStream_t st);  // dx = RNE(dy / HW)
+void mx_maxpool_bwd(cmx16 x, cmx16 dy, mx16 dx, int B, int H, int C, hipStream_t st);
 
 // regressor_train.hip
 int regressor_param_offset(int idx, bool bias);  // idx 3: mean theta; idx 4 (bias false): the total

@@ -94,3 +94,5 @@ ConvRoute route_conv(const HpePlan& pl, bool bf16, int idx, const ConvQuery& q);
 BlockRoute route_block(const HpePlan& pl, bool bf16, const ResBlock& blk, ConvQuery q);  // q.residual is ignored: the block says which layer has one
 // fp32 tile of a launch outside the table (the data-gradient GEMMs of encoder_train.hip)
 int pick_tile(const HpePlan& pl, int M, int N, int K, bool residual_expand = false, bool concurrent = false);
+// ... and the bf16 tile of one (the data-gradient GEMMs of the mixed-precision walk): the rule of the bf16 routes, alone on the device
+int pick_tile_bf16(const HpePlan& pl, int M, int N, int K, int mode);

@@ -222,6 +222,8 @@ static int pick_bf16(const HpePlan& pl, int M, int N, int K, bool residual_expan
     return tile;
 }
 
+int pick_tile_bf16(const HpePlan& pl, int M, int N, int K, int mode) { return pick_bf16(pl, M, N, K, false, false, mode); }
+
 // ---- the dispatch.  layer_packs() is the rule hpe_finalize packs by and the routes ask; the order of the tests in route_conv() is the
 // precedence of the kernels.
 unsigned layer_packs(const HpePlan& pl, bool bf16, int idx) {

@@ -647,12 +647,16 @@ class HpeEngine(object):
         return gflat, gfeat
 
     # ------------------------------------------------------------------ encoder training (fp32 contexts; BatchNorm statistics frozen or of the batch)
-    def reserve_encoder_train(self, B, batch_norm=False):
+    def reserve_encoder_train(self, B, batch_norm=False, precision="fp32"):
         """hpe_encoder_train_reserve: allocate the stash, cotangent buffers, partial sums and data-gradient packings for batches up to B.
         batch_norm=True (hpe_encoder_train_reserve_batchnorm): also the raw-output stash and the statistics buffers that ``bn="batch"``,
-        ``encoder_stats``, ``update_encoder_stats`` and ``set_encoder_stats_dev`` need."""
+        ``encoder_stats``, ``update_encoder_stats`` and ``set_encoder_stats_dev`` need.  precision="bf16"
+        (hpe_encoder_train_reserve_mixed): also the bf16 stash, cotangent buffers and weight operands of the mixed-precision walks."""
+        mixed = self._mixed(precision, "batch" if batch_norm else "frozen")
         if batch_norm:
             _lib.check(self.lib.hpe_encoder_train_reserve_batchnorm(self._h, int(B)))
+        elif mixed:
+            _lib.check(self.lib.hpe_encoder_train_reserve_mixed(self._h, int(B)))
         else:
             _lib.check(self.lib.hpe_encoder_train_reserve(self._h, int(B)))
 
@@ -661,6 +665,27 @@ class HpeEngine(object):
         if bn not in ("frozen", "batch"):
             raise ValueError("bn must be 'frozen' or 'batch', got %r" % (bn,))
         return bn == "batch"
+
+    @staticmethod
+    def _mixed(precision, bn="frozen"):
+        """True for precision="bf16": the mixed-precision walks (bf16 activations and cotangents on this fp32 context)"""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError("precision must be 'fp32' or 'bf16', got %r" % (precision,))
+        if precision == "bf16" and HpeEngine._bn_mode(bn):
+            raise ValueError("precision='bf16' runs with frozen BatchNorm statistics only: batch statistics in bf16 are the follow-up")
+        return precision == "bf16"
+
+    def _bf16_arg(self, t, name):
+        torch = _torch()
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("%s must be a torch.Tensor on the GPU" % name)
+        if t.dtype != torch.bfloat16:
+            raise TypeError("%s must be bfloat16 (got %s)" % (name, t.dtype))
+        return t.contiguous()
+
+    def _new_bf16(self, *shape):
+        torch = _torch()
+        return torch.empty(shape, dtype=torch.bfloat16, device=self.tdev)
 
     def encoder_stats(self):
         """hpe_encoder_get_stats: the installed moving statistics as one flat CUDA tensor [resnet_spec.ENCODER_STAT_FLOATS] (moving_mean of
@@ -844,21 +869,27 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_debug_encoder_packing(self._h, int(idx), int(which), out.data_ptr(), self._stream()))
         return out
 
-    def encoder_forward_train(self, images, bn="frozen"):
+    def encoder_forward_train(self, images, bn="frozen", precision="fp32"):
         """hpe_encoder_forward_train: images [B,224,224,3] -> features [B,2048], layer by layer, every activation kept in the stash.
-        bn="batch" (hpe_encoder_forward_batchnorm): every BatchNorm normalises with the statistics of this batch."""
+        bn="batch" (hpe_encoder_forward_batchnorm): every BatchNorm normalises with the statistics of this batch.  precision="bf16"
+        (hpe_encoder_forward_train_mixed): bf16 activations and matrix products, fp32 accumulation; images and features stay fp32."""
         fn = self.lib.hpe_encoder_forward_batchnorm if self._bn_mode(bn) else self.lib.hpe_encoder_forward_train
+        if self._mixed(precision, bn):
+            fn = self.lib.hpe_encoder_forward_train_mixed
         images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))
         B = images.shape[0]
         out = self._new(B, 2048)
         self._check_hooked(fn(self._h, images.data_ptr(), B, out.data_ptr(), self._stream()))
         return out
 
-    def encoder_backward(self, images, grad_features, bn="frozen"):
+    def encoder_backward(self, images, grad_features, bn="frozen", precision="fp32"):
         """hpe_encoder_backward: the gradient of sum(grad_features * features) with respect to the flat encoder parameters.  Stateless
         (the training forward runs again); same inputs, same bits.  bn="batch" (hpe_encoder_backward_batchnorm): through the batch
-        statistics; the bias slots are 0."""
+        statistics; the bias slots are 0.  precision="bf16" (hpe_encoder_backward_mixed): the mixed-precision walk; the flat gradient
+        is fp32."""
         fn = self.lib.hpe_encoder_backward_batchnorm if self._bn_mode(bn) else self.lib.hpe_encoder_backward
+        if self._mixed(precision, bn):
+            fn = self.lib.hpe_encoder_backward_mixed
         images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))
         B = images.shape[0]
         grad_features = _require_cuda_tensor(grad_features.detach(), "grad_features")
@@ -868,10 +899,22 @@ class HpeEngine(object):
         self._check_hooked(fn(self._h, images.data_ptr(), B, grad_features.data_ptr(), g.data_ptr(), self._stream()))
         return g
 
-    def debug_conv_backward(self, idx, x, y, dy, want_dx=True):
+    def debug_conv_backward(self, idx, x, y, dy, want_dx=True, precision="fp32"):
         """hpe_debug_conv_backward: one layer's gate, weight gradient and data gradient -> (dx or None, grad_layer = [kernel | bias |
-        gamma | beta] flat)"""
+        gamma | beta] flat).  precision="bf16" (hpe_debug_conv_backward_mixed): x, y, dy and dx are torch.bfloat16 (x of idx 0: the
+        float32 images); grad_layer is float32"""
         s = CONV_SPECS[idx]
+        if self._mixed(precision):
+            x = _require_cuda_tensor(x, "x") if idx == 0 else self._bf16_arg(x, "x")
+            dy = self._bf16_arg(dy, "dy")
+            y = self._bf16_arg(y, "y") if y is not None else None
+            B = x.shape[0]
+            want_dx = want_dx and idx != 0
+            dx = self._new_bf16(B, s.hin, s.hin, s.cin) if want_dx else None
+            gl = self._new(s.kh * s.kw * s.cin * s.cout + 3 * s.cout)
+            _lib.check(self.lib.hpe_debug_conv_backward_mixed(self._h, idx, x.data_ptr(), y.data_ptr() if y is not None else None, dy.data_ptr(),
+                                                              B, dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
+            return dx, gl
         x, dy = _require_cuda_tensor(x, "x"), _require_cuda_tensor(dy, "dy")
         y = _require_cuda_tensor(y, "y") if y is not None else None  # None: a layer without activation (dz = dy)
         B = x.shape[0]
@@ -882,20 +925,39 @@ class HpeEngine(object):
                                                     dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
         return dx, gl
 
-    def debug_maxpool_backward(self, x, dy):
+    def debug_maxpool_backward(self, x, dy, precision="fp32"):
+        if self._mixed(precision):
+            x, dy = self._bf16_arg(x, "x"), self._bf16_arg(dy, "dy")
+            dx = self._new_bf16(*x.shape)
+            _lib.check(self.lib.hpe_debug_maxpool_backward_mixed(x.data_ptr(), dy.data_ptr(), x.shape[0], x.shape[1], x.shape[3], dx.data_ptr(),
+                                                                 self._stream()))
+            return dx
         x, dy = _require_cuda_tensor(x, "x"), _require_cuda_tensor(dy, "dy")
         dx = self._new(*x.shape)
         _lib.check(self.lib.hpe_debug_maxpool_backward(x.data_ptr(), dy.data_ptr(), x.shape[0], x.shape[1], x.shape[3], dx.data_ptr(), self._stream()))
         return dx
 
-    def debug_avgpool_backward(self, dy, HW):
+    def debug_avgpool_backward(self, dy, HW, precision="fp32"):
         dy = _require_cuda_tensor(dy, "dy")
+        if self._mixed(precision):
+            dx = self._new_bf16(dy.shape[0], HW, dy.shape[1])
+            _lib.check(self.lib.hpe_debug_avgpool_backward_mixed(dy.data_ptr(), dy.shape[0], HW, dy.shape[1], dx.data_ptr(), self._stream()))
+            return dx
         dx = self._new(dy.shape[0], HW, dy.shape[1])
         _lib.check(self.lib.hpe_debug_avgpool_backward(dy.data_ptr(), dy.shape[0], HW, dy.shape[1], dx.data_ptr(), self._stream()))
         return dx
 
-    def encoder_stash(self, idx):
-        """hpe_debug_encoder_stash: layer idx's output of the last training forward, over that call's batch (idx -1: the max-pooled map)"""
+    def encoder_stash(self, idx, precision="fp32"):
+        """hpe_debug_encoder_stash: layer idx's output of the last training forward, over that call's batch (idx -1: the max-pooled map).
+        precision="bf16" (hpe_debug_encoder_stash_mixed): of the last mixed-precision forward, as torch.bfloat16"""
+        if self._mixed(precision):
+            B = self.lib.hpe_debug_encoder_stash_batch_mixed(self._h)
+            if B < 1:
+                raise _lib.HpeError("encoder_stash: no mixed-precision training forward has run")
+            s = CONV_SPECS[idx] if idx >= 0 else None
+            out = self._new_bf16(B, s.hout, s.hout, s.cout) if s else self._new_bf16(B, 56, 56, 64)
+            _lib.check(self.lib.hpe_debug_encoder_stash_mixed(self._h, idx, out.data_ptr(), self._stream()))
+            return out
         B = self.lib.hpe_debug_encoder_stash_batch(self._h)
         if B < 1:
             raise _lib.HpeError("encoder_stash: no training forward has run")

@@ -28,7 +28,7 @@ ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon
 class GeneratorTrainer(object):
     def __init__(self, engine, lr=GENERATOR_LR, betas=(0.9, 0.999), eps=ADAM_EPS, kpr_loss_weight=60.0, mr_loss_weight=0.001,
                  critic_loss_weight=0.01, dropout=0.5, generator=None, train_encoder=False, encoder_lr=None, encoder_bn="frozen",
-                 bn_momentum=0.99, bn_unbiased=True, optimizer="torch", reducer=None, global_batch=None):
+                 bn_momentum=0.99, bn_unbiased=True, optimizer="torch", reducer=None, global_batch=None, encoder_precision="fp32"):
         """engine: a finalized HpeEngine with a regressor, mean theta and SMPL (and a critic, for the critic term).  ``params`` is the
         flat parameter tensor (regressor_spec.flat_layout) the optimiser owns; ``regressor_spec.flat_to_params(params)`` gives the
         dict ``load_regressor`` / ``load_mean_theta`` take.  generator: the torch.Generator of the dropout draws.  train_encoder: also
@@ -41,7 +41,9 @@ class GeneratorTrainer(object):
         the regressor's and, with ``train_encoder``, the encoder's tensor under one step count, as the reference's
         ``generator_optimizer`` does; it has one rate, so an ``encoder_lr`` other than ``lr`` is refused.  reducer / global_batch:
         data-parallel training (the module's text); with ``encoder_bn="batch"`` the reducer's callback is installed as the engine's
-        reduce hook.  ``reducer=None`` is the single-process trainer, unchanged."""
+        reduce hook.  ``reducer=None`` is the single-process trainer, unchanged.  encoder_precision: "fp32", or "bf16" for the
+        mixed-precision encoder walks (needs ``engine.reserve_encoder_train(B, precision="bf16")``; ``encoder_bn="frozen"`` only): the
+        fp32 master tensor ``encoder_params``, the optimiser and ``set_encoder_params_dev`` are as in fp32."""
         import torch
 
         if not 0.0 <= dropout < 1.0:
@@ -74,6 +76,10 @@ class GeneratorTrainer(object):
         if not 0.0 <= bn_momentum <= 1.0:
             raise ValueError("bn_momentum must be in [0, 1]")
         self.encoder_bn, self.bn_momentum, self.bn_unbiased = encoder_bn, float(bn_momentum), bool(bn_unbiased)
+        from .engine import HpeEngine
+
+        HpeEngine._mixed(encoder_precision, encoder_bn)  # "bf16" with batch statistics is the follow-up: ValueError
+        self.encoder_precision = encoder_precision
         self.encoder_params = self.encoder_optimizer = self.encoder_stats = None
         if self.train_encoder and encoder_bn == "batch":
             self.encoder_stats = engine.encoder_stats()
@@ -129,7 +135,7 @@ class GeneratorTrainer(object):
             use_critic = eng.has_critic
         enc = self.train_encoder and x.dim() == 4
         if enc:
-            features = encoder_features(eng, x, self.encoder_params, self.encoder_bn)
+            features = encoder_features(eng, x, self.encoder_params, self.encoder_bn, self.encoder_precision)
             features.retain_grad()
         else:
             with torch.no_grad():

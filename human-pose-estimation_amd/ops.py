@@ -95,13 +95,17 @@ def generator_critic_loss(engine, joints, shapes, Rs, return_parts=False, global
     return -scores.mean(0).sum()
 
 
-def encoder_features(engine, images, params, bn="frozen"):
+def encoder_features(engine, images, params, bn="frozen", precision="fp32"):
     """features [B,2048] of the engine's encoder (layer by layer, BatchNorm statistics fixed), differentiable in ``params``, the flat
     tensor [resnet_spec.ENCODER_PARAM_FLOATS] that must equal ``engine.encoder_params()``; needs ``engine.reserve_encoder_train(B)``.
-    bn="batch": BatchNorm with the statistics of this batch, the gradient through them (``reserve_encoder_train(B, batch_norm=True)``)"""
+    bn="batch": BatchNorm with the statistics of this batch, the gradient through them (``reserve_encoder_train(B, batch_norm=True)``).
+    precision="bf16": the mixed-precision walks (``reserve_encoder_train(B, precision="bf16")``; frozen statistics only): bf16
+    activations, cotangents and matrix products with fp32 accumulation; ``params``, the features and ``.grad`` stay fp32"""
     from .autograd import EncoderFunction
+    from .engine import HpeEngine
 
-    return EncoderFunction.apply(engine, images, params, bn)
+    HpeEngine._mixed(precision, bn)  # refuses bn="batch" with precision="bf16" before anything runs
+    return EncoderFunction.apply(engine, images, params, bn, precision)
 
 
 def regressor_thetas(engine, features, params, drop=None):

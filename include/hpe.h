@@ -436,6 +436,41 @@ int hpe_debug_encoder_stash(hpe_ctx* ctx, int idx, float* out_dev, void* stream)
 /* The batch of the last training forward, i.e. the images hpe_debug_encoder_stash copies (0: none has run). */
 int hpe_debug_encoder_stash_batch(hpe_ctx* ctx);
 
+/* -- mixed-precision encoder training: bf16 walks on an fp32 context --
+ * The context keeps its fp32 master weights, hpe_encoder_set_params(_dev) and every fp32 call as they are; the calls below run the
+ * frozen-statistics training forward and backward with bf16 activations, bf16 cotangents and bf16 matrix products accumulated in fp32.
+ * fp32 contexts only (a bf16 context: HPE_ERR_STATE).  Images, features, grad_features and the flat gradient stay fp32.  RNE = round to
+ * nearest even to bf16; every sum is taken in fp32 in a fixed order:
+ *   W16 = RNE(W);  pixels are RNE-rounded by the bf16 pad;  y = RNE(act(s * acc + shift (+ res))), s / shift the context's folded fp32
+ *   BatchNorm, the residual added in fp32 before the one rounding;  the max-pool is exact;  features = (fp32 sum of 49 bf16 values) / 49;
+ *   g = RNE(grad_features / 49);  dz = dy * [y > 0] exact;  dzs = RNE(dz * s);  dx = RNE(acc (+ block cotangent));  the stride-2 scatter is
+ *   exact;  the max-pool backward sums its at most four cotangents in fp32 and rounds once.  G = A^T dz, dW = s * G, dshift, db, dbeta and
+ *   dgamma = (<W16, G> + (b - mean) * dshift) / sqrt(var + eps) are fp32 and never rounded to bf16.
+ * The bf16 weight operands are cast from the context's live fp32 weights by one launch at the start of EVERY mixed call: after
+ * hpe_encoder_set_params(_dev)(q) the next mixed call computes with RNE(q), and the setters do not know of these buffers.
+ * hpe_encoder_train_reserve_mixed: hpe_encoder_train_reserve(ctx, B) if that has not run, then, once and outside any capture: a bf16 stash,
+ * bf16 cotangent and operand buffers, the padded bf16 input, the bf16 weight operands of all 53 layers (Wt[n_pad][k_pad], k_pad a multiple
+ * of 64), the 52 bf16 data-gradient operands and the table of the cast launch.  The weight-gradient partials, the flat copy and the
+ * statistics of the fp32 reserve are shared.  hpe_encoder_train_ws_floats_mixed(B): the floats of both reserves together (host code).
+ * A second call with a B not above the first is a no-op; a larger one is refused (HPE_ERR_STATE). */
+int hpe_encoder_train_reserve_mixed(hpe_ctx* ctx, int B);
+long long hpe_encoder_train_ws_floats_mixed(int B);
+/* The contract of hpe_encoder_forward_train / hpe_encoder_backward: the backward is stateless (it reruns the forward), grad_flat_dev is
+ * overwritten, the same inputs give the same bits, no atomics, no allocation, capturable on one stream.  HPE_ERR_STATE before the mixed
+ * reserve; HPE_ERR_INVALID for NULL pointers or B outside [1, batch of the mixed-precision reserve]. */
+int hpe_encoder_forward_train_mixed(hpe_ctx* ctx, const float* images_dev, int B, float* features_dev, void* stream);
+int hpe_encoder_backward_mixed(hpe_ctx* ctx, const float* images_dev, int B, const float* grad_features_dev, float* grad_flat_dev, void* stream);
+/* hpe_debug_conv_backward in mixed precision: x_dev, y_dev (or NULL), dy_dev and dx_dev (or NULL) are bf16; for idx 0 x_dev is the fp32
+ * image tensor and dx_dev must be NULL.  grad_layer_dev is fp32. */
+int hpe_debug_conv_backward_mixed(hpe_ctx* ctx, int idx, const void* x_dev, const void* y_dev, const void* dy_dev, int B, void* dx_dev,
+                                  float* grad_layer_dev, void* stream);
+/* The pool backwards on bf16 maps (C a multiple of 8): x_dev, dy_dev, dx_dev bf16; the average pool's dy_dev [B,C] is fp32. */
+int hpe_debug_maxpool_backward_mixed(const void* x_dev, const void* dy_dev, int B, int H, int C, void* dx_dev, void* stream);
+int hpe_debug_avgpool_backward_mixed(const float* dy_dev, int B, int HW, int C, void* dx_dev, void* stream);
+/* The mixed stash (bf16) of the last mixed forward, and that call's batch: a counter of its own, not the fp32 stash's. */
+int hpe_debug_encoder_stash_mixed(hpe_ctx* ctx, int idx, void* out_dev, void* stream);
+int hpe_debug_encoder_stash_batch_mixed(hpe_ctx* ctx);
+
 /* -- encoder training with batch statistics: BatchNorm in training mode (src/trainer.py:386, image_feature_extractor(images, training=True)) --
  * fp32 contexts only.  Per layer, M = B * hout * hout rows:  z = conv(x, W) + b,  mu = mean_m z,  var = mean_m (z - mu)^2 (biased),
  * r = 1 / sqrt(var + eps),  xhat = (z - mu) * r,  y = act(gamma * xhat + beta (+ residual)).  Backward:  dz = dy * [y > 0] (a projection

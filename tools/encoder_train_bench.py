@@ -11,7 +11,12 @@ those bytes over the measured time.
     python tools/encoder_train_bench.py --bn batch [--out profiles/encoder_bn_train_bench.json]
 
 The batch-statistics leg, same method: ms per hpe_encoder_backward_batchnorm, per frozen hpe_encoder_backward in the same run, per
-hpe_encoder_update_stats + hpe_encoder_set_stats_dev, against torch fp32 autograd of the same ResNet-50 with F.batch_norm(training=True)."""
+hpe_encoder_update_stats + hpe_encoder_set_stats_dev, against torch fp32 autograd of the same ResNet-50 with F.batch_norm(training=True).
+
+    python tools/encoder_train_bench.py --precision bf16 [--out profiles/encoder_train_mixed_bench.json]
+
+The mixed-precision leg: ms per hpe_encoder_backward_mixed and per fp32 hpe_encoder_backward on the same context, the two alternating group
+by group (same events, 5 groups of `iters` calls each after 3 warm-up calls of each, medians), and the bytes of the two reserves."""
 import argparse
 import json
 import os
@@ -44,6 +49,24 @@ def timed(fn, iters):
         b.synchronize()
         groups.append(a.elapsed_time(b) / iters)
     return statistics.median(groups)
+
+
+def timed_pair(fn_a, fn_b, iters):
+    """timed() for two calls that alternate group by group, so that both see the same clocks and the same neighbours"""
+    for _ in range(3):
+        fn_a()
+        fn_b()
+    groups = ([], [])
+    for _ in range(5):
+        for fn, out in ((fn_a, groups[0]), (fn_b, groups[1])):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            b.synchronize()
+            out.append(a.elapsed_time(b) / iters)
+    return statistics.median(groups[0]), statistics.median(groups[1])
 
 
 class TorchResNet(object):
@@ -96,13 +119,16 @@ def main():
     ap.add_argument("--batches", default="8,32,64")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--bn", choices=("frozen", "batch"), default="frozen")
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32", help="bf16: the mixed-precision leg (frozen statistics only)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace-calls", type=int, default=0,
                     help="run only this many backward calls of the chosen mode at the first batch and exit: the workload of a rocprofv3 --kernel-trace --stats run")
     a = ap.parse_args()
-    bn = a.bn == "batch"
+    bn, mixed = a.bn == "batch", a.precision == "bf16"
+    if bn and mixed:
+        ap.error("--precision bf16 runs with frozen statistics only")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "encoder_bn_train_bench.json" if bn else "encoder_train_bench.json")
+        a.out = os.path.join(ROOT, "profiles", "encoder_train_mixed_bench.json" if mixed else "encoder_bn_train_bench.json" if bn else "encoder_train_bench.json")
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
     batches = [int(b) for b in a.batches.split(",")]
@@ -110,14 +136,30 @@ def main():
     eng = hpe_amd.HpeEngine(device=0, max_batch=max(batches))
     eng.load_encoder(params)
     eng.finalize()
-    eng.reserve_encoder_train(max(batches), batch_norm=bn)
+    eng.reserve_encoder_train(max(batches), batch_norm=bn, precision=a.precision)
     if a.trace_calls:
         img = torch.from_numpy(synthetic.make_images(batches[0], seed=1)).cuda()
         gf = torch.randn(batches[0], 2048, device="cuda")
         for _ in range(a.trace_calls):
-            eng.encoder_backward(img, gf, bn=a.bn)
+            eng.encoder_backward(img, gf, bn=a.bn, precision=a.precision)
         torch.cuda.synchronize()
         eng.close()
+        return
+    if mixed:
+        res = {"device": torch.cuda.get_device_name(0), "iters": a.iters, "method": "device events, the two calls alternating, median of 5 groups after 3 warm-ups",
+               "rows": []}
+        for B in batches:
+            img = torch.from_numpy(synthetic.make_images(B, seed=1)).cuda()
+            gf = torch.randn(B, 2048, device="cuda")
+            mx, f32 = timed_pair(lambda: eng.encoder_backward(img, gf, precision="bf16"), lambda: eng.encoder_backward(img, gf), a.iters)
+            res["rows"].append({"B": B, "hpe_encoder_backward_mixed_ms": round(mx, 3), "hpe_encoder_backward_ms": round(f32, 3),
+                                "fp32_over_mixed": round(f32 / mx, 3), "reserve_fp32_bytes": 4 * eng.lib.hpe_encoder_train_ws_floats(B),
+                                "reserve_fp32_and_mixed_bytes": 4 * eng.lib.hpe_encoder_train_ws_floats_mixed(B)})
+        eng.close()
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps(res))
         return
     ref = TorchResNet(params, batch_norm=bn)
     flat_dev = eng.encoder_params()
