@@ -235,6 +235,8 @@ _PROTOS = {
                                      C.c_void_p, C.c_void_p]),
     "hpe_val_losses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_eval_scores": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int,
+                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_critic_layer_name": (C.c_char_p, [C.c_int]),
     "hpe_critic_layer_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "hpe_load_critic": (C.c_int, [C.c_void_p, C.POINTER(HpeCriticModel)]),

@@ -34,6 +34,9 @@ from .smpl import SMPL
 from . import assets
 
 
+_FACES_NEEDED = "%s needs the SMPL faces: set config.smpl_face_path (smpl_faces.npy, or an SMPL .pkl / .npz with an 'f' field)"
+
+
 def _load_smpl_file(path):
     return assets.load_smpl_model(path)  # allow-list unpickler / .npz (batch_smpl.py:31-81)
 
@@ -81,6 +84,7 @@ class Predictor(object):
         self.checkpoint_dir = getattr(config, "checkpoint_dir", None)
         self.smpl_face_path = getattr(config, "smpl_face_path", None)
         self._renderer = None
+        self._score_faces = None  # the faces on the device, uploaded by the first score_step
         if self.img_size != 224:
             raise ValueError("img_size must be 224 (the encoder plan is built for 224x224 inputs)")
         self.num_joints = 14
@@ -151,8 +155,7 @@ class Predictor(object):
         use so that a predictor that never draws needs no face file."""
         if self._renderer is None:
             if not self.smpl_face_path:
-                raise FileNotFoundError("Predictor.renderer needs the SMPL faces: set config.smpl_face_path (smpl_faces.npy, or an SMPL "
-                                        ".pkl / .npz with an 'f' field)")
+                raise FileNotFoundError(_FACES_NEEDED % "Predictor.renderer")
             from .render import SMPLRenderer
 
             self._renderer = SMPLRenderer(img_size=self.img_size, face_path=self.smpl_face_path, max_batch=self.batch_size,
@@ -276,6 +279,38 @@ class Predictor(object):
             result["critic_parts"] = parts
             result["generator_critic_losses"] = [-(parts[i, :3] / parts[i, 3]).sum() * critic_loss_weight for i in range(len(stages))]
         return result
+
+    def score_faces(self):
+        """the SMPL faces of ``config.smpl_face_path`` as an int32 device tensor [F,3], loaded, checked and uploaded on first use"""
+        if self._score_faces is None:
+            from . import metrics
+
+            if not self.smpl_face_path:
+                raise FileNotFoundError(_FACES_NEEDED % "Predictor.score_step")
+            self._score_faces = metrics.upload_faces(assets.load_smpl_faces(self.smpl_face_path, num_verts=_engine.NUM_VERTS), _engine.NUM_VERTS,
+                                                     self.engine.tdev)
+        return self._score_faces
+
+    def score_step(self, images, seg_gts, kp2d_gts, all_stages=True):
+        """Forward + ``hpe_eval_scores`` (metrics.eval_scores; DESIGN.md "Checkpoint scores") of every IEF stage, or of the last with
+        ``all_stages=False`` -> (counts int32 [n_stage,B,4] = tp, fp, fn, tn of the projected mesh's silhouette against ``seg_gts > 0``,
+        kp_err float32 [n_stage,B,K] pixels with -1 for a joint that is not visible, norm float32 [B,2] torso and head length of the
+        ground truth with -1 where an end is not visible, iou float64 [n_stage,B] = tp / (tp + fp + fn) per image, NaN for an empty
+        union).  The faces come from ``config.smpl_face_path`` as the renderer's do and are uploaded once.  One forward, one launch,
+        nothing reads the device: feed the first three to ``metrics.Scores.add``."""
+        from . import metrics
+
+        images = self._to_device(images)
+        B = images.shape[0]
+        if B > self.batch_size:
+            raise ValueError("score_step needs B <= config.batch_size")
+        faces = self.score_faces()
+        stages = self.engine.forward(images, all_stages=True, want=("kp2d", "verts2d"))
+        if not all_stages:
+            stages = stages[-1:]
+        counts, kp_err, norm = metrics.eval_scores([st["verts2d"] for st in stages], faces, self._to_device(seg_gts),
+                                                   self._to_device(kp2d_gts), [st["kp2d"] for st in stages])
+        return counts, kp_err, norm, metrics.image_iou(counts)
 
     def predict_single_image(self, image):
         """reference: src/predictor.py:160-163"""

@@ -19,7 +19,11 @@ GLOBAL batch G; rank r steps on its ``shard_bounds(G, r, world)`` rows (datasets
 BatchNorm statistics and gradients are those of the G rows, the replicas start from rank 0's tensors and stay bit-identical; only
 rank 0 saves, summarises and logs.
 
-Not here: ``draw_text`` on the panels, the best / worst drawings of ``validate_checkpoint``.
+Scores (DESIGN.md "Checkpoint scores"): ``score_checkpoint`` gives PCK and the silhouette's IoU / foreground-background accuracy / F1 over
+one pass of the validation set, with the best and worst images drawn on request; ``config.score_validation`` (default False) adds four
+``metrics/...`` scalars of the batch to every validation step of ``train``.
+
+Not here: ``draw_text`` on the panels.
 ``generated_verts`` is not among ``train_step``'s result keys: drawing recomputes the vertices of the rows it shows from ``thetas``.
 ``use_kpr_loss`` decides, as in the reference, only whether the keypoint loss is logged: it is always minimised."""
 from __future__ import annotations
@@ -122,6 +126,27 @@ def rank_zero_only(rank, barrier=None, save=None, log=print, **hooks):
     return out
 
 
+SCORE_TAGS = ("iou", "fb_f1", "pck_torso_0.2", "pckh_0.5")  # what config.score_validation writes as metrics/<tag>
+
+
+class BestWorst(object):
+    """The ``n`` lowest and ``n`` highest of a stream of (value, record number), ties broken by record order (the earlier record ranks
+    first in both lists); NaN values are not ranked."""
+
+    def __init__(self, n):
+        self.n, self.low, self.high = int(n), [], []
+
+    def add(self, value, record):
+        value = float(value)
+        if value != value:
+            return
+        self.low = sorted(self.low + [(value, record)])[:self.n]
+        self.high = sorted(self.high + [(-value, record)])[:self.n]
+
+    def records(self):
+        return {r for _v, r in self.low + self.high}
+
+
 def _repeat(dataset):
     """batches of an iterable dataset, over and over (the reference's ``.repeat()``)"""
     while True:
@@ -181,6 +206,7 @@ class Trainer(object):
         self.model_dir = g("model_dir", None)
         self.write_summaries = self.model_dir is not None and bool(g("write_summaries", True)) and self.rank == 0
         self.log_img_step, self.do_bone_evaluation = int(g("log_img_step", 1000)), bool(g("do_bone_evaluation", False))
+        self.score_validation = bool(g("score_validation", False))
         lo, hi = D.shard_bounds(self.batch_size, self.rank, self.world)
         self.local_batch = hi - lo  # this rank's rows of a step; rank 0 has the largest shard
         if self.local_batch < 1:
@@ -411,6 +437,9 @@ class Trainer(object):
             w.scalar("generator/kpr_loss", result["kpr_losses"][-1], step)
         if self.use_mesh_repro_loss:
             w.scalar("generator/mr_loss", result["mr_losses"][-1], step)
+        if self.score_validation:
+            for tag in SCORE_TAGS:
+                w.scalar("metrics/" + tag, result["scores"][tag], step)
         if self.log_img_step > 0 and step % self.log_img_step == 0:
             self._write_images(w, step, batch, val_result=result)
             w.flush()
@@ -442,9 +471,14 @@ class Trainer(object):
 
         def val(val_batch):
             last["val"] = self._load_images(val_batch, augment=False)
-            return self.val_step(*last["val"])
+            r = self.val_step(*last["val"])
+            if self.score_validation:  # on every rank: the sums cross the ranks
+                r["scores"] = self.score_val_result(r, last["val"][1], last["val"][2])
+            return r
 
         hooks = {}
+        if self.score_validation and self.use_validation:
+            self.predictor.score_faces()  # fail before the first step, not at the first validation step
         if self.write_summaries:
             self._open_writers()
             hooks = {"after_train_step": lambda s, r: self._summarize_train_step(s, r, last["train"]),
@@ -502,6 +536,81 @@ class Trainer(object):
             raise ValueError("the validation dataset yields no batch")
         host = torch.stack([t.reshape(()).float() for t in kpr + mr]).cpu().numpy()
         return {"kpr_loss": float(host[:len(kpr)].mean()), "mr_loss": float(host[len(kpr):].mean()) if mr else None, "batches": len(kpr)}
+
+    def score_val_result(self, result, seg_gts, kp_gt):
+        """the last stage's scores of one validation batch from what ``val_step`` returned (no second forward): one ``hpe_eval_scores``
+        launch on the reprojected vertices, the sums reduced over the ranks -> ``Scores.result_tensors()``, device scalars"""
+        from .metrics import Scores, eval_scores
+        from .projection import reproject_vertices
+
+        S = self.predictor.img_size
+        verts2d = reproject_vertices(result["generated_verts"][:, -1].contiguous(), result["generated_cams"][:, -1].contiguous(), (S, S))
+        sc = Scores().add(*eval_scores([verts2d], self.predictor.score_faces(), seg_gts, kp_gt, [result["pred_keypoints"][:, -1].contiguous()]))
+        if self.reducer is not None:
+            sc.reduce(self.reducer)
+        return sc.result_tensors()
+
+    def score_checkpoint(self, restore=True, draw_best_worst=0):
+        """PCK and silhouette scores of the newest checkpoint over ONE pass of the validation set, loaded as ``validate_checkpoint`` loads
+        it (centre crop, no flip) -> ``metrics.Scores.result()`` of the last IEF stage, plus ``"stages"``: the same for every stage, and
+        ``"batches"``.  Data-parallel: every rank scores its shard and the sums are added over the ranks in one collective.
+        draw_best_worst = n > 0: the images of the pass are ranked by the last stage's mean pixel error of their visible joints and by
+        their IoU (ties: the earlier record first; an image with no visible joint / an empty union is not ranked), and the n best and n
+        worst of each are drawn (``draw_rows``) into an event file under ``<model_dir or checkpoint_dir>/checkpoint_scores`` as
+        ``best_kp/<i>``, ``worst_kp/<i>``, ``best_iou/<i>``, ``worst_iou/<i>`` (i = 0: the best / the worst), at step = the image's
+        1-based record number.  Only the batches of the at most 4n current candidates stay on the device; ranking reads two numbers per
+        image per batch.  This is the per-image form of the reference's best / worst drawings (src/trainer.py:916-989), which rank whole
+        batches by their loss.  Data-parallel: rank 0 draws, from its own shard."""
+        import torch
+
+        from .metrics import NUM_LSP_JOINTS, Scores
+
+        if self.val_dataset is None:
+            raise RuntimeError("score_checkpoint needs a validation dataset")
+        n = int(draw_best_worst)
+        draw = n > 0 and self.rank == 0
+        if draw and not (self.model_dir or self.checkpoint_dir):
+            raise RuntimeError("draw_best_worst needs config.model_dir or config.checkpoint_dir for its event file")
+        if restore:
+            self.restore()
+        scores, batches, seen = Scores(), 0, 0
+        by_kp, by_iou, kept = BestWorst(n), BestWorst(n), {}  # kept: first record number of a batch -> its loaded tensors
+        for batch in self.val_dataset:
+            loaded = self._load_images(batch, augment=False)
+            counts, kp_err, norm, iou = self.predictor.score_step(*loaded)
+            scores.add(counts, kp_err, norm)
+            batches += 1
+            if draw:
+                e = kp_err[-1, :, :NUM_LSP_JOINTS].double()
+                vis = e >= 0
+                px = torch.where(vis, e, torch.zeros_like(e)).sum(1) / vis.sum(1)  # NaN where no joint is visible
+                host = torch.stack([px, iou[-1]]).cpu().numpy()
+                for row in range(host.shape[1]):
+                    by_kp.add(host[0, row], seen + row)
+                    by_iou.add(host[1, row], seen + row)
+                kept[seen] = loaded
+                wanted = by_kp.records() | by_iou.records()
+                kept = {first: t for first, t in kept.items() if any(first <= r < first + int(t[0].shape[0]) for r in wanted)}
+            seen += int(loaded[0].shape[0])
+        if not batches:
+            raise ValueError("the validation dataset yields no batch")
+        if self.reducer is not None:
+            scores.reduce(self.reducer)
+        out = scores.result()
+        out["stages"], out["batches"] = scores.results(), batches
+        if draw:
+            from .summary import SummaryWriter
+
+            results = {}  # one val_step per kept batch: draw_rows takes the vertices, keypoints and cameras from it
+            with SummaryWriter(os.path.join(self.model_dir or self.checkpoint_dir, "checkpoint_scores")) as writer:
+                for family, ranked in (("best_kp", by_kp.low), ("worst_kp", by_kp.high), ("best_iou", by_iou.high), ("worst_iou", by_iou.low)):
+                    for i, (_value, record) in enumerate(ranked):
+                        first = max(f for f in kept if f <= record)
+                        if first not in results:
+                            results[first] = self.predictor.val_step(*kept[first], use_mesh_repro_loss=False)
+                        png = self.draw_rows(*kept[first], [record - first], val_result=results[first])[0]
+                        writer.image("%s/%d" % (family, i), png, record + 1)
+        return out
 
     # ------------------------------------------------------------------ checkpoints
     def weights(self):

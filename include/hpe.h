@@ -573,6 +573,26 @@ int hpe_debug_bn_backward_finish(hpe_ctx* ctx, int idx, const float* x_dev, cons
 int hpe_val_losses(hpe_ctx* ctx, const float* seg_dev, const float* kp_gt_dev, const float* const* kp2d_dev,
                    const float* const* verts2d_dev, int n_stage, int B, int K, int H, int W, int P, float* out_dev, void* stream);
 
+/* What a checkpoint is scored by (DESIGN.md "Checkpoint scores"), for all n_stage IEF stages of a batch in ONE launch, one workgroup per
+ * image: the confusion counts of the projected mesh's silhouette against the mask, and the keypoint errors in pixels.
+ * Silhouette part (verts2d_dev == NULL: none; then faces_dev, seg_dev and counts_dev are not read): verts2d_dev is a host array of
+ * n_stage device pointers, each [B,P,2] in the pixel coordinates of hpe_reproject_vertices; faces_dev [F,3] vertex indices (a face with
+ * an index outside [0, P) is dropped); seg_dev [B,H,W], foreground where > 0.  Mask pixel (row i, column j) is the point (x, y) = (j, i).
+ * Vertices are snapped to X = rint(256 x), Y = rint(256 y); a face is dropped when a vertex is non-finite or outside +-16384 px or its
+ * snapped area is 0; both windings are drawn; a pixel is covered when its point is inside some face by the renderer's rule (int64 edge
+ * functions, top-left tie rule).  counts_dev [n_stage][B][4] = tp, fp, fn, tn with "positive" = covered.
+ * Keypoint part (kp_gt_dev == NULL: none): kp_gt_dev [B,K,3] normalised x, y and visibility, kp2d_dev n_stage pointers, each [B,K,2];
+ * kp_err_dev [n_stage][B][K] = hypot(0.5 W dx, 0.5 H dy) in pixels, -1 where the joint's visibility is not > 0; norm_dev [B][2] = the
+ * ground truth's torso (joint 9 to joint 2) and head (joint 13 to joint 12) length in pixels, -1 where an end is not visible or K is
+ * too small to hold it.
+ * Stateless like hpe_orth_proj: no context, no workspace, no synchronisation, no allocation, no atomics on global memory, capturable; the
+ * same inputs give the same bits.  HPE_ERR_INVALID with a message for both parts absent, a NULL pointer of a part that is present,
+ * n_stage outside [1, 16], B, H, W < 1 (F, P, K < 1 where read), or H, W whose two bitmaps of H * ceil(W / 32) dwords do not fit the
+ * 64 KiB of LDS of a workgroup. */
+int hpe_eval_scores(const float* const* verts2d_dev, const int* faces_dev, int F, const float* seg_dev, const float* kp_gt_dev,
+                    const float* const* kp2d_dev, int n_stage, int B, int P, int K, int H, int W, int* counts_dev, float* kp_err_dev,
+                    float* norm_dev, void* stream);
+
 /* -- the steps right before / after the path -------------------------- */
 /* preprocess_image (preview.py:18-35) = resize_img + scale_and_crop (src/util/image.py:7-39) + [-1,1] normalisation,
  * fused: img_dev uint8 [H,W,C] (C = 3 or 4, RGB first) -> out224_dev float [224,224,3].
