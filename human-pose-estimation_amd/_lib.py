@@ -317,6 +317,7 @@ _PROTOS = {
     "hpe_debug_conv_route": (C.c_int, [C.POINTER(HpeConfig), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(HpeConvRoute)]),
     "hpe_debug_conv_stream1x1": (C.c_int, [C.POINTER(HpeConfig), C.c_int, C.c_int, C.c_int, C.c_int]),
     "hpe_debug_dual": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_debug_stream_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hpe_debug_maxpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_avgpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_joint_regress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -6,7 +6,7 @@
 //     a * w = sum_{i + j <= 2} a_i w_j  +  (a1 w2 + a2 w1 + a2 w2),
 // where the dropped terms are below 2^-9 * 2^-18 = 2^-27 of |a w| (the pieces shrink by >= 2^-9 each with round-to-nearest) -- under
 // fp32's own rounding of the product.  The six kept products go through v_mfma_f32_32x32x16_bf16 into fp32 accumulators.
-// Users: conv_gemm_f32s.hip (A in registers, weights split by the host packer), conv_stream_f32s.hip (A split once per workgroup), conv_wino.hip (the fused F(2x2) kernel), stem_fused.hip;
+// Users: conv_gemm_f32s.hip (A in registers, weights split by the host packer), conv_stream_f32s.hip (A split once per workgroup), conv_stream_chain_f32s.hip (that, and t3 and both weight matrices split in registers), conv_wino.hip (the fused F(2x2) kernel), stem_fused.hip;
 // each says which of the six products goes where.  tests/gemm_ref.py, stem_split_ref.py and wino_split_ref.py restate the arithmetic
 // in NumPy, separately on purpose.
 #pragma once

@@ -200,7 +200,9 @@ __global__ __launch_bounds__(64 * SNW, 2) void conv_stream_f32s_kernel(GemmArgs 
     wait_counts<0>();  // the DMA the last tile issued writes this workgroup's LDS: it lands before the wave ends
 }
 
-int device_cus() {
+}  // namespace
+
+int hpe_stream_device_cus() {
     static int n = 0;  // of the first device asked about, for the process: the devices of one host are the same part
     if (n == 0) {
         int dev = 0, v = 0;
@@ -209,8 +211,6 @@ int device_cus() {
     }
     return n;
 }
-
-}  // namespace
 
 bool hpe_stream_f32s_supported(int M, int N, int K) { return M > 0 && (K == 64 || K == 128) && N >= SBN && N % SBN == 0; }
 
@@ -230,7 +230,7 @@ hipError_t hpe_launch_stream_f32s(GemmArgs p, int mode, int max_walkers, hipStre
     p.split_k = 1;
     p.res_prefetch = 1;
     // two workgroups per CU, as many walkers per N-slice as that gives (a multiple of 8: one walker per XCD and round)
-    int walkers = 2 * device_cus() / p.n_ntiles;
+    int walkers = 2 * hpe_stream_device_cus() / p.n_ntiles;
     if (max_walkers > 0 && walkers > max_walkers) walkers = max_walkers;
     if (walkers > p.n_mtiles) walkers = p.n_mtiles;
     if (walkers < 1) walkers = 1;

@@ -864,6 +864,23 @@ int hpe_debug_dual(hpe_ctx* c, int idx2c, const float* t2, const float* x, int B
     return fail(HPE_ERR_INVALID, "hpe_debug_dual: idx2c must be the branch2c of a conv_block that this plan runs as the dual-source launch");
 }
 
+int hpe_debug_stream_chain(hpe_ctx* c, int idx2c, const float* t2, const float* x, int B, float* t3, float* u1, int slab8, int rows, void* stream) {
+    int rc = check_ready(c, B, NEED_ENC);
+    if (rc) return rc;
+    if (!t2 || !x || !t3 || !u1 || c->bf16 || rows < 0) return fail(HPE_ERR_INVALID, "hpe_debug_stream_chain: null pointer, negative rows, or a bf16 context");
+    for (const ResBlock& blk : blocks()) {
+        if (blk.i2c != idx2c || blk.last) continue;
+        const ConvSpec& s2 = specs()[blk.i2c];
+        const ConvSpec& sn = specs()[blk.i2c + (blk.first ? 2 : 1)];
+        // (the geometry is the launcher's to refuse: only what would read past the caller's buffers is stopped here)
+        if (rows > B * s2.hout * s2.hout || sn.cin != s2.cout || (blk.first && specs()[blk.i1].stride != 1)) break;
+        DeviceGuard g(c->cfg.device);
+        if (run_stream_chain(c, blk.i2c, blk.first, t2, x, B, t3, u1, static_cast<hipStream_t>(stream), slab8 != 0, rows) != hipSuccess) break;
+        return HPE_OK;
+    }
+    return fail(HPE_ERR_INVALID, "hpe_debug_stream_chain: refused (idx2c must be res2a_branch2c or res2b_branch2c, rows a multiple of 32 inside the batch); nothing was launched");
+}
+
 int hpe_debug_gemm(hpe_ctx* c, const float* x, const float* wt, int M, int N, int K, int w_rows, int tile, const float* residual,
                    int relu, float* y, void* stream) {
     if (!c || !c->finalized || !c->have_regressor) return fail(HPE_ERR_STATE, "needs a finalized ctx with the regressor loaded");

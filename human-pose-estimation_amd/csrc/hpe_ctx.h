@@ -379,6 +379,8 @@ hipError_t run_conv_nhwc(hpe_ctx* c, int idx, const float* x, int B, const float
                          const float* scale = nullptr, const float* shift = nullptr);
 hipError_t run_chain(hpe_ctx* c, int i2c, bool first, const float* t2, const float* res, int B, float* t3, float* u1, hipStream_t st,
                      bool u1_slab8 = false);
+hipError_t run_stream_chain(hpe_ctx* c, int i2c, bool first, const float* t2, const float* x, int B, float* t3, float* u1, hipStream_t st,
+                            bool u1_slab8, int rows = 0);
 hipError_t encoder_impl(hpe_ctx* c, const float* images, int B, float* features, int ldfeat, hipStream_t st);
 // partial == nullptr: the ctx's split-K workspace (the tail's own while a tail is being enqueued)
 hipError_t run_dense(hpe_ctx* c, const float* x, int lda, int M, int K, const float* w, int w_rows, int N, const float* scale, const float* shift,

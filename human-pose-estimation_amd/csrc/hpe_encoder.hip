@@ -167,6 +167,26 @@ hipError_t run_chain(hpe_ctx* c, int i2c, bool first, const float* t2, const flo
     return hpe_launch_chain_bf16(p, s2.cin, s2.cout, sn.cout, first ? specs()[i2c + 1].cin : 0, st);
 }
 
+// the chained streaming launch (BlockRoute::stream_chain): x is the block input -- the residual of an identity block, the second A source of a
+// conv_block.  The kernel reads the fp32 weights of both layers; a conv_block without its folded dual weights is an error
+hipError_t run_stream_chain(hpe_ctx* c, int i2c, bool first, const float* t2, const float* x, int B, float* t3, float* u1, hipStream_t st,
+                            bool u1_slab8, int rows) {
+    const ConvSpec& s2 = specs()[i2c];
+    const int inext = i2c + (first ? 2 : 1);
+    const ConvSpec& sn = specs()[inext];
+    const ConvLayer& L2 = c->conv[i2c];
+    const ConvLayer& Ln = c->conv[inext];
+    if (c->bf16 || (first && (!L2.w_dual || !L2.shift_dual))) return hipErrorInvalidValue;
+    StreamChainArgs q{};
+    q.t2 = t2, q.x = x, q.t3 = t3, q.u1 = u1;
+    q.wA = first ? L2.w_dual : L2.w, q.ldwA = first ? L2.k_dual : L2.k_pad;
+    q.scaleA = first ? c->ones : L2.scale, q.shiftA = first ? L2.shift_dual : L2.shift;
+    q.wB = Ln.w, q.ldwB = Ln.k_pad, q.scaleB = Ln.scale, q.shiftB = Ln.shift;
+    q.M = rows ? rows : B * s2.hout * s2.hout;  // (rows: hpe_debug_stream_chain's, the first rows of the batch)
+    q.u1_slab8 = u1_slab8 ? 1 : 0;
+    return hpe_launch_stream_chain_f32s(q, s2.cin, s2.cout, sn.cout, first ? specs()[i2c + 1].cin : 0, c->plan.stream1x1_walkers, st);
+}
+
 hipError_t run_dense(hpe_ctx* c, const float* x, int lda, int M, int K, const float* w, int w_rows, int N, const float* scale,
                      const float* shift, const float* res, int ldres, int relu, float* y, int ldy, hipStream_t st, float* partial,
                      size_t partial_floats) {
@@ -258,7 +278,21 @@ static hipError_t encoder_chunk(hpe_ctx* c, const float* images, int i0, int B, 
         have_2a = false;
         HIPE(timed_conv(c, i2b, br.r2b, T1, B, nullptr, 1, T2, st, wv, slot));
         const float* res = cur;
-        if (br.join == JOIN_CHAIN) {
+        if (br.stream_chain) {
+            // the block's join and the next block's branch2a as one launch of conv_stream_chain_f32s.hip (timed as layer i2c; the projection
+            // shortcut and the next branch2a then show 0)
+            const bool t2 = c->timing >= 2;
+            if (t2) HIPE(hipEventRecord(c->cev0[i2c], st));
+            HIPE(run_stream_chain(c, i2c, first, T2, cur, B, nxt, T1, st, br.stream_u1_slab8));
+            if (t2) {
+                HIPE(hipEventRecord(c->cev1[i2c], st));
+                if (first) {
+                    HIPE(hipEventRecord(c->cev0[i1], st));
+                    HIPE(hipEventRecord(c->cev1[i1], st));
+                }
+            }
+            have_2a = true;
+        } else if (br.join == JOIN_CHAIN) {
             // identity block followed by an identity block (bf16): relu(bn(W2c t2) + x) and the next block's relu(bn(W2a' .)) in one
             // launch; the 4C-wide sum is written once and not read back (timed as layer i2c; the next branch2a then shows 0)
             const bool t2 = c->timing >= 2;

@@ -68,6 +68,19 @@ hipError_t hpe_launch_gemm_f32s(GemmArgs p, int mode, int tile, hipStream_t st);
 bool hpe_stream_f32s_supported(int M, int N, int K);
 bool hpe_stream_f32s_dual_supported(int M, int N, int K1, int K2, int stride, int Hi, int Ho);
 hipError_t hpe_launch_stream_f32s(GemmArgs p, int mode, int max_walkers, hipStream_t st);
+int hpe_stream_device_cus();  // CUs of the device, asked once per process
+// conv_stream_chain_f32s.hip: the expand 1x1 of a stage-2 block chained with the next block's reduce 1x1 in one persistent launch, both on the
+// bf16 matrix cores (the weights are the layers' fp32 weights, split inside the kernel): t3 = relu(scaleA (wA . [t2 | x]) + shiftA) with
+// C2 = 64 channels of x as the second A source (conv_block form, folded weights), or t3 = relu(scaleA (wA . t2) + shiftA + x) with x the
+// residual [M][256] (C2 = 0); u1 = relu(scaleB (wB . t3) + shiftB), row-major or channel-slab major (u1_slab8).  M % 32 == 0, C = 64, C4 = 256,
+// CP = 64; anything else is refused (hipErrorInvalidValue, nothing is launched).  max_walkers > 0 caps the grid (the outputs do not depend on it)
+struct StreamChainArgs {
+    const float *t2, *x, *wA, *wB, *scaleA, *shiftA, *scaleB, *shiftB;
+    float *t3, *u1;
+    int M, ldwA, ldwB, u1_slab8;
+};
+bool hpe_stream_chain_f32s_supported(int M, int C, int C4, int CP, int C2);
+hipError_t hpe_launch_stream_chain_f32s(const StreamChainArgs& p, int C, int C4, int CP, int C2, int max_walkers, hipStream_t st);
 
 // conv_wino.hip: 3x3/s1 SAME convolution as Winograd F(2x2,3x3); U = G g G^T blocked [N/64][C/8][16][2][64][4], V workspace of
 // hpe_wino_v_floats(B, H, W, C) floats; C % 32 == 0, N % 64 == 0

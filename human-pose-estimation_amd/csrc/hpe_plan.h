@@ -30,8 +30,9 @@ struct HpePlan {
     int min_chunk = 32;         // HPE_MIN_CHUNK: smallest batch chunk that still gets its own stream
     int halo3_two = 4;          // HPE_HALO3_TWO: map sizes of halo3 on the two-workgroups-per-CU form of that kernel (default: 28x28)
     int f32s_min_tiles = 128;   // HPE_F32S_MIN_TILES: launches with fewer tiles than this keep the fp32 kernel (and its split-K)
-    int stream1x1 = 3;          // HPE_STREAM1X1: forms on conv_stream_f32s.hip (1: identity-block expand layers with K <= 128; 2: the dual-source
-                                // launch of res2a); needs f32_split != 0 (f32_split = 0 is the fp32-MFMA plan)
+    int stream1x1 = 15;         // HPE_STREAM1X1: forms on conv_stream_f32s.hip (1: identity-block expand layers with K <= 128; 2: the dual-source
+                                // launch of res2a) and its chained forms on conv_stream_chain_f32s.hip (4: res2b_branch2c + res2c_branch2a instead of
+                                // conv_chain_f32.hip; 8: the dual-source launch of res2a + res2b_branch2a); needs f32_split != 0 (= 0 is the fp32-MFMA plan)
     int stream1x1_min_m = 25088;  // HPE_STREAM1X1_MIN_M: launches with fewer rows keep the fp32 GEMM (default: 8 images of 56x56, 32 of 28x28)
     int stream1x1_walkers = 0;  // HPE_STREAM1X1_WALKERS: cap on the workgroups per 128-cout slice of such a launch (0: two workgroups per CU)
     int wino_streamk = 0;       // HPE_WINO_STREAMK: persistent stream-K scheduling of the F(2x2) Winograd GEMM
@@ -87,6 +88,11 @@ struct BlockRoute {
     ConvRoute r2a, r2b, r2c, r1;  // r2c: the dual-source launch when join == JOIN_DUAL; r1 only when a conv_block joins separately
     int join;
     bool u1_slab8;  // JOIN_CHAIN: the next block's branch2a output is written channel-slab major
+    // the inference walk runs the block's join AND the next block's branch2a as one launch of conv_stream_chain_f32s.hip (bits 4 / 8 of
+    // stream1x1, from stream1x1_min_m rows on).  Beside the route, as ConvRoute::stream: join / r2c name what runs without it, and the next
+    // block's r2a the GEMM its branch2a takes when launched alone
+    bool stream_chain;
+    bool stream_u1_slab8;  // ... and writes the next block's branch2a output channel-slab major (u1_slab8 itself stays what it was: JOIN_CHAIN's)
 };
 struct ResBlock;
 bool stream1x1_dual(const HpePlan& pl, bool bf16, const ResBlock& blk);  // the conv_block whose dual-source launch conv_stream_f32s.hip takes (ConvLayer::w_dual_stream of blk.i2c)

@@ -118,9 +118,10 @@ const PlanOption kPlanOptions[] = {
     {&HpePlan::min_chunk, nullptr, "HPE_MIN_CHUNK", {32, 24}, {ANY, ANY}, NO_LO, NO_HI},
     {&HpePlan::halo3_two, nullptr, "HPE_HALO3_TWO", {4, 4}, {7, 7}, NO_LO, NO_HI},
     {&HpePlan::f32s_min_tiles, nullptr, "HPE_F32S_MIN_TILES", {128, 128}, {ANY, ANY}, NO_LO, NO_HI},
-    // conv_stream_f32s.hip: form mask (1: the K <= 128 identity-block expand layers; 2: the dual-source launch of res2a), fp32 only; the
-    // smallest launch it takes; a cap on its grid (the walk tests)
-    {&HpePlan::stream1x1, nullptr, "HPE_STREAM1X1", {3, 0}, {3, 0}, 0, 3},
+    // conv_stream_f32s.hip: form mask (1: the K <= 128 identity-block expand layers; 2: the dual-source launch of res2a; 4 / 8: the chained
+    // forms of conv_stream_chain_f32s.hip, res2b -> res2c and res2a -> res2b), fp32 only; the smallest launch it takes; a cap on its grid
+    // (the walk tests)
+    {&HpePlan::stream1x1, nullptr, "HPE_STREAM1X1", {15, 0}, {15, 0}, 0, 15},
     {&HpePlan::stream1x1_min_m, nullptr, "HPE_STREAM1X1_MIN_M", {25088, 25088}, {ANY, ANY}, 1, NO_HI},
     {&HpePlan::stream1x1_walkers, nullptr, "HPE_STREAM1X1_WALKERS", {0, 0}, {ANY, ANY}, 0, NO_HI},
     // persistent stream-K scheduling of the Winograd GEMM: opt-in.  It removes the partial last round of workgroups (-7 % on a res4 layer,
@@ -337,6 +338,18 @@ static bool use_chain(const HpePlan& pl, bool bf16, const ResBlock& blk) {
     return (pl.chain_fuse & bit) && hpe_chain_bf16_supported(s2.cin, s2.cout, sn.cout, 0);
 }
 
+// the chained streaming launch of a stage-2 block and the next block's branch2a: form 3 (bit 4) where the plan chains the pair anyway (res2b),
+// form 4 (bit 8) on the dual-source conv_block (res2a).  Part of the split-bf16 family, as stream1x1_layer
+static bool stream_chain(const HpePlan& pl, bool bf16, const ResBlock& blk, int join, int M) {
+    if (bf16 || !pl.f32_split || blk.last || M < pl.stream1x1_min_m) return false;
+    if (!(pl.stream1x1 & (join == JOIN_CHAIN ? 4 : join == JOIN_DUAL ? 8 : 0))) return false;
+    const ConvSpec& s2 = specs()[blk.i2c];
+    const ConvSpec& sn = specs()[blk.i2c + (blk.first ? 2 : 1)];  // the next block's branch2a
+    if (sn.kh != 1 || sn.stride != 1 || sn.cin != s2.cout || s2.hout != s2.hin) return false;
+    if (blk.first && (specs()[blk.i1].stride != 1 || specs()[blk.i1].hin != s2.hin)) return false;
+    return hpe_stream_chain_f32s_supported(M, s2.cin, s2.cout, sn.cout, blk.first ? specs()[blk.i1].cin : 0);
+}
+
 BlockRoute route_block(const HpePlan& pl, bool bf16, const ResBlock& blk, ConvQuery q) {
     BlockRoute b{};
     q.residual = false;
@@ -358,5 +371,7 @@ BlockRoute route_block(const HpePlan& pl, bool bf16, const ResBlock& blk, ConvQu
         q.residual = true;
         b.r2c = route_conv(pl, bf16, blk.i2c, q);
     }
+    b.stream_chain = stream_chain(pl, bf16, blk, b.join, q.B * s2.hout * s2.hout);
+    if (b.stream_chain) b.stream_u1_slab8 = route_conv(pl, bf16, blk.i2c + (blk.first ? 3 : 2), q).in_slab8;
     return b;
 }

@@ -1,5 +1,5 @@
 // lds_dma.h -- the LDS-DMA, wait and barrier idioms of the conv kernels, stated once (device code only): conv_gemm.hip,
-// conv_gemm_f32s.hip, conv_stream_f32s.hip, conv_gemm_bf16.hip, conv_gemm_bf16_p8.hip, conv_chain_bf16.hip, conv_chain_f32.hip, conv3_halo_bf16.hip,
+// conv_gemm_f32s.hip, conv_stream_f32s.hip, conv_stream_chain_f32s.hip, conv_gemm_bf16.hip, conv_gemm_bf16_p8.hip, conv_chain_bf16.hip, conv_chain_f32.hip, conv3_halo_bf16.hip,
 // conv_wino.hip and conv_wino4.hip.  The kernels say at each site only what is specific to it (which slab has landed, what stays in flight).
 //
 // The rules behind every primitive here:

@@ -1100,6 +1100,27 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_debug_chain(self._h, idx2c, t2.data_ptr(), residual.data_ptr(), B, t3.data_ptr(), u1.data_ptr(), occ, self._stream()))
         return t3, u1, (occ[0], occ[1], occ[2])
 
+    def debug_stream_chain(self, idx2c, t2, x, slab8=False, rows=0):
+        """hpe_debug_stream_chain: the chained launch of conv_stream_chain_f32s.hip alone (fp32 contexts).  idx2c = res2b_branch2c with x the
+        residual [B,56,56,256], or res2a_branch2c with x the block input [B,56,56,64].  Returns (t3 [B,56,56,256], u1): u1 [B,56,56,64]
+        row-major, or the flat channel-slab major buffer [8, M, 8] when slab8.  rows: ask the launcher for the first `rows` rows only (zero
+        filled outputs beyond them); a count it refuses raises and launches nothing."""
+        s = CONV_SPECS[idx2c]
+        first = CONV_SPECS[idx2c + 1].name.endswith("branch1")
+        sn = CONV_SPECS[idx2c + (2 if first else 1)]
+        t2 = _require_cuda_tensor(t2, "t2", (s.hin, s.hin, s.cin))
+        x = _require_cuda_tensor(x, "x", (s.hout, s.hout, CONV_SPECS[idx2c + 1].cin if first else s.cout))
+        B = t2.shape[0]
+        t3 = self._new(B, s.hout, s.hout, s.cout)
+        M = int(rows) if rows else B * sn.hout * sn.hout
+        u1 = self._new(sn.cout // 8, M, 8) if slab8 else self._new(B, sn.hout, sn.hout, sn.cout)
+        if rows:
+            t3.zero_()
+            u1.zero_()
+        _lib.check(self.lib.hpe_debug_stream_chain(self._h, int(idx2c), t2.data_ptr(), x.data_ptr(), B, t3.data_ptr(), u1.data_ptr(), int(bool(slab8)),
+                                                   int(rows), self._stream()))
+        return t3, u1
+
     def debug_stem(self, images, rows_per_strip=0):
         images = _require_cuda_tensor(images, "images", (224, 224, 3))
         y = self._new(images.shape[0], 56, 56, 64)

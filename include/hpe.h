@@ -984,12 +984,22 @@ int hpe_debug_conv_route(const HpeConfig* cfg, int idx, int B, int concurrent, i
  * HPE_STREAM1X1_MIN_M rows on, and hpe_debug_conv_route then still names the GEMM the launch takes without it.  Asked of the plan alone, as
  * hpe_debug_conv_route: bit 0 = this launch runs on the streaming kernel, bit 1 = the layer is one of its layers (hpe_finalize keeps the
  * split weights it reads); -1 with hpe_last_error() set for a bad argument.  For res2a_branch2c the answer is about its block's dual-source
- * launch (value 2 of HPE_STREAM1X1). */
+ * launch (value 2 of HPE_STREAM1X1).  The chained forms of that kernel (values 4 and 8 of HPE_STREAM1X1: a stage-2 join and the next
+ * block's branch2a as one launch of conv_stream_chain_f32s.hip, hpe_debug_stream_chain below) are taken by the inference walk alone and
+ * change neither this answer nor hpe_debug_conv_route's. */
 int hpe_debug_conv_stream1x1(const HpeConfig* cfg, int idx, int B, int concurrent, int residual);
 /* The dual-source launch of a conv_block alone (fp32 contexts): y [B,ho,ho,cout] = relu(bn2c(W2c . t2) + bn1(W1 . x at the shortcut's stride)),
  * t2_dev [B,ho,ho,cin of idx2c] the branch2b output, x_dev [B,hi,hi,cin of branch1] the block input, through the kernel the plan routes
  * that launch to at batch B.  HPE_ERR_INVALID unless idx2c is the branch2c of a conv_block joined as the dual-source GEMM. */
 int hpe_debug_dual(hpe_ctx* ctx, int idx2c, const float* t2_dev, const float* x_dev, int B, float* y_dev, void* stream);
+/* The chained streaming launch of conv_stream_chain_f32s.hip alone (fp32 contexts), whatever HPE_STREAM1X1 says.  idx2c = res2b_branch2c:
+ * t3 [B,56,56,256] = relu(bn(conv2c(t2)) + x) with x_dev the residual [B,56,56,256]; idx2c = res2a_branch2c: t3 = relu(bn(conv2c(t2)) +
+ * bn(conv1(x))) with x_dev the block input [B,56,56,64]; both: u1 = relu(bn(conv2a_next(t3))), [B,56,56,64] row-major, or channel-slab
+ * major u1[(n / 8) * M + m][n % 8] when slab8 != 0.  rows: 0 = all M = B * 56 * 56 rows, else the launch is asked for the first `rows`
+ * rows of the batch (slab8 then counts M = rows).  The launcher takes whole 32-row tiles only: HPE_ERR_INVALID, and nothing is launched,
+ * for any other row count, for rows past the batch and for any idx2c but these two. */
+int hpe_debug_stream_chain(hpe_ctx* ctx, int idx2c, const float* t2_dev, const float* x_dev, int B, float* t3_dev, float* u1_dev, int slab8,
+                           int rows, void* stream);
 /* The dense mode of hpe_debug_gemm_ex with scale = ones, shift = zeros, lda = ldw = K, ldy = ldres = N and no split-K
  * workspace: y[M,N] = act(x[M,K] . wt[n][k]^T (+ residual)); K % 32 == 0; N <= 1024; tile 0..6 as above.  Needs the regressor loaded. */
 int hpe_debug_gemm(hpe_ctx* ctx, const float* x_dev, const float* wt_dev, int M, int N, int K, int w_rows, int tile,
