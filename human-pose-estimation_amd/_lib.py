@@ -283,6 +283,13 @@ _PROTOS = {
     "hpe_debug_avgpool_backward_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_encoder_stash_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_encoder_stash_batch_mixed": (C.c_int, [C.c_void_p]),
+    "hpe_encoder_train_reserve_batchnorm_mixed": (C.c_int, [C.c_void_p, C.c_int]),
+    "hpe_encoder_train_ws_floats_batchnorm_mixed": (C.c_longlong, [C.c_int]),
+    "hpe_encoder_forward_batchnorm_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hpe_encoder_backward_batchnorm_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_debug_conv_batchnorm_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_debug_conv_backward_batchnorm_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_debug_encoder_stash_raw_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_encoder_stat_floats": (C.c_int, []),
     "hpe_encoder_stat_offset": (C.c_int, [C.c_int, C.c_int]),
     "hpe_encoder_train_reserve_batchnorm": (C.c_int, [C.c_void_p, C.c_int]),

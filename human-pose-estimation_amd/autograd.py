@@ -128,7 +128,8 @@ class EncoderFunction(torch.autograd.Function):
     ``params`` -- the flat tensor the optimiser owns, which must EQUAL what the engine holds (``set_encoder_params_dev`` after every step):
     it carries ``.grad``, the arithmetic reads the engine's weights.  Images get no gradient.  hpe_encoder_backward is stateless, so only
     the images are saved.  ``bn``: "frozen" or "batch" (hpe_encoder_forward_batchnorm / hpe_encoder_backward_batchnorm).  ``precision``:
-    "fp32" or "bf16" (hpe_encoder_forward_train_mixed / hpe_encoder_backward_mixed; frozen statistics only): features and ``.grad`` stay fp32."""
+    "fp32" or "bf16" (hpe_encoder_forward_train_mixed / hpe_encoder_backward_mixed; frozen statistics only) or "mixed" (those two, or
+    with bn="batch" hpe_encoder_forward_batchnorm_mixed / hpe_encoder_backward_batchnorm_mixed): features and ``.grad`` stay fp32."""
 
     @staticmethod
     def forward(ctx, engine, images, params, bn="frozen", precision="fp32"):

@@ -315,20 +315,39 @@ bool bad_shape(long M, int N) { return M < 1 || M > 0x7fffffffL / 2 || N < 64 ||
 
 int bn_slices(int M, int N) { return bad_shape(M, N) ? -1 : geom(M, N).slices; }
 
+// the second launch of each reduction: from the slices' partials part[slice][2][N], whichever kernel wrote them (encoder_bn_bf16.hip too)
+hipError_t bn_finish_stats(const double* part, int slices, int M, int N, float eps, float* mu, float* var, float* r, hipStream_t st) {
+    hipLaunchKernelGGL(bn_stats_finish_kernel, dim3(N / 16), dim3(256), 0, st, part, slices, M, N, eps, mu, var, r);
+    return hipGetLastError();
+}
+
+hipError_t bn_finish_sums(const double* part, int slices, int N, double* sums, hipStream_t st) {
+    hipLaunchKernelGGL(bn_sums_kernel, dim3(N / 16), dim3(256), 0, st, part, slices, N, sums);
+    return hipGetLastError();
+}
+
+hipError_t bn_finish_bwd(const double* part, int slices, int N, float* db, float* dgamma, float* dbeta, hipStream_t st) {
+    hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3(N / 16), dim3(256), 0, st, part, slices, N, db, dgamma, dbeta);
+    return hipGetLastError();
+}
+
+hipError_t bn_finish_bwd_sums(const double* part, int slices, int N, double* sums, float* db, float* dgamma, float* dbeta, hipStream_t st) {
+    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(N / 16), dim3(256), 0, st, part, slices, N, sums, db, dgamma, dbeta);
+    return hipGetLastError();
+}
+
 hipError_t bn_launch_stats(const float* z, int M, int N, float eps, double* part, float* mu, float* var, float* r, hipStream_t st) {
     if (bad_shape(M, N)) return hipErrorInvalidValue;
     const BnGeom g = geom(M, N);
     hipLaunchKernelGGL(bn_stats_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(z), M, N, g.cg, g.rows, g.P, part);
-    hipLaunchKernelGGL(bn_stats_finish_kernel, dim3(N / 16), dim3(256), 0, st, part, g.slices, M, N, eps, mu, var, r);
-    return hipGetLastError();
+    return bn_finish_stats(part, g.slices, M, N, eps, mu, var, r, st);
 }
 
 hipError_t bn_launch_stats_sums(const float* z, int M, int N, double* part, double* sums, hipStream_t st) {
     if (bad_shape(M, N)) return hipErrorInvalidValue;
     const BnGeom g = geom(M, N);
     hipLaunchKernelGGL(bn_stats_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(z), M, N, g.cg, g.rows, g.P, part);
-    hipLaunchKernelGGL(bn_sums_kernel, dim3(N / 16), dim3(256), 0, st, part, g.slices, N, sums);
-    return hipGetLastError();
+    return bn_finish_sums(part, g.slices, N, sums, st);
 }
 
 hipError_t bn_launch_stats_from_sums(const double* sums, double M, int N, float eps, float* mu, float* var, float* r, hipStream_t st) {
@@ -350,8 +369,7 @@ hipError_t bn_launch_bwd_reduce(const float* dy, const float* y, const float* z,
     if (bad_shape(M, N)) return hipErrorInvalidValue;
     const BnGeom g = geom(M, N);
     hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(dy), q4(y), q4(z), q4(mu), q4(r), M, N, g.cg, g.rows, g.P, part);
-    hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3(N / 16), dim3(256), 0, st, part, g.slices, N, db, dgamma, dbeta);
-    return hipGetLastError();
+    return bn_finish_bwd(part, g.slices, N, db, dgamma, dbeta, st);
 }
 
 hipError_t bn_launch_bwd_sums(const float* dy, const float* y, const float* z, const float* mu, const float* r, int M, int N, double* part, double* sums,
@@ -359,8 +377,7 @@ hipError_t bn_launch_bwd_sums(const float* dy, const float* y, const float* z, c
     if (bad_shape(M, N)) return hipErrorInvalidValue;
     const BnGeom g = geom(M, N);
     hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(dy), q4(y), q4(z), q4(mu), q4(r), M, N, g.cg, g.rows, g.P, part);
-    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(N / 16), dim3(256), 0, st, part, g.slices, N, sums, db, dgamma, dbeta);
-    return hipGetLastError();
+    return bn_finish_bwd_sums(part, g.slices, N, sums, db, dgamma, dbeta, st);
 }
 
 hipError_t bn_launch_bwd_from_sums(const double* sums, int N, float* red, hipStream_t st) {

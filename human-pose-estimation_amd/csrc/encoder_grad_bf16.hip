@@ -261,23 +261,24 @@ hipError_t mx_cast_launch(hpe_ctx* c, int first, int segs, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t mx_conv_forward(hpe_ctx* c, int idx, cmx16 x, int B, cmx16 res, int relu, mx16 y, hipStream_t st) {
+hipError_t mx_conv_forward(hpe_ctx* c, int idx, cmx16 x, int B, cmx16 res, int relu, mx16 y, hipStream_t st, const float* scale, const float* shift) {
     const ConvSpec& s = specs()[idx];
     const ConvLayer& L = c->conv[idx];
+    if (!scale) scale = L.scale, shift = L.shift;
     const int kp = conv_k_pad(idx, true);
     // the kernel and tile a bf16 context would take for this layer alone on the device (a bf16 route never asks for a Winograd workspace)
     const ConvRoute r = route_conv(c->plan, true, idx, ConvQuery{B, false, res != nullptr, false});
     if (r.kernel == CONV_K_HALO3) {
         Halo3Args h{};
         h.x = reinterpret_cast<const __bf16*>(x), h.w = reinterpret_cast<const __bf16*>(c->et.mx_w[idx]), h.y = reinterpret_cast<__bf16*>(y);
-        h.scale = L.scale, h.shift = L.shift;
+        h.scale = scale, h.shift = shift;
         h.M = B * s.hout * s.hout, h.N = s.cout, h.ldw = kp;
         h.relu = relu, h.two = c->plan.halo3_two;
         return hpe_launch_halo3_bf16(h, s.hin, s.cin, st);
     }
     if (r.kernel != CONV_K_BF16 && r.kernel != CONV_K_BF16_P8) return hipErrorInvalidValue;
     GemmArgs p{};
-    p.x = as_f(x), p.w = as_f(c->et.mx_w[idx]), p.scale = L.scale, p.shift = L.shift, p.res = as_f(res), p.y = as_f(y), p.zero = c->zeros;
+    p.x = as_f(x), p.w = as_f(c->et.mx_w[idx]), p.scale = scale, p.shift = shift, p.res = as_f(res), p.y = as_f(y), p.zero = c->zeros;
     p.M = B * s.hout * s.hout, p.N = s.cout, p.K = kp;
     p.lda = s.cin, p.ldw = kp, p.w_rows = L.n_pad, p.ldy = p.ldres = s.cout;
     p.Hi = p.Wi = s.hin, p.Cin = s.cin, p.Ho = p.Wo = s.hout, p.stride = s.stride;
@@ -293,7 +294,7 @@ void mx_gate(cmx16 dy, cmx16 y, const float* s, mx16 dz, mx16 dzs, long n, int N
                        reinterpret_cast<bf16x8*>(dz), reinterpret_cast<bf16x8*>(dzs), n / 8, N / 8);
 }
 
-hipError_t mx_weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* grad_layer, hipStream_t st) {
+hipError_t mx_weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* grad_layer, hipStream_t st, bool bn) {
     const ConvSpec& s = specs()[idx];
     EncTrainWork& w = c->et;
     const bool stem = idx == 0;
@@ -326,7 +327,8 @@ hipError_t mx_weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* 
     const unsigned short* w16 = stem ? w.mx_w[0] : w.mx_dxw[idx];
     const int wrow = stem ? conv_k_pad(0, true) : s.kh * s.kw * s.cout;
     hipLaunchKernelGGL(conv_wg_fixup_bf16_kernel, dim3(a.n_nt, n_kc), dim3(256), 0, st, w.partial, slices, K, a.K, a.N, w16, stem ? 1 : 0, s.cin,
-                       s.kh * s.kw, wrow, c->conv[idx].scale, grad_layer, w.wgp);
+                       s.kh * s.kw, wrow, bn ? c->ones : c->conv[idx].scale, grad_layer, w.wgp);
+    if (bn) return hipGetLastError();
     return wg_finish(c, idx, n_kc, slices, grad_layer, st);
 }
 

@@ -13,8 +13,9 @@
 // sum_m dz * conv_raw = sum_k W[k][n] G[k][n] exactly, so the BatchNorm gradient needs neither the pre-BN tensor nor a division by s.
 //
 // The kernels and their launchers are in encoder_grad.hip, those of BatchNorm with batch statistics in encoder_bn.hip, those of the
-// mixed-precision walk (bf16 activations and cotangents on this fp32 context) in encoder_grad_bf16.hip; this file holds the layout, the
-// reserves, the two walks (one forward, one backward, each taking the BatchNorm mode or the mixed precision as a per-layer choice) and the C ABI.
+// mixed-precision walks (bf16 activations and cotangents on this fp32 context) in encoder_grad_bf16.hip and, for their BatchNorm with
+// batch statistics, encoder_bn_bf16.hip; this file holds the layout, the reserves, the two walks (one forward, one backward, each taking
+// the BatchNorm mode and the precision as per-layer choices) and the C ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -110,6 +111,12 @@ void train_buffers_mixed(EncTrainWork& w, int B, F&& f) {
     f(w.mx_cast, (size_t)MX_CAST_SEGS * sizeof(MxCastSeg) / sizeof(float), false);
 }
 
+// ... and what hpe_encoder_train_reserve_batchnorm_mixed adds to those two: the bf16 raw-output stash
+template <class F>
+void train_buffers_bn_mixed(EncTrainWork& w, int B, F&& f) {
+    f(w.mx_zstash, (size_t)B * layout().stash_pool / 2, false);
+}
+
 struct TrainAlloc {  // rc keeps the first failure, which ends the allocations
     hpe_ctx* c;
     int rc = HPE_OK;
@@ -120,19 +127,23 @@ struct TrainAlloc {  // rc keeps the first failure, which ends the allocations
     }
 };
 
-size_t ws_floats(int B, bool bn, bool mixed = false) {
+size_t ws_floats(int B, bool bn, bool mixed = false, bool bn_mixed = false) {
     EncTrainWork w;
     size_t n = encoder_repack_reserve_floats();  // the layer table of hpe_encoder_set_params_dev, allocated by encoder_repack_reserve
     auto add = [&n](auto&, size_t floats, bool) { n += floats; };
     train_buffers(w, B, add);
     if (bn) train_buffers_bn(w, B, add);
     if (mixed) train_buffers_mixed(w, B, add);
+    if (bn_mixed) train_buffers_bn_mixed(w, B, add);
     return n;
 }
 
-// the walks: frozen statistics in fp32, batch statistics in fp32, frozen statistics in mixed precision.  A mixed walk keeps bf16
-// elements behind the float pointers of its activations and cotangents (as a bf16 context does behind ConvLayer::w)
-enum Walk { WALK_FROZEN, WALK_BATCH, WALK_MIXED };
+// the walks: frozen statistics in fp32, batch statistics in fp32, frozen statistics in mixed precision, batch statistics in mixed
+// precision.  A mixed walk keeps bf16 elements behind the float pointers of its activations and cotangents (as a bf16 context does
+// behind ConvLayer::w)
+enum Walk { WALK_FROZEN, WALK_BATCH, WALK_MIXED, WALK_MIXED_BATCH };
+bool walk_bn(Walk wk) { return wk == WALK_BATCH || wk == WALK_MIXED_BATCH; }
+bool walk_mx(Walk wk) { return wk == WALK_MIXED || wk == WALK_MIXED_BATCH; }
 cmx16 h16(const float* p) { return reinterpret_cast<cmx16>(p); }
 mx16 h16(float* p) { return reinterpret_cast<mx16>(p); }
 float* f16(mx16 p) { return reinterpret_cast<float*>(p); }
@@ -157,7 +168,7 @@ float* stash_of(hpe_ctx* c, int idx, int B) {
 
 // ... of the walk's own stash: the mixed one has the same layout in bf16 elements
 float* stash_of(hpe_ctx* c, Walk wk, int idx, int B) {
-    if (wk != WALK_MIXED) return stash_of(c, idx, B);
+    if (!walk_mx(wk)) return stash_of(c, idx, B);
     const EncLayout& l = layout();
     return f16(c->et.mx_stash + (size_t)B * (idx < 0 ? l.stash_pool : l.stash[idx]));
 }
@@ -165,6 +176,7 @@ float* stash_of(hpe_ctx* c, Walk wk, int idx, int B) {
 // ---- BatchNorm with batch statistics (encoder_bn.hip holds the kernels): z kept beside y, the layer's statistics in its slots
 
 float* zstash_of(hpe_ctx* c, int idx, int B) { return c->et.zstash + (size_t)B * layout().stash[idx]; }
+mx16 mx_zstash_of(hpe_ctx* c, int idx, int B) { return c->et.mx_zstash + (size_t)B * layout().stash[idx]; }
 
 struct BnSlots {
     float *mu, *var, *r;
@@ -231,14 +243,52 @@ hipError_t layer_gate_bn(hpe_ctx* c, int idx, const float* dy, const float* y, c
     return bn_launch_bwd_apply(dy, y, z, s.mu, s.r, gamma, red + N, red, M, N, dz, dzraw, st, rows_all(c, idx));
 }
 
+// layer_forward_bn in mixed precision: z16 = RNE(conv(x16, W16) + b) through the layer's bf16 route, the statistics OF z16 into the same
+// slots, y16 = RNE(act(BN(z16) (+ res16))).  Only the first-stage kernels differ: the hook sees the same sums at the same place
+hipError_t layer_forward_bn16(hpe_ctx* c, int idx, cmx16 x, int B, cmx16 res, int relu, mx16 z, mx16 y, const BnSlots& s, hipStream_t st,
+                              bool reduce = false) {
+    const ConvSpec& sp = specs()[idx];
+    const EncLayout& l = layout();
+    const float* flat = c->et.flat;
+    const int M = B * sp.hout * sp.hout;
+    HIPE(mx_conv_forward(c, idx, x, B, nullptr, 0, z, st, c->ones, flat + l.off[idx][1]));
+    if (reduce) {
+        HIPE(bn16_launch_stats_sums(z, M, sp.cout, c->et.bn_part, reduce_sums(c), st));
+        HIPE(reduce_call(c, idx, 2LL * sp.cout, st));
+        HIPE(bn_launch_stats_from_sums(reduce_sums(c), rows_all(c, idx), sp.cout, c->cfg.bn_eps, s.mu, s.var, s.r, st));
+    } else {
+        HIPE(bn16_launch_stats(z, M, sp.cout, c->cfg.bn_eps, c->et.bn_part, s.mu, s.var, s.r, st));
+    }
+    return bn16_launch_apply(z, s.mu, s.r, flat + l.off[idx][2], flat + l.off[idx][3], res, relu, y, M, sp.cout, st);
+}
+
+// ... and layer_gate_bn: db (= 0), dgamma, dbeta (fp32) into grad_layer; dz (bf16, exact; may be nullptr, may alias dy) and dzraw16
+hipError_t layer_gate_bn16(hpe_ctx* c, int idx, cmx16 dy, cmx16 y, cmx16 z, int B, const BnSlots& s, float* grad_layer, mx16 dz, mx16 dzraw,
+                           hipStream_t st, bool reduce = false) {
+    const ConvSpec& sp = specs()[idx];
+    const int M = B * sp.hout * sp.hout, N = sp.cout, kn = sp.kh * sp.kw * sp.cin * N;
+    float *db = grad_layer + kn, *dgamma = db + N, *dbeta = dgamma + N;
+    const float* gamma = c->et.flat + layout().off[idx][2];
+    if (!reduce) {
+        HIPE(bn16_launch_bwd_reduce(dy, y, z, s.mu, s.r, M, N, c->et.bn_part, db, dgamma, dbeta, st));
+        return bn16_launch_bwd_apply(dy, y, z, s.mu, s.r, gamma, dgamma, dbeta, M, N, dz, dzraw, st);
+    }
+    float* red = reduce_grads(c);
+    HIPE(bn16_launch_bwd_sums(dy, y, z, s.mu, s.r, M, N, c->et.bn_part, reduce_sums(c), db, dgamma, dbeta, st));
+    HIPE(reduce_call(c, idx, 2LL * N, st));
+    HIPE(bn_launch_bwd_from_sums(reduce_sums(c), N, red, st));
+    return bn16_launch_bwd_apply(dy, y, z, s.mu, s.r, gamma, red + N, red, M, N, dz, dzraw, st, rows_all(c, idx));
+}
+
 // The training forward, every activation kept in the stash.  bn (batch statistics): z kept beside y, the statistics in the layers' slots
 //                       mixed: the weight operands are cast from the live fp32 weights first, every layer runs on the bf16 GEMMs
 hipError_t forward_train(hpe_ctx* c, Walk wk, const float* images, int B, float* features, hipStream_t st) {
-    const bool bn = wk == WALK_BATCH, mx = wk == WALK_MIXED;
+    const bool bn = walk_bn(wk), mx = walk_mx(wk);
     const bool reduce = bn && c->et.reduce != nullptr;
     auto stash = [&](int idx) { return stash_of(c, wk, idx, B); };
     auto layer = [&](int idx, const float* x, const float* res, int relu) {
         float* y = stash(idx);
+        if (mx && bn) return layer_forward_bn16(c, idx, h16(x), B, h16(res), relu, mx_zstash_of(c, idx, B), h16(y), bn_slots(c, idx, false), st, reduce);
         if (mx) return mx_conv_forward(c, idx, h16(x), B, h16(res), relu, h16(y), st);
         return bn ? layer_forward_bn(c, idx, x, B, res, relu, zstash_of(c, idx, B), y, bn_slots(c, idx, false), st, reduce)
                   : run_conv_nhwc(c, idx, x, B, res, relu, y, st);
@@ -279,10 +329,16 @@ struct GateOut {
 //           weight gradient reads dz
 //   batch   the bias / gamma / beta gradients go into grad_flat, copy = dzraw, which both gradients read; dz is written only if kept
 //   mixed   as frozen on bf16 elements; copy = RNE(dz * s)
+//   mixed batch   as batch on bf16 elements; copy = dzraw16, the bias / gamma / beta gradients stay fp32
 hipError_t layer_gate(hpe_ctx* c, Walk wk, int idx, float* dy, bool gated, bool keep, float* copy, int B, float* grad_flat, hipStream_t st,
                       GateOut* o) {
     const ConvSpec& s = specs()[idx];
     const float* y = gated ? stash_of(c, wk, idx, B) : nullptr;
+    if (wk == WALK_MIXED_BATCH) {
+        *o = {copy, copy};
+        return layer_gate_bn16(c, idx, h16(dy), h16(y), mx_zstash_of(c, idx, B), B, bn_slots(c, idx, false), grad_flat + layout().off[idx][0],
+                               keep ? h16(dy) : nullptr, h16(copy), st, c->et.reduce != nullptr);
+    }
     if (wk == WALK_MIXED) {
         float* dzs = idx == 0 ? nullptr : copy;
         mx_gate(h16(dy), h16(y), dzs ? c->conv[idx].scale : nullptr, gated ? h16(dy) : nullptr, h16(dzs), (long)B * s.hout * s.hout * s.cout, s.cout, st);
@@ -302,7 +358,7 @@ hipError_t layer_gate(hpe_ctx* c, Walk wk, int idx, float* dy, bool gated, bool 
 
 hipError_t backward(hpe_ctx* c, Walk wk, const float* images, int B, const float* grad_features, float* grad_flat, hipStream_t st) {
     EncTrainWork& w = c->et;
-    const bool bn = wk == WALK_BATCH, mx = wk == WALK_MIXED;
+    const bool bn = walk_bn(wk), mx = walk_mx(wk);
     HIPE(forward_train(c, wk, images, B, w.feat, st));
     auto stash = [&](int idx) { return stash_of(c, wk, idx, B); };
     auto lgate = [&](int idx, float* dy, bool gated, bool keep, float* copy, GateOut* o) {
@@ -310,7 +366,7 @@ hipError_t backward(hpe_ctx* c, Walk wk, const float* images, int B, const float
     };
     auto wgrad = [&](int idx, const float* x, const float* dz) {
         float* grad_layer = grad_flat + layout().off[idx][0];
-        return mx ? mx_weight_grad(c, idx, h16(x), h16(dz), B, grad_layer, st) : weight_grad(c, idx, x, dz, B, grad_layer, st, bn);
+        return mx ? mx_weight_grad(c, idx, h16(x), h16(dz), B, grad_layer, st, bn) : weight_grad(c, idx, x, dz, B, grad_layer, st, bn);
     };
     auto dgrad = [&](int idx, const float* dzs, const float* res, float* out) {
         return mx ? mx_data_grad(c, idx, h16(dzs), B, h16(res), h16(out), st) : data_grad(c, idx, dzs, B, res, out, st);
@@ -382,7 +438,7 @@ int debug_data_grad(hpe_ctx* c, int idx, const float* dzs, int B, float* dx, hip
 }
 
 // what a call needs: nothing reserved yet, hpe_encoder_train_reserve, or hpe_encoder_train_reserve_batchnorm as well
-enum Reserve { RESERVE_NONE, RESERVE_FROZEN, RESERVE_BN, RESERVE_MIXED };
+enum Reserve { RESERVE_NONE, RESERVE_FROZEN, RESERVE_BN, RESERVE_MIXED, RESERVE_BN_MIXED };
 
 int check_train(hpe_ctx* c, int B, Reserve need = RESERVE_FROZEN) {
     if (!c) return fail(HPE_ERR_INVALID, "null ctx");
@@ -393,8 +449,15 @@ int check_train(hpe_ctx* c, int B, Reserve need = RESERVE_FROZEN) {
     if (need != RESERVE_NONE && c->et.B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve() has not been called");
     if (need == RESERVE_BN && c->et.bn_B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_batchnorm() has not been called");
     if (need == RESERVE_MIXED && c->et.mx_B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_mixed() has not been called");
-    static const char* const range[] = {"max_batch", "reserved batch", "batch of the batch-norm reserve", "batch of the mixed-precision reserve"};
-    const int top = need == RESERVE_NONE ? c->cfg.max_batch : need == RESERVE_FROZEN ? c->et.B : need == RESERVE_BN ? c->et.bn_B : c->et.mx_B;
+    if (need == RESERVE_BN_MIXED && c->et.mxbn_B == 0)
+        return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_batchnorm_mixed() has not been called");
+    static const char* const range[] = {"max_batch", "reserved batch", "batch of the batch-norm reserve", "batch of the mixed-precision reserve",
+                                        "batch of the mixed-precision batch-norm reserve"};
+    const int top = need == RESERVE_NONE     ? c->cfg.max_batch
+                    : need == RESERVE_FROZEN ? c->et.B
+                    : need == RESERVE_BN     ? c->et.bn_B
+                    : need == RESERVE_MIXED  ? c->et.mx_B
+                                             : c->et.mxbn_B;
     if (B < 1 || B > top) return fail(HPE_ERR_INVALID, "batch " + std::to_string(B) + " outside [1, " + range[need] + "]");
     return HPE_OK;
 }
@@ -422,26 +485,32 @@ int walk_result(hpe_ctx* c, hipError_t e, const char* what) {
 }
 
 void walk_done(hpe_ctx* c, Walk wk, int B) {
-    if (wk == WALK_MIXED) {  // the mixed stash has its own batch counter: the fp32 stash is as it was
+    if (walk_mx(wk)) {  // the mixed stash has its own batch counter: the fp32 stash is as it was
         c->et.mx_stash_B = B;
-        return;
+        if (wk == WALK_MIXED) return;
+        c->et.mx_zstash_B = B;
+    } else {
+        c->et.stash_B = B;
+        if (wk != WALK_BATCH) return;
     }
-    c->et.stash_B = B;
-    if (wk != WALK_BATCH) return;
+    // the statistics in bn_batch are those of the last batch-statistics walk of either precision
+    c->et.bn_stat_mixed = walk_mx(wk);
     c->et.bn_stat_B = B;
     c->et.bn_stat_G = c->et.reduce ? c->et.reduce_G : B;
 }
 
-Reserve reserve_of(Walk wk) { return wk == WALK_BATCH ? RESERVE_BN : wk == WALK_MIXED ? RESERVE_MIXED : RESERVE_FROZEN; }
+Reserve reserve_of(Walk wk) {
+    return wk == WALK_BATCH ? RESERVE_BN : wk == WALK_MIXED ? RESERVE_MIXED : wk == WALK_MIXED_BATCH ? RESERVE_BN_MIXED : RESERVE_FROZEN;
+}
 
-// hpe_encoder_forward_train / _batchnorm / _mixed and hpe_encoder_backward / _batchnorm / _mixed
+// hpe_encoder_forward_train / _batchnorm / _mixed / _batchnorm_mixed and hpe_encoder_backward / _batchnorm / _mixed / _batchnorm_mixed
 int forward_entry(hpe_ctx* c, Walk wk, const float* images, int B, float* features, void* stream) {
     int rc = check_train(c, B, reserve_of(wk));
     if (rc) return rc;
     if (!images || !features) return fail(HPE_ERR_INVALID, "null pointer");
     DeviceGuard g(c->cfg.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((rc = check_reduce(c, wk == WALK_BATCH, B, st))) return rc;
+    if ((rc = check_reduce(c, walk_bn(wk), B, st))) return rc;
     if ((rc = walk_result(c, forward_train(c, wk, images, B, features, st), "forward"))) return rc;
     walk_done(c, wk, B);
     return HPE_OK;
@@ -453,7 +522,7 @@ int backward_entry(hpe_ctx* c, Walk wk, const float* images, int B, const float*
     if (!images || !grad_features || !grad_flat) return fail(HPE_ERR_INVALID, "null pointer");
     DeviceGuard g(c->cfg.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((rc = check_reduce(c, wk == WALK_BATCH, B, st))) return rc;
+    if ((rc = check_reduce(c, walk_bn(wk), B, st))) return rc;
     if ((rc = walk_result(c, backward(c, wk, images, B, grad_features, grad_flat, st), "backward"))) return rc;
     walk_done(c, wk, B);
     return HPE_OK;
@@ -776,6 +845,7 @@ int hpe_debug_encoder_stash_raw(hpe_ctx* c, int idx, float* out, void* stream) {
     if (idx < 0 || idx >= HPE_NUM_CONV || !out) return fail(HPE_ERR_INVALID, "bad argument");
     const int B = c->et.bn_stat_B;
     if (B == 0) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw: no batch-statistics forward has run");
+    if (c->et.bn_stat_mixed) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw: the last batch-statistics forward was a mixed-precision one");
     if (c->et.stash_B != B) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw: a frozen-statistics forward of another batch has refilled the stash since");
     DeviceGuard g(c->cfg.device);
     const size_t n = (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
@@ -959,6 +1029,103 @@ int hpe_debug_encoder_stash_mixed(hpe_ctx* c, int idx, void* out, void* stream) 
     DeviceGuard g(c->cfg.device);
     const size_t n = idx < 0 ? (size_t)POOL_FLOATS : (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
     HIP_TRY(hipMemcpyAsync(out, stash_of(c, WALK_MIXED, idx, B), (size_t)B * n * sizeof(unsigned short), hipMemcpyDeviceToDevice,
+                           static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
+// ---- mixed precision with batch statistics (encoder_bn_bf16.hip holds the kernels): both reserves and a bf16 raw-output stash
+
+long long hpe_encoder_train_ws_floats_batchnorm_mixed(int B) { return B < 1 ? 0 : (long long)ws_floats(B, true, true, true); }
+
+int hpe_encoder_train_reserve_batchnorm_mixed(hpe_ctx* c, int B) {
+    int rc = hpe_encoder_train_reserve_mixed(c, B);
+    if (rc) return rc;
+    if ((rc = hpe_encoder_train_reserve_batchnorm(c, B))) return rc;
+    EncTrainWork& w = c->et;
+    if (w.mxbn_B != 0)
+        return B <= w.mxbn_B ? HPE_OK : fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_batchnorm_mixed: already reserved for a smaller batch");
+    DeviceGuard g(c->cfg.device);
+    TrainAlloc alloc{c};
+    train_buffers_bn_mixed(w, B, alloc);
+    if (alloc.rc) return alloc.rc;
+    w.mxbn_B = B;
+    return HPE_OK;
+}
+
+int hpe_encoder_forward_batchnorm_mixed(hpe_ctx* c, const float* images, int B, float* features, void* stream) {
+    return forward_entry(c, WALK_MIXED_BATCH, images, B, features, stream);
+}
+
+int hpe_encoder_backward_batchnorm_mixed(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
+    return backward_entry(c, WALK_MIXED_BATCH, images, B, grad_features, grad_flat, stream);
+}
+
+int hpe_debug_conv_batchnorm_mixed(hpe_ctx* c, int idx, const void* x, int B, const void* residual, int relu, void* y, void* z_out, float* stats_out,
+                                   void* stream) {
+    int rc = check_train(c, B, RESERVE_BN_MIXED);
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !y || !z_out || !stats_out) return fail(HPE_ERR_INVALID, "bad argument");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    EncTrainWork& w = c->et;
+    HIP_TRY(mx_cast_launch(c, idx, 1, st));
+    cmx16 in = static_cast<cmx16>(x);
+    if (idx == 0) {  // x is the fp32 image tensor
+        HIP_TRY(hpe_launch_pad_input_bf16(static_cast<const float*>(x), w.mx_padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
+        in = w.mx_padded;
+    }
+    const BnSlots s = bn_slots(c, idx, true);
+    HIP_TRY(layer_forward_bn16(c, idx, in, B, static_cast<cmx16>(residual), relu, static_cast<mx16>(z_out), static_cast<mx16>(y), s, st));
+    const size_t n = (size_t)specs()[idx].cout * sizeof(float);
+    HIP_TRY(hipMemcpyAsync(stats_out, s.mu, n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(stats_out + specs()[idx].cout, s.var, n, hipMemcpyDeviceToDevice, st));
+    return HPE_OK;
+}
+
+int hpe_debug_conv_backward_batchnorm_mixed(hpe_ctx* c, int idx, const void* x, const void* z, const void* y, const void* dy, int B, void* dx,
+                                            float* grad_layer, void* stream) {
+    int rc = check_train(c, B, RESERVE_BN_MIXED);
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !z || !dy || !grad_layer) return fail(HPE_ERR_INVALID, "bad argument");
+    if (idx == 0 && dx) return fail(HPE_ERR_INVALID, "hpe_debug_conv_backward_batchnorm_mixed: conv1 has no data gradient, dx_dev must be NULL");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ConvSpec& s = specs()[idx];
+    EncTrainWork& w = c->et;
+    HIP_TRY(mx_cast_launch(c, idx, 1, st));
+    if (idx > 0) HIP_TRY(mx_cast_launch(c, HPE_NUM_CONV - 1 + idx, 1, st));
+    cmx16 in = static_cast<cmx16>(x);
+    if (idx == 0) {  // x is the fp32 image tensor
+        HIP_TRY(hpe_launch_pad_input_bf16(static_cast<const float*>(x), w.mx_padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
+        in = w.mx_padded;
+    }
+    const BnSlots sl = bn_slots(c, idx, true);
+    cmx16 z16 = static_cast<cmx16>(z);
+    HIP_TRY(bn16_launch_stats(z16, B * s.hout * s.hout, s.cout, c->cfg.bn_eps, w.bn_part, sl.mu, sl.var, sl.r, st));
+    HIP_TRY(layer_gate_bn16(c, idx, static_cast<cmx16>(dy), static_cast<cmx16>(y), z16, B, sl, grad_layer, nullptr, w.mx_sbig, st));
+    HIP_TRY(mx_weight_grad(c, idx, in, w.mx_sbig, B, grad_layer, st, true));
+    if (!dx) return HPE_OK;
+    if (s.stride == 1) {
+        HIP_TRY(mx_data_grad(c, idx, w.mx_sbig, B, nullptr, static_cast<mx16>(dx), st));
+    } else {  // a stride-2 layer's data gradient comes on the low-resolution map
+        HIP_TRY(mx_data_grad(c, idx, w.mx_sbig, B, nullptr, w.mx_t0, st));
+        mx_scatter2(w.mx_t0, static_cast<mx16>(dx), B, s.hout, s.cin, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return HPE_OK;
+}
+
+int hpe_debug_encoder_stash_raw_mixed(hpe_ctx* c, int idx, void* out, void* stream) {
+    int rc = check_train(c, 1, RESERVE_BN_MIXED);
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV || !out) return fail(HPE_ERR_INVALID, "bad argument");
+    const int B = c->et.mx_zstash_B;
+    if (B == 0) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw_mixed: no mixed-precision batch-statistics forward has run");
+    if (c->et.mx_stash_B != B)
+        return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw_mixed: a frozen-statistics mixed forward of another batch has refilled the stash since");
+    DeviceGuard g(c->cfg.device);
+    const size_t n = (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
+    HIP_TRY(hipMemcpyAsync(out, mx_zstash_of(c, idx, B), (size_t)B * n * sizeof(unsigned short), hipMemcpyDeviceToDevice,
                            static_cast<hipStream_t>(stream)));
     return HPE_OK;
 }

@@ -230,6 +230,11 @@ struct EncTrainWork {
     unsigned short *mx_w[HPE_NUM_CONV] = {};    // RNE of ConvLayer::w, Wt[n_pad][conv_k_pad(idx, true)]; the k padding is zero from the reserve on
     unsigned short *mx_dxw[HPE_NUM_CONV] = {};  // RNE of dxw
     void *mx_cast = nullptr;  // the device table of the cast launch that opens every mixed call: MX_CAST_SEGS segments
+    // ... with batch statistics (encoder_bn_bf16.hip), allocated by hpe_encoder_train_reserve_batchnorm_mixed only
+    int mxbn_B = 0;         // its reserved batch (0: not reserved)
+    int mx_zstash_B = 0;    // batch of the mixed batch-statistics forward that last filled mx_zstash
+    bool bn_stat_mixed = false;  // the forward that last filled bn_batch was a mixed one: zstash does not hold its raw outputs
+    unsigned short *mx_zstash = nullptr;  // every layer's raw output RNE(conv(x16, W16) + b), laid out as zstash
 };
 constexpr int MX_CAST_SEGS = 2 * HPE_NUM_CONV - 1;  // segment idx: mx_w[idx]; segment HPE_NUM_CONV - 1 + idx (idx >= 1): mx_dxw[idx]
 struct MxCastSeg {
@@ -418,6 +423,11 @@ hipError_t bn_launch_stats_from_sums(const double* sums, double M_all, int N, fl
 hipError_t bn_launch_bwd_sums(const float* dy, const float* y, const float* z, const float* mu, const float* r, int M, int N, double* part, double* sums,
                               float* db, float* dgamma, float* dbeta, hipStream_t st);
 hipError_t bn_launch_bwd_from_sums(const double* sums, int N, float* red, hipStream_t st);
+// the second launch of each reduction alone, from partials part[slice][2][N] in that layout
+hipError_t bn_finish_stats(const double* part, int slices, int M, int N, float eps, float* mu, float* var, float* r, hipStream_t st);
+hipError_t bn_finish_sums(const double* part, int slices, int N, double* sums, hipStream_t st);
+hipError_t bn_finish_bwd(const double* part, int slices, int N, float* db, float* dgamma, float* dbeta, hipStream_t st);
+hipError_t bn_finish_bwd_sums(const double* part, int slices, int N, double* sums, float* db, float* dgamma, float* dbeta, hipStream_t st);
 hipError_t bn_launch_momentum(float* stats, const float* batch, const int* hw, int B, int channels, double momentum, int unbiased, hipStream_t st);
 hipError_t bn_launch_install(const float* stats, int channels, float eps, float* keep, float* mean, float* istd, double* sd, hipStream_t st);
 
@@ -446,14 +456,30 @@ typedef unsigned short* mx16;
 typedef const unsigned short* cmx16;
 hipError_t mx_cast_launch(hpe_ctx* c, int first, int segs, hipStream_t st);  // segments [first, first + segs) of the cast table
 // y = RNE(act(s * conv(x, W16) + shift (+ res))) through the bf16 route of the layer; idx 0 reads the padded bf16 input
-hipError_t mx_conv_forward(hpe_ctx* c, int idx, cmx16 x, int B, cmx16 res, int relu, mx16 y, hipStream_t st);
+// scale / shift: in place of the layer's folded BatchNorm (the batch-statistics walk: a unit scale and the bias)
+hipError_t mx_conv_forward(hpe_ctx* c, int idx, cmx16 x, int B, cmx16 res, int relu, mx16 y, hipStream_t st, const float* scale = nullptr,
+                           const float* shift = nullptr);
 void mx_gate(cmx16 dy, cmx16 y, const float* s, mx16 dz, mx16 dzs, long n, int N, hipStream_t st);  // dzs = RNE(dz * s)
 // x: the layer's input (idx 0: the padded bf16 input); grad_layer fp32 as weight_grad writes it
-hipError_t mx_weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* grad_layer, hipStream_t st);
+// bn (batch statistics), as weight_grad: dz is dzraw16, dW = G with a unit scale, the finish is not launched
+hipError_t mx_weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* grad_layer, hipStream_t st, bool bn = false);
 hipError_t mx_data_grad(hpe_ctx* c, int idx, cmx16 dzs, int B, cmx16 res, mx16 out, hipStream_t st);
 void mx_scatter2(cmx16 lo, mx16 hi, int B, int H, int C, hipStream_t st);
 void mx_avgpool_bwd(const float* dy, mx16 dx, int B, int HW, int C, hipStream_t st);  // dx = RNE(dy / HW)
 void mx_maxpool_bwd(cmx16 x, cmx16 dy, mx16 dx, int B, int H, int C, hipStream_t st);
+
+// encoder_bn_bf16.hip: the launches of encoder_bn.hip on bf16 tensors z16 / y16 / res16 / dy16 / dz / dzraw16 (statistics, gamma, beta and
+// the gradients stay fp32); the partials have the layout of the fp32 reductions, whose finish launches run behind these
+hipError_t bn16_launch_stats(cmx16 z, int M, int N, float eps, double* part, float* mu, float* var, float* r, hipStream_t st);
+hipError_t bn16_launch_stats_sums(cmx16 z, int M, int N, double* part, double* sums, hipStream_t st);
+hipError_t bn16_launch_apply(cmx16 z, const float* mu, const float* r, const float* gamma, const float* beta, cmx16 res, int relu, mx16 y, int M, int N,
+                             hipStream_t st);
+hipError_t bn16_launch_bwd_reduce(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, int M, int N, double* part, float* db, float* dgamma,
+                                  float* dbeta, hipStream_t st);
+hipError_t bn16_launch_bwd_sums(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, int M, int N, double* part, double* sums, float* db,
+                                float* dgamma, float* dbeta, hipStream_t st);
+hipError_t bn16_launch_bwd_apply(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, const float* gamma, const float* dgamma,
+                                 const float* dbeta, int M, int N, mx16 dz, mx16 dzraw, hipStream_t st, double M_all = 0.0);
 
 // regressor_train.hip
 int regressor_param_offset(int idx, bool bias);  // idx 3: mean theta; idx 4 (bias false): the total

@@ -651,9 +651,13 @@ class HpeEngine(object):
         """hpe_encoder_train_reserve: allocate the stash, cotangent buffers, partial sums and data-gradient packings for batches up to B.
         batch_norm=True (hpe_encoder_train_reserve_batchnorm): also the raw-output stash and the statistics buffers that ``bn="batch"``,
         ``encoder_stats``, ``update_encoder_stats`` and ``set_encoder_stats_dev`` need.  precision="bf16"
-        (hpe_encoder_train_reserve_mixed): also the bf16 stash, cotangent buffers and weight operands of the mixed-precision walks."""
+        (hpe_encoder_train_reserve_mixed): also the bf16 stash, cotangent buffers and weight operands of the mixed-precision walks.
+        precision="mixed": the same with batch_norm=False; with batch_norm=True (hpe_encoder_train_reserve_batchnorm_mixed) both of
+        those reserves and the bf16 raw-output stash of the mixed-precision walks with batch statistics."""
         mixed = self._mixed(precision, "batch" if batch_norm else "frozen")
-        if batch_norm:
+        if batch_norm and mixed:
+            _lib.check(self.lib.hpe_encoder_train_reserve_batchnorm_mixed(self._h, int(B)))
+        elif batch_norm:
             _lib.check(self.lib.hpe_encoder_train_reserve_batchnorm(self._h, int(B)))
         elif mixed:
             _lib.check(self.lib.hpe_encoder_train_reserve_mixed(self._h, int(B)))
@@ -668,12 +672,15 @@ class HpeEngine(object):
 
     @staticmethod
     def _mixed(precision, bn="frozen"):
-        """True for precision="bf16": the mixed-precision walks (bf16 activations and cotangents on this fp32 context)"""
-        if precision not in ("fp32", "bf16"):
-            raise ValueError("precision must be 'fp32' or 'bf16', got %r" % (precision,))
-        if precision == "bf16" and HpeEngine._bn_mode(bn):
+        """True for precision="bf16" or "mixed": the mixed-precision walks (bf16 activations and cotangents on this fp32 context).
+        "bf16" is the frozen-statistics spelling only; "mixed" runs with both BatchNorm modes (bn="frozen": the walks of "bf16", the
+        same bits; bn="batch": BatchNorm arithmetic in fp32, its reductions in float64)"""
+        if precision not in ("fp32", "bf16", "mixed"):
+            raise ValueError("precision must be 'fp32', 'bf16' or 'mixed', got %r" % (precision,))
+        batch = HpeEngine._bn_mode(bn)
+        if precision == "bf16" and batch:
             raise ValueError("precision='bf16' runs with frozen BatchNorm statistics only: batch statistics in bf16 are the follow-up")
-        return precision == "bf16"
+        return precision != "fp32"
 
     def _bf16_arg(self, t, name):
         torch = _torch()
@@ -719,8 +726,17 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_debug_encoder_batch_stats(self._h, out.data_ptr(), self._stream()))
         return out
 
-    def encoder_stash_raw(self, idx):
-        """hpe_debug_encoder_stash_raw: layer idx's raw output conv(x, W) + b of the last ``bn="batch"`` forward, over that call's batch"""
+    def encoder_stash_raw(self, idx, precision="fp32"):
+        """hpe_debug_encoder_stash_raw: layer idx's raw output conv(x, W) + b of the last ``bn="batch"`` forward, over that call's batch.
+        precision="mixed" (hpe_debug_encoder_stash_raw_mixed): of the last mixed-precision one, as torch.bfloat16"""
+        if self._mixed(precision, "batch"):
+            B = self.lib.hpe_debug_encoder_stash_batch_mixed(self._h)
+            if B < 1:
+                raise _lib.HpeError("encoder_stash_raw: no mixed-precision training forward has run")
+            s = CONV_SPECS[idx]
+            out = self._new_bf16(B, s.hout, s.hout, s.cout)
+            _lib.check(self.lib.hpe_debug_encoder_stash_raw_mixed(self._h, idx, out.data_ptr(), self._stream()))
+            return out
         B = self.lib.hpe_debug_encoder_stash_batch(self._h)
         if B < 1:
             raise _lib.HpeError("encoder_stash_raw: no training forward has run")
@@ -729,9 +745,18 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_debug_encoder_stash_raw(self._h, idx, out.data_ptr(), self._stream()))
         return out
 
-    def debug_conv_batchnorm(self, idx, x, residual=None, relu=True):
-        """hpe_debug_conv_batchnorm: one layer with batch statistics -> (y, z, stats [2 * cout] = mu | var)"""
+    def debug_conv_batchnorm(self, idx, x, residual=None, relu=True, precision="fp32"):
+        """hpe_debug_conv_batchnorm: one layer with batch statistics -> (y, z, stats [2 * cout] = mu | var).  precision="mixed"
+        (hpe_debug_conv_batchnorm_mixed): x, residual, y and z are torch.bfloat16 (x of idx 0: the float32 images), stats float32"""
         s = CONV_SPECS[idx]
+        if self._mixed(precision, "batch"):
+            x = _require_cuda_tensor(x, "x") if idx == 0 else self._bf16_arg(x, "x")
+            B = x.shape[0]
+            y, z, st = self._new_bf16(B, s.hout, s.hout, s.cout), self._new_bf16(B, s.hout, s.hout, s.cout), self._new(2 * s.cout)
+            residual = self._bf16_arg(residual, "residual") if residual is not None else None
+            _lib.check(self.lib.hpe_debug_conv_batchnorm_mixed(self._h, idx, x.data_ptr(), B, residual.data_ptr() if residual is not None else None,
+                                                               int(relu), y.data_ptr(), z.data_ptr(), st.data_ptr(), self._stream()))
+            return y, z, st
         x = _require_cuda_tensor(x, "x")
         B = x.shape[0]
         y, z, st = self._new(B, s.hout, s.hout, s.cout), self._new(B, s.hout, s.hout, s.cout), self._new(2 * s.cout)
@@ -740,10 +765,24 @@ class HpeEngine(object):
                                                      self._stream()))
         return y, z, st
 
-    def debug_conv_backward_batchnorm(self, idx, x, z, y, dy, want_dx=True):
+    def debug_conv_backward_batchnorm(self, idx, x, z, y, dy, want_dx=True, precision="fp32"):
         """hpe_debug_conv_backward_batchnorm: one layer's gate, BatchNorm backward, weight and data gradient from its raw output z and
-        its activated output y (None: no activation) -> (dx or None, grad_layer = [kernel | bias = 0 | gamma | beta] flat)"""
+        its activated output y (None: no activation) -> (dx or None, grad_layer = [kernel | bias = 0 | gamma | beta] flat).
+        precision="mixed" (hpe_debug_conv_backward_batchnorm_mixed): x, z, y, dy and dx are torch.bfloat16 (x of idx 0: the float32
+        images); grad_layer is float32"""
         s = CONV_SPECS[idx]
+        if self._mixed(precision, "batch"):
+            x = _require_cuda_tensor(x, "x") if idx == 0 else self._bf16_arg(x, "x")
+            z, dy = self._bf16_arg(z, "z"), self._bf16_arg(dy, "dy")
+            y = self._bf16_arg(y, "y") if y is not None else None
+            B = x.shape[0]
+            want_dx = want_dx and idx != 0
+            dx = self._new_bf16(B, s.hin, s.hin, s.cin) if want_dx else None
+            gl = self._new(s.kh * s.kw * s.cin * s.cout + 3 * s.cout)
+            _lib.check(self.lib.hpe_debug_conv_backward_batchnorm_mixed(self._h, idx, x.data_ptr(), z.data_ptr(),
+                                                                        y.data_ptr() if y is not None else None, dy.data_ptr(), B,
+                                                                        dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
+            return dx, gl
         x, z, dy = _require_cuda_tensor(x, "x"), _require_cuda_tensor(z, "z"), _require_cuda_tensor(dy, "dy")
         y = _require_cuda_tensor(y, "y") if y is not None else None
         B = x.shape[0]
@@ -872,10 +911,12 @@ class HpeEngine(object):
     def encoder_forward_train(self, images, bn="frozen", precision="fp32"):
         """hpe_encoder_forward_train: images [B,224,224,3] -> features [B,2048], layer by layer, every activation kept in the stash.
         bn="batch" (hpe_encoder_forward_batchnorm): every BatchNorm normalises with the statistics of this batch.  precision="bf16"
-        (hpe_encoder_forward_train_mixed): bf16 activations and matrix products, fp32 accumulation; images and features stay fp32."""
+        (hpe_encoder_forward_train_mixed): bf16 activations and matrix products, fp32 accumulation; images and features stay fp32.
+        precision="mixed": the same with bn="frozen"; with bn="batch" (hpe_encoder_forward_batchnorm_mixed) the statistics of this
+        batch, taken of the bf16 raw outputs in float64."""
         fn = self.lib.hpe_encoder_forward_batchnorm if self._bn_mode(bn) else self.lib.hpe_encoder_forward_train
         if self._mixed(precision, bn):
-            fn = self.lib.hpe_encoder_forward_train_mixed
+            fn = self.lib.hpe_encoder_forward_batchnorm_mixed if bn == "batch" else self.lib.hpe_encoder_forward_train_mixed
         images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))
         B = images.shape[0]
         out = self._new(B, 2048)
@@ -886,10 +927,10 @@ class HpeEngine(object):
         """hpe_encoder_backward: the gradient of sum(grad_features * features) with respect to the flat encoder parameters.  Stateless
         (the training forward runs again); same inputs, same bits.  bn="batch" (hpe_encoder_backward_batchnorm): through the batch
         statistics; the bias slots are 0.  precision="bf16" (hpe_encoder_backward_mixed): the mixed-precision walk; the flat gradient
-        is fp32."""
+        is fp32.  precision="mixed": that walk with bn="frozen", hpe_encoder_backward_batchnorm_mixed with bn="batch"."""
         fn = self.lib.hpe_encoder_backward_batchnorm if self._bn_mode(bn) else self.lib.hpe_encoder_backward
         if self._mixed(precision, bn):
-            fn = self.lib.hpe_encoder_backward_mixed
+            fn = self.lib.hpe_encoder_backward_batchnorm_mixed if bn == "batch" else self.lib.hpe_encoder_backward_mixed
         images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))
         B = images.shape[0]
         grad_features = _require_cuda_tensor(grad_features.detach(), "grad_features")

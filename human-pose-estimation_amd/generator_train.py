@@ -43,7 +43,9 @@ class GeneratorTrainer(object):
         data-parallel training (the module's text); with ``encoder_bn="batch"`` the reducer's callback is installed as the engine's
         reduce hook.  ``reducer=None`` is the single-process trainer, unchanged.  encoder_precision: "fp32", or "bf16" for the
         mixed-precision encoder walks (needs ``engine.reserve_encoder_train(B, precision="bf16")``; ``encoder_bn="frozen"`` only): the
-        fp32 master tensor ``encoder_params``, the optimiser and ``set_encoder_params_dev`` are as in fp32."""
+        fp32 master tensor ``encoder_params``, the optimiser and ``set_encoder_params_dev`` are as in fp32.  "mixed": those walks with
+        either ``encoder_bn`` (with "batch": ``engine.reserve_encoder_train(B, batch_norm=True, precision="mixed")``); the moving
+        statistics, ``update_encoder_stats``, ``set_encoder_stats_dev`` and the reduce hook are as in fp32."""
         import torch
 
         if not 0.0 <= dropout < 1.0:
@@ -78,7 +80,7 @@ class GeneratorTrainer(object):
         self.encoder_bn, self.bn_momentum, self.bn_unbiased = encoder_bn, float(bn_momentum), bool(bn_unbiased)
         from .engine import HpeEngine
 
-        HpeEngine._mixed(encoder_precision, encoder_bn)  # "bf16" with batch statistics is the follow-up: ValueError
+        HpeEngine._mixed(encoder_precision, encoder_bn)  # "bf16" with batch statistics is refused ("mixed" is its spelling): ValueError
         self.encoder_precision = encoder_precision
         self.encoder_params = self.encoder_optimizer = self.encoder_stats = None
         if self.train_encoder and encoder_bn == "batch":

@@ -100,11 +100,13 @@ def encoder_features(engine, images, params, bn="frozen", precision="fp32"):
     tensor [resnet_spec.ENCODER_PARAM_FLOATS] that must equal ``engine.encoder_params()``; needs ``engine.reserve_encoder_train(B)``.
     bn="batch": BatchNorm with the statistics of this batch, the gradient through them (``reserve_encoder_train(B, batch_norm=True)``).
     precision="bf16": the mixed-precision walks (``reserve_encoder_train(B, precision="bf16")``; frozen statistics only): bf16
-    activations, cotangents and matrix products with fp32 accumulation; ``params``, the features and ``.grad`` stay fp32"""
+    activations, cotangents and matrix products with fp32 accumulation; ``params``, the features and ``.grad`` stay fp32.
+    precision="mixed": the same walks with bn="frozen"; with bn="batch" (``reserve_encoder_train(B, batch_norm=True,
+    precision="mixed")``) the bf16 walks with batch statistics, BatchNorm arithmetic in fp32 and its reductions in float64"""
     from .autograd import EncoderFunction
     from .engine import HpeEngine
 
-    HpeEngine._mixed(precision, bn)  # refuses bn="batch" with precision="bf16" before anything runs
+    HpeEngine._mixed(precision, bn)  # refuses bn="batch" with precision="bf16" (use "mixed") before anything runs
     return EncoderFunction.apply(engine, images, params, bn, precision)
 
 

@@ -163,7 +163,9 @@ class Trainer(object):
                  **predictor_args):
         """config: read by attribute like the reference's -- ``batch_size``, ``epoch``, ``generator_lr``, ``critic_lr``,
         ``kpr_loss_weight``, ``mr_loss_weight``, ``critic_loss_weight``, ``use_kpr_loss``, ``use_mesh_repro_loss``, ``encoder_only``,
-        ``use_validation``, ``validation_step_size``, ``train_from_checkpoint``, ``checkpoint_dir``, plus what ``Predictor`` reads (the
+        ``use_validation``, ``validation_step_size``, ``train_from_checkpoint``, ``checkpoint_dir``, ``encoder_precision`` ("fp32", the
+        default, or "mixed": the encoder's walks in bf16 with fp32 master weights, BatchNorm arithmetic in fp32; checkpoints are the
+        same either way), plus what ``Predictor`` reads (the
         SMPL model, the mean parameters and the starting weights: ``predictor_args`` are passed on).  dataset / val_dataset:
         ``RecordDataset``s of image records (batch size ``config.batch_size``) or any iterable of what ``load_training_batch`` takes: the
         reference's image records, whose ``image/encoded`` and ``image/seg_gt`` are JPEG or PNG streams (lsp_train / lsp_val masks and
@@ -233,10 +235,14 @@ class Trainer(object):
                                "weights, or a checkpoint with a discriminator) unless config.encoder_only is set")
         dp = {} if self.reducer is None else {"reducer": self.reducer}
         dp_gen = dict(dp, global_batch=self.batch_size) if dp else {}
-        eng.reserve_encoder_train(D.shard_bounds(self.batch_size, 0, self.world)[1], batch_norm=True)  # the largest shard
+        self.encoder_precision = g("encoder_precision", "fp32")
+        if self.encoder_precision not in ("fp32", "mixed"):
+            raise ValueError("config.encoder_precision must be 'fp32' or 'mixed', got %r" % (self.encoder_precision,))
+        eng.reserve_encoder_train(D.shard_bounds(self.batch_size, 0, self.world)[1], batch_norm=True,
+                                  precision=self.encoder_precision)  # the largest shard
         self.generator = GeneratorTrainer(eng, lr=self.generator_lr, kpr_loss_weight=self.kpr_loss_weight, mr_loss_weight=self.mr_loss_weight,
                                           critic_loss_weight=self.critic_loss_weight, generator=generator, train_encoder=True,
-                                          encoder_bn="batch", optimizer="keras", **dp_gen)
+                                          encoder_bn="batch", optimizer="keras", encoder_precision=self.encoder_precision, **dp_gen)
         if not self.encoder_only:
             self.critic = CriticTrainer(eng, lr=self.critic_lr, generator=generator, optimizer="keras", **dp)
         self._sync_replicas()

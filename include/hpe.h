@@ -564,6 +564,43 @@ int hpe_debug_bn_backward_finish(hpe_ctx* ctx, int idx, const float* x_dev, cons
                                  const double* sums_dev, const double* bwd_sums_dev, long long M, float* dx_dev, float* grad_layer_dev,
                                  void* stream);
 
+/* -- mixed-precision encoder training with batch statistics: the bf16 walks with BatchNorm in training mode --
+ * The calls of "encoder training with batch statistics" on the buffers of "mixed-precision encoder training": bf16 activations,
+ * cotangents and matrix products accumulated in fp32; BatchNorm arithmetic in fp32, its reductions in double.  fp32 contexts only.  The
+ * rounding points of the mixed section hold for W16, the pad, the pools, g and the scatter; per layer, M = B * hout * hout:
+ *   z16 = RNE(acc + b): the layer's bf16 convolution launch with a unit scale and the bias of the flat copy as shift;
+ *   mu, var (biased), r: the statistics OF z16 (double sums of the bf16 values and their squares), into the slots of the fp32 walk;
+ *   y16 = RNE(act(gamma * ((z16 - mu) * r) + beta (+ res16))), fp32, the residual added before the one rounding;
+ *   dz = dy16 * [y16 > 0] exact (a projection shortcut: dz = dy16);  xhat = (z16 - mu) * r in fp32;  dbeta = sum_m dz and
+ *   dgamma = sum_m dz * xhat in double, written as fp32, never rounded to bf16;  db = 0 exactly;
+ *   dzraw16 = RNE(gamma * r * (dz - dbeta / M - xhat * (dgamma / M)));  dW = A^T dzraw16 in fp32;  dx = RNE(acc (+ block cotangent)).
+ * No product is fused into a sum in the elementwise passes, so a float32 restatement gives their bits.
+ * hpe_encoder_train_reserve_batchnorm_mixed: hpe_encoder_train_reserve_mixed(ctx, B) and hpe_encoder_train_reserve_batchnorm(ctx, B) if
+ * they have not run, then, once and outside any capture, a bf16 stash of every layer's raw output z16 (laid out as the fp32 one).  The
+ * fp32 y and z stashes of the two shared reserves come with it.  hpe_encoder_train_ws_floats_batchnorm_mixed(B): the floats of all of
+ * it together (host code; 0 for B < 1).  A second call with a B not above the first is a no-op; a larger one is refused (HPE_ERR_STATE).
+ * hpe_encoder_forward_batchnorm_mixed / hpe_encoder_backward_batchnorm_mixed: the contract of the _mixed pair (stateless backward, the
+ * same inputs give the same bits, no atomics, no allocation, capturable on one stream without a hook), and that of the _batchnorm pair
+ * for the statistics and the hook: they fill the batch statistics that hpe_encoder_update_stats and hpe_debug_encoder_batch_stats read
+ * (those of the last batch-statistics call of EITHER precision), and a reduce hook (hpe_encoder_set_reduce) is called at the same two
+ * places per layer with the same sums.  HPE_ERR_STATE before this reserve, on a bf16 context, or on a captured stream with a hook set;
+ * HPE_ERR_INVALID for NULL pointers, B outside [1, batch of this reserve] or above the hook's global batch. */
+int hpe_encoder_train_reserve_batchnorm_mixed(hpe_ctx* ctx, int B);
+long long hpe_encoder_train_ws_floats_batchnorm_mixed(int B);
+int hpe_encoder_forward_batchnorm_mixed(hpe_ctx* ctx, const float* images_dev, int B, float* features_dev, void* stream);
+int hpe_encoder_backward_batchnorm_mixed(hpe_ctx* ctx, const float* images_dev, int B, const float* grad_features_dev, float* grad_flat_dev,
+                                         void* stream);
+/* hpe_debug_conv_batchnorm / hpe_debug_conv_backward_batchnorm in mixed precision: x_dev, residual_dev, y_dev, z_out_dev, z_dev, dy_dev
+ * and dx_dev are bf16, stats_out_dev and grad_layer_dev fp32; for idx 0 x_dev is the fp32 image tensor and dx_dev must be NULL.  Neither
+ * touches the statistics of the last whole-network call nor calls the hook. */
+int hpe_debug_conv_batchnorm_mixed(hpe_ctx* ctx, int idx, const void* x_dev, int B, const void* residual_dev, int relu, void* y_dev,
+                                   void* z_out_dev, float* stats_out_dev, void* stream);
+int hpe_debug_conv_backward_batchnorm_mixed(hpe_ctx* ctx, int idx, const void* x_dev, const void* z_dev, const void* y_dev, const void* dy_dev,
+                                            int B, void* dx_dev, float* grad_layer_dev, void* stream);
+/* Layer idx's raw output z16 (bf16) of the last mixed batch-statistics forward, B images of it; HPE_ERR_STATE if none has run.  (After
+ * such a forward hpe_debug_encoder_stash_raw is refused: the fp32 z stash does not hold what the statistics were taken of.) */
+int hpe_debug_encoder_stash_raw_mixed(hpe_ctx* ctx, int idx, void* out_dev, void* stream);
+
 /* Both reprojection losses of all n_stage IEF stages in ONE call -- what Trainer.val_step evaluates per step
  * (src/trainer.py:274-296): the work that depends only on seg_gts (tf.where compaction, src/trainer.py:291;
  * the silhouette bitmap) is done once per call instead of once per stage.

@@ -16,7 +16,12 @@ hpe_encoder_update_stats + hpe_encoder_set_stats_dev, against torch fp32 autogra
     python tools/encoder_train_bench.py --precision bf16 [--out profiles/encoder_train_mixed_bench.json]
 
 The mixed-precision leg: ms per hpe_encoder_backward_mixed and per fp32 hpe_encoder_backward on the same context, the two alternating group
-by group (same events, 5 groups of `iters` calls each after 3 warm-up calls of each, medians), and the bytes of the two reserves."""
+by group (same events, 5 groups of `iters` calls each after 3 warm-up calls of each, medians), and the bytes of the two reserves.
+
+    python tools/encoder_train_bench.py --bn batch --precision mixed [--out profiles/encoder_bn_mixed_bench.json]
+
+The mixed-precision leg with batch statistics, same method: ms per hpe_encoder_backward_batchnorm_mixed and per fp32
+hpe_encoder_backward_batchnorm on the same context, alternating group by group, and the bytes of the reserves."""
 import argparse
 import json
 import os
@@ -119,16 +124,18 @@ def main():
     ap.add_argument("--batches", default="8,32,64")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--bn", choices=("frozen", "batch"), default="frozen")
-    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32", help="bf16: the mixed-precision leg (frozen statistics only)")
+    ap.add_argument("--precision", choices=("fp32", "bf16", "mixed"), default="fp32",
+                    help="bf16: the mixed-precision leg (frozen statistics only); mixed: the same, or with --bn batch the mixed-precision leg with batch statistics")
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace-calls", type=int, default=0,
                     help="run only this many backward calls of the chosen mode at the first batch and exit: the workload of a rocprofv3 --kernel-trace --stats run")
     a = ap.parse_args()
-    bn, mixed = a.bn == "batch", a.precision == "bf16"
-    if bn and mixed:
-        ap.error("--precision bf16 runs with frozen statistics only")
+    bn, mixed = a.bn == "batch", a.precision != "fp32"
+    if bn and a.precision == "bf16":
+        ap.error("--precision bf16 runs with frozen statistics only: --precision mixed takes --bn batch")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "encoder_train_mixed_bench.json" if mixed else "encoder_bn_train_bench.json" if bn else "encoder_train_bench.json")
+        name = ("encoder_bn_mixed_bench.json" if bn else "encoder_train_mixed_bench.json") if mixed else "encoder_bn_train_bench.json" if bn else "encoder_train_bench.json"
+        a.out = os.path.join(ROOT, "profiles", name)
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
     batches = [int(b) for b in a.batches.split(",")]
@@ -151,7 +158,14 @@ def main():
         for B in batches:
             img = torch.from_numpy(synthetic.make_images(B, seed=1)).cuda()
             gf = torch.randn(B, 2048, device="cuda")
-            mx, f32 = timed_pair(lambda: eng.encoder_backward(img, gf, precision="bf16"), lambda: eng.encoder_backward(img, gf), a.iters)
+            mx, f32 = timed_pair(lambda: eng.encoder_backward(img, gf, bn=a.bn, precision=a.precision), lambda: eng.encoder_backward(img, gf, bn=a.bn),
+                                 a.iters)
+            if bn:
+                res["rows"].append({"B": B, "hpe_encoder_backward_batchnorm_mixed_ms": round(mx, 3), "hpe_encoder_backward_batchnorm_ms": round(f32, 3),
+                                    "fp32_over_mixed": round(f32 / mx, 3),
+                                    "reserve_fp32_batchnorm_bytes": 4 * eng.lib.hpe_encoder_train_ws_floats_batchnorm(B),
+                                    "reserve_batchnorm_mixed_bytes": 4 * eng.lib.hpe_encoder_train_ws_floats_batchnorm_mixed(B)})
+                continue
             res["rows"].append({"B": B, "hpe_encoder_backward_mixed_ms": round(mx, 3), "hpe_encoder_backward_ms": round(f32, 3),
                                 "fp32_over_mixed": round(f32 / mx, 3), "reserve_fp32_bytes": 4 * eng.lib.hpe_encoder_train_ws_floats(B),
                                 "reserve_fp32_and_mixed_bytes": 4 * eng.lib.hpe_encoder_train_ws_floats_mixed(B)})
