@@ -214,6 +214,13 @@ _PROTOS = {
     "hpe_adam_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "hpe_adam_set_step": (C.c_int, [C.c_void_p, C.c_longlong, C.c_double, C.c_double, C.c_void_p]),
     "hpe_debug_adam_power": (C.c_int, [C.c_double, C.c_longlong, C.POINTER(C.c_double)]),
+    "hpe_grad_stats_chunk": (C.c_int, []),
+    "hpe_grad_stats_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int]),
+    "hpe_grad_stats": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "hpe_adam_guard": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                 C.c_void_p]),
+    "hpe_adam_apply_guarded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                         C.c_float, C.c_void_p]),
     "hpe_jpeg_info": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_jpeg_decode": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpe_jpeg_backend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,

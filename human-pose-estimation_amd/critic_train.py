@@ -15,11 +15,15 @@ ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon (src/trainer.py:184)
 
 
 class CriticTrainer(object):
-    def __init__(self, engine, lr=CRITIC_LR, betas=(0.9, 0.999), eps=ADAM_EPS, gp_weight=10.0, generator=None, optimizer="torch", reducer=None):
+    def __init__(self, engine, lr=CRITIC_LR, betas=(0.9, 0.999), eps=ADAM_EPS, gp_weight=10.0, generator=None, optimizer="torch", reducer=None,
+                 clipnorm=None, skip_nonfinite=False):
         """engine: an HpeEngine with a loaded critic (the starting point: a checkpoint's discriminator or a fresh initialisation).
         ``params`` is the flat parameter tensor (critic_spec.flat_layout) the optimiser owns; ``critic_spec.flat_to_params(params)``
         gives the dict ``load_critic`` / ``weights.npz`` take.  generator: the torch.Generator of the interpolation draws.  optimizer:
-        "torch" (torch.optim.Adam) or "keras" (``KerasAdam``, optim.py: the reference's fused update in HIP)."""
+        "torch" (torch.optim.Adam) or "keras" (``KerasAdam``, optim.py: the reference's fused update in HIP).  clipnorm /
+        skip_nonfinite (``optimizer="keras"`` only): its guarded step -- global-norm clipping, and a step with a non-finite gradient
+        leaves the weights, the moments and the step count as they were -- decided on the device from per-layer statistics of the
+        gradient summed over the ranks; ``step`` then also returns ``grad_norm`` and ``step_applied`` (0-dim device tensors)."""
         import torch
 
         if not engine.has_critic:
@@ -31,11 +35,14 @@ class CriticTrainer(object):
         self.params = engine.critic_params()
         if optimizer not in ("torch", "keras"):
             raise ValueError("optimizer must be 'torch' or 'keras'")
+        self.guarded = clipnorm is not None or bool(skip_nonfinite)
+        if self.guarded and optimizer != "keras":
+            raise ValueError("clipnorm / skip_nonfinite need optimizer='keras' (the guarded step is KerasAdam's)")
         if optimizer == "keras":
-            from .optim import KerasAdam
+            from .optim import KerasAdam, layer_segments
 
-            self.optimizer = KerasAdam(lr, betas[0], betas[1], eps)
-            self.optimizer.add("critic", self.params)
+            self.optimizer = KerasAdam(lr, betas[0], betas[1], eps, global_clipnorm=clipnorm, skip_nonfinite=skip_nonfinite)
+            self.optimizer.add("critic", self.params, segments=layer_segments("critic", engine.lib)[0] if self.guarded else None)
         else:
             self.optimizer = torch.optim.Adam([self.params], lr=lr, betas=betas, eps=eps)
 
@@ -52,7 +59,10 @@ class CriticTrainer(object):
         self.params.grad = r["grad"]
         self.optimizer.step()
         self.engine.set_critic_params(self.params)
-        return {"critic_network_loss": r["loss"], "critic_penalty": r["penalty"], "critic_wgan": r["wgan"]}
+        out = {"critic_network_loss": r["loss"], "critic_penalty": r["penalty"], "critic_wgan": r["wgan"]}
+        if self.guarded:  # copies: the guard block is the next step's too
+            out["grad_norm"], out["step_applied"] = self.optimizer.grad_norm.clone(), self.optimizer.step_applied.clone()
+        return out
 
     def step_from_thetas(self, real, thetas, interp=None, global_batch=None):
         """The same with the fake rows taken from the generator's thetas: ``thetas`` is the list of the IEF stages' theta [B,85]; their

@@ -94,7 +94,9 @@ __global__ __launch_bounds__(256) void kp_loss_bwd_kernel(const float* __restric
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const float dlt = pred[i * 2 + c] - gt[i * 3 + c];
-            const float sg = dlt > 0.f ? 1.0f : (dlt < 0.f ? -1.0f : 0.f);
+            // sign(0) = 0; a NaN difference (a NaN in the record, where the loss itself is NaN) stays a NaN: it used to become 0, a finite
+            // update from a bad record that no guard of the optimiser step could see
+            const float sg = dlt > 0.f ? 1.0f : (dlt < 0.f ? -1.0f : (dlt == 0.f ? 0.f : dlt));
             grad_pred[i * 2 + c] = tc > 0.f ? gl * ((vis * sg) / tc) : 0.f;
         }
     }

@@ -28,7 +28,8 @@ ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon
 class GeneratorTrainer(object):
     def __init__(self, engine, lr=GENERATOR_LR, betas=(0.9, 0.999), eps=ADAM_EPS, kpr_loss_weight=60.0, mr_loss_weight=0.001,
                  critic_loss_weight=0.01, dropout=0.5, generator=None, train_encoder=False, encoder_lr=None, encoder_bn="frozen",
-                 bn_momentum=0.99, bn_unbiased=True, optimizer="torch", reducer=None, global_batch=None, encoder_precision="fp32"):
+                 bn_momentum=0.99, bn_unbiased=True, optimizer="torch", reducer=None, global_batch=None, encoder_precision="fp32",
+                 clipnorm=None, skip_nonfinite=False):
         """engine: a finalized HpeEngine with a regressor, mean theta and SMPL (and a critic, for the critic term).  ``params`` is the
         flat parameter tensor (regressor_spec.flat_layout) the optimiser owns; ``regressor_spec.flat_to_params(params)`` gives the
         dict ``load_regressor`` / ``load_mean_theta`` take.  generator: the torch.Generator of the dropout draws.  train_encoder: also
@@ -45,7 +46,11 @@ class GeneratorTrainer(object):
         mixed-precision encoder walks (needs ``engine.reserve_encoder_train(B, precision="bf16")``; ``encoder_bn="frozen"`` only): the
         fp32 master tensor ``encoder_params``, the optimiser and ``set_encoder_params_dev`` are as in fp32.  "mixed": those walks with
         either ``encoder_bn`` (with "batch": ``engine.reserve_encoder_train(B, batch_norm=True, precision="mixed")``); the moving
-        statistics, ``update_encoder_stats``, ``set_encoder_stats_dev`` and the reduce hook are as in fp32."""
+        statistics, ``update_encoder_stats``, ``set_encoder_stats_dev`` and the reduce hook are as in fp32.  clipnorm / skip_nonfinite
+        (``optimizer="keras"`` only): the guarded step of ``KerasAdam`` (global-norm clipping over the tensors stepped; a step with a
+        non-finite gradient is undone as a whole: both flat tensors, the moments, the step count and ``encoder_stats`` keep their
+        bits), decided on the device from per-layer statistics taken after the data-parallel sum, so every rank decides alike.  The
+        result of ``step`` then has ``grad_norm`` and ``step_applied`` (0-dim device tensors)."""
         import torch
 
         if not 0.0 <= dropout < 1.0:
@@ -63,13 +68,16 @@ class GeneratorTrainer(object):
         if optimizer not in ("torch", "keras"):
             raise ValueError("optimizer must be 'torch' or 'keras'")
         self.keras = optimizer == "keras"
+        self.guarded = clipnorm is not None or bool(skip_nonfinite)
+        if self.guarded and not self.keras:
+            raise ValueError("clipnorm / skip_nonfinite need optimizer='keras' (the guarded step is KerasAdam's)")
         if self.keras:
-            from .optim import KerasAdam
+            from .optim import KerasAdam, layer_segments
 
             if train_encoder and encoder_lr is not None and float(encoder_lr) != float(lr):
                 raise ValueError("optimizer='keras' steps the encoder and the regressor with one optimiser: encoder_lr must equal lr")
-            self.optimizer = KerasAdam(lr, betas[0], betas[1], eps)
-            self.optimizer.add("regressor", self.params)
+            self.optimizer = KerasAdam(lr, betas[0], betas[1], eps, global_clipnorm=clipnorm, skip_nonfinite=skip_nonfinite)
+            self.optimizer.add("regressor", self.params, segments=layer_segments("regressor", engine.lib)[0] if self.guarded else None)
         else:
             self.optimizer = torch.optim.Adam([self.params], lr=lr, betas=betas, eps=eps)
         self.train_encoder = bool(train_encoder)
@@ -88,7 +96,7 @@ class GeneratorTrainer(object):
         if self.train_encoder:
             self.encoder_params = engine.encoder_params().requires_grad_(True)
             if self.keras:
-                self.optimizer.add("encoder", self.encoder_params)
+                self.optimizer.add("encoder", self.encoder_params, segments=layer_segments("encoder", engine.lib)[0] if self.guarded else None)
             else:
                 self.encoder_optimizer = torch.optim.Adam([self.encoder_params], lr=lr if encoder_lr is None else encoder_lr, betas=betas, eps=eps)
         if reducer is not None and self.train_encoder and encoder_bn == "batch":
@@ -190,12 +198,20 @@ class GeneratorTrainer(object):
                 self.encoder_optimizer.step()
             eng.set_encoder_params_dev(self.encoder_params)
             if self.encoder_bn == "batch":
-                eng.update_encoder_stats(self.encoder_stats, self.bn_momentum, self.bn_unbiased)
+                if self.guarded:  # a skipped step leaves the moving statistics alone too: chosen on the device, from the guard's flag
+                    before = self.encoder_stats.clone()
+                    eng.update_encoder_stats(self.encoder_stats, self.bn_momentum, self.bn_unbiased)
+                    self.encoder_stats.copy_(torch.where(self.optimizer.step_applied != 0, self.encoder_stats, before))
+                else:
+                    eng.update_encoder_stats(self.encoder_stats, self.bn_momentum, self.bn_unbiased)
                 eng.set_encoder_stats_dev(self.encoder_stats)
         det = lambda ts: [t.detach() for t in ts]  # noqa: E731
         if red is not None:  # the ranks' shares into the losses of the global batch: one packed all-reduce for all of them
             block = red.sum_block(torch.stack([t.detach().reshape(()) for t in kpr + mr + gc]))
             kpr, mr, gc = list(block[:len(kpr)]), list(block[len(kpr):len(kpr) + len(mr)]), list(block[len(kpr) + len(mr):])
-        return {"kpr_losses": det(kpr), "mr_losses": det(mr), "generator_critic_losses": det(gc), "pred_keypoints": pred_kp,
-                "generated_cams": thetas[S - 1, :, :3].detach(), "thetas": [thetas[i].detach() for i in range(S)],
-                "grad_features": features.grad}
+        out = {"kpr_losses": det(kpr), "mr_losses": det(mr), "generator_critic_losses": det(gc), "pred_keypoints": pred_kp,
+               "generated_cams": thetas[S - 1, :, :3].detach(), "thetas": [thetas[i].detach() for i in range(S)],
+               "grad_features": features.grad}
+        if self.guarded:  # copies: the guard block is the next step's too
+            out["grad_norm"], out["step_applied"] = self.optimizer.grad_norm.clone(), self.optimizer.step_applied.clone()
+        return out

@@ -19,6 +19,13 @@ GLOBAL batch G; rank r steps on its ``shard_bounds(G, r, world)`` rows (datasets
 BatchNorm statistics and gradients are those of the G rows, the replicas start from rank 0's tensors and stay bit-identical; only
 rank 0 saves, summarises and logs.
 
+Guarded optimiser step (DESIGN.md "Guarded optimiser step"; the reference has no gradient clipping, src/trainer.py:84):
+``config.generator_clipnorm`` / ``config.critic_clipnorm`` (default None) clip each update's global gradient norm,
+``config.skip_nonfinite_steps`` (default False) undoes an update whose gradient holds a NaN or an infinity, ``config.log_grad_norms``
+(default False) adds one ``grad_norm/<layer>`` scalar per conv and dense layer.  With any of them set and summaries on, every step also
+writes ``optim/<generator|critic>_grad_norm``, ``_clip_scale`` and ``_skipped_steps``, and ``train_step``'s result has them as
+``<generator|critic>_grad_norm`` ... (device scalars) and ``layer_grad_norms``.  With none set nothing changes.
+
 Scores (DESIGN.md "Checkpoint scores"): ``score_checkpoint`` gives PCK and the silhouette's IoU / foreground-background accuracy / F1 over
 one pass of the validation set, with the best and worst images drawn on request; ``config.score_validation`` (default False) adds four
 ``metrics/...`` scalars of the batch to every validation step of ``train``.
@@ -240,11 +247,21 @@ class Trainer(object):
             raise ValueError("config.encoder_precision must be 'fp32' or 'mixed', got %r" % (self.encoder_precision,))
         eng.reserve_encoder_train(D.shard_bounds(self.batch_size, 0, self.world)[1], batch_norm=True,
                                   precision=self.encoder_precision)  # the largest shard
+        # the guarded optimiser step (DESIGN.md "Guarded optimiser step"): off unless one of these four is set
+        self.generator_clipnorm, self.critic_clipnorm = g("generator_clipnorm", None), g("critic_clipnorm", None)
+        self.skip_nonfinite_steps, self.log_grad_norms = bool(g("skip_nonfinite_steps", False)), bool(g("log_grad_norms", False))
+
+        def guard(clipnorm):  # the per-layer norms come from the guard's statistics: logging alone is a guard that never clips
+            clipnorm = float("inf") if clipnorm is None and self.log_grad_norms else clipnorm
+            return {} if clipnorm is None and not self.skip_nonfinite_steps else {"clipnorm": clipnorm, "skip_nonfinite": self.skip_nonfinite_steps}
+
         self.generator = GeneratorTrainer(eng, lr=self.generator_lr, kpr_loss_weight=self.kpr_loss_weight, mr_loss_weight=self.mr_loss_weight,
                                           critic_loss_weight=self.critic_loss_weight, generator=generator, train_encoder=True,
-                                          encoder_bn="batch", optimizer="keras", encoder_precision=self.encoder_precision, **dp_gen)
+                                          encoder_bn="batch", optimizer="keras", encoder_precision=self.encoder_precision, **dp_gen,
+                                          **guard(self.generator_clipnorm))
         if not self.encoder_only:
-            self.critic = CriticTrainer(eng, lr=self.critic_lr, generator=generator, optimizer="keras", **dp)
+            self.critic = CriticTrainer(eng, lr=self.critic_lr, generator=generator, optimizer="keras", **dp, **guard(self.critic_clipnorm))
+        self._layer_maps = {}
         self._sync_replicas()
 
     def _sync_replicas(self):
@@ -270,6 +287,32 @@ class Trainer(object):
         if self.critic is not None:
             eng.set_critic_params(self.critic.params)
 
+    def _guard_results(self, who, trainer, kinds, result):
+        """the guard's figures of ``trainer``'s last step into ``result`` as copies on the device: <who>_grad_norm, <who>_clip_scale,
+        <who>_skipped_steps and, with ``log_grad_norms``, layer_grad_norms[layer] = sqrt(sum of the sums of squares of the layer's segments)"""
+        import torch
+
+        from .optim import layer_segments
+
+        opt = trainer.optimizer
+        result[who + "_grad_norm"], result[who + "_step_applied"] = opt.grad_norm.clone(), opt.step_applied.clone()
+        result[who + "_clip_scale"], result[who + "_skipped_steps"] = opt.clip_scale.clone(), opt._guard_view("skipped").clone()
+        if not self.log_grad_norms:
+            return
+        norms = result.setdefault("layer_grad_norms", {})
+        for kind in kinds:
+            if kind not in self._layer_maps:  # [layers, segments] of 0 / 1: which segments make up which layer
+                names = layer_segments(kind, self.engine.lib)[1]
+                layers = list(dict.fromkeys(names))
+                m = torch.zeros((len(layers), len(names)), dtype=torch.float64)
+                for j, n in enumerate(names):
+                    m[layers.index(n), j] = 1.0
+                self._layer_maps[kind] = (layers, m.to(self.engine.tdev))
+            layers, m = self._layer_maps[kind]
+            per_layer = (m * opt.grad_stats(kind)[:, 0]).sum(1).sqrt()
+            for i, n in enumerate(layers):
+                norms[n] = per_layer[i]
+
     # ------------------------------------------------------------------ steps
     def train_step(self, images, seg_gts, kp_gt, joints=None, shapes=None, Rs=None, drop="draw", interp=None):
         """One update of the generator, then one of the critic on the thetas it produced (src/trainer.py:383-583).  images
@@ -285,9 +328,13 @@ class Trainer(object):
                   "thetas": r["thetas"]}
         if self.use_mesh_repro_loss:
             result["mr_losses"] = r["mr_losses"]
+        if self.generator.guarded:
+            self._guard_results("generator", self.generator, ("regressor", "encoder"), result)
         if not self.encoder_only:
             c = self.critic.step_from_thetas((joints, shapes, Rs), r["thetas"], interp=interp,
                                              global_batch=self.batch_size if self.reducer is not None else None)
+            if self.critic.guarded:
+                self._guard_results("critic", self.critic, ("critic",), result)
             result["generator_critic_losses"] = r["generator_critic_losses"]
             result["critic_penalty"], result["critic_network_loss"] = c["critic_penalty"], c["critic_network_loss"]
         if self.do_bone_evaluation:
@@ -433,6 +480,12 @@ class Trainer(object):
             w.scalar("critic/critic_network_loss", result["critic_network_loss"], step)
             w.scalar("critic/generator_critic_loss", result["generator_critic_losses"][-1], step)
             w.scalar("critic/penalty", result["critic_penalty"], step)
+        for who in ("generator", "critic"):  # the guarded optimiser step: not the reference's tags, and only with a guard configured
+            if who + "_grad_norm" in result:
+                for what in ("grad_norm", "clip_scale", "skipped_steps"):
+                    w.scalar("optim/%s_%s" % (who, what), result["%s_%s" % (who, what)], step)
+        for layer, norm in result.get("layer_grad_norms", {}).items():
+            w.scalar("grad_norm/" + layer, norm, step)
         if image_step:
             w.flush()
 

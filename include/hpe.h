@@ -209,7 +209,8 @@ int hpe_reproject_vertices(const float* verts_dev, const float* cam_dev, int B, 
  * Numerator and count are returned separately so that ranks can all-reduce them before dividing. */
 int hpe_kp_loss(const float* kp_gt_dev, const float* kp_pred_dev, int B, int K, float* out_dev, void* stream);
 /* gradient of hpe_kp_loss w.r.t. kp_pred: grad_loss_dev is one device float (NULL = 1); grad_kp_pred_dev [B,K,2] =
- * grad_loss * vis * sign(pred - gt) / (2 * #visible), zero where pred == gt and everywhere when nothing is visible */
+ * grad_loss * vis * sign(pred - gt) / (2 * #visible), zero where pred == gt and everywhere when nothing is visible.  A NaN
+ * difference gives a NaN gradient, as it gives a NaN loss: a bad record shows in the gradient, where hpe_grad_stats counts it. */
 int hpe_kp_loss_backward(const float* kp_gt_dev, const float* kp_pred_dev, int B, int K, const float* grad_loss_dev,
                          float* grad_kp_pred_dev, void* stream);
 /* mesh_reprojection_loss (src/ops.py:117-137) forward: seg_dev [B,H,W] (>0 = silhouette), verts2d_dev
@@ -697,6 +698,39 @@ int hpe_adam_apply(float* p, float* m, float* v, const float* g, long long n, co
 int hpe_adam_set_step(double* state_dev, long long t, double beta1, double beta2, void* stream);
 /* The host build of the power helper of the two calls above: *out = beta^t (t >= 0), square-and-multiply in double.  No device needed. */
 int hpe_debug_adam_power(double beta, long long t, double* out);
+
+/* -- the guarded step: global-norm clipping and a skip on non-finite gradients, decided on the device ---------------------------
+ * (the reference has neither: src/trainer.py:84.)  hpe_grad_stats per tensor, ONE hpe_adam_guard in the place of hpe_adam_advance, then
+ * hpe_adam_apply_guarded per tensor.  Nothing reads the host, nothing allocates, no atomics: stream-ordered and capturable.
+ * DESIGN.md "Guarded optimiser step" states the order of every sum; tests/grad_guard_ref.py restates it. */
+/* One record of 3 doubles per segment of g[n]: {sum of squares, largest |g| over the finite elements, number of non-finite elements}.
+ * The S + 1 ascending offsets (0 <= offsets[0], offsets[S] <= n; equal neighbours: an empty segment, record {0, 0, 0}) cut g into S
+ * segments; offsets_host is what this call checks and sizes its grid from, offsets_dev the caller's device copy the kernels read.
+ * Squares and sums are float64 ((double)g * (double)g is exact).  A segment is cut into chunks of hpe_grad_stats_chunk() elements from
+ * its own start; a chunk is summed in one fixed binary tree, a segment's chunk partials are added in index order: a record's bits depend
+ * on the segment's values alone -- not on the grid, the alignment of g, the segment's place in g or the other segments.  A non-finite
+ * element's square (inf or NaN) is part of its segment's sum.  16-byte loads where a chunk allows them, scalar loads elsewhere.
+ * Three launches (the chunk map, the chunks, the per-segment combine).  workspace_dev: at least hpe_grad_stats_workspace_bytes(n, S)
+ * bytes, 8-byte aligned, the caller's (-1 from that query, with hpe_last_error() set, for n < 0 or S < 1).  HPE_ERR_INVALID, before any
+ * launch and without a device, for a NULL pointer, n < 0, S < 1, descending offsets, an offset beyond n and a workspace too small. */
+int hpe_grad_stats_chunk(void);
+long long hpe_grad_stats_workspace_bytes(long long n, int S);
+int hpe_grad_stats(const float* g, long long n, const long long* offsets_host, const long long* offsets_dev, int S, double* records_dev,
+                   void* workspace_dev, long long workspace_bytes, void* stream);
+/* One launch, one deciding thread, float64, nothing contracted.  records_dev / counts (HOST arrays of n_lists <= 16 device pointers and
+ * record counts, >= 1 each): the records of the tensors of this step.  sumsq = their sums of squares added in list order, table order
+ * within a list; norm = sqrt(sumsq).  skip_nonfinite != 0 and a non-finite count > 0: applied = 0, state_dev keeps its bits (t does not
+ * move), skipped += 1.  Otherwise applied = 1, state_dev moves as by hpe_adam_advance, scale = (float)(clip_norm / fmax(norm,
+ * clip_norm)) -- exactly 1.0f for norm <= clip_norm, for clip_norm = +inf (no clipping) and for a NaN norm -- and clipped += 1 when
+ * scale < 1.  guard_dev: 8 doubles {norm, scale, applied, skipped, clipped, non-finite count, max |g|, sumsq}, zeros on a fresh
+ * optimiser; skipped and clipped are running counts, the rest is of this step.  HPE_ERR_INVALID as hpe_adam_advance, and for n_lists
+ * outside [1, 16], a NULL list, a count < 1 and a clip_norm that is negative or NaN; no device needed to refuse. */
+int hpe_adam_guard(double* state_dev, double* guard_dev, const double* const* records_dev, const int* counts, int n_lists, double lr,
+                   double beta1, double beta2, double clip_norm, int skip_nonfinite, void* stream);
+/* hpe_adam_apply under a guard block: applied == 0 stores nothing (the launch still happens); otherwise g' = g * scale, one float32
+ * multiply, then the element arithmetic of hpe_adam_apply on g' on the same paths.  scale == 1.0f gives the bits of hpe_adam_apply. */
+int hpe_adam_apply_guarded(float* p, float* m, float* v, const float* g, long long n, const double* state_dev, const double* guard_dev,
+                           float one_minus_beta1, float one_minus_beta2, float eps, void* stream);
 
 /* -- JPEG decode: tf.image.decode_jpeg(buf, channels) of the training records (src/util/data_utils.py:129-141) ---------------
  * Baseline sequential DCT streams only (SOF0, 8-bit samples and quantisation tables, 1 or 3 components, luma sampling 1x1, 2x1 or
