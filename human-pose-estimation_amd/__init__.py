@@ -36,7 +36,7 @@ from . import mat5_lite  # noqa: F401
 from .datasets import create_datasets, create_records, filename_pairs_lsp, filename_pairs_lspe, filename_pairs_mpii, image_record  # noqa: F401
 from .records import (RecordDataset, RecordError, TFRecordWriter, image_example, load_training_batch, mocap_example, parse_example,  # noqa: F401
                       parse_image_example, parse_mocap_example, read_tfrecords, serialize_example, write_tfrecords)
-from .metrics import Scores, eval_scores  # noqa: F401
+from .metrics import Scores, Scores3D, eval_scores, pose3d_scores, procrustes_align  # noqa: F401
 from .image import get_original, preprocess_batch, preprocess_image  # noqa: F401
 from .ops import critic_gradient_penalty, critic_scores, critic_wgan_loss, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas, encoder_features  # noqa: F401
 from .optim import KerasAdam  # noqa: F401

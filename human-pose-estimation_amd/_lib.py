@@ -244,6 +244,9 @@ _PROTOS = {
                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_eval_scores": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_pose3d_scores": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_debug_procrustes3": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "hpe_critic_layer_name": (C.c_char_p, [C.c_int]),
     "hpe_critic_layer_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "hpe_load_critic": (C.c_int, [C.c_void_p, C.POINTER(HpeCriticModel)]),

@@ -9,6 +9,13 @@ them the sums of every rank's shard) and ``Scores.result`` turns them into ratio
 
     counts, kp_err, norm = eval_scores([st["verts2d"] for st in stages], faces_dev, seg_gts, kp_gt, [st["kp2d"] for st in stages])
     s = Scores(); s.add(counts, kp_err, norm); s.result()["pck_torso_0.2"]
+
+The 3-D scores (DESIGN.md "3-D pose scores"): ``pose3d_scores`` is one ``hpe_pose3d_scores`` launch (csrc/pose3d_scores.hip) for all stages
+of a batch -- per image and stage the root-aligned and the Procrustes-aligned error of every joint, MPJPE, PA-MPJPE, PVE, PA-PVE and both
+similarity fits -- ``procrustes_align`` the fit alone, and ``Scores3D`` the sums and ratios, in millimetres.
+
+    joint_err, summary, xform = pose3d_scores([st["joints"] for st in stages], joints_gt, [st["verts"] for st in stages], verts_gt)
+    s = Scores3D(); s.add(joint_err, summary); s.result()["pa_mpjpe_mm"]
 """
 from __future__ import annotations
 
@@ -240,6 +247,185 @@ class Scores(object):
             out[k] = int(out[k])
         out["pck_per_joint"] = [float(v) for v in host[len(keys):]]
         return out
+
+    def results(self):
+        """``result`` of every stage"""
+        return [self.result(i) for i in range(self.sums.shape[0])]
+
+
+# ---------------------------------------------------------------------------------------------- 3-D scores (DESIGN.md "3-D pose scores")
+POSE3D_FLAG_ROOT, POSE3D_FLAG_PA_JOINTS, POSE3D_FLAG_PA_VERTS, POSE3D_FLAG_NO_VERTS = 1, 2, 4, 8  # summary[..., 5] of hpe_pose3d_scores
+PCK3D_THRESHOLDS_MM = tuple(range(0, 151, 5))  # the thresholds auc3d averages over; the last is pck3d_150's
+
+
+def _launch_pose3d(joints, joints_gt, weights, verts, verts_gt, roots, want=(True, True, True)):
+    """one hpe_pose3d_scores launch on checked, contiguous float32 CUDA tensors -> (joint_err, summary, xform), None where not wanted"""
+    import torch
+
+    lib = _lib.load()
+    n, dev = len(joints), joints_gt.device
+    B, K = int(joints_gt.shape[0]), int(joints_gt.shape[1])
+    P = int(verts_gt.shape[1]) if verts_gt is not None else 0
+    j_ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in joints])
+    v_ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in verts]) if verts is not None else None
+    joint_err = torch.empty((n, B, 2, K), dtype=torch.float32, device=dev) if want[0] else None
+    summary = torch.empty((n, B, 6), dtype=torch.float32, device=dev) if want[1] else None
+    xform = torch.empty((n, B, 2, 13), dtype=torch.float32, device=dev) if want[2] else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.hpe_pose3d_scores(j_ptrs, joints_gt.data_ptr(), ptr(weights), v_ptrs, ptr(verts_gt), n, B, K, P, int(roots[0]), int(roots[1]),
+                                         ptr(joint_err), ptr(summary), ptr(xform), st))
+    return joint_err, summary, xform
+
+
+def pose3d_scores(joints_list, joints_gt, verts_list=None, verts_gt=None, joint_weights=None, roots=(2, 3), num_joints=NUM_LSP_JOINTS):
+    """-> (joint_err float32 [n_stage,B,2,K]: row 0 the root-aligned, row 1 the Procrustes-aligned error of every joint, -1 where the joint
+    is not scored, NaN where the alignment is undefined; summary float32 [n_stage,B,6] = MPJPE, PA-MPJPE, PVE, PA-PVE, scored joints,
+    flags (``POSE3D_FLAG_*``); xform float32 [n_stage,B,2,13] = scale, R row-major, t of the joint fit and of the vertex fit), all in the
+    units of the inputs (``Scores3D`` reports millimetres).  joints_list: per stage [B,K,3] CUDA tensors; joints_gt [B,K,3]; the first
+    ``num_joints`` of the K keypoints are scored (None: all), and of those the ones whose ``joint_weights`` [B,K] entry is > 0;
+    ``roots``: the two joints whose mean is the root (the hips in LSP order).  verts_list per stage [B,P,3] with verts_gt [B,P,3], or
+    neither: joints only.  ONE ``hpe_pose3d_scores`` launch on the current stream; nothing reads the device."""
+    import torch
+
+    gt = _cuda_f32(joints_gt, "joints_gt")
+    if gt.dim() != 3 or gt.shape[2] != 3:
+        raise ValueError("pose3d_scores: joints_gt must be [B, K, 3], got %s" % (tuple(gt.shape),))
+    B, K = int(gt.shape[0]), int(gt.shape[1])
+    joints = [_cuda_f32(t, "joints") for t in joints_list]
+    if not joints or any(tuple(t.shape) != (B, K, 3) for t in joints):
+        raise ValueError("pose3d_scores: every stage's joints must be [%d, %d, 3]" % (B, K))
+    if (verts_list is None) != (verts_gt is None):
+        raise ValueError("pose3d_scores: verts_list and verts_gt are given together or not at all")
+    verts = vgt = None
+    if verts_gt is not None:
+        vgt = _cuda_f32(verts_gt, "verts_gt")
+        verts = [_cuda_f32(t, "verts") for t in verts_list]
+        if vgt.dim() != 3 or vgt.shape[0] != B or vgt.shape[2] != 3 or len(verts) != len(joints) or any(t.shape != vgt.shape for t in verts):
+            raise ValueError("pose3d_scores: verts_gt must be [%d, P, 3] and every stage's verts the same, one per stage" % B)
+    J = K if num_joints is None else int(num_joints)
+    if not 1 <= J <= K:
+        raise ValueError("pose3d_scores: num_joints %d outside [1, %d]" % (J, K))
+    w = None
+    if joint_weights is not None:
+        w = _cuda_f32(joint_weights, "joint_weights")
+        if tuple(w.shape) != (B, K):
+            raise ValueError("pose3d_scores: joint_weights must be [%d, %d]" % (B, K))
+    if J < K:  # the joints past num_joints are not scored: zero weights, no copy of the clouds
+        w = torch.ones((B, K), dtype=torch.float32, device=gt.device) if w is None else w.clone()
+        w[:, J:] = 0
+    return _launch_pose3d(joints, gt, w, verts, vgt, roots)
+
+
+def procrustes_align(src, dst, weights=None):
+    """The similarity transform that best maps ``src`` onto ``dst`` ([N,3] or [B,N,3] CUDA tensors) over the points whose weight is > 0
+    -> (aligned = scale * src R^T + t, scale [B], R [B,3,3], t [B,3]), without the batch axis for [N,3] inputs; NaN where the fit is
+    undefined (fewer than 3 points, or all of ``src`` in one place).  The fit is the joint fit of one ``hpe_pose3d_scores`` launch."""
+    s, d = _cuda_f32(src, "src"), _cuda_f32(dst, "dst")
+    single = s.dim() == 2
+    if single:
+        s, d = s[None], d[None]
+        weights = None if weights is None else weights[None]
+    if s.dim() != 3 or s.shape[2] != 3 or s.shape != d.shape:
+        raise ValueError("procrustes_align: src and dst must both be [N, 3] or [B, N, 3]")
+    w = None if weights is None else _cuda_f32(weights, "weights")
+    if w is not None and tuple(w.shape) != tuple(s.shape[:2]):
+        raise ValueError("procrustes_align: weights must be %s" % (tuple(s.shape[:2]),))
+    x = _launch_pose3d([s], d, w, None, None, (0, 0), want=(False, False, True))[2][0, :, 0]
+    scale, R, t = x[:, 0], x[:, 1:10].reshape(-1, 3, 3), x[:, 10:13]
+    aligned = scale[:, None, None] * (s @ R.transpose(1, 2)) + t[:, None, :]
+    return (aligned[0], scale[0], R[0], t[0]) if single else (aligned, scale, R, t)
+
+
+class Scores3D(object):
+    """Plain sums of ``pose3d_scores`` outputs over the batches of a pass, one float64 row per IEF stage (``sums`` [n_stage, M], on the
+    device of what is added: ``add`` reads nothing back), so one ``Reducer.sum_block`` makes them the sums of every rank's shard.
+
+    ``result()``, lengths in millimetres (the inputs times ``to_mm``, 1000 for metres):
+      mpjpe_mm, pa_mpjpe_mm   mean root-aligned / Procrustes-aligned error over the scored joints 0..J-1 of the images where that
+                              alignment is defined (``root_invalid_images`` / ``pa_invalid_images`` are left out)
+      pve_mm, pa_pve_mm       mean over the images of the per-image vertex error (images without vertices or without that alignment are
+                              left out)
+      mpjpe_per_joint_mm, pa_mpjpe_per_joint_mm   the first two for each joint (NaN for a joint never scored)
+      pck3d_150               the share of those joints whose root-aligned error is at most 150 mm
+      auc3d                   the mean of that share over the thresholds 0, 5, ..., 150 mm
+      images, pa_invalid_images, root_invalid_images
+    A ratio whose denominator is 0 is NaN; a NaN coordinate in a scored point makes the sums it enters NaN."""
+
+    def __init__(self, num_joints=NUM_LSP_JOINTS, to_mm=1000.0):
+        self.J, self.to_mm = int(num_joints), float(to_mm)
+        # columns: images root_invalid pa_invalid | pve_sum pve_images pa_pve_sum pa_pve_images | root err sum[J] | root count[J] |
+        #          pa err sum[J] | pa count[J] | hits per threshold[T]
+        self._joint0, self.T = 7, len(PCK3D_THRESHOLDS_MM)
+        self.M = self._joint0 + 4 * self.J + self.T
+        self.sums = None
+
+    def add(self, joint_err, summary, xform=None):
+        """one batch: joint_err [n_stage,B,2,K >= J], summary [n_stage,B,6] (tensors or arrays); xform is taken and not read, so that
+        ``add(*pose3d_scores(...))`` works"""
+        import torch
+
+        J, j0 = self.J, self._joint0
+        e = Scores._tensor(joint_err).double()
+        sm = Scores._tensor(summary).double().to(e.device)
+        if e.dim() != 4 or e.shape[2] != 2 or e.shape[3] < J or sm.shape != e.shape[:2] + (6,):
+            raise ValueError("Scores3D: joint_err must be [n_stage, B, 2, K >= %d] and summary [n_stage, B, 6]" % J)
+        n = e.shape[0]
+        if self.sums is None:
+            self.sums = torch.zeros((n, self.M), dtype=torch.float64, device=e.device)
+        if self.sums.shape[0] != n:
+            raise ValueError("Scores3D: %d stages were added before, now %d" % (self.sums.shape[0], n))
+        s = self.sums
+        flags = sm[:, :, 5].long()
+        root_ok, pa_ok = (flags & POSE3D_FLAG_ROOT) == 0, (flags & POSE3D_FLAG_PA_JOINTS) == 0
+        has_v = (flags & POSE3D_FLAG_NO_VERTS) == 0
+        pve_ok, pa_pve_ok = root_ok & has_v, has_v & ((flags & POSE3D_FLAG_PA_VERTS) == 0)
+        zero = torch.zeros((), dtype=torch.float64, device=e.device)
+        s[:, 0] += e.shape[1]
+        s[:, 1] += (~root_ok).sum(1)
+        s[:, 2] += (~pa_ok).sum(1)
+        s[:, 3] += torch.where(pve_ok, sm[:, :, 2] * self.to_mm, zero).sum(1)
+        s[:, 4] += pve_ok.sum(1)
+        s[:, 5] += torch.where(pa_pve_ok, sm[:, :, 3] * self.to_mm, zero).sum(1)
+        s[:, 6] += pa_pve_ok.sum(1)
+        e0, e1 = e[:, :, 0, :J] * self.to_mm, e[:, :, 1, :J] * self.to_mm
+        # -1 in both rows marks a joint that is not scored; an error is never negative, and a NaN (an undefined alignment, a NaN
+        # coordinate) compares false here, so its joint counts as scored, as it is
+        scored = ~((e0 < 0) & (e1 < 0))
+        r_on, p_on = scored & root_ok[:, :, None], scored & pa_ok[:, :, None]
+        s[:, j0:j0 + J] += torch.where(r_on, e0, zero).sum(1)
+        s[:, j0 + J:j0 + 2 * J] += r_on.sum(1)
+        s[:, j0 + 2 * J:j0 + 3 * J] += torch.where(p_on, e1, zero).sum(1)
+        s[:, j0 + 3 * J:j0 + 4 * J] += p_on.sum(1)
+        thr = torch.tensor(PCK3D_THRESHOLDS_MM, dtype=torch.float64, device=e.device)
+        s[:, j0 + 4 * J:] += (r_on[..., None] & (e0[..., None] <= thr)).sum((1, 2))
+        return self
+
+    def reduce(self, reducer):
+        """the sums of every rank, in ONE ``Reducer.sum_block``"""
+        if self.sums is None:
+            raise ValueError("Scores3D.reduce: nothing was added")
+        reducer.sum_block(self.sums)
+        return self
+
+    def result(self, stage=-1):
+        """the scores of one stage (default: the last) as Python floats, ints and lists: ONE transfer"""
+        if self.sums is None:
+            raise ValueError("Scores3D.result: nothing was added")
+        s, J, j0 = self.sums[stage].cpu().numpy(), self.J, self._joint0
+
+        def ratio(a, b):
+            with np.errstate(invalid="ignore", divide="ignore"):
+                return np.where(b > 0, a / np.where(b > 0, b, 1.0), np.nan)
+
+        r_sum, r_cnt, p_sum, p_cnt = (s[j0 + i * J:j0 + (i + 1) * J] for i in range(4))
+        share = ratio(s[j0 + 4 * J:], r_cnt.sum())
+        return {"mpjpe_mm": float(ratio(r_sum.sum(), r_cnt.sum())), "pa_mpjpe_mm": float(ratio(p_sum.sum(), p_cnt.sum())),
+                "pve_mm": float(ratio(s[3], s[4])), "pa_pve_mm": float(ratio(s[5], s[6])),
+                "mpjpe_per_joint_mm": [float(v) for v in ratio(r_sum, r_cnt)], "pa_mpjpe_per_joint_mm": [float(v) for v in ratio(p_sum, p_cnt)],
+                "pck3d_150": float(share[-1]), "auc3d": float(share.mean()), "images": int(s[0]), "pa_invalid_images": int(s[2]),
+                "root_invalid_images": int(s[1])}
 
     def results(self):
         """``result`` of every stage"""

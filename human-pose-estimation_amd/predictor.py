@@ -312,6 +312,43 @@ class Predictor(object):
                                                    self._to_device(kp2d_gts), [st["kp2d"] for st in stages])
         return counts, kp_err, norm, metrics.image_iou(counts)
 
+    def score_step_3d(self, images, theta_gt=None, joints3d_gt=None, verts_gt=None, joint_weights=None, all_stages=True):
+        """Forward + ``hpe_pose3d_scores`` (metrics.pose3d_scores; DESIGN.md "3-D pose scores") of every IEF stage, or of the last with
+        ``all_stages=False`` -> (joint_err [n_stage,B,2,19], summary [n_stage,B,6], xform [n_stage,B,2,13]) in metres: feed the first
+        two to ``metrics.Scores3D.add``.  The ground truth is ``theta_gt`` [B,85], pushed through ``engine.smpl`` (joints and vertices),
+        or ``joints3d_gt`` [B,19,3] -- [B,14,3] is taken as the 14 scored LSP joints -- with ``verts_gt`` [B,6890,3] where there is one
+        (without it only the joint scores are defined).  ``joint_weights`` [B,19] or [B,14]: the joints with a weight > 0 are scored.
+        One forward, one launch, nothing reads the device."""
+        import torch
+
+        from . import metrics
+
+        images = self._to_device(images)
+        B = images.shape[0]
+        if B > self.batch_size:
+            raise ValueError("score_step_3d needs B <= config.batch_size")
+        if (theta_gt is None) == (joints3d_gt is None):
+            raise ValueError("score_step_3d needs theta_gt or joints3d_gt, not both")
+        K, J = 19, metrics.NUM_LSP_JOINTS
+
+        def pad(t, fill):  # [B,14,...] -> [B,19,...]: the five face points are never scored
+            t = self._to_device(t).float()
+            if t.shape[1] == K:
+                return t
+            if t.shape[1] != J:
+                raise ValueError("score_step_3d: %d joints where %d or %d are expected" % (t.shape[1], J, K))
+            return torch.cat([t, t.new_full((t.shape[0], K - J) + tuple(t.shape[2:]), fill)], 1)
+
+        if theta_gt is not None:
+            gt = self.engine.smpl(self._to_device(theta_gt).float().contiguous(), want=("verts", "joints"))
+            joints_gt, verts_gt = gt["joints"], gt["verts"]
+        else:
+            joints_gt = pad(joints3d_gt, 0.0)
+            verts_gt = None if verts_gt is None else self._to_device(verts_gt)
+        stages = self.engine.forward(images, all_stages=all_stages, want=("joints", "verts"))  # the last stage alone: one set of outputs
+        return metrics.pose3d_scores([st["joints"] for st in stages], joints_gt, None if verts_gt is None else [st["verts"] for st in stages],
+                                     verts_gt, None if joint_weights is None else pad(joint_weights, 0.0), num_joints=J)
+
     def predict_single_image(self, image):
         """reference: src/predictor.py:160-163"""
         image = self._to_device(image)

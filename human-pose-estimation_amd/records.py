@@ -125,7 +125,7 @@ def parse_image_example(payload):
     """``parse_example_proto`` without the decode: {'image', 'seg': JPEG or PNG bytes, 'height', 'width': int, 'center': int64 [2] (x, y),
     'filename': bytes, 'kp': float32 [19,3]}.  kp is the 14 image/x, image/y, image/visibility columns followed by image/face_pts
     reshaped [3,5] (all zeros when the record has none: the reference's default).  A missing key or a wrong length raises RecordError
-    naming the key."""
+    naming the key.  Where the record holds them: 'gt3d' float32 [14,3], 'pose' float32 [72], 'shape' float32 [10], 'has_3d' int."""
     f = parse_example(payload)
     label = np.zeros((3, NUM_KP), np.float32)
     label[0, :14] = _need(f, "image/x", "float", 14)
@@ -133,10 +133,20 @@ def parse_image_example(payload):
     label[2, :14] = _need(f, "image/visibility", "int64", 14).astype(np.float32)
     if "image/face_pts" in f:
         label[:, 14:] = _need(f, "image/face_pts", "float", 15).reshape(3, 5)
-    return {"image": _need(f, "image/encoded", "bytes", 1)[0], "seg": _need(f, "image/seg_gt", "bytes", 1)[0],
-            "height": int(_need(f, "image/height", "int64", 1)[0]), "width": int(_need(f, "image/width", "int64", 1)[0]),
-            "center": _need(f, "image/center", "int64", 2).copy(), "filename": _need(f, "image/filename", "bytes", 1)[0],
-            "kp": np.ascontiguousarray(label.T)}
+    out = {"image": _need(f, "image/encoded", "bytes", 1)[0], "seg": _need(f, "image/seg_gt", "bytes", 1)[0],
+           "height": int(_need(f, "image/height", "int64", 1)[0]), "width": int(_need(f, "image/width", "int64", 1)[0]),
+           "center": _need(f, "image/center", "int64", 2).copy(), "filename": _need(f, "image/filename", "bytes", 1)[0],
+           "kp": np.ascontiguousarray(label.T)}
+    # the optional 3-D ground truth: each key only where the record holds the feature
+    if "mosh/gt3d" in f:
+        out["gt3d"] = _need(f, "mosh/gt3d", "float", 42).reshape(14, 3).copy()
+    if "mosh/pose" in f:
+        out["pose"] = _need(f, "mosh/pose", "float", 72).copy()
+    if "mosh/shape" in f:
+        out["shape"] = _need(f, "mosh/shape", "float", 10).copy()
+    if "meta/has_3d" in f:
+        out["has_3d"] = int(_need(f, "meta/has_3d", "int64", 1)[0])
+    return out
 
 
 def parse_mocap_example(payload):
@@ -231,15 +241,25 @@ def serialize_example(features):
     return _pb_bytes(1, entries)
 
 
-def image_example(image, seg, height, width, center, filename, x, y, vis, face_pts=None):
+def image_example(image, seg, height, width, center, filename, x, y, vis, face_pts=None, gt3d=None, pose=None, shape=None):
     """The record of src/util/create_dataset.py:52-70: image and mask bytes as they are, height, width, the file's base name, format
-    b"JPEG", center int64 [2] (x, y), the 14 visibilities (int64) and coordinates (float), and the 15 face floats if there are any."""
+    b"JPEG", center int64 [2] (x, y), the 14 visibilities (int64) and coordinates (float), and the 15 face floats if there are any.
+    Optional 3-D ground truth (DESIGN.md "3-D pose scores"): gt3d [14,3] joints in metres -> mosh/gt3d (42 floats), pose [72] ->
+    mosh/pose, shape [10] -> mosh/shape, and meta/has_3d = 1 when any of them is given; without them the bytes are what they always were."""
     name = filename if isinstance(filename, (bytes, bytearray)) else str(filename).encode("utf-8")
     feats = [("image/encoded", bytes(image)), ("image/seg_gt", bytes(seg)), ("image/height", [int(height)]), ("image/width", [int(width)]),
              ("image/filename", bytes(name)), ("image/format", b"JPEG"), ("image/center", np.asarray(center, np.int64)),
              ("image/visibility", np.asarray(vis, np.int64)), ("image/x", np.asarray(x, np.float32)), ("image/y", np.asarray(y, np.float32))]
     if face_pts is not None:
         feats.append(("image/face_pts", np.asarray(face_pts, np.float32)))
+    extra = [(key, np.asarray(v, np.float32).reshape(-1), n) for key, v, n in (("mosh/gt3d", gt3d, 42), ("mosh/pose", pose, 72), ("mosh/shape", shape, 10))
+             if v is not None]
+    for key, v, n in extra:
+        if v.size != n:
+            raise RecordError("'%s' must hold %d floats, got %d" % (key, n, v.size))
+        feats.append((key, v))
+    if extra:
+        feats.append(("meta/has_3d", [1]))
     return serialize_example(feats)
 
 

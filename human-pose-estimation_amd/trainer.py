@@ -671,6 +671,35 @@ class Trainer(object):
                         writer.image("%s/%d" % (family, i), png, record + 1)
         return out
 
+    def score_checkpoint_3d(self, dataset, restore=True):
+        """MPJPE, PA-MPJPE, PVE and PA-PVE (DESIGN.md "3-D pose scores") of the newest checkpoint over ONE pass of ``dataset``, an iterable
+        of ``(images_or_records, gt)``: images [B,224,224,3], or a list of parsed image records, loaded as ``validate_checkpoint`` loads
+        them (centre crop, no flip); ``gt`` a dict with ``theta`` [B,85], or with ``joints3d`` [B,19 or 14,3] and optionally ``verts``
+        [B,6890,3] and ``joint_weights``.  -> ``metrics.Scores3D.result()`` of the last IEF stage, plus ``"stages"``: the same for every
+        stage, and ``"batches"``.  Data-parallel: every rank scores its shard and the sums are added over the ranks in one collective;
+        rank 0 logs."""
+        from .metrics import Scores3D
+
+        if restore:
+            self.restore()
+        scores, batches = Scores3D(), 0
+        for images, gt in dataset:
+            if isinstance(images, (tuple, list)):
+                images = self._load_images(images, augment=False)[0]
+            joint_err, summary, _ = self.predictor.score_step_3d(images, theta_gt=gt.get("theta"), joints3d_gt=gt.get("joints3d"),
+                                                                 verts_gt=gt.get("verts"), joint_weights=gt.get("joint_weights"))
+            scores.add(joint_err, summary)
+            batches += 1
+        if not batches:
+            raise ValueError("the dataset yields no batch")
+        if self.reducer is not None:
+            scores.reduce(self.reducer)
+        out = scores.result()
+        out["stages"], out["batches"] = scores.results(), batches
+        self.log("3-D scores over %d images: mpjpe=%.1f mm pa_mpjpe=%.1f mm pve=%.1f mm pa_pve=%.1f mm pck3d_150=%.3f auc3d=%.3f"
+                 % (out["images"], out["mpjpe_mm"], out["pa_mpjpe_mm"], out["pve_mm"], out["pa_pve_mm"], out["pck3d_150"], out["auc3d"]))
+        return out
+
     # ------------------------------------------------------------------ checkpoints
     def weights(self):
         """the live networks as the Keras-layout dict (host arrays): encoder with its moving statistics, regressor, critic, and

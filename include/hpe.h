@@ -631,6 +631,35 @@ int hpe_eval_scores(const float* const* verts2d_dev, const int* faces_dev, int F
                     const float* const* kp2d_dev, int n_stage, int B, int P, int K, int H, int W, int* counts_dev, float* kp_err_dev,
                     float* norm_dev, void* stream);
 
+/* The 3-D scores of a batch (DESIGN.md "3-D pose scores"; restated in float64 by tests/pose3d_ref.py), for all n_stage IEF stages in ONE
+ * launch, one workgroup per (image, stage).  joints_dev: a host array of n_stage device pointers, each [B,K,3]; joints_gt_dev [B,K,3];
+ * joint_weights_dev [B,K], a joint is scored where its weight is > 0 (NULL: all are).  verts_dev (n_stage pointers, each [B,P,3]) and
+ * verts_gt_dev [B,P,3] are given together or both NULL (joints only).  Units are the caller's.
+ * The fit of a predicted cloud X to the ground truth Y over the scored points: means mu1, mu2; K = sum (x - mu1) (y - mu2)^T;
+ * var1 = sum |x - mu1|^2; R the proper rotation that maximises trace(R K) (never a reflection); scale = trace(R K) / var1;
+ * t = mu2 - scale R mu1.  It is undefined for fewer than 3 scored points or var1 == 0.  var1 is taken as sum |x'|^2 - n |mean x'|^2 of
+ * the points relative to the first scored one, and the test is "<= 0": exact for points that coincide (every x' is 0), while points
+ * within rounding of each other, not equal, may fall on either side of it -- their fit means nothing either way.  The root of a skeleton is the mean of its joints
+ * root_a and root_b (equal: a pelvis joint), defined when both are scored.
+ * joint_err_dev [n_stage][B][2][K]: row 0 |(x - rootX) - (y - rootY)|, row 1 |scale R (x - mu1) - (y - mu2)| with the fit on the scored
+ *   joints; -1 where the joint is not scored, NaN where the alignment is undefined.
+ * summary_dev [n_stage][B][6]: the means of the two rows over the scored joints (MPJPE, PA-MPJPE), the means over all P vertices of the
+ *   vertices translated by the JOINT roots (PVE) and aligned by the fit on the vertices themselves (PA-PVE), the number of scored
+ *   joints, and the flags as a float: 1 a root joint is not scored (MPJPE and PVE are NaN), 2 the joint fit is undefined (PA-MPJPE is
+ *   NaN), 4 the vertex fit is undefined (PA-PVE is NaN), 8 no vertices were given (PVE and PA-PVE are NaN).
+ * xform_dev [n_stage][B][2][13]: scale, R row-major, t of the joint fit and of the vertex fit (NaN where undefined or absent).
+ * Any output may be NULL, not all.  Every sum and the 3x3 solve are float64 in an order the launch shape fixes; the outputs are float32.
+ * A NaN coordinate of a scored point makes that image's values NaN and nothing else.  Stateless like hpe_eval_scores: no context, no
+ * workspace, no synchronisation, no allocation, no atomics, capturable; the same inputs give the same bits.  HPE_ERR_INVALID with a
+ * message, before any HIP call, for NULL joints (or a NULL entry), n_stage outside [1, 16], B or K < 1, a root outside [0, K), vertices
+ * on one side only, P < 1 with vertices, and all three outputs NULL. */
+int hpe_pose3d_scores(const float* const* joints_dev, const float* joints_gt_dev, const float* joint_weights_dev, const float* const* verts_dev,
+                      const float* verts_gt_dev, int n_stage, int B, int K, int P, int root_a, int root_b, float* joint_err_dev,
+                      float* summary_dev, float* xform_dev, void* stream);
+/* The host build of the 3x3 solver of the call above (csrc/procrustes3.h): K, R row-major; R is the proper rotation that maximises
+ * trace(R K), *trace_RK that maximum.  A K that holds a NaN or an infinity gives NaN.  No device needed. */
+int hpe_debug_procrustes3(const double K[9], double R[9], double* trace_RK);
+
 /* -- the steps right before / after the path -------------------------- */
 /* preprocess_image (preview.py:18-35) = resize_img + scale_and_crop (src/util/image.py:7-39) + [-1,1] normalisation,
  * fused: img_dev uint8 [H,W,C] (C = 3 or 4, RGB first) -> out224_dev float [224,224,3].
