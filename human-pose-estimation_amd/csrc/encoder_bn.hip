@@ -16,6 +16,8 @@
 // rank's rows as [2][N] doubles (added over the slices in the finish kernels' order), the caller adds the other ranks' to them, and
 // bn_stats_from_sums_kernel / bn_bwd_from_sums_kernel finish from the sums over all M rows with the arithmetic of the one-rank finish.
 // N is a multiple of 64 on every layer; rows past M are never read.
+// bn_geom and bn_bad_shape (the slicing and the shapes taken, at `vec` channels a thread) and the finish launches serve the bf16 first
+// stages of encoder_bn_bf16.hip too, whose launchers are overloads of the ones here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,29 +25,6 @@
 #include "hpe_ctx.h"
 
 namespace {
-
-struct BnGeom {
-    int cg;    // channel groups (of four) per workgroup: min(N / 4, 64)
-    int rows;  // row lanes per workgroup: 256 / cg
-    int gx;    // workgroups along N
-    int P;     // pixels per slice
-    int slices;
-};
-
-BnGeom geom(int M, int N) {
-    BnGeom g{};
-    const int n4 = N / 4;
-    g.cg = std::min(n4, 64);
-    g.rows = 256 / g.cg;
-    g.gx = n4 / g.cg;
-    // at least eight rows per thread, about 2048 workgroups at most, and a partial buffer of BN_PART_COLS columns
-    int sl = std::max(1, (M + g.rows * 8 - 1) / (g.rows * 8));
-    sl = std::min(sl, std::max(1, 2048 / g.gx));
-    sl = std::min(sl, std::min(BN_MAX_SLICES, BN_PART_COLS / N));
-    g.P = (M + sl - 1) / sl;
-    g.slices = (M + g.P - 1) / g.P;
-    return g;
-}
 
 // acc[0..3] / acc[4..7] of the workgroup's row lanes, added in ascending lane order; lane 0 of every column writes part[slice][0 / 1][N]
 __device__ inline void bn_block_reduce(const double (&acc)[8], int cg, int rows, int N, double* __restrict__ part) {
@@ -308,12 +287,50 @@ __global__ __launch_bounds__(256) void bn_install_kernel(const float* __restrict
 const f32x4* q4(const float* p) { return reinterpret_cast<const f32x4*>(p); }
 f32x4* q4(float* p) { return reinterpret_cast<f32x4*>(p); }
 
-// N: whole workgroups of channel groups along N (geom: N / 4 at most 64, or a multiple of 64), which every ResNet-50 layer has
-bool bad_shape(long M, int N) { return M < 1 || M > 0x7fffffffL / 2 || N < 64 || N > 2048 || (N <= 256 ? N % 64 != 0 : N % 256 != 0); }
+constexpr int VEC = 4;  // channels a thread
+bool bad_shape(long M, int N) { return bn_bad_shape(M, N, VEC); }
+
+// the first launch of each reduction; *slices: how many partials the finish adds
+hipError_t launch_stats(const float* z, int M, int N, double* part, int* slices, hipStream_t st) {
+    if (bad_shape(M, N)) return hipErrorInvalidValue;
+    const BnGeom g = bn_geom(M, N, VEC);
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(z), M, N, g.cg, g.rows, g.P, part);
+    *slices = g.slices;
+    return hipGetLastError();
+}
+
+hipError_t launch_bwd_reduce(const float* dy, const float* y, const float* z, const float* mu, const float* r, int M, int N, double* part, int* slices,
+                             hipStream_t st) {
+    if (bad_shape(M, N)) return hipErrorInvalidValue;
+    const BnGeom g = bn_geom(M, N, VEC);
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(dy), q4(y), q4(z), q4(mu), q4(r), M, N, g.cg, g.rows, g.P, part);
+    *slices = g.slices;
+    return hipGetLastError();
+}
 
 }  // namespace
 
-int bn_slices(int M, int N) { return bad_shape(M, N) ? -1 : geom(M, N).slices; }
+// vec channels a thread: N is whole workgroups of channel groups (N / vec at most 64, or a multiple of 64), which every ResNet-50 layer has
+bool bn_bad_shape(long M, int N, int vec) {
+    return M < 1 || M > 0x7fffffffL / 2 || N < 64 || N > 2048 || (N <= 64 * vec ? N % 64 != 0 : N % (64 * vec) != 0);
+}
+
+BnGeom bn_geom(int M, int N, int vec) {
+    BnGeom g{};
+    const int nv = N / vec;
+    g.cg = std::min(nv, 64);
+    g.rows = 256 / g.cg;
+    g.gx = nv / g.cg;
+    // at least eight rows per thread, about 2048 workgroups at most, and a partial buffer of BN_PART_COLS columns
+    int sl = std::max(1, (M + g.rows * 8 - 1) / (g.rows * 8));
+    sl = std::min(sl, std::max(1, 2048 / g.gx));
+    sl = std::min(sl, std::min(BN_MAX_SLICES, BN_PART_COLS / N));
+    g.P = (M + sl - 1) / sl;
+    g.slices = (M + g.P - 1) / g.P;
+    return g;
+}
+
+int bn_slices(int M, int N) { return bad_shape(M, N) ? -1 : bn_geom(M, N, VEC).slices; }
 
 // the second launch of each reduction: from the slices' partials part[slice][2][N], whichever kernel wrote them (encoder_bn_bf16.hip too)
 hipError_t bn_finish_stats(const double* part, int slices, int M, int N, float eps, float* mu, float* var, float* r, hipStream_t st) {
@@ -337,17 +354,15 @@ hipError_t bn_finish_bwd_sums(const double* part, int slices, int N, double* sum
 }
 
 hipError_t bn_launch_stats(const float* z, int M, int N, float eps, double* part, float* mu, float* var, float* r, hipStream_t st) {
-    if (bad_shape(M, N)) return hipErrorInvalidValue;
-    const BnGeom g = geom(M, N);
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(z), M, N, g.cg, g.rows, g.P, part);
-    return bn_finish_stats(part, g.slices, M, N, eps, mu, var, r, st);
+    int slices;
+    hipError_t e = launch_stats(z, M, N, part, &slices, st);
+    return e != hipSuccess ? e : bn_finish_stats(part, slices, M, N, eps, mu, var, r, st);
 }
 
 hipError_t bn_launch_stats_sums(const float* z, int M, int N, double* part, double* sums, hipStream_t st) {
-    if (bad_shape(M, N)) return hipErrorInvalidValue;
-    const BnGeom g = geom(M, N);
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(z), M, N, g.cg, g.rows, g.P, part);
-    return bn_finish_sums(part, g.slices, N, sums, st);
+    int slices;
+    hipError_t e = launch_stats(z, M, N, part, &slices, st);
+    return e != hipSuccess ? e : bn_finish_sums(part, slices, N, sums, st);
 }
 
 hipError_t bn_launch_stats_from_sums(const double* sums, double M, int N, float eps, float* mu, float* var, float* r, hipStream_t st) {
@@ -366,18 +381,16 @@ hipError_t bn_launch_apply(const float* z, const float* mu, const float* r, cons
 
 hipError_t bn_launch_bwd_reduce(const float* dy, const float* y, const float* z, const float* mu, const float* r, int M, int N, double* part, float* db,
                                 float* dgamma, float* dbeta, hipStream_t st) {
-    if (bad_shape(M, N)) return hipErrorInvalidValue;
-    const BnGeom g = geom(M, N);
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(dy), q4(y), q4(z), q4(mu), q4(r), M, N, g.cg, g.rows, g.P, part);
-    return bn_finish_bwd(part, g.slices, N, db, dgamma, dbeta, st);
+    int slices;
+    hipError_t e = launch_bwd_reduce(dy, y, z, mu, r, M, N, part, &slices, st);
+    return e != hipSuccess ? e : bn_finish_bwd(part, slices, N, db, dgamma, dbeta, st);
 }
 
 hipError_t bn_launch_bwd_sums(const float* dy, const float* y, const float* z, const float* mu, const float* r, int M, int N, double* part, double* sums,
                               float* db, float* dgamma, float* dbeta, hipStream_t st) {
-    if (bad_shape(M, N)) return hipErrorInvalidValue;
-    const BnGeom g = geom(M, N);
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, q4(dy), q4(y), q4(z), q4(mu), q4(r), M, N, g.cg, g.rows, g.P, part);
-    return bn_finish_bwd_sums(part, g.slices, N, sums, db, dgamma, dbeta, st);
+    int slices;
+    hipError_t e = launch_bwd_reduce(dy, y, z, mu, r, M, N, part, &slices, st);
+    return e != hipSuccess ? e : bn_finish_bwd_sums(part, slices, N, sums, db, dgamma, dbeta, st);
 }
 
 hipError_t bn_launch_bwd_from_sums(const double* sums, int N, float* red, hipStream_t st) {

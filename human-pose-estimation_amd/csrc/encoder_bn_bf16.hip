@@ -1,6 +1,7 @@
 // encoder_bn_bf16.hip -- BatchNorm with the statistics of the batch on bf16 tensors, for the mixed-precision encoder walk with batch
-// statistics (encoder_train.hip, WALK_MIXED_BATCH; DESIGN.md section 4, "Mixed-precision encoder training with batch statistics"): the
-// bf16 forms of the four memory passes of encoder_bn.hip.  Per layer, z16 [M][N] = RNE(conv(x16, W16) + b), M = B * hout * hout:
+// statistics (encoder_train.hip, the walks at T = bf16e; DESIGN.md section 4, "Mixed-precision encoder training with batch statistics"):
+// the bf16 forms of the four memory passes of encoder_bn.hip, launched by the cmx16 / mx16 overloads of its bn_launch_* functions with its
+// geometry (bn_geom, bn_bad_shape) at eight channels a thread.  Per layer, z16 [M][N] = RNE(conv(x16, W16) + b), M = B * hout * hout:
 //
 //   forward    mu, var, r of z16 (what is normalised is what was measured)    y16 = RNE(act(gamma * ((z16 - mu) * r) + beta (+ res16)))
 //   backward   dz = dy16 * [y16 > 0] (exact)    xhat = (z16 - mu) * r    dbeta = sum_m dz    dgamma = sum_m dz * xhat
@@ -27,29 +28,6 @@ namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-struct Bn16Geom {
-    int cg;    // channel groups (of eight) per workgroup: min(N / 8, 64)
-    int rows;  // row lanes per workgroup: 256 / cg
-    int gx;    // workgroups along N
-    int P;     // pixels per slice
-    int slices;
-};
-
-Bn16Geom geom(int M, int N) {
-    Bn16Geom g{};
-    const int n8 = N / 8;
-    g.cg = std::min(n8, 64);
-    g.rows = 256 / g.cg;
-    g.gx = n8 / g.cg;
-    // at least eight rows per thread, about 2048 workgroups at most, and a partial buffer of BN_PART_COLS columns
-    int sl = std::max(1, (M + g.rows * 8 - 1) / (g.rows * 8));
-    sl = std::min(sl, std::max(1, 2048 / g.gx));
-    sl = std::min(sl, std::min(BN_MAX_SLICES, BN_PART_COLS / N));
-    g.P = (M + sl - 1) / sl;
-    g.slices = (M + g.P - 1) / g.P;
-    return g;
-}
-
 // eight floats of a 16-byte aligned per-channel array / of one that is only float-aligned (the caller's gradient)
 __device__ __forceinline__ void load8(const float* __restrict__ p, int c8, float (&o)[8]) {
     const f32x4 a = reinterpret_cast<const f32x4*>(p)[2 * c8], b = reinterpret_cast<const f32x4*>(p)[2 * c8 + 1];
@@ -62,7 +40,7 @@ __device__ __forceinline__ void load8_unaligned(const float* __restrict__ p, int
 
 // acc[0..7] / acc[8..15] of the workgroup's row lanes, added in ascending lane order; lane 0 of every column writes part[slice][0 / 1][N].
 // Every thread of the workgroup arrives here
-__device__ inline void bn16_block_reduce(const double (&acc)[16], int cg, int rows, int N, double* __restrict__ part) {
+__device__ inline void bn_block_reduce_bf16(const double (&acc)[16], int cg, int rows, int N, double* __restrict__ part) {
     __shared__ double red[8][256];
     const int t = threadIdx.x, col = t % cg, ry = t / cg;
     const int n = (blockIdx.x * cg + col) * 8;
@@ -110,7 +88,7 @@ __global__ __launch_bounds__(256) void bn_stats_bf16_kernel(const bf16x8* __rest
         for (int u = 0; u < 8; ++u) add(v[u]);
     }
     for (; m < m_end; m += rows) add(z[(size_t)m * n8 + c8]);
-    bn16_block_reduce(acc, cg, rows, N, part);
+    bn_block_reduce_bf16(acc, cg, rows, N, part);
 }
 
 // y16 = RNE(act(gamma * ((z16 - mu) * r) + beta (+ res16))): bn_apply_kernel's expression, the residual added in fp32 before the one
@@ -179,7 +157,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_bf16_kernel(const bf16x8* _
         const bf16x8 d = dy[i];
         add(d, y ? y[i] : d, z[i]);
     }
-    bn16_block_reduce(acc, cg, rows, N, part);
+    bn_block_reduce_bf16(acc, cg, rows, N, part);
 }
 
 // dz = dy16 * [y16 > 0] (y == nullptr: dz = dy16), exact, and dzraw16 = RNE(gamma * r * (dz - dbeta / M - xhat * (dgamma / M))):
@@ -216,12 +194,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_bf16_kernel(const bf16x8* dy
 const bf16x8* v8(cmx16 p) { return reinterpret_cast<const bf16x8*>(p); }
 bf16x8* v8(mx16 p) { return reinterpret_cast<bf16x8*>(p); }
 
-// N: whole workgroups of channel groups along N (geom: N / 8 at most 64, or a multiple of 64), which every ResNet-50 layer has
-bool bad_shape(long M, int N) { return M < 1 || M > 0x7fffffffL / 2 || N < 64 || N > 2048 || (N <= 512 ? N % 64 != 0 : N % 512 != 0); }
+constexpr int VEC = 8;  // channels a thread
+bool bad_shape(long M, int N) { return bn_bad_shape(M, N, VEC); }
 
 hipError_t launch_stats(cmx16 z, int M, int N, double* part, int* slices, hipStream_t st) {
     if (bad_shape(M, N)) return hipErrorInvalidValue;
-    const Bn16Geom g = geom(M, N);
+    const BnGeom g = bn_geom(M, N, VEC);
     hipLaunchKernelGGL(bn_stats_bf16_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, v8(z), M, N, g.cg, g.rows, g.P, part);
     *slices = g.slices;
     return hipGetLastError();
@@ -229,7 +207,7 @@ hipError_t launch_stats(cmx16 z, int M, int N, double* part, int* slices, hipStr
 
 hipError_t launch_bwd_reduce(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, int M, int N, double* part, int* slices, hipStream_t st) {
     if (bad_shape(M, N)) return hipErrorInvalidValue;
-    const Bn16Geom g = geom(M, N);
+    const BnGeom g = bn_geom(M, N, VEC);
     hipLaunchKernelGGL(bn_bwd_reduce_bf16_kernel, dim3(g.gx, g.slices), dim3(256), 0, st, v8(dy), v8(y), v8(z), mu, r, M, N, g.cg, g.rows, g.P, part);
     *slices = g.slices;
     return hipGetLastError();
@@ -237,42 +215,42 @@ hipError_t launch_bwd_reduce(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const 
 
 }  // namespace
 
-hipError_t bn16_launch_stats(cmx16 z, int M, int N, float eps, double* part, float* mu, float* var, float* r, hipStream_t st) {
+hipError_t bn_launch_stats(cmx16 z, int M, int N, float eps, double* part, float* mu, float* var, float* r, hipStream_t st) {
     int slices;
     hipError_t e = launch_stats(z, M, N, part, &slices, st);
     return e != hipSuccess ? e : bn_finish_stats(part, slices, M, N, eps, mu, var, r, st);
 }
 
-hipError_t bn16_launch_stats_sums(cmx16 z, int M, int N, double* part, double* sums, hipStream_t st) {
+hipError_t bn_launch_stats_sums(cmx16 z, int M, int N, double* part, double* sums, hipStream_t st) {
     int slices;
     hipError_t e = launch_stats(z, M, N, part, &slices, st);
     return e != hipSuccess ? e : bn_finish_sums(part, slices, N, sums, st);
 }
 
-hipError_t bn16_launch_apply(cmx16 z, const float* mu, const float* r, const float* gamma, const float* beta, cmx16 res, int relu, mx16 y, int M, int N,
-                             hipStream_t st) {
+hipError_t bn_launch_apply(cmx16 z, const float* mu, const float* r, const float* gamma, const float* beta, cmx16 res, int relu, mx16 y, int M, int N,
+                           hipStream_t st) {
     if (bad_shape(M, N)) return hipErrorInvalidValue;
     const long n8 = (long)M * (N / 8);
     hipLaunchKernelGGL(bn_apply_bf16_kernel, grid1(n8), dim3(256), 0, st, v8(z), mu, r, gamma, beta, v8(res), relu, v8(y), n8, N / 8);
     return hipGetLastError();
 }
 
-hipError_t bn16_launch_bwd_reduce(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, int M, int N, double* part, float* db, float* dgamma,
-                                  float* dbeta, hipStream_t st) {
+hipError_t bn_launch_bwd_reduce(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, int M, int N, double* part, float* db, float* dgamma,
+                                float* dbeta, hipStream_t st) {
     int slices;
     hipError_t e = launch_bwd_reduce(dy, y, z, mu, r, M, N, part, &slices, st);
     return e != hipSuccess ? e : bn_finish_bwd(part, slices, N, db, dgamma, dbeta, st);
 }
 
-hipError_t bn16_launch_bwd_sums(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, int M, int N, double* part, double* sums, float* db,
-                                float* dgamma, float* dbeta, hipStream_t st) {
+hipError_t bn_launch_bwd_sums(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, int M, int N, double* part, double* sums, float* db,
+                              float* dgamma, float* dbeta, hipStream_t st) {
     int slices;
     hipError_t e = launch_bwd_reduce(dy, y, z, mu, r, M, N, part, &slices, st);
     return e != hipSuccess ? e : bn_finish_bwd_sums(part, slices, N, sums, db, dgamma, dbeta, st);
 }
 
-hipError_t bn16_launch_bwd_apply(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, const float* gamma, const float* dgamma,
-                                 const float* dbeta, int M, int N, mx16 dz, mx16 dzraw, hipStream_t st, double M_all) {
+hipError_t bn_launch_bwd_apply(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, const float* gamma, const float* dgamma, const float* dbeta,
+                               int M, int N, mx16 dz, mx16 dzraw, hipStream_t st, double M_all) {
     if (bad_shape(M, N)) return hipErrorInvalidValue;
     const long n8 = (long)M * (N / 8);
     hipLaunchKernelGGL(bn_bwd_apply_bf16_kernel, grid1(n8), dim3(256), 0, st, v8(dy), v8(y), v8(z), mu, r, gamma, dgamma, dbeta,

@@ -7,6 +7,7 @@
 // slice writes its partial tile; conv_wg_fixup_kernel adds the slices in ascending order, writes dW and the per-64-row partial sums of
 // <W, G>; conv_wg_finish_kernel adds those and the per-slice column sums of dz in ascending order.  No atomics anywhere: the same inputs
 // give the same bits.  Rows past M, taps outside the map and columns past K / N are masked to zero and never read.
+// The launchers here take float tensors; encoder_grad_bf16.hip holds their overloads on bf16 ones, and shares wg_slicing and wg_finish.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -251,20 +252,14 @@ int wg_slices_unrounded(int idx, int B) {
 
 }  // namespace
 
-void wg_slicing(int idx, int B, int* P, int* slices) {
+// a slice is whole groups of `group` pixels: 8 for conv_wg_gemm_kernel, 16 for conv_wg_gemm_bf16_kernel (encoder_grad_bf16.hip)
+void wg_slicing(int idx, int B, int group, int* P, int* slices) {
     const int M = B * specs()[idx].hout * specs()[idx].hout, sl = wg_slices_unrounded(idx, B);
-    *P = round_up((M + sl - 1) / sl, 8);
+    *P = round_up((M + sl - 1) / sl, group);
     *slices = (M + *P - 1) / *P;
 }
 
-// the same with whole groups of 16 pixels a slice: what conv_wg_gemm_bf16_kernel (encoder_grad_bf16.hip) steps by
-void wg_slicing16(int idx, int B, int* P, int* slices) {
-    const int M = B * specs()[idx].hout * specs()[idx].hout, sl = wg_slices_unrounded(idx, B);
-    *P = round_up((M + sl - 1) / sl, 16);
-    *slices = (M + *P - 1) / *P;
-}
-
-// sized from the slice count before P is rounded to a multiple of 8, which is monotone in the batch and never below the count wg_slicing
+// sized from the slice count before P is rounded to whole groups, which is monotone in the batch and never below the count wg_slicing
 // ends with (the rounded count is not monotone in the batch: a larger P can leave fewer slices)
 size_t wg_partial_floats(int B) {
     size_t need = 0;
@@ -299,7 +294,7 @@ hipError_t weight_grad(hpe_ctx* c, int idx, const float* x, const float* dz, int
     a.stride = s.stride;
     a.pad = (s.kh - 1) / 2;
     int slices;
-    wg_slicing(idx, B, &a.P, &slices);
+    wg_slicing(idx, B, 8, &a.P, &slices);
     a.n_nt = (a.N + 63) / 64;
     const int n_kt = (a.K + 63) / 64, n_kc = (a.K + 3) / 4;
     if ((size_t)slices * a.K * a.N > w.partial_floats || slices > WG_MAX_SLICES || (size_t)n_kc * a.N > WG_WGP_FLOATS) return hipErrorInvalidValue;

@@ -1,6 +1,7 @@
 // encoder_grad_bf16.hip -- the kernels of the mixed-precision encoder walks and their launchers: bf16 activations, bf16 cotangents, bf16
 // matrix products with fp32 accumulation, fp32 gradients of fp32 master weights (encoder_train.hip holds the walks; DESIGN.md section 4,
-// "Mixed-precision encoder training", states the rounding points).
+// "Mixed-precision encoder training", states the rounding points).  The launchers are the cmx16 / mx16 overloads of those of
+// encoder_grad.hip (gate, weight_grad, data_grad, scatter2, avgpool_bwd, maxpool_bwd), plus the weight cast and the layer's bf16 convolution.
 //
 // conv_wg_gemm_bf16_kernel: G[k][n] = sum_m A[m][k] dz[m][n] on v_mfma_f32_32x32x16_bf16.  The reduction index is the pixel, and the MFMA
 // wants eight reduction elements per lane, while NHWC memory has the channels contiguous: the operands are transposed in registers.  For
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(64) void conv_wg_gemm_bf16_kernel(WgArgs16 a) {
             bv[u] = (live && nok) ? *reinterpret_cast<const unsigned*>(a.dz + (long)m * a.N + col) : 0u;
             m += 2;
             wo += 2;
-            if (wo >= a.Wo) {  // Wo >= 2 (mx_weight_grad refuses anything else): one wrap per step
+            if (wo >= a.Wo) {  // Wo >= 2 (weight_grad refuses anything else): one wrap per step
                 wo -= a.Wo;
                 if (++ho >= a.Ho) {
                     ho = 0;
@@ -289,12 +290,12 @@ hipError_t mx_conv_forward(hpe_ctx* c, int idx, cmx16 x, int B, cmx16 res, int r
     return hpe_launch_gemm_bf16(p, r.mode, r.tile, st);
 }
 
-void mx_gate(cmx16 dy, cmx16 y, const float* s, mx16 dz, mx16 dzs, long n, int N, hipStream_t st) {
+void gate(cmx16 dy, cmx16 y, const float* s, mx16 dz, mx16 dzs, long n, int N, hipStream_t st) {
     hipLaunchKernelGGL(enc_gate_bf16_kernel, grid1(n / 8), dim3(256), 0, st, reinterpret_cast<const bf16x8*>(dy), reinterpret_cast<const bf16x8*>(y), s,
                        reinterpret_cast<bf16x8*>(dz), reinterpret_cast<bf16x8*>(dzs), n / 8, N / 8);
 }
 
-hipError_t mx_weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* grad_layer, hipStream_t st, bool bn) {
+hipError_t weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* grad_layer, hipStream_t st, bool bn) {
     const ConvSpec& s = specs()[idx];
     EncTrainWork& w = c->et;
     const bool stem = idx == 0;
@@ -315,7 +316,7 @@ hipError_t mx_weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* 
     }
     a.K = s.kh * s.kw * a.Cin;
     int slices;
-    wg_slicing16(idx, B, &a.P, &slices);
+    wg_slicing(idx, B, 16, &a.P, &slices);
     a.n_nt = (a.N + 63) / 64;
     const int K = s.kh * s.kw * s.cin;  // rows of dW
     const int n_kt = (a.K + 63) / 64, n_kc = (K + 3) / 4;
@@ -324,7 +325,7 @@ hipError_t mx_weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* 
     if (a.Wo < 2 || a.P < 16 || a.P % 16 != 0 || a.Cin % 2 != 0 || a.N % 2 != 0) return hipErrorInvalidValue;
     if (stem && (s.kh != 7 || s.cin != 3 || 2 * (s.hout - 1) + 7 > STEM_HP || 2 * (s.hout - 1) + 7 > STEM_WP)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(conv_wg_gemm_bf16_kernel, dim3(n_kt * a.n_nt, slices), dim3(64), 0, st, a);
-    const unsigned short* w16 = stem ? w.mx_w[0] : w.mx_dxw[idx];
+    cmx16 w16 = stem ? w.mx_w[0] : w.mx_dxw[idx];
     const int wrow = stem ? conv_k_pad(0, true) : s.kh * s.kw * s.cout;
     hipLaunchKernelGGL(conv_wg_fixup_bf16_kernel, dim3(a.n_nt, n_kc), dim3(256), 0, st, w.partial, slices, K, a.K, a.N, w16, stem ? 1 : 0, s.cin,
                        s.kh * s.kw, wrow, bn ? c->ones : c->conv[idx].scale, grad_layer, w.wgp);
@@ -332,7 +333,7 @@ hipError_t mx_weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* 
     return wg_finish(c, idx, n_kc, slices, grad_layer, st);
 }
 
-hipError_t mx_data_grad(hpe_ctx* c, int idx, cmx16 dzs, int B, cmx16 res, mx16 out, hipStream_t st) {
+hipError_t data_grad(hpe_ctx* c, int idx, cmx16 dzs, int B, cmx16 res, mx16 out, hipStream_t st) {
     const ConvSpec& s = specs()[idx];
     GemmArgs p{};
     p.x = as_f(dzs);
@@ -360,13 +361,13 @@ hipError_t mx_data_grad(hpe_ctx* c, int idx, cmx16 dzs, int B, cmx16 res, mx16 o
 }
 
 // a move of 16-byte words, whatever they hold: the fp32 launch on C / 2 floats a pixel (C % 8 == 0)
-void mx_scatter2(cmx16 lo, mx16 hi, int B, int H, int C, hipStream_t st) { scatter2(as_f(lo), as_f(hi), B, H, C / 2, st); }
+void scatter2(cmx16 lo, mx16 hi, int B, int H, int C, hipStream_t st) { scatter2(as_f(lo), as_f(hi), B, H, C / 2, st); }
 
-void mx_avgpool_bwd(const float* dy, mx16 dx, int B, int HW, int C, hipStream_t st) {
+void avgpool_bwd(const float* dy, mx16 dx, int B, int HW, int C, hipStream_t st) {
     hipLaunchKernelGGL(enc_avgpool_bwd_bf16_kernel, grid1((long)B * HW * (C / 8)), dim3(256), 0, st, dy, reinterpret_cast<bf16x8*>(dx), B, HW, C / 8);
 }
 
-void mx_maxpool_bwd(cmx16 x, cmx16 dy, mx16 dx, int B, int H, int C, hipStream_t st) {
+void maxpool_bwd(cmx16 x, cmx16 dy, mx16 dx, int B, int H, int C, hipStream_t st) {
     hipLaunchKernelGGL(enc_maxpool_bwd_bf16_kernel, grid1((long)B * H * H * (C / 8)), dim3(256), 0, st, reinterpret_cast<const bf16x8*>(x),
                        reinterpret_cast<const bf16x8*>(dy), reinterpret_cast<bf16x8*>(dx), B, H, C / 8);
 }

@@ -14,8 +14,9 @@
 //
 // The kernels and their launchers are in encoder_grad.hip, those of BatchNorm with batch statistics in encoder_bn.hip, those of the
 // mixed-precision walks (bf16 activations and cotangents on this fp32 context) in encoder_grad_bf16.hip and, for their BatchNorm with
-// batch statistics, encoder_bn_bf16.hip; this file holds the layout, the reserves, the two walks (one forward, one backward, each taking
-// the BatchNorm mode and the precision as per-layer choices) and the C ABI.
+// batch statistics, encoder_bn_bf16.hip; each launcher is an overload on the element type of its tensors (float, or bf16e for bf16).
+// This file holds the layout, the reserves, the two walks and the C ABI.  The walks (one forward, one backward) are templates on that
+// element type and take the BatchNorm mode as a per-layer choice; Prec<T> states the few steps in which the precisions really differ.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,66 +56,66 @@ const EncLayout& layout() {
 
 namespace {
 
-// Every buffer of hpe_encoder_train_reserve at batch B, in allocation order, as f(member, floats, zero-filled): the reserve allocates
-// through this and hpe_encoder_train_ws_floats adds it up
-template <class F>
-void train_buffers(EncTrainWork& w, int B, F&& f) {
-    const EncLayout& l = layout();
-    const size_t nb = (size_t)B;
-    f(w.stash, nb * l.stash_per_image, false);
-    f(w.g0, nb * BIG, false);
-    f(w.g1, nb * BIG, false);
-    f(w.sbig, nb * BIG, false);
-    f(w.t0, nb * MID, false);
-    f(w.t1, nb * MID, false);
-    f(w.ssmall, nb * MID, false);
-    f(w.partial, wg_partial_floats(B), false);
-    f(w.dsh, (size_t)WG_MAX_SLICES * 2048, false);
-    f(w.wgp, (size_t)WG_WGP_FLOATS, false);
-    f(w.zeros, 2048, true);
-    f(w.feat, nb * HPE_FEATURE_DIM, false);
-    f(w.flat, l.total, false);
-    f(w.mean, l.channels, false);
-    f(w.istd, l.channels, false);
-    f(w.sd, 2 * (size_t)l.channels, false);  // `channels` doubles
-    for (int i = 1; i < HPE_NUM_CONV; ++i) f(w.dxw[i], conv_dxw_floats(i), false);
+// The activation buffers of one precision at batch B, in allocation order, as f(member, floats, zero-filled); a bf16 element is half a
+// float (every count is even).  zstash is not among them: the batch-statistics reserves add it
+template <class T, class F>
+void act_buffers(EncActs<T>& a, int B, F&& f) {
+    const size_t nb = (size_t)B * sizeof(T);
+    f(a.stash, nb * layout().stash_per_image / sizeof(float), false);
+    f(a.g0, nb * BIG / sizeof(float), false);
+    f(a.g1, nb * BIG / sizeof(float), false);
+    f(a.sbig, nb * BIG / sizeof(float), false);
+    f(a.t0, nb * MID / sizeof(float), false);
+    f(a.t1, nb * MID / sizeof(float), false);
+    f(a.ssmall, nb * MID / sizeof(float), false);
+}
+template <class T, class F>
+void zstash_buffer(EncActs<T>& a, int B, F&& f) {
+    f(a.zstash, (size_t)B * sizeof(T) * layout().stash_pool / sizeof(float), false);
 }
 
-// ... and what hpe_encoder_train_reserve_batchnorm adds
-template <class F>
-void train_buffers_bn(EncTrainWork& w, int B, F&& f) {
-    const EncLayout& l = layout();
-    f(w.zstash, (size_t)B * l.stash_pool, false);
-    f(w.bn_batch, 3 * (size_t)l.channels + 3 * 2048, true);
-    f(w.bn_stats, 2 * (size_t)l.channels, false);
-    f(w.bn_part, 4 * (size_t)BN_PART_COLS, false);  // 2 * BN_PART_COLS doubles
-    f(w.bn_hw, l.channels, false);
-}
-
-// ... and what hpe_encoder_train_reserve_mixed adds: bf16 elements, two to a float (every count is even).  The weight operands are zeroed:
-// the cast that opens a mixed call never writes their k padding
+// Every buffer of a reserve at batch B, in allocation order, through the same f: the reserve allocates through this and
+// hpe_encoder_train_ws_floats* add it up.  RESERVE_BN and RESERVE_MIXED build on RESERVE_FROZEN, RESERVE_BN_MIXED on both
+enum Reserve { RESERVE_NONE, RESERVE_FROZEN, RESERVE_BN, RESERVE_MIXED, RESERVE_BN_MIXED };
 constexpr size_t PADDED16 = (size_t)STEM_HP * STEM_WP * 4;  // the padded bf16 input, per image
 template <class F>
-void train_buffers_mixed(EncTrainWork& w, int B, F&& f) {
+void train_buffers(EncTrainWork& w, Reserve r, int B, F&& f) {
     const EncLayout& l = layout();
     const size_t nb = (size_t)B;
-    f(w.mx_stash, nb * l.stash_per_image / 2, false);
-    f(w.mx_g0, nb * BIG / 2, false);
-    f(w.mx_g1, nb * BIG / 2, false);
-    f(w.mx_sbig, nb * BIG / 2, false);
-    f(w.mx_t0, nb * MID / 2, false);
-    f(w.mx_t1, nb * MID / 2, false);
-    f(w.mx_ssmall, nb * MID / 2, false);
-    f(w.mx_padded, nb * PADDED16 / 2, false);
-    for (int i = 0; i < HPE_NUM_CONV; ++i) f(w.mx_w[i], (size_t)round_up(specs()[i].cout, 128) * conv_k_pad(i, true) / 2, true);
-    for (int i = 1; i < HPE_NUM_CONV; ++i) f(w.mx_dxw[i], conv_dxw_floats(i) / 2, false);
-    f(w.mx_cast, (size_t)MX_CAST_SEGS * sizeof(MxCastSeg) / sizeof(float), false);
-}
-
-// ... and what hpe_encoder_train_reserve_batchnorm_mixed adds to those two: the bf16 raw-output stash
-template <class F>
-void train_buffers_bn_mixed(EncTrainWork& w, int B, F&& f) {
-    f(w.mx_zstash, (size_t)B * layout().stash_pool / 2, false);
+    switch (r) {
+    case RESERVE_NONE:
+        break;
+    case RESERVE_FROZEN:
+        act_buffers(w.f32, B, f);
+        f(w.partial, wg_partial_floats(B), false);
+        f(w.dsh, (size_t)WG_MAX_SLICES * 2048, false);
+        f(w.wgp, (size_t)WG_WGP_FLOATS, false);
+        f(w.zeros, 2048, true);
+        f(w.feat, nb * HPE_FEATURE_DIM, false);
+        f(w.flat, l.total, false);
+        f(w.mean, l.channels, false);
+        f(w.istd, l.channels, false);
+        f(w.sd, 2 * (size_t)l.channels, false);  // `channels` doubles
+        for (int i = 1; i < HPE_NUM_CONV; ++i) f(w.dxw[i], conv_dxw_floats(i), false);
+        break;
+    case RESERVE_BN:
+        zstash_buffer(w.f32, B, f);
+        f(w.bn_batch, 3 * (size_t)l.channels + 3 * 2048, true);
+        f(w.bn_stats, 2 * (size_t)l.channels, false);
+        f(w.bn_part, 4 * (size_t)BN_PART_COLS, false);  // 2 * BN_PART_COLS doubles
+        f(w.bn_hw, l.channels, false);
+        break;
+    case RESERVE_MIXED:  // the weight operands are zeroed: the cast that opens a mixed call never writes their k padding
+        act_buffers(w.b16, B, f);
+        f(w.mx_padded, nb * PADDED16 / 2, false);
+        for (int i = 0; i < HPE_NUM_CONV; ++i) f(w.mx_w[i], (size_t)round_up(specs()[i].cout, 128) * conv_k_pad(i, true) / 2, true);
+        for (int i = 1; i < HPE_NUM_CONV; ++i) f(w.mx_dxw[i], conv_dxw_floats(i) / 2, false);
+        f(w.mx_cast, (size_t)MX_CAST_SEGS * sizeof(MxCastSeg) / sizeof(float), false);
+        break;
+    case RESERVE_BN_MIXED:
+        zstash_buffer(w.b16, B, f);
+        break;
+    }
 }
 
 struct TrainAlloc {  // rc keeps the first failure, which ends the allocations
@@ -131,22 +132,12 @@ size_t ws_floats(int B, bool bn, bool mixed = false, bool bn_mixed = false) {
     EncTrainWork w;
     size_t n = encoder_repack_reserve_floats();  // the layer table of hpe_encoder_set_params_dev, allocated by encoder_repack_reserve
     auto add = [&n](auto&, size_t floats, bool) { n += floats; };
-    train_buffers(w, B, add);
-    if (bn) train_buffers_bn(w, B, add);
-    if (mixed) train_buffers_mixed(w, B, add);
-    if (bn_mixed) train_buffers_bn_mixed(w, B, add);
+    train_buffers(w, RESERVE_FROZEN, B, add);
+    if (bn) train_buffers(w, RESERVE_BN, B, add);
+    if (mixed) train_buffers(w, RESERVE_MIXED, B, add);
+    if (bn_mixed) train_buffers(w, RESERVE_BN_MIXED, B, add);
     return n;
 }
-
-// the walks: frozen statistics in fp32, batch statistics in fp32, frozen statistics in mixed precision, batch statistics in mixed
-// precision.  A mixed walk keeps bf16 elements behind the float pointers of its activations and cotangents (as a bf16 context does
-// behind ConvLayer::w)
-enum Walk { WALK_FROZEN, WALK_BATCH, WALK_MIXED, WALK_MIXED_BATCH };
-bool walk_bn(Walk wk) { return wk == WALK_BATCH || wk == WALK_MIXED_BATCH; }
-bool walk_mx(Walk wk) { return wk == WALK_MIXED || wk == WALK_MIXED_BATCH; }
-cmx16 h16(const float* p) { return reinterpret_cast<cmx16>(p); }
-mx16 h16(float* p) { return reinterpret_cast<mx16>(p); }
-float* f16(mx16 p) { return reinterpret_cast<float*>(p); }
 
 // the data-gradient operand of layer idx in the forward GEMM's Wt[n][k] form: rows = input channels (zero padded to 128), k = output channels
 // (1x1: the HWIO matrix itself) or (tap', output channel) with the taps flipped (3x3)
@@ -161,22 +152,77 @@ void pack_dx_weights(int idx, const float* kernel, std::vector<float>& out) {
         }
 }
 
-float* stash_of(hpe_ctx* c, int idx, int B) {
+// What differs between the two precisions of a walk, each stated once.  T = float: the fp32 walks; T = bf16e: the mixed ones, whose
+// weight operands are cast from the live fp32 weights by the launch that opens every mixed call
+template <class T>
+struct Prec;
+template <>
+struct Prec<float> {
+    static constexpr bool mixed = false;
+    static constexpr const char* suffix = "";
+    static constexpr Reserve reserve(bool bn) { return bn ? RESERVE_BN : RESERVE_FROZEN; }
+    static hipError_t cast(hpe_ctx*, int, int, hipStream_t) { return hipSuccess; }  // the fp32 weights are the operands
+    static float* padded(hpe_ctx* c) { return c->padded; }                          // conv1's input
+    // what conv1's weight gradient reads: the images themselves, with pad = (kh - 1) / 2
+    static constexpr bool wg0_padded = false;
+    static const float* wg0_input(hpe_ctx*, const float* images) { return images; }
+    static void done(EncTrainWork& w, int B, bool) { w.stash_B = B; }
+    // the batch whose activations / raw outputs the stash / zstash holds for the debug calls, or 0 and why not
+    static int stash_batch(const EncTrainWork& w, const char** why) {
+        *why = "no training forward has run";
+        return w.stash_B;
+    }
+    static int zstash_batch(const EncTrainWork& w, const char** why) {
+        *why = w.bn_stat_B == 0   ? "no batch-statistics forward has run"
+               : w.bn_stat_mixed ? "the last batch-statistics forward was a mixed-precision one"
+                                 : "a frozen-statistics forward of another batch has refilled the stash since";
+        return w.bn_stat_mixed || w.stash_B != w.bn_stat_B ? 0 : w.bn_stat_B;
+    }
+};
+template <>
+struct Prec<bf16e> {
+    static constexpr bool mixed = true;
+    static constexpr const char* suffix = "_mixed";
+    static constexpr Reserve reserve(bool bn) { return bn ? RESERVE_BN_MIXED : RESERVE_MIXED; }
+    static hipError_t cast(hpe_ctx* c, int first, int segs, hipStream_t st) { return mx_cast_launch(c, first, segs, st); }
+    static bf16e* padded(hpe_ctx* c) { return c->et.mx_padded; }
+    // ... the padded bf16 input
+    static constexpr bool wg0_padded = true;
+    static const bf16e* wg0_input(hpe_ctx* c, const float*) { return c->et.mx_padded; }
+    // the mixed stash has its own batch counters: the fp32 stash is as it was
+    static void done(EncTrainWork& w, int B, bool bn) {
+        w.mx_stash_B = B;
+        if (bn) w.mx_zstash_B = B;
+    }
+    static int stash_batch(const EncTrainWork& w, const char** why) {
+        *why = "no mixed-precision forward has run";
+        return w.mx_stash_B;
+    }
+    static int zstash_batch(const EncTrainWork& w, const char** why) {
+        *why = w.mx_zstash_B == 0 ? "no mixed-precision batch-statistics forward has run"
+                                  : "a frozen-statistics mixed forward of another batch has refilled the stash since";
+        return w.mx_stash_B != w.mx_zstash_B ? 0 : w.mx_zstash_B;
+    }
+};
+
+template <class T>
+T* stash_of(hpe_ctx* c, int idx, int B) {
     const EncLayout& l = layout();
-    return c->et.stash + (size_t)B * (idx < 0 ? l.stash_pool : l.stash[idx]);
+    return c->et.acts<T>().stash + (size_t)B * (idx < 0 ? l.stash_pool : l.stash[idx]);
 }
 
-// ... of the walk's own stash: the mixed one has the same layout in bf16 elements
-float* stash_of(hpe_ctx* c, Walk wk, int idx, int B) {
-    if (!walk_mx(wk)) return stash_of(c, idx, B);
-    const EncLayout& l = layout();
-    return f16(c->et.mx_stash + (size_t)B * (idx < 0 ? l.stash_pool : l.stash[idx]));
+template <class T>
+hipError_t pad_images(hpe_ctx* c, const float* images, int B, hipStream_t st) {
+    return enc_pad_input(images, Prec<T>::padded(c), B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st);
 }
 
-// ---- BatchNorm with batch statistics (encoder_bn.hip holds the kernels): z kept beside y, the layer's statistics in its slots
+// ---- BatchNorm with batch statistics (encoder_bn.hip / encoder_bn_bf16.hip hold the kernels): z kept beside y, the layer's statistics
+// in its slots
 
-float* zstash_of(hpe_ctx* c, int idx, int B) { return c->et.zstash + (size_t)B * layout().stash[idx]; }
-mx16 mx_zstash_of(hpe_ctx* c, int idx, int B) { return c->et.mx_zstash + (size_t)B * layout().stash[idx]; }
+template <class T>
+T* zstash_of(hpe_ctx* c, int idx, int B) {
+    return c->et.acts<T>().zstash + (size_t)B * layout().stash[idx];
+}
 
 struct BnSlots {
     float *mu, *var, *r;
@@ -206,14 +252,17 @@ hipError_t reduce_call(hpe_ctx* c, int idx, long long count, hipStream_t st) {
 }
 
 // z = conv(x, W) + b (the layer's own route, unit scale, the bias of the flat copy as shift), its statistics, y = act(BN(z) (+ res)).
-// reduce: the statistics of all ranks' rows (the hook is set)
-hipError_t layer_forward_bn(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* z, float* y, const BnSlots& s, hipStream_t st,
+// Mixed: z and y are rounded to bf16 where they are written, and the statistics are those OF the rounded z.
+// reduce: the statistics of all ranks' rows (the hook is set).  Only the first-stage kernels differ between the precisions: the hook
+// sees the same sums at the same place
+template <class T>
+hipError_t layer_forward_bn(hpe_ctx* c, int idx, const T* x, int B, const T* res, int relu, T* z, T* y, const BnSlots& s, hipStream_t st,
                             bool reduce = false) {
     const ConvSpec& sp = specs()[idx];
     const EncLayout& l = layout();
     const float* flat = c->et.flat;
     const int M = B * sp.hout * sp.hout;
-    HIPE(run_conv_nhwc(c, idx, x, B, nullptr, 0, z, st, c->ones, flat + l.off[idx][1]));
+    HIPE(layer_conv(c, idx, x, B, nullptr, 0, z, st, c->ones, flat + l.off[idx][1]));
     if (reduce) {
         HIPE(bn_launch_stats_sums(z, M, sp.cout, c->et.bn_part, reduce_sums(c), st));
         HIPE(reduce_call(c, idx, 2LL * sp.cout, st));
@@ -224,10 +273,11 @@ hipError_t layer_forward_bn(hpe_ctx* c, int idx, const float* x, int B, const fl
     return bn_launch_apply(z, s.mu, s.r, flat + l.off[idx][2], flat + l.off[idx][3], res, relu, y, M, sp.cout, st);
 }
 
-// the gate and the BatchNorm backward of layer idx: db (= 0), dgamma, dbeta into grad_layer; dz (may be nullptr, may alias dy) and dzraw
-// reduce: grad_layer keeps this rank's partial sums, dzraw is that of the batch of all ranks (the hook is set)
-hipError_t layer_gate_bn(hpe_ctx* c, int idx, const float* dy, const float* y, const float* z, int B, const BnSlots& s, float* grad_layer, float* dz,
-                         float* dzraw, hipStream_t st, bool reduce = false) {
+// the gate and the BatchNorm backward of layer idx: db (= 0), dgamma, dbeta (fp32) into grad_layer; dz (exact in bf16 too; may be nullptr,
+// may alias dy) and dzraw.  reduce: grad_layer keeps this rank's partial sums, dzraw is that of the batch of all ranks (the hook is set)
+template <class T>
+hipError_t layer_gate_bn(hpe_ctx* c, int idx, const T* dy, const T* y, const T* z, int B, const BnSlots& s, float* grad_layer, T* dz, T* dzraw,
+                         hipStream_t st, bool reduce = false) {
     const ConvSpec& sp = specs()[idx];
     const int M = B * sp.hout * sp.hout, N = sp.cout, kn = sp.kh * sp.kw * sp.cin * N;
     float *db = grad_layer + kn, *dgamma = db + N, *dbeta = dgamma + N;
@@ -243,155 +293,85 @@ hipError_t layer_gate_bn(hpe_ctx* c, int idx, const float* dy, const float* y, c
     return bn_launch_bwd_apply(dy, y, z, s.mu, s.r, gamma, red + N, red, M, N, dz, dzraw, st, rows_all(c, idx));
 }
 
-// layer_forward_bn in mixed precision: z16 = RNE(conv(x16, W16) + b) through the layer's bf16 route, the statistics OF z16 into the same
-// slots, y16 = RNE(act(BN(z16) (+ res16))).  Only the first-stage kernels differ: the hook sees the same sums at the same place
-hipError_t layer_forward_bn16(hpe_ctx* c, int idx, cmx16 x, int B, cmx16 res, int relu, mx16 z, mx16 y, const BnSlots& s, hipStream_t st,
-                              bool reduce = false) {
-    const ConvSpec& sp = specs()[idx];
-    const EncLayout& l = layout();
-    const float* flat = c->et.flat;
-    const int M = B * sp.hout * sp.hout;
-    HIPE(mx_conv_forward(c, idx, x, B, nullptr, 0, z, st, c->ones, flat + l.off[idx][1]));
-    if (reduce) {
-        HIPE(bn16_launch_stats_sums(z, M, sp.cout, c->et.bn_part, reduce_sums(c), st));
-        HIPE(reduce_call(c, idx, 2LL * sp.cout, st));
-        HIPE(bn_launch_stats_from_sums(reduce_sums(c), rows_all(c, idx), sp.cout, c->cfg.bn_eps, s.mu, s.var, s.r, st));
-    } else {
-        HIPE(bn16_launch_stats(z, M, sp.cout, c->cfg.bn_eps, c->et.bn_part, s.mu, s.var, s.r, st));
-    }
-    return bn16_launch_apply(z, s.mu, s.r, flat + l.off[idx][2], flat + l.off[idx][3], res, relu, y, M, sp.cout, st);
-}
-
-// ... and layer_gate_bn: db (= 0), dgamma, dbeta (fp32) into grad_layer; dz (bf16, exact; may be nullptr, may alias dy) and dzraw16
-hipError_t layer_gate_bn16(hpe_ctx* c, int idx, cmx16 dy, cmx16 y, cmx16 z, int B, const BnSlots& s, float* grad_layer, mx16 dz, mx16 dzraw,
-                           hipStream_t st, bool reduce = false) {
-    const ConvSpec& sp = specs()[idx];
-    const int M = B * sp.hout * sp.hout, N = sp.cout, kn = sp.kh * sp.kw * sp.cin * N;
-    float *db = grad_layer + kn, *dgamma = db + N, *dbeta = dgamma + N;
-    const float* gamma = c->et.flat + layout().off[idx][2];
-    if (!reduce) {
-        HIPE(bn16_launch_bwd_reduce(dy, y, z, s.mu, s.r, M, N, c->et.bn_part, db, dgamma, dbeta, st));
-        return bn16_launch_bwd_apply(dy, y, z, s.mu, s.r, gamma, dgamma, dbeta, M, N, dz, dzraw, st);
-    }
-    float* red = reduce_grads(c);
-    HIPE(bn16_launch_bwd_sums(dy, y, z, s.mu, s.r, M, N, c->et.bn_part, reduce_sums(c), db, dgamma, dbeta, st));
-    HIPE(reduce_call(c, idx, 2LL * N, st));
-    HIPE(bn_launch_bwd_from_sums(reduce_sums(c), N, red, st));
-    return bn16_launch_bwd_apply(dy, y, z, s.mu, s.r, gamma, red + N, red, M, N, dz, dzraw, st, rows_all(c, idx));
-}
-
-// The training forward, every activation kept in the stash.  bn (batch statistics): z kept beside y, the statistics in the layers' slots
-//                       mixed: the weight operands are cast from the live fp32 weights first, every layer runs on the bf16 GEMMs
-hipError_t forward_train(hpe_ctx* c, Walk wk, const float* images, int B, float* features, hipStream_t st) {
-    const bool bn = walk_bn(wk), mx = walk_mx(wk);
+// The training forward at the precision T, every activation kept in the stash.  bn (batch statistics): z kept beside y, the statistics
+// in the layers' slots
+template <class T>
+hipError_t forward_train(hpe_ctx* c, bool bn, const float* images, int B, float* features, hipStream_t st) {
     const bool reduce = bn && c->et.reduce != nullptr;
-    auto stash = [&](int idx) { return stash_of(c, wk, idx, B); };
-    auto layer = [&](int idx, const float* x, const float* res, int relu) {
-        float* y = stash(idx);
-        if (mx && bn) return layer_forward_bn16(c, idx, h16(x), B, h16(res), relu, mx_zstash_of(c, idx, B), h16(y), bn_slots(c, idx, false), st, reduce);
-        if (mx) return mx_conv_forward(c, idx, h16(x), B, h16(res), relu, h16(y), st);
-        return bn ? layer_forward_bn(c, idx, x, B, res, relu, zstash_of(c, idx, B), y, bn_slots(c, idx, false), st, reduce)
-                  : run_conv_nhwc(c, idx, x, B, res, relu, y, st);
+    auto stash = [&](int idx) { return stash_of<T>(c, idx, B); };
+    auto layer = [&](int idx, const T* x, const T* res, int relu) {
+        T* y = stash(idx);
+        return bn ? layer_forward_bn<T>(c, idx, x, B, res, relu, zstash_of<T>(c, idx, B), y, bn_slots(c, idx, false), st, reduce)
+                  : layer_conv(c, idx, x, B, res, relu, y, st);
     };
-    if (mx) {
-        HIPE(mx_cast_launch(c, 0, MX_CAST_SEGS, st));
-        HIPE(hpe_launch_pad_input_bf16(images, c->et.mx_padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
-        HIPE(layer(0, f16(c->et.mx_padded), nullptr, 1));
-        HIPE(hpe_launch_maxpool_bf16(stash(0), stash(-1), B, 112, 64, st));
-    } else {
-        HIPE(hpe_launch_pad_input(images, c->padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
-        HIPE(layer(0, c->padded, nullptr, 1));
-        HIPE(hpe_launch_maxpool(stash(0), stash(-1), B, 112, 64, st));
-    }
+    HIPE(Prec<T>::cast(c, 0, MX_CAST_SEGS, st));
+    HIPE(pad_images<T>(c, images, B, st));
+    HIPE(layer(0, Prec<T>::padded(c), nullptr, 1));
+    HIPE(enc_maxpool(stash(0), stash(-1), B, 112, 64, st));
     for (const ResBlock& blk : blocks()) {
-        const float* cur = stash(blk.in);
+        const T* cur = stash(blk.in);
         HIPE(layer(blk.i2a, cur, nullptr, 1));
         HIPE(layer(blk.i2b, stash(blk.i2a), nullptr, 1));
-        const float* res = cur;
+        const T* res = cur;
         if (blk.first) {
             HIPE(layer(blk.i1, cur, nullptr, 0));
             res = stash(blk.i1);
         }
         HIPE(layer(blk.i2c, stash(blk.i2b), res, 1));
     }
-    const float* last = stash(blocks().back().i2c);
-    if (mx) return hpe_launch_avgpool_bf16(last, features, B, 49, HPE_FEATURE_DIM, HPE_FEATURE_DIM, st);
-    return hpe_launch_avgpool(last, features, B, 49, HPE_FEATURE_DIM, HPE_FEATURE_DIM, st);
+    return enc_avgpool(stash(blocks().back().i2c), features, B, 49, HPE_FEATURE_DIM, HPE_FEATURE_DIM, st);
 }
 
+template <class T>
 struct GateOut {
-    const float *wg, *dg;  // what the layer's weight gradient and its data gradient read
+    const T *wg, *dg;  // what the layer's weight gradient and its data gradient read
 };
 
 // The cotangent dy of layer idx's output -> that of its convolution.  gated: the layer has a ReLU; keep: dy's buffer must hold dz
 // afterwards (branch2c: it is the shortcut's cotangent too); copy: receives the data-gradient operand.
-//   frozen  dz in place where there is a ReLU (without one dz is dy), copy = dz * s (none for conv1, which has no data gradient); the
-//           weight gradient reads dz
-//   batch   the bias / gamma / beta gradients go into grad_flat, copy = dzraw, which both gradients read; dz is written only if kept
-//   mixed   as frozen on bf16 elements; copy = RNE(dz * s)
-//   mixed batch   as batch on bf16 elements; copy = dzraw16, the bias / gamma / beta gradients stay fp32
-hipError_t layer_gate(hpe_ctx* c, Walk wk, int idx, float* dy, bool gated, bool keep, float* copy, int B, float* grad_flat, hipStream_t st,
-                      GateOut* o) {
+//   frozen  dz in place where there is a ReLU (without one dz is dy), copy = dz * s (none for conv1, which has no data gradient; bf16:
+//           rounded to nearest even); the weight gradient reads dz
+//   batch   the bias / gamma / beta gradients (fp32) go into grad_flat, copy = dzraw, which both gradients read; dz is written only if kept
+template <class T>
+hipError_t layer_gate(hpe_ctx* c, bool bn, int idx, T* dy, bool gated, bool keep, T* copy, int B, float* grad_flat, hipStream_t st, GateOut<T>* o) {
     const ConvSpec& s = specs()[idx];
-    const float* y = gated ? stash_of(c, wk, idx, B) : nullptr;
-    if (wk == WALK_MIXED_BATCH) {
+    const T* y = gated ? stash_of<T>(c, idx, B) : nullptr;
+    if (bn) {
         *o = {copy, copy};
-        return layer_gate_bn16(c, idx, h16(dy), h16(y), mx_zstash_of(c, idx, B), B, bn_slots(c, idx, false), grad_flat + layout().off[idx][0],
-                               keep ? h16(dy) : nullptr, h16(copy), st, c->et.reduce != nullptr);
+        return layer_gate_bn<T>(c, idx, dy, y, zstash_of<T>(c, idx, B), B, bn_slots(c, idx, false), grad_flat + layout().off[idx][0],
+                                keep ? dy : nullptr, copy, st, c->et.reduce != nullptr);
     }
-    if (wk == WALK_MIXED) {
-        float* dzs = idx == 0 ? nullptr : copy;
-        mx_gate(h16(dy), h16(y), dzs ? c->conv[idx].scale : nullptr, gated ? h16(dy) : nullptr, h16(dzs), (long)B * s.hout * s.hout * s.cout, s.cout, st);
-        *o = {dy, dzs};
-        return hipSuccess;
-    }
-    if (wk == WALK_BATCH) {
-        *o = {copy, copy};
-        return layer_gate_bn(c, idx, dy, y, zstash_of(c, idx, B), B, bn_slots(c, idx, false), grad_flat + layout().off[idx][0], keep ? dy : nullptr,
-                             copy, st, c->et.reduce != nullptr);
-    }
-    float* dzs = idx == 0 ? nullptr : copy;
+    T* dzs = idx == 0 ? nullptr : copy;
     gate(dy, y, dzs ? c->conv[idx].scale : nullptr, gated ? dy : nullptr, dzs, (long)B * s.hout * s.hout * s.cout, s.cout, st);
     *o = {dy, dzs};
     return hipSuccess;
 }
 
-hipError_t backward(hpe_ctx* c, Walk wk, const float* images, int B, const float* grad_features, float* grad_flat, hipStream_t st) {
-    EncTrainWork& w = c->et;
-    const bool bn = walk_bn(wk), mx = walk_mx(wk);
-    HIPE(forward_train(c, wk, images, B, w.feat, st));
-    auto stash = [&](int idx) { return stash_of(c, wk, idx, B); };
-    auto lgate = [&](int idx, float* dy, bool gated, bool keep, float* copy, GateOut* o) {
-        return layer_gate(c, wk, idx, dy, gated, keep, copy, B, grad_flat, st, o);
+template <class T>
+hipError_t backward(hpe_ctx* c, bool bn, const float* images, int B, const float* grad_features, float* grad_flat, hipStream_t st) {
+    EncActs<T>& a = c->et.acts<T>();
+    HIPE(forward_train<T>(c, bn, images, B, c->et.feat, st));
+    auto stash = [&](int idx) { return stash_of<T>(c, idx, B); };
+    auto lgate = [&](int idx, T* dy, bool gated, bool keep, T* copy, GateOut<T>* o) {
+        return layer_gate<T>(c, bn, idx, dy, gated, keep, copy, B, grad_flat, st, o);
     };
-    auto wgrad = [&](int idx, const float* x, const float* dz) {
-        float* grad_layer = grad_flat + layout().off[idx][0];
-        return mx ? mx_weight_grad(c, idx, h16(x), h16(dz), B, grad_layer, st, bn) : weight_grad(c, idx, x, dz, B, grad_layer, st, bn);
-    };
-    auto dgrad = [&](int idx, const float* dzs, const float* res, float* out) {
-        return mx ? mx_data_grad(c, idx, h16(dzs), B, h16(res), h16(out), st) : data_grad(c, idx, dzs, B, res, out, st);
-    };
-    GateOut o2c, o2b, o2a, o1, o0;
-    // the cotangent and operand buffers of the walk's precision
-    float *g = mx ? f16(w.mx_g0) : w.g0, *go = mx ? f16(w.mx_g1) : w.g1, *sbig = mx ? f16(w.mx_sbig) : w.sbig;
-    float *t0 = mx ? f16(w.mx_t0) : w.t0, *t1 = mx ? f16(w.mx_t1) : w.t1, *ssmall = mx ? f16(w.mx_ssmall) : w.ssmall;
-    if (mx) {
-        mx_avgpool_bwd(grad_features, h16(g), B, 49, HPE_FEATURE_DIM, st);
-    } else {
-        avgpool_bwd(grad_features, g, B, 49, HPE_FEATURE_DIM, st);
-    }
+    auto wgrad = [&](int idx, const T* x, const T* dz) { return weight_grad(c, idx, x, dz, B, grad_flat + layout().off[idx][0], st, bn); };
+    auto dgrad = [&](int idx, const T* dzs, const T* res, T* out) { return data_grad(c, idx, dzs, B, res, out, st); };
+    GateOut<T> o2c, o2b, o2a, o1, o0;
+    T *g = a.g0, *go = a.g1;
+    avgpool_bwd(grad_features, g, B, 49, HPE_FEATURE_DIM, st);
     for (auto it = blocks().rbegin(); it != blocks().rend(); ++it) {
         const int i2a = it->i2a, i2b = it->i2b, i2c = it->i2c, i1 = it->i1;
         const ConvSpec& sa = specs()[i2a];
-        const float* xin = stash(it->in);  // the block's input: the previous block's branch2c output
+        const T* xin = stash(it->in);  // the block's input: the previous block's branch2c output
         // branch2c: g becomes dz (the cotangent of the shortcut too)
-        HIPE(lgate(i2c, g, true, true, sbig, &o2c));
+        HIPE(lgate(i2c, g, true, true, a.sbig, &o2c));
         HIPE(wgrad(i2c, stash(i2b), o2c.wg));
-        HIPE(dgrad(i2c, o2c.dg, nullptr, t0));
-        HIPE(lgate(i2b, t0, true, false, ssmall, &o2b));
+        HIPE(dgrad(i2c, o2c.dg, nullptr, a.t0));
+        HIPE(lgate(i2b, a.t0, true, false, a.ssmall, &o2b));
         HIPE(wgrad(i2b, stash(i2a), o2b.wg));
-        HIPE(dgrad(i2b, o2b.dg, nullptr, t1));
-        HIPE(lgate(i2a, t1, true, false, ssmall, &o2a));
+        HIPE(dgrad(i2b, o2b.dg, nullptr, a.t1));
+        HIPE(lgate(i2a, a.t1, true, false, a.ssmall, &o2a));
         HIPE(wgrad(i2a, xin, o2a.wg));
         if (!it->first) {
             HIPE(dgrad(i2a, o2a.dg, g, go));
@@ -399,46 +379,47 @@ hipError_t backward(hpe_ctx* c, Walk wk, const float* images, int B, const float
             continue;
         }
         // projection shortcut: no activation of its own, its dz is the block's
-        HIPE(lgate(i1, g, false, false, sbig, &o1));
+        HIPE(lgate(i1, g, false, false, a.sbig, &o1));
         HIPE(wgrad(i1, xin, o1.wg));
         if (sa.stride == 1) {
             HIPE(dgrad(i2a, o2a.dg, nullptr, go));
             HIPE(dgrad(i1, o1.dg, go, g));
         } else {
-            HIPE(dgrad(i2a, o2a.dg, nullptr, t0));
-            HIPE(dgrad(i1, o1.dg, t0, t1));
-            if (mx) {
-                mx_scatter2(h16(t1), h16(go), B, sa.hout, sa.cin, st);
-            } else {
-                scatter2(t1, go, B, sa.hout, sa.cin, st);
-            }
+            HIPE(dgrad(i2a, o2a.dg, nullptr, a.t0));
+            HIPE(dgrad(i1, o1.dg, a.t0, a.t1));
+            scatter2(a.t1, go, B, sa.hout, sa.cin, st);
             std::swap(g, go);
         }
     }
-    if (mx) {
-        mx_maxpool_bwd(h16(stash(0)), h16(g), h16(go), B, 112, 64, st);
-    } else {
-        maxpool_bwd(stash(0), g, go, B, 112, 64, st);
-    }
-    HIPE(lgate(0, go, true, false, sbig, &o0));
-    return wgrad(0, mx ? f16(w.mx_padded) : images, o0.wg);  // conv1's weight gradient reads the images; mixed: the padded bf16 input
+    maxpool_bwd(stash(0), g, go, B, 112, 64, st);
+    HIPE(lgate(0, go, true, false, a.sbig, &o0));
+    return wgrad(0, Prec<T>::wg0_input(c, images), o0.wg);
 }
 
 // dx of layer idx from its data-gradient operand, for the one-layer debug calls: a stride-2 layer's comes on the low-resolution map
-int debug_data_grad(hpe_ctx* c, int idx, const float* dzs, int B, float* dx, hipStream_t st) {
+template <class T>
+int debug_data_grad(hpe_ctx* c, int idx, const T* dzs, int B, T* dx, hipStream_t st) {
     const ConvSpec& s = specs()[idx];
+    T* t0 = c->et.acts<T>().t0;
     if (s.stride == 1) {
         HIP_TRY(data_grad(c, idx, dzs, B, nullptr, dx, st));
     } else {
-        HIP_TRY(data_grad(c, idx, dzs, B, nullptr, c->et.t0, st));
-        scatter2(c->et.t0, dx, B, s.hout, s.cin, st);
+        HIP_TRY(data_grad(c, idx, dzs, B, nullptr, t0, st));
+        scatter2(t0, dx, B, s.hout, s.cin, st);
         HIP_TRY(hipGetLastError());
     }
     return HPE_OK;
 }
 
-// what a call needs: nothing reserved yet, hpe_encoder_train_reserve, or hpe_encoder_train_reserve_batchnorm as well
-enum Reserve { RESERVE_NONE, RESERVE_FROZEN, RESERVE_BN, RESERVE_MIXED, RESERVE_BN_MIXED };
+// what a call needs reserved (nothing yet, or one of the four reserves): the reserve's batch, its entry point, the name of its range
+const struct {
+    int EncTrainWork::*batch;
+    const char *call, *range;
+} reserves[] = {{nullptr, nullptr, "max_batch"},
+                {&EncTrainWork::B, "hpe_encoder_train_reserve", "reserved batch"},
+                {&EncTrainWork::bn_B, "hpe_encoder_train_reserve_batchnorm", "batch of the batch-norm reserve"},
+                {&EncTrainWork::mx_B, "hpe_encoder_train_reserve_mixed", "batch of the mixed-precision reserve"},
+                {&EncTrainWork::mxbn_B, "hpe_encoder_train_reserve_batchnorm_mixed", "batch of the mixed-precision batch-norm reserve"}};
 
 int check_train(hpe_ctx* c, int B, Reserve need = RESERVE_FROZEN) {
     if (!c) return fail(HPE_ERR_INVALID, "null ctx");
@@ -446,19 +427,11 @@ int check_train(hpe_ctx* c, int B, Reserve need = RESERVE_FROZEN) {
     if (!c->finalized) return fail(HPE_ERR_STATE, "hpe_finalize() has not been called");
     if (!c->have_encoder) return fail(HPE_ERR_STATE, "encoder weights were not loaded before hpe_finalize");
     if (c->bf16) return fail(HPE_ERR_STATE, "encoder training needs an fp32 context");
-    if (need != RESERVE_NONE && c->et.B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve() has not been called");
-    if (need == RESERVE_BN && c->et.bn_B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_batchnorm() has not been called");
-    if (need == RESERVE_MIXED && c->et.mx_B == 0) return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_mixed() has not been called");
-    if (need == RESERVE_BN_MIXED && c->et.mxbn_B == 0)
-        return fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_batchnorm_mixed() has not been called");
-    static const char* const range[] = {"max_batch", "reserved batch", "batch of the batch-norm reserve", "batch of the mixed-precision reserve",
-                                        "batch of the mixed-precision batch-norm reserve"};
-    const int top = need == RESERVE_NONE     ? c->cfg.max_batch
-                    : need == RESERVE_FROZEN ? c->et.B
-                    : need == RESERVE_BN     ? c->et.bn_B
-                    : need == RESERVE_MIXED  ? c->et.mx_B
-                                             : c->et.mxbn_B;
-    if (B < 1 || B > top) return fail(HPE_ERR_INVALID, "batch " + std::to_string(B) + " outside [1, " + range[need] + "]");
+    if (need != RESERVE_NONE)  // the frozen reserve, which every other one builds on, then the call's own
+        for (Reserve r : {RESERVE_FROZEN, need})
+            if (c->et.*reserves[r].batch == 0) return fail(HPE_ERR_STATE, std::string(reserves[r].call) + "() has not been called");
+    const int top = need == RESERVE_NONE ? c->cfg.max_batch : c->et.*reserves[need].batch;
+    if (B < 1 || B > top) return fail(HPE_ERR_INVALID, "batch " + std::to_string(B) + " outside [1, " + reserves[need].range + "]");
     return HPE_OK;
 }
 
@@ -484,47 +457,40 @@ int walk_result(hpe_ctx* c, hipError_t e, const char* what) {
     return HPE_OK;
 }
 
-void walk_done(hpe_ctx* c, Walk wk, int B) {
-    if (walk_mx(wk)) {  // the mixed stash has its own batch counter: the fp32 stash is as it was
-        c->et.mx_stash_B = B;
-        if (wk == WALK_MIXED) return;
-        c->et.mx_zstash_B = B;
-    } else {
-        c->et.stash_B = B;
-        if (wk != WALK_BATCH) return;
-    }
+template <class T>
+void walk_done(hpe_ctx* c, bool bn, int B) {
+    Prec<T>::done(c->et, B, bn);
+    if (!bn) return;
     // the statistics in bn_batch are those of the last batch-statistics walk of either precision
-    c->et.bn_stat_mixed = walk_mx(wk);
+    c->et.bn_stat_mixed = Prec<T>::mixed;
     c->et.bn_stat_B = B;
     c->et.bn_stat_G = c->et.reduce ? c->et.reduce_G : B;
 }
 
-Reserve reserve_of(Walk wk) {
-    return wk == WALK_BATCH ? RESERVE_BN : wk == WALK_MIXED ? RESERVE_MIXED : wk == WALK_MIXED_BATCH ? RESERVE_BN_MIXED : RESERVE_FROZEN;
-}
-
 // hpe_encoder_forward_train / _batchnorm / _mixed / _batchnorm_mixed and hpe_encoder_backward / _batchnorm / _mixed / _batchnorm_mixed
-int forward_entry(hpe_ctx* c, Walk wk, const float* images, int B, float* features, void* stream) {
-    int rc = check_train(c, B, reserve_of(wk));
+template <class T>
+int forward_entry(hpe_ctx* c, bool bn, const float* images, int B, float* features, void* stream) {
+    int rc = check_train(c, B, Prec<T>::reserve(bn));
     if (rc) return rc;
     if (!images || !features) return fail(HPE_ERR_INVALID, "null pointer");
     DeviceGuard g(c->cfg.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((rc = check_reduce(c, walk_bn(wk), B, st))) return rc;
-    if ((rc = walk_result(c, forward_train(c, wk, images, B, features, st), "forward"))) return rc;
-    walk_done(c, wk, B);
+    if ((rc = check_reduce(c, bn, B, st))) return rc;
+    if ((rc = walk_result(c, forward_train<T>(c, bn, images, B, features, st), "forward"))) return rc;
+    walk_done<T>(c, bn, B);
     return HPE_OK;
 }
 
-int backward_entry(hpe_ctx* c, Walk wk, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
-    int rc = check_train(c, B, reserve_of(wk));
+template <class T>
+int backward_entry(hpe_ctx* c, bool bn, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
+    int rc = check_train(c, B, Prec<T>::reserve(bn));
     if (rc) return rc;
     if (!images || !grad_features || !grad_flat) return fail(HPE_ERR_INVALID, "null pointer");
     DeviceGuard g(c->cfg.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((rc = check_reduce(c, walk_bn(wk), B, st))) return rc;
-    if ((rc = walk_result(c, backward(c, wk, images, B, grad_features, grad_flat, st), "backward"))) return rc;
-    walk_done(c, wk, B);
+    if ((rc = check_reduce(c, bn, B, st))) return rc;
+    if ((rc = walk_result(c, backward<T>(c, bn, images, B, grad_features, grad_flat, st), "backward"))) return rc;
+    walk_done<T>(c, bn, B);
     return HPE_OK;
 }
 
@@ -550,6 +516,101 @@ int debug_bn_check(hpe_ctx* c, int idx, int B, long long M, bool with_m) {
     return HPE_OK;
 }
 
+// ---- the one-layer and stash debug calls, one body for both precisions.  T = bf16e: the tensors are bf16 and the call is the _mixed one
+
+// What opens a one-layer debug call: mixed, the cast of the layer's weight operand (backward: and of its data-gradient operand).  *in:
+// the layer's input x, or for conv1, where x is the fp32 images, what the precision reads in their place -- the padded input of the
+// convolution, or (backward) what Prec<T> says conv1's weight gradient reads
+template <class T>
+hipError_t debug_open(hpe_ctx* c, int idx, const void* x, int B, bool backward, hipStream_t st, const T** in) {
+    HIPE(Prec<T>::cast(c, idx, 1, st));
+    if (backward && idx > 0) HIPE(Prec<T>::cast(c, HPE_NUM_CONV - 1 + idx, 1, st));
+    *in = static_cast<const T*>(x);
+    if (idx != 0) return hipSuccess;
+    const float* images = static_cast<const float*>(x);
+    if (!backward || Prec<T>::wg0_padded) HIPE(pad_images<T>(c, images, B, st));
+    *in = backward ? Prec<T>::wg0_input(c, images) : Prec<T>::padded(c);
+    return hipSuccess;
+}
+
+// hpe_debug_conv_backward / _mixed
+template <class T>
+int debug_conv_backward(hpe_ctx* c, int idx, const void* x, const T* y, const T* dy, int B, T* dx, float* grad_layer, void* stream) {
+    int rc = check_train(c, B, Prec<T>::reserve(false));
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !dy || !grad_layer) return fail(HPE_ERR_INVALID, "bad argument");
+    if (idx == 0 && dx)
+        return fail(HPE_ERR_INVALID, std::string("hpe_debug_conv_backward") + Prec<T>::suffix + ": conv1 has no data gradient, dx_dev must be NULL");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ConvSpec& s = specs()[idx];
+    EncActs<T>& a = c->et.acts<T>();
+    const T* in;
+    HIP_TRY(debug_open<T>(c, idx, x, B, true, st, &in));
+    const long n = (long)B * s.hout * s.hout * s.cout;
+    gate(dy, y, c->conv[idx].scale, a.g0, dx ? a.sbig : nullptr, n, s.cout, st);
+    HIP_TRY(weight_grad(c, idx, in, a.g0, B, grad_layer, st));
+    return dx ? debug_data_grad<T>(c, idx, a.sbig, B, dx, st) : HPE_OK;
+}
+
+// hpe_debug_conv_batchnorm / _mixed
+template <class T>
+int debug_conv_batchnorm(hpe_ctx* c, int idx, const void* x, int B, const T* residual, int relu, T* y, T* z_out, float* stats_out, void* stream) {
+    int rc = check_train(c, B, Prec<T>::reserve(true));
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !y || !z_out || !stats_out) return fail(HPE_ERR_INVALID, "bad argument");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const T* in;
+    HIP_TRY(debug_open<T>(c, idx, x, B, false, st, &in));
+    const BnSlots s = bn_slots(c, idx, true);
+    HIP_TRY(layer_forward_bn<T>(c, idx, in, B, residual, relu, z_out, y, s, st));
+    const size_t n = (size_t)specs()[idx].cout * sizeof(float);
+    HIP_TRY(hipMemcpyAsync(stats_out, s.mu, n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(stats_out + specs()[idx].cout, s.var, n, hipMemcpyDeviceToDevice, st));
+    return HPE_OK;
+}
+
+// hpe_debug_conv_backward_batchnorm / _mixed
+template <class T>
+int debug_conv_backward_batchnorm(hpe_ctx* c, int idx, const void* x, const T* z, const T* y, const T* dy, int B, T* dx, float* grad_layer,
+                                  void* stream) {
+    int rc = check_train(c, B, Prec<T>::reserve(true));
+    if (rc) return rc;
+    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !z || !dy || !grad_layer) return fail(HPE_ERR_INVALID, "bad argument");
+    if (idx == 0 && dx)
+        return fail(HPE_ERR_INVALID,
+                    std::string("hpe_debug_conv_backward_batchnorm") + Prec<T>::suffix + ": conv1 has no data gradient, dx_dev must be NULL");
+    DeviceGuard g(c->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ConvSpec& s = specs()[idx];
+    EncTrainWork& w = c->et;
+    T* sbig = w.acts<T>().sbig;
+    const T* in;
+    HIP_TRY(debug_open<T>(c, idx, x, B, true, st, &in));
+    const BnSlots sl = bn_slots(c, idx, true);
+    HIP_TRY(bn_launch_stats(z, B * s.hout * s.hout, s.cout, c->cfg.bn_eps, w.bn_part, sl.mu, sl.var, sl.r, st));
+    HIP_TRY(layer_gate_bn<T>(c, idx, dy, y, z, B, sl, grad_layer, nullptr, sbig, st));
+    HIP_TRY(weight_grad(c, idx, in, sbig, B, grad_layer, st, true));
+    return dx ? debug_data_grad<T>(c, idx, sbig, B, dx, st) : HPE_OK;
+}
+
+// hpe_debug_encoder_stash / _mixed (idx -1: the pooled map) and hpe_debug_encoder_stash_raw / _raw_mixed
+template <class T>
+int debug_stash(hpe_ctx* c, bool raw, int idx, T* out, void* stream) {
+    int rc = check_train(c, 1, Prec<T>::reserve(raw));
+    if (rc) return rc;
+    if (idx < (raw ? 0 : -1) || idx >= HPE_NUM_CONV || !out) return fail(HPE_ERR_INVALID, "bad argument");
+    const char* why;
+    const int B = raw ? Prec<T>::zstash_batch(c->et, &why) : Prec<T>::stash_batch(c->et, &why);
+    if (B == 0) return fail(HPE_ERR_STATE, std::string("hpe_debug_encoder_stash") + (raw ? "_raw" : "") + Prec<T>::suffix + ": " + why);
+    DeviceGuard g(c->cfg.device);
+    const size_t n = idx < 0 ? (size_t)POOL_FLOATS : (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
+    const T* src = raw ? zstash_of<T>(c, idx, B) : stash_of<T>(c, idx, B);
+    HIP_TRY(hipMemcpyAsync(out, src, (size_t)B * n * sizeof(T), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return HPE_OK;
+}
+
 }  // namespace
 
 #pragma GCC visibility push(default)
@@ -567,7 +628,7 @@ long long hpe_encoder_train_ws_floats(int B) { return B < 1 ? 0 : (long long)ws_
 int hpe_encoder_wg_slices(int idx, int B) {
     if (idx < 0 || idx >= HPE_NUM_CONV || B < 1) return -1;
     int P, sl;
-    wg_slicing(idx, B, &P, &sl);
+    wg_slicing(idx, B, 8, &P, &sl);
     return sl;
 }
 
@@ -579,7 +640,7 @@ int hpe_encoder_train_reserve(hpe_ctx* c, int B) {
     DeviceGuard g(c->cfg.device);
     const EncLayout& l = layout();
     TrainAlloc alloc{c};
-    train_buffers(w, B, alloc);
+    train_buffers(w, RESERVE_FROZEN, B, alloc);
     if (alloc.rc) return alloc.rc;
     w.partial_floats = wg_partial_floats(B);
     // the flat parameters: hpe_finalize released the host kernels, so they come back from the packed device weights Wt[n][k] (fp32: exact)
@@ -617,11 +678,11 @@ int hpe_encoder_train_reserve(hpe_ctx* c, int B) {
 }
 
 int hpe_encoder_forward_train(hpe_ctx* c, const float* images, int B, float* features, void* stream) {
-    return forward_entry(c, WALK_FROZEN, images, B, features, stream);
+    return forward_entry<float>(c, false, images, B, features, stream);
 }
 
 int hpe_encoder_backward(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
-    return backward_entry(c, WALK_FROZEN, images, B, grad_features, grad_flat, stream);
+    return backward_entry<float>(c, false, images, B, grad_features, grad_flat, stream);
 }
 
 int hpe_encoder_get_params(hpe_ctx* c, float* flat, void* stream) {
@@ -676,18 +737,7 @@ int hpe_encoder_set_params_dev(hpe_ctx* c, const float* flat, void* stream) {
 
 int hpe_debug_conv_backward(hpe_ctx* c, int idx, const float* x, const float* y, const float* dy, int B, float* dx, float* grad_layer,
                             void* stream) {
-    int rc = check_train(c, B);
-    if (rc) return rc;
-    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !dy || !grad_layer) return fail(HPE_ERR_INVALID, "bad argument");
-    if (idx == 0 && dx) return fail(HPE_ERR_INVALID, "hpe_debug_conv_backward: conv1 has no data gradient, dx_dev must be NULL");
-    DeviceGuard g(c->cfg.device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const ConvSpec& s = specs()[idx];
-    EncTrainWork& w = c->et;
-    const long n = (long)B * s.hout * s.hout * s.cout;
-    gate(dy, y, c->conv[idx].scale, w.g0, dx ? w.sbig : nullptr, n, s.cout, st);
-    HIP_TRY(weight_grad(c, idx, x, w.g0, B, grad_layer, st));
-    return dx ? debug_data_grad(c, idx, w.sbig, B, dx, st) : HPE_OK;
+    return debug_conv_backward<float>(c, idx, x, y, dy, B, dx, grad_layer, stream);
 }
 
 int hpe_debug_maxpool_backward(const float* x, const float* dy, int B, int H, int C, float* dx, void* stream) {
@@ -707,15 +757,7 @@ int hpe_debug_avgpool_backward(const float* dy, int B, int HW, int C, float* dx,
 int hpe_debug_encoder_stash_batch(hpe_ctx* c) { return (c && c->finalized && !c->dead) ? c->et.stash_B : 0; }
 
 int hpe_debug_encoder_stash(hpe_ctx* c, int idx, float* out, void* stream) {
-    int rc = check_train(c, 1);
-    if (rc) return rc;
-    if (idx < -1 || idx >= HPE_NUM_CONV || !out) return fail(HPE_ERR_INVALID, "bad argument");
-    const int B = c->et.stash_B;
-    if (B == 0) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash: no training forward has run");
-    DeviceGuard g(c->cfg.device);
-    const size_t n = idx < 0 ? (size_t)POOL_FLOATS : (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
-    HIP_TRY(hipMemcpyAsync(out, stash_of(c, idx, B), (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-    return HPE_OK;
+    return debug_stash<float>(c, false, idx, out, stream);
 }
 
 // ---- BatchNorm with batch statistics
@@ -742,7 +784,7 @@ int hpe_encoder_train_reserve_batchnorm(hpe_ctx* c, int B) {
     DeviceGuard g(c->cfg.device);
     const EncLayout& l = layout();
     TrainAlloc alloc{c};
-    train_buffers_bn(w, B, alloc);
+    train_buffers(w, RESERVE_BN, B, alloc);
     if (alloc.rc) return alloc.rc;
     // the statistics as loaded (nothing can have moved them: hpe_encoder_set_stats_dev needs this reserve) and every channel's map size
     std::vector<float> stats(2 * (size_t)l.channels);
@@ -762,11 +804,11 @@ int hpe_encoder_train_reserve_batchnorm(hpe_ctx* c, int B) {
 }
 
 int hpe_encoder_forward_batchnorm(hpe_ctx* c, const float* images, int B, float* features, void* stream) {
-    return forward_entry(c, WALK_BATCH, images, B, features, stream);
+    return forward_entry<float>(c, true, images, B, features, stream);
 }
 
 int hpe_encoder_backward_batchnorm(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
-    return backward_entry(c, WALK_BATCH, images, B, grad_features, grad_flat, stream);
+    return backward_entry<float>(c, true, images, B, grad_features, grad_flat, stream);
 }
 
 int hpe_encoder_get_stats(hpe_ctx* c, float* stats, void* stream) {
@@ -804,53 +846,16 @@ int hpe_encoder_set_stats_dev(hpe_ctx* c, const float* stats, void* stream) {
 
 int hpe_debug_conv_batchnorm(hpe_ctx* c, int idx, const float* x, int B, const float* residual, int relu, float* y, float* z_out, float* stats_out,
                              void* stream) {
-    int rc = check_train(c, B, RESERVE_BN);
-    if (rc) return rc;
-    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !y || !z_out || !stats_out) return fail(HPE_ERR_INVALID, "bad argument");
-    DeviceGuard g(c->cfg.device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const float* in = x;
-    if (idx == 0) {
-        HIP_TRY(hpe_launch_pad_input(x, c->padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
-        in = c->padded;
-    }
-    const BnSlots s = bn_slots(c, idx, true);
-    HIP_TRY(layer_forward_bn(c, idx, in, B, residual, relu, z_out, y, s, st));
-    const size_t n = (size_t)specs()[idx].cout * sizeof(float);
-    HIP_TRY(hipMemcpyAsync(stats_out, s.mu, n, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(stats_out + specs()[idx].cout, s.var, n, hipMemcpyDeviceToDevice, st));
-    return HPE_OK;
+    return debug_conv_batchnorm<float>(c, idx, x, B, residual, relu, y, z_out, stats_out, stream);
 }
 
 int hpe_debug_conv_backward_batchnorm(hpe_ctx* c, int idx, const float* x, const float* z, const float* y, const float* dy, int B, float* dx,
                                       float* grad_layer, void* stream) {
-    int rc = check_train(c, B, RESERVE_BN);
-    if (rc) return rc;
-    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !z || !dy || !grad_layer) return fail(HPE_ERR_INVALID, "bad argument");
-    if (idx == 0 && dx) return fail(HPE_ERR_INVALID, "hpe_debug_conv_backward_batchnorm: conv1 has no data gradient, dx_dev must be NULL");
-    DeviceGuard g(c->cfg.device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const ConvSpec& s = specs()[idx];
-    EncTrainWork& w = c->et;
-    const BnSlots sl = bn_slots(c, idx, true);
-    HIP_TRY(bn_launch_stats(z, B * s.hout * s.hout, s.cout, c->cfg.bn_eps, w.bn_part, sl.mu, sl.var, sl.r, st));
-    HIP_TRY(layer_gate_bn(c, idx, dy, y, z, B, sl, grad_layer, nullptr, w.sbig, st));
-    HIP_TRY(weight_grad(c, idx, x, w.sbig, B, grad_layer, st, true));
-    return dx ? debug_data_grad(c, idx, w.sbig, B, dx, st) : HPE_OK;
+    return debug_conv_backward_batchnorm<float>(c, idx, x, z, y, dy, B, dx, grad_layer, stream);
 }
 
 int hpe_debug_encoder_stash_raw(hpe_ctx* c, int idx, float* out, void* stream) {
-    int rc = check_train(c, 1, RESERVE_BN);
-    if (rc) return rc;
-    if (idx < 0 || idx >= HPE_NUM_CONV || !out) return fail(HPE_ERR_INVALID, "bad argument");
-    const int B = c->et.bn_stat_B;
-    if (B == 0) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw: no batch-statistics forward has run");
-    if (c->et.bn_stat_mixed) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw: the last batch-statistics forward was a mixed-precision one");
-    if (c->et.stash_B != B) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw: a frozen-statistics forward of another batch has refilled the stash since");
-    DeviceGuard g(c->cfg.device);
-    const size_t n = (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
-    HIP_TRY(hipMemcpyAsync(out, zstash_of(c, idx, B), (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-    return HPE_OK;
+    return debug_stash<float>(c, true, idx, out, stream);
 }
 
 int hpe_debug_encoder_batch_stats(hpe_ctx* c, float* out, void* stream) {
@@ -933,9 +938,9 @@ int hpe_debug_bn_backward_finish(hpe_ctx* c, int idx, const float* x, const floa
     HIP_TRY(bn_launch_stats_from_sums(sums, (double)M, N, c->cfg.bn_eps, sl.mu, sl.var, sl.r, st));
     HIP_TRY(bn_launch_bwd_sums(dy, y, z, sl.mu, sl.r, rows, N, w.bn_part, reduce_sums(c), db, dgamma, dbeta, st));
     HIP_TRY(bn_launch_bwd_from_sums(bwd_sums, N, red, st));
-    HIP_TRY(bn_launch_bwd_apply(dy, y, z, sl.mu, sl.r, w.flat + layout().off[idx][2], red + N, red, rows, N, nullptr, w.sbig, st, (double)M));
-    HIP_TRY(weight_grad(c, idx, x, w.sbig, B, grad_layer, st, true));
-    return dx ? debug_data_grad(c, idx, w.sbig, B, dx, st) : HPE_OK;
+    HIP_TRY(bn_launch_bwd_apply(dy, y, z, sl.mu, sl.r, w.flat + layout().off[idx][2], red + N, red, rows, N, nullptr, w.f32.sbig, st, (double)M));
+    HIP_TRY(weight_grad(c, idx, x, w.f32.sbig, B, grad_layer, st, true));
+    return dx ? debug_data_grad<float>(c, idx, w.f32.sbig, B, dx, st) : HPE_OK;
 }
 
 // ---- mixed precision: bf16 walks on an fp32 context.  The bf16 weight operands are cast from the context's live fp32 weights
@@ -950,7 +955,7 @@ int hpe_encoder_train_reserve_mixed(hpe_ctx* c, int B) {
     if (w.mx_B != 0) return B <= w.mx_B ? HPE_OK : fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_mixed: already reserved for a smaller batch");
     DeviceGuard g(c->cfg.device);
     TrainAlloc alloc{c};
-    train_buffers_mixed(w, B, alloc);
+    train_buffers(w, RESERVE_MIXED, B, alloc);
     if (alloc.rc) return alloc.rc;
     std::vector<MxCastSeg> table(MX_CAST_SEGS);
     for (int i = 0; i < HPE_NUM_CONV; ++i) {
@@ -966,54 +971,28 @@ int hpe_encoder_train_reserve_mixed(hpe_ctx* c, int B) {
 }
 
 int hpe_encoder_forward_train_mixed(hpe_ctx* c, const float* images, int B, float* features, void* stream) {
-    return forward_entry(c, WALK_MIXED, images, B, features, stream);
+    return forward_entry<bf16e>(c, false, images, B, features, stream);
 }
 
 int hpe_encoder_backward_mixed(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
-    return backward_entry(c, WALK_MIXED, images, B, grad_features, grad_flat, stream);
+    return backward_entry<bf16e>(c, false, images, B, grad_features, grad_flat, stream);
 }
 
 int hpe_debug_conv_backward_mixed(hpe_ctx* c, int idx, const void* x, const void* y, const void* dy, int B, void* dx, float* grad_layer,
                                   void* stream) {
-    int rc = check_train(c, B, RESERVE_MIXED);
-    if (rc) return rc;
-    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !dy || !grad_layer) return fail(HPE_ERR_INVALID, "bad argument");
-    if (idx == 0 && dx) return fail(HPE_ERR_INVALID, "hpe_debug_conv_backward_mixed: conv1 has no data gradient, dx_dev must be NULL");
-    DeviceGuard g(c->cfg.device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const ConvSpec& s = specs()[idx];
-    EncTrainWork& w = c->et;
-    HIP_TRY(mx_cast_launch(c, idx, 1, st));
-    if (idx > 0) HIP_TRY(mx_cast_launch(c, HPE_NUM_CONV - 1 + idx, 1, st));
-    cmx16 in = static_cast<cmx16>(x);
-    if (idx == 0) {  // x is the fp32 image tensor
-        HIP_TRY(hpe_launch_pad_input_bf16(static_cast<const float*>(x), w.mx_padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
-        in = w.mx_padded;
-    }
-    const long n = (long)B * s.hout * s.hout * s.cout;
-    mx_gate(static_cast<cmx16>(dy), static_cast<cmx16>(y), c->conv[idx].scale, w.mx_g0, dx ? w.mx_sbig : nullptr, n, s.cout, st);
-    HIP_TRY(mx_weight_grad(c, idx, in, w.mx_g0, B, grad_layer, st));
-    if (!dx) return HPE_OK;
-    if (s.stride == 1) {
-        HIP_TRY(mx_data_grad(c, idx, w.mx_sbig, B, nullptr, static_cast<mx16>(dx), st));
-    } else {  // a stride-2 layer's data gradient comes on the low-resolution map
-        HIP_TRY(mx_data_grad(c, idx, w.mx_sbig, B, nullptr, w.mx_t0, st));
-        mx_scatter2(w.mx_t0, static_cast<mx16>(dx), B, s.hout, s.cin, st);
-        HIP_TRY(hipGetLastError());
-    }
-    return HPE_OK;
+    return debug_conv_backward<bf16e>(c, idx, x, static_cast<cmx16>(y), static_cast<cmx16>(dy), B, static_cast<mx16>(dx), grad_layer, stream);
 }
 
 int hpe_debug_maxpool_backward_mixed(const void* x, const void* dy, int B, int H, int C, void* dx, void* stream) {
     if (!x || !dy || !dx || B < 1 || H < 2 || (H & 1) || C < 8 || (C & 7)) return fail(HPE_ERR_INVALID, "bad argument");
-    mx_maxpool_bwd(static_cast<cmx16>(x), static_cast<cmx16>(dy), static_cast<mx16>(dx), B, H, C, static_cast<hipStream_t>(stream));
+    maxpool_bwd(static_cast<cmx16>(x), static_cast<cmx16>(dy), static_cast<mx16>(dx), B, H, C, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return HPE_OK;
 }
 
 int hpe_debug_avgpool_backward_mixed(const float* dy, int B, int HW, int C, void* dx, void* stream) {
     if (!dy || !dx || B < 1 || HW < 1 || C < 8 || (C & 7)) return fail(HPE_ERR_INVALID, "bad argument");
-    mx_avgpool_bwd(dy, static_cast<mx16>(dx), B, HW, C, static_cast<hipStream_t>(stream));
+    avgpool_bwd(dy, static_cast<mx16>(dx), B, HW, C, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return HPE_OK;
 }
@@ -1021,16 +1000,7 @@ int hpe_debug_avgpool_backward_mixed(const float* dy, int B, int HW, int C, void
 int hpe_debug_encoder_stash_batch_mixed(hpe_ctx* c) { return (c && c->finalized && !c->dead) ? c->et.mx_stash_B : 0; }
 
 int hpe_debug_encoder_stash_mixed(hpe_ctx* c, int idx, void* out, void* stream) {
-    int rc = check_train(c, 1, RESERVE_MIXED);
-    if (rc) return rc;
-    if (idx < -1 || idx >= HPE_NUM_CONV || !out) return fail(HPE_ERR_INVALID, "bad argument");
-    const int B = c->et.mx_stash_B;
-    if (B == 0) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_mixed: no mixed-precision forward has run");
-    DeviceGuard g(c->cfg.device);
-    const size_t n = idx < 0 ? (size_t)POOL_FLOATS : (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
-    HIP_TRY(hipMemcpyAsync(out, stash_of(c, WALK_MIXED, idx, B), (size_t)B * n * sizeof(unsigned short), hipMemcpyDeviceToDevice,
-                           static_cast<hipStream_t>(stream)));
-    return HPE_OK;
+    return debug_stash<bf16e>(c, false, idx, static_cast<mx16>(out), stream);
 }
 
 // ---- mixed precision with batch statistics (encoder_bn_bf16.hip holds the kernels): both reserves and a bf16 raw-output stash
@@ -1046,88 +1016,33 @@ int hpe_encoder_train_reserve_batchnorm_mixed(hpe_ctx* c, int B) {
         return B <= w.mxbn_B ? HPE_OK : fail(HPE_ERR_STATE, "hpe_encoder_train_reserve_batchnorm_mixed: already reserved for a smaller batch");
     DeviceGuard g(c->cfg.device);
     TrainAlloc alloc{c};
-    train_buffers_bn_mixed(w, B, alloc);
+    train_buffers(w, RESERVE_BN_MIXED, B, alloc);
     if (alloc.rc) return alloc.rc;
     w.mxbn_B = B;
     return HPE_OK;
 }
 
 int hpe_encoder_forward_batchnorm_mixed(hpe_ctx* c, const float* images, int B, float* features, void* stream) {
-    return forward_entry(c, WALK_MIXED_BATCH, images, B, features, stream);
+    return forward_entry<bf16e>(c, true, images, B, features, stream);
 }
 
 int hpe_encoder_backward_batchnorm_mixed(hpe_ctx* c, const float* images, int B, const float* grad_features, float* grad_flat, void* stream) {
-    return backward_entry(c, WALK_MIXED_BATCH, images, B, grad_features, grad_flat, stream);
+    return backward_entry<bf16e>(c, true, images, B, grad_features, grad_flat, stream);
 }
 
 int hpe_debug_conv_batchnorm_mixed(hpe_ctx* c, int idx, const void* x, int B, const void* residual, int relu, void* y, void* z_out, float* stats_out,
                                    void* stream) {
-    int rc = check_train(c, B, RESERVE_BN_MIXED);
-    if (rc) return rc;
-    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !y || !z_out || !stats_out) return fail(HPE_ERR_INVALID, "bad argument");
-    DeviceGuard g(c->cfg.device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    EncTrainWork& w = c->et;
-    HIP_TRY(mx_cast_launch(c, idx, 1, st));
-    cmx16 in = static_cast<cmx16>(x);
-    if (idx == 0) {  // x is the fp32 image tensor
-        HIP_TRY(hpe_launch_pad_input_bf16(static_cast<const float*>(x), w.mx_padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
-        in = w.mx_padded;
-    }
-    const BnSlots s = bn_slots(c, idx, true);
-    HIP_TRY(layer_forward_bn16(c, idx, in, B, static_cast<cmx16>(residual), relu, static_cast<mx16>(z_out), static_cast<mx16>(y), s, st));
-    const size_t n = (size_t)specs()[idx].cout * sizeof(float);
-    HIP_TRY(hipMemcpyAsync(stats_out, s.mu, n, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(stats_out + specs()[idx].cout, s.var, n, hipMemcpyDeviceToDevice, st));
-    return HPE_OK;
+    return debug_conv_batchnorm<bf16e>(c, idx, x, B, static_cast<cmx16>(residual), relu, static_cast<mx16>(y), static_cast<mx16>(z_out), stats_out, stream);
 }
 
 int hpe_debug_conv_backward_batchnorm_mixed(hpe_ctx* c, int idx, const void* x, const void* z, const void* y, const void* dy, int B, void* dx,
                                             float* grad_layer, void* stream) {
-    int rc = check_train(c, B, RESERVE_BN_MIXED);
-    if (rc) return rc;
-    if (idx < 0 || idx >= HPE_NUM_CONV || !x || !z || !dy || !grad_layer) return fail(HPE_ERR_INVALID, "bad argument");
-    if (idx == 0 && dx) return fail(HPE_ERR_INVALID, "hpe_debug_conv_backward_batchnorm_mixed: conv1 has no data gradient, dx_dev must be NULL");
-    DeviceGuard g(c->cfg.device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const ConvSpec& s = specs()[idx];
-    EncTrainWork& w = c->et;
-    HIP_TRY(mx_cast_launch(c, idx, 1, st));
-    if (idx > 0) HIP_TRY(mx_cast_launch(c, HPE_NUM_CONV - 1 + idx, 1, st));
-    cmx16 in = static_cast<cmx16>(x);
-    if (idx == 0) {  // x is the fp32 image tensor
-        HIP_TRY(hpe_launch_pad_input_bf16(static_cast<const float*>(x), w.mx_padded, B, HPE_IMG_SIZE, HPE_IMG_SIZE, STEM_HP, STEM_WP, st));
-        in = w.mx_padded;
-    }
-    const BnSlots sl = bn_slots(c, idx, true);
-    cmx16 z16 = static_cast<cmx16>(z);
-    HIP_TRY(bn16_launch_stats(z16, B * s.hout * s.hout, s.cout, c->cfg.bn_eps, w.bn_part, sl.mu, sl.var, sl.r, st));
-    HIP_TRY(layer_gate_bn16(c, idx, static_cast<cmx16>(dy), static_cast<cmx16>(y), z16, B, sl, grad_layer, nullptr, w.mx_sbig, st));
-    HIP_TRY(mx_weight_grad(c, idx, in, w.mx_sbig, B, grad_layer, st, true));
-    if (!dx) return HPE_OK;
-    if (s.stride == 1) {
-        HIP_TRY(mx_data_grad(c, idx, w.mx_sbig, B, nullptr, static_cast<mx16>(dx), st));
-    } else {  // a stride-2 layer's data gradient comes on the low-resolution map
-        HIP_TRY(mx_data_grad(c, idx, w.mx_sbig, B, nullptr, w.mx_t0, st));
-        mx_scatter2(w.mx_t0, static_cast<mx16>(dx), B, s.hout, s.cin, st);
-        HIP_TRY(hipGetLastError());
-    }
-    return HPE_OK;
+    return debug_conv_backward_batchnorm<bf16e>(c, idx, x, static_cast<cmx16>(z), static_cast<cmx16>(y), static_cast<cmx16>(dy), B, static_cast<mx16>(dx), grad_layer,
+                                                stream);
 }
 
 int hpe_debug_encoder_stash_raw_mixed(hpe_ctx* c, int idx, void* out, void* stream) {
-    int rc = check_train(c, 1, RESERVE_BN_MIXED);
-    if (rc) return rc;
-    if (idx < 0 || idx >= HPE_NUM_CONV || !out) return fail(HPE_ERR_INVALID, "bad argument");
-    const int B = c->et.mx_zstash_B;
-    if (B == 0) return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw_mixed: no mixed-precision batch-statistics forward has run");
-    if (c->et.mx_stash_B != B)
-        return fail(HPE_ERR_STATE, "hpe_debug_encoder_stash_raw_mixed: a frozen-statistics mixed forward of another batch has refilled the stash since");
-    DeviceGuard g(c->cfg.device);
-    const size_t n = (size_t)specs()[idx].hout * specs()[idx].hout * specs()[idx].cout;
-    HIP_TRY(hipMemcpyAsync(out, mx_zstash_of(c, idx, B), (size_t)B * n * sizeof(unsigned short), hipMemcpyDeviceToDevice,
-                           static_cast<hipStream_t>(stream)));
-    return HPE_OK;
+    return debug_stash<bf16e>(c, true, idx, static_cast<mx16>(out), stream);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hpe.h"
@@ -185,6 +186,18 @@ struct RegTrainWork {
 // flat and dxw follow the live parameters: hpe_encoder_set_params uploads them from the host, hpe_encoder_set_params_dev rewrites them on
 // the device with every packing of ConvLayer (encoder_repack.hip); mean / istd / sd are written by the reserve and rewritten by
 // hpe_encoder_set_stats_dev; the repack table is written once, by the reserve
+typedef unsigned short bf16e;  // a bf16 element as the host carries it: a pointer type of its own, so no fp32 launcher takes a bf16 buffer
+typedef bf16e* mx16;
+typedef const bf16e* cmx16;
+// The activation and cotangent buffers of the training walks, once per element type (float: the fp32 walks, bf16e: the mixed ones)
+template <class T>
+struct EncActs {
+    T *stash = nullptr;   // every layer's post-activation output, then the max-pooled map; layer-major, B images each
+    T *zstash = nullptr;  // batch statistics only: every layer's raw output conv(x, W) + b, laid out as the stash (without the pooled map)
+    T *g0 = nullptr, *g1 = nullptr;  // [B][802816] block cotangents (ping-pong)
+    T *sbig = nullptr;    // [B][802816] dz * s of the wide layers (branch2c, branch1)
+    T *t0 = nullptr, *t1 = nullptr, *ssmall = nullptr;  // [B][200704] bottleneck cotangents / low-resolution data gradients / dz * s
+};
 struct EncTrainWork {
     int B = 0;        // reserved batch (0: not reserved)
     int stash_B = 0;  // batch of the training forward that last filled the stash
@@ -193,10 +206,16 @@ struct EncTrainWork {
     double *sd = nullptr;    // sqrt((double)moving_variance + (double)eps) of the same channels: what bn_fold divides by (encoder_repack.hip)
     void *repack = nullptr;  // the device-side layer table of hpe_encoder_set_params_dev (encoder_repack.hip), built once by the reserve
     unsigned repack_grid[8] = {};  // workgroups of each of its launches (0: the context holds nothing of that form)
-    float *stash = nullptr;  // every layer's post-activation output, then the max-pooled map; layer-major, B images each
-    float *g0 = nullptr, *g1 = nullptr;  // [B][802816] block cotangents (ping-pong)
-    float *sbig = nullptr;   // [B][802816] dz * s of the wide layers (branch2c, branch1)
-    float *t0 = nullptr, *t1 = nullptr, *ssmall = nullptr;  // [B][200704] bottleneck cotangents / low-resolution data gradients / dz * s
+    EncActs<float> f32;  // hpe_encoder_train_reserve (zstash: hpe_encoder_train_reserve_batchnorm)
+    EncActs<bf16e> b16;  // hpe_encoder_train_reserve_mixed (zstash: hpe_encoder_train_reserve_batchnorm_mixed)
+    template <class T>
+    EncActs<T>& acts() {
+        if constexpr (std::is_same<T, float>::value) {
+            return f32;
+        } else {
+            return b16;
+        }
+    }
     float *partial = nullptr;  // [slices][K][N] of the weight gradient in flight
     size_t partial_floats = 0;
     float *dsh = nullptr;    // [128][2048] column sums of dz per slice
@@ -206,8 +225,7 @@ struct EncTrainWork {
     float *dxw[HPE_NUM_CONV] = {};  // data-gradient operands Wt[cin][k], beside the forward's packings
     // BatchNorm with batch statistics (encoder_bn.hip), allocated by hpe_encoder_train_reserve_batchnorm only
     int bn_B = 0;       // its reserved batch (0: not reserved)
-    int bn_stat_B = 0;  // batch of the batch-statistics forward that last filled zstash / bn_batch (0: none has run)
-    float *zstash = nullptr;    // every layer's raw output conv(x, W) + b, laid out as the stash (without the pooled map)
+    int bn_stat_B = 0;  // batch of the batch-statistics forward that last filled a zstash and bn_batch (0: none has run)
     float *bn_batch = nullptr;  // [mu | var | r] of that forward, `channels` floats each, then 3 x 2048 floats for the one-layer debug calls
     float *bn_stats = nullptr;  // the installed moving statistics [mean of every channel | variance of every channel]
     double *bn_part = nullptr;  // [slices][2][N] partial column sums of the reduction in flight (2 * BN_PART_COLS doubles)
@@ -220,26 +238,23 @@ struct EncTrainWork {
     int reduce_G = 0;
     int reduce_failed = -1;  // the layer at which the hook reported a failure during the walk in flight (-1: none)
     int bn_stat_G = 0;       // the batch the statistics in bn_batch were taken over: bn_stat_B, or reduce_G where the hook ran
-    // Mixed precision (encoder_grad_bf16.hip), allocated by hpe_encoder_train_reserve_mixed only: bf16 elements behind every pointer.
+    // Mixed precision (encoder_grad_bf16.hip), allocated by hpe_encoder_train_reserve_mixed only, beside b16.
     // partial / dsh / wgp / flat / mean / istd / feat / zeros above are shared with the fp32 walks
     int mx_B = 0;        // its reserved batch (0: not reserved)
-    int mx_stash_B = 0;  // batch of the mixed forward that last filled mx_stash
-    unsigned short *mx_stash = nullptr;   // laid out as the stash
-    unsigned short *mx_g0 = nullptr, *mx_g1 = nullptr, *mx_sbig = nullptr, *mx_t0 = nullptr, *mx_t1 = nullptr, *mx_ssmall = nullptr;
-    unsigned short *mx_padded = nullptr;  // [B][STEM_HP][STEM_WP][4] the padded input, the 4th channel zero
-    unsigned short *mx_w[HPE_NUM_CONV] = {};    // RNE of ConvLayer::w, Wt[n_pad][conv_k_pad(idx, true)]; the k padding is zero from the reserve on
-    unsigned short *mx_dxw[HPE_NUM_CONV] = {};  // RNE of dxw
+    int mx_stash_B = 0;  // batch of the mixed forward that last filled b16.stash
+    bf16e *mx_padded = nullptr;  // [B][STEM_HP][STEM_WP][4] the padded input, the 4th channel zero
+    bf16e *mx_w[HPE_NUM_CONV] = {};    // RNE of ConvLayer::w, Wt[n_pad][conv_k_pad(idx, true)]; the k padding is zero from the reserve on
+    bf16e *mx_dxw[HPE_NUM_CONV] = {};  // RNE of dxw
     void *mx_cast = nullptr;  // the device table of the cast launch that opens every mixed call: MX_CAST_SEGS segments
     // ... with batch statistics (encoder_bn_bf16.hip), allocated by hpe_encoder_train_reserve_batchnorm_mixed only
     int mxbn_B = 0;         // its reserved batch (0: not reserved)
-    int mx_zstash_B = 0;    // batch of the mixed batch-statistics forward that last filled mx_zstash
-    bool bn_stat_mixed = false;  // the forward that last filled bn_batch was a mixed one: zstash does not hold its raw outputs
-    unsigned short *mx_zstash = nullptr;  // every layer's raw output RNE(conv(x16, W16) + b), laid out as zstash
+    int mx_zstash_B = 0;    // batch of the mixed batch-statistics forward that last filled b16.zstash: RNE(conv(x16, W16) + b)
+    bool bn_stat_mixed = false;  // the forward that last filled bn_batch was a mixed one: f32.zstash does not hold its raw outputs
 };
 constexpr int MX_CAST_SEGS = 2 * HPE_NUM_CONV - 1;  // segment idx: mx_w[idx]; segment HPE_NUM_CONV - 1 + idx (idx >= 1): mx_dxw[idx]
 struct MxCastSeg {
     const float* src;     // rows of src_pitch floats
-    unsigned short* dst;  // rows of dst_pitch >= src_pitch bf16; columns past src_pitch are not written
+    bf16e* dst;           // rows of dst_pitch >= src_pitch bf16; columns past src_pitch are not written
     int src_pitch, dst_pitch;
     long quads;           // rows * src_pitch / 4
 };
@@ -404,24 +419,45 @@ hipError_t encoder_repack_launch(hpe_ctx* c, const float* flat_dev, hipStream_t 
 // the two of them that fold the statistics (scale / shift, the dual-source weights), from the ctx's own flat copy: hpe_encoder_set_stats_dev
 hipError_t encoder_repack_stats_launch(hpe_ctx* c, hipStream_t st);
 
-// encoder_bn.hip: BatchNorm with batch statistics around a layer's raw output z [M][N] (N a multiple of 64, at most 2048).  part: 2 *
-// BN_PART_COLS doubles.  mu / var / r / gamma / beta are 16-byte aligned; dgamma / dbeta / db need not be
-int bn_slices(int M, int N);  // pixel slices of the reductions (-1: a shape they do not take)
+// encoder_bn.hip / encoder_bn_bf16.hip: BatchNorm with batch statistics around a layer's raw output z [M][N] (N a multiple of 64, at most
+// 2048), each launcher overloaded on the element type of the tensors z / y / res / dy / dz / dzraw.  The statistics, gamma, beta and the
+// gradients are fp32 in both; the bf16 first stages write partials in the fp32 layout, so one set of finish launches runs behind both.
+// part: 2 * BN_PART_COLS doubles.  mu / var / r / gamma / beta are 16-byte aligned; dgamma / dbeta / db need not be
+struct BnGeom {
+    int cg;    // channel groups (of vec channels, one 16-byte load) per workgroup: min(N / vec, 64)
+    int rows;  // row lanes per workgroup: 256 / cg
+    int gx;    // workgroups along N
+    int P;     // pixels per slice
+    int slices;
+};
+BnGeom bn_geom(int M, int N, int vec);          // vec: channels a thread, 4 (fp32) or 8 (bf16)
+bool bn_bad_shape(long M, int N, int vec);      // a shape the launchers refuse: N is not whole workgroups of channel groups
+int bn_slices(int M, int N);  // pixel slices of the fp32 reductions (-1: a shape they do not take)
 hipError_t bn_launch_stats(const float* z, int M, int N, float eps, double* part, float* mu, float* var, float* r, hipStream_t st);
+hipError_t bn_launch_stats(cmx16 z, int M, int N, float eps, double* part, float* mu, float* var, float* r, hipStream_t st);
 hipError_t bn_launch_apply(const float* z, const float* mu, const float* r, const float* gamma, const float* beta, const float* res, int relu, float* y,
                            int M, int N, hipStream_t st);
+hipError_t bn_launch_apply(cmx16 z, const float* mu, const float* r, const float* gamma, const float* beta, cmx16 res, int relu, mx16 y, int M, int N,
+                           hipStream_t st);
 hipError_t bn_launch_bwd_reduce(const float* dy, const float* y, const float* z, const float* mu, const float* r, int M, int N, double* part, float* db,
                                 float* dgamma, float* dbeta, hipStream_t st);
+hipError_t bn_launch_bwd_reduce(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, int M, int N, double* part, float* db, float* dgamma,
+                                float* dbeta, hipStream_t st);
 // M_all > 0: the rows the statistics were taken over (all ranks'), where that is more than the M rows held here
 hipError_t bn_launch_bwd_apply(const float* dy, const float* y, const float* z, const float* mu, const float* r, const float* gamma, const float* dgamma,
                                const float* dbeta, int M, int N, float* dz, float* dzraw, hipStream_t st, double M_all = 0.0);
+hipError_t bn_launch_bwd_apply(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, const float* gamma, const float* dgamma, const float* dbeta,
+                               int M, int N, mx16 dz, mx16 dzraw, hipStream_t st, double M_all = 0.0);
 // The two reductions cut where the ranks of data-parallel training meet: the local column sums into sums [2][N] doubles (which the caller
 // adds over the ranks, in place), then the finish from the sums.  The backward's first half also writes the LOCAL db (= 0), dgamma and
 // dbeta; its second half rounds the summed (dbeta | dgamma) into red [2][N] floats for bn_launch_bwd_apply
 hipError_t bn_launch_stats_sums(const float* z, int M, int N, double* part, double* sums, hipStream_t st);
+hipError_t bn_launch_stats_sums(cmx16 z, int M, int N, double* part, double* sums, hipStream_t st);
 hipError_t bn_launch_stats_from_sums(const double* sums, double M_all, int N, float eps, float* mu, float* var, float* r, hipStream_t st);
 hipError_t bn_launch_bwd_sums(const float* dy, const float* y, const float* z, const float* mu, const float* r, int M, int N, double* part, double* sums,
                               float* db, float* dgamma, float* dbeta, hipStream_t st);
+hipError_t bn_launch_bwd_sums(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, int M, int N, double* part, double* sums, float* db,
+                              float* dgamma, float* dbeta, hipStream_t st);
 hipError_t bn_launch_bwd_from_sums(const double* sums, int N, float* red, hipStream_t st);
 // the second launch of each reduction alone, from partials part[slice][2][N] in that layout
 hipError_t bn_finish_stats(const double* part, int slices, int M, int N, float eps, float* mu, float* var, float* r, hipStream_t st);
@@ -431,55 +467,61 @@ hipError_t bn_finish_bwd_sums(const double* part, int slices, int N, double* sum
 hipError_t bn_launch_momentum(float* stats, const float* batch, const int* hw, int B, int channels, double momentum, int unbiased, hipStream_t st);
 hipError_t bn_launch_install(const float* stats, int channels, float eps, float* keep, float* mean, float* istd, double* sd, hipStream_t st);
 
-// encoder_grad.hip: the launches of the encoder's backward
-// pixels per slice and the slice count of layer idx's weight gradient at batch B; the floats of its partial buffer for every batch up to B
-void wg_slicing(int idx, int B, int* P, int* slices);
+// encoder_grad.hip / encoder_grad_bf16.hip: the launches of the encoder's backward, overloaded on the element type of the activations and
+// cotangents (bf16e: the mixed-precision walks -- bf16 products with fp32 accumulation, fp32 gradients of the fp32 master weights)
+// pixels per slice (whole groups of `group` pixels: 8 for the fp32 kernel, 16 for the bf16 one) and the slice count of layer idx's weight
+// gradient at batch B; the floats of its partial buffer for every batch up to B
+void wg_slicing(int idx, int B, int group, int* P, int* slices);
 size_t wg_partial_floats(int B);
-// dz = dy * [y > 0] (y == nullptr: no activation), dzs = dz * s.  dz / dzs may be nullptr; dz may alias dy.  n elements, N channels
-void gate(const float* dy, const float* y, const float* s, float* dz, float* dzs, long n, int N, hipStream_t st);
-// the weight gradient of layer idx and what hangs on it, into grad_layer = [kernel | bias | gamma | beta]: three launches.  bn (batch
-// statistics): dz is dzraw, dW = G with a unit scale, and the finish is not launched -- bias, gamma and beta come from bn_launch_bwd_reduce
-hipError_t weight_grad(hpe_ctx* c, int idx, const float* x, const float* dz, int B, float* grad_layer, hipStream_t st, bool bn = false);
-// out [M][cin] = dzs [M][cout] . W^T (+ res) on the map of the layer's OUTPUT (a stride-2 layer: the low-resolution map)
-hipError_t data_grad(hpe_ctx* c, int idx, const float* dzs, int B, const float* res, float* out, hipStream_t st);
-void scatter2(const float* lo, float* hi, int B, int H, int C, hipStream_t st);  // lo [B][H][H][C] -> the even pixels of hi [B][2H][2H][C]
-void avgpool_bwd(const float* dy, float* dx, int B, int HW, int C, hipStream_t st);
-void maxpool_bwd(const float* x, const float* dy, float* dx, int B, int H, int C, hipStream_t st);  // x [B][H][H][C], the pool's input
-
-// ... what the mixed-precision weight gradient shares with them: the slicing with whole groups of 16 pixels, and the finish launch
-void wg_slicing16(int idx, int B, int* P, int* slices);
-hipError_t wg_finish(hpe_ctx* c, int idx, int n_kc, int slices, float* grad_layer, hipStream_t st);
-
-// encoder_grad_bf16.hip: the launches of the mixed-precision walks (bf16 activations and cotangents, fp32 accumulation, fp32 gradients).
-// Every activation pointer names bf16 elements
-typedef unsigned short* mx16;
-typedef const unsigned short* cmx16;
+hipError_t wg_finish(hpe_ctx* c, int idx, int n_kc, int slices, float* grad_layer, hipStream_t st);  // the finish launch both precisions share
 hipError_t mx_cast_launch(hpe_ctx* c, int first, int segs, hipStream_t st);  // segments [first, first + segs) of the cast table
 // y = RNE(act(s * conv(x, W16) + shift (+ res))) through the bf16 route of the layer; idx 0 reads the padded bf16 input
 // scale / shift: in place of the layer's folded BatchNorm (the batch-statistics walk: a unit scale and the bias)
 hipError_t mx_conv_forward(hpe_ctx* c, int idx, cmx16 x, int B, cmx16 res, int relu, mx16 y, hipStream_t st, const float* scale = nullptr,
                            const float* shift = nullptr);
-void mx_gate(cmx16 dy, cmx16 y, const float* s, mx16 dz, mx16 dzs, long n, int N, hipStream_t st);  // dzs = RNE(dz * s)
-// x: the layer's input (idx 0: the padded bf16 input); grad_layer fp32 as weight_grad writes it
-// bn (batch statistics), as weight_grad: dz is dzraw16, dW = G with a unit scale, the finish is not launched
-hipError_t mx_weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* grad_layer, hipStream_t st, bool bn = false);
-hipError_t mx_data_grad(hpe_ctx* c, int idx, cmx16 dzs, int B, cmx16 res, mx16 out, hipStream_t st);
-void mx_scatter2(cmx16 lo, mx16 hi, int B, int H, int C, hipStream_t st);
-void mx_avgpool_bwd(const float* dy, mx16 dx, int B, int HW, int C, hipStream_t st);  // dx = RNE(dy / HW)
-void mx_maxpool_bwd(cmx16 x, cmx16 dy, mx16 dx, int B, int H, int C, hipStream_t st);
+// layer idx's convolution, alone on the device, at the precision of its tensors
+inline hipError_t layer_conv(hpe_ctx* c, int idx, const float* x, int B, const float* res, int relu, float* y, hipStream_t st,
+                             const float* scale = nullptr, const float* shift = nullptr) {
+    return run_conv_nhwc(c, idx, x, B, res, relu, y, st, scale, shift);
+}
+inline hipError_t layer_conv(hpe_ctx* c, int idx, cmx16 x, int B, cmx16 res, int relu, mx16 y, hipStream_t st, const float* scale = nullptr,
+                             const float* shift = nullptr) {
+    return mx_conv_forward(c, idx, x, B, res, relu, y, st, scale, shift);
+}
+// dz = dy * [y > 0] (y == nullptr: no activation), dzs = dz * s (bf16: rounded to nearest even).  dz / dzs may be nullptr; dz may alias
+// dy.  n elements, N channels
+void gate(const float* dy, const float* y, const float* s, float* dz, float* dzs, long n, int N, hipStream_t st);
+void gate(cmx16 dy, cmx16 y, const float* s, mx16 dz, mx16 dzs, long n, int N, hipStream_t st);
+// the weight gradient of layer idx and what hangs on it, into the fp32 grad_layer = [kernel | bias | gamma | beta]: three launches.  x: the
+// layer's input; for idx 0 the images (fp32) or the padded bf16 input.  bn (batch statistics): dz is dzraw, dW = G with a unit scale, and
+// the finish is not launched -- bias, gamma and beta come from bn_launch_bwd_reduce
+hipError_t weight_grad(hpe_ctx* c, int idx, const float* x, const float* dz, int B, float* grad_layer, hipStream_t st, bool bn = false);
+hipError_t weight_grad(hpe_ctx* c, int idx, cmx16 x, cmx16 dz, int B, float* grad_layer, hipStream_t st, bool bn = false);
+// out [M][cin] = dzs [M][cout] . W^T (+ res) on the map of the layer's OUTPUT (a stride-2 layer: the low-resolution map)
+hipError_t data_grad(hpe_ctx* c, int idx, const float* dzs, int B, const float* res, float* out, hipStream_t st);
+hipError_t data_grad(hpe_ctx* c, int idx, cmx16 dzs, int B, cmx16 res, mx16 out, hipStream_t st);
+void scatter2(const float* lo, float* hi, int B, int H, int C, hipStream_t st);  // lo [B][H][H][C] -> the even pixels of hi [B][2H][2H][C]
+void scatter2(cmx16 lo, mx16 hi, int B, int H, int C, hipStream_t st);
+void avgpool_bwd(const float* dy, float* dx, int B, int HW, int C, hipStream_t st);
+void avgpool_bwd(const float* dy, mx16 dx, int B, int HW, int C, hipStream_t st);  // dx = RNE(dy / HW)
+void maxpool_bwd(const float* x, const float* dy, float* dx, int B, int H, int C, hipStream_t st);  // x [B][H][H][C], the pool's input
+void maxpool_bwd(cmx16 x, cmx16 dy, mx16 dx, int B, int H, int C, hipStream_t st);
 
-// encoder_bn_bf16.hip: the launches of encoder_bn.hip on bf16 tensors z16 / y16 / res16 / dy16 / dz / dzraw16 (statistics, gamma, beta and
-// the gradients stay fp32); the partials have the layout of the fp32 reductions, whose finish launches run behind these
-hipError_t bn16_launch_stats(cmx16 z, int M, int N, float eps, double* part, float* mu, float* var, float* r, hipStream_t st);
-hipError_t bn16_launch_stats_sums(cmx16 z, int M, int N, double* part, double* sums, hipStream_t st);
-hipError_t bn16_launch_apply(cmx16 z, const float* mu, const float* r, const float* gamma, const float* beta, cmx16 res, int relu, mx16 y, int M, int N,
-                             hipStream_t st);
-hipError_t bn16_launch_bwd_reduce(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, int M, int N, double* part, float* db, float* dgamma,
-                                  float* dbeta, hipStream_t st);
-hipError_t bn16_launch_bwd_sums(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, int M, int N, double* part, double* sums, float* db,
-                                float* dgamma, float* dbeta, hipStream_t st);
-hipError_t bn16_launch_bwd_apply(cmx16 dy, cmx16 y, cmx16 z, const float* mu, const float* r, const float* gamma, const float* dgamma,
-                                 const float* dbeta, int M, int N, mx16 dz, mx16 dzraw, hipStream_t st, double M_all = 0.0);
+// the three glue launches of the training forward at the precision of their tensors (encoder_ops.hip, conv_gemm_bf16.hip)
+inline hipError_t enc_pad_input(const float* img, float* out, int B, int H, int W, int Hp, int Wp, hipStream_t st) {
+    return hpe_launch_pad_input(img, out, B, H, W, Hp, Wp, st);
+}
+inline hipError_t enc_pad_input(const float* img, mx16 out, int B, int H, int W, int Hp, int Wp, hipStream_t st) {
+    return hpe_launch_pad_input_bf16(img, out, B, H, W, Hp, Wp, st);
+}
+inline hipError_t enc_maxpool(const float* x, float* y, int B, int H, int C, hipStream_t st) { return hpe_launch_maxpool(x, y, B, H, C, st); }
+inline hipError_t enc_maxpool(cmx16 x, mx16 y, int B, int H, int C, hipStream_t st) { return hpe_launch_maxpool_bf16(x, y, B, H, C, st); }
+inline hipError_t enc_avgpool(const float* x, float* y, int B, int HW, int C, int ldy, hipStream_t st) {
+    return hpe_launch_avgpool(x, y, B, HW, C, ldy, st);
+}
+inline hipError_t enc_avgpool(cmx16 x, float* y, int B, int HW, int C, int ldy, hipStream_t st) {
+    return hpe_launch_avgpool_bf16(x, y, B, HW, C, ldy, st);
+}
 
 // regressor_train.hip
 int regressor_param_offset(int idx, bool bias);  // idx 3: mean theta; idx 4 (bias false): the total
