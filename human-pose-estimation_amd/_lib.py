@@ -284,22 +284,6 @@ _PROTOS = {
     "hpe_debug_avgpool_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_encoder_stash": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_debug_encoder_stash_batch": (C.c_int, [C.c_void_p]),
-    "hpe_encoder_train_reserve_mixed": (C.c_int, [C.c_void_p, C.c_int]),
-    "hpe_encoder_train_ws_floats_mixed": (C.c_longlong, [C.c_int]),
-    "hpe_encoder_forward_train_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "hpe_encoder_backward_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "hpe_debug_conv_backward_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "hpe_debug_maxpool_backward_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "hpe_debug_avgpool_backward_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "hpe_debug_encoder_stash_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "hpe_debug_encoder_stash_batch_mixed": (C.c_int, [C.c_void_p]),
-    "hpe_encoder_train_reserve_batchnorm_mixed": (C.c_int, [C.c_void_p, C.c_int]),
-    "hpe_encoder_train_ws_floats_batchnorm_mixed": (C.c_longlong, [C.c_int]),
-    "hpe_encoder_forward_batchnorm_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "hpe_encoder_backward_batchnorm_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "hpe_debug_conv_batchnorm_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "hpe_debug_conv_backward_batchnorm_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "hpe_debug_encoder_stash_raw_mixed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hpe_encoder_stat_floats": (C.c_int, []),
     "hpe_encoder_stat_offset": (C.c_int, [C.c_int, C.c_int]),
     "hpe_encoder_train_reserve_batchnorm": (C.c_int, [C.c_void_p, C.c_int]),
@@ -354,6 +338,33 @@ _PROTOS = {
     "hpe_debug_render_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(HpeRenderParams),
                                             C.c_void_p, C.c_void_p]),
 }
+
+# The entry points of encoder training by role: (with frozen BatchNorm statistics, with batch statistics); None: no such call in
+# that mode.  Each exists in fp32 under this name and for the mixed-precision walks under this name + "_mixed", with the same argument
+# list (bf16 buffers cross the ABI as void*), so the *_mixed prototypes are derived here, not listed.
+ENCODER_ENTRY = {
+    "reserve": ("hpe_encoder_train_reserve", "hpe_encoder_train_reserve_batchnorm"),
+    "ws_floats": ("hpe_encoder_train_ws_floats", "hpe_encoder_train_ws_floats_batchnorm"),
+    "forward": ("hpe_encoder_forward_train", "hpe_encoder_forward_batchnorm"),
+    "backward": ("hpe_encoder_backward", "hpe_encoder_backward_batchnorm"),
+    "stash": ("hpe_debug_encoder_stash", "hpe_debug_encoder_stash"),
+    "stash_batch": ("hpe_debug_encoder_stash_batch", "hpe_debug_encoder_stash_batch"),
+    "stash_raw": (None, "hpe_debug_encoder_stash_raw"),
+    "conv_batchnorm": (None, "hpe_debug_conv_batchnorm"),
+    "conv_backward": ("hpe_debug_conv_backward", "hpe_debug_conv_backward_batchnorm"),
+    "maxpool_backward": ("hpe_debug_maxpool_backward", "hpe_debug_maxpool_backward"),
+    "avgpool_backward": ("hpe_debug_avgpool_backward", "hpe_debug_avgpool_backward"),
+}
+_PROTOS.update({name + "_mixed": _PROTOS[name] for pair in ENCODER_ENTRY.values() for name in pair if name})
+
+
+def encoder_symbol(role, batch, suffix=""):
+    """the C symbol of ENCODER_ENTRY[role] with (batch) or without batch statistics; suffix "_mixed": its mixed-precision twin"""
+    name = ENCODER_ENTRY[role][bool(batch)]
+    if name is None:
+        raise ValueError("%s exists with batch statistics only" % role)
+    return name + suffix
+
 
 _lib = None
 

@@ -4,6 +4,7 @@ torch-tensor plumbing around the C-ABI calls.  PyTorch is used for device memory
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -33,6 +34,50 @@ def _require_cuda_tensor(t, name, shape_tail=None):
     if shape_tail is not None and tuple(t.shape[1:]) != tuple(shape_tail):
         raise ValueError("%s must have shape [B,%s], got %s" % (name, ",".join(map(str, shape_tail)), tuple(t.shape)))
     return t.contiguous()
+
+
+def _require_bf16_tensor(t, name):
+    torch = _torch()
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError("%s must be a torch.Tensor on the GPU" % name)
+    if t.dtype != torch.bfloat16:
+        raise TypeError("%s must be bfloat16 (got %s)" % (name, t.dtype))
+    return t.contiguous()
+
+
+def _ptr(t):
+    """device address of an optional tensor: None crosses the ABI as a null pointer"""
+    return t.data_ptr() if t is not None else None
+
+
+def _flat_arg(t, n, name):
+    """-> t as a flat float32 CUDA tensor of exactly n elements"""
+    t = _require_cuda_tensor(t.detach(), name)
+    if tuple(t.shape) != (n,):
+        raise ValueError("%s must be [%d], got %s" % (name, n, tuple(t.shape)))
+    return t
+
+
+class _Prec(collections.namedtuple("_Prec", "suffix dtype check forward")):
+    """What differs between the encoder's fp32 and mixed-precision training calls, the counterpart of Prec<T> in csrc/encoder_train.hip:
+    the suffix of the C symbols (_lib.ENCODER_ENTRY), the torch dtype of activations and cotangents (by name), the checker of such an
+    argument and the words the "no ... has run" errors use for the forward.  Everything else is float32 in both precisions: the images
+    (so layer 0's x), features, statistics, grad_layer, grad_flat, and the pooled cotangent ``dy`` of ``debug_avgpool_backward``."""
+    __slots__ = ()
+
+    def act(self, t, name, idx=None, optional=False):
+        """an activation or cotangent argument (optional: or None) checked; ``x`` of layer idx 0 is the float32 images"""
+        if t is None and optional:
+            return None
+        return _require_cuda_tensor(t, name) if idx == 0 else self.check(t, name)
+
+    def new(self, engine, *shape):
+        """an uninitialised activation or cotangent tensor on the engine's device"""
+        return engine._new(*shape, dtype=self.dtype)
+
+
+_FP32 = _Prec("", "float32", _require_cuda_tensor, "training forward")
+_MIXED = _Prec("_mixed", "bfloat16", _require_bf16_tensor, "mixed-precision training forward")
 
 
 class HpeEngine(object):
@@ -179,11 +224,11 @@ class HpeEngine(object):
     def _stream(self):
         return C.c_void_p(_torch().cuda.current_stream(self.tdev).cuda_stream)
 
-    def _new(self, *shape):
-        return _torch().empty(shape, dtype=_torch().float32, device=self.tdev)
+    def _new(self, *shape, dtype="float32"):
+        return _torch().empty(shape, dtype=getattr(_torch(), dtype), device=self.tdev)
 
-    def _alloc_outputs(self, B, want):
-        shapes = {
+    def _output_shapes(self, B):
+        return {
             "verts": (B, NUM_VERTS, 3),
             "joints": (B, self.num_kp, 3),
             "cams": (B, 3),
@@ -193,9 +238,20 @@ class HpeEngine(object):
             "verts2d": (B, NUM_VERTS, 2),
             "Rs": (B, 24, 3, 3),
         }
+
+    def _alloc_outputs(self, B, want):
+        shapes = self._output_shapes(B)
         tensors = {k: self._new(*shapes[k]) for k in want}
-        o = _lib.HpeOutputs(*[tensors[k].data_ptr() if k in tensors else None for k in _lib.OUTPUT_FIELDS])
+        o = _lib.HpeOutputs(*[_ptr(tensors.get(k)) for k in _lib.OUTPUT_FIELDS])
         return tensors, o
+
+    def _output_sets(self, B, want, n_outs):
+        """-> (outs, arr): n_outs freshly allocated output dicts and the HpeOutputs array that names their buffers"""
+        outs, arr = [], (_lib.HpeOutputs * n_outs)()
+        for i in range(n_outs):
+            t, arr[i] = self._alloc_outputs(B, want)
+            outs.append(t)
+        return outs, arr
 
     # ------------------------------------------------------------------ compute
     DEFAULT_OUTPUTS = ("verts", "joints", "cams", "theta", "J_transformed", "kp2d")
@@ -209,12 +265,7 @@ class HpeEngine(object):
         images = _require_cuda_tensor(images, "images", (224, 224, 3))
         B = images.shape[0]
         n_outs = self.num_stage if all_stages else 1
-        outs = []
-        arr = (_lib.HpeOutputs * n_outs)()
-        for i in range(n_outs):
-            t, o = self._alloc_outputs(B, want)
-            outs.append(t)
-            arr[i] = o
+        outs, arr = self._output_sets(B, want, n_outs)
         fwd = self.lib.hpe_forward_pipelined if pipelined else self.lib.hpe_forward
         if pipelined:
             ts = self.tail_stream()
@@ -229,12 +280,7 @@ class HpeEngine(object):
         features = _require_cuda_tensor(features, "features", (2048,))
         B = features.shape[0]
         n_outs = self.num_stage if all_stages else 1
-        outs = []
-        arr = (_lib.HpeOutputs * n_outs)()
-        for i in range(n_outs):
-            t, o = self._alloc_outputs(B, want)
-            outs.append(t)
-            arr[i] = o
+        outs, arr = self._output_sets(B, want, n_outs)
         _lib.check(self.lib.hpe_tail(self._h, features.data_ptr(), B, arr, n_outs, self._stream()))
         return outs
 
@@ -252,14 +298,7 @@ class HpeEngine(object):
         set rotation are captured after an eager warm-up; images are copied into a static input buffer."""
         torch = _torch()
         n_outs = self.num_stage if all_stages else 1
-        sets = []
-        for _ in range(n_sets):
-            outs, arr = [], (_lib.HpeOutputs * n_outs)()
-            for i in range(n_outs):
-                t, o = self._alloc_outputs(B, want)
-                outs.append(t)
-                arr[i] = o
-            sets.append((outs, arr))
+        sets = [self._output_sets(B, want, n_outs) for _ in range(n_sets)]
         feats = [self._new(B, 2048) for _ in range(2)]
         # the side branch runs on the ctx's own tail stream: a process should keep <= 4 busy HIP streams (DESIGN.md, "hardware queues")
         side = self.tail_stream()
@@ -280,53 +319,37 @@ class HpeEngine(object):
             if with_tail:
                 cur.wait_stream(side)
 
-        if not graph:
+        run = enqueue  # run(images, k, with_tail, with_enc): step k of the pipeline, eagerly or (below) as the replay of its graph
+        if graph:
+            static_in = torch.zeros((B, 224, 224, 3), dtype=torch.float32, device=self.tdev)
+            self.enable_timing(0)  # event timing cannot be captured
+            # eager warm-up of every launch shape (lazy module loading, workspace growth) before capture
+            enqueue(static_in, 0, False, True)
+            enqueue(static_in, 1, True, True)
+            enqueue(None, 2, True, False)
+            torch.cuda.synchronize(self.tdev)
+            period = 2 * n_sets // (2 if n_sets % 2 == 0 else 1)  # lcm(2, n_sets): (feature parity, output set) repeats with this period
 
-            def step(images):
-                k = state["k"]
-                enqueue(images, k, k > 0, True)
-                state["k"] = k + 1
-                if k > 0:
-                    step.last = (k - 1) % n_sets
-                return sets[(k - 1) % n_sets][0] if k > 0 else None
+            def capture(k, with_tail, with_enc):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    enqueue(static_in, k, with_tail, with_enc)
+                return g
 
-            def flush():
-                k = state["k"]
-                if k == 0:
-                    return None
-                enqueue(None, k, True, False)
-                state["k"] = 0
-                step.last = (k - 1) % n_sets
-                return sets[(k - 1) % n_sets][0]
+            g_first = capture(0, False, True)
+            g_steady = [capture(period + r, True, True) for r in range(period)]  # index r == k % period, k >= 1
+            g_flush = [capture(period + r, True, False) for r in range(period)]
 
-            step.flush = flush
-            step.last = None  # index (into step.sets) of the output set of the most recently completed batch
-            step.sets = [s_[0] for s_ in sets]
-            return step
+            def replay(images, k, with_tail, with_enc):
+                if with_enc:
+                    static_in.copy_(images, non_blocking=True)
+                (g_first if not with_tail else g_steady[k % period] if with_enc else g_flush[k % period]).replay()
 
-        static_in = torch.zeros((B, 224, 224, 3), dtype=torch.float32, device=self.tdev)
-        self.enable_timing(0)  # event timing cannot be captured
-        # eager warm-up of every launch shape (lazy module loading, workspace growth) before capture
-        enqueue(static_in, 0, False, True)
-        enqueue(static_in, 1, True, True)
-        enqueue(None, 2, True, False)
-        torch.cuda.synchronize(self.tdev)
-        period = 2 * n_sets // (2 if n_sets % 2 == 0 else 1)  # lcm(2, n_sets): (feature parity, output set) repeats with this period
-
-        def capture(k, with_tail, with_enc):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                enqueue(static_in, k, with_tail, with_enc)
-            return g
-
-        g_first = capture(0, False, True)
-        g_steady = [capture(period + r, True, True) for r in range(period)]  # index r == k % period, k >= 1
-        g_flush = [capture(period + r, True, False) for r in range(period)]
+            run = replay
 
         def step(images):
             k = state["k"]
-            static_in.copy_(images, non_blocking=True)
-            (g_first if k == 0 else g_steady[k % period]).replay()
+            run(images, k, k > 0, True)
             state["k"] = k + 1
             if k > 0:
                 step.last = (k - 1) % n_sets
@@ -336,15 +359,16 @@ class HpeEngine(object):
             k = state["k"]
             if k == 0:
                 return None
-            g_flush[k % period].replay()
+            run(None, k, True, False)
             state["k"] = 0
             step.last = (k - 1) % n_sets
             return sets[(k - 1) % n_sets][0]
 
         step.flush = flush
-        step.last = None
+        step.last = None  # index (into step.sets) of the output set of the most recently completed batch
         step.sets = [s_[0] for s_ in sets]
-        step.graphs = (g_first, g_steady, g_flush)  # keep alive
+        if graph:
+            step.graphs = (g_first, g_steady, g_flush)  # keep alive
         return step
 
     def tail_stream(self):
@@ -368,12 +392,7 @@ class HpeEngine(object):
         k+1); the caller reads the outputs after ``join()`` or from work enqueued on ``tail_stream()``."""
         torch = _torch()
         n_outs = self.num_stage if all_stages else 1
-        outs = []
-        arr = (_lib.HpeOutputs * n_outs)()
-        for i in range(n_outs):
-            t, o = self._alloc_outputs(B, want)
-            outs.append(t)
-            arr[i] = o
+        outs, arr = self._output_sets(B, want, n_outs)
         lib, h = self.lib, self._h
         fwd = lib.hpe_forward_pipelined if pipelined else lib.hpe_forward
         if pipelined and graph:
@@ -421,25 +440,11 @@ class HpeEngine(object):
     def regress_stage(self, features, theta_prev=None):
         features = _require_cuda_tensor(features, "features", (2048,))
         B = features.shape[0]
-        tp = None
         if theta_prev is not None:
             theta_prev = _require_cuda_tensor(theta_prev, "theta_prev", (85,))
-            tp = theta_prev.data_ptr()
         out = self._new(B, 85)
-        _lib.check(self.lib.hpe_regress_stage(self._h, features.data_ptr(), tp, B, out.data_ptr(), self._stream()))
+        _lib.check(self.lib.hpe_regress_stage(self._h, features.data_ptr(), _ptr(theta_prev), B, out.data_ptr(), self._stream()))
         return out
-
-    def _output_shapes(self, B):
-        return {
-            "verts": (B, NUM_VERTS, 3),
-            "joints": (B, self.num_kp, 3),
-            "cams": (B, 3),
-            "theta": (B, 85),
-            "J_transformed": (B, 24, 3),
-            "kp2d": (B, self.num_kp, 2),
-            "verts2d": (B, NUM_VERTS, 2),
-            "Rs": (B, 24, 3, 3),
-        }
 
     def smpl(self, theta, want=("verts", "joints", "J_transformed", "kp2d", "Rs")):
         """hpe_smpl on theta rows [B,85].  A theta that requires grad goes through ``autograd.SmplFunction`` (the outputs then
@@ -475,7 +480,7 @@ class HpeEngine(object):
         mb = self.max_batch
         for lo in range(0, B, mb):
             n = min(mb, B - lo)
-            o = _lib.HpeOutputs(*[g[k][lo : lo + n].data_ptr() if k in g else None for k in _lib.OUTPUT_FIELDS])
+            o = _lib.HpeOutputs(*[_ptr(g[k][lo : lo + n] if k in g else None) for k in _lib.OUTPUT_FIELDS])
             _lib.check(self.lib.hpe_smpl_backward(self._h, theta[lo : lo + n].data_ptr(), n, C.byref(o), out[lo : lo + n].data_ptr(), self._stream()))
         return out
 
@@ -513,8 +518,8 @@ class HpeEngine(object):
         joints, betas, Rs, N, K, stride = self._critic_inputs(joints, betas, Rs)
         scores = self._new(N, 3)
         kcs = self._new(N, 13, 13) if want_kcs else None
-        _lib.check(self.lib.hpe_critic(self._h, joints.data_ptr(), K, betas.data_ptr(), stride, Rs.data_ptr(), N, scores.data_ptr(),
-                                       kcs.data_ptr() if want_kcs else None, self._stream()))
+        _lib.check(self.lib.hpe_critic(self._h, joints.data_ptr(), K, betas.data_ptr(), stride, Rs.data_ptr(), N, scores.data_ptr(), _ptr(kcs),
+                                       self._stream()))
         return (scores, kcs) if want_kcs else scores
 
     def critic_backward(self, joints, betas, Rs, grad_scores=None, want=("joints", "betas", "Rs")):
@@ -529,9 +534,9 @@ class HpeEngine(object):
         shapes_of["joints"] = (K, 3)
         gs = self._grad_scores(grad_scores, N)
         out = {k: self._new(N, *shapes_of[k]) for k in want}
-        ptr = [out[k].data_ptr() if k in out else None for k in ("joints", "betas", "Rs", "kcs")]
-        _lib.check(self.lib.hpe_critic_backward(self._h, joints.data_ptr(), K, betas.data_ptr(), stride, Rs.data_ptr(), N,
-                                                gs.data_ptr() if gs is not None else None, *ptr, self._stream()))
+        ptr = [_ptr(out.get(k)) for k in ("joints", "betas", "Rs", "kcs")]
+        _lib.check(self.lib.hpe_critic_backward(self._h, joints.data_ptr(), K, betas.data_ptr(), stride, Rs.data_ptr(), N, _ptr(gs), *ptr,
+                                                self._stream()))
         return out
 
     _TANGENT_SHAPES = {"kcs": (13, 13), "joints": (14, 3), "betas": (10,), "Rs": (23, 3, 3)}
@@ -568,10 +573,9 @@ class HpeEngine(object):
             per_row = row
             keep[k] = v
         out = self._new(PARAM_FLOATS)
-        ptr = [keep[k].data_ptr() if k in keep else None for k in ("kcs", "joints", "betas", "Rs")]
-        _lib.check(self.lib.hpe_critic_weight_grad(self._h, joints.data_ptr(), K, betas.data_ptr(), stride, Rs.data_ptr(), N,
-                                                   gs.data_ptr() if gs is not None else None, *ptr, 1 if per_row else 0, out.data_ptr(),
-                                                   self._stream()))
+        ptr = [_ptr(keep.get(k)) for k in ("kcs", "joints", "betas", "Rs")]
+        _lib.check(self.lib.hpe_critic_weight_grad(self._h, joints.data_ptr(), K, betas.data_ptr(), stride, Rs.data_ptr(), N, _ptr(gs), *ptr,
+                                                   1 if per_row else 0, out.data_ptr(), self._stream()))
         return out
 
     def critic_reserve(self, N):
@@ -588,10 +592,7 @@ class HpeEngine(object):
     def set_critic_params(self, flat):
         """hpe_critic_set_params_dev: replace the live critic weights by ``flat`` on the device, in stream order, without a host round
         trip (``load_critic`` comes first, once; ``critic_spec.flat_to_params`` turns a flat tensor back into its dict)"""
-        flat = _require_cuda_tensor(flat.detach(), "flat")
-        if tuple(flat.shape) != (PARAM_FLOATS,):
-            raise ValueError("flat must be [%d], got %s" % (PARAM_FLOATS, tuple(flat.shape)))
-        _lib.check(self.lib.hpe_critic_set_params_dev(self._h, flat.data_ptr(), self._stream()))
+        _lib.check(self.lib.hpe_critic_set_params_dev(self._h, _flat_arg(flat, PARAM_FLOATS, "flat").data_ptr(), self._stream()))
 
     # ------------------------------------------------------------------ regressor training
     def regressor_params(self):
@@ -604,10 +605,7 @@ class HpeEngine(object):
     def set_regressor_params(self, flat):
         """hpe_regressor_set_params_dev: replace the live regressor and mean theta by ``flat`` on the device, in stream order, without
         a host round trip (``regressor_spec.flat_to_params`` turns a flat tensor back into its dict)"""
-        flat = _require_cuda_tensor(flat.detach(), "flat")
-        if tuple(flat.shape) != (REGRESSOR_PARAM_FLOATS,):
-            raise ValueError("flat must be [%d], got %s" % (REGRESSOR_PARAM_FLOATS, tuple(flat.shape)))
-        _lib.check(self.lib.hpe_regressor_set_params_dev(self._h, flat.data_ptr(), self._stream()))
+        _lib.check(self.lib.hpe_regressor_set_params_dev(self._h, _flat_arg(flat, REGRESSOR_PARAM_FLOATS, "flat").data_ptr(), self._stream()))
 
     def _drop(self, drop, B):
         if drop is None:
@@ -624,8 +622,7 @@ class HpeEngine(object):
         B = features.shape[0]
         drop = self._drop(drop, B)
         out = self._new(self.num_stage, B, 85)
-        _lib.check(self.lib.hpe_regressor_forward_train(self._h, features.data_ptr(), B, drop.data_ptr() if drop is not None else None,
-                                                        out.data_ptr(), self._stream()))
+        _lib.check(self.lib.hpe_regressor_forward_train(self._h, features.data_ptr(), B, _ptr(drop), out.data_ptr(), self._stream()))
         return out
 
     def regressor_backward(self, features, grad_thetas, drop=None, want_grad_features=True):
@@ -641,9 +638,8 @@ class HpeEngine(object):
                 raise ValueError("grad_thetas must be [%d,%d,85], got %s" % (self.num_stage, B, tuple(grad_thetas.shape)))
         gflat = self._new(REGRESSOR_PARAM_FLOATS)
         gfeat = self._new(B, 2048) if want_grad_features else None
-        _lib.check(self.lib.hpe_regressor_backward(self._h, features.data_ptr(), B, drop.data_ptr() if drop is not None else None,
-                                                   grad_thetas.data_ptr() if grad_thetas is not None else None, gflat.data_ptr(),
-                                                   gfeat.data_ptr() if want_grad_features else None, self._stream()))
+        _lib.check(self.lib.hpe_regressor_backward(self._h, features.data_ptr(), B, _ptr(drop), _ptr(grad_thetas), gflat.data_ptr(), _ptr(gfeat),
+                                                   self._stream()))
         return gflat, gfeat
 
     # ------------------------------------------------------------------ encoder training (fp32 contexts; BatchNorm statistics frozen or of the batch)
@@ -654,15 +650,20 @@ class HpeEngine(object):
         (hpe_encoder_train_reserve_mixed): also the bf16 stash, cotangent buffers and weight operands of the mixed-precision walks.
         precision="mixed": the same with batch_norm=False; with batch_norm=True (hpe_encoder_train_reserve_batchnorm_mixed) both of
         those reserves and the bf16 raw-output stash of the mixed-precision walks with batch statistics."""
-        mixed = self._mixed(precision, "batch" if batch_norm else "frozen")
-        if batch_norm and mixed:
-            _lib.check(self.lib.hpe_encoder_train_reserve_batchnorm_mixed(self._h, int(B)))
-        elif batch_norm:
-            _lib.check(self.lib.hpe_encoder_train_reserve_batchnorm(self._h, int(B)))
-        elif mixed:
-            _lib.check(self.lib.hpe_encoder_train_reserve_mixed(self._h, int(B)))
-        else:
-            _lib.check(self.lib.hpe_encoder_train_reserve(self._h, int(B)))
+        fn, _ = self._entry("reserve", "batch" if batch_norm else "frozen", precision)
+        _lib.check(fn(self._h, int(B)))
+
+    @staticmethod
+    def _entry_symbol(role, bn="frozen", precision="fp32"):
+        """-> (name of the C entry point of ``role`` in this BatchNorm mode and precision (_lib.ENCODER_ENTRY), the precision's _Prec)"""
+        batch = HpeEngine._bn_mode(bn)
+        prec = _MIXED if HpeEngine._mixed(precision, bn) else _FP32
+        return _lib.encoder_symbol(role, batch, prec.suffix), prec
+
+    def _entry(self, role, bn="frozen", precision="fp32"):
+        """``_entry_symbol`` with the library's function in place of its name"""
+        name, prec = self._entry_symbol(role, bn, precision)
+        return getattr(self.lib, name), prec
 
     @staticmethod
     def _bn_mode(bn):
@@ -682,18 +683,6 @@ class HpeEngine(object):
             raise ValueError("precision='bf16' runs with frozen BatchNorm statistics only: batch statistics in bf16 are the follow-up")
         return precision != "fp32"
 
-    def _bf16_arg(self, t, name):
-        torch = _torch()
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError("%s must be a torch.Tensor on the GPU" % name)
-        if t.dtype != torch.bfloat16:
-            raise TypeError("%s must be bfloat16 (got %s)" % (name, t.dtype))
-        return t.contiguous()
-
-    def _new_bf16(self, *shape):
-        torch = _torch()
-        return torch.empty(shape, dtype=torch.bfloat16, device=self.tdev)
-
     def encoder_stats(self):
         """hpe_encoder_get_stats: the installed moving statistics as one flat CUDA tensor [resnet_spec.ENCODER_STAT_FLOATS] (moving_mean of
         every layer, then moving_variance of every layer)"""
@@ -701,24 +690,18 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_encoder_get_stats(self._h, out.data_ptr(), self._stream()))
         return out
 
-    def _stats_arg(self, stats):
-        stats = _require_cuda_tensor(stats.detach(), "stats")
-        if tuple(stats.shape) != (ENCODER_STAT_FLOATS,):
-            raise ValueError("stats must be [%d], got %s" % (ENCODER_STAT_FLOATS, tuple(stats.shape)))
-        return stats
-
     def update_encoder_stats(self, stats, momentum=0.99, unbiased=True):
         """hpe_encoder_update_stats: stats <- momentum * stats + (1 - momentum) * (the batch statistics of the last ``bn="batch"`` forward
         or backward), in place on the CUDA tensor ``stats``; unbiased multiplies each batch variance by M / (M - 1).  Returns ``stats``.
         It installs nothing: ``set_encoder_stats_dev`` does."""
-        _lib.check(self.lib.hpe_encoder_update_stats(self._h, self._stats_arg(stats).data_ptr(), float(momentum), int(bool(unbiased)), self._stream()))
+        _lib.check(self.lib.hpe_encoder_update_stats(self._h, _flat_arg(stats, ENCODER_STAT_FLOATS, "stats").data_ptr(), float(momentum),
+                                                     int(bool(unbiased)), self._stream()))
         return stats
 
     def set_encoder_stats_dev(self, stats):
         """hpe_encoder_set_stats_dev: install the CUDA tensor ``stats`` as the moving statistics, in stream order: the folded BatchNorm
         scale / shift and the dual-source weights are rewritten from them and the live parameters.  Capturable."""
-        stats = self._stats_arg(stats)
-        _lib.check(self.lib.hpe_encoder_set_stats_dev(self._h, stats.data_ptr(), self._stream()))
+        _lib.check(self.lib.hpe_encoder_set_stats_dev(self._h, _flat_arg(stats, ENCODER_STAT_FLOATS, "stats").data_ptr(), self._stream()))
 
     def encoder_batch_stats(self):
         """hpe_debug_encoder_batch_stats: mu | var of every layer of the last ``bn="batch"`` forward, in the statistics layout"""
@@ -726,72 +709,56 @@ class HpeEngine(object):
         _lib.check(self.lib.hpe_debug_encoder_batch_stats(self._h, out.data_ptr(), self._stream()))
         return out
 
+    def _stash(self, role, what, idx, bn, precision):
+        """one stashed map of the last training forward of this precision, over that call's batch (idx -1: the max-pooled map)"""
+        stash_batch, prec = self._entry("stash_batch", bn, precision)
+        fn, _ = self._entry(role, bn, precision)
+        B = stash_batch(self._h)
+        if B < 1:
+            raise _lib.HpeError("%s: no %s has run" % (what, prec.forward))
+        s = CONV_SPECS[idx] if idx >= 0 else None
+        out = prec.new(self, B, s.hout, s.hout, s.cout) if s else prec.new(self, B, 56, 56, 64)
+        _lib.check(fn(self._h, idx, out.data_ptr(), self._stream()))
+        return out
+
     def encoder_stash_raw(self, idx, precision="fp32"):
         """hpe_debug_encoder_stash_raw: layer idx's raw output conv(x, W) + b of the last ``bn="batch"`` forward, over that call's batch.
         precision="mixed" (hpe_debug_encoder_stash_raw_mixed): of the last mixed-precision one, as torch.bfloat16"""
-        if self._mixed(precision, "batch"):
-            B = self.lib.hpe_debug_encoder_stash_batch_mixed(self._h)
-            if B < 1:
-                raise _lib.HpeError("encoder_stash_raw: no mixed-precision training forward has run")
-            s = CONV_SPECS[idx]
-            out = self._new_bf16(B, s.hout, s.hout, s.cout)
-            _lib.check(self.lib.hpe_debug_encoder_stash_raw_mixed(self._h, idx, out.data_ptr(), self._stream()))
-            return out
-        B = self.lib.hpe_debug_encoder_stash_batch(self._h)
-        if B < 1:
-            raise _lib.HpeError("encoder_stash_raw: no training forward has run")
-        s = CONV_SPECS[idx]
-        out = self._new(B, s.hout, s.hout, s.cout)
-        _lib.check(self.lib.hpe_debug_encoder_stash_raw(self._h, idx, out.data_ptr(), self._stream()))
-        return out
+        return self._stash("stash_raw", "encoder_stash_raw", idx, "batch", precision)
 
     def debug_conv_batchnorm(self, idx, x, residual=None, relu=True, precision="fp32"):
         """hpe_debug_conv_batchnorm: one layer with batch statistics -> (y, z, stats [2 * cout] = mu | var).  precision="mixed"
         (hpe_debug_conv_batchnorm_mixed): x, residual, y and z are torch.bfloat16 (x of idx 0: the float32 images), stats float32"""
+        fn, prec = self._entry("conv_batchnorm", "batch", precision)
         s = CONV_SPECS[idx]
-        if self._mixed(precision, "batch"):
-            x = _require_cuda_tensor(x, "x") if idx == 0 else self._bf16_arg(x, "x")
-            B = x.shape[0]
-            y, z, st = self._new_bf16(B, s.hout, s.hout, s.cout), self._new_bf16(B, s.hout, s.hout, s.cout), self._new(2 * s.cout)
-            residual = self._bf16_arg(residual, "residual") if residual is not None else None
-            _lib.check(self.lib.hpe_debug_conv_batchnorm_mixed(self._h, idx, x.data_ptr(), B, residual.data_ptr() if residual is not None else None,
-                                                               int(relu), y.data_ptr(), z.data_ptr(), st.data_ptr(), self._stream()))
-            return y, z, st
-        x = _require_cuda_tensor(x, "x")
+        x = prec.act(x, "x", idx)
         B = x.shape[0]
-        y, z, st = self._new(B, s.hout, s.hout, s.cout), self._new(B, s.hout, s.hout, s.cout), self._new(2 * s.cout)
-        r = _require_cuda_tensor(residual, "residual").data_ptr() if residual is not None else None
-        _lib.check(self.lib.hpe_debug_conv_batchnorm(self._h, idx, x.data_ptr(), B, r, int(relu), y.data_ptr(), z.data_ptr(), st.data_ptr(),
-                                                     self._stream()))
+        y, z, st = prec.new(self, B, s.hout, s.hout, s.cout), prec.new(self, B, s.hout, s.hout, s.cout), self._new(2 * s.cout)
+        residual = prec.act(residual, "residual", optional=True)
+        _lib.check(fn(self._h, idx, x.data_ptr(), B, _ptr(residual), int(relu), y.data_ptr(), z.data_ptr(), st.data_ptr(), self._stream()))
         return y, z, st
+
+    def _conv_backward(self, bn, precision, idx, x, z, y, dy, want_dx):
+        """one layer's backward in either BatchNorm mode (z: the raw output, read with batch statistics only) and either precision"""
+        fn, prec = self._entry("conv_backward", bn, precision)
+        s = CONV_SPECS[idx]
+        x = prec.act(x, "x", idx)
+        z = prec.act(z, "z") if bn == "batch" else None
+        dy = prec.act(dy, "dy")
+        y = prec.act(y, "y", optional=True)  # None: a layer without activation (dz = dy)
+        B = x.shape[0]
+        dx = prec.new(self, B, s.hin, s.hin, s.cin) if want_dx and idx != 0 else None
+        gl = self._new(s.kh * s.kw * s.cin * s.cout + 3 * s.cout)
+        acts = [x.data_ptr()] + ([z.data_ptr()] if bn == "batch" else []) + [_ptr(y), dy.data_ptr()]
+        _lib.check(fn(self._h, idx, *acts, B, _ptr(dx), gl.data_ptr(), self._stream()))
+        return dx, gl
 
     def debug_conv_backward_batchnorm(self, idx, x, z, y, dy, want_dx=True, precision="fp32"):
         """hpe_debug_conv_backward_batchnorm: one layer's gate, BatchNorm backward, weight and data gradient from its raw output z and
         its activated output y (None: no activation) -> (dx or None, grad_layer = [kernel | bias = 0 | gamma | beta] flat).
         precision="mixed" (hpe_debug_conv_backward_batchnorm_mixed): x, z, y, dy and dx are torch.bfloat16 (x of idx 0: the float32
         images); grad_layer is float32"""
-        s = CONV_SPECS[idx]
-        if self._mixed(precision, "batch"):
-            x = _require_cuda_tensor(x, "x") if idx == 0 else self._bf16_arg(x, "x")
-            z, dy = self._bf16_arg(z, "z"), self._bf16_arg(dy, "dy")
-            y = self._bf16_arg(y, "y") if y is not None else None
-            B = x.shape[0]
-            want_dx = want_dx and idx != 0
-            dx = self._new_bf16(B, s.hin, s.hin, s.cin) if want_dx else None
-            gl = self._new(s.kh * s.kw * s.cin * s.cout + 3 * s.cout)
-            _lib.check(self.lib.hpe_debug_conv_backward_batchnorm_mixed(self._h, idx, x.data_ptr(), z.data_ptr(),
-                                                                        y.data_ptr() if y is not None else None, dy.data_ptr(), B,
-                                                                        dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
-            return dx, gl
-        x, z, dy = _require_cuda_tensor(x, "x"), _require_cuda_tensor(z, "z"), _require_cuda_tensor(dy, "dy")
-        y = _require_cuda_tensor(y, "y") if y is not None else None
-        B = x.shape[0]
-        want_dx = want_dx and idx != 0
-        dx = self._new(B, s.hin, s.hin, s.cin) if want_dx else None
-        gl = self._new(s.kh * s.kw * s.cin * s.cout + 3 * s.cout)
-        _lib.check(self.lib.hpe_debug_conv_backward_batchnorm(self._h, idx, x.data_ptr(), z.data_ptr(), y.data_ptr() if y is not None else None,
-                                                              dy.data_ptr(), B, dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
-        return dx, gl
+        return self._conv_backward("batch", precision, idx, x, z, y, dy, want_dx)
 
     # ------------------------------------------------------------------ data-parallel training: statistics over the batch of all ranks
     def set_encoder_reduce(self, callback, global_batch=0, owner=None):
@@ -838,19 +805,19 @@ class HpeEngine(object):
         s = CONV_SPECS[idx]
         z, sums = _require_cuda_tensor(z, "z"), self._sums_arg(sums, idx, "sums")
         y, st = self._new(*z.shape), self._new(2 * s.cout)
-        r = _require_cuda_tensor(residual, "residual").data_ptr() if residual is not None else None
-        _lib.check(self.lib.hpe_debug_bn_finish(self._h, idx, sums.data_ptr(), int(M), z.data_ptr(), z.shape[0], r, int(relu), y.data_ptr(),
-                                                st.data_ptr(), self._stream()))
+        residual = _FP32.act(residual, "residual", optional=True)
+        _lib.check(self.lib.hpe_debug_bn_finish(self._h, idx, sums.data_ptr(), int(M), z.data_ptr(), z.shape[0], _ptr(residual), int(relu),
+                                                y.data_ptr(), st.data_ptr(), self._stream()))
         return y, st
 
     def debug_bn_backward_sums(self, idx, z, y, dy, sums, M):
         """hpe_debug_bn_backward_sums: -> [2, cout] float64 = (sum dz | sum dz * xhat) over the rows given, xhat from (sums, M)"""
         torch = _torch()
         z, dy, sums = _require_cuda_tensor(z, "z"), _require_cuda_tensor(dy, "dy"), self._sums_arg(sums, idx, "sums")
-        y = _require_cuda_tensor(y, "y") if y is not None else None
+        y = _FP32.act(y, "y", optional=True)
         out = torch.empty((2, CONV_SPECS[idx].cout), dtype=torch.float64, device=self.tdev)
-        _lib.check(self.lib.hpe_debug_bn_backward_sums(self._h, idx, z.data_ptr(), y.data_ptr() if y is not None else None, dy.data_ptr(),
-                                                       z.shape[0], sums.data_ptr(), int(M), out.data_ptr(), self._stream()))
+        _lib.check(self.lib.hpe_debug_bn_backward_sums(self._h, idx, z.data_ptr(), _ptr(y), dy.data_ptr(), z.shape[0], sums.data_ptr(), int(M),
+                                                       out.data_ptr(), self._stream()))
         return out
 
     def debug_bn_backward_finish(self, idx, x, z, y, dy, sums, bwd_sums, M, want_dx=True):
@@ -858,15 +825,13 @@ class HpeEngine(object):
         ``bwd_sums`` -> (dx or None, grad_layer = [kernel | bias = 0 | gamma | beta], each the partial of these rows)"""
         s = CONV_SPECS[idx]
         x, z, dy = _require_cuda_tensor(x, "x"), _require_cuda_tensor(z, "z"), _require_cuda_tensor(dy, "dy")
-        y = _require_cuda_tensor(y, "y") if y is not None else None
+        y = _FP32.act(y, "y", optional=True)
         sums, bwd_sums = self._sums_arg(sums, idx, "sums"), self._sums_arg(bwd_sums, idx, "bwd_sums")
         B = x.shape[0]
-        want_dx = want_dx and idx != 0
-        dx = self._new(B, s.hin, s.hin, s.cin) if want_dx else None
+        dx = self._new(B, s.hin, s.hin, s.cin) if want_dx and idx != 0 else None
         gl = self._new(s.kh * s.kw * s.cin * s.cout + 3 * s.cout)
-        _lib.check(self.lib.hpe_debug_bn_backward_finish(self._h, idx, x.data_ptr(), z.data_ptr(), y.data_ptr() if y is not None else None,
-                                                         dy.data_ptr(), B, sums.data_ptr(), bwd_sums.data_ptr(), int(M),
-                                                         dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
+        _lib.check(self.lib.hpe_debug_bn_backward_finish(self._h, idx, x.data_ptr(), z.data_ptr(), _ptr(y), dy.data_ptr(), B, sums.data_ptr(),
+                                                         bwd_sums.data_ptr(), int(M), _ptr(dx), gl.data_ptr(), self._stream()))
         return dx, gl
 
     def encoder_params(self):
@@ -890,10 +855,7 @@ class HpeEngine(object):
         """hpe_encoder_set_params_dev: replace the encoder's trainable parameters by the CUDA tensor ``flat`` on the device, in stream
         order: every packing the context holds is rewritten by gather kernels, bit for bit what a fresh context would hold.  No host
         round trip, no synchronisation, capturable."""
-        flat = _require_cuda_tensor(flat.detach(), "flat")
-        if tuple(flat.shape) != (ENCODER_PARAM_FLOATS,):
-            raise ValueError("flat must be [%d], got %s" % (ENCODER_PARAM_FLOATS, tuple(flat.shape)))
-        _lib.check(self.lib.hpe_encoder_set_params_dev(self._h, flat.data_ptr(), self._stream()))
+        _lib.check(self.lib.hpe_encoder_set_params_dev(self._h, _flat_arg(flat, ENCODER_PARAM_FLOATS, "flat").data_ptr(), self._stream()))
 
     def encoder_packing(self, idx, which):
         """hpe_debug_encoder_packing: the bytes of one packing of layer idx (``which``: a name of _lib.ENCODER_PACKINGS or its index)
@@ -914,9 +876,7 @@ class HpeEngine(object):
         (hpe_encoder_forward_train_mixed): bf16 activations and matrix products, fp32 accumulation; images and features stay fp32.
         precision="mixed": the same with bn="frozen"; with bn="batch" (hpe_encoder_forward_batchnorm_mixed) the statistics of this
         batch, taken of the bf16 raw outputs in float64."""
-        fn = self.lib.hpe_encoder_forward_batchnorm if self._bn_mode(bn) else self.lib.hpe_encoder_forward_train
-        if self._mixed(precision, bn):
-            fn = self.lib.hpe_encoder_forward_batchnorm_mixed if bn == "batch" else self.lib.hpe_encoder_forward_train_mixed
+        fn, _ = self._entry("forward", bn, precision)
         images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))
         B = images.shape[0]
         out = self._new(B, 2048)
@@ -928,9 +888,7 @@ class HpeEngine(object):
         (the training forward runs again); same inputs, same bits.  bn="batch" (hpe_encoder_backward_batchnorm): through the batch
         statistics; the bias slots are 0.  precision="bf16" (hpe_encoder_backward_mixed): the mixed-precision walk; the flat gradient
         is fp32.  precision="mixed": that walk with bn="frozen", hpe_encoder_backward_batchnorm_mixed with bn="batch"."""
-        fn = self.lib.hpe_encoder_backward_batchnorm if self._bn_mode(bn) else self.lib.hpe_encoder_backward
-        if self._mixed(precision, bn):
-            fn = self.lib.hpe_encoder_backward_batchnorm_mixed if bn == "batch" else self.lib.hpe_encoder_backward_mixed
+        fn, _ = self._entry("backward", bn, precision)
         images = _require_cuda_tensor(images.detach(), "images", (224, 224, 3))
         B = images.shape[0]
         grad_features = _require_cuda_tensor(grad_features.detach(), "grad_features")
@@ -944,68 +902,26 @@ class HpeEngine(object):
         """hpe_debug_conv_backward: one layer's gate, weight gradient and data gradient -> (dx or None, grad_layer = [kernel | bias |
         gamma | beta] flat).  precision="bf16" (hpe_debug_conv_backward_mixed): x, y, dy and dx are torch.bfloat16 (x of idx 0: the
         float32 images); grad_layer is float32"""
-        s = CONV_SPECS[idx]
-        if self._mixed(precision):
-            x = _require_cuda_tensor(x, "x") if idx == 0 else self._bf16_arg(x, "x")
-            dy = self._bf16_arg(dy, "dy")
-            y = self._bf16_arg(y, "y") if y is not None else None
-            B = x.shape[0]
-            want_dx = want_dx and idx != 0
-            dx = self._new_bf16(B, s.hin, s.hin, s.cin) if want_dx else None
-            gl = self._new(s.kh * s.kw * s.cin * s.cout + 3 * s.cout)
-            _lib.check(self.lib.hpe_debug_conv_backward_mixed(self._h, idx, x.data_ptr(), y.data_ptr() if y is not None else None, dy.data_ptr(),
-                                                              B, dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
-            return dx, gl
-        x, dy = _require_cuda_tensor(x, "x"), _require_cuda_tensor(dy, "dy")
-        y = _require_cuda_tensor(y, "y") if y is not None else None  # None: a layer without activation (dz = dy)
-        B = x.shape[0]
-        want_dx = want_dx and idx != 0
-        dx = self._new(B, s.hin, s.hin, s.cin) if want_dx else None
-        gl = self._new(s.kh * s.kw * s.cin * s.cout + 3 * s.cout)
-        _lib.check(self.lib.hpe_debug_conv_backward(self._h, idx, x.data_ptr(), y.data_ptr() if y is not None else None, dy.data_ptr(), B,
-                                                    dx.data_ptr() if want_dx else None, gl.data_ptr(), self._stream()))
-        return dx, gl
+        return self._conv_backward("frozen", precision, idx, x, None, y, dy, want_dx)
 
     def debug_maxpool_backward(self, x, dy, precision="fp32"):
-        if self._mixed(precision):
-            x, dy = self._bf16_arg(x, "x"), self._bf16_arg(dy, "dy")
-            dx = self._new_bf16(*x.shape)
-            _lib.check(self.lib.hpe_debug_maxpool_backward_mixed(x.data_ptr(), dy.data_ptr(), x.shape[0], x.shape[1], x.shape[3], dx.data_ptr(),
-                                                                 self._stream()))
-            return dx
-        x, dy = _require_cuda_tensor(x, "x"), _require_cuda_tensor(dy, "dy")
-        dx = self._new(*x.shape)
-        _lib.check(self.lib.hpe_debug_maxpool_backward(x.data_ptr(), dy.data_ptr(), x.shape[0], x.shape[1], x.shape[3], dx.data_ptr(), self._stream()))
+        fn, prec = self._entry("maxpool_backward", "frozen", precision)
+        x, dy = prec.act(x, "x"), prec.act(dy, "dy")
+        dx = prec.new(self, *x.shape)
+        _lib.check(fn(x.data_ptr(), dy.data_ptr(), x.shape[0], x.shape[1], x.shape[3], dx.data_ptr(), self._stream()))
         return dx
 
     def debug_avgpool_backward(self, dy, HW, precision="fp32"):
-        dy = _require_cuda_tensor(dy, "dy")
-        if self._mixed(precision):
-            dx = self._new_bf16(dy.shape[0], HW, dy.shape[1])
-            _lib.check(self.lib.hpe_debug_avgpool_backward_mixed(dy.data_ptr(), dy.shape[0], HW, dy.shape[1], dx.data_ptr(), self._stream()))
-            return dx
-        dx = self._new(dy.shape[0], HW, dy.shape[1])
-        _lib.check(self.lib.hpe_debug_avgpool_backward(dy.data_ptr(), dy.shape[0], HW, dy.shape[1], dx.data_ptr(), self._stream()))
+        dy = _require_cuda_tensor(dy, "dy")  # the cotangent of the features: float32 in both precisions
+        fn, prec = self._entry("avgpool_backward", "frozen", precision)
+        dx = prec.new(self, dy.shape[0], HW, dy.shape[1])
+        _lib.check(fn(dy.data_ptr(), dy.shape[0], HW, dy.shape[1], dx.data_ptr(), self._stream()))
         return dx
 
     def encoder_stash(self, idx, precision="fp32"):
         """hpe_debug_encoder_stash: layer idx's output of the last training forward, over that call's batch (idx -1: the max-pooled map).
         precision="bf16" (hpe_debug_encoder_stash_mixed): of the last mixed-precision forward, as torch.bfloat16"""
-        if self._mixed(precision):
-            B = self.lib.hpe_debug_encoder_stash_batch_mixed(self._h)
-            if B < 1:
-                raise _lib.HpeError("encoder_stash: no mixed-precision training forward has run")
-            s = CONV_SPECS[idx] if idx >= 0 else None
-            out = self._new_bf16(B, s.hout, s.hout, s.cout) if s else self._new_bf16(B, 56, 56, 64)
-            _lib.check(self.lib.hpe_debug_encoder_stash_mixed(self._h, idx, out.data_ptr(), self._stream()))
-            return out
-        B = self.lib.hpe_debug_encoder_stash_batch(self._h)
-        if B < 1:
-            raise _lib.HpeError("encoder_stash: no training forward has run")
-        s = CONV_SPECS[idx] if idx >= 0 else None
-        out = self._new(B, s.hout, s.hout, s.cout) if s else self._new(B, 56, 56, 64)
-        _lib.check(self.lib.hpe_debug_encoder_stash(self._h, idx, out.data_ptr(), self._stream()))
-        return out
+        return self._stash("stash", "encoder_stash", idx, "frozen", precision)
 
     def mesh_loss(self, seg, verts2d):
         torch = _torch()
@@ -1035,8 +951,7 @@ class HpeEngine(object):
             nn_pix = torch.empty((B, H, W), dtype=torch.int32, device=self.tdev)
             nn_vert = torch.empty((B, P), dtype=torch.int32, device=self.tdev)
         _lib.check(self.lib.hpe_mesh_loss_grad(self._h, seg.data_ptr(), verts2d.data_ptr(), B, H, W, P, out.data_ptr(), grad.data_ptr(),
-                                               nn_pix.data_ptr() if want_neighbours else None,
-                                               nn_vert.data_ptr() if want_neighbours else None, self._stream()))
+                                               _ptr(nn_pix), _ptr(nn_vert), self._stream()))
         return (out[0], grad, nn_pix, nn_vert) if want_neighbours else (out[0], grad)
 
     def val_losses(self, kp_gt, kp2d_stages, seg=None, verts2d_stages=None, out=None):
@@ -1072,10 +987,8 @@ class HpeEngine(object):
         x = _require_cuda_tensor(x, "x")
         B = x.shape[0]
         y = self._new(B, s.hout, s.hout, s.cout)
-        r = None
-        if residual is not None:
-            r = _require_cuda_tensor(residual, "residual").data_ptr()
-        _lib.check(self.lib.hpe_debug_conv(self._h, idx, x.data_ptr(), B, r, int(relu), y.data_ptr(), self._stream()))
+        residual = _FP32.act(residual, "residual", optional=True)
+        _lib.check(self.lib.hpe_debug_conv(self._h, idx, x.data_ptr(), B, _ptr(residual), int(relu), y.data_ptr(), self._stream()))
         return y
 
     def conv_route(self, idx, B, concurrent=False, residual=False, workspace=True):
@@ -1251,13 +1164,11 @@ def kp_loss_backward(kp_gt, kp_pred, grad_loss=None):
     kp_gt = _require_cuda_tensor(kp_gt, "kp_gt")
     kp_pred = _require_cuda_tensor(kp_pred, "kp_pred")
     B, K = kp_gt.shape[0], kp_gt.shape[1]
-    gl = None
     if grad_loss is not None:
         grad_loss = _require_cuda_tensor(grad_loss.reshape(1), "grad_loss")
-        gl = grad_loss.data_ptr()
     out = _torch().empty((B, K, 2), dtype=_torch().float32, device=kp_gt.device)
     with _torch().cuda.device(kp_gt.device):
-        _lib.check(_lib.load().hpe_kp_loss_backward(kp_gt.data_ptr(), kp_pred.data_ptr(), B, K, gl, out.data_ptr(), _cur_stream(kp_gt)))
+        _lib.check(_lib.load().hpe_kp_loss_backward(kp_gt.data_ptr(), kp_pred.data_ptr(), B, K, _ptr(grad_loss), out.data_ptr(), _cur_stream(kp_gt)))
     return out
 
 
