@@ -20,7 +20,7 @@ except ValueError:
 
 from . import critic_spec, regressor_spec, resnet_spec, synthetic  # noqa: F401,E402
 from ._lib import HpeError  # noqa: F401
-from .augment import augment_batch, draw_augmentation, mocap_real, plan_augmentation  # noqa: F401
+from .augment import augment_batch, draw_augmentation, gt3d_real, mocap_real, plan_augmentation, reflect_joints3d, reflect_pose  # noqa: F401
 from .critic_train import CriticTrainer  # noqa: F401
 from . import distributed  # noqa: F401
 from .distributed import Reducer, ShardedPredictor  # noqa: F401
@@ -34,10 +34,11 @@ from .png_encode import encode_png_batch  # noqa: F401
 from .jpeg_encode import encode_jpeg_batch, forward_dct_batch, quant_tables  # noqa: F401
 from . import mat5_lite  # noqa: F401
 from .datasets import create_datasets, create_records, filename_pairs_lsp, filename_pairs_lspe, filename_pairs_mpii, image_record  # noqa: F401
-from .records import (RecordDataset, RecordError, TFRecordWriter, image_example, load_training_batch, mocap_example, parse_example,  # noqa: F401
+from .records import (RecordDataset, RecordError, TFRecordWriter, image_example, load_training_batch, load_training_batch_3d, mocap_example, parse_example,  # noqa: F401
                       parse_image_example, parse_mocap_example, read_tfrecords, serialize_example, write_tfrecords)
 from .metrics import Scores, Scores3D, eval_scores, pose3d_scores, procrustes_align  # noqa: F401
 from .image import get_original, preprocess_batch, preprocess_image  # noqa: F401
+from .ops import Gt3D, joints3d_loss, loss3d_counts, smpl_param_loss  # noqa: F401
 from .ops import critic_gradient_penalty, critic_scores, critic_wgan_loss, generator_critic_loss, kp_reprojection_loss, mesh_reprojection_loss, regressor_thetas, encoder_features  # noqa: F401
 from .optim import KerasAdam  # noqa: F401
 from .predictor import Predictor  # noqa: F401
@@ -46,3 +47,12 @@ from .render import SMPLRenderer  # noqa: F401
 from .smpl import SMPL  # noqa: F401
 from .summary import SummaryWriter, read_events  # noqa: F401
 from .trainer import Trainer  # noqa: F401
+
+
+def __getattr__(name):
+    # the autograd glue imports torch at module level, the package does not: Loss3DFunction is resolved on first use
+    if name == "Loss3DFunction":
+        from .autograd import Loss3DFunction
+
+        return Loss3DFunction
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

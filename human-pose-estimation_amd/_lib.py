@@ -357,6 +357,14 @@ ENCODER_ENTRY = {
 }
 _PROTOS.update({name + "_mixed": _PROTOS[name] for pair in ENCODER_ENTRY.values() for name in pair if name})
 
+# The 3-D supervision extension (include/hpe_loss3d.h, which include/hpe.h includes): a table of its own, bound by load() like the core
+# table; ``declared_symbols`` stays the core list of include/hpe.h, ``loss3d_symbols`` is this header's.
+_PROTOS_LOSS3D = {
+    "hpe_loss3d": (C.c_int, [C.POINTER(C.c_void_p)] * 3 + [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpe_loss3d_backward": (C.c_int, [C.POINTER(C.c_void_p)] * 3 + [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p] +
+                            [C.POINTER(C.c_void_p)] * 3 + [C.c_void_p]),
+}
+
 
 def encoder_symbol(role, batch, suffix=""):
     """the C symbol of ENCODER_ENTRY[role] with (batch) or without batch statistics; suffix "_mixed": its mixed-precision twin"""
@@ -370,7 +378,7 @@ _lib = None
 
 
 def load():
-    """dlopen the in-tree library and bind every symbol of include/hpe.h.  Raises if it is missing."""
+    """dlopen the in-tree library and bind every symbol of include/hpe.h and include/hpe_loss3d.h.  Raises if it is missing."""
     global _lib
     if _lib is not None:
         return _lib
@@ -386,7 +394,7 @@ def load():
     except Exception:  # pragma: no cover - the library itself does not need torch
         pass
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in _PROTOS.items():
+    for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_LOSS3D.items()):
         fn = getattr(lib, name)  # AttributeError here == header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -396,6 +404,11 @@ def load():
 
 def declared_symbols():
     return sorted(_PROTOS)
+
+
+def loss3d_symbols():
+    """the entry points of include/hpe_loss3d.h"""
+    return sorted(_PROTOS_LOSS3D)
 
 
 def check(rc):

@@ -15,6 +15,8 @@ NUM_KP = 19
 TRANS_MAX = 20  # src/config.py:72
 SCALE_RANGE = (0.8, 1.23)  # src/config.py:73-74
 SWAP_INDS = (5, 4, 3, 2, 1, 0, 11, 10, 9, 8, 7, 6, 12, 13, 14, 16, 15, 18, 17)  # flip_image, src/util/data_utils.py:234-235
+SWAP14 = SWAP_INDS[:14]  # the same swap on the 14 joints of the 3-D labels
+PERM24 = (0, 2, 1, 3, 5, 4, 6, 8, 7, 9, 11, 10, 12, 14, 13, 15, 17, 16, 19, 18, 21, 20, 23, 22)  # the SMPL joints' left/right swap
 # HpeAugmentFrame (include/hpe.h) as a numpy record
 TABLE_DTYPE = _lib.record_dtype(_lib.HpeAugmentFrame)
 
@@ -199,3 +201,70 @@ def mocap_real(engine, poses, shapes):
     with torch.no_grad():
         parts = [engine.smpl(theta[lo:lo + mb], want=("joints", "Rs")) for lo in range(0, N, mb)]
     return torch.cat([p["joints"] for p in parts]), shapes, torch.cat([p["Rs"] for p in parts])
+
+
+def reflect_pose(pose72):
+    """The SMPL pose [..., 72] (24 axis-angle vectors) of the body mirrored about the x axis, in the record's own format: joint j takes
+    the vector of joint ``PERM24[j]`` with signs (1, -1, -1).  In rotation space that is M R[PERM24[j]] M with M = diag(-1, 1, 1), the
+    rule hpe_loss3d applies to a flipped row (DESIGN.md "3-D supervision").  Host arrays; applying it twice is the identity."""
+    p = np.asarray(pose72)
+    if p.shape[-1] != 72:
+        raise ValueError("pose must be [..., 72], got %s" % (list(p.shape),))
+    v = p.reshape(p.shape[:-1] + (24, 3))[..., list(PERM24), :] * np.asarray((1, -1, -1), p.dtype)
+    return np.ascontiguousarray(v.reshape(p.shape))
+
+
+def reflect_joints3d(j14):
+    """The 3-D joints [..., 14, 3] of the body mirrored about the x axis: joint k takes (-x, y, z) of joint ``SWAP14[k]``.  Host arrays;
+    applying it twice is the identity."""
+    j = np.asarray(j14)
+    if j.shape[-2:] != (14, 3):
+        raise ValueError("joints must be [..., 14, 3], got %s" % (list(j.shape),))
+    return np.ascontiguousarray(j[..., list(SWAP14), :] * np.asarray((-1, 1, 1), j.dtype))
+
+
+def gt3d_real(engine, records, flip=None):
+    """The 3-D ground truth of a batch as the 3-D losses take it (``ops.Gt3D``; DESIGN.md "3-D supervision"), beside ``mocap_real``.
+    records: parsed image records (``parse_image_example`` dicts; 'gt3d' [14,3], 'pose' [72] and 'shape' [10] are each optional per
+    record), or one dict of stacked host arrays under those keys (a key that is absent is absent for every row).  flip: the
+    augmentation's draw (bool [B], host or device; None: no flips) -- the labels stay UNFLIPPED, the loss mirrors them.
+    Absent fields are zeros.  w_joints = 1 where 'gt3d' is present; w_smpl = 1 where 'pose' and 'shape' both are; Rs come from ONE pass
+    of ``engine.smpl`` over the ground-truth theta (chunks of ``max_batch`` rows, no gradient), exactly as ``mocap_real`` makes them;
+    a row with 'pose' and 'shape' but no 'gt3d' takes its joints from that same pass and w_joints = 1."""
+    import torch
+
+    if isinstance(records, dict):
+        B = len(next(iter(records.values()))) if records else 0
+        records = [{k: v[i] for k, v in records.items()} for i in range(B)]
+    B = len(records)
+    if B < 1:
+        raise ValueError("records is empty")
+    j, pose, shape = np.zeros((B, 14, 3), np.float32), np.zeros((B, 72), np.float32), np.zeros((B, 10), np.float32)
+    has_j, has_s = np.zeros(B, bool), np.zeros(B, bool)
+    for i, r in enumerate(records):
+        if r.get("gt3d") is not None:
+            j[i], has_j[i] = np.asarray(r["gt3d"], np.float32).reshape(14, 3), True
+        if r.get("pose") is not None and r.get("shape") is not None:
+            pose[i], shape[i], has_s[i] = np.asarray(r["pose"], np.float32).reshape(72), np.asarray(r["shape"], np.float32).reshape(10), True
+    dev = engine.tdev
+    joints, shapes = torch.from_numpy(j).to(dev), torch.from_numpy(shape).to(dev)
+    if has_s.any():
+        cam = np.zeros((B, 3), np.float32)  # the camera does not enter joints or Rs
+        cam[:, 0] = 1.0
+        theta = torch.from_numpy(np.concatenate([cam, pose, shape], 1)).to(dev)
+        mb = engine.max_batch
+        with torch.no_grad():
+            parts = [engine.smpl(theta[lo:lo + mb].contiguous(), want=("joints", "Rs")) for lo in range(0, B, mb)]
+        Rs = torch.cat([p["Rs"] for p in parts])
+        from_smpl = has_s & ~has_j
+        if from_smpl.any():
+            joints = torch.where(torch.from_numpy(from_smpl).to(dev)[:, None, None], torch.cat([p["joints"] for p in parts])[:, :14], joints)
+            has_j = has_j | from_smpl
+    else:
+        Rs = torch.zeros((B, 24, 3, 3), dtype=torch.float32, device=dev)
+    if flip is not None:
+        flip = torch.as_tensor(np.asarray(flip.cpu()) if hasattr(flip, "cpu") else np.asarray(flip)).reshape(B).to(torch.bool).to(dev)
+    from .ops import Gt3D
+
+    return Gt3D(joints.contiguous(), Rs.contiguous(), shapes, torch.from_numpy(has_j.astype(np.float32)).to(dev),
+                torch.from_numpy(has_s.astype(np.float32)).to(dev), flip)

@@ -69,6 +69,40 @@ class KpLossShareFunction(torch.autograd.Function):
         return None, _engine.kp_loss_backward(kp_gt, kp_pred, grad_loss.to(torch.float32) * ratio), None
 
 
+class Loss3DFunction(torch.autograd.Function):
+    """(L_joints, L_smpl) = the 3-D supervision losses of one stage (DESIGN.md "3-D supervision"; hpe_loss3d), differentiable in joints
+    [B,K,3], betas [B,10] and Rs [B,24,3,3] (hpe_loss3d_backward; stateless, so only the inputs are saved).  ``gt``: ``ops.Gt3D``.
+    ``counts``: None for this batch's own (cnt_j, cnt_s), or those two as a [2] CUDA tensor already summed over the ranks
+    (``loss3d_counts`` and one all-reduce): the losses are then this rank's SHARES, which add up to the losses of the global batch, 0
+    where nothing is supervised anywhere.  ``parts``: this stage's row [5] of a ``loss3d_parts`` launch the caller made for several
+    stages at once (None: launched here).  The backward scales by grad_loss * 0.5 / count on the device; nothing reads it."""
+
+    @staticmethod
+    def forward(ctx, joints, betas, Rs, gt, counts=None, parts=None):
+        j, b, R = joints.detach(), betas.detach(), Rs.detach()
+        if parts is None:
+            parts = _engine.loss3d_parts(j, b, R, gt)[0]
+        cnt = parts[3:5] if counts is None else counts.detach().reshape(2).to(torch.float32)
+        den = torch.clamp(cnt, min=1.0)
+        zero = torch.zeros_like(den)
+        ctx.gt = gt
+        ctx.save_for_backward(j, b, R, torch.where(cnt > 0, 0.5 / den, zero))
+        loss = torch.where(cnt > 0, 0.5 * torch.stack([parts[0], parts[1] + parts[2]]) / den, zero)
+        return loss[0], loss[1]
+
+    @staticmethod
+    def backward(ctx, grad_joints_loss, grad_smpl_loss):
+        j, b, R, half = ctx.saved_tensors
+        names = ("joints", "betas", "Rs")
+        want = tuple(k for k, need in zip(names, ctx.needs_input_grad[:3]) if need)
+        if not want:
+            return (None,) * 6
+        scale = [half[i : i + 1] * g.to(torch.float32) if g is not None else torch.zeros_like(half[i : i + 1])
+                 for i, g in enumerate((grad_joints_loss, grad_smpl_loss))]
+        g = _engine.loss3d_backward(j, b, R, ctx.gt, scale[0], scale[1], want=want)
+        return tuple(g.get(k) for k in names) + (None, None, None)
+
+
 class MeshLossFunction(torch.autograd.Function):
     """loss = mesh_reprojection_loss(seg, verts2d), differentiable in verts2d: the forward is ONE hpe_mesh_loss_grad call, which
     returns the loss and d loss / d verts2d from the same pair of searches; the backward scales the saved gradient."""

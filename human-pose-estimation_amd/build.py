@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libhpe_hip.so")
-SOURCES = ["conv_gemm.hip", "conv_gemm_f32s.hip", "conv_stream_f32s.hip", "conv_stream_chain_f32s.hip", "conv_gemm_bf16.hip", "conv_gemm_bf16_p8.hip", "conv_chain_bf16.hip", "conv_chain_f32.hip", "conv3_halo_bf16.hip", "conv_wino.hip", "conv_wino4.hip", "stem_fused.hip", "encoder_ops.hip", "smpl.hip", "losses.hip", "prepost.hip", "render.hip", "hpe_plan.hip", "hpe_finalize.hip", "hpe_encoder.hip", "hpe_api.hip", "hpe_render_api.hip", "smpl_bwd.hip", "critic.hip", "critic_train.hip", "regressor_train.hip", "augment.hip", "encoder_train.hip", "encoder_grad.hip", "encoder_grad_bf16.hip", "encoder_repack.hip", "encoder_bn.hip", "encoder_bn_bf16.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "jpeg_huffman_enc.hip", "jpeg_encode.hip", "png_decode.hip", "png_encode.hip", "draw.hip", "adam.hip", "eval_scores.hip", "pose3d_scores.hip"]
+SOURCES = ["conv_gemm.hip", "conv_gemm_f32s.hip", "conv_stream_f32s.hip", "conv_stream_chain_f32s.hip", "conv_gemm_bf16.hip", "conv_gemm_bf16_p8.hip", "conv_chain_bf16.hip", "conv_chain_f32.hip", "conv3_halo_bf16.hip", "conv_wino.hip", "conv_wino4.hip", "stem_fused.hip", "encoder_ops.hip", "smpl.hip", "losses.hip", "prepost.hip", "render.hip", "hpe_plan.hip", "hpe_finalize.hip", "hpe_encoder.hip", "hpe_api.hip", "hpe_render_api.hip", "smpl_bwd.hip", "critic.hip", "critic_train.hip", "regressor_train.hip", "augment.hip", "encoder_train.hip", "encoder_grad.hip", "encoder_grad_bf16.hip", "encoder_repack.hip", "encoder_bn.hip", "encoder_bn_bf16.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "jpeg_huffman_enc.hip", "jpeg_encode.hip", "png_decode.hip", "png_encode.hip", "draw.hip", "adam.hip", "eval_scores.hip", "pose3d_scores.hip", "loss3d.hip"]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fno-fast-math"]
 
 
@@ -27,7 +27,7 @@ def _hipcc():
 
 
 def _deps():
-    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", "hpe.h")]
+    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", h) for h in ("hpe.h", "hpe_loss3d.h")]
 
 
 def _obj_stale(src, obj):
@@ -55,7 +55,7 @@ def _stale():
     if built_flags() != _flags_now():
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "hpe.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h) for h in ("hpe.h", "hpe_loss3d.h")]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

@@ -1181,3 +1181,93 @@ def kp_loss_parts(kp_gt, kp_pred):
     with _torch().cuda.device(kp_gt.device):
         _lib.check(_lib.load().hpe_kp_loss(kp_gt.data_ptr(), kp_pred.data_ptr(), B, K, out.data_ptr(), _cur_stream(kp_gt)))
     return out[:3]
+
+
+def _loss3d_call(symbol, joints, betas, Rs, gt, tail):
+    """The one body of the two 3-D loss calls (hpe_loss3d, hpe_loss3d_backward): the predictions, per-stage lists of joints [B,K,3],
+    betas [B,10] (a ``theta[:, 75:]`` view is read in place) and Rs [B,24,3,3] (a single tensor each: one stage), and the ground
+    truth ``gt`` (``ops.Gt3D``) checked once; ``tail(n, B, K, dev)`` -> (what to return, the call's trailing arguments)."""
+    torch = _torch()
+    as_list = lambda x: [x] if isinstance(x, torch.Tensor) else list(x)  # noqa: E731
+    joints, betas, Rs = as_list(joints), as_list(betas), as_list(Rs)
+    n = len(joints)
+    if not 1 <= n <= 16 or len(betas) != n or len(Rs) != n:
+        raise ValueError("joints, betas and Rs must be one tensor each or lists of the same length in [1, 16]")
+    gj = _require_cuda_tensor(gt.joints, "gt.joints", (14, 3))
+    gR = _require_cuda_tensor(gt.Rs, "gt.Rs", (24, 3, 3))
+    gs = _require_cuda_tensor(gt.shape, "gt.shape", (10,))
+    wj, ws = _require_cuda_tensor(gt.w_joints, "gt.w_joints"), _require_cuda_tensor(gt.w_smpl, "gt.w_smpl")
+    B, dev = gj.shape[0], gj.device
+    flip = gt.flip
+    if flip is not None:
+        if not isinstance(flip, torch.Tensor) or not flip.is_cuda or flip.dtype not in (torch.uint8, torch.bool) or tuple(flip.shape) != (B,):
+            raise ValueError("gt.flip must be a uint8 or bool CUDA tensor [%d], or None" % B)
+        flip = flip.to(torch.uint8).contiguous()
+    if B < 1 or gR.shape[0] != B or gs.shape[0] != B or tuple(wj.shape) != (B,) or tuple(ws.shape) != (B,):
+        raise ValueError("gt must hold joints [B,14,3], Rs [B,24,3,3], shape [B,10], w_joints [B] and w_smpl [B] with one B >= 1")
+    joints = [_require_cuda_tensor(t.detach(), "joints") for t in joints]
+    Rs = [_require_cuda_tensor(t.detach(), "Rs", (24, 3, 3)) for t in Rs]
+    K = joints[0].shape[1] if joints[0].dim() == 3 else 0
+    if any(t.dim() != 3 or tuple(t.shape) != (B, K, 3) for t in joints) or not 14 <= K <= 24:
+        raise ValueError("every stage's joints must be [%d,K,3] with one 14 <= K <= 24" % B)
+    if any(t.shape[0] != B for t in Rs):
+        raise ValueError("every stage's Rs must be [%d,24,3,3]" % B)
+    bs = [b.detach() for b in betas]
+    if any(not b.is_cuda or b.dtype != torch.float32 or tuple(b.shape) != (B, 10) for b in bs):
+        raise ValueError("every stage's betas must be a float32 CUDA tensor [%d,10]" % B)
+    strides = {b.stride(0) for b in bs} if B > 1 else {10}
+    if any(b.stride(1) != 1 for b in bs) or len(strides) != 1 or min(strides) < 10:  # the call has one row stride for all stages
+        bs, strides = [b.contiguous() for b in bs], {10}
+    stride = strides.pop()
+    if any(t.device != dev for t in joints + Rs + bs + [gR, gs, wj, ws] + ([flip] if flip is not None else [])):
+        raise ValueError("the predictions and gt must live on one device")
+    ptrs = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
+    with torch.cuda.device(dev):
+        result, args = tail(n, B, K, dev)
+        _lib.check(getattr(_lib.load(), symbol)(ptrs(joints), ptrs(Rs), ptrs(bs), stride, gj.data_ptr(), gR.data_ptr(), gs.data_ptr(), wj.data_ptr(),
+                                                ws.data_ptr(), _ptr(flip), n, B, K, *args, _cur_stream(gj)))
+    return result
+
+
+def loss3d_parts(joints, betas, Rs, gt, want_per_image=False):
+    """hpe_loss3d for all the stages given in ONE launch -> parts [n_stage,5] = (num_j, num_pose, num_shape, cnt_j, cnt_s), the
+    numerators and counts of the joint and the SMPL-parameter loss (DESIGN.md "3-D supervision"); want_per_image=True returns (parts,
+    per_image [n_stage,B,3], each row's unweighted sums of squares: joints, rotations, shape; 0 where the term's weight is 0)."""
+
+    def tail(n, B, K, dev):
+        parts = _torch().empty((n, 5), dtype=_torch().float32, device=dev)
+        per = _torch().empty((n, B, 3), dtype=_torch().float32, device=dev) if want_per_image else None
+        return ((parts, per) if want_per_image else parts), (parts.data_ptr(), _ptr(per))
+
+    return _loss3d_call("hpe_loss3d", joints, betas, Rs, gt, tail)
+
+
+def loss3d_backward(joints, betas, Rs, gt, scale_j=None, scale_s=None, want=("joints", "betas", "Rs")):
+    """hpe_loss3d_backward: the gradient of the two losses with respect to the predictions named in ``want`` (among joints, betas, Rs)
+    -> dict of per-stage lists (of tensors, where the predictions were single tensors).  scale_j / scale_s: CUDA float tensors of one
+    element per stage, grad_loss * 0.5 / count with the local or the global count; scale_j is needed for 'joints', scale_s for the
+    other two.  Nothing reads the device."""
+    torch = _torch()
+    names = ("joints", "Rs", "betas")  # the ABI's order
+    if not want or any(k not in names for k in want):
+        raise ValueError("want must name some of %s, got %r" % (sorted(names), tuple(want)))
+    single = isinstance(joints, torch.Tensor)
+
+    def tail(n, B, K, dev):
+        def scale(t, name, needed):
+            if not needed:
+                return None
+            if t is None:
+                raise ValueError("%s is needed for %s" % (name, "'joints'" if name == "scale_j" else "'betas' and 'Rs'"))
+            t = _require_cuda_tensor(t.detach().reshape(-1), name)
+            if t.numel() != n or t.device != dev:
+                raise ValueError("%s must hold one float per stage (%d) on %s" % (name, n, dev))
+            return t
+
+        sj, ss = scale(scale_j, "scale_j", "joints" in want), scale(scale_s, "scale_s", "betas" in want or "Rs" in want)
+        shapes = {"joints": (B, K, 3), "Rs": (B, 24, 3, 3), "betas": (B, 10)}
+        out = {k: [torch.empty(shapes[k], dtype=torch.float32, device=dev) for _ in range(n)] for k in want}
+        arrs = [(C.c_void_p * n)(*[t.data_ptr() for t in out[k]]) if k in out else None for k in names]
+        return ({k: v[0] if single else v for k, v in out.items()}), (_ptr(sj), _ptr(ss), *arrs)
+
+    return _loss3d_call("hpe_loss3d_backward", joints, betas, Rs, gt, tail)

@@ -15,11 +15,16 @@ rank's rows of a batch of G spread across the ranks.  Every loss term is the ran
 the visible count of all ranks (all-reduced on the device before the forward), the mesh sum as it is, the critic's column sums over G --
 so that after ``loss.backward()`` ONE sum per flat gradient over the ranks is the gradient of the global batch, which every rank then
 steps with; BatchNorm takes its statistics over the G images (``HpeEngine.set_encoder_reduce``) and the moving statistics follow
-those.  The reported losses are the global values, from one packed all-reduce per step."""
+those.  The reported losses are the global values, from one packed all-reduce per step.
+
+3-D supervision (DESIGN.md "3-D supervision"): ``step(..., gt3d=)`` with ``joints3d_loss_weight`` / ``smpl_loss_weight`` above 0 adds the
+L2 loss on the pelvis-aligned 3-D joints and the L2 loss on the rotations and the shape (hpe_loss3d: one launch for all stages;
+hpe_loss3d_backward for the last), masked per row; data-parallel, their two counts travel with the keypoint count."""
 from __future__ import annotations
 
-from .ops import (encoder_features, generator_critic_loss, kp_reprojection_loss, kp_reprojection_loss_share, kp_visible_count,
-                  mesh_reprojection_loss, regressor_thetas)
+from . import engine as _engine
+from .ops import (encoder_features, generator_critic_loss, kp_reprojection_loss, kp_reprojection_loss_share, kp_visible_count, loss3d,
+                  loss3d_counts, mesh_reprojection_loss, regressor_thetas)
 
 GENERATOR_LR = 0.0001  # the reference's generator_lr (src/config.py:64-69)
 ADAM_EPS = 1e-7  # tf.keras.optimizers.Adam's epsilon
@@ -29,7 +34,7 @@ class GeneratorTrainer(object):
     def __init__(self, engine, lr=GENERATOR_LR, betas=(0.9, 0.999), eps=ADAM_EPS, kpr_loss_weight=60.0, mr_loss_weight=0.001,
                  critic_loss_weight=0.01, dropout=0.5, generator=None, train_encoder=False, encoder_lr=None, encoder_bn="frozen",
                  bn_momentum=0.99, bn_unbiased=True, optimizer="torch", reducer=None, global_batch=None, encoder_precision="fp32",
-                 clipnorm=None, skip_nonfinite=False):
+                 clipnorm=None, skip_nonfinite=False, joints3d_loss_weight=0.0, smpl_loss_weight=0.0):
         """engine: a finalized HpeEngine with a regressor, mean theta and SMPL (and a critic, for the critic term).  ``params`` is the
         flat parameter tensor (regressor_spec.flat_layout) the optimiser owns; ``regressor_spec.flat_to_params(params)`` gives the
         dict ``load_regressor`` / ``load_mean_theta`` take.  generator: the torch.Generator of the dropout draws.  train_encoder: also
@@ -50,7 +55,8 @@ class GeneratorTrainer(object):
         (``optimizer="keras"`` only): the guarded step of ``KerasAdam`` (global-norm clipping over the tensors stepped; a step with a
         non-finite gradient is undone as a whole: both flat tensors, the moments, the step count and ``encoder_stats`` keep their
         bits), decided on the device from per-layer statistics taken after the data-parallel sum, so every rank decides alike.  The
-        result of ``step`` then has ``grad_norm`` and ``step_applied`` (0-dim device tensors)."""
+        result of ``step`` then has ``grad_norm`` and ``step_applied`` (0-dim device tensors).  joints3d_loss_weight /
+        smpl_loss_weight: the weights of the two 3-D supervision terms of ``step(..., gt3d=)``; 0, the default, leaves a term out."""
         import torch
 
         if not 0.0 <= dropout < 1.0:
@@ -62,6 +68,9 @@ class GeneratorTrainer(object):
                 raise ValueError("reducer= needs global_batch, the rows of all ranks together")
             self.global_batch = int(global_batch)
         self.kpr_loss_weight, self.mr_loss_weight, self.critic_loss_weight = float(kpr_loss_weight), float(mr_loss_weight), float(critic_loss_weight)
+        self.joints3d_loss_weight, self.smpl_loss_weight = float(joints3d_loss_weight), float(smpl_loss_weight)
+        if self.joints3d_loss_weight < 0.0 or self.smpl_loss_weight < 0.0:
+            raise ValueError("joints3d_loss_weight and smpl_loss_weight must be >= 0")
         self.dropout = float(dropout)
         self.generator = generator
         self.params = engine.regressor_params().requires_grad_(True)
@@ -129,10 +138,12 @@ class GeneratorTrainer(object):
         if enc:
             self.reducer.sum_grad(self.encoder_params.grad)
 
-    def step(self, images_or_features, kp_gt, seg_gts=None, use_critic=None, drop="draw"):
+    def step(self, images_or_features, kp_gt, seg_gts=None, use_critic=None, drop="draw", gt3d=None):
         """One generator update.  images_or_features: images [B,224,224,3] (the encoder runs without gradient) or features [B,2048];
         kp_gt [B,K,3] (x, y, visibility); seg_gts [B,H,W(,1)] adds the mesh reprojection loss; use_critic (default: the engine has a
-        critic) adds the critic term.  drop: the multipliers [2,B,1024] of this step, None for none, "draw" to draw them.
+        critic) adds the critic term.  drop: the multipliers [2,B,1024] of this step, None for none, "draw" to draw them.  gt3d: the
+        batch's ``ops.Gt3D`` (``augment.gt3d_real``); each 3-D term whose weight is above 0 then joins the loss, and the result gains
+        joints3d_losses / smpl_param_losses (lists over the stages, weighted).  None, or both weights 0: the step without them.
         -> the reference's result keys: kpr_losses, mr_losses, generator_critic_losses (lists over the stages, already weighted, 0-dim
         device tensors; the LAST stage's terms are what is minimised, src/trainer.py:487-496), pred_keypoints, generated_cams (last
         stage), thetas (list over the stages: what CriticTrainer.step_from_thetas takes), and grad_features [B,2048].  Nothing reads
@@ -161,16 +172,27 @@ class GeneratorTrainer(object):
         if red is not None:
             if B > G:
                 raise ValueError("this rank's %d rows exceed global_batch %d" % (B, G))
-            count = red.sum_block(kp_visible_count(kp_gt))  # 2 * #visible of all ranks, before the forward; stays on the device
-        kpr, mr, gc = [], [], []
+        use3d = gt3d is not None and (self.joints3d_loss_weight > 0.0 or self.smpl_loss_weight > 0.0)
+        if use3d and gt3d.joints.shape[0] != B:
+            raise ValueError("gt3d holds %d rows, the batch %d" % (gt3d.joints.shape[0], B))
+        counts3d = None
+        if red is not None:
+            if use3d:  # the two 3-D counts travel with the keypoint count: one collective, three numbers
+                block = red.sum_block(torch.cat([kp_visible_count(kp_gt), loss3d_counts(gt3d)]))
+                count, counts3d = block[:1], block[1:3]
+            else:
+                count = red.sum_block(kp_visible_count(kp_gt))  # 2 * #visible of all ranks, before the forward; stays on the device
+        kpr, mr, gc, j3, sp = [], [], [], [], []
         # kp2d / verts2d: batch_orth_proj_idrot / reproject_vertices of the stage, as outputs of the one hpe_smpl call (and of its backward)
         want = ("kp2d", "joints", "Rs") + (("verts2d",) if seg_gts is not None else ())
         loss = pred_kp = None
+        outs = []
         for i in range(S):
             last = i == S - 1
             with torch.set_grad_enabled(last):
                 th = thetas[i] if last else thetas[i].detach()
                 o = self._smpl(th, want)
+                outs.append((o["joints"], th[:, 75:], o["Rs"]))
                 kp = o["kp2d"]
                 kpr.append(self.kpr_loss_weight * (kp_reprojection_loss(kp_gt, kp) if red is None else kp_reprojection_loss_share(kp_gt, kp, count)))
                 if seg_gts is not None:
@@ -180,6 +202,16 @@ class GeneratorTrainer(object):
                 if last:
                     pred_kp = kp.detach()
                     loss = kpr[-1] + (mr[-1] if mr else 0.0) + (gc[-1] if gc else 0.0)
+        if use3d:  # ONE forward launch for all stages; the last stage's row carries the gradient (hpe_loss3d_backward)
+            parts = _engine.loss3d_parts(*[[o[k] for o in outs] for k in range(3)], gt3d)
+            for i in range(S):
+                with torch.set_grad_enabled(i == S - 1):
+                    lj, ls = loss3d(*outs[i], gt3d, counts3d, parts[i])
+                if self.joints3d_loss_weight > 0.0:
+                    j3.append(self.joints3d_loss_weight * lj)
+                if self.smpl_loss_weight > 0.0:
+                    sp.append(self.smpl_loss_weight * ls)
+            loss = loss + (j3[-1] if j3 else 0.0) + (sp[-1] if sp else 0.0)
         if self.keras:
             self.optimizer.zero_grad()
             loss.backward()
@@ -207,11 +239,16 @@ class GeneratorTrainer(object):
                 eng.set_encoder_stats_dev(self.encoder_stats)
         det = lambda ts: [t.detach() for t in ts]  # noqa: E731
         if red is not None:  # the ranks' shares into the losses of the global batch: one packed all-reduce for all of them
-            block = red.sum_block(torch.stack([t.detach().reshape(()) for t in kpr + mr + gc]))
-            kpr, mr, gc = list(block[:len(kpr)]), list(block[len(kpr):len(kpr) + len(mr)]), list(block[len(kpr) + len(mr):])
+            block = red.sum_block(torch.stack([t.detach().reshape(()) for t in kpr + mr + gc + j3 + sp]))
+            cut = [0]
+            for ts in (kpr, mr, gc, j3, sp):
+                cut.append(cut[-1] + len(ts))
+            kpr, mr, gc, j3, sp = (list(block[lo:hi]) for lo, hi in zip(cut, cut[1:]))
         out = {"kpr_losses": det(kpr), "mr_losses": det(mr), "generator_critic_losses": det(gc), "pred_keypoints": pred_kp,
                "generated_cams": thetas[S - 1, :, :3].detach(), "thetas": [thetas[i].detach() for i in range(S)],
                "grad_features": features.grad}
+        if use3d:
+            out["joints3d_losses"], out["smpl_param_losses"] = det(j3), det(sp)
         if self.guarded:  # copies: the guard block is the next step's too
             out["grad_norm"], out["step_applied"] = self.optimizer.grad_norm.clone(), self.optimizer.step_applied.clone()
         return out

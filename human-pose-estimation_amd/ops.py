@@ -2,6 +2,8 @@
 HIP-backed (BASELINE config 5)."""
 from __future__ import annotations
 
+import collections
+
 from . import engine as _engine
 
 
@@ -44,6 +46,46 @@ def kp_reprojection_loss_share(kp_gt, kp_pred, global_count):
 
         return KpLossShareFunction.apply(kp_gt, kp_pred, global_count)
     return kp_loss_share(_engine.kp_loss_parts(kp_gt, kp_pred)[0], global_count)
+
+
+class Gt3D(collections.namedtuple("Gt3D", "joints Rs shape w_joints w_smpl flip")):
+    """The 3-D ground truth of a batch as the 3-D losses take it (DESIGN.md "3-D supervision"; built by ``augment.gt3d_real``), all CUDA
+    tensors: joints float32 [B,14,3], Rs float32 [B,24,3,3] (``engine.smpl``'s rotations of the ground-truth theta), shape float32
+    [B,10], the row weights w_joints [B] and w_smpl [B] (0: the row is not supervised by that term, and its labels are not read), and
+    flip uint8 or bool [B] (None: no flips): the labels are UNFLIPPED, the kernel mirrors those of a flipped row."""
+    __slots__ = ()
+
+    def rows(self, lo, hi):
+        """the ground truth of rows lo .. hi - 1"""
+        return Gt3D(*[None if t is None else t[lo:hi] for t in self])
+
+
+def loss3d_counts(gt):
+    """(42 * #rows with w_joints != 0, 226 * #rows with w_smpl != 0) of ``gt`` as a [2] CUDA tensor (hpe_loss3d's own counts): what a
+    data-parallel caller sums over the ranks BEFORE the forward, so that every rank divides by the counts of the global batch"""
+    return _engine.loss3d_parts(gt.joints, gt.shape, gt.Rs, gt)[0, 3:5].clone()
+
+
+def loss3d(joints, betas, Rs, gt, counts=None, parts=None):
+    """-> (joints3d_loss, smpl_param_loss) of one stage from one hpe_loss3d launch (``Loss3DFunction``)"""
+    from .autograd import Loss3DFunction
+
+    return Loss3DFunction.apply(joints, betas, Rs, gt, counts, parts)
+
+
+def joints3d_loss(joints, gt, counts=None):
+    """0.5 * sum_i w_i sum_k |e_ik|^2 / (42 * #supervised rows): the L2 loss on the first 14 joints of joints [B,K,3] against
+    ``gt.joints``, both relative to their pelvis (the midpoint of the hips, joints 2 and 3), over the rows with ``gt.w_joints`` != 0; 0
+    where there is none.  counts: ``loss3d_counts`` summed over the ranks, for this rank's share.  Differentiable in joints
+    (hpe_loss3d_backward, the derivative of the alignment included)."""
+    return loss3d(joints, gt.shape, gt.Rs, gt, counts)[0]  # the SMPL term of the same launch compares gt with itself and is dropped
+
+
+def smpl_param_loss(betas, Rs, gt, counts=None):
+    """0.5 * sum_i w_i (|Rs_i - R_i|_F^2 + |betas_i - shape_i|^2) / (226 * #supervised rows): the L2 loss on the 24 rotation matrices
+    Rs [B,24,3,3] and the shape betas [B,10] (a ``theta[:, 75:]`` view is read in place) over the rows with ``gt.w_smpl`` != 0; 0
+    where there is none.  counts as ``joints3d_loss``.  Differentiable in betas and Rs."""
+    return loss3d(gt.joints, betas, Rs, gt, counts)[1]
 
 
 def critic_term_share(scores, global_rows):

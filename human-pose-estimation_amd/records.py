@@ -326,3 +326,21 @@ def load_training_batch(records, draws=None, generator=None, threads=None, **aug
     kp = np.stack([r["kp"] for r in recs]).astype(np.float32)
     centers = np.stack([np.asarray(r["center"]) for r in recs]).astype(np.int32)
     return augment_batch(frames, segs, kp, centers, draws=draws, generator=generator, **augment_args)
+
+
+def load_training_batch_3d(records, engine, draws=None, generator=None, threads=None, **augment_args):
+    """``load_training_batch`` with the records' 3-D ground truth: -> (images, seg_gts, kp_gt, gt), gt the ``ops.Gt3D`` of
+    ``augment.gt3d_real(engine, records, draws["flip"])``.  The draws are made HERE when ``draws`` is None, with the generator and the
+    ``trans_max`` / ``scale_range`` that ``augment_batch`` would use, so the first three outputs are bit-identical to
+    ``load_training_batch`` from the same generator state and the generator is left as it would be; the labels in ``gt`` stay
+    unflipped, the flip draw travels with them and the loss mirrors them."""
+    from .augment import SCALE_RANGE, TRANS_MAX, draw_augmentation, gt3d_real
+
+    recs = [parse_image_example(r) if isinstance(r, (bytes, bytearray, memoryview)) else r for r in records]
+    if not recs:
+        raise ValueError("records is empty")
+    if draws is None:
+        draws = draw_augmentation(len(recs), generator=generator, trans_max=augment_args.get("trans_max", TRANS_MAX),
+                                  scale_range=augment_args.get("scale_range", SCALE_RANGE))
+    images, seg_gts, kp_gt = load_training_batch(recs, draws=draws, threads=threads, **augment_args)
+    return images, seg_gts, kp_gt, gt3d_real(engine, recs, draws["flip"])

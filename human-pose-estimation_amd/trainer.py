@@ -172,7 +172,8 @@ class Trainer(object):
         ``kpr_loss_weight``, ``mr_loss_weight``, ``critic_loss_weight``, ``use_kpr_loss``, ``use_mesh_repro_loss``, ``encoder_only``,
         ``use_validation``, ``validation_step_size``, ``train_from_checkpoint``, ``checkpoint_dir``, ``encoder_precision`` ("fp32", the
         default, or "mixed": the encoder's walks in bf16 with fp32 master weights, BatchNorm arithmetic in fp32; checkpoints are the
-        same either way), plus what ``Predictor`` reads (the
+        same either way), ``joints3d_loss_weight`` and ``smpl_loss_weight`` (both 0 by default: no 3-D supervision; above 0 the records'
+        ``gt3d`` / ``pose`` / ``shape`` are trained on, DESIGN.md "3-D supervision"), plus what ``Predictor`` reads (the
         SMPL model, the mean parameters and the starting weights: ``predictor_args`` are passed on).  dataset / val_dataset:
         ``RecordDataset``s of image records (batch size ``config.batch_size``) or any iterable of what ``load_training_batch`` takes: the
         reference's image records, whose ``image/encoded`` and ``image/seg_gt`` are JPEG or PNG streams (lsp_train / lsp_val masks and
@@ -208,6 +209,9 @@ class Trainer(object):
         self.generator_lr, self.critic_lr = float(g("generator_lr", GENERATOR_LR)), float(g("critic_lr", CRITIC_LR))
         self.kpr_loss_weight, self.mr_loss_weight = float(g("kpr_loss_weight", 60.0)), float(g("mr_loss_weight", 0.001))
         self.critic_loss_weight = float(g("critic_loss_weight", 0.01))
+        # 3-D supervision (DESIGN.md "3-D supervision"): off by default; above 0 the records' gt3d / pose / shape are loaded and trained on
+        self.joints3d_loss_weight, self.smpl_loss_weight = float(g("joints3d_loss_weight", 0.0)), float(g("smpl_loss_weight", 0.0))
+        self.use_3d_loss = self.joints3d_loss_weight > 0.0 or self.smpl_loss_weight > 0.0
         self.use_kpr_loss, self.use_mesh_repro_loss = bool(g("use_kpr_loss", True)), bool(g("use_mesh_repro_loss", False))
         self.encoder_only, self.use_validation = bool(g("encoder_only", False)), bool(g("use_validation", True))
         self.val_step_size = int(g("validation_step_size", 50))
@@ -257,7 +261,8 @@ class Trainer(object):
 
         self.generator = GeneratorTrainer(eng, lr=self.generator_lr, kpr_loss_weight=self.kpr_loss_weight, mr_loss_weight=self.mr_loss_weight,
                                           critic_loss_weight=self.critic_loss_weight, generator=generator, train_encoder=True,
-                                          encoder_bn="batch", optimizer="keras", encoder_precision=self.encoder_precision, **dp_gen,
+                                          encoder_bn="batch", optimizer="keras", encoder_precision=self.encoder_precision,
+                                          joints3d_loss_weight=self.joints3d_loss_weight, smpl_loss_weight=self.smpl_loss_weight, **dp_gen,
                                           **guard(self.generator_clipnorm))
         if not self.encoder_only:
             self.critic = CriticTrainer(eng, lr=self.critic_lr, generator=generator, optimizer="keras", **dp, **guard(self.critic_clipnorm))
@@ -314,20 +319,24 @@ class Trainer(object):
                 norms[n] = per_layer[i]
 
     # ------------------------------------------------------------------ steps
-    def train_step(self, images, seg_gts, kp_gt, joints=None, shapes=None, Rs=None, drop="draw", interp=None):
+    def train_step(self, images, seg_gts, kp_gt, joints=None, shapes=None, Rs=None, drop="draw", interp=None, gt3d=None):
         """One update of the generator, then one of the critic on the thetas it produced (src/trainer.py:383-583).  images
         [B,224,224,3], seg_gts [B,224,224(,1)], kp_gt [B,19,3]; joints / shapes / Rs: the real triple of ``mocap_real`` (B * num_stage
-        or B rows), unused with ``encoder_only``.  drop / interp: fixed dropout multipliers and interpolation draws (tests).
+        or B rows), unused with ``encoder_only``.  drop / interp: fixed dropout multipliers and interpolation draws (tests).  gt3d: the
+        batch's ``ops.Gt3D``; with a 3-D weight above 0 the result gains joints3d_losses and smpl_param_losses.
         -> the reference's result keys: kpr_losses, mr_losses (with ``use_mesh_repro_loss``), pred_keypoints, generated_cams and, unless
         ``encoder_only``, generator_critic_losses, critic_penalty, critic_network_loss; plus ``thetas``; with ``do_bone_evaluation``
         also avg_total_bone_length_pred (all stages' joints) and avg_total_bone_length_gt (``joints``).  Nothing reads the device."""
         if self.generator is None:
             raise RuntimeError("this Trainer was built with validation_only")
-        r = self.generator.step(images, kp_gt, seg_gts if self.use_mesh_repro_loss else None, use_critic=not self.encoder_only, drop=drop)
+        r = self.generator.step(images, kp_gt, seg_gts if self.use_mesh_repro_loss else None, use_critic=not self.encoder_only, drop=drop,
+                                gt3d=gt3d if self.use_3d_loss else None)
         result = {"kpr_losses": r["kpr_losses"], "pred_keypoints": r["pred_keypoints"], "generated_cams": r["generated_cams"],
                   "thetas": r["thetas"]}
         if self.use_mesh_repro_loss:
             result["mr_losses"] = r["mr_losses"]
+        if "joints3d_losses" in r:
+            result["joints3d_losses"], result["smpl_param_losses"] = r["joints3d_losses"], r["smpl_param_losses"]
         if self.generator.guarded:
             self._guard_results("generator", self.generator, ("regressor", "encoder"), result)
         if not self.encoder_only:
@@ -347,25 +356,54 @@ class Trainer(object):
             result["avg_total_bone_length_gt"] = total_bone_length(joints)
         return result
 
-    def val_step(self, images, seg_gts, kp2d_gts):
-        """data-parallel: this rank's rows (the validation dataset is sharded like the training one), the losses those of all ranks"""
+    def val_step(self, images, seg_gts, kp2d_gts, gt3d=None):
+        """data-parallel: this rank's rows (the validation dataset is sharded like the training one), the losses those of all ranks.
+        gt3d: the batch's ``ops.Gt3D``; with a 3-D weight above 0 the result gains the weighted joints3d_losses and smpl_param_losses
+        of the last stage (lists of one), from one hpe_loss3d launch on a forward of its own."""
         kw = dict(use_mesh_repro_loss=self.use_mesh_repro_loss, kpr_loss_weight=self.kpr_loss_weight, mr_loss_weight=self.mr_loss_weight)
         if self.sharded is not None:
-            return self.sharded.val_step(images, seg_gts, kp2d_gts, presharded=True, **kw)
-        return self.predictor.val_step(images, seg_gts, kp2d_gts, **kw)
+            r = self.sharded.val_step(images, seg_gts, kp2d_gts, presharded=True, **kw)
+        else:
+            r = self.predictor.val_step(images, seg_gts, kp2d_gts, **kw)
+        if gt3d is not None and self.use_3d_loss:
+            r["joints3d_losses"], r["smpl_param_losses"] = self._val_losses_3d(images, gt3d)
+        return r
+
+    def _val_losses_3d(self, images, gt3d):
+        """the weighted 3-D terms of the last stage's prediction for ``images`` against gt3d -> ([joints3d_loss], [smpl_param_loss]), each
+        empty where its weight is 0; data-parallel: the terms of all ranks, numerators and counts summed in one collective before the
+        division"""
+        import torch
+
+        from .engine import loss3d_parts
+
+        with torch.no_grad():
+            o = self.engine.forward(images, all_stages=False, want=("joints", "theta", "Rs"))[0]
+        parts = loss3d_parts(o["joints"], o["theta"][:, 75:], o["Rs"], gt3d)[0].clone()
+        if self.reducer is not None:
+            parts = self.reducer.sum_block(parts)
+        den = torch.clamp(parts[3:5], min=1.0)  # a count of 0 has a numerator of 0
+        lj, ls = 0.5 * parts[0] / den[0], 0.5 * (parts[1] + parts[2]) / den[1]
+        return ([self.joints3d_loss_weight * lj] if self.joints3d_loss_weight > 0.0 else [],
+                [self.smpl_loss_weight * ls] if self.smpl_loss_weight > 0.0 else [])
 
     # ------------------------------------------------------------------ data
-    def _load_images(self, records, augment=True):
+    def _load_images(self, records, augment=True, with_3d=False):
+        """-> (images, seg_gts, kp_gt); with_3d (the steps of ``train``, and only with a 3-D weight above 0): a fourth element, the
+        batch's ``ops.Gt3D`` from ``load_training_batch_3d`` (None for a ready triple, which carries none)"""
         from .augment import draw_augmentation
-        from .records import load_training_batch
+        from .records import load_training_batch, load_training_batch_3d
 
-        if isinstance(records, (tuple, list)) and len(records) == 3 and hasattr(records[0], "is_cuda"):
-            return records  # an (images, seg_gts, kp_gt) triple, ready
+        with_3d = with_3d and self.use_3d_loss
+        if isinstance(records, (tuple, list)) and len(records) in (3, 4) and hasattr(records[0], "is_cuda"):
+            ready = tuple(records)  # an (images, seg_gts, kp_gt[, gt3d]) tuple, ready
+            return ready[:3] + ((ready[3] if len(ready) == 4 else None,) if with_3d else ())
+        load = (lambda recs, **kw: load_training_batch_3d(recs, self.engine, **kw)) if with_3d else load_training_batch
         if augment:
-            return load_training_batch(records, generator=self._aug)
+            return load(records, generator=self._aug)
         draws = draw_augmentation(len(records), trans_max=0, scale_range=(1.0, 1.0))  # validation: centre crop, no jitter, no flip
         draws["flip"][:] = False
-        return load_training_batch(records, draws=draws)
+        return load(records, draws=draws)
 
     def _load_mocap(self, rows):
         import torch
@@ -405,6 +443,9 @@ class Trainer(object):
             cols.append(("kpr", "{:04.2f}", [r["kpr_losses"][-1] for r in train_results]))
         if self.use_mesh_repro_loss:
             cols.append(("mr", "{:05.2f}", [r["mr_losses"][-1] for r in train_results]))
+        for name, key in (("j3d", "joints3d_losses"), ("smpl", "smpl_param_losses")):  # only with the 3-D terms on
+            if any(r.get(key) for r in train_results):
+                cols.append((name, "{:06.4f}", [r[key][-1] for r in train_results if r.get(key)]))
         if not self.encoder_only:
             cols.append(("gc", "{:05.2f}", [r["generator_critic_losses"][-1] for r in train_results]))
             cols.append(("cn", "{:05.2f}", [r["critic_network_loss"] for r in train_results]))
@@ -470,6 +511,7 @@ class Trainer(object):
             w.scalar("generator/kpr_loss", result["kpr_losses"][-1], step)
         if self.use_mesh_repro_loss:
             w.scalar("generator/mr_loss", result["mr_losses"][-1], step)
+        self._summarize_3d(w, step, result)
         if self.do_bone_evaluation:
             w.scalar("bones/avg_total_bone_lenth_pred", result["avg_total_bone_length_pred"], step)  # the reference's spelling
             w.scalar("bones/avg_total_bone_lenth_gt", result["avg_total_bone_length_gt"], step)
@@ -489,6 +531,13 @@ class Trainer(object):
         if image_step:
             w.flush()
 
+    @staticmethod
+    def _summarize_3d(w, step, result):
+        """the 3-D supervision terms (not the reference's tags), where the step computed them"""
+        for tag, key in (("generator/joints3d_loss", "joints3d_losses"), ("generator/smpl_param_loss", "smpl_param_losses")):
+            if result.get(key):
+                w.scalar(tag, result[key][-1], step)
+
     def _summarize_val_step(self, step, result, batch):
         """the validation writer's block (src/trainer.py:798-812)"""
         w = self.val_writer
@@ -496,6 +545,7 @@ class Trainer(object):
             w.scalar("generator/kpr_loss", result["kpr_losses"][-1], step)
         if self.use_mesh_repro_loss:
             w.scalar("generator/mr_loss", result["mr_losses"][-1], step)
+        self._summarize_3d(w, step, result)
         if self.score_validation:
             for tag in SCORE_TAGS:
                 w.scalar("metrics/" + tag, result["scores"][tag], step)
@@ -524,13 +574,15 @@ class Trainer(object):
         last = {}  # the loaded batches of the step in flight: what an image step draws over
 
         def step(gen_batch, critic_batch):
-            last["train"] = images, segs, kp = self._load_images(gen_batch)
+            images, segs, kp, *gt3d = self._load_images(gen_batch, with_3d=True)
+            last["train"] = images, segs, kp
             real = self._load_mocap(critic_batch) if not self.encoder_only or self.do_bone_evaluation else (None, None, None)
-            return self.train_step(images, segs, kp, *real)
+            return self.train_step(images, segs, kp, *real, gt3d=gt3d[0] if gt3d else None)
 
         def val(val_batch):
-            last["val"] = self._load_images(val_batch, augment=False)
-            r = self.val_step(*last["val"])
+            images, segs, kp, *gt3d = self._load_images(val_batch, augment=False, with_3d=True)
+            last["val"] = images, segs, kp
+            r = self.val_step(images, segs, kp, gt3d=gt3d[0] if gt3d else None)
             if self.score_validation:  # on every rank: the sums cross the ranks
                 r["scores"] = self.score_val_result(r, last["val"][1], last["val"][2])
             return r

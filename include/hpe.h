@@ -660,6 +660,12 @@ int hpe_pose3d_scores(const float* const* joints_dev, const float* joints_gt_dev
  * trace(R K), *trace_RK that maximum.  A K that holds a NaN or an infinity gives NaN.  No device needed. */
 int hpe_debug_procrustes3(const double K[9], double R[9], double* trace_RK);
 
+/* The 3-D supervision terms of the generator step (DESIGN.md "3-D supervision"): the joint and SMPL-parameter losses on 3-D ground truth
+ * and their gradient, two stateless calls in the style of the one above.  They are an extension of this interface with a header of their
+ * own, hpe_loss3d.h, which this header includes: a consumer of hpe.h sees them, and the core list of entry points above stays the list
+ * that the binding's core table pins. */
+#include "hpe_loss3d.h"
+
 /* -- the steps right before / after the path -------------------------- */
 /* preprocess_image (preview.py:18-35) = resize_img + scale_and_crop (src/util/image.py:7-39) + [-1,1] normalisation,
  * fused: img_dev uint8 [H,W,C] (C = 3 or 4, RGB first) -> out224_dev float [224,224,3].
